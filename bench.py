@@ -13,6 +13,13 @@ stops the run without a number.
 One rank per GPU; every rank owns 64 images (weak scaling: the path is per-image independent, the only exchange
 is one all-gather of the packed [64,100,7] detections + [64] num_valid per step).  Rank 0 prints ONE JSON line.
 A step = one pass of the hot path over one batch already resident in HBM.
+
+A plain run only sets up, warms up, times --steps steps and prints the line (plus --dump-outputs).  --full adds everything
+else the line can carry: the parity gates against the oracle, the rank-order check of the all-gather, the in-kernel clock,
+the f32x3 / f32x2 alternatives, the CPU baseline, and the eager conv-stack timing of a --graph run.
+
+--dump-outputs DIR writes what the last timed step returned (the unpacked detections and num_valid, plus the decoded
+boxes / classes / scores they were selected from) as DIR/<name>.npy in float32, at most 64 MB in all.
 """
 import argparse
 import json
@@ -184,6 +191,41 @@ def cpu_baseline(program, weights, anchors, images_host, budget_s=20.0):
             "naive_c_port_sample": f"1 image end to end through oracle/y3_oracle.c (scalar loops, OpenMP, {cores} threads)"}
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def outputs_of_step(gathered, decoded):
+    """The arrays a caller of the timed step receives, on the host: the (gathered) packed detections unpacked into boxes /
+    scores / classes / indices plus num_valid, and the decoded boxes / classes / scores NMS selected them from."""
+    import numpy as np
+    packed, nv = (t.cpu().numpy() for t in gathered)
+    words = np.ascontiguousarray(packed[..., :5]).view(np.float32)
+    bboxes, cls, scores = (t.cpu().numpy() for t in decoded)
+    return {"detection_boxes": words[..., :4], "detection_scores": words[..., 4], "detection_classes": packed[..., 5],
+            "detection_indices": packed[..., 6], "num_valid": nv,
+            "decoded_boxes": bboxes, "decoded_classes": cls, "decoded_scores": scores}
+
+
+def write_outputs(out_dir, arrays, budget=DUMP_BUDGET_BYTES):
+    """DIR/<name>.npy in float32 (the integer arrays hold classes / indices / counts below 2^24: exact).  Over the budget,
+    every array keeps the same fraction of its rows (first axis = image), drawn by a fixed seed: two runs with the same
+    arguments write the same sample."""
+    import numpy as np
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    room = budget - 256 * len(arrays)      # each .npy file's header
+    if total > room:
+        frac = room / total
+        for k, a in arrays.items():
+            keep = max(1, int(len(a) * frac))
+            rows = np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))
+            arrays[k] = np.ascontiguousarray(a[rows])
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return arrays
+
+
 def launch_ranks(n, rehearse):
     """`python bench.py --gpus N` without a launcher: N ranks through torch.distributed.run as a child process, one per GPU.
     Fails (non-zero, no JSON line) when the box has fewer than N GPUs, unless the gloo rehearsal mode shares them."""
@@ -228,26 +270,33 @@ def main():
                     help="fixed TOTAL number of images split over the ranks (parallel.shard_range): the strong-scaling run "
                          "SURVEY.md 8(d) names for config 4 (e.g. 512 over 1/2/4/8 GPUs); 0 = --batch images per GPU (weak)")
     ap.add_argument("--image-size", type=int, default=416)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the gates and the extra measurements (parity, rank order, sclk, alt modes, CPU baseline, "
+                         "eager conv timing of --graph); a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--parity-images", type=int, default=2,
-                    help="images of the batch run through the oracle before anything is reported (0: skip the gate)")
+                    help="(--full) images of the batch run through the oracle before anything is reported (0: skip the gate)")
     ap.add_argument("--lanes", type=int, default=0,
                     help="concurrent sub-batches per forward (y3_net_set_lanes); 0 = what the tuning table of the mode says")
     ap.add_argument("--dtype", choices=["f32", "f32x3", "f32x2", "bf16"], default="f32",
                     help="conv arithmetic: f32 (headline, fp32 MFMA), f32x3 / f32x2 (fp32-accurate plane-split modes on the "
                          "bf16 / fp16 matrix cores) or bf16 (BASELINE config 5: bf16 MFMA, fp32 accumulate)")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra f32x3 / f32x2 measurements appended to the f32 line")
+    ap.add_argument("--no-alt", action="store_true", help="(--full) skip the extra f32x3 / f32x2 measurements appended to the f32 line")
     ap.add_argument("--graph", action="store_true", help="capture the per-batch pipeline in a HIP graph and replay it")
     ap.add_argument("--collective", choices=["y3", "torch"], default="y3",
                     help="all-gather of the packed detections: y3 = y3_allgather_results (RCCL behind the C ABI, one group on "
                          "the compute stream, graph-capturable); torch = torch.distributed.all_gather_into_tensor (RCCL)")
     ap.add_argument("--per-layer", action="store_true", help="also print the per-conv timing table to stderr")
     ap.add_argument("--no-sclk", action="store_true",
-                    help="skip the in-kernel clock measurement (~1 s of extra forwards after the timed region): profiler runs "
+                    help="(--full) skip the in-kernel clock measurement (~1 s of extra forwards after the timed region): profiler runs "
                          "(tools/profile.sh) use it so that every conv launch of the run belongs to a counted step")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # --gpus N means N ranks, or no number.  Without a launcher (no WORLD_SIZE in the environment) and N > 1, this process
     # becomes the launcher: it starts `python -m torch.distributed.run --nproc-per-node N bench.py <same args>` as a CHILD
@@ -357,7 +406,7 @@ def main():
         gathered[1].copy_(hn)
         return gathered
 
-    if use_dist:
+    if use_dist and args.full:
         # fail loud and early: one untimed gather of rank-stamped rows through the very route the timed loop uses; every
         # rank checks that block r of the result carries r (a communicator that mixes ranks up, or a route that silently
         # returns the local rows, stops the run here instead of producing a number)
@@ -397,11 +446,11 @@ def main():
 
     for _ in range(max(1, args.warmup)):
         out = step()
-    # parity gate: nothing is timed or reported unless the path's results on this very batch
+    # parity gate (--full): nothing is timed or reported unless the path's results on this very batch
     # match the oracle; fp32-accurate modes only (bf16 is measured against its own bar in tests/)
     parity = None
     fused_equal = None
-    if rank == 0 and args.parity_images > 0:
+    if rank == 0 and args.full and args.parity_images > 0:
         # the route the loop times (y3_net_forward_decode: the head convs decode their own tiles) against the composed route
         # (forward into grids + y3_yolo_decode_scores) on this very plan and batch: bit-identical by contract, checked here at the
         # bench's geometry for both dtypes (the bf16 gate below compares head logits, which the timed route never writes)
@@ -412,17 +461,18 @@ def main():
         if not fused_equal:
             raise SystemExit("PARITY GATE FAILED: y3_net_forward_decode differs from y3_net_forward + y3_yolo_decode_scores on the bench's plan -- no number reported")
         del fb, fc, fs, cb, cc, cs
-    if rank == 0 and args.parity_images > 0 and args.dtype != "bf16":
+    if rank == 0 and args.full and args.parity_images > 0 and args.dtype != "bf16":
         torch.cuda.synchronize()
         parity = parity_gate(program, weights, anchors, images_host, last["tuple"], min(args.parity_images, B), M, 0.5, 0.1)
-    elif rank == 0 and args.parity_images > 0:
+    elif rank == 0 and args.full and args.parity_images > 0:
         net.forward(images, out=grids)       # the bf16 gate compares head logits: one forward that writes the grids
         torch.cuda.synchronize()
         parity = parity_gate_bf16(program, weights, images_host, grids, min(args.parity_images, B, 1))   # one image: three oracle passes
-    if use_dist:
-        dist.barrier()
-    for _ in range(2):      # the gate left the GPU idle for seconds: bring clocks and caches back before the timed region
-        out = step()
+    if args.full:
+        if use_dist:
+            dist.barrier()
+        for _ in range(2):      # the gate left the GPU idle for seconds: bring clocks and caches back before the timed region
+            out = step()
     graph = None
     if args.graph and (world == 1 or comm is not None):
         # one replay = one step; the conv-stack events are recorded inside the captured stream once
@@ -444,10 +494,14 @@ def main():
             out = step(i)
     fence()
     dt = time.perf_counter() - t0
+    # what the last timed step returned, copied out before anything below (alt modes, sclk forwards) runs the net again
+    dumped = outputs_of_step(out, last["tuple"][:3]) if rank == 0 and args.dump_outputs else None
     # shader clock under this load, measured in-kernel after the timed region (sysfs / rocm-smi report the DPM level, not
     # the clock the chip holds at its power cap): ~1 s of forwards back to back, the last one's stem kernel is stamped
     sclk_mhz, sclk_src = None, None
-    if rank == 0 and args.no_sclk:
+    if rank == 0 and not args.full:
+        sclk_src = "not measured (plain run; --full measures it)"
+    elif rank == 0 and args.no_sclk:
         sclk_src = "not measured (--no-sclk)"
     elif rank == 0:
         try:
@@ -475,16 +529,18 @@ def main():
         dt = float(t.item())
     nv_mean = float(out[1].float().mean().item())
 
-    if graph is not None:   # events cannot be read out of a replayed graph: time the conv stack eagerly afterwards
+    if graph is not None and args.full:   # events cannot be read out of a replayed graph: time the conv stack eagerly afterwards
         for i in range(args.steps):
             ev[i][0].record()
             net.forward_decode(images, anchors)
             ev[i][1].record()
         torch.cuda.synchronize()
-    conv_ms = sorted(a.elapsed_time(b) for a, b in ev)
-    conv_ms_mean = sum(conv_ms) / len(conv_ms)
     flops_step = net.flops_per_image() * B
-    achieved = flops_step / (conv_ms_mean * 1e-3) / 1e12
+    conv_ms, conv_ms_mean, achieved = None, None, None
+    if graph is None or args.full:
+        conv_ms = sorted(a.elapsed_time(b) for a, b in ev)
+        conv_ms_mean = sum(conv_ms) / len(conv_ms)
+        achieved = flops_step / (conv_ms_mean * 1e-3) / 1e12
     peak = F32_MFMA_PEAK_TFLOPS if args.dtype == "f32" else BF16_MFMA_PEAK_TFLOPS
     # partial products issued per fp32 product: six bf16 (three planes) or three fp16 (two planes)
     mfma_flops_factor = {"f32x3": 6.0, "f32x2": 3.0}.get(args.dtype, 1.0)
@@ -511,7 +567,7 @@ def main():
     # Extra information on the default (f32) line: the same workload in the fp32-accurate three-plane mode (bf16 matrix
     # cores, same parity tests as f32).  Not the headline value.
     alts = {}
-    if args.dtype == "f32" and not args.no_alt and graph is None:
+    if args.full and args.dtype == "f32" and not args.no_alt and graph is None:
         for tag, dt_id, factor, what in (
                 ("f32x3", y3lib.Y3_DTYPE_F32X3, 6.0, "3 bf16 planes per value, 6 bf16 MFMAs per fp32 product"),
                 ("f32x2", y3lib.Y3_DTYPE_F32X2, 3.0, "2 fp16 planes per value (2^-22 representation), 3 fp16 MFMAs per fp32 product")):
@@ -567,7 +623,7 @@ def main():
                        # the gloo rehearsal, which never touches RCCL; "rehearsal" says which of the two it was)
                        "collective": collective, "rccl_ranks": world if (use_dist and not rehearse) else 0,
                        "rehearsal": bool(use_dist and rehearse),
-                       "rank_order_checked": bool(use_dist), "hip_graph": graph is not None,
+                       "rank_order_checked": bool(use_dist and args.full), "hip_graph": graph is not None,
                        "lanes": headline_lanes,   # concurrent sub-batches per forward (tuning table / --lanes)
                        "global_batch": world * B, "image_size": S, "parallelism": f"dp{world}",
                        "mean_num_valid": round(nv_mean, 2)},
@@ -575,23 +631,25 @@ def main():
                 "bound": "mfma", "kernel": ("conv stack (fused stem kernel = conv0..2 in one launch + 69 x conv_f32_mfma + 3 x conv_head_decode_f32 (head 1x1 + decode) launches per step and lane)" if args.dtype == "f32"
                                             else "conv stack (fused stem kernel = conv0..2 in one launch + 72 x conv_bf16_mfma launches per step and lane, the three heads decoding in their epilogue)" if args.dtype == "bf16"
                                             else f"conv stack (74 x conv_f32x3_mfma{'<2 planes>' if args.dtype == 'f32x2' else ''} launches + 1 first-layer conv per step)"),
-                "achieved": round(achieved, 2), "peak": peak, "unit": "TFLOP/s",
-                "frac": round(achieved * mfma_flops_factor / peak, 4), "traffic": traffic, "traffic_round": traffic_round, "traffic_source": traffic_source,
+                # None: a plain --graph run (the conv stack is timed in extra eager forwards under --full only)
+                "achieved": round(achieved, 2) if conv_ms else None, "peak": peak, "unit": "TFLOP/s",
+                "frac": round(achieved * mfma_flops_factor / peak, 4) if conv_ms else None, "traffic": traffic, "traffic_round": traffic_round, "traffic_source": traffic_source,
                 "sclk_mhz": round(sclk_mhz, 1) if sclk_mhz else None, "sclk_source": sclk_src,
                 "frac_of_clock_limited_peak": (round(achieved * mfma_flops_factor / (peak * sclk_mhz / 2400.0), 4)
-                                               if sclk_mhz else None),
+                                               if sclk_mhz and conv_ms else None),
                 "issued_over_algorithmic_flops": mfma_flops_factor,
-                "flops_per_launch": flops_step, "ms_per_launch": round(conv_ms_mean, 3),
-                "ms_median": round(conv_ms[len(conv_ms) // 2], 3),
+                "flops_per_launch": flops_step, "ms_per_launch": round(conv_ms_mean, 3) if conv_ms else None,
+                "ms_median": round(conv_ms[len(conv_ms) // 2], 3) if conv_ms else None,
             },
         }
+        line["full"] = bool(args.full)
         line["parity_checked"] = parity["images"] if parity else 0
         if parity:
             parity["timed_route_equals_composed_route"] = fused_equal
             line["parity"] = parity
         for tag, alt in alts.items():
             line["alt_" + tag] = alt
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(program, weights, anchors, images_host)
         if args.per_layer:
             net.plan(B, S, dt_ids[args.dtype])       # the alt measurements re-planned the net: back to the headline mode
@@ -607,6 +665,8 @@ def main():
                 fl = 2.0 * o.size * o.size * o.cin * o.cout * ho * ho * B + (fused_fl if o.conv_index == carrier else 0.0)
                 print(f"conv{o.conv_index:<3d} {o.size}x{o.size}/{o.stride} {o.cin:>4d}->{o.cout:<4d} @{ho:<3d} "
                       f"{t:8.3f} ms {fl / t / 1e9:8.1f} TF/s" + ("  (fused stem: incl. the layers timed with it)" if o.conv_index == carrier else ""), file=sys.stderr)
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped)
         sys.stdout.flush()
         os.dup2(real_stdout, 1)
         print(json.dumps(line), flush=True)

@@ -25,7 +25,7 @@ def test_bench_two_ranks_rehearsal(extra, scaling, global_batch):
     env = dict(os.environ, Y3_BENCH_REHEARSE_GLOO="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--batch", "4", "--image-size", "96",
-           "--steps", "3", "--warmup", "1", "--no-alt", "--no-cpu-baseline", "--no-sclk"] + extra
+           "--steps", "3", "--warmup", "1", "--full", "--no-alt", "--no-cpu-baseline", "--no-sclk"] + extra
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -70,7 +70,7 @@ def test_gpus_n_must_equal_the_launchers_world_size():
 @pytest.mark.gpu
 def test_bench_launcherless_two_ranks_rehearsal():
     """`python bench.py --gpus 2` with no launcher: bench.py starts the two ranks itself (child process), relays ONE JSON line."""
-    r = _bench(["--gpus", "2", "--batch", "4", "--image-size", "96", "--steps", "3", "--warmup", "1", "--no-alt",
+    r = _bench(["--gpus", "2", "--batch", "4", "--image-size", "96", "--steps", "3", "--warmup", "1", "--full", "--no-alt",
                 "--no-cpu-baseline", "--no-sclk"], {"Y3_BENCH_REHEARSE_GLOO": "1"})
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]

@@ -15,5 +15,5 @@ run() { # name, timeout, cmd...
 : > gpurun_out/round.log
 run smoke 300 python __graft_entry__.py smoke
 run pytest 900 python -m pytest tests -m gpu -q -x --timeout 600 ${PYTEST_ARGS:-}
-run bench 600 python bench.py --steps ${STEPS:-5} --warmup 2 --per-layer ${BENCH_ARGS:-}
+run bench 600 python bench.py --full --steps ${STEPS:-5} --warmup 2 --per-layer ${BENCH_ARGS:-}
 exit 0

@@ -15,5 +15,5 @@ run() { # name, timeout, cmd...
 : > gpurun_out/round.log
 run pytest 900 python -m pytest tests -m gpu -q --timeout 600 ${PYTEST_ARGS:-}
 run sweep_sk 600 python tools/tune_tiles.py --batch 64 --image-size 416 --reps 3 --tiles 10,11,9,17,26,27,31,32,33,34,35,36,37,38,39,40
-run bench 600 python bench.py --steps ${STEPS:-10} --warmup 3 --per-layer --no-alt ${BENCH_ARGS:-}
+run bench 600 python bench.py --full --steps ${STEPS:-10} --warmup 3 --per-layer --no-alt ${BENCH_ARGS:-}
 exit 0

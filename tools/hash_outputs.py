@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""SHA-256 of what the conv program produces (three head grids + the fused decode outputs) for a seeded batch: two builds of the library
-(Y3_LIB_PATH) that print the same digests are bit-identical on that plan.   python tools/hash_outputs.py --dtype bf16 --batch 128"""
+"""SHA-256 of what the conv program produces (three head grids, the fused decode outputs, the packed detections and num_valid of
+net.detect) for a seeded batch: two builds of the library (Y3_LIB_PATH) that print the same digests are bit-identical on that plan.
+   python tools/hash_outputs.py --dtype bf16 --batch 128          (--dtype f32 | bf16 | f32x3 | f32x2; --lanes N overrides the table's)"""
 import argparse
 import hashlib
 import os
@@ -23,14 +24,18 @@ def main():
     ap.add_argument("--dtype", default="bf16")
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--image-size", type=int, default=416)
+    ap.add_argument("--lanes", type=int, default=0, help="concurrent sub-batches (0: what plan() takes from the tuning table)")
     a = ap.parse_args()
     p = load_program(os.path.join(ROOT, "config/models/yolov3/model.yaml"), 80)
     net = runtime.Net(p)
     net.load_weights(synthetic_weights(p, seed=4321))
-    net.plan(a.batch, a.image_size, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16}[a.dtype])
+    net.plan(a.batch, a.image_size, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f32x3": _lib.Y3_DTYPE_F32X3,
+                                     "f32x2": _lib.Y3_DTYPE_F32X2}[a.dtype])
+    if a.lanes:   # after plan(): it sets the lane count from the tuning table
+        net.set_lanes(a.lanes)
     anchors = get_anchors(os.path.join(ROOT, "datasets/coco2012/anchors.txt")).astype(np.float32)
     x = torch.from_numpy(np.random.default_rng(77).random((a.batch, a.image_size, a.image_size, 3), dtype=np.float32)).cuda()
-    outs = list(net.forward(x)) + list(net.forward_decode(x, anchors))
+    outs = list(net.forward(x)) + list(net.forward_decode(x, anchors)) + list(net.detect(x, anchors, 100, 0.5, 0.1))
     torch.cuda.synchronize()
     for i, t in enumerate(outs):
         print(f"DIGEST {i} {tuple(t.shape)} {hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()}")

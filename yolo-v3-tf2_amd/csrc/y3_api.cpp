@@ -23,19 +23,10 @@ namespace {
 // (include/y3.h: no entry point throws or aborts -- not even while it reports that the host ran out of memory).
 thread_local char g_err[512] = "";
 
-int fail(int code, const char *fmt, ...) noexcept
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
 }  // namespace
 
 namespace y3 {
-// for the other translation units of the library (comm.cpp)
+// record the message as this thread's last error and return `code` (here and in the other translation units: comm.cpp)
 int fail_msg(int code, const char *fmt, ...) noexcept
 {
     va_list ap;
@@ -73,6 +64,8 @@ bool test_fail_alloc() noexcept
 #define Y3_CATCH(who) catch (...) { return y3::on_exception(who); }
 
 namespace {
+
+constexpr auto fail = y3::fail_msg;
 
 #define HIP_TRY(expr)                                                                             \
     do {                                                                                          \
@@ -157,18 +150,12 @@ struct y3_net {
     // y3_net_plan for max_batch images and Y3_MAX_OUTPUT_BOXES rows, so y3_net_detect itself only enqueues work
     void *det_buf = nullptr;
     size_t det_bytes = 0;
-    // y3_net_forward_decode: while set, the three head convs decode their own tiles into these buffers (per scale: first box
-    // index, grid size, anchors) instead of writing grids.  Null outside that call.
-    const y3::DecodeHead *fuse = nullptr;   // [3], in output order
     int stem_mode = 1;             // y3_net_set_stem_fusion: 1 = conv0 + conv1 (+ the 1x1 after them) as one kernel when the graph allows it; 2 = conv0 + conv1 only
     bool stem_mode_set = false;    // y3_net_set_stem_fusion was called (the Y3_STEM_MODE tool override then stays out)
     bool stem_fused = false;       // (at plan time) the first two convs run as the fused stem kernel
     bool stem_conv2 = false;       // ... and the 1x1 conv that follows them (64 -> 32) runs inside it as well (fp32 and bf16 plans)
-    unsigned long long *clk_stamps = nullptr;   // y3_net_measure_sclk: device buffer one conv launch stamps into (else null)
-    int clk_conv = -1;                          // ... and which conv (-2: every conv, 8 words each at clk_stamps + 8 conv)
     int xcd_mode = 1;              // y3_net_set_xcd_mode: 0 contiguous tile runs per XCD, 1 XCD-blocked order chosen per conv
     int k_chunk = -1;              // y3_net_set_k_chunk: fp32 3x3 convs walk K chunk-major, this many input channels per chunk; 0 tap-major; -1 per-conv default
-    int cur_batch = 1;             // batch of the forward being enqueued
     hipEvent_t fork_ev = nullptr;
     hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t join_ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -241,44 +228,106 @@ float f16_to_f32(unsigned short h)
     return (h & 0x8000) ? -v : v;
 }
 
+// ---- weight packing (y3_net_set_conv_weights): HWIO w is [K][Cout], k = tap*Cin + c
+
+// [CoutPad][K], rows past Cout zero; scale (or null): folded into each output channel's row
+std::vector<float> pack_rows(const float *w, int K, int cout, int cout_pad, const float *scale)
+{
+    std::vector<float> pk((size_t)cout_pad * K, 0.0f);
+    for (int k = 0; k < K; ++k)
+        for (int n = 0; n < cout; ++n) pk[(size_t)n * K + k] = scale ? w[(size_t)k * cout + n] * scale[n] : w[(size_t)k * cout + n];
+    return pk;
+}
+
+// first layer, fused stem kernel: conv0 on the matrix cores wants K = 27 padded to 28 rows of [Cout]; scale (or null) folded in
+std::vector<float> pack_stem28(const float *w, int K, int cout, const float *scale)
+{
+    std::vector<float> w28((size_t)28 * cout, 0.0f);
+    for (int k = 0; k < K; ++k)
+        for (int n = 0; n < cout; ++n) w28[(size_t)k * cout + n] = scale ? w[(size_t)k * cout + n] * scale[n] : w[(size_t)k * cout + n];
+    return w28;
+}
+
+// three bf16 planes: x = hi + mid + lo exactly
+void split_bf16x3(float x, unsigned short v[3])
+{
+    v[0] = f32_to_bf16_rne(x);
+    const float r1 = x - bf16_to_f32(v[0]);
+    v[1] = f32_to_bf16_rne(r1);
+    v[2] = f32_to_bf16_rne(r1 - bf16_to_f32(v[1]));
+}
+
+// two fp16 planes: w = h + l' * 2^-11 (up to 2^-22 |w|) while |w| < 65504
+void split_f16x2(float x, unsigned short v[2])
+{
+    v[0] = f32_to_f16_rne(x);
+    v[1] = f32_to_f16_rne((x - f16_to_f32(v[0])) * 2048.0f);
+}
+
+// [rows][P][K] planes of [CoutPad][K] weights (rows past Cout zero), split(x, v) giving the P plane values of x
+template <int P>
+std::vector<unsigned short> pack_planes(const std::vector<float> &pk, int K, int cout, int rows, void (*split)(float, unsigned short *))
+{
+    std::vector<unsigned short> px((size_t)rows * P * K, 0);
+    unsigned short v[P];
+    for (int n = 0; n < cout; ++n)
+        for (int k = 0; k < K; ++k) {
+            split(pk[(size_t)n * K + k], v);
+            for (int p = 0; p < P; ++p) px[((size_t)n * P + p) * K + k] = v[p];
+        }
+    return px;
+}
+
+// hipMalloc the device buffer on first use, then copy the host vector into it
+template <class P, class T>
+hipError_t upload(P *&dev, const std::vector<T> &host)
+{
+    const size_t bytes = host.size() * sizeof(T);
+    if (!dev)
+        if (hipError_t e = hipMalloc(reinterpret_cast<void **>(&dev), bytes); e != hipSuccess) return e;
+    return hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
+}
+
+// The first candidate tile that fits the conv and gives at least `want` workgroups for M rows over `cout_pad` channels; the last
+// candidate when none does.
+template <size_t N, class Fits>
+int first_reaching(const int (&cand)[N], y3::TileInfo (*info)(int), long long M, int cout_pad, long long want, Fits fits)
+{
+    for (int t : cand) {
+        const y3::TileInfo s = info(t);
+        if (fits(s) && ((M + s.bm - 1) / s.bm) * (cout_pad / s.bn) >= want) return t;
+    }
+    return cand[N - 1];
+}
+
 int choose_tile_x2(const ConvSlot &c, long long M)
 {
     // widest tile that still gives every CU at least two workgroups
-    const int cand128[] = {4, 8, 0, 3, 2}, cand64[] = {1, 2};
-    const int *cand = c.cout_pad64 % 128 == 0 ? cand128 : cand64;
-    const int n = c.cout_pad64 % 128 == 0 ? 5 : 2;
-    int best = cand[n - 1];
-    for (int k = 0; k < n; ++k) {
-        y3::TileInfo s = y3::conv_x3_tile_info(cand[k]);
-        if (c.cout_pad64 % s.bn || c.d.cin % s.stages || (c.d.src1 >= 0 && c.d.c0 % s.stages)) continue;
-        long long blocks = ((M + s.bm - 1) / s.bm) * (c.cout_pad64 / s.bn);
-        if (blocks >= 512) {
-            best = cand[k];
-            break;
-        }
-    }
-    return best;
+    static constexpr int wide[] = {4, 8, 0, 3, 2}, narrow[] = {1, 2};
+    auto fits = [&](const y3::TileInfo &s) { return !(c.cout_pad64 % s.bn || c.d.cin % s.stages || (c.d.src1 >= 0 && c.d.c0 % s.stages)); };
+    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
+    return first_reaching(narrow, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
 }
 
 int choose_tile_x3(const ConvSlot &c, long long M)
 {
-    std::vector<int> cand;
-    if (c.cout_pad64 % 128 == 0)
-        cand = {0, 3, 2};
-    else
-        cand = {1, 2};
-    int best = cand.back();
-    for (int t : cand) {
-        y3::TileInfo s = y3::conv_x3_tile_info(t);
-        if (c.cout_pad64 % s.bn) continue;
-        long long blocks = ((M + s.bm - 1) / s.bm) * (c.cout_pad64 / s.bn);
-        if (blocks >= 512) {
-            best = t;
-            break;
-        }
-    }
-    return best;
+    static constexpr int wide[] = {0, 3, 2}, narrow[] = {1, 2};
+    auto fits = [&](const y3::TileInfo &s) { return c.cout_pad64 % s.bn == 0; };
+    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
+    return first_reaching(narrow, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
 }
+
+// What the two plane-split modes (three bf16 planes, two fp16 planes per value) differ in at launch time
+struct PlaneSplit {
+    void *ConvSlot::*w;     // packed weights
+    int planes;
+    int ConvSlot::*tile;    // forced tile (y3_net_set_tile_x3 / _x2), -1: the chooser's
+    int (*choose)(const ConvSlot &, long long);
+    hipError_t (*launch)(const y3::ConvArgs &, int, bool, hipStream_t);
+    hipError_t (*launch_first)(const y3::ConvArgs &, const float *, hipStream_t);   // the Cin = 3 first layer
+};
+constexpr PlaneSplit X3_SPLIT = {&ConvSlot::wx3_dev, 3, &ConvSlot::tile_x3, choose_tile_x3, y3::launch_conv_f32x3, y3::launch_conv_first_f32x3};
+constexpr PlaneSplit X2_SPLIT = {&ConvSlot::wx2_dev, 2, &ConvSlot::tile_x2, choose_tile_x2, y3::launch_conv_f32x2, y3::launch_conv_first_f32x2};
 
 // M = rows of this call (per lane); M_plan = rows of the planned batch.  The MFMA SHAPE (16x16x32 vs 32x32x16: two K groupings,
 // results differ in the last bits) is decided from plan-time quantities only, so that an image's result does not depend on the
@@ -289,6 +338,7 @@ int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16
         y3::TileInfo s = y3::conv_bf16_tile_info(t);
         return ((M + s.bm - 1) / s.bm) * (c.cout_pad / s.bn);
     };
+    auto fits = [&](const y3::TileInfo &s) { return c.cout_pad % s.bn == 0; };
     // large 3x3 convs: the 16x16x32 form once the PLANNED batch fills the chip with 256x256 tiles of 16 waves (tile 24 wins every
     // such signature of the 64- and 128-image tables, tuning/bf16_b*_s416.json); smaller calls of the same plan take the 128x128 /
     // 64x128 tiles of the same MFMA shape (27, 29)
@@ -299,24 +349,13 @@ int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16
     // early 3x3 / stride-1 convs with Cin = 32 / 64 (K = 288 / 576): weights resident in LDS, input patch by LDS-DMA (tile id 32,
     // conv_res_bf16.hip) -- from the conv's shape alone, so batch- and lane-independent
     if (bf16_out && c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && (c.d.cin == 32 || c.d.cin == 64) && c.d.cout % 64 == 0) return 32;
-    std::vector<int> cand;
-    if (c.d.cin % 64)
-        cand = {5, 6};                       // BK = 32 (Cin = 32 layers, Cout = 64)
-    else if (c.cout_pad % 128 == 0)
-        cand = {8, 12, 11};                  // LDS-DMA variants: 128x128, 64x128, 64x64
-    else if (c.cout_pad % 64 == 0)
-        cand = {10, 11};
-    else
-        cand = {4};
-    int best = cand.back();
-    for (int t : cand) {
-        if (c.cout_pad % y3::conv_bf16_tile_info(t).bn) continue;
-        if (blocks(t) >= 512) {
-            best = t;
-            break;
-        }
-    }
-    return best;
+    static constexpr int bk32[] = {5, 6},    // BK = 32 (Cin = 32 layers, Cout = 64)
+                         n128[] = {8, 12, 11},   // LDS-DMA variants: 128x128, 64x128, 64x64
+                         n64[] = {10, 11}, n32[] = {4};
+    if (c.d.cin % 64) return first_reaching(bk32, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
+    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
+    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
+    return first_reaching(n32, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
 }
 
 // channels per K chunk of a 3x3 fp32 conv when the caller has not chosen (y3_net_set_k_chunk(-1)); Y3_K_CHUNK overrides (tools)
@@ -362,26 +401,16 @@ int choose_tile(const ConvSlot &c, long long M)
     if (c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && c.d.cin == 32 && c.d.cout % 64 == 0 && c.cout_pad == c.d.cout) return 33;
     // measured on MI355X (tools/tune_tiles.py): many co-resident waves beat big wave tiles for the 64-cycle
     // fp32 MFMA; prefer the largest block tile that still yields >= 2 workgroups per CU
-    std::vector<int> cand;
-    if (c.cout_pad % 128 == 0)
-        cand = {10, 11};
-    else if (c.cout_pad % 64 == 0)
-        cand = {11};
-    else
-        cand = {8};
-    int best = cand.back();
-    for (int t : cand) {
-        y3::TileInfo s = y3::conv_tile_info(t);
-        long long blocks = ((M + s.bm - 1) / s.bm) * (c.cout_pad / s.bn);
-        if (blocks >= 1024) {
-            best = t;
-            break;
-        }
-    }
-    return best;
+    static constexpr int n128[] = {10, 11}, n64[] = {11}, n32[] = {8};
+    auto any = [](const y3::TileInfo &) { return true; };
+    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_tile_info, M, c.cout_pad, 1024, any);
+    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_tile_info, M, c.cout_pad, 1024, any);
+    return first_reaching(n32, y3::conv_tile_info, M, c.cout_pad, 1024, any);
 }
 
 }  // namespace
+
+static bool is_output(const y3_net *net, int t) { return t == net->outputs[0] || t == net->outputs[1] || t == net->outputs[2]; }
 
 // The first two ops are conv0 (3x3/1, 3 -> 32) and conv1 (3x3/2, 32 -> 64, no shortcut, single source) reading it, nobody
 // else reads conv0's output, and the plan is fp32 with every intermediate reusable: the pair runs as csrc/conv_stem.hip.
@@ -395,8 +424,7 @@ static bool stem_applicable(const y3_net *net)
     if (!c0.first_layer || a.size != 3 || a.stride != 1 || a.cout != 32 || a.residual >= 0 || a.src1 >= 0) return false;
     if (b.size != 3 || b.stride != 2 || b.cin != 32 || b.cout != 64 || b.residual >= 0 || b.src1 >= 0 || b.src0 != a.dst) return false;
     if (a.src0 != net->input_tensor) return false;
-    for (int k = 0; k < 3; ++k)
-        if (net->outputs[k] == a.dst || net->outputs[k] == b.dst) return false;
+    if (is_output(net, a.dst) || is_output(net, b.dst)) return false;
     for (size_t i = 2; i < net->ops.size(); ++i) {
         if (net->ops[i].kind == 0) {
             const y3_conv_desc &d = net->convs[net->ops[i].index].d;
@@ -416,21 +444,36 @@ static bool stem_conv2_applicable(const y3_net *net)
     if ((net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16) || net->ops.size() < 3 || net->ops[2].kind != 0) return false;
     const y3_conv_desc &b = net->convs[net->ops[1].index].d, &c = net->convs[net->ops[2].index].d;
     if (c.size != 1 || c.stride != 1 || c.cin != 64 || c.cout != 32 || c.residual >= 0 || c.src1 >= 0 || c.src0 != b.dst) return false;
-    for (int k = 0; k < 3; ++k)
-        if (net->outputs[k] == c.dst) return false;
-    return true;
+    return !is_output(net, c.dst);
 }
 
-// Does this conv's launch write an fp32 net output directly (bf16 / plane-split plans)?  Mirrors the `staged` rule of y3_net_plan: an
-// output that another op reads, or that a shortcut / first-layer conv writes, stays in the arena in the mode's format instead.
-static bool writes_f32_output(const y3_net *net, const ConvSlot &c)
+// Is net output t staged in a non-fp32 plan -- produced in the arena in the mode's own format and converted into the caller's fp32
+// grid at the end of the forward -- because a conv reads it again inside the net, or a conv with no fp32-output form of its launch
+// (shortcut, first layer) writes it?  Needs no plan: y3_net_plan marks `staged` by it, and y3_net_set_tile_bf16 refuses the
+// bf16-only tile 32 on a conv whose output is not staged.
+static bool output_staged(const y3_net *net, int t)
 {
-    const int t = c.d.dst;
-    if (t != net->outputs[0] && t != net->outputs[1] && t != net->outputs[2]) return false;
-    if (c.d.residual >= 0 || c.first_layer) return false;
-    for (const ConvSlot &o : net->convs)
-        if (o.d.src0 == t || o.d.src1 == t || o.d.residual == t) return false;
-    return true;
+    for (const Op &o : net->ops) {
+        if (o.kind != 0) continue;
+        const ConvSlot &c = net->convs[o.index];
+        if (c.d.src0 == t || c.d.src1 == t || c.d.residual == t) return true;
+        if (c.d.dst == t && (c.d.residual >= 0 || c.first_layer)) return true;
+    }
+    return false;
+}
+
+// bytes per element of an arena tensor: fp32, bf16, three bf16 planes, or two fp16 planes (4 bytes as well)
+static size_t arena_elem_bytes(int dtype) { return dtype == Y3_DTYPE_BF16 ? 2 : dtype == Y3_DTYPE_F32X3 ? 6 : 4; }
+
+// staged activation (the plan's format) -> fp32, npix pixels of C channels
+static hipError_t to_f32(int dtype, const void *src, float *dst, size_t npix, int C, hipStream_t s)
+{
+    switch (dtype) {
+        case Y3_DTYPE_F32X2: return y3::launch_x2_to_f32(src, dst, npix, C, s);
+        case Y3_DTYPE_F32X3: return y3::launch_x3_to_f32(src, dst, npix, C, s);
+        case Y3_DTYPE_BF16: return y3::launch_bf16_to_f32(src, dst, npix * C, s);
+        default: return hipMemcpyAsync(dst, src, npix * C * sizeof(float), hipMemcpyDeviceToDevice, s);
+    }
 }
 
 extern "C" {
@@ -529,16 +572,9 @@ void y3_net_destroy(y3_net *net)
             (void)hipEventDestroy(net->join_ev[i]);
         }
     }
-    for (ConvSlot &c : net->convs) {
-        if (c.w_dev) (void)hipFree(c.w_dev);
-        if (c.w0stem_dev) (void)hipFree(c.w0stem_dev);
-        if (c.w0raw_dev) (void)hipFree(c.w0raw_dev);
-        if (c.wbf_dev) (void)hipFree(c.wbf_dev);
-        if (c.wx3_dev) (void)hipFree(c.wx3_dev);
-        if (c.wx2_dev) (void)hipFree(c.wx2_dev);
-        if (c.scale_dev) (void)hipFree(c.scale_dev);
-        if (c.shift_dev) (void)hipFree(c.shift_dev);
-    }
+    for (ConvSlot &c : net->convs)
+        for (void *p : {(void *)c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, c.wbf_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev})
+            if (p) (void)hipFree(p);
     delete net;
 }
 
@@ -563,77 +599,26 @@ try {
             shift[n] = bias[n];
         }
     }
-    std::vector<float> pk;
-    if (c.first_layer) {
-        pk.assign(w, w + (size_t)K * d.cout);  // HWIO as is
-    } else {
-        pk.assign((size_t)CP * K, 0.0f);       // [CoutPad][K], k = tap*Cin + c  (HWIO is [K][Cout])
-        for (int k = 0; k < K; ++k)
-            for (int n = 0; n < d.cout; ++n) pk[(size_t)n * K + k] = w[(size_t)k * d.cout + n];
-    }
-    // fp32 path: the BN scale is folded into the packed weights (one VALU multiply less per output element; VALU
-    // time is matrix-pipe time for the fp32 MFMA).  The bf16 copy keeps the unscaled weights + scale in the epilogue.
-    std::vector<float> pk_scaled;
-    if (!c.first_layer) {
-        pk_scaled = pk;
-        for (int n = 0; n < d.cout; ++n)
-            for (int k = 0; k < K; ++k) pk_scaled[(size_t)n * K + k] *= scale[n];
-    }
     Y3_ENTER_DEVICE(net);
-    if (!c.w_dev) HIP_TRY(hipMalloc(&c.w_dev, pk.size() * sizeof(float)));
-    if (!c.scale_dev) HIP_TRY(hipMalloc(&c.scale_dev, CP64 * sizeof(float)));
-    if (!c.shift_dev) HIP_TRY(hipMalloc(&c.shift_dev, CP64 * sizeof(float)));
-    HIP_TRY(hipMemcpy(c.w_dev, (c.first_layer ? pk : pk_scaled).data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+    // every format is packed whatever the plan's dtype: one net can be re-planned in another mode
     if (c.first_layer) {
-        // fused stem kernel: conv0 on the matrix cores wants K = 27 padded to 28 and the BN scale folded in
-        std::vector<float> w28((size_t)28 * d.cout, 0.0f);
-        for (int k = 0; k < K; ++k)
-            for (int n = 0; n < d.cout; ++n) w28[(size_t)k * d.cout + n] = w[(size_t)k * d.cout + n] * scale[n];
-        if (!c.w0stem_dev) HIP_TRY(hipMalloc(&c.w0stem_dev, w28.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(c.w0stem_dev, w28.data(), w28.size() * sizeof(float), hipMemcpyHostToDevice));
-        for (int k = 0; k < K; ++k)
-            for (int n = 0; n < d.cout; ++n) w28[(size_t)k * d.cout + n] = w[(size_t)k * d.cout + n];
-        if (!c.w0raw_dev) HIP_TRY(hipMalloc(&c.w0raw_dev, w28.size() * sizeof(float)));
-        HIP_TRY(hipMemcpy(c.w0raw_dev, w28.data(), w28.size() * sizeof(float), hipMemcpyHostToDevice));
+        // HWIO as is (the Cin = 3 direct kernels); the fused stem kernel's 28 rows with the BN scale folded in (fp32) and without (bf16)
+        HIP_TRY(upload(c.w_dev, std::vector<float>(w, w + (size_t)K * d.cout)));
+        HIP_TRY(upload(c.w0stem_dev, pack_stem28(w, K, d.cout, scale.data())));
+        HIP_TRY(upload(c.w0raw_dev, pack_stem28(w, K, d.cout, nullptr)));
+    } else {
+        // fp32 path: the BN scale is folded into the packed weights (one VALU multiply less per output element; VALU
+        // time is matrix-pipe time for the fp32 MFMA).  The bf16 copy keeps the unscaled weights + scale in the epilogue.
+        const std::vector<float> pk = pack_rows(w, K, d.cout, CP, nullptr), pk_scaled = pack_rows(w, K, d.cout, CP, scale.data());
+        HIP_TRY(upload(c.w_dev, pk_scaled));
+        HIP_TRY(upload(c.wbf_dev, pack_planes<1>(pk, K, d.cout, CP, [](float x, unsigned short *v) { v[0] = f32_to_bf16_rne(x); })));
+        // a scaled weight outside the fp16 range: y3_net_plan(Y3_DTYPE_F32X2) refuses the net; other modes are unaffected
+        c.x2_ok = std::all_of(pk_scaled.begin(), pk_scaled.end(), [](float x) { return fabsf(x) < 65504.0f; });
+        HIP_TRY(upload(c.wx3_dev, pack_planes<3>(pk, K, d.cout, CP64, split_bf16x3)));         // unscaled, like the bf16 copy
+        HIP_TRY(upload(c.wx2_dev, pack_planes<2>(pk_scaled, K, d.cout, CP64, split_f16x2)));   // BN-scaled, like the fp32 copy
     }
-    if (!c.first_layer) {
-        std::vector<unsigned short> pb(pk.size());
-        for (size_t i = 0; i < pk.size(); ++i) pb[i] = f32_to_bf16_rne(pk[i]);
-        if (!c.wbf_dev) HIP_TRY(hipMalloc(&c.wbf_dev, pb.size() * sizeof(unsigned short)));
-        HIP_TRY(hipMemcpy(c.wbf_dev, pb.data(), pb.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    }
-    HIP_TRY(hipMemcpy(c.scale_dev, scale.data(), CP64 * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(c.shift_dev, shift.data(), CP64 * sizeof(float), hipMemcpyHostToDevice));
-    if (!c.first_layer) {
-        // three-plane split of the (unscaled) weights: x = hi + mid + lo exactly
-        std::vector<unsigned short> px((size_t)CP64 * 3 * K, 0);
-        for (int n = 0; n < d.cout; ++n)
-            for (int k = 0; k < K; ++k) {
-                const float x = pk[(size_t)n * K + k];
-                const unsigned short h = f32_to_bf16_rne(x);
-                const float r1 = x - bf16_to_f32(h);
-                const unsigned short m = f32_to_bf16_rne(r1);
-                const float r2 = r1 - bf16_to_f32(m);
-                px[((size_t)n * 3 + 0) * K + k] = h;
-                px[((size_t)n * 3 + 1) * K + k] = m;
-                px[((size_t)n * 3 + 2) * K + k] = f32_to_bf16_rne(r2);
-            }
-        if (!c.wx3_dev) HIP_TRY(hipMalloc(&c.wx3_dev, px.size() * sizeof(unsigned short)));
-        HIP_TRY(hipMemcpy(c.wx3_dev, px.data(), px.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-        // two fp16 planes of the BN-scaled weights: w = h + l' * 2^-11 (up to 2^-22 |w|); |w| must stay below 65504
-        std::vector<unsigned short> p2((size_t)CP64 * 2 * K, 0);
-        c.x2_ok = true;
-        for (int n = 0; n < d.cout; ++n)
-            for (int k = 0; k < K; ++k) {
-                const float x = pk_scaled[(size_t)n * K + k];
-                if (!(fabsf(x) < 65504.0f)) c.x2_ok = false;   // reported by y3_net_plan(Y3_DTYPE_F32X2); other modes are unaffected
-                const unsigned short h = f32_to_f16_rne(x);
-                p2[((size_t)n * 2 + 0) * K + k] = h;
-                p2[((size_t)n * 2 + 1) * K + k] = f32_to_f16_rne((x - f16_to_f32(h)) * 2048.0f);
-            }
-        if (!c.wx2_dev) HIP_TRY(hipMalloc(&c.wx2_dev, p2.size() * sizeof(unsigned short)));
-        HIP_TRY(hipMemcpy(c.wx2_dev, p2.data(), p2.size() * sizeof(unsigned short), hipMemcpyHostToDevice));
-    }
+    HIP_TRY(upload(c.scale_dev, scale));
+    HIP_TRY(upload(c.shift_dev, shift));
     c.loaded = true;
     return Y3_OK;
 }
@@ -673,7 +658,7 @@ try {
         // tile 32 stores bf16 only: a conv whose destination is a net output that the forward hands over as fp32 straight from the launch
         // (not read again inside the net, no shortcut: y3_net_plan does not stage it) cannot take it -- refused here, by name, instead of a
         // launch error in the forward
-        if (tile == 32 && writes_f32_output(net, c))
+        if (tile == 32 && is_output(net, c.d.dst) && !output_staged(net, c.d.dst))
             return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile 32 (weight-resident) stores bf16 only; conv %d writes an fp32 net output", slot);
     }
     c.tile_bf16 = tile;
@@ -782,6 +767,44 @@ static y3_status ensure_lanes(y3_net *net)
     return Y3_OK;
 }
 
+// Arena blocks for the plan's tensors from their liveness [first, last] over the op list
+static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const std::vector<int> &last)
+{
+    const int nt = (int)net->tensors.size();
+    struct Blk { void *p; size_t bytes; int free_at; };
+    std::vector<Blk> pool;
+    // allocate in order of first definition; the image batch and the head grids are caller-owned
+    std::vector<int> order;
+    for (int t = 0; t < nt; ++t) {
+        const bool external = t == net->input_tensor || (is_output(net, t) && !net->staged[t]);
+        if (first[t] >= 0 && !external) order.push_back(t);
+    }
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
+    for (int t : order) {
+        const int until = (net->keep_all || net->dense[t]) ? (int)net->ops.size() + 1 : last[t];
+        int pick = -1;
+        for (int k = 0; k < (int)pool.size() && !net->dense[t]; ++k)
+            if (pool[k].free_at < first[t] && pool[k].bytes >= net->tbytes[t] &&
+                (pick < 0 || pool[k].bytes < pool[pick].bytes))
+                pick = k;
+        if (pick < 0) {
+            void *p = nullptr;
+            hipError_t e = hipMalloc(&p, net->tbytes[t] + 4096);
+            if (e != hipSuccess) {
+                free_plan(net);
+                return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) failed: %s", net->tbytes[t], hipGetErrorString(e));
+            }
+            net->blocks.push_back(p);
+            pool.push_back({p, net->tbytes[t], until});
+            pick = (int)pool.size() - 1;
+        }
+        pool[pick].free_at = until;
+        net->tdev[t] = pool[pick].p;
+        net->tblock[t] = pool[pick].bytes;
+    }
+    return Y3_OK;
+}
+
 y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype)
 try {
     if (!net || max_batch <= 0 || image_size <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
@@ -823,21 +846,12 @@ try {
         }
     }
     net->staged.assign(nt, 0);
-    if (dtype != Y3_DTYPE_F32) {
-        for (int i = 0; i < (int)net->ops.size(); ++i) {
-            const Op &o = net->ops[i];
-            if (o.kind != 0) continue;
-            const ConvSlot &c = net->convs[o.index];
-            const y3_conv_desc &d = c.d;
-            for (int k = 0; k < 3; ++k) {
-                const int out = net->outputs[k];
-                if (d.src0 == out || d.src1 == out || d.residual == out) net->staged[out] = 1;     // read again inside the net
-                if (d.dst == out && (d.residual >= 0 || c.first_layer)) net->staged[out] = 1;       // no fp32-output form of that launch
-            }
-        }
+    if (dtype != Y3_DTYPE_F32)
         for (int k = 0; k < 3; ++k)
-            if (net->staged[net->outputs[k]]) last[net->outputs[k]] = (int)net->ops.size();        // alive until the final conversion
-    }
+            if (output_staged(net, net->outputs[k])) {
+                net->staged[net->outputs[k]] = 1;
+                last[net->outputs[k]] = (int)net->ops.size();        // alive until the final conversion
+            }
     // chunked leading segment: every op before the (early_convs)-th conv; tensors it writes get blocks of their own,
     // laid out densely by image, because they are rewritten chunk after chunk while earlier chunks' results are still live
     net->early_ops = 0;
@@ -853,42 +867,11 @@ try {
     for (int t = 0; t < nt; ++t) net->dense[t] = (first[t] >= 0 && first[t] < net->early_ops) ? 1 : 0;
     for (int t = 0; t < nt; ++t) {
         const int s = image_size / net->tensors[t].div;
-        net->tbytes[t] = (size_t)max_batch * s * s * net->tensors[t].channels * (dtype == Y3_DTYPE_BF16 ? 2 : dtype == Y3_DTYPE_F32X3 ? 6 : 4);   // two fp16 planes: 4 bytes as well
+        net->tbytes[t] = (size_t)max_batch * s * s * net->tensors[t].channels * arena_elem_bytes(dtype);
         if (net->tbytes[t] >= 0xFFFFFFF0ull && first[t] >= 0)
             return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, net->tbytes[t]);
     }
-    struct Blk { void *p; size_t bytes; int free_at; };
-    std::vector<Blk> pool;
-    // allocate in order of first definition; the image batch and the head grids are caller-owned
-    std::vector<int> order;
-    for (int t = 0; t < nt; ++t) {
-        const bool external = (t == net->input_tensor ||
-                               ((t == net->outputs[0] || t == net->outputs[1] || t == net->outputs[2]) && !net->staged[t]));
-        if (first[t] >= 0 && !external) order.push_back(t);
-    }
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
-    for (int t : order) {
-        const int until = (net->keep_all || net->dense[t]) ? (int)net->ops.size() + 1 : last[t];
-        int pick = -1;
-        for (int k = 0; k < (int)pool.size() && !net->dense[t]; ++k)
-            if (pool[k].free_at < first[t] && pool[k].bytes >= net->tbytes[t] &&
-                (pick < 0 || pool[k].bytes < pool[pick].bytes))
-                pick = k;
-        if (pick < 0) {
-            void *p = nullptr;
-            hipError_t e = hipMalloc(&p, net->tbytes[t] + 4096);
-            if (e != hipSuccess) {
-                free_plan(net);
-                return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) failed: %s", net->tbytes[t], hipGetErrorString(e));
-            }
-            net->blocks.push_back(p);
-            pool.push_back({p, net->tbytes[t], until});
-            pick = (int)pool.size() - 1;
-        }
-        pool[pick].free_at = until;
-        net->tdev[t] = pool[pick].p;
-        net->tblock[t] = pool[pick].bytes;
-    }
+    if (y3_status st = place_tensors(net, first, last); st != Y3_OK) return st;
     if (y3_status st = ensure_lanes(net); st != Y3_OK) return st;
     {   // Y3_STEM_MODE (tools: same-process-tree A/B of the stem forms) overrides the default, not an explicit setter call
         static const int env = [] { const char *e = getenv("Y3_STEM_MODE"); return e ? atoi(e) : -1; }();
@@ -945,264 +928,304 @@ double y3_net_flops_per_image(const y3_net *net)
     return tot;
 }
 
-// Enqueue the whole op list for images [b0, b0+nb) of the batch on stream s (tensor pointers offset by b0 images).
-// op_begin/op_end select a segment of the op list (-1: to the end).
-static y3_status run_slice(y3_net *net, const float *images, float *const grids[3], int b0, int nb, hipStream_t s,
-                           float *ms_out, int n_ms, int lane = 0, int /*lanes*/ = 1, int op_begin = 0, int op_end = -1)
+// One call's forward: everything that belongs to the call rather than the net.  Built on the stack by each entry point that
+// runs the conv program; the net itself is read-only while a forward is enqueued.
+struct Forward {
+    const float *images;
+    float *const *grids;                     // [3] caller's fp32 head grids
+    int batch;
+    hipStream_t stream;
+    int lanes;                               // concurrent sub-batches this call may use (the net's y3_net_set_lanes, or 1)
+    const y3::DecodeHead *heads = nullptr;   // [3] in output order: the head convs decode their own tiles into these buffers
+                                             // (per scale: first box index, grid size, anchors) instead of writing grids
+    unsigned long long *clk = nullptr;       // y3_net_measure_sclk*: device buffer the stamped launch(es) write
+    int clk_conv = -1;                       // ... which conv (-2: every conv, 8 words each at clk + 8 conv)
+    float *ms_out = nullptr;                 // y3_net_profile_convs: milliseconds per conv slot (n_ms entries)
+    int n_ms = 0;
+};
+
+// argument checks shared by the entry points that run the conv program; `heads`: the call needs detection heads
+static y3_status check_forward_args(const y3_net *net, bool args_ok, int batch, bool heads, const char *who)
 {
-    if (op_end < 0) op_end = (int)net->ops.size();
-    auto img_elems = [&](int t) -> size_t {
-        const int sp = spatial(net, t);
-        return (size_t)sp * sp * net->tensors[t].channels;
-    };
-    const bool bf = net->dtype == Y3_DTYPE_BF16;
-    const bool x3 = net->dtype == Y3_DTYPE_F32X3;
-    const bool x2 = net->dtype == Y3_DTYPE_F32X2;
-    const size_t asz = bf ? 2 : x3 ? 6 : 4;   // bytes per element of an arena tensor (fp32, or 2 x fp16)
-    auto is_out = [&](int t) { return (t == net->outputs[0] || t == net->outputs[1] || t == net->outputs[2]) && !net->staged[t]; };
+    if (!net || !args_ok || batch <= 0) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
+    if (heads && net->nclasses <= 0) return fail(Y3_ERR_STATE, "%s: the net was created without detection heads (nclasses = 0)", who);
+    if (!net->image_size) return fail(Y3_ERR_STATE, "%s: call y3_net_plan first", who);
+    if (batch > net->max_batch) return fail(Y3_ERR_INVALID, "%s: batch %d > planned %d", who, batch, net->max_batch);
+    return Y3_OK;
+}
+
+// The part of a forward one run() step enqueues: images [b0, b0 + nb) of the batch, as lane `lane`, on stream s
+struct Slice {
+    const y3_net *net;
+    const Forward &f;
+    int b0, nb, lane;
+    hipStream_t s;
+
+    size_t img_elems(int t) const { return (size_t)spatial(net, t) * spatial(net, t) * net->tensors[t].channels; }
+    // a net output written straight into the caller's fp32 grid (not staged)
+    bool caller_grid(int t) const { return is_output(net, t) && !net->staged[t]; }
     // element size: head grids are always fp32; the image batch is fp32 when the Cin = 3 first-layer kernel reads it
     // (a model whose input feeds an MFMA conv directly hands bf16 in bf16 mode); everything else follows the plan
-    auto esz = [&](int t) -> size_t {
-        if (is_out(t)) return 4;
-        if (t == net->input_tensor) return net->tensors[t].channels != 3 ? asz : 4;
-        return asz;
-    };
-    auto ptr = [&](int t) -> void * {
+    size_t elem_bytes(int t) const
+    {
+        if (caller_grid(t)) return 4;
+        if (t == net->input_tensor) return net->tensors[t].channels != 3 ? arena_elem_bytes(net->dtype) : 4;
+        return arena_elem_bytes(net->dtype);
+    }
+    size_t bytes(int t) const { return (size_t)nb * img_elems(t) * elem_bytes(t); }
+
+    void *ptr(int t) const
+    {
         if (t < 0) return nullptr;
         char *base = nullptr;
-        if (t == net->input_tensor) base = reinterpret_cast<char *>(const_cast<float *>(images));
+        if (t == net->input_tensor) base = reinterpret_cast<char *>(const_cast<float *>(f.images));
         for (int i = 0; i < 3 && !base; ++i)
-            if (t == net->outputs[i] && !net->staged[t]) base = reinterpret_cast<char *>(grids[i]);
-        if (base) return base + (size_t)b0 * img_elems(t) * esz(t);
+            if (t == net->outputs[i] && !net->staged[t]) base = reinterpret_cast<char *>(f.grids[i]);
+        if (base) return base + (size_t)b0 * img_elems(t) * elem_bytes(t);
         // arena tensors share blocks with other (dead) tensors of different per-image size: give every lane its
         // own 1/lanes region of the block so that concurrent sub-batches never alias
         char *blk = static_cast<char *>(net->tdev[t]);
         if (!blk) return nullptr;
-        if (net->dense[t]) return blk + (size_t)b0 * img_elems(t) * esz(t);
+        if (net->dense[t]) return blk + (size_t)b0 * img_elems(t) * elem_bytes(t);
         // lane regions start at the lane's first image (scaled to the block size), 256-B aligned; blocks carry 4 KiB of slack
-        const size_t off = ((size_t)((double)net->tblock[t] * b0 / net->cur_batch) + 255) & ~(size_t)255;
+        const size_t off = ((size_t)((double)net->tblock[t] * b0 / f.batch) + 255) & ~(size_t)255;
         return blk + (lane ? off : 0);
-    };
-    auto bytes = [&](int t) -> size_t { return (size_t)nb * img_elems(t) * esz(t); };
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    if (ms_out) {
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
     }
-    for (int oi = op_begin; oi < op_end; ++oi) {
-        const Op &o = net->ops[oi];
-        if (o.kind == 0) {
-            ConvSlot &c = net->convs[o.index];
-            const y3_conv_desc &d = c.d;
-            y3::ConvArgs a{};
-            a.src0 = ptr(d.src0);
-            a.src1 = ptr(d.src1);
-            a.wpk = c.w_dev;
-            a.scale = c.scale_dev;
-            a.shift = c.shift_dev;
-            a.residual = ptr(d.residual);
-            a.dst = ptr(d.dst);
-            a.B = nb;
-            a.H = a.W = net->image_size / d.in_div;
-            a.Ho = a.Wo = net->image_size / d.out_div;
-            a.Cin = d.cin;
-            a.C0 = d.c0;
-            a.Cout = d.cout;
-            a.CoutPad = c.cout_pad;
-            a.ksize = d.size;
-            a.stride = d.stride;
-            a.pad = (d.size == 3) ? 1 : 0;
-            a.up0 = d.src0_upsample;
-            a.leaky = d.leaky;
-            a.M = nb * a.Ho * a.Wo;
-            a.K = c.K;
-            a.src0_bytes = (unsigned)bytes(d.src0);
-            a.src1_bytes = d.src1 >= 0 ? (unsigned)bytes(d.src1) : 0;
-            a.w_bytes = (unsigned)((size_t)c.cout_pad * c.K * sizeof(float));
-            a.dst_bytes = (unsigned)bytes(d.dst);
-            a.xcd_gn = 0;
-            a.k_chunk = 0;
-            a.n_cus = net->n_cus;
-            a.device = net->device;
-            a.clk_stamps = (net->clk_conv == o.index) ? net->clk_stamps : (net->clk_conv == -2 && net->clk_stamps) ? net->clk_stamps + 8 * o.index : nullptr;   // fp32 MFMA kernel and stem only
-            int head = -1;   // fused decode: which output this conv produces (its grid is then not written)
-            if (net->fuse)
-                for (int k = 0; k < 3; ++k)
-                    if (d.dst == net->outputs[k] && !net->staged[d.dst]) head = k;
-            if (head >= 0) {
-                a.dec = net->fuse[head];
-                a.dec.boxes += (size_t)b0 * a.dec.N * 4;
-                a.dec.cls += (size_t)b0 * a.dec.N;
-                a.dec.scores += (size_t)b0 * a.dec.N;
-                a.dst = nullptr;
-                a.dst_bytes = 0;
+
+    // ConvArgs of conv slot `conv`; *head: which output it decodes in place (fused decode; its grid is then not written), else -1
+    y3::ConvArgs conv_args(int conv, int *head) const
+    {
+        const ConvSlot &c = net->convs[conv];
+        const y3_conv_desc &d = c.d;
+        y3::ConvArgs a{};
+        a.src0 = ptr(d.src0);
+        a.src1 = ptr(d.src1);
+        a.wpk = c.w_dev;
+        a.scale = c.scale_dev;
+        a.shift = c.shift_dev;
+        a.residual = ptr(d.residual);
+        a.dst = ptr(d.dst);
+        a.B = nb;
+        a.H = a.W = net->image_size / d.in_div;
+        a.Ho = a.Wo = net->image_size / d.out_div;
+        a.Cin = d.cin;
+        a.C0 = d.c0;
+        a.Cout = d.cout;
+        a.CoutPad = c.cout_pad;
+        a.ksize = d.size;
+        a.stride = d.stride;
+        a.pad = (d.size == 3) ? 1 : 0;
+        a.up0 = d.src0_upsample;
+        a.leaky = d.leaky;
+        a.M = nb * a.Ho * a.Wo;
+        a.K = c.K;
+        a.src0_bytes = (unsigned)bytes(d.src0);
+        a.src1_bytes = d.src1 >= 0 ? (unsigned)bytes(d.src1) : 0;
+        a.w_bytes = (unsigned)((size_t)c.cout_pad * c.K * sizeof(float));
+        a.dst_bytes = (unsigned)bytes(d.dst);
+        a.n_cus = net->n_cus;
+        a.device = net->device;
+        a.clk_stamps = !f.clk ? nullptr : f.clk_conv == conv ? f.clk : f.clk_conv == -2 ? f.clk + 8 * conv : nullptr;   // fp32 MFMA kernel and stem only
+        *head = -1;
+        if (f.heads)
+            for (int k = 0; k < 3; ++k)
+                if (d.dst == net->outputs[k] && !net->staged[d.dst]) *head = k;
+        if (*head >= 0) {
+            a.dec = f.heads[*head];
+            a.dec.boxes += (size_t)b0 * a.dec.N * 4;
+            a.dec.cls += (size_t)b0 * a.dec.N;
+            a.dec.scores += (size_t)b0 * a.dec.N;
+            a.dst = nullptr;
+            a.dst_bytes = 0;
+        }
+        return a;
+    }
+
+    // the fused stem launch (op 1) from conv1's own args: conv0 (op 0) and, with stem_conv2, the 1x1 of op 2 run inside it
+    y3_status launch_stem(const y3::ConvArgs &a1) const
+    {
+        const bool bf = net->dtype == Y3_DTYPE_BF16;
+        const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[1].index];
+        y3::StemArgs sa{};
+        sa.img = static_cast<const float *>(ptr(c0.d.src0));
+        sa.w0 = bf ? c0.w0raw_dev : c0.w0stem_dev;
+        sa.scale0 = c0.scale_dev;
+        sa.shift0 = c0.shift_dev;
+        sa.w1 = bf ? c1.wbf_dev : static_cast<const void *>(c1.w_dev);
+        sa.scale1 = c1.scale_dev;
+        sa.shift1 = c1.shift_dev;
+        sa.dst = a1.dst;
+        sa.B = nb;
+        sa.S = net->image_size;
+        sa.leaky0 = c0.d.leaky;
+        sa.leaky1 = c1.d.leaky;
+        sa.img_bytes = (unsigned)bytes(c0.d.src0);
+        sa.dst_bytes = a1.dst_bytes;
+        sa.device = net->device;
+        sa.n_cus = net->n_cus;
+        sa.clk_stamps = a1.clk_stamps;
+        if (net->stem_conv2) {
+            const ConvSlot &c2 = net->convs[net->ops[2].index];
+            sa.w2 = bf ? c2.wbf_dev : static_cast<const void *>(c2.w_dev);
+            sa.scale2 = c2.scale_dev;
+            sa.shift2 = c2.shift_dev;
+            sa.dst2 = ptr(c2.d.dst);
+            sa.leaky2 = c2.d.leaky;
+            sa.dst2_bytes = (unsigned)bytes(c2.d.dst);
+            if (!sa.dst2) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", net->ops[2].index);
+        }
+        hipError_t e = bf ? y3::launch_conv_stem_bf16(sa, s) : y3::launch_conv_stem_f32(sa, s);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "conv %d launch: %s", net->ops[1].index, hipGetErrorString(e));
+        return Y3_OK;
+    }
+
+    // pick and launch the kernel of conv op oi (args from conv_args, adjusted here per mode)
+    y3_status launch_conv(int oi, y3::ConvArgs &a, int head) const
+    {
+        if (net->stem_fused && oi == 1) return launch_stem(a);
+        const int conv = net->ops[oi].index;
+        const ConvSlot &c = net->convs[conv];
+        const y3_conv_desc &d = c.d;
+        const bool bf = net->dtype == Y3_DTYPE_BF16;
+        const PlaneSplit *split = net->dtype == Y3_DTYPE_F32X3 ? &X3_SPLIT : net->dtype == Y3_DTYPE_F32X2 ? &X2_SPLIT : nullptr;
+        const bool out_f32 = caller_grid(d.dst);   // bf16 / plane-split plans: the launch stores the fp32 grid itself
+        hipError_t e;
+        if (net->dtype != Y3_DTYPE_F32 && c.first_layer) {
+            if (out_f32) return fail(Y3_ERR_INVALID, "conv %d: first layer cannot be a head in this mode", conv);
+            e = bf ? y3::launch_conv_first_bf16(a, c.w_dev, s) : split->launch_first(a, c.w_dev, s);
+        } else if (split) {
+            a.wpk = c.*split->w;
+            a.CoutPad = c.cout_pad64;
+            a.w_bytes = (unsigned)((size_t)c.cout_pad64 * split->planes * c.K * 2);
+            if (d.residual >= 0 && out_f32) return fail(Y3_ERR_INVALID, "conv %d: residual on a head output is not supported in this mode", conv);
+            e = split->launch(a, c.*split->tile >= 0 ? c.*split->tile : split->choose(c, a.M), out_f32, s);
+        } else if (bf) {
+            a.wpk = c.wbf_dev;
+            a.w_bytes = (unsigned)((size_t)c.cout_pad * c.K * 2);
+            if (d.residual >= 0 && out_f32) return fail(Y3_ERR_INVALID, "conv %d: residual on a head output is not supported in bf16 mode", conv);
+            int tile = c.tile_bf16 >= 0 ? c.tile_bf16 : choose_tile_bf16(c, a.M, (long long)net->max_batch * a.Ho * a.Wo, !out_f32);
+            if (head >= 0 && y3::conv_bf16_tile_info(tile).bn != 256) {   // a box's logits must meet in one workgroup: all 256 channels in the tile
+                const bool m16 = tile >= 24 && tile <= 29;                // keep the MFMA shape of the plan's tile: same K grouping, same bits
+                const bool big = (a.M + 255) / 256 >= 256;                // 256x256 once it fills the chip, else 128x256 (16 waves both)
+                tile = m16 ? (big ? 24 : 26) : (big ? 17 : 19);
             }
-            if (!a.src0 || (!a.dst && head < 0)) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", o.index);
-            if ((net->stem_fused && oi == 0) || (net->stem_conv2 && oi == 2)) {   // runs inside conv1's launch (fused stem)
-                if (ms_out && o.index < n_ms) ms_out[o.index] = 0.0f;
+            e = y3::launch_conv_bf16(a, tile, out_f32, s);
+        } else if (c.first_layer) {
+            e = y3::launch_conv_first_f32(a, c.w_dev, s);
+        } else if (head >= 0) {
+            e = y3::launch_conv_head_decode_f32(a, s);
+        } else {
+            const int tile = c.tile >= 0 ? c.tile : choose_tile(c, a.M);
+            if (net->xcd_mode) a.xcd_gn = choose_xcd_gn(c, a, y3::conv_tile_info(tile));
+            {   // K order of the 3x3 convs (conv_f32.hip): chunk-major when the conv has more input channels than one chunk
+                const int ck = net->k_chunk >= 0 ? net->k_chunk : default_k_chunk(c);
+                if (d.size == 3 && d.src1 < 0 && ck > 0 && d.cin > ck && d.cin % ck == 0 && ck % 32 == 0) a.k_chunk = ck;
+            }
+            e = y3::launch_conv_f32(a, tile, s);
+        }
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "conv %d launch: %s", conv, hipGetErrorString(e));
+        return Y3_OK;
+    }
+
+    y3_status run_aux(int index) const
+    {
+        if (net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
+        const y3_aux_desc &x = net->aux[index];
+        auto p = [&](int t) { return static_cast<float *>(ptr(t)); };
+        const int sp = spatial(net, x.dst);
+        const int C = net->tensors[x.dst].channels;
+        hipError_t e = hipSuccess;
+        if (x.kind == Y3_AUX_ADD)
+            e = y3::launch_add(p(x.src0), p(x.src1), p(x.dst), (size_t)nb * sp * sp * C, s);
+        else if (x.kind == Y3_AUX_UPSAMPLE2X)
+            e = y3::launch_upsample2x(p(x.src0), nb, sp / 2, sp / 2, C, p(x.dst), s);
+        else if (x.kind == Y3_AUX_CONCAT)
+            e = y3::launch_concat(p(x.src0), net->tensors[x.src0].channels, p(x.src1), net->tensors[x.src1].channels, (size_t)nb * sp * sp, p(x.dst), s);
+        else
+            return fail(Y3_ERR_INVALID, "unknown aux op kind %d", x.kind);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d launch: %s", index, hipGetErrorString(e));
+        return Y3_OK;
+    }
+
+    // Enqueue ops [op_begin, op_end) of the op list; the segment that ends the list also converts the staged outputs to fp32.
+    y3_status run(int op_begin, int op_end) const
+    {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (f.ms_out) {
+            HIP_TRY(hipEventCreate(&ev0));
+            HIP_TRY(hipEventCreate(&ev1));
+        }
+        for (int oi = op_begin; oi < op_end; ++oi) {
+            const Op &o = net->ops[oi];
+            if (o.kind != 0) {
+                if (y3_status st = run_aux(o.index); st != Y3_OK) return st;
                 continue;
             }
-            if (ms_out) HIP_TRY(hipEventRecord(ev0, s));
-            hipError_t e;
-            if (net->stem_fused && oi == 1) {
-                const ConvSlot &c0 = net->convs[net->ops[0].index];
-                y3::StemArgs sa{};
-                sa.img = static_cast<const float *>(ptr(c0.d.src0));
-                sa.w0 = bf ? c0.w0raw_dev : c0.w0stem_dev;
-                sa.scale0 = c0.scale_dev;
-                sa.shift0 = c0.shift_dev;
-                sa.w1 = bf ? c.wbf_dev : static_cast<const void *>(c.w_dev);
-                sa.scale1 = c.scale_dev;
-                sa.shift1 = c.shift_dev;
-                sa.dst = a.dst;
-                sa.B = nb;
-                sa.S = net->image_size;
-                sa.leaky0 = c0.d.leaky;
-                sa.leaky1 = d.leaky;
-                sa.img_bytes = (unsigned)bytes(c0.d.src0);
-                sa.dst_bytes = a.dst_bytes;
-                sa.device = net->device;
-                sa.n_cus = net->n_cus;
-                sa.clk_stamps = (net->clk_conv == o.index) ? net->clk_stamps : (net->clk_conv == -2 && net->clk_stamps) ? net->clk_stamps + 8 * o.index : nullptr;
-                if (net->stem_conv2) {
-                    const ConvSlot &c2 = net->convs[net->ops[2].index];
-                    sa.w2 = bf ? c2.wbf_dev : static_cast<const void *>(c2.w_dev);
-                    sa.scale2 = c2.scale_dev;
-                    sa.shift2 = c2.shift_dev;
-                    sa.dst2 = ptr(c2.d.dst);
-                    sa.leaky2 = c2.d.leaky;
-                    sa.dst2_bytes = (unsigned)bytes(c2.d.dst);
-                    if (!sa.dst2) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", net->ops[2].index);
-                }
-                e = bf ? y3::launch_conv_stem_bf16(sa, s) : y3::launch_conv_stem_f32(sa, s);
-            } else if ((bf || x3 || x2) && c.first_layer) {
-                if (is_out(d.dst)) return fail(Y3_ERR_INVALID, "conv %d: first layer cannot be a head in this mode", o.index);
-                e = bf ? y3::launch_conv_first_bf16(a, c.w_dev, s)
-                       : x3 ? y3::launch_conv_first_f32x3(a, c.w_dev, s) : y3::launch_conv_first_f32x2(a, c.w_dev, s);
-            } else if (x2) {
-                a.wpk = c.wx2_dev;
-                a.CoutPad = c.cout_pad64;
-                a.w_bytes = (unsigned)((size_t)c.cout_pad64 * 2 * c.K * 2);
-                const bool out_f32 = is_out(d.dst);
-                if (d.residual >= 0 && out_f32) return fail(Y3_ERR_INVALID, "conv %d: residual on a head output is not supported in this mode", o.index);
-                const int tile = c.tile_x2 >= 0 ? c.tile_x2 : choose_tile_x2(c, a.M);
-                e = y3::launch_conv_f32x2(a, tile, out_f32, s);
-            } else if (x3) {
-                a.wpk = c.wx3_dev;
-                a.CoutPad = c.cout_pad64;
-                a.w_bytes = (unsigned)((size_t)c.cout_pad64 * 3 * c.K * 2);
-                const bool out_f32 = is_out(d.dst);
-                if (d.residual >= 0 && out_f32) return fail(Y3_ERR_INVALID, "conv %d: residual on a head output is not supported in this mode", o.index);
-                const int tile = c.tile_x3 >= 0 ? c.tile_x3 : choose_tile_x3(c, a.M);
-                e = y3::launch_conv_f32x3(a, tile, out_f32, s);
-            } else if (bf) {
-                a.wpk = c.wbf_dev;
-                a.w_bytes = (unsigned)((size_t)c.cout_pad * c.K * 2);
-                const bool out_f32 = is_out(d.dst);
-                if (d.residual >= 0 && out_f32) return fail(Y3_ERR_INVALID, "conv %d: residual on a head output is not supported in bf16 mode", o.index);
-                int tile = c.tile_bf16 >= 0 ? c.tile_bf16 : choose_tile_bf16(c, a.M, (long long)net->max_batch * a.Ho * a.Wo, !out_f32);
-                if (head >= 0 && y3::conv_bf16_tile_info(tile).bn != 256) {   // a box's logits must meet in one workgroup: all 256 channels in the tile
-                    const bool m16 = tile >= 24 && tile <= 29;                // keep the MFMA shape of the plan's tile: same K grouping, same bits
-                    const bool big = (a.M + 255) / 256 >= 256;                // 256x256 once it fills the chip, else 128x256 (16 waves both)
-                    tile = m16 ? (big ? 24 : 26) : (big ? 17 : 19);
-                }
-                e = y3::launch_conv_bf16(a, tile, out_f32, s);
-            } else if (c.first_layer) {
-                e = y3::launch_conv_first_f32(a, c.w_dev, s);
-            } else if (head >= 0) {
-                e = y3::launch_conv_head_decode_f32(a, s);
-            } else {
-                const int tile = c.tile >= 0 ? c.tile : choose_tile(c, a.M);
-                if (net->xcd_mode) a.xcd_gn = choose_xcd_gn(c, a, y3::conv_tile_info(tile));
-                {   // K order of the 3x3 convs (conv_f32.hip): chunk-major when the conv has more input channels than one chunk
-                    const int ck = net->k_chunk >= 0 ? net->k_chunk : default_k_chunk(c);
-                    if (d.size == 3 && d.src1 < 0 && ck > 0 && d.cin > ck && d.cin % ck == 0 && ck % 32 == 0) a.k_chunk = ck;
-                }
-                e = y3::launch_conv_f32(a, tile, s);
+            int head;
+            y3::ConvArgs a = conv_args(o.index, &head);
+            if (!a.src0 || (!a.dst && head < 0)) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", o.index);
+            if ((net->stem_fused && oi == 0) || (net->stem_conv2 && oi == 2)) {   // runs inside conv1's launch (fused stem)
+                if (f.ms_out && o.index < f.n_ms) f.ms_out[o.index] = 0.0f;
+                continue;
             }
-            if (e != hipSuccess) return fail(Y3_ERR_HIP, "conv %d launch: %s", o.index, hipGetErrorString(e));
-            if (ms_out) {
+            if (f.ms_out) HIP_TRY(hipEventRecord(ev0, s));
+            if (y3_status st = launch_conv(oi, a, head); st != Y3_OK) return st;
+            if (f.ms_out) {
                 HIP_TRY(hipEventRecord(ev1, s));
                 HIP_TRY(hipEventSynchronize(ev1));
                 float ms = 0;
                 HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-                if (o.index < n_ms) ms_out[o.index] = ms;
+                if (o.index < f.n_ms) f.ms_out[o.index] = ms;
             }
-        } else {
-            if (bf || x3 || x2) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
-            const y3_aux_desc &x = net->aux[o.index];
-            const int sp = spatial(net, x.dst);
-            const int C = net->tensors[x.dst].channels;
-            hipError_t e = hipSuccess;
-            if (x.kind == Y3_AUX_ADD)
-                e = y3::launch_add((const float *)ptr(x.src0), (const float *)ptr(x.src1), (float *)ptr(x.dst),
-                                   (size_t)nb * sp * sp * C, s);
-            else if (x.kind == Y3_AUX_UPSAMPLE2X)
-                e = y3::launch_upsample2x((const float *)ptr(x.src0), nb, sp / 2, sp / 2, C, (float *)ptr(x.dst), s);
-            else if (x.kind == Y3_AUX_CONCAT)
-                e = y3::launch_concat((const float *)ptr(x.src0), net->tensors[x.src0].channels,
-                                      (const float *)ptr(x.src1), net->tensors[x.src1].channels,
-                                      (size_t)nb * sp * sp, (float *)ptr(x.dst), s);
-            else
-                return fail(Y3_ERR_INVALID, "unknown aux op kind %d", x.kind);
-            if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d launch: %s", o.index, hipGetErrorString(e));
         }
-    }
-    if (op_end == (int)net->ops.size()) {
-        for (int k = 0; k < 3; ++k) {
+        for (int k = 0; k < 3 && op_end == (int)net->ops.size(); ++k) {
             const int t = net->outputs[k];
             if (!net->staged[t]) continue;
-            float *dst = grids[k] + (size_t)b0 * img_elems(t);
-            const int sp = spatial(net, t), C = net->tensors[t].channels;
-            const size_t npix = (size_t)nb * sp * sp;
-            hipError_t e = x2 ? y3::launch_x2_to_f32(ptr(t), dst, npix, C, s)
-                         : x3 ? y3::launch_x3_to_f32(ptr(t), dst, npix, C, s)
-                              : y3::launch_bf16_to_f32(ptr(t), dst, npix * C, s);
+            const size_t npix = (size_t)nb * spatial(net, t) * spatial(net, t);
+            hipError_t e = to_f32(net->dtype, ptr(t), f.grids[k] + (size_t)b0 * img_elems(t), npix, net->tensors[t].channels, s);
             if (e != hipSuccess) return fail(Y3_ERR_HIP, "output %d conversion: %s", k, hipGetErrorString(e));
         }
+        if (f.ms_out) {
+            (void)hipEventDestroy(ev0);
+            (void)hipEventDestroy(ev1);
+        }
+        return Y3_OK;
     }
-    if (ms_out) {
-        (void)hipEventDestroy(ev0);
-        (void)hipEventDestroy(ev1);
-    }
-    return Y3_OK;
-}
+};
 
-static y3_status run(y3_net *net, const float *images, int batch, float *const grids[3], hipStream_t s,
-                     float *ms_out, int n_ms)
+static y3_status run(const y3_net *net, const Forward &f)
 {
-    if (!net || !images || !grids || batch <= 0) return fail(Y3_ERR_INVALID, "y3_net_forward: bad argument");
-    if (!net->image_size) return fail(Y3_ERR_STATE, "y3_net_forward: call y3_net_plan first");
-    if (batch > net->max_batch) return fail(Y3_ERR_INVALID, "y3_net_forward: batch %d > planned %d", batch, net->max_batch);
+    if (y3_status st = check_forward_args(net, f.images && f.grids, f.batch, false, "y3_net_forward"); st != Y3_OK) return st;
     for (size_t i = 0; i < net->convs.size(); ++i)
         if (!net->convs[i].loaded) return fail(Y3_ERR_STATE, "y3_net_forward: conv %zu has no weights", i);
     if (net->dtype == Y3_DTYPE_F32X2)
         for (size_t i = 0; i < net->convs.size(); ++i)
             if (!net->convs[i].x2_ok) return fail(Y3_ERR_INVALID, "y3_net_forward: conv %zu has a weight outside the fp16 range of the two-plane mode", i);
     for (int i = 0; i < 3; ++i)
-        if (!grids[i] || ((uintptr_t)grids[i] & 15)) return fail(Y3_ERR_INVALID, "y3_net_forward: grid %d null or not 16-byte aligned", i);
-    if ((uintptr_t)images & 3) return fail(Y3_ERR_INVALID, "y3_net_forward: images not 4-byte aligned");
+        if (!f.grids[i] || ((uintptr_t)f.grids[i] & 15)) return fail(Y3_ERR_INVALID, "y3_net_forward: grid %d null or not 16-byte aligned", i);
+    if ((uintptr_t)f.images & 3) return fail(Y3_ERR_INVALID, "y3_net_forward: images not 4-byte aligned");
     Y3_ENTER_DEVICE(net);   // launches go to the net's device whatever the caller's current one is; restored on return
+    const hipStream_t s = f.stream;
+    const int batch = f.batch;
     // Images are independent, so the batch can run as `lanes` sub-batches on forked streams: while one sub-batch's
     // conv kernel drains (its last workgroups leave CUs under-occupied), the other sub-batch's kernel fills them.
-    net->cur_batch = batch;
-    int lanes = (ms_out || net->lanes < 2) ? 1 : net->lanes;
+    int lanes = f.lanes;
     while (lanes > 1 && batch / lanes < 1) --lanes;
     // leading segment in chunks small enough for their activations to stay in the 256 MB Infinity Cache between the
     // conv that writes them and the one that reads them, then the rest of the op list on the whole (sub-)batch
-    const int k_early = ms_out ? 0 : net->early_ops;
-    auto run_lane = [&](int b0, int nb, hipStream_t st, int lane, int nl) -> y3_status {
+    const int k_early = f.ms_out ? 0 : net->early_ops;
+    auto run_lane = [&](int b0, int nb, hipStream_t st, int lane) -> y3_status {
         if (k_early > 0) {
             for (int c0 = 0; c0 < nb; c0 += net->early_chunk) {
                 const int cn = nb - c0 < net->early_chunk ? nb - c0 : net->early_chunk;
-                y3_status r = run_slice(net, images, grids, b0 + c0, cn, st, nullptr, 0, lane, nl, 0, k_early);
+                y3_status r = Slice{net, f, b0 + c0, cn, lane, st}.run(0, k_early);
                 if (r != Y3_OK) return r;
             }
         }
-        return run_slice(net, images, grids, b0, nb, st, ms_out, n_ms, lane, nl, k_early, -1);
+        return Slice{net, f, b0, nb, lane, st}.run(k_early, (int)net->ops.size());
     };
-    if (lanes == 1) return run_lane(0, batch, s, 0, 1);
-    if (y3_status st = ensure_lanes(net); st != Y3_OK) return st;
+    if (lanes == 1) return run_lane(0, batch, s, 0);
+    if (!net->fork_ev) return fail(Y3_ERR_STATE, "y3_net_forward: no lane streams (y3_net_plan creates them)");
     HIP_TRY(hipEventRecord(net->fork_ev, s));
     // equal sub-batches (measured with tools/lanes_sweep.py: weighted 2:3 / 3:4:5 splits were 2-3 % slower)
     int start[Y3_MAX_LANES + 1];
@@ -1217,7 +1240,7 @@ static y3_status run(y3_net *net, const float *images, int batch, float *const g
         for (int l = 0; l < lanes; ++l) {
             const int nb = start[l + 1] - start[l];
             if (nb <= 0) continue;
-            y3_status st = run_lane(start[l], nb, ls[l], l, lanes);
+            y3_status st = run_lane(start[l], nb, ls[l], l);
             if (st != Y3_OK) return st;
         }
     } else {
@@ -1232,7 +1255,7 @@ static y3_status run(y3_net *net, const float *images, int batch, float *const g
             for (int l = 0; l < lanes; ++l) {
                 const int nb = start[l + 1] - start[l];
                 if (nb <= 0) continue;
-                y3_status st = run_slice(net, images, grids, start[l], nb, ls[l], nullptr, 0, l, lanes, oi, oi + 1);
+                y3_status st = Slice{net, f, start[l], nb, l, ls[l]}.run(oi, oi + 1);
                 if (st != Y3_OK) return st;
             }
     }
@@ -1247,7 +1270,7 @@ static y3_status run(y3_net *net, const float *images, int batch, float *const g
 
 y3_status y3_net_forward(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], void *stream)
 try {
-    return run(net, images_dev, batch, grids_dev, (hipStream_t)stream, nullptr, 0);
+    return run(net, {images_dev, grids_dev, batch, (hipStream_t)stream, net ? net->lanes : 1});
 }
 Y3_CATCH("y3_net_forward")
 
@@ -1266,7 +1289,10 @@ try {
             return fail(Y3_ERR_OOM, "y3_net_profile_convs: hipMalloc: %s", hipGetErrorString(e));
         }
     }
-    y3_status st = run(net, images_dev, batch, g, (hipStream_t)stream, ms_out, n);
+    Forward f{images_dev, g, batch, (hipStream_t)stream, 1};   // one lane: each launch is timed on its own
+    f.ms_out = ms_out;
+    f.n_ms = n;
+    y3_status st = run(net, f);
     (void)hipStreamSynchronize((hipStream_t)stream);
     for (int i = 0; i < 3; ++i) (void)hipFree(g[i]);
     return st;
@@ -1284,45 +1310,9 @@ bool conv_carries_stamps(const y3_net *net, size_t i)
         return false;    // runs inside the stem launch
     return net->dtype == Y3_DTYPE_F32 && !c.first_layer;
 }
-y3_status measure_sclk_impl(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
-                            int pick, float *mhz_out, void *stream);
-}  // namespace
-
-y3_status y3_net_measure_sclk_conv(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
-                                   int conv, float *mhz_out, void *stream)
-try {
-    if (!net || !mhz_out || forwards < 1 || conv < 0 || conv >= (int)net->convs.size())
-        return fail(Y3_ERR_INVALID, "y3_net_measure_sclk_conv: bad argument");
-    if (!conv_carries_stamps(net, (size_t)conv))
-        return fail(Y3_ERR_STATE, "y3_net_measure_sclk_conv: the launch of conv %d carries no clock stamps in this plan", conv);
-    return measure_sclk_impl(net, images_dev, batch, grids_dev, forwards, conv, mhz_out, stream);
-}
-Y3_CATCH("y3_net_measure_sclk_conv")
-
-y3_status y3_net_measure_sclk(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
-                              float *mhz_out, void *stream)
-try {
-    if (!net || !mhz_out || forwards < 1) return fail(Y3_ERR_INVALID, "y3_net_measure_sclk: bad argument");
-    // the launch that carries the stamps: the conv with the most FLOPs among those whose kernel has them -- the fp32 MFMA
-    // kernel (fp32 plans; a steady-state workgroup of a ~0.8 ms launch) or the fused stem kernel (fp32 and bf16 plans)
-    int pick = -1;
-    double best = 0;
-    for (size_t i = 0; i < net->convs.size(); ++i) {
-        const ConvSlot &c = net->convs[i];
-        if (!conv_carries_stamps(net, i)) continue;
-        const double ho = net->image_size ? net->image_size / c.d.out_div : 0;
-        const double fl = 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * ho;
-        if (fl > best) { best = fl; pick = (int)i; }
-    }
-    if (pick < 0) return fail(Y3_ERR_STATE, "y3_net_measure_sclk: no launch of this plan carries clock stamps (fp32 plan or fused stem needed)");
-    return measure_sclk_impl(net, images_dev, batch, grids_dev, forwards, pick, mhz_out, stream);
-}
-Y3_CATCH("y3_net_measure_sclk")
-
-namespace {
 // pick >= 0: that conv, *mhz_out one value; pick == -2: every conv that carries stamps, mhz_out / start_us / end_us arrays of
 // convs.size() entries (0 where a conv left no stamps; times relative to the earliest stamp, from s_memrealtime)
-y3_status measure_sclk_arrays(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
+y3_status measure_sclk_arrays(const y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
                               int pick, float *mhz_out, double *start_us, double *end_us, void *stream)
 {
     Y3_ENTER_DEVICE(net);
@@ -1334,16 +1324,13 @@ y3_status measure_sclk_arrays(y3_net *net, const float *images_dev, int batch, f
     hipError_t e = hipMemsetAsync(buf, 0, words * sizeof(unsigned long long), (hipStream_t)stream);
     // the chip's clock follows the load of the last milliseconds: stamp the LAST of `forwards` back-to-back forwards
     y3_status st = Y3_OK;
-    const int lanes_saved = net->lanes;
-    net->lanes = 1;             // one launch of a stamped conv (concurrent sub-batches would each stamp the same words)
+    // one lane: one launch of a stamped conv (concurrent sub-batches would each stamp the same words)
+    Forward f{images_dev, grids_dev, batch, (hipStream_t)stream, 1};
     for (int i = 0; i < forwards && st == Y3_OK && e == hipSuccess; ++i) {
-        net->clk_stamps = (i == forwards - 1) ? buf : nullptr;
-        net->clk_conv = (i == forwards - 1) ? pick : -1;
-        st = run(net, images_dev, batch, grids_dev, (hipStream_t)stream, nullptr, 0);
+        f.clk = (i == forwards - 1) ? buf : nullptr;
+        f.clk_conv = (i == forwards - 1) ? pick : -1;
+        st = run(net, f);
     }
-    net->clk_stamps = nullptr;
-    net->clk_conv = -1;
-    net->lanes = lanes_saved;
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     if (e == hipSuccess) e = hipMemcpy(host.data(), buf, words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
     (void)hipFree(buf);
@@ -1373,12 +1360,38 @@ y3_status measure_sclk_arrays(y3_net *net, const float *images_dev, int batch, f
     if (!stamped) return fail(Y3_ERR_STATE, "y3_net_measure_sclk_all: no launch of this plan left clock stamps (fp32 plan or fused stem needed)");
     return Y3_OK;
 }
-y3_status measure_sclk_impl(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
-                            int pick, float *mhz_out, void *stream)
-{
+}  // namespace
+
+y3_status y3_net_measure_sclk_conv(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
+                                   int conv, float *mhz_out, void *stream)
+try {
+    if (!net || !mhz_out || forwards < 1 || conv < 0 || conv >= (int)net->convs.size())
+        return fail(Y3_ERR_INVALID, "y3_net_measure_sclk_conv: bad argument");
+    if (!conv_carries_stamps(net, (size_t)conv))
+        return fail(Y3_ERR_STATE, "y3_net_measure_sclk_conv: the launch of conv %d carries no clock stamps in this plan", conv);
+    return measure_sclk_arrays(net, images_dev, batch, grids_dev, forwards, conv, mhz_out, nullptr, nullptr, stream);
+}
+Y3_CATCH("y3_net_measure_sclk_conv")
+
+y3_status y3_net_measure_sclk(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
+                              float *mhz_out, void *stream)
+try {
+    if (!net || !mhz_out || forwards < 1) return fail(Y3_ERR_INVALID, "y3_net_measure_sclk: bad argument");
+    // the launch that carries the stamps: the conv with the most FLOPs among those whose kernel has them -- the fp32 MFMA
+    // kernel (fp32 plans; a steady-state workgroup of a ~0.8 ms launch) or the fused stem kernel (fp32 and bf16 plans)
+    int pick = -1;
+    double best = 0;
+    for (size_t i = 0; i < net->convs.size(); ++i) {
+        const ConvSlot &c = net->convs[i];
+        if (!conv_carries_stamps(net, i)) continue;
+        const double ho = net->image_size ? net->image_size / c.d.out_div : 0;
+        const double fl = 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * ho;
+        if (fl > best) { best = fl; pick = (int)i; }
+    }
+    if (pick < 0) return fail(Y3_ERR_STATE, "y3_net_measure_sclk: no launch of this plan carries clock stamps (fp32 plan or fused stem needed)");
     return measure_sclk_arrays(net, images_dev, batch, grids_dev, forwards, pick, mhz_out, nullptr, nullptr, stream);
 }
-}  // namespace
+Y3_CATCH("y3_net_measure_sclk")
 
 y3_status y3_net_measure_sclk_all(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
                                   float *mhz_out, double *start_us, double *end_us, void *stream)
@@ -1398,22 +1411,8 @@ try {
     if (!dst_dev) return Y3_OK;
     if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
     Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
-    if (net->dtype == Y3_DTYPE_F32X2) {
-        hipError_t e = y3::launch_x2_to_f32(net->tdev[t], dst_dev, (size_t)batch * sp * sp, net->tensors[t].channels, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
-        return Y3_OK;
-    }
-    if (net->dtype == Y3_DTYPE_F32X3) {
-        hipError_t e = y3::launch_x3_to_f32(net->tdev[t], dst_dev, (size_t)batch * sp * sp, net->tensors[t].channels, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
-        return Y3_OK;
-    }
-    if (net->dtype == Y3_DTYPE_BF16) {
-        hipError_t e = y3::launch_bf16_to_f32(net->tdev[t], dst_dev, n, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
-        return Y3_OK;
-    }
-    HIP_TRY(hipMemcpyAsync(dst_dev, net->tdev[t], n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    hipError_t e = to_f32(net->dtype, net->tdev[t], dst_dev, (size_t)batch * sp * sp, net->tensors[t].channels, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
     return Y3_OK;
 }
 Y3_CATCH("y3_net_read_tensor")
@@ -1560,11 +1559,9 @@ bool heads_can_decode(const y3_net *net)
 y3_status y3_net_forward_decode(y3_net *net, const float *images_dev, int batch, const float *anchors_host, float *bboxes_dev,
                                 int64_t *class_idx_dev, float *scores_dev, void *stream)
 try {
-    if (!net || !images_dev || !anchors_host || !bboxes_dev || !class_idx_dev || !scores_dev || batch <= 0)
-        return fail(Y3_ERR_INVALID, "y3_net_forward_decode: bad argument");
-    if (net->nclasses <= 0) return fail(Y3_ERR_STATE, "y3_net_forward_decode: the net was created without detection heads (nclasses = 0)");
-    if (!net->image_size) return fail(Y3_ERR_STATE, "y3_net_forward_decode: call y3_net_plan first");
-    if (batch > net->max_batch) return fail(Y3_ERR_INVALID, "y3_net_forward_decode: batch %d > planned %d", batch, net->max_batch);
+    y3_status st = check_forward_args(net, images_dev && anchors_host && bboxes_dev && class_idx_dev && scores_dev, batch, true,
+                                      "y3_net_forward_decode");
+    if (st != Y3_OK) return st;
     if ((uintptr_t)bboxes_dev & 15) return fail(Y3_ERR_INVALID, "y3_net_forward_decode: bboxes not 16-byte aligned");
     Y3_ENTER_DEVICE(net);
     int32_t gs[3];
@@ -1574,9 +1571,9 @@ try {
         return fail(Y3_ERR_STATE, "y3_net_forward_decode: detect scratch not planned (y3_net_plan allocates it)");
     char *b = static_cast<char *>(net->det_buf);
     float *grids[3] = {reinterpret_cast<float *>(b + off[0]), reinterpret_cast<float *>(b + off[1]), reinterpret_cast<float *>(b + off[2])};
+    Forward f{images_dev, grids, batch, (hipStream_t)stream, net->lanes};
     if (!heads_can_decode(net)) {   // composed route: grids into the scratch, then the stand-alone decode
-        y3_status st = y3_net_forward(net, images_dev, batch, grids, stream);
-        if (st != Y3_OK) return st;
+        if ((st = run(net, f)) != Y3_OK) return st;
         return y3_yolo_decode_scores(grids, gs, batch, net->nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
     }
     y3::DecodeHead heads[3];
@@ -1595,10 +1592,8 @@ try {
         }
         first += gs[k] * gs[k] * 3;
     }
-    net->fuse = heads;
-    y3_status st = run(net, images_dev, batch, grids, (hipStream_t)stream, nullptr, 0);
-    net->fuse = nullptr;
-    return st;
+    f.heads = heads;
+    return run(net, f);
 }
 Y3_CATCH("y3_net_forward_decode")
 
@@ -1608,11 +1603,8 @@ y3_status y3_net_detect(y3_net *net, const float *images_dev, int batch, const f
                         float iou_threshold, float score_threshold, void *packed_dev, int32_t *num_valid_dev,
                         void *stream)
 try {
-    if (!net || !images_dev || !anchors_host || !packed_dev || !num_valid_dev || batch <= 0)
-        return fail(Y3_ERR_INVALID, "y3_net_detect: bad argument");
-    if (net->nclasses <= 0) return fail(Y3_ERR_STATE, "y3_net_detect: the net was created without detection heads (nclasses = 0)");
-    if (!net->image_size) return fail(Y3_ERR_STATE, "y3_net_detect: call y3_net_plan first");
-    if (batch > net->max_batch) return fail(Y3_ERR_INVALID, "y3_net_detect: batch %d > planned %d", batch, net->max_batch);
+    y3_status st = check_forward_args(net, images_dev && anchors_host && packed_dev && num_valid_dev, batch, true, "y3_net_detect");
+    if (st != Y3_OK) return st;
     if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES)
         return fail(Y3_ERR_INVALID, "y3_net_detect: max_boxes must be in [1,%d]", Y3_MAX_OUTPUT_BOXES);
     Y3_ENTER_DEVICE(net);   // the decode / NMS / pack launches below go to the net's device; the caller's current device is restored on return
@@ -1631,7 +1623,7 @@ try {
     // conv program with the head convs decoding their own tiles (grids neither written nor read back) where the graph allows it.
     // (Round 5 ran NMS + pack per lane, on each lane's stream behind its last conv: bit-identical and 0.2 % slower under graph replay -- the NMS
     // workgroups take CUs from the other lane's last convs; profiles/r05_ab_bf16_lane_nms.txt.  Batch-wide launches behind the join again.)
-    y3_status st = y3_net_forward_decode(net, images_dev, batch, anchors_host, boxes, cls, scores, stream);
+    st = y3_net_forward_decode(net, images_dev, batch, anchors_host, boxes, cls, scores, stream);
     if (st != Y3_OK) return st;
     st = y3_nms_padded(boxes, scores, batch, (int)n, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
                        b + o_ws, ws_bytes, stream);

@@ -31,6 +31,9 @@ def short(name):
         npl, tm, tn, wr, wc, bk = (int(m.group(i)) for i in range(1, 7))
         return (f"conv_f32x{npl}_mfma<{32*tm*wr}x{32*tn*wc},w{wr*wc},k{bk},s{m.group(9)}{',cat' if m.group(7) == 'true' else ''}"
                 f"{',f32out' if m.group(8) == 'true' else ''}>")
+    m = re.search(r"conv_first<\d+, (\d)>", name)   # conv_first<COUT, FMT>, FMT = Y3_DTYPE_* (labels as before the one kernel)
+    if m:
+        return ("conv_first_f32", "conv_first_bf16", "conv_first_f32x3", "conv_first_f32x2")[int(m.group(1))]
     m = re.search(r"conv_first_f32x3<\d+, (\d)>", name)
     if m:
         return f"conv_first_f32x{m.group(1)}"

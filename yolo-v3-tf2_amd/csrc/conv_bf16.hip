@@ -11,25 +11,14 @@
 #include <type_traits>
 
 #include "decode_box.h"
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
 {
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
-}
-
-__device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
-{
-    const unsigned short a = __builtin_bit_cast(unsigned short, (__bf16)lo);
-    const unsigned short b = __builtin_bit_cast(unsigned short, (__bf16)hi);
-    return (unsigned)a | ((unsigned)b << 16);
 }
 
 // DMA: operand tiles filled by direct-to-LDS buffer loads (BK = 64 only): unpadded 128-B rows, 16-B chunk index
@@ -84,19 +73,14 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WC, wc = wave % WC;
 
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int logical = xcd_contiguous_tile(blockIdx.x, gridDim.x);
     const int tilesN = p.CoutPad / BN;
     const int mt = logical / tilesN, nt = logical - mt * tilesN;
     const int m0 = mt * BM, n0 = nt * BN;
 
-    const __amdgpu_buffer_rsrc_t rs0 =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.src0), 0, p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void *>(CONCAT ? p.src1 : p.src0), 0, CONCAT ? p.src1_bytes : p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.wpk), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(CONCAT ? p.src1 : p.src0, CONCAT ? p.src1_bytes : p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
     const unsigned OOB0 = p.src0_bytes, OOB1 = CONCAT ? p.src1_bytes : p.src0_bytes;
 
     const int lrow = tid / LPR;
@@ -164,7 +148,6 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
 
     u32x4 ra[AP], rb[BP];
     int kglob = 0;
-    typedef __attribute__((address_space(3))) void *lds_ptr;
     auto fetch_dma = [&](int buf) {
         unsigned char *sa = smem + buf * STAGE_B + wave * DROWS * ROWB;   // wave w fills rows [pass*RP + DROWS*w, +DROWS)
         unsigned char *sb = sa + BM * ROWB;
@@ -519,102 +502,6 @@ hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream
         case 29: return launch_tb<1, 2, 2, 2, 64, true, 1, true>(a, out_f32, s);   // tile 12 (64x128, 4 waves) on 16x16x32
         default: return hipErrorInvalidValue;
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// First layer in bf16 mode: fp32 image in, fp32 arithmetic (K = 27), bf16 out.  Same structure as
-// conv_first_f32; the LDS transpose lets 4 lanes write one pixel's 32 bf16 channels (64 B) as 16-B stores.
-// ---------------------------------------------------------------------------------------------------------
-template <int COUT>
-__global__ __launch_bounds__(256) void conv_first_bf16(const ConvArgs p, const float *__restrict__ w)
-{
-    constexpr int ROW = COUT + 4;
-    __shared__ __attribute__((aligned(16))) float tr[4][64 * ROW];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int mw = blockIdx.x * 256 + wave * 64;
-    const int m = mw + lane;
-    const int HW = p.H * p.W;
-    const bool live = m < p.M;
-    const int mm = live ? m : 0;
-    const int b = mm / HW;
-    const int r = mm - b * HW;
-    const int ho = r / p.W, wo = r - ho * p.W;
-    const float *x = static_cast<const float *>(p.src0);
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc2[COUT / 2];   // packed pairs: v_pk_fma_f32 retires two MACs per VALU instruction
-#pragma unroll
-    for (int n = 0; n < COUT / 2; ++n) acc2[n] = f32x2{0.0f, 0.0f};
-#pragma unroll 1
-    for (int u = 0; u < 3; ++u) {
-        const int hi = ho - 1 + u;
-#pragma unroll 1
-        for (int v = 0; v < 3; ++v) {
-            const int wi = wo - 1 + v;
-            const bool ok = live && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            const float *xp = x + ((size_t)(b * p.H + (ok ? hi : 0)) * p.W + (ok ? wi : 0)) * 3;
-            float xv[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xv[c] = ok ? xp[c] : 0.0f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float *wr = w + ((u * 3 + v) * 3 + c) * COUT;
-#pragma unroll
-                for (int n = 0; n < COUT; n += 2)
-                    acc2[n / 2] = __builtin_elementwise_fma(f32x2{xv[c], xv[c]}, f32x2{wr[n], wr[n + 1]}, acc2[n / 2]);
-            }
-        }
-    }
-    float *t = tr[wave];
-#pragma unroll
-    for (int n = 0; n < COUT; n += 4) {
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = acc2[(n + e) / 2][(n + e) & 1] * p.scale[n + e] + p.shift[n + e];
-            if (p.leaky) v = fmaxf(v, 0.1f * v);
-            o[e] = v;
-        }
-        *reinterpret_cast<f32x4 *>(t + lane * ROW + n) = o;
-    }
-    unsigned short *dst = static_cast<unsigned short *>(p.dst);
-    constexpr int CH = COUT / 8;   // 16-B pieces (8 bf16) per pixel
-    constexpr int PPI = 64 / CH;   // pixels per store instruction
-    const int c8 = lane % CH, pl = lane / CH;
-#pragma unroll
-    for (int it = 0; it < CH; ++it) {
-        const int px = it * PPI + pl;
-        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(t + px * ROW + c8 * 8);
-        const f32x4 v1 = *reinterpret_cast<const f32x4 *>(t + px * ROW + c8 * 8 + 4);
-        u32x4 o;
-        o[0] = pack_bf16(v0[0], v0[1]);
-        o[1] = pack_bf16(v0[2], v0[3]);
-        o[2] = pack_bf16(v1[0], v1[1]);
-        o[3] = pack_bf16(v1[2], v1[3]);
-        if (mw + px < p.M) *reinterpret_cast<u32x4 *>(dst + (size_t)(mw + px) * COUT + c8 * 8) = o;
-    }
-}
-
-hipError_t launch_conv_first_bf16(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s)
-{
-    if (a.Cin != 3 || a.ksize != 3 || a.stride != 1 || a.Cout != 32 || a.residual || a.src1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(conv_first_bf16<32>, dim3((a.M + 255) / 256), dim3(256), 0, s, a, w_hwio_dev);
-    return hipGetLastError();
-}
-
-// bf16 -> fp32 copy (y3_net_read_tensor in bf16 mode)
-__global__ __launch_bounds__(256) void bf16_to_f32_kernel(const unsigned short *x, float *y, size_t n)
-{
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256)
-        y[i] = __uint_as_float((unsigned)x[i] << 16);
-}
-
-hipError_t launch_bf16_to_f32(const void *x, float *y, size_t n, hipStream_t s)
-{
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(bf16_to_f32_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s,
-                       static_cast<const unsigned short *>(x), y, n);
-    return hipGetLastError();
 }
 
 }  // namespace y3

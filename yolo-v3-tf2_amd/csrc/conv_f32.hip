@@ -19,13 +19,10 @@
 #include <algorithm>
 #include <type_traits>
 
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int BK = 32;
 static constexpr int LDS_ROW_PADDED = BK + 4;  // floats (register-staged variant)
@@ -78,40 +75,27 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
-    if (p.clk_stamps != nullptr && blockIdx.x == (gridDim.x >> 1) && tid == 0) {   // measurement launches only (y3_net_measure_sclk): a workgroup of the launch's steady state
-        p.clk_stamps[0] = __builtin_amdgcn_s_memtime();
-        p.clk_stamps[1] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (p.clk_stamps != nullptr && blockIdx.x == 0 && tid == 0) p.clk_stamps[4] = __builtin_amdgcn_s_memrealtime();   // the launch's first workgroup: when the kernel began
+    clk_stamp_entry(p.clk_stamps);   // measurement launches only (y3_net_measure_sclk)
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WC, wc = wave % WC;
 
-    // XCD-aware tile order: blocks b and b+8 share an XCD (and its L2); give each XCD a contiguous
-    // run of logical tiles so that the N-tiles of one pixel tile and neighbouring pixel tiles meet
-    // in one L2.  Bijective for any grid size.
-    const int nwg = gridDim.x;
-    const int bid = blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int nwg = gridDim.x;   // read here: passing gridDim.x further down reorders this kernel's prologue
+    const int bid = blockIdx.x, xcd = bid & 7;
+    const int logical = xcd_contiguous_tile(bid, nwg);   // (the xcd_gn > 0 order below replaces it)
     const int tilesN = p.CoutPad / BN;
     const int KT = p.K / BK;
-    const __amdgpu_buffer_rsrc_t rs0 =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.src0), 0, p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void *>(CONCAT ? p.src1 : p.src0), 0, CONCAT ? p.src1_bytes : p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.wpk), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(CONCAT ? p.src1 : p.src0, CONCAT ? p.src1_bytes : p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
     // a voffset equal to num_records is out of range for the buffer's bounds check -> the load returns 0
     const unsigned OOB0 = p.src0_bytes, OOB1 = CONCAT ? p.src1_bytes : p.src0_bytes;
 
-    const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, p.dst_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void *>(p.residual ? p.residual : p.dst), 0, p.dst_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsd = buffer_rsrc(p.dst, p.dst_bytes);
+    const __amdgpu_buffer_rsrc_t rsr = buffer_rsrc(p.residual ? p.residual : p.dst, p.dst_bytes);
     const int fr = lane & 31, fh = lane >> 5;
 
-    const int tile = logical;
-    int mt = tile / tilesN, nt = tile - mt * tilesN;
+    int mt = logical / tilesN, nt = logical - mt * tilesN;
     if (p.xcd_gn > 0) {
         // XCD-blocked order (launch_k sizes the grid for it): the 8 XCDs form a (8/gn) x gn grid over the tile matrix;
         // XCD (xm, xn) owns M-tiles [xm*tilesM/gm, (xm+1)*tilesM/gm) x N-tiles [xn*tilesN/gn, +tilesN/gn), N fastest.
@@ -238,7 +222,6 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     set_tap();
 
     f32x4 ra[AP], rb[BP];
-    typedef __attribute__((address_space(3))) void *lds_ptr;
     auto fetch_dma = [&](int buf) {
         // wave w fills rows [pass*RP + 8w, +8) of each tile: LDS destination = M0 base + lane*16
         float *sa = smem + buf * STAGE + wave * 8 * LDS_ROW;
@@ -419,7 +402,6 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
                 // element pairs as 2-vectors: the compiler selects v_pk_add_f32 / v_pk_mul_f32 (one instruction per pair, the same
                 // IEEE operation per element): with the SIMD full of 64-cycle MFMAs every vector instruction of an epilogue
                 // waits ~one MFMA for its issue slot, so the count of instructions is what the epilogue costs
-                typedef float f32x2 __attribute__((ext_vector_type(2)));
 #pragma unroll
                 for (int e = 0; e < 16; e += 2) {
                     f32x2 v2 = f32x2{acc[i][j][e], acc[i][j][e + 1]} + f32x2{sh, sh};
@@ -452,10 +434,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
         if (p.leaky) emit2(T_{}, F_{}); else emit2(F_{}, F_{});
     }
     Y3_STAMP32(4);   // thread 0 = wave 0: its own stores issued (not yet retired)
-    if (p.clk_stamps != nullptr && blockIdx.x == (gridDim.x >> 1) && tid == 0) {
-        p.clk_stamps[2] = __builtin_amdgcn_s_memtime();
-        p.clk_stamps[3] = __builtin_amdgcn_s_memrealtime();
-    }
+    clk_stamp_exit(p.clk_stamps);
 }
 
 // tile table: {BM, BN, waves, LDS stages}; ids are stable (tuning files refer to them).  Ids 20..22 and 25 were the
@@ -540,90 +519,6 @@ hipError_t launch_conv_f32(const ConvArgs &a, int tile, hipStream_t s)
         case 32: return a.src1 ? launch_k<1, 1, 2, 2, true, 1, 4, 1>(a, s) : launch_k<1, 1, 2, 2, false, 1, 4, 1>(a, s);  // 64x64, 1 stage
         default: return hipErrorInvalidValue;
     }
-}
-
-// ---------------------------------------------------------------------------------------------
-// First layer: 3x3 / stride 1 / Cin = 3 / Cout = 32 (K = 27 is too thin for the MFMA tile and the
-// layer is bound by its 4*Cout bytes of output per pixel).  One thread = one output pixel x all
-// output channels; weights are wave-uniform (scalar loads), accumulation order (u,v,c) like the
-// GEMM kernel's k order.
-// ---------------------------------------------------------------------------------------------
-template <int COUT>
-__global__ __launch_bounds__(256) void conv_first_f32(const ConvArgs p, const float *__restrict__ w)
-{
-    // per-wave transpose buffer: 64 pixels x (COUT + 4) floats (row stride 9 x 16 B -> conflict-free b128 access)
-    constexpr int ROW = COUT + 4;
-    __shared__ __attribute__((aligned(16))) float tr[4][64 * ROW];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int mw = blockIdx.x * 256 + wave * 64;  // first pixel of this wave
-    const int m = mw + lane;
-    const int HW = p.H * p.W;
-    const bool live = m < p.M;
-    const int mm = live ? m : 0;
-    const int b = mm / HW;
-    const int r = mm - b * HW;
-    const int ho = r / p.W, wo = r - ho * p.W;
-    const float *x = static_cast<const float *>(p.src0);
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc2[COUT / 2];   // packed pairs: v_pk_fma_f32 retires two MACs per VALU instruction
-#pragma unroll
-    for (int n = 0; n < COUT / 2; ++n) acc2[n] = f32x2{0.0f, 0.0f};
-#pragma unroll 1
-    for (int u = 0; u < 3; ++u) {
-        const int hi = ho - 1 + u;
-#pragma unroll 1
-        for (int v = 0; v < 3; ++v) {
-            const int wi = wo - 1 + v;
-            const bool ok = live && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            const float *xp = x + ((size_t)(b * p.H + (ok ? hi : 0)) * p.W + (ok ? wi : 0)) * 3;
-            float xv[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xv[c] = ok ? xp[c] : 0.0f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float *wr = w + ((u * 3 + v) * 3 + c) * COUT;  // HWIO, wave-uniform address -> scalar loads
-#pragma unroll
-                for (int n = 0; n < COUT; n += 2)
-                    acc2[n / 2] = __builtin_elementwise_fma(f32x2{xv[c], xv[c]}, f32x2{wr[n], wr[n + 1]}, acc2[n / 2]);
-            }
-        }
-    }
-    // epilogue into LDS (lane = pixel), then 16-B stores with 8 lanes per pixel: every wave store instruction
-    // writes 1 KiB of contiguous NHWC output (the lane-per-pixel store wrote 16 B per 128-B line and cost 2.2x
-    // the bytes at the memory side: WRITE_SIZE in profiles/r01_derived.txt)
-    float *t = tr[wave];
-#pragma unroll
-    for (int n = 0; n < COUT; n += 4) {
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = acc2[(n + e) / 2][(n + e) & 1] * p.scale[n + e] + p.shift[n + e];
-            if (p.leaky) v = fmaxf(v, 0.1f * v);
-            o[e] = v;
-        }
-        *reinterpret_cast<f32x4 *>(t + lane * ROW + n) = o;
-    }
-    // same wave wrote and reads: no barrier needed, only the LDS counter (compiler inserts the wait)
-    float *dst = static_cast<float *>(p.dst);
-    constexpr int CH = COUT / 4;           // 16-B chunks per pixel
-    constexpr int PPI = 64 / CH;           // pixels per store instruction
-    const int c4 = lane % CH, pl = lane / CH;
-#pragma unroll
-    for (int it = 0; it < CH; ++it) {
-        const int px = it * PPI + pl;
-        const f32x4 o = *reinterpret_cast<const f32x4 *>(t + px * ROW + c4 * 4);
-        if (mw + px < p.M) *reinterpret_cast<f32x4 *>(dst + (size_t)(mw + px) * COUT + c4 * 4) = o;
-    }
-}
-
-hipError_t launch_conv_first_f32(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s)
-{
-    if (a.Cin != 3 || a.ksize != 3 || a.stride != 1 || a.Cout != 32 || a.residual || a.src1)
-        return hipErrorInvalidValue;
-    dim3 grid((a.M + 255) / 256), block(256);
-    hipLaunchKernelGGL(conv_first_f32<32>, grid, block, 0, s, a, w_hwio_dev);
-    return hipGetLastError();
 }
 
 }  // namespace y3

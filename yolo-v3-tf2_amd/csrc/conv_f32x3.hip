@@ -20,78 +20,10 @@
 // 2*BK bytes with the 16-B chunk index XOR-swizzled on the source address and on the fragment reads.
 #include <type_traits>
 
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float bf16_round(float x) { return (float)(__bf16)x; }
-__device__ __forceinline__ unsigned short bf16_bits(float x) { return __builtin_bit_cast(unsigned short, (__bf16)x); }
-
-// x -> (hi, mid, lo) bf16 bit patterns with hi + mid + lo == x (fp32 subtractions of nearby values are exact)
-__device__ __forceinline__ void split3(float x, unsigned short &hi, unsigned short &mid, unsigned short &lo)
-{
-    const float h = bf16_round(x);
-    const float r1 = x - h;
-    const float m = bf16_round(r1);
-    const float r2 = r1 - m;
-    hi = bf16_bits(h);
-    mid = bf16_bits(m);
-    lo = bf16_bits(r2);
-}
-
-// x -> (h, l') fp16 bit patterns with h + l' * 2^-11 == x up to 2^-22 |x|
-__device__ __forceinline__ void split2(float x, unsigned short &hi, unsigned short &lo)
-{
-    const _Float16 h = (_Float16)x;
-    const _Float16 l = (_Float16)((x - (float)h) * 2048.0f);
-    hi = __builtin_bit_cast(unsigned short, h);
-    lo = __builtin_bit_cast(unsigned short, l);
-}
-__device__ __forceinline__ float f16lo(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u & 0xffffu)); }
-__device__ __forceinline__ float f16hi(unsigned u) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(u >> 16)); }
-
-// eight consecutive channels: fp32 -> NPL packed planes (o[plane] = 8 x 16-bit)
-template <int NPL>
-__device__ __forceinline__ void split_planes(const float (&v)[8], u32x4 (&o)[NPL])
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        if (NPL == 3) {
-            unsigned short h0, m0_, l0, h1, m1, l1;
-            split3(v[2 * k], h0, m0_, l0);
-            split3(v[2 * k + 1], h1, m1, l1);
-            o[0][k] = (unsigned)h0 | ((unsigned)h1 << 16);
-            o[1][k] = (unsigned)m0_ | ((unsigned)m1 << 16);
-            o[NPL - 1][k] = (unsigned)l0 | ((unsigned)l1 << 16);
-        } else {
-            unsigned short h0, l0, h1, l1;
-            split2(v[2 * k], h0, l0);
-            split2(v[2 * k + 1], h1, l1);
-            o[0][k] = (unsigned)h0 | ((unsigned)h1 << 16);
-            o[1][k] = (unsigned)l0 | ((unsigned)l1 << 16);
-        }
-    }
-}
-
-// packed planes of two adjacent channels -> their fp32 values
-template <int NPL>
-__device__ __forceinline__ void join_planes(const u32x4 (&q)[NPL], int k, float &a0, float &a1)
-{
-    if (NPL == 3) {
-        a0 = (__uint_as_float(q[0][k] << 16) + __uint_as_float(q[1][k] << 16)) + __uint_as_float(q[NPL - 1][k] << 16);
-        a1 = (__uint_as_float(q[0][k] & 0xffff0000u) + __uint_as_float(q[1][k] & 0xffff0000u)) +
-             __uint_as_float(q[NPL - 1][k] & 0xffff0000u);
-    } else {
-        a0 = f16lo(q[0][k]) + f16lo(q[1][k]) * (1.0f / 2048.0f);
-        a1 = f16hi(q[0][k]) + f16hi(q[1][k]) * (1.0f / 2048.0f);
-    }
-}
 
 // VAR: schedule variants of the K loop (one kernel body, so that they stay comparable):
 //   V_BURST      the LDS-DMA instructions of the next K tile are issued together at the top of the iteration (default)
@@ -128,19 +60,14 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     const int wr = wave / WC, wc = wave % WC;
 
     constexpr bool ILV = VAR == V_ILV || VAR == V_ILV_PINNED;
-    const int nwg = (int)gridDim.x, bid = (int)blockIdx.x;
-    const int q8 = nwg >> 3, r8 = nwg & 7, xcd = bid & 7;
-    const int logical = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int logical = xcd_contiguous_tile((int)blockIdx.x, (int)gridDim.x);
     const int tilesN = p.CoutPad / BN;
     const int mt = logical / tilesN, nt = logical - mt * tilesN;
     const int m0 = mt * BM, n0 = nt * BN;
 
-    const __amdgpu_buffer_rsrc_t rs0 =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.src0), 0, p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(
-        const_cast<void *>(CONCAT ? p.src1 : p.src0), 0, CONCAT ? p.src1_bytes : p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw =
-        __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.wpk), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(CONCAT ? p.src1 : p.src0, CONCAT ? p.src1_bytes : p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
     const unsigned OOB0 = p.src0_bytes, OOB1 = CONCAT ? p.src1_bytes : p.src0_bytes;
 
     const int lrow = tid / LPR;
@@ -205,7 +132,6 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     set_tap();
 
     int kglob = 0;
-    typedef __attribute__((address_space(3))) void *lds_ptr;
     auto fetch_dma = [&](int buf) {
 #pragma unroll
         for (int pl = 0; pl < NPL; ++pl) {
@@ -588,138 +514,6 @@ bool conv_x2_tile_built(int tile)
         case 0: case 1: case 2: case 3: case 4: case 8: case 12: case 26: case 27: return true;
         default: return false;
     }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// First layer: fp32 image in, fp32 arithmetic (K = 27), plane-split output (NPL = 3: bf16 x 3, NPL = 2: fp16 x 2).
-// ---------------------------------------------------------------------------------------------------------
-template <int COUT, int NPL>
-__global__ __launch_bounds__(256) void conv_first_f32x3(const ConvArgs p, const float *__restrict__ w)
-{
-    constexpr int ROW = COUT + 4;
-    __shared__ __attribute__((aligned(16))) float tr[4][64 * ROW];
-    const int lane = threadIdx.x & 63;
-    const int wave = threadIdx.x >> 6;
-    const int mw = blockIdx.x * 256 + wave * 64;
-    const int m = mw + lane;
-    const int HW = p.H * p.W;
-    const bool live = m < p.M;
-    const int mm = live ? m : 0;
-    const int b = mm / HW;
-    const int r = mm - b * HW;
-    const int ho = r / p.W, wo = r - ho * p.W;
-    const float *x = static_cast<const float *>(p.src0);
-    typedef float f32x2 __attribute__((ext_vector_type(2)));
-    f32x2 acc2[COUT / 2];
-#pragma unroll
-    for (int n = 0; n < COUT / 2; ++n) acc2[n] = f32x2{0.0f, 0.0f};
-#pragma unroll 1
-    for (int u = 0; u < 3; ++u) {
-        const int hi = ho - 1 + u;
-#pragma unroll 1
-        for (int v = 0; v < 3; ++v) {
-            const int wi = wo - 1 + v;
-            const bool ok = live && (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-            const float *xp = x + ((size_t)(b * p.H + (ok ? hi : 0)) * p.W + (ok ? wi : 0)) * 3;
-            float xv[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) xv[c] = ok ? xp[c] : 0.0f;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const float *wr = w + ((u * 3 + v) * 3 + c) * COUT;
-#pragma unroll
-                for (int n = 0; n < COUT; n += 2)
-                    acc2[n / 2] = __builtin_elementwise_fma(f32x2{xv[c], xv[c]}, f32x2{wr[n], wr[n + 1]}, acc2[n / 2]);
-            }
-        }
-    }
-    float *t = tr[wave];
-#pragma unroll
-    for (int n = 0; n < COUT; n += 4) {
-        f32x4 o;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float v = acc2[(n + e) / 2][(n + e) & 1] * p.scale[n + e] + p.shift[n + e];
-            if (p.leaky) v = fmaxf(v, 0.1f * v);
-            o[e] = v;
-        }
-        *reinterpret_cast<f32x4 *>(t + lane * ROW + n) = o;
-    }
-    unsigned short *dst = static_cast<unsigned short *>(p.dst);
-    constexpr int CH = COUT / 8;
-    constexpr int PPI = 64 / CH;
-    const int c8 = lane % CH, pl_ = lane / CH;
-#pragma unroll
-    for (int it = 0; it < CH; ++it) {
-        const int px = it * PPI + pl_;
-        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(t + px * ROW + c8 * 8);
-        const f32x4 v1 = *reinterpret_cast<const f32x4 *>(t + px * ROW + c8 * 8 + 4);
-        const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-        u32x4 o[NPL];
-        split_planes<NPL>(v, o);
-        if (mw + px < p.M) {
-#pragma unroll
-            for (int pl = 0; pl < NPL; ++pl)
-                *reinterpret_cast<u32x4 *>(dst + (size_t)(mw + px) * NPL * COUT + pl * COUT + c8 * 8) = o[pl];
-        }
-    }
-}
-
-hipError_t launch_conv_first_f32x3(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s)
-{
-    if (a.Cin != 3 || a.ksize != 3 || a.stride != 1 || a.Cout != 32 || a.residual || a.src1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv_first_f32x3<32, 3>), dim3((a.M + 255) / 256), dim3(256), 0, s, a, w_hwio_dev);
-    return hipGetLastError();
-}
-
-hipError_t launch_conv_first_f32x2(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s)
-{
-    if (a.Cin != 3 || a.ksize != 3 || a.stride != 1 || a.Cout != 32 || a.residual || a.src1) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((conv_first_f32x3<32, 2>), dim3((a.M + 255) / 256), dim3(256), 0, s, a, w_hwio_dev);
-    return hipGetLastError();
-}
-
-// two-plane -> fp32 (y3_net_read_tensor)
-__global__ __launch_bounds__(256) void x2_to_f32_kernel(const unsigned short *x, float *y, size_t npix, int C)
-{
-    const size_t n = npix * C;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const size_t px = i / C;
-        const int c = (int)(i - px * C);
-        const unsigned short *q = x + px * 2 * C + c;
-        y[i] = f16lo(q[0]) + f16lo(q[C]) * (1.0f / 2048.0f);
-    }
-}
-
-hipError_t launch_x2_to_f32(const void *x, float *y, size_t npix, int C, hipStream_t s)
-{
-    const size_t n = npix * C;
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(x2_to_f32_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s,
-                       static_cast<const unsigned short *>(x), y, npix, C);
-    return hipGetLastError();
-}
-
-// three-plane -> fp32 (y3_net_read_tensor)
-__global__ __launch_bounds__(256) void x3_to_f32_kernel(const unsigned short *x, float *y, size_t npix, int C)
-{
-    const size_t n = npix * C;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
-        const size_t px = i / C;
-        const int c = (int)(i - px * C);
-        const unsigned short *q = x + px * 3 * C + c;
-        y[i] = (__uint_as_float((unsigned)q[0] << 16) + __uint_as_float((unsigned)q[C] << 16)) +
-               __uint_as_float((unsigned)q[2 * C] << 16);
-    }
-}
-
-hipError_t launch_x3_to_f32(const void *x, float *y, size_t npix, int C, hipStream_t s)
-{
-    const size_t n = npix * C;
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
-    hipLaunchKernelGGL(x3_to_f32_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s,
-                       static_cast<const unsigned short *>(x), y, npix, C);
-    return hipGetLastError();
 }
 
 }  // namespace y3

@@ -11,12 +11,10 @@
 // (tests/test_gpu_parity.py::test_detect_single_call_equals_composed_pipeline).  After the K loop the tile (+ bias) goes to LDS
 // as [64][257] floats; the raw grid is written from there only when the caller wants it (ConvArgs.dst != nullptr).
 #include "decode_box.h"
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace {
 constexpr int HBK = 32, HBM = 64, HBN = 256, HNT = 512, HRP = HNT / 8;   // 64 rows per load pass: A in one pass, B in four
@@ -35,8 +33,8 @@ __global__ __launch_bounds__(HNT, 2) void conv_head_decode_f32(const ConvArgs p)
     const int m0 = (int)blockIdx.x * HBM;
     const int KT = p.K / HBK;
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.src0), 0, p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.wpk), 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
 
     const int lrow = tid >> 3;
     const int lchunk = (((tid & 7) ^ ((lrow >> 1) & 7)) * 4);   // logical 16-B chunk that lands in physical chunk tid & 7 (see conv_f32.hip)
@@ -46,7 +44,6 @@ __global__ __launch_bounds__(HNT, 2) void conv_head_decode_f32(const ConvArgs p)
 #pragma unroll
     for (int j = 0; j < 4; ++j) boff[j] = (unsigned)((j * HRP + lrow) * p.K + lchunk) * 4u;
 
-    typedef __attribute__((address_space(3))) void *lds_ptr;
     int kglob = 0;
     auto fetch = [&](int buf) {
         float *sa = smem + buf * HSTAGE + wave * 8 * HBK;   // wave w fills rows [pass * 64 + 8 w, +8)

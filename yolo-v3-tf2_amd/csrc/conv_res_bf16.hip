@@ -15,14 +15,10 @@
 //   * per-wave epilogue through a private LDS scratch (no barrier): y = acc * scale + shift, leaky, + shortcut in fp32, ONE
 //     rounding to bf16 (where the oracle's bf16 mode rounds), 16-byte stores; the shortcut rows are requested before the K loop.
 // One barrier per tile.  k order = tap * Cin + c in groups of 16 (v_mfma_f32_32x32x16_bf16), as in conv_bf16_mfma's 32x32x16 tiles.
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int RTH = 4, RTW = 32;            // output tile (rows x columns): wave (wm, wn) = row wm, channels [32 wn, +32) of the slice
@@ -45,13 +41,6 @@ template <int CIN> struct ResGeom {
     static constexpr int KS = CIN / 16;                 // MFMA k steps per tap: 2 or 4
     static_assert(LDS_BYTES <= 160 * 1024, "LDS budget");
 };
-
-__device__ __forceinline__ unsigned pack_bf16_(float lo, float hi)
-{
-    const unsigned short a = __builtin_bit_cast(unsigned short, (__bf16)lo);
-    const unsigned short b = __builtin_bit_cast(unsigned short, (__bf16)hi);
-    return (unsigned)a | ((unsigned)b << 16);
-}
 
 // swizzle key of a patch column: the 16 lanes of a ds_read_b128 group (consecutive columns of one patch row) then touch 16
 // different 16-byte slots of the 256-byte bank row
@@ -78,7 +67,7 @@ __global__ __launch_bounds__(RNT, 2) void conv3x3_res_bf16(const ConvArgs p, int
     const int n0 = slice * RSLICE;
     if (st >= n_spatial) return;
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.src0), 0, p.src0_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
     const unsigned OOB = p.src0_bytes;
     const int H = p.H, W = p.W;
 
@@ -109,7 +98,6 @@ __global__ __launch_bounds__(RNT, 2) void conv3x3_res_bf16(const ConvArgs p, int
         const int lc = (lane % G::CPP) ^ key_col<CIN>(px);
         dconst[k] = (unsigned)((py * W + px) * G::PB + lc * 16);
     }
-    typedef __attribute__((address_space(3))) void *lds_ptr;
     auto tile_coords = [&](int s_, int &b, int &ty, int &tx) {
         const int per_img = tiles_y * tiles_x;
         b = s_ / per_img;
@@ -144,8 +132,8 @@ __global__ __launch_bounds__(RNT, 2) void conv3x3_res_bf16(const ConvArgs p, int
     float *const S = scratch + wave * (32 * 32);
     // output / shortcut through buffer descriptors: a dead pixel (tile columns beyond the image) gets the out-of-range offset, so
     // every lane ALWAYS issues its two loads and two stores -- the counted wait at the end of a tile relies on that
-    const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, p.dst_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.residual ? p.residual : p.dst), 0, p.dst_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsd = buffer_rsrc(p.dst, p.dst_bytes);
+    const __amdgpu_buffer_rsrc_t rsr = buffer_rsrc(p.residual ? p.residual : p.dst, p.dst_bytes);
     const bool has_res = p.residual != nullptr;
 
     // shortcut rows of a tile's 32 pixels x 32 channels of this wave: 2 pieces of 8 channels per lane.  Requested ONE TILE AHEAD
@@ -220,7 +208,7 @@ __global__ __launch_bounds__(RNT, 2) void conv3x3_res_bf16(const ConvArgs p, int
             }
             u32x4 out;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) out[k] = pack_bf16_(v[2 * k], v[2 * k + 1]);
+            for (int k = 0; k < 4; ++k) out[k] = pack_bf16(v[2 * k], v[2 * k + 1]);
             __builtin_amdgcn_raw_buffer_store_b128(out, rsd, (int)ooff[it], 0, 0);   // (dropped by the bounds check for a dead pixel)
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // ... and the next tile's scratch writes stay below these reads

@@ -13,13 +13,10 @@
 //   * per-wave epilogue through a private LDS scratch: + shift, leaky, + shortcut (requested a tile ahead), 16-byte stores.
 // SAME k order and lane grouping as conv_f32_mfma (k = tap * 32 + c; lanes 0-31 / 32-63 take c = 8q + t / 8q + 4 + t of MFMA
 // (q, t)), so the result is bit-identical to the generic tiles (tests/test_gpu_parity.py::test_f32_weight_resident_conv...).
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 constexpr int FTH = 8, FTW = 16;              // output tile: wave (wm, wn) = rows 2 wm, 2 wm + 1 (16 pixels each), channels [32 wn, +32) of the slice
@@ -45,13 +42,9 @@ __global__ __launch_bounds__(FNT, 2) void conv3x3_res_f32(const ConvArgs p, int 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wm = wave >> 1, wn = wave & 1;
     const int fr = lane & 31, fh = lane >> 5;
-    // measurement launches only (y3_net_measure_sclk*, same protocol as conv_f32_mfma): thread 0 of the middle workgroup stamps
-    // {s_memtime, s_memrealtime} at its entry and after its last tile, workgroup 0 the kernel's begin.  Null in product launches.
-    if (p.clk_stamps != nullptr && blockIdx.x == (gridDim.x >> 1) && tid == 0) {
-        p.clk_stamps[0] = __builtin_amdgcn_s_memtime();
-        p.clk_stamps[1] = __builtin_amdgcn_s_memrealtime();
-    }
-    if (p.clk_stamps != nullptr && blockIdx.x == 0 && tid == 0) p.clk_stamps[4] = __builtin_amdgcn_s_memrealtime();
+    // measurement launches only (y3_net_measure_sclk*, same protocol as conv_f32_mfma): the middle workgroup stamps its entry and
+    // the end of its last tile, workgroup 0 the kernel's begin
+    clk_stamp_entry(p.clk_stamps);
 
     const int slice = (int)blockIdx.x % slices;
     const int sstep = (int)gridDim.x / slices;
@@ -59,9 +52,9 @@ __global__ __launch_bounds__(FNT, 2) void conv3x3_res_f32(const ConvArgs p, int 
     const int n0 = slice * FSLICE;
     if (st >= n_spatial) return;
 
-    const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.src0), 0, p.src0_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, p.dst_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p.residual ? p.residual : p.dst), 0, p.dst_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
+    const __amdgpu_buffer_rsrc_t rsd = buffer_rsrc(p.dst, p.dst_bytes);
+    const __amdgpu_buffer_rsrc_t rsr = buffer_rsrc(p.residual ? p.residual : p.dst, p.dst_bytes);
     const bool has_res = p.residual != nullptr;
     const unsigned OOB = p.src0_bytes;
     const int H = p.H, W = p.W;
@@ -87,7 +80,6 @@ __global__ __launch_bounds__(FNT, 2) void conv3x3_res_f32(const ConvArgs p, int 
         dpx[k] = px;
         dconst[k] = (unsigned)((py * W + px) * FPB + (((lane & 7) ^ fkey(px)) << 4));
     }
-    typedef __attribute__((address_space(3))) void *lds_ptr;
     auto tile_coords = [&](int s_, int &b, int &ty, int &tx) {
         const int per_img = tiles_y * tiles_x;
         b = s_ / per_img;
@@ -198,10 +190,7 @@ __global__ __launch_bounds__(FNT, 2) void conv3x3_res_f32(const ConvArgs p, int 
             }
         }
     }
-    if (p.clk_stamps != nullptr && blockIdx.x == (gridDim.x >> 1) && tid == 0) {
-        p.clk_stamps[2] = __builtin_amdgcn_s_memtime();
-        p.clk_stamps[3] = __builtin_amdgcn_s_memrealtime();
-    }
+    clk_stamp_exit(p.clk_stamps);
 }
 }  // namespace
 

@@ -29,12 +29,10 @@
 // conv1 identical to conv_f32_mfma (tap-major, 8q+t / 8q+4+t).  The order is the same for every pixel of every image.
 #include <type_traits>
 
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 namespace stem {
 constexpr int TH = 8, TW = 16;            // conv1 output pixels per tile
@@ -58,18 +56,9 @@ __host__ __device__ constexpr int k_of_step(int s, int h) { return s < 9 ? (h ? 
 }  // namespace stem
 
 
-// shader-clock stamps (measurement launches only: StemArgs.clk_stamps != nullptr)
-__device__ __forceinline__ void stem_stamp(unsigned long long *out, int slot)
-{
-    if (out != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
-        out[slot] = __builtin_amdgcn_s_memtime();
-        out[slot + 1] = __builtin_amdgcn_s_memrealtime();
-    }
-}
-
 __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
 {
-    stem_stamp(p.clk_stamps, 0);
+    clk_stamp<false>(p.clk_stamps, 0);   // measurement launches only: workgroup 0 at kernel entry and exit
     using namespace stem;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float *w1s = smem + PATCH_F;
@@ -123,8 +112,8 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
     for (int q = 0; q < 4; ++q)
         bw[q] = (PATCH_F + (wn * 32 + fr) * K1 + (((2 * q + fh) ^ (((wn * 32 + fr) >> 1) & 7)) << 2)) * 4;
 
-    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.img), 0, p.img_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rsd = __builtin_amdgcn_make_buffer_rsrc(p.dst, 0, p.dst_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsi = buffer_rsrc(p.img, p.img_bytes);
+    const __amdgpu_buffer_rsrc_t rsd = buffer_rsrc(p.dst, p.dst_bytes);
     const int S = p.S, So = p.S >> 1;
     const int tiles_per_img = p.tiles_y * p.tiles_x;
     const char *lds = reinterpret_cast<const char *>(smem);
@@ -156,7 +145,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
             sh2[t] = p.shift2[l15 + 16 * t];
         }
     }
-    const __amdgpu_buffer_rsrc_t rsd2 = __builtin_amdgcn_make_buffer_rsrc(with2 ? p.dst2 : p.dst, 0, with2 ? p.dst2_bytes : p.dst_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsd2 = buffer_rsrc(with2 ? p.dst2 : p.dst, with2 ? p.dst2_bytes : p.dst_bytes);
 
     // image patch of a tile: element i of the 19 x 35 x 3 patch <- image (iy0 + i / 105, ix0 + (i % 105) / 3, channel);
     // positions outside the image read as 0 (conv0's 'same' padding) through the buffer range check
@@ -318,8 +307,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
                 *reinterpret_cast<float *>(const_cast<char *>(lds) + xt[(cm & 3) + 4 * (cm >> 3)] + imm) = acc[e];
             }
             __syncthreads();   // tile complete
-            typedef float f32x4v __attribute__((ext_vector_type(4)));
-            f32x4v c0 = {0.0f, 0.0f, 0.0f, 0.0f}, c1 = {0.0f, 0.0f, 0.0f, 0.0f};
+            f32x4 c0 = {0.0f, 0.0f, 0.0f, 0.0f}, c1 = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
             for (int s = 0; s < 4; ++s) {
                 const f32x4 fa = *reinterpret_cast<const f32x4 *>(lds + a3[s]);
@@ -346,7 +334,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
         if (next < p.n_tiles) img_stage();
         __syncthreads();   // patch free for the next tile; its image patch is in place
     }
-    stem_stamp(p.clk_stamps, 2);
+    clk_stamp<false>(p.clk_stamps, 2);
 }
 
 hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s)
@@ -376,9 +364,6 @@ hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s)
 // The output tile leaves through LDS (the patch region, dead after phase 2): every store instruction writes whole
 // 128-B pixels (64 channels x 2 B), 16 pixels of a row contiguous.
 // -----------------------------------------------------------------------------------------------------------------
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4s __attribute__((ext_vector_type(4)));
-
 namespace stemb {
 using namespace stem;
 constexpr int PATCH_B = PH * PW * C0 * 2;     // 35904 bytes
@@ -387,11 +372,9 @@ constexpr int IMG_B = (IMG_F + 1) * 4;        // 7984 bytes (one pad float: conv
 constexpr int LDS_BYTES_B = PATCH_B + W1_B + IMG_B;   // 80752 <= 81920: two workgroups per CU
 }  // namespace stemb
 
-__device__ __forceinline__ unsigned short bf16_bits(float v) { return __builtin_bit_cast(unsigned short, (__bf16)v); }
-
 __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
 {
-    stem_stamp(p.clk_stamps, 0);
+    clk_stamp<false>(p.clk_stamps, 0);   // measurement launches only: workgroup 0 at kernel entry and exit
     using namespace stemb;
     extern __shared__ __attribute__((aligned(16))) unsigned char smemb[];
     const int tid = threadIdx.x;
@@ -406,9 +389,9 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
         const unsigned short *w1 = static_cast<const unsigned short *>(p.w1);
         for (int g = tid; g < C1 * (K1 / 8); g += NT) {
             const int n = g / (K1 / 8), kc = g - n * (K1 / 8);
-            const u32x4s v = *reinterpret_cast<const u32x4s *>(w1 + n * K1 + kc * 8);
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(w1 + n * K1 + kc * 8);
             const int kp = (kc & ~3) | ((kc & 3) ^ ((n >> 2) & 3));
-            *reinterpret_cast<u32x4s *>(lds + PATCH_B + n * (K1 * 2) + kp * 16) = v;
+            *reinterpret_cast<u32x4 *>(lds + PATCH_B + n * (K1 * 2) + kp * 16) = v;
         }
     }
     // conv0 on the bf16 matrix cores with fp32-class accuracy: image values and weights are split x = hi + lo (two bf16, 16
@@ -490,7 +473,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
 #pragma unroll
     for (int s = 0; s < 2; ++s) bw[s] = PATCH_B + (wn * 32 + fr) * (K1 * 2) + (((2 * s + fh) ^ (((wn * 32 + fr) >> 2) & 3)) << 4);
 
-    const __amdgpu_buffer_rsrc_t rsi = __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(p.img), 0, p.img_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rsi = buffer_rsrc(p.img, p.img_bytes);
     const int S = p.S, So = p.S >> 1;
     const int tiles_per_img = p.tiles_y * p.tiles_x;
 
@@ -623,9 +606,9 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             for (int i = 0; i < 2; ++i) {
                 const int g = tid + i * NT;                         // 1024 chunks of 16 B
                 const int P = g >> 3, ch = g & 7;
-                const u32x4s v = *reinterpret_cast<const u32x4s *>(lds + P * 128 + ch * 16);
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + P * 128 + ch * 16);
                 const int oy = ty * TH + (P >> 4), ox = tx * TW + (P & 15);
-                *reinterpret_cast<u32x4s *>(dst + ((size_t)(b * So + oy) * So + ox) * C1 + ch * 8) = v;
+                *reinterpret_cast<u32x4 *>(dst + ((size_t)(b * So + oy) * So + ox) * C1 + ch * 8) = v;
             }
         }
         if (with2) {
@@ -656,15 +639,15 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             {
                 unsigned short *dst2 = static_cast<unsigned short *>(p.dst2);
                 const int P = tid >> 2, ch = tid & 3;               // 512 chunks of 16 B
-                const u32x4s v = *reinterpret_cast<const u32x4s *>(lds + OUT2_OFF + P * 64 + ch * 16);
+                const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + OUT2_OFF + P * 64 + ch * 16);
                 const int oy = ty * TH + (P >> 4), ox = tx * TW + (P & 15);
-                *reinterpret_cast<u32x4s *>(dst2 + ((size_t)(b * So + oy) * So + ox) * 32 + ch * 8) = v;
+                *reinterpret_cast<u32x4 *>(dst2 + ((size_t)(b * So + oy) * So + ox) * 32 + ch * 8) = v;
             }
         }
         if (next < p.n_tiles) img_stage();
         __syncthreads();   // (4) staging tile read, next image patch in place
     }
-    stem_stamp(p.clk_stamps, 2);
+    clk_stamp<false>(p.clk_stamps, 2);
 }
 
 hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s)

@@ -9,12 +9,11 @@
 // 28 waves per CU in flight, so the copy of one workgroup overlaps the sigmoids of the others.  Class probabilities are
 // written back through LDS so that the [B,N,nc] store is coalesced.
 // Arithmetic: sigmoid(x) = 1/(1+exp(-x)), true divisions, fp32, no contraction (-ffp-contract=off).
+#include "y3_device.h"
 #include "y3_kernels.h"
 #include "decode_box.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 static constexpr int DEC_BOXES = 64;    // boxes per workgroup
 static constexpr int DEC_LANES = 4;     // lanes per box

@@ -1,11 +1,12 @@
 // Stand-alone Add / UpSampling2D(2) / Concatenate(axis=3) (reference: core/parse_model.py:155-156,72,134).
 // YOLOv3's own graph never launches these (the lowering folds all of them into conv launches); they exist
 // so that a model description whose pattern does not fold still runs.  HBM-bound, 16-B accesses.
+// Also the conversion of a staged tensor (held in the plan's format) to fp32.
+#include "../../include/y3.h"
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 __global__ __launch_bounds__(256) void add_kernel(const f32x4 *a, const f32x4 *b, f32x4 *y, size_t n4)
 {
@@ -65,6 +66,46 @@ hipError_t launch_concat(const float *a, int Ca, const float *b, int Cb, size_t 
     const unsigned blocks = (unsigned)((total + 255) / 256 < 2048 ? (total + 255) / 256 : 2048);
     hipLaunchKernelGGL(concat_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, (const f32x4 *)a, Ca >> 2,
                        (const f32x4 *)b, Cb >> 2, npix, (f32x4 *)y);
+    return hipGetLastError();
+}
+
+// staged tensor -> fp32 (the end of a forward in a non-fp32 plan, y3_net_read_tensor): bf16, or FMT's planes of each pixel rebuilt
+// with join_planes -- the summation order of the conv kernels' shortcut operand
+template <int FMT>
+__global__ __launch_bounds__(256) void to_f32_kernel(const unsigned short *x, float *y, size_t npix, int C)
+{
+    const size_t n = npix * C;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
+        if constexpr (FMT == Y3_DTYPE_BF16) {
+            y[i] = __uint_as_float((unsigned)x[i] << 16);
+        } else {
+            constexpr int NPL = FMT == Y3_DTYPE_F32X3 ? 3 : 2;
+            const size_t px = i / C;
+            const int c = (int)(i - px * C);
+            const unsigned short *q = x + px * NPL * C + c;
+            u32x4 planes[NPL];
+#pragma unroll
+            for (int pl = 0; pl < NPL; ++pl) planes[pl] = u32x4{q[pl * C], 0u, 0u, 0u};
+            float lo, hi;
+            join_planes<NPL>(planes, 0, lo, hi);
+            y[i] = lo;
+        }
+    }
+}
+
+hipError_t launch_to_f32(int dtype, const void *src, float *dst, size_t npix, int C, hipStream_t s)
+{
+    const size_t n = npix * C;
+    if (dtype == Y3_DTYPE_F32) return hipMemcpyAsync(dst, src, n * sizeof(float), hipMemcpyDeviceToDevice, s);
+    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const dim3 grid(blocks ? blocks : 1), block(256);
+    const unsigned short *x = static_cast<const unsigned short *>(src);
+    switch (dtype) {
+        case Y3_DTYPE_BF16: hipLaunchKernelGGL(to_f32_kernel<Y3_DTYPE_BF16>, grid, block, 0, s, x, dst, npix, C); break;
+        case Y3_DTYPE_F32X3: hipLaunchKernelGGL(to_f32_kernel<Y3_DTYPE_F32X3>, grid, block, 0, s, x, dst, npix, C); break;
+        case Y3_DTYPE_F32X2: hipLaunchKernelGGL(to_f32_kernel<Y3_DTYPE_F32X2>, grid, block, 0, s, x, dst, npix, C); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 

@@ -23,11 +23,11 @@
 // are written to lists and turned into indices by all threads afterwards.  Two more (same round): the test against the kept list works on
 // (candidate, kept box) pairs spread over all threads, and the suppression rows come from balanced pairs (128 steps per thread instead of
 // 255 for thread 0).  93 -> 68 us per call at 64-128 images x 10647 boxes (profiles/r05_nms_chains.txt).
+#include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 static constexpr int NMS_THREADS = 256;

@@ -324,10 +324,9 @@ struct PlaneSplit {
     int ConvSlot::*tile;    // forced tile (y3_net_set_tile_x3 / _x2), -1: the chooser's
     int (*choose)(const ConvSlot &, long long);
     hipError_t (*launch)(const y3::ConvArgs &, int, bool, hipStream_t);
-    hipError_t (*launch_first)(const y3::ConvArgs &, const float *, hipStream_t);   // the Cin = 3 first layer
 };
-constexpr PlaneSplit X3_SPLIT = {&ConvSlot::wx3_dev, 3, &ConvSlot::tile_x3, choose_tile_x3, y3::launch_conv_f32x3, y3::launch_conv_first_f32x3};
-constexpr PlaneSplit X2_SPLIT = {&ConvSlot::wx2_dev, 2, &ConvSlot::tile_x2, choose_tile_x2, y3::launch_conv_f32x2, y3::launch_conv_first_f32x2};
+constexpr PlaneSplit X3_SPLIT = {&ConvSlot::wx3_dev, 3, &ConvSlot::tile_x3, choose_tile_x3, y3::launch_conv_f32x3};
+constexpr PlaneSplit X2_SPLIT = {&ConvSlot::wx2_dev, 2, &ConvSlot::tile_x2, choose_tile_x2, y3::launch_conv_f32x2};
 
 // M = rows of this call (per lane); M_plan = rows of the planned batch.  The MFMA SHAPE (16x16x32 vs 32x32x16: two K groupings,
 // results differ in the last bits) is decided from plan-time quantities only, so that an image's result does not depend on the
@@ -464,17 +463,6 @@ static bool output_staged(const y3_net *net, int t)
 
 // bytes per element of an arena tensor: fp32, bf16, three bf16 planes, or two fp16 planes (4 bytes as well)
 static size_t arena_elem_bytes(int dtype) { return dtype == Y3_DTYPE_BF16 ? 2 : dtype == Y3_DTYPE_F32X3 ? 6 : 4; }
-
-// staged activation (the plan's format) -> fp32, npix pixels of C channels
-static hipError_t to_f32(int dtype, const void *src, float *dst, size_t npix, int C, hipStream_t s)
-{
-    switch (dtype) {
-        case Y3_DTYPE_F32X2: return y3::launch_x2_to_f32(src, dst, npix, C, s);
-        case Y3_DTYPE_F32X3: return y3::launch_x3_to_f32(src, dst, npix, C, s);
-        case Y3_DTYPE_BF16: return y3::launch_bf16_to_f32(src, dst, npix * C, s);
-        default: return hipMemcpyAsync(dst, src, npix * C * sizeof(float), hipMemcpyDeviceToDevice, s);
-    }
-}
 
 extern "C" {
 
@@ -1090,9 +1078,9 @@ struct Slice {
         const PlaneSplit *split = net->dtype == Y3_DTYPE_F32X3 ? &X3_SPLIT : net->dtype == Y3_DTYPE_F32X2 ? &X2_SPLIT : nullptr;
         const bool out_f32 = caller_grid(d.dst);   // bf16 / plane-split plans: the launch stores the fp32 grid itself
         hipError_t e;
-        if (net->dtype != Y3_DTYPE_F32 && c.first_layer) {
-            if (out_f32) return fail(Y3_ERR_INVALID, "conv %d: first layer cannot be a head in this mode", conv);
-            e = bf ? y3::launch_conv_first_bf16(a, c.w_dev, s) : split->launch_first(a, c.w_dev, s);
+        if (c.first_layer) {
+            if (net->dtype != Y3_DTYPE_F32 && out_f32) return fail(Y3_ERR_INVALID, "conv %d: first layer cannot be a head in this mode", conv);
+            e = y3::launch_conv_first(a, c.w_dev, net->dtype, s);
         } else if (split) {
             a.wpk = c.*split->w;
             a.CoutPad = c.cout_pad64;
@@ -1110,8 +1098,6 @@ struct Slice {
                 tile = m16 ? (big ? 24 : 26) : (big ? 17 : 19);
             }
             e = y3::launch_conv_bf16(a, tile, out_f32, s);
-        } else if (c.first_layer) {
-            e = y3::launch_conv_first_f32(a, c.w_dev, s);
         } else if (head >= 0) {
             e = y3::launch_conv_head_decode_f32(a, s);
         } else {
@@ -1182,7 +1168,7 @@ struct Slice {
             const int t = net->outputs[k];
             if (!net->staged[t]) continue;
             const size_t npix = (size_t)nb * spatial(net, t) * spatial(net, t);
-            hipError_t e = to_f32(net->dtype, ptr(t), f.grids[k] + (size_t)b0 * img_elems(t), npix, net->tensors[t].channels, s);
+            hipError_t e = y3::launch_to_f32(net->dtype, ptr(t), f.grids[k] + (size_t)b0 * img_elems(t), npix, net->tensors[t].channels, s);
             if (e != hipSuccess) return fail(Y3_ERR_HIP, "output %d conversion: %s", k, hipGetErrorString(e));
         }
         if (f.ms_out) {
@@ -1411,7 +1397,7 @@ try {
     if (!dst_dev) return Y3_OK;
     if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
     Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
-    hipError_t e = to_f32(net->dtype, net->tdev[t], dst_dev, (size_t)batch * sp * sp, net->tensors[t].channels, (hipStream_t)stream);
+    hipError_t e = y3::launch_to_f32(net->dtype, net->tdev[t], dst_dev, (size_t)batch * sp * sp, net->tensors[t].channels, (hipStream_t)stream);
     if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
     return Y3_OK;
 }

@@ -70,8 +70,10 @@ hipError_t launch_conv_res_f32(const ConvArgs &a, hipStream_t s);
 // 1x1 head conv (Cout = 3 * (5 + nc) <= 256) + bias with yolo_decode + arg-max / score fused in (conv_head.hip)
 bool conv_head_decode_f32_fits(const ConvArgs &a);
 hipError_t launch_conv_head_decode_f32(const ConvArgs &a, hipStream_t s);
-// first layer: 3x3 stride-1 conv with Cin=3 (direct, VALU)
-hipError_t launch_conv_first_f32(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s);
+// first layer: 3x3 stride-1 conv with Cin = 3 (direct, VALU; conv_first.hip): fp32 image in, output in the format of dtype (Y3_DTYPE_*)
+hipError_t launch_conv_first(const ConvArgs &a, const float *w_hwio, int dtype, hipStream_t s);
+// staged tensor in the format of dtype (Y3_DTYPE_*) -> fp32, npix pixels of C channels (fp32: a device-to-device copy)
+hipError_t launch_to_f32(int dtype, const void *src, float *dst, size_t npix, int C, hipStream_t s);
 
 // fused stem (conv_stem.hip): conv0 (3x3/1, 3->32) + conv1 (3x3/2, 32->64), both BN + optional leaky, one launch
 struct StemArgs {
@@ -113,21 +115,15 @@ hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream
 // weight-resident 3x3 / stride-1 conv for Cin = 32 / 64 (conv_res_bf16.hip): the early short-K layers of the bf16 path
 bool conv_res_bf16_fits(const ConvArgs &a);
 hipError_t launch_conv_res_bf16(const ConvArgs &a, hipStream_t s);
-hipError_t launch_conv_first_bf16(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s);
-hipError_t launch_bf16_to_f32(const void *x, float *y, size_t n, hipStream_t s);
 
 // fp32-accurate path on the bf16 matrix cores, three bf16 planes per value (conv_f32x3.hip); TileInfo.stages holds BK
 static constexpr int X3_TILE_COUNT = 34;
 TileInfo conv_x3_tile_info(int tile);
 hipError_t launch_conv_f32x3(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
-hipError_t launch_conv_first_f32x3(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s);
-hipError_t launch_x3_to_f32(const void *x, float *y, size_t npix, int C, hipStream_t s);
 // two fp16 planes per value on the fp16 matrix cores (same kernel, same tile ids; a subset is instantiated)
 hipError_t launch_conv_f32x2(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
 bool conv_x2_tile_built(int tile);
 bool conv_x3_tile_built(int tile);
-hipError_t launch_conv_first_f32x2(const ConvArgs &a, const float *w_hwio_dev, hipStream_t s);
-hipError_t launch_x2_to_f32(const void *x, float *y, size_t npix, int C, hipStream_t s);
 
 hipError_t launch_add(const float *a, const float *b, float *y, size_t n, hipStream_t s);
 hipError_t launch_upsample2x(const float *x, int B, int H, int W, int C, float *y, hipStream_t s);

@@ -214,6 +214,18 @@ y3_status y3_net_profile_convs(y3_net *net, const float *images_dev, int batch, 
 y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, int width, int channels,
                               float *batch_dev, int slot, int image_size, void *stream);
 
+/* The same stage for a batch of unlike images in one launch per 64 images (no reference counterpart: the reference resizes
+ * image by image).  All images lie in ONE device blob `pixels_dev` of `pixels_bytes` bytes; image i starts `offset` bytes into
+ * it, is [height,width,channels] (channels 3 or 4, alpha dropped) and has `mode` with the meaning of is_uint8 above: 0 float32
+ * (offset and pixels_dev 4-byte aligned), 1 uint8 * 1/255 before the resize, 2 uint8 divided by 255 after it.  Image i is
+ * written to batch_dev[first_slot + i]; every value is bit-identical to the per-image call.  descs_host is read during the call (the
+ * descriptors travel in the kernel arguments), so the caller may reuse it at once.  All arguments are checked on the host
+ * before anything is enqueued (Y3_ERR_INVALID names the index of the bad image); the call only enqueues on `stream`: it does
+ * not allocate, query or synchronise, and can be captured into a HIP graph (the descriptors are then frozen into it). */
+typedef struct y3_image_desc { uint64_t offset; int32_t height, width, channels, mode; } y3_image_desc;
+y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
+                              float *batch_dev, int first_slot, int image_size, void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * yolo_decode   (reference: core/yolo_decode_layer.py:15-36)
  * grids_dev[s]: [B,g_s,g_s,3,5+nc]; anchors_host: [3][3][2] normalised (w,h), scale s uses anchors[s].

@@ -46,7 +46,8 @@ def short(name):
         return f"conv_res3x3_bf16<cin{m.group(1)}>"
     if "conv3x3_res_f32" in name:
         return "conv_res3x3_f32"
-    for k in ("conv_head_decode_f32", "conv_stem_f32", "conv_stem_bf16", "conv_first_f32x3", "conv_first_f32", "conv_first_bf16", "decode_kernel", "nms_kernel", "pack_kernel", "class_scores"):
+    for k in ("conv_head_decode_f32", "conv_stem_f32", "conv_stem_bf16", "conv_first_f32x3", "conv_first_f32", "conv_first_bf16", "decode_kernel", "nms_kernel", "pack_kernel", "class_scores",
+              "preprocess_batch_kernel", "resize_kernel"):
         if k in name:
             return k
     return name[:60]

@@ -81,6 +81,12 @@ class TensorDesc(C.Structure):
     _fields_ = [("channels", C.c_int32), ("div", C.c_int32)]
 
 
+class ImageDesc(C.Structure):
+    """y3_image_desc: one image of a y3_preprocess_batch pixel blob."""
+    _fields_ = [("offset", C.c_uint64), ("height", C.c_int32), ("width", C.c_int32), ("channels", C.c_int32),
+                ("mode", C.c_int32)]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _fp = C.POINTER(C.c_float)
 
@@ -113,6 +119,7 @@ SYMBOLS = {
     "y3_net_flops_per_image": (C.c_double, [_vp]),
     "y3_net_profile_convs": (_i, [_vp, _vp, _i, _fp, _i, _vp]),
     "y3_preprocess_image": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "y3_preprocess_batch": (_i, [_vp, _sz, C.POINTER(ImageDesc), _i, _vp, _i, _i, _vp]),
     "y3_yolo_decode": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_yolo_decode_scores": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_class_scores": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),

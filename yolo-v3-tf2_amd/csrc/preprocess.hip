@@ -8,7 +8,8 @@
 // which is mode 2 below.
 // Arithmetic restated from TF's ResizeBilinear CPU kernel: in = (out + 0.5) * (in_size / out_size) - 0.5,
 // lower = max(floor(in), 0), upper = min(ceil(in), in_size - 1), lerp = in - floor(in); interpolate along x first
-// (top, bottom) then along y; fp32, no contraction.  HBM-bound and tiny; one thread per output pixel.
+// (top, bottom) then along y; fp32, no contraction.  HBM-bound and tiny.  resize_kernel: one image per launch, one thread per
+// output pixel; preprocess_batch_kernel: up to 64 unlike images per launch, four pixels per thread.
 #include <type_traits>
 
 #include "y3_kernels.h"
@@ -26,12 +27,11 @@ struct RawU8 { unsigned char v; };   // uint8 taken as 0..255, divided by 255 af
 template <>
 __device__ __forceinline__ float px<RawU8>(const RawU8 *p) { return (float)p->v; }
 
+// One output pixel (3 floats) of the resize: the per-pixel body of both kernels below, so that the per-image and the
+// batched launch cannot drift apart.  i = oy * S + ox.
 template <typename T>
-__global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, int H, int W, int pix_stride,
-                                                     float *__restrict__ dst, int S)
+__device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, int S, int i, float *out)
 {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= S * S) return;
     const int oy = i / S, ox = i - oy * S;
     const float sy = (float)H / (float)S, sx = (float)W / (float)S;
     const float fy = ((float)oy + 0.5f) * sy - 0.5f, fx = ((float)ox + 0.5f) * sx - 0.5f;
@@ -47,8 +47,64 @@ __global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, 
         const float top = tl + (tr - tl) * lx;
         const float bot = bl + (br - bl) * lx;
         const float v = top + (bot - top) * ly;
-        dst[(size_t)i * 3 + c] = std::is_same<T, RawU8>::value ? v / 255.0f : v;
+        out[c] = std::is_same<T, RawU8>::value ? v / 255.0f : v;
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, int H, int W, int pix_stride,
+                                                     float *__restrict__ dst, int S)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S * S) return;
+    float v[3];
+    resize_pixel<T>(src, H, W, pix_stride, S, i, v);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) dst[(size_t)i * 3 + c] = v[c];
+}
+
+// A batch of unlike images in one launch: blockIdx.y is the image within the launch, blockIdx.x tiles its S*S output pixels.
+// The descriptors travel by value in the kernel arguments (PreprocessTable, 1.5 KB of the 4 KB limit): nothing extra is
+// copied, they have no lifetime to manage, and the launch can be captured into a graph.
+// VEC: every thread produces four consecutive pixels (12 floats) and writes them as three 16-byte stores; needs
+// S*S % 4 == 0 and a 16-byte aligned destination, which holds for every network size (S a multiple of 32).  Otherwise one
+// pixel and three scalar stores per thread.
+template <typename T, bool VEC>
+__device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src, int H, int W, int pix_stride,
+                                                      float *__restrict__ dst, int S)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (VEC) {
+        if (q * 4 >= S * S) return;
+        float v[12];
+#pragma unroll
+        for (int p = 0; p < 4; ++p) resize_pixel<T>(src, H, W, pix_stride, S, q * 4 + p, v + 3 * p);
+        float4 *o = reinterpret_cast<float4 *>(dst + (size_t)q * 12);
+        o[0] = make_float4(v[0], v[1], v[2], v[3]);
+        o[1] = make_float4(v[4], v[5], v[6], v[7]);
+        o[2] = make_float4(v[8], v[9], v[10], v[11]);
+    } else {
+        if (q >= S * S) return;
+        float v[3];
+        resize_pixel<T>(src, H, W, pix_stride, S, q, v);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) dst[(size_t)q * 3 + c] = v[c];
+    }
+}
+
+template <bool VEC>
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char *__restrict__ pixels, PreprocessTable table,
+                                                               float *__restrict__ batch, int S)
+{
+    const y3_image_desc d = table.d[blockIdx.y];          // uniform per workgroup: scalar loads from the kernel arguments
+    const unsigned char *src = pixels + d.offset;
+    float *dst = batch + (size_t)blockIdx.y * S * S * 3;
+    if (d.mode == 2)                                      // one branch per workgroup, outside the pixel body
+        preprocess_batch_body<RawU8, VEC>(reinterpret_cast<const RawU8 *>(src), d.height, d.width, d.channels, dst, S);
+    else if (d.mode == 1)
+        preprocess_batch_body<unsigned char, VEC>(src, d.height, d.width, d.channels, dst, S);
+    else
+        preprocess_batch_body<float, VEC>(reinterpret_cast<const float *>(src), d.height, d.width, d.channels, dst, S);
 }
 
 hipError_t launch_resize(const void *src, int is_u8, int H, int W, int pix_stride, float *dst, int S, hipStream_t s)
@@ -61,6 +117,22 @@ hipError_t launch_resize(const void *src, int is_u8, int H, int W, int pix_strid
                            pix_stride, dst, S);
     else
         hipLaunchKernelGGL(resize_kernel<float>, grid, block, 0, s, static_cast<const float *>(src), H, W, pix_stride, dst, S);
+    return hipGetLastError();
+}
+
+// descs: n (1..kPreprocessTableImages) validated descriptors; dst: slot of the first image.  Vector stores when the geometry allows.
+hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, int n, float *dst, int S, hipStream_t s)
+{
+    PreprocessTable table{};
+    for (int i = 0; i < n; ++i) table.d[i] = descs[i];
+    const bool vec = ((size_t)S * S) % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+    const int per_block = vec ? 1024 : 256;
+    dim3 grid((unsigned)(((size_t)S * S + per_block - 1) / per_block), (unsigned)n), block(256);
+    const unsigned char *p = static_cast<const unsigned char *>(pixels);
+    if (vec)
+        hipLaunchKernelGGL(preprocess_batch_kernel<true>, grid, block, 0, s, p, table, dst, S);
+    else
+        hipLaunchKernelGGL(preprocess_batch_kernel<false>, grid, block, 0, s, p, table, dst, S);
     return hipGetLastError();
 }
 

@@ -1417,6 +1417,41 @@ try {
 }
 Y3_CATCH("y3_preprocess_image")
 
+y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
+                              float *batch_dev, int first_slot, int image_size, void *stream)
+try {
+    if (!pixels_dev || !descs_host || !batch_dev || n_images < 1 || first_slot < 0 || image_size <= 0)
+        return fail(Y3_ERR_INVALID, "y3_preprocess_batch: bad argument (null pointer, n_images < 1, first_slot < 0 or image_size <= 0)");
+    // every check before the first launch: a bad image late in the list must not leave the batch half written
+    for (int i = 0; i < n_images; ++i) {
+        const y3_image_desc &d = descs_host[i];
+        if (d.channels < 3 || d.channels > 4)
+            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: channels must be 3 or 4 (got %d)", i, d.channels);
+        if (d.mode < 0 || d.mode > 2)
+            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: mode must be 0, 1 or 2 (got %d)", i, d.mode);
+        if (d.height < 1 || d.width < 1)
+            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: height and width must be at least 1 (got %d x %d)", i,
+                        d.height, d.width);
+        if (d.mode == 0 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
+            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: float32 pixels must be 4-byte aligned (offset %llu)", i,
+                        (unsigned long long)d.offset);
+        // height, width < 2^31 and channels * elemsize <= 16: the product stays below 2^66, so take it in 128 bits
+        const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (d.mode == 0 ? 4 : 1));
+        if ((unsigned __int128)d.offset + bytes > (unsigned __int128)pixels_bytes)
+            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", i,
+                        d.height, d.width, d.channels, (unsigned long long)d.offset, pixels_bytes);
+    }
+    const size_t per_image = (size_t)image_size * image_size * 3;
+    for (int i0 = 0; i0 < n_images; i0 += y3::kPreprocessTableImages) {
+        const int n = std::min(y3::kPreprocessTableImages, n_images - i0);
+        hipError_t e = y3::launch_preprocess_batch(pixels_dev, descs_host + i0, n, batch_dev + ((size_t)first_slot + i0) * per_image,
+                                                   image_size, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_preprocess_batch launch: %s", hipGetErrorString(e));
+    }
+    return Y3_OK;
+}
+Y3_CATCH("y3_preprocess_batch")
+
 // ------------------------------------------------------------------------------------------ TFRecord checksum
 uint32_t y3_crc32c(const void *data_host, size_t nbytes)
 {

@@ -4,6 +4,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "../../include/y3.h"
 #include "decode_box.h"
 
 namespace y3 {
@@ -142,6 +143,11 @@ hipError_t launch_class_scores(const float *conf, const float *probs, size_t n, 
                                float *scores, hipStream_t s);
 
 hipError_t launch_resize(const void *src, int is_u8, int H, int W, int pix_stride, float *dst, int S, hipStream_t s);
+// The image descriptors of one preprocess_batch_kernel launch, passed by value in the kernel arguments (the limit is 4 KB).
+constexpr int kPreprocessTableImages = 64;
+struct PreprocessTable { y3_image_desc d[kPreprocessTableImages]; };
+static_assert(sizeof(y3_image_desc) == 24 && sizeof(PreprocessTable) + 64 <= 4096, "descriptor table must fit the kernel arguments");
+hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, int n, float *dst, int S, hipStream_t s);
 
 size_t nms_workspace_bytes(int B, int N);
 hipError_t launch_nms(const float *boxes, const float *scores, int B, int N, int M, float T, float S, int32_t *sel,

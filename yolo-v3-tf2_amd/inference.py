@@ -134,8 +134,9 @@ class Inference:
                 nonlocal image_index
                 batch_dev = torch.empty((len(images_u8), image_size, image_size, 3), dtype=torch.float32,
                                         device="cuda")
-                for slot, u8 in enumerate(images_u8):
-                    runtime.preprocess_image(torch.from_numpy(u8).cuda(), batch_dev, slot, divide_after=True)
+                # one copy and one launch for the batch (mode 2: resize the 0..255 values, then / 255)
+                blob, descs = runtime.pack_images(images_u8, 2)
+                runtime.preprocess_batch(torch.from_numpy(blob).cuda(), descs, batch_dev)
                 b_boxes, b_cls, b_scores, b_sel, b_nv = (t.cpu().numpy() for t in model(batch_dev))
                 for bb, cc, ss, sel, nv, img in zip(b_boxes, b_cls, b_scores, b_sel, b_nv, batch_dev.cpu().numpy()):
                     bboxes, classes, scores = self.gather_valid_detections_results(bb, cc, ss, sel, int(nv))

@@ -311,6 +311,74 @@ class Net:
                                      float(score_threshold), _dev(packed), _dev(nv), _lib.stream_ptr()), "y3_net_detect")
         return packed, nv
 
+    def detect_stream(self, batches, anchors, max_boxes: int, iou_threshold: float, score_threshold: float, mode=1,
+                      depth: int = 2, max_batch: Optional[int] = None, max_blob_bytes: Optional[int] = None):
+        """Frames in host memory -> detections, overlapped: a generator over an iterable of image lists (each image a
+        NumPy [H,W,3|4] uint8 or float32 array; `mode` as for pack_images) that yields (packed [B,max_boxes,7] int32 words,
+        num_valid [B] int32) as NumPy arrays, one pair per list, in submission order; a ragged last list is allowed.
+        Batch i+1 is packed, copied and resized on the InputStage's copy stream before y3_net_detect of batch i is
+        enqueued on the current stream, and only the packed rows come back to the host (pinned buffers, one event per
+        batch): the host waits for the result of batch i while batch i+1 is already queued behind it.
+        The net keeps its planned image size and is re-planned at most once, for max_batch images; the stage's blobs hold
+        max_blob_bytes.  Both default to the largest list of `batches`, which must then be a list or tuple."""
+        if max_batch is None or max_blob_bytes is None:
+            if not isinstance(batches, (list, tuple)):
+                raise Y3Error("detect_stream: pass max_batch and max_blob_bytes when `batches` is not a list or tuple")
+            if max_batch is None:
+                max_batch = max((len(b) for b in batches), default=0)
+            if max_blob_bytes is None:
+                max_blob_bytes = max((packed_nbytes(b) for b in batches), default=0)
+        S = self.image_size
+        if S <= 0:
+            raise Y3Error("detect_stream: plan() the net first (the image size is the plan's)")
+        if depth < 2:
+            raise Y3Error("detect_stream: depth must be at least 2 (batch i+1 is staged while batch i is detected)")
+        if max_batch < 1:
+            return
+        stage = InputStage(S, max_batch, max(int(max_blob_bytes), 16), depth)
+        if max_batch > self.max_batch:
+            self.plan(max_batch, S)
+        a = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 3, 2))
+        M = int(max_boxes)
+        dev = stage.device
+        outs = [(torch.empty((max_batch, M, 7), dtype=torch.int32, device=dev),
+                 torch.empty((max_batch,), dtype=torch.int32, device=dev),
+                 torch.empty((max_batch, M, 7), dtype=torch.int32, pin_memory=True),
+                 torch.empty((max_batch,), dtype=torch.int32, pin_memory=True),
+                 torch.cuda.Event()) for _ in range(stage.depth)]
+        pending = []
+
+        def result(entry):
+            k, n = entry
+            _, _, packed_host, nv_host, done = outs[k]
+            done.synchronize()      # an event wait: the next batch's detect is already queued behind this one
+            return packed_host[:n].numpy().copy(), nv_host[:n].numpy().copy()
+
+        it = iter(batches)
+        first = next(it, None)
+        handle = stage.submit(first, mode) if first is not None else None
+        i = 0
+        while handle is not None:
+            nxt = next(it, None)
+            following = stage.submit(nxt, mode) if nxt is not None else None   # batch i+1 goes in before detect of batch i
+            cur = torch.cuda.current_stream()
+            cur.wait_event(handle.ready)
+            k, n = i % stage.depth, handle.batch.shape[0]
+            packed_dev, nv_dev, packed_host, nv_host, done = outs[k]
+            check(self.lib.y3_net_detect(self._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
+                                         float(score_threshold), _dev(packed_dev), _dev(nv_dev), C.c_void_p(cur.cuda_stream)),
+                  "y3_net_detect")
+            stage.release(handle)
+            packed_host[:n].copy_(packed_dev[:n], non_blocking=True)
+            nv_host[:n].copy_(nv_dev[:n], non_blocking=True)
+            done.record(cur)
+            pending.append((k, n))
+            if len(pending) == stage.depth:     # its output buffers are the next to be reused
+                yield result(pending.pop(0))
+            handle, i = following, i + 1
+        while pending:
+            yield result(pending.pop(0))
+
     def flops_per_image(self) -> float:
         return float(self.lib.y3_net_flops_per_image(self._h))
 
@@ -414,6 +482,153 @@ def preprocess_image(image: torch.Tensor, batch: torch.Tensor, slot: int, divide
     check(_lib.load().y3_preprocess_image(_dev(image), mode, H, W, C_, _dev(batch), slot,
                                           batch.shape[1], _lib.stream_ptr()), "y3_preprocess_image")
     return batch
+
+
+# y3_image_desc (include/y3.h), as a NumPy structured dtype: what pack_images returns and preprocess_batch takes
+IMAGE_DESC_DTYPE = np.dtype([("offset", "<u8"), ("height", "<i4"), ("width", "<i4"), ("channels", "<i4"), ("mode", "<i4")])
+_BLOB_ALIGN = 16     # image starts inside a pixel blob
+
+
+def _image_modes(images, mode):
+    if np.ndim(mode) == 0:
+        modes = [int(mode)] * len(images)
+    else:
+        modes = [int(m) for m in mode]
+        if len(modes) != len(images):
+            raise Y3Error(f"pack_images: {len(modes)} modes for {len(images)} images")
+    for i, (im, m) in enumerate(zip(images, modes)):
+        if not isinstance(im, np.ndarray) or im.ndim != 3 or im.shape[2] not in (3, 4) or 0 in im.shape:
+            raise Y3Error(f"pack_images: image {i} must be a non-empty NumPy array [H,W,3|4]")
+        want = {0: np.float32, 1: np.uint8, 2: np.uint8}.get(m)
+        if want is None:
+            raise Y3Error(f"pack_images: image {i}: mode must be 0, 1 or 2 (got {m})")
+        if im.dtype != want:
+            raise Y3Error(f"pack_images: image {i} is {im.dtype}, mode {m} takes {np.dtype(want)}")
+    return modes
+
+
+def _blob_offsets(images):
+    offsets, end = [], 0
+    for im in images:
+        start = -(-end // _BLOB_ALIGN) * _BLOB_ALIGN
+        offsets.append(start)
+        end = start + im.nbytes
+    return offsets, end
+
+
+def packed_nbytes(images) -> int:
+    """Bytes pack_images needs for this list (image starts 16-byte aligned)."""
+    return _blob_offsets(images)[1]
+
+
+def pack_images(images, mode, out: Optional[np.ndarray] = None):
+    """A list of [H,W,3|4] uint8 / float32 arrays -> (blob_u8, descs): one contiguous byte buffer with every image start
+    16-byte aligned, and the y3_image_desc array (IMAGE_DESC_DTYPE) that names them.  Pure NumPy.
+    mode: one value for the whole list or one per image -- 0 float32, 1 uint8 scaled by 1/255 before the resize (the
+    image_file / images_dir sources), 2 uint8 divided by 255 after it (the tfrecords source).
+    out: a 1-D uint8 array to pack into (e.g. a view of pinned memory); blob_u8 is then its used prefix."""
+    images = list(images)
+    modes = _image_modes(images, mode)
+    offsets, total = _blob_offsets(images)
+    if out is None:
+        out = np.empty(total, np.uint8)
+    elif not isinstance(out, np.ndarray) or out.dtype != np.uint8 or out.ndim != 1 or not out.flags.c_contiguous:
+        raise Y3Error("pack_images: out must be a contiguous 1-D uint8 array")
+    elif out.size < total:
+        raise Y3Error(f"pack_images: out holds {out.size} bytes, the images need {total}")
+    descs = np.zeros(len(images), IMAGE_DESC_DTYPE)
+    for i, (im, m, off) in enumerate(zip(images, modes, offsets)):
+        np.copyto(out[off:off + im.nbytes].view(im.dtype).reshape(im.shape), im)
+        descs[i] = (off, im.shape[0], im.shape[1], im.shape[2], m)
+    return out[:total], descs
+
+
+def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Tensor, first_slot: int = 0):
+    """The pixel blob of pack_images on the GPU (1-D uint8) -> batch[first_slot + i] for image i, one launch per 64
+    images (y3_preprocess_batch); every slot has the bits preprocess_image gives for the same image."""
+    _need_cuda(blob_dev, batch)
+    if blob_dev.dtype != torch.uint8 or blob_dev.dim() != 1:
+        raise Y3Error("blob_dev must be a 1-D uint8 tensor")
+    if not isinstance(descs, np.ndarray) or descs.dtype != IMAGE_DESC_DTYPE or descs.ndim != 1:
+        raise Y3Error("descs must be the descriptor array of pack_images")
+    if batch.dtype != torch.float32 or batch.dim() != 4 or batch.shape[1] != batch.shape[2] or batch.shape[3] != 3:
+        raise Y3Error("batch must be float32 [B,S,S,3]")
+    if not (0 <= first_slot and first_slot + len(descs) <= batch.shape[0]):
+        raise Y3Error(f"slots {first_slot}..{first_slot + len(descs) - 1} are outside the batch of {batch.shape[0]}")
+    d = np.ascontiguousarray(descs)
+    check(_lib.load().y3_preprocess_batch(_dev(blob_dev), blob_dev.numel(), d.ctypes.data_as(C.POINTER(_lib.ImageDesc)),
+                                          len(d), _dev(batch), int(first_slot), batch.shape[1], _lib.stream_ptr()),
+          "y3_preprocess_batch")
+    return batch
+
+
+class StagedBatch:
+    """What InputStage.submit returns: `batch` ([n,S,S,3] fp32 on the GPU) holds the images once a stream has waited on
+    the event `ready`; hand it back with InputStage.release when the consumer's work on it is enqueued."""
+
+    def __init__(self, slot, batch, ready):
+        self.slot, self.batch, self.ready = slot, batch, ready
+
+
+class _StageSlot:
+    def __init__(self, image_size, max_batch, max_blob_bytes, device):
+        self.pinned = torch.empty(max_blob_bytes, dtype=torch.uint8, pin_memory=True)
+        self.pinned_np = self.pinned.numpy()
+        self.blob_dev = torch.empty(max_blob_bytes, dtype=torch.uint8, device=device)
+        self.batch = torch.empty((max_batch, image_size, image_size, 3), dtype=torch.float32, device=device)
+        self.ready = torch.cuda.Event()      # copy stream: pixels copied and resized into `batch`
+        self.released = torch.cuda.Event()   # consumer stream: `batch` has been read
+        self.state = "free"                  # free -> held (submit) -> released (release) -> held ...
+
+
+class InputStage:
+    """Host frames -> device batches, overlapped with the consumer: a ring of `depth` slots, each a pinned host blob, a
+    device blob and a device batch [max_batch,S,S,3], fed by one copy stream.
+    submit(images, mode) packs the list into the next slot's pinned blob and enqueues, on the copy stream, one
+    host-to-device copy and y3_preprocess_batch; release(handle) tells the stage that the consumer's reads are enqueued.
+    Every wait is on an event: the host waits for `ready` of the slot's previous use before it overwrites the pinned
+    blob, the copy stream waits for `released` before it overwrites the device buffers.  Nothing synchronises the device."""
+
+    def __init__(self, image_size: int, max_batch: int, max_blob_bytes: int, depth: int = 2):
+        _lib.require_gpu()
+        if image_size < 1 or max_batch < 1 or max_blob_bytes < 1 or depth < 1:
+            raise Y3Error("InputStage: image_size, max_batch, max_blob_bytes and depth must be at least 1")
+        self.image_size, self.max_batch, self.depth = int(image_size), int(max_batch), int(depth)
+        self.device = torch.device("cuda", torch.cuda.current_device())
+        self.stream = torch.cuda.Stream(self.device)
+        self.slots = [_StageSlot(self.image_size, self.max_batch, int(max_blob_bytes), self.device) for _ in range(self.depth)]
+        for s in self.slots:     # used on the copy stream for as long as the stage lives
+            s.blob_dev.record_stream(self.stream)
+            s.batch.record_stream(self.stream)
+        self._next = 0
+
+    def submit(self, images, mode) -> StagedBatch:
+        images = list(images)
+        if not 1 <= len(images) <= self.max_batch:
+            raise Y3Error(f"InputStage.submit: {len(images)} images, the stage holds 1..{self.max_batch}")
+        slot = self.slots[self._next]
+        if slot.state == "held":
+            raise Y3Error(f"InputStage.submit: all {self.depth} slots are in use; release() the oldest batch first")
+        if slot.state == "released":
+            slot.ready.synchronize()     # the slot's earlier copy has left the pinned blob
+        blob, descs = pack_images(images, mode, out=slot.pinned_np)
+        n = blob.size
+        with torch.cuda.stream(self.stream):
+            if slot.state == "released":
+                self.stream.wait_event(slot.released)
+            slot.blob_dev[:n].copy_(slot.pinned[:n], non_blocking=True)
+            preprocess_batch(slot.blob_dev, descs, slot.batch, 0)
+            slot.ready.record(self.stream)
+        slot.state = "held"
+        self._next = (self._next + 1) % self.depth
+        return StagedBatch(slot, slot.batch[:len(images)], slot.ready)
+
+    def release(self, handle: StagedBatch):
+        """Call on the consumer's stream after its last use of handle.batch has been enqueued."""
+        if handle.slot.state != "held" or handle.ready is not handle.slot.ready:
+            raise Y3Error("InputStage.release: not a batch in flight")
+        handle.slot.released.record(torch.cuda.current_stream())
+        handle.slot.state = "released"
 
 
 _ws_cache: Dict[tuple, torch.Tensor] = {}

@@ -210,14 +210,26 @@ y3_status y3_net_profile_convs(y3_net *net, const float *images_dev, int batch, 
  * float32 (is_uint8=0); channels 3 or 4 (alpha dropped).  is_uint8=2 is the tfrecords source's order of operations
  * (reference: core/load_tfrecords.py:46-48): uint8 taken as 0..255, resized, then divided by 255.  Writes the bilinear (half-pixel centres, no antialias)
  * resize to image_size x image_size into batch_dev[slot] of an NHWC fp32 batch [*,image_size,image_size,3].
+ *
+ * Y3_IMAGE_LETTERBOX, OR-ed into is_uint8 (and into y3_image_desc.mode below), keeps the aspect ratio instead: the image is
+ * resized to sh x sw and centred on a zero canvas (reference: core/utils.py:17-28, resize_image = tf.image.resize(
+ * preserve_aspect_ratio=True) + pad_to_bounding_box).  The geometry {sh, sw, top, left} is, in fp32,
+ *   scale = min((float)S / (float)h, (float)S / (float)w)
+ *   sh = max(1, (int)nearbyintf(scale * (float)h)), sw = max(1, (int)nearbyintf(scale * (float)w))   (round half to even)
+ *   top = (S - sh) / 2, left = (S - sw) / 2                                                           (floor)
+ * A pixel inside [top, top + sh) x [left, left + sw) is the bilinear sample of a resize to sh x sw; every other pixel of
+ * the slot is written as 0.0f.  A geometry that does not fit the canvas is Y3_ERR_INVALID (pad_to_bounding_box raises).
+ * The valid values of is_uint8 / mode are 0, 1, 2, each with or without the flag.
  * ---------------------------------------------------------------------------------------- */
+#define Y3_IMAGE_LETTERBOX 0x100
 y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, int width, int channels,
                               float *batch_dev, int slot, int image_size, void *stream);
 
 /* The same stage for a batch of unlike images in one launch per 64 images (no reference counterpart: the reference resizes
  * image by image).  All images lie in ONE device blob `pixels_dev` of `pixels_bytes` bytes; image i starts `offset` bytes into
  * it, is [height,width,channels] (channels 3 or 4, alpha dropped) and has `mode` with the meaning of is_uint8 above: 0 float32
- * (offset and pixels_dev 4-byte aligned), 1 uint8 * 1/255 before the resize, 2 uint8 divided by 255 after it.  Image i is
+ * (offset and pixels_dev 4-byte aligned), 1 uint8 * 1/255 before the resize, 2 uint8 divided by 255 after it, each optionally
+ * OR-ed with Y3_IMAGE_LETTERBOX (per image: one batch may mix stretched and letterboxed images).  Image i is
  * written to batch_dev[first_slot + i]; every value is bit-identical to the per-image call.  descs_host is read during the call (the
  * descriptors travel in the kernel arguments), so the caller may reuse it at once.  All arguments are checked on the host
  * before anything is enqueued (Y3_ERR_INVALID names the index of the bad image); the call only enqueues on `stream`: it does
@@ -225,6 +237,12 @@ y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, i
 typedef struct y3_image_desc { uint64_t offset; int32_t height, width, channels, mode; } y3_image_desc;
 y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
                               float *batch_dev, int first_slot, int image_size, void *stream);
+
+/* The letterbox geometry of a batch, on the host (no HIP call): geoms_out_host[n_images][4] = {sh, sw, top, left} by the
+ * formula above, from height / width / mode of each descriptor (offset and channels are not read); an image without
+ * Y3_IMAGE_LETTERBOX gets {image_size, image_size, 0, 0}.  y3_preprocess_batch and y3_preprocess_image compute their
+ * geometries with the same routine.  One call per batch. */
+y3_status y3_letterbox_geometry(const y3_image_desc *descs_host, int n_images, int image_size, int32_t *geoms_out_host);
 
 /* ------------------------------------------------------------------------------------------
  * yolo_decode   (reference: core/yolo_decode_layer.py:15-36)
@@ -285,6 +303,20 @@ y3_status y3_net_forward_decode(y3_net *net, const float *images_dev, int batch,
 y3_status y3_net_detect(y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
                         float iou_threshold, float score_threshold, void *packed_dev, int32_t *num_valid_dev,
                         void *stream);
+
+/* Packed detections of letterboxed images -> coordinates of the source frames, in place (no reference counterpart: the
+ * reference leaves its boxes on the padded canvas).  packed_dev [batch,max_boxes,7] and num_valid_dev [batch] as written by
+ * y3_net_detect / y3_pack_detections; geoms_host [batch][4] = {sh, sw, top, left} as y3_letterbox_geometry gives them, read
+ * during the call (they travel in the kernel arguments, 64 images per launch).  For every row r < num_valid[b], in fp32,
+ * each operation rounded on its own:
+ *   xmin' = (xmin * (float)S - (float)left) / (float)sw      xmax' likewise
+ *   ymin' = (ymin * (float)S - (float)top) / (float)sh       ymax' likewise
+ * Boxes are not clipped (the reference never clips).  Score, class and index words, rows >= num_valid, and every row of an
+ * image whose geometry is {S, S, 0, 0} are not touched.  The geometries (1 <= sh, sw; 0 <= top, left; top + sh <= S,
+ * left + sw <= S) and max_boxes in [1,1024] are checked on the host before anything is enqueued (Y3_ERR_INVALID names the
+ * bad image); the call only enqueues on `stream` -- no allocation, query or synchronise -- and can be captured. */
+y3_status y3_unletterbox_detections(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                    int max_boxes, int image_size, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Multi-GPU exchange (no reference counterpart: the reference is single-device).

@@ -18,6 +18,9 @@ Every shape is warmed up; a timed window ends in a synchronise and lasts about -
   python tools/time_input_stage.py --summarize DIR [--out profiles/input_stage_kernel_stats.txt]
   rocprofv3 --kernel-trace --memory-copy-trace -d DIR2 -o run --output-format csv -- python tools/time_input_stage.py --trace-pipelined
   python tools/time_input_stage.py --summarize-trace DIR2 [--out profiles/input_stage_pipeline_trace.txt]
+
+--letterbox (with any of the above): the frames keep their aspect ratio (zero padding, Y3_IMAGE_LETTERBOX) and the detections
+come back in frame coordinates; --kernels-only then also runs unletterbox_kernel on 64 x 100 valid rows per repetition.
 """
 import argparse
 import csv
@@ -68,31 +71,39 @@ def run_config(dtype, B, a, anchors, program, weights):
     out = {}
     for kind in ("640x480", "ragged"):
         imgs = frames(kind, B, a.seed)
-        blob, descs = runtime.pack_images(imgs, 1)
+        lb = a.letterbox
+        blob, descs = runtime.pack_images(imgs, 1, letterbox=lb)
+        geoms = runtime.letterbox_geometries(descs, S)
         resident_batch = torch.empty((B, S, S, 3), device="cuda")
         runtime.preprocess_batch(torch.from_numpy(blob).cuda(), descs, resident_batch)
 
+        def detect(batch):
+            packed, nv = net.detect(batch, anchors, 100, 0.5, 0.1)
+            if lb:
+                runtime.unletterbox_detections(packed, nv, geoms, S)
+            return packed, nv
+
         def resident(k):
             for _ in range(k):
-                net.detect(resident_batch, anchors, 100, 0.5, 0.1)
+                detect(resident_batch)
 
         def per_image(k):
             for _ in range(k):
                 batch = torch.empty((B, S, S, 3), device="cuda")
                 for slot, u8 in enumerate(imgs):
-                    runtime.preprocess_image(torch.from_numpy(u8).cuda(), batch, slot)
-                packed, nv = net.detect(batch, anchors, 100, 0.5, 0.1)
+                    runtime.preprocess_image(torch.from_numpy(u8).cuda(), batch, slot, letterbox=lb)
+                packed, nv = detect(batch)
                 packed.cpu().numpy(), nv.cpu().numpy()
 
         def pipelined(k):
-            for _ in net.detect_stream([imgs] * k, anchors, 100, 0.5, 0.1, mode=1, depth=2):
+            for _ in net.detect_stream([imgs] * k, anchors, 100, 0.5, 0.1, mode=1, depth=2, letterbox=lb):
                 pass
 
         routes = {"resident": resident, "per_image": per_image, "pipelined": pipelined}
         # the three routes must agree before any of them is timed
-        ref = net.detect(resident_batch, anchors, 100, 0.5, 0.1)
+        ref = detect(resident_batch)
         ref = (ref[0].cpu().numpy(), ref[1].cpu().numpy())
-        got = list(net.detect_stream([imgs], anchors, 100, 0.5, 0.1))[0]
+        got = list(net.detect_stream([imgs], anchors, 100, 0.5, 0.1, letterbox=lb))[0]
         assert np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]), "pipelined route differs from the resident one"
         per_window = {}
         for name, fn in routes.items():          # warm-up, then size the window from a short timing
@@ -106,10 +117,15 @@ def run_config(dtype, B, a, anchors, program, weights):
                 rates[name].append(k * B / timed(routes[name], k))
         t0 = time.perf_counter()
         for _ in range(5):
-            runtime.pack_images(imgs, 1, out=blob)
+            runtime.pack_images(imgs, 1, out=blob, letterbox=lb)
         pack_ms = (time.perf_counter() - t0) / 5 * 1e3
         res = {"images_per_batch": B, "source_mbytes_per_batch": round(blob.size / 1e6, 2), "batches_per_window": per_window,
                "host_pack_ms_per_batch": round(pack_ms, 2), "host_pack_images_per_s": round(B / pack_ms * 1e3, 1)}
+        if lb:      # the one host call the letterbox route adds per batch, next to the packing it follows
+            t0 = time.perf_counter()
+            for _ in range(200):
+                runtime.letterbox_geometries(descs, S)
+            res["host_geometry_ms_per_batch"] = round((time.perf_counter() - t0) / 200 * 1e3, 4)
         for name, v in rates.items():
             res[name] = {"images_per_s_median": round(float(np.median(v)), 1), "spread": round(float(max(v) - min(v)), 1),
                          "rounds": [round(float(x), 1) for x in v]}
@@ -118,10 +134,11 @@ def run_config(dtype, B, a, anchors, program, weights):
         res["pipelined_minus_per_image_over_per_image_spread"] = round(
             (res["pipelined"]["images_per_s_median"] - res["per_image"]["images_per_s_median"]) / max(res["per_image"]["spread"], 1e-9), 1)
         out[kind] = res
-        print(f"{dtype} {B} x {S}^2, {kind} frames (decode excluded): " + ", ".join(
+        print(f"{dtype} {B} x {S}^2, {kind} frames{' letterboxed' if lb else ''} (decode excluded): " + ", ".join(
             f"{n} {res[n]['images_per_s_median']:.0f} img/s (spread {res[n]['spread']:.0f})" for n in routes) +
             f"; pipelined / per-image {res['pipelined_over_per_image']:.2f}, pipelined / resident {res['pipelined_over_resident']:.2f}; "
-            f"host packing alone {res['host_pack_images_per_s']:.0f} img/s", flush=True)
+            f"host packing alone {res['host_pack_images_per_s']:.0f} img/s" +
+            (f", geometry call {res['host_geometry_ms_per_batch'] * 1e3:.1f} us per batch" if lb else ""), flush=True)
     return out
 
 
@@ -131,17 +148,27 @@ def kernels_only(a):
     from yolo_v3_tf2_amd import runtime
     for kind in ("640x480", "ragged"):
         imgs = frames(kind, 64, a.seed)
-        blob, descs = runtime.pack_images(imgs, 1)
+        blob, descs = runtime.pack_images(imgs, 1, letterbox=a.letterbox)
         blob_dev = torch.from_numpy(blob).cuda()
         singles = [torch.from_numpy(u8).cuda() for u8 in imgs]
         batch = torch.empty((64, S, S, 3), device="cuda")
+        if a.letterbox:     # 64 x 100 valid rows of boxes inside the unit square, the shape y3_net_detect hands over
+            geoms = runtime.letterbox_geometries(descs, S)
+            rows = np.zeros((64, 100, 7), np.int32)
+            rows[..., :5] = np.random.default_rng(a.seed).random((64, 100, 5), dtype=np.float32).view(np.int32)
+            rows_dev, packed = torch.from_numpy(rows).cuda(), torch.empty((64, 100, 7), dtype=torch.int32, device="cuda")
+            nv = torch.full((64,), 100, dtype=torch.int32, device="cuda")
         for _ in range(a.kernel_reps + 2):      # the first two repetitions are warm-up; the summary drops them
             runtime.preprocess_batch(blob_dev, descs, batch)
             torch.cuda.synchronize()
             for slot, t in enumerate(singles):
-                runtime.preprocess_image(t, batch, slot)
+                runtime.preprocess_image(t, batch, slot, letterbox=a.letterbox)
             torch.cuda.synchronize()
-    print("kernels-only run done (image decode excluded; frames resident on the device)")
+            if a.letterbox:
+                packed.copy_(rows_dev)
+                runtime.unletterbox_detections(packed, nv, geoms, S)
+                torch.cuda.synchronize()
+    print(f"kernels-only run done{' (letterboxed)' if a.letterbox else ''} (image decode excluded; frames resident on the device)")
 
 
 def trace_pipelined(a, anchors, program, weights):
@@ -151,7 +178,7 @@ def trace_pipelined(a, anchors, program, weights):
     net.load_weights(weights)
     net.plan(128, S, _lib.Y3_DTYPE_BF16)
     imgs = frames("ragged", 128, a.seed)
-    for _ in net.detect_stream([imgs] * 24, anchors, 100, 0.5, 0.1):
+    for _ in net.detect_stream([imgs] * 24, anchors, 100, 0.5, 0.1, letterbox=a.letterbox):
         pass
     print("pipelined trace run done: 24 batches of 128 ragged frames, bf16 (image decode excluded)")
 
@@ -206,10 +233,12 @@ def summarize(a):
                   for r in csv.DictReader(open(files[0])))
     batch = [d for _, d, n in rows if "preprocess_batch_kernel" in n]
     single = [d for _, d, n in rows if "resize_kernel" in n]
+    unlb = [d for _, d, n in rows if "unletterbox_kernel" in n]
     reps = a.kernel_reps + 2
     assert len(batch) == 2 * reps and len(single) == 2 * reps * 64, (len(batch), len(single))
     lines = ["# rocprofv3 --kernel-trace --stats of `tools/time_input_stage.py --kernels-only`: 64 uint8 frames -> 64 x 416^2 x 3 fp32,",
-             "# frames resident on the device, image decode excluded.  Algorithmic bytes = source bytes read + 416*416*12 written per image.",
+             "# frames resident on the device, image decode excluded.  Algorithmic bytes = source bytes read + 416*416*12 written per image." +
+             ("  LETTERBOXED (--letterbox)." if a.letterbox else ""),
              f"# HBM peak {HBM_PEAK_TBS} TB/s (specification), {HBM_MEASURED_TBS} TB/s measured with a float4 copy (MI355X_MICROARCH.md).",
              f"# median over {a.kernel_reps} repetitions after 2 warm-up repetitions",
              f"{'frames':<10s} {'kernel':<34s} {'launches':>8s} {'us per 64 images':>17s} {'us per image':>13s} {'GB/s':>9s} {'% of 8 TB/s':>12s}"]
@@ -222,6 +251,10 @@ def summarize(a):
             gbs = nbytes / (us * 1e-6) / 1e9
             lines.append(f"{kind:<10s} {name:<34s} {launches:>8d} {us:17.2f} {us / 64:13.3f} {gbs:9.1f} {gbs / (HBM_PEAK_TBS * 1e3) * 100:12.2f}")
         lines.append(f"# {kind}: {nbytes / 1e6:.2f} MB algorithmic; batch kernel time / summed per-image kernel time = {float(np.median(b) / np.median(s)):.3f}")
+        if a.letterbox:
+            assert len(unlb) == 2 * reps, len(unlb)
+            u = np.array(unlb[i * reps:(i + 1) * reps][2:], np.float64)
+            lines.append(f"{kind:<10s} {'unletterbox_kernel (64 x 100 rows)':<34s} {1:>8d} {float(np.median(u)) / 1e3:17.2f}")
     lines.append("# kernel time only: the 64 launches of the per-image route also pay 64 launch gaps, which this table leaves out")
     text = "\n".join(lines) + "\n"
     print(text, end="")
@@ -240,6 +273,7 @@ def main():
     ap.add_argument("--kernels-only", action="store_true")
     ap.add_argument("--kernel-reps", type=int, default=10)
     ap.add_argument("--trace-pipelined", action="store_true")
+    ap.add_argument("--letterbox", action="store_true", help="aspect-preserving resize + zero pad, detections in frame coordinates")
     ap.add_argument("--summarize-trace", default="", help="directory of a rocprofv3 kernel + memory-copy trace of --trace-pipelined")
     ap.add_argument("--summarize", default="", help="directory of a rocprofv3 --kernel-trace run of --kernels-only")
     a = ap.parse_args()
@@ -261,7 +295,7 @@ def main():
     if a.trace_pipelined:
         return trace_pipelined(a, anchors, program, weights)
     doc = {"what": "images/s from decoded uint8 frames in host memory to packed detections on the host; image decode excluded",
-           "image_size": S, "rounds": a.rounds, "window_s": a.window, "seed": a.seed,
+           "image_size": S, "rounds": a.rounds, "window_s": a.window, "seed": a.seed, **({"letterbox": True} if a.letterbox else {}),
            "routes": {"resident": "Net.detect on a batch already on the device", "per_image": "per image .cuda() + preprocess_image, Net.detect, blocking read-back",
                       "pipelined": "Net.detect_stream (depth 2)"}}
     for dtype, B in CONFIGS:

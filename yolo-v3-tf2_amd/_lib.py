@@ -120,6 +120,8 @@ SYMBOLS = {
     "y3_net_profile_convs": (_i, [_vp, _vp, _i, _fp, _i, _vp]),
     "y3_preprocess_image": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
     "y3_preprocess_batch": (_i, [_vp, _sz, C.POINTER(ImageDesc), _i, _vp, _i, _i, _vp]),
+    "y3_letterbox_geometry": (_i, [C.POINTER(ImageDesc), _i, _i, C.POINTER(C.c_int32)]),
+    "y3_unletterbox_detections": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp]),
     "y3_yolo_decode": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_yolo_decode_scores": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_class_scores": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
@@ -136,6 +138,7 @@ SYMBOLS = {
     "y3_allgather_results": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
 }
 Y3_COMM_ID_BYTES = 128
+Y3_IMAGE_LETTERBOX = 0x100   # include/y3.h: OR-ed into y3_image_desc.mode / is_uint8
 Y3_ERR_INVALID, Y3_ERR_HIP, Y3_ERR_OOM, Y3_ERR_STATE, Y3_ERR_NODEVICE, Y3_ERR_COMM, Y3_ERR_INTERNAL = -1, -2, -3, -4, -5, -6, -7   # include/y3.h
 
 _lib = None

@@ -46,24 +46,54 @@ def resize_bilinear(img, out_h, out_w):
     return (top + (bot - top) * yfr[:, None, None]).astype(np.float32)
 
 
+def letterbox_geometry(h, w, target_height, target_width):
+    """Where resize_image puts an h x w source on a (target_height, target_width) canvas: int32 [..., 4] =
+    (sh, sw, top, left), the scaled size and its top-left corner.  Every operation in float32, as tf.image.resize(
+    preserve_aspect_ratio=True) does it: scale = min(th / h, tw / w), sh = max(1, round-half-even(scale * h)), likewise
+    sw; the padding is centred with the odd pixel after (floor).  The same formula in float64 gives another size for
+    some sources, so the precision is part of the definition (the library: y3_letterbox_geometry).  h, w: scalars or
+    arrays of one shape."""
+    h, w = np.asarray(h), np.asarray(w)
+    fh, fw = h.astype(np.float32), w.astype(np.float32)
+    scale = np.minimum(np.float32(target_height) / fh, np.float32(target_width) / fw)
+    sh = np.maximum(1, np.rint(scale * fh).astype(np.int64))
+    sw = np.maximum(1, np.rint(scale * fw).astype(np.int64))
+    top, left = (target_height - sh) // 2, (target_width - sw) // 2
+    return np.stack([sh, sw, top, left], axis=-1).astype(np.int32)
+
+
 def resize_image(img, target_height, target_width):
     """Aspect-preserving resize then centred zero padding to (target_height, target_width) -- reference
     core/utils.py:17-28 (tf.image.resize(preserve_aspect_ratio=True) + tf.image.pad_to_bounding_box).  `img` is one
-    HWC image or an NHWC batch, float32.  Scaled size = round-half-even(min(th/h, tw/w) * (h, w)), at least 1."""
+    HWC image or an NHWC batch, float32.  Scaled size and position: letterbox_geometry."""
     img = np.asarray(img, np.float32)
     if img.ndim == 4:
         return np.stack([resize_image(i, target_height, target_width) for i in img])
     h, w = img.shape[0], img.shape[1]
-    scale = min(np.float32(target_height) / np.float32(h), np.float32(target_width) / np.float32(w))
-    sh = max(1, int(np.rint(scale * np.float32(h))))
-    sw = max(1, int(np.rint(scale * np.float32(w))))
+    sh, sw, top, left = (int(v) for v in letterbox_geometry(h, w, target_height, target_width))
     scaled = img if (sh, sw) == (h, w) else resize_bilinear(img, sh, sw)   # same-size bilinear is the identity
-    top, left = (target_height - sh) // 2, (target_width - sw) // 2
     if top < 0 or left < 0 or top + sh > target_height or left + sw > target_width:
         raise ValueError("resize_image: scaled image does not fit the target")   # pad_to_bounding_box raises too
     out = np.zeros((target_height, target_width, img.shape[2]), np.float32)
     out[top:top + sh, left:left + sw] = scaled
     return out
+
+
+def unletterbox_boxes(boxes, geometry, image_size):
+    """Normalised (xmin, ymin, xmax, ymax) boxes on the padded image_size^2 canvas -> normalised to the source frame
+    that letterbox_geometry placed there; boxes [..., 4] float32, geometry (sh, sw, top, left).  float32, one rounding
+    per operation: x' = (x * S - left) / sw, y' = (y * S - top) / sh; no clipping (the reference never clips boxes).
+    A geometry that is the whole canvas returns the values as they are (x * S / S is not x in float32).  Host
+    restatement of y3_unletterbox_detections."""
+    boxes = np.asarray(boxes, np.float32)
+    sh, sw, top, left = (int(v) for v in np.asarray(geometry).reshape(4))
+    S = int(image_size)
+    if (sh, sw, top, left) == (S, S, 0, 0):
+        return boxes.copy()
+    fs = np.float32(S)
+    off = np.array([left, top, left, top], np.float32)
+    div = np.array([sw, sh, sw, sh], np.float32)
+    return ((boxes * fs - off) / div).astype(np.float32)
 
 
 def load_image_rgb01(path):

@@ -10,6 +10,8 @@
 // lower = max(floor(in), 0), upper = min(ceil(in), in_size - 1), lerp = in - floor(in); interpolate along x first
 // (top, bottom) then along y; fp32, no contraction.  HBM-bound and tiny.  resize_kernel: one image per launch, one thread per
 // output pixel; preprocess_batch_kernel: up to 64 unlike images per launch, four pixels per thread.
+// Both also serve the aspect-preserving form of reference core/utils.py:17-28 (resize_image: tf.image.resize(
+// preserve_aspect_ratio=True) + pad_to_bounding_box), flag Y3_IMAGE_LETTERBOX: resize to sh x sw, centred on a zero canvas.
 #include <type_traits>
 
 #include "y3_kernels.h"
@@ -29,11 +31,24 @@ __device__ __forceinline__ float px<RawU8>(const RawU8 *p) { return (float)p->v;
 
 // One output pixel (3 floats) of the resize: the per-pixel body of both kernels below, so that the per-image and the
 // batched launch cannot drift apart.  i = oy * S + ox.
-template <typename T>
-__device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, int S, int i, float *out)
+// LB (Y3_IMAGE_LETTERBOX): the resize is to g.sh x g.sw and sits at (g.top, g.left) of the S x S canvas; a pixel outside that
+// block is 0.0f -- it is written like any other, a reused slot keeps nothing of its last image.  Inside, the same operations in
+// the same order with (sh, sw) in the place of (S, S).  LB = false compiles to what it was before the flag existed.
+template <typename T, bool LB>
+__device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, int S, LetterboxGeom g, int i,
+                                             float *out)
 {
-    const int oy = i / S, ox = i - oy * S;
-    const float sy = (float)H / (float)S, sx = (float)W / (float)S;
+    int oy = i / S, ox = i - oy * S;
+    if (LB) {
+        oy -= g.top;
+        ox -= g.left;
+        if ((unsigned)oy >= (unsigned)g.sh || (unsigned)ox >= (unsigned)g.sw) {
+            out[0] = out[1] = out[2] = 0.0f;
+            return;
+        }
+    }
+    const int OH = LB ? g.sh : S, OW = LB ? g.sw : S;
+    const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
     const float fy = ((float)oy + 0.5f) * sy - 0.5f, fx = ((float)ox + 0.5f) * sx - 0.5f;
     const float fly = floorf(fy), flx = floorf(fx);
     const int y0 = max((int)fly, 0), y1 = min((int)ceilf(fy), H - 1);
@@ -51,34 +66,35 @@ __device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, i
     }
 }
 
-template <typename T>
+template <typename T, bool LB>
 __global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, int H, int W, int pix_stride,
-                                                     float *__restrict__ dst, int S)
+                                                     float *__restrict__ dst, int S, LetterboxGeom g)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= S * S) return;
     float v[3];
-    resize_pixel<T>(src, H, W, pix_stride, S, i, v);
+    resize_pixel<T, LB>(src, H, W, pix_stride, S, g, i, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[(size_t)i * 3 + c] = v[c];
 }
 
 // A batch of unlike images in one launch: blockIdx.y is the image within the launch, blockIdx.x tiles its S*S output pixels.
-// The descriptors travel by value in the kernel arguments (PreprocessTable, 1.5 KB of the 4 KB limit): nothing extra is
-// copied, they have no lifetime to manage, and the launch can be captured into a graph.
+// The descriptors and geometries travel by value in the kernel arguments (PreprocessTable, 2.5 KB of the 4 KB limit): nothing
+// extra is copied, they have no lifetime to manage, and the launch can be captured into a graph.
 // VEC: every thread produces four consecutive pixels (12 floats) and writes them as three 16-byte stores; needs
 // S*S % 4 == 0 and a 16-byte aligned destination, which holds for every network size (S a multiple of 32).  Otherwise one
-// pixel and three scalar stores per thread.
-template <typename T, bool VEC>
+// pixel and three scalar stores per thread.  Each of the four pixels decides on its own whether it is padding: a thread may
+// straddle the edge of the letterboxed block.
+template <typename T, bool VEC, bool LB>
 __device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src, int H, int W, int pix_stride,
-                                                      float *__restrict__ dst, int S)
+                                                      float *__restrict__ dst, int S, LetterboxGeom g)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (VEC) {
         if (q * 4 >= S * S) return;
         float v[12];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) resize_pixel<T>(src, H, W, pix_stride, S, q * 4 + p, v + 3 * p);
+        for (int p = 0; p < 4; ++p) resize_pixel<T, LB>(src, H, W, pix_stride, S, g, q * 4 + p, v + 3 * p);
         float4 *o = reinterpret_cast<float4 *>(dst + (size_t)q * 12);
         o[0] = make_float4(v[0], v[1], v[2], v[3]);
         o[1] = make_float4(v[4], v[5], v[6], v[7]);
@@ -86,10 +102,22 @@ __device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src,
     } else {
         if (q >= S * S) return;
         float v[3];
-        resize_pixel<T>(src, H, W, pix_stride, S, q, v);
+        resize_pixel<T, LB>(src, H, W, pix_stride, S, g, q, v);
 #pragma unroll
         for (int c = 0; c < 3; ++c) dst[(size_t)q * 3 + c] = v[c];
     }
+}
+
+template <bool VEC, bool LB>
+__device__ __forceinline__ void preprocess_batch_modes(const unsigned char *__restrict__ src, const y3_image_desc &d, int mode,
+                                                       float *__restrict__ dst, int S, LetterboxGeom g)
+{
+    if (mode == 2)
+        preprocess_batch_body<RawU8, VEC, LB>(reinterpret_cast<const RawU8 *>(src), d.height, d.width, d.channels, dst, S, g);
+    else if (mode == 1)
+        preprocess_batch_body<unsigned char, VEC, LB>(src, d.height, d.width, d.channels, dst, S, g);
+    else
+        preprocess_batch_body<float, VEC, LB>(reinterpret_cast<const float *>(src), d.height, d.width, d.channels, dst, S, g);
 }
 
 template <bool VEC>
@@ -99,32 +127,47 @@ __global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned ch
     const y3_image_desc d = table.d[blockIdx.y];          // uniform per workgroup: scalar loads from the kernel arguments
     const unsigned char *src = pixels + d.offset;
     float *dst = batch + (size_t)blockIdx.y * S * S * 3;
-    if (d.mode == 2)                                      // one branch per workgroup, outside the pixel body
-        preprocess_batch_body<RawU8, VEC>(reinterpret_cast<const RawU8 *>(src), d.height, d.width, d.channels, dst, S);
-    else if (d.mode == 1)
-        preprocess_batch_body<unsigned char, VEC>(src, d.height, d.width, d.channels, dst, S);
+    const int mode = d.mode & ~Y3_IMAGE_LETTERBOX;
+    if (d.mode & Y3_IMAGE_LETTERBOX)                      // one branch per workgroup each, outside the pixel body
+        preprocess_batch_modes<VEC, true>(src, d, mode, dst, S, table.g[blockIdx.y]);
     else
-        preprocess_batch_body<float, VEC>(reinterpret_cast<const float *>(src), d.height, d.width, d.channels, dst, S);
+        preprocess_batch_modes<VEC, false>(src, d, mode, dst, S, LetterboxGeom{});
 }
 
-hipError_t launch_resize(const void *src, int is_u8, int H, int W, int pix_stride, float *dst, int S, hipStream_t s)
+template <typename T>
+static void launch_resize_as(bool lb, dim3 grid, hipStream_t s, const void *src, int H, int W, int pix_stride, float *dst, int S,
+                             const LetterboxGeom &g)
 {
-    dim3 grid((S * S + 255) / 256), block(256);
-    if (is_u8 == 2)
-        hipLaunchKernelGGL(resize_kernel<RawU8>, grid, block, 0, s, static_cast<const RawU8 *>(src), H, W, pix_stride, dst, S);
-    else if (is_u8)
-        hipLaunchKernelGGL(resize_kernel<unsigned char>, grid, block, 0, s, static_cast<const unsigned char *>(src), H, W,
-                           pix_stride, dst, S);
+    if (lb)
+        hipLaunchKernelGGL((resize_kernel<T, true>), grid, dim3(256), 0, s, static_cast<const T *>(src), H, W, pix_stride, dst, S, g);
     else
-        hipLaunchKernelGGL(resize_kernel<float>, grid, block, 0, s, static_cast<const float *>(src), H, W, pix_stride, dst, S);
+        hipLaunchKernelGGL((resize_kernel<T, false>), grid, dim3(256), 0, s, static_cast<const T *>(src), H, W, pix_stride, dst, S, g);
+}
+
+hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride, float *dst, int S, const LetterboxGeom &g, hipStream_t s)
+{
+    dim3 grid((S * S + 255) / 256);
+    const bool lb = (mode & Y3_IMAGE_LETTERBOX) != 0;
+    const int m = mode & ~Y3_IMAGE_LETTERBOX;
+    if (m == 2)
+        launch_resize_as<RawU8>(lb, grid, s, src, H, W, pix_stride, dst, S, g);
+    else if (m)
+        launch_resize_as<unsigned char>(lb, grid, s, src, H, W, pix_stride, dst, S, g);
+    else
+        launch_resize_as<float>(lb, grid, s, src, H, W, pix_stride, dst, S, g);
     return hipGetLastError();
 }
 
-// descs: n (1..kPreprocessTableImages) validated descriptors; dst: slot of the first image.  Vector stores when the geometry allows.
-hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, int n, float *dst, int S, hipStream_t s)
+// descs / geoms: n (1..kPreprocessTableImages) validated descriptors and their geometries; dst: slot of the first image.
+// Vector stores when the geometry allows.
+hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int S,
+                                   hipStream_t s)
 {
     PreprocessTable table{};
-    for (int i = 0; i < n; ++i) table.d[i] = descs[i];
+    for (int i = 0; i < n; ++i) {
+        table.d[i] = descs[i];
+        table.g[i] = geoms[i];
+    }
     const bool vec = ((size_t)S * S) % 4 == 0 && ((uintptr_t)dst & 15) == 0;
     const int per_block = vec ? 1024 : 256;
     dim3 grid((unsigned)(((size_t)S * S + per_block - 1) / per_block), (unsigned)n), block(256);

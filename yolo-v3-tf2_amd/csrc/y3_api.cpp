@@ -59,6 +59,19 @@ bool test_fail_alloc() noexcept
     const char *e = getenv("Y3_TEST_FAIL_ALLOC");
     return e && e[0] == '1';
 }
+
+// include/y3.h, Y3_IMAGE_LETTERBOX.  Every operation in fp32 (this file is compiled with -ffp-contract=off), nearbyintf in the
+// default rounding mode (half to even): bit for bit what core/utils.letterbox_geometry computes with np.float32 and np.rint.
+LetterboxGeom letterbox_geom(int h, int w, int S)
+{
+    const float scale = std::min((float)S / (float)h, (float)S / (float)w);
+    LetterboxGeom g;
+    g.sh = std::max(1, (int)nearbyintf(scale * (float)h));
+    g.sw = std::max(1, (int)nearbyintf(scale * (float)w));
+    g.top = (S - g.sh) >> 1;       // floor, also where the difference is negative (refused by letterbox_geom_fits)
+    g.left = (S - g.sw) >> 1;
+    return g;
+}
 }  // namespace y3
 
 #define Y3_CATCH(who) catch (...) { return y3::on_exception(who); }
@@ -1404,14 +1417,28 @@ try {
 Y3_CATCH("y3_net_read_tensor")
 
 // ------------------------------------------------------------------------------------------ image input
+namespace {
+// is_uint8 / y3_image_desc.mode: 0, 1 or 2, with or without Y3_IMAGE_LETTERBOX
+bool image_mode_ok(int mode) { return (mode & ~Y3_IMAGE_LETTERBOX) >= 0 && (mode & ~Y3_IMAGE_LETTERBOX) <= 2; }
+// the geometry of one image: the whole canvas without the flag
+y3::LetterboxGeom image_geom(int mode, int h, int w, int S)
+{
+    return (mode & Y3_IMAGE_LETTERBOX) ? y3::letterbox_geom(h, w, S) : y3::LetterboxGeom{S, S, 0, 0};
+}
+}  // namespace
+
 y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, int width, int channels,
                               float *batch_dev, int slot, int image_size, void *stream)
 try {
     if (!image_dev || !batch_dev || height <= 0 || width <= 0 || channels < 3 || channels > 4 || slot < 0 ||
-        image_size <= 0 || is_uint8 < 0 || is_uint8 > 2 || (is_uint8 == 0 && ((uintptr_t)image_dev & 3)))
+        image_size <= 0 || !image_mode_ok(is_uint8) || ((is_uint8 & ~Y3_IMAGE_LETTERBOX) == 0 && ((uintptr_t)image_dev & 3)))
         return fail(Y3_ERR_INVALID, "y3_preprocess_image: bad argument (channels must be 3 or 4)");
+    const y3::LetterboxGeom g = image_geom(is_uint8, height, width, image_size);
+    if (!y3::letterbox_geom_fits(g, image_size))
+        return fail(Y3_ERR_INVALID, "y3_preprocess_image: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", height, width,
+                    g.sh, g.sw, g.top, g.left, image_size, image_size);
     float *dst = batch_dev + (size_t)slot * image_size * image_size * 3;
-    hipError_t e = y3::launch_resize(image_dev, is_uint8, height, width, channels, dst, image_size, (hipStream_t)stream);
+    hipError_t e = y3::launch_resize(image_dev, is_uint8, height, width, channels, dst, image_size, g, (hipStream_t)stream);
     if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_preprocess_image launch: %s", hipGetErrorString(e));
     return Y3_OK;
 }
@@ -1427,30 +1454,86 @@ try {
         const y3_image_desc &d = descs_host[i];
         if (d.channels < 3 || d.channels > 4)
             return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: channels must be 3 or 4 (got %d)", i, d.channels);
-        if (d.mode < 0 || d.mode > 2)
-            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: mode must be 0, 1 or 2 (got %d)", i, d.mode);
+        if (!image_mode_ok(d.mode))
+            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", i, d.mode);
         if (d.height < 1 || d.width < 1)
             return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: height and width must be at least 1 (got %d x %d)", i,
                         d.height, d.width);
-        if (d.mode == 0 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
+        const bool f32 = (d.mode & ~Y3_IMAGE_LETTERBOX) == 0;
+        if (f32 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
             return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: float32 pixels must be 4-byte aligned (offset %llu)", i,
                         (unsigned long long)d.offset);
         // height, width < 2^31 and channels * elemsize <= 16: the product stays below 2^66, so take it in 128 bits
-        const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (d.mode == 0 ? 4 : 1));
+        const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (f32 ? 4 : 1));
         if ((unsigned __int128)d.offset + bytes > (unsigned __int128)pixels_bytes)
             return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", i,
                         d.height, d.width, d.channels, (unsigned long long)d.offset, pixels_bytes);
+        const y3::LetterboxGeom g = image_geom(d.mode, d.height, d.width, image_size);
+        if (!y3::letterbox_geom_fits(g, image_size))
+            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", i,
+                        d.height, d.width, g.sh, g.sw, g.top, g.left, image_size, image_size);
     }
     const size_t per_image = (size_t)image_size * image_size * 3;
     for (int i0 = 0; i0 < n_images; i0 += y3::kPreprocessTableImages) {
         const int n = std::min(y3::kPreprocessTableImages, n_images - i0);
-        hipError_t e = y3::launch_preprocess_batch(pixels_dev, descs_host + i0, n, batch_dev + ((size_t)first_slot + i0) * per_image,
+        y3::LetterboxGeom geoms[y3::kPreprocessTableImages];     // on the stack: the call allocates nothing
+        for (int i = 0; i < n; ++i) geoms[i] = image_geom(descs_host[i0 + i].mode, descs_host[i0 + i].height, descs_host[i0 + i].width, image_size);
+        hipError_t e = y3::launch_preprocess_batch(pixels_dev, descs_host + i0, geoms, n, batch_dev + ((size_t)first_slot + i0) * per_image,
                                                    image_size, (hipStream_t)stream);
         if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_preprocess_batch launch: %s", hipGetErrorString(e));
     }
     return Y3_OK;
 }
 Y3_CATCH("y3_preprocess_batch")
+
+y3_status y3_letterbox_geometry(const y3_image_desc *descs_host, int n_images, int image_size, int32_t *geoms_out_host)
+try {
+    if (!descs_host || !geoms_out_host || n_images < 1 || image_size <= 0)
+        return fail(Y3_ERR_INVALID, "y3_letterbox_geometry: bad argument (null pointer, n_images < 1 or image_size <= 0)");
+    for (int i = 0; i < n_images; ++i) {
+        const y3_image_desc &d = descs_host[i];
+        if (!image_mode_ok(d.mode))
+            return fail(Y3_ERR_INVALID, "y3_letterbox_geometry: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", i, d.mode);
+        if (d.height < 1 || d.width < 1)
+            return fail(Y3_ERR_INVALID, "y3_letterbox_geometry: image %d: height and width must be at least 1 (got %d x %d)", i,
+                        d.height, d.width);
+    }
+    static_assert(sizeof(y3::LetterboxGeom) == 4 * sizeof(int32_t), "a geometry is four int32");
+    for (int i = 0; i < n_images; ++i) {
+        const y3::LetterboxGeom g = image_geom(descs_host[i].mode, descs_host[i].height, descs_host[i].width, image_size);
+        memcpy(geoms_out_host + (size_t)i * 4, &g, sizeof(g));
+    }
+    return Y3_OK;
+}
+Y3_CATCH("y3_letterbox_geometry")
+
+y3_status y3_unletterbox_detections(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                    int max_boxes, int image_size, void *stream)
+try {
+    if (!packed_dev || !num_valid_dev || !geoms_host || batch < 1 || image_size <= 0)
+        return fail(Y3_ERR_INVALID, "y3_unletterbox_detections: bad argument (null pointer, batch < 1 or image_size <= 0)");
+    if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES)
+        return fail(Y3_ERR_INVALID, "y3_unletterbox_detections: max_boxes must be in [1,%d]", Y3_MAX_OUTPUT_BOXES);
+    // every check before the first launch: the rows are rewritten in place
+    for (int i = 0; i < batch; ++i) {
+        y3::LetterboxGeom g;
+        memcpy(&g, geoms_host + (size_t)i * 4, sizeof(g));
+        if (!y3::letterbox_geom_fits(g, image_size))
+            return fail(Y3_ERR_INVALID, "y3_unletterbox_detections: image %d: geometry %d x %d at (%d, %d) does not lie inside %d x %d", i,
+                        g.sh, g.sw, g.top, g.left, image_size, image_size);
+    }
+    unsigned *packed = static_cast<unsigned *>(packed_dev);
+    for (int i0 = 0; i0 < batch; i0 += y3::kUnletterboxTableImages) {
+        const int n = std::min(y3::kUnletterboxTableImages, batch - i0);
+        y3::LetterboxGeom geoms[y3::kUnletterboxTableImages];
+        memcpy(geoms, geoms_host + (size_t)i0 * 4, (size_t)n * sizeof(y3::LetterboxGeom));
+        hipError_t e = y3::launch_unletterbox(packed + (size_t)i0 * max_boxes * 7, num_valid_dev + i0, geoms, n, max_boxes, image_size,
+                                              (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_unletterbox_detections launch: %s", hipGetErrorString(e));
+    }
+    return Y3_OK;
+}
+Y3_CATCH("y3_unletterbox_detections")
 
 // ------------------------------------------------------------------------------------------ TFRecord checksum
 uint32_t y3_crc32c(const void *data_host, size_t nbytes)

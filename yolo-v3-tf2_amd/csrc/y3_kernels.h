@@ -142,12 +142,30 @@ hipError_t launch_decode(const DecodeArgs &a, float *bboxes, float *conf, float 
 hipError_t launch_class_scores(const float *conf, const float *probs, size_t n, int nc, int64_t *cls,
                                float *scores, hipStream_t s);
 
-hipError_t launch_resize(const void *src, int is_u8, int H, int W, int pix_stride, float *dst, int S, hipStream_t s);
-// The image descriptors of one preprocess_batch_kernel launch, passed by value in the kernel arguments (the limit is 4 KB).
+// Letterbox geometry (include/y3.h, Y3_IMAGE_LETTERBOX): the aspect-preserving resize is to sh x sw, placed at (top, left) of
+// the S x S canvas.  Layout of the int32[4] rows of y3_letterbox_geometry / y3_unletterbox_detections.
+struct LetterboxGeom { int32_t sh, sw, top, left; };
+// The one definition of the geometry: fp32, round half to even (reference core/utils.py:17-28 through tf.image.resize(
+// preserve_aspect_ratio=True)); host only.  The same formula in double gives another (sh, sw) for some sizes.
+LetterboxGeom letterbox_geom(int h, int w, int S);
+inline bool letterbox_geom_fits(const LetterboxGeom &g, int S)
+{
+    return g.sh >= 1 && g.sw >= 1 && g.top >= 0 && g.left >= 0 && g.top <= S - g.sh && g.left <= S - g.sw;
+}
+
+// mode: 0, 1, 2 (y3_preprocess_image's is_uint8), optionally | Y3_IMAGE_LETTERBOX with the geometry g
+hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride, float *dst, int S, const LetterboxGeom &g, hipStream_t s);
+// The image descriptors and geometries of one preprocess_batch_kernel launch, passed by value in the kernel arguments (the limit is 4 KB).
 constexpr int kPreprocessTableImages = 64;
-struct PreprocessTable { y3_image_desc d[kPreprocessTableImages]; };
+struct PreprocessTable { y3_image_desc d[kPreprocessTableImages]; LetterboxGeom g[kPreprocessTableImages]; };
 static_assert(sizeof(y3_image_desc) == 24 && sizeof(PreprocessTable) + 64 <= 4096, "descriptor table must fit the kernel arguments");
-hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, int n, float *dst, int S, hipStream_t s);
+hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int S,
+                                   hipStream_t s);
+
+// The geometries of one unletterbox_kernel launch, by value in the kernel arguments like PreprocessTable.
+constexpr int kUnletterboxTableImages = 64;
+struct UnletterboxTable { LetterboxGeom g[kUnletterboxTableImages]; };
+hipError_t launch_unletterbox(void *packed, const int32_t *nv, const LetterboxGeom *geoms, int n, int M, int S, hipStream_t s);
 
 size_t nms_workspace_bytes(int B, int N);
 hipError_t launch_nms(const float *boxes, const float *scores, int B, int N, int M, float T, float S, int32_t *sel,

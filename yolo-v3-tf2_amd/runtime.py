@@ -312,13 +312,16 @@ class Net:
         return packed, nv
 
     def detect_stream(self, batches, anchors, max_boxes: int, iou_threshold: float, score_threshold: float, mode=1,
-                      depth: int = 2, max_batch: Optional[int] = None, max_blob_bytes: Optional[int] = None):
+                      depth: int = 2, max_batch: Optional[int] = None, max_blob_bytes: Optional[int] = None, letterbox=False):
         """Frames in host memory -> detections, overlapped: a generator over an iterable of image lists (each image a
         NumPy [H,W,3|4] uint8 or float32 array; `mode` as for pack_images) that yields (packed [B,max_boxes,7] int32 words,
         num_valid [B] int32) as NumPy arrays, one pair per list, in submission order; a ragged last list is allowed.
         Batch i+1 is packed, copied and resized on the InputStage's copy stream before y3_net_detect of batch i is
         enqueued on the current stream, and only the packed rows come back to the host (pinned buffers, one event per
         batch): the host waits for the result of batch i while batch i+1 is already queued behind it.
+        letterbox=True: the frames keep their aspect ratio (zero padding around them, core/utils.resize_image) and the
+        boxes of the yielded rows are normalised to the frame that was handed in, not to the padded network input:
+        y3_unletterbox_detections runs behind y3_net_detect on the same stream, before the read-back.
         The net keeps its planned image size and is re-planned at most once, for max_batch images; the stage's blobs hold
         max_blob_bytes.  Both default to the largest list of `batches`, which must then be a list or tuple."""
         if max_batch is None or max_blob_bytes is None:
@@ -356,11 +359,11 @@ class Net:
 
         it = iter(batches)
         first = next(it, None)
-        handle = stage.submit(first, mode) if first is not None else None
+        handle = stage.submit(first, mode, letterbox) if first is not None else None
         i = 0
         while handle is not None:
             nxt = next(it, None)
-            following = stage.submit(nxt, mode) if nxt is not None else None   # batch i+1 goes in before detect of batch i
+            following = stage.submit(nxt, mode, letterbox) if nxt is not None else None   # batch i+1 goes in before detect of batch i
             cur = torch.cuda.current_stream()
             cur.wait_event(handle.ready)
             k, n = i % stage.depth, handle.batch.shape[0]
@@ -369,6 +372,10 @@ class Net:
                                          float(score_threshold), _dev(packed_dev), _dev(nv_dev), C.c_void_p(cur.cuda_stream)),
                   "y3_net_detect")
             stage.release(handle)
+            if letterbox:
+                g = handle.geometry
+                check(self.lib.y3_unletterbox_detections(_dev(packed_dev), _dev(nv_dev), g.ctypes.data_as(C.POINTER(C.c_int32)), n, M, S,
+                                                         C.c_void_p(cur.cuda_stream)), "y3_unletterbox_detections")
             packed_host[:n].copy_(packed_dev[:n], non_blocking=True)
             nv_host[:n].copy_(nv_dev[:n], non_blocking=True)
             done.record(cur)
@@ -466,10 +473,12 @@ def split2_planes(x: torch.Tensor) -> torch.Tensor:
     return torch.stack([h, lo], dim=-2).contiguous()
 
 
-def preprocess_image(image: torch.Tensor, batch: torch.Tensor, slot: int, divide_after: bool = False):
+def preprocess_image(image: torch.Tensor, batch: torch.Tensor, slot: int, divide_after: bool = False, letterbox: bool = False):
     """image [H,W,3|4] uint8 or float32 on the GPU -> batch[slot] ([S,S,3] fp32, values in [0,1] for uint8 input):
     decode_image's uint8->float conversion fused with tf.image.resize's bilinear resampling.  divide_after=True is
-    the tfrecords source's order (reference: core/load_tfrecords.py:46-48): resize the 0..255 values, then / 255."""
+    the tfrecords source's order (reference: core/load_tfrecords.py:46-48): resize the 0..255 values, then / 255.
+    letterbox=True keeps the aspect ratio and pads with zeros (reference: core/utils.py:17-28, resize_image); the whole
+    slot is written."""
     _need_cuda(image, batch)
     if image.dim() != 3 or image.dtype not in (torch.uint8, torch.float32) or batch.dtype != torch.float32:
         raise Y3Error("image must be [H,W,C] uint8/float32 and batch float32 [B,S,S,3]")
@@ -479,6 +488,8 @@ def preprocess_image(image: torch.Tensor, batch: torch.Tensor, slot: int, divide
     mode = (2 if divide_after else 1) if image.dtype == torch.uint8 else 0
     if divide_after and mode == 0:
         raise Y3Error("divide_after applies to uint8 images")
+    if letterbox:
+        mode |= _lib.Y3_IMAGE_LETTERBOX
     check(_lib.load().y3_preprocess_image(_dev(image), mode, H, W, C_, _dev(batch), slot,
                                           batch.shape[1], _lib.stream_ptr()), "y3_preprocess_image")
     return batch
@@ -521,14 +532,26 @@ def packed_nbytes(images) -> int:
     return _blob_offsets(images)[1]
 
 
-def pack_images(images, mode, out: Optional[np.ndarray] = None):
+def _image_flags(images, letterbox):
+    if np.ndim(letterbox) == 0:
+        return [_lib.Y3_IMAGE_LETTERBOX if letterbox else 0] * len(images)
+    flags = [_lib.Y3_IMAGE_LETTERBOX if f else 0 for f in letterbox]
+    if len(flags) != len(images):
+        raise Y3Error(f"pack_images: {len(flags)} letterbox flags for {len(images)} images")
+    return flags
+
+
+def pack_images(images, mode, out: Optional[np.ndarray] = None, letterbox=False):
     """A list of [H,W,3|4] uint8 / float32 arrays -> (blob_u8, descs): one contiguous byte buffer with every image start
     16-byte aligned, and the y3_image_desc array (IMAGE_DESC_DTYPE) that names them.  Pure NumPy.
     mode: one value for the whole list or one per image -- 0 float32, 1 uint8 scaled by 1/255 before the resize (the
     image_file / images_dir sources), 2 uint8 divided by 255 after it (the tfrecords source).
+    letterbox: one bool for the whole list or one per image -- True sets Y3_IMAGE_LETTERBOX in the descriptor's mode: the
+    image keeps its aspect ratio and is padded with zeros (core/utils.resize_image) instead of being stretched.
     out: a 1-D uint8 array to pack into (e.g. a view of pinned memory); blob_u8 is then its used prefix."""
     images = list(images)
     modes = _image_modes(images, mode)
+    flags = _image_flags(images, letterbox)
     offsets, total = _blob_offsets(images)
     if out is None:
         out = np.empty(total, np.uint8)
@@ -537,10 +560,42 @@ def pack_images(images, mode, out: Optional[np.ndarray] = None):
     elif out.size < total:
         raise Y3Error(f"pack_images: out holds {out.size} bytes, the images need {total}")
     descs = np.zeros(len(images), IMAGE_DESC_DTYPE)
-    for i, (im, m, off) in enumerate(zip(images, modes, offsets)):
+    for i, (im, m, f, off) in enumerate(zip(images, modes, flags, offsets)):
         np.copyto(out[off:off + im.nbytes].view(im.dtype).reshape(im.shape), im)
-        descs[i] = (off, im.shape[0], im.shape[1], im.shape[2], m)
+        descs[i] = (off, im.shape[0], im.shape[1], im.shape[2], m | f)
     return out[:total], descs
+
+
+def letterbox_geometries(descs: np.ndarray, image_size: int) -> np.ndarray:
+    """The descriptor array of pack_images -> int32 [n,4] (sh, sw, top, left): where each image lies on the
+    image_size^2 canvas, (S, S, 0, 0) for an image without the letterbox flag.  One host call for the whole batch
+    (y3_letterbox_geometry; no GPU needed); the rows unletterbox_detections takes."""
+    if not isinstance(descs, np.ndarray) or descs.dtype != IMAGE_DESC_DTYPE or descs.ndim != 1:
+        raise Y3Error("descs must be the descriptor array of pack_images")
+    d = np.ascontiguousarray(descs)
+    geoms = np.empty((len(d), 4), np.int32)
+    check(_lib.load().y3_letterbox_geometry(d.ctypes.data_as(C.POINTER(_lib.ImageDesc)), len(d), int(image_size),
+                                            geoms.ctypes.data_as(C.POINTER(C.c_int32))), "y3_letterbox_geometry")
+    return geoms
+
+
+def unletterbox_detections(packed: torch.Tensor, num_valid: torch.Tensor, geoms, image_size: int):
+    """packed [B,M,7] int32 words and num_valid [B] int32 on the GPU (Net.detect / pack_detections), geoms int32 [B,4]
+    on the host (letterbox_geometries): the boxes of the valid rows are rewritten in place from the padded canvas to
+    the coordinates of the source frames (y3_unletterbox_detections; host restatement: core/utils.unletterbox_boxes).
+    Nothing else is touched.  Enqueues on the current stream only."""
+    _need_cuda(packed, num_valid)
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != 7 or not packed.is_contiguous():
+        raise Y3Error("packed must be contiguous int32 [B,M,7]")
+    if num_valid.dtype != torch.int32 or num_valid.shape != (packed.shape[0],) or not num_valid.is_contiguous():
+        raise Y3Error("num_valid must be contiguous int32 [B]")
+    g = np.ascontiguousarray(geoms, dtype=np.int32)
+    if g.shape != (packed.shape[0], 4):
+        raise Y3Error(f"geoms must be int32 [{packed.shape[0]},4]")
+    check(_lib.load().y3_unletterbox_detections(_dev(packed), _dev(num_valid), g.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                packed.shape[0], packed.shape[1], int(image_size), _lib.stream_ptr()),
+          "y3_unletterbox_detections")
+    return packed
 
 
 def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Tensor, first_slot: int = 0):
@@ -564,10 +619,11 @@ def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Ten
 
 class StagedBatch:
     """What InputStage.submit returns: `batch` ([n,S,S,3] fp32 on the GPU) holds the images once a stream has waited on
-    the event `ready`; hand it back with InputStage.release when the consumer's work on it is enqueued."""
+    the event `ready`; hand it back with InputStage.release when the consumer's work on it is enqueued.  `geometry`
+    (int32 [n,4] on the host: sh, sw, top, left) says where each frame lies in its slot."""
 
-    def __init__(self, slot, batch, ready):
-        self.slot, self.batch, self.ready = slot, batch, ready
+    def __init__(self, slot, batch, ready, geometry):
+        self.slot, self.batch, self.ready, self.geometry = slot, batch, ready, geometry
 
 
 class _StageSlot:
@@ -584,7 +640,7 @@ class _StageSlot:
 class InputStage:
     """Host frames -> device batches, overlapped with the consumer: a ring of `depth` slots, each a pinned host blob, a
     device blob and a device batch [max_batch,S,S,3], fed by one copy stream.
-    submit(images, mode) packs the list into the next slot's pinned blob and enqueues, on the copy stream, one
+    submit(images, mode, letterbox) packs the list into the next slot's pinned blob and enqueues, on the copy stream, one
     host-to-device copy and y3_preprocess_batch; release(handle) tells the stage that the consumer's reads are enqueued.
     Every wait is on an event: the host waits for `ready` of the slot's previous use before it overwrites the pinned
     blob, the copy stream waits for `released` before it overwrites the device buffers.  Nothing synchronises the device."""
@@ -602,7 +658,7 @@ class InputStage:
             s.batch.record_stream(self.stream)
         self._next = 0
 
-    def submit(self, images, mode) -> StagedBatch:
+    def submit(self, images, mode, letterbox=False) -> StagedBatch:
         images = list(images)
         if not 1 <= len(images) <= self.max_batch:
             raise Y3Error(f"InputStage.submit: {len(images)} images, the stage holds 1..{self.max_batch}")
@@ -611,7 +667,8 @@ class InputStage:
             raise Y3Error(f"InputStage.submit: all {self.depth} slots are in use; release() the oldest batch first")
         if slot.state == "released":
             slot.ready.synchronize()     # the slot's earlier copy has left the pinned blob
-        blob, descs = pack_images(images, mode, out=slot.pinned_np)
+        blob, descs = pack_images(images, mode, out=slot.pinned_np, letterbox=letterbox)
+        geometry = letterbox_geometries(descs, self.image_size)     # one host call per batch
         n = blob.size
         with torch.cuda.stream(self.stream):
             if slot.state == "released":
@@ -621,7 +678,7 @@ class InputStage:
             slot.ready.record(self.stream)
         slot.state = "held"
         self._next = (self._next + 1) % self.depth
-        return StagedBatch(slot, slot.batch[:len(images)], slot.ready)
+        return StagedBatch(slot, slot.batch[:len(images)], slot.ready, geometry)
 
     def release(self, handle: StagedBatch):
         """Call on the consumer's stream after its last use of handle.batch has been enqueued."""

@@ -13,6 +13,8 @@ pytestmark = pytest.mark.gpu
 
 torch = pytest.importorskip("torch")
 
+from yolo_v3_tf2_amd import _lib  # noqa: E402  (tile tables for the parametrised tile tests)
+
 
 @pytest.fixture(scope="module")
 def rt():
@@ -235,7 +237,7 @@ def test_x3_conv_layers_match_fp32_oracle(rt, case):
         assert np.abs(g - r).max() <= tol, (case, float(np.abs(g - r).max()), tol)
 
 
-@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 8, 9, 12, 13, 14])      # _lib.TILES_X3_BUILT
+@pytest.mark.parametrize("tile", _lib.TILES_X3_BUILT)
 def test_x3_every_tile(rt, tile):
     from tests.helpers import mini_program
     from yolo_v3_tf2_amd.weights import synthetic_weights
@@ -340,7 +342,7 @@ def test_x2_rejects_weights_outside_fp16_range_only_in_that_mode(rt):
         net.plan(1, 8, _lib.Y3_DTYPE_F32X2)
 
 
-@pytest.mark.parametrize("tile", [0, 1, 2, 3, 4, 8, 12, 26, 27])          # _lib.TILES_X2_BUILT
+@pytest.mark.parametrize("tile", _lib.TILES_X2_BUILT)
 def test_x2_every_tile(rt, tile):
     from tests.helpers import mini_program
     from yolo_v3_tf2_amd.weights import synthetic_weights
@@ -440,7 +442,7 @@ def test_bf16_conv_layers_match_bf16_oracle(rt, case):
         assert np.abs(g - r).max() <= 2e-4 * max(1.0, float(np.abs(r).max())), (case, float(np.abs(g - r).max()))
 
 
-@pytest.mark.parametrize("tile", [0, 3, 4, 5, 6, 8, 10, 11, 12, 17, 19, 22, 24, 26, 27, 29])    # every built bf16 tile but 32 (the weight-resident kernel, tested below)
+@pytest.mark.parametrize("tile", [t for t, row in enumerate(_lib.TILES_BF16) if row[0] > 0 and t != 32])    # 32: the weight-resident kernel, tested below
 def test_bf16_every_tile(rt, tile):
     from tests.helpers import mini_program
     from yolo_v3_tf2_amd.weights import synthetic_weights

@@ -8,6 +8,7 @@
 //   * MFMA 32x32x16: lane (r = l & 31, h = l >> 5) feeds A[row r][k = 16s + 8h .. +7] as one ds_read_b128;
 //   * epilogue through LDS: accumulators (+scale/shift, leaky) are written as an fp32 [BM][BN+4] tile, then every
 //     thread converts 8 consecutive channels (+ bf16 residual) and issues ONE 16-byte store -> full 128-B lines.
+#include <algorithm>
 #include <type_traits>
 
 #include "decode_box.h"
@@ -146,8 +147,19 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
     };
     set_tap();
 
-    u32x4 ra[AP], rb[BP];
     int kglob = 0;
+    // the K walk both fetch forms end with: the next BK channels of this tap, else the next tap
+    auto advance_k = [&]() {
+        kglob += BK;
+        c0 += BK;
+        if (c0 == p.Cin) {
+            c0 = 0;
+            ++tap;
+            if (!CONCAT) set_tap();
+        }
+    };
+
+    u32x4 ra[AP], rb[BP];
     auto fetch_dma = [&](int buf) {
         unsigned char *sa = smem + buf * STAGE_B + wave * DROWS * ROWB;   // wave w fills rows [pass*RP + DROWS*w, +DROWS)
         unsigned char *sb = sa + BM * ROWB;
@@ -163,13 +175,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
 #pragma unroll
         for (int j = 0; j < BP; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(sb + j * RP * ROWB), 16, (int)boff[j], kglob * 2, 0, 0);
-        kglob += BK;
-        c0 += BK;
-        if (c0 == p.Cin) {
-            c0 = 0;
-            ++tap;
-            if (!CONCAT) set_tap();
-        }
+        advance_k();
     };
     auto fetch = [&]() {
         if (CONCAT) {
@@ -186,13 +192,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
         }
 #pragma unroll
         for (int j = 0; j < BP; ++j) rb[j] = bload16(rsw, boff[j], kglob * 2);
-        kglob += BK;
-        c0 += BK;
-        if (c0 == p.Cin) {
-            c0 = 0;
-            ++tap;
-            if (!CONCAT) set_tap();
-        }
+        advance_k();
     };
     auto stage = [&](int buf) {
         unsigned char *sa = smem + buf * STAGE_B;
@@ -420,23 +420,72 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
 // the first) was correct on the first build and 10-15 % SLOWER than the 16-wave two-phase tile 17
 // (profiles/r02_tile_sweep_bf16_pipelined_b128_s416.txt, r02_bf16_pipelined_tile_pmc.txt: MFMA busy 0.45 vs 0.58).
 // ---------------------------------------------------------------------------------------------------------
-// tile table of the bf16 kernel: {BM, BN, waves, BK}
-// Round 5: the table holds exactly the tiles a plan can select -- a packaged tuning table (tuning/bf16_*.json), the library's heuristic or
-// the head-decode fallback (choose_tile_bf16 / run_slice in y3_api.cpp) names every one of them (tests/test_abi.py); the other ids are retired.
-static const TileInfo kTilesBf16[BF16_TILE_COUNT] = {
-    {128, 128, 4, 64}, {0, 0, 0, 64}, {0, 0, 0, 64}, {64, 64, 4, 64}, {128, 32, 4, 64},
-    {128, 64, 4, 32}, {64, 64, 4, 32}, {0, 0, 0, 64},
-    {128, 128, 4, 64}, {0, 0, 0, 64}, {128, 64, 4, 64}, {64, 64, 4, 64}, {64, 128, 4, 64}, {0, 0, 0, 64},  // 8..13: LDS-DMA
-    {0, 0, 0, 64}, {0, 0, 0, 64}, {0, 0, 0, 64},                  // 14..16
-    {256, 256, 16, 64}, {0, 0, 0, 64}, {128, 256, 16, 64},        // 17..19: LDS-DMA, 16 waves (64x64 / 32x64 wave tiles)
-    {0, 0, 0, 64},                                                // 20
-    {0, 0, 0, 32}, {256, 128, 8, 32}, {0, 0, 0, 32},              // 21..23: LDS-DMA with BK = 32, two workgroups per CU
-    {256, 256, 16, 64}, {0, 0, 0, 64}, {128, 256, 16, 64}, {128, 128, 4, 64}, {0, 0, 0, 64}, {64, 128, 4, 64},  // 24..29: 16x16x32 MFMAs
-    {0, 0, 0, 32}, {0, 0, 0, 32},                                 // 30, 31
-    {128, 64, 8, 32},                                             // 32: weight-resident 3x3 / stride 1, Cin = 32 / 64 (conv_res_bf16.hip): 4 x 32 pixels x 64 channels per workgroup tile
+template <int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, bool DMA, int MINW, bool M16>
+static hipError_t launch_kb(const ConvArgs &a, hipStream_t s)
+{
+    constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
+    const int tilesM = (a.M + BM - 1) / BM, tilesN = a.CoutPad / BN;
+    const size_t stages = 2 * (size_t)(BM + BN) * (DMA ? 2 * BK : 2 * BK + 16);
+    // epilogue: fp32 output -> one workgroup-wide 32-row block per wave row; bf16 output -> 32 x (32 TN) floats per wave
+    const size_t ctile = OUT_F32 ? (size_t)WR * 32 * (BN + 4) * sizeof(float) : (size_t)WR * WC * 32 * 32 * TN * sizeof(float);
+    return launch_conv_kernel<conv_bf16_mfma<TM, TN, WR, WC, BK, CONCAT, OUT_F32, DMA, MINW, M16>>(a, tilesM * tilesN, 64 * WR * WC,
+                                                                                                 std::max(stages, ctile), s);
+}
+
+template <int TM, int TN, int WR, int WC, int BK, bool DMA, int MINW, bool M16>
+static hipError_t launch_tb(const ConvArgs &a, bool out_f32, hipStream_t s)
+{
+    if (a.src1)
+        return out_f32 ? launch_kb<TM, TN, WR, WC, BK, true, true, DMA, MINW, M16>(a, s) : launch_kb<TM, TN, WR, WC, BK, true, false, DMA, MINW, M16>(a, s);
+    return out_f32 ? launch_kb<TM, TN, WR, WC, BK, false, true, DMA, MINW, M16>(a, s) : launch_kb<TM, TN, WR, WC, BK, false, false, DMA, MINW, M16>(a, s);
+}
+
+// One row per tile id: the geometry, read off the template arguments (the kernel is always double buffered), and the launcher of that
+// instantiation; a retired id is an empty row.
+struct TileBf16 { TileInfo info; hipError_t (*launch)(const ConvArgs &, bool out_f32, hipStream_t); };
+template <int TM, int TN, int WR, int WC, int BK, bool DMA = false, int MINW = 1, bool M16 = false>
+static constexpr TileBf16 tile() { return {{32 * TM * WR, 32 * TN * WC, WR * WC, 2, BK}, launch_tb<TM, TN, WR, WC, BK, DMA, MINW, M16>}; }
+
+// weight-resident 3x3 / stride 1, Cin = 32 / 64 (conv_res_bf16.hip): 4 x 32 pixels x 64 channels per workgroup tile; stores bf16 only
+static hipError_t launch_res(const ConvArgs &a, bool out_f32, hipStream_t s)
+{
+    return (!out_f32 && conv_res_bf16_fits(a)) ? launch_conv_res_bf16(a, s) : hipErrorInvalidValue;
+}
+
+// Ids are stable (tuning files refer to them).  The table holds exactly the tiles a plan can select -- a packaged tuning table
+// (tuning/bf16_*.json), the library's heuristic or the head-decode fallback (choose_tile_bf16 / run_slice in y3_api.cpp) names every one of
+// them (tests/test_abi.py); the other ids are retired.
+static const TileBf16 kTilesBf16[BF16_TILE_COUNT] = {
+    tile<2, 2, 2, 2, 64>(),                  //  0: 128x128
+    {}, {},
+    tile<1, 1, 2, 2, 64>(),                  //  3: 64x64
+    tile<1, 1, 4, 1, 64>(),                  //  4: 128x32
+    tile<2, 1, 2, 2, 32>(),                  //  5: 128x64, BK 32 (Cin = 32 layers)
+    tile<1, 1, 2, 2, 32>(),                  //  6: 64x64, BK 32
+    {},
+    tile<2, 2, 2, 2, 64, true>(),            //  8: 128x128 LDS-DMA
+    {},
+    tile<2, 1, 2, 2, 64, true>(),            // 10: 128x64 LDS-DMA
+    tile<1, 1, 2, 2, 64, true>(),            // 11: 64x64 LDS-DMA
+    tile<1, 2, 2, 2, 64, true>(),            // 12: 64x128 LDS-DMA
+    {}, {}, {}, {},                          // 13..16
+    tile<2, 2, 4, 4, 64, true>(),            // 17: 256x256, 16 waves, LDS-DMA
+    {},
+    tile<1, 2, 4, 4, 64, true>(),            // 19: 128x256, 16 waves, LDS-DMA
+    {}, {},                                  // 20 (the pipelined tile of round 2, see above), 21
+    tile<2, 2, 4, 2, 32, true, 4>(),         // 22: 256x128, 8 waves, LDS-DMA with BK 32, two workgroups per CU
+    {},
+    tile<2, 2, 4, 4, 64, true, 1, true>(),   // 24: tile 17 on 16x16x32 MFMAs
+    {},
+    tile<1, 2, 4, 4, 64, true, 1, true>(),   // 26: tile 19 on 16x16x32
+    tile<2, 2, 2, 2, 64, true, 1, true>(),   // 27: tile 8 (128x128, 4 waves) on 16x16x32
+    {},
+    tile<1, 2, 2, 2, 64, true, 1, true>(),   // 29: tile 12 (64x128, 4 waves) on 16x16x32
+    {}, {},                                  // 30, 31
+    {{128, 64, 8, 2, 32}, launch_res},       // 32
     // 33..35 (3x3 / stride 1 with tap-row reuse) and 36 (256x256 on four waves of 128x128, hand-pipelined): parity-green, neutral / slower in the
     // two-lane step (profiles/r04_ab_bf16_rs.txt, r04_tile_sweep_bf16_w4.txt); code in the history (commit 1777145)
-    {0, 0, 0, 64}, {0, 0, 0, 64}, {0, 0, 0, 64}, {0, 0, 0, 64},
+    {}, {}, {}, {},
 };
 
 #ifdef Y3_PHASE_STAMPS
@@ -447,61 +496,18 @@ extern "C" int y3_dbg_copy_stamps(unsigned long long *dst, int n_words)
 }
 #endif
 
-TileInfo conv_bf16_tile_info(int tile) { return kTilesBf16[(tile >= 0 && tile < BF16_TILE_COUNT) ? tile : 0]; }
+TileInfo conv_bf16_tile_info(int tile) { return kTilesBf16[(tile >= 0 && tile < BF16_TILE_COUNT) ? tile : 0].info; }
 
-bool conv_bf16_tile_built(int tile) { return tile >= 0 && tile < BF16_TILE_COUNT && kTilesBf16[tile].bm > 0; }
-
-template <int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, bool DMA = false, int MINW = 1, bool M16 = false>
-static hipError_t launch_kb(const ConvArgs &a, hipStream_t s)
-{
-    constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
-    const int tilesM = (a.M + BM - 1) / BM, tilesN = a.CoutPad / BN;
-    const size_t stages = 2 * (size_t)(BM + BN) * (DMA ? 2 * BK : 2 * BK + 16);
-    // epilogue: fp32 output -> one workgroup-wide 32-row block per wave row; bf16 output -> 32 x (32 TN) floats per wave
-    const size_t ctile = OUT_F32 ? (size_t)WR * 32 * (BN + 4) * sizeof(float) : (size_t)WR * WC * 32 * 32 * TN * sizeof(float);
-    const size_t lds = stages > ctile ? stages : ctile;
-    auto k = conv_bf16_mfma<TM, TN, WR, WC, BK, CONCAT, OUT_F32, DMA, MINW, M16>;
-    static LdsAttrOnce attr;  // per instantiation
-    if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(k), (int)lds, a.device); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(tilesM * tilesN), dim3(64 * WR * WC), lds, s, a);
-    return hipGetLastError();
-}
-
-template <int TM, int TN, int WR, int WC, int BK, bool DMA = false, int MINW = 1, bool M16 = false>
-static hipError_t launch_tb(const ConvArgs &a, bool out_f32, hipStream_t s)
-{
-    if (a.src1)
-        return out_f32 ? launch_kb<TM, TN, WR, WC, BK, true, true, DMA, MINW, M16>(a, s) : launch_kb<TM, TN, WR, WC, BK, true, false, DMA, MINW, M16>(a, s);
-    return out_f32 ? launch_kb<TM, TN, WR, WC, BK, false, true, DMA, MINW, M16>(a, s) : launch_kb<TM, TN, WR, WC, BK, false, false, DMA, MINW, M16>(a, s);
-}
+bool conv_bf16_tile_built(int tile) { return tile >= 0 && tile < BF16_TILE_COUNT && kTilesBf16[tile].launch; }
 
 hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s)
 {
     if (!conv_bf16_tile_built(tile)) return hipErrorInvalidValue;
-    const TileInfo t = kTilesBf16[tile];
+    const TileInfo &t = kTilesBf16[tile].info;
     if (a.dec.boxes != nullptr && (!out_f32 || t.bn < a.CoutPad)) return hipErrorInvalidValue;   // a fused head needs all its channels in one tile
     if (a.dst == nullptr && a.dec.boxes == nullptr) return hipErrorInvalidValue;
-    if (a.Cin % t.stages || a.CoutPad % t.bn || (a.src1 && a.C0 % t.stages)) return hipErrorInvalidValue;  // .stages holds BK
-    if (tile == 32) return (!out_f32 && conv_res_bf16_fits(a)) ? launch_conv_res_bf16(a, s) : hipErrorInvalidValue;
-    switch (tile) {
-        case 0: return launch_tb<2, 2, 2, 2, 64>(a, out_f32, s);
-        case 3: return launch_tb<1, 1, 2, 2, 64>(a, out_f32, s);
-        case 4: return launch_tb<1, 1, 4, 1, 64>(a, out_f32, s);
-        case 5: return launch_tb<2, 1, 2, 2, 32>(a, out_f32, s);
-        case 6: return launch_tb<1, 1, 2, 2, 32>(a, out_f32, s);
-        case 8: return launch_tb<2, 2, 2, 2, 64, true>(a, out_f32, s);    // 128x128 LDS-DMA
-        case 10: return launch_tb<2, 1, 2, 2, 64, true>(a, out_f32, s);   // 128x64 LDS-DMA
-        case 11: return launch_tb<1, 1, 2, 2, 64, true>(a, out_f32, s);   // 64x64 LDS-DMA
-        case 12: return launch_tb<1, 2, 2, 2, 64, true>(a, out_f32, s);   // 64x128 LDS-DMA
-        case 17: return launch_tb<2, 2, 4, 4, 64, true>(a, out_f32, s);   // 256x256, 16 waves, LDS-DMA
-        case 19: return launch_tb<1, 2, 4, 4, 64, true>(a, out_f32, s);   // 128x256, 16 waves, LDS-DMA
-        case 22: return launch_tb<2, 2, 4, 2, 32, true, 4>(a, out_f32, s);   // 256x128, 8 waves, BK 32, two workgroups per CU
-        case 24: return launch_tb<2, 2, 4, 4, 64, true, 1, true>(a, out_f32, s);   // tile 17 on 16x16x32 MFMAs
-        case 26: return launch_tb<1, 2, 4, 4, 64, true, 1, true>(a, out_f32, s);   // tile 19 on 16x16x32
-        case 27: return launch_tb<2, 2, 2, 2, 64, true, 1, true>(a, out_f32, s);   // tile 8 (128x128, 4 waves) on 16x16x32
-        case 29: return launch_tb<1, 2, 2, 2, 64, true, 1, true>(a, out_f32, s);   // tile 12 (64x128, 4 waves) on 16x16x32
-        default: return hipErrorInvalidValue;
-    }
+    if (!tile_fits(t, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
+    return kTilesBf16[tile].launch(a, out_f32, s);
 }
 
 }  // namespace y3

@@ -10,7 +10,7 @@
 // Block tile BM x BN x 32, WR x WC waves (64*WR*WC threads), wave tile (32*TM) x (32*TN).
 // Both operand tiles live in LDS as [rows][32+4] floats (K contiguous, one 16-B pad per row:
 // row stride 9 x 16 B makes every ds_read_b128 of 16 different rows conflict-free), filled with
-// 16-B buffer loads -> ds_write_b128 and double buffered (one barrier per K tile).
+// 16-B buffer loads -> ds_write_b128 (one LDS stage; the LDS-DMA tiles below also come double buffered, one barrier per K tile).
 // A lane reads 4 consecutive k of its row as one ds_read_b128 and feeds them to 4 MFMAs; lanes
 // 0-31 / 32-63 take k = 8q+t / 8q+4+t in MFMA (q,t), identically for A and B, so every k is
 // contracted exactly once (the order of k inside a tile is irrelevant to the sum's value up to
@@ -25,7 +25,8 @@
 namespace y3 {
 
 static constexpr int BK = 32;
-static constexpr int LDS_ROW_PADDED = BK + 4;  // floats (register-staged variant)
+// floats per LDS row: register-staged loads pad the row by 16 B, LDS-DMA rows are unpadded and swizzled
+static constexpr int lds_row(int dma) { return dma ? BK : BK + 4; }
 
 // 16-byte buffer load: per-lane voffset (range-checked against num_records) + wave-uniform soffset
 __device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
@@ -63,7 +64,8 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
         y3_dbg32_stamps[blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
     }
 #endif
-    constexpr int LDS_ROW = DMA ? BK : BK + 4;  // floats per LDS row
+    static_assert(DMA || STAGES == 1, "register-staged operand loads are single-stage; two stages need the LDS-DMA loads");
+    constexpr int LDS_ROW = lds_row(DMA);
     constexpr int BM = 32 * TM * WR;
     constexpr int BN = 32 * TN * WC;
     constexpr int NT = 64 * WR * WC;
@@ -221,6 +223,21 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     }
     set_tap();
 
+    // the K walk both fetch forms end with: the next 32 channels of this tap, else the next tap (chunked order: of this channel chunk)
+    auto advance_k = [&]() {
+        c0 += BK;
+        if (c0 == cend) {
+            ++tap;
+            if (!CONCAT && tap == taps && cend != p.Cin) {   // chunked order: next channel chunk, first tap again
+                tap = 0;
+                cend += CK;
+            }
+            c0 = cend - CK;
+            if (!CONCAT) set_tap();
+        }
+        kglob = tap * p.Cin + c0;
+    };
+
     f32x4 ra[AP], rb[BP];
     auto fetch_dma = [&](int buf) {
         // wave w fills rows [pass*RP + 8w, +8) of each tile: LDS destination = M0 base + lane*16
@@ -238,17 +255,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
 #pragma unroll
         for (int j = 0; j < BP; ++j)
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(sb + j * RP * LDS_ROW), 16, (int)boff[j], kglob * 4, 0, 0);
-        c0 += BK;
-        if (c0 == cend) {
-            ++tap;
-            if (!CONCAT && tap == taps && cend != p.Cin) {   // chunked order: next channel chunk, first tap again
-                tap = 0;
-                cend += CK;
-            }
-            c0 = cend - CK;
-            if (!CONCAT) set_tap();
-        }
-        kglob = tap * p.Cin + c0;
+        advance_k();
     };
     auto fetch = [&]() {
         if (CONCAT) {
@@ -266,17 +273,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
         }
 #pragma unroll
         for (int j = 0; j < BP; ++j) rb[j] = buf_load16(rsw, boff[j], kglob * 4);
-        c0 += BK;
-        if (c0 == cend) {
-            ++tap;
-            if (!CONCAT && tap == taps && cend != p.Cin) {   // chunked order: next channel chunk, first tap again
-                tap = 0;
-                cend += CK;
-            }
-            c0 = cend - CK;
-            if (!CONCAT) set_tap();
-        }
-        kglob = tap * p.Cin + c0;
+        advance_k();
     };
     auto stage = [&](int buf) {
         float *sa = smem + buf * STAGE;
@@ -351,9 +348,6 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
             }
-        } else if (STAGES == 2) {
-            if (kt + 1 < KT) stage(cur ^ 1);
-            __syncthreads();
         } else if (kt + 1 < KT) {
             __syncthreads();  // every wave is done reading the tile
             stage(0);
@@ -437,23 +431,65 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     clk_stamp_exit(p.clk_stamps);
 }
 
-// tile table: {BM, BN, waves, LDS stages}; ids are stable (tuning files refer to them).  Ids 20..22 and 25 were the
-// timing-only probes of rounds 1-2 (removed in round 4; the ids stay reserved), 33..45 the stream-K / residual-prefetch tiles.
-// Round 5: the table holds exactly the tiles a plan can select -- a packaged tuning table (tuning/f32_*.json) or the library's heuristic
-// (choose_tile in y3_api.cpp) names every one of them (tests/test_abi.py).  The other ids of rounds 1-4 (two-stage forms of 0..5, the 8- and
-// 16-wave 128x128 / 256x128 tiles, the register-budget variant 24, the two-stage LDS-DMA tiles 28..30, the ablations 20..22, 25) are retired:
-// {0,0,0,0}, y3_tile_built answers 0; the kernel template itself is general and the sweeps that retired them are under profiles/.
-static const TileInfo kTiles[TILE_COUNT] = {
-    {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0},                                  // 0..5
-    {128, 128, 4, 1}, {0, 0, 0, 0}, {256, 32, 4, 1}, {128, 64, 4, 1}, {64, 128, 4, 1}, {64, 64, 4, 1},                 // 6..11: single LDS stage
-    {128, 128, 8, 1}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0},                                                          // 12..15
-    {0, 0, 0, 0}, {128, 64, 8, 1}, {0, 0, 0, 0}, {0, 0, 0, 0},                                                           // 16..19
-    {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0},                                                                            // 20..22
-    {128, 128, 4, 1}, {0, 0, 0, 0},                      // 23: 128x128 with the register budget of 3 waves per SIMD
-    {0, 0, 0, 0},                                        // 25
-    {64, 128, 4, 2}, {64, 64, 4, 2}, {0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0},   // 26, 27: LDS-DMA loads, two stages
-    {64, 128, 4, 1}, {64, 64, 4, 1},                     // 31, 32: LDS-DMA, single stage
-    {128, 64, 8, 2},                                     // 33: weight-resident 3x3 / stride 1 / Cin = 32 (conv_res_f32.hip): 8 x 16 pixels x 64 channels per workgroup tile
+template <int TM, int TN, int WR, int WC, bool CONCAT, int STAGES, int MINW, int DMA>
+static hipError_t launch_k(const ConvArgs &a, hipStream_t s)
+{
+    constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
+    const int tilesM = (a.M + BM - 1) / BM, tilesN = a.CoutPad / BN;
+    const size_t lds = STAGES * (size_t)(BM + BN) * lds_row(DMA) * sizeof(float);
+    int grid = tilesM * tilesN;
+    if (a.xcd_gn > 0) {
+        if (8 % a.xcd_gn || tilesN % a.xcd_gn) return hipErrorInvalidValue;
+        const int gm = 8 / a.xcd_gn;
+        int rows = 0;                                           // largest M block
+        for (int xm = 0; xm < gm; ++xm) rows = std::max(rows, (xm + 1) * tilesM / gm - xm * tilesM / gm);
+        grid = 8 * rows * (tilesN / a.xcd_gn);
+    }
+    return launch_conv_kernel<conv_f32_mfma<TM, TN, WR, WC, CONCAT, STAGES, MINW, DMA>>(a, grid, 64 * WR * WC, lds, s);
+}
+
+template <int TM, int TN, int WR, int WC, int STAGES, int MINW, int DMA>
+static hipError_t launch_t(const ConvArgs &a, hipStream_t s)
+{
+    return a.src1 ? launch_k<TM, TN, WR, WC, true, STAGES, MINW, DMA>(a, s) : launch_k<TM, TN, WR, WC, false, STAGES, MINW, DMA>(a, s);
+}
+
+// One row per tile id: the geometry, read off the template arguments, and the launcher of that instantiation; a retired id is an empty row.
+struct TileF32 { TileInfo info; hipError_t (*launch)(const ConvArgs &, hipStream_t); };
+// MINW: register budget (waves per SIMD) -- with 4, the two accumulators of the 32x64 wave tile stay in architectural VGPRs and the epilogue
+// needs no v_accvgpr_read (nor the prologue 32-64 v_accvgpr_write: with the SIMD full of 64-cycle MFMAs every vector instruction outside the
+// K loop waits ~one MFMA for its issue slot, profiles/r03_ab_f32_prologue.txt).  DMA: direct-to-LDS operand loads.
+template <int TM, int TN, int WR, int WC, int STAGES = 1, int MINW = 1, int DMA = 0>
+static constexpr TileF32 tile() { return {{32 * TM * WR, 32 * TN * WC, WR * WC, STAGES, BK}, launch_t<TM, TN, WR, WC, STAGES, MINW, DMA>}; }
+
+// weight-resident 3x3 / stride 1 / Cin = 32 (conv_res_f32.hip): 8 x 16 pixels x 64 channels per workgroup tile
+static hipError_t launch_res(const ConvArgs &a, hipStream_t s) { return conv_res_f32_fits(a) ? launch_conv_res_f32(a, s) : hipErrorInvalidValue; }
+
+// Ids are stable (tuning files refer to them).  The table holds exactly the tiles a plan can select -- a packaged tuning table
+// (tuning/f32_*.json) or the library's heuristic (choose_tile in y3_api.cpp) names every one of them (tests/test_abi.py).  The other ids of
+// rounds 1-4 (the register-staged two-stage tiles 0..5, the 8- and 16-wave 128x128 / 256x128 tiles, the register-budget variant 24, the
+// two-stage LDS-DMA tiles 28..30, the timing-only probes 20..22, 25) are retired: y3_tile_built answers 0; the sweeps that retired them
+// are under profiles/.
+static const TileF32 kTiles[TILE_COUNT] = {
+    {}, {}, {}, {}, {}, {},           //  0..5
+    tile<2, 2, 2, 2>(),               //  6: 128x128, 4 waves
+    {},
+    tile<2, 1, 4, 1>(),               //  8: 256x32
+    tile<1, 2, 4, 1, 1, 4>(),         //  9: 128x64
+    tile<1, 2, 2, 2, 1, 4>(),         // 10: 64x128
+    tile<1, 1, 2, 2, 1, 4>(),         // 11: 64x64
+    tile<2, 1, 2, 4>(),               // 12: 128x128, 8 waves
+    {}, {}, {}, {},                   // 13..16
+    tile<1, 1, 4, 2>(),               // 17: 128x64, 8 waves
+    {}, {}, {}, {}, {},               // 18..22
+    tile<2, 2, 2, 2, 1, 3>(),         // 23: 128x128 within 3 waves per SIMD of registers
+    {}, {},                           // 24, 25
+    tile<1, 2, 2, 2, 2, 4, 1>(),      // 26: 64x128, LDS-DMA, two stages
+    tile<1, 1, 2, 2, 2, 4, 1>(),      // 27: 64x64, LDS-DMA, two stages
+    {}, {}, {},                       // 28..30
+    tile<1, 2, 2, 2, 1, 4, 1>(),      // 31: 64x128, LDS-DMA, single stage
+    tile<1, 1, 2, 2, 1, 4, 1>(),      // 32: 64x64, LDS-DMA, single stage
+    {{128, 64, 8, 2, BK}, launch_res},   // 33
 };
 
 #ifdef Y3_PHASE_STAMPS
@@ -464,61 +500,14 @@ extern "C" int y3_dbg32_copy_stamps(unsigned long long *dst, int n_words)
 }
 #endif
 
-TileInfo conv_tile_info(int tile) { return kTiles[(tile >= 0 && tile < TILE_COUNT) ? tile : 0]; }
+TileInfo conv_tile_info(int tile) { return kTiles[(tile >= 0 && tile < TILE_COUNT) ? tile : 0].info; }
 
-bool conv_tile_built(int tile) { return tile >= 0 && tile < TILE_COUNT && kTiles[tile].bm > 0; }
-
-template <int TM, int TN, int WR, int WC, bool CONCAT, int STAGES, int MINW = 1, int DMA = 0>
-static hipError_t launch_k(const ConvArgs &a_in, hipStream_t s)
-{
-    constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
-    ConvArgs a = a_in;
-    const int tilesM = (a.M + BM - 1) / BM, tilesN = a.CoutPad / BN;
-    const size_t lds = STAGES * (size_t)(BM + BN) * (DMA ? BK : LDS_ROW_PADDED) * sizeof(float);
-    auto k = conv_f32_mfma<TM, TN, WR, WC, CONCAT, STAGES, MINW, DMA>;
-    static LdsAttrOnce attr;  // per instantiation
-    if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(k), (int)lds, a.device); e != hipSuccess) return e;
-    int grid = tilesM * tilesN;
-    if (a.xcd_gn > 0) {
-        if (8 % a.xcd_gn || tilesN % a.xcd_gn) return hipErrorInvalidValue;
-        const int gm = 8 / a.xcd_gn;
-        int rows = 0;                                           // largest M block
-        for (int xm = 0; xm < gm; ++xm) rows = std::max(rows, (xm + 1) * tilesM / gm - xm * tilesM / gm);
-        grid = 8 * rows * (tilesN / a.xcd_gn);
-    }
-    hipLaunchKernelGGL(k, dim3(grid), dim3(64 * WR * WC), lds, s, a);
-    return hipGetLastError();
-}
-
-// single LDS stage, register-staged operand loads.  MINW: register budget (waves per SIMD) -- with 4, the two accumulators of the 32x64 wave
-// tile stay in architectural VGPRs and the epilogue needs no v_accvgpr_read (nor the prologue 32-64 v_accvgpr_write: with the SIMD full of
-// 64-cycle MFMAs every vector instruction outside the K loop waits ~one MFMA for its issue slot, profiles/r03_ab_f32_prologue.txt)
-template <int TM, int TN, int WR, int WC, int MINW = 1>
-static hipError_t launch_s1(const ConvArgs &a, hipStream_t s)
-{
-    return a.src1 ? launch_k<TM, TN, WR, WC, true, 1, MINW>(a, s) : launch_k<TM, TN, WR, WC, false, 1, MINW>(a, s);
-}
+bool conv_tile_built(int tile) { return tile >= 0 && tile < TILE_COUNT && kTiles[tile].launch; }
 
 hipError_t launch_conv_f32(const ConvArgs &a, int tile, hipStream_t s)
 {
-    if (!conv_tile_built(tile)) return hipErrorInvalidValue;
-    if (tile == 33) return conv_res_f32_fits(a) ? launch_conv_res_f32(a, s) : hipErrorInvalidValue;
-    switch (tile) {
-        case 6: return launch_s1<2, 2, 2, 2>(a, s);        // 128x128, 4 waves
-        case 8: return launch_s1<2, 1, 4, 1>(a, s);        // 256x32
-        case 9: return launch_s1<1, 2, 4, 1, 4>(a, s);     // 128x64
-        case 10: return launch_s1<1, 2, 2, 2, 4>(a, s);    // 64x128
-        case 11: return launch_s1<1, 1, 2, 2, 4>(a, s);    // 64x64
-        case 12: return launch_s1<2, 1, 2, 4>(a, s);       // 128x128, 8 waves
-        case 17: return launch_s1<1, 1, 4, 2>(a, s);       // 128x64, 8 waves
-        case 23: return launch_s1<2, 2, 2, 2, 3>(a, s);    // 128x128 within 3 waves per SIMD of registers
-        // direct-to-LDS operand loads
-        case 26: return a.src1 ? launch_k<1, 2, 2, 2, true, 2, 4, 1>(a, s) : launch_k<1, 2, 2, 2, false, 2, 4, 1>(a, s);  // 64x128, two stages
-        case 27: return a.src1 ? launch_k<1, 1, 2, 2, true, 2, 4, 1>(a, s) : launch_k<1, 1, 2, 2, false, 2, 4, 1>(a, s);  // 64x64, two stages
-        case 31: return a.src1 ? launch_k<1, 2, 2, 2, true, 1, 4, 1>(a, s) : launch_k<1, 2, 2, 2, false, 1, 4, 1>(a, s);  // 64x128, 1 stage
-        case 32: return a.src1 ? launch_k<1, 1, 2, 2, true, 1, 4, 1>(a, s) : launch_k<1, 1, 2, 2, false, 1, 4, 1>(a, s);  // 64x64, 1 stage
-        default: return hipErrorInvalidValue;
-    }
+    if (!conv_tile_built(tile) || !tile_fits(kTiles[tile].info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
+    return kTiles[tile].launch(a, s);
 }
 
 }  // namespace y3

@@ -18,6 +18,7 @@
 // Layout: activations [pixel][plane 0..2][C] bf16, weights [CoutPad][plane][K] bf16, head outputs fp32.
 // Operand tiles go HBM/L2 -> LDS by direct-to-LDS buffer loads (one tile per plane), double buffered; LDS rows are
 // 2*BK bytes with the 16-B chunk index XOR-swizzled on the source address and on the fragment reads.
+#include <algorithm>
 #include <type_traits>
 
 #include "y3_device.h"
@@ -25,19 +26,15 @@
 
 namespace y3 {
 
-// VAR: schedule variants of the K loop (one kernel body, so that they stay comparable):
-//   V_BURST      the LDS-DMA instructions of the next K tile are issued together at the top of the iteration (default)
-//   V_ILV        ... issued one or two at a time between the MFMA groups of the current tile (measured: no gain)
-//   V_ILV_PINNED ... and pinned there with sched_group_barrier (no gain)
-// (the timing-only probes of round 1 -- A for one tap, split K, no fetches, fetches only, one accumulator set -- were removed in
-// round 4; their records are profiles/r01_probe_*.txt)
-enum { V_BURST = 0, V_ILV = 1, V_ILV_PINNED = 2 };
-template <int NPL, int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, int STAGES = 2, int VAR = V_BURST>
+// The LDS-DMA instructions of the next K tile are issued together at the top of the iteration.  Issuing them one or two at a time between
+// the MFMA groups (also pinned there with sched_group_barrier), three LDS stages and BK 16 / 64 were measured and retired
+// (profiles/r01_tile_sweep_f32x3_b64_s416.txt; the timing-only probes of round 1: profiles/r01_probe_*.txt).
+template <int NPL, int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, int STAGES = 2>
 __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p)
 {
     static_assert(NPL == 2 || NPL == 3, "two fp16 planes or three bf16 planes");
+    static_assert(STAGES == 1 || STAGES == 2, "one LDS stage or two (double buffered)");
     constexpr int NACC = NPL == 2 ? 2 : 1;   // accumulator sets (two-plane scheme: cross terms carry a 2^11 scale)
-    constexpr int MPG = NPL == 2 ? 3 : 6;    // MFMAs per (i, j, k-step) group
     constexpr int BM = 32 * TM * WR;
     constexpr int BN = 32 * TN * WC;
     constexpr int NT = 64 * WR * WC;
@@ -59,7 +56,6 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WC, wc = wave % WC;
 
-    constexpr bool ILV = VAR == V_ILV || VAR == V_ILV_PINNED;
     const int logical = xcd_contiguous_tile((int)blockIdx.x, (int)gridDim.x);
     const int tilesN = p.CoutPad / BN;
     const int mt = logical / tilesN, nt = logical - mt * tilesN;
@@ -165,58 +161,6 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
         }
     };
 
-    // one LDS-DMA instruction of the next tile (pc = plane * (AP + BP) + row pass); state advances in dma_advance()
-    auto dma_piece = [&](int buf, int pc) {
-        const int pl = pc / (AP + BP), r = pc - pl * (AP + BP);
-        unsigned char *sa = smem + buf * STAGE_B + pl * PLANE_B + wave * RPI * ROWB;
-        unsigned char *sb = sa + BM * ROWB;
-        if (r < AP) {
-            if ((r + 1) * RP <= BM || r * RP + wave * RPI < BM) {
-                if (CONCAT && c0 >= p.C0)
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lds_ptr)(sa + r * RP * ROWB), 16, (int)avoff1[r],
-                                                             (pl * C1 + c0 - p.C0) * 2, 0, 0);
-                else
-                    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lds_ptr)(sa + r * RP * ROWB), 16, (int)avoff[r],
-                                                             (pl * (CONCAT ? p.C0 : p.Cin) + c0) * 2, 0, 0);
-            }
-        } else {
-            const int j = r - AP;
-            if ((j + 1) * RP <= BN || j * RP + wave * RPI < BN)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(sb + j * RP * ROWB), 16, (int)boff[j],
-                                                         (pl * p.K + kglob) * 2, 0, 0);
-        }
-    };
-    auto dma_advance = [&]() {
-        kglob += BK;
-        c0 += BK;
-        if (c0 == p.Cin) {
-            c0 = 0;
-            ++tap;
-            if (!CONCAT) set_tap();
-        }
-    };
-
-    // three stages: while tile kt is multiplied, tiles kt+1 and kt+2 are in flight; "tile kt+1 has landed" is then
-    // "at most this wave's own DMA instructions of tile kt+2 are outstanding" (vmcnt retires in order)
-    int ndma = 0;
-    if (STAGES == 3) {
-#pragma unroll
-        for (int i = 0; i < AP; ++i) ndma += (i * RP + wave * RPI < BM) ? NPL : 0;
-#pragma unroll
-        for (int j = 0; j < BP; ++j) ndma += (j * RP + wave * RPI < BN) ? NPL : 0;
-    }
-    auto wait_all_but_newest_tile = [&]() {
-        // s_waitcnt takes an immediate: pick the matching one (wave-uniform branches)
-        if (ndma >= 12) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
-        else if (ndma >= 9) asm volatile("s_waitcnt vmcnt(9)" ::: "memory");
-        else if (ndma >= 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-        else if (ndma >= 6) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
-        else if (ndma >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else if (ndma >= 3) asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-        else if (ndma >= 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    };
-
     f32x16 acc[NACC][TM][TN];
 #pragma unroll
     for (int a = 0; a < NACC; ++a)
@@ -229,12 +173,7 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
 
     const int KT = p.K / BK;
     fetch_dma(0);
-    if (STAGES == 3 && KT > 1) {
-        fetch_dma(1);
-        wait_all_but_newest_tile();
-    } else {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
     const int fr = lane & 31, fh = lane >> 5;
@@ -244,15 +183,10 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
 #pragma unroll
     for (int s_ = 0; s_ < BK / 16; ++s_) foff[s_] = (((2 * s_ + fh) ^ ((fr >> SWZ_SHIFT) & (LPR - 1))) * 16);
 
-    int cur3 = 0;   // STAGES == 3: stage of tile kt
     for (int kt = 0; kt < KT; ++kt) {
-        const int cur = (STAGES == 3) ? cur3 : (STAGES == 2) ? (kt & 1) : 0;
+        const int cur = (STAGES == 2) ? (kt & 1) : 0;
         const bool more = kt + 1 < KT;
-        if (STAGES == 2 && !ILV && more) fetch_dma(cur ^ 1);
-        if (STAGES == 3 && kt + 2 < KT) fetch_dma(cur3 == 0 ? 2 : cur3 - 1);   // stage of tile kt-1, free since the last barrier
-        constexpr int NP = NPL * (AP + BP);             // DMA instructions per tile
-        constexpr int NG = (BK / 16) * TM * TN;         // MFMA groups (MPG MFMAs each) per tile
-        int grp = 0;
+        if (STAGES == 2 && more) fetch_dma(cur ^ 1);
         const unsigned char *st = smem + cur * STAGE_B;
 #pragma unroll
         for (int s = 0; s < BK / 16; ++s) {
@@ -288,43 +222,13 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
                             c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[q == 1 ? 1 : 0][i], fb[q == 0 ? 1 : 0][j], c, 0, 0, 0);
                         }
             }
-#pragma unroll
-            for (int i = 0; i < TM; ++i)
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-                    if (ILV && STAGES == 2) {
-                        // issued on the last tile too (branch-free): it lands in the idle stage, and every address
-                        // is range-checked by its buffer descriptor
-#pragma unroll
-                        for (int pc = 0; pc < NP; ++pc)
-                            if (pc * NG / NP == s * TM * TN + i * TN + j) dma_piece(cur ^ 1, pc);
-                    }
-                    ++grp;
-                }
         }
-        (void)grp;
-        if (VAR == V_ILV_PINNED && STAGES == 2) {
-            // pin the issue order: a few MFMAs, then one DMA instruction, repeated
-#pragma unroll
-            for (int g = 0; g < NP; ++g) {
-                __builtin_amdgcn_sched_group_barrier(0x008, (NG * MPG) / (NP + 1), 0);
-                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-            }
-        }
-        if (ILV && STAGES == 2) dma_advance();
-        if (STAGES == 3) {
-            if (kt + 2 < KT)
-                wait_all_but_newest_tile();
-            else
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            cur3 = cur3 == 2 ? 0 : cur3 + 1;
-        } else if (STAGES == 2) {
+        if (STAGES == 2) {
             asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __syncthreads();
         } else {
             __syncthreads();                       // every wave is done reading the single stage
-            if (kt + 1 < KT) {
+            if (more) {
                 fetch_dma(0);
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 __syncthreads();
@@ -408,112 +312,85 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     }
 }
 
-// tile table: {BM, BN, waves, BK}
-// Round 5: only the tiles a plan can select are instantiated (tuning/f32x3_*.json, f32x2_*.json, choose_tile_x3 / choose_tile_x2 in
-// y3_api.cpp; tests/test_abi.py); the schedule variants of rounds 1-2 (BK 16 / 64, interleaved / pinned DMA issue, three stages) are retired.
-static const TileInfo kTilesX3[X3_TILE_COUNT] = {
-    {128, 128, 4, 32}, {128, 64, 4, 32}, {64, 64, 4, 32}, {64, 128, 4, 32}, {256, 128, 8, 32}, {0, 0, 0, 32},
-    {0, 0, 0, 64}, {0, 0, 0, 64}, {128, 256, 8, 32},
-    {128, 128, 4, 32}, {0, 0, 0, 32}, {0, 0, 0, 32}, {128, 128, 8, 32}, {128, 64, 4, 32}, {64, 128, 4, 32}, {0, 0, 0, 32},   // 9, 13, 14: single LDS stage
-    {0, 0, 0, 16}, {0, 0, 0, 16}, {0, 0, 0, 16}, {0, 0, 0, 16},
-    {0, 0, 0, 32}, {0, 0, 0, 32}, {0, 0, 0, 32}, {0, 0, 0, 32},
-    {0, 0, 0, 32}, {0, 0, 0, 32},
-    {256, 128, 16, 32}, {128, 256, 16, 32},                                       // 26..27: 16 waves, 64x32 wave tiles (two-plane mode)
-    {0, 0, 0, 32}, {0, 0, 0, 32},
-    {0, 0, 0, 32}, {0, 0, 0, 32}, {0, 0, 0, 32}, {0, 0, 0, 32},
-};
-
-bool conv_x3_tile_built(int tile);
-TileInfo conv_x3_tile_info(int tile) { return kTilesX3[(tile >= 0 && tile < X3_TILE_COUNT) ? tile : 0]; }
-
-template <int NPL, int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, int STAGES = 2, int VAR = V_BURST>
+template <int NPL, int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, int STAGES>
 static hipError_t launch_kx(const ConvArgs &a, hipStream_t s)
 {
     constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
     const int tilesM = (a.M + BM - 1) / BM, tilesN = a.CoutPad / BN;
     const size_t stages = STAGES * (size_t)NPL * (BM + BN) * (2 * BK);
     const size_t ctile = (size_t)WR * 32 * (BN + 4) * sizeof(float);
-    const size_t lds = stages > ctile ? stages : ctile;
-    if (lds > 160 * 1024) return hipErrorInvalidValue;
-    auto k = conv_f32x3_mfma<NPL, TM, TN, WR, WC, BK, CONCAT, OUT_F32, STAGES, VAR>;
-    static LdsAttrOnce attr;  // per instantiation
-    if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(k), (int)lds, a.device); e != hipSuccess) return e;
-    hipLaunchKernelGGL(k, dim3(tilesM * tilesN), dim3(64 * WR * WC), lds, s, a);
-    return hipGetLastError();
+    return launch_conv_kernel<conv_f32x3_mfma<NPL, TM, TN, WR, WC, BK, CONCAT, OUT_F32, STAGES>>(a, tilesM * tilesN, 64 * WR * WC,
+                                                                                                std::max(stages, ctile), s);
 }
 
-template <int NPL, int TM, int TN, int WR, int WC, int BK, int STAGES = 2, int VAR = V_BURST>
+template <int NPL, int TM, int TN, int WR, int WC, int BK, int STAGES>
 static hipError_t launch_tp(const ConvArgs &a, bool out_f32, hipStream_t s)
 {
     if (a.src1)
-        return out_f32 ? launch_kx<NPL, TM, TN, WR, WC, BK, true, true, STAGES, VAR>(a, s)
-                       : launch_kx<NPL, TM, TN, WR, WC, BK, true, false, STAGES, VAR>(a, s);
-    return out_f32 ? launch_kx<NPL, TM, TN, WR, WC, BK, false, true, STAGES, VAR>(a, s)
-                   : launch_kx<NPL, TM, TN, WR, WC, BK, false, false, STAGES, VAR>(a, s);
+        return out_f32 ? launch_kx<NPL, TM, TN, WR, WC, BK, true, true, STAGES>(a, s)
+                       : launch_kx<NPL, TM, TN, WR, WC, BK, true, false, STAGES>(a, s);
+    return out_f32 ? launch_kx<NPL, TM, TN, WR, WC, BK, false, true, STAGES>(a, s)
+                   : launch_kx<NPL, TM, TN, WR, WC, BK, false, false, STAGES>(a, s);
 }
 
-template <int TM, int TN, int WR, int WC, int BK, int STAGES = 2, int VAR = V_BURST>
-static hipError_t launch_tx(const ConvArgs &a, bool out_f32, hipStream_t s)
+// One row per tile id, shared by the two plane-split modes: the geometry and, per mode, the launcher of its instantiation (null: not built
+// for that mode; both null: a retired id).  The geometry is read off the template arguments the launchers are instantiated with.
+using LaunchX = hipError_t (*)(const ConvArgs &, bool out_f32, hipStream_t);
+struct TileX3 { TileInfo info; LaunchX launch3, launch2; };   // three bf16 planes, two fp16 planes
+enum { P3 = 1, P2 = 2 };
+template <int TM, int TN, int WR, int WC, int STAGES, int MODES>
+static constexpr TileX3 tile()
 {
-    return launch_tp<3, TM, TN, WR, WC, BK, STAGES, VAR>(a, out_f32, s);
+    constexpr int BK = 32;
+    TileX3 r = {{32 * TM * WR, 32 * TN * WC, WR * WC, STAGES, BK}, nullptr, nullptr};
+    if constexpr ((MODES & P3) != 0) r.launch3 = launch_tp<3, TM, TN, WR, WC, BK, STAGES>;
+    if constexpr ((MODES & P2) != 0) r.launch2 = launch_tp<2, TM, TN, WR, WC, BK, STAGES>;
+    return r;
+}
+
+// Ids are stable (tuning/f32x3_*.json, f32x2_*.json name them).  Only the tiles a plan can select are built (the tuning tables, choose_tile_x3 /
+// choose_tile_x2 in y3_api.cpp; tests/test_abi.py); the two-plane mode takes the schedules that won or came close in the three-plane sweeps.
+static const TileX3 kTilesX3[X3_TILE_COUNT] = {
+    tile<2, 2, 2, 2, 2, P3 | P2>(),   //  0: 128x128, 4 waves
+    tile<2, 1, 2, 2, 2, P3 | P2>(),   //  1: 128x64
+    tile<1, 1, 2, 2, 2, P3 | P2>(),   //  2: 64x64
+    tile<1, 2, 2, 2, 2, P3 | P2>(),   //  3: 64x128
+    tile<2, 2, 4, 2, 2, P3 | P2>(),   //  4: 256x128, 8 waves
+    {}, {}, {},                       //  5..7
+    tile<2, 2, 2, 4, 2, P3 | P2>(),   //  8: 128x256, 8 waves
+    tile<2, 2, 2, 2, 1, P3>(),        //  9: 128x128, 4 waves, single LDS stage (3 workgroups / CU)
+    {}, {},                           // 10, 11
+    tile<2, 1, 2, 4, 2, P3 | P2>(),   // 12: 128x128, 8 waves (64x32 wave tile)
+    tile<2, 1, 2, 2, 1, P3>(),        // 13: 128x64, single stage
+    tile<1, 2, 2, 2, 1, P3>(),        // 14: 64x128, single stage
+    {}, {}, {}, {}, {}, {}, {}, {}, {}, {}, {},   // 15..25
+    tile<2, 1, 4, 4, 2, P2>(),        // 26: 256x128, 16 waves (64x32 wave tiles)
+    tile<2, 1, 2, 8, 2, P2>(),        // 27: 128x256, 16 waves
+    {}, {}, {}, {}, {}, {},           // 28..33
+};
+
+static const TileX3 *row_x3(int tile) { return (tile >= 0 && tile < X3_TILE_COUNT) ? &kTilesX3[tile] : nullptr; }
+
+TileInfo conv_x3_tile_info(int tile) { return kTilesX3[row_x3(tile) ? tile : 0].info; }
+bool conv_x3_tile_built(int tile) { return row_x3(tile) && row_x3(tile)->launch3; }
+bool conv_x2_tile_built(int tile) { return row_x3(tile) && row_x3(tile)->launch2; }
+
+static hipError_t launch_row(const TileX3 *t, LaunchX launch, const ConvArgs &a, bool out_f32, hipStream_t s)
+{
+    if (!launch || !tile_fits(t->info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;   // retired id / other mode only
+    return launch(a, out_f32, s);
 }
 
 hipError_t launch_conv_f32x3(const ConvArgs &a, int tile, bool out_f32, hipStream_t s)
 {
-    if (tile < 0 || tile >= X3_TILE_COUNT) return hipErrorInvalidValue;
-    const TileInfo t = kTilesX3[tile];
-    if (t.bm == 0 || !conv_x3_tile_built(tile)) return hipErrorInvalidValue;   // retired id / two-plane only
-    if (a.Cin % t.stages || a.CoutPad % t.bn || (a.src1 && a.C0 % t.stages)) return hipErrorInvalidValue;  // .stages holds BK
-    switch (tile) {
-        case 0: return launch_tx<2, 2, 2, 2, 32>(a, out_f32, s);
-        case 1: return launch_tx<2, 1, 2, 2, 32>(a, out_f32, s);
-        case 2: return launch_tx<1, 1, 2, 2, 32>(a, out_f32, s);
-        case 3: return launch_tx<1, 2, 2, 2, 32>(a, out_f32, s);
-        case 4: return launch_tx<2, 2, 4, 2, 32>(a, out_f32, s);
-        case 8: return launch_tx<2, 2, 2, 4, 32>(a, out_f32, s);
-        case 9: return launch_tx<2, 2, 2, 2, 32, 1>(a, out_f32, s);    // 128x128 w4, single stage (3 workgroups / CU)
-        case 12: return launch_tx<2, 1, 2, 4, 32>(a, out_f32, s);      // 128x128 w8 (64x32 wave tile)
-        case 13: return launch_tx<2, 1, 2, 2, 32, 1>(a, out_f32, s);   // 128x64 w4, single stage
-        case 14: return launch_tx<1, 2, 2, 2, 32, 1>(a, out_f32, s);   // 64x128 w4, single stage
-        default: return hipErrorInvalidValue;
-    }
+    const TileX3 *t = row_x3(tile);
+    return launch_row(t, t ? t->launch3 : nullptr, a, out_f32, s);
 }
 
-// two fp16 planes: the same tile ids (a subset: the schedules that won or came close in the three-plane sweeps)
 hipError_t launch_conv_f32x2(const ConvArgs &a, int tile, bool out_f32, hipStream_t s)
 {
-    if (tile < 0 || tile >= X3_TILE_COUNT) return hipErrorInvalidValue;
-    const TileInfo t = kTilesX3[tile];
-    if (t.bm == 0) return hipErrorInvalidValue;   // retired id
-    if (a.Cin % t.stages || a.CoutPad % t.bn || (a.src1 && a.C0 % t.stages)) return hipErrorInvalidValue;
-    switch (tile) {
-        case 0: return launch_tp<2, 2, 2, 2, 2, 32>(a, out_f32, s);       // 128x128 w4
-        case 1: return launch_tp<2, 2, 1, 2, 2, 32>(a, out_f32, s);       // 128x64 w4
-        case 2: return launch_tp<2, 1, 1, 2, 2, 32>(a, out_f32, s);       // 64x64 w4
-        case 3: return launch_tp<2, 1, 2, 2, 2, 32>(a, out_f32, s);       // 64x128 w4
-        case 4: return launch_tp<2, 2, 2, 4, 2, 32>(a, out_f32, s);       // 256x128 w8
-        case 8: return launch_tp<2, 2, 2, 2, 4, 32>(a, out_f32, s);       // 128x256 w8
-        case 12: return launch_tp<2, 2, 1, 2, 4, 32>(a, out_f32, s);      // 128x128 w8
-        case 26: return launch_tp<2, 2, 1, 4, 4, 32>(a, out_f32, s);      // 256x128 w16
-        case 27: return launch_tp<2, 2, 1, 2, 8, 32>(a, out_f32, s);      // 128x256 w16
-        default: return hipErrorInvalidValue;
-    }
-}
-
-bool conv_x3_tile_built(int tile)
-{
-    switch (tile) {
-        case 0: case 1: case 2: case 3: case 4: case 8: case 9: case 12: case 13: case 14: return true;
-        default: return false;
-    }
-}
-
-bool conv_x2_tile_built(int tile)
-{
-    switch (tile) {
-        case 0: case 1: case 2: case 3: case 4: case 8: case 12: case 26: case 27: return true;
-        default: return false;
-    }
+    const TileX3 *t = row_x3(tile);
+    return launch_row(t, t ? t->launch2 : nullptr, a, out_f32, s);
 }
 
 }  // namespace y3

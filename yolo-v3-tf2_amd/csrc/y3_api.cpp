@@ -301,14 +301,17 @@ hipError_t upload(P *&dev, const std::vector<T> &host)
     return hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
 }
 
+// Does the tile divide the conv (y3::tile_fits)?  cout_pad: the padded Cout of the mode's weights (ConvSlot::cout_pad / cout_pad64)
+bool fits(const y3::TileInfo &t, const ConvSlot &c, int cout_pad) { return y3::tile_fits(t, c.d.cin, c.d.src1 >= 0 ? c.d.c0 : -1, cout_pad); }
+
 // The first candidate tile that fits the conv and gives at least `want` workgroups for M rows over `cout_pad` channels; the last
 // candidate when none does.
-template <size_t N, class Fits>
-int first_reaching(const int (&cand)[N], y3::TileInfo (*info)(int), long long M, int cout_pad, long long want, Fits fits)
+template <size_t N>
+int first_reaching(const int (&cand)[N], y3::TileInfo (*info)(int), const ConvSlot &c, int cout_pad, long long M, long long want)
 {
     for (int t : cand) {
         const y3::TileInfo s = info(t);
-        if (fits(s) && ((M + s.bm - 1) / s.bm) * (cout_pad / s.bn) >= want) return t;
+        if (fits(s, c, cout_pad) && ((M + s.bm - 1) / s.bm) * (cout_pad / s.bn) >= want) return t;
     }
     return cand[N - 1];
 }
@@ -317,29 +320,16 @@ int choose_tile_x2(const ConvSlot &c, long long M)
 {
     // widest tile that still gives every CU at least two workgroups
     static constexpr int wide[] = {4, 8, 0, 3, 2}, narrow[] = {1, 2};
-    auto fits = [&](const y3::TileInfo &s) { return !(c.cout_pad64 % s.bn || c.d.cin % s.stages || (c.d.src1 >= 0 && c.d.c0 % s.stages)); };
-    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
-    return first_reaching(narrow, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
+    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
+    return first_reaching(narrow, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
 }
 
 int choose_tile_x3(const ConvSlot &c, long long M)
 {
     static constexpr int wide[] = {0, 3, 2}, narrow[] = {1, 2};
-    auto fits = [&](const y3::TileInfo &s) { return c.cout_pad64 % s.bn == 0; };
-    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
-    return first_reaching(narrow, y3::conv_x3_tile_info, M, c.cout_pad64, 512, fits);
+    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
+    return first_reaching(narrow, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
 }
-
-// What the two plane-split modes (three bf16 planes, two fp16 planes per value) differ in at launch time
-struct PlaneSplit {
-    void *ConvSlot::*w;     // packed weights
-    int planes;
-    int ConvSlot::*tile;    // forced tile (y3_net_set_tile_x3 / _x2), -1: the chooser's
-    int (*choose)(const ConvSlot &, long long);
-    hipError_t (*launch)(const y3::ConvArgs &, int, bool, hipStream_t);
-};
-constexpr PlaneSplit X3_SPLIT = {&ConvSlot::wx3_dev, 3, &ConvSlot::tile_x3, choose_tile_x3, y3::launch_conv_f32x3};
-constexpr PlaneSplit X2_SPLIT = {&ConvSlot::wx2_dev, 2, &ConvSlot::tile_x2, choose_tile_x2, y3::launch_conv_f32x2};
 
 // M = rows of this call (per lane); M_plan = rows of the planned batch.  The MFMA SHAPE (16x16x32 vs 32x32x16: two K groupings,
 // results differ in the last bits) is decided from plan-time quantities only, so that an image's result does not depend on the
@@ -350,7 +340,6 @@ int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16
         y3::TileInfo s = y3::conv_bf16_tile_info(t);
         return ((M + s.bm - 1) / s.bm) * (c.cout_pad / s.bn);
     };
-    auto fits = [&](const y3::TileInfo &s) { return c.cout_pad % s.bn == 0; };
     // large 3x3 convs: the 16x16x32 form once the PLANNED batch fills the chip with 256x256 tiles of 16 waves (tile 24 wins every
     // such signature of the 64- and 128-image tables, tuning/bf16_b*_s416.json); smaller calls of the same plan take the 128x128 /
     // 64x128 tiles of the same MFMA shape (27, 29)
@@ -364,10 +353,10 @@ int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16
     static constexpr int bk32[] = {5, 6},    // BK = 32 (Cin = 32 layers, Cout = 64)
                          n128[] = {8, 12, 11},   // LDS-DMA variants: 128x128, 64x128, 64x64
                          n64[] = {10, 11}, n32[] = {4};
-    if (c.d.cin % 64) return first_reaching(bk32, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
-    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
-    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
-    return first_reaching(n32, y3::conv_bf16_tile_info, M, c.cout_pad, 512, fits);
+    if (c.d.cin % 64) return first_reaching(bk32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    return first_reaching(n32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
 }
 
 // channels per K chunk of a 3x3 fp32 conv when the caller has not chosen (y3_net_set_k_chunk(-1)); Y3_K_CHUNK overrides (tools)
@@ -414,10 +403,9 @@ int choose_tile(const ConvSlot &c, long long M)
     // measured on MI355X (tools/tune_tiles.py): many co-resident waves beat big wave tiles for the 64-cycle
     // fp32 MFMA; prefer the largest block tile that still yields >= 2 workgroups per CU
     static constexpr int n128[] = {10, 11}, n64[] = {11}, n32[] = {8};
-    auto any = [](const y3::TileInfo &) { return true; };
-    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_tile_info, M, c.cout_pad, 1024, any);
-    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_tile_info, M, c.cout_pad, 1024, any);
-    return first_reaching(n32, y3::conv_tile_info, M, c.cout_pad, 1024, any);
+    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_tile_info, c, c.cout_pad, M, 1024);
+    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_tile_info, c, c.cout_pad, M, 1024);
+    return first_reaching(n32, y3::conv_tile_info, c, c.cout_pad, M, 1024);
 }
 
 }  // namespace
@@ -477,6 +465,89 @@ static bool output_staged(const y3_net *net, int t)
 // bytes per element of an arena tensor: fp32, bf16, three bf16 planes, or two fp16 planes (4 bytes as well)
 static size_t arena_elem_bytes(int dtype) { return dtype == Y3_DTYPE_BF16 ? 2 : dtype == Y3_DTYPE_F32X3 ? 6 : 4; }
 
+// One conv family per plan mode (Y3_DTYPE_*): its tile table (y3_tile_built), the tile a caller forced on a conv and the texts with which
+// its setter refuses one (y3_net_set_tile*).
+struct ConvFamily {
+    int count;                                     // tile ids are [0, count)
+    y3::TileInfo (*info)(int);
+    bool (*built)(int);
+    int ConvSlot::*tile;                           // forced tile, -1: the chooser's
+    int ConvSlot::*cout_pad;                       // padded Cout of the mode's packed weights
+    const char *bad, *retired, *misfit;            // refusals: bad argument, retired id (format: the id), tile does not fit the conv
+    int resident;                                  // id of the weight-resident kernel, -1: none
+    y3_status (*resident_rule)(const y3_net *, const ConvSlot &, int slot);   // its own shape rule
+};
+// ... and what the two plane-split modes (three bf16 planes, two fp16 planes per value) differ in at launch time
+struct PlaneSplit : ConvFamily {
+    void *ConvSlot::*w;     // packed weights
+    int planes;
+    int (*choose)(const ConvSlot &, long long);
+    hipError_t (*launch)(const y3::ConvArgs &, int, bool, hipStream_t);
+};
+
+static y3_status resident_rule_f32(const y3_net *, const ConvSlot &c, int)
+{
+    if (!(c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && c.d.cin == 32 && c.d.cout % 64 == 0))
+        return fail(Y3_ERR_INVALID, "y3_net_set_tile: tile 33 (weight-resident) needs a 3x3 / stride-1 conv with 32 input channels and Cout %% 64 == 0");
+    return Y3_OK;
+}
+
+static y3_status resident_rule_bf16(const y3_net *net, const ConvSlot &c, int slot)
+{
+    if (!(c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && (c.d.cin == 32 || c.d.cin == 64) && c.d.cout % 64 == 0))
+        return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile 32 (weight-resident) needs a 3x3 / stride-1 conv with 32 or 64 input channels and Cout %% 64 == 0");
+    // tile 32 stores bf16 only: a conv whose destination is a net output that the forward hands over as fp32 straight from the launch
+    // (not read again inside the net, no shortcut: y3_net_plan does not stage it) cannot take it -- refused here, by name, instead of a
+    // launch error in the forward
+    if (is_output(net, c.d.dst) && !output_staged(net, c.d.dst))
+        return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile 32 (weight-resident) stores bf16 only; conv %d writes an fp32 net output", slot);
+    return Y3_OK;
+}
+
+static constexpr ConvFamily F32_FAMILY = {
+    y3::TILE_COUNT, y3::conv_tile_info, y3::conv_tile_built, &ConvSlot::tile, &ConvSlot::cout_pad,
+    "y3_net_set_tile: bad argument", "y3_net_set_tile: tile id %d is retired (the timing ablations of rounds 1-2; y3_tile_built)",
+    "y3_net_set_tile: tile does not divide Cout", 33, resident_rule_f32};
+static constexpr ConvFamily BF16_FAMILY = {
+    y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
+    "y3_net_set_tile_bf16: bad argument",
+    "y3_net_set_tile_bf16: tile id %d is retired (20: the pipelined tile of round 2; 33..36: tap-row reuse and the four-wave tile of round 4; y3_tile_built)",
+    "y3_net_set_tile_bf16: tile does not fit this conv", 32, resident_rule_bf16};
+static constexpr PlaneSplit X3_SPLIT = {
+    {y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x3_tile_built, &ConvSlot::tile_x3, &ConvSlot::cout_pad64,
+     "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: tile does not fit this conv", -1, nullptr},
+    &ConvSlot::wx3_dev, 3, choose_tile_x3, y3::launch_conv_f32x3};
+static constexpr PlaneSplit X2_SPLIT = {
+    {y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x2_tile_built, &ConvSlot::tile_x2, &ConvSlot::cout_pad64,
+     "y3_net_set_tile_x2: bad argument", "y3_net_set_tile_x2: tile does not fit this conv", "y3_net_set_tile_x2: tile does not fit this conv", -1, nullptr},
+    &ConvSlot::wx2_dev, 2, choose_tile_x2, y3::launch_conv_f32x2};
+
+static const ConvFamily *conv_family(int dtype)
+{
+    switch (dtype) {
+        case Y3_DTYPE_F32: return &F32_FAMILY;
+        case Y3_DTYPE_BF16: return &BF16_FAMILY;
+        case Y3_DTYPE_F32X3: return &X3_SPLIT;
+        case Y3_DTYPE_F32X2: return &X2_SPLIT;
+        default: return nullptr;
+    }
+}
+
+// The one body of y3_net_set_tile / _bf16 / _x3 / _x2: a built id that fits the conv (-1: back to the tuning table / the heuristic)
+static y3_status set_forced_tile(const ConvFamily &f, y3_net *net, int slot, int tile)
+{
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || tile >= f.count) return fail(Y3_ERR_INVALID, "%s", f.bad);
+    ConvSlot &c = net->convs[slot];
+    if (tile >= 0) {
+        if (!f.built(tile)) return fail(Y3_ERR_INVALID, f.retired, tile);
+        if (c.first_layer || !fits(f.info(tile), c, c.*f.cout_pad)) return fail(Y3_ERR_INVALID, "%s", f.misfit);
+        if (tile == f.resident)
+            if (y3_status st = f.resident_rule(net, c, slot); st != Y3_OK) return st;
+    }
+    c.*f.tile = tile;
+    return Y3_OK;
+}
+
 extern "C" {
 
 int y3_version(void) { return 100; }
@@ -492,13 +563,8 @@ int y3_device_count(void)
 
 int y3_tile_built(int dtype, int tile)
 {
-    switch (dtype) {
-        case Y3_DTYPE_F32: return y3::conv_tile_built(tile) ? 1 : 0;
-        case Y3_DTYPE_BF16: return y3::conv_bf16_tile_built(tile) ? 1 : 0;
-        case Y3_DTYPE_F32X3: return (tile >= 0 && tile < y3::X3_TILE_COUNT && y3::conv_x3_tile_built(tile)) ? 1 : 0;
-        case Y3_DTYPE_F32X2: return (tile >= 0 && tile < y3::X3_TILE_COUNT && y3::conv_x2_tile_built(tile)) ? 1 : 0;
-        default: return 0;
-    }
+    const ConvFamily *f = conv_family(dtype);
+    return (f && f->built(tile)) ? 1 : 0;
 }
 
 y3_status y3_net_create(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
@@ -627,74 +693,25 @@ Y3_CATCH("y3_net_set_conv_weights")
 
 y3_status y3_net_set_tile(y3_net *net, int slot, int tile)
 try {
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || tile >= y3::TILE_COUNT)
-        return fail(Y3_ERR_INVALID, "y3_net_set_tile: bad argument");
-    ConvSlot &c = net->convs[slot];
-    if (tile >= 0) {
-        if (!y3::conv_tile_built(tile))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile: tile id %d is retired (the timing ablations of rounds 1-2; y3_tile_built)", tile);
-        y3::TileInfo s = y3::conv_tile_info(tile);
-        if (c.first_layer || c.cout_pad % s.bn) return fail(Y3_ERR_INVALID, "y3_net_set_tile: tile does not divide Cout");
-        if (tile == 33 && !(c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && c.d.cin == 32 && c.d.cout % 64 == 0))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile: tile 33 (weight-resident) needs a 3x3 / stride-1 conv with 32 input channels and Cout %% 64 == 0");
-    }
-    c.tile = tile;
-    return Y3_OK;
+    return set_forced_tile(F32_FAMILY, net, slot, tile);
 }
 Y3_CATCH("y3_net_set_tile")
 
 y3_status y3_net_set_tile_bf16(y3_net *net, int slot, int tile)
 try {
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || tile >= y3::BF16_TILE_COUNT)
-        return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: bad argument");
-    ConvSlot &c = net->convs[slot];
-    if (tile >= 0) {
-        if (!y3::conv_bf16_tile_built(tile))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile id %d is retired (20: the pipelined tile of round 2; 33..36: tap-row reuse and the four-wave tile of round 4; y3_tile_built)", tile);
-        y3::TileInfo s = y3::conv_bf16_tile_info(tile);
-        if (c.first_layer || c.cout_pad % s.bn || c.d.cin % s.stages || (c.d.src1 >= 0 && c.d.c0 % s.stages))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile does not fit this conv");
-        if (tile == 32 && !(c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && (c.d.cin == 32 || c.d.cin == 64) && c.d.cout % 64 == 0))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile 32 (weight-resident) needs a 3x3 / stride-1 conv with 32 or 64 input channels and Cout %% 64 == 0");
-        // tile 32 stores bf16 only: a conv whose destination is a net output that the forward hands over as fp32 straight from the launch
-        // (not read again inside the net, no shortcut: y3_net_plan does not stage it) cannot take it -- refused here, by name, instead of a
-        // launch error in the forward
-        if (tile == 32 && is_output(net, c.d.dst) && !output_staged(net, c.d.dst))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile 32 (weight-resident) stores bf16 only; conv %d writes an fp32 net output", slot);
-    }
-    c.tile_bf16 = tile;
-    return Y3_OK;
+    return set_forced_tile(BF16_FAMILY, net, slot, tile);
 }
 Y3_CATCH("y3_net_set_tile_bf16")
 
 y3_status y3_net_set_tile_x3(y3_net *net, int slot, int tile)
 try {
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || tile >= y3::X3_TILE_COUNT || (tile >= 0 && !y3::conv_x3_tile_built(tile)))
-        return fail(Y3_ERR_INVALID, "y3_net_set_tile_x3: bad argument");
-    ConvSlot &c = net->convs[slot];
-    if (tile >= 0) {
-        y3::TileInfo s = y3::conv_x3_tile_info(tile);
-        if (c.first_layer || c.cout_pad64 % s.bn || c.d.cin % s.stages || (c.d.src1 >= 0 && c.d.c0 % s.stages))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile_x3: tile does not fit this conv");
-    }
-    c.tile_x3 = tile;
-    return Y3_OK;
+    return set_forced_tile(X3_SPLIT, net, slot, tile);
 }
 Y3_CATCH("y3_net_set_tile_x3")
 
 y3_status y3_net_set_tile_x2(y3_net *net, int slot, int tile)
 try {
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || tile >= y3::X3_TILE_COUNT)
-        return fail(Y3_ERR_INVALID, "y3_net_set_tile_x2: bad argument");
-    ConvSlot &c = net->convs[slot];
-    if (tile >= 0) {
-        y3::TileInfo s = y3::conv_x3_tile_info(tile);
-        if (!y3::conv_x2_tile_built(tile) || c.first_layer || c.cout_pad64 % s.bn || c.d.cin % s.stages ||
-            (c.d.src1 >= 0 && c.d.c0 % s.stages))
-            return fail(Y3_ERR_INVALID, "y3_net_set_tile_x2: tile does not fit this conv");
-    }
-    c.tile_x2 = tile;
-    return Y3_OK;
+    return set_forced_tile(X2_SPLIT, net, slot, tile);
 }
 Y3_CATCH("y3_net_set_tile_x2")
 

@@ -58,9 +58,28 @@ inline hipError_t set_max_lds_once(LdsAttrOnce &st, const void *fn, int bytes, i
     return e;
 }
 
-// tile configurations of the fp32 MFMA kernel (index into the table in conv_f32.hip)
+// The tail every MFMA conv launcher shares: the dynamic-LDS attribute once per (instantiation, device), the launch, its status.
+template <auto KERNEL>
+static hipError_t launch_conv_kernel(const ConvArgs &a, int grid, int threads, size_t lds, hipStream_t s)
+{
+    if (lds > 160 * 1024) return hipErrorInvalidValue;
+    static LdsAttrOnce attr;  // per instantiation
+    if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(KERNEL), (int)lds, a.device); e != hipSuccess) return e;
+    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), lds, s, a);
+    return hipGetLastError();
+}
+
+// One tile configuration of an MFMA conv kernel: block tile bm x bn, waves per workgroup, LDS stages, K tile.  Every conv file keeps one
+// table of {TileInfo, launcher(s)} rows indexed by tile id; a retired id is an all-zero row with no launcher.
+struct TileInfo { int bm, bn, waves, stages, bk; };
+// Does the tile divide the conv?  c0: channels of the first source of a concat conv, -1 without a second source.
+inline bool tile_fits(const TileInfo &t, int cin, int c0, int cout_pad)
+{
+    return t.bm > 0 && cin % t.bk == 0 && cout_pad % t.bn == 0 && (c0 < 0 || c0 % t.bk == 0);
+}
+
+// fp32 MFMA kernel (table in conv_f32.hip; bk = 32)
 static constexpr int TILE_COUNT = 34;  // 33: the weight-resident 3x3 kernel (conv_res_f32.hip); ids without a selecting plan are retired (conv_f32.hip)
-struct TileInfo { int bm, bn, waves, stages; };
 TileInfo conv_tile_info(int tile);
 bool conv_tile_built(int tile);        // false: retired id
 
@@ -108,7 +127,7 @@ struct StemArgs {
 hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s);
 hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s);   // conv0 on bf16 MFMA from split (hi + lo) operands (~2^-16 per product), bf16 patch, conv1 on bf16 MFMA
 
-// bf16 path (conv_bf16.hip); TileInfo.stages holds BK for these tiles
+// bf16 path (conv_bf16.hip)
 static constexpr int BF16_TILE_COUNT = 37;   // 32: the weight-resident 3x3 kernel (conv_res_bf16.hip); 20, 33..36: retired ids
 TileInfo conv_bf16_tile_info(int tile);
 bool conv_bf16_tile_built(int tile);
@@ -117,14 +136,14 @@ hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream
 bool conv_res_bf16_fits(const ConvArgs &a);
 hipError_t launch_conv_res_bf16(const ConvArgs &a, hipStream_t s);
 
-// fp32-accurate path on the bf16 matrix cores, three bf16 planes per value (conv_f32x3.hip); TileInfo.stages holds BK
+// fp32-accurate path on the bf16 matrix cores, three bf16 planes per value (conv_f32x3.hip)
 static constexpr int X3_TILE_COUNT = 34;
 TileInfo conv_x3_tile_info(int tile);
 hipError_t launch_conv_f32x3(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
 // two fp16 planes per value on the fp16 matrix cores (same kernel, same tile ids; a subset is instantiated)
 hipError_t launch_conv_f32x2(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
-bool conv_x2_tile_built(int tile);
-bool conv_x3_tile_built(int tile);
+bool conv_x3_tile_built(int tile);     // 9, 13, 14: three planes only
+bool conv_x2_tile_built(int tile);     // 26, 27: two planes only
 
 hipError_t launch_add(const float *a, const float *b, float *y, size_t n, hipStream_t s);
 hipError_t launch_upsample2x(const float *x, int B, int H, int W, int C, float *y, hipStream_t s);

@@ -319,6 +319,46 @@ y3_status y3_unletterbox_detections(void *packed_dev, const int32_t *num_valid_d
                                     int max_boxes, int image_size, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Evaluation counters for every NMS score threshold of a sweep, from ONE detect pass (reference:
+ * evaluate_detections.py:37-48,82-135, EvaluateDetections.iou_alg / evaluate; evaluate_yolov3.py:153-232, the loop over
+ * evaluate_nms_score_thresholds that the reference runs as one whole pass over the data set per threshold).
+ * The greedy padded NMS suppresses a box only by survivors scored above it, so the detections at a higher score threshold are
+ * the rows of the lowest threshold's result with score > threshold, in the same order: packed_dev [batch,max_boxes,7] and
+ * num_valid_dev [batch] are what y3_net_detect (at the lowest threshold of the sweep), y3_pack_detections or
+ * y3_unletterbox_detections leave behind.  Ground truth: gt_boxes_dev [batch,max_gt,4] {xmin,ymin,xmax,ymax}, gt_classes_dev
+ * [batch,max_gt] int32, the first gt_count_dev[b] rows of image b (counts are clamped to [0,max_gt], num_valid to [0,max_boxes]).
+ * score_thresholds_host [n_thresholds] is read during the call (the thresholds travel in the kernel arguments).
+ * Per image b and threshold t, exactly EvaluateDetections.evaluate, quirks included:
+ *   predictions     rows r < num_valid[b] with score[r] > S_t (strict, fp32)
+ *   one_class != 0  every prediction class and every ground-truth class is taken as 0
+ *   error image     a ground-truth class outside [0,nclasses): errors[t] += 1 and nothing else is counted; likewise (never from
+ *                   y3_net_detect) a class outside the range among the predictions of threshold t
+ *   IoU             fp32, each operation rounded on its own: ow = max(min(x2,x2') - max(x1,x1'), 0), oh likewise, inter = ow*oh,
+ *                   iou = inter / ((a1 + a2) - inter); true division, no epsilon; min / max pass a NaN on
+ *   best            the ground-truth row with the first maximum IoU as np.argmax takes it: a NaN (0/0 between two zero-area
+ *                   boxes that do not overlap) counts as the maximum
+ *   decision        iou[best] > iou_threshold && class[gt best] == class[pred]; false with no ground truth.  Every prediction
+ *                   is tested against the EMPTY assignment (two predictions that pick the same ground-truth box are both TP);
+ *                   `assigned` (some prediction decided for the row) only feeds fn
+ *   counters        tp[c_pred] += decision, fp[c_pred] += !decision, preds[c_pred] += 1, gts[c_gt] += 1,
+ *                   fn[c_gt] += !assigned, examples[t] += 1
+ * counters_dev: int64 [n_thresholds][5*nclasses + 2] = preds, gts, tp, fp, fn (each [nclasses]), errors, examples.
+ * ADDED to (never zeroed by) the call, so one buffer accumulates a data set; integer adds commute, the result does not depend
+ * on any order.  Checked on the host before anything is enqueued (Y3_ERR_INVALID with a message): batch >= 1, max_boxes in
+ * [1,1024], max_gt in [1,1024], nclasses in [1,4096], n_thresholds in [1,16], no null pointer.  The call only enqueues on
+ * `stream` -- no allocation, query or synchronise -- and can be captured into a HIP graph (the thresholds are then frozen in).
+ * One exception: a launch that needs more than 64 KB of LDS (20 max_gt + 20 nclasses bytes: beyond ~2000 classes) asks for the
+ * current device, and the first such launch on a device raises the kernel's LDS limit once (hipFuncSetAttribute), as the conv
+ * launches of y3_net_forward do.
+ * Host restatement: evaluate_detections.sweep_counters.
+ * ---------------------------------------------------------------------------------------- */
+y3_status y3_evaluate_detections(const void *packed_dev, const int32_t *num_valid_dev, int batch, int max_boxes,
+                                 const float *gt_boxes_dev /*[batch,max_gt,4]*/, const int32_t *gt_classes_dev /*[batch,max_gt]*/,
+                                 const int32_t *gt_count_dev /*[batch]*/, int max_gt, int nclasses, float iou_threshold,
+                                 const float *score_thresholds_host, int n_thresholds, int one_class,
+                                 int64_t *counters_dev, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU exchange (no reference counterpart: the reference is single-device).
  * One process per GPU; images are sharded by rank and are independent end to end, so the only collective of the path
  * is the all-gather of the packed final detections (north_star: "RCCL all-gather of the final box list over xGMI").

@@ -1552,6 +1552,33 @@ try {
 }
 Y3_CATCH("y3_unletterbox_detections")
 
+y3_status y3_evaluate_detections(const void *packed_dev, const int32_t *num_valid_dev, int batch, int max_boxes,
+                                 const float *gt_boxes_dev, const int32_t *gt_classes_dev, const int32_t *gt_count_dev, int max_gt,
+                                 int nclasses, float iou_threshold, const float *score_thresholds_host, int n_thresholds,
+                                 int one_class, int64_t *counters_dev, void *stream)
+try {
+    if (!packed_dev || !num_valid_dev || !gt_boxes_dev || !gt_classes_dev || !gt_count_dev || !score_thresholds_host || !counters_dev)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: null pointer");
+    if (batch < 1) return fail(Y3_ERR_INVALID, "y3_evaluate_detections: batch must be at least 1 (got %d)", batch);
+    if (max_boxes < 1 || max_boxes > y3::kEvalMaxBoxes)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: max_boxes must be in [1,%d] (got %d)", y3::kEvalMaxBoxes, max_boxes);
+    if (max_gt < 1 || max_gt > y3::kEvalMaxGt)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: max_gt must be in [1,%d] (got %d)", y3::kEvalMaxGt, max_gt);
+    if (nclasses < 1 || nclasses > y3::kEvalMaxClasses)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: nclasses must be in [1,%d] (got %d)", y3::kEvalMaxClasses, nclasses);
+    if (n_thresholds < 1 || n_thresholds > y3::kEvalMaxThresholds)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: n_thresholds must be in [1,%d] (got %d)", y3::kEvalMaxThresholds, n_thresholds);
+    if (((uintptr_t)packed_dev & 3) || ((uintptr_t)gt_boxes_dev & 3) || ((uintptr_t)counters_dev & 7))
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: packed / gt_boxes not 4-byte or counters not 8-byte aligned");
+    y3::EvalThresholds thr{};
+    for (int t = 0; t < n_thresholds; ++t) thr.s[t] = score_thresholds_host[t];
+    hipError_t e = y3::launch_evaluate(packed_dev, num_valid_dev, batch, max_boxes, gt_boxes_dev, gt_classes_dev, gt_count_dev, max_gt,
+                                       nclasses, iou_threshold, thr, n_thresholds, one_class != 0, counters_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_evaluate_detections launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_evaluate_detections")
+
 // ------------------------------------------------------------------------------------------ TFRecord checksum
 uint32_t y3_crc32c(const void *data_host, size_t nbytes)
 {

@@ -186,6 +186,15 @@ constexpr int kUnletterboxTableImages = 64;
 struct UnletterboxTable { LetterboxGeom g[kUnletterboxTableImages]; };
 hipError_t launch_unletterbox(void *packed, const int32_t *nv, const LetterboxGeom *geoms, int n, int M, int S, hipStream_t s);
 
+// Evaluation counters (evaluate.hip; include/y3.h, y3_evaluate_detections).  The score thresholds of one launch travel by value in the
+// kernel arguments, like the letterbox geometries.
+constexpr int kEvalMaxBoxes = 1024, kEvalMaxGt = 1024, kEvalMaxClasses = 4096, kEvalMaxThresholds = 16;
+struct EvalThresholds { float s[kEvalMaxThresholds]; };
+size_t evaluate_lds_bytes(int max_gt, int nclasses);
+hipError_t launch_evaluate(const void *packed, const int32_t *nv, int B, int M, const float *gt_boxes, const int32_t *gt_classes,
+                           const int32_t *gt_count, int G, int nc, float iou_thr, const EvalThresholds &thr, int T, int one_class,
+                           int64_t *counters, hipStream_t s);
+
 size_t nms_workspace_bytes(int B, int N);
 hipError_t launch_nms(const float *boxes, const float *scores, int B, int N, int M, float T, float S, int32_t *sel,
                       int32_t *num_valid, void *ws, hipStream_t s);

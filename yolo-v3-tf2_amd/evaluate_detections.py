@@ -5,6 +5,9 @@ counters from IoU matching of one image's predictions against its ground truth. 
 vectorised quirk of the reference: every prediction is matched against the *initial* (empty) assignment vector
 (reference: evaluate_detections.py:107-112), so two predictions that pick the same ground-truth box both count as
 true positives; the assignment vector only feeds the false-negative count.
+
+`sweep_counters` restates, in NumPy, what the device kernel behind y3_evaluate_detections computes (csrc/evaluate.hip): the
+counters of every NMS score threshold of a sweep from ONE set of packed detections, taken at the lowest threshold.
 """
 from __future__ import annotations
 
@@ -66,3 +69,80 @@ class EvaluateDetections:
     def recall_precision(self):
         tp, fp, fn = (self.counters[k].sum() for k in ("tp", "fp", "fn"))
         return tp / max(tp + fn, 1), tp / max(tp + fp, 1)
+
+
+COUNTER_KEYS = ("preds", "gts", "tp", "fp", "fn")    # the per-class blocks of a counters row, in order; then errors, examples
+
+
+def counters_from_row(row, nclasses):
+    """One row [5*nclasses + 2] of sweep_counters / y3_evaluate_detections -> the dict EvaluateDetections.counters has."""
+    row = np.asarray(row, np.int64).reshape(-1)
+    if row.size != 5 * nclasses + 2:
+        raise ValueError(f"a counters row of {nclasses} classes has {5 * nclasses + 2} entries, got {row.size}")
+    c = {k: row[i * nclasses:(i + 1) * nclasses].copy() for i, k in enumerate(COUNTER_KEYS)}
+    c["errors"], c["examples"] = int(row[5 * nclasses]), int(row[5 * nclasses + 1])
+    return c
+
+
+def sweep_counters(packed, num_valid, gt_boxes, gt_classes, gt_count, nclasses, iou_threshold, score_thresholds,
+                   one_class=False):
+    """Host restatement of y3_evaluate_detections (include/y3.h), no GPU: packed [B,M,7] int32 words and num_valid [B] as
+    Net.detect leaves them at the LOWEST score threshold of the sweep, padded ground truth (gt_boxes [B,G,4] f32, gt_classes
+    [B,G] i32, gt_count [B]) -> int64 [T, 5*nclasses + 2]: per threshold preds, gts, tp, fp, fn (each [nclasses]), errors,
+    examples.  The greedy padded NMS never lets a box be affected by boxes scored below it, so the detections at threshold t
+    are the rows r < num_valid with score[r] > t (strict, fp32), and on those rows the counters are EvaluateDetections.evaluate
+    exactly.  one_class: every class id is taken as 0.  A prediction class outside [0,nclasses) among the rows of a threshold
+    (EvaluateDetections would raise) makes the image an error image at that threshold, like a bad ground-truth class does."""
+    packed = np.ascontiguousarray(packed, np.int32)
+    if packed.ndim != 3 or packed.shape[2] != 7:
+        raise ValueError("packed must be [B,M,7] int32 words")
+    B, M = packed.shape[:2]
+    gt_boxes = np.ascontiguousarray(gt_boxes, np.float32).reshape(B, -1, 4)
+    G = gt_boxes.shape[1]
+    gt_classes = np.asarray(gt_classes).astype(np.int64).reshape(B, G)
+    num_valid = np.clip(np.asarray(num_valid).astype(np.int64).reshape(B), 0, M)
+    gt_count = np.clip(np.asarray(gt_count).astype(np.int64).reshape(B), 0, G)
+    thresholds = np.asarray(score_thresholds, np.float32).reshape(-1)
+    iou_thresh = np.float32(iou_threshold)
+    nc = int(nclasses)
+    out = np.zeros((len(thresholds), 5 * nc + 2), np.int64)
+    boxes = packed[..., :4].copy().view(np.float32)
+    scores = packed[..., 4].copy().view(np.float32)
+    for b in range(B):
+        n, g = int(num_valid[b]), int(gt_count[b])
+        pb, pc, ps = boxes[b, :n], packed[b, :n, 5].astype(np.int64), scores[b, :n]
+        gb, gc = gt_boxes[b, :g], gt_classes[b, :g]
+        if one_class:
+            pc, gc = np.zeros_like(pc), np.zeros_like(gc)
+        if ((gc < 0) | (gc >= nc)).any():
+            out[:, 5 * nc] += 1
+            continue
+        best = np.zeros(n, np.int64)
+        decisions = np.zeros(n, bool)
+        if n and g:
+            with np.errstate(invalid="ignore", divide="ignore"):
+                ow = np.maximum(np.minimum(pb[:, None, 2], gb[None, :, 2]) - np.maximum(pb[:, None, 0], gb[None, :, 0]), np.float32(0))
+                oh = np.maximum(np.minimum(pb[:, None, 3], gb[None, :, 3]) - np.maximum(pb[:, None, 1], gb[None, :, 1]), np.float32(0))
+                inter = ow * oh
+                a1 = ((pb[:, 2] - pb[:, 0]) * (pb[:, 3] - pb[:, 1]))[:, None]
+                a2 = ((gb[:, 2] - gb[:, 0]) * (gb[:, 3] - gb[:, 1]))[None, :]
+                iou = inter / (a1 + a2 - inter)                                  # [n,g] fp32
+                best = iou.argmax(axis=1)                                        # first maximum; a NaN counts as the maximum
+                decisions = (iou[np.arange(n), best] > iou_thresh) & (gc[best] == pc)
+        for t, thr in enumerate(thresholds):
+            active = ps > thr
+            c = pc[active]
+            if ((c < 0) | (c >= nc)).any():
+                out[t, 5 * nc] += 1
+                continue
+            d = decisions[active]
+            assigned = np.zeros(g, bool)
+            assigned[best[active][d]] = True
+            row = out[t]
+            row[0 * nc:1 * nc] += np.bincount(c, minlength=nc)
+            row[1 * nc:2 * nc] += np.bincount(gc, minlength=nc)
+            row[2 * nc:3 * nc] += np.bincount(c[d], minlength=nc)
+            row[3 * nc:4 * nc] += np.bincount(c[~d], minlength=nc)
+            row[4 * nc:5 * nc] += np.bincount(gc[~assigned], minlength=nc)
+            row[5 * nc + 1] += 1
+    return out

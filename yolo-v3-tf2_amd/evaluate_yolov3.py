@@ -4,8 +4,13 @@ TFRecord dataset -> batches through the GPU detect path -> per-image gather -> `
 recall / precision per NMS score threshold.  Same function names and argument meaning as the reference; NumPy arrays
 where it has tf tensors, Python lists where it has ragged tensors.  The reference script as shipped cannot run (it
 imports `decoded_output` but calls `yolo_decode`, evaluate_yolov3.py:23,109); the intended behaviour is built here.
+
+`evaluate(..., on_device=True)` gives the same results from ONE pass over the data set: one model, one y3_net_detect per
+batch at the lowest threshold, and the counters of every threshold counted on the GPU (runtime.Net.evaluate_stream).
 """
 from __future__ import annotations
+
+import collections
 
 import numpy as np
 import yaml
@@ -13,7 +18,7 @@ import yaml
 from .core.load_tfrecords import parse_tfrecords
 from .core.parse_model import Input, ParseModel
 from .core.utils import get_anchors, resize_image
-from .evaluate_detections import EvaluateDetections
+from .evaluate_detections import EvaluateDetections, counters_from_row
 from .inference import DetectModel
 
 
@@ -68,14 +73,73 @@ def calc_recal_precision(counters):
     return recall, precision
 
 
+def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_batches, weights, one_class, anchors_table, nclasses):
+    """One model and one pass: the un-stacked data set is batched here (images with unlike numbers of boxes may share a batch)
+    by a generator that Net.evaluate_stream draws from, so records are decoded while earlier batches run and the data set is
+    never held in memory; only the counters come back."""
+    S, batch_size = int(detect_config["image_size"]), int(detect_config["batch_size"])
+    model = create_model(detect_config["model_config_file"], nclasses, anchors_table, min(thresholds),
+                         detect_config["nms_iou_threshold"], detect_config["yolo_max_boxes"],
+                         detect_config.get("input_weights_path"), weights)
+    net = model.model._device_net()
+    if net.image_size != S or net.max_batch < batch_size:
+        net.plan(max(batch_size, net.max_batch), S)
+    dataset = parse_tfrecords(detect_config["tfrecords_dir"], image_size=S, max_bboxes=detect_config["yolo_max_boxes"],
+                              class_file=detect_config["classes_name_file"])
+    max_boxes = int(detect_config["yolo_max_boxes"])
+    truths = collections.deque()       # ground truth of the batches the stream has drawn and not yet counted (at most its depth)
+
+    def frames():
+        """One list of float32 [S,S,3] frames in [0,1] per batch (mode 0: the stage's resize to S x S is the identity), read
+        from the records as the stream asks for them; its ground truth is queued beside it."""
+        images, gt = [], []
+        for n, (image, y) in enumerate(dataset):
+            if max_batches is not None and n >= max_batches * batch_size:
+                break
+            y = y[y[..., 4] == 1]          # rows whose objectness column is 1: drops the zero padding (prepare_dataset)
+            images.append(image)
+            gt.append((y[:, 0:4], y[:, 5].astype(np.int32)))
+            if len(images) == batch_size:
+                truths.append(gt)
+                yield images
+                images, gt = [], []
+        if images:
+            truths.append(gt)
+            yield images
+
+    def ground_truth():
+        while truths:
+            yield truths.popleft()
+
+    out = net.evaluate_stream(frames(), ground_truth(), anchors_table, max_boxes, detect_config["nms_iou_threshold"],
+                              thresholds, nclasses, evaluate_iou_threshold=evaluate_iou_threshold,
+                              one_class="both" if one_class else False, mode=0, max_batch=batch_size,
+                              max_blob_bytes=batch_size * (S * S * 12 + 16), max_gt=max_boxes)
+    plain, one = out if one_class else (out, None)
+    results = []
+    for t, threshold in enumerate(thresholds):
+        counters = counters_from_row(plain[t], nclasses)
+        counters_oneclass = counters_from_row(one[t], nclasses) if one_class else EvaluateDetections(nclasses, evaluate_iou_threshold).counters
+        recall, precision = calc_recal_precision(counters)
+        results.append((threshold, recall, precision, counters, counters_oneclass))
+    return results
+
+
 def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshold=0.5, max_batches=20, weights=None,
-             one_class=True):
+             one_class=True, on_device=False):
     """The loop of reference evaluate_yolov3.py:153-232: for every score threshold build the detect model, run the
     first `max_batches` dataset batches (`dataset.take(20)` there), count, and report (recall, precision).
-    Returns [(threshold, recall, precision, counters, counters_oneclass)]."""
+    Returns [(threshold, recall, precision, counters, counters_oneclass)].
+    on_device=True: the same list from one model and ONE pass over the data set -- the detections at a higher score threshold
+    are the rows with score > threshold of the lowest threshold's, so every batch is detected once and the counters of all
+    thresholds are counted on the GPU (Net.evaluate_stream).  That route batches the un-stacked data set itself: images with
+    unlike numbers of boxes may share a batch, which the host route cannot stack."""
     anchors_table = np.asarray(get_anchors(detect_config["anchors_file"]), np.float32)
     class_names = [c.strip() for c in open(detect_config["classes_name_file"]).readlines()]
     nclasses = len(class_names)
+    if on_device:
+        return _evaluate_on_device(detect_config, list(evaluate_nms_score_thresholds), evaluate_iou_threshold, max_batches, weights,
+                                   one_class, anchors_table, nclasses)
     dataset = prepare_dataset(detect_config["tfrecords_dir"], detect_config["batch_size"], detect_config["image_size"],
                               detect_config["yolo_max_boxes"], detect_config["classes_name_file"])
     results = []
@@ -107,12 +171,14 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="config/detect_config.yaml")
     ap.add_argument("--evaluate-config", default="config/evaluate_config.yaml")
+    ap.add_argument("--on-device", action="store_true",
+                    help="one pass over the data set for all thresholds, counters computed on the GPU")
     a = ap.parse_args(argv)
     with open(a.evaluate_config) as s:
         thresholds = yaml.safe_load(s)["evaluate_nms_score_thresholds"]
     with open(a.config) as s:
         detect_config = yaml.safe_load(s)
-    print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in evaluate(detect_config, thresholds)])
+    print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in evaluate(detect_config, thresholds, on_device=a.on_device)])
 
 
 if __name__ == "__main__":

@@ -324,39 +324,59 @@ class Net:
         y3_unletterbox_detections runs behind y3_net_detect on the same stream, before the read-back.
         The net keeps its planned image size and is re-planned at most once, for max_batch images; the stage's blobs hold
         max_blob_bytes.  Both default to the largest list of `batches`, which must then be a list or tuple."""
+        M = int(max_boxes)
+        outs = {}       # ring slot -> pinned rows, pinned counts, event: made on the slot's first use
+        pending = []
+
+        def result(entry):
+            k, n = entry
+            packed_host, nv_host, done = outs[k]
+            done.synchronize()      # an event wait: the next batch's detect is already queued behind this one
+            return packed_host[:n].numpy().copy(), nv_host[:n].numpy().copy()
+
+        for i, handle, packed_dev, nv_dev, cur, stage in self._detect_batches(
+                "detect_stream", batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes, letterbox):
+            k, n = i % stage.depth, handle.batch.shape[0]
+            if k not in outs:
+                outs[k] = (torch.empty((stage.max_batch, M, 7), dtype=torch.int32, pin_memory=True),
+                           torch.empty((stage.max_batch,), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
+            packed_host, nv_host, done = outs[k]
+            packed_host[:n].copy_(packed_dev[:n], non_blocking=True)
+            nv_host[:n].copy_(nv_dev[:n], non_blocking=True)
+            done.record(cur)
+            pending.append((k, n))
+            if len(pending) == stage.depth:     # its output buffers are the next to be reused
+                yield result(pending.pop(0))
+        while pending:
+            yield result(pending.pop(0))
+
+    def _detect_batches(self, who, batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes,
+                        letterbox):
+        """The loop detect_stream and evaluate_stream share: a generator that stages batch i+1 on the InputStage's copy stream,
+        enqueues y3_net_detect (and, with letterbox, y3_unletterbox_detections) of batch i on the current stream, and yields
+        (i, handle, packed_dev, nv_dev, stream, stage) for the consumer to enqueue its own work on `stream` behind them.  The
+        device buffers are slot i % depth of a ring: the consumer's reads are ordered before their reuse by the stream."""
         if max_batch is None or max_blob_bytes is None:
             if not isinstance(batches, (list, tuple)):
-                raise Y3Error("detect_stream: pass max_batch and max_blob_bytes when `batches` is not a list or tuple")
+                raise Y3Error(f"{who}: pass max_batch and max_blob_bytes when `batches` is not a list or tuple")
             if max_batch is None:
                 max_batch = max((len(b) for b in batches), default=0)
             if max_blob_bytes is None:
                 max_blob_bytes = max((packed_nbytes(b) for b in batches), default=0)
         S = self.image_size
         if S <= 0:
-            raise Y3Error("detect_stream: plan() the net first (the image size is the plan's)")
+            raise Y3Error(f"{who}: plan() the net first (the image size is the plan's)")
         if depth < 2:
-            raise Y3Error("detect_stream: depth must be at least 2 (batch i+1 is staged while batch i is detected)")
+            raise Y3Error(f"{who}: depth must be at least 2 (batch i+1 is staged while batch i is detected)")
         if max_batch < 1:
             return
         stage = InputStage(S, max_batch, max(int(max_blob_bytes), 16), depth)
         if max_batch > self.max_batch:
             self.plan(max_batch, S)
         a = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 3, 2))
-        M = int(max_boxes)
         dev = stage.device
-        outs = [(torch.empty((max_batch, M, 7), dtype=torch.int32, device=dev),
-                 torch.empty((max_batch,), dtype=torch.int32, device=dev),
-                 torch.empty((max_batch, M, 7), dtype=torch.int32, pin_memory=True),
-                 torch.empty((max_batch,), dtype=torch.int32, pin_memory=True),
-                 torch.cuda.Event()) for _ in range(stage.depth)]
-        pending = []
-
-        def result(entry):
-            k, n = entry
-            _, _, packed_host, nv_host, done = outs[k]
-            done.synchronize()      # an event wait: the next batch's detect is already queued behind this one
-            return packed_host[:n].numpy().copy(), nv_host[:n].numpy().copy()
-
+        ring = [(torch.empty((max_batch, M, 7), dtype=torch.int32, device=dev),
+                 torch.empty((max_batch,), dtype=torch.int32, device=dev)) for _ in range(stage.depth)]
         it = iter(batches)
         first = next(it, None)
         handle = stage.submit(first, mode, letterbox) if first is not None else None
@@ -366,8 +386,8 @@ class Net:
             following = stage.submit(nxt, mode, letterbox) if nxt is not None else None   # batch i+1 goes in before detect of batch i
             cur = torch.cuda.current_stream()
             cur.wait_event(handle.ready)
-            k, n = i % stage.depth, handle.batch.shape[0]
-            packed_dev, nv_dev, packed_host, nv_host, done = outs[k]
+            n = handle.batch.shape[0]
+            packed_dev, nv_dev = ring[i % stage.depth]
             check(self.lib.y3_net_detect(self._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
                                          float(score_threshold), _dev(packed_dev), _dev(nv_dev), C.c_void_p(cur.cuda_stream)),
                   "y3_net_detect")
@@ -376,15 +396,82 @@ class Net:
                 g = handle.geometry
                 check(self.lib.y3_unletterbox_detections(_dev(packed_dev), _dev(nv_dev), g.ctypes.data_as(C.POINTER(C.c_int32)), n, M, S,
                                                          C.c_void_p(cur.cuda_stream)), "y3_unletterbox_detections")
-            packed_host[:n].copy_(packed_dev[:n], non_blocking=True)
-            nv_host[:n].copy_(nv_dev[:n], non_blocking=True)
-            done.record(cur)
-            pending.append((k, n))
-            if len(pending) == stage.depth:     # its output buffers are the next to be reused
-                yield result(pending.pop(0))
+            yield i, handle, packed_dev, nv_dev, cur, stage
             handle, i = following, i + 1
-        while pending:
-            yield result(pending.pop(0))
+
+    def evaluate_stream(self, batches, gts, anchors, max_boxes: int, iou_threshold: float, score_thresholds, nclasses: int,
+                        evaluate_iou_threshold: float = 0.5, one_class=False, mode=1, depth: int = 2,
+                        max_batch: Optional[int] = None, max_blob_bytes: Optional[int] = None, letterbox=False,
+                        max_gt: Optional[int] = None):
+        """Frames in host memory -> the evaluation counters of EVERY NMS score threshold, from one detect pass: NumPy int64
+        [T, 5*nclasses + 2] (rows as y3_evaluate_detections / evaluate_detections.counters_from_row name them), T =
+        len(score_thresholds).  one_class=True: every class id taken as 0; one_class="both": the pair (plain counters,
+        one-class counters) from the same pass.
+        batches as for detect_stream (the same InputStage pipeline and the same loop); gts: per batch, a list of per-image
+        (boxes [g,4], classes [g]) in normalised (xmin, ymin, xmax, ymax) -- with letterbox=True in the coordinates of the
+        frame that was handed in, like the rows detect_stream yields.
+        Per batch ONE y3_net_detect is enqueued, at min(score_thresholds): the detections of a higher threshold are its rows
+        with score > threshold.  The ground truth goes up through a small pinned buffer per ring slot, y3_evaluate_detections
+        accumulates into one device buffer, nothing is read back and the host waits for no result until the stream ends:
+        then T x (5*nclasses + 2) integers (twice that for "both") come back in one copy.
+        max_gt: the rows of ground truth the buffers hold per image.  By default the largest count of `gts`, which must then be
+        a list or tuple; with max_gt given, `gts` may be any iterable and is consumed one entry per batch, in step with
+        `batches` (a data set can then be streamed through without ever being held in memory).  The number of entries of `gts`
+        must equal the number of batches either way."""
+        thresholds = [float(t) for t in score_thresholds]
+        both = isinstance(one_class, str)
+        if both and one_class != "both":
+            raise Y3Error('evaluate_stream: one_class must be False, True or "both"')
+        if not 1 <= len(thresholds) <= 16:
+            raise Y3Error("evaluate_stream: 1 to 16 score thresholds")
+        if max_gt is None:
+            if not isinstance(gts, (list, tuple)):
+                raise Y3Error("evaluate_stream: pass max_gt when `gts` is not a list or tuple")
+            G = max((len(np.asarray(c).reshape(-1)) for g in gts for _, c in g), default=0) or 1
+        else:
+            G = int(max_gt)
+        gt_iter, missing = iter(gts), object()
+        nc, M, T = int(nclasses), int(max_boxes), len(thresholds)
+        variants = (0, 1) if both else (int(bool(one_class)),)
+        thr = np.asarray(thresholds, np.float32)
+        counters = None
+        slots = {}      # ring slot -> pinned ground-truth words, their device copy, "copied" event
+        for i, handle, packed_dev, nv_dev, cur, stage in self._detect_batches(
+                "evaluate_stream", batches, anchors, M, iou_threshold, min(thresholds), mode, depth, max_batch, max_blob_bytes, letterbox):
+            n, k = handle.batch.shape[0], i % stage.depth
+            gt = next(gt_iter, missing)
+            if gt is missing:
+                raise Y3Error(f"evaluate_stream: `gts` ends before batch {i}")
+            gt = list(gt)
+            if len(gt) != n:
+                raise Y3Error(f"evaluate_stream: batch {i} has {n} frames, its ground truth {len(gt)} entries")
+            if counters is None:
+                counters = torch.zeros((len(variants), T, 5 * nc + 2), dtype=torch.int64, device=stage.device)
+            if k not in slots:
+                words = stage.max_batch * (G * 5 + 1)
+                slots[k] = (torch.empty(words, dtype=torch.int32, pin_memory=True),
+                            torch.empty(words, dtype=torch.int32, device=stage.device), torch.cuda.Event(), [False])
+            pinned, gt_dev, copied, used = slots[k]
+            if used[0]:
+                copied.synchronize()      # the slot's earlier copy (depth batches ago) has left the pinned words
+            boxes_w, classes_w, count_w = _gt_views(pinned.numpy(), n, G)
+            pack_ground_truth(gt, G, out=(boxes_w.view(np.float32), classes_w, count_w))
+            words = n * (G * 5 + 1)
+            gt_dev[:words].copy_(pinned[:words], non_blocking=True)
+            copied.record(cur)
+            used[0] = True
+            boxes_d, classes_d, count_d = _gt_views(gt_dev, n, G)
+            for v, oc in enumerate(variants):
+                check(self.lib.y3_evaluate_detections(_dev(packed_dev), _dev(nv_dev), n, M, _dev(boxes_d), _dev(classes_d),
+                                                      _dev(count_d), G, nc, float(evaluate_iou_threshold), _fptr(thr), T, oc,
+                                                      _dev(counters[v]), C.c_void_p(cur.cuda_stream)), "y3_evaluate_detections")
+        if next(gt_iter, missing) is not missing:
+            raise Y3Error("evaluate_stream: `gts` has more entries than there are batches")
+        if counters is None:
+            out = np.zeros((len(variants), T, 5 * nc + 2), np.int64)
+        else:
+            out = counters.cpu().numpy()      # the one read-back: waits for the stream
+        return (out[0], out[1]) if both else out[0]
 
     def flops_per_image(self) -> float:
         return float(self.lib.y3_net_flops_per_image(self._h))
@@ -596,6 +683,75 @@ def unletterbox_detections(packed: torch.Tensor, num_valid: torch.Tensor, geoms,
                                                 packed.shape[0], packed.shape[1], int(image_size), _lib.stream_ptr()),
           "y3_unletterbox_detections")
     return packed
+
+
+def pack_ground_truth(gts, max_gt: Optional[int] = None, out=None):
+    """A list of per-image (boxes [g,4], classes [g]) -> padded (boxes [B,G,4] float32, classes [B,G] int32, count [B] int32),
+    the ground-truth form of evaluate_detections.  Pure NumPy.  G = max_gt, by default the largest g of the list (at least 1);
+    an image with more rows than max_gt raises.  out: the three arrays to fill (e.g. views of pinned memory); rows behind
+    an image's count are zeroed."""
+    gts = [(np.asarray(b, np.float32).reshape(-1, 4), np.asarray(c).reshape(-1)) for b, c in gts]
+    for i, (b, c) in enumerate(gts):
+        if len(b) != len(c):
+            raise Y3Error(f"pack_ground_truth: image {i} has {len(b)} boxes and {len(c)} classes")
+    most = max((len(c) for _, c in gts), default=0)
+    G = max(most, 1) if max_gt is None else int(max_gt)
+    if G < 1 or most > G:
+        raise Y3Error(f"pack_ground_truth: max_gt = {G}, the images hold up to {most} boxes")
+    B = len(gts)
+    if out is None:
+        out = (np.empty((B, G, 4), np.float32), np.empty((B, G), np.int32), np.empty((B,), np.int32))
+    boxes, classes, count = out
+    if (boxes.shape, classes.shape, count.shape) != ((B, G, 4), (B, G), (B,)) or \
+            (boxes.dtype, classes.dtype, count.dtype) != (np.float32, np.int32, np.int32):
+        raise Y3Error(f"pack_ground_truth: out must be float32 [{B},{G},4], int32 [{B},{G}], int32 [{B}]")
+    boxes[...] = 0
+    classes[...] = 0
+    for i, (b, c) in enumerate(gts):
+        boxes[i, :len(b)] = b
+        classes[i, :len(c)] = c
+        count[i] = len(c)
+    return boxes, classes, count
+
+
+def _gt_views(words, n: int, G: int):
+    """A 1-D int32 buffer (NumPy or torch) -> its (boxes [n,G,4], classes [n,G], count [n]) parts, boxes still as words."""
+    nb, ncl = n * G * 4, n * G
+    return words[:nb].reshape(n, G, 4), words[nb:nb + ncl].reshape(n, G), words[nb + ncl:nb + ncl + n]
+
+
+def evaluate_detections(packed: torch.Tensor, num_valid: torch.Tensor, gt_boxes: torch.Tensor, gt_classes: torch.Tensor,
+                        gt_count: torch.Tensor, nclasses: int, iou_threshold: float, score_thresholds, one_class=False,
+                        counters: Optional[torch.Tensor] = None):
+    """packed [B,M,7] int32 words and num_valid [B] int32 on the GPU (Net.detect at the LOWEST threshold of the sweep,
+    pack_detections, unletterbox_detections), ground truth on the GPU as pack_ground_truth lays it out (gt_boxes [B,G,4]
+    float32, gt_classes [B,G] int32, gt_count [B] int32) -> the counters of every score threshold, int64
+    [T, 5*nclasses + 2] on the GPU: preds, gts, tp, fp, fn (each [nclasses]), errors, examples per threshold
+    (y3_evaluate_detections; host restatement: evaluate_detections.sweep_counters).  counters=None: a zeroed tensor is
+    made; otherwise the call ADDS to the one given.  Enqueues on the current stream only."""
+    _need_cuda(packed, num_valid, gt_boxes, gt_classes, gt_count, counters)
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != 7:
+        raise Y3Error("packed must be contiguous int32 [B,M,7]")
+    B, M = packed.shape[0], packed.shape[1]
+    if num_valid.dtype != torch.int32 or num_valid.shape != (B,):
+        raise Y3Error(f"num_valid must be int32 [{B}]")
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 4:
+        raise Y3Error(f"gt_boxes must be float32 [{B},G,4]")
+    G = gt_boxes.shape[1]
+    if gt_classes.dtype != torch.int32 or gt_classes.shape != (B, G):
+        raise Y3Error(f"gt_classes must be int32 [{B},{G}]")
+    if gt_count.dtype != torch.int32 or gt_count.shape != (B,):
+        raise Y3Error(f"gt_count must be int32 [{B}]")
+    thr = np.ascontiguousarray(np.asarray(score_thresholds, np.float32).reshape(-1))
+    nc = int(nclasses)
+    if counters is None:
+        counters = torch.zeros((len(thr), 5 * nc + 2), dtype=torch.int64, device=packed.device)
+    elif counters.dtype != torch.int64 or counters.shape != (len(thr), 5 * nc + 2):
+        raise Y3Error(f"counters must be int64 [{len(thr)},{5 * nc + 2}]")
+    check(_lib.load().y3_evaluate_detections(_dev(packed), _dev(num_valid), B, M, _dev(gt_boxes), _dev(gt_classes), _dev(gt_count),
+                                             G, nc, float(iou_threshold), _fptr(thr), len(thr), int(bool(one_class)),
+                                             _dev(counters), _lib.stream_ptr()), "y3_evaluate_detections")
+    return counters
 
 
 def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Tensor, first_slot: int = 0):

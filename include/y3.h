@@ -359,6 +359,63 @@ y3_status y3_evaluate_detections(const void *packed_dev, const int32_t *num_vali
                                  int64_t *counters_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Validation loss from the raw head grids (reference: core/preprocess_dataset.py:19-92, _arrange_in_grid; core/loss_func.py:19-69,
+ * get_loss_func; train.py:39-54, _calc_loss).  The reference picks a checkpoint by val_loss; these two calls give its four sums
+ * (xy, wh, obj, class) per image and scale from the grids y3_net_forward writes.  No gradient is taken and nothing here trains;
+ * the regulariser (model.losses) is not part of the result.  The Keras / TF operators are those of TF 2.8.1 / Keras 2.8.0.
+ * All arithmetic is fp32 with every operation rounded on its own unless said otherwise; eps = 1e-7f, hi = 1.0f - eps,
+ * sigmoid(x) = 1 / (1 + expf(-x)).
+ * Ground truth as for y3_evaluate_detections: gt_boxes_dev [batch,max_gt,4] {xmin,ymin,xmax,ymax} normalised, gt_classes_dev
+ * [batch,max_gt] int32, gt_count_dev [batch] clamped to [0,max_gt]; rows r < count are the reference's rows with obj = 1.
+ * anchors_host [3][3][2] as for y3_yolo_decode: scale s uses anchors[s], the flattened anchor index is 3 s + a.  grid_sizes
+ * [3] = g_s, each in [1,256].
+ *
+ * y3_yolo_assign_targets -> cells_dev [batch,max_gt] int32, bit-exact.  Per image and row r < count:
+ *   best anchor   w = xmax - xmin, h = ymax - ymin; per anchor (aw, ah): inter = min(w,aw) * min(h,ah),
+ *                 iou = inter / ((w*h + aw*ah) - inter), true division; best = the first maximum (anchor 0, then a later one only
+ *                 when strictly greater: a NaN never wins); s = best / 3 (the reference's histogram_fixed_width_bins), a = best % 3
+ *   cell          cx = (xmin + xmax) / 2, cy likewise; col = (int)(cx * (float)g_s), row = (int)(cy * (float)g_s), the cast
+ *                 truncating toward zero as tf.cast does
+ *   error image   a non-finite coordinate, a class outside [0,nclasses), or row / col outside [0,g_s) (the reference's scatter
+ *                 raises there): the image is assigned nothing and contributes nothing to any loss term
+ *   collisions    several rows on one (s,row,col,a): the highest r wins (tensor_scatter_nd_update applies updates in order)
+ *   cells[b][r]   n = 3 sum_{t<s} g_t^2 + (row g_s + col) 3 + a, the row's index in decode's row order; -1 for r >= count;
+ *                 -2 for a row that lost its cell; -3 for every row r < count of an error image
+ *
+ * y3_yolo_loss -> loss_dev double [batch][3][4], columns xy, wh, obj, class; WRITTEN, not added to.  Per image and scale s over
+ * grids_dev[s] [batch,g,g,3,5+nc], t = the logits of a row, p_obj = min(max(sigmoid(t[4]), eps), hi):
+ *   obj     over EVERY row of the grid (the reference has no ignore mask): -logf((1.0f - p_obj) + eps) for an unassigned row,
+ *           -logf(p_obj + eps) for an assigned one (Keras' binary_crossentropy: the other product is 0 * finite)
+ *   xy      over assigned rows: tw = xmax - xmin, th = ymax - ymin, scale = 2.0f - tw*th, tx = cx*(float)g - (float)col,
+ *           ty = cy*(float)g - (float)row, dx = tx - sigmoid(t[0]), dy = ty - sigmoid(t[1]); term = scale * (dx*dx + dy*dy)
+ *   wh      over assigned rows: lw = logf(tw / aw), lh = logf(th / ah) with the anchor of (s,a); an infinite value is replaced
+ *           by 0 (tf.where(is_inf)), a NaN is not and propagates; term = scale * ((lw - t[2])^2 + (lh - t[3])^2)
+ *   class   over assigned rows, sparse_categorical_crossentropy applied to probabilities: l_k = logf(min(max(sigmoid(t[5+k]),
+ *           eps), hi)), m = max_k l_k, term = logf(sum_k expf(l_k - m)) - (l_c - m); exactly 0.0f with nclasses = 1
+ * An image with a -3 in its cells gets twelve zeros; so does (never from y3_yolo_assign_targets with the same nclasses) an
+ * image with an assigned row whose class is outside [0,nclasses).  Cells outside [0, 3 sum g_s^2) are ignored.  The cells of
+ * y3_yolo_assign_targets never name one row twice within an image; if a caller's do, the row counts once, with the xy / wh /
+ * class terms of the lowest r that names it.
+ * The fp32 terms of one (image, scale) are summed in fp64 by ONE workgroup in an order fixed by the grid size alone: an
+ * image's twelve numbers are bit-identical across runs, positions in the batch, batch sizes, max_gt and the order of its rows.
+ * For a data set val_loss = sum of the 12 entries of (sum_images loss / images) -- the eager loop's loss_fn(label, output) /
+ * batch_size for full batches; perGrid = its row sums, perSource[xy,wh,obj,class] = its column sums.
+ *
+ * Both calls check every argument on the host before anything is enqueued (Y3_ERR_INVALID with a message): batch >= 1, max_gt
+ * in [1,1024], nclasses in [1,4096], grid sizes in [1,256], no null pointer, 4-byte aligned buffers (loss_dev 8-byte).  They
+ * only enqueue on `stream` -- no allocation, query or synchronise -- and can be captured into a HIP graph (anchors and grid
+ * sizes travel in the kernel arguments and are then frozen in).
+ * Host restatements: core/preprocess_dataset.assign_targets, core/loss_func.loss_from_cells.
+ * ---------------------------------------------------------------------------------------- */
+y3_status y3_yolo_assign_targets(const float *gt_boxes_dev /*[batch,max_gt,4]*/, const int32_t *gt_classes_dev /*[batch,max_gt]*/,
+                                 const int32_t *gt_count_dev /*[batch]*/, int batch, int max_gt, int nclasses,
+                                 const int32_t grid_sizes[3], const float *anchors_host, int32_t *cells_dev /*[batch,max_gt]*/,
+                                 void *stream);
+y3_status y3_yolo_loss(const float *const grids_dev[3], const int32_t grid_sizes[3], int batch, int nclasses,
+                       const float *anchors_host, const float *gt_boxes_dev, const int32_t *gt_classes_dev,
+                       const int32_t *cells_dev, int max_gt, double *loss_dev /*[batch][3][4]*/, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Multi-GPU exchange (no reference counterpart: the reference is single-device).
  * One process per GPU; images are sharded by rank and are independent end to end, so the only collective of the path
  * is the all-gather of the packed final detections (north_star: "RCCL all-gather of the final box list over xGMI").

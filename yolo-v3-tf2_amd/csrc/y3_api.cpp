@@ -1579,6 +1579,75 @@ try {
 }
 Y3_CATCH("y3_evaluate_detections")
 
+// ------------------------------------------------------------------------------------------ validation loss
+namespace {
+// The checks and the by-value geometry the two loss entries share: grid sizes, first decode row per scale, anchors.
+y3_status loss_geometry(const char *who, const int32_t *grid_sizes, const float *anchors_host, int batch, int max_gt, int nclasses,
+                        y3::LossGeom *geo)
+{
+    if (!grid_sizes || !anchors_host) return fail(Y3_ERR_INVALID, "%s: null pointer", who);
+    if (batch < 1) return fail(Y3_ERR_INVALID, "%s: batch must be at least 1 (got %d)", who, batch);
+    if (max_gt < 1 || max_gt > y3::kEvalMaxGt) return fail(Y3_ERR_INVALID, "%s: max_gt must be in [1,%d] (got %d)", who, y3::kEvalMaxGt, max_gt);
+    if (nclasses < 1 || nclasses > y3::kEvalMaxClasses)
+        return fail(Y3_ERR_INVALID, "%s: nclasses must be in [1,%d] (got %d)", who, y3::kEvalMaxClasses, nclasses);
+    int off = 0;
+    for (int s = 0; s < 3; ++s) {
+        if (grid_sizes[s] < 1 || grid_sizes[s] > y3::kLossMaxGrid)
+            return fail(Y3_ERR_INVALID, "%s: grid_sizes[%d] must be in [1,%d] (got %d)", who, s, y3::kLossMaxGrid, grid_sizes[s]);
+        geo->g[s] = grid_sizes[s];
+        geo->off[s] = off;
+        off += 3 * grid_sizes[s] * grid_sizes[s];
+        for (int a = 0; a < 3; ++a) {
+            geo->anchors[s][a][0] = anchors_host[(s * 3 + a) * 2 + 0];
+            geo->anchors[s][a][1] = anchors_host[(s * 3 + a) * 2 + 1];
+        }
+    }
+    return Y3_OK;
+}
+}  // namespace
+
+y3_status y3_yolo_assign_targets(const float *gt_boxes_dev, const int32_t *gt_classes_dev, const int32_t *gt_count_dev, int batch,
+                                 int max_gt, int nclasses, const int32_t grid_sizes[3], const float *anchors_host,
+                                 int32_t *cells_dev, void *stream)
+try {
+    if (!gt_boxes_dev || !gt_classes_dev || !gt_count_dev || !cells_dev)
+        return fail(Y3_ERR_INVALID, "y3_yolo_assign_targets: null pointer");
+    y3::LossGeom geo{};
+    y3_status st = loss_geometry("y3_yolo_assign_targets", grid_sizes, anchors_host, batch, max_gt, nclasses, &geo);
+    if (st != Y3_OK) return st;
+    if (((uintptr_t)gt_boxes_dev & 3) || ((uintptr_t)gt_classes_dev & 3) || ((uintptr_t)gt_count_dev & 3) || ((uintptr_t)cells_dev & 3))
+        return fail(Y3_ERR_INVALID, "y3_yolo_assign_targets: a device pointer is not 4-byte aligned");
+    hipError_t e = y3::launch_assign_targets(gt_boxes_dev, gt_classes_dev, gt_count_dev, batch, max_gt, nclasses, geo, cells_dev,
+                                             (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_yolo_assign_targets launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_yolo_assign_targets")
+
+y3_status y3_yolo_loss(const float *const grids_dev[3], const int32_t grid_sizes[3], int batch, int nclasses,
+                       const float *anchors_host, const float *gt_boxes_dev, const int32_t *gt_classes_dev,
+                       const int32_t *cells_dev, int max_gt, double *loss_dev, void *stream)
+try {
+    if (!grids_dev || !gt_boxes_dev || !gt_classes_dev || !cells_dev || !loss_dev)
+        return fail(Y3_ERR_INVALID, "y3_yolo_loss: null pointer");
+    y3::LossGeom geo{};
+    y3_status st = loss_geometry("y3_yolo_loss", grid_sizes, anchors_host, batch, max_gt, nclasses, &geo);
+    if (st != Y3_OK) return st;
+    y3::LossGrids grids{};
+    for (int s = 0; s < 3; ++s) {
+        if (!grids_dev[s] || ((uintptr_t)grids_dev[s] & 3))
+            return fail(Y3_ERR_INVALID, "y3_yolo_loss: grid %d null or not 4-byte aligned", s);
+        grids.p[s] = grids_dev[s];
+    }
+    if (((uintptr_t)gt_boxes_dev & 3) || ((uintptr_t)gt_classes_dev & 3) || ((uintptr_t)cells_dev & 3) || ((uintptr_t)loss_dev & 7))
+        return fail(Y3_ERR_INVALID, "y3_yolo_loss: gt_boxes / gt_classes / cells not 4-byte or loss not 8-byte aligned");
+    hipError_t e = y3::launch_yolo_loss(grids, geo, batch, nclasses, gt_boxes_dev, gt_classes_dev, cells_dev, max_gt, loss_dev,
+                                        (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_yolo_loss launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_yolo_loss")
+
 // ------------------------------------------------------------------------------------------ TFRecord checksum
 uint32_t y3_crc32c(const void *data_host, size_t nbytes)
 {

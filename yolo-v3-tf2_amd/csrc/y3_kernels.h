@@ -195,6 +195,18 @@ hipError_t launch_evaluate(const void *packed, const int32_t *nv, int B, int M, 
                            const int32_t *gt_count, int G, int nc, float iou_thr, const EvalThresholds &thr, int T, int one_class,
                            int64_t *counters, hipStream_t s);
 
+// Validation loss (loss.hip; include/y3.h, y3_yolo_assign_targets / y3_yolo_loss).  Grid sizes, the first decode row of each scale and the
+// anchors travel by value in the kernel arguments.  A grid side is at most kLossMaxGrid: row indices stay far inside an int and the
+// bitmap of a scale's rows inside LDS.
+constexpr int kLossMaxGrid = 256;
+struct LossGeom { int g[3]; int off[3]; float anchors[3][3][2]; };
+struct LossGrids { const float *p[3]; };
+size_t loss_lds_bytes(int max_gt, int g);
+hipError_t launch_assign_targets(const float *gt_boxes, const int32_t *gt_classes, const int32_t *gt_count, int B, int G, int nc,
+                                 const LossGeom &geo, int32_t *cells, hipStream_t s);
+hipError_t launch_yolo_loss(const LossGrids &grids, const LossGeom &geo, int B, int nc, const float *gt_boxes,
+                            const int32_t *gt_classes, const int32_t *cells, int G, double *loss, hipStream_t s);
+
 size_t nms_workspace_bytes(int B, int N);
 hipError_t launch_nms(const float *boxes, const float *scores, int B, int N, int M, float T, float S, int32_t *sel,
                       int32_t *num_valid, void *ws, hipStream_t s);

@@ -7,6 +7,8 @@ imports `decoded_output` but calls `yolo_decode`, evaluate_yolov3.py:23,109); th
 
 `evaluate(..., on_device=True)` gives the same results from ONE pass over the data set: one model, one y3_net_detect per
 batch at the lowest threshold, and the counters of every threshold counted on the GPU (runtime.Net.evaluate_stream).
+With `loss=True` the same pass also gives what the reference picks a checkpoint by: val_loss and its per-grid / per-source
+breakdown (reference: train.py:39-54,86-91; core/loss_func.py), computed on the GPU from the raw head grids.
 """
 from __future__ import annotations
 
@@ -18,6 +20,7 @@ import yaml
 from .core.load_tfrecords import parse_tfrecords
 from .core.parse_model import Input, ParseModel
 from .core.utils import get_anchors, resize_image
+from .core.loss_func import summarize_loss
 from .evaluate_detections import EvaluateDetections, counters_from_row
 from .inference import DetectModel
 
@@ -73,7 +76,19 @@ def calc_recal_precision(counters):
     return recall, precision
 
 
-def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_batches, weights, one_class, anchors_table, nclasses):
+def report_loss(loss):
+    """Print the loss of an evaluation pass in the wording of the reference's eager loop (train.py:86-91) and return
+    (val_loss, perGrid [3], perSource [4]).  The reference's totLoss also holds the regulariser; this number does not."""
+    val_loss, per_grid, per_source = summarize_loss(loss["sum"], loss["images"])
+    print(f'val_loss:{val_loss}, '
+          f'perGrid{list(per_grid)}, '
+          f'perSource[xy,wh,obj,class]:{per_source}, '
+          f'images:{loss["images"]}, errors:{loss["errors"]}')
+    return val_loss, per_grid, per_source
+
+
+def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_batches, weights, one_class, anchors_table, nclasses,
+                        loss=False):
     """One model and one pass: the un-stacked data set is batched here (images with unlike numbers of boxes may share a batch)
     by a generator that Net.evaluate_stream draws from, so records are decoded while earlier batches run and the data set is
     never held in memory; only the counters come back."""
@@ -114,7 +129,8 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     out = net.evaluate_stream(frames(), ground_truth(), anchors_table, max_boxes, detect_config["nms_iou_threshold"],
                               thresholds, nclasses, evaluate_iou_threshold=evaluate_iou_threshold,
                               one_class="both" if one_class else False, mode=0, max_batch=batch_size,
-                              max_blob_bytes=batch_size * (S * S * 12 + 16), max_gt=max_boxes)
+                              max_blob_bytes=batch_size * (S * S * 12 + 16), max_gt=max_boxes, loss=loss)
+    out, loss_sums = out if loss else (out, None)
     plain, one = out if one_class else (out, None)
     results = []
     for t, threshold in enumerate(thresholds):
@@ -122,24 +138,33 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
         counters_oneclass = counters_from_row(one[t], nclasses) if one_class else EvaluateDetections(nclasses, evaluate_iou_threshold).counters
         recall, precision = calc_recal_precision(counters)
         results.append((threshold, recall, precision, counters, counters_oneclass))
+    if loss:
+        report_loss(loss_sums)
+        return results, loss_sums
     return results
 
 
 def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshold=0.5, max_batches=20, weights=None,
-             one_class=True, on_device=False):
+             one_class=True, on_device=False, loss=False):
     """The loop of reference evaluate_yolov3.py:153-232: for every score threshold build the detect model, run the
     first `max_batches` dataset batches (`dataset.take(20)` there), count, and report (recall, precision).
     Returns [(threshold, recall, precision, counters, counters_oneclass)].
     on_device=True: the same list from one model and ONE pass over the data set -- the detections at a higher score threshold
     are the rows with score > threshold of the lowest threshold's, so every batch is detected once and the counters of all
     thresholds are counted on the GPU (Net.evaluate_stream).  That route batches the un-stacked data set itself: images with
-    unlike numbers of boxes may share a batch, which the host route cannot stack."""
+    unlike numbers of boxes may share a batch, which the host route cannot stack.
+    loss=True (with on_device=True): the same pass also computes the validation loss of reference core/loss_func.py on the GPU;
+    val_loss, perGrid and perSource[xy,wh,obj,class] are printed as the reference's eager loop prints them (train.py:86-91) and
+    the return value becomes (results, {"sum": float64 [3,4], "images": int, "errors": int}) as Net.evaluate_stream gives it.
+    The regulariser (model.losses, decay_factor) that the reference's totLoss includes is not part of it."""
+    if loss and not on_device:
+        raise ValueError("evaluate: loss=True needs on_device=True (the loss is computed on the GPU, from the device pass)")
     anchors_table = np.asarray(get_anchors(detect_config["anchors_file"]), np.float32)
     class_names = [c.strip() for c in open(detect_config["classes_name_file"]).readlines()]
     nclasses = len(class_names)
     if on_device:
         return _evaluate_on_device(detect_config, list(evaluate_nms_score_thresholds), evaluate_iou_threshold, max_batches, weights,
-                                   one_class, anchors_table, nclasses)
+                                   one_class, anchors_table, nclasses, loss=loss)
     dataset = prepare_dataset(detect_config["tfrecords_dir"], detect_config["batch_size"], detect_config["image_size"],
                               detect_config["yolo_max_boxes"], detect_config["classes_name_file"])
     results = []
@@ -173,12 +198,19 @@ def main(argv=None):
     ap.add_argument("--evaluate-config", default="config/evaluate_config.yaml")
     ap.add_argument("--on-device", action="store_true",
                     help="one pass over the data set for all thresholds, counters computed on the GPU")
+    ap.add_argument("--loss", action="store_true",
+                    help="with --on-device: also val_loss, perGrid and perSource[xy,wh,obj,class] from the same pass")
     a = ap.parse_args(argv)
+    if a.loss and not a.on_device:
+        ap.error("--loss needs --on-device")
     with open(a.evaluate_config) as s:
         thresholds = yaml.safe_load(s)["evaluate_nms_score_thresholds"]
     with open(a.config) as s:
         detect_config = yaml.safe_load(s)
-    print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in evaluate(detect_config, thresholds, on_device=a.on_device)])
+    results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss)
+    if a.loss:
+        results = results[0]      # the loss has been printed by evaluate
+    print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in results])
 
 
 if __name__ == "__main__":

@@ -334,7 +334,7 @@ class Net:
             done.synchronize()      # an event wait: the next batch's detect is already queued behind this one
             return packed_host[:n].numpy().copy(), nv_host[:n].numpy().copy()
 
-        for i, handle, packed_dev, nv_dev, cur, stage in self._detect_batches(
+        for i, handle, packed_dev, nv_dev, cur, stage, _ in self._detect_batches(
                 "detect_stream", batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes, letterbox):
             k, n = i % stage.depth, handle.batch.shape[0]
             if k not in outs:
@@ -351,11 +351,15 @@ class Net:
             yield result(pending.pop(0))
 
     def _detect_batches(self, who, batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes,
-                        letterbox):
+                        letterbox, keep_grids=False):
         """The loop detect_stream and evaluate_stream share: a generator that stages batch i+1 on the InputStage's copy stream,
         enqueues y3_net_detect (and, with letterbox, y3_unletterbox_detections) of batch i on the current stream, and yields
-        (i, handle, packed_dev, nv_dev, stream, stage) for the consumer to enqueue its own work on `stream` behind them.  The
-        device buffers are slot i % depth of a ring: the consumer's reads are ordered before their reuse by the stream."""
+        (i, handle, packed_dev, nv_dev, stream, stage, grids) for the consumer to enqueue its own work on `stream` behind them.
+        The device buffers are slot i % depth of a ring: the consumer's reads are ordered before their reuse by the stream.
+        keep_grids: the consumer wants the raw head grids as well (`grids`: three [n,g,g,3,5+nc] views, otherwise None), so
+        each batch takes the composed route include/y3.h documents as bit-identical to y3_net_detect: y3_net_forward into
+        grid buffers made once here, y3_yolo_decode_scores, y3_nms_padded, y3_pack_detections.  One set of buffers serves
+        every batch: all of it runs on the one stream."""
         if max_batch is None or max_blob_bytes is None:
             if not isinstance(batches, (list, tuple)):
                 raise Y3Error(f"{who}: pass max_batch and max_blob_bytes when `batches` is not a list or tuple")
@@ -377,6 +381,20 @@ class Net:
         dev = stage.device
         ring = [(torch.empty((max_batch, M, 7), dtype=torch.int32, device=dev),
                  torch.empty((max_batch,), dtype=torch.int32, device=dev)) for _ in range(stage.depth)]
+        grid_bufs = None
+        if keep_grids:
+            nc, gs = self.program.nclasses, self.grid_sizes()
+            if nc <= 0:
+                raise Y3Error(f"{who}: the program has no detection heads")
+            N = sum(3 * g * g for g in gs)
+            grid_bufs = [torch.empty((max_batch, g, g, 3, 5 + nc), dtype=torch.float32, device=dev) for g in gs]
+            grid_ptrs, grid_sizes = (C.c_void_p * 3)(*[t.data_ptr() for t in grid_bufs]), (C.c_int32 * 3)(*gs)
+            bboxes = torch.empty((max_batch, N, 4), dtype=torch.float32, device=dev)
+            cls = torch.empty((max_batch, N), dtype=torch.int64, device=dev)
+            scores = torch.empty((max_batch, N), dtype=torch.float32, device=dev)
+            sel = torch.empty((max_batch, M), dtype=torch.int32, device=dev)
+            ws_bytes = self.lib.y3_nms_workspace_bytes(max_batch, N)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
         it = iter(batches)
         first = next(it, None)
         handle = stage.submit(first, mode, letterbox) if first is not None else None
@@ -388,21 +406,30 @@ class Net:
             cur.wait_event(handle.ready)
             n = handle.batch.shape[0]
             packed_dev, nv_dev = ring[i % stage.depth]
-            check(self.lib.y3_net_detect(self._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
-                                         float(score_threshold), _dev(packed_dev), _dev(nv_dev), C.c_void_p(cur.cuda_stream)),
-                  "y3_net_detect")
+            sp = C.c_void_p(cur.cuda_stream)
+            if keep_grids:      # the first n images of every buffer are a contiguous prefix
+                check(self.lib.y3_net_forward(self._h, _dev(handle.batch), n, grid_ptrs, sp), "y3_net_forward")
+                check(self.lib.y3_yolo_decode_scores(grid_ptrs, grid_sizes, n, nc, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores), sp),
+                      "y3_yolo_decode_scores")
+                check(self.lib.y3_nms_padded(_dev(bboxes), _dev(scores), n, N, M, float(iou_threshold), float(score_threshold),
+                                             _dev(sel), _dev(nv_dev), _dev(ws), ws_bytes, sp), "y3_nms_padded")
+                check(self.lib.y3_pack_detections(_dev(bboxes), _dev(cls), _dev(scores), _dev(sel), _dev(nv_dev), n, N, M,
+                                                  _dev(packed_dev), sp), "y3_pack_detections")
+            else:
+                check(self.lib.y3_net_detect(self._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
+                                             float(score_threshold), _dev(packed_dev), _dev(nv_dev), sp), "y3_net_detect")
             stage.release(handle)
             if letterbox:
                 g = handle.geometry
                 check(self.lib.y3_unletterbox_detections(_dev(packed_dev), _dev(nv_dev), g.ctypes.data_as(C.POINTER(C.c_int32)), n, M, S,
                                                          C.c_void_p(cur.cuda_stream)), "y3_unletterbox_detections")
-            yield i, handle, packed_dev, nv_dev, cur, stage
+            yield i, handle, packed_dev, nv_dev, cur, stage, ([t[:n] for t in grid_bufs] if keep_grids else None)
             handle, i = following, i + 1
 
     def evaluate_stream(self, batches, gts, anchors, max_boxes: int, iou_threshold: float, score_thresholds, nclasses: int,
                         evaluate_iou_threshold: float = 0.5, one_class=False, mode=1, depth: int = 2,
                         max_batch: Optional[int] = None, max_blob_bytes: Optional[int] = None, letterbox=False,
-                        max_gt: Optional[int] = None):
+                        max_gt: Optional[int] = None, loss=False):
         """Frames in host memory -> the evaluation counters of EVERY NMS score threshold, from one detect pass: NumPy int64
         [T, 5*nclasses + 2] (rows as y3_evaluate_detections / evaluate_detections.counters_from_row name them), T =
         len(score_thresholds).  one_class=True: every class id taken as 0; one_class="both": the pair (plain counters,
@@ -417,8 +444,23 @@ class Net:
         max_gt: the rows of ground truth the buffers hold per image.  By default the largest count of `gts`, which must then be
         a list or tuple; with max_gt given, `gts` may be any iterable and is consumed one entry per batch, in step with
         `batches` (a data set can then be streamed through without ever being held in memory).  The number of entries of `gts`
-        must equal the number of batches either way."""
+        must equal the number of batches either way.
+        loss=True: the validation loss of reference core/loss_func.py from the same pass; the return value becomes (counters,
+        {"sum": float64 [3,4], "images": int, "errors": int}).  "sum" holds, per scale, the sums xy, wh, obj, class over the
+        "images" images that were counted; "errors" images were not (a class outside [0,nclasses), a box centred outside the
+        image, a non-finite coordinate: they add nothing to "sum").  core.loss_func.summarize_loss turns it into val_loss,
+        perGrid and perSource as reference train.py:45-52 forms them.  It is the validation loss only: no gradient is taken and
+        the regulariser the reference's training loop adds (model.losses) is not part of it.  Each batch then takes the composed
+        route y3_net_forward -> y3_yolo_decode_scores -> y3_nms_padded -> y3_pack_detections (bit-identical detections; the raw
+        grids are written and read back, which y3_net_detect avoids), y3_yolo_assign_targets and y3_yolo_loss run on the same
+        grids with the ground truth already on the device, and the sums come back with the counters in the one final copy.
+        nclasses must be the program's.  Not together with letterbox=True: the reference trains on letterboxed images with
+        unmapped boxes, and mapping the ground truth onto the canvas is a decision this method does not take."""
         thresholds = [float(t) for t in score_thresholds]
+        if loss and letterbox:
+            raise Y3Error("evaluate_stream: loss=True cannot be combined with letterbox=True (the ground truth is not mapped onto the canvas)")
+        if loss and int(nclasses) != self.program.nclasses:
+            raise Y3Error(f"evaluate_stream: loss=True needs nclasses = {self.program.nclasses}, the program's (got {int(nclasses)})")
         both = isinstance(one_class, str)
         if both and one_class != "both":
             raise Y3Error('evaluate_stream: one_class must be False, True or "both"')
@@ -435,9 +477,12 @@ class Net:
         variants = (0, 1) if both else (int(bool(one_class)),)
         thr = np.asarray(thresholds, np.float32)
         counters = None
+        n_counters = len(variants) * T * (5 * nc + 2)
+        a = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 3, 2))
         slots = {}      # ring slot -> pinned ground-truth words, their device copy, "copied" event
-        for i, handle, packed_dev, nv_dev, cur, stage in self._detect_batches(
-                "evaluate_stream", batches, anchors, M, iou_threshold, min(thresholds), mode, depth, max_batch, max_blob_bytes, letterbox):
+        for i, handle, packed_dev, nv_dev, cur, stage, grids in self._detect_batches(
+                "evaluate_stream", batches, anchors, M, iou_threshold, min(thresholds), mode, depth, max_batch, max_blob_bytes, letterbox,
+                keep_grids=bool(loss)):
             n, k = handle.batch.shape[0], i % stage.depth
             gt = next(gt_iter, missing)
             if gt is missing:
@@ -446,7 +491,14 @@ class Net:
             if len(gt) != n:
                 raise Y3Error(f"evaluate_stream: batch {i} has {n} frames, its ground truth {len(gt)} entries")
             if counters is None:
-                counters = torch.zeros((len(variants), T, 5 * nc + 2), dtype=torch.int64, device=stage.device)
+                # one buffer of 64-bit words, read back once: the counters, then (loss) the [3,4] float64 sums, the images counted and the errors
+                result = torch.zeros(n_counters + (14 if loss else 0), dtype=torch.int64, device=stage.device)
+                counters = result[:n_counters].view(len(variants), T, 5 * nc + 2)
+                if loss:
+                    loss_sum, loss_images = result[n_counters:n_counters + 12].view(torch.float64).view(3, 4), result[n_counters + 12:]
+                    cells_d = torch.empty((stage.max_batch, G), dtype=torch.int32, device=stage.device)
+                    loss_d = torch.empty((stage.max_batch, 3, 4), dtype=torch.float64, device=stage.device)
+                    gs = self.grid_sizes()
             if k not in slots:
                 words = stage.max_batch * (G * 5 + 1)
                 slots[k] = (torch.empty(words, dtype=torch.int32, pin_memory=True),
@@ -465,13 +517,24 @@ class Net:
                 check(self.lib.y3_evaluate_detections(_dev(packed_dev), _dev(nv_dev), n, M, _dev(boxes_d), _dev(classes_d),
                                                       _dev(count_d), G, nc, float(evaluate_iou_threshold), _fptr(thr), T, oc,
                                                       _dev(counters[v]), C.c_void_p(cur.cuda_stream)), "y3_evaluate_detections")
+            if loss:
+                assign_targets(boxes_d.view(torch.float32), classes_d, count_d, a, gs, nc, cells=cells_d[:n])
+                yolo_loss(grids, a, nc, boxes_d.view(torch.float32), classes_d, cells_d[:n], loss=loss_d[:n])
+                loss_sum += loss_d[:n].sum(dim=0)
+                bad = (cells_d[:n, 0] == -3).sum()
+                loss_images += torch.stack([n - bad, bad])
         if next(gt_iter, missing) is not missing:
             raise Y3Error("evaluate_stream: `gts` has more entries than there are batches")
         if counters is None:
-            out = np.zeros((len(variants), T, 5 * nc + 2), np.int64)
+            out = np.zeros(n_counters + (14 if loss else 0), np.int64)
         else:
-            out = counters.cpu().numpy()      # the one read-back: waits for the stream
-        return (out[0], out[1]) if both else out[0]
+            out = result.cpu().numpy()      # the one read-back: waits for the stream
+        words, out = out, out[:n_counters].reshape(len(variants), T, 5 * nc + 2)
+        counted = (out[0], out[1]) if both else out[0]
+        if not loss:
+            return counted
+        return counted, {"sum": words[n_counters:n_counters + 12].view(np.float64).reshape(3, 4).copy(),
+                         "images": int(words[n_counters + 12]), "errors": int(words[n_counters + 13])}
 
     def flops_per_image(self) -> float:
         return float(self.lib.y3_net_flops_per_image(self._h))
@@ -752,6 +815,70 @@ def evaluate_detections(packed: torch.Tensor, num_valid: torch.Tensor, gt_boxes:
                                              G, nc, float(iou_threshold), _fptr(thr), len(thr), int(bool(one_class)),
                                              _dev(counters), _lib.stream_ptr()), "y3_evaluate_detections")
     return counters
+
+
+def _gt_args(who, gt_boxes, gt_classes):
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4:
+        raise Y3Error(f"{who}: gt_boxes must be float32 [B,G,4]")
+    B, G = gt_boxes.shape[0], gt_boxes.shape[1]
+    if gt_classes.dtype != torch.int32 or gt_classes.shape != (B, G):
+        raise Y3Error(f"{who}: gt_classes must be int32 [{B},{G}]")
+    return B, G
+
+
+def assign_targets(gt_boxes: torch.Tensor, gt_classes: torch.Tensor, gt_count: torch.Tensor, anchors_table, grid_sizes,
+                   nclasses: int, cells: Optional[torch.Tensor] = None):
+    """Ground truth on the GPU as pack_ground_truth lays it out (gt_boxes [B,G,4] float32, gt_classes [B,G] int32, gt_count [B]
+    int32) -> cells [B,G] int32 on the GPU: per ground-truth row the index of its label's row in decode's row order (best
+    anchor by width/height IoU, the cell of its centre, the later row winning a shared cell), -1 behind the count, -2 for a row
+    that lost its cell, -3 for the rows of an error image (y3_yolo_assign_targets; reference
+    core/preprocess_dataset.py::_arrange_in_grid in sparse form; host restatement: core.preprocess_dataset.assign_targets).
+    cells: the tensor to write.  Enqueues on the current stream only."""
+    _need_cuda(gt_boxes, gt_classes, gt_count, cells)
+    B, G = _gt_args("assign_targets", gt_boxes, gt_classes)
+    if gt_count.dtype != torch.int32 or gt_count.shape != (B,):
+        raise Y3Error(f"assign_targets: gt_count must be int32 [{B}]")
+    gs = [int(g) for g in grid_sizes]
+    if len(gs) != 3:
+        raise Y3Error("assign_targets: three grid sizes")
+    a = _anchors(anchors_table)
+    if cells is None:
+        cells = torch.empty((B, G), dtype=torch.int32, device=gt_boxes.device)
+    elif cells.dtype != torch.int32 or cells.shape != (B, G):
+        raise Y3Error(f"assign_targets: cells must be int32 [{B},{G}]")
+    check(_lib.load().y3_yolo_assign_targets(_dev(gt_boxes), _dev(gt_classes), _dev(gt_count), B, G, int(nclasses),
+                                             (C.c_int32 * 3)(*gs), _fptr(a), _dev(cells), _lib.stream_ptr()),
+          "y3_yolo_assign_targets")
+    return cells
+
+
+def yolo_loss(grids, anchors_table, nclasses: int, gt_boxes: torch.Tensor, gt_classes: torch.Tensor, cells: torch.Tensor,
+              loss: Optional[torch.Tensor] = None):
+    """The raw head grids of Net.forward ([B,g,g,3,5+nc] each) + ground truth + the cells of assign_targets -> float64 [B,3,4] on
+    the GPU: per image and scale the sums xy, wh, obj, class of reference core/loss_func.py (y3_yolo_loss; host restatement:
+    core.loss_func.loss_from_cells).  An error image (cells -3) gets twelve zeros.  Each image's numbers are bit-identical
+    whatever batch it is in.  This is the validation loss: no gradient, and the regulariser the reference's training loop adds
+    (model.losses) is not part of it.  loss: the tensor to write (overwritten, not added to).  Enqueues on the current stream only."""
+    ptrs, gs, B, _ = _grids_args(grids)
+    _need_cuda(gt_boxes, gt_classes, cells, loss)
+    nc = int(nclasses)
+    if any(g.shape[4] != 5 + nc for g in grids):
+        raise Y3Error(f"yolo_loss: each grid must be float32 [B,g,g,3,{5 + nc}]")
+    if any(g.shape[0] != B for g in grids):
+        raise Y3Error("yolo_loss: the grids hold unlike batches")
+    Bg, G = _gt_args("yolo_loss", gt_boxes, gt_classes)
+    if Bg != B:
+        raise Y3Error(f"yolo_loss: {B} images in the grids, {Bg} in the ground truth")
+    if cells.dtype != torch.int32 or cells.shape != (B, G):
+        raise Y3Error(f"yolo_loss: cells must be int32 [{B},{G}]")
+    a = _anchors(anchors_table)
+    if loss is None:
+        loss = torch.empty((B, 3, 4), dtype=torch.float64, device=gt_boxes.device)
+    elif loss.dtype != torch.float64 or loss.shape != (B, 3, 4):
+        raise Y3Error(f"yolo_loss: loss must be float64 [{B},3,4]")
+    check(_lib.load().y3_yolo_loss(ptrs, gs, B, nc, _fptr(a), _dev(gt_boxes), _dev(gt_classes), _dev(cells), G, _dev(loss),
+                                   _lib.stream_ptr()), "y3_yolo_loss")
+    return loss
 
 
 def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Tensor, first_slot: int = 0):

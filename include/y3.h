@@ -190,6 +190,17 @@ y3_status y3_net_set_early_chunk(y3_net *net, int n_convs, int chunk_images);
  * is kept in the arena in the mode's format and converted into the caller's fp32 buffer at the end of the forward. */
 y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype);
 
+/* The same for a rectangular canvas: batches of height x width inputs (the reference model is Input(shape=(None, None, 3)) and
+ * fully convolutional: core/parse_model.py:279-314).  Both sides must be divisible by every tensor's `div` (32 for YOLOv3),
+ * otherwise Y3_ERR_INVALID with a message.  y3_net_plan(net, b, S, dtype) IS y3_net_plan_hw(net, b, S, S, dtype): one code path,
+ * square results are unchanged bit for bit.  Every call on a planned net (y3_net_forward, y3_net_forward_decode, y3_net_detect,
+ * y3_net_read_tensor, y3_net_flops_per_image, y3_net_profile_convs, the measure_sclk calls) follows the planned geometry:
+ * images_dev is [B,height,width,3], head grid s is [B, height/div_s, width/div_s, 3*(5+nc)], N = 3 * sum gh_s * gw_s.  The
+ * decode inside y3_net_forward_decode / y3_net_detect is y3_yolo_decode_scores_hw below (per-axis normalisation); anchors are
+ * normalised (w, h): the caller divides w by the canvas width and h by the canvas height.  The fused stem (y3_net_set_stem_fusion)
+ * and the fused head decode serve rectangular plans like square ones.  No tile was tuned for a rectangular plan. */
+y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int dtype);
+
 /* images_dev [B,S,S,3] fp32 -> grids_dev[3], each [B,g,g,3*(5+nc)] fp32 (== [B,g,g,3,5+nc]).
  * Replaces model(inputs) (reference: inference.py:109). */
 y3_status y3_net_forward(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], void *stream);
@@ -198,7 +209,7 @@ y3_status y3_net_forward(y3_net *net, const float *images_dev, int batch, float 
  * through *n_elems; dst_dev may be NULL to query the size) */
 y3_status y3_net_read_tensor(y3_net *net, int tensor_id, int batch, float *dst_dev, size_t *n_elems, void *stream);
 
-/* conv FLOPs (2*MAC) of one image at the planned size */
+/* conv FLOPs (2*MAC) of one image at the planned size (height x width) */
 double y3_net_flops_per_image(const y3_net *net);
 
 /* Time every conv launch of one forward (hipEvents on `stream`); ms_out[n_convs]. Synchronises. */
@@ -224,6 +235,13 @@ y3_status y3_net_profile_convs(y3_net *net, const float *images_dev, int batch, 
 #define Y3_IMAGE_LETTERBOX 0x100
 y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, int width, int channels,
                               float *batch_dev, int slot, int image_size, void *stream);
+/* The same onto a canvas_h x canvas_w canvas (batch_dev is [*,canvas_h,canvas_w,3]).  Without the flag the image is stretched to
+ * canvas_h x canvas_w.  With it the geometry is, in fp32,
+ *   scale = min((float)canvas_h / (float)h, (float)canvas_w / (float)w)
+ *   sh, sw as above;  top = (canvas_h - sh) / 2, left = (canvas_w - sw) / 2
+ * y3_preprocess_image(..., S, stream) IS y3_preprocess_image_hw(..., S, S, stream).  Same argument checks. */
+y3_status y3_preprocess_image_hw(const void *image_dev, int is_uint8, int height, int width, int channels,
+                                 float *batch_dev, int slot, int canvas_h, int canvas_w, void *stream);
 
 /* The same stage for a batch of unlike images in one launch per 64 images (no reference counterpart: the reference resizes
  * image by image).  All images lie in ONE device blob `pixels_dev` of `pixels_bytes` bytes; image i starts `offset` bytes into
@@ -237,12 +255,17 @@ y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, i
 typedef struct y3_image_desc { uint64_t offset; int32_t height, width, channels, mode; } y3_image_desc;
 y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
                               float *batch_dev, int first_slot, int image_size, void *stream);
+/* ... onto a canvas_h x canvas_w canvas; the square call is this one with canvas_h == canvas_w.  Same checks, same messages. */
+y3_status y3_preprocess_batch_hw(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
+                                 float *batch_dev, int first_slot, int canvas_h, int canvas_w, void *stream);
 
 /* The letterbox geometry of a batch, on the host (no HIP call): geoms_out_host[n_images][4] = {sh, sw, top, left} by the
  * formula above, from height / width / mode of each descriptor (offset and channels are not read); an image without
  * Y3_IMAGE_LETTERBOX gets {image_size, image_size, 0, 0}.  y3_preprocess_batch and y3_preprocess_image compute their
  * geometries with the same routine.  One call per batch. */
 y3_status y3_letterbox_geometry(const y3_image_desc *descs_host, int n_images, int image_size, int32_t *geoms_out_host);
+/* ... for a canvas_h x canvas_w canvas (y3_preprocess_image_hw gives the formula); without the flag {canvas_h, canvas_w, 0, 0}. */
+y3_status y3_letterbox_geometry_hw(const y3_image_desc *descs_host, int n_images, int canvas_h, int canvas_w, int32_t *geoms_out_host);
 
 /* ------------------------------------------------------------------------------------------
  * yolo_decode   (reference: core/yolo_decode_layer.py:15-36)
@@ -258,6 +281,23 @@ y3_status y3_yolo_decode(const float *const grids_dev[3], const int32_t grid_siz
 y3_status y3_yolo_decode_scores(const float *const grids_dev[3], const int32_t grid_sizes[3], int batch,
                                 int nclasses, const float *anchors_host, float *bboxes_dev,
                                 int64_t *class_idx_dev, float *scores_dev, void *stream);
+
+/* The two decodes for rectangular grids: grid_hw[s] = {gh_s, gw_s}, grids_dev[s] is [B,gh_s,gw_s,3,5+nc], N = 3 * sum gh_s * gw_s.
+ * Row order as above: n = off_s + (row * gw_s + col) * 3 + a.  Each centre is normalised by the extent of ITS OWN axis:
+ *   x = (sigmoid(tx) + col) / (float)gw      y = (sigmoid(ty) + row) / (float)gh
+ * so that boxes are normalised (xmin,ymin,xmax,ymax) of the gh x gw canvas.  This is a DELIBERATE departure from the reference
+ * for gh != gw: its __arrange_bbox (core/yolo_decode_layer.py:5-8) divides (x, y) by cast(shape[1:3]) = (gh, gw) -- x by the
+ * number of rows -- and oracle/y3_oracle.c:162-163 restates exactly that.  The two coincide for every square grid, which is all
+ * the reference ever runs; for other grids the reference's result is not a normalised coordinate.  y3_yolo_decode /
+ * y3_yolo_decode_scores ARE these calls with {g, g}: the same kernel body, square results unchanged bit for bit.
+ * Anchors stay normalised (w, h): the caller normalises w by the canvas width and h by the canvas height.
+ * Host restatement: core/yolo_decode_layer.yolo_decode_hw_host. */
+y3_status y3_yolo_decode_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
+                            const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev,
+                            void *stream);
+y3_status y3_yolo_decode_scores_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch,
+                                   int nclasses, const float *anchors_host, float *bboxes_dev,
+                                   int64_t *class_idx_dev, float *scores_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * yolo_nms / YoloNmsLayer.call   (reference: core/yolo_nms.py:16-34, core/yolo_nms_layer.py:26-29)
@@ -317,6 +357,11 @@ y3_status y3_net_detect(y3_net *net, const float *images_dev, int batch, const f
  * bad image); the call only enqueues on `stream` -- no allocation, query or synchronise -- and can be captured. */
 y3_status y3_unletterbox_detections(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
                                     int max_boxes, int image_size, void *stream);
+/* ... for a canvas_h x canvas_w canvas (geometries of y3_letterbox_geometry_hw):
+ *   x' = (x * (float)canvas_w - (float)left) / (float)sw      y' = (y * (float)canvas_h - (float)top) / (float)sh
+ * an image whose geometry is {canvas_h, canvas_w, 0, 0} is not touched.  The square call is this one with canvas_h == canvas_w. */
+y3_status y3_unletterbox_detections_hw(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                       int max_boxes, int canvas_h, int canvas_w, void *stream);
 
 /* ------------------------------------------------------------------------------------------
  * Evaluation counters for every NMS score threshold of a sweep, from ONE detect pass (reference:

@@ -21,6 +21,10 @@ Every shape is warmed up; a timed window ends in a synchronise and lasts about -
 
 --letterbox (with any of the above): the frames keep their aspect ratio (zero padding, Y3_IMAGE_LETTERBOX) and the detections
 come back in frame coordinates; --kernels-only then also runs unletterbox_kernel on 64 x 100 valid rows per repetition.
+--letterbox --rect: the net is planned for runtime.rect_canvas of the frame size (--frame HxW, default 480x640) instead of the
+416^2 square, with the anchors rescaled to that canvas (runtime.rect_anchors); the uniform frame set only.
+--letterbox --compare-rect [--out profiles/rect_canvas.txt]: the square and the rect plan in ONE process, pipelined route,
+windows alternated; images/s of both, their ratio, the FLOP ratio beside it and the per-conv times of both plans.
 """
 import argparse
 import csv
@@ -42,15 +46,16 @@ CONFIGS = (("f32", 64), ("bf16", 128))
 RAGGED_SHAPES = [(100, 37, 3), (480, 640, 3), (1080, 1920, 3), (375, 500, 4), (720, 1280, 3), (416, 416, 3), (812, 667, 4), (240, 320, 3)]
 
 
-def frames(kind, n, seed):
+def frames(kind, n, seed, frame=(480, 640)):
+    """kind "640x480": n frames of `frame` (H, W), three channels; "ragged": the mixed set."""
     rng = np.random.default_rng(seed)
-    shapes = [(480, 640, 3)] * n if kind == "640x480" else [RAGGED_SHAPES[i % len(RAGGED_SHAPES)] for i in range(n)]
+    shapes = [(*frame, 3)] * n if kind == "640x480" else [RAGGED_SHAPES[i % len(RAGGED_SHAPES)] for i in range(n)]
     return [rng.integers(0, 256, s, dtype=np.uint8) for s in shapes]
 
 
-def algorithmic_bytes(images):
-    """Source bytes read + S*S*12 written, per image, summed."""
-    return int(sum(im.nbytes + S * S * 12 for im in images))
+def algorithmic_bytes(images, canvas=(S, S)):
+    """Source bytes read + Hc*Wc*12 written, per image, summed."""
+    return int(sum(im.nbytes + canvas[0] * canvas[1] * 12 for im in images))
 
 
 def timed(fn, batches_per_window):
@@ -62,25 +67,29 @@ def timed(fn, batches_per_window):
     return time.perf_counter() - t0
 
 
-def run_config(dtype, B, a, anchors, program, weights):
+def run_config(dtype, B, a, anchors, program, weights, canvas=(S, S), frame=(480, 640)):
+    """canvas: the plan's (H, W) -- the 416^2 square, or (--rect) runtime.rect_canvas of `frame` with `anchors` rescaled to it by
+    the caller; a rectangular canvas runs the uniform frame set only."""
     import torch
     from yolo_v3_tf2_amd import _lib, runtime
     net = runtime.Net(program)
     net.load_weights(weights)
-    net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16}[dtype])
+    Hc, Wc = canvas
+    rect = Hc != Wc
+    net.plan(B, canvas if rect else Hc, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16}[dtype])
     out = {}
-    for kind in ("640x480", "ragged"):
-        imgs = frames(kind, B, a.seed)
+    for kind in (("640x480",) if rect else ("640x480", "ragged")):
+        imgs = frames(kind, B, a.seed, frame)
         lb = a.letterbox
         blob, descs = runtime.pack_images(imgs, 1, letterbox=lb)
-        geoms = runtime.letterbox_geometries(descs, S)
-        resident_batch = torch.empty((B, S, S, 3), device="cuda")
+        geoms = runtime.letterbox_geometries(descs, canvas)
+        resident_batch = torch.empty((B, Hc, Wc, 3), device="cuda")
         runtime.preprocess_batch(torch.from_numpy(blob).cuda(), descs, resident_batch)
 
         def detect(batch):
             packed, nv = net.detect(batch, anchors, 100, 0.5, 0.1)
             if lb:
-                runtime.unletterbox_detections(packed, nv, geoms, S)
+                runtime.unletterbox_detections(packed, nv, geoms, canvas)
             return packed, nv
 
         def resident(k):
@@ -89,7 +98,7 @@ def run_config(dtype, B, a, anchors, program, weights):
 
         def per_image(k):
             for _ in range(k):
-                batch = torch.empty((B, S, S, 3), device="cuda")
+                batch = torch.empty((B, Hc, Wc, 3), device="cuda")
                 for slot, u8 in enumerate(imgs):
                     runtime.preprocess_image(torch.from_numpy(u8).cuda(), batch, slot, letterbox=lb)
                 packed, nv = detect(batch)
@@ -124,7 +133,7 @@ def run_config(dtype, B, a, anchors, program, weights):
         if lb:      # the one host call the letterbox route adds per batch, next to the packing it follows
             t0 = time.perf_counter()
             for _ in range(200):
-                runtime.letterbox_geometries(descs, S)
+                runtime.letterbox_geometries(descs, canvas)
             res["host_geometry_ms_per_batch"] = round((time.perf_counter() - t0) / 200 * 1e3, 4)
         for name, v in rates.items():
             res[name] = {"images_per_s_median": round(float(np.median(v)), 1), "spread": round(float(max(v) - min(v)), 1),
@@ -134,12 +143,77 @@ def run_config(dtype, B, a, anchors, program, weights):
         res["pipelined_minus_per_image_over_per_image_spread"] = round(
             (res["pipelined"]["images_per_s_median"] - res["per_image"]["images_per_s_median"]) / max(res["per_image"]["spread"], 1e-9), 1)
         out[kind] = res
-        print(f"{dtype} {B} x {S}^2, {kind} frames{' letterboxed' if lb else ''} (decode excluded): " + ", ".join(
+        print(f"{dtype} {B} x {Hc}x{Wc}, {kind if kind == 'ragged' else f'{frame[1]}x{frame[0]}'} frames{' letterboxed' if lb else ''} (decode excluded): " + ", ".join(
             f"{n} {res[n]['images_per_s_median']:.0f} img/s (spread {res[n]['spread']:.0f})" for n in routes) +
             f"; pipelined / per-image {res['pipelined_over_per_image']:.2f}, pipelined / resident {res['pipelined_over_resident']:.2f}; "
             f"host packing alone {res['host_pack_images_per_s']:.0f} img/s" +
             (f", geometry call {res['host_geometry_ms_per_batch'] * 1e3:.1f} us per batch" if lb else ""), flush=True)
     return out
+
+
+def compare_rect(a, anchors, program, weights):
+    """Square letterbox plan against the rect_canvas plan of the same frames: one process, the pipelined route of both,
+    windows alternated (the square run of the same session is the yardstick); then the per-conv times of both plans."""
+    import torch
+    from yolo_v3_tf2_amd import _lib, runtime
+    lines = ["# tools/time_input_stage.py --letterbox --compare-rect: Net.detect_stream (depth 2, letterbox=True) on uniform uint8 frames,",
+             f"# square {S}^2 plan against the runtime.rect_canvas plan, one process, windows alternated, {a.rounds} rounds of ~{a.window} s each,",
+             "# median (spread = max - min); image decode excluded.  FLOP ratio = y3_net_flops_per_image(rect) / (square): the bound of the gain.",
+             "# The rect plan takes the tile table of the square plan (tuning/<mode>_b<batch>_s416.json); no tile was tuned for it."]
+    for frame in ((480, 640), (1080, 1920)):
+        canvas = runtime.rect_canvas(*frame, S)
+        for dtype, B in CONFIGS:
+            if a.dtype not in ("", dtype):
+                continue
+            imgs = [np.random.default_rng(a.seed).integers(0, 256, (*frame, 3), dtype=np.uint8)] * B
+            plans = {}
+            for name, size, anc in (("square", S, anchors), ("rect", canvas, runtime.rect_anchors(anchors, S, canvas))):
+                net = runtime.Net(program)
+                net.load_weights(weights)
+                net.plan(B, size, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16}[dtype])
+                plans[name] = (net, anc)
+
+            def route(name):
+                net, anc = plans[name]
+                def fn(k):
+                    for _ in net.detect_stream([imgs] * k, anc, 100, 0.5, 0.1, mode=1, depth=2, letterbox=True):
+                        pass
+                return fn
+            routes = {n: route(n) for n in plans}
+            per_window, rates = {}, {n: [] for n in plans}
+            for n, fn in routes.items():
+                fn(2)
+                per_window[n] = max(3, int(np.ceil(a.window / (timed(fn, 3) / 3))))
+            for r in range(a.rounds):
+                for n in (list(routes) if r % 2 == 0 else list(routes)[::-1]):
+                    rates[n].append(per_window[n] * B / timed(routes[n], per_window[n]))
+            med = {n: float(np.median(v)) for n, v in rates.items()}
+            flops = {n: plans[n][0].flops_per_image() for n in plans}
+            fr = flops["rect"] / flops["square"]
+            gain, bound = med["rect"] / med["square"], 1.0 / fr
+            lines.append(f"\n## {frame[1]}x{frame[0]} frames, {dtype}, {B} per batch: square {S}x{S} vs rect {canvas[0]}x{canvas[1]}")
+            for n in plans:
+                lines.append(f"{n:<7s} {med[n]:9.1f} images/s  (spread {max(rates[n]) - min(rates[n]):.1f}; rounds {', '.join(f'{x:.1f}' for x in rates[n])})")
+            lines.append(f"rect / square images/s {gain:.3f}   FLOP ratio rect / square {fr:.3f} (bound of the gain: x {bound:.3f})   "
+                         f"share of the possible gain realised {(gain - 1) / (bound - 1) * 100:.0f} %")
+            ms = {}
+            for n, (net, _) in plans.items():
+                Hc, Wc = net.canvas
+                x = torch.rand((B, Hc, Wc, 3), device="cuda")
+                net.profile_convs(x)
+                ms[n] = np.median([net.profile_convs(x) for _ in range(3)], axis=0)
+            lines.append(f"per-conv ms (profile_convs, one lane, median of 3; 0 = runs inside the fused stem launch); sum square {ms['square'].sum():.3f}, rect {ms['rect'].sum():.3f}")
+            lines.append(f"{'conv':>4s} {'k':>1s} {'s':>1s} {'cin':>5s} {'cout':>5s} {'div':>3s} {'square ms':>10s} {'rect ms':>9s} {'rect/square':>11s} {'vs FLOP ratio':>13s}")
+            for i, o in enumerate(plans["square"][0].conv_ops):
+                q = ms["rect"][i] / ms["square"][i] if ms["square"][i] > 0 else 0.0
+                lines.append(f"{i:4d} {o.size:1d} {o.stride:1d} {o.cin:5d} {o.cout:5d} {o.out_div:3d} {ms['square'][i]:10.4f} {ms['rect'][i]:9.4f} {q:11.3f} {q / fr:13.3f}")
+            del plans, routes
+            torch.cuda.empty_cache()
+            print("\n".join(lines[-80:]), flush=True)
+    text = "\n".join(lines) + "\n"
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(text)
 
 
 def kernels_only(a):
@@ -274,9 +348,17 @@ def main():
     ap.add_argument("--kernel-reps", type=int, default=10)
     ap.add_argument("--trace-pipelined", action="store_true")
     ap.add_argument("--letterbox", action="store_true", help="aspect-preserving resize + zero pad, detections in frame coordinates")
+    ap.add_argument("--rect", action="store_true", help="with --letterbox: plan runtime.rect_canvas of the frame size instead of the square")
+    ap.add_argument("--frame", default="480x640", help="HxW of the uniform frame set (default 480x640)")
+    ap.add_argument("--compare-rect", action="store_true", help="with --letterbox: square plan against the rect plan, alternated, one process")
     ap.add_argument("--summarize-trace", default="", help="directory of a rocprofv3 kernel + memory-copy trace of --trace-pipelined")
     ap.add_argument("--summarize", default="", help="directory of a rocprofv3 --kernel-trace run of --kernels-only")
     a = ap.parse_args()
+    frame = tuple(int(v) for v in a.frame.lower().split("x"))
+    if frame != (480, 640) and not a.rect:
+        ap.error("--frame applies to --rect runs (the square runs keep the 640x480 set their records were made with)")
+    if (a.rect or a.compare_rect) and not a.letterbox:
+        ap.error("--rect / --compare-rect need --letterbox")
     if a.summarize:
         return summarize(a)
     if a.summarize_trace:
@@ -294,13 +376,20 @@ def main():
     anchors = get_anchors(os.path.join(ROOT, "datasets/coco2012/anchors.txt")).astype(np.float32)
     if a.trace_pipelined:
         return trace_pipelined(a, anchors, program, weights)
+    if a.compare_rect:
+        return compare_rect(a, anchors, program, weights)
     doc = {"what": "images/s from decoded uint8 frames in host memory to packed detections on the host; image decode excluded",
-           "image_size": S, "rounds": a.rounds, "window_s": a.window, "seed": a.seed, **({"letterbox": True} if a.letterbox else {}),
+           "image_size": S, **({"rect": True, "frame": list(frame)} if a.rect else {}), "rounds": a.rounds, "window_s": a.window, "seed": a.seed, **({"letterbox": True} if a.letterbox else {}),
            "routes": {"resident": "Net.detect on a batch already on the device", "per_image": "per image .cuda() + preprocess_image, Net.detect, blocking read-back",
                       "pipelined": "Net.detect_stream (depth 2)"}}
     for dtype, B in CONFIGS:
         if a.dtype in ("", dtype):
-            doc[f"{dtype}_b{B}"] = run_config(dtype, B, a, anchors, program, weights)
+            if a.rect:
+                from yolo_v3_tf2_amd import runtime
+                canvas = runtime.rect_canvas(*frame, S)
+                doc[f"{dtype}_b{B}"] = run_config(dtype, B, a, runtime.rect_anchors(anchors, S, canvas), program, weights, canvas, frame)
+            else:
+                doc[f"{dtype}_b{B}"] = run_config(dtype, B, a, anchors, program, weights)
     line = json.dumps(doc)
     if a.out:
         with open(a.out, "w") as f:

@@ -114,19 +114,26 @@ SYMBOLS = {
     "y3_net_measure_sclk_conv": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _i, _fp, _vp]),
     "y3_net_measure_sclk_all": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _fp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "y3_net_plan": (_i, [_vp, _i, _i, _i]),
+    "y3_net_plan_hw": (_i, [_vp, _i, _i, _i, _i]),
     "y3_net_forward": (_i, [_vp, _vp, _i, C.POINTER(_vp), _vp]),
     "y3_net_read_tensor": (_i, [_vp, _i, _i, _vp, C.POINTER(_sz), _vp]),
     "y3_net_flops_per_image": (C.c_double, [_vp]),
     "y3_net_profile_convs": (_i, [_vp, _vp, _i, _fp, _i, _vp]),
     "y3_preprocess_image": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),
+    "y3_preprocess_image_hw": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _i, _vp]),
     "y3_preprocess_batch": (_i, [_vp, _sz, C.POINTER(ImageDesc), _i, _vp, _i, _i, _vp]),
+    "y3_preprocess_batch_hw": (_i, [_vp, _sz, C.POINTER(ImageDesc), _i, _vp, _i, _i, _i, _vp]),
     "y3_letterbox_geometry": (_i, [C.POINTER(ImageDesc), _i, _i, C.POINTER(C.c_int32)]),
+    "y3_letterbox_geometry_hw": (_i, [C.POINTER(ImageDesc), _i, _i, _i, C.POINTER(C.c_int32)]),
     "y3_unletterbox_detections": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp]),
+    "y3_unletterbox_detections_hw": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _i, _vp]),
     "y3_evaluate_detections": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _f, _fp, _i, _i, _vp, _vp]),
     "y3_yolo_assign_targets": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_int32), _fp, _vp, _vp]),
     "y3_yolo_loss": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _i, _vp, _vp]),
     "y3_yolo_decode": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_yolo_decode_scores": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
+    "y3_yolo_decode_hw": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),   # grid_hw[3][2] as six int32
+    "y3_yolo_decode_scores_hw": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_class_scores": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "y3_nms_workspace_bytes": (_sz, [_i, _i]),
     "y3_nms_padded": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),

@@ -80,17 +80,17 @@ def resize_image(img, target_height, target_width):
 
 
 def unletterbox_boxes(boxes, geometry, image_size):
-    """Normalised (xmin, ymin, xmax, ymax) boxes on the padded image_size^2 canvas -> normalised to the source frame
-    that letterbox_geometry placed there; boxes [..., 4] float32, geometry (sh, sw, top, left).  float32, one rounding
-    per operation: x' = (x * S - left) / sw, y' = (y * S - top) / sh; no clipping (the reference never clips boxes).
-    A geometry that is the whole canvas returns the values as they are (x * S / S is not x in float32).  Host
-    restatement of y3_unletterbox_detections."""
+    """Normalised (xmin, ymin, xmax, ymax) boxes on the padded canvas (image_size: an int S for S x S, or an (H, W)
+    pair) -> normalised to the source frame that letterbox_geometry placed there; boxes [..., 4] float32, geometry
+    (sh, sw, top, left).  float32, one rounding per operation: x' = (x * W - left) / sw, y' = (y * H - top) / sh; no
+    clipping (the reference never clips boxes).  A geometry that is the whole canvas returns the values as they are
+    (x * W / W is not x in float32).  Host restatement of y3_unletterbox_detections_hw."""
     boxes = np.asarray(boxes, np.float32)
     sh, sw, top, left = (int(v) for v in np.asarray(geometry).reshape(4))
-    S = int(image_size)
-    if (sh, sw, top, left) == (S, S, 0, 0):
+    H, W = (int(image_size),) * 2 if np.ndim(image_size) == 0 else (int(v) for v in image_size)
+    if (sh, sw, top, left) == (H, W, 0, 0):
         return boxes.copy()
-    fs = np.float32(S)
+    fs = np.array([W, H, W, H], np.float32)
     off = np.array([left, top, left, top], np.float32)
     div = np.array([sw, sh, sw, sh], np.float32)
     return ((boxes * fs - off) / div).astype(np.float32)

@@ -114,7 +114,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
 
     const __amdgpu_buffer_rsrc_t rsi = buffer_rsrc(p.img, p.img_bytes);
     const __amdgpu_buffer_rsrc_t rsd = buffer_rsrc(p.dst, p.dst_bytes);
-    const int S = p.S, So = p.S >> 1;
+    const int H = p.H, W = p.W, Ho = p.H >> 1, Wo = p.W >> 1;
     const int tiles_per_img = p.tiles_y * p.tiles_x;
     const char *lds = reinterpret_cast<const char *>(smem);
 
@@ -159,8 +159,8 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
             const int iy = e / (IW * 3), rem = e - iy * (IW * 3);
             const int ix = rem / 3, c = rem - ix * 3;
             const int gy = iy0 + iy, gx = ix0 + ix;
-            const bool ok = e < IMG_F && (unsigned)gy < (unsigned)S && (unsigned)gx < (unsigned)S;
-            vo[i] = ok ? (unsigned)(((b * S + gy) * S + gx) * 3 + c) * 4u : p.img_bytes;
+            const bool ok = e < IMG_F && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+            vo[i] = ok ? (unsigned)(((b * H + gy) * W + gx) * 3 + c) * 4u : p.img_bytes;
         }
     };
     float rimg[IMG_PER_THREAD];
@@ -293,7 +293,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
                 const int rr = (row >> 4), cc = (row & 15) + 4 * fh;  // row & 15 + 4 fh < 16: rows 0-3, 8-11 (+4) only
                 float v = acc[e] + sh1;
                 if (p.leaky1) v = fmaxf(v, 0.1f * v);
-                const unsigned off = (unsigned)((((b * So + oy0 + rr) * So) + ox0 + cc) * C1 + n) * 4u;
+                const unsigned off = (unsigned)((((b * Ho + oy0 + rr) * Wo) + ox0 + cc) * C1 + n) * 4u;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), rsd, (int)off, 0, 0);
                 acc[e] = v;      // kept for phase 3
             }
@@ -326,7 +326,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
                     v0 = fmaxf(v0, 0.1f * v0);
                     v1 = fmaxf(v1, 0.1f * v1);
                 }
-                const unsigned off = (unsigned)(((b * So + oy) * So + ox + i) * 32 + l15) * 4u;
+                const unsigned off = (unsigned)(((b * Ho + oy) * Wo + ox + i) * 32 + l15) * 4u;
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v0), rsd2, (int)off, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v1), rsd2, (int)off, 64, 0);
             }
@@ -340,10 +340,10 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
 hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s)
 {
     using namespace stem;
-    if (a.S % 32 || a.B <= 0 || !a.img || !a.w0 || !a.w1 || !a.dst) return hipErrorInvalidValue;
+    if (a.H % 32 || a.W % 32 || a.B <= 0 || !a.img || !a.w0 || !a.w1 || !a.dst) return hipErrorInvalidValue;
     StemArgs p = a;
-    p.tiles_y = (a.S / 2) / TH;
-    p.tiles_x = (a.S / 2) / TW;
+    p.tiles_y = (a.H / 2) / TH;
+    p.tiles_x = (a.W / 2) / TW;
     p.n_tiles = a.B * p.tiles_y * p.tiles_x;
     static LdsAttrOnce attr;
     if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv_stem_f32), LDS_BYTES, a.device); e != hipSuccess) return e;
@@ -474,7 +474,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
     for (int s = 0; s < 2; ++s) bw[s] = PATCH_B + (wn * 32 + fr) * (K1 * 2) + (((2 * s + fh) ^ (((wn * 32 + fr) >> 2) & 3)) << 4);
 
     const __amdgpu_buffer_rsrc_t rsi = buffer_rsrc(p.img, p.img_bytes);
-    const int S = p.S, So = p.S >> 1;
+    const int H = p.H, W = p.W, Ho = p.H >> 1, Wo = p.W >> 1;
     const int tiles_per_img = p.tiles_y * p.tiles_x;
 
     auto img_voff = [&](int tile, unsigned (&vo)[IMG_PER_THREAD]) {
@@ -487,8 +487,8 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             const int iy = e / (IW * 3), rem = e - iy * (IW * 3);
             const int ix = rem / 3, c = rem - ix * 3;
             const int gy = iy0 + iy, gx = ix0 + ix;
-            const bool ok = e < IMG_F && (unsigned)gy < (unsigned)S && (unsigned)gx < (unsigned)S;
-            vo[i] = ok ? (unsigned)(((b * S + gy) * S + gx) * 3 + c) * 4u : p.img_bytes;
+            const bool ok = e < IMG_F && (unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W;
+            vo[i] = ok ? (unsigned)(((b * H + gy) * W + gx) * 3 + c) * 4u : p.img_bytes;
         }
     };
     float rimg[IMG_PER_THREAD];
@@ -608,7 +608,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 const int P = g >> 3, ch = g & 7;
                 const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + P * 128 + ch * 16);
                 const int oy = ty * TH + (P >> 4), ox = tx * TW + (P & 15);
-                *reinterpret_cast<u32x4 *>(dst + ((size_t)(b * So + oy) * So + ox) * C1 + ch * 8) = v;
+                *reinterpret_cast<u32x4 *>(dst + ((size_t)(b * Ho + oy) * Wo + ox) * C1 + ch * 8) = v;
             }
         }
         if (with2) {
@@ -641,7 +641,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 const int P = tid >> 2, ch = tid & 3;               // 512 chunks of 16 B
                 const u32x4 v = *reinterpret_cast<const u32x4 *>(lds + OUT2_OFF + P * 64 + ch * 16);
                 const int oy = ty * TH + (P >> 4), ox = tx * TW + (P & 15);
-                *reinterpret_cast<u32x4 *>(dst2 + ((size_t)(b * So + oy) * So + ox) * 32 + ch * 8) = v;
+                *reinterpret_cast<u32x4 *>(dst2 + ((size_t)(b * Ho + oy) * Wo + ox) * 32 + ch * 8) = v;
             }
         }
         if (next < p.n_tiles) img_stage();
@@ -653,10 +653,10 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
 hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s)
 {
     using namespace stemb;
-    if (a.S % 32 || a.B <= 0 || !a.img || !a.w0 || !a.w1 || !a.dst || !a.scale0 || !a.scale1) return hipErrorInvalidValue;
+    if (a.H % 32 || a.W % 32 || a.B <= 0 || !a.img || !a.w0 || !a.w1 || !a.dst || !a.scale0 || !a.scale1) return hipErrorInvalidValue;
     StemArgs p = a;
-    p.tiles_y = (a.S / 2) / TH;
-    p.tiles_x = (a.S / 2) / TW;
+    p.tiles_y = (a.H / 2) / TH;
+    p.tiles_x = (a.W / 2) / TW;
     p.n_tiles = a.B * p.tiles_y * p.tiles_x;
     static LdsAttrOnce attr;
     if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv_stem_bf16), LDS_BYTES_B, a.device); e != hipSuccess) return e;

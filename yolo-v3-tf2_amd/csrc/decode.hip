@@ -34,8 +34,8 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_kernel(const DecodeLaunch 
     int s = 0;
     if ((int)blockIdx.x >= L.blk_start[1]) s = 1;
     if ((int)blockIdx.x >= L.blk_start[2]) s = 2;
-    const int g = L.a.g[s];
-    const int per_img = g * g * 3;
+    const int gh = L.a.gh[s], gw = L.a.gw[s];
+    const int per_img = gh * gw * 3;
     const long long total = (long long)L.a.B * per_img;            // boxes of this scale over the batch
     const long long box0 = (long long)((int)blockIdx.x - L.blk_start[s]) * DEC_BOXES;
     const int nbox = (int)((total - box0) < DEC_BOXES ? (total - box0) : DEC_BOXES);
@@ -56,14 +56,14 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_kernel(const DecodeLaunch 
     const int r = (int)(gi - (long long)b * per_img);
     const int a = r % 3;
     const int cell = r / 3;
-    const int row = cell / g, col = cell - row * g;
+    const int row = cell / gw, col = cell - row * gw;
     const long long out_row = (long long)b * L.a.N + L.a.off[s] + r;
     float *t = lds + jj * F;
     // lane 0: x, lane 1: y, lane 2: w, lane 3: h; classes q, q + 4, ... (decode_box.h: the body the fused head convs share)
     f32x4 bb;
     float c, best;
     int besti;
-    decode_box_lanes<WRITE_PROBS, WRITE_SCORES>(t, q, tid & 63, L.a.nc, g, row, col, q >= 2 ? L.a.anchors[s][a][q - 2] : 0.0f, live, bb, c, best, besti);
+    decode_box_lanes<WRITE_PROBS, WRITE_SCORES>(t, q, tid & 63, L.a.nc, gh, gw, row, col, q >= 2 ? L.a.anchors[s][a][q - 2] : 0.0f, live, bb, c, best, besti);
     if (q == 0 && live) {
         *reinterpret_cast<f32x4 *>(bboxes + out_row * 4) = bb;
         if (conf) conf[out_row] = c;
@@ -96,7 +96,7 @@ hipError_t launch_decode(const DecodeArgs &a, float *bboxes, float *conf, float 
     int acc = 0;
     for (int i = 0; i < 3; ++i) {
         L.blk_start[i] = acc;
-        const long long total = (long long)a.B * a.g[i] * a.g[i] * 3;
+        const long long total = (long long)a.B * a.gh[i] * a.gw[i] * 3;
         acc += (int)((total + DEC_BOXES - 1) / DEC_BOXES);
     }
     L.blk_start[3] = acc;

@@ -19,13 +19,14 @@ __device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf
 // anchor_wh: anchors[a][q - 2] for q >= 2 (ignored otherwise).  On return: bb / conf are valid in lane q == 0, best / besti in
 // all four lanes (MERGE) or per lane (no MERGE).  WRITE_PROBS stores the lane's class probabilities back over their logits.
 template <bool WRITE_PROBS, bool MERGE>
-__device__ __forceinline__ void decode_box_lanes(float *t, int q, int wave_lane, int nc, int g, int row, int col, float anchor_wh,
+__device__ __forceinline__ void decode_box_lanes(float *t, int q, int wave_lane, int nc, int gh, int gw, int row, int col, float anchor_wh,
                                                  bool live, dec_f32x4 &bb, float &conf, float &best, int &besti)
 {
-    // grid = meshgrid(range(W), range(H)): (...,0) = col, (...,1) = row; divisor cast([H,W]) (square grid)
+    // grid = meshgrid(range(W), range(H)): (...,0) = col, (...,1) = row; each axis divided by its own extent: x by gw, y by gh.
+    // (The reference divides (x, y) by cast([H, W]), the same for every square grid; for gh != gw see include/y3.h, y3_yolo_decode_hw.)
     float v;
     if (q < 2)
-        v = (sigmoidf_(t[q]) + (float)(q == 0 ? col : row)) / (float)g;
+        v = (sigmoidf_(t[q]) + (float)(q == 0 ? col : row)) / (float)(q == 0 ? gw : gh);
     else
         v = expf(t[q]) * anchor_wh;
     const int base = wave_lane & ~3;             // first lane of this box inside the wave
@@ -66,7 +67,7 @@ struct DecodeHead {
     float *boxes;        // [B, N, 4] of the (sub-)batch this launch covers
     int64_t *cls;        // [B, N]
     float *scores;       // [B, N]
-    int g, off, N, nc;   // grid size of this scale, first box index of the scale, boxes per image, classes
+    int gh, gw, off, N, nc;   // grid rows and columns of this scale, first box index of the scale, boxes per image, classes
     float anchors[3][2];
 };
 
@@ -77,7 +78,7 @@ __device__ __forceinline__ void decode_rows_from_lds(float *C, int stride, int n
 {
     const int tid = threadIdx.x;
     const int F = 5 + h.nc;
-    const int cells = h.g * h.g;
+    const int cells = h.gh * h.gw;
     const int tasks = nrows * 12;                      // 3 boxes per pixel x 4 lanes per box
     for (int base = 0; base < tasks; base += NT) {
         const int idx = base + tid;
@@ -91,12 +92,12 @@ __device__ __forceinline__ void decode_rows_from_lds(float *C, int stride, int n
         const int mm = live ? m : 0;
         const int b = mm / cells;
         const int cell = mm - b * cells;
-        const int row = cell / h.g, col = cell - row * h.g;
+        const int row = cell / h.gw, col = cell - row * h.gw;
         float *t = C + r * stride + a * F;
         dec_f32x4 bb;
         float conf, best;
         int besti;
-        decode_box_lanes<false, true>(t, q, tid & 63, h.nc, h.g, row, col, q >= 2 ? h.anchors[a][q - 2] : 0.0f, live, bb, conf, best, besti);
+        decode_box_lanes<false, true>(t, q, tid & 63, h.nc, h.gh, h.gw, row, col, q >= 2 ? h.anchors[a][q - 2] : 0.0f, live, bb, conf, best, besti);
         if (q == 0 && live) {
             const long long out_row = (long long)b * h.N + h.off + cell * 3 + a;
             *reinterpret_cast<dec_f32x4 *>(h.boxes + out_row * 4) = bb;

@@ -353,31 +353,31 @@ hipError_t launch_pack(const float *boxes, const int64_t *cls, const float *scor
 // Packed rows of letterboxed images -> coordinates of the source frame, in place (include/y3.h, y3_unletterbox_detections).
 // blockIdx.y is the image within the launch (its geometry: scalar loads from the kernel arguments), one thread per packed row.
 // Four separately rounded fp32 operations per coordinate; the library is built with -ffp-contract=off.  An image whose
-// geometry is the whole canvas is left alone: x * S / S is not x in fp32.
+// geometry is the whole Hc x Wc canvas is left alone: x * Wc / Wc is not x in fp32.
 __global__ __launch_bounds__(256) void unletterbox_kernel(unsigned *__restrict__ packed, const int32_t *__restrict__ nv,
-                                                          UnletterboxTable table, int M, int S)
+                                                          UnletterboxTable table, int M, int Hc, int Wc)
 {
     const LetterboxGeom g = table.g[blockIdx.y];
-    if (g.sh == S && g.sw == S && g.top == 0 && g.left == 0) return;
+    if (g.sh == Hc && g.sw == Wc && g.top == 0 && g.left == 0) return;
     const int r = blockIdx.x * 256 + threadIdx.x;
     if (r >= M || r >= nv[blockIdx.y]) return;
     unsigned *o = packed + ((size_t)blockIdx.y * M + r) * 7;
-    const float fs = (float)S, fl = (float)g.left, ft = (float)g.top, fw = (float)g.sw, fh = (float)g.sh;
+    const float fcw = (float)Wc, fch = (float)Hc, fl = (float)g.left, ft = (float)g.top, fw = (float)g.sw, fh = (float)g.sh;
     const float xmin = __uint_as_float(o[0]), ymin = __uint_as_float(o[1]);
     const float xmax = __uint_as_float(o[2]), ymax = __uint_as_float(o[3]);
-    o[0] = __float_as_uint((xmin * fs - fl) / fw);
-    o[1] = __float_as_uint((ymin * fs - ft) / fh);
-    o[2] = __float_as_uint((xmax * fs - fl) / fw);
-    o[3] = __float_as_uint((ymax * fs - ft) / fh);
+    o[0] = __float_as_uint((xmin * fcw - fl) / fw);
+    o[1] = __float_as_uint((ymin * fch - ft) / fh);
+    o[2] = __float_as_uint((xmax * fcw - fl) / fw);
+    o[3] = __float_as_uint((ymax * fch - ft) / fh);
 }
 
 // geoms: n (1..kUnletterboxTableImages) validated geometries; packed / nv: first image of the launch
-hipError_t launch_unletterbox(void *packed, const int32_t *nv, const LetterboxGeom *geoms, int n, int M, int S, hipStream_t s)
+hipError_t launch_unletterbox(void *packed, const int32_t *nv, const LetterboxGeom *geoms, int n, int M, int Hc, int Wc, hipStream_t s)
 {
     UnletterboxTable table{};
     for (int i = 0; i < n; ++i) table.g[i] = geoms[i];
     dim3 grid((unsigned)((M + 255) / 256), (unsigned)n), block(256);
-    hipLaunchKernelGGL(unletterbox_kernel, grid, block, 0, s, static_cast<unsigned *>(packed), nv, table, M, S);
+    hipLaunchKernelGGL(unletterbox_kernel, grid, block, 0, s, static_cast<unsigned *>(packed), nv, table, M, Hc, Wc);
     return hipGetLastError();
 }
 

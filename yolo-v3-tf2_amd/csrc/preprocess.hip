@@ -1,5 +1,5 @@
 // Image input stage on the GPU (SURVEY.md 8f "n2"): uint8 HWC image -> float32 in [0,1] -> bilinear resize to
-// S x S, written straight into slot b of the NHWC batch the conv program reads.
+// Hc x Wc (a square S x S for the entry points without _hw), written straight into slot b of the NHWC batch the conv program reads.
 // Replaces, for the image_file / images_dir sources of reference inference.py:157-158,
 //   tf.image.decode_image(..., channels=3, dtype=tf.float32)   (uint8 -> float: cast * (1/255), alpha dropped)
 //   tf.image.resize(image, (S, S))                              (bilinear, antialias=False, half-pixel centres)
@@ -30,15 +30,15 @@ template <>
 __device__ __forceinline__ float px<RawU8>(const RawU8 *p) { return (float)p->v; }
 
 // One output pixel (3 floats) of the resize: the per-pixel body of both kernels below, so that the per-image and the
-// batched launch cannot drift apart.  i = oy * S + ox.
-// LB (Y3_IMAGE_LETTERBOX): the resize is to g.sh x g.sw and sits at (g.top, g.left) of the S x S canvas; a pixel outside that
+// batched launch cannot drift apart.  i = oy * Wc + ox on the Hc x Wc canvas.
+// LB (Y3_IMAGE_LETTERBOX): the resize is to g.sh x g.sw and sits at (g.top, g.left) of the canvas; a pixel outside that
 // block is 0.0f -- it is written like any other, a reused slot keeps nothing of its last image.  Inside, the same operations in
-// the same order with (sh, sw) in the place of (S, S).  LB = false compiles to what it was before the flag existed.
+// the same order with (sh, sw) in the place of (Hc, Wc).  LB = false compiles to what it was before the flag existed.
 template <typename T, bool LB>
-__device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, int S, LetterboxGeom g, int i,
+__device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, int Hc, int Wc, LetterboxGeom g, int i,
                                              float *out)
 {
-    int oy = i / S, ox = i - oy * S;
+    int oy = i / Wc, ox = i - oy * Wc;
     if (LB) {
         oy -= g.top;
         ox -= g.left;
@@ -47,7 +47,7 @@ __device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, i
             return;
         }
     }
-    const int OH = LB ? g.sh : S, OW = LB ? g.sw : S;
+    const int OH = LB ? g.sh : Hc, OW = LB ? g.sw : Wc;
     const float sy = (float)H / (float)OH, sx = (float)W / (float)OW;
     const float fy = ((float)oy + 0.5f) * sy - 0.5f, fx = ((float)ox + 0.5f) * sx - 0.5f;
     const float fly = floorf(fy), flx = floorf(fx);
@@ -68,41 +68,41 @@ __device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, i
 
 template <typename T, bool LB>
 __global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, int H, int W, int pix_stride,
-                                                     float *__restrict__ dst, int S, LetterboxGeom g)
+                                                     float *__restrict__ dst, int Hc, int Wc, LetterboxGeom g)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= S * S) return;
+    if (i >= Hc * Wc) return;
     float v[3];
-    resize_pixel<T, LB>(src, H, W, pix_stride, S, g, i, v);
+    resize_pixel<T, LB>(src, H, W, pix_stride, Hc, Wc, g, i, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[(size_t)i * 3 + c] = v[c];
 }
 
-// A batch of unlike images in one launch: blockIdx.y is the image within the launch, blockIdx.x tiles its S*S output pixels.
+// A batch of unlike images in one launch: blockIdx.y is the image within the launch, blockIdx.x tiles its Hc*Wc output pixels.
 // The descriptors and geometries travel by value in the kernel arguments (PreprocessTable, 2.5 KB of the 4 KB limit): nothing
 // extra is copied, they have no lifetime to manage, and the launch can be captured into a graph.
 // VEC: every thread produces four consecutive pixels (12 floats) and writes them as three 16-byte stores; needs
-// S*S % 4 == 0 and a 16-byte aligned destination, which holds for every network size (S a multiple of 32).  Otherwise one
+// Hc*Wc % 4 == 0 and a 16-byte aligned destination, which holds for every network size (sides multiples of 32).  Otherwise one
 // pixel and three scalar stores per thread.  Each of the four pixels decides on its own whether it is padding: a thread may
 // straddle the edge of the letterboxed block.
 template <typename T, bool VEC, bool LB>
 __device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src, int H, int W, int pix_stride,
-                                                      float *__restrict__ dst, int S, LetterboxGeom g)
+                                                      float *__restrict__ dst, int Hc, int Wc, LetterboxGeom g)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
     if (VEC) {
-        if (q * 4 >= S * S) return;
+        if (q * 4 >= Hc * Wc) return;
         float v[12];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) resize_pixel<T, LB>(src, H, W, pix_stride, S, g, q * 4 + p, v + 3 * p);
+        for (int p = 0; p < 4; ++p) resize_pixel<T, LB>(src, H, W, pix_stride, Hc, Wc, g, q * 4 + p, v + 3 * p);
         float4 *o = reinterpret_cast<float4 *>(dst + (size_t)q * 12);
         o[0] = make_float4(v[0], v[1], v[2], v[3]);
         o[1] = make_float4(v[4], v[5], v[6], v[7]);
         o[2] = make_float4(v[8], v[9], v[10], v[11]);
     } else {
-        if (q >= S * S) return;
+        if (q >= Hc * Wc) return;
         float v[3];
-        resize_pixel<T, LB>(src, H, W, pix_stride, S, g, q, v);
+        resize_pixel<T, LB>(src, H, W, pix_stride, Hc, Wc, g, q, v);
 #pragma unroll
         for (int c = 0; c < 3; ++c) dst[(size_t)q * 3 + c] = v[c];
     }
@@ -110,72 +110,73 @@ __device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src,
 
 template <bool VEC, bool LB>
 __device__ __forceinline__ void preprocess_batch_modes(const unsigned char *__restrict__ src, const y3_image_desc &d, int mode,
-                                                       float *__restrict__ dst, int S, LetterboxGeom g)
+                                                       float *__restrict__ dst, int Hc, int Wc, LetterboxGeom g)
 {
     if (mode == 2)
-        preprocess_batch_body<RawU8, VEC, LB>(reinterpret_cast<const RawU8 *>(src), d.height, d.width, d.channels, dst, S, g);
+        preprocess_batch_body<RawU8, VEC, LB>(reinterpret_cast<const RawU8 *>(src), d.height, d.width, d.channels, dst, Hc, Wc, g);
     else if (mode == 1)
-        preprocess_batch_body<unsigned char, VEC, LB>(src, d.height, d.width, d.channels, dst, S, g);
+        preprocess_batch_body<unsigned char, VEC, LB>(src, d.height, d.width, d.channels, dst, Hc, Wc, g);
     else
-        preprocess_batch_body<float, VEC, LB>(reinterpret_cast<const float *>(src), d.height, d.width, d.channels, dst, S, g);
+        preprocess_batch_body<float, VEC, LB>(reinterpret_cast<const float *>(src), d.height, d.width, d.channels, dst, Hc, Wc, g);
 }
 
 template <bool VEC>
 __global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char *__restrict__ pixels, PreprocessTable table,
-                                                               float *__restrict__ batch, int S)
+                                                               float *__restrict__ batch, int Hc, int Wc)
 {
     const y3_image_desc d = table.d[blockIdx.y];          // uniform per workgroup: scalar loads from the kernel arguments
     const unsigned char *src = pixels + d.offset;
-    float *dst = batch + (size_t)blockIdx.y * S * S * 3;
+    float *dst = batch + (size_t)blockIdx.y * Hc * Wc * 3;
     const int mode = d.mode & ~Y3_IMAGE_LETTERBOX;
     if (d.mode & Y3_IMAGE_LETTERBOX)                      // one branch per workgroup each, outside the pixel body
-        preprocess_batch_modes<VEC, true>(src, d, mode, dst, S, table.g[blockIdx.y]);
+        preprocess_batch_modes<VEC, true>(src, d, mode, dst, Hc, Wc, table.g[blockIdx.y]);
     else
-        preprocess_batch_modes<VEC, false>(src, d, mode, dst, S, LetterboxGeom{});
+        preprocess_batch_modes<VEC, false>(src, d, mode, dst, Hc, Wc, LetterboxGeom{});
 }
 
 template <typename T>
-static void launch_resize_as(bool lb, dim3 grid, hipStream_t s, const void *src, int H, int W, int pix_stride, float *dst, int S,
+static void launch_resize_as(bool lb, dim3 grid, hipStream_t s, const void *src, int H, int W, int pix_stride, float *dst, int Hc, int Wc,
                              const LetterboxGeom &g)
 {
     if (lb)
-        hipLaunchKernelGGL((resize_kernel<T, true>), grid, dim3(256), 0, s, static_cast<const T *>(src), H, W, pix_stride, dst, S, g);
+        hipLaunchKernelGGL((resize_kernel<T, true>), grid, dim3(256), 0, s, static_cast<const T *>(src), H, W, pix_stride, dst, Hc, Wc, g);
     else
-        hipLaunchKernelGGL((resize_kernel<T, false>), grid, dim3(256), 0, s, static_cast<const T *>(src), H, W, pix_stride, dst, S, g);
+        hipLaunchKernelGGL((resize_kernel<T, false>), grid, dim3(256), 0, s, static_cast<const T *>(src), H, W, pix_stride, dst, Hc, Wc, g);
 }
 
-hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride, float *dst, int S, const LetterboxGeom &g, hipStream_t s)
+hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride, float *dst, int Hc, int Wc, const LetterboxGeom &g,
+                         hipStream_t s)
 {
-    dim3 grid((S * S + 255) / 256);
+    dim3 grid((Hc * Wc + 255) / 256);
     const bool lb = (mode & Y3_IMAGE_LETTERBOX) != 0;
     const int m = mode & ~Y3_IMAGE_LETTERBOX;
     if (m == 2)
-        launch_resize_as<RawU8>(lb, grid, s, src, H, W, pix_stride, dst, S, g);
+        launch_resize_as<RawU8>(lb, grid, s, src, H, W, pix_stride, dst, Hc, Wc, g);
     else if (m)
-        launch_resize_as<unsigned char>(lb, grid, s, src, H, W, pix_stride, dst, S, g);
+        launch_resize_as<unsigned char>(lb, grid, s, src, H, W, pix_stride, dst, Hc, Wc, g);
     else
-        launch_resize_as<float>(lb, grid, s, src, H, W, pix_stride, dst, S, g);
+        launch_resize_as<float>(lb, grid, s, src, H, W, pix_stride, dst, Hc, Wc, g);
     return hipGetLastError();
 }
 
 // descs / geoms: n (1..kPreprocessTableImages) validated descriptors and their geometries; dst: slot of the first image.
 // Vector stores when the geometry allows.
-hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int S,
-                                   hipStream_t s)
+hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
+                                   int Wc, hipStream_t s)
 {
     PreprocessTable table{};
     for (int i = 0; i < n; ++i) {
         table.d[i] = descs[i];
         table.g[i] = geoms[i];
     }
-    const bool vec = ((size_t)S * S) % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+    const bool vec = ((size_t)Hc * Wc) % 4 == 0 && ((uintptr_t)dst & 15) == 0;
     const int per_block = vec ? 1024 : 256;
-    dim3 grid((unsigned)(((size_t)S * S + per_block - 1) / per_block), (unsigned)n), block(256);
+    dim3 grid((unsigned)(((size_t)Hc * Wc + per_block - 1) / per_block), (unsigned)n), block(256);
     const unsigned char *p = static_cast<const unsigned char *>(pixels);
     if (vec)
-        hipLaunchKernelGGL(preprocess_batch_kernel<true>, grid, block, 0, s, p, table, dst, S);
+        hipLaunchKernelGGL(preprocess_batch_kernel<true>, grid, block, 0, s, p, table, dst, Hc, Wc);
     else
-        hipLaunchKernelGGL(preprocess_batch_kernel<false>, grid, block, 0, s, p, table, dst, S);
+        hipLaunchKernelGGL(preprocess_batch_kernel<false>, grid, block, 0, s, p, table, dst, Hc, Wc);
     return hipGetLastError();
 }
 

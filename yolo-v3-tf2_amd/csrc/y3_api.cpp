@@ -62,14 +62,14 @@ bool test_fail_alloc() noexcept
 
 // include/y3.h, Y3_IMAGE_LETTERBOX.  Every operation in fp32 (this file is compiled with -ffp-contract=off), nearbyintf in the
 // default rounding mode (half to even): bit for bit what core/utils.letterbox_geometry computes with np.float32 and np.rint.
-LetterboxGeom letterbox_geom(int h, int w, int S)
+LetterboxGeom letterbox_geom(int h, int w, int Hc, int Wc)
 {
-    const float scale = std::min((float)S / (float)h, (float)S / (float)w);
+    const float scale = std::min((float)Hc / (float)h, (float)Wc / (float)w);
     LetterboxGeom g;
     g.sh = std::max(1, (int)nearbyintf(scale * (float)h));
     g.sw = std::max(1, (int)nearbyintf(scale * (float)w));
-    g.top = (S - g.sh) >> 1;       // floor, also where the difference is negative (refused by letterbox_geom_fits)
-    g.left = (S - g.sw) >> 1;
+    g.top = (Hc - g.sh) >> 1;      // floor, also where the difference is negative (refused by letterbox_geom_fits)
+    g.left = (Wc - g.sw) >> 1;
     return g;
 }
 }  // namespace y3
@@ -149,7 +149,7 @@ struct y3_net {
     int outputs[3] = {0, 0, 0};
     int nclasses = 0;
     // plan
-    int max_batch = 0, image_size = 0, dtype = Y3_DTYPE_F32;
+    int max_batch = 0, height = 0, width = 0, dtype = Y3_DTYPE_F32;   // the planned canvas: height x width (0: no plan)
     int keep_all = 0;              // 1: no buffer reuse, every intermediate stays readable after a forward
     int lanes = 1;                 // sub-batches run concurrently on forked streams (y3_net_set_lanes)
     int early_convs = 0;           // y3_net_set_early_chunk: the first early_convs convs run early_chunk images at a time
@@ -180,7 +180,8 @@ struct y3_net {
 
 namespace {
 
-int spatial(const y3_net *n, int t) { return n->image_size / n->tensors[t].div; }
+int rows(const y3_net *n, int t) { return n->height / n->tensors[t].div; }
+int cols(const y3_net *n, int t) { return n->width / n->tensors[t].div; }
 
 void free_plan(y3_net *n)
 {
@@ -416,7 +417,7 @@ static bool is_output(const y3_net *net, int t) { return t == net->outputs[0] ||
 // else reads conv0's output, and the plan is fp32 with every intermediate reusable: the pair runs as csrc/conv_stem.hip.
 static bool stem_applicable(const y3_net *net)
 {
-    if ((net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16) || net->keep_all || net->image_size % 32 || net->early_ops > 0)
+    if ((net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16) || net->keep_all || net->height % 32 || net->width % 32 || net->early_ops > 0)
         return false;
     if (net->ops.size() < 2 || net->ops[0].kind != 0 || net->ops[1].kind != 0) return false;
     const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[1].index];
@@ -729,7 +730,7 @@ try {
     net->stem_mode = on;
     net->stem_mode_set = true;
     // takes effect at once on a planned net when the graph qualifies (decided again by the next y3_net_plan)
-    if (net->image_size) {
+    if (net->height) {
         net->stem_fused = on && stem_applicable(net);
         net->stem_conv2 = net->stem_fused && on == 1 && stem_conv2_applicable(net);
     }
@@ -771,7 +772,7 @@ try {
 }
 Y3_CATCH("y3_net_keep_activations")
 
-static void detect_layout(const y3_net *net, int batch, size_t off[9], size_t *n_boxes, int32_t gs[3], size_t gelems[3]);
+static void detect_layout(const y3_net *net, int batch, size_t off[9], size_t *n_boxes, int32_t gs[3][2], size_t gelems[3]);
 
 // forked streams / events of the concurrent sub-batches: created at plan time so that a forward enqueues work only
 static y3_status ensure_lanes(y3_net *net)
@@ -823,13 +824,16 @@ static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const
     return Y3_OK;
 }
 
-y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype)
+y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int dtype)
 try {
-    if (!net || max_batch <= 0 || image_size <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
+    if (!net || max_batch <= 0 || height <= 0 || width <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
     if (dtype != Y3_DTYPE_F32 && dtype != Y3_DTYPE_BF16 && dtype != Y3_DTYPE_F32X3 && dtype != Y3_DTYPE_F32X2)
         return fail(Y3_ERR_INVALID, "y3_net_plan: unknown dtype %d", dtype);
     for (const y3_tensor_desc &t : net->tensors)
-        if (t.div <= 0 || image_size % t.div) return fail(Y3_ERR_INVALID, "y3_net_plan: image_size %d not divisible by %d", image_size, t.div);
+        if (t.div <= 0 || height % t.div || width % t.div) {
+            if (height == width) return fail(Y3_ERR_INVALID, "y3_net_plan: image_size %d not divisible by %d", height, t.div);   // the square call's text, as ever
+            return fail(Y3_ERR_INVALID, "y3_net_plan_hw: image size %d x %d (height x width) not divisible by %d", height, width, t.div);
+        }
     if (dtype == Y3_DTYPE_F32X2)
         for (size_t i = 0; i < net->convs.size(); ++i)
             if (net->convs[i].loaded && !net->convs[i].x2_ok)
@@ -843,7 +847,8 @@ try {
     }
     free_plan(net);
     net->max_batch = max_batch;
-    net->image_size = image_size;
+    net->height = height;
+    net->width = width;
     net->dtype = dtype;
     const int nt = (int)net->tensors.size();
     // liveness over the op list; tensors with equal lifetime class share blocks (first-fit free list)
@@ -884,8 +889,7 @@ try {
     net->dense.assign(nt, 0);
     for (int t = 0; t < nt; ++t) net->dense[t] = (first[t] >= 0 && first[t] < net->early_ops) ? 1 : 0;
     for (int t = 0; t < nt; ++t) {
-        const int s = image_size / net->tensors[t].div;
-        net->tbytes[t] = (size_t)max_batch * s * s * net->tensors[t].channels * arena_elem_bytes(dtype);
+        net->tbytes[t] = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels * arena_elem_bytes(dtype);
         if (net->tbytes[t] >= 0xFFFFFFF0ull && first[t] >= 0)
             return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, net->tbytes[t]);
     }
@@ -899,7 +903,7 @@ try {
     net->stem_conv2 = net->stem_fused && net->stem_mode == 1 && stem_conv2_applicable(net);
     if (net->nclasses > 0) {   // scratch of y3_net_detect: no allocation inside the stream-ordered call
         size_t off[9], n_boxes, gelems[3];
-        int32_t gs[3];
+        int32_t gs[3][2];
         detect_layout(net, max_batch, off, &n_boxes, gs, gelems);
         hipError_t e = hipMalloc(&net->det_buf, off[8]);
         if (e != hipSuccess) {
@@ -910,17 +914,24 @@ try {
     }
     return Y3_OK;
 }
+Y3_CATCH("y3_net_plan_hw")
+
+y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype)
+try {
+    return y3_net_plan_hw(net, max_batch, image_size, image_size, dtype);
+}
 Y3_CATCH("y3_net_plan")
 
 // byte offsets of the y3_net_detect scratch for `batch` images (and the total in [8])
-static void detect_layout(const y3_net *net, int batch, size_t off[9], size_t *n_boxes, int32_t gs[3], size_t gelems[3])
+static void detect_layout(const y3_net *net, int batch, size_t off[9], size_t *n_boxes, int32_t gs[3][2], size_t gelems[3])
 {
     const size_t per = (size_t)3 * (5 + net->nclasses);
     size_t n = 0;
     for (int i = 0; i < 3; ++i) {
-        gs[i] = spatial(net, net->outputs[i]);
-        gelems[i] = (size_t)batch * gs[i] * gs[i] * per;
-        n += (size_t)3 * gs[i] * gs[i];
+        gs[i][0] = rows(net, net->outputs[i]);
+        gs[i][1] = cols(net, net->outputs[i]);
+        gelems[i] = (size_t)batch * gs[i][0] * gs[i][1] * per;
+        n += (size_t)3 * gs[i][0] * gs[i][1];
     }
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     off[0] = 0;                                              // grid 0
@@ -937,11 +948,11 @@ static void detect_layout(const y3_net *net, int batch, size_t off[9], size_t *n
 
 double y3_net_flops_per_image(const y3_net *net)
 {
-    if (!net || !net->image_size) return 0.0;
+    if (!net || !net->height) return 0.0;
     double tot = 0;
     for (const ConvSlot &c : net->convs) {
-        const double ho = net->image_size / c.d.out_div;
-        tot += 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * ho;
+        const double ho = net->height / c.d.out_div, wo = net->width / c.d.out_div;
+        tot += 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * wo;
     }
     return tot;
 }
@@ -967,7 +978,7 @@ static y3_status check_forward_args(const y3_net *net, bool args_ok, int batch, 
 {
     if (!net || !args_ok || batch <= 0) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
     if (heads && net->nclasses <= 0) return fail(Y3_ERR_STATE, "%s: the net was created without detection heads (nclasses = 0)", who);
-    if (!net->image_size) return fail(Y3_ERR_STATE, "%s: call y3_net_plan first", who);
+    if (!net->height) return fail(Y3_ERR_STATE, "%s: call y3_net_plan first", who);
     if (batch > net->max_batch) return fail(Y3_ERR_INVALID, "%s: batch %d > planned %d", who, batch, net->max_batch);
     return Y3_OK;
 }
@@ -979,7 +990,7 @@ struct Slice {
     int b0, nb, lane;
     hipStream_t s;
 
-    size_t img_elems(int t) const { return (size_t)spatial(net, t) * spatial(net, t) * net->tensors[t].channels; }
+    size_t img_elems(int t) const { return (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels; }
     // a net output written straight into the caller's fp32 grid (not staged)
     bool caller_grid(int t) const { return is_output(net, t) && !net->staged[t]; }
     // element size: head grids are always fp32; the image batch is fp32 when the Cin = 3 first-layer kernel reads it
@@ -1024,8 +1035,10 @@ struct Slice {
         a.residual = ptr(d.residual);
         a.dst = ptr(d.dst);
         a.B = nb;
-        a.H = a.W = net->image_size / d.in_div;
-        a.Ho = a.Wo = net->image_size / d.out_div;
+        a.H = net->height / d.in_div;
+        a.W = net->width / d.in_div;
+        a.Ho = net->height / d.out_div;
+        a.Wo = net->width / d.out_div;
         a.Cin = d.cin;
         a.C0 = d.c0;
         a.Cout = d.cout;
@@ -1074,7 +1087,8 @@ struct Slice {
         sa.shift1 = c1.shift_dev;
         sa.dst = a1.dst;
         sa.B = nb;
-        sa.S = net->image_size;
+        sa.H = net->height;
+        sa.W = net->width;
         sa.leaky0 = c0.d.leaky;
         sa.leaky1 = c1.d.leaky;
         sa.img_bytes = (unsigned)bytes(c0.d.src0);
@@ -1148,15 +1162,15 @@ struct Slice {
         if (net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
         const y3_aux_desc &x = net->aux[index];
         auto p = [&](int t) { return static_cast<float *>(ptr(t)); };
-        const int sp = spatial(net, x.dst);
+        const int sh = rows(net, x.dst), sw = cols(net, x.dst);
         const int C = net->tensors[x.dst].channels;
         hipError_t e = hipSuccess;
         if (x.kind == Y3_AUX_ADD)
-            e = y3::launch_add(p(x.src0), p(x.src1), p(x.dst), (size_t)nb * sp * sp * C, s);
+            e = y3::launch_add(p(x.src0), p(x.src1), p(x.dst), (size_t)nb * sh * sw * C, s);
         else if (x.kind == Y3_AUX_UPSAMPLE2X)
-            e = y3::launch_upsample2x(p(x.src0), nb, sp / 2, sp / 2, C, p(x.dst), s);
+            e = y3::launch_upsample2x(p(x.src0), nb, sh / 2, sw / 2, C, p(x.dst), s);
         else if (x.kind == Y3_AUX_CONCAT)
-            e = y3::launch_concat(p(x.src0), net->tensors[x.src0].channels, p(x.src1), net->tensors[x.src1].channels, (size_t)nb * sp * sp, p(x.dst), s);
+            e = y3::launch_concat(p(x.src0), net->tensors[x.src0].channels, p(x.src1), net->tensors[x.src1].channels, (size_t)nb * sh * sw, p(x.dst), s);
         else
             return fail(Y3_ERR_INVALID, "unknown aux op kind %d", x.kind);
         if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d launch: %s", index, hipGetErrorString(e));
@@ -1197,7 +1211,7 @@ struct Slice {
         for (int k = 0; k < 3 && op_end == (int)net->ops.size(); ++k) {
             const int t = net->outputs[k];
             if (!net->staged[t]) continue;
-            const size_t npix = (size_t)nb * spatial(net, t) * spatial(net, t);
+            const size_t npix = (size_t)nb * rows(net, t) * cols(net, t);
             hipError_t e = y3::launch_to_f32(net->dtype, ptr(t), f.grids[k] + (size_t)b0 * img_elems(t), npix, net->tensors[t].channels, s);
             if (e != hipSuccess) return fail(Y3_ERR_HIP, "output %d conversion: %s", k, hipGetErrorString(e));
         }
@@ -1294,12 +1308,12 @@ y3_status y3_net_profile_convs(y3_net *net, const float *images_dev, int batch, 
 try {
     if (!net || !ms_out) return fail(Y3_ERR_INVALID, "y3_net_profile_convs: bad argument");
     // head grids go to scratch owned by this call
-    if (!net->image_size || batch <= 0) return fail(Y3_ERR_STATE, "y3_net_profile_convs: call y3_net_plan first (and batch > 0)");
+    if (!net->height || batch <= 0) return fail(Y3_ERR_STATE, "y3_net_profile_convs: call y3_net_plan first (and batch > 0)");
     Y3_ENTER_DEVICE(net);
     float *g[3] = {nullptr, nullptr, nullptr};
     for (int i = 0; i < 3; ++i) {
-        const int sp = spatial(net, net->outputs[i]);
-        hipError_t e = hipMalloc(&g[i], (size_t)batch * sp * sp * net->tensors[net->outputs[i]].channels * sizeof(float));
+        const int t = net->outputs[i];
+        hipError_t e = hipMalloc(&g[i], (size_t)batch * rows(net, t) * cols(net, t) * net->tensors[net->outputs[i]].channels * sizeof(float));
         if (e != hipSuccess) {
             for (int k = 0; k < i; ++k) (void)hipFree(g[k]);
             return fail(Y3_ERR_OOM, "y3_net_profile_convs: hipMalloc: %s", hipGetErrorString(e));
@@ -1400,8 +1414,8 @@ try {
     for (size_t i = 0; i < net->convs.size(); ++i) {
         const ConvSlot &c = net->convs[i];
         if (!conv_carries_stamps(net, i)) continue;
-        const double ho = net->image_size ? net->image_size / c.d.out_div : 0;
-        const double fl = 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * ho;
+        const double ho = net->height / c.d.out_div, wo = net->width / c.d.out_div;   // 0 without a plan
+        const double fl = 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * wo;
         if (fl > best) { best = fl; pick = (int)i; }
     }
     if (pick < 0) return fail(Y3_ERR_STATE, "y3_net_measure_sclk: no launch of this plan carries clock stamps (fp32 plan or fused stem needed)");
@@ -1419,15 +1433,15 @@ Y3_CATCH("y3_net_measure_sclk_all")
 
 y3_status y3_net_read_tensor(y3_net *net, int t, int batch, float *dst_dev, size_t *n_elems, void *stream)
 try {
-    if (!net || t < 0 || t >= (int)net->tensors.size() || !net->image_size)
+    if (!net || t < 0 || t >= (int)net->tensors.size() || !net->height)
         return fail(Y3_ERR_INVALID, "y3_net_read_tensor: bad argument");
-    const int sp = spatial(net, t);
-    const size_t n = (size_t)batch * sp * sp * net->tensors[t].channels;
+    const size_t npix = (size_t)batch * rows(net, t) * cols(net, t);
+    const size_t n = npix * net->tensors[t].channels;
     if (n_elems) *n_elems = n;
     if (!dst_dev) return Y3_OK;
     if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
     Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
-    hipError_t e = y3::launch_to_f32(net->dtype, net->tdev[t], dst_dev, (size_t)batch * sp * sp, net->tensors[t].channels, (hipStream_t)stream);
+    hipError_t e = y3::launch_to_f32(net->dtype, net->tdev[t], dst_dev, npix, net->tensors[t].channels, (hipStream_t)stream);
     if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
     return Y3_OK;
 }
@@ -1438,117 +1452,169 @@ namespace {
 // is_uint8 / y3_image_desc.mode: 0, 1 or 2, with or without Y3_IMAGE_LETTERBOX
 bool image_mode_ok(int mode) { return (mode & ~Y3_IMAGE_LETTERBOX) >= 0 && (mode & ~Y3_IMAGE_LETTERBOX) <= 2; }
 // the geometry of one image: the whole canvas without the flag
-y3::LetterboxGeom image_geom(int mode, int h, int w, int S)
+y3::LetterboxGeom image_geom(int mode, int h, int w, int Hc, int Wc)
 {
-    return (mode & Y3_IMAGE_LETTERBOX) ? y3::letterbox_geom(h, w, S) : y3::LetterboxGeom{S, S, 0, 0};
+    return (mode & Y3_IMAGE_LETTERBOX) ? y3::letterbox_geom(h, w, Hc, Wc) : y3::LetterboxGeom{Hc, Wc, 0, 0};
 }
 }  // namespace
+
+// The square entry points (y3_preprocess_image, ...) are their _hw counterparts with canvas_h == canvas_w; `who` names the
+// entry point the caller used in the messages.
+static y3_status preprocess_image_hw(const char *who, const void *image_dev, int is_uint8, int height, int width, int channels,
+                                     float *batch_dev, int slot, int Hc, int Wc, void *stream)
+{
+    if (!image_dev || !batch_dev || height <= 0 || width <= 0 || channels < 3 || channels > 4 || slot < 0 ||
+        Hc <= 0 || Wc <= 0 || !image_mode_ok(is_uint8) || ((is_uint8 & ~Y3_IMAGE_LETTERBOX) == 0 && ((uintptr_t)image_dev & 3)))
+        return fail(Y3_ERR_INVALID, "%s: bad argument (channels must be 3 or 4)", who);
+    const y3::LetterboxGeom g = image_geom(is_uint8, height, width, Hc, Wc);
+    if (!y3::letterbox_geom_fits(g, Hc, Wc))
+        return fail(Y3_ERR_INVALID, "%s: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, height, width,
+                    g.sh, g.sw, g.top, g.left, Hc, Wc);
+    float *dst = batch_dev + (size_t)slot * Hc * Wc * 3;
+    hipError_t e = y3::launch_resize(image_dev, is_uint8, height, width, channels, dst, Hc, Wc, g, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}
+
+y3_status y3_preprocess_image_hw(const void *image_dev, int is_uint8, int height, int width, int channels,
+                                 float *batch_dev, int slot, int canvas_h, int canvas_w, void *stream)
+try {
+    return preprocess_image_hw("y3_preprocess_image_hw", image_dev, is_uint8, height, width, channels, batch_dev, slot, canvas_h, canvas_w, stream);
+}
+Y3_CATCH("y3_preprocess_image_hw")
 
 y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, int width, int channels,
                               float *batch_dev, int slot, int image_size, void *stream)
 try {
-    if (!image_dev || !batch_dev || height <= 0 || width <= 0 || channels < 3 || channels > 4 || slot < 0 ||
-        image_size <= 0 || !image_mode_ok(is_uint8) || ((is_uint8 & ~Y3_IMAGE_LETTERBOX) == 0 && ((uintptr_t)image_dev & 3)))
-        return fail(Y3_ERR_INVALID, "y3_preprocess_image: bad argument (channels must be 3 or 4)");
-    const y3::LetterboxGeom g = image_geom(is_uint8, height, width, image_size);
-    if (!y3::letterbox_geom_fits(g, image_size))
-        return fail(Y3_ERR_INVALID, "y3_preprocess_image: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", height, width,
-                    g.sh, g.sw, g.top, g.left, image_size, image_size);
-    float *dst = batch_dev + (size_t)slot * image_size * image_size * 3;
-    hipError_t e = y3::launch_resize(image_dev, is_uint8, height, width, channels, dst, image_size, g, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_preprocess_image launch: %s", hipGetErrorString(e));
-    return Y3_OK;
+    return preprocess_image_hw("y3_preprocess_image", image_dev, is_uint8, height, width, channels, batch_dev, slot, image_size, image_size, stream);
 }
 Y3_CATCH("y3_preprocess_image")
 
-y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
-                              float *batch_dev, int first_slot, int image_size, void *stream)
-try {
-    if (!pixels_dev || !descs_host || !batch_dev || n_images < 1 || first_slot < 0 || image_size <= 0)
-        return fail(Y3_ERR_INVALID, "y3_preprocess_batch: bad argument (null pointer, n_images < 1, first_slot < 0 or image_size <= 0)");
+static y3_status preprocess_batch_hw(const char *who, const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host,
+                                     int n_images, float *batch_dev, int first_slot, int Hc, int Wc, void *stream)
+{
+    if (!pixels_dev || !descs_host || !batch_dev || n_images < 1 || first_slot < 0 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_images < 1, first_slot < 0 or image_size <= 0)", who);
     // every check before the first launch: a bad image late in the list must not leave the batch half written
     for (int i = 0; i < n_images; ++i) {
         const y3_image_desc &d = descs_host[i];
         if (d.channels < 3 || d.channels > 4)
-            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: channels must be 3 or 4 (got %d)", i, d.channels);
+            return fail(Y3_ERR_INVALID, "%s: image %d: channels must be 3 or 4 (got %d)", who, i, d.channels);
         if (!image_mode_ok(d.mode))
-            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", i, d.mode);
+            return fail(Y3_ERR_INVALID, "%s: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
         if (d.height < 1 || d.width < 1)
-            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: height and width must be at least 1 (got %d x %d)", i,
+            return fail(Y3_ERR_INVALID, "%s: image %d: height and width must be at least 1 (got %d x %d)", who, i,
                         d.height, d.width);
         const bool f32 = (d.mode & ~Y3_IMAGE_LETTERBOX) == 0;
         if (f32 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
-            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: float32 pixels must be 4-byte aligned (offset %llu)", i,
+            return fail(Y3_ERR_INVALID, "%s: image %d: float32 pixels must be 4-byte aligned (offset %llu)", who, i,
                         (unsigned long long)d.offset);
         // height, width < 2^31 and channels * elemsize <= 16: the product stays below 2^66, so take it in 128 bits
         const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (f32 ? 4 : 1));
         if ((unsigned __int128)d.offset + bytes > (unsigned __int128)pixels_bytes)
-            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", i,
+            return fail(Y3_ERR_INVALID, "%s: image %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", who, i,
                         d.height, d.width, d.channels, (unsigned long long)d.offset, pixels_bytes);
-        const y3::LetterboxGeom g = image_geom(d.mode, d.height, d.width, image_size);
-        if (!y3::letterbox_geom_fits(g, image_size))
-            return fail(Y3_ERR_INVALID, "y3_preprocess_batch: image %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", i,
-                        d.height, d.width, g.sh, g.sw, g.top, g.left, image_size, image_size);
+        const y3::LetterboxGeom g = image_geom(d.mode, d.height, d.width, Hc, Wc);
+        if (!y3::letterbox_geom_fits(g, Hc, Wc))
+            return fail(Y3_ERR_INVALID, "%s: image %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, i,
+                        d.height, d.width, g.sh, g.sw, g.top, g.left, Hc, Wc);
     }
-    const size_t per_image = (size_t)image_size * image_size * 3;
+    const size_t per_image = (size_t)Hc * Wc * 3;
     for (int i0 = 0; i0 < n_images; i0 += y3::kPreprocessTableImages) {
         const int n = std::min(y3::kPreprocessTableImages, n_images - i0);
         y3::LetterboxGeom geoms[y3::kPreprocessTableImages];     // on the stack: the call allocates nothing
-        for (int i = 0; i < n; ++i) geoms[i] = image_geom(descs_host[i0 + i].mode, descs_host[i0 + i].height, descs_host[i0 + i].width, image_size);
+        for (int i = 0; i < n; ++i) geoms[i] = image_geom(descs_host[i0 + i].mode, descs_host[i0 + i].height, descs_host[i0 + i].width, Hc, Wc);
         hipError_t e = y3::launch_preprocess_batch(pixels_dev, descs_host + i0, geoms, n, batch_dev + ((size_t)first_slot + i0) * per_image,
-                                                   image_size, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_preprocess_batch launch: %s", hipGetErrorString(e));
+                                                   Hc, Wc, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
     }
     return Y3_OK;
 }
+
+y3_status y3_preprocess_batch_hw(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
+                                 float *batch_dev, int first_slot, int canvas_h, int canvas_w, void *stream)
+try {
+    return preprocess_batch_hw("y3_preprocess_batch_hw", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, canvas_h, canvas_w, stream);
+}
+Y3_CATCH("y3_preprocess_batch_hw")
+
+y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
+                              float *batch_dev, int first_slot, int image_size, void *stream)
+try {
+    return preprocess_batch_hw("y3_preprocess_batch", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, image_size, image_size, stream);
+}
 Y3_CATCH("y3_preprocess_batch")
 
-y3_status y3_letterbox_geometry(const y3_image_desc *descs_host, int n_images, int image_size, int32_t *geoms_out_host)
-try {
-    if (!descs_host || !geoms_out_host || n_images < 1 || image_size <= 0)
-        return fail(Y3_ERR_INVALID, "y3_letterbox_geometry: bad argument (null pointer, n_images < 1 or image_size <= 0)");
+static y3_status letterbox_geometry_hw(const char *who, const y3_image_desc *descs_host, int n_images, int Hc, int Wc, int32_t *geoms_out_host)
+{
+    if (!descs_host || !geoms_out_host || n_images < 1 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_images < 1 or image_size <= 0)", who);
     for (int i = 0; i < n_images; ++i) {
         const y3_image_desc &d = descs_host[i];
         if (!image_mode_ok(d.mode))
-            return fail(Y3_ERR_INVALID, "y3_letterbox_geometry: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", i, d.mode);
+            return fail(Y3_ERR_INVALID, "%s: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
         if (d.height < 1 || d.width < 1)
-            return fail(Y3_ERR_INVALID, "y3_letterbox_geometry: image %d: height and width must be at least 1 (got %d x %d)", i,
+            return fail(Y3_ERR_INVALID, "%s: image %d: height and width must be at least 1 (got %d x %d)", who, i,
                         d.height, d.width);
     }
     static_assert(sizeof(y3::LetterboxGeom) == 4 * sizeof(int32_t), "a geometry is four int32");
     for (int i = 0; i < n_images; ++i) {
-        const y3::LetterboxGeom g = image_geom(descs_host[i].mode, descs_host[i].height, descs_host[i].width, image_size);
+        const y3::LetterboxGeom g = image_geom(descs_host[i].mode, descs_host[i].height, descs_host[i].width, Hc, Wc);
         memcpy(geoms_out_host + (size_t)i * 4, &g, sizeof(g));
     }
     return Y3_OK;
 }
+
+y3_status y3_letterbox_geometry_hw(const y3_image_desc *descs_host, int n_images, int canvas_h, int canvas_w, int32_t *geoms_out_host)
+try {
+    return letterbox_geometry_hw("y3_letterbox_geometry_hw", descs_host, n_images, canvas_h, canvas_w, geoms_out_host);
+}
+Y3_CATCH("y3_letterbox_geometry_hw")
+
+y3_status y3_letterbox_geometry(const y3_image_desc *descs_host, int n_images, int image_size, int32_t *geoms_out_host)
+try {
+    return letterbox_geometry_hw("y3_letterbox_geometry", descs_host, n_images, image_size, image_size, geoms_out_host);
+}
 Y3_CATCH("y3_letterbox_geometry")
 
-y3_status y3_unletterbox_detections(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
-                                    int max_boxes, int image_size, void *stream)
-try {
-    if (!packed_dev || !num_valid_dev || !geoms_host || batch < 1 || image_size <= 0)
-        return fail(Y3_ERR_INVALID, "y3_unletterbox_detections: bad argument (null pointer, batch < 1 or image_size <= 0)");
+static y3_status unletterbox_hw(const char *who, void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                int max_boxes, int Hc, int Wc, void *stream)
+{
+    if (!packed_dev || !num_valid_dev || !geoms_host || batch < 1 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, batch < 1 or image_size <= 0)", who);
     if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES)
-        return fail(Y3_ERR_INVALID, "y3_unletterbox_detections: max_boxes must be in [1,%d]", Y3_MAX_OUTPUT_BOXES);
+        return fail(Y3_ERR_INVALID, "%s: max_boxes must be in [1,%d]", who, Y3_MAX_OUTPUT_BOXES);
     // every check before the first launch: the rows are rewritten in place
     for (int i = 0; i < batch; ++i) {
         y3::LetterboxGeom g;
         memcpy(&g, geoms_host + (size_t)i * 4, sizeof(g));
-        if (!y3::letterbox_geom_fits(g, image_size))
-            return fail(Y3_ERR_INVALID, "y3_unletterbox_detections: image %d: geometry %d x %d at (%d, %d) does not lie inside %d x %d", i,
-                        g.sh, g.sw, g.top, g.left, image_size, image_size);
+        if (!y3::letterbox_geom_fits(g, Hc, Wc))
+            return fail(Y3_ERR_INVALID, "%s: image %d: geometry %d x %d at (%d, %d) does not lie inside %d x %d", who, i,
+                        g.sh, g.sw, g.top, g.left, Hc, Wc);
     }
     unsigned *packed = static_cast<unsigned *>(packed_dev);
     for (int i0 = 0; i0 < batch; i0 += y3::kUnletterboxTableImages) {
         const int n = std::min(y3::kUnletterboxTableImages, batch - i0);
         y3::LetterboxGeom geoms[y3::kUnletterboxTableImages];
         memcpy(geoms, geoms_host + (size_t)i0 * 4, (size_t)n * sizeof(y3::LetterboxGeom));
-        hipError_t e = y3::launch_unletterbox(packed + (size_t)i0 * max_boxes * 7, num_valid_dev + i0, geoms, n, max_boxes, image_size,
+        hipError_t e = y3::launch_unletterbox(packed + (size_t)i0 * max_boxes * 7, num_valid_dev + i0, geoms, n, max_boxes, Hc, Wc,
                                               (hipStream_t)stream);
-        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_unletterbox_detections launch: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
     }
     return Y3_OK;
+}
+
+y3_status y3_unletterbox_detections_hw(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                       int max_boxes, int canvas_h, int canvas_w, void *stream)
+try {
+    return unletterbox_hw("y3_unletterbox_detections_hw", packed_dev, num_valid_dev, geoms_host, batch, max_boxes, canvas_h, canvas_w, stream);
+}
+Y3_CATCH("y3_unletterbox_detections_hw")
+
+y3_status y3_unletterbox_detections(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                    int max_boxes, int image_size, void *stream)
+try {
+    return unletterbox_hw("y3_unletterbox_detections", packed_dev, num_valid_dev, geoms_host, batch, max_boxes, image_size, image_size, stream);
 }
 Y3_CATCH("y3_unletterbox_detections")
 
@@ -1681,7 +1747,8 @@ uint32_t y3_crc32c(const void *data_host, size_t nbytes)
 }
 
 // ------------------------------------------------------------------------------------------ decode
-static y3_status decode_common(const float *const grids[3], const int32_t gs[3], int batch, int nc,
+// gs: grid_hw[3][2] = {gh, gw} per scale (the square entry points hand {g, g})
+static y3_status decode_common(const float *const grids[3], const int32_t (*gs)[2], int batch, int nc,
                                const float *anchors, float *bboxes, float *conf, float *probs, int64_t *cls,
                                float *scores, void *stream, const char *who)
 {
@@ -1689,12 +1756,13 @@ static y3_status decode_common(const float *const grids[3], const int32_t gs[3],
     y3::DecodeArgs a{};
     int off = 0;
     for (int s = 0; s < 3; ++s) {
-        if (!grids[s] || gs[s] <= 0 || ((uintptr_t)grids[s] & 15))
+        if (!grids[s] || gs[s][0] <= 0 || gs[s][1] <= 0 || ((uintptr_t)grids[s] & 15))
             return fail(Y3_ERR_INVALID, "%s: grid %d null, empty or not 16-byte aligned", who, s);
         a.grid[s] = grids[s];
-        a.g[s] = gs[s];
+        a.gh[s] = gs[s][0];
+        a.gw[s] = gs[s][1];
         a.off[s] = off;
-        off += gs[s] * gs[s] * 3;
+        off += gs[s][0] * gs[s][1] * 3;
         for (int k = 0; k < 3; ++k) {
             a.anchors[s][k][0] = anchors[(s * 3 + k) * 2 + 0];
             a.anchors[s][k][1] = anchors[(s * 3 + k) * 2 + 1];
@@ -1709,12 +1777,43 @@ static y3_status decode_common(const float *const grids[3], const int32_t gs[3],
     return Y3_OK;
 }
 
+// The square entry points are the _hw ones with {g, g}; `who` names the entry point the caller used in the messages.
+static y3_status yolo_decode_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+                                const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
+{
+    if (!conf_dev || !probs_dev) return fail(Y3_ERR_INVALID, "%s: null output", who);
+    return decode_common(grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, nullptr, nullptr, stream, who);
+}
+
+static y3_status yolo_decode_scores_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+                                       const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream)
+{
+    if (!class_idx_dev || !scores_dev) return fail(Y3_ERR_INVALID, "%s: null output", who);
+    return decode_common(grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, nullptr, nullptr, class_idx_dev, scores_dev, stream, who);
+}
+
+y3_status y3_yolo_decode_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
+                            const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
+try {
+    return yolo_decode_hw("y3_yolo_decode_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode_hw")
+
+y3_status y3_yolo_decode_scores_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
+                                   const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev,
+                                   float *scores_dev, void *stream)
+try {
+    return yolo_decode_scores_hw("y3_yolo_decode_scores_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode_scores_hw")
+
 y3_status y3_yolo_decode(const float *const grids_dev[3], const int32_t grid_sizes[3], int batch, int nclasses,
                          const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
 try {
     if (!conf_dev || !probs_dev) return fail(Y3_ERR_INVALID, "y3_yolo_decode: null output");
-    return decode_common(grids_dev, grid_sizes, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, nullptr,
-                         nullptr, stream, "y3_yolo_decode");
+    if (!grid_sizes) return fail(Y3_ERR_INVALID, "y3_yolo_decode: bad argument");
+    const int32_t hw[3][2] = {{grid_sizes[0], grid_sizes[0]}, {grid_sizes[1], grid_sizes[1]}, {grid_sizes[2], grid_sizes[2]}};
+    return yolo_decode_hw("y3_yolo_decode", grids_dev, hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
 }
 Y3_CATCH("y3_yolo_decode")
 
@@ -1723,8 +1822,9 @@ y3_status y3_yolo_decode_scores(const float *const grids_dev[3], const int32_t g
                                 float *scores_dev, void *stream)
 try {
     if (!class_idx_dev || !scores_dev) return fail(Y3_ERR_INVALID, "y3_yolo_decode_scores: null output");
-    return decode_common(grids_dev, grid_sizes, batch, nclasses, anchors_host, bboxes_dev, nullptr, nullptr,
-                         class_idx_dev, scores_dev, stream, "y3_yolo_decode_scores");
+    if (!grid_sizes) return fail(Y3_ERR_INVALID, "y3_yolo_decode_scores: bad argument");
+    const int32_t hw[3][2] = {{grid_sizes[0], grid_sizes[0]}, {grid_sizes[1], grid_sizes[1]}, {grid_sizes[2], grid_sizes[2]}};
+    return yolo_decode_scores_hw("y3_yolo_decode_scores", grids_dev, hw, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
 }
 Y3_CATCH("y3_yolo_decode_scores")
 
@@ -1781,7 +1881,7 @@ try {
     if (st != Y3_OK) return st;
     if ((uintptr_t)bboxes_dev & 15) return fail(Y3_ERR_INVALID, "y3_net_forward_decode: bboxes not 16-byte aligned");
     Y3_ENTER_DEVICE(net);
-    int32_t gs[3];
+    int32_t gs[3][2];
     size_t gelems[3], n = 0, off[9];
     detect_layout(net, batch, off, &n, gs, gelems);
     if (!net->det_buf || net->det_bytes < off[8])
@@ -1791,7 +1891,7 @@ try {
     Forward f{images_dev, grids, batch, (hipStream_t)stream, net->lanes};
     if (!heads_can_decode(net)) {   // composed route: grids into the scratch, then the stand-alone decode
         if ((st = run(net, f)) != Y3_OK) return st;
-        return y3_yolo_decode_scores(grids, gs, batch, net->nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+        return yolo_decode_scores_hw("y3_yolo_decode_scores", grids, gs, batch, net->nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
     }
     y3::DecodeHead heads[3];
     int first = 0;
@@ -1799,7 +1899,8 @@ try {
         heads[k].boxes = bboxes_dev;
         heads[k].cls = class_idx_dev;
         heads[k].scores = scores_dev;
-        heads[k].g = gs[k];
+        heads[k].gh = gs[k][0];
+        heads[k].gw = gs[k][1];
         heads[k].off = first;
         heads[k].N = (int)n;
         heads[k].nc = net->nclasses;
@@ -1807,7 +1908,7 @@ try {
             heads[k].anchors[a][0] = anchors_host[(k * 3 + a) * 2 + 0];
             heads[k].anchors[a][1] = anchors_host[(k * 3 + a) * 2 + 1];
         }
-        first += gs[k] * gs[k] * 3;
+        first += gs[k][0] * gs[k][1] * 3;
     }
     f.heads = heads;
     return run(net, f);
@@ -1825,7 +1926,7 @@ try {
     if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES)
         return fail(Y3_ERR_INVALID, "y3_net_detect: max_boxes must be in [1,%d]", Y3_MAX_OUTPUT_BOXES);
     Y3_ENTER_DEVICE(net);   // the decode / NMS / pack launches below go to the net's device; the caller's current device is restored on return
-    int32_t gs[3];
+    int32_t gs[3][2];
     size_t gelems[3], n = 0, off[9];
     detect_layout(net, batch, off, &n, gs, gelems);
     if (!net->det_buf || net->det_bytes < off[8])

@@ -97,23 +97,23 @@ hipError_t launch_to_f32(int dtype, const void *src, float *dst, size_t npix, in
 
 // fused stem (conv_stem.hip): conv0 (3x3/1, 3->32) + conv1 (3x3/2, 32->64), both BN + optional leaky, one launch
 struct StemArgs {
-    const float *img;      // [B,S,S,3] fp32
+    const float *img;      // [B,H,W,3] fp32
     const float *w0;       // conv0 weights [28][32] fp32, row k = (u*3 + v)*3 + c, row 27 = 0 (fp32 kernel: BN scale folded in)
     const float *scale0;   // [32]  (bf16 kernel only: y = acc*scale + shift like the stand-alone bf16 launches)
     const float *shift0;   // [32]
     const void *w1;        // conv1 packed [64][288], k = tap*32 + c: fp32 with the BN scale folded in / bf16 unscaled
     const float *scale1;   // [64]  (bf16 kernel only)
     const float *shift1;   // [64]
-    void *dst;             // [B,S/2,S/2,64] fp32 / bf16
+    void *dst;             // [B,H/2,W/2,64] fp32 / bf16
     // optional third layer: the 1x1 conv reading conv1's output (64 -> 32, BN, leaky), computed from the tile
     // while it is still on chip.  w2 = nullptr: absent.
     const void *w2;        // packed [32][64]: fp32 with the BN scale folded in / bf16 unscaled
     const float *scale2;   // [32]  (bf16 kernel only)
     const float *shift2;   // [32]
-    void *dst2;            // [B,S/2,S/2,32] fp32 / bf16
+    void *dst2;            // [B,H/2,W/2,32] fp32 / bf16
     int leaky2;
     unsigned dst2_bytes;
-    int B, S;              // S % 32 == 0
+    int B, H, W;           // image height and width, each % 32 == 0
     int leaky0, leaky1;
     unsigned img_bytes, dst_bytes;
     int tiles_y, tiles_x, n_tiles;   // filled by the launcher
@@ -151,7 +151,7 @@ hipError_t launch_concat(const float *a, int Ca, const float *b, int Cb, size_t 
 
 struct DecodeArgs {
     const float *grid[3];
-    int g[3];
+    int gh[3], gw[3];   // grid rows and columns of each scale
     int off[3];     // first box index of each scale
     float anchors[3][3][2];
     int B, N, nc;
@@ -162,29 +162,30 @@ hipError_t launch_class_scores(const float *conf, const float *probs, size_t n, 
                                float *scores, hipStream_t s);
 
 // Letterbox geometry (include/y3.h, Y3_IMAGE_LETTERBOX): the aspect-preserving resize is to sh x sw, placed at (top, left) of
-// the S x S canvas.  Layout of the int32[4] rows of y3_letterbox_geometry / y3_unletterbox_detections.
+// the Hc x Wc canvas (square entry points: Hc = Wc = S).  Layout of the int32[4] rows of y3_letterbox_geometry / y3_unletterbox_detections.
 struct LetterboxGeom { int32_t sh, sw, top, left; };
 // The one definition of the geometry: fp32, round half to even (reference core/utils.py:17-28 through tf.image.resize(
 // preserve_aspect_ratio=True)); host only.  The same formula in double gives another (sh, sw) for some sizes.
-LetterboxGeom letterbox_geom(int h, int w, int S);
-inline bool letterbox_geom_fits(const LetterboxGeom &g, int S)
+LetterboxGeom letterbox_geom(int h, int w, int Hc, int Wc);
+inline bool letterbox_geom_fits(const LetterboxGeom &g, int Hc, int Wc)
 {
-    return g.sh >= 1 && g.sw >= 1 && g.top >= 0 && g.left >= 0 && g.top <= S - g.sh && g.left <= S - g.sw;
+    return g.sh >= 1 && g.sw >= 1 && g.top >= 0 && g.left >= 0 && g.top <= Hc - g.sh && g.left <= Wc - g.sw;
 }
 
 // mode: 0, 1, 2 (y3_preprocess_image's is_uint8), optionally | Y3_IMAGE_LETTERBOX with the geometry g
-hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride, float *dst, int S, const LetterboxGeom &g, hipStream_t s);
+hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride, float *dst, int Hc, int Wc, const LetterboxGeom &g,
+                         hipStream_t s);
 // The image descriptors and geometries of one preprocess_batch_kernel launch, passed by value in the kernel arguments (the limit is 4 KB).
 constexpr int kPreprocessTableImages = 64;
 struct PreprocessTable { y3_image_desc d[kPreprocessTableImages]; LetterboxGeom g[kPreprocessTableImages]; };
 static_assert(sizeof(y3_image_desc) == 24 && sizeof(PreprocessTable) + 64 <= 4096, "descriptor table must fit the kernel arguments");
-hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int S,
-                                   hipStream_t s);
+hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
+                                   int Wc, hipStream_t s);
 
 // The geometries of one unletterbox_kernel launch, by value in the kernel arguments like PreprocessTable.
 constexpr int kUnletterboxTableImages = 64;
 struct UnletterboxTable { LetterboxGeom g[kUnletterboxTableImages]; };
-hipError_t launch_unletterbox(void *packed, const int32_t *nv, const LetterboxGeom *geoms, int n, int M, int S, hipStream_t s);
+hipError_t launch_unletterbox(void *packed, const int32_t *nv, const LetterboxGeom *geoms, int n, int M, int Hc, int Wc, hipStream_t s);
 
 // Evaluation counters (evaluate.hip; include/y3.h, y3_evaluate_detections).  The score thresholds of one launch travel by value in the
 // kernel arguments, like the letterbox geometries.

@@ -92,6 +92,9 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     """One model and one pass: the un-stacked data set is batched here (images with unlike numbers of boxes may share a batch)
     by a generator that Net.evaluate_stream draws from, so records are decoded while earlier batches run and the data set is
     never held in memory; only the counters come back."""
+    if not isinstance(detect_config["image_size"], int):
+        raise ValueError("evaluate_yolov3: image_size must be an int; the records are resized to a square on the host "
+                         "(an [H, W] canvas is served by Net.evaluate_stream and by inference.py)")
     S, batch_size = int(detect_config["image_size"]), int(detect_config["batch_size"])
     model = create_model(detect_config["model_config_file"], nclasses, anchors_table, min(thresholds),
                          detect_config["nms_iou_threshold"], detect_config["yolo_max_boxes"],

@@ -15,6 +15,7 @@ No arithmetic happens here; this is host logic only and runs without a GPU.
 from __future__ import annotations
 
 import ast
+import numbers
 import operator
 import os
 from dataclasses import dataclass, field
@@ -118,16 +119,24 @@ class Program:
     def conv_ops(self) -> List[ConvOp]:
         return [o for o in self.ops if isinstance(o, ConvOp)]
 
-    def flops_per_image(self, image_size: int, backbone_only: bool = False) -> float:
-        """2*MAC over the convolutions (SURVEY.md 8d algorithmic work)."""
+    def grid_sizes(self, image_size):
+        """Per head (coarsest first): g = S // div for an int S; (gh, gw) = (H // div, W // div) for an (H, W) pair."""
+        divs = [self.tensors[o].div for o in self.outputs]
+        if isinstance(image_size, numbers.Integral):
+            return [int(image_size) // d for d in divs]
+        h, w = (int(v) for v in image_size)
+        return [(h // d, w // d) for d in divs]
+
+    def flops_per_image(self, image_size, backbone_only: bool = False) -> float:
+        """2*MAC over the convolutions (SURVEY.md 8d algorithmic work); image_size: an int S or an (H, W) pair."""
+        h, w = (image_size, image_size) if isinstance(image_size, numbers.Integral) else image_size
         tot = 0.0
         for n in self.conv_nodes:
             if backbone_only and n.sub_model != "backbone":
                 continue
             t_in = self.tensors[n.inputs[0]]
             t_out = self.tensors[n.output]
-            ho = image_size // t_out.div
-            tot += 2.0 * n.size * n.size * t_in.channels * n.filters * ho * ho
+            tot += 2.0 * n.size * n.size * t_in.channels * n.filters * (h // t_out.div) * (w // t_out.div)
         return tot
 
     def n_params(self) -> int:

@@ -84,6 +84,20 @@ class Inference:
             detections.append((label, xmin, ymin, xmax, ymax))
         return pil, detections
 
+    @staticmethod
+    def canvas_and_anchors(image_size, anchors_table):
+        """image_size of the config -- an int S, or [H, W] for a rectangular network input (both multiples of 32) -- and the
+        anchors of the anchors file -> ((H, W), the anchors for that canvas).  Convention: the anchors file is normalised by
+        the square side the model was trained at, and for an [H, W] canvas that side is taken to be max(H, W), the long side
+        (what runtime.rect_canvas keeps at image_size): the anchors are rescaled per axis (runtime.rect_anchors), the long
+        axis is left as the file has it.  An int, or H == W, leaves the anchors untouched."""
+        from . import runtime
+        canvas_h, canvas_w = runtime.canvas_hw(image_size)
+        anchors_table = np.asarray(anchors_table, np.float32)
+        if canvas_h != canvas_w:
+            anchors_table = runtime.rect_anchors(anchors_table, max(canvas_h, canvas_w), (canvas_h, canvas_w))
+        return (canvas_h, canvas_w), anchors_table
+
     def build(self, model_config_file, classes_name_file, anchors_file, input_weights_path, yolo_max_boxes,
               nms_iou_threshold, nms_score_threshold, weights=None):
         anchors_table = get_anchors(anchors_file).astype(np.float32)      # reference: inference.py:83
@@ -122,6 +136,7 @@ class Inference:
         results = []
         import torch
         from . import runtime
+        (canvas_h, canvas_w), model.anchors_table = self.canvas_and_anchors(image_size, model.anchors_table)
         if input_data_source == "tfrecords":
             # reference: inference.py:119-144.  Records are parsed on the host (core/load_tfrecords.py); the
             # resize(0..255 values) / 255 of parse_tfrecord_fn runs on the GPU straight into the batch tensor.  The
@@ -132,7 +147,7 @@ class Inference:
 
             def run_batch(images_u8):
                 nonlocal image_index
-                batch_dev = torch.empty((len(images_u8), image_size, image_size, 3), dtype=torch.float32,
+                batch_dev = torch.empty((len(images_u8), canvas_h, canvas_w, 3), dtype=torch.float32,
                                         device="cuda")
                 # one copy and one launch for the batch (mode 2: resize the 0..255 values, then / 255)
                 blob, descs = runtime.pack_images(images_u8, 2)
@@ -165,7 +180,7 @@ class Inference:
             # decode on the host, then uint8 -> [0,1] -> bilinear resize on the GPU straight into the batch tensor
             # (reference: inference.py:157-158 decode_image + tf.image.resize)
             orig_image = load_image_u8(file)
-            batch_dev = torch.empty((1, image_size, image_size, 3), dtype=torch.float32, device="cuda")
+            batch_dev = torch.empty((1, canvas_h, canvas_w, 3), dtype=torch.float32, device="cuda")
             runtime.preprocess_image(torch.from_numpy(orig_image).cuda(), batch_dev, 0)
             b_boxes, b_cls, b_scores, b_sel, b_nv = (t.cpu().numpy() for t in model(batch_dev))
             batch = batch_dev.cpu().numpy()

@@ -35,14 +35,68 @@ def _need_cuda(*ts):
             raise Y3Error("expected contiguous CUDA(HIP) tensors; the y3 kernels have no CPU fallback")
 
 
-def tuning_table_path(tag: str, batch: int, image_size: int) -> str:
+def canvas_hw(image_size):
+    """An image size as the (H, W) of the network canvas: an int S is the square (S, S), a pair is taken as (H, W)."""
+    if isinstance(image_size, (int, np.integer)):
+        return int(image_size), int(image_size)
+    hw = tuple(int(v) for v in image_size)
+    if len(hw) != 2:
+        raise Y3Error(f"image_size must be an int or an (H, W) pair (got {image_size!r})")
+    return hw
+
+
+def _f32_geometry(h: int, w: int, Hc: int, Wc: int):
+    """(sh, sw) of the letterbox geometry in the library's own fp32 arithmetic (include/y3.h, Y3_IMAGE_LETTERBOX;
+    core/utils.letterbox_geometry is the same restatement with the offsets)."""
+    scale = min(np.float32(Hc) / np.float32(h), np.float32(Wc) / np.float32(w))
+    return max(1, int(np.rint(scale * np.float32(h)))), max(1, int(np.rint(scale * np.float32(w))))
+
+
+def rect_canvas(height: int, width: int, image_size: int, stride: int = 32):
+    """The smallest (H, W) canvas, both sides multiples of `stride`, that holds the aspect-preserving resize of a
+    height x width frame whose long side becomes image_size -- the plan to letterbox such frames onto instead of the
+    image_size^2 square, whose zero bars the conv stack would convolve.  (480, 640, 416) -> (320, 416).
+    The resized extent is computed with the library's fp32 geometry; the canvas found is then checked with the same
+    geometry (the frame letterboxed onto it must fit) and a side grows by one stride where rounding says otherwise."""
+    h, w, S, st = int(height), int(width), int(image_size), int(stride)
+    if h < 1 or w < 1 or S < 1 or st < 1:
+        raise Y3Error("rect_canvas: height, width, image_size and stride must be at least 1")
+    sh, sw = _f32_geometry(h, w, S, S)
+    up = lambda v: -(-v // st) * st
+    H, W = up(sh), up(sw)
+    while True:
+        gh, gw = _f32_geometry(h, w, H, W)
+        if gh <= H and gw <= W:
+            return H, W
+        H, W = (H + st, W) if gh > H else (H, W + st)
+
+
+def rect_anchors(anchors_table, image_size: int, canvas):
+    """Anchors normalised by the square image_size (datasets/*/anchors.txt through core.utils.get_anchors) -> normalised
+    by an (H, W) canvas: aw * S / W, ah * S / H, in fp32.  The anchor keeps its size in pixels.  An axis whose side equals
+    image_size -- the long side of every rect_canvas -- is copied, not computed: x * S / S is not x in fp32."""
+    H, W = canvas_hw(canvas)
+    a = np.asarray(anchors_table, np.float32)
+    out = a.copy()
+    if W != int(image_size):
+        out[..., 0] = a[..., 0] * np.float32(image_size) / np.float32(W)
+    if H != int(image_size):
+        out[..., 1] = a[..., 1] * np.float32(image_size) / np.float32(H)
+    return out
+
+
+def tuning_table_path(tag: str, batch: int, image_size) -> str:
     """The tile table of a plan: tuning/<mode>_b<batch>_s<size>.json of the package (may not exist: heuristic tiles).
     Y3_TUNING_FILE (tools: A/B of tables) replaces it only for the plan it was made for: the file names its mode
     ("dtype": "f32" | "bf16" | "f32x3" | "f32x2") and its batch / image_size; a plan of another mode or geometry in the
-    same process (bench.py's alt measurements re-plan the net) keeps its own packaged table."""
+    same process (bench.py's alt measurements re-plan the net) keeps its own packaged table.
+    A non-square (H, W) plan takes the table of (mode, batch, max(H, W)), every row of it (Net.conv_signature is formed at
+    max(H, W) as well): tile validity depends on channel counts only; whether those tiles are the fastest for the smaller M is
+    unmeasured."""
     import json
     import os
     from . import PACKAGE_DIR
+    image_size = max(canvas_hw(image_size))
     path = os.path.join(PACKAGE_DIR, "tuning", f"{tag}_b{batch}_s{image_size}.json")
     override = os.environ.get("Y3_TUNING_FILE")
     if override and os.path.exists(override):
@@ -84,6 +138,7 @@ class Net:
         check(self.lib.y3_net_create(tens, len(p.tensors), k_arr, len(kinds), c_arr, len(convs), a_arr, len(auxs),
                                      p.input_tensor, outs, p.nclasses, C.byref(self._h)), "y3_net_create")
         self.image_size = 0
+        self.canvas = (0, 0)     # the planned (H, W); image_size is the int S for a plan made with an int
         self.max_batch = 0
         self.dtype = _lib.Y3_DTYPE_F32
         self.weights_loaded = False
@@ -160,19 +215,23 @@ class Net:
     def set_tile_bf16(self, slot: int, tile: int):
         self._force("_bf16", self.lib.y3_net_set_tile_bf16, slot, tile)
 
-    def plan(self, max_batch: int, image_size: int, dtype: Optional[int] = None):
-        """dtype: _lib.Y3_DTYPE_F32 (default, fp32 MFMA), _lib.Y3_DTYPE_F32X3 (fp32-accurate on the bf16 matrix cores:
+    def plan(self, max_batch: int, image_size, dtype: Optional[int] = None):
+        """image_size: an int S (the S x S canvas) or an (H, W) pair, both sides multiples of 32 (y3_net_plan_hw).
+        dtype: _lib.Y3_DTYPE_F32 (default, fp32 MFMA), _lib.Y3_DTYPE_F32X3 (fp32-accurate on the bf16 matrix cores:
         three bf16 planes per value), _lib.Y3_DTYPE_F32X2 (two fp16 planes per value, 2^-22 representation, |x| < 65504)
         or _lib.Y3_DTYPE_BF16 (bf16 activations/weights, fp32 accumulate)."""
         if dtype is None:
             dtype = self.dtype
-        check(self.lib.y3_net_plan(self._h, max_batch, image_size, dtype), "y3_net_plan")
-        self.max_batch, self.image_size, self.dtype = max_batch, image_size, dtype
+        H, W = canvas_hw(image_size)
+        check(self.lib.y3_net_plan_hw(self._h, max_batch, H, W, dtype), "y3_net_plan")
+        self.max_batch, self.dtype, self.canvas = max_batch, dtype, (H, W)
+        # the form grid_sizes() answers in -- g for an int plan, (gh, gw) for a pair plan -- is that of the last plan() a caller made
+        self.image_size = int(image_size) if isinstance(image_size, (int, np.integer)) else (H, W)
         self._apply_tuning()
 
     @staticmethod
-    def conv_signature(o: ConvOp, image_size: int) -> str:
-        ho = image_size // o.out_div
+    def conv_signature(o: ConvOp, image_size) -> str:
+        ho = max(canvas_hw(image_size)) // o.out_div
         return f"k{o.size}s{o.stride}_c{o.cin}_n{o.cout}_h{ho}_r{int(o.residual >= 0)}_u{int(o.src1 >= 0)}"
 
     def _apply_tuning(self):
@@ -199,11 +258,25 @@ class Net:
             check(fn(self._h, slot, int(table.get(self.conv_signature(o, self.image_size), -1))), f"y3_net_set_tile{kind}")
 
     def grid_sizes(self, image_size=None):
-        s = image_size or self.image_size
-        return [s // self.program.tensors[o].div for o in self.program.outputs]
+        """Per head: g for an int image size, (gh, gw) for an (H, W) pair (default: what the net was planned with)."""
+        return self.program.grid_sizes(image_size or self.image_size)
+
+    def _grid_hw(self):
+        return [(self.canvas[0] // self.program.tensors[o].div, self.canvas[1] // self.program.tensors[o].div)
+                for o in self.program.outputs]
+
+    def _plan_for(self, images: torch.Tensor):
+        """Re-plan when the batch's [B,H,W,..] does not match the plan.  The plan keeps the form the caller last gave it: a net
+        planned with a pair stays a pair plan (grid_sizes() keeps returning pairs) also for an H == W batch; a net planned with
+        an int, or never planned, takes a square batch as an int plan."""
+        B, H, W = images.shape[0], images.shape[1], images.shape[2]
+        if (H, W) != self.canvas or B > self.max_batch:
+            pair = H != W or isinstance(self.image_size, tuple)
+            self.plan(max(B, self.max_batch), (H, W) if pair else H)
+        return B
 
     def forward(self, images: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
-        """images [B,S,S,3] fp32 on the GPU -> [grid13, grid26, grid52], each [B,g,g,3,5+nc]."""
+        """images [B,H,W,3] fp32 on the GPU -> [grid13, grid26, grid52], each [B,gh,gw,3,5+nc]."""
         _need_cuda(images)
         cin = self.program.tensors[self.program.input_tensor].channels
         # bf16 plan + an input that feeds an MFMA conv directly (layer tests): the input is bf16 as well
@@ -216,19 +289,17 @@ class Net:
                 raise Y3Error(f"images must be float16 [B,S,S,2,{cin}] (split2_planes) in the two-plane mode")
         else:
             want = torch.bfloat16 if (self.dtype == _lib.Y3_DTYPE_BF16 and cin != 3) else torch.float32
-            if images.dtype != want or images.dim() != 4 or images.shape[3] != cin or images.shape[1] != images.shape[2]:
+            if images.dtype != want or images.dim() != 4 or images.shape[3] != cin:
                 raise Y3Error(f"images must be {want} [B,S,S,{cin}]")
-        B, S = images.shape[0], images.shape[1]
-        if S != self.image_size or B > self.max_batch:
-            self.plan(max(B, self.max_batch), S)
+        B = self._plan_for(images)
         nc = self.program.nclasses
-        gs = self.grid_sizes()
+        gs = self._grid_hw()
         if out is None:
             if nc > 0:
-                out = [torch.empty((B, g, g, 3, 5 + nc), dtype=torch.float32, device=images.device) for g in gs]
+                out = [torch.empty((B, gh, gw, 3, 5 + nc), dtype=torch.float32, device=images.device) for gh, gw in gs]
             else:  # raw feature outputs (layer tests)
-                out = [torch.empty((B, g, g, self.program.tensors[o].channels), dtype=torch.float32,
-                                   device=images.device) for g, o in zip(gs, self.program.outputs)]
+                out = [torch.empty((B, gh, gw, self.program.tensors[o].channels), dtype=torch.float32,
+                                   device=images.device) for (gh, gw), o in zip(gs, self.program.outputs)]
         _need_cuda(*out)
         ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in out])
         check(self.lib.y3_net_forward(self._h, _dev(images), B, ptrs, _lib.stream_ptr()), "y3_net_forward")
@@ -269,8 +340,7 @@ class Net:
         n = C.c_size_t()
         check(self.lib.y3_net_read_tensor(self._h, tensor_id, batch, None, C.byref(n), None), "y3_net_read_tensor")
         t = self.program.tensors[tensor_id]
-        s = self.image_size // t.div
-        out = torch.empty((batch, s, s, t.channels), dtype=torch.float32, device="cuda")
+        out = torch.empty((batch, self.canvas[0] // t.div, self.canvas[1] // t.div, t.channels), dtype=torch.float32, device="cuda")
         assert out.numel() == n.value
         check(self.lib.y3_net_read_tensor(self._h, tensor_id, batch, _dev(out), C.byref(n), _lib.stream_ptr()),
               "y3_net_read_tensor")
@@ -282,12 +352,10 @@ class Net:
         forward() + yolo_decode_scores()."""
         _need_cuda(images)
         if images.dtype != torch.float32 or images.dim() != 4 or images.shape[3] != 3:
-            raise Y3Error("images must be float32 [B,S,S,3]")
-        B, S = images.shape[0], images.shape[1]
-        if S != self.image_size or B > self.max_batch:
-            self.plan(max(B, self.max_batch), S)
+            raise Y3Error("images must be float32 [B,H,W,3]")
+        B = self._plan_for(images)
         a = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 3, 2))
-        n = sum(3 * g * g for g in self.grid_sizes())
+        n = sum(3 * gh * gw for gh, gw in self._grid_hw())
         bboxes = torch.empty((B, n, 4), dtype=torch.float32, device=images.device)
         cls = torch.empty((B, n), dtype=torch.int64, device=images.device)
         scores = torch.empty((B, n), dtype=torch.float32, device=images.device)
@@ -300,10 +368,8 @@ class Net:
         `unpack_detections` splits the rows."""
         _need_cuda(images)
         if images.dtype != torch.float32 or images.dim() != 4 or images.shape[3] != 3:
-            raise Y3Error("images must be float32 [B,S,S,3]")
-        B, S = images.shape[0], images.shape[1]
-        if S != self.image_size or B > self.max_batch:
-            self.plan(max(B, self.max_batch), S)
+            raise Y3Error("images must be float32 [B,H,W,3]")
+        B = self._plan_for(images)
         a = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 3, 2))
         packed = torch.empty((B, int(max_boxes), 7), dtype=torch.int32, device=images.device)
         nv = torch.empty((B,), dtype=torch.int32, device=images.device)
@@ -322,7 +388,8 @@ class Net:
         letterbox=True: the frames keep their aspect ratio (zero padding around them, core/utils.resize_image) and the
         boxes of the yielded rows are normalised to the frame that was handed in, not to the padded network input:
         y3_unletterbox_detections runs behind y3_net_detect on the same stream, before the read-back.
-        The net keeps its planned image size and is re-planned at most once, for max_batch images; the stage's blobs hold
+        The net keeps its planned image size -- an (H, W) plan letterboxes (or stretches) onto that canvas, and the yielded
+        boxes are in source-frame coordinates all the same; the anchors are then the caller's rect_anchors -- and is re-planned at most once, for max_batch images; the stage's blobs hold
         max_blob_bytes.  Both default to the largest list of `batches`, which must then be a list or tuple."""
         M = int(max_boxes)
         outs = {}       # ring slot -> pinned rows, pinned counts, event: made on the slot's first use
@@ -368,7 +435,8 @@ class Net:
             if max_blob_bytes is None:
                 max_blob_bytes = max((packed_nbytes(b) for b in batches), default=0)
         S = self.image_size
-        if S <= 0:
+        Hc, Wc = self.canvas
+        if Hc <= 0:
             raise Y3Error(f"{who}: plan() the net first (the image size is the plan's)")
         if depth < 2:
             raise Y3Error(f"{who}: depth must be at least 2 (batch i+1 is staged while batch i is detected)")
@@ -383,12 +451,12 @@ class Net:
                  torch.empty((max_batch,), dtype=torch.int32, device=dev)) for _ in range(stage.depth)]
         grid_bufs = None
         if keep_grids:
-            nc, gs = self.program.nclasses, self.grid_sizes()
+            nc, gs = self.program.nclasses, self._grid_hw()
             if nc <= 0:
                 raise Y3Error(f"{who}: the program has no detection heads")
-            N = sum(3 * g * g for g in gs)
-            grid_bufs = [torch.empty((max_batch, g, g, 3, 5 + nc), dtype=torch.float32, device=dev) for g in gs]
-            grid_ptrs, grid_sizes = (C.c_void_p * 3)(*[t.data_ptr() for t in grid_bufs]), (C.c_int32 * 3)(*gs)
+            N = sum(3 * gh * gw for gh, gw in gs)
+            grid_bufs = [torch.empty((max_batch, gh, gw, 3, 5 + nc), dtype=torch.float32, device=dev) for gh, gw in gs]
+            grid_ptrs, grid_hw = (C.c_void_p * 3)(*[t.data_ptr() for t in grid_bufs]), (C.c_int32 * 6)(*[v for g in gs for v in g])
             bboxes = torch.empty((max_batch, N, 4), dtype=torch.float32, device=dev)
             cls = torch.empty((max_batch, N), dtype=torch.int64, device=dev)
             scores = torch.empty((max_batch, N), dtype=torch.float32, device=dev)
@@ -409,7 +477,7 @@ class Net:
             sp = C.c_void_p(cur.cuda_stream)
             if keep_grids:      # the first n images of every buffer are a contiguous prefix
                 check(self.lib.y3_net_forward(self._h, _dev(handle.batch), n, grid_ptrs, sp), "y3_net_forward")
-                check(self.lib.y3_yolo_decode_scores(grid_ptrs, grid_sizes, n, nc, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores), sp),
+                check(self.lib.y3_yolo_decode_scores_hw(grid_ptrs, grid_hw, n, nc, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores), sp),
                       "y3_yolo_decode_scores")
                 check(self.lib.y3_nms_padded(_dev(bboxes), _dev(scores), n, N, M, float(iou_threshold), float(score_threshold),
                                              _dev(sel), _dev(nv_dev), _dev(ws), ws_bytes, sp), "y3_nms_padded")
@@ -421,8 +489,8 @@ class Net:
             stage.release(handle)
             if letterbox:
                 g = handle.geometry
-                check(self.lib.y3_unletterbox_detections(_dev(packed_dev), _dev(nv_dev), g.ctypes.data_as(C.POINTER(C.c_int32)), n, M, S,
-                                                         C.c_void_p(cur.cuda_stream)), "y3_unletterbox_detections")
+                check(self.lib.y3_unletterbox_detections_hw(_dev(packed_dev), _dev(nv_dev), g.ctypes.data_as(C.POINTER(C.c_int32)), n, M, Hc, Wc,
+                                                            C.c_void_p(cur.cuda_stream)), "y3_unletterbox_detections")
             yield i, handle, packed_dev, nv_dev, cur, stage, ([t[:n] for t in grid_bufs] if keep_grids else None)
             handle, i = following, i + 1
 
@@ -455,10 +523,14 @@ class Net:
         grids are written and read back, which y3_net_detect avoids), y3_yolo_assign_targets and y3_yolo_loss run on the same
         grids with the ground truth already on the device, and the sums come back with the counters in the one final copy.
         nclasses must be the program's.  Not together with letterbox=True: the reference trains on letterboxed images with
-        unmapped boxes, and mapping the ground truth onto the canvas is a decision this method does not take."""
+        unmapped boxes, and mapping the ground truth onto the canvas is a decision this method does not take.  Not on a
+        non-square (H, W) plan either: y3_yolo_assign_targets / y3_yolo_loss take one g per scale."""
         thresholds = [float(t) for t in score_thresholds]
         if loss and letterbox:
             raise Y3Error("evaluate_stream: loss=True cannot be combined with letterbox=True (the ground truth is not mapped onto the canvas)")
+        if loss and self.canvas[0] != self.canvas[1]:
+            raise ValueError(f"evaluate_stream: loss=True needs a square plan (the net is planned for {self.canvas[0]} x {self.canvas[1]}; "
+                          "the loss kernels take one grid size per scale)")
         if loss and int(nclasses) != self.program.nclasses:
             raise Y3Error(f"evaluate_stream: loss=True needs nclasses = {self.program.nclasses}, the program's (got {int(nclasses)})")
         both = isinstance(one_class, str)
@@ -498,7 +570,7 @@ class Net:
                     loss_sum, loss_images = result[n_counters:n_counters + 12].view(torch.float64).view(3, 4), result[n_counters + 12:]
                     cells_d = torch.empty((stage.max_batch, G), dtype=torch.int32, device=stage.device)
                     loss_d = torch.empty((stage.max_batch, 3, 4), dtype=torch.float64, device=stage.device)
-                    gs = self.grid_sizes()
+                    gs = [g for g, _ in self._grid_hw()]
             if k not in slots:
                 words = stage.max_batch * (G * 5 + 1)
                 slots[k] = (torch.empty(words, dtype=torch.int32, pin_memory=True),
@@ -548,15 +620,18 @@ class Net:
 
 
 # ------------------------------------------------------------------------------------------------
-def _grids_args(grids):
+def _grids_args(grids, square=True):
     _need_cuda(*grids)
     if len(grids) != 3:
         raise Y3Error("expected three grids")
     for g in grids:
-        if g.dtype != torch.float32 or g.dim() != 5 or g.shape[1] != g.shape[2] or g.shape[3] != 3:
-            raise Y3Error("each grid must be float32 [B,g,g,3,5+nc]")
+        if g.dtype != torch.float32 or g.dim() != 5 or g.shape[3] != 3 or (square and g.shape[1] != g.shape[2]):
+            raise Y3Error("each grid must be float32 [B,g,g,3,5+nc]" if square else "each grid must be float32 [B,gh,gw,3,5+nc]")
     ptrs = (C.c_void_p * 3)(*[g.data_ptr() for g in grids])
-    gs = (C.c_int32 * 3)(*[g.shape[1] for g in grids])
+    if square:
+        gs = (C.c_int32 * 3)(*[g.shape[1] for g in grids])
+    else:       # grid_hw[3][2] = {gh, gw}
+        gs = (C.c_int32 * 6)(*[v for g in grids for v in (g.shape[1], g.shape[2])])
     B = grids[0].shape[0]
     N = sum(3 * g.shape[1] * g.shape[2] for g in grids)
     return ptrs, gs, B, N
@@ -571,27 +646,28 @@ def _anchors(anchors_table):
 
 
 def yolo_decode(grids, anchors_table, nclasses):
-    """-> (bboxes [B,N,4], confidence [B,N,1], class_probs [B,N,nc])"""
-    ptrs, gs, B, N = _grids_args(grids)
+    """-> (bboxes [B,N,4], confidence [B,N,1], class_probs [B,N,nc]).  Grids [B,gh,gw,3,5+nc]: each centre is normalised by
+    its own axis (include/y3.h, y3_yolo_decode_hw), which for gh == gw is the reference's arithmetic bit for bit."""
+    ptrs, gs, B, N = _grids_args(grids, square=False)
     a = _anchors(anchors_table)
     dev = grids[0].device
     bboxes = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
     conf = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
     probs = torch.empty((B, N, nclasses), dtype=torch.float32, device=dev)
-    check(_lib.load().y3_yolo_decode(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(conf), _dev(probs),
+    check(_lib.load().y3_yolo_decode_hw(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(conf), _dev(probs),
                                      _lib.stream_ptr()), "y3_yolo_decode")
     return bboxes, conf, probs
 
 
 def yolo_decode_scores(grids, anchors_table, nclasses):
     """fused decode + class arg-max/score -> (bboxes [B,N,4], class_indices [B,N] i64, scores [B,N])"""
-    ptrs, gs, B, N = _grids_args(grids)
+    ptrs, gs, B, N = _grids_args(grids, square=False)
     a = _anchors(anchors_table)
     dev = grids[0].device
     bboxes = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
     cls = torch.empty((B, N), dtype=torch.int64, device=dev)
     scores = torch.empty((B, N), dtype=torch.float32, device=dev)
-    check(_lib.load().y3_yolo_decode_scores(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores),
+    check(_lib.load().y3_yolo_decode_scores_hw(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores),
                                             _lib.stream_ptr()), "y3_yolo_decode_scores")
     return bboxes, cls, scores
 
@@ -624,24 +700,24 @@ def split2_planes(x: torch.Tensor) -> torch.Tensor:
 
 
 def preprocess_image(image: torch.Tensor, batch: torch.Tensor, slot: int, divide_after: bool = False, letterbox: bool = False):
-    """image [H,W,3|4] uint8 or float32 on the GPU -> batch[slot] ([S,S,3] fp32, values in [0,1] for uint8 input):
+    """image [H,W,3|4] uint8 or float32 on the GPU -> batch[slot] ([Hc,Wc,3] fp32, the canvas the batch's shape names; values in [0,1] for uint8 input):
     decode_image's uint8->float conversion fused with tf.image.resize's bilinear resampling.  divide_after=True is
     the tfrecords source's order (reference: core/load_tfrecords.py:46-48): resize the 0..255 values, then / 255.
     letterbox=True keeps the aspect ratio and pads with zeros (reference: core/utils.py:17-28, resize_image); the whole
     slot is written."""
     _need_cuda(image, batch)
     if image.dim() != 3 or image.dtype not in (torch.uint8, torch.float32) or batch.dtype != torch.float32:
-        raise Y3Error("image must be [H,W,C] uint8/float32 and batch float32 [B,S,S,3]")
-    if batch.dim() != 4 or batch.shape[1] != batch.shape[2] or batch.shape[3] != 3 or not (0 <= slot < batch.shape[0]):
-        raise Y3Error("batch must be [B,S,S,3] and slot inside it")
+        raise Y3Error("image must be [H,W,C] uint8/float32 and batch float32 [B,Hc,Wc,3]")
+    if batch.dim() != 4 or batch.shape[3] != 3 or not (0 <= slot < batch.shape[0]):
+        raise Y3Error("batch must be [B,Hc,Wc,3] and slot inside it")
     H, W, C_ = image.shape
     mode = (2 if divide_after else 1) if image.dtype == torch.uint8 else 0
     if divide_after and mode == 0:
         raise Y3Error("divide_after applies to uint8 images")
     if letterbox:
         mode |= _lib.Y3_IMAGE_LETTERBOX
-    check(_lib.load().y3_preprocess_image(_dev(image), mode, H, W, C_, _dev(batch), slot,
-                                          batch.shape[1], _lib.stream_ptr()), "y3_preprocess_image")
+    check(_lib.load().y3_preprocess_image_hw(_dev(image), mode, H, W, C_, _dev(batch), slot,
+                                             batch.shape[1], batch.shape[2], _lib.stream_ptr()), "y3_preprocess_image")
     return batch
 
 
@@ -716,24 +792,25 @@ def pack_images(images, mode, out: Optional[np.ndarray] = None, letterbox=False)
     return out[:total], descs
 
 
-def letterbox_geometries(descs: np.ndarray, image_size: int) -> np.ndarray:
+def letterbox_geometries(descs: np.ndarray, image_size) -> np.ndarray:
     """The descriptor array of pack_images -> int32 [n,4] (sh, sw, top, left): where each image lies on the
-    image_size^2 canvas, (S, S, 0, 0) for an image without the letterbox flag.  One host call for the whole batch
+    canvas (image_size: an int S or an (H, W) pair), the whole canvas (H, W, 0, 0) for an image without the letterbox flag.  One host call for the whole batch
     (y3_letterbox_geometry; no GPU needed); the rows unletterbox_detections takes."""
     if not isinstance(descs, np.ndarray) or descs.dtype != IMAGE_DESC_DTYPE or descs.ndim != 1:
         raise Y3Error("descs must be the descriptor array of pack_images")
     d = np.ascontiguousarray(descs)
     geoms = np.empty((len(d), 4), np.int32)
-    check(_lib.load().y3_letterbox_geometry(d.ctypes.data_as(C.POINTER(_lib.ImageDesc)), len(d), int(image_size),
-                                            geoms.ctypes.data_as(C.POINTER(C.c_int32))), "y3_letterbox_geometry")
+    Hc, Wc = canvas_hw(image_size)
+    check(_lib.load().y3_letterbox_geometry_hw(d.ctypes.data_as(C.POINTER(_lib.ImageDesc)), len(d), Hc, Wc,
+                                               geoms.ctypes.data_as(C.POINTER(C.c_int32))), "y3_letterbox_geometry")
     return geoms
 
 
-def unletterbox_detections(packed: torch.Tensor, num_valid: torch.Tensor, geoms, image_size: int):
+def unletterbox_detections(packed: torch.Tensor, num_valid: torch.Tensor, geoms, image_size):
     """packed [B,M,7] int32 words and num_valid [B] int32 on the GPU (Net.detect / pack_detections), geoms int32 [B,4]
     on the host (letterbox_geometries): the boxes of the valid rows are rewritten in place from the padded canvas to
     the coordinates of the source frames (y3_unletterbox_detections; host restatement: core/utils.unletterbox_boxes).
-    Nothing else is touched.  Enqueues on the current stream only."""
+    Nothing else is touched.  image_size: the canvas, an int S or an (H, W) pair.  Enqueues on the current stream only."""
     _need_cuda(packed, num_valid)
     if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != 7 or not packed.is_contiguous():
         raise Y3Error("packed must be contiguous int32 [B,M,7]")
@@ -742,8 +819,9 @@ def unletterbox_detections(packed: torch.Tensor, num_valid: torch.Tensor, geoms,
     g = np.ascontiguousarray(geoms, dtype=np.int32)
     if g.shape != (packed.shape[0], 4):
         raise Y3Error(f"geoms must be int32 [{packed.shape[0]},4]")
-    check(_lib.load().y3_unletterbox_detections(_dev(packed), _dev(num_valid), g.ctypes.data_as(C.POINTER(C.c_int32)),
-                                                packed.shape[0], packed.shape[1], int(image_size), _lib.stream_ptr()),
+    Hc, Wc = canvas_hw(image_size)
+    check(_lib.load().y3_unletterbox_detections_hw(_dev(packed), _dev(num_valid), g.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   packed.shape[0], packed.shape[1], Hc, Wc, _lib.stream_ptr()),
           "y3_unletterbox_detections")
     return packed
 
@@ -889,13 +967,13 @@ def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Ten
         raise Y3Error("blob_dev must be a 1-D uint8 tensor")
     if not isinstance(descs, np.ndarray) or descs.dtype != IMAGE_DESC_DTYPE or descs.ndim != 1:
         raise Y3Error("descs must be the descriptor array of pack_images")
-    if batch.dtype != torch.float32 or batch.dim() != 4 or batch.shape[1] != batch.shape[2] or batch.shape[3] != 3:
-        raise Y3Error("batch must be float32 [B,S,S,3]")
+    if batch.dtype != torch.float32 or batch.dim() != 4 or batch.shape[3] != 3:
+        raise Y3Error("batch must be float32 [B,Hc,Wc,3]")
     if not (0 <= first_slot and first_slot + len(descs) <= batch.shape[0]):
         raise Y3Error(f"slots {first_slot}..{first_slot + len(descs) - 1} are outside the batch of {batch.shape[0]}")
     d = np.ascontiguousarray(descs)
-    check(_lib.load().y3_preprocess_batch(_dev(blob_dev), blob_dev.numel(), d.ctypes.data_as(C.POINTER(_lib.ImageDesc)),
-                                          len(d), _dev(batch), int(first_slot), batch.shape[1], _lib.stream_ptr()),
+    check(_lib.load().y3_preprocess_batch_hw(_dev(blob_dev), blob_dev.numel(), d.ctypes.data_as(C.POINTER(_lib.ImageDesc)),
+                                             len(d), _dev(batch), int(first_slot), batch.shape[1], batch.shape[2], _lib.stream_ptr()),
           "y3_preprocess_batch")
     return batch
 
@@ -914,7 +992,7 @@ class _StageSlot:
         self.pinned = torch.empty(max_blob_bytes, dtype=torch.uint8, pin_memory=True)
         self.pinned_np = self.pinned.numpy()
         self.blob_dev = torch.empty(max_blob_bytes, dtype=torch.uint8, device=device)
-        self.batch = torch.empty((max_batch, image_size, image_size, 3), dtype=torch.float32, device=device)
+        self.batch = torch.empty((max_batch, *canvas_hw(image_size), 3), dtype=torch.float32, device=device)
         self.ready = torch.cuda.Event()      # copy stream: pixels copied and resized into `batch`
         self.released = torch.cuda.Event()   # consumer stream: `batch` has been read
         self.state = "free"                  # free -> held (submit) -> released (release) -> held ...
@@ -928,11 +1006,12 @@ class InputStage:
     Every wait is on an event: the host waits for `ready` of the slot's previous use before it overwrites the pinned
     blob, the copy stream waits for `released` before it overwrites the device buffers.  Nothing synchronises the device."""
 
-    def __init__(self, image_size: int, max_batch: int, max_blob_bytes: int, depth: int = 2):
-        _lib.require_gpu()
-        if image_size < 1 or max_batch < 1 or max_blob_bytes < 1 or depth < 1:
+    def __init__(self, image_size, max_batch: int, max_blob_bytes: int, depth: int = 2):
+        _lib.require_gpu()      # image_size: an int S or an (H, W) canvas
+        if min(canvas_hw(image_size)) < 1 or max_batch < 1 or max_blob_bytes < 1 or depth < 1:
             raise Y3Error("InputStage: image_size, max_batch, max_blob_bytes and depth must be at least 1")
-        self.image_size, self.max_batch, self.depth = int(image_size), int(max_batch), int(depth)
+        self.image_size = int(image_size) if isinstance(image_size, (int, np.integer)) else canvas_hw(image_size)
+        self.max_batch, self.depth = int(max_batch), int(depth)
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.stream = torch.cuda.Stream(self.device)
         self.slots = [_StageSlot(self.image_size, self.max_batch, int(max_blob_bytes), self.device) for _ in range(self.depth)]

@@ -137,6 +137,26 @@ y3_status y3_net_set_xcd_mode(y3_net *net, int mode);
  * major order re-fetched the operands of the 13x13 layers ~18x from beyond L2).  The same products in another summation
  * order: results differ from the tap-major ones in the last bits.  0: tap-major; -1 (default): chosen per conv. */
 y3_status y3_net_set_k_chunk(y3_net *net, int channels);
+/* Low-latency fp32 plans: split-K convs for small batches (one to eight images), off by default.
+ * At one 416^2 image the convs of the 13^2 .. 52^2 grids launch 24 .. 172 workgroups on 256 compute units, each walking the whole
+ * K = taps * Cin alone.  With y3_net_set_low_latency(net, 1), called before y3_net_plan, each eligible conv is cut along K into S slices
+ * that run as S times the workgroups; every slice stores its raw accumulators into a workspace owned by the plan, and a second launch on
+ * the same stream adds the slices in the fixed order 0, 1, ..., S-1 and applies the epilogue (no atomics: two runs give the same bits).
+ * S is decided at plan time by y3_choose_split_k from the conv's shape, its tile at the planned max_batch and the device's compute
+ * units -- never from the rows of a call, so inside one plan an image's result does not depend on its batch or position.  S = 1 (the
+ * ordinary launch) wherever the planned batch already fills the chip.  Never split: the first layer, the fused stem, the weight-
+ * resident tile 33, the three detection-head convs (y3_net_detect and the composed route stay bit-identical), any plan that is not
+ * Y3_DTYPE_F32.  The same products in another summation order: results differ from the default plan's in the last bits (as
+ * y3_net_set_k_chunk says of itself).  With it off nothing changes.
+ * y3_net_set_split_k: S of one conv: -1 = y3_choose_split_k when low latency is on (else 1), 1 = off, 2..16 = that value whether or not
+ * low latency is on.  An ineligible conv or S > the conv's K tiles (K / 32) is refused here with Y3_ERR_INVALID and a message, not
+ * by the forward.  y3_net_get_split_k: the value in force after planning (1 before).
+ * y3_choose_split_k (pure, no device): 1 when tiles >= 2 * n_cus; else the smallest S with tiles * S >= 2 * n_cus, capped at
+ * k_tiles / 4, at 16 and at 16 MiB of slabs (S * slab_bytes_per_slice); tiles = workgroups of the unsplit launch. */
+y3_status y3_net_set_low_latency(y3_net *net, int on);
+y3_status y3_net_set_split_k(y3_net *net, int conv_slot, int S);
+int y3_net_get_split_k(const y3_net *net, int conv_slot);
+int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice);
 y3_status y3_net_keep_activations(y3_net *net, int keep);
 /* 1 (default): when the program starts with conv0 (3x3/1, 3 -> 32) feeding only conv1 (3x3/2, 32 -> 64) -- the Darknet-53
  * stem, reference config/models/yolov3/backbone.yaml layers 1-2 -- and the plan is fp32 or bf16 without keep_activations,

@@ -19,7 +19,7 @@ from yolo_v3_tf2_amd import runtime, _lib
 from yolo_v3_tf2_amd.graph import load_program
 from yolo_v3_tf2_amd.weights import synthetic_weights
 p = load_program(os.path.join(%r, "config/models/yolov3/model.yaml"), 80)
-B, S, dt, data, route = %d, %d, %r, %r, %r
+B, S, dt, data, route, steps = %d, %d, %r, %r, %r, %d
 w = synthetic_weights(p)
 if data == "zeros":   # every operand of every MFMA is zero: no toggling in the matrix pipes or on the data paths (a power experiment)
     for k in w:
@@ -32,12 +32,13 @@ import numpy as np
 from yolo_v3_tf2_amd.core.utils import get_anchors
 anchors = get_anchors(os.path.join(%r, "datasets/coco2012/anchors.txt")).astype(np.float32)
 step = (lambda: net.forward(x, out=g)) if route == "forward" else (lambda: net.forward_decode(x, anchors))   # decode: the route bench.py times (head convs decode their own tiles)
+if route == "detect": step = lambda: net.detect(x, anchors, 100, 0.5, 0.1)   # the whole call a small-batch caller makes (tools/time_latency.py)
 for _ in range(5): step()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 torch.cuda.synchronize(); e0.record()
-for _ in range(30): step()
+for _ in range(steps): step()
 e1.record(); torch.cuda.synchronize()
-ms = e0.elapsed_time(e1) / 30
+ms = e0.elapsed_time(e1) / steps
 print("RESULT %%.4f %%.2f" %% (ms, net.flops_per_image() * B / ms / 1e9), flush=True)
 '''
 
@@ -49,10 +50,11 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--image-size", type=int, default=416)
     ap.add_argument("--rounds", type=int, default=3)
-    ap.add_argument("--route", default="forward", choices=["forward", "decode"], help="forward: y3_net_forward (grids written); decode: y3_net_forward_decode, the route bench.py times")
+    ap.add_argument("--route", default="forward", choices=["forward", "decode", "detect"], help="forward: y3_net_forward (grids written); decode: y3_net_forward_decode, the route bench.py times; detect: y3_net_detect")
+    ap.add_argument("--steps", type=int, default=30, help="timed steps per child process")
     ap.add_argument("--data", default="rand", choices=["rand", "zeros"], help="zeros: all-zero weights and images (what the step costs without data toggling: the power wall)")
     a = ap.parse_args()
-    code = CHILD % (ROOT, ROOT, a.batch, a.image_size, a.dtype, a.data, a.route, ROOT)
+    code = CHILD % (ROOT, ROOT, a.batch, a.image_size, a.dtype, a.data, a.route, a.steps, ROOT)
     res = {lib: [] for lib in a.libs}
     for r in range(a.rounds):
         for lib in a.libs:

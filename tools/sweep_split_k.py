@@ -1,0 +1,87 @@
+#!/usr/bin/env python3
+"""Per-conv sweep of the split-K factor S (y3_net_set_split_k) on a small-batch fp32 plan: what the constants of y3_choose_split_k
+are set from.  For every eligible conv and every S of --splits (clamped to the conv's K tiles) the launch -- slices plus finish
+launch -- is timed alone with y3_net_profile_convs, median of --repeats; the table gives per conv the time at every S, the best S,
+the S the rule picks and what the rule leaves on the table, then the sums over the conv stack: unsplit, rule, best per conv.
+    python tools/sweep_split_k.py [--size 416] [--batches 1 2 4 8] [--out profiles/latency_splitk_sweep.txt]"""
+import argparse
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, nargs="+", default=[416])
+    ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8])
+    ap.add_argument("--splits", type=int, nargs="+", default=[1, 2, 3, 4, 6, 8, 12, 16])
+    ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+
+    import torch
+    import yolo_v3_tf2_amd  # noqa: F401
+    from yolo_v3_tf2_amd import runtime
+    from yolo_v3_tf2_amd.graph import load_program
+    from yolo_v3_tf2_amd.weights import synthetic_weights
+
+    lines = []
+
+    def say(s=""):
+        print(s, flush=True)
+        lines.append(s)
+
+    program = load_program(os.path.join(ROOT, "config/models/yolov3/model.yaml"), 80)
+    net = runtime.Net(program)
+    net.load_weights(synthetic_weights(program))
+    n = len(net.conv_ops)
+    say(f"# tools/sweep_split_k.py  device: {torch.cuda.get_device_name(0)}  fp32; ms per conv launch alone (split: slices + finish), median of {a.repeats}")
+    for S_img in a.size:
+        for B in a.batches:
+            x = torch.rand((B, S_img, S_img, 3), device="cuda")
+            for i in range(n):
+                net.set_split_k(i, -1)
+            net.set_low_latency(True)
+            net.plan(B, S_img)
+            rule = [net.split_k(i) for i in range(n)]
+            net.set_low_latency(False)
+            ms, eff = {}, {}
+            splits = sorted(set(a.splits) | set(rule))      # the rule's own values are always measured
+            for S in splits:
+                for i, o in enumerate(net.conv_ops):
+                    want = min(S, max(1, o.size * o.size * o.cin // 32))
+                    try:
+                        net.set_split_k(i, want if want > 1 else 1)
+                    except runtime.Y3Error:
+                        net.set_split_k(i, 1)
+                eff[S] = [net.split_k(i) for i in range(n)]
+                net.profile_convs(x)
+                ms[S] = np.median([net.profile_convs(x) for _ in range(a.repeats)], axis=0)
+            say(f"\n== {S_img} x {S_img}, batch {B}")
+            say("slot  signature                            " + "".join(f"  S={S:<5d}" for S in splits) + "  best  rule   rule-best ms")
+            tot = {"unsplit": 0.0, "rule": 0.0, "best": 0.0}
+            for i, o in enumerate(net.conv_ops):
+                t = {S: float(ms[S][i]) for S in splits}
+                # time at the S in force (a clamped or refused request repeats a smaller S: take the first column with that value)
+                at = {}
+                for S in splits:
+                    at.setdefault(eff[S][i], t[S])
+                best = min(at, key=at.get)
+                t_rule = at[rule[i]]
+                tot["unsplit"] += at[1]
+                tot["rule"] += t_rule
+                tot["best"] += at[best]
+                cols = "".join(f"  {t[S]:7.4f}" if eff[S][i] == S else "        -" for S in splits)
+                say(f"{i:4d}  {runtime.Net.conv_signature(o, S_img):36s}{cols}  {best:4d}  {rule[i]:4d}   {t_rule - at[best]:+.4f}")
+            say(f"sum over the conv stack: unsplit {tot['unsplit']:.4f} ms | rule {tot['rule']:.4f} ms | best S per conv {tot['best']:.4f} ms")
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()

@@ -11,7 +11,9 @@ import os
 
 from . import PACKAGE_DIR
 
-# Y3_LIB_PATH: load another build of the same ABI (A/B of kernel variants on one box: tools/ab_libs.py)
+# Y3_LIB_PATH: load another build of the same ABI (A/B of kernel variants on one box: tools/ab_libs.py).  Such a build may be an
+# OLDER one (an earlier commit's library as the baseline of an A/B): a symbol it lacks is bound to a stub that raises Y3Error when
+# called.  The package's own library must export every symbol.
 LIB_PATH = os.environ.get("Y3_LIB_PATH") or os.path.join(PACKAGE_DIR, "lib", "liby3hip.so")
 
 Y3_OK = 0
@@ -110,6 +112,10 @@ SYMBOLS = {
     "y3_net_set_xcd_mode": (_i, [_vp, _i]),
     "y3_net_set_k_chunk": (_i, [_vp, _i]),
     "y3_net_set_stem_fusion": (_i, [_vp, _i]),
+    "y3_net_set_low_latency": (_i, [_vp, _i]),
+    "y3_net_set_split_k": (_i, [_vp, _i, _i]),
+    "y3_net_get_split_k": (_i, [_vp, _i]),
+    "y3_choose_split_k": (_i, [C.c_longlong, _i, _i, C.c_longlong]),
     "y3_net_measure_sclk": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _fp, _vp]),
     "y3_net_measure_sclk_conv": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _i, _fp, _vp]),
     "y3_net_measure_sclk_all": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _fp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
@@ -164,10 +170,22 @@ def load():
         import torch  # noqa: F401  -- first, so that torch's bundled HIP runtime (same soname) is the one we share
         lib = C.CDLL(LIB_PATH)
         for name, (res, args) in SYMBOLS.items():
-            fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
+            try:
+                fn = getattr(lib, name)  # AttributeError if the .so does not export what the header declares
+            except AttributeError:
+                if not os.environ.get("Y3_LIB_PATH"):
+                    raise
+                setattr(lib, name, _missing(name))
+                continue
             fn.restype, fn.argtypes = res, args
         _lib = lib
     return _lib
+
+
+def _missing(name):
+    def stub(*_):
+        raise Y3Error(f"{LIB_PATH} (Y3_LIB_PATH) is an older build that does not export {name}")
+    return stub
 
 
 def tile_built(dtype: int, tile: int) -> bool:

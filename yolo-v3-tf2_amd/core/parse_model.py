@@ -40,15 +40,26 @@ class YoloModel:
         self.name = name
         self._net = None
         self._weights = None
+        self.low_latency = False
 
     # lazily create the device object so that building/inspecting a model works without a GPU
     def _device_net(self):
         if self._net is None:
             from ..runtime import Net
             self._net = Net(self.program)
+            if self.low_latency:
+                self._net.set_low_latency(True)
             if self._weights is not None:
                 self._net.load_weights(self._weights)
         return self._net
+
+    def set_low_latency(self, on=True):
+        """Low-latency fp32 plans (runtime.Net.set_low_latency): split-K convs for batches of one to eight images.  Takes
+        effect at the next plan, i.e. before the first call or when the batch shape changes."""
+        from ..runtime import Net
+        self.low_latency = Net._low_latency_arg(on)
+        if self._net is not None:
+            self._net.set_low_latency(self.low_latency)
 
     def set_weights_dict(self, weights):
         self._weights = weights

@@ -16,6 +16,12 @@
 // contracted exactly once (the order of k inside a tile is irrelevant to the sum's value up to
 // fp32 rounding).
 // Epilogue from the accumulators: y = acc*scale[n] + shift[n]; leaky; + residual; store.
+//
+// Split-K (SPLIT = true, the low-latency plans of y3_net_set_low_latency): a launch of S slices runs S times the workgroups,
+// gridDim.y = S.  Slice y walks K tiles [y*KT/S, (y+1)*KT/S) of the SAME walk an unsplit launch takes -- the chunk-major order is
+// kept where it is in force, and slices are counted along that walk -- and stores its raw accumulators (no epilogue, rows >= M
+// included: the slab is padded to whole tiles) into slab y of a workspace [S][Mpad][CoutPad].  splitk_finish_f32, a separate launch
+// on the same stream, adds the slabs in the order 0, 1, ..., S-1 and applies the epilogue above.
 #include <algorithm>
 #include <type_traits>
 
@@ -54,9 +60,10 @@ __device__ int y3_dbg32_sel_k = -1;
 #define Y3_STAMP32(k) do { } while (0)
 #endif
 
-template <int TM, int TN, int WR, int WC, bool CONCAT, int STAGES, int MINW = 1, int DMA = 0>
+template <int TM, int TN, int WR, int WC, bool CONCAT, int STAGES, int MINW = 1, int DMA = 0, bool SPLIT = false>
 __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvArgs p)
 {
+    static_assert(!SPLIT || (!DMA && STAGES == 1), "the split-K form is built for the register-staged single-stage tiles");
     Y3_STAMP32(0);
 #ifdef Y3_PHASE_STAMPS
     if (threadIdx.x == 0 && blockIdx.x < 32768 && p.K == y3_dbg32_sel_k) {
@@ -77,7 +84,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     extern __shared__ __attribute__((aligned(16))) float smem[];
 
     const int tid = threadIdx.x;
-    clk_stamp_entry(p.clk_stamps);   // measurement launches only (y3_net_measure_sclk)
+    if constexpr (!SPLIT) clk_stamp_entry(p.clk_stamps);   // measurement launches only (y3_net_measure_sclk); a split launch carries no stamps
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WC, wc = wave % WC;
@@ -86,7 +93,9 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     const int bid = blockIdx.x, xcd = bid & 7;
     const int logical = xcd_contiguous_tile(bid, nwg);   // (the xcd_gn > 0 order below replaces it)
     const int tilesN = p.CoutPad / BN;
-    const int KT = p.K / BK;
+    // K tiles of this workgroup's walk: all of them, or slice blockIdx.y of gridDim.y (starting at tile kt0 of the walk)
+    const int kt0 = SPLIT ? (int)blockIdx.y * (p.K / BK) / (int)gridDim.y : 0;
+    const int KT = SPLIT ? ((int)blockIdx.y + 1) * (p.K / BK) / (int)gridDim.y - kt0 : p.K / BK;
     const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
     const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(CONCAT ? p.src1 : p.src0, CONCAT ? p.src1_bytes : p.src0_bytes);
     const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
@@ -176,6 +185,17 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     int c0 = 0;
     int cend = CK;            // end of the current channel chunk (classic order: Cin)
     const int taps = p.ksize * p.ksize;
+    if constexpr (SPLIT) {
+        // the walk's state at tile kt0: chunks of CK channels (the whole Cin in the classic order and for a concat 1x1), inside a
+        // chunk tap after tap, inside a tap CK / 32 tiles.  A concat slice may begin anywhere in src0 or src1: the fetch picks the
+        // source from c0.
+        const int tpc = CK / BK, per_chunk = taps * tpc;
+        const int chunk = kt0 / per_chunk, r = kt0 - chunk * per_chunk;
+        tap = r / tpc;
+        c0 = chunk * CK + (r - tap * tpc) * BK;
+        cend = (chunk + 1) * CK;
+        kglob = tap * p.Cin + c0;
+    }
     unsigned avoff[AP];                  // voffset of this lane's piece for the current tap (or OOB0)
     unsigned okmask[CONCAT ? 1 : AP];    // !CONCAT: bit t = tap t of this row lies inside the image
     unsigned abase4[CONCAT ? 1 : AP];    // !CONCAT: byte offset of this lane's piece of the row at tap (0, 0), channel 0
@@ -356,6 +376,25 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     }
 
     Y3_STAMP32(3);
+    if constexpr (SPLIT) {
+        // raw accumulators -> slab blockIdx.y: p.dst is the workspace, p.dst_bytes the bytes of ONE slab [Mpad][CoutPad] (Mpad = whole
+        // tiles, so every row of the tile has its place; the range check of the slab's own buffer resource drops anything else)
+        const __amdgpu_buffer_rsrc_t rss = buffer_rsrc(static_cast<const char *>(p.dst) + (size_t)blockIdx.y * p.dst_bytes, p.dst_bytes);
+        const int slab_row_bytes = p.CoutPad * 4;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n0 + (wc * TN + j) * 32 + fr;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const int mbase = m0 + (wr * TM + i) * 32 + 4 * fh;
+                const unsigned vbase = (unsigned)(mbase * p.CoutPad + n) * 4u;
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i][j][e]), rss, (int)vbase,
+                                                          ((e & 3) + 8 * (e >> 2)) * slab_row_bytes, 0);
+            }
+        }
+    } else {
     // ---- epilogue ----------------------------------------------------------------------------
     // accumulator element e of lane l: column (n) = l & 31, row (m) = (e & 3) + 8*(e >> 2) + 4*(l >> 5).
     // Straight-line: out-of-tile elements get a voffset == num_records, which the buffer bounds check
@@ -429,6 +468,36 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     }
     Y3_STAMP32(4);   // thread 0 = wave 0: its own stores issued (not yet retired)
     clk_stamp_exit(p.clk_stamps);
+    }
+}
+
+// Second half of a split-K conv: dst[m][n] = epilogue(slab[0][m][n] + slab[1][m][n] + ... + slab[S-1][m][n]), the slabs added in that
+// order, then exactly the conv epilogue's operations (+ shift, leaky as max(v, 0.1 v), + residual).  VEC: four channels per thread with
+// 16-byte accesses (Cout % 4 == 0); otherwise one element per thread (the Cout = 255 head shape).
+template <bool VEC>
+__global__ __launch_bounds__(256) void splitk_finish_f32(const float *__restrict__ ws, int S, size_t slab_elems, int cout_pad,
+                                                         const float *__restrict__ shift, const float *__restrict__ residual,
+                                                         float *__restrict__ dst, int M, int cout, int leaky)
+{
+    constexpr int W = VEC ? 4 : 1;
+    typedef float vec __attribute__((ext_vector_type(W)));
+    const int per_row = cout / W;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)M * per_row) return;
+    const int m = (int)(idx / per_row);
+    const int n = ((int)(idx - (size_t)m * per_row)) * W;
+    const float *src = ws + (size_t)m * cout_pad + n;
+    vec v = *reinterpret_cast<const vec *>(src);
+    for (int s = 1; s < S; ++s) v = v + *reinterpret_cast<const vec *>(src + (size_t)s * slab_elems);
+    v = v + *reinterpret_cast<const vec *>(shift + n);
+    if (leaky) {
+        const vec t = v * 0.1f;
+#pragma unroll
+        for (int k = 0; k < W; ++k) v[k] = fmaxf(v[k], t[k]);
+    }
+    const size_t o = (size_t)m * cout + n;
+    if (residual) v = *reinterpret_cast<const vec *>(residual + o) + v;
+    *reinterpret_cast<vec *>(dst + o) = v;
 }
 
 template <int TM, int TN, int WR, int WC, bool CONCAT, int STAGES, int MINW, int DMA>
@@ -499,6 +568,49 @@ extern "C" int y3_dbg32_copy_stamps(unsigned long long *dst, int n_words)
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(y3_dbg32_stamps), (size_t)n_words * sizeof(unsigned long long));
 }
 #endif
+
+// The split-K form is instantiated for the two tiles a small plan selects: 10 (64x128) and 11 (64x64), both register-staged, single-stage
+template <int TN>
+static hipError_t launch_split_t(const ConvArgs &c, int grid, int S, hipStream_t s)
+{
+    constexpr size_t lds = (size_t)(64 + 64 * TN) * lds_row(0) * sizeof(float);
+    if (c.src1) return launch_conv_kernel<conv_f32_mfma<1, TN, 2, 2, true, 1, 4, 0, true>>(c, grid, 256, lds, s, S);
+    return launch_conv_kernel<conv_f32_mfma<1, TN, 2, 2, false, 1, 4, 0, true>>(c, grid, 256, lds, s, S);
+}
+
+bool conv_split_tile(int tile) { return tile == 10 || tile == 11; }
+
+size_t conv_split_slab_bytes(int tile, long long M, int cout_pad)
+{
+    const TileInfo t = conv_tile_info(tile);
+    return (size_t)((M + t.bm - 1) / t.bm) * t.bm * cout_pad * sizeof(float);
+}
+
+hipError_t launch_conv_f32_split(const ConvArgs &a, int tile, int S, void *ws, size_t ws_bytes, hipStream_t s)
+{
+    if (!conv_split_tile(tile) || !tile_fits(kTiles[tile].info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
+    const size_t slab = conv_split_slab_bytes(tile, a.M, a.CoutPad);
+    if (S < 2 || S > a.K / BK || !ws || !a.dst || slab > 0x7fffffffull || (size_t)S * slab > ws_bytes) return hipErrorInvalidValue;
+    const TileInfo t = kTiles[tile].info;
+    ConvArgs c = a;
+    c.dst = ws;
+    c.dst_bytes = (unsigned)slab;
+    c.residual = nullptr;
+    c.xcd_gn = 0;
+    c.clk_stamps = nullptr;
+    const int grid = ((a.M + t.bm - 1) / t.bm) * (a.CoutPad / t.bn);
+    if (hipError_t e = tile == 10 ? launch_split_t<2>(c, grid, S, s) : launch_split_t<1>(c, grid, S, s); e != hipSuccess) return e;
+    const float *wsf = static_cast<const float *>(ws), *res = static_cast<const float *>(a.residual);
+    float *dst = static_cast<float *>(a.dst);
+    const bool vec = a.Cout % 4 == 0 && ((uintptr_t)dst & 15) == 0 && ((uintptr_t)res & 15) == 0;
+    const size_t n = (size_t)a.M * (vec ? a.Cout / 4 : a.Cout);
+    const dim3 fgrid((unsigned)((n + 255) / 256));
+    if (vec)
+        hipLaunchKernelGGL(splitk_finish_f32<true>, fgrid, dim3(256), 0, s, wsf, S, slab / 4, a.CoutPad, a.shift, res, dst, a.M, a.Cout, a.leaky);
+    else
+        hipLaunchKernelGGL(splitk_finish_f32<false>, fgrid, dim3(256), 0, s, wsf, S, slab / 4, a.CoutPad, a.shift, res, dst, a.M, a.Cout, a.leaky);
+    return hipGetLastError();
+}
 
 TileInfo conv_tile_info(int tile) { return kTiles[(tile >= 0 && tile < TILE_COUNT) ? tile : 0].info; }
 

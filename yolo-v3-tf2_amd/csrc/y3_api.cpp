@@ -113,6 +113,8 @@ struct ConvSlot {
     int cout_pad = 0;
     int K = 0;
     int tile = -1;             // -1: choose by heuristic at plan time
+    int split_req = -1;        // y3_net_set_split_k: -1 the heuristic (low-latency plans only), 1 off, 2..16 forced
+    int split_k = 1;           // K slices in force, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
     int tile_bf16 = -1;
     int tile_x3 = -1;
     int cout_pad64 = 0;        // Cout rounded up to 64 (the three-plane kernel has no 32-wide N tile)
@@ -168,6 +170,11 @@ struct y3_net {
     bool stem_fused = false;       // (at plan time) the first two convs run as the fused stem kernel
     bool stem_conv2 = false;       // ... and the 1x1 conv that follows them (64 -> 32) runs inside it as well (fp32 and bf16 plans)
     int xcd_mode = 1;              // y3_net_set_xcd_mode: 0 contiguous tile runs per XCD, 1 XCD-blocked order chosen per conv
+    bool low_latency_set = false;  // y3_net_set_low_latency was called (the Y3_LOW_LATENCY tool override then stays out)
+    bool low_latency = false;      // y3_net_set_low_latency: every eligible fp32 conv takes y3_choose_split_k
+    void *split_ws = nullptr;      // split-K slabs: split_ws_lanes regions of split_ws_lane bytes, one per lane (lanes run concurrently)
+    size_t split_ws_lane = 0;
+    int split_ws_lanes = 0;
     int k_chunk = -1;              // y3_net_set_k_chunk: fp32 3x3 convs walk K chunk-major, this many input channels per chunk; 0 tap-major; -1 per-conv default
     hipEvent_t fork_ev = nullptr;
     hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -188,6 +195,10 @@ void free_plan(y3_net *n)
     if (n->det_buf) (void)hipFree(n->det_buf);
     n->det_buf = nullptr;
     n->det_bytes = 0;
+    if (n->split_ws) (void)hipFree(n->split_ws);
+    n->split_ws = nullptr;
+    n->split_ws_lane = 0;
+    n->split_ws_lanes = 0;
     for (void *p : n->blocks) (void)hipFree(p);
     n->blocks.clear();
     n->tdev.assign(n->tensors.size(), nullptr);
@@ -448,6 +459,77 @@ static bool stem_conv2_applicable(const y3_net *net)
     return !is_output(net, c.dst);
 }
 
+// ---- split-K (low-latency fp32 plans) --------------------------------------------------------------------------------------
+// Can conv `slot` ever run split?  From the graph and the forced tile alone (no plan needed): not the first layer, not the
+// weight-resident tile 33, not a detection head (y3_net_detect runs the heads through conv_head.hip, and the composed route
+// must stay bit-identical to it), and only on the two tiles the split form is built for.  why: the refusal's text.
+static bool split_eligible(const y3_net *net, int slot, const char **why)
+{
+    const ConvSlot &c = net->convs[slot];
+    const char *w = nullptr;
+    if (c.first_layer) w = "the first layer (Cin = 3) is never split";
+    else if (net->nclasses > 0 && is_output(net, c.d.dst)) w = "a detection-head conv is never split (y3_net_detect decodes it in its own kernel)";
+    else if (c.tile >= 0 ? !y3::conv_split_tile(c.tile) : !y3::conv_split_tile(choose_tile(c, 1)))
+        w = "the conv's tile has no split form (tiles 10 and 11 have; the weight-resident tile 33 and the 32-wide tile 8 have not)";
+    if (why) *why = w;
+    return !w;
+}
+
+// does conv op oi run inside the fused stem launch (or as it)?
+static bool in_fused_stem(const y3_net *net, int oi) { return (net->stem_fused && oi < 2) || (net->stem_conv2 && oi == 2); }
+
+// Decide ConvSlot::split_k of every conv and size the slab workspace.  Runs at the end of y3_net_plan_hw and again from every
+// setter that changes an input of the decision on a planned net; never from the enqueue path.  Inputs: the conv's shape, its tile at
+// the planned batch, max_batch, n_cus, the caller's request -- never the rows of a call, so within one plan an image's bits do not
+// depend on its batch or position (the rule choose_tile_bf16 states for the MFMA shape).
+static y3_status resolve_splits(y3_net *net)
+{
+    if (!net->height) return Y3_OK;
+    size_t lane_bytes = 0;
+    for (int oi = 0; oi < (int)net->ops.size(); ++oi) {
+        if (net->ops[oi].kind != 0) continue;
+        const int slot = net->ops[oi].index;
+        ConvSlot &c = net->convs[slot];
+        c.split_k = 1;
+        if (net->dtype != Y3_DTYPE_F32 || in_fused_stem(net, oi) || !split_eligible(net, slot, nullptr)) continue;
+        if (c.split_req == 1 || (c.split_req < 0 && !net->low_latency)) continue;
+        const long long M = (long long)net->max_batch * (net->height / c.d.out_div) * (net->width / c.d.out_div);
+        const int tile = c.tile >= 0 ? c.tile : choose_tile(c, M);
+        const y3::TileInfo t = y3::conv_tile_info(tile);
+        const long long tiles = ((M + t.bm - 1) / t.bm) * (c.cout_pad / t.bn);
+        const size_t slab = y3::conv_split_slab_bytes(tile, M, c.cout_pad);
+        const int kt = c.K / t.bk;
+        int S = c.split_req > 1 ? c.split_req : y3_choose_split_k(tiles, kt, net->n_cus, (long long)slab);
+        if (S > kt) S = kt;
+        if (S < 2 || slab > 0x7fffffffull) continue;
+        c.split_k = S;
+        lane_bytes = std::max(lane_bytes, (size_t)S * slab);
+    }
+    if (lane_bytes > net->split_ws_lane || (lane_bytes && net->lanes > net->split_ws_lanes)) {
+        if (net->split_ws) (void)hipFree(net->split_ws);
+        net->split_ws = nullptr;
+        net->split_ws_lane = 0;
+        net->split_ws_lanes = 0;
+        lane_bytes = (lane_bytes + 255) & ~(size_t)255;
+        hipError_t e = hipMalloc(&net->split_ws, lane_bytes * net->lanes);
+        if (e != hipSuccess) {
+            for (ConvSlot &c : net->convs) c.split_k = 1;
+            return fail(Y3_ERR_OOM, "split-K workspace: hipMalloc(%zu) failed: %s", lane_bytes * net->lanes, hipGetErrorString(e));
+        }
+        net->split_ws_lane = lane_bytes;
+        net->split_ws_lanes = net->lanes;
+    }
+    return Y3_OK;
+}
+
+// ... from a setter: nothing to decide before the first plan; afterwards on the net's device (the workspace may grow)
+static y3_status resolve_splits_of_setter(y3_net *net)
+{
+    if (!net->height) return Y3_OK;
+    Y3_ENTER_DEVICE(net);
+    return resolve_splits(net);
+}
+
 // Is net output t staged in a non-fp32 plan -- produced in the arena in the mode's own format and converted into the caller's fp32
 // grid at the end of the forward -- because a conv reads it again inside the net, or a conv with no fp32-output form of its launch
 // (shortcut, first layer) writes it?  Needs no plan: y3_net_plan marks `staged` by it, and y3_net_set_tile_bf16 refuses the
@@ -694,7 +776,8 @@ Y3_CATCH("y3_net_set_conv_weights")
 
 y3_status y3_net_set_tile(y3_net *net, int slot, int tile)
 try {
-    return set_forced_tile(F32_FAMILY, net, slot, tile);
+    if (y3_status st = set_forced_tile(F32_FAMILY, net, slot, tile); st != Y3_OK) return st;
+    return resolve_splits_of_setter(net);   // the tile is an input of the split decision
 }
 Y3_CATCH("y3_net_set_tile")
 
@@ -720,7 +803,7 @@ y3_status y3_net_set_lanes(y3_net *net, int lanes)
 try {
     if (!net || lanes < 1 || lanes > Y3_MAX_LANES) return fail(Y3_ERR_INVALID, "y3_net_set_lanes: lanes must be in [1,%d]", Y3_MAX_LANES);
     net->lanes = lanes;
-    return Y3_OK;
+    return resolve_splits_of_setter(net);   // one slab workspace per lane
 }
 Y3_CATCH("y3_net_set_lanes")
 
@@ -734,7 +817,7 @@ try {
         net->stem_fused = on && stem_applicable(net);
         net->stem_conv2 = net->stem_fused && on == 1 && stem_conv2_applicable(net);
     }
-    return Y3_OK;
+    return resolve_splits_of_setter(net);   // a conv inside the fused stem is not split
 }
 Y3_CATCH("y3_net_set_stem_fusion")
 
@@ -745,6 +828,34 @@ try {
     return Y3_OK;
 }
 Y3_CATCH("y3_net_set_k_chunk")
+
+y3_status y3_net_set_low_latency(y3_net *net, int on)
+try {
+    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "y3_net_set_low_latency: argument must be 0 or 1");
+    net->low_latency = on != 0;
+    net->low_latency_set = true;
+    return resolve_splits_of_setter(net);
+}
+Y3_CATCH("y3_net_set_low_latency")
+
+y3_status y3_net_set_split_k(y3_net *net, int slot, int S)
+try {
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || S < -1 || S == 0 || S > 16)
+        return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv slot out of range, or S not -1, 1 or 2..16");
+    ConvSlot &c = net->convs[slot];
+    if (S > 1) {
+        const char *why = nullptr;
+        if (!split_eligible(net, slot, &why)) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d: %s", slot, why);
+        if (net->height && net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d: only Y3_DTYPE_F32 plans split K", slot);
+        for (int oi = 0; oi < 3 && oi < (int)net->ops.size() && net->height; ++oi)
+            if (net->ops[oi].kind == 0 && net->ops[oi].index == slot && in_fused_stem(net, oi))
+                return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d runs inside the fused stem kernel, which is never split", slot);
+        if (S > c.K / 32) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d has %d K tiles, fewer than S = %d", slot, c.K / 32, S);
+    }
+    c.split_req = S;
+    return resolve_splits_of_setter(net);
+}
+Y3_CATCH("y3_net_set_split_k")
 
 y3_status y3_net_set_xcd_mode(y3_net *net, int mode)
 try {
@@ -901,6 +1012,10 @@ try {
     }
     net->stem_fused = net->stem_mode && stem_applicable(net);
     net->stem_conv2 = net->stem_fused && net->stem_mode == 1 && stem_conv2_applicable(net);
+    {   // Y3_LOW_LATENCY (tools/ab_libs.py: a low-latency plan in a child process that knows nothing of it) overrides the default, not the setter
+        static const int env = [] { const char *e = getenv("Y3_LOW_LATENCY"); return e ? atoi(e) : -1; }();
+        if ((env == 0 || env == 1) && !net->low_latency_set) net->low_latency = env == 1;
+    }
     if (net->nclasses > 0) {   // scratch of y3_net_detect: no allocation inside the stream-ordered call
         size_t off[9], n_boxes, gelems[3];
         int32_t gs[3][2];
@@ -911,6 +1026,10 @@ try {
             return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) for the detect scratch failed: %s", off[8], hipGetErrorString(e));
         }
         net->det_bytes = off[8];
+    }
+    if (y3_status st = resolve_splits(net); st != Y3_OK) {
+        free_plan(net);
+        return st;
     }
     return Y3_OK;
 }
@@ -944,6 +1063,30 @@ static void detect_layout(const y3_net *net, int batch, size_t off[9], size_t *n
     off[7] = off[6] + up((size_t)batch * Y3_MAX_OUTPUT_BOXES * 4);   // NMS workspace
     off[8] = off[7] + y3::nms_workspace_bytes(batch, (int)n);
     *n_boxes = n;
+}
+
+int y3_net_get_split_k(const y3_net *net, int slot)
+{
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height) return 1;
+    return net->convs[slot].split_k;
+}
+
+int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice)
+{
+    // Below two workgroups per CU the wall time of a conv launch is one workgroup's walk through K (the 13^2 512 -> 1024 conv at
+    // one image: 48 workgroups x 144 K tiles on 256 CUs), so slices multiply the workgroups until the chip holds two per CU -- but a
+    // slice keeps at least kSplitMinTiles K tiles (its prologue and its slab store are paid per slice), at most kSplitMax slices
+    // exist, and the slabs of one launch stay under kSplitMaxBytes (they are written and read once more by the finish launch).
+    constexpr int kSplitMinTiles = 4, kSplitMax = 16;
+    constexpr long long kSplitMaxBytes = 16ll << 20;
+    if (tiles <= 0 || k_tiles <= 0 || n_cus <= 0 || slab_bytes_per_slice <= 0) return 1;
+    const long long want = 2ll * n_cus;
+    if (tiles >= want) return 1;
+    long long S = (want + tiles - 1) / tiles;
+    S = std::min<long long>(S, k_tiles / kSplitMinTiles);
+    S = std::min<long long>(S, kSplitMax);
+    S = std::min<long long>(S, kSplitMaxBytes / slab_bytes_per_slice);
+    return S < 2 ? 1 : (int)S;
 }
 
 double y3_net_flops_per_image(const y3_net *net)
@@ -1146,12 +1289,18 @@ struct Slice {
             e = y3::launch_conv_head_decode_f32(a, s);
         } else {
             const int tile = c.tile >= 0 ? c.tile : choose_tile(c, a.M);
-            if (net->xcd_mode) a.xcd_gn = choose_xcd_gn(c, a, y3::conv_tile_info(tile));
+            if (net->xcd_mode && c.split_k <= 1) a.xcd_gn = choose_xcd_gn(c, a, y3::conv_tile_info(tile));
             {   // K order of the 3x3 convs (conv_f32.hip): chunk-major when the conv has more input channels than one chunk
                 const int ck = net->k_chunk >= 0 ? net->k_chunk : default_k_chunk(c);
                 if (d.size == 3 && d.src1 < 0 && ck > 0 && d.cin > ck && d.cin % ck == 0 && ck % 32 == 0) a.k_chunk = ck;
             }
-            e = y3::launch_conv_f32(a, tile, s);
+            if (c.split_k > 1) {   // low-latency plan: S slices of the K walk into this lane's slabs, then the finish launch
+                if (lane >= net->split_ws_lanes) return fail(Y3_ERR_STATE, "conv %d: no split-K workspace for lane %d", conv, lane);
+                e = y3::launch_conv_f32_split(a, tile, c.split_k, static_cast<char *>(net->split_ws) + (size_t)lane * net->split_ws_lane,
+                                              net->split_ws_lane, s);
+            } else {
+                e = y3::launch_conv_f32(a, tile, s);
+            }
         }
         if (e != hipSuccess) return fail(Y3_ERR_HIP, "conv %d launch: %s", conv, hipGetErrorString(e));
         return Y3_OK;
@@ -1338,7 +1487,7 @@ bool conv_carries_stamps(const y3_net *net, size_t i)
     if (stem) return true;
     if (net->stem_fused && (i == (size_t)net->ops[0].index || (net->stem_conv2 && net->ops.size() > 2 && i == (size_t)net->ops[2].index)))
         return false;    // runs inside the stem launch
-    return net->dtype == Y3_DTYPE_F32 && !c.first_layer;
+    return net->dtype == Y3_DTYPE_F32 && !c.first_layer && c.split_k <= 1;   // a split launch carries no stamps
 }
 // pick >= 0: that conv, *mhz_out one value; pick == -2: every conv that carries stamps, mhz_out / start_us / end_us arrays of
 // convs.size() entries (0 where a conv left no stamps; times relative to the earliest stamp, from s_memrealtime)

@@ -60,12 +60,12 @@ inline hipError_t set_max_lds_once(LdsAttrOnce &st, const void *fn, int bytes, i
 
 // The tail every MFMA conv launcher shares: the dynamic-LDS attribute once per (instantiation, device), the launch, its status.
 template <auto KERNEL>
-static hipError_t launch_conv_kernel(const ConvArgs &a, int grid, int threads, size_t lds, hipStream_t s)
+static hipError_t launch_conv_kernel(const ConvArgs &a, int grid, int threads, size_t lds, hipStream_t s, int grid_y = 1)
 {
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     static LdsAttrOnce attr;  // per instantiation
     if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(KERNEL), (int)lds, a.device); e != hipSuccess) return e;
-    hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(threads), lds, s, a);
+    hipLaunchKernelGGL(KERNEL, dim3(grid, grid_y), dim3(threads), lds, s, a);
     return hipGetLastError();
 }
 
@@ -84,6 +84,12 @@ TileInfo conv_tile_info(int tile);
 bool conv_tile_built(int tile);        // false: retired id
 
 hipError_t launch_conv_f32(const ConvArgs &a, int tile, hipStream_t s);
+// split-K form of the same conv (conv_f32.hip): S >= 2 slices of the K walk as S times the workgroups, raw accumulators into
+// ws [S][Mpad][CoutPad] fp32 (at least S * conv_split_slab_bytes), then splitk_finish_f32 on the same stream: the slabs added in
+// the order 0..S-1, the epilogue, the store to a.dst.  Tiles 10 and 11 only (conv_split_tile).
+bool conv_split_tile(int tile);
+size_t conv_split_slab_bytes(int tile, long long M, int cout_pad);
+hipError_t launch_conv_f32_split(const ConvArgs &a, int tile, int S, void *ws, size_t ws_bytes, hipStream_t s);
 // weight-resident 3x3 / stride-1 / Cin = 32 conv (conv_res_f32.hip): tile id 33
 bool conv_res_f32_fits(const ConvArgs &a);
 hipError_t launch_conv_res_f32(const ConvArgs &a, hipStream_t s);

@@ -99,7 +99,9 @@ class Inference:
         return (canvas_h, canvas_w), anchors_table
 
     def build(self, model_config_file, classes_name_file, anchors_file, input_weights_path, yolo_max_boxes,
-              nms_iou_threshold, nms_score_threshold, weights=None):
+              nms_iou_threshold, nms_score_threshold, weights=None, low_latency=None):
+        """low_latency (optional YAML key; None or absent: off): plan the network for latency at one to eight images -- the
+        fp32 convs that leave most of the chip idle at such a batch are split along K (runtime.Net.set_low_latency)."""
         anchors_table = get_anchors(anchors_file).astype(np.float32)      # reference: inference.py:83
         class_names = [c.strip() for c in open(classes_name_file).readlines()]
         nclasses = len(class_names)
@@ -116,6 +118,7 @@ class Inference:
             model.set_weights_dict(weights)
         else:
             model.load_weights(input_weights_path).expect_partial()
+        model.set_low_latency(low_latency)
         print("weights loaded")
         return DetectModel(model, anchors_table, nclasses, yolo_max_boxes, nms_iou_threshold,
                            nms_score_threshold), class_names
@@ -123,7 +126,7 @@ class Inference:
     def __call__(self, model_config_file, classes_name_file, anchors_file, input_weights_path, image_size,
                  input_data_source, images_dir, tfrecords_dir, batch_size, image_file_path, output_dir, yolo_max_boxes,
                  nms_iou_threshold, nms_score_threshold, bbox_color, font_size, display_result_images=None,
-                 save_model_path=None, weights=None):
+                 save_model_path=None, weights=None, low_latency=None):
         os.makedirs(output_dir, exist_ok=True)
         detections_text_list_outfile = f"{output_dir}/detect.txt"
         try:
@@ -132,7 +135,7 @@ class Inference:
             pass
         out = open(detections_text_list_outfile, "a")
         model, class_names = self.build(model_config_file, classes_name_file, anchors_file, input_weights_path,
-                                        yolo_max_boxes, nms_iou_threshold, nms_score_threshold, weights)
+                                        yolo_max_boxes, nms_iou_threshold, nms_score_threshold, weights, low_latency)
         results = []
         import torch
         from . import runtime

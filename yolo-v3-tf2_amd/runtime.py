@@ -183,6 +183,42 @@ class Net:
         """K order of the fp32 3x3 convs: channels per chunk (multiple of 32) walked chunk-major, 0 tap-major, -1 default."""
         check(self.lib.y3_net_set_k_chunk(self._h, int(channels)), "y3_net_set_k_chunk")
 
+    @staticmethod
+    def _low_latency_arg(on) -> bool:
+        if on is None:
+            return False
+        if isinstance(on, (bool, np.bool_)) or (isinstance(on, (int, np.integer)) and int(on) in (0, 1)):
+            return bool(on)
+        raise Y3Error(f"low_latency must be None, a bool, 0 or 1 (got {on!r})")
+
+    @staticmethod
+    def _split_k_arg(S) -> int:
+        if isinstance(S, (bool, np.bool_)) or not isinstance(S, (int, np.integer)) or not (int(S) in (-1, 1) or 2 <= int(S) <= 16):
+            raise Y3Error(f"split_k must be -1 (heuristic), 1 (off) or an int in 2..16 (got {S!r})")
+        return int(S)
+
+    def set_low_latency(self, on=True):
+        """Low-latency fp32 plan for one to eight images (y3_net_set_low_latency), before plan(): each eligible conv is cut
+        along K into the number of slices y3_choose_split_k gives for the planned batch, summed in a fixed order by a second
+        launch.  Off by default; results differ from the default plan's in the last bits.  None means off."""
+        on = int(self._low_latency_arg(on))
+        check(self.lib.y3_net_set_low_latency(self._h, on), "y3_net_set_low_latency")
+
+    def set_split_k(self, slot: int, S: int):
+        """K slices of conv `slot`: -1 the heuristic (in force only with set_low_latency), 1 off, 2..16 forced.  An
+        ineligible conv (first layer, fused stem, tile 33, a detection head, a plan that is not fp32) or S above the conv's K
+        tiles raises here."""
+        S = self._split_k_arg(S)
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
+            raise Y3Error(f"set_split_k: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
+        check(self.lib.y3_net_set_split_k(self._h, int(slot), S), "y3_net_set_split_k")
+
+    def split_k(self, slot: int) -> int:
+        """K slices in force for conv `slot` after plan() (1: the ordinary launch)."""
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
+            raise Y3Error(f"split_k: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
+        return int(self.lib.y3_net_get_split_k(self._h, int(slot)))
+
     def set_stem_fusion(self, on):
         """conv0 + conv1 (+ the 1x1 conv that follows them) as one kernel (default on; applies when the program starts with
         the Darknet-53 stem and the plan is fp32 or bf16 without keep_activations).  2: conv0 + conv1 only."""

@@ -11,9 +11,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "decode_box.h"
-#include "y3_device.h"
-#include "y3_kernels.h"
+#include "conv_common.h"
 
 namespace y3 {
 
@@ -22,9 +20,9 @@ __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, unsigned voff
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
 }
 
-// DMA: operand tiles filled by direct-to-LDS buffer loads (BK = 64 only): unpadded 128-B rows, 16-B chunk index
-// XOR-swizzled with (row >> 1) & 7 on the source address and on the fragment reads (see conv_f32.hip).
-// DMA with BK = 32 (round 3): 64-B rows, a wave instruction fills 16 rows, chunk index XOR-ed with (row >> 2) & 3.  Half the
+// DMA: operand tiles filled by direct-to-LDS buffer loads: unpadded 128-B rows, 16-B chunk index XOR-swizzled on the source
+// address and on the fragment reads (swizzled_chunk, conv_common.h).
+// DMA with BK = 32 (round 3): 64-B rows, a wave instruction fills 16 rows.  Half the
 // LDS per stage: 128x256 / 256x128 tiles of 8 waves fit TWO workgroups per CU (MINW = 4 caps the registers at 128), so that
 // one workgroup's epilogue (27 % of the bf16 conv stack, profiles/r03_ab_bf16_epilogue_probe.txt) runs beside the other's K loop.
 // M16 (round 3): the same tile on v_mfma_f32_16x16x32_bf16 -- 2TM x 2TN blocks of 16x16 per wave instead of TM x TN of 32x32.
@@ -85,40 +83,23 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
     const unsigned OOB0 = p.src0_bytes, OOB1 = CONCAT ? p.src1_bytes : p.src0_bytes;
 
     const int lrow = tid / LPR;
-    // first bf16 of this lane's 16-B piece inside the K tile (DMA: physical chunk tid & 7 holds logical chunk
-    // (tid & 7) ^ ((row >> 1) & 7))
-    const int lchunk = DMA ? (BK == 64 ? (((tid % LPR) ^ ((lrow >> 1) & 7)) * 8) : (((tid % LPR) ^ ((lrow >> 2) & 3)) * 8)) : (tid % LPR) * 8;
+    // first bf16 of this lane's 16-B piece in the K tile (DMA: the logical chunk landing in physical chunk tid % LPR; BK 32 key written out: measured)
+    const int lchunk = DMA ? (BK == 64 ? swizzled_chunk<8>(lrow, tid % LPR) : (tid % LPR) ^ ((lrow >> 2) & 3)) * 8 : (tid % LPR) * 8;
     int aoff[AP];
     int aoff1[CONCAT ? AP : 1];
     int ahw[AP];
-    const int HoWo = p.Ho * p.Wo;
     const int C1 = p.Cin - p.C0;
-    const int b0 = m0 / HoWo;
-    const int r0 = m0 - b0 * HoWo;
-    const int ho0 = r0 / p.Wo;
-    const int wo0 = r0 - ho0 * p.Wo;
-    const float rcpW = 1.0f / (float)p.Wo, rcpH = 1.0f / (float)p.Ho;
+    const TileOrigin org = tile_origin(p, m0);   // (b, ho, wo) of every row: conv_common.h
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
-        const int m = m0 + i * RP + lrow;
-        const int x = wo0 + i * RP + lrow;
-        const int qx = (int)(((float)x + 0.5f) * rcpW);
-        const int wo = x - qx * p.Wo;
-        const int y = ho0 + qx;
-        const int qy = (int)(((float)y + 0.5f) * rcpH);
-        const int ho = y - qy * p.Ho;
-        const int b = b0 + qy;
-        if (CONCAT) {
-            const int H0 = p.up0 ? (p.H >> 1) : p.H, W0 = p.up0 ? (p.W >> 1) : p.W;
-            const int h0 = p.up0 ? (ho >> 1) : ho, w0 = p.up0 ? (wo >> 1) : wo;
-            aoff[i] = ((b * H0 + h0) * W0 + w0) * p.C0;
-            aoff1[i] = ((b * p.H + ho) * p.W + wo) * C1;
-            ahw[i] = (m < p.M) ? 0 : (int)0x80000000;
-        } else {
+        if constexpr (OUT_F32 && !CONCAT) {   // the head convs: gather_row's offsets written out (through it five prologue instructions moved: measured)
+            const int m = m0 + i * RP + lrow;
+            int b, ho, wo;
+            tile_row(p, org, org.wo0 + i * RP + lrow, b, ho, wo);
             const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
             aoff[i] = ((b * p.H + hi0) * p.W + wi0) * p.Cin;
             ahw[i] = (m < p.M) ? ((hi0 << 16) | (wi0 & 0xffff)) : (int)0x80000000;
-        }
+        } else gather_row<CONCAT, 1>(p, org, m0 + i * RP + lrow, org.wo0 + i * RP + lrow, C1, aoff[i], aoff1[CONCAT ? i : 0], ahw[i]);
     }
     unsigned boff[BP];
 #pragma unroll
@@ -127,7 +108,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
     int tap = 0, c0 = 0;
     unsigned avoff[AP];
     unsigned avoff1[CONCAT ? AP : 1];
-    auto set_tap = [&]() {
+    auto set_tap = [&]() {   // as in conv_f32x3.hip; written out in both: DESIGN.md section 4, "One row per tile"
         if (CONCAT) {
 #pragma unroll
             for (int i = 0; i < AP; ++i) {
@@ -231,8 +212,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
     int foff[KS];  // byte offset of this lane's 16-B piece of k-step s inside its row
 #pragma unroll
     for (int s_ = 0; s_ < KS; ++s_)
-        foff[s_] = M16 ? (((4 * s_ + fh) ^ ((fr >> 1) & 7)) * 16)
-                       : DMA ? (BK == 64 ? (((2 * s_ + fh) ^ ((fr >> 1) & 7)) * 16) : (((2 * s_ + fh) ^ ((fr >> 2) & 3)) * 16)) : s_ * 32;
+        foff[s_] = DMA ? swizzled_chunk<LPR>(fr, (M16 ? 4 : 2) * s_ + fh) * 16 : s_ * 32;
 
     for (int kt = 0; kt < KT; ++kt) {
         const int cur = kt & 1;
@@ -314,7 +294,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
                         for (int e = 0; e < 4; ++e) {
                             float v = acc[2 * i + mb][j][e] * sc[j] + sh[j];
                             if (p.leaky) v = fmaxf(v, 0.1f * v);
-                            S[(16 * mb + 4 * fh + e) * CW + j * 16 + fr] = v;
+                            S[mfma16_row(e, fh, mb) * CW + j * 16 + fr] = v;
                         }
             } else {
 #pragma unroll
@@ -323,7 +303,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
                     for (int e = 0; e < 16; ++e) {
                         float v = acc[i][j][e] * sc[j] + sh[j];
                         if (p.leaky) v = fmaxf(v, 0.1f * v);
-                        S[(4 * fh + (e & 3) + 8 * (e >> 2)) * CW + j * 32 + fr] = v;
+                        S[mfma32_row(e, fh) * CW + j * 32 + fr] = v;
                     }
                 }
             }
@@ -358,7 +338,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
         }
         Y3_STAMP(4);   // thread 0 = wave 0: its own stores issued (not yet retired)
     } else {
-        // ---- fp32 output (head grids, Cout = 255): workgroup-wide fp32 tile, one 32-row block of every wave per pass ----
+        // ---- fp32 output (head grids, Cout = 255): workgroup-wide fp32 tile, one 32-row block of every wave per pass, as in conv_f32x3.hip ----
         constexpr int EROWS = WR * 32;
         float *C = reinterpret_cast<float *>(smem);
 #pragma unroll
@@ -375,14 +355,14 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
                         for (int e = 0; e < 4; ++e) {
                             float v = acc[2 * i + mb][j][e] * sc + sh;
                             if (p.leaky) v = fmaxf(v, 0.1f * v);
-                            C[(wr * 32 + 16 * mb + 4 * fh + e) * CROW + nl] = v;
+                            C[(wr * 32 + 16 * mb + mfma16_row(e, fh)) * CROW + nl] = v;
                         }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         float v = acc[i][j][e] * sc + sh;
                         if (p.leaky) v = fmaxf(v, 0.1f * v);
-                        C[(wr * 32 + 4 * fh + (e & 3) + 8 * (e >> 2)) * CROW + nl] = v;
+                        C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = v;
                     }
                 }
             }
@@ -435,9 +415,9 @@ static hipError_t launch_kb(const ConvArgs &a, hipStream_t s)
 template <int TM, int TN, int WR, int WC, int BK, bool DMA, int MINW, bool M16>
 static hipError_t launch_tb(const ConvArgs &a, bool out_f32, hipStream_t s)
 {
-    if (a.src1)
-        return out_f32 ? launch_kb<TM, TN, WR, WC, BK, true, true, DMA, MINW, M16>(a, s) : launch_kb<TM, TN, WR, WC, BK, true, false, DMA, MINW, M16>(a, s);
-    return out_f32 ? launch_kb<TM, TN, WR, WC, BK, false, true, DMA, MINW, M16>(a, s) : launch_kb<TM, TN, WR, WC, BK, false, false, DMA, MINW, M16>(a, s);
+    return dispatch_concat_out(a.src1 != nullptr, out_f32, [&](auto concat, auto f32) {
+        return launch_kb<TM, TN, WR, WC, BK, decltype(concat)::value, decltype(f32)::value, DMA, MINW, M16>(a, s);
+    });
 }
 
 // One row per tile id: the geometry, read off the template arguments (the kernel is always double buffered), and the launcher of that

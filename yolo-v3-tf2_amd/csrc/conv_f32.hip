@@ -25,8 +25,7 @@
 #include <algorithm>
 #include <type_traits>
 
-#include "y3_device.h"
-#include "y3_kernels.h"
+#include "conv_common.h"
 
 namespace y3 {
 
@@ -44,7 +43,7 @@ __device__ __forceinline__ f32x4 buf_load16(__amdgpu_buffer_rsrc_t r, unsigned v
 // DMA != 0: operand tiles are filled by direct-to-LDS buffer loads (no VGPR round trip, no ds_write): measured with
 // tools/mfma_probe.hip, a 16-B load to VGPRs costs the SIMD ~8-16 cycles of matrix-pipe time and a ds_write_b128 ~13,
 // an LDS-DMA load ~4.  LDS rows are then unpadded 128 B (a wave instruction writes 8 whole rows) and bank conflicts
-// are avoided by an XOR swizzle of the 16-B chunk index applied on the SOURCE address and on the fragment reads.
+// are avoided by an XOR swizzle of the 16-B chunk index (swizzled_chunk) applied on the SOURCE address and on the fragment reads.
 //
 // Removed in round 4 (records under profiles/r01_*, r02_*, code in the history): the timing-only PROBE ablations, the
 // persistent stream-K schedule (neutral on 3x3, -10 % on 1x1 layers: profiles/r02_tile_sweep_f32_streamk_b64_s416.txt) and the
@@ -127,45 +126,17 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
 
     // ---- per-thread gather state -------------------------------------------------------------
     const int lrow = tid >> 3;         // row inside a pass
-    // first float of this lane's 16-B piece inside the 32-float K tile (DMA: the piece that lands in physical chunk
-    // tid & 7 of the row is logical chunk (tid & 7) ^ ((row >> 1) & 7); rows of a pass differ by multiples of 32)
-    const int lchunk = DMA ? (((tid & 7) ^ ((lrow >> 1) & 7)) * 4) : (tid & 7) * 4;
+    // first float of this lane's 16-B piece inside the 32-float K tile (DMA: the logical chunk that lands in physical chunk
+    // tid & 7 of the row; rows of a pass differ by multiples of 32)
+    const int lchunk = DMA ? swizzled_chunk<8>(lrow, tid & 7) * 4 : (tid & 7) * 4;
     int aoff[AP];                      // element offset of (b, hi0, wi0, 0) in src0 (may be negative)
     int aoff1[CONCAT ? AP : 1];        // CONCAT: element offset of (b, ho, wo, 0) in src1
     int ahw[AP];                       // hi0 << 16 | (wi0 & 0xffff); row >= M marked by hi0 = -32768
-    const int HoWo = p.Ho * p.Wo;
     const int C1 = p.Cin - p.C0;
-    // (b, ho, wo) of row m: the tile's first row is decomposed with wave-uniform (scalar) divisions; the lane's
-    // displacement (< BM + Wo) is folded in with an exact small float division -- vector integer division costs
-    // ~40 VALU instructions each, and VALU time is lost MFMA time for every wave on the SIMD.
-    const int b0 = m0 / HoWo;
-    const int r0 = m0 - b0 * HoWo;
-    const int ho0 = r0 / p.Wo;
-    const int wo0 = r0 - ho0 * p.Wo;
-    const float rcpW = 1.0f / (float)p.Wo, rcpH = 1.0f / (float)p.Ho;
+    const TileOrigin org = tile_origin(p, m0);   // (b, ho, wo) of every row: conv_common.h
 #pragma unroll
-    for (int i = 0; i < AP; ++i) {
-        const int m = m0 + i * RP + lrow;
-        const int x = wo0 + i * RP + lrow;                       // < BM + Wo <= 1024: (x+0.5)*rcp is exact
-        const int qx = (int)(((float)x + 0.5f) * rcpW);
-        const int wo = x - qx * p.Wo;
-        const int y = ho0 + qx;
-        const int qy = (int)(((float)y + 0.5f) * rcpH);
-        const int ho = y - qy * p.Ho;
-        const int b = b0 + qy;
-        if (CONCAT) {
-            // 1x1 conv: src0 optionally read through nearest x2 up-sampling
-            const int H0 = p.up0 ? (p.H >> 1) : p.H, W0 = p.up0 ? (p.W >> 1) : p.W;
-            const int h0 = p.up0 ? (ho >> 1) : ho, w0 = p.up0 ? (wo >> 1) : wo;
-            aoff[i] = ((b * H0 + h0) * W0 + w0) * p.C0;
-            aoff1[i] = ((b * p.H + ho) * p.W + wo) * C1;
-            ahw[i] = (m < p.M) ? 0 : (int)0x80000000;
-        } else {
-            const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-            aoff[i] = ((b * p.H + hi0) * p.W + wi0) * p.Cin;
-            ahw[i] = (m < p.M) ? ((hi0 << 16) | (wi0 & 0xffff)) : (int)0x80000000;
-        }
-    }
+    for (int i = 0; i < AP; ++i)
+        gather_row<CONCAT, 1>(p, org, m0 + i * RP + lrow, org.wo0 + i * RP + lrow, C1, aoff[i], aoff1[CONCAT ? i : 0], ahw[i]);
     unsigned boff[BP];  // byte offset of this lane's piece of weight row n, k = 0
 #pragma unroll
     for (int j = 0; j < BP; ++j) boff[j] = (unsigned)((n0 + j * RP + lrow) * p.K + lchunk) * 4u;
@@ -327,7 +298,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     const int b_frag = BM * LDS_ROW + (wc * 32 * TN + fr) * LDS_ROW + (DMA ? 0 : fh * 4);
     int foff[4];  // float offset of this lane's k-chunk q inside its row
 #pragma unroll
-    for (int q = 0; q < 4; ++q) foff[q] = DMA ? ((((2 * q + fh) ^ ((fr >> 1) & 7)) * 4)) : q * 8;
+    for (int q = 0; q < 4; ++q) foff[q] = DMA ? swizzled_chunk<8>(fr, 2 * q + fh) * 4 : q * 8;
 
     // epilogue geometry
     const bool interior = (m0 + BM <= p.M) && (n0 + BN <= p.Cout);
@@ -391,12 +362,12 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
 #pragma unroll
                 for (int e = 0; e < 16; ++e)
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i][j][e]), rss, (int)vbase,
-                                                          ((e & 3) + 8 * (e >> 2)) * slab_row_bytes, 0);
+                                                          mfma32_row(e) * slab_row_bytes, 0);
             }
         }
     } else {
     // ---- epilogue ----------------------------------------------------------------------------
-    // accumulator element e of lane l: column (n) = l & 31, row (m) = (e & 3) + 8*(e >> 2) + 4*(l >> 5).
+    // accumulator element e of lane l: column (n) = l & 31, row (m) = mfma32_row(e, l >> 5).
     // Straight-line: out-of-tile elements get a voffset == num_records, which the buffer bounds check
     // turns into "load 0 / drop the store"; the 16 residual loads of a sub-tile are issued together.
     // interior tiles (the common case): one per-lane voffset per sub-tile, the row displacement of accumulator
@@ -419,7 +390,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
                 if (!interior) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int m = mbase + (e & 3) + 8 * (e >> 2);
+                        const int m = mbase + mfma32_row(e);
                         off[e] = (n_ok && m < p.M) ? (unsigned)(m * p.Cout + n) * 4u : p.dst_bytes;
                     }
                 }
@@ -427,7 +398,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
                 if (RES) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        const int so = ((e & 3) + 8 * (e >> 2)) * row_bytes;
+                        const int so = mfma32_row(e) * row_bytes;
                         r[e] = __builtin_bit_cast(float, interior ? __builtin_amdgcn_raw_buffer_load_b32(rsr, (int)vbase, so, 0)
                                                                   : __builtin_amdgcn_raw_buffer_load_b32(rsr, (int)off[e], 0, 0));
                     }
@@ -446,7 +417,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
 #pragma unroll
                     for (int h = 0; h < 2; ++h) {
                         const int ee = e + h;
-                        const int so = ((ee & 3) + 8 * (ee >> 2)) * row_bytes;
+                        const int so = mfma32_row(ee) * row_bytes;
                         if (interior)
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)v2[h]), rsd, (int)vbase, so, 0);
                         else

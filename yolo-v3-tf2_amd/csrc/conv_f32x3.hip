@@ -17,12 +17,11 @@
 // Same fused op as conv_f32.hip / conv_bf16.hip (reference: core/parse_model.py:27-52,72,134,155-156).
 // Layout: activations [pixel][plane 0..2][C] bf16, weights [CoutPad][plane][K] bf16, head outputs fp32.
 // Operand tiles go HBM/L2 -> LDS by direct-to-LDS buffer loads (one tile per plane), double buffered; LDS rows are
-// 2*BK bytes with the 16-B chunk index XOR-swizzled on the source address and on the fragment reads.
+// 2*BK bytes with the 16-B chunk index XOR-swizzled (swizzled_chunk) on the source address and on the fragment reads.
 #include <algorithm>
 #include <type_traits>
 
-#include "y3_device.h"
-#include "y3_kernels.h"
+#include "conv_common.h"
 
 namespace y3 {
 
@@ -47,8 +46,6 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     constexpr int PLANE_B = (BM + BN) * ROWB;         // one plane of one stage: A rows then B rows
     constexpr int STAGE_B = NPL * PLANE_B;
     constexpr int CROW = BN + 4;
-    // swizzle key (row >> SWZ_SHIFT) & (LPR - 1): 16 consecutive rows then cover all 16 of the 16-B slots of a 256-B bank row
-    constexpr int SWZ_SHIFT = (LPR == 8) ? 1 : (LPR == 4) ? 2 : 3;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x;
@@ -67,39 +64,15 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     const unsigned OOB0 = p.src0_bytes, OOB1 = CONCAT ? p.src1_bytes : p.src0_bytes;
 
     const int lrow = tid / LPR;
-    const int lchunk = (((tid % LPR) ^ ((lrow >> SWZ_SHIFT) & (LPR - 1))) * 8);  // logical chunk landing in physical chunk tid % LPR
+    const int lchunk = swizzled_chunk<LPR>(lrow, tid % LPR) * 8;  // logical chunk landing in physical chunk tid % LPR
     int aoff[AP];
     int aoff1[CONCAT ? AP : 1];
     int ahw[AP];
-    const int HoWo = p.Ho * p.Wo;
     const int C1 = p.Cin - p.C0;
-    const int b0 = m0 / HoWo;
-    const int r0 = m0 - b0 * HoWo;
-    const int ho0 = r0 / p.Wo;
-    const int wo0 = r0 - ho0 * p.Wo;
-    const float rcpW = 1.0f / (float)p.Wo, rcpH = 1.0f / (float)p.Ho;
+    const TileOrigin org = tile_origin(p, m0);   // (b, ho, wo) of every row: conv_common.h
 #pragma unroll
-    for (int i = 0; i < AP; ++i) {
-        const int m = m0 + i * RP + lrow;
-        const int x = wo0 + i * RP + lrow;
-        const int qx = (int)(((float)x + 0.5f) * rcpW);
-        const int wo = x - qx * p.Wo;
-        const int y = ho0 + qx;
-        const int qy = (int)(((float)y + 0.5f) * rcpH);
-        const int ho = y - qy * p.Ho;
-        const int b = b0 + qy;
-        if (CONCAT) {
-            const int H0 = p.up0 ? (p.H >> 1) : p.H, W0 = p.up0 ? (p.W >> 1) : p.W;
-            const int h0 = p.up0 ? (ho >> 1) : ho, w0 = p.up0 ? (wo >> 1) : wo;
-            aoff[i] = ((b * H0 + h0) * W0 + w0) * NPL * p.C0;
-            aoff1[i] = ((b * p.H + ho) * p.W + wo) * NPL * C1;
-            ahw[i] = (m < p.M) ? 0 : (int)0x80000000;
-        } else {
-            const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-            aoff[i] = ((b * p.H + hi0) * p.W + wi0) * NPL * p.Cin;
-            ahw[i] = (m < p.M) ? ((hi0 << 16) | (wi0 & 0xffff)) : (int)0x80000000;
-        }
-    }
+    for (int i = 0; i < AP; ++i)
+        gather_row<CONCAT, NPL>(p, org, m0 + i * RP + lrow, org.wo0 + i * RP + lrow, C1, aoff[i], aoff1[CONCAT ? i : 0], ahw[i]);
     unsigned boff[BP];  // byte offset of plane 0 of weight row n, this lane's chunk
 #pragma unroll
     for (int j = 0; j < BP; ++j) boff[j] = (unsigned)((n0 + j * RP + lrow) * NPL * p.K + lchunk) * 2u;
@@ -107,7 +80,7 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     int tap = 0, c0 = 0;
     unsigned avoff[AP];
     unsigned avoff1[CONCAT ? AP : 1];
-    auto set_tap = [&]() {
+    auto set_tap = [&]() {   // as in conv_bf16.hip; written out in both: DESIGN.md section 4, "One row per tile"
         if (CONCAT) {
 #pragma unroll
             for (int i = 0; i < AP; ++i) {
@@ -181,7 +154,7 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
     const int b_frag = BM * ROWB + (wc * 32 * TN + fr) * ROWB;
     int foff[BK / 16];
 #pragma unroll
-    for (int s_ = 0; s_ < BK / 16; ++s_) foff[s_] = (((2 * s_ + fh) ^ ((fr >> SWZ_SHIFT) & (LPR - 1))) * 16);
+    for (int s_ = 0; s_ < BK / 16; ++s_) foff[s_] = swizzled_chunk<LPR>(fr, 2 * s_ + fh) * 16;
 
     for (int kt = 0; kt < KT; ++kt) {
         const int cur = (STAGES == 2) ? (kt & 1) : 0;
@@ -271,7 +244,7 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
                 float v = NPL == 3 ? acc[0][i][j][e] * sc + sh
                                    : (acc[0][i][j][e] + acc[NACC - 1][i][j][e] * (1.0f / 2048.0f)) + sh;
                 if (p.leaky) v = fmaxf(v, 0.1f * v);
-                C[(wr * 32 + 4 * fh + (e & 3) + 8 * (e >> 2)) * CROW + nl] = v;
+                C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = v;
             }
         }
         __syncthreads();
@@ -326,11 +299,9 @@ static hipError_t launch_kx(const ConvArgs &a, hipStream_t s)
 template <int NPL, int TM, int TN, int WR, int WC, int BK, int STAGES>
 static hipError_t launch_tp(const ConvArgs &a, bool out_f32, hipStream_t s)
 {
-    if (a.src1)
-        return out_f32 ? launch_kx<NPL, TM, TN, WR, WC, BK, true, true, STAGES>(a, s)
-                       : launch_kx<NPL, TM, TN, WR, WC, BK, true, false, STAGES>(a, s);
-    return out_f32 ? launch_kx<NPL, TM, TN, WR, WC, BK, false, true, STAGES>(a, s)
-                   : launch_kx<NPL, TM, TN, WR, WC, BK, false, false, STAGES>(a, s);
+    return dispatch_concat_out(a.src1 != nullptr, out_f32, [&](auto concat, auto f32) {
+        return launch_kx<NPL, TM, TN, WR, WC, BK, decltype(concat)::value, decltype(f32)::value, STAGES>(a, s);
+    });
 }
 
 // One row per tile id, shared by the two plane-split modes: the geometry and, per mode, the launcher of its instantiation (null: not built

@@ -10,9 +10,7 @@
 // k-ordered fp32 sum as in a stand-alone launch: the fused route gives the same bits as y3_net_forward + y3_yolo_decode_scores
 // (tests/test_gpu_parity.py::test_detect_single_call_equals_composed_pipeline).  After the K loop the tile (+ bias) goes to LDS
 // as [64][257] floats; the raw grid is written from there only when the caller wants it (ConvArgs.dst != nullptr).
-#include "decode_box.h"
-#include "y3_device.h"
-#include "y3_kernels.h"
+#include "conv_common.h"
 
 namespace y3 {
 
@@ -37,7 +35,7 @@ __global__ __launch_bounds__(HNT, 2) void conv_head_decode_f32(const ConvArgs p)
     const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
 
     const int lrow = tid >> 3;
-    const int lchunk = (((tid & 7) ^ ((lrow >> 1) & 7)) * 4);   // logical 16-B chunk that lands in physical chunk tid & 7 (see conv_f32.hip)
+    const int lchunk = swizzled_chunk<8>(lrow, tid & 7) * 4;   // logical 16-B chunk that lands in physical chunk tid & 7 (conv_common.h)
     const unsigned m = (unsigned)(m0 + lrow);
     const unsigned avoff = m < (unsigned)p.M ? (m * (unsigned)p.Cin + (unsigned)lchunk) * 4u : p.src0_bytes;   // 1x1: row m is pixel m
     unsigned boff[4];
@@ -69,7 +67,7 @@ __global__ __launch_bounds__(HNT, 2) void conv_head_decode_f32(const ConvArgs p)
     const int b_frag = HBM * HBK + (wc * 64 + fr) * HBK;
     int foff[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) foff[q] = (((2 * q + fh) ^ ((fr >> 1) & 7)) * 4);
+    for (int q = 0; q < 4; ++q) foff[q] = swizzled_chunk<8>(fr, 2 * q + fh) * 4;
 
     // double-buffered K loop (the conv_f32_mfma LDS-DMA two-stage form): K tile kt+1 lands under the MFMAs of K tile kt
     for (int kt = 0; kt < KT; ++kt) {
@@ -92,7 +90,6 @@ __global__ __launch_bounds__(HNT, 2) void conv_head_decode_f32(const ConvArgs p)
     }
 
     // ---- the tile (+ bias; the BN scale of a BN head would be folded into the weights) into LDS: C[pixel][channel] -----------
-    // accumulator element e of lane l: column (n) = l & 31, row (m) = (e & 3) + 8*(e >> 2) + 4*(l >> 5)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int n = wc * 64 + j * 32 + fr;
@@ -101,7 +98,7 @@ __global__ __launch_bounds__(HNT, 2) void conv_head_decode_f32(const ConvArgs p)
         for (int e = 0; e < 16; ++e) {
             float v = acc[j][e] + sh;
             if (p.leaky) v = fmaxf(v, 0.1f * v);
-            smem[(wr * 32 + 4 * fh + (e & 3) + 8 * (e >> 2)) * HCROW + n] = v;
+            smem[(wr * 32 + mfma32_row(e, fh)) * HCROW + n] = v;
         }
     }
     __syncthreads();
@@ -127,10 +124,7 @@ bool conv_head_decode_f32_fits(const ConvArgs &a)
 hipError_t launch_conv_head_decode_f32(const ConvArgs &a, hipStream_t s)
 {
     if (!conv_head_decode_f32_fits(a)) return hipErrorInvalidValue;
-    static LdsAttrOnce attr;
-    if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv_head_decode_f32), (int)HLDS, a.device); e != hipSuccess) return e;
-    hipLaunchKernelGGL(conv_head_decode_f32, dim3((a.M + HBM - 1) / HBM), dim3(HNT), HLDS, s, a);
-    return hipGetLastError();
+    return launch_conv_kernel<conv_head_decode_f32>(a, (a.M + HBM - 1) / HBM, HNT, HLDS, s);
 }
 
 }  // namespace y3

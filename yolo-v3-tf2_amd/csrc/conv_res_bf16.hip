@@ -15,8 +15,7 @@
 //   * per-wave epilogue through a private LDS scratch (no barrier): y = acc * scale + shift, leaky, + shortcut in fp32, ONE
 //     rounding to bf16 (where the oracle's bf16 mode rounds), 16-byte stores; the shortcut rows are requested before the K loop.
 // One barrier per tile.  k order = tap * Cin + c in groups of 16 (v_mfma_f32_32x32x16_bf16), as in conv_bf16_mfma's 32x32x16 tiles.
-#include "y3_device.h"
-#include "y3_kernels.h"
+#include "conv_common.h"
 
 namespace y3 {
 
@@ -187,7 +186,7 @@ __global__ __launch_bounds__(RNT, 2) void conv3x3_res_bf16(const ConvArgs p, int
         for (int e = 0; e < 16; ++e) {
             float v = acc[e] * sc + sh;
             if (p.leaky) v = fmaxf(v, 0.1f * v);
-            S[(4 * fh + (e & 3) + 8 * (e >> 2)) * 32 + fr] = v;
+            S[mfma32_row(e, fh) * 32 + fr] = v;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // lanes read what other lanes of this wave wrote (in-order LDS; pins the compiler)
         __builtin_amdgcn_wave_barrier();

@@ -13,8 +13,7 @@
 //   * per-wave epilogue through a private LDS scratch: + shift, leaky, + shortcut (requested a tile ahead), 16-byte stores.
 // SAME k order and lane grouping as conv_f32_mfma (k = tap * 32 + c; lanes 0-31 / 32-63 take c = 8q + t / 8q + 4 + t of MFMA
 // (q, t)), so the result is bit-identical to the generic tiles (tests/test_gpu_parity.py::test_f32_weight_resident_conv...).
-#include "y3_device.h"
-#include "y3_kernels.h"
+#include "conv_common.h"
 
 namespace y3 {
 
@@ -163,7 +162,7 @@ __global__ __launch_bounds__(FNT, 2) void conv3x3_res_f32(const ConvArgs p, int 
         for (int e = 0; e < 16; ++e) {
             float v = acc[e] + sh;
             if (p.leaky) v = fmaxf(v, 0.1f * v);
-            S[(4 * fh + (e & 3) + 8 * (e >> 2)) * 32 + fr] = v;
+            S[mfma32_row(e, fh) * 32 + fr] = v;
         }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();

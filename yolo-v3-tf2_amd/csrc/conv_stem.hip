@@ -29,8 +29,7 @@
 // conv1 identical to conv_f32_mfma (tap-major, 8q+t / 8q+4+t).  The order is the same for every pixel of every image.
 #include <type_traits>
 
-#include "y3_device.h"
-#include "y3_kernels.h"
+#include "conv_common.h"
 
 namespace y3 {
 
@@ -214,7 +213,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
             for (int k = 0; k < 8; ++k) wa[k] = base + xr[k];
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int xe = (e & 3) + 8 * (e >> 2);
+                const int xe = mfma32_row(e);
                 float v = acc[e] + sh0;
                 if (p.leaky0) v = fmaxf(v, 0.1f * v);
                 const bool zero = zrow || (tx == 0 && xe == 0 && fh == 0);
@@ -244,7 +243,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
             for (int s = 0; s < 14; ++s) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[s], b0[s], acc, 0, 0, 0);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int y = (e & 3) + 8 * (e >> 2) + 4 * fh;        // accumulator row = patch row
+                const int y = mfma32_row(e) + 4 * fh;        // accumulator row = patch row
                 float v = acc[e] + sh0;
                 if (p.leaky0) v = fmaxf(v, 0.1f * v);
                 v = (ty == 0 && y == 0) ? 0.0f : v;
@@ -289,7 +288,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
             const int n = wn * 32 + fr;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int row = (e & 3) + 8 * (e >> 2);               // + 4*fh: pixel (row + 4 fh) >> 4, & 15
+                const int row = mfma32_row(e);               // + 4*fh: pixel (row + 4 fh) >> 4, & 15
                 const int rr = (row >> 4), cc = (row & 15) + 4 * fh;  // row & 15 + 4 fh < 16: rows 0-3, 8-11 (+4) only
                 float v = acc[e] + sh1;
                 if (p.leaky1) v = fmaxf(v, 0.1f * v);
@@ -303,7 +302,7 @@ __global__ __launch_bounds__(stem::NT, 1) void conv_stem_f32(const StemArgs p)
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int cm = (e & 3) + 8 * ((e >> 2) & 1);
-                const int imm = ((e & 3) + 8 * (e >> 2)) * 256;
+                const int imm = mfma32_row(e) * 256;
                 *reinterpret_cast<float *>(const_cast<char *>(lds) + xt[(cm & 3) + 4 * (cm >> 3)] + imm) = acc[e];
             }
             __syncthreads();   // tile complete
@@ -531,7 +530,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             for (int k = 0; k < 4; ++k) wa[k] = base + xr[k];
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int xe = (e & 3) + 8 * (e >> 2);
+                const int xe = mfma32_row(e);
                 float v = acc[e] * sc0 + sh0;
                 if (p.leaky0) v = fmaxf(v, 0.1f * v);
                 const bool zero = zrow || (tx == 0 && xe == 0 && fh == 0);
@@ -551,7 +550,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             const f32x16 acc = conv0_block(PATCH_B + W1_B + ((yl * IW + 32) * 3) * 4);
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int y = (e & 3) + 8 * (e >> 2) + 4 * fh;
+                const int y = mfma32_row(e) + 4 * fh;
                 float v = acc[e] * sc0 + sh0;
                 if (p.leaky0) v = fmaxf(v, 0.1f * v);
                 v = (ty == 0 && y == 0) ? 0.0f : v;
@@ -593,7 +592,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             const int n = wn * 32 + fr;
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                const int m = (e & 3) + 8 * (e >> 2) + 4 * fh;      // pixel of this wave's 32
+                const int m = mfma32_row(e) + 4 * fh;      // pixel of this wave's 32
                 float v = acc[e] * sc1 + sh1;
                 if (p.leaky1) v = fmaxf(v, 0.1f * v);
                 *reinterpret_cast<unsigned short *>(lds + (wm * 32 + m) * 128 + n * 2) = bf16_bits(v);
@@ -629,7 +628,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 }
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
-                    const int m = (e & 3) + 8 * (e >> 2) + 4 * fh;
+                    const int m = mfma32_row(e) + 4 * fh;
                     float v = acc2[e] * sc2 + sh2;
                     if (p.leaky2) v = fmaxf(v, 0.1f * v);
                     *reinterpret_cast<unsigned short *>(lds + OUT2_OFF + (wave * 32 + m) * 64 + fr * 2) = bf16_bits(v);

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/y3.h"
 #include "decode_box.h"
@@ -67,6 +68,14 @@ static hipError_t launch_conv_kernel(const ConvArgs &a, int grid, int threads, s
     if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(KERNEL), (int)lds, a.device); e != hipSuccess) return e;
     hipLaunchKernelGGL(KERNEL, dim3(grid, grid_y), dim3(threads), lds, s, a);
     return hipGetLastError();
+}
+
+// The four instantiations of a 16-bit tile: launch(concat, out_f32) gets the two flags as std::true_type / std::false_type values.
+template <typename LAUNCH>
+static hipError_t dispatch_concat_out(bool concat, bool out_f32, LAUNCH launch)
+{
+    using T = std::true_type; using F = std::false_type;
+    return concat ? (out_f32 ? launch(T{}, T{}) : launch(T{}, F{})) : (out_f32 ? launch(F{}, T{}) : launch(F{}, F{}));
 }
 
 // One tile configuration of an MFMA conv kernel: block tile bm x bn, waves per workgroup, LDS stages, K tile.  Every conv file keeps one

@@ -129,17 +129,26 @@ def test_exception_barrier_turns_a_failed_allocation_into_a_status():
 
 def test_no_extern_c_entry_without_the_barrier():
     """Every y3_status entry point defined in csrc/*.cpp is a function-try-block closed by Y3_CATCH (the barrier is structural, not
-    a convention someone has to remember)."""
-    for f in ("y3_api.cpp", "comm.cpp"):
-        src = open(os.path.join(ROOT, "yolo-v3-tf2_amd", "csrc", f)).read()
+    a convention someone has to remember).  Every csrc/*.cpp with an extern "C" block is walked, and between them they define every function
+    include/y3.h declares as returning y3_status: none sits where this test does not look."""
+    import glob
+    found = set()
+    for path in sorted(glob.glob(os.path.join(ROOT, "yolo-v3-tf2_amd", "csrc", "*.cpp"))):
+        f, src = os.path.basename(path), open(path).read()
+        if 'extern "C" {' not in src:
+            continue
         src = src[src.index('extern "C" {'):]
         defs = re.findall(r"^y3_status (y3_\w+)\((?:[^{};]|\n)*?\)\n(try \{|\{)", src, flags=re.M)
         assert defs, f
         for name, opener in defs:
+            assert name not in found, (f, name)
+            found.add(name)
             if name == "y3_comm_info":      # two stores through caller pointers: nothing in it can throw
                 continue
             assert opener == "try {", (f, name)
             assert 'Y3_CATCH("%s")' % name in src, (f, name)
+    declared = set(re.findall(r"^y3_status (y3_\w+)\(", open(os.path.join(ROOT, "include", "y3.h")).read(), flags=re.M))
+    assert len(declared) > 40 and found == declared, sorted(found ^ declared)
 
 
 def test_tile_built_reports_the_default_tile_set():
@@ -170,7 +179,7 @@ def test_tile_built_reports_the_default_tile_set():
             if t >= 0:
                 named.setdefault(tag, set()).add(t)
     # ... and nothing else is: every tile id the library builds is named by a packaged table or picked by the library's heuristics
-    # (_lib.HEURISTIC_TILES mirrors choose_tile* / the head-decode fallback of csrc/y3_api.cpp) -- no kernel ships that no plan can select
+    # (_lib.HEURISTIC_TILES mirrors choose_tile* / the head-decode fallback of csrc/y3_net.cpp) -- no kernel ships that no plan can select
     for tag, built in (("f32", f32), ("bf16", bf16), ("f32x3", x3), ("f32x2", x2)):
         assert set(built) == named.get(tag, set()) | set(_lib.HEURISTIC_TILES[tag]), (tag, sorted(set(built) ^ (named.get(tag, set()) | set(_lib.HEURISTIC_TILES[tag]))))
 

@@ -6,7 +6,7 @@ pytestmark = pytest.mark.gpu
 
 
 def _output_staged(ops, t):
-    """csrc/y3_api.cpp output_staged: a conv reads net output t again, or a shortcut / first-layer conv writes it."""
+    """csrc/y3_net.cpp output_staged: a conv reads net output t again, or a shortcut / first-layer conv writes it."""
     return any(t in (o.src0, o.src1, o.residual) or (o.dst == t and (o.residual >= 0 or o.cin == 3)) for o in ops)
 
 

@@ -59,7 +59,7 @@ TILES_BF16 = [(128, 128, 4, 64), _Z64, _Z64, (64, 64, 4, 64), (128, 32, 4, 64),
               _Z32, _Z32,
               (128, 64, 8, 32),                                           # 32: weight-resident 3x3 / stride 1, Cin 32 / 64 (csrc/conv_res_bf16.hip)
               _Z64, _Z64, _Z64, _Z64]                                     # 33..36: retired in round 5
-# Tile ids the library's own heuristics can pick (choose_tile* and the head-decode fallback in csrc/y3_api.cpp); with the packaged tuning tables they
+# Tile ids the library's own heuristics can pick (choose_tile* and the head-decode fallback in csrc/y3_net.cpp); with the packaged tuning tables they
 # name every tile the library builds (tests/test_abi.py::test_tile_built_reports_the_default_tile_set)
 HEURISTIC_TILES = {"f32": (8, 10, 11, 33), "bf16": (4, 5, 6, 8, 10, 11, 12, 17, 19, 24, 26, 27, 29, 32), "f32x3": (0, 1, 2, 3), "f32x2": (0, 1, 2, 3, 4, 8)}
 TILE_NAMES = [f"{bm}x{bn}w{w}s{st}" + ("dma" if 26 <= i <= 32 else "") + ("res" if i == 33 else "") for i, (bm, bn, w, st) in enumerate(TILES)]

@@ -19,14 +19,7 @@
 #include <new>
 #include <string>
 
-#include "../../include/y3.h"
-
-namespace y3 {
-int fail_msg(int code, const char *fmt, ...) noexcept;   // y3_api.cpp: fills the thread-local error buffer, returns code
-int on_exception(const char *who) noexcept;              // y3_api.cpp: the exception barrier of the C ABI (rethrows and classifies)
-bool test_fail_alloc() noexcept;                         // y3_api.cpp: Y3_TEST_FAIL_ALLOC=1 (tests)
-}
-#define Y3_CATCH(who) catch (...) { return y3::on_exception(who); }
+#include "y3_host.h"
 
 namespace {
 

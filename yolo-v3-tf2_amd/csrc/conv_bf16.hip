@@ -433,7 +433,7 @@ static hipError_t launch_res(const ConvArgs &a, bool out_f32, hipStream_t s)
 }
 
 // Ids are stable (tuning files refer to them).  The table holds exactly the tiles a plan can select -- a packaged tuning table
-// (tuning/bf16_*.json), the library's heuristic or the head-decode fallback (choose_tile_bf16 / run_slice in y3_api.cpp) names every one of
+// (tuning/bf16_*.json), the library's heuristic or the head-decode fallback (choose_tile_bf16 / refine_bf16 in y3_net.cpp) names every one of
 // them (tests/test_abi.py); the other ids are retired.
 static const TileBf16 kTilesBf16[BF16_TILE_COUNT] = {
     tile<2, 2, 2, 2, 64>(),                  //  0: 128x128

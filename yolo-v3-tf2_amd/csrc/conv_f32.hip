@@ -380,7 +380,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int n = n0 + (wc * TN + j) * 32 + fr;
-            const float sh = p.shift[n];   // the BN scale is folded into the packed weights (y3_api.cpp)
+            const float sh = p.shift[n];   // the BN scale is folded into the packed weights (y3_net.cpp)
             const bool n_ok = n < p.Cout;
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
@@ -506,7 +506,7 @@ static constexpr TileF32 tile() { return {{32 * TM * WR, 32 * TN * WC, WR * WC, 
 static hipError_t launch_res(const ConvArgs &a, hipStream_t s) { return conv_res_f32_fits(a) ? launch_conv_res_f32(a, s) : hipErrorInvalidValue; }
 
 // Ids are stable (tuning files refer to them).  The table holds exactly the tiles a plan can select -- a packaged tuning table
-// (tuning/f32_*.json) or the library's heuristic (choose_tile in y3_api.cpp) names every one of them (tests/test_abi.py).  The other ids of
+// (tuning/f32_*.json) or the library's heuristic (choose_tile in y3_net.cpp) names every one of them (tests/test_abi.py).  The other ids of
 // rounds 1-4 (the register-staged two-stage tiles 0..5, the 8- and 16-wave 128x128 / 256x128 tiles, the register-budget variant 24, the
 // two-stage LDS-DMA tiles 28..30, the timing-only probes 20..22, 25) are retired: y3_tile_built answers 0; the sweeps that retired them
 // are under profiles/.

@@ -320,7 +320,7 @@ static constexpr TileX3 tile()
 }
 
 // Ids are stable (tuning/f32x3_*.json, f32x2_*.json name them).  Only the tiles a plan can select are built (the tuning tables, choose_tile_x3 /
-// choose_tile_x2 in y3_api.cpp; tests/test_abi.py); the two-plane mode takes the schedules that won or came close in the three-plane sweeps.
+// choose_tile_x2 in y3_net.cpp; tests/test_abi.py); the two-plane mode takes the schedules that won or came close in the three-plane sweeps.
 static const TileX3 kTilesX3[X3_TILE_COUNT] = {
     tile<2, 2, 2, 2, 2, P3 | P2>(),   //  0: 128x128, 4 waves
     tile<2, 1, 2, 2, 2, P3 | P2>(),   //  1: 128x64

@@ -1,0 +1,579 @@
+// Running a planned net: one call's Forward, the Slice of it that one lane enqueues, and the entry points that run the conv program --
+// forward, forward + decode, detect, the tensor read-back and the per-conv measurements.
+#include <cstdlib>
+#include <vector>
+
+#include "y3_host.h"
+
+// One call's forward: everything that belongs to the call rather than the net.  Built on the stack by each entry point that
+// runs the conv program; the net itself is read-only while a forward is enqueued.
+struct Forward {
+    const float *images;
+    float *const *grids;                     // [3] caller's fp32 head grids
+    int batch;
+    hipStream_t stream;
+    int lanes;                               // concurrent sub-batches this call may use (the net's y3_net_set_lanes, or 1)
+    const y3::DecodeHead *heads = nullptr;   // [3] in output order: the head convs decode their own tiles into these buffers
+                                             // (per scale: first box index, grid size, anchors) instead of writing grids
+    unsigned long long *clk = nullptr;       // y3_net_measure_sclk*: device buffer the stamped launch(es) write
+    int clk_conv = -1;                       // ... which conv (-2: every conv, 8 words each at clk + 8 conv)
+    float *ms_out = nullptr;                 // y3_net_profile_convs: milliseconds per conv slot (n_ms entries)
+    int n_ms = 0;
+};
+
+// argument checks shared by the entry points that run the conv program; `heads`: the call needs detection heads
+static y3_status check_forward_args(const y3_net *net, bool args_ok, int batch, bool heads, const char *who)
+{
+    if (!net || !args_ok || batch <= 0) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
+    if (heads && net->nclasses <= 0) return fail(Y3_ERR_STATE, "%s: the net was created without detection heads (nclasses = 0)", who);
+    if (!net->height) return fail(Y3_ERR_STATE, "%s: call y3_net_plan first", who);
+    if (batch > net->max_batch) return fail(Y3_ERR_INVALID, "%s: batch %d > planned %d", who, batch, net->max_batch);
+    return Y3_OK;
+}
+
+// The part of a forward one run() step enqueues: images [b0, b0 + nb) of the batch, as lane `lane`, on stream s
+struct Slice {
+    const y3_net *net;
+    const Forward &f;
+    int b0, nb, lane;
+    hipStream_t s;
+    const y3::ConvFamily &fam = *y3::conv_family(net->dtype);
+
+    size_t img_elems(int t) const { return (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels; }
+    // element size: head grids are always fp32; the image batch is fp32 when the Cin = 3 first-layer kernel reads it
+    // (a model whose input feeds an MFMA conv directly hands bf16 in bf16 mode); everything else follows the plan
+    size_t elem_bytes(int t) const
+    {
+        if (net->out_slot[t] >= 0) return 4;
+        if (t == net->input_tensor) return net->tensors[t].channels != 3 ? fam.elem_bytes : 4;
+        return fam.elem_bytes;
+    }
+    size_t bytes(int t) const { return (size_t)nb * img_elems(t) * elem_bytes(t); }
+
+    void *ptr(int t) const
+    {
+        if (t < 0) return nullptr;
+        char *base = nullptr;
+        if (t == net->input_tensor) base = reinterpret_cast<char *>(const_cast<float *>(f.images));
+        else if (net->out_slot[t] >= 0) base = reinterpret_cast<char *>(f.grids[net->out_slot[t]]);
+        if (base) return base + (size_t)b0 * img_elems(t) * elem_bytes(t);
+        // arena tensors share blocks with other (dead) tensors of different per-image size: give every lane its
+        // own 1/lanes region of the block so that concurrent sub-batches never alias
+        char *blk = static_cast<char *>(net->tdev[t]);
+        if (!blk) return nullptr;
+        if (net->dense[t]) return blk + (size_t)b0 * img_elems(t) * elem_bytes(t);
+        // lane regions start at the lane's first image (scaled to the block size), 256-B aligned; blocks carry 4 KiB of slack
+        const size_t off = ((size_t)((double)net->tblock[t] * b0 / f.batch) + 255) & ~(size_t)255;
+        return blk + (lane ? off : 0);
+    }
+
+    // ConvArgs of conv slot `conv` in the plan's mode; a.dec set where it decodes its output in place (fused decode; its grid is then
+    // not written).  The launch decision (y3::choose_conv) adds k_chunk and xcd_gn; nothing else is changed afterwards.
+    y3::ConvArgs conv_args(int conv) const
+    {
+        const ConvSlot &c = net->convs[conv];
+        const y3_conv_desc &d = c.d;
+        y3::ConvArgs a{};
+        a.src0 = ptr(d.src0);
+        a.src1 = ptr(d.src1);
+        a.wpk = c.*fam.w;
+        a.scale = c.scale_dev;
+        a.shift = c.shift_dev;
+        a.residual = ptr(d.residual);
+        a.dst = ptr(d.dst);
+        a.B = nb;
+        a.H = net->height / d.in_div;
+        a.W = net->width / d.in_div;
+        a.Ho = net->height / d.out_div;
+        a.Wo = net->width / d.out_div;
+        a.Cin = d.cin;
+        a.C0 = d.c0;
+        a.Cout = d.cout;
+        a.CoutPad = c.*fam.cout_pad;
+        a.ksize = d.size;
+        a.stride = d.stride;
+        a.pad = (d.size == 3) ? 1 : 0;
+        a.up0 = d.src0_upsample;
+        a.leaky = d.leaky;
+        a.M = nb * a.Ho * a.Wo;
+        a.K = c.K;
+        a.src0_bytes = (unsigned)bytes(d.src0);
+        a.src1_bytes = d.src1 >= 0 ? (unsigned)bytes(d.src1) : 0;
+        a.w_bytes = (unsigned)((size_t)a.CoutPad * c.K * fam.elem_bytes);
+        a.dst_bytes = (unsigned)bytes(d.dst);
+        a.n_cus = net->n_cus;
+        a.device = net->device;
+        a.clk_stamps = !f.clk ? nullptr : f.clk_conv == conv ? f.clk : f.clk_conv == -2 ? f.clk + 8 * conv : nullptr;   // fp32 MFMA kernel and stem only
+        if (f.heads && net->out_slot[d.dst] >= 0) {
+            a.dec = f.heads[net->out_slot[d.dst]];
+            a.dec.boxes += (size_t)b0 * a.dec.N * 4;
+            a.dec.cls += (size_t)b0 * a.dec.N;
+            a.dec.scores += (size_t)b0 * a.dec.N;
+            a.dst = nullptr;
+            a.dst_bytes = 0;
+        }
+        return a;
+    }
+
+    // the fused stem launch (op 1) from conv1's own args: conv0 (op 0) and, with stem_conv2, the 1x1 of op 2 run inside it
+    y3_status launch_stem(const y3::ConvArgs &a1) const
+    {
+        const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[1].index];
+        y3::StemArgs sa{};
+        sa.img = static_cast<const float *>(ptr(c0.d.src0));
+        sa.w0 = c0.*fam.w0_stem;
+        sa.scale0 = c0.scale_dev;
+        sa.shift0 = c0.shift_dev;
+        sa.w1 = c1.*fam.w;
+        sa.scale1 = c1.scale_dev;
+        sa.shift1 = c1.shift_dev;
+        sa.dst = a1.dst;
+        sa.B = nb;
+        sa.H = net->height;
+        sa.W = net->width;
+        sa.leaky0 = c0.d.leaky;
+        sa.leaky1 = c1.d.leaky;
+        sa.img_bytes = (unsigned)bytes(c0.d.src0);
+        sa.dst_bytes = a1.dst_bytes;
+        sa.device = net->device;
+        sa.n_cus = net->n_cus;
+        sa.clk_stamps = a1.clk_stamps;
+        if (net->stem_conv2) {
+            const ConvSlot &c2 = net->convs[net->ops[2].index];
+            sa.w2 = c2.*fam.w;
+            sa.scale2 = c2.scale_dev;
+            sa.shift2 = c2.shift_dev;
+            sa.dst2 = ptr(c2.d.dst);
+            sa.leaky2 = c2.d.leaky;
+            sa.dst2_bytes = (unsigned)bytes(c2.d.dst);
+            if (!sa.dst2) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", net->ops[2].index);
+        }
+        hipError_t e = fam.launch_stem(sa, s);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "conv %d launch: %s", net->ops[1].index, hipGetErrorString(e));
+        return Y3_OK;
+    }
+
+    // launch conv op oi as y3::choose_conv decided
+    y3_status launch_conv(int oi, const y3::ConvArgs &a, const y3::ConvChoice &ch) const
+    {
+        const int conv = net->ops[oi].index;
+        const ConvSlot &c = net->convs[conv];
+        hipError_t e;
+        switch (ch.kind) {
+            case y3::ConvKind::Stem: return launch_stem(a);
+            case y3::ConvKind::First: e = y3::launch_conv_first(a, static_cast<const float *>(c.w_dev), net->dtype, s); break;
+            case y3::ConvKind::HeadDecodeF32: e = y3::launch_conv_head_decode_f32(a, s); break;
+            case y3::ConvKind::SplitK:
+                if (lane >= net->split_ws_lanes) return fail(Y3_ERR_STATE, "conv %d: no split-K workspace for lane %d", conv, lane);
+                e = y3::launch_conv_f32_split(a, ch.tile, ch.split_k, static_cast<char *>(net->split_ws) + (size_t)lane * net->split_ws_lane,
+                                              net->split_ws_lane, s);
+                break;
+            default:   // Mfma; out_f32 (bf16 / plane-split plans): the launch stores the caller's fp32 grid itself
+                e = fam.launch(a, ch.tile, net->out_slot[c.d.dst] >= 0, s);
+        }
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "conv %d launch: %s", conv, hipGetErrorString(e));
+        return Y3_OK;
+    }
+
+    y3_status run_aux(int index) const
+    {
+        if (net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
+        const y3_aux_desc &x = net->aux[index];
+        auto p = [&](int t) { return static_cast<float *>(ptr(t)); };
+        const int sh = rows(net, x.dst), sw = cols(net, x.dst);
+        const int C = net->tensors[x.dst].channels;
+        hipError_t e = hipSuccess;
+        if (x.kind == Y3_AUX_ADD)
+            e = y3::launch_add(p(x.src0), p(x.src1), p(x.dst), (size_t)nb * sh * sw * C, s);
+        else if (x.kind == Y3_AUX_UPSAMPLE2X)
+            e = y3::launch_upsample2x(p(x.src0), nb, sh / 2, sw / 2, C, p(x.dst), s);
+        else if (x.kind == Y3_AUX_CONCAT)
+            e = y3::launch_concat(p(x.src0), net->tensors[x.src0].channels, p(x.src1), net->tensors[x.src1].channels, (size_t)nb * sh * sw, p(x.dst), s);
+        else
+            return fail(Y3_ERR_INVALID, "unknown aux op kind %d", x.kind);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d launch: %s", index, hipGetErrorString(e));
+        return Y3_OK;
+    }
+
+    // Enqueue ops [op_begin, op_end) of the op list; the segment that ends the list also converts the staged outputs to fp32.
+    y3_status run(int op_begin, int op_end) const
+    {
+        hipEvent_t ev0 = nullptr, ev1 = nullptr;
+        if (f.ms_out) {
+            HIP_TRY(hipEventCreate(&ev0));
+            HIP_TRY(hipEventCreate(&ev1));
+        }
+        for (int oi = op_begin; oi < op_end; ++oi) {
+            const Op &o = net->ops[oi];
+            if (o.kind != 0) {
+                if (y3_status st = run_aux(o.index); st != Y3_OK) return st;
+                continue;
+            }
+            y3::ConvArgs a = conv_args(o.index);
+            if (!a.src0 || (!a.dst && !a.dec.boxes)) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", o.index);
+            const y3::ConvChoice ch = y3::choose_conv(net, oi, a);
+            a.k_chunk = ch.k_chunk;
+            a.xcd_gn = ch.xcd_gn;
+            if (ch.kind == y3::ConvKind::InStem) {   // runs inside conv1's launch (fused stem)
+                if (f.ms_out && o.index < f.n_ms) f.ms_out[o.index] = 0.0f;
+                continue;
+            }
+            if (f.ms_out) HIP_TRY(hipEventRecord(ev0, s));
+            if (y3_status st = launch_conv(oi, a, ch); st != Y3_OK) return st;
+            if (f.ms_out) {
+                HIP_TRY(hipEventRecord(ev1, s));
+                HIP_TRY(hipEventSynchronize(ev1));
+                float ms = 0;
+                HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+                if (o.index < f.n_ms) f.ms_out[o.index] = ms;
+            }
+        }
+        for (int k = 0; k < 3 && op_end == (int)net->ops.size(); ++k) {
+            const int t = net->outputs[k];
+            if (!net->staged[t]) continue;
+            const size_t npix = (size_t)nb * rows(net, t) * cols(net, t);
+            hipError_t e = y3::launch_to_f32(net->dtype, ptr(t), f.grids[k] + (size_t)b0 * img_elems(t), npix, net->tensors[t].channels, s);
+            if (e != hipSuccess) return fail(Y3_ERR_HIP, "output %d conversion: %s", k, hipGetErrorString(e));
+        }
+        if (f.ms_out) {
+            (void)hipEventDestroy(ev0);
+            (void)hipEventDestroy(ev1);
+        }
+        return Y3_OK;
+    }
+};
+
+static y3_status run(const y3_net *net, const Forward &f)
+{
+    if (y3_status st = check_forward_args(net, f.images && f.grids, f.batch, false, "y3_net_forward"); st != Y3_OK) return st;
+    for (size_t i = 0; i < net->convs.size(); ++i)
+        if (!net->convs[i].loaded) return fail(Y3_ERR_STATE, "y3_net_forward: conv %zu has no weights", i);
+    if (net->dtype == Y3_DTYPE_F32X2)
+        for (size_t i = 0; i < net->convs.size(); ++i)
+            if (!net->convs[i].x2_ok) return fail(Y3_ERR_INVALID, "y3_net_forward: conv %zu has a weight outside the fp16 range of the two-plane mode", i);
+    for (int i = 0; i < 3; ++i)
+        if (!f.grids[i] || ((uintptr_t)f.grids[i] & 15)) return fail(Y3_ERR_INVALID, "y3_net_forward: grid %d null or not 16-byte aligned", i);
+    if ((uintptr_t)f.images & 3) return fail(Y3_ERR_INVALID, "y3_net_forward: images not 4-byte aligned");
+    Y3_ENTER_DEVICE(net);   // launches go to the net's device whatever the caller's current one is; restored on return
+    const hipStream_t s = f.stream;
+    const int batch = f.batch;
+    // Images are independent, so the batch can run as `lanes` sub-batches on forked streams: while one sub-batch's
+    // conv kernel drains (its last workgroups leave CUs under-occupied), the other sub-batch's kernel fills them.
+    int lanes = f.lanes;
+    while (lanes > 1 && batch / lanes < 1) --lanes;
+    // leading segment in chunks small enough for their activations to stay in the 256 MB Infinity Cache between the
+    // conv that writes them and the one that reads them, then the rest of the op list on the whole (sub-)batch
+    const int k_early = f.ms_out ? 0 : net->early_ops;
+    auto run_lane = [&](int b0, int nb, hipStream_t st, int lane) -> y3_status {
+        if (k_early > 0) {
+            for (int c0 = 0; c0 < nb; c0 += net->early_chunk) {
+                const int cn = nb - c0 < net->early_chunk ? nb - c0 : net->early_chunk;
+                y3_status r = Slice{net, f, b0 + c0, cn, lane, st}.run(0, k_early);
+                if (r != Y3_OK) return r;
+            }
+        }
+        return Slice{net, f, b0, nb, lane, st}.run(k_early, (int)net->ops.size());
+    };
+    if (lanes == 1) return run_lane(0, batch, s, 0);
+    if (!net->fork_ev) return fail(Y3_ERR_STATE, "y3_net_forward: no lane streams (y3_net_plan creates them)");
+    HIP_TRY(hipEventRecord(net->fork_ev, s));
+    // equal sub-batches (measured with tools/lanes_sweep.py: weighted 2:3 / 3:4:5 splits were 2-3 % slower)
+    int start[Y3_MAX_LANES + 1];
+    for (int l = 0; l <= lanes; ++l) start[l] = (int)((long long)batch * l / lanes);
+    // lane 0 runs on the caller's stream itself: its first kernel needs no cross-queue signal to start, and the join waits for the other lanes only
+    // (fp32 eager step 31.324 -> 31.218 ms, +0.3 %, every round of three; bf16 graph replay unchanged: profiles/r05_ab_lane0_on_caller_stream.txt)
+    hipStream_t ls[Y3_MAX_LANES];
+    for (int l = 0; l < Y3_MAX_LANES; ++l) ls[l] = l == 0 ? s : net->lane_stream[l];
+    for (int l = 0; l < lanes; ++l)
+        if (start[l + 1] > start[l] && ls[l] != s) HIP_TRY(hipStreamWaitEvent(ls[l], net->fork_ev, 0));
+    if (k_early > 0) {
+        for (int l = 0; l < lanes; ++l) {
+            const int nb = start[l + 1] - start[l];
+            if (nb <= 0) continue;
+            y3_status st = run_lane(start[l], nb, ls[l], l);
+            if (st != Y3_OK) return st;
+        }
+    } else {
+        // op-major enqueue: op k of every lane before op k+1 of any.  Enqueued lane by lane, an eager forward gives lane 0 a
+        // head start of one whole forward's worth of host launch time (0.3 ms; 0.9 ms under a profiler: the per-queue timeline of
+        // tools/timeline_dump.py shows lane 0 four kernels ahead), and a start offset between the lanes only costs
+        // (profiles/r03_ab_lane_stagger.txt).  A captured forward replays with both branches released at once either way.
+        const int n_ops = (int)net->ops.size();
+        // (A start offset between the lanes was measured again in round 5 for the fp32 plan -- lane 1 released 1 / 2 / 4 ops behind lane 0: at most
+        // +0.28 %, inside the process-to-process spread, profiles/r05_ab_f32_lane_stagger.txt; not kept.)
+        for (int oi = 0; oi < n_ops; ++oi)
+            for (int l = 0; l < lanes; ++l) {
+                const int nb = start[l + 1] - start[l];
+                if (nb <= 0) continue;
+                y3_status st = Slice{net, f, start[l], nb, l, ls[l]}.run(oi, oi + 1);
+                if (st != Y3_OK) return st;
+            }
+    }
+    for (int l = 0; l < lanes; ++l) {
+        if (start[l + 1] <= start[l]) continue;
+        if (ls[l] == s) continue;
+        HIP_TRY(hipEventRecord(net->join_ev[l], ls[l]));
+        HIP_TRY(hipStreamWaitEvent(s, net->join_ev[l], 0));
+    }
+    return Y3_OK;
+}
+
+extern "C" {
+
+y3_status y3_net_forward(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], void *stream)
+try {
+    return run(net, {images_dev, grids_dev, batch, (hipStream_t)stream, net ? net->lanes : 1});
+}
+Y3_CATCH("y3_net_forward")
+
+y3_status y3_net_profile_convs(y3_net *net, const float *images_dev, int batch, float *ms_out, int n, void *stream)
+try {
+    if (!net || !ms_out) return fail(Y3_ERR_INVALID, "y3_net_profile_convs: bad argument");
+    // head grids go to scratch owned by this call
+    if (!net->height || batch <= 0) return fail(Y3_ERR_STATE, "y3_net_profile_convs: call y3_net_plan first (and batch > 0)");
+    Y3_ENTER_DEVICE(net);
+    float *g[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; ++i) {
+        const int t = net->outputs[i];
+        hipError_t e = hipMalloc(&g[i], (size_t)batch * rows(net, t) * cols(net, t) * net->tensors[net->outputs[i]].channels * sizeof(float));
+        if (e != hipSuccess) {
+            for (int k = 0; k < i; ++k) (void)hipFree(g[k]);
+            return fail(Y3_ERR_OOM, "y3_net_profile_convs: hipMalloc: %s", hipGetErrorString(e));
+        }
+    }
+    Forward f{images_dev, g, batch, (hipStream_t)stream, 1};   // one lane: each launch is timed on its own
+    f.ms_out = ms_out;
+    f.n_ms = n;
+    y3_status st = run(net, f);
+    (void)hipStreamSynchronize((hipStream_t)stream);
+    for (int i = 0; i < 3; ++i) (void)hipFree(g[i]);
+    return st;
+}
+Y3_CATCH("y3_net_profile_convs")
+
+namespace {
+// can conv slot i of this plan carry the clock stamps?  The fp32 MFMA kernel (fp32 plans) and the fused stem kernel do.
+bool conv_carries_stamps(const y3_net *net, size_t i)
+{
+    const int oi = y3::conv_op(net, (int)i);
+    if (oi < 0) return false;
+    const y3::ConvKind k = y3::choose_conv_planned(net, oi).kind;   // a split launch carries no stamps, nor does a conv inside the stem launch
+    return k == y3::ConvKind::Stem || (k == y3::ConvKind::Mfma && net->dtype == Y3_DTYPE_F32);
+}
+// pick >= 0: that conv, *mhz_out one value; pick == -2: every conv that carries stamps, mhz_out / start_us / end_us arrays of
+// convs.size() entries (0 where a conv left no stamps; times relative to the earliest stamp, from s_memrealtime)
+y3_status measure_sclk_arrays(const y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
+                              int pick, float *mhz_out, double *start_us, double *end_us, void *stream)
+{
+    Y3_ENTER_DEVICE(net);
+    const size_t nconv = net->convs.size();
+    const size_t words = pick == -2 ? 8 * nconv : 8;   // per conv: memtime, realtime at entry; the same after the epilogue; realtime at the entry of workgroup 0
+    std::vector<unsigned long long> host(words, 0ull);
+    unsigned long long *buf = nullptr;
+    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&buf), words * sizeof(unsigned long long)));
+    hipError_t e = hipMemsetAsync(buf, 0, words * sizeof(unsigned long long), (hipStream_t)stream);
+    // the chip's clock follows the load of the last milliseconds: stamp the LAST of `forwards` back-to-back forwards
+    y3_status st = Y3_OK;
+    // one lane: one launch of a stamped conv (concurrent sub-batches would each stamp the same words)
+    Forward f{images_dev, grids_dev, batch, (hipStream_t)stream, 1};
+    for (int i = 0; i < forwards && st == Y3_OK && e == hipSuccess; ++i) {
+        f.clk = (i == forwards - 1) ? buf : nullptr;
+        f.clk_conv = (i == forwards - 1) ? pick : -1;
+        st = run(net, f);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    if (e == hipSuccess) e = hipMemcpy(host.data(), buf, words * sizeof(unsigned long long), hipMemcpyDeviceToHost);
+    (void)hipFree(buf);
+    if (st != Y3_OK) return st;
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_measure_sclk: %s", hipGetErrorString(e));
+    if (pick >= 0) {
+        const double ticks = (double)(host[2] - host[0]), real = (double)(host[3] - host[1]);
+        if (!(real > 0.0) || !(ticks > 0.0)) return fail(Y3_ERR_STATE, "y3_net_measure_sclk: conv %d left no stamps", pick);
+        *mhz_out = (float)(ticks / real * 100.0);   // s_memrealtime counts at 100 MHz
+        return Y3_OK;
+    }
+    // start = entry of the launch's FIRST workgroup (word 4; the stem kernel stamps in workgroup 0 throughout: word 1),
+    // end = after the epilogue of the clock-stamped workgroup (a middle one; the stem: workgroup 0, resident to the end)
+    auto first = [&](size_t c) { return host[8 * c + 4] ? host[8 * c + 4] : host[8 * c + 1]; };
+    unsigned long long t0 = ~0ull;
+    for (size_t c = 0; c < nconv; ++c)
+        if (host[8 * c + 3] > host[8 * c + 1] && first(c) < t0) t0 = first(c);
+    int stamped = 0;
+    for (size_t c = 0; c < nconv; ++c) {
+        const double ticks = (double)(host[8 * c + 2] - host[8 * c]), real = (double)(host[8 * c + 3] - host[8 * c + 1]);
+        const bool ok = host[8 * c + 3] > host[8 * c + 1] && host[8 * c + 2] > host[8 * c];
+        mhz_out[c] = ok ? (float)(ticks / real * 100.0) : 0.0f;
+        if (start_us) start_us[c] = ok ? (double)(first(c) - t0) / 100.0 : 0.0;
+        if (end_us) end_us[c] = ok ? (double)(host[8 * c + 3] - t0) / 100.0 : 0.0;
+        stamped += ok;
+    }
+    if (!stamped) return fail(Y3_ERR_STATE, "y3_net_measure_sclk_all: no launch of this plan left clock stamps (fp32 plan or fused stem needed)");
+    return Y3_OK;
+}
+}  // namespace
+
+y3_status y3_net_measure_sclk_conv(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
+                                   int conv, float *mhz_out, void *stream)
+try {
+    if (!net || !mhz_out || forwards < 1 || conv < 0 || conv >= (int)net->convs.size())
+        return fail(Y3_ERR_INVALID, "y3_net_measure_sclk_conv: bad argument");
+    if (!conv_carries_stamps(net, (size_t)conv))
+        return fail(Y3_ERR_STATE, "y3_net_measure_sclk_conv: the launch of conv %d carries no clock stamps in this plan", conv);
+    return measure_sclk_arrays(net, images_dev, batch, grids_dev, forwards, conv, mhz_out, nullptr, nullptr, stream);
+}
+Y3_CATCH("y3_net_measure_sclk_conv")
+
+y3_status y3_net_measure_sclk(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
+                              float *mhz_out, void *stream)
+try {
+    if (!net || !mhz_out || forwards < 1) return fail(Y3_ERR_INVALID, "y3_net_measure_sclk: bad argument");
+    // the launch that carries the stamps: the conv with the most FLOPs among those whose kernel has them -- the fp32 MFMA
+    // kernel (fp32 plans; a steady-state workgroup of a ~0.8 ms launch) or the fused stem kernel (fp32 and bf16 plans)
+    int pick = -1;
+    double best = 0;
+    for (size_t i = 0; i < net->convs.size(); ++i) {
+        const ConvSlot &c = net->convs[i];
+        if (!conv_carries_stamps(net, i)) continue;
+        const double ho = net->height / c.d.out_div, wo = net->width / c.d.out_div;   // 0 without a plan
+        const double fl = 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * wo;
+        if (fl > best) { best = fl; pick = (int)i; }
+    }
+    if (pick < 0) return fail(Y3_ERR_STATE, "y3_net_measure_sclk: no launch of this plan carries clock stamps (fp32 plan or fused stem needed)");
+    return measure_sclk_arrays(net, images_dev, batch, grids_dev, forwards, pick, mhz_out, nullptr, nullptr, stream);
+}
+Y3_CATCH("y3_net_measure_sclk")
+
+y3_status y3_net_measure_sclk_all(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], int forwards,
+                                  float *mhz_out, double *start_us, double *end_us, void *stream)
+try {
+    if (!net || !mhz_out || forwards < 1) return fail(Y3_ERR_INVALID, "y3_net_measure_sclk_all: bad argument");
+    return measure_sclk_arrays(net, images_dev, batch, grids_dev, forwards, -2, mhz_out, start_us, end_us, stream);
+}
+Y3_CATCH("y3_net_measure_sclk_all")
+
+y3_status y3_net_read_tensor(y3_net *net, int t, int batch, float *dst_dev, size_t *n_elems, void *stream)
+try {
+    if (!net || t < 0 || t >= (int)net->tensors.size() || !net->height)
+        return fail(Y3_ERR_INVALID, "y3_net_read_tensor: bad argument");
+    const size_t npix = (size_t)batch * rows(net, t) * cols(net, t);
+    const size_t n = npix * net->tensors[t].channels;
+    if (n_elems) *n_elems = n;
+    if (!dst_dev) return Y3_OK;
+    if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
+    Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
+    hipError_t e = y3::launch_to_f32(net->dtype, net->tdev[t], dst_dev, npix, net->tensors[t].channels, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_read_tensor")
+
+// ------------------------------------------------------------------------------------------ forward + decode
+namespace {
+// Can the three heads decode in place?  Each output must come from a 1x1 / stride-1 single-source conv without shortcut whose
+// 3 * (5 + nc) channels fit one 256-wide tile, written straight to the caller-visible grid (not staged), in an fp32 or bf16
+// plan.  Y3_FUSE_DECODE=0 (tools: A/B against the composed route) switches the fusion off.
+bool heads_can_decode(const y3_net *net)
+{
+    static const bool off = [] { const char *e = getenv("Y3_FUSE_DECODE"); return e && e[0] == '0'; }();
+    if (off || net->nclasses <= 0 || (net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16)) return false;
+    if (net->keep_all || net->early_ops > 0 || 3 * (5 + net->nclasses) > 256) return false;
+    for (int k = 0; k < 3; ++k) {
+        const int t = net->outputs[k];
+        if (net->staged[t]) return false;
+        int producers = 0;
+        for (const ConvSlot &c : net->convs) {
+            if (c.d.dst != t) continue;
+            ++producers;
+            if (c.first_layer || c.d.size != 1 || c.d.stride != 1 || c.d.src1 >= 0 || c.d.residual >= 0 || c.d.cin % 64 ||
+                c.d.cout != 3 * (5 + net->nclasses) || c.cout_pad != 256)
+                return false;
+        }
+        if (producers != 1) return false;
+        // the fused route does not write the grid: nobody inside the net may read it (fp32 plans never stage an output, so a
+        // consumer would read the caller's buffer -- on this route uninitialised scratch)
+        for (const ConvSlot &c : net->convs)
+            if (c.d.src0 == t || c.d.src1 == t || c.d.residual == t) return false;
+        for (const y3_aux_desc &x : net->aux)
+            if (x.dst == t || x.src0 == t || x.src1 == t) return false;
+    }
+    return true;
+}
+// y3_net_forward_decode on the net's device, with the scratch layout L of this batch
+y3_status forward_decode(const y3_net *net, const y3::DetectLayout &L, const float *images_dev, int batch, const float *anchors_host,
+                         float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream)
+{
+    char *b = static_cast<char *>(net->det_buf);
+    float *grids[3] = {reinterpret_cast<float *>(b + L.grid[0]), reinterpret_cast<float *>(b + L.grid[1]), reinterpret_cast<float *>(b + L.grid[2])};
+    Forward f{images_dev, grids, batch, (hipStream_t)stream, net->lanes};
+    if (!heads_can_decode(net)) {   // composed route: grids into the scratch, then the stand-alone decode
+        if (y3_status st = run(net, f); st != Y3_OK) return st;
+        return y3::decode_scores_hw("y3_yolo_decode_scores", grids, L.gs, batch, net->nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+    }
+    y3::DecodeHead heads[3];
+    int first = 0;
+    for (int k = 0; k < 3; ++k) {
+        heads[k].boxes = bboxes_dev;
+        heads[k].cls = class_idx_dev;
+        heads[k].scores = scores_dev;
+        heads[k].gh = L.gs[k][0];
+        heads[k].gw = L.gs[k][1];
+        heads[k].off = first;
+        heads[k].N = (int)L.n_boxes;
+        heads[k].nc = net->nclasses;
+        for (int a = 0; a < 3; ++a) {
+            heads[k].anchors[a][0] = anchors_host[(k * 3 + a) * 2 + 0];
+            heads[k].anchors[a][1] = anchors_host[(k * 3 + a) * 2 + 1];
+        }
+        first += L.gs[k][0] * L.gs[k][1] * 3;
+    }
+    f.heads = heads;
+    return run(net, f);
+}
+}  // namespace
+
+y3_status y3_net_forward_decode(y3_net *net, const float *images_dev, int batch, const float *anchors_host, float *bboxes_dev,
+                                int64_t *class_idx_dev, float *scores_dev, void *stream)
+try {
+    y3_status st = check_forward_args(net, images_dev && anchors_host && bboxes_dev && class_idx_dev && scores_dev, batch, true,
+                                      "y3_net_forward_decode");
+    if (st != Y3_OK) return st;
+    if ((uintptr_t)bboxes_dev & 15) return fail(Y3_ERR_INVALID, "y3_net_forward_decode: bboxes not 16-byte aligned");
+    Y3_ENTER_DEVICE(net);
+    const y3::DetectLayout L = y3::detect_layout(net, batch);
+    if (!net->det_buf || net->det_bytes < L.total)
+        return fail(Y3_ERR_STATE, "y3_net_forward_decode: detect scratch not planned (y3_net_plan allocates it)");
+    return forward_decode(net, L, images_dev, batch, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+}
+Y3_CATCH("y3_net_forward_decode")
+
+// ------------------------------------------------------------------------------------------ whole pipeline
+y3_status y3_net_detect(y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
+                        float iou_threshold, float score_threshold, void *packed_dev, int32_t *num_valid_dev,
+                        void *stream)
+try {
+    y3_status st = check_forward_args(net, images_dev && anchors_host && packed_dev && num_valid_dev, batch, true, "y3_net_detect");
+    if (st != Y3_OK) return st;
+    if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES)
+        return fail(Y3_ERR_INVALID, "y3_net_detect: max_boxes must be in [1,%d]", Y3_MAX_OUTPUT_BOXES);
+    Y3_ENTER_DEVICE(net);   // the decode / NMS / pack launches below go to the net's device; the caller's current device is restored on return
+    const y3::DetectLayout L = y3::detect_layout(net, batch);
+    if (!net->det_buf || net->det_bytes < L.total)
+        return fail(Y3_ERR_STATE, "y3_net_detect: detect scratch not planned (y3_net_plan allocates it)");
+    const int n = (int)L.n_boxes;
+    char *b = static_cast<char *>(net->det_buf);
+    float *boxes = reinterpret_cast<float *>(b + L.boxes), *scores = reinterpret_cast<float *>(b + L.scores);
+    int64_t *cls = reinterpret_cast<int64_t *>(b + L.cls);
+    int32_t *sel = reinterpret_cast<int32_t *>(b + L.sel);
+    // conv program with the head convs decoding their own tiles (grids neither written nor read back) where the graph allows it.
+    // (Round 5 ran NMS + pack per lane, on each lane's stream behind its last conv: bit-identical and 0.2 % slower under graph replay -- the NMS
+    // workgroups take CUs from the other lane's last convs; profiles/r05_ab_bf16_lane_nms.txt.  Batch-wide launches behind the join again.)
+    st = forward_decode(net, L, images_dev, batch, anchors_host, boxes, cls, scores, stream);
+    if (st != Y3_OK) return st;
+    st = y3_nms_padded(boxes, scores, batch, n, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
+                       b + L.nms_ws, L.total - L.nms_ws, stream);
+    if (st != Y3_OK) return st;
+    return y3_pack_detections(boxes, cls, scores, sel, num_valid_dev, batch, n, max_boxes, packed_dev, stream);
+}
+Y3_CATCH("y3_net_detect")
+
+}  // extern "C"

@@ -1,0 +1,197 @@
+// Host-only internals of liby3hip.so, shared by y3_net.cpp, y3_plan.cpp, y3_forward.cpp, y3_ops.cpp and comm.cpp: the error plumbing of
+// the C ABI, the net object, and what crosses those files.  No .hip file includes it (the kernels see y3_kernels.h only).
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <vector>
+
+#include "../../include/y3.h"
+#include "y3_kernels.h"
+
+namespace y3 {
+// record the message as this thread's last error and return `code` (a fixed thread-local buffer: reporting allocates nothing)
+int fail_msg(int code, const char *fmt, ...) noexcept;
+// The exception barrier of the C ABI.  Every extern "C" entry point that can reach an allocation (std::vector, new, std::string)
+// is a function-try-block ending in Y3_CATCH: a C++ exception becomes a status + message instead of crossing the boundary and
+// terminating the host process (a ctypes / cgo / JNI caller has no handler for it).
+int on_exception(const char *who) noexcept;
+// Test hook (tests/test_abi.py): Y3_TEST_FAIL_ALLOC=1 makes the object allocations of y3_net_create / y3_comm_init_rank fail the
+// way operator new does; read on every call so that a test can switch it on and off inside one process.
+bool test_fail_alloc() noexcept;
+}  // namespace y3
+
+#define Y3_CATCH(who) catch (...) { return y3::on_exception(who); }
+
+constexpr auto fail = y3::fail_msg;
+
+#define HIP_TRY(expr)                                                                             \
+    do {                                                                                          \
+        hipError_t e_ = (expr);                                                                   \
+        if (e_ != hipSuccess)                                                                     \
+            return fail(e_ == hipErrorOutOfMemory ? Y3_ERR_OOM : Y3_ERR_HIP, "%s: %s", #expr,     \
+                        hipGetErrorString(e_));                                                   \
+    } while (0)
+
+// Enter the net's device for the duration of a call and give the caller its own current device back on every return path (a
+// process driving several GPUs -- PyTorch with nets on different devices -- must not find its current device changed).
+struct DeviceGuard {
+    int prev = -1;
+    hipError_t err = hipSuccess;
+    explicit DeviceGuard(int dev)
+    {
+        err = hipGetDevice(&prev);
+        if (err == hipSuccess && prev != dev) err = hipSetDevice(dev); else if (err == hipSuccess) prev = -1;
+    }
+    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+    DeviceGuard(const DeviceGuard &) = delete;
+    DeviceGuard &operator=(const DeviceGuard &) = delete;
+};
+#define Y3_ENTER_DEVICE(net_)                                                                      \
+    DeviceGuard dev_guard_((net_)->device);                                                        \
+    if (dev_guard_.err != hipSuccess) return fail(Y3_ERR_HIP, "hipSetDevice(%d): %s", (net_)->device, hipGetErrorString(dev_guard_.err))
+
+struct ConvSlot {
+    y3_conv_desc d{};
+    bool loaded = false;
+    bool first_layer = false;  // Cin == 3 direct kernel
+    int cout_pad = 0;
+    int K = 0;
+    int tile = -1;             // -1: choose by heuristic at plan time
+    int split_req = -1;        // y3_net_set_split_k: -1 the heuristic (low-latency plans only), 1 off, 2..16 forced
+    int split_k = 1;           // K slices in force, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
+    int tile_bf16 = -1;
+    int tile_x3 = -1;
+    int cout_pad64 = 0;        // Cout rounded up to 64 (the three-plane kernel has no 32-wide N tile)
+    void *wx3_dev = nullptr;   // packed [CoutPad64][3 planes][K] bf16 (hi, mid, lo of the fp32 weights)
+    int tile_x2 = -1;
+    bool x2_ok = true;         // false: a BN-scaled weight is outside the fp16 range, the two-plane mode cannot be planned
+    void *wx2_dev = nullptr;   // packed [CoutPad64][2 planes][K] fp16 (h, l' = (w - h) * 2^11 of the BN-scaled weights)
+    void *w_dev = nullptr;     // packed [CoutPad][K] fp32 (or HWIO for the first layer)
+    float *w0stem_dev = nullptr;   // first layer only: [28][Cout] = HWIO rows x BN scale, row 27 zero (fused stem kernel, fp32)
+    float *w0raw_dev = nullptr;    // first layer only: the same without the scale (fused stem kernel, bf16 mode)
+    void *wbf_dev = nullptr;   // same, bf16 (not for the first layer)
+    float *scale_dev = nullptr;
+    float *shift_dev = nullptr;
+};
+
+struct Op {
+    int kind;  // 0 conv, 1 aux
+    int index;
+};
+
+constexpr int Y3_MAX_LANES = 4;
+constexpr int Y3_MAX_OUTPUT_BOXES = 1024;   // upper bound of max_output_size (y3_nms_padded) the detect scratch is sized for
+
+struct y3_net {
+    int device = 0;
+    int n_cus = 0;                 // compute units of `device`, read once by y3_net_plan (grids of the persistent kernels)
+    std::vector<y3_tensor_desc> tensors;
+    std::vector<Op> ops;
+    std::vector<ConvSlot> convs;
+    std::vector<y3_aux_desc> aux;
+    int input_tensor = 0;
+    int outputs[3] = {0, 0, 0};
+    int nclasses = 0;
+    // plan
+    int max_batch = 0, height = 0, width = 0, dtype = Y3_DTYPE_F32;   // the planned canvas: height x width (0: no plan)
+    int keep_all = 0;              // 1: no buffer reuse, every intermediate stays readable after a forward
+    int lanes = 1;                 // sub-batches run concurrently on forked streams (y3_net_set_lanes)
+    int early_convs = 0;           // y3_net_set_early_chunk: the first early_convs convs run early_chunk images at a time
+    int early_chunk = 0;
+    int early_ops = 0;             // (at plan time) number of leading ops that form the chunked segment
+    std::vector<char> dense;       // tensor written by the chunked segment: own block, image i at i * image_bytes
+    // (non-fp32 modes) output tensors that another op reads, or that a residual / first-layer conv writes: produced in
+    // the arena in the mode's own format and converted into the caller's fp32 buffer at the end of the forward
+    std::vector<char> staged;
+    // per tensor: which of the caller's three fp32 grids a launch writes it into (a net output that is not staged), -1 for every
+    // other tensor (all of them before the first plan)
+    std::vector<signed char> out_slot;
+    // y3_net_detect scratch (grids, decoded boxes / classes / scores, selected indices, NMS workspace): allocated by
+    // y3_net_plan for max_batch images and Y3_MAX_OUTPUT_BOXES rows, so y3_net_detect itself only enqueues work
+    void *det_buf = nullptr;
+    size_t det_bytes = 0;
+    int stem_mode = 1;             // y3_net_set_stem_fusion: 1 = conv0 + conv1 (+ the 1x1 after them) as one kernel when the graph allows it; 2 = conv0 + conv1 only
+    bool stem_mode_set = false;    // y3_net_set_stem_fusion was called (the Y3_STEM_MODE tool override then stays out)
+    bool stem_fused = false;       // (at plan time) the first two convs run as the fused stem kernel
+    bool stem_conv2 = false;       // ... and the 1x1 conv that follows them (64 -> 32) runs inside it as well (fp32 and bf16 plans)
+    int xcd_mode = 1;              // y3_net_set_xcd_mode: 0 contiguous tile runs per XCD, 1 XCD-blocked order chosen per conv
+    bool low_latency_set = false;  // y3_net_set_low_latency was called (the Y3_LOW_LATENCY tool override then stays out)
+    bool low_latency = false;      // y3_net_set_low_latency: every eligible fp32 conv takes y3_choose_split_k
+    void *split_ws = nullptr;      // split-K slabs: split_ws_lanes regions of split_ws_lane bytes, one per lane (lanes run concurrently)
+    size_t split_ws_lane = 0;
+    int split_ws_lanes = 0;
+    int k_chunk = -1;              // y3_net_set_k_chunk: fp32 3x3 convs walk K chunk-major, this many input channels per chunk; 0 tap-major; -1 per-conv default
+    hipEvent_t fork_ev = nullptr;
+    hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
+    hipEvent_t join_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    std::vector<void *> tdev;      // arena pointer per tensor (nullptr: not materialised / external)
+    std::vector<size_t> tbytes;    // bytes at max_batch
+    std::vector<size_t> tblock;    // size of the arena block the tensor lives in
+    std::vector<void *> blocks;    // distinct hipMalloc'ed blocks
+};
+
+inline int rows(const y3_net *n, int t) { return n->height / n->tensors[t].div; }
+inline int cols(const y3_net *n, int t) { return n->width / n->tensors[t].div; }
+inline bool is_output(const y3_net *net, int t) { return t == net->outputs[0] || t == net->outputs[1] || t == net->outputs[2]; }
+
+namespace y3 {
+
+// One conv family per plan mode (Y3_DTYPE_*): its tile table (y3_tile_built), the tile a caller forced on a conv, the texts with which
+// its setter refuses one (y3_net_set_tile*), and what a launch of the mode takes: weights, chooser, launcher.
+struct ConvChoice;
+struct ConvFamily {
+    int count;                                     // tile ids are [0, count)
+    TileInfo (*info)(int);
+    bool (*built)(int);
+    int ConvSlot::*tile;                           // forced tile, -1: the chooser's
+    int ConvSlot::*cout_pad;                       // padded Cout of the mode's packed weights
+    const char *bad, *retired, *misfit;            // refusals: bad argument, retired id (format: the id), tile does not fit the conv
+    int resident;                                  // id of the weight-resident kernel, -1: none
+    y3_status (*resident_rule)(const y3_net *, const ConvSlot &, int slot);   // its own shape rule
+    void *ConvSlot::*w;                            // packed weights [CoutPad][K] values of the mode
+    // bytes per value of the mode, in the arena and in a packed weight row (K of them): fp32, bf16, three bf16 planes, two fp16 planes
+    int elem_bytes;
+    // M: rows of the call; M_plan: rows of the planned batch; arena_out: the launch stores the mode's own format, not an fp32 grid
+    int (*choose)(const ConvSlot &, long long M, long long M_plan, bool arena_out);
+    hipError_t (*launch)(const ConvArgs &, int tile, bool out_f32, hipStream_t);
+    // what the mode adds to the choice once its tile is known (null: nothing)
+    void (*refine)(const y3_net *, const ConvSlot &, const ConvArgs &, ConvChoice &);
+    // fused stem kernel (null: the mode has none) and the first layer's 28-row weights it reads
+    hipError_t (*launch_stem)(const StemArgs &, hipStream_t);
+    float *ConvSlot::*w0_stem;
+};
+const ConvFamily *conv_family(int dtype);   // null: no such mode
+
+// What conv op `oi` launches for the rows of one call.  InStem: nothing of its own, it runs inside the Stem launch of op 1.
+enum class ConvKind { First, Stem, InStem, HeadDecodeF32, Mfma, SplitK };
+struct ConvChoice {
+    ConvKind kind;
+    int tile;      // Mfma, SplitK: tile id of the family's table
+    int k_chunk;   // ConvArgs::k_chunk
+    int xcd_gn;    // ConvArgs::xcd_gn
+    int split_k;   // SplitK: slices
+};
+// The one launch decision.  `a`: the slice's ConvArgs (rows of the call, byte sizes, a.dec set when the conv decodes its own tiles).
+ConvChoice choose_conv(const y3_net *net, int oi, const ConvArgs &a);
+ConvChoice choose_conv_planned(const y3_net *net, int oi);   // ... for max_batch images, as a plain forward launches it
+int conv_op(const y3_net *net, int slot);                    // the op that runs conv `slot`, -1: none
+
+bool stem_applicable(const y3_net *net);
+bool stem_conv2_applicable(const y3_net *net);
+bool output_staged(const y3_net *net, int t);
+y3_status resolve_splits(y3_net *net);
+void free_plan(y3_net *net);
+
+// y3_net_detect scratch for `batch` images: grid sizes {gh, gw}, boxes per image, byte offsets of the parts and their total
+struct DetectLayout {
+    int32_t gs[3][2];
+    size_t n_boxes;
+    size_t grid[3], boxes, cls, scores, sel, nms_ws, total;
+};
+DetectLayout detect_layout(const y3_net *net, int batch);
+
+// y3_yolo_decode_scores_hw under the caller's name `who`
+y3_status decode_scores_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+                           const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream);
+
+}  // namespace y3

@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI layer (y3_api.cpp) and the gfx950 kernels.
+// Internal launch interface between the C-ABI layer (y3_net.cpp, y3_plan.cpp, y3_forward.cpp, y3_ops.cpp) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

@@ -1,0 +1,806 @@
+// The net object of liby3hip.so behind the C ABI (include/y3.h): error buffer and exception barrier, create / destroy, weight packing,
+// the setters, the conv families with their tile heuristics, the launch decision (choose_conv) and the split-K resolution.
+#include <algorithm>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <exception>
+#include <memory>
+#include <new>
+
+#include "y3_host.h"
+
+namespace {
+
+// The last error of this thread: a fixed buffer, so that reporting a failure allocates nothing and cannot itself throw
+// (include/y3.h: no entry point throws or aborts -- not even while it reports that the host ran out of memory).
+thread_local char g_err[512] = "";
+
+}  // namespace
+
+namespace y3 {   // declared, with what they are for, in y3_host.h
+int fail_msg(int code, const char *fmt, ...) noexcept
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+int on_exception(const char *who) noexcept
+{
+    try {
+        throw;
+    } catch (const std::bad_alloc &) {
+        return fail_msg(Y3_ERR_OOM, "%s: out of host memory (std::bad_alloc)", who);
+    } catch (const std::exception &e) {
+        return fail_msg(Y3_ERR_INTERNAL, "%s: C++ exception: %s", who, e.what());
+    } catch (...) {
+        return fail_msg(Y3_ERR_INTERNAL, "%s: unknown C++ exception", who);
+    }
+}
+
+bool test_fail_alloc() noexcept
+{
+    const char *e = getenv("Y3_TEST_FAIL_ALLOC");
+    return e && e[0] == '1';
+}
+
+}  // namespace y3
+
+namespace {
+
+unsigned short f32_to_bf16_rne(float f)
+{
+    unsigned u;
+    memcpy(&u, &f, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);  // NaN stays NaN
+    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+float bf16_to_f32(unsigned short h)
+{
+    unsigned u = (unsigned)h << 16;
+    float f;
+    memcpy(&f, &u, 4);
+    return f;
+}
+
+// fp32 -> fp16 bits, round to nearest even, subnormals kept, >= 65520 -> inf
+unsigned short f32_to_f16_rne(float f)
+{
+    unsigned x;
+    memcpy(&x, &f, 4);
+    const unsigned short sign = (unsigned short)((x >> 16) & 0x8000u);
+    x &= 0x7fffffffu;
+    if (x > 0x7f800000u) return (unsigned short)(sign | 0x7e00u);
+    if (x >= 0x477ff000u) return (unsigned short)(sign | 0x7c00u);
+    if (x < 0x38800000u) {   // below 2^-14: a multiple of 2^-24
+        float a;
+        memcpy(&a, &x, 4);
+        return (unsigned short)(sign | (unsigned short)lrintf(a * 16777216.0f));
+    }
+    unsigned h = (((x >> 23) - 112u) << 10) | ((x & 0x7fffffu) >> 13);
+    const unsigned rem = x & 0x1fffu;
+    if (rem > 0x1000u || (rem == 0x1000u && (h & 1u))) ++h;
+    return (unsigned short)(sign | h);
+}
+
+float f16_to_f32(unsigned short h)
+{
+    const int e = (h >> 10) & 31, m = h & 0x3ff;
+    float v;
+    if (e == 0)
+        v = ldexpf((float)m, -24);
+    else if (e == 31)
+        v = m ? NAN : INFINITY;
+    else
+        v = ldexpf((float)(1024 + m), e - 25);
+    return (h & 0x8000) ? -v : v;
+}
+
+// ---- weight packing (y3_net_set_conv_weights): HWIO w is [K][Cout], k = tap*Cin + c
+
+// [CoutPad][K], rows past Cout zero; scale (or null): folded into each output channel's row
+std::vector<float> pack_rows(const float *w, int K, int cout, int cout_pad, const float *scale)
+{
+    std::vector<float> pk((size_t)cout_pad * K, 0.0f);
+    for (int k = 0; k < K; ++k)
+        for (int n = 0; n < cout; ++n) pk[(size_t)n * K + k] = scale ? w[(size_t)k * cout + n] * scale[n] : w[(size_t)k * cout + n];
+    return pk;
+}
+
+// first layer, fused stem kernel: conv0 on the matrix cores wants K = 27 padded to 28 rows of [Cout]; scale (or null) folded in
+std::vector<float> pack_stem28(const float *w, int K, int cout, const float *scale)
+{
+    std::vector<float> w28((size_t)28 * cout, 0.0f);
+    for (int k = 0; k < K; ++k)
+        for (int n = 0; n < cout; ++n) w28[(size_t)k * cout + n] = scale ? w[(size_t)k * cout + n] * scale[n] : w[(size_t)k * cout + n];
+    return w28;
+}
+
+// three bf16 planes: x = hi + mid + lo exactly
+void split_bf16x3(float x, unsigned short v[3])
+{
+    v[0] = f32_to_bf16_rne(x);
+    const float r1 = x - bf16_to_f32(v[0]);
+    v[1] = f32_to_bf16_rne(r1);
+    v[2] = f32_to_bf16_rne(r1 - bf16_to_f32(v[1]));
+}
+
+// two fp16 planes: w = h + l' * 2^-11 (up to 2^-22 |w|) while |w| < 65504
+void split_f16x2(float x, unsigned short v[2])
+{
+    v[0] = f32_to_f16_rne(x);
+    v[1] = f32_to_f16_rne((x - f16_to_f32(v[0])) * 2048.0f);
+}
+
+// [rows][P][K] planes of [CoutPad][K] weights (rows past Cout zero), split(x, v) giving the P plane values of x
+template <int P>
+std::vector<unsigned short> pack_planes(const std::vector<float> &pk, int K, int cout, int rows, void (*split)(float, unsigned short *))
+{
+    std::vector<unsigned short> px((size_t)rows * P * K, 0);
+    unsigned short v[P];
+    for (int n = 0; n < cout; ++n)
+        for (int k = 0; k < K; ++k) {
+            split(pk[(size_t)n * K + k], v);
+            for (int p = 0; p < P; ++p) px[((size_t)n * P + p) * K + k] = v[p];
+        }
+    return px;
+}
+
+// hipMalloc the device buffer on first use, then copy the host vector into it
+template <class P, class T>
+hipError_t upload(P *&dev, const std::vector<T> &host)
+{
+    const size_t bytes = host.size() * sizeof(T);
+    if (!dev)
+        if (hipError_t e = hipMalloc(reinterpret_cast<void **>(&dev), bytes); e != hipSuccess) return e;
+    return hipMemcpy(dev, host.data(), bytes, hipMemcpyHostToDevice);
+}
+
+// Does the tile divide the conv (y3::tile_fits)?  cout_pad: the padded Cout of the mode's weights (ConvSlot::cout_pad / cout_pad64)
+bool fits(const y3::TileInfo &t, const ConvSlot &c, int cout_pad) { return y3::tile_fits(t, c.d.cin, c.d.src1 >= 0 ? c.d.c0 : -1, cout_pad); }
+
+// The first candidate tile that fits the conv and gives at least `want` workgroups for M rows over `cout_pad` channels; the last
+// candidate when none does.
+template <size_t N>
+int first_reaching(const int (&cand)[N], y3::TileInfo (*info)(int), const ConvSlot &c, int cout_pad, long long M, long long want)
+{
+    for (int t : cand) {
+        const y3::TileInfo s = info(t);
+        if (fits(s, c, cout_pad) && ((M + s.bm - 1) / s.bm) * (cout_pad / s.bn) >= want) return t;
+    }
+    return cand[N - 1];
+}
+
+int choose_tile_x2(const ConvSlot &c, long long M, long long, bool)
+{
+    // widest tile that still gives every CU at least two workgroups
+    static constexpr int wide[] = {4, 8, 0, 3, 2}, narrow[] = {1, 2};
+    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
+    return first_reaching(narrow, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
+}
+
+int choose_tile_x3(const ConvSlot &c, long long M, long long, bool)
+{
+    static constexpr int wide[] = {0, 3, 2}, narrow[] = {1, 2};
+    if (c.cout_pad64 % 128 == 0) return first_reaching(wide, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
+    return first_reaching(narrow, y3::conv_x3_tile_info, c, c.cout_pad64, M, 512);
+}
+
+// M = rows of this call (per lane); M_plan = rows of the planned batch.  The MFMA SHAPE (16x16x32 vs 32x32x16: two K groupings,
+// results differ in the last bits) is decided from plan-time quantities only, so that an image's result does not depend on the
+// batch or lane it runs in (y3_net_set_lanes: "results are unchanged"); the tile SIZE within one shape follows the call.
+int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16_out)
+{
+    auto blocks = [&](int t) {
+        y3::TileInfo s = y3::conv_bf16_tile_info(t);
+        return ((M + s.bm - 1) / s.bm) * (c.cout_pad / s.bn);
+    };
+    // large 3x3 convs: the 16x16x32 form once the PLANNED batch fills the chip with 256x256 tiles of 16 waves (tile 24 wins every
+    // such signature of the 64- and 128-image tables, tuning/bf16_b*_s416.json); smaller calls of the same plan take the 128x128 /
+    // 64x128 tiles of the same MFMA shape (27, 29)
+    if (c.d.size == 3 && c.d.src1 < 0 && c.d.cin % 64 == 0 && c.cout_pad % 256 == 0 && ((M_plan + 255) / 256) * (c.cout_pad / 256) >= 256) {
+        if (blocks(24) >= 256) return 24;
+        return blocks(27) >= 512 ? 27 : 29;
+    }
+    // early 3x3 / stride-1 convs with Cin = 32 / 64 (K = 288 / 576): weights resident in LDS, input patch by LDS-DMA (tile id 32,
+    // conv_res_bf16.hip) -- from the conv's shape alone, so batch- and lane-independent
+    if (bf16_out && c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && (c.d.cin == 32 || c.d.cin == 64) && c.d.cout % 64 == 0) return 32;
+    static constexpr int bk32[] = {5, 6},    // BK = 32 (Cin = 32 layers, Cout = 64)
+                         n128[] = {8, 12, 11},   // LDS-DMA variants: 128x128, 64x128, 64x64
+                         n64[] = {10, 11}, n32[] = {4};
+    if (c.d.cin % 64) return first_reaching(bk32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    return first_reaching(n32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+}
+
+// channels per K chunk of a 3x3 fp32 conv when the caller has not chosen (y3_net_set_k_chunk(-1)); Y3_K_CHUNK overrides (tools)
+int default_k_chunk(const ConvSlot &c)
+{
+    static const int env = [] { const char *e = getenv("Y3_K_CHUNK"); return e ? atoi(e) : -1; }();
+    if (env >= 0) return env;
+    // 128 channels per chunk: traffic beyond L2 of the whole conv stack 42.1 -> 29.6 GB per 64-image step (1.96 x -> 1.42 x the
+    // algorithmic bytes) at the same images/s (-0.1 %, inside the run-to-run spread); 64 per chunk: 27.2 GB but -0.4 %
+    // (profiles/r03_k_chunk_sweep.txt, r03_traffic_per_layer_*.txt)
+    return (c.d.size == 3 && c.d.cin >= 256) ? 128 : 0;
+}
+
+// How the 8 XCDs (each with its own 4 MB L2) divide the tile matrix of one fp32 conv launch: as a (8/gn) x gn grid of
+// blocks.  An XCD then streams 1/gn of the weights and 1/gm of the activations; the L2-miss traffic of the launch is
+// about gn * (activation bytes) + gm * (weight bytes), provided an XCD's weight slice stays L2-resident (<= 2.5 MB) while
+// its workgroups walk the K loop.  0 = not applicable (tile count too small / not divisible).
+int choose_xcd_gn(const ConvSlot &c, const y3::ConvArgs &a, const y3::TileInfo &t)
+{
+    const int tilesN = a.CoutPad / t.bn;
+    const long long tilesM = (a.M + t.bm - 1) / t.bm;
+    if (tilesM * tilesN < 64) return 0;
+    const double w_bytes = (double)a.CoutPad * c.K * 4.0, a_bytes = (double)a.src0_bytes + a.src1_bytes;
+    int best = 0;
+    double best_cost = 0;
+    for (int gn = 1; gn <= 8; gn *= 2) {
+        const int gm = 8 / gn;
+        if (tilesN % gn || tilesM < gm) continue;
+        double cost = gn * a_bytes + gm * w_bytes;
+        if (w_bytes / gn > 2.5e6) cost += 8.0 * (a_bytes + w_bytes);   // weight slice does not stay in L2: last resort
+        if (!best || cost < best_cost) {
+            best = gn;
+            best_cost = cost;
+        }
+    }
+    return best > 1 ? best : 0;   // gn = 1 is the contiguous order (8 pixel-tile runs), which needs no padding workgroups
+}
+
+int choose_tile(const ConvSlot &c, long long M, long long, bool)
+{
+    // the first residual block's 3x3 (32 -> 64 @208): weights resident in registers, input patch by LDS-DMA (tile id 33, conv_res_f32.hip).
+    // From the conv's shape alone (never the rows of the call); bit-identical to the generic tiles anyway.
+    if (c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && c.d.cin == 32 && c.d.cout % 64 == 0 && c.cout_pad == c.d.cout) return 33;
+    // measured on MI355X (tools/tune_tiles.py): many co-resident waves beat big wave tiles for the 64-cycle
+    // fp32 MFMA; prefer the largest block tile that still yields >= 2 workgroups per CU
+    static constexpr int n128[] = {10, 11}, n64[] = {11}, n32[] = {8};
+    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_tile_info, c, c.cout_pad, M, 1024);
+    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_tile_info, c, c.cout_pad, M, 1024);
+    return first_reaching(n32, y3::conv_tile_info, c, c.cout_pad, M, 1024);
+}
+
+}  // namespace
+
+// The first two ops are conv0 (3x3/1, 3 -> 32) and conv1 (3x3/2, 32 -> 64, no shortcut, single source) reading it, nobody
+// else reads conv0's output, and the plan is fp32 with every intermediate reusable: the pair runs as csrc/conv_stem.hip.
+bool y3::stem_applicable(const y3_net *net)
+{
+    if ((net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16) || net->keep_all || net->height % 32 || net->width % 32 || net->early_ops > 0)
+        return false;
+    if (net->ops.size() < 2 || net->ops[0].kind != 0 || net->ops[1].kind != 0) return false;
+    const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[1].index];
+    const y3_conv_desc &a = c0.d, &b = c1.d;
+    if (!c0.first_layer || a.size != 3 || a.stride != 1 || a.cout != 32 || a.residual >= 0 || a.src1 >= 0) return false;
+    if (b.size != 3 || b.stride != 2 || b.cin != 32 || b.cout != 64 || b.residual >= 0 || b.src1 >= 0 || b.src0 != a.dst) return false;
+    if (a.src0 != net->input_tensor) return false;
+    if (is_output(net, a.dst) || is_output(net, b.dst)) return false;
+    for (size_t i = 2; i < net->ops.size(); ++i) {
+        if (net->ops[i].kind == 0) {
+            const y3_conv_desc &d = net->convs[net->ops[i].index].d;
+            if (d.src0 == a.dst || d.src1 == a.dst || d.residual == a.dst) return false;
+        } else {
+            const y3_aux_desc &x = net->aux[net->ops[i].index];
+            if (x.src0 == a.dst || x.src1 == a.dst) return false;
+        }
+    }
+    return true;
+}
+
+// third op = 1x1 conv 64 -> 32 reading conv1's output (backbone.yaml layer 3): computed by the stem kernel from the tile it
+// still holds on chip (fp32 and bf16 plans)
+bool y3::stem_conv2_applicable(const y3_net *net)
+{
+    if ((net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16) || net->ops.size() < 3 || net->ops[2].kind != 0) return false;
+    const y3_conv_desc &b = net->convs[net->ops[1].index].d, &c = net->convs[net->ops[2].index].d;
+    if (c.size != 1 || c.stride != 1 || c.cin != 64 || c.cout != 32 || c.residual >= 0 || c.src1 >= 0 || c.src0 != b.dst) return false;
+    return !is_output(net, c.dst);
+}
+
+// Is net output t staged in a non-fp32 plan -- produced in the arena in the mode's own format and converted into the caller's fp32
+// grid at the end of the forward -- because a conv reads it again inside the net, or a conv with no fp32-output form of its launch
+// (shortcut, first layer) writes it?  Needs no plan: y3_net_plan marks `staged` by it, and y3_net_set_tile_bf16 refuses the
+// bf16-only tile 32 on a conv whose output is not staged.
+bool y3::output_staged(const y3_net *net, int t)
+{
+    for (const Op &o : net->ops) {
+        if (o.kind != 0) continue;
+        const ConvSlot &c = net->convs[o.index];
+        if (c.d.src0 == t || c.d.src1 == t || c.d.residual == t) return true;
+        if (c.d.dst == t && (c.d.residual >= 0 || c.first_layer)) return true;
+    }
+    return false;
+}
+
+namespace {
+
+y3_status resident_rule_f32(const y3_net *, const ConvSlot &c, int)
+{
+    if (!(c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && c.d.cin == 32 && c.d.cout % 64 == 0))
+        return fail(Y3_ERR_INVALID, "y3_net_set_tile: tile 33 (weight-resident) needs a 3x3 / stride-1 conv with 32 input channels and Cout %% 64 == 0");
+    return Y3_OK;
+}
+
+y3_status resident_rule_bf16(const y3_net *net, const ConvSlot &c, int slot)
+{
+    if (!(c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && (c.d.cin == 32 || c.d.cin == 64) && c.d.cout % 64 == 0))
+        return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile 32 (weight-resident) needs a 3x3 / stride-1 conv with 32 or 64 input channels and Cout %% 64 == 0");
+    // tile 32 stores bf16 only: a conv whose destination is a net output that the forward hands over as fp32 straight from the launch
+    // (not read again inside the net, no shortcut: y3_net_plan does not stage it) cannot take it -- refused here, by name, instead of a
+    // launch error in the forward
+    if (is_output(net, c.d.dst) && !y3::output_staged(net, c.d.dst))
+        return fail(Y3_ERR_INVALID, "y3_net_set_tile_bf16: tile 32 (weight-resident) stores bf16 only; conv %d writes an fp32 net output", slot);
+    return Y3_OK;
+}
+
+// fp32 plans: the head kernel when the conv decodes its own tiles; else the split resolve_splits decided, the XCD order and the K order
+void refine_f32(const y3_net *net, const ConvSlot &c, const y3::ConvArgs &a, y3::ConvChoice &ch)
+{
+    if (a.dec.boxes) { ch.kind = y3::ConvKind::HeadDecodeF32; return; }
+    ch.split_k = c.split_k;
+    if (c.split_k > 1) ch.kind = y3::ConvKind::SplitK;   // low-latency plan: S slices of the K walk into the lane's slabs, then the finish launch
+    else if (net->xcd_mode) ch.xcd_gn = choose_xcd_gn(c, a, y3::conv_tile_info(ch.tile));
+    // K order of the 3x3 convs (conv_f32.hip): chunk-major when the conv has more input channels than one chunk
+    const int ck = net->k_chunk >= 0 ? net->k_chunk : default_k_chunk(c);
+    if (c.d.size == 3 && c.d.src1 < 0 && ck > 0 && c.d.cin > ck && c.d.cin % ck == 0 && ck % 32 == 0) ch.k_chunk = ck;
+}
+
+// bf16 plans: a head conv that decodes its own tiles needs a 256-wide tile
+void refine_bf16(const y3_net *, const ConvSlot &, const y3::ConvArgs &a, y3::ConvChoice &ch)
+{
+    if (a.dec.boxes && y3::conv_bf16_tile_info(ch.tile).bn != 256) {   // a box's logits must meet in one workgroup: all 256 channels in the tile
+        const bool m16 = ch.tile >= 24 && ch.tile <= 29;               // keep the MFMA shape of the plan's tile: same K grouping, same bits
+        const bool big = (a.M + 255) / 256 >= 256;                     // 256x256 once it fills the chip, else 128x256 (16 waves both)
+        ch.tile = m16 ? (big ? 24 : 26) : (big ? 17 : 19);
+    }
+}
+
+hipError_t launch_f32(const y3::ConvArgs &a, int tile, bool, hipStream_t s) { return y3::launch_conv_f32(a, tile, s); }
+
+constexpr y3::ConvFamily F32_FAMILY = {
+    y3::TILE_COUNT, y3::conv_tile_info, y3::conv_tile_built, &ConvSlot::tile, &ConvSlot::cout_pad,
+    "y3_net_set_tile: bad argument", "y3_net_set_tile: tile id %d is retired (the timing ablations of rounds 1-2; y3_tile_built)",
+    "y3_net_set_tile: tile does not divide Cout", 33, resident_rule_f32,
+    &ConvSlot::w_dev, 4, choose_tile, launch_f32, refine_f32, y3::launch_conv_stem_f32, &ConvSlot::w0stem_dev};
+constexpr y3::ConvFamily BF16_FAMILY = {
+    y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
+    "y3_net_set_tile_bf16: bad argument",
+    "y3_net_set_tile_bf16: tile id %d is retired (20: the pipelined tile of round 2; 33..36: tap-row reuse and the four-wave tile of round 4; y3_tile_built)",
+    "y3_net_set_tile_bf16: tile does not fit this conv", 32, resident_rule_bf16,
+    &ConvSlot::wbf_dev, 2, choose_tile_bf16, y3::launch_conv_bf16, refine_bf16, y3::launch_conv_stem_bf16, &ConvSlot::w0raw_dev};
+constexpr y3::ConvFamily X3_FAMILY = {
+    y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x3_tile_built, &ConvSlot::tile_x3, &ConvSlot::cout_pad64,
+    "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: tile does not fit this conv", -1, nullptr,
+    &ConvSlot::wx3_dev, 6, choose_tile_x3, y3::launch_conv_f32x3, nullptr, nullptr, nullptr};
+constexpr y3::ConvFamily X2_FAMILY = {
+    y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x2_tile_built, &ConvSlot::tile_x2, &ConvSlot::cout_pad64,
+    "y3_net_set_tile_x2: bad argument", "y3_net_set_tile_x2: tile does not fit this conv", "y3_net_set_tile_x2: tile does not fit this conv", -1, nullptr,
+    &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr};
+
+// "forced tile, else the family's chooser": the tile part of the launch decision
+int family_tile(const y3::ConvFamily &f, const ConvSlot &c, long long M, long long M_plan, bool arena_out)
+{
+    return c.*f.tile >= 0 ? c.*f.tile : f.choose(c, M, M_plan, arena_out);
+}
+
+}  // namespace
+
+const y3::ConvFamily *y3::conv_family(int dtype)
+{
+    switch (dtype) {
+        case Y3_DTYPE_F32: return &F32_FAMILY;
+        case Y3_DTYPE_BF16: return &BF16_FAMILY;
+        case Y3_DTYPE_F32X3: return &X3_FAMILY;
+        case Y3_DTYPE_F32X2: return &X2_FAMILY;
+        default: return nullptr;
+    }
+}
+
+// Which kernel, with which tile, K order, XCD order and split, conv op oi launches for the rows of `a`.  Everything that asks this --
+// the enqueue path, resolve_splits, the stamp and profile entry points -- asks it here.  Two rules hold throughout: the MFMA SHAPE
+// follows the planned rows and the tile SIZE the rows of the call (choose_tile_bf16), and a split follows the plan alone
+// (resolve_splits), so within one plan an image's bits depend neither on its batch nor on its lane.
+y3::ConvChoice y3::choose_conv(const y3_net *net, int oi, const ConvArgs &a)
+{
+    const ConvSlot &c = net->convs[net->ops[oi].index];
+    ConvChoice ch{ConvKind::Mfma, -1, 0, 0, 1};
+    if ((net->stem_fused && oi == 0) || (net->stem_conv2 && oi == 2)) ch.kind = ConvKind::InStem;
+    else if (net->stem_fused && oi == 1) ch.kind = ConvKind::Stem;
+    else if (c.first_layer) ch.kind = ConvKind::First;
+    if (ch.kind != ConvKind::Mfma) return ch;
+    const ConvFamily &f = *conv_family(net->dtype);
+    ch.tile = family_tile(f, c, a.M, (long long)net->max_batch * a.Ho * a.Wo, net->out_slot[c.d.dst] < 0);
+    if (f.refine) f.refine(net, c, a, ch);
+    return ch;
+}
+
+y3::ConvChoice y3::choose_conv_planned(const y3_net *net, int oi)
+{
+    const ConvSlot &c = net->convs[net->ops[oi].index];
+    ConvArgs a{};
+    a.Ho = net->height / c.d.out_div;
+    a.Wo = net->width / c.d.out_div;
+    a.M = net->max_batch * a.Ho * a.Wo;
+    a.CoutPad = c.*conv_family(net->dtype)->cout_pad;
+    return choose_conv(net, oi, a);
+}
+
+int y3::conv_op(const y3_net *net, int slot)
+{
+    for (int oi = 0; oi < (int)net->ops.size(); ++oi)
+        if (net->ops[oi].kind == 0 && net->ops[oi].index == slot) return oi;
+    return -1;
+}
+
+// The one body of y3_net_set_tile / _bf16 / _x3 / _x2: a built id that fits the conv (-1: back to the tuning table / the heuristic)
+static y3_status set_forced_tile(const y3::ConvFamily &f, y3_net *net, int slot, int tile)
+{
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || tile >= f.count) return fail(Y3_ERR_INVALID, "%s", f.bad);
+    ConvSlot &c = net->convs[slot];
+    if (tile >= 0) {
+        if (!f.built(tile)) return fail(Y3_ERR_INVALID, f.retired, tile);
+        if (c.first_layer || !fits(f.info(tile), c, c.*f.cout_pad)) return fail(Y3_ERR_INVALID, "%s", f.misfit);
+        if (tile == f.resident)
+            if (y3_status st = f.resident_rule(net, c, slot); st != Y3_OK) return st;
+    }
+    c.*f.tile = tile;
+    return Y3_OK;
+}
+
+// ---- split-K (low-latency fp32 plans) --------------------------------------------------------------------------------------
+// Can conv `slot` ever run split?  From the graph and the forced tile alone (no plan needed): not the first layer, not the
+// weight-resident tile 33, not a detection head (y3_net_detect runs the heads through conv_head.hip, and the composed route
+// must stay bit-identical to it), and only on the two tiles the split form is built for.  why: the refusal's text.
+static bool split_eligible(const y3_net *net, int slot, const char **why)
+{
+    const ConvSlot &c = net->convs[slot];
+    const char *w = nullptr;
+    if (c.first_layer) w = "the first layer (Cin = 3) is never split";
+    else if (net->nclasses > 0 && is_output(net, c.d.dst)) w = "a detection-head conv is never split (y3_net_detect decodes it in its own kernel)";
+    else if (!y3::conv_split_tile(family_tile(F32_FAMILY, c, 1, 1, true)))
+        w = "the conv's tile has no split form (tiles 10 and 11 have; the weight-resident tile 33 and the 32-wide tile 8 have not)";
+    if (why) *why = w;
+    return !w;
+}
+
+// Decide ConvSlot::split_k of every conv and size the slab workspace.  Runs at the end of y3_net_plan_hw and again from every
+// setter that changes an input of the decision on a planned net; never from the enqueue path.  Inputs: the conv's shape, its tile at
+// the planned batch, max_batch, n_cus, the caller's request -- never the rows of a call, so within one plan an image's bits do not
+// depend on its batch or position (the rule choose_tile_bf16 states for the MFMA shape).
+y3_status y3::resolve_splits(y3_net *net)
+{
+    if (!net->height) return Y3_OK;
+    size_t lane_bytes = 0;
+    for (int oi = 0; oi < (int)net->ops.size(); ++oi) {
+        if (net->ops[oi].kind != 0) continue;
+        const int slot = net->ops[oi].index;
+        ConvSlot &c = net->convs[slot];
+        c.split_k = 1;
+        if (net->dtype != Y3_DTYPE_F32 || !split_eligible(net, slot, nullptr)) continue;
+        if (c.split_req == 1 || (c.split_req < 0 && !net->low_latency)) continue;
+        const ConvChoice ch = choose_conv_planned(net, oi);   // split_k is 1 here: the unsplit launch at the planned rows
+        if (ch.kind != ConvKind::Mfma) continue;               // runs as, or inside, the fused stem launch
+        const long long M = (long long)net->max_batch * (net->height / c.d.out_div) * (net->width / c.d.out_div);
+        const int tile = ch.tile;
+        const y3::TileInfo t = y3::conv_tile_info(tile);
+        const long long tiles = ((M + t.bm - 1) / t.bm) * (c.cout_pad / t.bn);
+        const size_t slab = y3::conv_split_slab_bytes(tile, M, c.cout_pad);
+        const int kt = c.K / t.bk;
+        int S = c.split_req > 1 ? c.split_req : y3_choose_split_k(tiles, kt, net->n_cus, (long long)slab);
+        if (S > kt) S = kt;
+        if (S < 2 || slab > 0x7fffffffull) continue;
+        c.split_k = S;
+        lane_bytes = std::max(lane_bytes, (size_t)S * slab);
+    }
+    if (lane_bytes > net->split_ws_lane || (lane_bytes && net->lanes > net->split_ws_lanes)) {
+        if (net->split_ws) (void)hipFree(net->split_ws);
+        net->split_ws = nullptr;
+        net->split_ws_lane = 0;
+        net->split_ws_lanes = 0;
+        lane_bytes = (lane_bytes + 255) & ~(size_t)255;
+        hipError_t e = hipMalloc(&net->split_ws, lane_bytes * net->lanes);
+        if (e != hipSuccess) {
+            for (ConvSlot &c : net->convs) c.split_k = 1;
+            return fail(Y3_ERR_OOM, "split-K workspace: hipMalloc(%zu) failed: %s", lane_bytes * net->lanes, hipGetErrorString(e));
+        }
+        net->split_ws_lane = lane_bytes;
+        net->split_ws_lanes = net->lanes;
+    }
+    return Y3_OK;
+}
+
+// ... from a setter: nothing to decide before the first plan; afterwards on the net's device (the workspace may grow)
+static y3_status resolve_splits_of_setter(y3_net *net)
+{
+    if (!net->height) return Y3_OK;
+    Y3_ENTER_DEVICE(net);
+    return y3::resolve_splits(net);
+}
+
+extern "C" {
+
+int y3_version(void) { return 100; }
+
+const char *y3_last_error(void) { return g_err; }
+
+int y3_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+int y3_tile_built(int dtype, int tile)
+{
+    const y3::ConvFamily *f = y3::conv_family(dtype);
+    return (f && f->built(tile)) ? 1 : 0;
+}
+
+y3_status y3_net_create(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
+                        const y3_conv_desc *convs, int n_convs, const y3_aux_desc *aux, int n_aux, int input_tensor,
+                        const int32_t outputs[3], int nclasses, y3_net **out)
+try {
+    if (!tensors || !op_kinds || !convs || !outputs || !out || n_tensors <= 0 || n_ops <= 0 || n_convs < 0 || n_aux < 0)
+        return fail(Y3_ERR_INVALID, "y3_net_create: null, empty or negative-count argument");
+    if (y3::test_fail_alloc()) throw std::bad_alloc();   // tests only: the allocation below failing
+    std::unique_ptr<y3_net> net(new y3_net());           // released to the caller on success only: no path leaks it, thrown ones included
+    if (hipGetDevice(&net->device) != hipSuccess) return fail(Y3_ERR_NODEVICE, "y3_net_create: no HIP device");
+    net->tensors.assign(tensors, tensors + n_tensors);
+    net->aux.assign(aux, aux + (aux ? n_aux : 0));
+    net->convs.resize(n_convs);
+    auto bad_t = [&](int t) { return t < 0 || t >= n_tensors; };
+    for (int i = 0; i < n_convs; ++i) {
+        ConvSlot &c = net->convs[i];
+        c.d = convs[i];
+        const y3_conv_desc &d = c.d;
+        int err = 0;
+        if (bad_t(d.src0) || bad_t(d.dst) || (d.src1 >= 0 && bad_t(d.src1)) || (d.residual >= 0 && bad_t(d.residual))) err = 1;
+        if (!(d.size == 1 || d.size == 3) || !(d.stride == 1 || (d.stride == 2 && d.size == 3))) err = 2;
+        if (d.src1 >= 0 && (d.size != 1 || d.c0 % 32 || (d.cin - d.c0) % 32 || d.c0 <= 0 || d.c0 >= d.cin)) err = 3;
+        if (d.src1 < 0 && (d.c0 != d.cin || d.src0_upsample)) err = 4;
+        c.first_layer = (d.cin == 3);
+        if (c.first_layer && !(d.size == 3 && d.stride == 1 && d.cout == 32 && d.residual < 0 && d.src1 < 0)) err = 5;
+        if (!c.first_layer && d.cin % 32) err = 6;
+        if (d.cout <= 0 || d.out_div != d.in_div * d.stride) err = err ? err : 7;
+        if (err) {
+            return fail(Y3_ERR_INVALID, "y3_net_create: conv %d unsupported or inconsistent (check %d)", i, err);
+        }
+        c.cout_pad = (d.cout + 31) / 32 * 32;
+        c.cout_pad64 = (d.cout + 63) / 64 * 64;
+        c.K = d.size * d.size * d.cin;
+    }
+    int ci = 0, ai = 0;
+    for (int i = 0; i < n_ops; ++i) {
+        if (op_kinds[i] == 0) {
+            if (ci >= n_convs) { return fail(Y3_ERR_INVALID, "y3_net_create: more conv ops than descriptors"); }
+            net->ops.push_back({0, ci++});
+        } else {
+            if (ai >= n_aux) { return fail(Y3_ERR_INVALID, "y3_net_create: more aux ops than descriptors"); }
+            net->ops.push_back({1, ai++});
+        }
+    }
+    if (bad_t(input_tensor)) { return fail(Y3_ERR_INVALID, "y3_net_create: bad input tensor"); }
+    net->input_tensor = input_tensor;
+    for (int i = 0; i < 3; ++i) {
+        // nclasses == 0: raw feature outputs (layer tests); otherwise the yolo head layout is enforced
+        if (bad_t(outputs[i]) || (nclasses > 0 && tensors[outputs[i]].channels != 3 * (5 + nclasses))) {
+            return fail(Y3_ERR_INVALID, "y3_net_create: output %d must have 3*(5+nclasses) channels", i);
+        }
+        net->outputs[i] = outputs[i];
+    }
+    net->nclasses = nclasses;
+    net->tdev.assign(n_tensors, nullptr);
+    net->tbytes.assign(n_tensors, 0);
+    net->tblock.assign(n_tensors, 0);
+    net->out_slot.assign(n_tensors, -1);
+    *out = net.release();
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_create")
+
+void y3_net_destroy(y3_net *net)
+{
+    if (!net) return;
+    y3::free_plan(net);
+    if (net->fork_ev) {
+        (void)hipEventDestroy(net->fork_ev);
+        for (int i = 0; i < Y3_MAX_LANES; ++i) {
+            (void)hipStreamDestroy(net->lane_stream[i]);
+            (void)hipEventDestroy(net->join_ev[i]);
+        }
+    }
+    for (ConvSlot &c : net->convs)
+        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, c.wbf_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev})
+            if (p) (void)hipFree(p);
+    delete net;
+}
+
+y3_status y3_net_set_conv_weights(y3_net *net, int slot, const float *w, const float *gamma, const float *beta,
+                                  const float *mean, const float *var, const float *bias, float eps)
+try {
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || !w)
+        return fail(Y3_ERR_INVALID, "y3_net_set_conv_weights: bad slot or null weights");
+    ConvSlot &c = net->convs[slot];
+    const y3_conv_desc &d = c.d;
+    if (d.bn ? !(gamma && beta && mean && var) : !bias)
+        return fail(Y3_ERR_INVALID, "y3_net_set_conv_weights: conv %d needs %s", slot, d.bn ? "gamma/beta/mean/var" : "bias");
+    const int K = c.K, CP = c.cout_pad, CP64 = c.cout_pad64;
+    std::vector<float> scale(CP64, 1.0f), shift(CP64, 0.0f);
+    for (int n = 0; n < d.cout; ++n) {
+        if (d.bn) {
+            // BatchNormalization inference: y = x*scale + (beta - mean*scale), scale = gamma*rsqrt(var+eps)
+            const float inv = 1.0f / sqrtf(var[n] + eps);
+            scale[n] = inv * gamma[n];
+            shift[n] = beta[n] - mean[n] * scale[n];
+        } else {
+            shift[n] = bias[n];
+        }
+    }
+    Y3_ENTER_DEVICE(net);
+    // every format is packed whatever the plan's dtype: one net can be re-planned in another mode
+    if (c.first_layer) {
+        // HWIO as is (the Cin = 3 direct kernels); the fused stem kernel's 28 rows with the BN scale folded in (fp32) and without (bf16)
+        HIP_TRY(upload(c.w_dev, std::vector<float>(w, w + (size_t)K * d.cout)));
+        HIP_TRY(upload(c.w0stem_dev, pack_stem28(w, K, d.cout, scale.data())));
+        HIP_TRY(upload(c.w0raw_dev, pack_stem28(w, K, d.cout, nullptr)));
+    } else {
+        // fp32 path: the BN scale is folded into the packed weights (one VALU multiply less per output element; VALU
+        // time is matrix-pipe time for the fp32 MFMA).  The bf16 copy keeps the unscaled weights + scale in the epilogue.
+        const std::vector<float> pk = pack_rows(w, K, d.cout, CP, nullptr), pk_scaled = pack_rows(w, K, d.cout, CP, scale.data());
+        HIP_TRY(upload(c.w_dev, pk_scaled));
+        HIP_TRY(upload(c.wbf_dev, pack_planes<1>(pk, K, d.cout, CP, [](float x, unsigned short *v) { v[0] = f32_to_bf16_rne(x); })));
+        // a scaled weight outside the fp16 range: y3_net_plan(Y3_DTYPE_F32X2) refuses the net; other modes are unaffected
+        c.x2_ok = std::all_of(pk_scaled.begin(), pk_scaled.end(), [](float x) { return fabsf(x) < 65504.0f; });
+        HIP_TRY(upload(c.wx3_dev, pack_planes<3>(pk, K, d.cout, CP64, split_bf16x3)));         // unscaled, like the bf16 copy
+        HIP_TRY(upload(c.wx2_dev, pack_planes<2>(pk_scaled, K, d.cout, CP64, split_f16x2)));   // BN-scaled, like the fp32 copy
+    }
+    HIP_TRY(upload(c.scale_dev, scale));
+    HIP_TRY(upload(c.shift_dev, shift));
+    c.loaded = true;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_conv_weights")
+
+y3_status y3_net_set_tile(y3_net *net, int slot, int tile)
+try {
+    if (y3_status st = set_forced_tile(F32_FAMILY, net, slot, tile); st != Y3_OK) return st;
+    return resolve_splits_of_setter(net);   // the tile is an input of the split decision
+}
+Y3_CATCH("y3_net_set_tile")
+
+y3_status y3_net_set_tile_bf16(y3_net *net, int slot, int tile)
+try {
+    return set_forced_tile(BF16_FAMILY, net, slot, tile);
+}
+Y3_CATCH("y3_net_set_tile_bf16")
+
+y3_status y3_net_set_tile_x3(y3_net *net, int slot, int tile)
+try {
+    return set_forced_tile(X3_FAMILY, net, slot, tile);
+}
+Y3_CATCH("y3_net_set_tile_x3")
+
+y3_status y3_net_set_tile_x2(y3_net *net, int slot, int tile)
+try {
+    return set_forced_tile(X2_FAMILY, net, slot, tile);
+}
+Y3_CATCH("y3_net_set_tile_x2")
+
+y3_status y3_net_set_lanes(y3_net *net, int lanes)
+try {
+    if (!net || lanes < 1 || lanes > Y3_MAX_LANES) return fail(Y3_ERR_INVALID, "y3_net_set_lanes: lanes must be in [1,%d]", Y3_MAX_LANES);
+    net->lanes = lanes;
+    return resolve_splits_of_setter(net);   // one slab workspace per lane
+}
+Y3_CATCH("y3_net_set_lanes")
+
+y3_status y3_net_set_stem_fusion(y3_net *net, int on)
+try {
+    if (!net || on < 0 || on > 2) return fail(Y3_ERR_INVALID, "y3_net_set_stem_fusion: argument must be 0, 1 or 2");
+    net->stem_mode = on;
+    net->stem_mode_set = true;
+    // takes effect at once on a planned net when the graph qualifies (decided again by the next y3_net_plan)
+    if (net->height) {
+        net->stem_fused = on && y3::stem_applicable(net);
+        net->stem_conv2 = net->stem_fused && on == 1 && y3::stem_conv2_applicable(net);
+    }
+    return resolve_splits_of_setter(net);   // a conv inside the fused stem is not split
+}
+Y3_CATCH("y3_net_set_stem_fusion")
+
+y3_status y3_net_set_k_chunk(y3_net *net, int channels)
+try {
+    if (!net || channels < -1 || (channels > 0 && channels % 32)) return fail(Y3_ERR_INVALID, "y3_net_set_k_chunk: -1, 0 or a multiple of 32 channels");
+    net->k_chunk = channels;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_k_chunk")
+
+y3_status y3_net_set_low_latency(y3_net *net, int on)
+try {
+    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "y3_net_set_low_latency: argument must be 0 or 1");
+    net->low_latency = on != 0;
+    net->low_latency_set = true;
+    return resolve_splits_of_setter(net);
+}
+Y3_CATCH("y3_net_set_low_latency")
+
+y3_status y3_net_set_split_k(y3_net *net, int slot, int S)
+try {
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || S < -1 || S == 0 || S > 16)
+        return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv slot out of range, or S not -1, 1 or 2..16");
+    ConvSlot &c = net->convs[slot];
+    if (S > 1) {
+        const char *why = nullptr;
+        if (!split_eligible(net, slot, &why)) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d: %s", slot, why);
+        if (net->height && net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d: only Y3_DTYPE_F32 plans split K", slot);
+        if (const int oi = y3::conv_op(net, slot); net->height && oi >= 0)
+            if (const y3::ConvKind k = y3::choose_conv_planned(net, oi).kind; k == y3::ConvKind::Stem || k == y3::ConvKind::InStem)
+                return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d runs inside the fused stem kernel, which is never split", slot);
+        if (S > c.K / 32) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d has %d K tiles, fewer than S = %d", slot, c.K / 32, S);
+    }
+    c.split_req = S;
+    return resolve_splits_of_setter(net);
+}
+Y3_CATCH("y3_net_set_split_k")
+
+y3_status y3_net_set_xcd_mode(y3_net *net, int mode)
+try {
+    if (!net || mode < 0 || mode > 1) return fail(Y3_ERR_INVALID, "y3_net_set_xcd_mode: mode must be 0 or 1");
+    net->xcd_mode = mode;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_xcd_mode")
+
+y3_status y3_net_set_early_chunk(y3_net *net, int n_convs, int chunk_images)
+try {
+    if (!net || n_convs < 0 || chunk_images < 0) return fail(Y3_ERR_INVALID, "y3_net_set_early_chunk: bad argument");
+    if (n_convs >= (int)net->convs.size()) return fail(Y3_ERR_INVALID, "y3_net_set_early_chunk: n_convs must leave at least one conv for the full batch");
+    net->early_convs = (chunk_images > 0) ? n_convs : 0;
+    net->early_chunk = (n_convs > 0) ? chunk_images : 0;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_early_chunk")
+
+y3_status y3_net_keep_activations(y3_net *net, int keep)
+try {
+    if (!net) return fail(Y3_ERR_INVALID, "y3_net_keep_activations: null net");
+    net->keep_all = keep ? 1 : 0;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_keep_activations")
+
+int y3_net_get_split_k(const y3_net *net, int slot)
+{
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height) return 1;
+    return net->convs[slot].split_k;
+}
+
+int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice)
+{
+    // Below two workgroups per CU the wall time of a conv launch is one workgroup's walk through K (the 13^2 512 -> 1024 conv at
+    // one image: 48 workgroups x 144 K tiles on 256 CUs), so slices multiply the workgroups until the chip holds two per CU -- but a
+    // slice keeps at least kSplitMinTiles K tiles (its prologue and its slab store are paid per slice), at most kSplitMax slices
+    // exist, and the slabs of one launch stay under kSplitMaxBytes (they are written and read once more by the finish launch).
+    constexpr int kSplitMinTiles = 4, kSplitMax = 16;
+    constexpr long long kSplitMaxBytes = 16ll << 20;
+    if (tiles <= 0 || k_tiles <= 0 || n_cus <= 0 || slab_bytes_per_slice <= 0) return 1;
+    const long long want = 2ll * n_cus;
+    if (tiles >= want) return 1;
+    long long S = (want + tiles - 1) / tiles;
+    S = std::min<long long>(S, k_tiles / kSplitMinTiles);
+    S = std::min<long long>(S, kSplitMax);
+    S = std::min<long long>(S, kSplitMaxBytes / slab_bytes_per_slice);
+    return S < 2 ? 1 : (int)S;
+}
+
+}  // extern "C"

@@ -1,0 +1,456 @@
+// The entry points that take no net: image input (resize, letterbox and its inverse), evaluation counters, validation loss, the
+// TFRecord checksum, decode and class scores, NMS and the packing of detections.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "y3_host.h"
+
+namespace y3 {
+// include/y3.h, Y3_IMAGE_LETTERBOX.  Every operation in fp32 (this file is compiled with -ffp-contract=off), nearbyintf in the
+// default rounding mode (half to even): bit for bit what core/utils.letterbox_geometry computes with np.float32 and np.rint.
+LetterboxGeom letterbox_geom(int h, int w, int Hc, int Wc)
+{
+    const float scale = std::min((float)Hc / (float)h, (float)Wc / (float)w);
+    LetterboxGeom g;
+    g.sh = std::max(1, (int)nearbyintf(scale * (float)h));
+    g.sw = std::max(1, (int)nearbyintf(scale * (float)w));
+    g.top = (Hc - g.sh) >> 1;      // floor, also where the difference is negative (refused by letterbox_geom_fits)
+    g.left = (Wc - g.sw) >> 1;
+    return g;
+}
+}  // namespace y3
+
+// ------------------------------------------------------------------------------------------ image input
+namespace {
+// is_uint8 / y3_image_desc.mode: 0, 1 or 2, with or without Y3_IMAGE_LETTERBOX
+bool image_mode_ok(int mode) { return (mode & ~Y3_IMAGE_LETTERBOX) >= 0 && (mode & ~Y3_IMAGE_LETTERBOX) <= 2; }
+// the geometry of one image: the whole canvas without the flag
+y3::LetterboxGeom image_geom(int mode, int h, int w, int Hc, int Wc)
+{
+    return (mode & Y3_IMAGE_LETTERBOX) ? y3::letterbox_geom(h, w, Hc, Wc) : y3::LetterboxGeom{Hc, Wc, 0, 0};
+}
+}  // namespace
+
+// ------------------------------------------------------------------------------------------ decode
+// gs: grid_hw[3][2] = {gh, gw} per scale (the square entry points hand {g, g})
+static y3_status decode_common(const float *const grids[3], const int32_t (*gs)[2], int batch, int nc,
+                               const float *anchors, float *bboxes, float *conf, float *probs, int64_t *cls,
+                               float *scores, void *stream, const char *who)
+{
+    if (!grids || !gs || !anchors || !bboxes || batch <= 0 || nc <= 0) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
+    y3::DecodeArgs a{};
+    int off = 0;
+    for (int s = 0; s < 3; ++s) {
+        if (!grids[s] || gs[s][0] <= 0 || gs[s][1] <= 0 || ((uintptr_t)grids[s] & 15))
+            return fail(Y3_ERR_INVALID, "%s: grid %d null, empty or not 16-byte aligned", who, s);
+        a.grid[s] = grids[s];
+        a.gh[s] = gs[s][0];
+        a.gw[s] = gs[s][1];
+        a.off[s] = off;
+        off += gs[s][0] * gs[s][1] * 3;
+        for (int k = 0; k < 3; ++k) {
+            a.anchors[s][k][0] = anchors[(s * 3 + k) * 2 + 0];
+            a.anchors[s][k][1] = anchors[(s * 3 + k) * 2 + 1];
+        }
+    }
+    if ((uintptr_t)bboxes & 15) return fail(Y3_ERR_INVALID, "%s: bboxes not 16-byte aligned", who);
+    a.B = batch;
+    a.N = off;
+    a.nc = nc;
+    hipError_t e = y3::launch_decode(a, bboxes, conf, probs, cls, scores, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}
+
+// The square entry points are the _hw ones with {g, g}; `who` names the entry point the caller used in the messages.
+static y3_status yolo_decode_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+                                const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
+{
+    if (!conf_dev || !probs_dev) return fail(Y3_ERR_INVALID, "%s: null output", who);
+    return decode_common(grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, nullptr, nullptr, stream, who);
+}
+
+y3_status y3::decode_scores_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+                                       const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream)
+{
+    if (!class_idx_dev || !scores_dev) return fail(Y3_ERR_INVALID, "%s: null output", who);
+    return decode_common(grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, nullptr, nullptr, class_idx_dev, scores_dev, stream, who);
+}
+
+extern "C" {
+
+// The square entry points (y3_preprocess_image, ...) are their _hw counterparts with canvas_h == canvas_w; `who` names the
+// entry point the caller used in the messages.
+static y3_status preprocess_image_hw(const char *who, const void *image_dev, int is_uint8, int height, int width, int channels,
+                                     float *batch_dev, int slot, int Hc, int Wc, void *stream)
+{
+    if (!image_dev || !batch_dev || height <= 0 || width <= 0 || channels < 3 || channels > 4 || slot < 0 ||
+        Hc <= 0 || Wc <= 0 || !image_mode_ok(is_uint8) || ((is_uint8 & ~Y3_IMAGE_LETTERBOX) == 0 && ((uintptr_t)image_dev & 3)))
+        return fail(Y3_ERR_INVALID, "%s: bad argument (channels must be 3 or 4)", who);
+    const y3::LetterboxGeom g = image_geom(is_uint8, height, width, Hc, Wc);
+    if (!y3::letterbox_geom_fits(g, Hc, Wc))
+        return fail(Y3_ERR_INVALID, "%s: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, height, width,
+                    g.sh, g.sw, g.top, g.left, Hc, Wc);
+    float *dst = batch_dev + (size_t)slot * Hc * Wc * 3;
+    hipError_t e = y3::launch_resize(image_dev, is_uint8, height, width, channels, dst, Hc, Wc, g, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}
+
+y3_status y3_preprocess_image_hw(const void *image_dev, int is_uint8, int height, int width, int channels,
+                                 float *batch_dev, int slot, int canvas_h, int canvas_w, void *stream)
+try {
+    return preprocess_image_hw("y3_preprocess_image_hw", image_dev, is_uint8, height, width, channels, batch_dev, slot, canvas_h, canvas_w, stream);
+}
+Y3_CATCH("y3_preprocess_image_hw")
+
+y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, int width, int channels,
+                              float *batch_dev, int slot, int image_size, void *stream)
+try {
+    return preprocess_image_hw("y3_preprocess_image", image_dev, is_uint8, height, width, channels, batch_dev, slot, image_size, image_size, stream);
+}
+Y3_CATCH("y3_preprocess_image")
+
+static y3_status preprocess_batch_hw(const char *who, const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host,
+                                     int n_images, float *batch_dev, int first_slot, int Hc, int Wc, void *stream)
+{
+    if (!pixels_dev || !descs_host || !batch_dev || n_images < 1 || first_slot < 0 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_images < 1, first_slot < 0 or image_size <= 0)", who);
+    // every check before the first launch: a bad image late in the list must not leave the batch half written
+    for (int i = 0; i < n_images; ++i) {
+        const y3_image_desc &d = descs_host[i];
+        if (d.channels < 3 || d.channels > 4)
+            return fail(Y3_ERR_INVALID, "%s: image %d: channels must be 3 or 4 (got %d)", who, i, d.channels);
+        if (!image_mode_ok(d.mode))
+            return fail(Y3_ERR_INVALID, "%s: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
+        if (d.height < 1 || d.width < 1)
+            return fail(Y3_ERR_INVALID, "%s: image %d: height and width must be at least 1 (got %d x %d)", who, i,
+                        d.height, d.width);
+        const bool f32 = (d.mode & ~Y3_IMAGE_LETTERBOX) == 0;
+        if (f32 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
+            return fail(Y3_ERR_INVALID, "%s: image %d: float32 pixels must be 4-byte aligned (offset %llu)", who, i,
+                        (unsigned long long)d.offset);
+        // height, width < 2^31 and channels * elemsize <= 16: the product stays below 2^66, so take it in 128 bits
+        const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (f32 ? 4 : 1));
+        if ((unsigned __int128)d.offset + bytes > (unsigned __int128)pixels_bytes)
+            return fail(Y3_ERR_INVALID, "%s: image %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", who, i,
+                        d.height, d.width, d.channels, (unsigned long long)d.offset, pixels_bytes);
+        const y3::LetterboxGeom g = image_geom(d.mode, d.height, d.width, Hc, Wc);
+        if (!y3::letterbox_geom_fits(g, Hc, Wc))
+            return fail(Y3_ERR_INVALID, "%s: image %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, i,
+                        d.height, d.width, g.sh, g.sw, g.top, g.left, Hc, Wc);
+    }
+    const size_t per_image = (size_t)Hc * Wc * 3;
+    for (int i0 = 0; i0 < n_images; i0 += y3::kPreprocessTableImages) {
+        const int n = std::min(y3::kPreprocessTableImages, n_images - i0);
+        y3::LetterboxGeom geoms[y3::kPreprocessTableImages];     // on the stack: the call allocates nothing
+        for (int i = 0; i < n; ++i) geoms[i] = image_geom(descs_host[i0 + i].mode, descs_host[i0 + i].height, descs_host[i0 + i].width, Hc, Wc);
+        hipError_t e = y3::launch_preprocess_batch(pixels_dev, descs_host + i0, geoms, n, batch_dev + ((size_t)first_slot + i0) * per_image,
+                                                   Hc, Wc, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    }
+    return Y3_OK;
+}
+
+y3_status y3_preprocess_batch_hw(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
+                                 float *batch_dev, int first_slot, int canvas_h, int canvas_w, void *stream)
+try {
+    return preprocess_batch_hw("y3_preprocess_batch_hw", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, canvas_h, canvas_w, stream);
+}
+Y3_CATCH("y3_preprocess_batch_hw")
+
+y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
+                              float *batch_dev, int first_slot, int image_size, void *stream)
+try {
+    return preprocess_batch_hw("y3_preprocess_batch", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, image_size, image_size, stream);
+}
+Y3_CATCH("y3_preprocess_batch")
+
+static y3_status letterbox_geometry_hw(const char *who, const y3_image_desc *descs_host, int n_images, int Hc, int Wc, int32_t *geoms_out_host)
+{
+    if (!descs_host || !geoms_out_host || n_images < 1 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_images < 1 or image_size <= 0)", who);
+    for (int i = 0; i < n_images; ++i) {
+        const y3_image_desc &d = descs_host[i];
+        if (!image_mode_ok(d.mode))
+            return fail(Y3_ERR_INVALID, "%s: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
+        if (d.height < 1 || d.width < 1)
+            return fail(Y3_ERR_INVALID, "%s: image %d: height and width must be at least 1 (got %d x %d)", who, i,
+                        d.height, d.width);
+    }
+    static_assert(sizeof(y3::LetterboxGeom) == 4 * sizeof(int32_t), "a geometry is four int32");
+    for (int i = 0; i < n_images; ++i) {
+        const y3::LetterboxGeom g = image_geom(descs_host[i].mode, descs_host[i].height, descs_host[i].width, Hc, Wc);
+        memcpy(geoms_out_host + (size_t)i * 4, &g, sizeof(g));
+    }
+    return Y3_OK;
+}
+
+y3_status y3_letterbox_geometry_hw(const y3_image_desc *descs_host, int n_images, int canvas_h, int canvas_w, int32_t *geoms_out_host)
+try {
+    return letterbox_geometry_hw("y3_letterbox_geometry_hw", descs_host, n_images, canvas_h, canvas_w, geoms_out_host);
+}
+Y3_CATCH("y3_letterbox_geometry_hw")
+
+y3_status y3_letterbox_geometry(const y3_image_desc *descs_host, int n_images, int image_size, int32_t *geoms_out_host)
+try {
+    return letterbox_geometry_hw("y3_letterbox_geometry", descs_host, n_images, image_size, image_size, geoms_out_host);
+}
+Y3_CATCH("y3_letterbox_geometry")
+
+static y3_status unletterbox_hw(const char *who, void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                int max_boxes, int Hc, int Wc, void *stream)
+{
+    if (!packed_dev || !num_valid_dev || !geoms_host || batch < 1 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, batch < 1 or image_size <= 0)", who);
+    if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES)
+        return fail(Y3_ERR_INVALID, "%s: max_boxes must be in [1,%d]", who, Y3_MAX_OUTPUT_BOXES);
+    // every check before the first launch: the rows are rewritten in place
+    for (int i = 0; i < batch; ++i) {
+        y3::LetterboxGeom g;
+        memcpy(&g, geoms_host + (size_t)i * 4, sizeof(g));
+        if (!y3::letterbox_geom_fits(g, Hc, Wc))
+            return fail(Y3_ERR_INVALID, "%s: image %d: geometry %d x %d at (%d, %d) does not lie inside %d x %d", who, i,
+                        g.sh, g.sw, g.top, g.left, Hc, Wc);
+    }
+    unsigned *packed = static_cast<unsigned *>(packed_dev);
+    for (int i0 = 0; i0 < batch; i0 += y3::kUnletterboxTableImages) {
+        const int n = std::min(y3::kUnletterboxTableImages, batch - i0);
+        y3::LetterboxGeom geoms[y3::kUnletterboxTableImages];
+        memcpy(geoms, geoms_host + (size_t)i0 * 4, (size_t)n * sizeof(y3::LetterboxGeom));
+        hipError_t e = y3::launch_unletterbox(packed + (size_t)i0 * max_boxes * 7, num_valid_dev + i0, geoms, n, max_boxes, Hc, Wc,
+                                              (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    }
+    return Y3_OK;
+}
+
+y3_status y3_unletterbox_detections_hw(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                       int max_boxes, int canvas_h, int canvas_w, void *stream)
+try {
+    return unletterbox_hw("y3_unletterbox_detections_hw", packed_dev, num_valid_dev, geoms_host, batch, max_boxes, canvas_h, canvas_w, stream);
+}
+Y3_CATCH("y3_unletterbox_detections_hw")
+
+y3_status y3_unletterbox_detections(void *packed_dev, const int32_t *num_valid_dev, const int32_t *geoms_host, int batch,
+                                    int max_boxes, int image_size, void *stream)
+try {
+    return unletterbox_hw("y3_unletterbox_detections", packed_dev, num_valid_dev, geoms_host, batch, max_boxes, image_size, image_size, stream);
+}
+Y3_CATCH("y3_unletterbox_detections")
+
+y3_status y3_evaluate_detections(const void *packed_dev, const int32_t *num_valid_dev, int batch, int max_boxes,
+                                 const float *gt_boxes_dev, const int32_t *gt_classes_dev, const int32_t *gt_count_dev, int max_gt,
+                                 int nclasses, float iou_threshold, const float *score_thresholds_host, int n_thresholds,
+                                 int one_class, int64_t *counters_dev, void *stream)
+try {
+    if (!packed_dev || !num_valid_dev || !gt_boxes_dev || !gt_classes_dev || !gt_count_dev || !score_thresholds_host || !counters_dev)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: null pointer");
+    if (batch < 1) return fail(Y3_ERR_INVALID, "y3_evaluate_detections: batch must be at least 1 (got %d)", batch);
+    if (max_boxes < 1 || max_boxes > y3::kEvalMaxBoxes)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: max_boxes must be in [1,%d] (got %d)", y3::kEvalMaxBoxes, max_boxes);
+    if (max_gt < 1 || max_gt > y3::kEvalMaxGt)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: max_gt must be in [1,%d] (got %d)", y3::kEvalMaxGt, max_gt);
+    if (nclasses < 1 || nclasses > y3::kEvalMaxClasses)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: nclasses must be in [1,%d] (got %d)", y3::kEvalMaxClasses, nclasses);
+    if (n_thresholds < 1 || n_thresholds > y3::kEvalMaxThresholds)
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: n_thresholds must be in [1,%d] (got %d)", y3::kEvalMaxThresholds, n_thresholds);
+    if (((uintptr_t)packed_dev & 3) || ((uintptr_t)gt_boxes_dev & 3) || ((uintptr_t)counters_dev & 7))
+        return fail(Y3_ERR_INVALID, "y3_evaluate_detections: packed / gt_boxes not 4-byte or counters not 8-byte aligned");
+    y3::EvalThresholds thr{};
+    for (int t = 0; t < n_thresholds; ++t) thr.s[t] = score_thresholds_host[t];
+    hipError_t e = y3::launch_evaluate(packed_dev, num_valid_dev, batch, max_boxes, gt_boxes_dev, gt_classes_dev, gt_count_dev, max_gt,
+                                       nclasses, iou_threshold, thr, n_thresholds, one_class != 0, counters_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_evaluate_detections launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_evaluate_detections")
+
+// ------------------------------------------------------------------------------------------ validation loss
+namespace {
+// The checks and the by-value geometry the two loss entries share: grid sizes, first decode row per scale, anchors.
+y3_status loss_geometry(const char *who, const int32_t *grid_sizes, const float *anchors_host, int batch, int max_gt, int nclasses,
+                        y3::LossGeom *geo)
+{
+    if (!grid_sizes || !anchors_host) return fail(Y3_ERR_INVALID, "%s: null pointer", who);
+    if (batch < 1) return fail(Y3_ERR_INVALID, "%s: batch must be at least 1 (got %d)", who, batch);
+    if (max_gt < 1 || max_gt > y3::kEvalMaxGt) return fail(Y3_ERR_INVALID, "%s: max_gt must be in [1,%d] (got %d)", who, y3::kEvalMaxGt, max_gt);
+    if (nclasses < 1 || nclasses > y3::kEvalMaxClasses)
+        return fail(Y3_ERR_INVALID, "%s: nclasses must be in [1,%d] (got %d)", who, y3::kEvalMaxClasses, nclasses);
+    int off = 0;
+    for (int s = 0; s < 3; ++s) {
+        if (grid_sizes[s] < 1 || grid_sizes[s] > y3::kLossMaxGrid)
+            return fail(Y3_ERR_INVALID, "%s: grid_sizes[%d] must be in [1,%d] (got %d)", who, s, y3::kLossMaxGrid, grid_sizes[s]);
+        geo->g[s] = grid_sizes[s];
+        geo->off[s] = off;
+        off += 3 * grid_sizes[s] * grid_sizes[s];
+        for (int a = 0; a < 3; ++a) {
+            geo->anchors[s][a][0] = anchors_host[(s * 3 + a) * 2 + 0];
+            geo->anchors[s][a][1] = anchors_host[(s * 3 + a) * 2 + 1];
+        }
+    }
+    return Y3_OK;
+}
+}  // namespace
+
+y3_status y3_yolo_assign_targets(const float *gt_boxes_dev, const int32_t *gt_classes_dev, const int32_t *gt_count_dev, int batch,
+                                 int max_gt, int nclasses, const int32_t grid_sizes[3], const float *anchors_host,
+                                 int32_t *cells_dev, void *stream)
+try {
+    if (!gt_boxes_dev || !gt_classes_dev || !gt_count_dev || !cells_dev)
+        return fail(Y3_ERR_INVALID, "y3_yolo_assign_targets: null pointer");
+    y3::LossGeom geo{};
+    y3_status st = loss_geometry("y3_yolo_assign_targets", grid_sizes, anchors_host, batch, max_gt, nclasses, &geo);
+    if (st != Y3_OK) return st;
+    if (((uintptr_t)gt_boxes_dev & 3) || ((uintptr_t)gt_classes_dev & 3) || ((uintptr_t)gt_count_dev & 3) || ((uintptr_t)cells_dev & 3))
+        return fail(Y3_ERR_INVALID, "y3_yolo_assign_targets: a device pointer is not 4-byte aligned");
+    hipError_t e = y3::launch_assign_targets(gt_boxes_dev, gt_classes_dev, gt_count_dev, batch, max_gt, nclasses, geo, cells_dev,
+                                             (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_yolo_assign_targets launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_yolo_assign_targets")
+
+y3_status y3_yolo_loss(const float *const grids_dev[3], const int32_t grid_sizes[3], int batch, int nclasses,
+                       const float *anchors_host, const float *gt_boxes_dev, const int32_t *gt_classes_dev,
+                       const int32_t *cells_dev, int max_gt, double *loss_dev, void *stream)
+try {
+    if (!grids_dev || !gt_boxes_dev || !gt_classes_dev || !cells_dev || !loss_dev)
+        return fail(Y3_ERR_INVALID, "y3_yolo_loss: null pointer");
+    y3::LossGeom geo{};
+    y3_status st = loss_geometry("y3_yolo_loss", grid_sizes, anchors_host, batch, max_gt, nclasses, &geo);
+    if (st != Y3_OK) return st;
+    y3::LossGrids grids{};
+    for (int s = 0; s < 3; ++s) {
+        if (!grids_dev[s] || ((uintptr_t)grids_dev[s] & 3))
+            return fail(Y3_ERR_INVALID, "y3_yolo_loss: grid %d null or not 4-byte aligned", s);
+        grids.p[s] = grids_dev[s];
+    }
+    if (((uintptr_t)gt_boxes_dev & 3) || ((uintptr_t)gt_classes_dev & 3) || ((uintptr_t)cells_dev & 3) || ((uintptr_t)loss_dev & 7))
+        return fail(Y3_ERR_INVALID, "y3_yolo_loss: gt_boxes / gt_classes / cells not 4-byte or loss not 8-byte aligned");
+    hipError_t e = y3::launch_yolo_loss(grids, geo, batch, nclasses, gt_boxes_dev, gt_classes_dev, cells_dev, max_gt, loss_dev,
+                                        (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_yolo_loss launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_yolo_loss")
+
+// ------------------------------------------------------------------------------------------ TFRecord checksum
+uint32_t y3_crc32c(const void *data_host, size_t nbytes)
+{
+    // slicing-by-8 over the reflected Castagnoli polynomial
+    static uint32_t T[8][256];
+    static bool ready = [] {
+        for (uint32_t i = 0; i < 256; ++i) {
+            uint32_t c = i;
+            for (int k = 0; k < 8; ++k) c = (c >> 1) ^ (0x82F63B78u & (0u - (c & 1u)));
+            T[0][i] = c;
+        }
+        for (uint32_t i = 0; i < 256; ++i)
+            for (int t = 1; t < 8; ++t) T[t][i] = (T[t - 1][i] >> 8) ^ T[0][T[t - 1][i] & 0xFF];
+        return true;
+    }();
+    (void)ready;
+    const unsigned char *p = static_cast<const unsigned char *>(data_host);
+    uint32_t c = 0xFFFFFFFFu;
+    while (nbytes >= 8) {
+        uint32_t lo, hi;
+        memcpy(&lo, p, 4);
+        memcpy(&hi, p + 4, 4);
+        lo ^= c;
+        c = T[7][lo & 0xFF] ^ T[6][(lo >> 8) & 0xFF] ^ T[5][(lo >> 16) & 0xFF] ^ T[4][lo >> 24] ^ T[3][hi & 0xFF] ^
+            T[2][(hi >> 8) & 0xFF] ^ T[1][(hi >> 16) & 0xFF] ^ T[0][hi >> 24];
+        p += 8;
+        nbytes -= 8;
+    }
+    while (nbytes--) c = (c >> 8) ^ T[0][(c ^ *p++) & 0xFF];
+    return c ^ 0xFFFFFFFFu;
+}
+
+// ------------------------------------------------------------------------------------------ decode entry points
+y3_status y3_yolo_decode_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
+                            const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
+try {
+    return yolo_decode_hw("y3_yolo_decode_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode_hw")
+
+y3_status y3_yolo_decode_scores_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
+                                   const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev,
+                                   float *scores_dev, void *stream)
+try {
+    return y3::decode_scores_hw("y3_yolo_decode_scores_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode_scores_hw")
+
+y3_status y3_yolo_decode(const float *const grids_dev[3], const int32_t grid_sizes[3], int batch, int nclasses,
+                         const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
+try {
+    if (!conf_dev || !probs_dev) return fail(Y3_ERR_INVALID, "y3_yolo_decode: null output");
+    if (!grid_sizes) return fail(Y3_ERR_INVALID, "y3_yolo_decode: bad argument");
+    const int32_t hw[3][2] = {{grid_sizes[0], grid_sizes[0]}, {grid_sizes[1], grid_sizes[1]}, {grid_sizes[2], grid_sizes[2]}};
+    return yolo_decode_hw("y3_yolo_decode", grids_dev, hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode")
+
+y3_status y3_yolo_decode_scores(const float *const grids_dev[3], const int32_t grid_sizes[3], int batch, int nclasses,
+                                const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev,
+                                float *scores_dev, void *stream)
+try {
+    if (!class_idx_dev || !scores_dev) return fail(Y3_ERR_INVALID, "y3_yolo_decode_scores: null output");
+    if (!grid_sizes) return fail(Y3_ERR_INVALID, "y3_yolo_decode_scores: bad argument");
+    const int32_t hw[3][2] = {{grid_sizes[0], grid_sizes[0]}, {grid_sizes[1], grid_sizes[1]}, {grid_sizes[2], grid_sizes[2]}};
+    return y3::decode_scores_hw("y3_yolo_decode_scores", grids_dev, hw, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode_scores")
+
+y3_status y3_class_scores(const float *conf_dev, const float *probs_dev, int batch, int n, int nclasses,
+                          int64_t *class_idx_dev, float *scores_dev, void *stream)
+try {
+    if (!conf_dev || !probs_dev || !class_idx_dev || !scores_dev || batch <= 0 || n <= 0 || nclasses <= 0)
+        return fail(Y3_ERR_INVALID, "y3_class_scores: bad argument");
+    hipError_t e = y3::launch_class_scores(conf_dev, probs_dev, (size_t)batch * n, nclasses, class_idx_dev, scores_dev,
+                                           (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_class_scores launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_class_scores")
+
+size_t y3_nms_workspace_bytes(int batch, int n) { return (batch > 0 && n > 0) ? y3::nms_workspace_bytes(batch, n) : 0; }
+
+y3_status y3_nms_padded(const float *bboxes_dev, const float *scores_dev, int batch, int n, int max_output_size,
+                        float iou_threshold, float score_threshold, int32_t *selected_idx_dev,
+                        int32_t *num_valid_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
+try {
+    if (!bboxes_dev || !scores_dev || !selected_idx_dev || !num_valid_dev || batch <= 0 || n <= 0)
+        return fail(Y3_ERR_INVALID, "y3_nms_padded: bad argument");
+    if (max_output_size <= 0 || max_output_size > 1024)
+        return fail(Y3_ERR_INVALID, "y3_nms_padded: max_output_size must be in [1,1024]");
+    if ((uintptr_t)bboxes_dev & 15) return fail(Y3_ERR_INVALID, "y3_nms_padded: bboxes not 16-byte aligned");
+    if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
+        return fail(Y3_ERR_INVALID, "y3_nms_padded: iou_threshold <= 0 together with score_threshold < 0 is not supported");
+    if (!workspace_dev || workspace_bytes < y3::nms_workspace_bytes(batch, n))
+        return fail(Y3_ERR_INVALID, "y3_nms_padded: workspace too small (need %zu bytes)", y3::nms_workspace_bytes(batch, n));
+    hipError_t e = y3::launch_nms(bboxes_dev, scores_dev, batch, n, max_output_size, iou_threshold, score_threshold,
+                                  selected_idx_dev, num_valid_dev, workspace_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_nms_padded launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_nms_padded")
+
+y3_status y3_pack_detections(const float *bboxes_dev, const int64_t *class_idx_dev, const float *scores_dev,
+                             const int32_t *selected_idx_dev, const int32_t *num_valid_dev, int batch, int n,
+                             int max_out, void *packed_dev, void *stream)
+try {
+    if (!bboxes_dev || !class_idx_dev || !scores_dev || !selected_idx_dev || !num_valid_dev || !packed_dev ||
+        batch <= 0 || n <= 0 || max_out <= 0)
+        return fail(Y3_ERR_INVALID, "y3_pack_detections: bad argument");
+    hipError_t e = y3::launch_pack(bboxes_dev, class_idx_dev, scores_dev, selected_idx_dev, num_valid_dev, batch, n,
+                                   max_out, packed_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_pack_detections launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_pack_detections")
+
+}  // extern "C"

@@ -1,0 +1,215 @@
+// Planning a net for a batch, a canvas and a mode (y3_net_plan): tensor liveness and the activation arena, the lane streams, the
+// scratch of y3_net_detect, and what the planned net costs in FLOPs.
+#include <algorithm>
+#include <cstdlib>
+
+#include "y3_host.h"
+
+void y3::free_plan(y3_net *n)
+{
+    if (n->det_buf) (void)hipFree(n->det_buf);
+    n->det_buf = nullptr;
+    n->det_bytes = 0;
+    if (n->split_ws) (void)hipFree(n->split_ws);
+    n->split_ws = nullptr;
+    n->split_ws_lane = 0;
+    n->split_ws_lanes = 0;
+    for (void *p : n->blocks) (void)hipFree(p);
+    n->blocks.clear();
+    n->tdev.assign(n->tensors.size(), nullptr);
+}
+
+// forked streams / events of the concurrent sub-batches: created at plan time so that a forward enqueues work only
+static y3_status ensure_lanes(y3_net *net)
+{
+    if (net->fork_ev) return Y3_OK;
+    HIP_TRY(hipEventCreateWithFlags(&net->fork_ev, hipEventDisableTiming));
+    for (int i = 0; i < Y3_MAX_LANES; ++i) {
+        HIP_TRY(hipStreamCreateWithFlags(&net->lane_stream[i], hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(&net->join_ev[i], hipEventDisableTiming));
+    }
+    return Y3_OK;
+}
+
+// Arena blocks for the plan's tensors from their liveness [first, last] over the op list
+static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const std::vector<int> &last)
+{
+    const int nt = (int)net->tensors.size();
+    struct Blk { void *p; size_t bytes; int free_at; };
+    std::vector<Blk> pool;
+    // allocate in order of first definition; the image batch and the head grids are caller-owned
+    std::vector<int> order;
+    for (int t = 0; t < nt; ++t) {
+        const bool external = t == net->input_tensor || net->out_slot[t] >= 0;
+        if (first[t] >= 0 && !external) order.push_back(t);
+    }
+    std::sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
+    for (int t : order) {
+        const int until = (net->keep_all || net->dense[t]) ? (int)net->ops.size() + 1 : last[t];
+        int pick = -1;
+        for (int k = 0; k < (int)pool.size() && !net->dense[t]; ++k)
+            if (pool[k].free_at < first[t] && pool[k].bytes >= net->tbytes[t] &&
+                (pick < 0 || pool[k].bytes < pool[pick].bytes))
+                pick = k;
+        if (pick < 0) {
+            void *p = nullptr;
+            hipError_t e = hipMalloc(&p, net->tbytes[t] + 4096);
+            if (e != hipSuccess) {
+                y3::free_plan(net);
+                return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) failed: %s", net->tbytes[t], hipGetErrorString(e));
+            }
+            net->blocks.push_back(p);
+            pool.push_back({p, net->tbytes[t], until});
+            pick = (int)pool.size() - 1;
+        }
+        pool[pick].free_at = until;
+        net->tdev[t] = pool[pick].p;
+        net->tblock[t] = pool[pick].bytes;
+    }
+    return Y3_OK;
+}
+
+y3::DetectLayout y3::detect_layout(const y3_net *net, int batch)
+{
+    const size_t per = (size_t)3 * (5 + net->nclasses);
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    DetectLayout L{};
+    size_t n = 0, at = 0;
+    for (int i = 0; i < 3; ++i) {
+        L.gs[i][0] = rows(net, net->outputs[i]);
+        L.gs[i][1] = cols(net, net->outputs[i]);
+        L.grid[i] = at;
+        at += up((size_t)batch * L.gs[i][0] * L.gs[i][1] * per * 4);
+        n += (size_t)3 * L.gs[i][0] * L.gs[i][1];
+    }
+    L.n_boxes = n;
+    L.boxes = at;
+    L.cls = L.boxes + up((size_t)batch * n * 16);       // class indices (i64)
+    L.scores = L.cls + up((size_t)batch * n * 8);
+    L.sel = L.scores + up((size_t)batch * n * 4);       // selected indices
+    L.nms_ws = L.sel + up((size_t)batch * Y3_MAX_OUTPUT_BOXES * 4);
+    L.total = L.nms_ws + nms_workspace_bytes(batch, (int)n);
+    return L;
+}
+
+extern "C" {
+
+y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int dtype)
+try {
+    if (!net || max_batch <= 0 || height <= 0 || width <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
+    if (dtype != Y3_DTYPE_F32 && dtype != Y3_DTYPE_BF16 && dtype != Y3_DTYPE_F32X3 && dtype != Y3_DTYPE_F32X2)
+        return fail(Y3_ERR_INVALID, "y3_net_plan: unknown dtype %d", dtype);
+    for (const y3_tensor_desc &t : net->tensors)
+        if (t.div <= 0 || height % t.div || width % t.div) {
+            if (height == width) return fail(Y3_ERR_INVALID, "y3_net_plan: image_size %d not divisible by %d", height, t.div);   // the square call's text, as ever
+            return fail(Y3_ERR_INVALID, "y3_net_plan_hw: image size %d x %d (height x width) not divisible by %d", height, width, t.div);
+        }
+    if (dtype == Y3_DTYPE_F32X2)
+        for (size_t i = 0; i < net->convs.size(); ++i)
+            if (net->convs[i].loaded && !net->convs[i].x2_ok)
+                return fail(Y3_ERR_INVALID, "y3_net_plan: conv %zu has a BN-scaled weight outside the fp16 range (|w| >= 65504); "
+                                            "the two-plane mode cannot represent it, use Y3_DTYPE_F32 or Y3_DTYPE_F32X3", i);
+    Y3_ENTER_DEVICE(net);
+    if (net->n_cus <= 0) {   // once per net: the launch path itself makes no device query
+        int cus = 0;
+        HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, net->device));
+        net->n_cus = cus > 0 ? cus : 256;
+    }
+    y3::free_plan(net);
+    net->max_batch = max_batch;
+    net->height = height;
+    net->width = width;
+    net->dtype = dtype;
+    const int nt = (int)net->tensors.size();
+    // liveness over the op list; tensors with equal lifetime class share blocks (first-fit free list)
+    std::vector<int> first(nt, -1), last(nt, -1);
+    auto touch = [&](int t, int i) {
+        if (t < 0) return;
+        if (first[t] < 0) first[t] = i;
+        last[t] = i;
+    };
+    for (int i = 0; i < (int)net->ops.size(); ++i) {
+        const Op &o = net->ops[i];
+        if (o.kind == 0) {
+            const y3_conv_desc &d = net->convs[o.index].d;
+            touch(d.src0, i); touch(d.src1, i); touch(d.residual, i); touch(d.dst, i);
+        } else {
+            const y3_aux_desc &a = net->aux[o.index];
+            touch(a.src0, i); touch(a.src1, i); touch(a.dst, i);
+        }
+    }
+    // Invariant the launch path relies on: in a non-fp32 plan every output that a shortcut or first-layer conv writes is staged
+    // (output_staged), so a launch that stores an fp32 grid itself (out_slot >= 0) is never a first layer and never has a residual.
+    net->staged.assign(nt, 0);
+    net->out_slot.assign(nt, -1);
+    for (int k = 2; k >= 0; --k) {   // a tensor named twice takes the first grid
+        const int t = net->outputs[k];
+        net->staged[t] = dtype != Y3_DTYPE_F32 && y3::output_staged(net, t);
+        net->out_slot[t] = net->staged[t] ? -1 : (signed char)k;
+        if (net->staged[t]) last[t] = (int)net->ops.size();          // alive until the final conversion
+    }
+    // chunked leading segment: every op before the (early_convs)-th conv; tensors it writes get blocks of their own,
+    // laid out densely by image, because they are rewritten chunk after chunk while earlier chunks' results are still live
+    net->early_ops = 0;
+    if (net->early_convs > 0 && net->early_chunk > 0) {
+        int seen = 0;
+        for (int i = 0; i < (int)net->ops.size(); ++i) {
+            if (net->ops[i].kind == 0 && seen++ == net->early_convs) break;
+            net->early_ops = i + 1;
+        }
+        if (net->early_ops >= (int)net->ops.size()) net->early_ops = 0;
+    }
+    net->dense.assign(nt, 0);
+    for (int t = 0; t < nt; ++t) net->dense[t] = (first[t] >= 0 && first[t] < net->early_ops) ? 1 : 0;
+    for (int t = 0; t < nt; ++t) {
+        net->tbytes[t] = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels * y3::conv_family(dtype)->elem_bytes;
+        if (net->tbytes[t] >= 0xFFFFFFF0ull && first[t] >= 0)
+            return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, net->tbytes[t]);
+    }
+    if (y3_status st = place_tensors(net, first, last); st != Y3_OK) return st;
+    if (y3_status st = ensure_lanes(net); st != Y3_OK) return st;
+    {   // Y3_STEM_MODE (tools: same-process-tree A/B of the stem forms) overrides the default, not an explicit setter call
+        static const int env = [] { const char *e = getenv("Y3_STEM_MODE"); return e ? atoi(e) : -1; }();
+        if (env >= 0 && env <= 2 && !net->stem_mode_set) net->stem_mode = env;
+    }
+    net->stem_fused = net->stem_mode && y3::stem_applicable(net);
+    net->stem_conv2 = net->stem_fused && net->stem_mode == 1 && y3::stem_conv2_applicable(net);
+    {   // Y3_LOW_LATENCY (tools/ab_libs.py: a low-latency plan in a child process that knows nothing of it) overrides the default, not the setter
+        static const int env = [] { const char *e = getenv("Y3_LOW_LATENCY"); return e ? atoi(e) : -1; }();
+        if ((env == 0 || env == 1) && !net->low_latency_set) net->low_latency = env == 1;
+    }
+    if (net->nclasses > 0) {   // scratch of y3_net_detect: no allocation inside the stream-ordered call
+        const size_t bytes = y3::detect_layout(net, max_batch).total;
+        hipError_t e = hipMalloc(&net->det_buf, bytes);
+        if (e != hipSuccess) {
+            y3::free_plan(net);
+            return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) for the detect scratch failed: %s", bytes, hipGetErrorString(e));
+        }
+        net->det_bytes = bytes;
+    }
+    if (y3_status st = y3::resolve_splits(net); st != Y3_OK) {
+        y3::free_plan(net);
+        return st;
+    }
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_plan_hw")
+
+y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype)
+try {
+    return y3_net_plan_hw(net, max_batch, image_size, image_size, dtype);
+}
+Y3_CATCH("y3_net_plan")
+
+double y3_net_flops_per_image(const y3_net *net)
+{
+    if (!net || !net->height) return 0.0;
+    double tot = 0;
+    for (const ConvSlot &c : net->convs) {
+        const double ho = net->height / c.d.out_div, wo = net->width / c.d.out_div;
+        tot += 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * wo;
+    }
+    return tot;
+}
+
+}  // extern "C"

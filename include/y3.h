@@ -145,8 +145,9 @@ y3_status y3_net_set_k_chunk(y3_net *net, int channels);
  * S is decided at plan time by y3_choose_split_k from the conv's shape, its tile at the planned max_batch and the device's compute
  * units -- never from the rows of a call, so inside one plan an image's result does not depend on its batch or position.  S = 1 (the
  * ordinary launch) wherever the planned batch already fills the chip.  Never split: the first layer, the fused stem, the weight-
- * resident tile 33, the three detection-head convs (y3_net_detect and the composed route stay bit-identical), any plan that is not
- * Y3_DTYPE_F32.  The same products in another summation order: results differ from the default plan's in the last bits (as
+ * resident tile 33, the three detection-head convs (y3_net_detect and the composed route stay bit-identical), and -- by these three calls --
+ * any plan that is not Y3_DTYPE_F32 (a Y3_DTYPE_BF16 plan splits through the _bf16 calls below; the plane-split modes never split).
+ * The same products in another summation order: results differ from the default plan's in the last bits (as
  * y3_net_set_k_chunk says of itself).  With it off nothing changes.
  * y3_net_set_split_k: S of one conv: -1 = y3_choose_split_k when low latency is on (else 1), 1 = off, 2..16 = that value whether or not
  * low latency is on.  An ineligible conv or S > the conv's K tiles (K / 32) is refused here with Y3_ERR_INVALID and a message, not
@@ -157,6 +158,21 @@ y3_status y3_net_set_low_latency(y3_net *net, int on);
 y3_status y3_net_set_split_k(y3_net *net, int conv_slot, int S);
 int y3_net_get_split_k(const y3_net *net, int conv_slot);
 int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice);
+/* Low-latency bf16 plans: the same for Y3_DTYPE_BF16 plans, with a switch, a request and a decision of their own beside the fp32 ones
+ * (the fp32 calls above keep answering for fp32 plans only: y3_net_get_split_k is 1 on a bf16 plan, y3_net_set_split_k refuses one).
+ * The rule and its inputs are the same -- y3_choose_split_k on the conv's shape, its bf16 tile at the planned max_batch and the compute
+ * units -- with K tiles of 64 (K / 64), and only for convs of at least 32 K tiles (K >= 2048: measured, the shorter launches lose to the
+ * second launch; a forced S is taken as given).  A slice stores raw fp32 accumulators; the second launch adds the slices in the order 0, 1, ...,
+ * S-1 and applies the unsplit epilogue's own operations (* scale + shift, leaky, + the bf16 shortcut, one rounding to bf16), so equal
+ * sums give the unsplit launch's bits.  Never split in a bf16 plan: the first layer and the convs inside the fused stem, the weight-
+ * resident tile 32, the BK = 32 tiles (Cin = 32 layers), any conv whose tile at the planned rows is not 11 or 12 (the 64x64 and 64x128
+ * LDS-DMA tiles: the only ones with a split form), a conv storing bf16 with Cout % 8 != 0, the three detection-head convs.
+ * y3_net_set_low_latency_bf16: 0 / 1, off by default.  y3_net_set_split_k_bf16: -1 = the rule when the bf16 switch is on (else 1), 1 = off,
+ * 2..16 forced; an ineligible conv, S > K / 64, or a forced value on a planned net whose dtype is not Y3_DTYPE_BF16 is refused with
+ * Y3_ERR_INVALID and a message.  y3_net_get_split_k_bf16: the value in force after planning; 1 before, 1 on a plan that is not bf16. */
+y3_status y3_net_set_low_latency_bf16(y3_net *net, int on);
+y3_status y3_net_set_split_k_bf16(y3_net *net, int conv_slot, int S);
+int y3_net_get_split_k_bf16(const y3_net *net, int conv_slot);
 y3_status y3_net_keep_activations(y3_net *net, int keep);
 /* 1 (default): when the program starts with conv0 (3x3/1, 3 -> 32) feeding only conv1 (3x3/2, 32 -> 64) -- the Darknet-53
  * stem, reference config/models/yolov3/backbone.yaml layers 1-2 -- and the plan is fp32 or bf16 without keep_activations,

@@ -3,7 +3,8 @@
 are set from.  For every eligible conv and every S of --splits (clamped to the conv's K tiles) the launch -- slices plus finish
 launch -- is timed alone with y3_net_profile_convs, median of --repeats; the table gives per conv the time at every S, the best S,
 the S the rule picks and what the rule leaves on the table, then the sums over the conv stack: unsplit, rule, best per conv.
-    python tools/sweep_split_k.py [--size 416] [--batches 1 2 4 8] [--out profiles/latency_splitk_sweep.txt]"""
+    python tools/sweep_split_k.py [--size 416] [--batches 1 2 4 8] [--dtype f32] [--out profiles/latency_splitk_sweep.txt]
+--dtype bf16 sweeps a bf16 plan through y3_net_set_split_k_bf16 (K tiles of 64; profiles/latency_bf16_splitk_sweep.txt)."""
 import argparse
 import os
 import sys
@@ -20,12 +21,14 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8])
     ap.add_argument("--splits", type=int, nargs="+", default=[1, 2, 3, 4, 6, 8, 12, 16])
     ap.add_argument("--repeats", type=int, default=15)
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    bf16 = a.dtype == "bf16"
 
     import torch
     import yolo_v3_tf2_amd  # noqa: F401
-    from yolo_v3_tf2_amd import runtime
+    from yolo_v3_tf2_amd import _lib, runtime
     from yolo_v3_tf2_amd.graph import load_program
     from yolo_v3_tf2_amd.weights import synthetic_weights
 
@@ -39,26 +42,29 @@ def main():
     net = runtime.Net(program)
     net.load_weights(synthetic_weights(program))
     n = len(net.conv_ops)
-    say(f"# tools/sweep_split_k.py  device: {torch.cuda.get_device_name(0)}  fp32; ms per conv launch alone (split: slices + finish), median of {a.repeats}")
+    set_split, get_split, set_ll = ((net.set_split_k_bf16, net.split_k_bf16, net.set_low_latency_bf16) if bf16 else
+                                    (net.set_split_k, net.split_k, net.set_low_latency))
+    dtype, bk = (_lib.Y3_DTYPE_BF16, 64) if bf16 else (_lib.Y3_DTYPE_F32, 32)
+    say(f"# tools/sweep_split_k.py  device: {torch.cuda.get_device_name(0)}  {'bf16' if bf16 else 'fp32'}; ms per conv launch alone (split: slices + finish), median of {a.repeats}")
     for S_img in a.size:
         for B in a.batches:
             x = torch.rand((B, S_img, S_img, 3), device="cuda")
             for i in range(n):
-                net.set_split_k(i, -1)
-            net.set_low_latency(True)
-            net.plan(B, S_img)
-            rule = [net.split_k(i) for i in range(n)]
-            net.set_low_latency(False)
+                set_split(i, -1)
+            set_ll(True)
+            net.plan(B, S_img, dtype)
+            rule = [get_split(i) for i in range(n)]
+            set_ll(False)
             ms, eff = {}, {}
             splits = sorted(set(a.splits) | set(rule))      # the rule's own values are always measured
             for S in splits:
                 for i, o in enumerate(net.conv_ops):
-                    want = min(S, max(1, o.size * o.size * o.cin // 32))
+                    want = min(S, max(1, o.size * o.size * o.cin // bk))
                     try:
-                        net.set_split_k(i, want if want > 1 else 1)
+                        set_split(i, want if want > 1 else 1)
                     except runtime.Y3Error:
-                        net.set_split_k(i, 1)
-                eff[S] = [net.split_k(i) for i in range(n)]
+                        set_split(i, 1)
+                eff[S] = [get_split(i) for i in range(n)]
                 net.profile_convs(x)
                 ms[S] = np.median([net.profile_convs(x) for _ in range(a.repeats)], axis=0)
             say(f"\n== {S_img} x {S_img}, batch {B}")

@@ -9,7 +9,9 @@ ONE process.  Two forms per plan:
 Reported per (size, batch, form): median and 99th percentile over all calls of a plan, the median of every window, whether the
 low-latency plan was below the default plan in every alternated pair of windows, and the gain beside the default plan's own spread
 between its windows.  The split in force per conv is printed for every plan.
-    python tools/time_latency.py [--sizes 416 608] [--batches 1 2 4 8] [--calls 1000] [--windows 4] [--per-conv] [--out profiles/latency.txt]
+    python tools/time_latency.py [--sizes 416 608] [--batches 1 2 4 8] [--calls 1000] [--windows 4] [--per-conv] [--dtype f32] [--out profiles/latency.txt]
+--dtype bf16 times bf16 plans, the low-latency one through y3_net_set_low_latency_bf16 (profiles/latency_bf16.txt).
+--control makes "on" a SECOND DEFAULT-PLAN net: the same launches from two net objects, i.e. what the protocol reads when nothing differs.
 --per-conv adds, for batch 1, the per-conv table of y3_net_profile_convs (each launch timed alone; a split conv is its two launches)."""
 import argparse
 import os
@@ -30,12 +32,15 @@ def main():
     ap.add_argument("--windows", type=int, default=4, help="alternated windows the calls are divided into")
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--per-conv", action="store_true")
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
+    ap.add_argument("--control", action="store_true", help="'on' is a second default-plan net (two net objects, the same launches)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    bf16 = a.dtype == "bf16"
 
     import torch
     import yolo_v3_tf2_amd  # noqa: F401
-    from yolo_v3_tf2_amd import runtime
+    from yolo_v3_tf2_amd import _lib, runtime
     from yolo_v3_tf2_amd.core.utils import get_anchors
     from yolo_v3_tf2_amd.graph import load_program
     from yolo_v3_tf2_amd.weights import synthetic_weights
@@ -53,17 +58,18 @@ def main():
     for name in ("off", "on"):
         net = runtime.Net(program)
         net.load_weights(weights)
-        net.set_low_latency(name == "on")
+        (net.set_low_latency_bf16 if bf16 else net.set_low_latency)(name == "on" and not a.control)
         nets[name] = net
-    say(f"# tools/time_latency.py  device: {torch.cuda.get_device_name(0)}  fp32  calls per plan and form: {a.calls} in {a.windows} alternated windows")
-    say("# off = default plan, on = low-latency plan (split-K); times in ms; 'pairs' = windows in which on < off")
+    say(f"# tools/time_latency.py  device: {torch.cuda.get_device_name(0)}  {'bf16' if bf16 else 'fp32'}  calls per plan and form: {a.calls} in {a.windows} alternated windows")
+    say("# off = default plan, on = " + ("a second net with the default plan (control)" if a.control else "low-latency plan (split-K)") +
+        "; times in ms; 'pairs' = windows in which on < off")
     per_window = max(1, a.calls // a.windows)
     for S in a.sizes:
         for B in a.batches:
             x = torch.rand((B, S, S, 3), device="cuda")
             for net in nets.values():
-                net.plan(B, S)
-            splits = [nets["on"].split_k(i) for i in range(len(nets["on"].conv_ops))]
+                net.plan(B, S, _lib.Y3_DTYPE_BF16 if bf16 else _lib.Y3_DTYPE_F32)
+            splits = [(nets["on"].split_k_bf16 if bf16 else nets["on"].split_k)(i) for i in range(len(nets["on"].conv_ops))]
             say(f"\n== {S} x {S}, batch {B}: {sum(s > 1 for s in splits)} convs split; S per conv: {splits}")
             step = {k: (lambda n=n: n.detect(x, anchors, 100, 0.5, 0.1)) for k, n in nets.items()}
             for k in step:

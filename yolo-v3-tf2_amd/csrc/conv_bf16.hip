@@ -8,6 +8,11 @@
 //   * MFMA 32x32x16: lane (r = l & 31, h = l >> 5) feeds A[row r][k = 16s + 8h .. +7] as one ds_read_b128;
 //   * epilogue through LDS: accumulators (+scale/shift, leaky) are written as an fp32 [BM][BN+4] tile, then every
 //     thread converts 8 consecutive channels (+ bf16 residual) and issues ONE 16-byte store -> full 128-B lines.
+//
+// Split-K (SPLIT = true, the low-latency bf16 plans of y3_net_set_low_latency_bf16; tiles 11 and 12 only): gridDim.y = S, slice y walks
+// K tiles [y*KT/S, (y+1)*KT/S) of the same tap-major walk and stores its raw fp32 accumulators (no epilogue, rows >= M included) straight
+// from the accumulator registers into slab y of a workspace [S][Mpad][CoutPad] fp32, through the slab's own buffer resource.
+// splitk_finish_bf16, a separate launch on the same stream, adds the slabs in the order 0, 1, ..., S-1 and applies the epilogue.
 #include <algorithm>
 #include <type_traits>
 
@@ -18,6 +23,30 @@ namespace y3 {
 __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
 {
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
+}
+
+// The epilogue's arithmetic, shared by the unsplit kernel and splitk_finish_bf16 so that equal accumulators give equal bits:
+// y = acc * scale + shift (two roundings: the build never contracts them), leaky as max(y, 0.1 y) ...
+__device__ __forceinline__ float bn_act(float acc, float sc, float sh, int leaky)
+{
+    float v = acc * sc + sh;
+    if (leaky) v = fmaxf(v, 0.1f * v);
+    return v;
+}
+// ... then eight consecutive channels: + the bf16 shortcut widened to fp32 (when there is one), one rounding to bf16
+__device__ __forceinline__ u32x4 add_res_pack(float (&v)[8], const u32x4 &rr, bool has_res)
+{
+    if (has_res) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[2 * k] = __uint_as_float(rr[k] << 16) + v[2 * k];
+            v[2 * k + 1] = __uint_as_float(rr[k] & 0xffff0000u) + v[2 * k + 1];
+        }
+    }
+    u32x4 out;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) out[k] = pack_bf16(v[2 * k], v[2 * k + 1]);
+    return out;
 }
 
 // DMA: operand tiles filled by direct-to-LDS buffer loads: unpadded 128-B rows, 16-B chunk index XOR-swizzled on the source
@@ -40,9 +69,10 @@ __device__ int y3_dbg_sel_k = -1;
 #define Y3_STAMP(k) do { } while (0)
 #endif
 
-template <int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, bool DMA = false, int MINW = 1, bool M16 = false>
+template <int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, bool DMA = false, int MINW = 1, bool M16 = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvArgs p)
 {
+    static_assert(!SPLIT || (DMA && BK == 64 && !M16 && !OUT_F32), "the split-K form is built for the LDS-DMA 32x32x16 tiles with BK = 64");
     Y3_STAMP(0);
 #ifdef Y3_PHASE_STAMPS
     if (threadIdx.x == 0 && blockIdx.x < 8192 && p.K == y3_dbg_sel_k) {
@@ -105,7 +135,15 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
 #pragma unroll
     for (int j = 0; j < BP; ++j) boff[j] = (unsigned)((n0 + j * RP + lrow) * p.K + lchunk) * 2u;
 
+    // K tiles of this workgroup's walk: all of them, or slice blockIdx.y of gridDim.y (starting at tile kt0 of the walk)
+    const int kt0 = SPLIT ? (int)blockIdx.y * (p.K / BK) / (int)gridDim.y : 0;
+    const int KT = SPLIT ? ((int)blockIdx.y + 1) * (p.K / BK) / (int)gridDim.y - kt0 : p.K / BK;
     int tap = 0, c0 = 0;
+    if constexpr (SPLIT) {   // the walk's state at tile kt0 (wave-uniform); a concat slice may begin in either source: the fetch picks it from c0
+        const int tpt = p.Cin / BK;
+        tap = kt0 / tpt;
+        c0 = (kt0 - tap * tpt) * BK;
+    }
     unsigned avoff[AP];
     unsigned avoff1[CONCAT ? AP : 1];
     auto set_tap = [&]() {   // as in conv_f32x3.hip; written out in both: DESIGN.md section 4, "One row per tile"
@@ -128,7 +166,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
     };
     set_tap();
 
-    int kglob = 0;
+    int kglob = SPLIT ? kt0 * BK : 0;
     // the K walk both fetch forms end with: the next BK channels of this tap, else the next tap
     auto advance_k = [&]() {
         kglob += BK;
@@ -192,7 +230,6 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
 #pragma unroll
             for (int e = 0; e < (M16 ? 4 : 16); ++e) acc[i][j][e] = 0.0f;
 
-    const int KT = p.K / BK;
     Y3_STAMP(1);
     if (DMA) {
         fetch_dma(0);
@@ -248,7 +285,26 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
     // ---- epilogue through LDS, one 32-row sub-tile of every wave per pass ----------------------------------
     // pass i: wave (wr, wc) writes rows [wr*32, +32) x cols [wc*32*TN, +32*TN) of a [WR*32][BN+4] fp32 tile (its i-th
     // accumulator row block), then all threads convert 8 consecutive channels each and store 16 B.
-    if constexpr (!OUT_F32) {
+    if constexpr (SPLIT) {
+        // raw accumulators -> slab blockIdx.y, straight from the registers: p.dst is the workspace, p.dst_bytes the bytes of ONE slab
+        // [Mpad][CoutPad] (Mpad = whole tiles, so every row of the tile has its place; the range check of the slab's own buffer resource
+        // drops anything else).  A store instruction writes two rows of 32 consecutive floats: whole 128-byte lines.
+        const __amdgpu_buffer_rsrc_t rss = buffer_rsrc(static_cast<const char *>(p.dst) + (size_t)blockIdx.y * p.dst_bytes, p.dst_bytes);
+        const int slab_row_bytes = p.CoutPad * 4;
+#pragma unroll
+        for (int j = 0; j < TN; ++j) {
+            const int n = n0 + (wc * TN + j) * 32 + fr;
+#pragma unroll
+            for (int i = 0; i < TM; ++i) {
+                const int mbase = m0 + (wr * TM + i) * 32 + 4 * fh;
+                const unsigned vbase = (unsigned)(mbase * p.CoutPad + n) * 4u;
+#pragma unroll
+                for (int e = 0; e < 16; ++e)
+                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i][j][e]), rss, (int)vbase,
+                                                          mfma32_row(e) * slab_row_bytes, 0);
+            }
+        }
+    } else if constexpr (!OUT_F32) {
         // ---- bf16 output: per-wave epilogue, no workgroup barrier ------------------------------------------------------
         // Every wave transposes its own 32 x (32 TN) fp32 blocks through a private LDS scratch (the operand tiles are dead
         // after the loop's last barrier) and stores whole 16-byte pieces of 8 channels: rows of 64 TN bytes per wave, full
@@ -292,18 +348,14 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
                     for (int j = 0; j < NB; ++j)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float v = acc[2 * i + mb][j][e] * sc[j] + sh[j];
-                            if (p.leaky) v = fmaxf(v, 0.1f * v);
-                            S[mfma16_row(e, fh, mb) * CW + j * 16 + fr] = v;
+                            S[mfma16_row(e, fh, mb) * CW + j * 16 + fr] = bn_act(acc[2 * i + mb][j][e], sc[j], sh[j], p.leaky);
                         }
             } else {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        float v = acc[i][j][e] * sc[j] + sh[j];
-                        if (p.leaky) v = fmaxf(v, 0.1f * v);
-                        S[mfma32_row(e, fh) * CW + j * 32 + fr] = v;
+                        S[mfma32_row(e, fh) * CW + j * 32 + fr] = bn_act(acc[i][j][e], sc[j], sh[j], p.leaky);
                     }
                 }
             }
@@ -319,16 +371,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
                 const f32x4 v0 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8);
                 const f32x4 v1 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8 + 4);
                 float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                if (res) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        v[2 * k] = __uint_as_float(rr[it][k] << 16) + v[2 * k];
-                        v[2 * k + 1] = __uint_as_float(rr[it][k] & 0xffff0000u) + v[2 * k + 1];
-                    }
-                }
-                u32x4 out;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) out[k] = pack_bf16(v[2 * k], v[2 * k + 1]);
+                const u32x4 out = add_res_pack(v, rr[it], res != nullptr);
                 if (mw + r < p.M) *reinterpret_cast<u32x4 *>(dstb + (size_t)(mw + r) * p.Cout + nw + pc * 8) = out;
             }
             // ... and the next pass's writes below this pass's reads
@@ -353,16 +396,12 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
                     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            float v = acc[2 * i + mb][j][e] * sc + sh;
-                            if (p.leaky) v = fmaxf(v, 0.1f * v);
-                            C[(wr * 32 + 16 * mb + mfma16_row(e, fh)) * CROW + nl] = v;
+                            C[(wr * 32 + 16 * mb + mfma16_row(e, fh)) * CROW + nl] = bn_act(acc[2 * i + mb][j][e], sc, sh, p.leaky);
                         }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        float v = acc[i][j][e] * sc + sh;
-                        if (p.leaky) v = fmaxf(v, 0.1f * v);
-                        C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = v;
+                        C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = bn_act(acc[i][j][e], sc, sh, p.leaky);
                     }
                 }
             }
@@ -380,6 +419,47 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvA
             if (p.dec.boxes != nullptr)
                 decode_rows_from_lds<NT>(C, CROW, EROWS, [&](int r) { return m0 + (r >> 5) * 32 * TM + i * 32 + (r & 31); }, p.M, p.dec);
         }
+    }
+}
+
+// Second half of a split-K conv: per element slab[0] + slab[1] + ... + slab[S-1], added in that order, then exactly the unsplit epilogue's
+// operations through the same helpers (bn_act, add_res_pack).  bf16 output: eight channels per thread, 16-byte loads and stores
+// (Cout % 8 == 0).  OUT_F32 (a conv that writes an fp32 net output itself, Cout = 255 in CoutPad = 256 included): one element per thread.
+template <bool OUT_F32>
+__global__ __launch_bounds__(256) void splitk_finish_bf16(const float *__restrict__ ws, int S, size_t slab_elems, int cout_pad,
+                                                          const float *__restrict__ scale, const float *__restrict__ shift,
+                                                          const unsigned short *__restrict__ residual, void *__restrict__ dst, int M, int cout,
+                                                          int leaky)
+{
+    constexpr int W = OUT_F32 ? 1 : 8;
+    const int per_row = cout / W;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)M * per_row) return;
+    const int m = (int)(idx / per_row);
+    const int n = ((int)(idx - (size_t)m * per_row)) * W;
+    const float *src = ws + (size_t)m * cout_pad + n;
+    if constexpr (OUT_F32) {
+        float v = *src;
+        for (int s = 1; s < S; ++s) v = v + src[(size_t)s * slab_elems];
+        static_cast<float *>(dst)[(size_t)m * cout + n] = bn_act(v, scale[n], shift[n], leaky);
+    } else {
+        f32x4 a0 = *reinterpret_cast<const f32x4 *>(src), a1 = *reinterpret_cast<const f32x4 *>(src + 4);
+        for (int s = 1; s < S; ++s) {
+            a0 = a0 + *reinterpret_cast<const f32x4 *>(src + (size_t)s * slab_elems);
+            a1 = a1 + *reinterpret_cast<const f32x4 *>(src + (size_t)s * slab_elems + 4);
+        }
+        const f32x4 sc0 = *reinterpret_cast<const f32x4 *>(scale + n), sc1 = *reinterpret_cast<const f32x4 *>(scale + n + 4);
+        const f32x4 sh0 = *reinterpret_cast<const f32x4 *>(shift + n), sh1 = *reinterpret_cast<const f32x4 *>(shift + n + 4);
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = bn_act(a0[k], sc0[k], sh0[k], leaky);
+            v[4 + k] = bn_act(a1[k], sc1[k], sh1[k], leaky);
+        }
+        const size_t o = (size_t)m * cout + n;
+        u32x4 rr{0u, 0u, 0u, 0u};
+        if (residual) rr = *reinterpret_cast<const u32x4 *>(residual + o);
+        *reinterpret_cast<u32x4 *>(static_cast<unsigned short *>(dst) + o) = add_res_pack(v, rr, residual != nullptr);
     }
 }
 
@@ -475,6 +555,49 @@ extern "C" int y3_dbg_copy_stamps(unsigned long long *dst, int n_words)
     return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(y3_dbg_stamps), (size_t)n_words * sizeof(unsigned long long));
 }
 #endif
+
+// The split-K form is instantiated for the two tiles a small plan lands on: 11 (64x64) and 12 (64x128), both LDS-DMA, BK 64, four waves
+template <int TN>
+static hipError_t launch_split_t(const ConvArgs &c, int grid, int S, hipStream_t s)
+{
+    constexpr size_t lds = 2 * (size_t)(64 + 64 * TN) * 128;   // the two operand stages; a split launch has no epilogue tile
+    if (c.src1) return launch_conv_kernel<conv_bf16_mfma<1, TN, 2, 2, 64, true, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+    return launch_conv_kernel<conv_bf16_mfma<1, TN, 2, 2, 64, false, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+}
+
+bool conv_bf16_split_tile(int tile) { return tile == 11 || tile == 12; }
+
+size_t conv_bf16_split_slab_bytes(int tile, long long M, int cout_pad)
+{
+    const TileInfo t = conv_bf16_tile_info(tile);
+    return (size_t)((M + t.bm - 1) / t.bm) * t.bm * cout_pad * sizeof(float);
+}
+
+hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s)
+{
+    if (!conv_bf16_split_tile(tile) || !tile_fits(kTilesBf16[tile].info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
+    const size_t slab = conv_bf16_split_slab_bytes(tile, a.M, a.CoutPad);
+    if (S < 2 || S > a.K / 64 || !ws || !a.dst || a.dec.boxes || slab > 0x7fffffffull || (size_t)S * slab > ws_bytes) return hipErrorInvalidValue;
+    // the bf16 form of the finish launch moves eight channels per thread: whole 16-byte pieces of dst and of the shortcut
+    if (!out_f32 && (a.Cout % 8 || ((uintptr_t)a.dst & 15) || ((uintptr_t)a.residual & 15))) return hipErrorInvalidValue;
+    if (out_f32 && a.residual) return hipErrorInvalidValue;
+    const TileInfo t = kTilesBf16[tile].info;
+    ConvArgs c = a;
+    c.dst = ws;
+    c.dst_bytes = (unsigned)slab;
+    c.residual = nullptr;
+    const int grid = ((a.M + t.bm - 1) / t.bm) * (a.CoutPad / t.bn);
+    if (hipError_t e = tile == 12 ? launch_split_t<2>(c, grid, S, s) : launch_split_t<1>(c, grid, S, s); e != hipSuccess) return e;
+    const float *wsf = static_cast<const float *>(ws);
+    const unsigned short *res = static_cast<const unsigned short *>(a.residual);
+    const size_t n = (size_t)a.M * (out_f32 ? a.Cout : a.Cout / 8);
+    const dim3 fgrid((unsigned)((n + 255) / 256));
+    if (out_f32)
+        hipLaunchKernelGGL(splitk_finish_bf16<true>, fgrid, dim3(256), 0, s, wsf, S, slab / 4, a.CoutPad, a.scale, a.shift, res, a.dst, a.M, a.Cout, a.leaky);
+    else
+        hipLaunchKernelGGL(splitk_finish_bf16<false>, fgrid, dim3(256), 0, s, wsf, S, slab / 4, a.CoutPad, a.scale, a.shift, res, a.dst, a.M, a.Cout, a.leaky);
+    return hipGetLastError();
+}
 
 TileInfo conv_bf16_tile_info(int tile) { return kTilesBf16[(tile >= 0 && tile < BF16_TILE_COUNT) ? tile : 0].info; }
 

@@ -60,6 +60,8 @@ struct ConvSlot {
     int split_req = -1;        // y3_net_set_split_k: -1 the heuristic (low-latency plans only), 1 off, 2..16 forced
     int split_k = 1;           // K slices in force, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
     int tile_bf16 = -1;
+    int split_req_bf16 = -1;   // y3_net_set_split_k_bf16: as split_req, for bf16 plans
+    int split_k_bf16 = 1;      // K slices in force in a bf16 plan (resolve_splits); 1 in every other plan
     int tile_x3 = -1;
     int cout_pad64 = 0;        // Cout rounded up to 64 (the three-plane kernel has no 32-wide N tile)
     void *wx3_dev = nullptr;   // packed [CoutPad64][3 planes][K] bf16 (hi, mid, lo of the fp32 weights)
@@ -117,6 +119,7 @@ struct y3_net {
     int xcd_mode = 1;              // y3_net_set_xcd_mode: 0 contiguous tile runs per XCD, 1 XCD-blocked order chosen per conv
     bool low_latency_set = false;  // y3_net_set_low_latency was called (the Y3_LOW_LATENCY tool override then stays out)
     bool low_latency = false;      // y3_net_set_low_latency: every eligible fp32 conv takes y3_choose_split_k
+    bool low_latency_bf16 = false;       // y3_net_set_low_latency_bf16: every eligible bf16 conv takes y3_choose_split_k
     void *split_ws = nullptr;      // split-K slabs: split_ws_lanes regions of split_ws_lane bytes, one per lane (lanes run concurrently)
     size_t split_ws_lane = 0;
     int split_ws_lanes = 0;

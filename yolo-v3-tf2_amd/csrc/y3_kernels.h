@@ -147,6 +147,12 @@ static constexpr int BF16_TILE_COUNT = 37;   // 32: the weight-resident 3x3 kern
 TileInfo conv_bf16_tile_info(int tile);
 bool conv_bf16_tile_built(int tile);
 hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
+// split-K form of the same conv (conv_bf16.hip): S >= 2 slices of the K walk (K tiles of 64) as S times the workgroups, raw fp32
+// accumulators into ws [S][Mpad][CoutPad] (at least S * conv_bf16_split_slab_bytes), then splitk_finish_bf16 on the same stream: the
+// slabs added in the order 0..S-1, the epilogue, the store to a.dst (bf16, or fp32 with out_f32).  Tiles 11 and 12 only.
+bool conv_bf16_split_tile(int tile);
+size_t conv_bf16_split_slab_bytes(int tile, long long M, int cout_pad);
+hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s);
 // weight-resident 3x3 / stride-1 conv for Cin = 32 / 64 (conv_res_bf16.hip): the early short-K layers of the bf16 path
 bool conv_res_bf16_fits(const ConvArgs &a);
 hipError_t launch_conv_res_bf16(const ConvArgs &a, hipStream_t s);

@@ -355,8 +355,13 @@ void refine_f32(const y3_net *net, const ConvSlot &c, const y3::ConvArgs &a, y3:
 }
 
 // bf16 plans: a head conv that decodes its own tiles needs a 256-wide tile
-void refine_bf16(const y3_net *, const ConvSlot &, const y3::ConvArgs &a, y3::ConvChoice &ch)
+void refine_bf16(const y3_net *, const ConvSlot &c, const y3::ConvArgs &a, y3::ConvChoice &ch)
 {
+    if (c.split_k_bf16 > 1 && !a.dec.boxes) {   // low-latency plan: S slices of the K walk into the lane's slabs, then the finish launch
+        ch.split_k = c.split_k_bf16;
+        ch.kind = y3::ConvKind::SplitK;
+        return;
+    }
     if (a.dec.boxes && y3::conv_bf16_tile_info(ch.tile).bn != 256) {   // a box's logits must meet in one workgroup: all 256 channels in the tile
         const bool m16 = ch.tile >= 24 && ch.tile <= 29;               // keep the MFMA shape of the plan's tile: same K grouping, same bits
         const bool big = (a.M + 255) / 256 >= 256;                     // 256x256 once it fills the chip, else 128x256 (16 waves both)
@@ -456,7 +461,7 @@ static y3_status set_forced_tile(const y3::ConvFamily &f, y3_net *net, int slot,
     return Y3_OK;
 }
 
-// ---- split-K (low-latency fp32 plans) --------------------------------------------------------------------------------------
+// ---- split-K (low-latency fp32 and bf16 plans) --------------------------------------------------------------------------------------
 // Can conv `slot` ever run split?  From the graph and the forced tile alone (no plan needed): not the first layer, not the
 // weight-resident tile 33, not a detection head (y3_net_detect runs the heads through conv_head.hip, and the composed route
 // must stay bit-identical to it), and only on the two tiles the split form is built for.  why: the refusal's text.
@@ -468,6 +473,32 @@ static bool split_eligible(const y3_net *net, int slot, const char **why)
     else if (net->nclasses > 0 && is_output(net, c.d.dst)) w = "a detection-head conv is never split (y3_net_detect decodes it in its own kernel)";
     else if (!y3::conv_split_tile(family_tile(F32_FAMILY, c, 1, 1, true)))
         w = "the conv's tile has no split form (tiles 10 and 11 have; the weight-resident tile 33 and the 32-wide tile 8 have not)";
+    if (why) *why = w;
+    return !w;
+}
+
+// K tiles of 64 from which the rule splits a bf16 conv (resolve_splits says why).  Y3_SPLIT_MIN_K_TILES_BF16: a variant build for the record
+// (csrc/build.py --variant OUT.so y3_net.cpp -DY3_SPLIT_MIN_K_TILES_BF16=0: y3_choose_split_k alone decides).
+#ifndef Y3_SPLIT_MIN_K_TILES_BF16
+#define Y3_SPLIT_MIN_K_TILES_BF16 32
+#endif
+static constexpr int kSplitMinKTilesBf16 = Y3_SPLIT_MIN_K_TILES_BF16;
+
+// The same question for a bf16 plan: the split form exists for tiles 11 and 12 (LDS-DMA, BK = 64, 32x32x16 MFMA) only.
+static bool split_eligible_bf16(const y3_net *net, int slot, const char **why)
+{
+    const ConvSlot &c = net->convs[slot];
+    const char *w = nullptr;
+    // the conv's smallest tile; arena_out as the plan will have it (a conv writing an fp32 net output itself never takes tile 32)
+    const bool arena_out = !is_output(net, c.d.dst) || y3::output_staged(net, c.d.dst);
+    const int tile = c.first_layer ? -1 : family_tile(BF16_FAMILY, c, 1, 1, arena_out);
+    if (c.first_layer) w = "the first layer (Cin = 3) is never split";
+    else if (net->nclasses > 0 && is_output(net, c.d.dst)) w = "a detection-head conv is never split (y3_net_detect decodes it in its own launch)";
+    else if (tile == 32) w = "the weight-resident tile 32 has no split form";
+    else if (y3::conv_bf16_tile_info(tile).bk == 32) w = "the BK = 32 tiles (Cin = 32 layers) have no split form";
+    else if (!y3::conv_bf16_split_tile(tile)) w = "the conv's tile has no split form (tiles 11 and 12 have)";
+    // the finish launch stores bf16 in whole 16-byte pieces (a conv that writes an fp32 net output itself takes any Cout)
+    else if (c.d.cout % 8 && arena_out) w = "a split conv storing bf16 needs Cout % 8 == 0";
     if (why) *why = w;
     return !w;
 }
@@ -485,20 +516,32 @@ y3_status y3::resolve_splits(y3_net *net)
         const int slot = net->ops[oi].index;
         ConvSlot &c = net->convs[slot];
         c.split_k = 1;
-        if (net->dtype != Y3_DTYPE_F32 || !split_eligible(net, slot, nullptr)) continue;
-        if (c.split_req == 1 || (c.split_req < 0 && !net->low_latency)) continue;
-        const ConvChoice ch = choose_conv_planned(net, oi);   // split_k is 1 here: the unsplit launch at the planned rows
+        c.split_k_bf16 = 1;
+        // fp32 and bf16 plans split, each by its own request and switch; the rule and its inputs are the same
+        const bool bf16 = net->dtype == Y3_DTYPE_BF16;
+        if (!bf16 && net->dtype != Y3_DTYPE_F32) continue;
+        if (!(bf16 ? split_eligible_bf16(net, slot, nullptr) : split_eligible(net, slot, nullptr))) continue;
+        const int req = bf16 ? c.split_req_bf16 : c.split_req;
+        if (req == 1 || (req < 0 && !(bf16 ? net->low_latency_bf16 : net->low_latency))) continue;
+        const ConvChoice ch = choose_conv_planned(net, oi);   // the split in force is 1 here: the unsplit launch at the planned rows
         if (ch.kind != ConvKind::Mfma) continue;               // runs as, or inside, the fused stem launch
         const long long M = (long long)net->max_batch * (net->height / c.d.out_div) * (net->width / c.d.out_div);
         const int tile = ch.tile;
-        const y3::TileInfo t = y3::conv_tile_info(tile);
+        if (bf16 && !y3::conv_bf16_split_tile(tile)) continue;   // the tile at the planned rows is not 11 or 12 (K tiles of 64 from here on)
+        const y3::TileInfo t = bf16 ? y3::conv_bf16_tile_info(tile) : y3::conv_tile_info(tile);
         const long long tiles = ((M + t.bm - 1) / t.bm) * (c.cout_pad / t.bn);
-        const size_t slab = y3::conv_split_slab_bytes(tile, M, c.cout_pad);
+        const size_t slab = bf16 ? y3::conv_bf16_split_slab_bytes(tile, M, c.cout_pad) : y3::conv_split_slab_bytes(tile, M, c.cout_pad);
         const int kt = c.K / t.bk;
-        int S = c.split_req > 1 ? c.split_req : y3_choose_split_k(tiles, kt, net->n_cus, (long long)slab);
+        // bf16 plans leave a conv of fewer than 32 K tiles to its one launch: in profiles/latency_bf16_splitk_sweep.txt every conv of 36 or 72
+        // K tiles gains from the rule's S at every batch from 1 to 8, while the convs of 4 .. 18 K tiles (launches of 7 .. 15 us) lose to
+        // the finish launch and the slab traffic at some batch (the 13^2 1x1 of 16 K tiles: -2 us at one image, +3.5 us at eight; the 52^2
+        // 3x3 of 18 K tiles: +1.5 .. +5 us).  The sweep times one net object at every S; the end-to-end runs of profiles/latency_bf16.txt
+        // cannot resolve this at eight images (two net objects differ by more).  A forced S is taken as given.
+        if (bf16 && req < 0 && kt < kSplitMinKTilesBf16) continue;
+        int S = req > 1 ? req : y3_choose_split_k(tiles, kt, net->n_cus, (long long)slab);
         if (S > kt) S = kt;
         if (S < 2 || slab > 0x7fffffffull) continue;
-        c.split_k = S;
+        (bf16 ? c.split_k_bf16 : c.split_k) = S;
         lane_bytes = std::max(lane_bytes, (size_t)S * slab);
     }
     if (lane_bytes > net->split_ws_lane || (lane_bytes && net->lanes > net->split_ws_lanes)) {
@@ -509,7 +552,7 @@ y3_status y3::resolve_splits(y3_net *net)
         lane_bytes = (lane_bytes + 255) & ~(size_t)255;
         hipError_t e = hipMalloc(&net->split_ws, lane_bytes * net->lanes);
         if (e != hipSuccess) {
-            for (ConvSlot &c : net->convs) c.split_k = 1;
+            for (ConvSlot &c : net->convs) c.split_k = c.split_k_bf16 = 1;
             return fail(Y3_ERR_OOM, "split-K workspace: hipMalloc(%zu) failed: %s", lane_bytes * net->lanes, hipGetErrorString(e));
         }
         net->split_ws_lane = lane_bytes;
@@ -679,7 +722,8 @@ Y3_CATCH("y3_net_set_tile")
 
 y3_status y3_net_set_tile_bf16(y3_net *net, int slot, int tile)
 try {
-    return set_forced_tile(BF16_FAMILY, net, slot, tile);
+    if (y3_status st = set_forced_tile(BF16_FAMILY, net, slot, tile); st != Y3_OK) return st;
+    return resolve_splits_of_setter(net);   // the tile is an input of the split decision
 }
 Y3_CATCH("y3_net_set_tile_bf16")
 
@@ -753,6 +797,38 @@ try {
 }
 Y3_CATCH("y3_net_set_split_k")
 
+y3_status y3_net_set_low_latency_bf16(y3_net *net, int on)
+try {
+    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "y3_net_set_low_latency_bf16: argument must be 0 or 1");
+    net->low_latency_bf16 = on != 0;
+    return resolve_splits_of_setter(net);
+}
+Y3_CATCH("y3_net_set_low_latency_bf16")
+
+y3_status y3_net_set_split_k_bf16(y3_net *net, int slot, int S)
+try {
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || S < -1 || S == 0 || S > 16)
+        return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv slot out of range, or S not -1, 1 or 2..16");
+    ConvSlot &c = net->convs[slot];
+    if (S > 1) {
+        const char *why = nullptr;
+        if (!split_eligible_bf16(net, slot, &why)) return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d: %s", slot, why);
+        if (net->height && net->dtype != Y3_DTYPE_BF16)
+            return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d: only Y3_DTYPE_BF16 plans take a bf16 split", slot);
+        if (const int oi = y3::conv_op(net, slot); net->height && oi >= 0) {
+            const y3::ConvChoice ch = y3::choose_conv_planned(net, oi);   // .tile: the conv's tile at the planned rows, split or not
+            if (ch.kind == y3::ConvKind::Stem || ch.kind == y3::ConvKind::InStem)
+                return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d runs inside the fused stem kernel, which is never split", slot);
+            if (!y3::conv_bf16_split_tile(ch.tile))
+                return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d: its tile at the planned rows (%d) has no split form (tiles 11 and 12 have)", slot, ch.tile);
+        }
+        if (S > c.K / 64) return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d has %d K tiles, fewer than S = %d", slot, c.K / 64, S);
+    }
+    c.split_req_bf16 = S;
+    return resolve_splits_of_setter(net);
+}
+Y3_CATCH("y3_net_set_split_k_bf16")
+
 y3_status y3_net_set_xcd_mode(y3_net *net, int mode)
 try {
     if (!net || mode < 0 || mode > 1) return fail(Y3_ERR_INVALID, "y3_net_set_xcd_mode: mode must be 0 or 1");
@@ -783,6 +859,12 @@ int y3_net_get_split_k(const y3_net *net, int slot)
 {
     if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height) return 1;
     return net->convs[slot].split_k;
+}
+
+int y3_net_get_split_k_bf16(const y3_net *net, int slot)
+{
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height) return 1;
+    return net->convs[slot].split_k_bf16;
 }
 
 int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice)

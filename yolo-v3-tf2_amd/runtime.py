@@ -219,6 +219,27 @@ class Net:
             raise Y3Error(f"split_k: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
         return int(self.lib.y3_net_get_split_k(self._h, int(slot)))
 
+    def set_low_latency_bf16(self, on=True):
+        """Low-latency bf16 plan for one to eight images (y3_net_set_low_latency_bf16): as set_low_latency, for a plan made with
+        Y3_DTYPE_BF16.  The two switches are independent; each acts on plans of its own dtype only.  None means off."""
+        on = int(self._low_latency_arg(on))
+        check(self.lib.y3_net_set_low_latency_bf16(self._h, on), "y3_net_set_low_latency_bf16")
+
+    def set_split_k_bf16(self, slot: int, S: int):
+        """K slices of conv `slot` in a bf16 plan: -1 the heuristic (in force only with set_low_latency_bf16), 1 off, 2..16 forced.
+        An ineligible conv (first layer, fused stem, tile 32, a BK = 32 tile, a tile other than 11 / 12, a detection head, a plan that
+        is not bf16) or S above the conv's K tiles (K / 64) raises here."""
+        S = self._split_k_arg(S)
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
+            raise Y3Error(f"set_split_k_bf16: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
+        check(self.lib.y3_net_set_split_k_bf16(self._h, int(slot), S), "y3_net_set_split_k_bf16")
+
+    def split_k_bf16(self, slot: int) -> int:
+        """K slices in force for conv `slot` in a bf16 plan after plan() (1: the ordinary launch; 1 on every other plan)."""
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
+            raise Y3Error(f"split_k_bf16: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
+        return int(self.lib.y3_net_get_split_k_bf16(self._h, int(slot)))
+
     def set_stem_fusion(self, on):
         """conv0 + conv1 (+ the 1x1 conv that follows them) as one kernel (default on; applies when the program starts with
         the Darknet-53 stem and the plan is fp32 or bf16 without keep_activations).  2: conv0 + conv1 only."""

@@ -43,7 +43,7 @@ enum {
 };
 
 /* activation storage / MFMA input type of the conv stack */
-enum { Y3_DTYPE_F32 = 0, Y3_DTYPE_BF16 = 1, Y3_DTYPE_F32X3 = 2, Y3_DTYPE_F32X2 = 3 };
+enum { Y3_DTYPE_F32 = 0, Y3_DTYPE_BF16 = 1, Y3_DTYPE_F32X3 = 2, Y3_DTYPE_F32X2 = 3, Y3_DTYPE_F16 = 4 };
 
 int y3_version(void);
 const char *y3_last_error(void);
@@ -53,7 +53,8 @@ int y3_device_count(void);
  * (tuning tables refer to them); the ids of tiles that were measured and lost in rounds 1-4 (timing-only ablations, the
  * stream-K schedule, residual prefetch, the pipelined bf16 tile, bf16 tap-row reuse and the four-wave 256x256 bf16 tile;
  * DESIGN.md section 4, records under profiles/) are retired and answer 0.  Every id that answers 1 is named by a packaged
- * tuning table or chosen by the library's heuristic for some conv (tests/test_abi.py). */
+ * tuning table or chosen by the library's heuristic for some conv (tests/test_abi.py).  Y3_DTYPE_F16 shares the bf16 family's tile
+ * table: it answers what Y3_DTYPE_BF16 answers. */
 int y3_tile_built(int dtype, int tile);
 
 /* ------------------------------------------------------------------------------------------
@@ -118,7 +119,9 @@ y3_status y3_net_set_conv_weights(y3_net *net, int conv_slot, const float *w, co
  * A tile that cannot serve the conv (shape, or a bf16-only tile on a conv that writes an fp32 net output) is refused here with
  * Y3_ERR_INVALID and a message, not by the forward.
  * y3_net_keep_activations(1) before y3_net_plan: no buffer reuse, so y3_net_read_tensor can read any
- * intermediate after a forward. */
+ * intermediate after a forward.
+ * y3_net_set_tile_bf16 acts on both 16-bit plans: Y3_DTYPE_BF16 and Y3_DTYPE_F16 plans share the tile ids, the heuristic and this
+ * per-conv forced tile (no fp16 table is tuned or shipped). */
 y3_status y3_net_set_tile(y3_net *net, int conv_slot, int tile);
 y3_status y3_net_set_tile_bf16(y3_net *net, int conv_slot, int tile);
 y3_status y3_net_set_tile_x3(y3_net *net, int conv_slot, int tile);
@@ -146,7 +149,8 @@ y3_status y3_net_set_k_chunk(y3_net *net, int channels);
  * units -- never from the rows of a call, so inside one plan an image's result does not depend on its batch or position.  S = 1 (the
  * ordinary launch) wherever the planned batch already fills the chip.  Never split: the first layer, the fused stem, the weight-
  * resident tile 33, the three detection-head convs (y3_net_detect and the composed route stay bit-identical), and -- by these three calls --
- * any plan that is not Y3_DTYPE_F32 (a Y3_DTYPE_BF16 plan splits through the _bf16 calls below; the plane-split modes never split).
+ * any plan that is not Y3_DTYPE_F32 (a Y3_DTYPE_BF16 plan splits through the _bf16 calls below; the plane-split modes and Y3_DTYPE_F16
+ * never split).
  * The same products in another summation order: results differ from the default plan's in the last bits (as
  * y3_net_set_k_chunk says of itself).  With it off nothing changes.
  * y3_net_set_split_k: S of one conv: -1 = y3_choose_split_k when low latency is on (else 1), 1 = off, 2..16 = that value whether or not
@@ -169,13 +173,16 @@ int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_by
  * LDS-DMA tiles: the only ones with a split form), a conv storing bf16 with Cout % 8 != 0, the three detection-head convs.
  * y3_net_set_low_latency_bf16: 0 / 1, off by default.  y3_net_set_split_k_bf16: -1 = the rule when the bf16 switch is on (else 1), 1 = off,
  * 2..16 forced; an ineligible conv, S > K / 64, or a forced value on a planned net whose dtype is not Y3_DTYPE_BF16 is refused with
- * Y3_ERR_INVALID and a message.  y3_net_get_split_k_bf16: the value in force after planning; 1 before, 1 on a plan that is not bf16. */
+ * Y3_ERR_INVALID and a message.  y3_net_get_split_k_bf16: the value in force after planning; 1 before, 1 on a plan that is not bf16.
+ * Y3_DTYPE_F16 plans never split: the switch does not act on them, and a forced value on a planned fp16 net is refused like on any
+ * other plan that is not bf16. */
 y3_status y3_net_set_low_latency_bf16(y3_net *net, int on);
 y3_status y3_net_set_split_k_bf16(y3_net *net, int conv_slot, int S);
 int y3_net_get_split_k_bf16(const y3_net *net, int conv_slot);
 y3_status y3_net_keep_activations(y3_net *net, int keep);
 /* 1 (default): when the program starts with conv0 (3x3/1, 3 -> 32) feeding only conv1 (3x3/2, 32 -> 64) -- the Darknet-53
  * stem, reference config/models/yolov3/backbone.yaml layers 1-2 -- and the plan is fp32 or bf16 without keep_activations,
+ * (Y3_DTYPE_F16 plans never fuse the stem: one launch per conv, whatever this is set to),
  * the two run as ONE kernel that keeps conv0's output (the largest tensor of the network, 1.4 GB at 64 x 416^2) in LDS; the
  * 1x1 conv that follows (64 -> 32, backbone.yaml layer 3) is computed by the same kernel from conv1's tile.
  * 2: conv0 + conv1 in one kernel, the 1x1 conv as its own launch (bf16 plans: bit-identical to 1).
@@ -222,7 +229,15 @@ y3_status y3_net_set_early_chunk(y3_net *net, int n_convs, int chunk_images);
  * accumulators: representation error 2^-22 |x| (fp32: 2^-24), half the MFMAs of F32X3.  Values must stay inside the
  * fp16 range: BN-scaled weights are checked (|w| < 65504: y3_net_plan / y3_net_forward refuse the mode otherwise),
  * activations are not checked.
- * In the three non-fp32 modes an output tensor that another op of the net reads again, or that a residual conv writes,
+ * Y3_DTYPE_F16: the bf16 plan's rules with IEEE fp16 (11 significand bits against bf16's 8) in place of bf16 -- intermediate
+ * activations and weights are fp16 (v_mfma_f32_32x32x16_f16 / 16x16x32_f16 at the bf16 rate, fp32 accumulate, BN scale / shift and the
+ * shortcut add in fp32, ONE rounding to nearest even where the pipeline stores); the Cin = 3 first layer is fp32 arithmetic storing
+ * fp16, the image batch and the head grids stay fp32.  The weights are rounded to fp16 on the host (a further copy of them, 124 MB for
+ * YOLOv3, beside the other formats).  Overflow is IEEE's: a value beyond 65504 is stored as inf (as torch.float16 does), a weight
+ * beyond it becomes inf; nothing saturates and nothing is checked.  Subnormals are kept.  Same tile ids, heuristic and tuning tables as
+ * Y3_DTYPE_BF16 (y3_net_set_tile_bf16); never the fused stem, never split-K.  Head logits measured 8 x closer to fp32 than bf16's
+ * (DESIGN.md section 7).
+ * In the non-fp32 modes an output tensor that another op of the net reads again, or that a residual conv writes,
  * is kept in the arena in the mode's format and converted into the caller's fp32 buffer at the end of the forward. */
 y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype);
 

@@ -15,7 +15,7 @@ nms = [i for i, r in enumerate(rows) if "nms_kernel" in r["Kernel_Name"]]
 
 
 def short(n):
-    m = re.search(r"(conv_bf16_mfma|conv_f32_mfma|conv_\w+|nms_kernel|pack_kernel)(<[^>]*>)?", n)
+    m = re.search(r"(conv16_mfma|conv3x3_res16|conv_f32_mfma|conv_\w+|nms_kernel|pack_kernel)(<[^>]*>)?", n)
     return (m.group(1) + (m.group(2) or "")) if m else n[:24]
 
 

@@ -20,10 +20,11 @@ def short(name):
         dma = ",dma" if m.group(8) == "1" else ""
         extra = "".join(",x" + v.strip() for v in m.group(9).split(",") if v.strip() and v.strip() != "0")
         return f"conv_f32_mfma<{32*tm*wr}x{32*tn*wc},w{wr*wc},s{m.group(6)}{dma}{extra}{',cat' if m.group(5) == 'true' else ''}>"
-    m = re.search(r"conv_bf16_mfma<(\d+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false)(?:, (true|false), (\d+), (true|false))?", name)
+    m = re.search(r"(?:conv_bf16_mfma<|conv16_mfma<y3::(?:Bf16|F16)Elem, )(\d+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false)(?:, (true|false), (\d+), (true|false))?", name)
     if m:
         tm, tn, wr, wc, bk = (int(m.group(i)) for i in range(1, 6))
-        return (f"conv_bf16_mfma<{32*tm*wr}x{32*tn*wc},w{wr*wc},k{bk}{',dma' if m.group(8) == 'true' else ''}"
+        kind = "conv_f16_mfma" if "F16Elem" in m.group(0) else "conv_bf16_mfma"   # one kernel template for both 16-bit types (csrc/conv_16bit.h)
+        return (f"{kind}<{32*tm*wr}x{32*tn*wc},w{wr*wc},k{bk}{',dma' if m.group(8) == 'true' else ''}"
                 f"{',16x16x32' if m.group(10) == 'true' else ''}{',cat' if m.group(6) == 'true' else ''}"
                 f"{',f32out' if m.group(7) == 'true' else ''}>")
     m = re.search(r"conv_f32x3_mfma<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false), (\d+)", name)
@@ -33,7 +34,7 @@ def short(name):
                 f"{',f32out' if m.group(8) == 'true' else ''}>")
     m = re.search(r"conv_first<\d+, (\d)>", name)   # conv_first<COUT, FMT>, FMT = Y3_DTYPE_* (labels as before the one kernel)
     if m:
-        return ("conv_first_f32", "conv_first_bf16", "conv_first_f32x3", "conv_first_f32x2")[int(m.group(1))]
+        return ("conv_first_f32", "conv_first_bf16", "conv_first_f32x3", "conv_first_f32x2", "conv_first_f16")[int(m.group(1))]
     m = re.search(r"conv_first_f32x3<\d+, (\d)>", name)
     if m:
         return f"conv_first_f32x{m.group(1)}"
@@ -41,9 +42,9 @@ def short(name):
     if m:
         tm, tn, wr, wc = (int(m.group(i)) for i in range(1, 5))
         return f"conv_bf16_rs<{32*tm*wr}x{32*tn*wc},w{wr*wc}{',16x16x32' if m.group(5) == 'true' else ''}>"
-    m = re.search(r"conv3x3_res_bf16<(\d+)>", name)
+    m = re.search(r"conv3x3_res_bf16<(\d+)>|conv3x3_res16<y3::(Bf16|F16)Elem, (\d+)>", name)
     if m:
-        return f"conv_res3x3_bf16<cin{m.group(1)}>"
+        return f"conv_res3x3_{'f16' if m.group(2) == 'F16' else 'bf16'}<cin{m.group(1) or m.group(3)}>"
     if "conv3x3_res_f32" in name:
         return "conv_res3x3_f32"
     for k in ("conv_head_decode_f32", "conv_stem_f32", "conv_stem_bf16", "conv_first_f32x3", "conv_first_f32", "conv_first_bf16", "decode_kernel", "nms_kernel", "pack_kernel", "class_scores",

@@ -11,6 +11,7 @@ low-latency plan was below the default plan in every alternated pair of windows,
 between its windows.  The split in force per conv is printed for every plan.
     python tools/time_latency.py [--sizes 416 608] [--batches 1 2 4 8] [--calls 1000] [--windows 4] [--per-conv] [--dtype f32] [--out profiles/latency.txt]
 --dtype bf16 times bf16 plans, the low-latency one through y3_net_set_low_latency_bf16 (profiles/latency_bf16.txt).
+--dtype f16 times fp16 plans: they never split, so both nets hold the default plan (as with --control) and "off" is the fp16 latency.
 --control makes "on" a SECOND DEFAULT-PLAN net: the same launches from two net objects, i.e. what the protocol reads when nothing differs.
 --per-conv adds, for batch 1, the per-conv table of y3_net_profile_convs (each launch timed alone; a split conv is its two launches)."""
 import argparse
@@ -32,11 +33,13 @@ def main():
     ap.add_argument("--windows", type=int, default=4, help="alternated windows the calls are divided into")
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--per-conv", action="store_true")
-    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"])
     ap.add_argument("--control", action="store_true", help="'on' is a second default-plan net (two net objects, the same launches)")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     bf16 = a.dtype == "bf16"
+    if a.dtype == "f16":
+        a.control = True        # no low-latency fp16 plan exists
 
     import torch
     import yolo_v3_tf2_amd  # noqa: F401
@@ -58,9 +61,10 @@ def main():
     for name in ("off", "on"):
         net = runtime.Net(program)
         net.load_weights(weights)
-        (net.set_low_latency_bf16 if bf16 else net.set_low_latency)(name == "on" and not a.control)
+        if a.dtype != "f16":
+            (net.set_low_latency_bf16 if bf16 else net.set_low_latency)(name == "on" and not a.control)
         nets[name] = net
-    say(f"# tools/time_latency.py  device: {torch.cuda.get_device_name(0)}  {'bf16' if bf16 else 'fp32'}  calls per plan and form: {a.calls} in {a.windows} alternated windows")
+    say(f"# tools/time_latency.py  device: {torch.cuda.get_device_name(0)}  { {'f32': 'fp32', 'f16': 'fp16'}.get(a.dtype, a.dtype)}  calls per plan and form: {a.calls} in {a.windows} alternated windows")
     say("# off = default plan, on = " + ("a second net with the default plan (control)" if a.control else "low-latency plan (split-K)") +
         "; times in ms; 'pairs' = windows in which on < off")
     per_window = max(1, a.calls // a.windows)
@@ -68,7 +72,7 @@ def main():
         for B in a.batches:
             x = torch.rand((B, S, S, 3), device="cuda")
             for net in nets.values():
-                net.plan(B, S, _lib.Y3_DTYPE_BF16 if bf16 else _lib.Y3_DTYPE_F32)
+                net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f16": _lib.Y3_DTYPE_F16}[a.dtype])
             splits = [(nets["on"].split_k_bf16 if bf16 else nets["on"].split_k)(i) for i in range(len(nets["on"].conv_ops))]
             say(f"\n== {S} x {S}, batch {B}: {sum(s > 1 for s in splits)} convs split; S per conv: {splits}")
             step = {k: (lambda n=n: n.detect(x, anchors, 100, 0.5, 0.1)) for k, n in nets.items()}

@@ -17,8 +17,8 @@ from . import PACKAGE_DIR
 LIB_PATH = os.environ.get("Y3_LIB_PATH") or os.path.join(PACKAGE_DIR, "lib", "liby3hip.so")
 
 Y3_OK = 0
-Y3_DTYPE_F32, Y3_DTYPE_BF16, Y3_DTYPE_F32X3, Y3_DTYPE_F32X2 = 0, 1, 2, 3
-DTYPE_TAGS = {Y3_DTYPE_F32: "f32", Y3_DTYPE_BF16: "bf16", Y3_DTYPE_F32X3: "f32x3", Y3_DTYPE_F32X2: "f32x2"}
+Y3_DTYPE_F32, Y3_DTYPE_BF16, Y3_DTYPE_F32X3, Y3_DTYPE_F32X2, Y3_DTYPE_F16 = 0, 1, 2, 3, 4
+DTYPE_TAGS = {Y3_DTYPE_F32: "f32", Y3_DTYPE_BF16: "bf16", Y3_DTYPE_F32X3: "f32x3", Y3_DTYPE_F32X2: "f32x2", Y3_DTYPE_F16: "f16"}
 TILES_X2_BUILT = (0, 1, 2, 3, 4, 8, 12, 26, 27)
 TILES_X3_BUILT = (0, 1, 2, 3, 4, 8, 9, 12, 13, 14)
 Y3_AUX_ADD, Y3_AUX_UPSAMPLE2X, Y3_AUX_CONCAT = 0, 1, 2
@@ -47,7 +47,7 @@ TILES_X3 = [(128, 128, 4, 32), (128, 64, 4, 32), (64, 64, 4, 32), (64, 128, 4, 3
             (256, 128, 16, 32), (128, 256, 16, 32),                                       # 26..27: 16 waves (two-plane mode)
             _Z32, _Z32,
             _Z32, _Z32, _Z32, _Z32]
-# bf16 kernel tiles: (BM, BN, waves, BK)
+# bf16 kernel tiles: (BM, BN, waves, BK); fp16 plans (Y3_DTYPE_F16) share the table, the ids and set_tile_bf16
 TILES_BF16 = [(128, 128, 4, 64), _Z64, _Z64, (64, 64, 4, 64), (128, 32, 4, 64),
               (128, 64, 4, 32), (64, 64, 4, 32), _Z64,
               (128, 128, 4, 64), _Z64, (128, 64, 4, 64), (64, 64, 4, 64), (64, 128, 4, 64), _Z64,  # 8..13: LDS-DMA loads

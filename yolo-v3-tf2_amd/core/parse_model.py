@@ -41,6 +41,7 @@ class YoloModel:
         self._net = None
         self._weights = None
         self.low_latency = False
+        self.dtype = None     # None: fp32 (set_dtype)
 
     # lazily create the device object so that building/inspecting a model works without a GPU
     def _device_net(self):
@@ -49,6 +50,8 @@ class YoloModel:
             self._net = Net(self.program)
             if self.low_latency:
                 self._net.set_low_latency(True)
+            if self.dtype is not None:
+                self._net.set_dtype(self.dtype)
             if self._weights is not None:
                 self._net.load_weights(self._weights)
         return self._net
@@ -60,6 +63,14 @@ class YoloModel:
         self.low_latency = Net._low_latency_arg(on)
         if self._net is not None:
             self._net.set_low_latency(self.low_latency)
+
+    def set_dtype(self, dtype):
+        """Conv arithmetic of the plans (runtime.Net.set_dtype): None or "f32" (default), "bf16", "f16" -- 16-bit activations and
+        weights on the matrix cores, fp32 accumulation, fp32 images in and fp32 grids out -- or a plane-split mode."""
+        from ..runtime import Net
+        self.dtype = Net._dtype_arg(dtype)
+        if self._net is not None:
+            self._net.set_dtype(self.dtype)
 
     def set_weights_dict(self, weights):
         self._weights = weights

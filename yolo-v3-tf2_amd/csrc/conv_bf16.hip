@@ -1,63 +1,9 @@
-// bf16 implicit-GEMM convolution on the gfx950 matrix cores (v_mfma_f32_32x32x16_bf16), fp32 accumulate.
-//
-// BASELINE config 5 ("bf16 MFMA fused conv+BN+LeakyReLU"): same fused op as conv_f32.hip
-// (reference: core/parse_model.py:27-52,72,134,155-156) with bf16 activations/weights in HBM and LDS.
-//   * activations NHWC bf16, weights packed [CoutPad][K] bf16 (k = tap*Cin + c), head outputs fp32;
-//   * K tile = BK bf16 (BK = 64: one 128-B line per row; BK = 32 for the two Cin = 32 layers); LDS rows are
-//     2*BK + 16 bytes (odd number of 16-B slots -> conflict-free ds_read_b128 of 16 different rows), double buffered;
-//   * MFMA 32x32x16: lane (r = l & 31, h = l >> 5) feeds A[row r][k = 16s + 8h .. +7] as one ds_read_b128;
-//   * epilogue through LDS: accumulators (+scale/shift, leaky) are written as an fp32 [BM][BN+4] tile, then every
-//     thread converts 8 consecutive channels (+ bf16 residual) and issues ONE 16-byte store -> full 128-B lines.
-//
-// Split-K (SPLIT = true, the low-latency bf16 plans of y3_net_set_low_latency_bf16; tiles 11 and 12 only): gridDim.y = S, slice y walks
-// K tiles [y*KT/S, (y+1)*KT/S) of the same tap-major walk and stores its raw fp32 accumulators (no epilogue, rows >= M included) straight
-// from the accumulator registers into slab y of a workspace [S][Mpad][CoutPad] fp32, through the slab's own buffer resource.
-// splitk_finish_bf16, a separate launch on the same stream, adds the slabs in the order 0, 1, ..., S-1 and applies the epilogue.
-#include <algorithm>
-#include <type_traits>
-
+// bf16 plans: the instantiations of the 16-bit implicit-GEMM conv kernel (conv_16bit.h) for bf16 elements (v_mfma_f32_32x32x16_bf16 /
+// 16x16x32_bf16), and what only bf16 plans have: the split-K form of tiles 11 and 12 with its finish launch (the low-latency bf16 plans of
+// y3_net_set_low_latency_bf16) and the phase stamps of the diagnostic build.
 #include "conv_common.h"
 
 namespace y3 {
-
-__device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, unsigned voff, int soff)
-{
-    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
-}
-
-// The epilogue's arithmetic, shared by the unsplit kernel and splitk_finish_bf16 so that equal accumulators give equal bits:
-// y = acc * scale + shift (two roundings: the build never contracts them), leaky as max(y, 0.1 y) ...
-__device__ __forceinline__ float bn_act(float acc, float sc, float sh, int leaky)
-{
-    float v = acc * sc + sh;
-    if (leaky) v = fmaxf(v, 0.1f * v);
-    return v;
-}
-// ... then eight consecutive channels: + the bf16 shortcut widened to fp32 (when there is one), one rounding to bf16
-__device__ __forceinline__ u32x4 add_res_pack(float (&v)[8], const u32x4 &rr, bool has_res)
-{
-    if (has_res) {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[2 * k] = __uint_as_float(rr[k] << 16) + v[2 * k];
-            v[2 * k + 1] = __uint_as_float(rr[k] & 0xffff0000u) + v[2 * k + 1];
-        }
-    }
-    u32x4 out;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = pack_bf16(v[2 * k], v[2 * k + 1]);
-    return out;
-}
-
-// DMA: operand tiles filled by direct-to-LDS buffer loads: unpadded 128-B rows, 16-B chunk index XOR-swizzled on the source
-// address and on the fragment reads (swizzled_chunk, conv_common.h).
-// DMA with BK = 32 (round 3): 64-B rows, a wave instruction fills 16 rows.  Half the
-// LDS per stage: 128x256 / 256x128 tiles of 8 waves fit TWO workgroups per CU (MINW = 4 caps the registers at 128), so that
-// one workgroup's epilogue (27 % of the bf16 conv stack, profiles/r03_ab_bf16_epilogue_probe.txt) runs beside the other's K loop.
-// M16 (round 3): the same tile on v_mfma_f32_16x16x32_bf16 -- 2TM x 2TN blocks of 16x16 per wave instead of TM x TN of 32x32.
-// Same LDS image, same bytes read per K tile, same MFMA cycles per FLOP; the chip holds a higher clock on this shape
-// (MI355X_MICROARCH.md "DVFS give-back" item 7: 1.12-1.15 x the FLOP/s on random data).  Fragment: lane l holds k = 8 (l >> 4) ..
-// + 7 of row l & 15; C: acc[mb][nb][j] = row 16 mb + 4 (l >> 4) + j, column 16 nb + (l & 15).
 #ifdef Y3_PHASE_STAMPS
 // Diagnostic build only (csrc/build.py --variant ... -DY3_PHASE_STAMPS, tools/phase_stamps.py): thread 0 of every workgroup of the
 // launches whose K equals y3_dbg_sel_k stores s_memrealtime (100 MHz) at kernel entry, before the first fetch, after the first
@@ -65,362 +11,15 @@ __device__ __forceinline__ u32x4 add_res_pack(float (&v)[8], const u32x4 &rr, bo
 __device__ unsigned long long y3_dbg_stamps[8 * 8192];
 __device__ int y3_dbg_sel_k = -1;
 #define Y3_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192 && p.K == y3_dbg_sel_k) y3_dbg_stamps[blockIdx.x * 8 + (k)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define Y3_STAMP(k) do { } while (0)
+#define Y3_STAMP_IDS() do { if (threadIdx.x == 0 && blockIdx.x < 8192 && p.K == y3_dbg_sel_k) { \
+        y3_dbg_stamps[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    /* HW_REG_HW_ID */ \
+        y3_dbg_stamps[blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   /* HW_REG_XCC_ID */ } } while (0)
 #endif
+}  // namespace y3
 
-template <int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, bool DMA = false, int MINW = 1, bool M16 = false, bool SPLIT = false>
-__global__ __launch_bounds__(64 * WR * WC, MINW) void conv_bf16_mfma(const ConvArgs p)
-{
-    static_assert(!SPLIT || (DMA && BK == 64 && !M16 && !OUT_F32), "the split-K form is built for the LDS-DMA 32x32x16 tiles with BK = 64");
-    Y3_STAMP(0);
-#ifdef Y3_PHASE_STAMPS
-    if (threadIdx.x == 0 && blockIdx.x < 8192 && p.K == y3_dbg_sel_k) {
-        y3_dbg_stamps[blockIdx.x * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 4);    // HW_REG_HW_ID
-        y3_dbg_stamps[blockIdx.x * 8 + 6] = __builtin_amdgcn_s_getreg((31 << 11) | 20);   // HW_REG_XCC_ID
-    }
-#endif
-    static_assert(!DMA || BK == 64 || BK == 32, "LDS-DMA variant needs 128-byte or 64-byte rows");
-    static_assert(!M16 || (DMA && BK == 64), "the 16x16x32 form is built on the 128-byte swizzled rows");
-    constexpr int MB = M16 ? 2 * TM : TM, NB = M16 ? 2 * TN : TN;   // accumulator blocks per wave
-    using acc_t = typename std::conditional<M16, f32x4, f32x16>::type;
-    constexpr int DROWS = 1024 / (2 * BK);   // rows one wave DMA instruction (1 KiB) fills: 8 (BK 64) or 16 (BK 32)
-    constexpr int BM = 32 * TM * WR;
-    constexpr int BN = 32 * TN * WC;
-    constexpr int NT = 64 * WR * WC;
-    constexpr int LPR = BK / 8;      // lanes per row (16 B = 8 bf16 each)
-    constexpr int RP = NT / LPR;     // rows per load pass
-    constexpr int AP = BM / RP, BP = BN / RP;
-    static_assert(BM % RP == 0 && BN % RP == 0 && AP >= 1 && BP >= 1, "tile too small for the thread count");
-    constexpr int ROWB = DMA ? 2 * BK : 2 * BK + 16;  // LDS row bytes
-    constexpr int STAGE_B = (BM + BN) * ROWB;      // bytes per stage
-    constexpr int CROW = BN + 4;                   // floats per row of the epilogue tile
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+#include "conv_16bit.h"
 
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WC, wc = wave % WC;
-
-    const int logical = xcd_contiguous_tile(blockIdx.x, gridDim.x);
-    const int tilesN = p.CoutPad / BN;
-    const int mt = logical / tilesN, nt = logical - mt * tilesN;
-    const int m0 = mt * BM, n0 = nt * BN;
-
-    const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
-    const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(CONCAT ? p.src1 : p.src0, CONCAT ? p.src1_bytes : p.src0_bytes);
-    const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
-    const unsigned OOB0 = p.src0_bytes, OOB1 = CONCAT ? p.src1_bytes : p.src0_bytes;
-
-    const int lrow = tid / LPR;
-    // first bf16 of this lane's 16-B piece in the K tile (DMA: the logical chunk landing in physical chunk tid % LPR; BK 32 key written out: measured)
-    const int lchunk = DMA ? (BK == 64 ? swizzled_chunk<8>(lrow, tid % LPR) : (tid % LPR) ^ ((lrow >> 2) & 3)) * 8 : (tid % LPR) * 8;
-    int aoff[AP];
-    int aoff1[CONCAT ? AP : 1];
-    int ahw[AP];
-    const int C1 = p.Cin - p.C0;
-    const TileOrigin org = tile_origin(p, m0);   // (b, ho, wo) of every row: conv_common.h
-#pragma unroll
-    for (int i = 0; i < AP; ++i) {
-        if constexpr (OUT_F32 && !CONCAT) {   // the head convs: gather_row's offsets written out (through it five prologue instructions moved: measured)
-            const int m = m0 + i * RP + lrow;
-            int b, ho, wo;
-            tile_row(p, org, org.wo0 + i * RP + lrow, b, ho, wo);
-            const int hi0 = ho * p.stride - p.pad, wi0 = wo * p.stride - p.pad;
-            aoff[i] = ((b * p.H + hi0) * p.W + wi0) * p.Cin;
-            ahw[i] = (m < p.M) ? ((hi0 << 16) | (wi0 & 0xffff)) : (int)0x80000000;
-        } else gather_row<CONCAT, 1>(p, org, m0 + i * RP + lrow, org.wo0 + i * RP + lrow, C1, aoff[i], aoff1[CONCAT ? i : 0], ahw[i]);
-    }
-    unsigned boff[BP];
-#pragma unroll
-    for (int j = 0; j < BP; ++j) boff[j] = (unsigned)((n0 + j * RP + lrow) * p.K + lchunk) * 2u;
-
-    // K tiles of this workgroup's walk: all of them, or slice blockIdx.y of gridDim.y (starting at tile kt0 of the walk)
-    const int kt0 = SPLIT ? (int)blockIdx.y * (p.K / BK) / (int)gridDim.y : 0;
-    const int KT = SPLIT ? ((int)blockIdx.y + 1) * (p.K / BK) / (int)gridDim.y - kt0 : p.K / BK;
-    int tap = 0, c0 = 0;
-    if constexpr (SPLIT) {   // the walk's state at tile kt0 (wave-uniform); a concat slice may begin in either source: the fetch picks it from c0
-        const int tpt = p.Cin / BK;
-        tap = kt0 / tpt;
-        c0 = (kt0 - tap * tpt) * BK;
-    }
-    unsigned avoff[AP];
-    unsigned avoff1[CONCAT ? AP : 1];
-    auto set_tap = [&]() {   // as in conv_f32x3.hip; written out in both: DESIGN.md section 4, "One row per tile"
-        if (CONCAT) {
-#pragma unroll
-            for (int i = 0; i < AP; ++i) {
-                avoff[i] = (ahw[i] < 0) ? OOB0 : (unsigned)(aoff[i] + lchunk) * 2u;
-                avoff1[i] = (ahw[i] < 0) ? OOB1 : (unsigned)(aoff1[i] + lchunk) * 2u;
-            }
-        } else {
-            const int u = tap / p.ksize, v = tap - u * p.ksize;
-            const int toff = (u * p.W + v) * p.Cin + lchunk;
-#pragma unroll
-            for (int i = 0; i < AP; ++i) {
-                const int hi = (ahw[i] >> 16) + u, wi = (int)(short)(ahw[i] & 0xffff) + v;
-                const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-                avoff[i] = ok ? (unsigned)(aoff[i] + toff) * 2u : OOB0;
-            }
-        }
-    };
-    set_tap();
-
-    int kglob = SPLIT ? kt0 * BK : 0;
-    // the K walk both fetch forms end with: the next BK channels of this tap, else the next tap
-    auto advance_k = [&]() {
-        kglob += BK;
-        c0 += BK;
-        if (c0 == p.Cin) {
-            c0 = 0;
-            ++tap;
-            if (!CONCAT) set_tap();
-        }
-    };
-
-    u32x4 ra[AP], rb[BP];
-    auto fetch_dma = [&](int buf) {
-        unsigned char *sa = smem + buf * STAGE_B + wave * DROWS * ROWB;   // wave w fills rows [pass*RP + DROWS*w, +DROWS)
-        unsigned char *sb = sa + BM * ROWB;
-        if (CONCAT && c0 >= p.C0) {
-#pragma unroll
-            for (int i = 0; i < AP; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lds_ptr)(sa + i * RP * ROWB), 16, (int)avoff1[i], (c0 - p.C0) * 2, 0, 0);
-        } else {
-#pragma unroll
-            for (int i = 0; i < AP; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lds_ptr)(sa + i * RP * ROWB), 16, (int)avoff[i], c0 * 2, 0, 0);
-        }
-#pragma unroll
-        for (int j = 0; j < BP; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(sb + j * RP * ROWB), 16, (int)boff[j], kglob * 2, 0, 0);
-        advance_k();
-    };
-    auto fetch = [&]() {
-        if (CONCAT) {
-            if (c0 < p.C0) {
-#pragma unroll
-                for (int i = 0; i < AP; ++i) ra[i] = bload16(rs0, avoff[i], c0 * 2);
-            } else {
-#pragma unroll
-                for (int i = 0; i < AP; ++i) ra[i] = bload16(rs1, avoff1[i], (c0 - p.C0) * 2);
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < AP; ++i) ra[i] = bload16(rs0, avoff[i], c0 * 2);
-        }
-#pragma unroll
-        for (int j = 0; j < BP; ++j) rb[j] = bload16(rsw, boff[j], kglob * 2);
-        advance_k();
-    };
-    auto stage = [&](int buf) {
-        unsigned char *sa = smem + buf * STAGE_B;
-        unsigned char *sb = sa + BM * ROWB;
-#pragma unroll
-        for (int i = 0; i < AP; ++i) *reinterpret_cast<u32x4 *>(sa + (i * RP + lrow) * ROWB + lchunk * 2) = ra[i];
-#pragma unroll
-        for (int j = 0; j < BP; ++j) *reinterpret_cast<u32x4 *>(sb + (j * RP + lrow) * ROWB + lchunk * 2) = rb[j];
-    };
-
-    acc_t acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int e = 0; e < (M16 ? 4 : 16); ++e) acc[i][j][e] = 0.0f;
-
-    Y3_STAMP(1);
-    if (DMA) {
-        fetch_dma(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    } else {
-        fetch();
-        stage(0);
-    }
-    __syncthreads();
-    Y3_STAMP(2);
-
-    const int fr = M16 ? (lane & 15) : (lane & 31), fh = M16 ? (lane >> 4) : (lane >> 5);   // row in the block, k group
-    const int a_frag = (wr * 32 * TM + fr) * ROWB + (DMA ? 0 : fh * 16);
-    const int b_frag = BM * ROWB + (wc * 32 * TN + fr) * ROWB + (DMA ? 0 : fh * 16);
-    constexpr int KS = M16 ? BK / 32 : BK / 16;      // MFMA k steps per K tile
-    constexpr int BR = M16 ? 16 : 32;                // rows per block
-    int foff[KS];  // byte offset of this lane's 16-B piece of k-step s inside its row
-#pragma unroll
-    for (int s_ = 0; s_ < KS; ++s_)
-        foff[s_] = DMA ? swizzled_chunk<LPR>(fr, (M16 ? 4 : 2) * s_ + fh) * 16 : s_ * 32;
-
-    for (int kt = 0; kt < KT; ++kt) {
-        const int cur = kt & 1;
-        if (kt + 1 < KT) {
-            if (DMA) fetch_dma(cur ^ 1); else fetch();
-        }
-        const unsigned char *sa = smem + cur * STAGE_B + a_frag;
-        const unsigned char *sb = smem + cur * STAGE_B + b_frag;
-#pragma unroll
-        for (int s = 0; s < KS; ++s) {
-            bf16x8 fa[MB], fb[NB];
-#pragma unroll
-            for (int i = 0; i < MB; ++i) fa[i] = *reinterpret_cast<const bf16x8 *>(sa + i * BR * ROWB + foff[s]);
-#pragma unroll
-            for (int j = 0; j < NB; ++j) fb[j] = *reinterpret_cast<const bf16x8 *>(sb + j * BR * ROWB + foff[s]);
-#pragma unroll
-            for (int i = 0; i < MB; ++i)
-#pragma unroll
-                for (int j = 0; j < NB; ++j) {
-                    if constexpr (M16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-                    else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa[i], fb[j], acc[i][j], 0, 0, 0);
-                }
-        }
-        if (DMA) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        } else if (kt + 1 < KT) {
-            stage(cur ^ 1);
-        }
-        __syncthreads();
-    }
-
-    Y3_STAMP(3);
-    // ---- epilogue through LDS, one 32-row sub-tile of every wave per pass ----------------------------------
-    // pass i: wave (wr, wc) writes rows [wr*32, +32) x cols [wc*32*TN, +32*TN) of a [WR*32][BN+4] fp32 tile (its i-th
-    // accumulator row block), then all threads convert 8 consecutive channels each and store 16 B.
-    if constexpr (SPLIT) {
-        // raw accumulators -> slab blockIdx.y, straight from the registers: p.dst is the workspace, p.dst_bytes the bytes of ONE slab
-        // [Mpad][CoutPad] (Mpad = whole tiles, so every row of the tile has its place; the range check of the slab's own buffer resource
-        // drops anything else).  A store instruction writes two rows of 32 consecutive floats: whole 128-byte lines.
-        const __amdgpu_buffer_rsrc_t rss = buffer_rsrc(static_cast<const char *>(p.dst) + (size_t)blockIdx.y * p.dst_bytes, p.dst_bytes);
-        const int slab_row_bytes = p.CoutPad * 4;
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-            const int n = n0 + (wc * TN + j) * 32 + fr;
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-                const int mbase = m0 + (wr * TM + i) * 32 + 4 * fh;
-                const unsigned vbase = (unsigned)(mbase * p.CoutPad + n) * 4u;
-#pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i][j][e]), rss, (int)vbase,
-                                                          mfma32_row(e) * slab_row_bytes, 0);
-            }
-        }
-    } else if constexpr (!OUT_F32) {
-        // ---- bf16 output: per-wave epilogue, no workgroup barrier ------------------------------------------------------
-        // Every wave transposes its own 32 x (32 TN) fp32 blocks through a private LDS scratch (the operand tiles are dead
-        // after the loop's last barrier) and stores whole 16-byte pieces of 8 channels: rows of 64 TN bytes per wave, full
-        // 128-B lines for TN >= 2.  LDS operations of one wave execute in order, so the write -> read hand-off between
-        // its lanes needs no barrier, and a wave leaves as soon as ITS stores are issued.  The shortcut operand is added
-        // in fp32 before the single rounding to bf16 (the oracle's bf16 mode rounds where the pipeline stores).
-        // (round 3: the workgroup-wide fp32 tile + 2 barriers per pass this replaces cost 27 % of the bf16 conv stack,
-        // profiles/r03_ab_bf16_epilogue_probe.txt)
-        constexpr int CW = 32 * TN;              // floats per scratch row = channels per wave
-        constexpr int PPRW = CW / 8;             // 16-byte output pieces per row
-        constexpr int NPL = 32 * PPRW / 64;      // pieces per lane per 32-row block
-        float *S = reinterpret_cast<float *>(smem) + wave * (32 * CW);
-        unsigned short *dstb = static_cast<unsigned short *>(p.dst);
-        const unsigned short *res = static_cast<const unsigned short *>(p.residual);
-        const int nw = n0 + wc * CW;             // first channel of this wave
-        float sc[NB], sh[NB];
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            sc[j] = p.scale[nw + j * BR + fr];
-            sh[j] = p.shift[nw + j * BR + fr];
-        }
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            const int mw = m0 + (wr * TM + i) * 32;   // first row of this block
-            u32x4 rr[NPL];
-            // (round 5: all TM passes' shortcut loads requested up front, so that none queues behind a pass's stores, measured 0.6 % SLOWER,
-            // profiles/r05_ab_bf16_shortcut_hoist.txt: 64 loads per CU in flight at once instead of 32 twice)
-            if (res) {   // shortcut operand first: its latency hides behind the accumulator write-out
-#pragma unroll
-                for (int it = 0; it < NPL; ++it) {
-                    const int q = lane + it * 64;
-                    const int r = q / PPRW, pc = q - r * PPRW;
-                    rr[it] = (mw + r < p.M) ? *reinterpret_cast<const u32x4 *>(res + (size_t)(mw + r) * p.Cout + nw + pc * 8)
-                                            : u32x4{0u, 0u, 0u, 0u};
-                }
-            }
-            if constexpr (M16) {
-#pragma unroll
-                for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                    for (int j = 0; j < NB; ++j)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            S[mfma16_row(e, fh, mb) * CW + j * 16 + fr] = bn_act(acc[2 * i + mb][j][e], sc[j], sh[j], p.leaky);
-                        }
-            } else {
-#pragma unroll
-                for (int j = 0; j < TN; ++j) {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        S[mfma32_row(e, fh) * CW + j * 32 + fr] = bn_act(acc[i][j][e], sc[j], sh[j], p.leaky);
-                    }
-                }
-            }
-            // lanes read what OTHER lanes of this wave wrote: the hardware runs a wave's LDS operations in order, and these three
-            // builtins (no instructions) keep the compiler from moving the reads above the writes
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int it = 0; it < NPL; ++it) {
-                const int q = lane + it * 64;
-                const int r = q / PPRW, pc = q - r * PPRW;
-                const f32x4 v0 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8);
-                const f32x4 v1 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8 + 4);
-                float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                const u32x4 out = add_res_pack(v, rr[it], res != nullptr);
-                if (mw + r < p.M) *reinterpret_cast<u32x4 *>(dstb + (size_t)(mw + r) * p.Cout + nw + pc * 8) = out;
-            }
-            // ... and the next pass's writes below this pass's reads
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-        Y3_STAMP(4);   // thread 0 = wave 0: its own stores issued (not yet retired)
-    } else {
-        // ---- fp32 output (head grids, Cout = 255): workgroup-wide fp32 tile, one 32-row block of every wave per pass, as in conv_f32x3.hip ----
-        constexpr int EROWS = WR * 32;
-        float *C = reinterpret_cast<float *>(smem);
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-            if (i > 0) __syncthreads();   // previous pass fully read
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                const int nl = wc * TN * 32 + j * BR + fr;
-                const float sc = p.scale[n0 + nl], sh = p.shift[n0 + nl];
-                if constexpr (M16) {
-#pragma unroll
-                    for (int mb = 0; mb < 2; ++mb)
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) {
-                            C[(wr * 32 + 16 * mb + mfma16_row(e, fh)) * CROW + nl] = bn_act(acc[2 * i + mb][j][e], sc, sh, p.leaky);
-                        }
-                } else {
-#pragma unroll
-                    for (int e = 0; e < 16; ++e) {
-                        C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = bn_act(acc[i][j][e], sc, sh, p.leaky);
-                    }
-                }
-            }
-            __syncthreads();
-            float *dst = static_cast<float *>(p.dst);
-            if (dst != nullptr) {
-                for (int idx = tid; idx < EROWS * BN; idx += NT) {
-                    const int r = idx / BN, col = idx - r * BN;
-                    const int m = m0 + (r >> 5) * 32 * TM + i * 32 + (r & 31), n = n0 + col;
-                    if (m < p.M && n < p.Cout) dst[(size_t)m * p.Cout + n] = C[r * CROW + col];
-                }
-            }
-            // detection head with its decode fused in (y3_net_forward_decode; the launcher guarantees a tile that spans all
-            // 3 * (5 + nc) channels): the EROWS pixels of this pass are decoded from the fp32 tile in LDS, same body as decode.hip
-            if (p.dec.boxes != nullptr)
-                decode_rows_from_lds<NT>(C, CROW, EROWS, [&](int r) { return m0 + (r >> 5) * 32 * TM + i * 32 + (r & 31); }, p.M, p.dec);
-        }
-    }
-}
+namespace y3 {
 
 // Second half of a split-K conv: per element slab[0] + slab[1] + ... + slab[S-1], added in that order, then exactly the unsplit epilogue's
 // operations through the same helpers (bn_act, add_res_pack).  bf16 output: eight channels per thread, 16-byte loads and stores
@@ -459,94 +58,9 @@ __global__ __launch_bounds__(256) void splitk_finish_bf16(const float *__restric
         const size_t o = (size_t)m * cout + n;
         u32x4 rr{0u, 0u, 0u, 0u};
         if (residual) rr = *reinterpret_cast<const u32x4 *>(residual + o);
-        *reinterpret_cast<u32x4 *>(static_cast<unsigned short *>(dst) + o) = add_res_pack(v, rr, residual != nullptr);
+        *reinterpret_cast<u32x4 *>(static_cast<unsigned short *>(dst) + o) = add_res_pack<Bf16Elem>(v, rr, residual != nullptr);
     }
 }
-
-// ---------------------------------------------------------------------------------------------------------
-// Round-3 record (code removed again): a PERSISTENT form of this kernel -- workgroups walking tiles bid, bid + G, ...,
-// the next tile's first K tile prefetched before the epilogue, a counted s_waitcnt leaving the tile's stores in flight --
-// was built to hide the output stores (profiles/r03_ab_bf16_epilogue_probe.txt: the stores alone cost 20 % of the bf16
-// conv stack: 10.0 ms with them, 8.0 without).  Bit-identical, 34 bf16 parity tests green, and 10 % SLOWER (11.09 vs
-// 10.07 ms, profiles/r03_ab_bf16_persistent.txt).  Two facts defeat it: (1) memory operations retire in issue order, so the
-// first wait for a K tile issued after the stores waits for the stores as well -- they can overlap one K iteration
-// (~1 us), not a tile; (2) with one workgroup per CU (128 KB of LDS) and equal work per tile all 256 workgroups store at
-// the same moment: a 32 MB burst, 4 MB per XCD = the whole L2, which drains at the HBM write rate (~8 us) while HBM idles
-// during the K loops.  What would help is out-of-phase workgroups (two per CU), which this tile's LDS and register
-// budget do not admit.
-// ---------------------------------------------------------------------------------------------------------
-// Round-2 record (code removed in round 4): a pipelined 256x256x64 tile (id 20) with the K loop of the guide's "256^2 8-phase
-// template" (LDS-DMA loads in flight across raw s_barriers, counted vmcnt, the second M half of the waves one barrier behind
-// the first) was correct on the first build and 10-15 % SLOWER than the 16-wave two-phase tile 17
-// (profiles/r02_tile_sweep_bf16_pipelined_b128_s416.txt, r02_bf16_pipelined_tile_pmc.txt: MFMA busy 0.45 vs 0.58).
-// ---------------------------------------------------------------------------------------------------------
-template <int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, bool DMA, int MINW, bool M16>
-static hipError_t launch_kb(const ConvArgs &a, hipStream_t s)
-{
-    constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
-    const int tilesM = (a.M + BM - 1) / BM, tilesN = a.CoutPad / BN;
-    const size_t stages = 2 * (size_t)(BM + BN) * (DMA ? 2 * BK : 2 * BK + 16);
-    // epilogue: fp32 output -> one workgroup-wide 32-row block per wave row; bf16 output -> 32 x (32 TN) floats per wave
-    const size_t ctile = OUT_F32 ? (size_t)WR * 32 * (BN + 4) * sizeof(float) : (size_t)WR * WC * 32 * 32 * TN * sizeof(float);
-    return launch_conv_kernel<conv_bf16_mfma<TM, TN, WR, WC, BK, CONCAT, OUT_F32, DMA, MINW, M16>>(a, tilesM * tilesN, 64 * WR * WC,
-                                                                                                 std::max(stages, ctile), s);
-}
-
-template <int TM, int TN, int WR, int WC, int BK, bool DMA, int MINW, bool M16>
-static hipError_t launch_tb(const ConvArgs &a, bool out_f32, hipStream_t s)
-{
-    return dispatch_concat_out(a.src1 != nullptr, out_f32, [&](auto concat, auto f32) {
-        return launch_kb<TM, TN, WR, WC, BK, decltype(concat)::value, decltype(f32)::value, DMA, MINW, M16>(a, s);
-    });
-}
-
-// One row per tile id: the geometry, read off the template arguments (the kernel is always double buffered), and the launcher of that
-// instantiation; a retired id is an empty row.
-struct TileBf16 { TileInfo info; hipError_t (*launch)(const ConvArgs &, bool out_f32, hipStream_t); };
-template <int TM, int TN, int WR, int WC, int BK, bool DMA = false, int MINW = 1, bool M16 = false>
-static constexpr TileBf16 tile() { return {{32 * TM * WR, 32 * TN * WC, WR * WC, 2, BK}, launch_tb<TM, TN, WR, WC, BK, DMA, MINW, M16>}; }
-
-// weight-resident 3x3 / stride 1, Cin = 32 / 64 (conv_res_bf16.hip): 4 x 32 pixels x 64 channels per workgroup tile; stores bf16 only
-static hipError_t launch_res(const ConvArgs &a, bool out_f32, hipStream_t s)
-{
-    return (!out_f32 && conv_res_bf16_fits(a)) ? launch_conv_res_bf16(a, s) : hipErrorInvalidValue;
-}
-
-// Ids are stable (tuning files refer to them).  The table holds exactly the tiles a plan can select -- a packaged tuning table
-// (tuning/bf16_*.json), the library's heuristic or the head-decode fallback (choose_tile_bf16 / refine_bf16 in y3_net.cpp) names every one of
-// them (tests/test_abi.py); the other ids are retired.
-static const TileBf16 kTilesBf16[BF16_TILE_COUNT] = {
-    tile<2, 2, 2, 2, 64>(),                  //  0: 128x128
-    {}, {},
-    tile<1, 1, 2, 2, 64>(),                  //  3: 64x64
-    tile<1, 1, 4, 1, 64>(),                  //  4: 128x32
-    tile<2, 1, 2, 2, 32>(),                  //  5: 128x64, BK 32 (Cin = 32 layers)
-    tile<1, 1, 2, 2, 32>(),                  //  6: 64x64, BK 32
-    {},
-    tile<2, 2, 2, 2, 64, true>(),            //  8: 128x128 LDS-DMA
-    {},
-    tile<2, 1, 2, 2, 64, true>(),            // 10: 128x64 LDS-DMA
-    tile<1, 1, 2, 2, 64, true>(),            // 11: 64x64 LDS-DMA
-    tile<1, 2, 2, 2, 64, true>(),            // 12: 64x128 LDS-DMA
-    {}, {}, {}, {},                          // 13..16
-    tile<2, 2, 4, 4, 64, true>(),            // 17: 256x256, 16 waves, LDS-DMA
-    {},
-    tile<1, 2, 4, 4, 64, true>(),            // 19: 128x256, 16 waves, LDS-DMA
-    {}, {},                                  // 20 (the pipelined tile of round 2, see above), 21
-    tile<2, 2, 4, 2, 32, true, 4>(),         // 22: 256x128, 8 waves, LDS-DMA with BK 32, two workgroups per CU
-    {},
-    tile<2, 2, 4, 4, 64, true, 1, true>(),   // 24: tile 17 on 16x16x32 MFMAs
-    {},
-    tile<1, 2, 4, 4, 64, true, 1, true>(),   // 26: tile 19 on 16x16x32
-    tile<2, 2, 2, 2, 64, true, 1, true>(),   // 27: tile 8 (128x128, 4 waves) on 16x16x32
-    {},
-    tile<1, 2, 2, 2, 64, true, 1, true>(),   // 29: tile 12 (64x128, 4 waves) on 16x16x32
-    {}, {},                                  // 30, 31
-    {{128, 64, 8, 2, 32}, launch_res},       // 32
-    // 33..35 (3x3 / stride 1 with tap-row reuse) and 36 (256x256 on four waves of 128x128, hand-pipelined): parity-green, neutral / slower in the
-    // two-lane step (profiles/r04_ab_bf16_rs.txt, r04_tile_sweep_bf16_w4.txt); code in the history (commit 1777145)
-    {}, {}, {}, {},
-};
 
 #ifdef Y3_PHASE_STAMPS
 extern "C" int y3_dbg_select_k(int K) { return (int)hipMemcpyToSymbol(HIP_SYMBOL(y3_dbg_sel_k), &K, sizeof(int)); }
@@ -561,8 +75,8 @@ template <int TN>
 static hipError_t launch_split_t(const ConvArgs &c, int grid, int S, hipStream_t s)
 {
     constexpr size_t lds = 2 * (size_t)(64 + 64 * TN) * 128;   // the two operand stages; a split launch has no epilogue tile
-    if (c.src1) return launch_conv_kernel<conv_bf16_mfma<1, TN, 2, 2, 64, true, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
-    return launch_conv_kernel<conv_bf16_mfma<1, TN, 2, 2, 64, false, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+    if (c.src1) return launch_conv_kernel<conv16_mfma<Bf16Elem, 1, TN, 2, 2, 64, true, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+    return launch_conv_kernel<conv16_mfma<Bf16Elem, 1, TN, 2, 2, 64, false, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
 }
 
 bool conv_bf16_split_tile(int tile) { return tile == 11 || tile == 12; }
@@ -575,13 +89,13 @@ size_t conv_bf16_split_slab_bytes(int tile, long long M, int cout_pad)
 
 hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    if (!conv_bf16_split_tile(tile) || !tile_fits(kTilesBf16[tile].info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
+    if (!conv_bf16_split_tile(tile) || !tile_fits(Tiles16<Bf16Elem>::table[tile].info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
     const size_t slab = conv_bf16_split_slab_bytes(tile, a.M, a.CoutPad);
     if (S < 2 || S > a.K / 64 || !ws || !a.dst || a.dec.boxes || slab > 0x7fffffffull || (size_t)S * slab > ws_bytes) return hipErrorInvalidValue;
     // the bf16 form of the finish launch moves eight channels per thread: whole 16-byte pieces of dst and of the shortcut
     if (!out_f32 && (a.Cout % 8 || ((uintptr_t)a.dst & 15) || ((uintptr_t)a.residual & 15))) return hipErrorInvalidValue;
     if (out_f32 && a.residual) return hipErrorInvalidValue;
-    const TileInfo t = kTilesBf16[tile].info;
+    const TileInfo t = Tiles16<Bf16Elem>::table[tile].info;
     ConvArgs c = a;
     c.dst = ws;
     c.dst_bytes = (unsigned)slab;
@@ -599,18 +113,10 @@ hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int
     return hipGetLastError();
 }
 
-TileInfo conv_bf16_tile_info(int tile) { return kTilesBf16[(tile >= 0 && tile < BF16_TILE_COUNT) ? tile : 0].info; }
+TileInfo conv_bf16_tile_info(int tile) { return Tiles16<Bf16Elem>::table[(tile >= 0 && tile < BF16_TILE_COUNT) ? tile : 0].info; }
 
-bool conv_bf16_tile_built(int tile) { return tile >= 0 && tile < BF16_TILE_COUNT && kTilesBf16[tile].launch; }
+bool conv_bf16_tile_built(int tile) { return tile >= 0 && tile < BF16_TILE_COUNT && Tiles16<Bf16Elem>::table[tile].launch; }
 
-hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s)
-{
-    if (!conv_bf16_tile_built(tile)) return hipErrorInvalidValue;
-    const TileInfo &t = kTilesBf16[tile].info;
-    if (a.dec.boxes != nullptr && (!out_f32 || t.bn < a.CoutPad)) return hipErrorInvalidValue;   // a fused head needs all its channels in one tile
-    if (a.dst == nullptr && a.dec.boxes == nullptr) return hipErrorInvalidValue;
-    if (!tile_fits(t, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
-    return kTilesBf16[tile].launch(a, out_f32, s);
-}
+hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s) { return launch_conv16<Bf16Elem>(a, tile, out_f32, s); }
 
 }  // namespace y3

@@ -3,7 +3,7 @@
 // its output bytes.  Runs when the stem is not fused (keep_activations, early chunks, the plane-split plans).
 // One thread = one output pixel x all output channels; fp32 image in, fp32 arithmetic in every mode; weights are wave-uniform
 // (scalar loads), accumulation order (u,v,c) like the GEMM kernel's k order.  The output leaves in the plan's format (FMT =
-// Y3_DTYPE_*): fp32, bf16, three bf16 planes or two fp16 planes per value.
+// Y3_DTYPE_*): fp32, bf16, fp16, three bf16 planes or two fp16 planes per value.
 #include "../../include/y3.h"
 #include "y3_device.h"
 #include "y3_kernels.h"
@@ -94,6 +94,13 @@ __global__ __launch_bounds__(256) void conv_first(const ConvArgs p, const float 
                 o[2] = pack_bf16(v1[0], v1[1]);
                 o[3] = pack_bf16(v1[2], v1[3]);
                 if (mw + px < p.M) *reinterpret_cast<u32x4 *>(dst + (size_t)(mw + px) * COUT + c8 * 8) = o;
+            } else if constexpr (FMT == Y3_DTYPE_F16) {
+                u32x4 o;
+                o[0] = pack_f16(v0[0], v0[1]);
+                o[1] = pack_f16(v0[2], v0[3]);
+                o[2] = pack_f16(v1[0], v1[1]);
+                o[3] = pack_f16(v1[2], v1[3]);
+                if (mw + px < p.M) *reinterpret_cast<u32x4 *>(dst + (size_t)(mw + px) * COUT + c8 * 8) = o;
             } else {
                 constexpr int NPL = FMT == Y3_DTYPE_F32X3 ? 3 : 2;
                 const float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
@@ -118,6 +125,7 @@ hipError_t launch_conv_first(const ConvArgs &a, const float *w_hwio, int dtype, 
         case Y3_DTYPE_BF16: hipLaunchKernelGGL((conv_first<32, Y3_DTYPE_BF16>), grid, block, 0, s, a, w_hwio); break;
         case Y3_DTYPE_F32X3: hipLaunchKernelGGL((conv_first<32, Y3_DTYPE_F32X3>), grid, block, 0, s, a, w_hwio); break;
         case Y3_DTYPE_F32X2: hipLaunchKernelGGL((conv_first<32, Y3_DTYPE_F32X2>), grid, block, 0, s, a, w_hwio); break;
+        case Y3_DTYPE_F16: hipLaunchKernelGGL((conv_first<32, Y3_DTYPE_F16>), grid, block, 0, s, a, w_hwio); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -69,7 +69,7 @@ hipError_t launch_concat(const float *a, int Ca, const float *b, int Cb, size_t 
     return hipGetLastError();
 }
 
-// staged tensor -> fp32 (the end of a forward in a non-fp32 plan, y3_net_read_tensor): bf16, or FMT's planes of each pixel rebuilt
+// staged tensor -> fp32 (the end of a forward in a non-fp32 plan, y3_net_read_tensor): bf16, fp16, or FMT's planes of each pixel rebuilt
 // with join_planes -- the summation order of the conv kernels' shortcut operand
 template <int FMT>
 __global__ __launch_bounds__(256) void to_f32_kernel(const unsigned short *x, float *y, size_t npix, int C)
@@ -78,6 +78,8 @@ __global__ __launch_bounds__(256) void to_f32_kernel(const unsigned short *x, fl
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) {
         if constexpr (FMT == Y3_DTYPE_BF16) {
             y[i] = __uint_as_float((unsigned)x[i] << 16);
+        } else if constexpr (FMT == Y3_DTYPE_F16) {
+            y[i] = (float)__builtin_bit_cast(_Float16, x[i]);
         } else {
             constexpr int NPL = FMT == Y3_DTYPE_F32X3 ? 3 : 2;
             const size_t px = i / C;
@@ -104,6 +106,7 @@ hipError_t launch_to_f32(int dtype, const void *src, float *dst, size_t npix, in
         case Y3_DTYPE_BF16: hipLaunchKernelGGL(to_f32_kernel<Y3_DTYPE_BF16>, grid, block, 0, s, x, dst, npix, C); break;
         case Y3_DTYPE_F32X3: hipLaunchKernelGGL(to_f32_kernel<Y3_DTYPE_F32X3>, grid, block, 0, s, x, dst, npix, C); break;
         case Y3_DTYPE_F32X2: hipLaunchKernelGGL(to_f32_kernel<Y3_DTYPE_F32X2>, grid, block, 0, s, x, dst, npix, C); break;
+        case Y3_DTYPE_F16: hipLaunchKernelGGL(to_f32_kernel<Y3_DTYPE_F16>, grid, block, 0, s, x, dst, npix, C); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -60,6 +60,36 @@ __device__ __forceinline__ unsigned pack_bf16(float lo, float hi)
     return (unsigned)a | ((unsigned)b << 16);
 }
 
+// ---- fp16 (IEEE half; the conversions round to nearest even and overflow to inf, never a round-toward-zero pack) --------------
+__device__ __forceinline__ unsigned short f16_bits(float x) { return __builtin_bit_cast(unsigned short, (_Float16)x); }
+// two values -> one word of two fp16 (lo in the low half)
+__device__ __forceinline__ unsigned pack_f16(float lo, float hi)
+{
+    const unsigned short a = f16_bits(lo);
+    const unsigned short b = f16_bits(hi);
+    return (unsigned)a | ((unsigned)b << 16);
+}
+
+// ---- element traits of the 16-bit MFMA conv kernels (conv_16bit.h, conv_res_16bit.h): the fragment of eight elements a lane feeds
+// an MFMA, the two MFMA shapes, two floats -> one packed word (one rounding each, to nearest even), one packed word -> two floats.
+// The lane maps of the operands and of the accumulators are the same for both types.
+struct Bf16Elem {
+    using frag = bf16x8;
+    static __device__ __forceinline__ f32x16 mfma32(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_bf16(lo, hi); }
+    static __device__ __forceinline__ float widen_lo(unsigned w) { return __uint_as_float(w << 16); }
+    static __device__ __forceinline__ float widen_hi(unsigned w) { return __uint_as_float(w & 0xffff0000u); }
+};
+struct F16Elem {
+    using frag = f16x8;
+    static __device__ __forceinline__ f32x16 mfma32(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
+    static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_f16(lo, hi); }
+    static __device__ __forceinline__ float widen_lo(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w & 0xffffu)); }
+    static __device__ __forceinline__ float widen_hi(unsigned w) { return (float)__builtin_bit_cast(_Float16, (unsigned short)(w >> 16)); }
+};
+
 // ---- plane-split values (conv_f32x3.hip): three bf16 planes or two fp16 planes per fp32 value --------------------------------
 // x -> (hi, mid, lo) bf16 bit patterns with hi + mid + lo == x (fp32 subtractions of nearby values are exact)
 __device__ __forceinline__ void split3(float x, unsigned short &hi, unsigned short &mid, unsigned short &lo)

@@ -41,7 +41,7 @@ struct Slice {
 
     size_t img_elems(int t) const { return (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels; }
     // element size: head grids are always fp32; the image batch is fp32 when the Cin = 3 first-layer kernel reads it
-    // (a model whose input feeds an MFMA conv directly hands bf16 in bf16 mode); everything else follows the plan
+    // (a model whose input feeds an MFMA conv directly hands bf16 in bf16 mode, fp16 in fp16 mode); everything else follows the plan
     size_t elem_bytes(int t) const
     {
         if (net->out_slot[t] >= 0) return 4;
@@ -474,12 +474,12 @@ Y3_CATCH("y3_net_read_tensor")
 // ------------------------------------------------------------------------------------------ forward + decode
 namespace {
 // Can the three heads decode in place?  Each output must come from a 1x1 / stride-1 single-source conv without shortcut whose
-// 3 * (5 + nc) channels fit one 256-wide tile, written straight to the caller-visible grid (not staged), in an fp32 or bf16
-// plan.  Y3_FUSE_DECODE=0 (tools: A/B against the composed route) switches the fusion off.
+// 3 * (5 + nc) channels fit one 256-wide tile, written straight to the caller-visible grid (not staged), in an fp32, bf16
+// or fp16 plan.  Y3_FUSE_DECODE=0 (tools: A/B against the composed route) switches the fusion off.
 bool heads_can_decode(const y3_net *net)
 {
     static const bool off = [] { const char *e = getenv("Y3_FUSE_DECODE"); return e && e[0] == '0'; }();
-    if (off || net->nclasses <= 0 || (net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16)) return false;
+    if (off || net->nclasses <= 0 || (net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16 && net->dtype != Y3_DTYPE_F16)) return false;
     if (net->keep_all || net->early_ops > 0 || 3 * (5 + net->nclasses) > 256) return false;
     for (int k = 0; k < 3; ++k) {
         const int t = net->outputs[k];

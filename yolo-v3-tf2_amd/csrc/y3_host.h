@@ -59,7 +59,7 @@ struct ConvSlot {
     int tile = -1;             // -1: choose by heuristic at plan time
     int split_req = -1;        // y3_net_set_split_k: -1 the heuristic (low-latency plans only), 1 off, 2..16 forced
     int split_k = 1;           // K slices in force, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
-    int tile_bf16 = -1;
+    int tile_bf16 = -1;        // the 16-bit plans' forced tile: bf16 and fp16 plans share the tile table (y3_net_set_tile_bf16)
     int split_req_bf16 = -1;   // y3_net_set_split_k_bf16: as split_req, for bf16 plans
     int split_k_bf16 = 1;      // K slices in force in a bf16 plan (resolve_splits); 1 in every other plan
     int tile_x3 = -1;
@@ -72,6 +72,7 @@ struct ConvSlot {
     float *w0stem_dev = nullptr;   // first layer only: [28][Cout] = HWIO rows x BN scale, row 27 zero (fused stem kernel, fp32)
     float *w0raw_dev = nullptr;    // first layer only: the same without the scale (fused stem kernel, bf16 mode)
     void *wbf_dev = nullptr;   // same, bf16 (not for the first layer)
+    void *wf16_dev = nullptr;  // same, IEEE fp16 rounded to nearest even on the host (Y3_DTYPE_F16 plans; not for the first layer)
     float *scale_dev = nullptr;
     float *shift_dev = nullptr;
 };

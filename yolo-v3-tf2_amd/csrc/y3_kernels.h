@@ -142,7 +142,7 @@ struct StemArgs {
 hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s);
 hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s);   // conv0 on bf16 MFMA from split (hi + lo) operands (~2^-16 per product), bf16 patch, conv1 on bf16 MFMA
 
-// bf16 path (conv_bf16.hip)
+// bf16 path (conv_bf16.hip; the kernel body, shared with the fp16 path: conv_16bit.h)
 static constexpr int BF16_TILE_COUNT = 37;   // 32: the weight-resident 3x3 kernel (conv_res_bf16.hip); 20, 33..36: retired ids
 TileInfo conv_bf16_tile_info(int tile);
 bool conv_bf16_tile_built(int tile);
@@ -156,6 +156,10 @@ hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int
 // weight-resident 3x3 / stride-1 conv for Cin = 32 / 64 (conv_res_bf16.hip): the early short-K layers of the bf16 path
 bool conv_res_bf16_fits(const ConvArgs &a);
 hipError_t launch_conv_res_bf16(const ConvArgs &a, hipStream_t s);
+// fp16 path (conv_f16.hip, conv_res_f16.hip; Y3_DTYPE_F16): the same kernels on the f16 forms of the two MFMA instructions, the bf16
+// path's tile ids and table (conv_bf16_tile_info / conv_bf16_tile_built / conv_res_bf16_fits answer for both); no split-K form
+hipError_t launch_conv_f16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
+hipError_t launch_conv_res_f16(const ConvArgs &a, hipStream_t s);
 
 // fp32-accurate path on the bf16 matrix cores, three bf16 planes per value (conv_f32x3.hip)
 static constexpr int X3_TILE_COUNT = 34;

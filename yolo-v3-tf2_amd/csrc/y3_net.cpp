@@ -354,7 +354,7 @@ void refine_f32(const y3_net *net, const ConvSlot &c, const y3::ConvArgs &a, y3:
     if (c.d.size == 3 && c.d.src1 < 0 && ck > 0 && c.d.cin > ck && c.d.cin % ck == 0 && ck % 32 == 0) ch.k_chunk = ck;
 }
 
-// bf16 plans: a head conv that decodes its own tiles needs a 256-wide tile
+// bf16 and fp16 plans: a head conv that decodes its own tiles needs a 256-wide tile (split_k_bf16 is 1 throughout an fp16 plan)
 void refine_bf16(const y3_net *, const ConvSlot &c, const y3::ConvArgs &a, y3::ConvChoice &ch)
 {
     if (c.split_k_bf16 > 1 && !a.dec.boxes) {   // low-latency plan: S slices of the K walk into the lane's slabs, then the finish launch
@@ -382,6 +382,11 @@ constexpr y3::ConvFamily BF16_FAMILY = {
     "y3_net_set_tile_bf16: tile id %d is retired (20: the pipelined tile of round 2; 33..36: tap-row reuse and the four-wave tile of round 4; y3_tile_built)",
     "y3_net_set_tile_bf16: tile does not fit this conv", 32, resident_rule_bf16,
     &ConvSlot::wbf_dev, 2, choose_tile_bf16, y3::launch_conv_bf16, refine_bf16, y3::launch_conv_stem_bf16, &ConvSlot::w0raw_dev};
+// fp16 plans: the bf16 family's tile table, forced-tile field, chooser and refine rule; fp16 weights and launcher; no fused stem
+constexpr y3::ConvFamily F16_FAMILY = {
+    y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
+    BF16_FAMILY.bad, BF16_FAMILY.retired, BF16_FAMILY.misfit, 32, resident_rule_bf16,
+    &ConvSlot::wf16_dev, 2, choose_tile_bf16, y3::launch_conv_f16, refine_bf16, nullptr, nullptr};
 constexpr y3::ConvFamily X3_FAMILY = {
     y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x3_tile_built, &ConvSlot::tile_x3, &ConvSlot::cout_pad64,
     "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: tile does not fit this conv", -1, nullptr,
@@ -406,6 +411,7 @@ const y3::ConvFamily *y3::conv_family(int dtype)
         case Y3_DTYPE_BF16: return &BF16_FAMILY;
         case Y3_DTYPE_F32X3: return &X3_FAMILY;
         case Y3_DTYPE_F32X2: return &X2_FAMILY;
+        case Y3_DTYPE_F16: return &F16_FAMILY;
         default: return nullptr;
     }
 }
@@ -517,7 +523,7 @@ y3_status y3::resolve_splits(y3_net *net)
         ConvSlot &c = net->convs[slot];
         c.split_k = 1;
         c.split_k_bf16 = 1;
-        // fp32 and bf16 plans split, each by its own request and switch; the rule and its inputs are the same
+        // fp32 and bf16 plans split, each by its own request and switch; the rule and its inputs are the same (fp16 and plane-split plans never)
         const bool bf16 = net->dtype == Y3_DTYPE_BF16;
         if (!bf16 && net->dtype != Y3_DTYPE_F32) continue;
         if (!(bf16 ? split_eligible_bf16(net, slot, nullptr) : split_eligible(net, slot, nullptr))) continue;
@@ -662,7 +668,7 @@ void y3_net_destroy(y3_net *net)
         }
     }
     for (ConvSlot &c : net->convs)
-        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, c.wbf_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev})
+        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev})
             if (p) (void)hipFree(p);
     delete net;
 }
@@ -701,6 +707,8 @@ try {
         const std::vector<float> pk = pack_rows(w, K, d.cout, CP, nullptr), pk_scaled = pack_rows(w, K, d.cout, CP, scale.data());
         HIP_TRY(upload(c.w_dev, pk_scaled));
         HIP_TRY(upload(c.wbf_dev, pack_planes<1>(pk, K, d.cout, CP, [](float x, unsigned short *v) { v[0] = f32_to_bf16_rne(x); })));
+        // the fp16 copy, packed like the bf16 one (unscaled, round to nearest even; |w| beyond the fp16 range becomes inf, as IEEE says)
+        HIP_TRY(upload(c.wf16_dev, pack_planes<1>(pk, K, d.cout, CP, [](float x, unsigned short *v) { v[0] = f32_to_f16_rne(x); })));
         // a scaled weight outside the fp16 range: y3_net_plan(Y3_DTYPE_F32X2) refuses the net; other modes are unaffected
         c.x2_ok = std::all_of(pk_scaled.begin(), pk_scaled.end(), [](float x) { return fabsf(x) < 65504.0f; });
         HIP_TRY(upload(c.wx3_dev, pack_planes<3>(pk, K, d.cout, CP64, split_bf16x3)));         // unscaled, like the bf16 copy

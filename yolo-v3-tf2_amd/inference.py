@@ -99,9 +99,10 @@ class Inference:
         return (canvas_h, canvas_w), anchors_table
 
     def build(self, model_config_file, classes_name_file, anchors_file, input_weights_path, yolo_max_boxes,
-              nms_iou_threshold, nms_score_threshold, weights=None, low_latency=None):
+              nms_iou_threshold, nms_score_threshold, weights=None, low_latency=None, dtype=None):
         """low_latency (optional YAML key; None or absent: off): plan the network for latency at one to eight images -- the
-        fp32 convs that leave most of the chip idle at such a batch are split along K (runtime.Net.set_low_latency)."""
+        fp32 convs that leave most of the chip idle at such a batch are split along K (runtime.Net.set_low_latency).
+        dtype (optional YAML key: f32 | bf16 | f16; None or absent: f32): the conv arithmetic (runtime.Net.set_dtype)."""
         anchors_table = get_anchors(anchors_file).astype(np.float32)      # reference: inference.py:83
         class_names = [c.strip() for c in open(classes_name_file).readlines()]
         nclasses = len(class_names)
@@ -119,6 +120,7 @@ class Inference:
         else:
             model.load_weights(input_weights_path).expect_partial()
         model.set_low_latency(low_latency)
+        model.set_dtype(dtype)
         print("weights loaded")
         return DetectModel(model, anchors_table, nclasses, yolo_max_boxes, nms_iou_threshold,
                            nms_score_threshold), class_names
@@ -126,7 +128,7 @@ class Inference:
     def __call__(self, model_config_file, classes_name_file, anchors_file, input_weights_path, image_size,
                  input_data_source, images_dir, tfrecords_dir, batch_size, image_file_path, output_dir, yolo_max_boxes,
                  nms_iou_threshold, nms_score_threshold, bbox_color, font_size, display_result_images=None,
-                 save_model_path=None, weights=None, low_latency=None):
+                 save_model_path=None, weights=None, low_latency=None, dtype=None):
         os.makedirs(output_dir, exist_ok=True)
         detections_text_list_outfile = f"{output_dir}/detect.txt"
         try:
@@ -135,7 +137,8 @@ class Inference:
             pass
         out = open(detections_text_list_outfile, "a")
         model, class_names = self.build(model_config_file, classes_name_file, anchors_file, input_weights_path,
-                                        yolo_max_boxes, nms_iou_threshold, nms_score_threshold, weights, low_latency)
+                                        yolo_max_boxes, nms_iou_threshold, nms_score_threshold, weights, low_latency, dtype)
+        self.detect_model = model    # the DetectModel of the last call (its .model is the YoloModel, ._device_net() the planned Net)
         results = []
         import torch
         from . import runtime

@@ -184,6 +184,26 @@ class Net:
         check(self.lib.y3_net_set_k_chunk(self._h, int(channels)), "y3_net_set_k_chunk")
 
     @staticmethod
+    def _dtype_arg(dtype) -> int:
+        """None (absent: fp32), a _lib.Y3_DTYPE_* value or its tag ("f32", "bf16", "f16", "f32x3", "f32x2") -> the Y3_DTYPE_* value."""
+        if dtype is None:
+            return _lib.Y3_DTYPE_F32
+        if isinstance(dtype, str) and dtype in _lib.DTYPE_TAGS.values():
+            return next(k for k, v in _lib.DTYPE_TAGS.items() if v == dtype)
+        if not isinstance(dtype, (bool, np.bool_)) and isinstance(dtype, (int, np.integer)) and int(dtype) in _lib.DTYPE_TAGS:
+            return int(dtype)
+        raise Y3Error(f"dtype must be None or one of {sorted(_lib.DTYPE_TAGS.values())} (got {dtype!r})")
+
+    def set_dtype(self, dtype):
+        """The conv arithmetic of the plans this net makes for itself from now on (forward / detect re-plan when the batch
+        shape changes; plan() without a dtype): None or "f32", "bf16", "f16", "f32x3", "f32x2", or a _lib.Y3_DTYPE_* value.
+        A net already planned in another dtype is planned again, same batch and canvas."""
+        dtype = self._dtype_arg(dtype)
+        if self.max_batch and dtype != self.dtype:
+            self.plan(self.max_batch, self.image_size, dtype)
+        self.dtype = dtype
+
+    @staticmethod
     def _low_latency_arg(on) -> bool:
         if on is None:
             return False
@@ -270,13 +290,15 @@ class Net:
         self._force("_x2", self.lib.y3_net_set_tile_x2, slot, tile)
 
     def set_tile_bf16(self, slot: int, tile: int):
+        """Force a tile of the 16-bit conv family on conv `slot`: acts on bf16 and fp16 plans alike (one tile table, one field)."""
         self._force("_bf16", self.lib.y3_net_set_tile_bf16, slot, tile)
 
     def plan(self, max_batch: int, image_size, dtype: Optional[int] = None):
         """image_size: an int S (the S x S canvas) or an (H, W) pair, both sides multiples of 32 (y3_net_plan_hw).
         dtype: _lib.Y3_DTYPE_F32 (default, fp32 MFMA), _lib.Y3_DTYPE_F32X3 (fp32-accurate on the bf16 matrix cores:
         three bf16 planes per value), _lib.Y3_DTYPE_F32X2 (two fp16 planes per value, 2^-22 representation, |x| < 65504)
-        or _lib.Y3_DTYPE_BF16 (bf16 activations/weights, fp32 accumulate)."""
+        _lib.Y3_DTYPE_BF16 (bf16 activations/weights, fp32 accumulate) or _lib.Y3_DTYPE_F16 (the same with IEEE fp16: 8 x closer to
+        fp32, values beyond 65504 become inf; never the fused stem, never split-K)."""
         if dtype is None:
             dtype = self.dtype
         H, W = canvas_hw(image_size)
@@ -293,14 +315,16 @@ class Net:
 
     def _apply_tuning(self):
         """Per-conv tile ids measured by tools/tune_tiles.py for this (dtype, batch, image size), if a table exists;
-        otherwise the library's heuristic stays in force."""
+        otherwise the library's heuristic stays in force.  An fp16 plan takes the bf16 table of its batch and size, lanes included,
+        through set_tile_bf16 (same kernels, same tile ids; no fp16 table is tuned or shipped)."""
         import json
         import os
-        tag = _lib.DTYPE_TAGS[self.dtype]
+        tag = _lib.DTYPE_TAGS[_lib.Y3_DTYPE_BF16 if self.dtype == _lib.Y3_DTYPE_F16 else self.dtype]
         path = tuning_table_path(tag, self.max_batch, self.image_size)
         kind, fn = {_lib.Y3_DTYPE_F32: ("", self.lib.y3_net_set_tile), _lib.Y3_DTYPE_BF16: ("_bf16", self.lib.y3_net_set_tile_bf16),
                     _lib.Y3_DTYPE_F32X3: ("_x3", self.lib.y3_net_set_tile_x3),
-                    _lib.Y3_DTYPE_F32X2: ("_x2", self.lib.y3_net_set_tile_x2)}[self.dtype]
+                    _lib.Y3_DTYPE_F32X2: ("_x2", self.lib.y3_net_set_tile_x2),
+                    _lib.Y3_DTYPE_F16: ("_bf16", self.lib.y3_net_set_tile_bf16)}[self.dtype]
         forced = self.__dict__.get("_forced_tiles", {})
         table, lanes = {}, 1
         if os.path.exists(path) and not os.environ.get("Y3_NO_TUNING"):
@@ -336,7 +360,7 @@ class Net:
         """images [B,H,W,3] fp32 on the GPU -> [grid13, grid26, grid52], each [B,gh,gw,3,5+nc]."""
         _need_cuda(images)
         cin = self.program.tensors[self.program.input_tensor].channels
-        # bf16 plan + an input that feeds an MFMA conv directly (layer tests): the input is bf16 as well
+        # bf16 / fp16 plan + an input that feeds an MFMA conv directly (layer tests): the input is bf16 / fp16 as well
         if self.dtype == _lib.Y3_DTYPE_F32X3 and cin != 3:
             # layer tests: an input feeding an MFMA conv directly is handed over as three bf16 planes [B,S,S,3,C]
             if images.dtype != torch.bfloat16 or images.dim() != 5 or images.shape[3] != 3 or images.shape[4] != cin:
@@ -345,7 +369,7 @@ class Net:
             if images.dtype != torch.float16 or images.dim() != 5 or images.shape[3] != 2 or images.shape[4] != cin:
                 raise Y3Error(f"images must be float16 [B,S,S,2,{cin}] (split2_planes) in the two-plane mode")
         else:
-            want = torch.bfloat16 if (self.dtype == _lib.Y3_DTYPE_BF16 and cin != 3) else torch.float32
+            want = torch.float32 if cin == 3 else {_lib.Y3_DTYPE_BF16: torch.bfloat16, _lib.Y3_DTYPE_F16: torch.float16}.get(self.dtype, torch.float32)
             if images.dtype != want or images.dim() != 4 or images.shape[3] != cin:
                 raise Y3Error(f"images must be {want} [B,S,S,{cin}]")
         B = self._plan_for(images)

@@ -451,3 +451,45 @@ def test_split_bf16_refusals(rt, program, weights):
     assert all(net.split_k(i) == 1 for i in range(len(ops)))
     with pytest.raises(rt.Y3Error, match="F32"):
         net.set_split_k(small, 2)
+
+
+# ---------------------------------------------------------------------------------------------- 8. one value in force, requests per mode
+def test_one_split_in_force_follows_the_plans_mode(rt, program, weights):
+    """ConvSlot::split_k is the one value in force while the requests and switches stay per mode: a net with both switches on and one
+    forced split per mode, planned fp32, bf16, fp16 and fp32 again, shows after every plan the slices (own mode's getter; all 1 from the
+    other's, all 1 from both on the fp16 plan) and the three grids, bit for bit, of a fresh net planned once in that mode."""
+    F32, F16 = _lib.Y3_DTYPE_F32, _lib.Y3_DTYPE_F16
+    x = _cuda(np.random.default_rng(51).random((1, 64, 64, 3), dtype=np.float32))
+
+    def make():
+        net = rt.Net(program)
+        net.load_weights(weights)
+        net.set_low_latency(True)
+        net.set_low_latency_bf16(True)
+        return net
+
+    ops = make().conv_ops
+    s32 = next(i for i, o in enumerate(ops) if o.size == 1 and o.cin == 128 and o.cout == 64)     # 4 K tiles of 32
+    s16 = next(i for i, o in enumerate(ops) if o.size == 1 and o.cin == 256 and o.cout == 128)    # 4 K tiles of 64
+    ones = [1] * len(ops)
+
+    def state(net):
+        grids = [g.clone() for g in net.forward(x)]
+        torch.cuda.synchronize()
+        return [net.split_k(i) for i in range(len(ops))], _splits(net), grids
+
+    fresh = {}
+    for dtype in (BF16, F16, F32):     # the fp32 one, fresh here, is the net that is planned again below
+        net = make()
+        net.set_split_k(s32, 4)
+        net.set_split_k_bf16(s16, 2)
+        net.plan(1, 64, dtype)
+        fresh[dtype] = state(net)
+    assert fresh[F32][0][s32] == 4 and any(s > 1 for i, s in enumerate(fresh[F32][0]) if i != s32) and fresh[F32][1] == ones
+    assert fresh[BF16][1][s16] == 2 and any(s > 1 for i, s in enumerate(fresh[BF16][1]) if i != s16) and fresh[BF16][0] == ones
+    assert fresh[F16][0] == ones and fresh[F16][1] == ones
+    for dtype in (BF16, F16, F32):
+        net.plan(1, 64, dtype)
+        f32_splits, bf16_splits, grids = state(net)
+        assert f32_splits == fresh[dtype][0] and bf16_splits == fresh[dtype][1], dtype
+        assert all(torch.equal(a, b) for a, b in zip(grids, fresh[dtype][2])), dtype

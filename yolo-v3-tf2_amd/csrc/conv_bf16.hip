@@ -81,26 +81,14 @@ static hipError_t launch_split_t(const ConvArgs &c, int grid, int S, hipStream_t
 
 bool conv_bf16_split_tile(int tile) { return tile == 11 || tile == 12; }
 
-size_t conv_bf16_split_slab_bytes(int tile, long long M, int cout_pad)
-{
-    const TileInfo t = conv_bf16_tile_info(tile);
-    return (size_t)((M + t.bm - 1) / t.bm) * t.bm * cout_pad * sizeof(float);
-}
-
 hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    if (!conv_bf16_split_tile(tile) || !tile_fits(Tiles16<Bf16Elem>::table[tile].info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
-    const size_t slab = conv_bf16_split_slab_bytes(tile, a.M, a.CoutPad);
-    if (S < 2 || S > a.K / 64 || !ws || !a.dst || a.dec.boxes || slab > 0x7fffffffull || (size_t)S * slab > ws_bytes) return hipErrorInvalidValue;
+    if (!conv_bf16_split_tile(tile)) return hipErrorInvalidValue;
+    const auto [c, slab, grid] = split_launch(a, Tiles16<Bf16Elem>::table[tile].info, S, ws, ws_bytes);
+    if (!slab) return hipErrorInvalidValue;
     // the bf16 form of the finish launch moves eight channels per thread: whole 16-byte pieces of dst and of the shortcut
     if (!out_f32 && (a.Cout % 8 || ((uintptr_t)a.dst & 15) || ((uintptr_t)a.residual & 15))) return hipErrorInvalidValue;
     if (out_f32 && a.residual) return hipErrorInvalidValue;
-    const TileInfo t = Tiles16<Bf16Elem>::table[tile].info;
-    ConvArgs c = a;
-    c.dst = ws;
-    c.dst_bytes = (unsigned)slab;
-    c.residual = nullptr;
-    const int grid = ((a.M + t.bm - 1) / t.bm) * (a.CoutPad / t.bn);
     if (hipError_t e = tile == 12 ? launch_split_t<2>(c, grid, S, s) : launch_split_t<1>(c, grid, S, s); e != hipSuccess) return e;
     const float *wsf = static_cast<const float *>(ws);
     const unsigned short *res = static_cast<const unsigned short *>(a.residual);

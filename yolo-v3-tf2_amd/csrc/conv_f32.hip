@@ -551,25 +551,11 @@ static hipError_t launch_split_t(const ConvArgs &c, int grid, int S, hipStream_t
 
 bool conv_split_tile(int tile) { return tile == 10 || tile == 11; }
 
-size_t conv_split_slab_bytes(int tile, long long M, int cout_pad)
-{
-    const TileInfo t = conv_tile_info(tile);
-    return (size_t)((M + t.bm - 1) / t.bm) * t.bm * cout_pad * sizeof(float);
-}
-
 hipError_t launch_conv_f32_split(const ConvArgs &a, int tile, int S, void *ws, size_t ws_bytes, hipStream_t s)
 {
-    if (!conv_split_tile(tile) || !tile_fits(kTiles[tile].info, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
-    const size_t slab = conv_split_slab_bytes(tile, a.M, a.CoutPad);
-    if (S < 2 || S > a.K / BK || !ws || !a.dst || slab > 0x7fffffffull || (size_t)S * slab > ws_bytes) return hipErrorInvalidValue;
-    const TileInfo t = kTiles[tile].info;
-    ConvArgs c = a;
-    c.dst = ws;
-    c.dst_bytes = (unsigned)slab;
-    c.residual = nullptr;
-    c.xcd_gn = 0;
-    c.clk_stamps = nullptr;
-    const int grid = ((a.M + t.bm - 1) / t.bm) * (a.CoutPad / t.bn);
+    if (!conv_split_tile(tile)) return hipErrorInvalidValue;
+    const auto [c, slab, grid] = split_launch(a, kTiles[tile].info, S, ws, ws_bytes);
+    if (!slab) return hipErrorInvalidValue;
     if (hipError_t e = tile == 10 ? launch_split_t<2>(c, grid, S, s) : launch_split_t<1>(c, grid, S, s); e != hipSuccess) return e;
     const float *wsf = static_cast<const float *>(ws), *res = static_cast<const float *>(a.residual);
     float *dst = static_cast<float *>(a.dst);

@@ -37,7 +37,7 @@ struct Slice {
     const Forward &f;
     int b0, nb, lane;
     hipStream_t s;
-    const y3::ConvFamily &fam = *y3::conv_family(net->dtype);
+    const y3::ConvFamily &fam = y3::family_of(net);
 
     size_t img_elems(int t) const { return (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels; }
     // element size: head grids are always fp32; the image batch is fp32 when the Cin = 3 first-layer kernel reads it
@@ -165,12 +165,8 @@ struct Slice {
             case y3::ConvKind::HeadDecodeF32: e = y3::launch_conv_head_decode_f32(a, s); break;
             case y3::ConvKind::SplitK:
                 if (lane >= net->split_ws_lanes) return fail(Y3_ERR_STATE, "conv %d: no split-K workspace for lane %d", conv, lane);
-                if (net->dtype == Y3_DTYPE_BF16)
-                    e = y3::launch_conv_bf16_split(a, ch.tile, net->out_slot[c.d.dst] >= 0, ch.split_k,
-                                                   static_cast<char *>(net->split_ws) + (size_t)lane * net->split_ws_lane, net->split_ws_lane, s);
-                else
-                    e = y3::launch_conv_f32_split(a, ch.tile, ch.split_k, static_cast<char *>(net->split_ws) + (size_t)lane * net->split_ws_lane,
-                                                  net->split_ws_lane, s);
+                e = fam.split->launch(a, ch.tile, net->out_slot[c.d.dst] >= 0, ch.split_k,
+                                      static_cast<char *>(net->split_ws) + (size_t)lane * net->split_ws_lane, net->split_ws_lane, s);
                 break;
             default:   // Mfma; out_f32 (bf16 / plane-split plans): the launch stores the caller's fp32 grid itself
                 e = fam.launch(a, ch.tile, net->out_slot[c.d.dst] >= 0, s);

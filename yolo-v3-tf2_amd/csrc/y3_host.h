@@ -58,10 +58,9 @@ struct ConvSlot {
     int K = 0;
     int tile = -1;             // -1: choose by heuristic at plan time
     int split_req = -1;        // y3_net_set_split_k: -1 the heuristic (low-latency plans only), 1 off, 2..16 forced
-    int split_k = 1;           // K slices in force, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
-    int tile_bf16 = -1;        // the 16-bit plans' forced tile: bf16 and fp16 plans share the tile table (y3_net_set_tile_bf16)
     int split_req_bf16 = -1;   // y3_net_set_split_k_bf16: as split_req, for bf16 plans
-    int split_k_bf16 = 1;      // K slices in force in a bf16 plan (resolve_splits); 1 in every other plan
+    int split_k = 1;           // K slices in force in the current plan, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
+    int tile_bf16 = -1;        // the 16-bit plans' forced tile: bf16 and fp16 plans share the tile table (y3_net_set_tile_bf16)
     int tile_x3 = -1;
     int cout_pad64 = 0;        // Cout rounded up to 64 (the three-plane kernel has no 32-wide N tile)
     void *wx3_dev = nullptr;   // packed [CoutPad64][3 planes][K] bf16 (hi, mid, lo of the fp32 weights)
@@ -120,7 +119,7 @@ struct y3_net {
     int xcd_mode = 1;              // y3_net_set_xcd_mode: 0 contiguous tile runs per XCD, 1 XCD-blocked order chosen per conv
     bool low_latency_set = false;  // y3_net_set_low_latency was called (the Y3_LOW_LATENCY tool override then stays out)
     bool low_latency = false;      // y3_net_set_low_latency: every eligible fp32 conv takes y3_choose_split_k
-    bool low_latency_bf16 = false;       // y3_net_set_low_latency_bf16: every eligible bf16 conv takes y3_choose_split_k
+    bool low_latency_bf16 = false; // y3_net_set_low_latency_bf16: every eligible bf16 conv takes y3_choose_split_k
     void *split_ws = nullptr;      // split-K slabs: split_ws_lanes regions of split_ws_lane bytes, one per lane (lanes run concurrently)
     size_t split_ws_lane = 0;
     int split_ws_lanes = 0;
@@ -143,6 +142,19 @@ namespace y3 {
 // One conv family per plan mode (Y3_DTYPE_*): its tile table (y3_tile_built), the tile a caller forced on a conv, the texts with which
 // its setter refuses one (y3_net_set_tile*), and what a launch of the mode takes: weights, chooser, launcher.
 struct ConvChoice;
+// What a mode needs in order to split K (ConvFamily::split).  The request and the switch stay per mode; ConvSlot::split_k is the plan's.
+struct SplitForm {
+    bool (*tile)(int);                             // the tile ids with a split form
+    hipError_t (*launch)(const ConvArgs &, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t);
+    int bk, min_k_tiles;                           // K-tile width of those tiles; the rule leaves a conv of fewer K tiles alone
+    int ConvSlot::*req;                            // the caller's request: -1 the rule (low-latency plans only), 1 off, 2..16 forced
+    bool y3_net::*low_latency;                     // the switch: every eligible conv takes y3_choose_split_k
+    const char *set_split, *set_switch;            // the two setters' names, for their messages
+    const char *(*no_form)(int tile);              // refusals: the tile has no split form,
+    const char *tiles, *other_plan;                // nor has the tile at the planned rows ("tiles A and B have"), the plan is another mode's,
+    int cout_mult;                                 // Cout of a conv storing the mode's own format is no multiple of this
+    const char *bad_cout;
+};
 struct ConvFamily {
     int count;                                     // tile ids are [0, count)
     TileInfo (*info)(int);
@@ -163,8 +175,10 @@ struct ConvFamily {
     // fused stem kernel (null: the mode has none) and the first layer's 28-row weights it reads
     hipError_t (*launch_stem)(const StemArgs &, hipStream_t);
     float *ConvSlot::*w0_stem;
+    const SplitForm *split;                        // null: the mode never splits K
 };
 const ConvFamily *conv_family(int dtype);   // null: no such mode
+inline const ConvFamily &family_of(const y3_net *net) { return *conv_family(net->dtype); }   // the planned mode's (fp32 before the first plan)
 
 // What conv op `oi` launches for the rows of one call.  InStem: nothing of its own, it runs inside the Stem launch of op 1.
 enum class ConvKind { First, Stem, InStem, HeadDecodeF32, Mfma, SplitK };

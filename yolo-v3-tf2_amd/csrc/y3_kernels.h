@@ -87,6 +87,26 @@ inline bool tile_fits(const TileInfo &t, int cin, int c0, int cout_pad)
     return t.bm > 0 && cin % t.bk == 0 && cout_pad % t.bn == 0 && (c0 < 0 || c0 % t.bk == 0);
 }
 
+// Split-K: one slice's slab of raw fp32 accumulators, [Mpad][CoutPad] with M padded to whole tiles
+inline size_t split_slab_bytes(const TileInfo &t, long long M, int cout_pad) { return (size_t)((M + t.bm - 1) / t.bm) * t.bm * cout_pad * sizeof(float); }
+// What the split launchers of conv_f32.hip and conv_bf16.hip share before their kernel dispatch: S, the slab and the workspace checked,
+// then the slice launch's arguments (raw accumulators into ws: no shortcut, no tile order, no stamps) and its grid.  slab = 0: refused.
+struct SplitLaunch { ConvArgs c; size_t slab; int grid; };
+inline SplitLaunch split_launch(const ConvArgs &a, const TileInfo &t, int S, void *ws, size_t ws_bytes)
+{
+    SplitLaunch l{a, 0, 0};
+    const size_t slab = tile_fits(t, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad) ? split_slab_bytes(t, a.M, a.CoutPad) : 0;
+    if (!slab || S < 2 || S > a.K / t.bk || !ws || !a.dst || a.dec.boxes || slab > 0x7fffffffull || (size_t)S * slab > ws_bytes) return l;
+    l.c.dst = ws;
+    l.c.dst_bytes = (unsigned)slab;
+    l.c.residual = nullptr;
+    l.c.xcd_gn = 0;
+    l.c.clk_stamps = nullptr;
+    l.slab = slab;
+    l.grid = ((a.M + t.bm - 1) / t.bm) * (a.CoutPad / t.bn);
+    return l;
+}
+
 // fp32 MFMA kernel (table in conv_f32.hip; bk = 32)
 static constexpr int TILE_COUNT = 34;  // 33: the weight-resident 3x3 kernel (conv_res_f32.hip); ids without a selecting plan are retired (conv_f32.hip)
 TileInfo conv_tile_info(int tile);
@@ -94,10 +114,9 @@ bool conv_tile_built(int tile);        // false: retired id
 
 hipError_t launch_conv_f32(const ConvArgs &a, int tile, hipStream_t s);
 // split-K form of the same conv (conv_f32.hip): S >= 2 slices of the K walk as S times the workgroups, raw accumulators into
-// ws [S][Mpad][CoutPad] fp32 (at least S * conv_split_slab_bytes), then splitk_finish_f32 on the same stream: the slabs added in
+// ws [S][Mpad][CoutPad] fp32 (at least S * split_slab_bytes), then splitk_finish_f32 on the same stream: the slabs added in
 // the order 0..S-1, the epilogue, the store to a.dst.  Tiles 10 and 11 only (conv_split_tile).
 bool conv_split_tile(int tile);
-size_t conv_split_slab_bytes(int tile, long long M, int cout_pad);
 hipError_t launch_conv_f32_split(const ConvArgs &a, int tile, int S, void *ws, size_t ws_bytes, hipStream_t s);
 // weight-resident 3x3 / stride-1 / Cin = 32 conv (conv_res_f32.hip): tile id 33
 bool conv_res_f32_fits(const ConvArgs &a);
@@ -148,10 +167,9 @@ TileInfo conv_bf16_tile_info(int tile);
 bool conv_bf16_tile_built(int tile);
 hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
 // split-K form of the same conv (conv_bf16.hip): S >= 2 slices of the K walk (K tiles of 64) as S times the workgroups, raw fp32
-// accumulators into ws [S][Mpad][CoutPad] (at least S * conv_bf16_split_slab_bytes), then splitk_finish_bf16 on the same stream: the
+// accumulators into ws [S][Mpad][CoutPad] (at least S * split_slab_bytes), then splitk_finish_bf16 on the same stream: the
 // slabs added in the order 0..S-1, the epilogue, the store to a.dst (bf16, or fp32 with out_f32).  Tiles 11 and 12 only.
 bool conv_bf16_split_tile(int tile);
-size_t conv_bf16_split_slab_bytes(int tile, long long M, int cout_pad);
 hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s);
 // weight-resident 3x3 / stride-1 conv for Cin = 32 / 64 (conv_res_bf16.hip): the early short-K layers of the bf16 path
 bool conv_res_bf16_fits(const ConvArgs &a);

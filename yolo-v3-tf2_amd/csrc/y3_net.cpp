@@ -272,10 +272,10 @@ int choose_tile(const ConvSlot &c, long long M, long long, bool)
 }  // namespace
 
 // The first two ops are conv0 (3x3/1, 3 -> 32) and conv1 (3x3/2, 32 -> 64, no shortcut, single source) reading it, nobody
-// else reads conv0's output, and the plan is fp32 with every intermediate reusable: the pair runs as csrc/conv_stem.hip.
+// else reads conv0's output, and the plan's mode has a fused stem with every intermediate reusable: the pair runs as csrc/conv_stem.hip.
 bool y3::stem_applicable(const y3_net *net)
 {
-    if ((net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16) || net->keep_all || net->height % 32 || net->width % 32 || net->early_ops > 0)
+    if (!family_of(net).launch_stem || net->keep_all || net->height % 32 || net->width % 32 || net->early_ops > 0)
         return false;
     if (net->ops.size() < 2 || net->ops[0].kind != 0 || net->ops[1].kind != 0) return false;
     const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[1].index];
@@ -300,7 +300,7 @@ bool y3::stem_applicable(const y3_net *net)
 // still holds on chip (fp32 and bf16 plans)
 bool y3::stem_conv2_applicable(const y3_net *net)
 {
-    if ((net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16) || net->ops.size() < 3 || net->ops[2].kind != 0) return false;
+    if (!family_of(net).launch_stem || net->ops.size() < 3 || net->ops[2].kind != 0) return false;
     const y3_conv_desc &b = net->convs[net->ops[1].index].d, &c = net->convs[net->ops[2].index].d;
     if (c.size != 1 || c.stride != 1 || c.cin != 64 || c.cout != 32 || c.residual >= 0 || c.src1 >= 0 || c.src0 != b.dst) return false;
     return !is_output(net, c.dst);
@@ -354,11 +354,11 @@ void refine_f32(const y3_net *net, const ConvSlot &c, const y3::ConvArgs &a, y3:
     if (c.d.size == 3 && c.d.src1 < 0 && ck > 0 && c.d.cin > ck && c.d.cin % ck == 0 && ck % 32 == 0) ch.k_chunk = ck;
 }
 
-// bf16 and fp16 plans: a head conv that decodes its own tiles needs a 256-wide tile (split_k_bf16 is 1 throughout an fp16 plan)
+// bf16 and fp16 plans: a head conv that decodes its own tiles needs a 256-wide tile (split_k is 1 throughout an fp16 plan)
 void refine_bf16(const y3_net *, const ConvSlot &c, const y3::ConvArgs &a, y3::ConvChoice &ch)
 {
-    if (c.split_k_bf16 > 1 && !a.dec.boxes) {   // low-latency plan: S slices of the K walk into the lane's slabs, then the finish launch
-        ch.split_k = c.split_k_bf16;
+    if (c.split_k > 1 && !a.dec.boxes) {   // low-latency plan: S slices of the K walk into the lane's slabs, then the finish launch
+        ch.split_k = c.split_k;
         ch.kind = y3::ConvKind::SplitK;
         return;
     }
@@ -370,31 +370,60 @@ void refine_bf16(const y3_net *, const ConvSlot &c, const y3::ConvArgs &a, y3::C
 }
 
 hipError_t launch_f32(const y3::ConvArgs &a, int tile, bool, hipStream_t s) { return y3::launch_conv_f32(a, tile, s); }
+hipError_t launch_f32_split(const y3::ConvArgs &a, int tile, bool, int S, void *ws, size_t n, hipStream_t s) { return y3::launch_conv_f32_split(a, tile, S, ws, n, s); }
+
+// K tiles of 64 from which the rule splits a bf16 conv.  bf16 plans leave a conv of fewer than 32 K tiles to its one launch: in
+// profiles/latency_bf16_splitk_sweep.txt every conv of 36 or 72 K tiles gains from the rule's S at every batch from 1 to 8, while the
+// convs of 4 .. 18 K tiles (launches of 7 .. 15 us) lose to the finish launch and the slab traffic at some batch (the 13^2 1x1 of 16 K
+// tiles: -2 us at one image, +3.5 us at eight; the 52^2 3x3 of 18 K tiles: +1.5 .. +5 us).  The sweep times one net object at every S; the
+// end-to-end runs of profiles/latency_bf16.txt cannot resolve this at eight images (two net objects differ by more).  A forced S is taken
+// as given.  Y3_SPLIT_MIN_K_TILES_BF16: a variant build for the record (csrc/build.py --variant OUT.so y3_net.cpp
+// -DY3_SPLIT_MIN_K_TILES_BF16=0: y3_choose_split_k alone decides).
+#ifndef Y3_SPLIT_MIN_K_TILES_BF16
+#define Y3_SPLIT_MIN_K_TILES_BF16 32
+#endif
+constexpr int kSplitMinKTilesBf16 = Y3_SPLIT_MIN_K_TILES_BF16;
+
+// fp32: tiles 10 and 11 (register-staged, BK = 32), any K, any Cout (the finish launch has a scalar form)
+constexpr y3::SplitForm F32_SPLIT = {
+    y3::conv_split_tile, launch_f32_split, 32, 0, &ConvSlot::split_req, &y3_net::low_latency, "y3_net_set_split_k", "y3_net_set_low_latency",
+    [](int) { return "the conv's tile has no split form (tiles 10 and 11 have; the weight-resident tile 33 and the 32-wide tile 8 have not)"; },
+    "tiles 10 and 11 have",
+    "only Y3_DTYPE_F32 plans split K", 1, nullptr};
+// bf16: tiles 11 and 12 (LDS-DMA, BK = 64, 32x32x16 MFMA); the finish launch stores bf16 in whole 16-byte pieces (a conv that writes an
+// fp32 net output itself takes any Cout)
+constexpr y3::SplitForm BF16_SPLIT = {
+    y3::conv_bf16_split_tile, y3::launch_conv_bf16_split, 64, kSplitMinKTilesBf16, &ConvSlot::split_req_bf16, &y3_net::low_latency_bf16,
+    "y3_net_set_split_k_bf16", "y3_net_set_low_latency_bf16",
+    [](int tile) { return tile == 32 ? "the weight-resident tile 32 has no split form" : y3::conv_bf16_tile_info(tile).bk == 32
+                       ? "the BK = 32 tiles (Cin = 32 layers) have no split form" : "the conv's tile has no split form (tiles 11 and 12 have)"; },
+    "tiles 11 and 12 have",
+    "only Y3_DTYPE_BF16 plans take a bf16 split", 8, "a split conv storing bf16 needs Cout % 8 == 0"};
 
 constexpr y3::ConvFamily F32_FAMILY = {
     y3::TILE_COUNT, y3::conv_tile_info, y3::conv_tile_built, &ConvSlot::tile, &ConvSlot::cout_pad,
     "y3_net_set_tile: bad argument", "y3_net_set_tile: tile id %d is retired (the timing ablations of rounds 1-2; y3_tile_built)",
     "y3_net_set_tile: tile does not divide Cout", 33, resident_rule_f32,
-    &ConvSlot::w_dev, 4, choose_tile, launch_f32, refine_f32, y3::launch_conv_stem_f32, &ConvSlot::w0stem_dev};
+    &ConvSlot::w_dev, 4, choose_tile, launch_f32, refine_f32, y3::launch_conv_stem_f32, &ConvSlot::w0stem_dev, &F32_SPLIT};
 constexpr y3::ConvFamily BF16_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
     "y3_net_set_tile_bf16: bad argument",
     "y3_net_set_tile_bf16: tile id %d is retired (20: the pipelined tile of round 2; 33..36: tap-row reuse and the four-wave tile of round 4; y3_tile_built)",
     "y3_net_set_tile_bf16: tile does not fit this conv", 32, resident_rule_bf16,
-    &ConvSlot::wbf_dev, 2, choose_tile_bf16, y3::launch_conv_bf16, refine_bf16, y3::launch_conv_stem_bf16, &ConvSlot::w0raw_dev};
-// fp16 plans: the bf16 family's tile table, forced-tile field, chooser and refine rule; fp16 weights and launcher; no fused stem
+    &ConvSlot::wbf_dev, 2, choose_tile_bf16, y3::launch_conv_bf16, refine_bf16, y3::launch_conv_stem_bf16, &ConvSlot::w0raw_dev, &BF16_SPLIT};
+// fp16 plans: the bf16 family's tile table, forced-tile field, chooser and refine rule; fp16 weights and launcher; no fused stem, no split form
 constexpr y3::ConvFamily F16_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
     BF16_FAMILY.bad, BF16_FAMILY.retired, BF16_FAMILY.misfit, 32, resident_rule_bf16,
-    &ConvSlot::wf16_dev, 2, choose_tile_bf16, y3::launch_conv_f16, refine_bf16, nullptr, nullptr};
+    &ConvSlot::wf16_dev, 2, choose_tile_bf16, y3::launch_conv_f16, refine_bf16, nullptr, nullptr, nullptr};
 constexpr y3::ConvFamily X3_FAMILY = {
     y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x3_tile_built, &ConvSlot::tile_x3, &ConvSlot::cout_pad64,
     "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: tile does not fit this conv", -1, nullptr,
-    &ConvSlot::wx3_dev, 6, choose_tile_x3, y3::launch_conv_f32x3, nullptr, nullptr, nullptr};
+    &ConvSlot::wx3_dev, 6, choose_tile_x3, y3::launch_conv_f32x3, nullptr, nullptr, nullptr, nullptr};
 constexpr y3::ConvFamily X2_FAMILY = {
     y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x2_tile_built, &ConvSlot::tile_x2, &ConvSlot::cout_pad64,
     "y3_net_set_tile_x2: bad argument", "y3_net_set_tile_x2: tile does not fit this conv", "y3_net_set_tile_x2: tile does not fit this conv", -1, nullptr,
-    &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr};
+    &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr, nullptr};
 
 // "forced tile, else the family's chooser": the tile part of the launch decision
 int family_tile(const y3::ConvFamily &f, const ConvSlot &c, long long M, long long M_plan, bool arena_out)
@@ -428,7 +457,7 @@ y3::ConvChoice y3::choose_conv(const y3_net *net, int oi, const ConvArgs &a)
     else if (net->stem_fused && oi == 1) ch.kind = ConvKind::Stem;
     else if (c.first_layer) ch.kind = ConvKind::First;
     if (ch.kind != ConvKind::Mfma) return ch;
-    const ConvFamily &f = *conv_family(net->dtype);
+    const ConvFamily &f = family_of(net);
     ch.tile = family_tile(f, c, a.M, (long long)net->max_batch * a.Ho * a.Wo, net->out_slot[c.d.dst] < 0);
     if (f.refine) f.refine(net, c, a, ch);
     return ch;
@@ -441,7 +470,7 @@ y3::ConvChoice y3::choose_conv_planned(const y3_net *net, int oi)
     a.Ho = net->height / c.d.out_div;
     a.Wo = net->width / c.d.out_div;
     a.M = net->max_batch * a.Ho * a.Wo;
-    a.CoutPad = c.*conv_family(net->dtype)->cout_pad;
+    a.CoutPad = c.*family_of(net).cout_pad;
     return choose_conv(net, oi, a);
 }
 
@@ -468,43 +497,22 @@ static y3_status set_forced_tile(const y3::ConvFamily &f, y3_net *net, int slot,
 }
 
 // ---- split-K (low-latency fp32 and bf16 plans) --------------------------------------------------------------------------------------
-// Can conv `slot` ever run split?  From the graph and the forced tile alone (no plan needed): not the first layer, not the
-// weight-resident tile 33, not a detection head (y3_net_detect runs the heads through conv_head.hip, and the composed route
-// must stay bit-identical to it), and only on the two tiles the split form is built for.  why: the refusal's text.
-static bool split_eligible(const y3_net *net, int slot, const char **why)
+// Can conv `slot` ever run split in the mode of `f` (which has a split form)?  From the graph and the forced tile alone (no plan needed):
+// not the first layer, not a detection head (y3_net_detect runs the heads through conv_head.hip / decodes them in the launch, and the
+// composed route must stay bit-identical to it), only on the tiles the split form is built for, and with a Cout the mode's finish launch
+// can store.  why: the refusal's text.
+static bool split_eligible(const y3::ConvFamily &f, const y3_net *net, int slot, const char **why)
 {
+    const y3::SplitForm &sf = *f.split;
     const ConvSlot &c = net->convs[slot];
     const char *w = nullptr;
-    if (c.first_layer) w = "the first layer (Cin = 3) is never split";
-    else if (net->nclasses > 0 && is_output(net, c.d.dst)) w = "a detection-head conv is never split (y3_net_detect decodes it in its own kernel)";
-    else if (!y3::conv_split_tile(family_tile(F32_FAMILY, c, 1, 1, true)))
-        w = "the conv's tile has no split form (tiles 10 and 11 have; the weight-resident tile 33 and the 32-wide tile 8 have not)";
-    if (why) *why = w;
-    return !w;
-}
-
-// K tiles of 64 from which the rule splits a bf16 conv (resolve_splits says why).  Y3_SPLIT_MIN_K_TILES_BF16: a variant build for the record
-// (csrc/build.py --variant OUT.so y3_net.cpp -DY3_SPLIT_MIN_K_TILES_BF16=0: y3_choose_split_k alone decides).
-#ifndef Y3_SPLIT_MIN_K_TILES_BF16
-#define Y3_SPLIT_MIN_K_TILES_BF16 32
-#endif
-static constexpr int kSplitMinKTilesBf16 = Y3_SPLIT_MIN_K_TILES_BF16;
-
-// The same question for a bf16 plan: the split form exists for tiles 11 and 12 (LDS-DMA, BK = 64, 32x32x16 MFMA) only.
-static bool split_eligible_bf16(const y3_net *net, int slot, const char **why)
-{
-    const ConvSlot &c = net->convs[slot];
-    const char *w = nullptr;
-    // the conv's smallest tile; arena_out as the plan will have it (a conv writing an fp32 net output itself never takes tile 32)
+    // the conv's smallest tile; arena_out as the plan will have it (a conv writing an fp32 net output itself never takes bf16's tile 32)
     const bool arena_out = !is_output(net, c.d.dst) || y3::output_staged(net, c.d.dst);
-    const int tile = c.first_layer ? -1 : family_tile(BF16_FAMILY, c, 1, 1, arena_out);
+    const int tile = c.first_layer ? -1 : family_tile(f, c, 1, 1, arena_out);
     if (c.first_layer) w = "the first layer (Cin = 3) is never split";
     else if (net->nclasses > 0 && is_output(net, c.d.dst)) w = "a detection-head conv is never split (y3_net_detect decodes it in its own launch)";
-    else if (tile == 32) w = "the weight-resident tile 32 has no split form";
-    else if (y3::conv_bf16_tile_info(tile).bk == 32) w = "the BK = 32 tiles (Cin = 32 layers) have no split form";
-    else if (!y3::conv_bf16_split_tile(tile)) w = "the conv's tile has no split form (tiles 11 and 12 have)";
-    // the finish launch stores bf16 in whole 16-byte pieces (a conv that writes an fp32 net output itself takes any Cout)
-    else if (c.d.cout % 8 && arena_out) w = "a split conv storing bf16 needs Cout % 8 == 0";
+    else if (!sf.tile(tile)) w = sf.no_form(tile);
+    else if (c.d.cout % sf.cout_mult && arena_out) w = sf.bad_cout;
     if (why) *why = w;
     return !w;
 }
@@ -516,38 +524,31 @@ static bool split_eligible_bf16(const y3_net *net, int slot, const char **why)
 y3_status y3::resolve_splits(y3_net *net)
 {
     if (!net->height) return Y3_OK;
+    const ConvFamily &f = family_of(net);
     size_t lane_bytes = 0;
     for (int oi = 0; oi < (int)net->ops.size(); ++oi) {
         if (net->ops[oi].kind != 0) continue;
         const int slot = net->ops[oi].index;
         ConvSlot &c = net->convs[slot];
         c.split_k = 1;
-        c.split_k_bf16 = 1;
-        // fp32 and bf16 plans split, each by its own request and switch; the rule and its inputs are the same (fp16 and plane-split plans never)
-        const bool bf16 = net->dtype == Y3_DTYPE_BF16;
-        if (!bf16 && net->dtype != Y3_DTYPE_F32) continue;
-        if (!(bf16 ? split_eligible_bf16(net, slot, nullptr) : split_eligible(net, slot, nullptr))) continue;
-        const int req = bf16 ? c.split_req_bf16 : c.split_req;
-        if (req == 1 || (req < 0 && !(bf16 ? net->low_latency_bf16 : net->low_latency))) continue;
+        // a mode with a split form splits by its own request and switch; the rule and its inputs are the same for all
+        if (!f.split || !split_eligible(f, net, slot, nullptr)) continue;
+        const SplitForm &sf = *f.split;
+        const int req = c.*sf.req;
+        if (req == 1 || (req < 0 && !(net->*sf.low_latency))) continue;
         const ConvChoice ch = choose_conv_planned(net, oi);   // the split in force is 1 here: the unsplit launch at the planned rows
         if (ch.kind != ConvKind::Mfma) continue;               // runs as, or inside, the fused stem launch
+        if (!sf.tile(ch.tile)) continue;                       // the tile at the planned rows has no split form (bf16: 8 instead of 11 / 12)
         const long long M = (long long)net->max_batch * (net->height / c.d.out_div) * (net->width / c.d.out_div);
-        const int tile = ch.tile;
-        if (bf16 && !y3::conv_bf16_split_tile(tile)) continue;   // the tile at the planned rows is not 11 or 12 (K tiles of 64 from here on)
-        const y3::TileInfo t = bf16 ? y3::conv_bf16_tile_info(tile) : y3::conv_tile_info(tile);
+        const TileInfo t = f.info(ch.tile);
         const long long tiles = ((M + t.bm - 1) / t.bm) * (c.cout_pad / t.bn);
-        const size_t slab = bf16 ? y3::conv_bf16_split_slab_bytes(tile, M, c.cout_pad) : y3::conv_split_slab_bytes(tile, M, c.cout_pad);
-        const int kt = c.K / t.bk;
-        // bf16 plans leave a conv of fewer than 32 K tiles to its one launch: in profiles/latency_bf16_splitk_sweep.txt every conv of 36 or 72
-        // K tiles gains from the rule's S at every batch from 1 to 8, while the convs of 4 .. 18 K tiles (launches of 7 .. 15 us) lose to
-        // the finish launch and the slab traffic at some batch (the 13^2 1x1 of 16 K tiles: -2 us at one image, +3.5 us at eight; the 52^2
-        // 3x3 of 18 K tiles: +1.5 .. +5 us).  The sweep times one net object at every S; the end-to-end runs of profiles/latency_bf16.txt
-        // cannot resolve this at eight images (two net objects differ by more).  A forced S is taken as given.
-        if (bf16 && req < 0 && kt < kSplitMinKTilesBf16) continue;
+        const size_t slab = split_slab_bytes(t, M, c.cout_pad);
+        const int kt = c.K / sf.bk;
+        if (req < 0 && kt < sf.min_k_tiles) continue;          // the mode's floor (kSplitMinKTilesBf16 says why); a forced S is taken as given
         int S = req > 1 ? req : y3_choose_split_k(tiles, kt, net->n_cus, (long long)slab);
         if (S > kt) S = kt;
         if (S < 2 || slab > 0x7fffffffull) continue;
-        (bf16 ? c.split_k_bf16 : c.split_k) = S;
+        c.split_k = S;
         lane_bytes = std::max(lane_bytes, (size_t)S * slab);
     }
     if (lane_bytes > net->split_ws_lane || (lane_bytes && net->lanes > net->split_ws_lanes)) {
@@ -558,7 +559,7 @@ y3_status y3::resolve_splits(y3_net *net)
         lane_bytes = (lane_bytes + 255) & ~(size_t)255;
         hipError_t e = hipMalloc(&net->split_ws, lane_bytes * net->lanes);
         if (e != hipSuccess) {
-            for (ConvSlot &c : net->convs) c.split_k = c.split_k_bf16 = 1;
+            for (ConvSlot &c : net->convs) c.split_k = 1;
             return fail(Y3_ERR_OOM, "split-K workspace: hipMalloc(%zu) failed: %s", lane_bytes * net->lanes, hipGetErrorString(e));
         }
         net->split_ws_lane = lane_bytes;
@@ -573,6 +574,46 @@ static y3_status resolve_splits_of_setter(y3_net *net)
     if (!net->height) return Y3_OK;
     Y3_ENTER_DEVICE(net);
     return y3::resolve_splits(net);
+}
+
+// The one body of y3_net_set_low_latency / _bf16.  was_set: the flag that records the call (fp32: the Y3_LOW_LATENCY override then stays out)
+static y3_status set_low_latency(const y3::ConvFamily &f, y3_net *net, int on, bool y3_net::*was_set = nullptr)
+{
+    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "%s: argument must be 0 or 1", f.split->set_switch);
+    net->*f.split->low_latency = on != 0;
+    if (was_set) net->*was_set = true;
+    return resolve_splits_of_setter(net);
+}
+
+// The one body of y3_net_set_split_k / _bf16: the request of the mode of `f`; a forced S only where the conv can take it
+static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int S)
+{
+    const y3::SplitForm &sf = *f.split;
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || S < -1 || S == 0 || S > 16)
+        return fail(Y3_ERR_INVALID, "%s: conv slot out of range, or S not -1, 1 or 2..16", sf.set_split);
+    ConvSlot &c = net->convs[slot];
+    if (S > 1) {
+        const char *why = nullptr;
+        if (!split_eligible(f, net, slot, &why)) return fail(Y3_ERR_INVALID, "%s: conv %d: %s", sf.set_split, slot, why);
+        if (net->height && &y3::family_of(net) != &f) return fail(Y3_ERR_INVALID, "%s: conv %d: %s", sf.set_split, slot, sf.other_plan);
+        if (const int oi = y3::conv_op(net, slot); net->height && oi >= 0) {
+            const y3::ConvChoice ch = y3::choose_conv_planned(net, oi);   // .tile: the conv's tile at the planned rows, split or not
+            if (ch.kind == y3::ConvKind::Stem || ch.kind == y3::ConvKind::InStem)
+                return fail(Y3_ERR_INVALID, "%s: conv %d runs inside the fused stem kernel, which is never split", sf.set_split, slot);
+            if (!sf.tile(ch.tile))
+                return fail(Y3_ERR_INVALID, "%s: conv %d: its tile at the planned rows (%d) has no split form (%s)", sf.set_split, slot, ch.tile, sf.tiles);
+        }
+        if (S > c.K / sf.bk) return fail(Y3_ERR_INVALID, "%s: conv %d has %d K tiles, fewer than S = %d", sf.set_split, slot, c.K / sf.bk, S);
+    }
+    c.*sf.req = S;
+    return resolve_splits_of_setter(net);
+}
+
+// y3_net_get_split_k / _bf16: the split in force when the net is planned in the mode of `f`, 1 otherwise
+static int split_in_force(const y3::ConvFamily &f, const y3_net *net, int slot)
+{
+    if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height || &y3::family_of(net) != &f) return 1;
+    return net->convs[slot].split_k;
 }
 
 extern "C" {
@@ -736,15 +777,11 @@ try {
 Y3_CATCH("y3_net_set_tile_bf16")
 
 y3_status y3_net_set_tile_x3(y3_net *net, int slot, int tile)
-try {
-    return set_forced_tile(X3_FAMILY, net, slot, tile);
-}
+try { return set_forced_tile(X3_FAMILY, net, slot, tile); }
 Y3_CATCH("y3_net_set_tile_x3")
 
 y3_status y3_net_set_tile_x2(y3_net *net, int slot, int tile)
-try {
-    return set_forced_tile(X2_FAMILY, net, slot, tile);
-}
+try { return set_forced_tile(X2_FAMILY, net, slot, tile); }
 Y3_CATCH("y3_net_set_tile_x2")
 
 y3_status y3_net_set_lanes(y3_net *net, int lanes)
@@ -778,63 +815,19 @@ try {
 Y3_CATCH("y3_net_set_k_chunk")
 
 y3_status y3_net_set_low_latency(y3_net *net, int on)
-try {
-    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "y3_net_set_low_latency: argument must be 0 or 1");
-    net->low_latency = on != 0;
-    net->low_latency_set = true;
-    return resolve_splits_of_setter(net);
-}
+try { return set_low_latency(F32_FAMILY, net, on, &y3_net::low_latency_set); }
 Y3_CATCH("y3_net_set_low_latency")
 
 y3_status y3_net_set_split_k(y3_net *net, int slot, int S)
-try {
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || S < -1 || S == 0 || S > 16)
-        return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv slot out of range, or S not -1, 1 or 2..16");
-    ConvSlot &c = net->convs[slot];
-    if (S > 1) {
-        const char *why = nullptr;
-        if (!split_eligible(net, slot, &why)) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d: %s", slot, why);
-        if (net->height && net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d: only Y3_DTYPE_F32 plans split K", slot);
-        if (const int oi = y3::conv_op(net, slot); net->height && oi >= 0)
-            if (const y3::ConvKind k = y3::choose_conv_planned(net, oi).kind; k == y3::ConvKind::Stem || k == y3::ConvKind::InStem)
-                return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d runs inside the fused stem kernel, which is never split", slot);
-        if (S > c.K / 32) return fail(Y3_ERR_INVALID, "y3_net_set_split_k: conv %d has %d K tiles, fewer than S = %d", slot, c.K / 32, S);
-    }
-    c.split_req = S;
-    return resolve_splits_of_setter(net);
-}
+try { return set_split_k(F32_FAMILY, net, slot, S); }
 Y3_CATCH("y3_net_set_split_k")
 
 y3_status y3_net_set_low_latency_bf16(y3_net *net, int on)
-try {
-    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "y3_net_set_low_latency_bf16: argument must be 0 or 1");
-    net->low_latency_bf16 = on != 0;
-    return resolve_splits_of_setter(net);
-}
+try { return set_low_latency(BF16_FAMILY, net, on); }
 Y3_CATCH("y3_net_set_low_latency_bf16")
 
 y3_status y3_net_set_split_k_bf16(y3_net *net, int slot, int S)
-try {
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || S < -1 || S == 0 || S > 16)
-        return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv slot out of range, or S not -1, 1 or 2..16");
-    ConvSlot &c = net->convs[slot];
-    if (S > 1) {
-        const char *why = nullptr;
-        if (!split_eligible_bf16(net, slot, &why)) return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d: %s", slot, why);
-        if (net->height && net->dtype != Y3_DTYPE_BF16)
-            return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d: only Y3_DTYPE_BF16 plans take a bf16 split", slot);
-        if (const int oi = y3::conv_op(net, slot); net->height && oi >= 0) {
-            const y3::ConvChoice ch = y3::choose_conv_planned(net, oi);   // .tile: the conv's tile at the planned rows, split or not
-            if (ch.kind == y3::ConvKind::Stem || ch.kind == y3::ConvKind::InStem)
-                return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d runs inside the fused stem kernel, which is never split", slot);
-            if (!y3::conv_bf16_split_tile(ch.tile))
-                return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d: its tile at the planned rows (%d) has no split form (tiles 11 and 12 have)", slot, ch.tile);
-        }
-        if (S > c.K / 64) return fail(Y3_ERR_INVALID, "y3_net_set_split_k_bf16: conv %d has %d K tiles, fewer than S = %d", slot, c.K / 64, S);
-    }
-    c.split_req_bf16 = S;
-    return resolve_splits_of_setter(net);
-}
+try { return set_split_k(BF16_FAMILY, net, slot, S); }
 Y3_CATCH("y3_net_set_split_k_bf16")
 
 y3_status y3_net_set_xcd_mode(y3_net *net, int mode)
@@ -863,17 +856,9 @@ try {
 }
 Y3_CATCH("y3_net_keep_activations")
 
-int y3_net_get_split_k(const y3_net *net, int slot)
-{
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height) return 1;
-    return net->convs[slot].split_k;
-}
+int y3_net_get_split_k(const y3_net *net, int slot) { return split_in_force(F32_FAMILY, net, slot); }
 
-int y3_net_get_split_k_bf16(const y3_net *net, int slot)
-{
-    if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height) return 1;
-    return net->convs[slot].split_k_bf16;
-}
+int y3_net_get_split_k_bf16(const y3_net *net, int slot) { return split_in_force(BF16_FAMILY, net, slot); }
 
 int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice)
 {

@@ -97,8 +97,7 @@ extern "C" {
 y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int dtype)
 try {
     if (!net || max_batch <= 0 || height <= 0 || width <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
-    if (dtype != Y3_DTYPE_F32 && dtype != Y3_DTYPE_BF16 && dtype != Y3_DTYPE_F32X3 && dtype != Y3_DTYPE_F32X2 && dtype != Y3_DTYPE_F16)
-        return fail(Y3_ERR_INVALID, "y3_net_plan: unknown dtype %d", dtype);
+    if (!y3::conv_family(dtype)) return fail(Y3_ERR_INVALID, "y3_net_plan: unknown dtype %d", dtype);
     for (const y3_tensor_desc &t : net->tensors)
         if (t.div <= 0 || height % t.div || width % t.div) {
             if (height == width) return fail(Y3_ERR_INVALID, "y3_net_plan: image_size %d not divisible by %d", height, t.div);   // the square call's text, as ever

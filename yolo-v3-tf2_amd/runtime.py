@@ -217,48 +217,53 @@ class Net:
             raise Y3Error(f"split_k must be -1 (heuristic), 1 (off) or an int in 2..16 (got {S!r})")
         return int(S)
 
+    def _slot_arg(self, who: str, slot) -> int:
+        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
+            raise Y3Error(f"{who}: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
+        return int(slot)
+
+    def _set_low_latency(self, sfx: str, on):   # sfx, here and below: "" the fp32 plans' entry points, "_bf16" the bf16 plans'
+        on = int(self._low_latency_arg(on))     # the argument checks come first: they need no device net
+        check(getattr(self.lib, "y3_net_set_low_latency" + sfx)(self._h, on), "y3_net_set_low_latency" + sfx)
+
+    def _set_split_k(self, sfx: str, slot, S):
+        S, slot = self._split_k_arg(S), self._slot_arg("set_split_k" + sfx, slot)
+        check(getattr(self.lib, "y3_net_set_split_k" + sfx)(self._h, slot, S), "y3_net_set_split_k" + sfx)
+
+    def _split_k(self, sfx: str, slot) -> int:
+        slot = self._slot_arg("split_k" + sfx, slot)
+        return int(getattr(self.lib, "y3_net_get_split_k" + sfx)(self._h, slot))
+
     def set_low_latency(self, on=True):
         """Low-latency fp32 plan for one to eight images (y3_net_set_low_latency), before plan(): each eligible conv is cut
         along K into the number of slices y3_choose_split_k gives for the planned batch, summed in a fixed order by a second
         launch.  Off by default; results differ from the default plan's in the last bits.  None means off."""
-        on = int(self._low_latency_arg(on))
-        check(self.lib.y3_net_set_low_latency(self._h, on), "y3_net_set_low_latency")
+        self._set_low_latency("", on)
 
     def set_split_k(self, slot: int, S: int):
         """K slices of conv `slot`: -1 the heuristic (in force only with set_low_latency), 1 off, 2..16 forced.  An
         ineligible conv (first layer, fused stem, tile 33, a detection head, a plan that is not fp32) or S above the conv's K
         tiles raises here."""
-        S = self._split_k_arg(S)
-        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
-            raise Y3Error(f"set_split_k: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
-        check(self.lib.y3_net_set_split_k(self._h, int(slot), S), "y3_net_set_split_k")
+        self._set_split_k("", slot, S)
 
     def split_k(self, slot: int) -> int:
         """K slices in force for conv `slot` after plan() (1: the ordinary launch)."""
-        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
-            raise Y3Error(f"split_k: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
-        return int(self.lib.y3_net_get_split_k(self._h, int(slot)))
+        return self._split_k("", slot)
 
     def set_low_latency_bf16(self, on=True):
         """Low-latency bf16 plan for one to eight images (y3_net_set_low_latency_bf16): as set_low_latency, for a plan made with
         Y3_DTYPE_BF16.  The two switches are independent; each acts on plans of its own dtype only.  None means off."""
-        on = int(self._low_latency_arg(on))
-        check(self.lib.y3_net_set_low_latency_bf16(self._h, on), "y3_net_set_low_latency_bf16")
+        self._set_low_latency("_bf16", on)
 
     def set_split_k_bf16(self, slot: int, S: int):
         """K slices of conv `slot` in a bf16 plan: -1 the heuristic (in force only with set_low_latency_bf16), 1 off, 2..16 forced.
         An ineligible conv (first layer, fused stem, tile 32, a BK = 32 tile, a tile other than 11 / 12, a detection head, a plan that
         is not bf16) or S above the conv's K tiles (K / 64) raises here."""
-        S = self._split_k_arg(S)
-        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
-            raise Y3Error(f"set_split_k_bf16: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
-        check(self.lib.y3_net_set_split_k_bf16(self._h, int(slot), S), "y3_net_set_split_k_bf16")
+        self._set_split_k("_bf16", slot, S)
 
     def split_k_bf16(self, slot: int) -> int:
         """K slices in force for conv `slot` in a bf16 plan after plan() (1: the ordinary launch; 1 on every other plan)."""
-        if isinstance(slot, (bool, np.bool_)) or not isinstance(slot, (int, np.integer)) or not 0 <= int(slot) < len(self.conv_ops):
-            raise Y3Error(f"split_k_bf16: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
-        return int(self.lib.y3_net_get_split_k_bf16(self._h, int(slot)))
+        return self._split_k("_bf16", slot)
 
     def set_stem_fusion(self, on):
         """conv0 + conv1 (+ the 1x1 conv that follows them) as one kernel (default on; applies when the program starts with

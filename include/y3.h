@@ -149,8 +149,8 @@ y3_status y3_net_set_k_chunk(y3_net *net, int channels);
  * units -- never from the rows of a call, so inside one plan an image's result does not depend on its batch or position.  S = 1 (the
  * ordinary launch) wherever the planned batch already fills the chip.  Never split: the first layer, the fused stem, the weight-
  * resident tile 33, the three detection-head convs (y3_net_detect and the composed route stay bit-identical), and -- by these three calls --
- * any plan that is not Y3_DTYPE_F32 (a Y3_DTYPE_BF16 plan splits through the _bf16 calls below; the plane-split modes and Y3_DTYPE_F16
- * never split).
+ * any plan that is not Y3_DTYPE_F32 (a Y3_DTYPE_BF16 plan splits through the _bf16 calls below, a Y3_DTYPE_F16 plan through the _f16
+ * calls; the plane-split modes never split).
  * The same products in another summation order: results differ from the default plan's in the last bits (as
  * y3_net_set_k_chunk says of itself).  With it off nothing changes.
  * y3_net_set_split_k: S of one conv: -1 = y3_choose_split_k when low latency is on (else 1), 1 = off, 2..16 = that value whether or not
@@ -174,15 +174,25 @@ int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_by
  * y3_net_set_low_latency_bf16: 0 / 1, off by default.  y3_net_set_split_k_bf16: -1 = the rule when the bf16 switch is on (else 1), 1 = off,
  * 2..16 forced; an ineligible conv, S > K / 64, or a forced value on a planned net whose dtype is not Y3_DTYPE_BF16 is refused with
  * Y3_ERR_INVALID and a message.  y3_net_get_split_k_bf16: the value in force after planning; 1 before, 1 on a plan that is not bf16.
- * Y3_DTYPE_F16 plans never split: the switch does not act on them, and a forced value on a planned fp16 net is refused like on any
- * other plan that is not bf16. */
+ * These three do not act on Y3_DTYPE_F16 plans: the switch splits nothing there, and a forced value on a planned fp16 net is refused like
+ * on any other plan that is not bf16 ("only Y3_DTYPE_BF16 plans take a bf16 split"). */
 y3_status y3_net_set_low_latency_bf16(y3_net *net, int on);
 y3_status y3_net_set_split_k_bf16(y3_net *net, int conv_slot, int S);
 int y3_net_get_split_k_bf16(const y3_net *net, int conv_slot);
+/* Low-latency fp16 plans: the same once more for Y3_DTYPE_F16 plans, again with a switch, a request and a decision of their own (off and
+ * -1 by default: an fp16 plan on which these are never called launches what it always did).  Every rule of the _bf16 three holds with
+ * "fp16" for "bf16": the same kernels on the f16 MFMA, tiles 11 and 12, K tiles of 64, the floor of 32 K tiles, the finish launch adding
+ * the fp32 slabs in the order 0, 1, ..., S-1 and applying the unsplit fp16 epilogue (one rounding to nearest even, IEEE overflow), so equal
+ * sums give the unsplit launch's bits; the same convs are never split (the fused stem's are those of y3_net_set_stem_fusion_f16).  A forced
+ * value on a planned net that is not Y3_DTYPE_F16 is refused ("only Y3_DTYPE_F16 plans take an fp16 split").  y3_net_get_split_k_f16: the
+ * value in force after planning; 1 before, 1 on a plan that is not fp16 (the fp32 and bf16 getters answer 1 on an fp16 plan). */
+y3_status y3_net_set_low_latency_f16(y3_net *net, int on);
+y3_status y3_net_set_split_k_f16(y3_net *net, int conv_slot, int S);
+int y3_net_get_split_k_f16(const y3_net *net, int conv_slot);
 y3_status y3_net_keep_activations(y3_net *net, int keep);
 /* 1 (default): when the program starts with conv0 (3x3/1, 3 -> 32) feeding only conv1 (3x3/2, 32 -> 64) -- the Darknet-53
  * stem, reference config/models/yolov3/backbone.yaml layers 1-2 -- and the plan is fp32 or bf16 without keep_activations,
- * (Y3_DTYPE_F16 plans never fuse the stem: one launch per conv, whatever this is set to),
+ * (this call does not act on Y3_DTYPE_F16 plans: one launch per conv whatever it is set to, unless y3_net_set_stem_fusion_f16 below),
  * the two run as ONE kernel that keeps conv0's output (the largest tensor of the network, 1.4 GB at 64 x 416^2) in LDS; the
  * 1x1 conv that follows (64 -> 32, backbone.yaml layer 3) is computed by the same kernel from conv1's tile.
  * 2: conv0 + conv1 in one kernel, the 1x1 conv as its own launch (bf16 plans: bit-identical to 1).
@@ -192,9 +202,21 @@ y3_status y3_net_keep_activations(y3_net *net, int keep);
  * bf16 where the pipeline stores it; against the one-launch-per-conv form a fraction of a percent of conv0's bf16 values round
  * the other way (bounded by tests/test_gpu_parity.py::test_fused_stem_bf16_matches_oracle_and_the_two_launch_form). */
 y3_status y3_net_set_stem_fusion(y3_net *net, int on);
+/* The same switch for Y3_DTYPE_F16 plans, and for them only: 0 (default: one launch per conv, as an fp16 plan always ran), 1, 2 with the
+ * meanings above; it does not act on a plan of any other mode, as y3_net_set_stem_fusion does not act on an fp16 plan.  The graph decides
+ * as for bf16.  The kernel is the bf16 one on v_mfma_f32_32x32x16_f16, every rounding the fp16 round-to-nearest-even of the fp16 convs
+ * (2: bit-identical to 1).  conv0's products come from operands split v = hi + lo' * 2^-11 with hi = |v| < 2^-14 ? 0 : fp16(v) and
+ * lo' = fp16((v - hi) * 2048): per K step of 16 the cross terms lo'_x hi_w + hi_x lo'_w are summed on their own, that sum times 2^-11 is the
+ * C input of the hi_x hi_w terms (~2^-22 relative error per product; lo' lo' dropped).  conv0's weights are divided per output channel by
+ * the power of two that brings the channel's largest magnitude into [1, 2), and the channel's scale multiplied by it, both exactly, so
+ * the accuracy does not depend on the weights' magnitude and no operand that matters is subnormal (nothing relies on what the matrix
+ * pipe does with one).  Against the one-launch-per-conv fp16 plan a fraction of a percent of conv0's fp16 values round the other way
+ * (bounded by tests/test_f16_stem_gpu.py).  Precondition: pixel values finite and of magnitude at most 65504 -- a larger one makes hi
+ * infinite and the result NaN, where the unfused fp16 plan only overflows at its outputs. */
+y3_status y3_net_set_stem_fusion_f16(y3_net *net, int on);
 /* Measurement aid (bench.py): the shader clock the chip holds under this network's load.  Runs `forwards` forwards back to
  * back (grids_dev as for y3_net_forward); in the last one, thread 0 of the middle workgroup of the conv with the most FLOPs (fp32
- * plans: an MFMA conv launch; bf16 plans: the fused stem kernel) reads s_memtime and s_memrealtime at its entry and after
+ * plans: an MFMA conv launch; bf16 plans, and fp16 plans with y3_net_set_stem_fusion_f16: the fused stem kernel) reads s_memtime and s_memrealtime at its entry and after
  * its epilogue: MHz = d(memtime) / d(memrealtime) x 100 (MI355X_MICROARCH.md, DVFS give-back item 6).  Synchronises the
  * stream.  No product launch carries stamps (the kernels test a null pointer).  The three measure_sclk calls temporarily
  * change the net's lane count and stamp fields: never run them concurrently with a forward on the same net. */
@@ -235,7 +257,8 @@ y3_status y3_net_set_early_chunk(y3_net *net, int n_convs, int chunk_images);
  * fp16, the image batch and the head grids stay fp32.  The weights are rounded to fp16 on the host (a further copy of them, 124 MB for
  * YOLOv3, beside the other formats).  Overflow is IEEE's: a value beyond 65504 is stored as inf (as torch.float16 does), a weight
  * beyond it becomes inf; nothing saturates and nothing is checked.  Subnormals are kept.  Same tile ids, heuristic and tuning tables as
- * Y3_DTYPE_BF16 (y3_net_set_tile_bf16); never the fused stem, never split-K.  Head logits measured 8 x closer to fp32 than bf16's
+ * Y3_DTYPE_BF16 (y3_net_set_tile_bf16); no fused stem unless switched on by y3_net_set_stem_fusion_f16, no split-K unless switched on by
+ * y3_net_set_low_latency_f16 / y3_net_set_split_k_f16 (the fp32 / bf16 switches do not act on an fp16 plan).  Head logits measured 8 x closer to fp32 than bf16's
  * (DESIGN.md section 7).
  * In the non-fp32 modes an output tensor that another op of the net reads again, or that a residual conv writes,
  * is kept in the arena in the mode's format and converted into the caller's fp32 buffer at the end of the forward. */

@@ -25,7 +25,7 @@ if data == "zeros":   # every operand of every MFMA is zero: no toggling in the 
     for k in w:
         if not k.endswith(".var"): w[k] = w[k] * 0
 net = runtime.Net(p); net.load_weights(w)
-net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f32x2": _lib.Y3_DTYPE_F32X2, "f32x3": _lib.Y3_DTYPE_F32X3}[dt])
+net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f32x2": _lib.Y3_DTYPE_F32X2, "f32x3": _lib.Y3_DTYPE_F32X3, "f16": _lib.Y3_DTYPE_F16}[dt])
 x = torch.rand((B, S, S, 3), device="cuda") if data != "zeros" else torch.zeros((B, S, S, 3), device="cuda")
 g = [torch.empty((B, s, s, 3, 85), device="cuda") for s in net.grid_sizes()]
 import numpy as np

@@ -2,7 +2,7 @@
 """SHA-256 of what the conv program produces (three head grids, the fused decode outputs, the packed detections and num_valid of
 net.detect) for a seeded batch: two builds of the library (Y3_LIB_PATH) that print the same digests are bit-identical on that plan.
    python tools/hash_outputs.py --dtype bf16 --batch 128          (--dtype f32 | bf16 | f16 | f32x3 | f32x2; --lanes N overrides the table's;
-                                                                   --low-latency: the low-latency plan of an f32 or bf16 net)"""
+                                                                   --low-latency: the low-latency plan of an f32, bf16 or f16 net)"""
 import argparse
 import hashlib
 import os
@@ -26,16 +26,16 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--image-size", type=int, default=416)
     ap.add_argument("--lanes", type=int, default=0, help="concurrent sub-batches (0: what plan() takes from the tuning table)")
-    ap.add_argument("--low-latency", action="store_true", help="the split-K plan of --dtype f32 / bf16 (set_low_latency / set_low_latency_bf16)")
+    ap.add_argument("--low-latency", action="store_true", help="the split-K plan of --dtype f32 / bf16 / f16 (set_low_latency / set_low_latency_bf16 / set_low_latency_f16)")
     a = ap.parse_args()
     dtype = runtime.Net._dtype_arg(a.dtype)
-    if a.low_latency and dtype not in (_lib.Y3_DTYPE_F32, _lib.Y3_DTYPE_BF16):
-        ap.error("--low-latency: only f32 and bf16 plans split K")
+    if a.low_latency and dtype not in (_lib.Y3_DTYPE_F32, _lib.Y3_DTYPE_BF16, _lib.Y3_DTYPE_F16):
+        ap.error("--low-latency: only f32, bf16 and f16 plans split K")
     p = load_program(os.path.join(ROOT, "config/models/yolov3/model.yaml"), 80)
     net = runtime.Net(p)
     net.load_weights(synthetic_weights(p, seed=4321))
     if a.low_latency:   # before plan(): the switch of the chosen dtype
-        (net.set_low_latency_bf16 if dtype == _lib.Y3_DTYPE_BF16 else net.set_low_latency)(True)
+        {_lib.Y3_DTYPE_BF16: net.set_low_latency_bf16, _lib.Y3_DTYPE_F16: net.set_low_latency_f16}.get(dtype, net.set_low_latency)(True)
     net.plan(a.batch, a.image_size, dtype)
     if a.lanes:   # after plan(): it sets the lane count from the tuning table
         net.set_lanes(a.lanes)

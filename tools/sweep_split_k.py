@@ -4,7 +4,8 @@ are set from.  For every eligible conv and every S of --splits (clamped to the c
 launch -- is timed alone with y3_net_profile_convs, median of --repeats; the table gives per conv the time at every S, the best S,
 the S the rule picks and what the rule leaves on the table, then the sums over the conv stack: unsplit, rule, best per conv.
     python tools/sweep_split_k.py [--size 416] [--batches 1 2 4 8] [--dtype f32] [--out profiles/latency_splitk_sweep.txt]
---dtype bf16 sweeps a bf16 plan through y3_net_set_split_k_bf16 (K tiles of 64; profiles/latency_bf16_splitk_sweep.txt)."""
+--dtype bf16 sweeps a bf16 plan through y3_net_set_split_k_bf16 (K tiles of 64; profiles/latency_bf16_splitk_sweep.txt).
+--dtype f16 sweeps an fp16 plan through y3_net_set_split_k_f16 (K tiles of 64; profiles/latency_f16_splitk_sweep.txt)."""
 import argparse
 import os
 import sys
@@ -21,10 +22,10 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8])
     ap.add_argument("--splits", type=int, nargs="+", default=[1, 2, 3, 4, 6, 8, 12, 16])
     ap.add_argument("--repeats", type=int, default=15)
-    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16"])
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    bf16 = a.dtype == "bf16"
+    sfx = {"f32": "", "bf16": "_bf16", "f16": "_f16"}[a.dtype]
 
     import torch
     import yolo_v3_tf2_amd  # noqa: F401
@@ -42,10 +43,9 @@ def main():
     net = runtime.Net(program)
     net.load_weights(synthetic_weights(program))
     n = len(net.conv_ops)
-    set_split, get_split, set_ll = ((net.set_split_k_bf16, net.split_k_bf16, net.set_low_latency_bf16) if bf16 else
-                                    (net.set_split_k, net.split_k, net.set_low_latency))
-    dtype, bk = (_lib.Y3_DTYPE_BF16, 64) if bf16 else (_lib.Y3_DTYPE_F32, 32)
-    say(f"# tools/sweep_split_k.py  device: {torch.cuda.get_device_name(0)}  {'bf16' if bf16 else 'fp32'}; ms per conv launch alone (split: slices + finish), median of {a.repeats}")
+    set_split, get_split, set_ll = getattr(net, "set_split_k" + sfx), getattr(net, "split_k" + sfx), getattr(net, "set_low_latency" + sfx)
+    dtype, bk = {"f32": (_lib.Y3_DTYPE_F32, 32), "bf16": (_lib.Y3_DTYPE_BF16, 64), "f16": (_lib.Y3_DTYPE_F16, 64)}[a.dtype]
+    say(f"# tools/sweep_split_k.py  device: {torch.cuda.get_device_name(0)}  { {'f32': 'fp32', 'f16': 'fp16'}.get(a.dtype, a.dtype)}; ms per conv launch alone (split: slices + finish), median of {a.repeats}")
     for S_img in a.size:
         for B in a.batches:
             x = torch.rand((B, S_img, S_img, 3), device="cuda")

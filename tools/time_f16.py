@@ -2,11 +2,12 @@
 """fp16 plans (Y3_DTYPE_F16) beside bf16 plans: throughput of the benchmark's step, and precision on the device.
 
 Throughput: the step bench.py times with --dtype bf16 --batch 128 --graph (forward_decode -> nms_padded -> pack_detections on a device-
-resident batch, captured once, replayed) for THREE plans held in one process -- bf16 as shipped (fused stem), bf16 with the stem
-unfused (set_stem_fusion(0)) and fp16 (which never fuses the stem) -- in alternated windows; median of the window medians and the spread
-between a plan's own windows.  fp16 against bf16-unfused compares the kernels (both run the same launches, same tiles, same lanes); the
-distance from there to bf16 as shipped is what a fused fp16 stem would return.  --per-conv adds y3_net_profile_convs of the two plans
-that run the same launches (each launch timed alone, median of 9).
+resident batch, captured once, replayed) for FOUR plans held in one process -- bf16 as shipped (fused stem), bf16 with the stem
+unfused (set_stem_fusion(0)), fp16 as shipped (no fused stem) and fp16 with the fused stem (set_stem_fusion_f16) -- in alternated
+windows; median of the window medians and the spread between a plan's own windows.  fp16 against bf16-unfused compares the kernels
+(both run the same launches, same tiles, same lanes); fp16 with the fused stem against fp16 is what the switch returns, beside what the
+fused stem is worth to bf16.  --per-conv adds y3_net_profile_convs of the four plans (each launch timed alone, median of 9; the convs
+inside a fused stem show 0 and their time is conv 1's).
 
 Precision (--precision): girl.png at 416^2 through forward_decode on a bf16 and on an fp16 plan against the fp32 oracle's decode:
 largest deviation of a box coordinate and of a score, over all candidates and over those the oracle scores above 0.1.
@@ -60,16 +61,19 @@ def main():
     anchors = get_anchors(os.path.join(ROOT, "datasets/coco2012/anchors.txt")).astype(np.float32)
     say(f"# tools/time_f16.py  device: {torch.cuda.get_device_name(0)}")
 
-    def make(dtype, stem):
+    def make(dtype, stem, stem_f16=None):
         net = runtime.Net(program)
         net.load_weights(weights)
         if stem is not None:
             net.set_stem_fusion(stem)
+        if stem_f16 is not None:
+            net.set_stem_fusion_f16(stem_f16)
         return net, dtype
 
     if not a.no_throughput:
         B, S = a.batch, a.size
-        plans = {"bf16": make(_lib.Y3_DTYPE_BF16, None), "bf16-unfused-stem": make(_lib.Y3_DTYPE_BF16, 0), "f16": make(_lib.Y3_DTYPE_F16, None)}
+        plans = {"bf16": make(_lib.Y3_DTYPE_BF16, None), "bf16-unfused-stem": make(_lib.Y3_DTYPE_BF16, 0), "f16": make(_lib.Y3_DTYPE_F16, None),
+                 "f16-fused-stem": make(_lib.Y3_DTYPE_F16, None, 1)}
         x = torch.rand((B, S, S, 3), device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))
         if a.zeros:
             x.zero_()
@@ -115,14 +119,22 @@ def main():
         say(f"f16 / bf16-unfused-stem {med['f16'] / med['bf16-unfused-stem']:.4f} (the kernels: same launches); "
             f"f16 / bf16 as shipped {med['f16'] / med['bf16']:.4f}; bf16-unfused-stem / bf16 {med['bf16-unfused-stem'] / med['bf16']:.4f} "
             f"(what the fused stem is worth)")
+        d16, dbf = med["f16"] - med["f16-fused-stem"], med["bf16-unfused-stem"] - med["bf16"]
+        every = all(f < u for f, u in zip(win["f16-fused-stem"], win["f16"]))
+        say(f"f16-fused-stem / f16 {med['f16-fused-stem'] / med['f16']:.4f}: {d16:.3f} ms returned of the {dbf:.3f} ms the fused stem returns to bf16 "
+            f"({100 * d16 / dbf if dbf > 0 else float('nan'):.0f} %); below f16 in every window: {every}; f16's own window spread "
+            f"{max(win['f16']) - min(win['f16']):.3f} ms")
         if a.per_conv:
             del graphs
-            ms = {k: np.median([plans[k][0].profile_convs(x) for _ in range(9)], axis=0) for k in ("bf16-unfused-stem", "f16")}
-            say("-- per conv (each launch alone, median of 9): slot signature bf16-unfused ms, f16 ms, f16 / bf16")
+            ms = {k: np.median([plans[k][0].profile_convs(x) for _ in range(9)], axis=0) for k in plans}
+            say("-- per conv (each launch alone, median of 9): slot signature bf16-unfused ms, f16 ms, f16 / bf16-unfused | bf16 ms, f16-fused-stem ms")
             for i, o in enumerate(plans["f16"][0].conv_ops):
                 b, f = ms["bf16-unfused-stem"][i], ms["f16"][i]
-                say(f"{i:4d}  {runtime.Net.conv_signature(o, S):36s} {b:8.4f} {f:8.4f}   {f / b if b > 0 else float('nan'):6.3f}")
-            say(f"sum   {'':36s} {ms['bf16-unfused-stem'].sum():8.4f} {ms['f16'].sum():8.4f}   {ms['f16'].sum() / ms['bf16-unfused-stem'].sum():6.3f}")
+                say(f"{i:4d}  {runtime.Net.conv_signature(o, S):36s} {b:8.4f} {f:8.4f}   {f / b if b > 0 else float('nan'):6.3f} | "
+                    f"{ms['bf16'][i]:8.4f} {ms['f16-fused-stem'][i]:8.4f}")
+            say(f"sum   {'':36s} {ms['bf16-unfused-stem'].sum():8.4f} {ms['f16'].sum():8.4f}   {ms['f16'].sum() / ms['bf16-unfused-stem'].sum():6.3f} | "
+                f"{ms['bf16'].sum():8.4f} {ms['f16-fused-stem'].sum():8.4f}")
+            say("stem (convs 0..2): " + ", ".join(f"{k} {ms[k][:3].sum():.4f} ms" for k in plans))
         del plans
 
     if a.precision:

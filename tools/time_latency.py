@@ -11,7 +11,8 @@ low-latency plan was below the default plan in every alternated pair of windows,
 between its windows.  The split in force per conv is printed for every plan.
     python tools/time_latency.py [--sizes 416 608] [--batches 1 2 4 8] [--calls 1000] [--windows 4] [--per-conv] [--dtype f32] [--out profiles/latency.txt]
 --dtype bf16 times bf16 plans, the low-latency one through y3_net_set_low_latency_bf16 (profiles/latency_bf16.txt).
---dtype f16 times fp16 plans: they never split, so both nets hold the default plan (as with --control) and "off" is the fp16 latency.
+--dtype f16 times fp16 plans, the low-latency one through y3_net_set_low_latency_f16 (profiles/latency_f16.txt).
+--f16-fused-stem (with --dtype f16) switches the fused stem on in the "on" plan as well (y3_net_set_stem_fusion_f16).
 --control makes "on" a SECOND DEFAULT-PLAN net: the same launches from two net objects, i.e. what the protocol reads when nothing differs.
 --per-conv adds, for batch 1, the per-conv table of y3_net_profile_convs (each launch timed alone; a split conv is its two launches)."""
 import argparse
@@ -35,11 +36,10 @@ def main():
     ap.add_argument("--per-conv", action="store_true")
     ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"])
     ap.add_argument("--control", action="store_true", help="'on' is a second default-plan net (two net objects, the same launches)")
+    ap.add_argument("--f16-fused-stem", action="store_true", help="fp16: the 'on' plan also fuses the stem")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    bf16 = a.dtype == "bf16"
-    if a.dtype == "f16":
-        a.control = True        # no low-latency fp16 plan exists
+    sfx = {"f32": "", "bf16": "_bf16", "f16": "_f16"}[a.dtype]
 
     import torch
     import yolo_v3_tf2_amd  # noqa: F401
@@ -61,11 +61,13 @@ def main():
     for name in ("off", "on"):
         net = runtime.Net(program)
         net.load_weights(weights)
-        if a.dtype != "f16":
-            (net.set_low_latency_bf16 if bf16 else net.set_low_latency)(name == "on" and not a.control)
+        getattr(net, "set_low_latency" + sfx)(name == "on" and not a.control)
+        if a.f16_fused_stem and a.dtype == "f16" and name == "on" and not a.control:
+            net.set_stem_fusion_f16(True)
         nets[name] = net
     say(f"# tools/time_latency.py  device: {torch.cuda.get_device_name(0)}  { {'f32': 'fp32', 'f16': 'fp16'}.get(a.dtype, a.dtype)}  calls per plan and form: {a.calls} in {a.windows} alternated windows")
-    say("# off = default plan, on = " + ("a second net with the default plan (control)" if a.control else "low-latency plan (split-K)") +
+    say("# off = default plan, on = " + ("a second net with the default plan (control)" if a.control else "low-latency plan (split-K)" +
+                                (" with the fused stem" if a.f16_fused_stem and a.dtype == "f16" else "")) +
         "; times in ms; 'pairs' = windows in which on < off")
     per_window = max(1, a.calls // a.windows)
     for S in a.sizes:
@@ -73,7 +75,7 @@ def main():
             x = torch.rand((B, S, S, 3), device="cuda")
             for net in nets.values():
                 net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f16": _lib.Y3_DTYPE_F16}[a.dtype])
-            splits = [(nets["on"].split_k_bf16 if bf16 else nets["on"].split_k)(i) for i in range(len(nets["on"].conv_ops))]
+            splits = [getattr(nets["on"], "split_k" + sfx)(i) for i in range(len(nets["on"].conv_ops))]
             say(f"\n== {S} x {S}, batch {B}: {sum(s > 1 for s in splits)} convs split; S per conv: {splits}")
             step = {k: (lambda n=n: n.detect(x, anchors, 100, 0.5, 0.1)) for k, n in nets.items()}
             for k in step:

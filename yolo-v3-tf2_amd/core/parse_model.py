@@ -41,6 +41,8 @@ class YoloModel:
         self._net = None
         self._weights = None
         self.low_latency = False
+        self.low_latency_f16 = False
+        self.stem_fusion_f16 = 0
         self.dtype = None     # None: fp32 (set_dtype)
 
     # lazily create the device object so that building/inspecting a model works without a GPU
@@ -50,6 +52,10 @@ class YoloModel:
             self._net = Net(self.program)
             if self.low_latency:
                 self._net.set_low_latency(True)
+            if self.low_latency_f16:
+                self._net.set_low_latency_f16(True)
+            if self.stem_fusion_f16:
+                self._net.set_stem_fusion_f16(self.stem_fusion_f16)
             if self.dtype is not None:
                 self._net.set_dtype(self.dtype)
             if self._weights is not None:
@@ -63,6 +69,20 @@ class YoloModel:
         self.low_latency = Net._low_latency_arg(on)
         if self._net is not None:
             self._net.set_low_latency(self.low_latency)
+
+    def set_low_latency_f16(self, on=True):
+        """Low-latency fp16 plans (runtime.Net.set_low_latency_f16): the same for plans made with dtype "f16"."""
+        from ..runtime import Net
+        self.low_latency_f16 = Net._low_latency_arg(on)
+        if self._net is not None:
+            self._net.set_low_latency_f16(self.low_latency_f16)
+
+    def set_stem_fusion_f16(self, on=True):
+        """The fused stem kernel for fp16 plans (runtime.Net.set_stem_fusion_f16): off by default; acts on dtype "f16" only."""
+        from ..runtime import Net
+        self.stem_fusion_f16 = Net._stem_fusion_arg(on)
+        if self._net is not None:
+            self._net.set_stem_fusion_f16(self.stem_fusion_f16)
 
     def set_dtype(self, dtype):
         """Conv arithmetic of the plans (runtime.Net.set_dtype): None or "f32" (default), "bf16", "f16" -- 16-bit activations and

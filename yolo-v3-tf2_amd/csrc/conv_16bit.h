@@ -13,11 +13,11 @@
 //   * epilogue through LDS: accumulators (+scale/shift, leaky) are written as an fp32 [BM][BN+4] tile, then every
 //     thread converts 8 consecutive channels (+ 16-bit residual) and issues ONE 16-byte store -> full 128-B lines.
 //
-// Split-K (SPLIT = true, the low-latency bf16 plans of y3_net_set_low_latency_bf16; tiles 11 and 12 only, instantiated by conv_bf16.hip
-// alone: fp16 plans never split): gridDim.y = S, slice y walks
+// Split-K (SPLIT = true, the low-latency plans of y3_net_set_low_latency_bf16 / _f16; tiles 11 and 12 only, instantiated by both
+// files through launch_conv16_split below): gridDim.y = S, slice y walks
 // K tiles [y*KT/S, (y+1)*KT/S) of the same tap-major walk and stores its raw fp32 accumulators (no epilogue, rows >= M included) straight
 // from the accumulator registers into slab y of a workspace [S][Mpad][CoutPad] fp32, through the slab's own buffer resource.
-// splitk_finish_bf16, a separate launch on the same stream, adds the slabs in the order 0, 1, ..., S-1 and applies the epilogue.
+// splitk_finish16, a separate launch on the same stream, adds the slabs in the order 0, 1, ..., S-1 and applies the epilogue.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -31,7 +31,7 @@ __device__ __forceinline__ u32x4 bload16(__amdgpu_buffer_rsrc_t r, unsigned voff
     return __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, soff, 0);
 }
 
-// The epilogue's arithmetic, shared by the unsplit kernel and splitk_finish_bf16 so that equal accumulators give equal bits:
+// The epilogue's arithmetic, shared by the unsplit kernel and splitk_finish16 so that equal accumulators give equal bits:
 // y = acc * scale + shift (two roundings: the build never contracts them), leaky as max(y, 0.1 y) ...
 __device__ __forceinline__ float bn_act(float acc, float sc, float sh, int leaky)
 {
@@ -519,6 +519,80 @@ static hipError_t launch_conv16(const ConvArgs &a, int tile, bool out_f32, hipSt
     if (a.dst == nullptr && a.dec.boxes == nullptr) return hipErrorInvalidValue;
     if (!tile_fits(t, a.Cin, a.src1 ? a.C0 : -1, a.CoutPad)) return hipErrorInvalidValue;
     return Tiles16<E>::table[tile].launch(a, out_f32, s);
+}
+
+// Second half of a split-K conv: per element slab[0] + slab[1] + ... + slab[S-1], added in that order, then exactly the unsplit epilogue's
+// operations through the same helpers (bn_act, add_res_pack<E>).  16-bit output: eight channels per thread, 16-byte loads and stores
+// (Cout % 8 == 0).  OUT_F32 (a conv that writes an fp32 net output itself, Cout = 255 in CoutPad = 256 included): one element per thread.
+template <class E, bool OUT_F32>
+__global__ __launch_bounds__(256) void splitk_finish16(const float *__restrict__ ws, int S, size_t slab_elems, int cout_pad,
+                                                       const float *__restrict__ scale, const float *__restrict__ shift,
+                                                       const unsigned short *__restrict__ residual, void *__restrict__ dst, int M, int cout,
+                                                       int leaky)
+{
+    constexpr int W = OUT_F32 ? 1 : 8;
+    const int per_row = cout / W;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)M * per_row) return;
+    const int m = (int)(idx / per_row);
+    const int n = ((int)(idx - (size_t)m * per_row)) * W;
+    const float *src = ws + (size_t)m * cout_pad + n;
+    if constexpr (OUT_F32) {
+        float v = *src;
+        for (int s = 1; s < S; ++s) v = v + src[(size_t)s * slab_elems];
+        static_cast<float *>(dst)[(size_t)m * cout + n] = bn_act(v, scale[n], shift[n], leaky);
+    } else {
+        f32x4 a0 = *reinterpret_cast<const f32x4 *>(src), a1 = *reinterpret_cast<const f32x4 *>(src + 4);
+        for (int s = 1; s < S; ++s) {
+            a0 = a0 + *reinterpret_cast<const f32x4 *>(src + (size_t)s * slab_elems);
+            a1 = a1 + *reinterpret_cast<const f32x4 *>(src + (size_t)s * slab_elems + 4);
+        }
+        const f32x4 sc0 = *reinterpret_cast<const f32x4 *>(scale + n), sc1 = *reinterpret_cast<const f32x4 *>(scale + n + 4);
+        const f32x4 sh0 = *reinterpret_cast<const f32x4 *>(shift + n), sh1 = *reinterpret_cast<const f32x4 *>(shift + n + 4);
+        float v[8];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = bn_act(a0[k], sc0[k], sh0[k], leaky);
+            v[4 + k] = bn_act(a1[k], sc1[k], sh1[k], leaky);
+        }
+        const size_t o = (size_t)m * cout + n;
+        u32x4 rr{0u, 0u, 0u, 0u};
+        if (residual) rr = *reinterpret_cast<const u32x4 *>(residual + o);
+        *reinterpret_cast<u32x4 *>(static_cast<unsigned short *>(dst) + o) = add_res_pack<E>(v, rr, residual != nullptr);
+    }
+}
+
+// The split-K form is instantiated for the two tiles a small plan lands on: 11 (64x64) and 12 (64x128), both LDS-DMA, BK 64, four waves
+template <class E, int TN>
+static hipError_t launch_split_t(const ConvArgs &c, int grid, int S, hipStream_t s)
+{
+    constexpr size_t lds = 2 * (size_t)(64 + 64 * TN) * 128;   // the two operand stages; a split launch has no epilogue tile
+    if (c.src1) return launch_conv_kernel<conv16_mfma<E, 1, TN, 2, 2, 64, true, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+    return launch_conv_kernel<conv16_mfma<E, 1, TN, 2, 2, 64, false, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+}
+
+inline bool conv16_split_tile(int tile) { return tile == 11 || tile == 12; }
+
+// The split launch of tile id `tile` for element type E and its finish launch on the same stream (launch_conv_bf16_split / launch_conv_f16_split)
+template <class E>
+static hipError_t launch_conv16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s)
+{
+    if (!conv16_split_tile(tile)) return hipErrorInvalidValue;
+    const auto [c, slab, grid] = split_launch(a, Tiles16<E>::table[tile].info, S, ws, ws_bytes);
+    if (!slab) return hipErrorInvalidValue;
+    // the 16-bit form of the finish launch moves eight channels per thread: whole 16-byte pieces of dst and of the shortcut
+    if (!out_f32 && (a.Cout % 8 || ((uintptr_t)a.dst & 15) || ((uintptr_t)a.residual & 15))) return hipErrorInvalidValue;
+    if (out_f32 && a.residual) return hipErrorInvalidValue;
+    if (hipError_t e = tile == 12 ? launch_split_t<E, 2>(c, grid, S, s) : launch_split_t<E, 1>(c, grid, S, s); e != hipSuccess) return e;
+    const float *wsf = static_cast<const float *>(ws);
+    const unsigned short *res = static_cast<const unsigned short *>(a.residual);
+    const size_t n = (size_t)a.M * (out_f32 ? a.Cout : a.Cout / 8);
+    const dim3 fgrid((unsigned)((n + 255) / 256));
+    if (out_f32)
+        hipLaunchKernelGGL((splitk_finish16<E, true>), fgrid, dim3(256), 0, s, wsf, S, slab / 4, a.CoutPad, a.scale, a.shift, res, a.dst, a.M, a.Cout, a.leaky);
+    else
+        hipLaunchKernelGGL((splitk_finish16<E, false>), fgrid, dim3(256), 0, s, wsf, S, slab / 4, a.CoutPad, a.scale, a.shift, res, a.dst, a.M, a.Cout, a.leaky);
+    return hipGetLastError();
 }
 
 }  // namespace y3

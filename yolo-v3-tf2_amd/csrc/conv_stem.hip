@@ -353,7 +353,9 @@ hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s)
 }
 
 // -----------------------------------------------------------------------------------------------------------------
-// bf16 variant (BASELINE config 5): same tiling and phase structure.  conv0 runs on the BF16 matrix cores from split
+// 16-bit variant, generic over the element traits E (Bf16Elem / F16Elem, y3_device.h) the way conv_16bit.h is: conv_stem16<Bf16Elem> for
+// bf16 plans, conv_stem16<F16Elem> for fp16 plans with y3_net_set_stem_fusion_f16.  The bf16 form first; what fp16 changes follows it.
+// bf16 (BASELINE config 5): same tiling and phase structure.  conv0 runs on the BF16 matrix cores from split
 // operands (x = hi + lo, products hi*hi + hi*lo + lo*hi with fp32 accumulation: ~2^-16 relative error per product -- close to,
 // but NOT, the fp32 arithmetic of the stand-alone bf16 first-layer launch; see phase 1 below), then y = acc*scale + shift, leaky,
 // and the result is rounded to bf16 exactly where the two-launch form stores it -- here into the LDS patch; conv1 runs on
@@ -362,6 +364,20 @@ hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s)
 // c ^ ((n >> 2) & 3)), image patch 7,980 B: 80,748 B -> TWO workgroups per CU, one computing while the other stores.
 // The output tile leaves through LDS (the patch region, dead after phase 2): every store instruction writes whole
 // 128-B pixels (64 channels x 2 B), 16 pixels of a row contiguous.
+// Summation order of conv0 per output element, bf16: one accumulator; per K step s = 0, 1 (16 slots each, below) the MFMAs lo_x * hi_w,
+// hi_x * lo_w, hi_x * hi_w in that order.
+//
+// fp16: the same kernel on v_mfma_f32_32x32x16_f16 (conv0, conv1, phase 3), every rounding the fp16 round-to-nearest-even of the fp16 convs
+// (E::bits) where bf16 rounds to bf16: into the LDS patch and into the staging tiles.  Only conv0's arithmetic differs.  An fp16 lo plane of
+// a value in [0, 1] would be subnormal, and nothing here relies on what the f16 matrix pipe does with a subnormal operand: for a value v
+//     hi = |v| < 2^-14 ? 0 : f16(v),   lo' = f16((v - hi) * 2048)        (hi + lo' * 2^-11 == v to 2^-22 |v|, to 2^-25 absolute below 2^-14)
+// so hi is never subnormal and lo' is subnormal only where the lo it stands for is below 2^-25.  The host hands conv0's weights over divided
+// by a power of two per output channel (largest magnitude of a channel in [1, 2); StemArgs::w0, scale0 carry it), so the same holds for the
+// weights whatever their magnitude.  Pixel values must be finite and at most 65504 in magnitude (a larger one makes hi infinite).
+// Summation order of conv0 per output element, fp16: ONE accumulator set, chained (a second set of sixteen accumulators does not fit the 128
+// registers that two workgroups per CU leave a lane; the chain needs none): the cross terms of both K steps first -- lo'_x * hi_w, hi_x * lo'_w
+// of step 0, then of step 1 -- the sixteen accumulator elements times 2^-11 (exact), then hi_x * hi_w of step 0 and of step 1 with that as
+// their C input.  lo * lo is dropped as in bf16.
 // -----------------------------------------------------------------------------------------------------------------
 namespace stemb {
 using namespace stem;
@@ -371,10 +387,14 @@ constexpr int IMG_B = (IMG_F + 1) * 4;        // 7984 bytes (one pad float: conv
 constexpr int LDS_BYTES_B = PATCH_B + W1_B + IMG_B;   // 80752 <= 81920: two workgroups per CU
 }  // namespace stemb
 
-__global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
+template <class E>
+__global__ __launch_bounds__(stem::NT, 4) void conv_stem16(const StemArgs p)
 {
     clk_stamp<false>(p.clk_stamps, 0);   // measurement launches only: workgroup 0 at kernel entry and exit
     using namespace stemb;
+    using frag = typename E::frag;
+    using elem = typename E::elem;
+    constexpr bool F16 = std::is_same_v<E, F16Elem>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smemb[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -383,7 +403,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
     char *lds = reinterpret_cast<char *>(smemb);
     float *imgs = reinterpret_cast<float *>(smemb + PATCH_B + W1_B);
 
-    // conv1 weights (bf16 [64][288]) into LDS: 16-B chunk kc (8 channels; 4 chunks per tap) of row n
+    // conv1 weights (16-bit [64][288]) into LDS: 16-B chunk kc (8 channels; 4 chunks per tap) of row n
     {
         const unsigned short *w1 = static_cast<const unsigned short *>(p.w1);
         for (int g = tid; g < C1 * (K1 / 8); g += NT) {
@@ -399,7 +419,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
     // instead of 896 matrix-pipe cycles per 32 x 32 block.  The result is rounded to bf16 into the patch as before.
     // K slots (group g = 2 s + h of MFMA step s, lane half h; 8 slots j each), k = 9 u + i = float offset 105 u + i in the patch:
     //   g0: k = j              g1: k = 9 + j              g2: k = 18 + j              g3: j = 0, 1, 2 -> k = 8, 17, 26; else zero weight
-    bf16x8 bh[2], bl[2];
+    frag bh[2], bl[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s)
 #pragma unroll
@@ -409,9 +429,9 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             const float w0v = p.w0[k0 * C0 + fr];
             const float w1v = k1 >= 0 ? p.w0[k1 * C0 + fr] : 0.0f;
             const float wv = fh ? w1v : w0v;
-            const __bf16 hi = (__bf16)wv;
+            const elem hi = E::split_hi(wv);
             bh[s][j] = hi;
-            bl[s][j] = (__bf16)(wv - (float)hi);
+            bl[s][j] = E::split_lo(wv, hi);
         }
     const float sc0 = p.scale0[fr], sh0 = p.shift0[fr];
     const int wm = wave >> 1, wn = wave & 1;
@@ -427,31 +447,59 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
     const int d0 = 420 * fh, d1 = fh ? 32 : 840, d2 = fh ? 452 - 4 : 840, d3 = fh ? 872 - 8 : 840;
     const int a1o = PATCH_B + W1_B + (2 * wave * IW * 3 + fr * 3) * 4;      // origin of pixel (y = 2 wave, x = fr)
     auto conv0_block = [&](int o) -> f32x16 {
-        float xs[16];
         const int v0 = o + d0, v1 = o + d1, v2 = o + d2, v3 = o + d3;
+        auto load_step = [&](auto stag, float (&x)[8]) {   // the eight image values of K step 0 / 1
+            if constexpr (decltype(stag)::value == 0) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) xs[j] = *reinterpret_cast<const float *>(lds + v0 + j * 4);
-        xs[8] = *reinterpret_cast<const float *>(lds + v1);
-        xs[9] = *reinterpret_cast<const float *>(lds + v2 + 4);
-        xs[10] = *reinterpret_cast<const float *>(lds + v3 + 8);
+                for (int j = 0; j < 8; ++j) x[j] = *reinterpret_cast<const float *>(lds + v0 + j * 4);
+            } else {
+                x[0] = *reinterpret_cast<const float *>(lds + v1);
+                x[1] = *reinterpret_cast<const float *>(lds + v2 + 4);
+                x[2] = *reinterpret_cast<const float *>(lds + v3 + 8);
 #pragma unroll
-        for (int j = 3; j < 8; ++j) xs[8 + j] = *reinterpret_cast<const float *>(lds + v1 + j * 4);
+                for (int j = 3; j < 8; ++j) x[j] = *reinterpret_cast<const float *>(lds + v1 + j * 4);
+            }
+        };
+        auto split8 = [&](const float (&x)[8], frag &ah, frag &al) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const elem hi = E::split_hi(x[j]);
+                ah[j] = hi;
+                al[j] = E::split_lo(x[j], hi);
+            }
+        };
+        using S0 = std::integral_constant<int, 0>;
+        using S1 = std::integral_constant<int, 1>;
+        float x0[8], x1[8];
         f32x16 acc;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+        if constexpr (F16) {   // chained: cross terms of both steps, x 2^-11, then the hi * hi terms (header comment)
+            frag ah0, ah1, al;
+            load_step(S0{}, x0);
+            split8(x0, ah0, al);
+            acc = E::mfma32(al, bh[0], acc);
+            acc = E::mfma32(ah0, bl[0], acc);
+            load_step(S1{}, x1);
+            split8(x1, ah1, al);
+            acc = E::mfma32(al, bh[1], acc);
+            acc = E::mfma32(ah1, bl[1], acc);
 #pragma unroll
-        for (int s_ = 0; s_ < 2; ++s_) {
-            bf16x8 ah, al;
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const float xv = xs[8 * s_ + j];
-                const __bf16 hi = (__bf16)xv;
-                ah[j] = hi;
-                al[j] = (__bf16)(xv - (float)hi);
-            }
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bh[s_], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bl[s_], acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bh[s_], acc, 0, 0, 0);
+            for (int e = 0; e < 16; ++e) acc[e] = acc[e] * (1.0f / 2048.0f);
+            acc = E::mfma32(ah0, bh[0], acc);
+            acc = E::mfma32(ah1, bh[1], acc);
+        } else {
+            frag ah, al;
+            load_step(S0{}, x0);
+            load_step(S1{}, x1);
+            split8(x0, ah, al);
+            acc = E::mfma32(al, bh[0], acc);
+            acc = E::mfma32(ah, bl[0], acc);
+            acc = E::mfma32(ah, bh[0], acc);
+            split8(x1, ah, al);
+            acc = E::mfma32(al, bh[1], acc);
+            acc = E::mfma32(ah, bl[1], acc);
+            acc = E::mfma32(ah, bh[1], acc);
         }
         return acc;
     };
@@ -518,7 +566,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
         const int b = tile / tiles_per_img, t2 = tile - b * tiles_per_img;
         const int ty = t2 / p.tiles_x, tx = t2 - ty * p.tiles_x;
 
-        // ---- phase 1: conv0 (fp32 MFMA) -> bf16 patch ----
+        // ---- phase 1: conv0 (split operands on the 16-bit MFMA) -> 16-bit patch ----
         auto conv0_row = [&](auto ytag) {
             constexpr int YD = decltype(ytag)::value;
             const f32x16 acc = conv0_block(a1o + YD * IW * 3 * 4);
@@ -536,7 +584,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 const bool zero = zrow || (tx == 0 && xe == 0 && fh == 0);
                 v = zero ? 0.0f : v;
                 const int imm = ((xe >> 1) + (xe & 1) * 17) * 64;
-                *reinterpret_cast<unsigned short *>(lds + wa[(xe >> 2) & 3] + imm) = bf16_bits(v);
+                *reinterpret_cast<unsigned short *>(lds + wa[(xe >> 2) & 3] + imm) = E::bits(v);
             }
         };
         using I0 = std::integral_constant<int, 0>;
@@ -556,7 +604,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 v = (ty == 0 && y == 0) ? 0.0f : v;
                 // x = 32: index y*33 + 16, key (32 >> 2) & 3 = 0
                 const int off = (y * PW + 16) * 64 + ((fr >> 3) << 4) + (fr & 7) * 2;
-                if (y < PH) *reinterpret_cast<unsigned short *>(lds + off) = bf16_bits(v);
+                if (y < PH) *reinterpret_cast<unsigned short *>(lds + off) = E::bits(v);
             }
         }
         __syncthreads();   // (1) patch complete, image patch free
@@ -568,7 +616,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             img_fetch(vo);
         }
 
-        // ---- phase 2: conv1 on the bf16 matrix cores, everything from LDS ----
+        // ---- phase 2: conv1 on the 16-bit matrix cores, everything from LDS ----
         f32x16 acc;
 #pragma unroll
         for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
@@ -580,14 +628,14 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 const int bimm = (u * 3 + v) * 64;
 #pragma unroll
                 for (int s = 0; s < 2; ++s) {
-                    const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(lds + a2[v >> 1][s] + aimm);
-                    const bf16x8 fb = *reinterpret_cast<const bf16x8 *>(lds + bw[s] + bimm);
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc, 0, 0, 0);
+                    const frag fa = *reinterpret_cast<const frag *>(lds + a2[v >> 1][s] + aimm);
+                    const frag fb = *reinterpret_cast<const frag *>(lds + bw[s] + bimm);
+                    acc = E::mfma32(fa, fb, acc);
                 }
             }
         __syncthreads();   // (2) every wave is done reading the patch: it becomes the output staging tile
 
-        // ---- epilogue: [128 pixels][64 channels] bf16 through LDS, then whole 128-B pixels to HBM ----
+        // ---- epilogue: [128 pixels][64 channels] 16-bit through LDS, then whole 128-B pixels to HBM ----
         {
             const int n = wn * 32 + fr;
 #pragma unroll
@@ -595,7 +643,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 const int m = mfma32_row(e) + 4 * fh;      // pixel of this wave's 32
                 float v = acc[e] * sc1 + sh1;
                 if (p.leaky1) v = fmaxf(v, 0.1f * v);
-                *reinterpret_cast<unsigned short *>(lds + (wm * 32 + m) * 128 + n * 2) = bf16_bits(v);
+                *reinterpret_cast<unsigned short *>(lds + (wm * 32 + m) * 128 + n * 2) = E::bits(v);
             }
         }
         __syncthreads();   // (3) staging tile complete
@@ -611,7 +659,7 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
             }
         }
         if (with2) {
-            // ---- phase 3: the 1x1 conv that follows conv1 (64 -> 32), from the staging tile = conv1's output as stored (bf16) ----
+            // ---- phase 3: the 1x1 conv that follows conv1 (64 -> 32), from the staging tile = conv1's output as stored (16-bit) ----
             // waves 0..3: one 32-pixel block each, K = 64 = four steps of v_mfma_f32_32x32x16_bf16 in the k grouping of
             // conv_bf16_mfma (lane half h takes k = 16 s + 8 h .. + 7): bit-identical to the separate launch.  Weights
             // ([32][64] bf16, 4 KB, L1-resident) are fetched per tile: the kernel has no registers to keep them (118 of 128).
@@ -622,16 +670,16 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
                 const unsigned short *w2 = static_cast<const unsigned short *>(p.w2);
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
-                    const bf16x8 fa = *reinterpret_cast<const bf16x8 *>(lds + (wave * 32 + fr) * 128 + (2 * s + fh) * 16);
-                    const bf16x8 fb = *reinterpret_cast<const bf16x8 *>(w2 + fr * C1 + (2 * s + fh) * 8);
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fa, fb, acc2, 0, 0, 0);
+                    const frag fa = *reinterpret_cast<const frag *>(lds + (wave * 32 + fr) * 128 + (2 * s + fh) * 16);
+                    const frag fb = *reinterpret_cast<const frag *>(w2 + fr * C1 + (2 * s + fh) * 8);
+                    acc2 = E::mfma32(fa, fb, acc2);
                 }
 #pragma unroll
                 for (int e = 0; e < 16; ++e) {
                     const int m = mfma32_row(e) + 4 * fh;
                     float v = acc2[e] * sc2 + sh2;
                     if (p.leaky2) v = fmaxf(v, 0.1f * v);
-                    *reinterpret_cast<unsigned short *>(lds + OUT2_OFF + (wave * 32 + m) * 64 + fr * 2) = bf16_bits(v);
+                    *reinterpret_cast<unsigned short *>(lds + OUT2_OFF + (wave * 32 + m) * 64 + fr * 2) = E::bits(v);
                 }
             }
             __syncthreads();   // (3b) second staging tile ([128 pixels][32 channels] bf16) complete
@@ -649,7 +697,8 @@ __global__ __launch_bounds__(stem::NT, 4) void conv_stem_bf16(const StemArgs p)
     clk_stamp<false>(p.clk_stamps, 2);
 }
 
-hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s)
+template <class E>
+static hipError_t launch_conv_stem16(const StemArgs &a, hipStream_t s)
 {
     using namespace stemb;
     if (a.H % 32 || a.W % 32 || a.B <= 0 || !a.img || !a.w0 || !a.w1 || !a.dst || !a.scale0 || !a.scale1) return hipErrorInvalidValue;
@@ -657,12 +706,15 @@ hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s)
     p.tiles_y = (a.H / 2) / TH;
     p.tiles_x = (a.W / 2) / TW;
     p.n_tiles = a.B * p.tiles_y * p.tiles_x;
-    static LdsAttrOnce attr;
-    if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv_stem_bf16), LDS_BYTES_B, a.device); e != hipSuccess) return e;
+    static LdsAttrOnce attr;   // per instantiation
+    if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv_stem16<E>), LDS_BYTES_B, a.device); e != hipSuccess) return e;
     const int cus = a.n_cus > 0 ? a.n_cus : 256;                // read once at plan time (y3_net_plan)
     const int grid = p.n_tiles < 2 * cus ? p.n_tiles : 2 * cus;   // two persistent workgroups per CU
-    hipLaunchKernelGGL(conv_stem_bf16, dim3(grid), dim3(NT), LDS_BYTES_B, s, p);
+    hipLaunchKernelGGL(conv_stem16<E>, dim3(grid), dim3(NT), LDS_BYTES_B, s, p);
     return hipGetLastError();
 }
+
+hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s) { return launch_conv_stem16<Bf16Elem>(a, s); }
+hipError_t launch_conv_stem_f16(const StemArgs &a, hipStream_t s) { return launch_conv_stem16<F16Elem>(a, s); }
 
 }  // namespace y3

@@ -72,9 +72,14 @@ __device__ __forceinline__ unsigned pack_f16(float lo, float hi)
 
 // ---- element traits of the 16-bit MFMA conv kernels (conv_16bit.h, conv_res_16bit.h): the fragment of eight elements a lane feeds
 // an MFMA, the two MFMA shapes, two floats -> one packed word (one rounding each, to nearest even), one packed word -> two floats.
-// The lane maps of the operands and of the accumulators are the same for both types.
+// The lane maps of the operands and of the accumulators are the same for both types.  split_hi / split_lo: the two elements a value is split
+// into for the fused stem's conv0 (conv_stem.hip): bf16 v = hi + lo; fp16 v = hi + lo * 2^-11 with hi = 0 below the normal range.
 struct Bf16Elem {
     using frag = bf16x8;
+    using elem = __bf16;
+    static __device__ __forceinline__ unsigned short bits(float x) { return bf16_bits(x); }
+    static __device__ __forceinline__ elem split_hi(float v) { return (__bf16)v; }
+    static __device__ __forceinline__ elem split_lo(float v, elem hi) { return (__bf16)(v - (float)hi); }
     static __device__ __forceinline__ f32x16 mfma32(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_bf16(lo, hi); }
@@ -83,6 +88,10 @@ struct Bf16Elem {
 };
 struct F16Elem {
     using frag = f16x8;
+    using elem = _Float16;
+    static __device__ __forceinline__ unsigned short bits(float x) { return f16_bits(x); }
+    static __device__ __forceinline__ elem split_hi(float v) { return fabsf(v) < 6.103515625e-05f ? (_Float16)0.0f : (_Float16)v; }
+    static __device__ __forceinline__ elem split_lo(float v, elem hi) { return (_Float16)((v - (float)hi) * 2048.0f); }
     static __device__ __forceinline__ f32x16 mfma32(frag a, frag b, f32x16 c) { return __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ f32x4 mfma16(frag a, frag b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }
     static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_f16(lo, hi); }

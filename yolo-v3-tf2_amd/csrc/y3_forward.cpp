@@ -122,7 +122,7 @@ struct Slice {
         y3::StemArgs sa{};
         sa.img = static_cast<const float *>(ptr(c0.d.src0));
         sa.w0 = c0.*fam.w0_stem;
-        sa.scale0 = c0.scale_dev;
+        sa.scale0 = c0.*fam.scale0_stem;
         sa.shift0 = c0.shift_dev;
         sa.w1 = c1.*fam.w;
         sa.scale1 = c1.scale_dev;
@@ -352,7 +352,8 @@ try {
 Y3_CATCH("y3_net_profile_convs")
 
 namespace {
-// can conv slot i of this plan carry the clock stamps?  The fp32 MFMA kernel (fp32 plans) and the fused stem kernel do.
+// can conv slot i of this plan carry the clock stamps?  The fp32 MFMA kernel (fp32 plans) and the fused stem kernel (fp32 and bf16 plans; fp16
+// plans with y3_net_set_stem_fusion_f16) do.
 bool conv_carries_stamps(const y3_net *net, size_t i)
 {
     const int oi = y3::conv_op(net, (int)i);
@@ -407,7 +408,7 @@ y3_status measure_sclk_arrays(const y3_net *net, const float *images_dev, int ba
         if (end_us) end_us[c] = ok ? (double)(host[8 * c + 3] - t0) / 100.0 : 0.0;
         stamped += ok;
     }
-    if (!stamped) return fail(Y3_ERR_STATE, "y3_net_measure_sclk_all: no launch of this plan left clock stamps (fp32 plan or fused stem needed)");
+    if (!stamped) return fail(Y3_ERR_STATE, "y3_net_measure_sclk_all: no launch of this plan left clock stamps (fp32 plan or fused stem needed; an fp16 plan fuses its stem by y3_net_set_stem_fusion_f16)");
     return Y3_OK;
 }
 }  // namespace
@@ -428,7 +429,8 @@ y3_status y3_net_measure_sclk(y3_net *net, const float *images_dev, int batch, f
 try {
     if (!net || !mhz_out || forwards < 1) return fail(Y3_ERR_INVALID, "y3_net_measure_sclk: bad argument");
     // the launch that carries the stamps: the conv with the most FLOPs among those whose kernel has them -- the fp32 MFMA
-    // kernel (fp32 plans; a steady-state workgroup of a ~0.8 ms launch) or the fused stem kernel (fp32 and bf16 plans)
+    // kernel (fp32 plans; a steady-state workgroup of a ~0.8 ms launch) or the fused stem kernel (fp32 and bf16 plans; fp16 plans once
+    // y3_net_set_stem_fusion_f16 has switched it on)
     int pick = -1;
     double best = 0;
     for (size_t i = 0; i < net->convs.size(); ++i) {
@@ -438,7 +440,7 @@ try {
         const double fl = 2.0 * c.d.size * c.d.size * c.d.cin * c.d.cout * ho * wo;
         if (fl > best) { best = fl; pick = (int)i; }
     }
-    if (pick < 0) return fail(Y3_ERR_STATE, "y3_net_measure_sclk: no launch of this plan carries clock stamps (fp32 plan or fused stem needed)");
+    if (pick < 0) return fail(Y3_ERR_STATE, "y3_net_measure_sclk: no launch of this plan carries clock stamps (fp32 plan or fused stem needed; an fp16 plan fuses its stem by y3_net_set_stem_fusion_f16)");
     return measure_sclk_arrays(net, images_dev, batch, grids_dev, forwards, pick, mhz_out, nullptr, nullptr, stream);
 }
 Y3_CATCH("y3_net_measure_sclk")

@@ -59,6 +59,7 @@ struct ConvSlot {
     int tile = -1;             // -1: choose by heuristic at plan time
     int split_req = -1;        // y3_net_set_split_k: -1 the heuristic (low-latency plans only), 1 off, 2..16 forced
     int split_req_bf16 = -1;   // y3_net_set_split_k_bf16: as split_req, for bf16 plans
+    int split_req_f16 = -1;    // y3_net_set_split_k_f16: as split_req, for fp16 plans
     int split_k = 1;           // K slices in force in the current plan, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
     int tile_bf16 = -1;        // the 16-bit plans' forced tile: bf16 and fp16 plans share the tile table (y3_net_set_tile_bf16)
     int tile_x3 = -1;
@@ -70,6 +71,10 @@ struct ConvSlot {
     void *w_dev = nullptr;     // packed [CoutPad][K] fp32 (or HWIO for the first layer)
     float *w0stem_dev = nullptr;   // first layer only: [28][Cout] = HWIO rows x BN scale, row 27 zero (fused stem kernel, fp32)
     float *w0raw_dev = nullptr;    // first layer only: the same without the scale (fused stem kernel, bf16 mode)
+    // first layer only, fused stem kernel of fp16 plans: w0raw_dev with every output channel n divided by 2^e_n (its largest magnitude in
+    // [1, 2); e_n = 0 for an all-zero channel), and the conv0 scale of that kernel alone, scale * 2^e_n (scale_dev stays conv_first's)
+    float *w0norm_dev = nullptr;
+    float *scale0norm_dev = nullptr;
     void *wbf_dev = nullptr;   // same, bf16 (not for the first layer)
     void *wf16_dev = nullptr;  // same, IEEE fp16 rounded to nearest even on the host (Y3_DTYPE_F16 plans; not for the first layer)
     float *scale_dev = nullptr;
@@ -114,12 +119,14 @@ struct y3_net {
     size_t det_bytes = 0;
     int stem_mode = 1;             // y3_net_set_stem_fusion: 1 = conv0 + conv1 (+ the 1x1 after them) as one kernel when the graph allows it; 2 = conv0 + conv1 only
     bool stem_mode_set = false;    // y3_net_set_stem_fusion was called (the Y3_STEM_MODE tool override then stays out)
+    int stem_mode_f16 = 0;         // y3_net_set_stem_fusion_f16: the same three values for Y3_DTYPE_F16 plans, which stem_mode does not act on; off by default
     bool stem_fused = false;       // (at plan time) the first two convs run as the fused stem kernel
     bool stem_conv2 = false;       // ... and the 1x1 conv that follows them (64 -> 32) runs inside it as well (fp32 and bf16 plans)
     int xcd_mode = 1;              // y3_net_set_xcd_mode: 0 contiguous tile runs per XCD, 1 XCD-blocked order chosen per conv
     bool low_latency_set = false;  // y3_net_set_low_latency was called (the Y3_LOW_LATENCY tool override then stays out)
     bool low_latency = false;      // y3_net_set_low_latency: every eligible fp32 conv takes y3_choose_split_k
     bool low_latency_bf16 = false; // y3_net_set_low_latency_bf16: every eligible bf16 conv takes y3_choose_split_k
+    bool low_latency_f16 = false;  // y3_net_set_low_latency_f16: every eligible fp16 conv takes y3_choose_split_k
     void *split_ws = nullptr;      // split-K slabs: split_ws_lanes regions of split_ws_lane bytes, one per lane (lanes run concurrently)
     size_t split_ws_lane = 0;
     int split_ws_lanes = 0;
@@ -175,6 +182,8 @@ struct ConvFamily {
     // fused stem kernel (null: the mode has none) and the first layer's 28-row weights it reads
     hipError_t (*launch_stem)(const StemArgs &, hipStream_t);
     float *ConvSlot::*w0_stem;
+    float *ConvSlot::*scale0_stem;                 // conv0's scale for that kernel (fp16: its weights are normalised per channel)
+    int y3_net::*stem_mode;                        // the switch: 0 off, 1 conv0 + conv1 + the 1x1 after them, 2 conv0 + conv1
     const SplitForm *split;                        // null: the mode never splits K
 };
 const ConvFamily *conv_family(int dtype);   // null: no such mode
@@ -196,6 +205,7 @@ int conv_op(const y3_net *net, int slot);                    // the op that runs
 
 bool stem_applicable(const y3_net *net);
 bool stem_conv2_applicable(const y3_net *net);
+void resolve_stem(y3_net *net);   // stem_fused / stem_conv2 of a planned net from the planned mode's switch and the graph
 bool output_staged(const y3_net *net, int t);
 y3_status resolve_splits(y3_net *net);
 void free_plan(y3_net *net);

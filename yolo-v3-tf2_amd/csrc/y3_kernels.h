@@ -89,7 +89,7 @@ inline bool tile_fits(const TileInfo &t, int cin, int c0, int cout_pad)
 
 // Split-K: one slice's slab of raw fp32 accumulators, [Mpad][CoutPad] with M padded to whole tiles
 inline size_t split_slab_bytes(const TileInfo &t, long long M, int cout_pad) { return (size_t)((M + t.bm - 1) / t.bm) * t.bm * cout_pad * sizeof(float); }
-// What the split launchers of conv_f32.hip and conv_bf16.hip share before their kernel dispatch: S, the slab and the workspace checked,
+// What the split launchers of conv_f32.hip and conv_16bit.h share before their kernel dispatch: S, the slab and the workspace checked,
 // then the slice launch's arguments (raw accumulators into ws: no shortcut, no tile order, no stamps) and its grid.  slab = 0: refused.
 struct SplitLaunch { ConvArgs c; size_t slab; int grid; };
 inline SplitLaunch split_launch(const ConvArgs &a, const TileInfo &t, int S, void *ws, size_t ws_bytes)
@@ -132,8 +132,9 @@ hipError_t launch_to_f32(int dtype, const void *src, float *dst, size_t npix, in
 // fused stem (conv_stem.hip): conv0 (3x3/1, 3->32) + conv1 (3x3/2, 32->64), both BN + optional leaky, one launch
 struct StemArgs {
     const float *img;      // [B,H,W,3] fp32
-    const float *w0;       // conv0 weights [28][32] fp32, row k = (u*3 + v)*3 + c, row 27 = 0 (fp32 kernel: BN scale folded in)
-    const float *scale0;   // [32]  (bf16 kernel only: y = acc*scale + shift like the stand-alone bf16 launches)
+    const float *w0;       // conv0 weights [28][32] fp32, row k = (u*3 + v)*3 + c, row 27 = 0 (fp32 kernel: BN scale folded in;
+                           // fp16 kernel: every channel divided by a power of two 2^e_n, its largest magnitude in [1, 2))
+    const float *scale0;   // [32]  (16-bit kernels only: y = acc*scale + shift like the stand-alone launches; fp16 kernel: scale * 2^e_n)
     const float *shift0;   // [32]
     const void *w1;        // conv1 packed [64][288], k = tap*32 + c: fp32 with the BN scale folded in / bf16 unscaled
     const float *scale1;   // [64]  (bf16 kernel only)
@@ -160,6 +161,7 @@ struct StemArgs {
 };
 hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s);
 hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s);   // conv0 on bf16 MFMA from split (hi + lo) operands (~2^-16 per product), bf16 patch, conv1 on bf16 MFMA
+hipError_t launch_conv_stem_f16(const StemArgs &a, hipStream_t s);    // the same kernel on f16 MFMA: conv0 from (hi + lo' 2^-11) operands (~2^-22 per product), fp16 patch
 
 // bf16 path (conv_bf16.hip; the kernel body, shared with the fp16 path: conv_16bit.h)
 static constexpr int BF16_TILE_COUNT = 37;   // 32: the weight-resident 3x3 kernel (conv_res_bf16.hip); 20, 33..36: retired ids
@@ -167,16 +169,18 @@ TileInfo conv_bf16_tile_info(int tile);
 bool conv_bf16_tile_built(int tile);
 hipError_t launch_conv_bf16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
 // split-K form of the same conv (conv_bf16.hip): S >= 2 slices of the K walk (K tiles of 64) as S times the workgroups, raw fp32
-// accumulators into ws [S][Mpad][CoutPad] (at least S * split_slab_bytes), then splitk_finish_bf16 on the same stream: the
+// accumulators into ws [S][Mpad][CoutPad] (at least S * split_slab_bytes), then splitk_finish16 on the same stream: the
 // slabs added in the order 0..S-1, the epilogue, the store to a.dst (bf16, or fp32 with out_f32).  Tiles 11 and 12 only.
+// launch_conv_f16_split (conv_f16.hip): the same for fp16 plans; conv_bf16_split_tile answers for both.
 bool conv_bf16_split_tile(int tile);
 hipError_t launch_conv_bf16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s);
 // weight-resident 3x3 / stride-1 conv for Cin = 32 / 64 (conv_res_bf16.hip): the early short-K layers of the bf16 path
 bool conv_res_bf16_fits(const ConvArgs &a);
 hipError_t launch_conv_res_bf16(const ConvArgs &a, hipStream_t s);
 // fp16 path (conv_f16.hip, conv_res_f16.hip; Y3_DTYPE_F16): the same kernels on the f16 forms of the two MFMA instructions, the bf16
-// path's tile ids and table (conv_bf16_tile_info / conv_bf16_tile_built / conv_res_bf16_fits answer for both); no split-K form
+// path's tile ids and table (conv_bf16_tile_info / conv_bf16_tile_built / conv_res_bf16_fits / conv_bf16_split_tile answer for both)
 hipError_t launch_conv_f16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
+hipError_t launch_conv_f16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s);
 hipError_t launch_conv_res_f16(const ConvArgs &a, hipStream_t s);
 
 // fp32-accurate path on the bf16 matrix cores, three bf16 planes per value (conv_f32x3.hip)

@@ -122,6 +122,22 @@ std::vector<float> pack_stem28(const float *w, int K, int cout, const float *sca
     return w28;
 }
 
+// fp16 plans' fused stem kernel: the 28 unscaled rows with every output channel n divided by 2^e_n, e_n such that the channel's largest
+// magnitude lands in [1, 2) (0 for an all-zero channel) -- exact, a power of two -- and exps[n] = e_n for the kernel's conv0 scale
+std::vector<float> pack_stem28_norm(const float *w, int K, int cout, std::vector<int> &exps)
+{
+    std::vector<float> w28 = pack_stem28(w, K, cout, nullptr);
+    exps.assign(cout, 0);
+    for (int n = 0; n < cout; ++n) {
+        float mx = 0.0f;
+        for (int k = 0; k < K; ++k) mx = std::max(mx, fabsf(w28[(size_t)k * cout + n]));
+        if (!(mx > 0.0f) || !std::isfinite(mx)) continue;
+        exps[n] = std::ilogb(mx);
+        for (int k = 0; k < K; ++k) w28[(size_t)k * cout + n] = ldexpf(w28[(size_t)k * cout + n], -exps[n]);
+    }
+    return w28;
+}
+
 // three bf16 planes: x = hi + mid + lo exactly
 void split_bf16x3(float x, unsigned short v[3])
 {
@@ -306,6 +322,15 @@ bool y3::stem_conv2_applicable(const y3_net *net)
     return !is_output(net, c.dst);
 }
 
+// The planned mode's stem switch (y3_net_set_stem_fusion: fp32 and bf16 plans; y3_net_set_stem_fusion_f16: fp16 plans) and the graph decide
+void y3::resolve_stem(y3_net *net)
+{
+    const ConvFamily &f = family_of(net);
+    const int mode = f.launch_stem ? net->*f.stem_mode : 0;
+    net->stem_fused = mode && stem_applicable(net);
+    net->stem_conv2 = net->stem_fused && mode == 1 && stem_conv2_applicable(net);
+}
+
 // Is net output t staged in a non-fp32 plan -- produced in the arena in the mode's own format and converted into the caller's fp32
 // grid at the end of the forward -- because a conv reads it again inside the net, or a conv with no fp32-output form of its launch
 // (shortcut, first layer) writes it?  Needs no plan: y3_net_plan marks `staged` by it, and y3_net_set_tile_bf16 refuses the
@@ -354,7 +379,7 @@ void refine_f32(const y3_net *net, const ConvSlot &c, const y3::ConvArgs &a, y3:
     if (c.d.size == 3 && c.d.src1 < 0 && ck > 0 && c.d.cin > ck && c.d.cin % ck == 0 && ck % 32 == 0) ch.k_chunk = ck;
 }
 
-// bf16 and fp16 plans: a head conv that decodes its own tiles needs a 256-wide tile (split_k is 1 throughout an fp16 plan)
+// bf16 and fp16 plans: a head conv that decodes its own tiles needs a 256-wide tile
 void refine_bf16(const y3_net *, const ConvSlot &c, const y3::ConvArgs &a, y3::ConvChoice &ch)
 {
     if (c.split_k > 1 && !a.dec.boxes) {   // low-latency plan: S slices of the K walk into the lane's slabs, then the finish launch
@@ -400,30 +425,41 @@ constexpr y3::SplitForm BF16_SPLIT = {
     "tiles 11 and 12 have",
     "only Y3_DTYPE_BF16 plans take a bf16 split", 8, "a split conv storing bf16 needs Cout % 8 == 0"};
 
+// fp16: the bf16 row with the fp16 launcher, request and switch.  The floor is bf16's: the fp16 kernels are the bf16 ones instruction for
+// instruction but the MFMA and the conversions of the epilogue.
+constexpr y3::SplitForm F16_SPLIT = {
+    y3::conv_bf16_split_tile, y3::launch_conv_f16_split, 64, kSplitMinKTilesBf16, &ConvSlot::split_req_f16, &y3_net::low_latency_f16,
+    "y3_net_set_split_k_f16", "y3_net_set_low_latency_f16", BF16_SPLIT.no_form, BF16_SPLIT.tiles,
+    "only Y3_DTYPE_F16 plans take an fp16 split", 8, "a split conv storing fp16 needs Cout % 8 == 0"};
+
 constexpr y3::ConvFamily F32_FAMILY = {
     y3::TILE_COUNT, y3::conv_tile_info, y3::conv_tile_built, &ConvSlot::tile, &ConvSlot::cout_pad,
     "y3_net_set_tile: bad argument", "y3_net_set_tile: tile id %d is retired (the timing ablations of rounds 1-2; y3_tile_built)",
     "y3_net_set_tile: tile does not divide Cout", 33, resident_rule_f32,
-    &ConvSlot::w_dev, 4, choose_tile, launch_f32, refine_f32, y3::launch_conv_stem_f32, &ConvSlot::w0stem_dev, &F32_SPLIT};
+    &ConvSlot::w_dev, 4, choose_tile, launch_f32, refine_f32, y3::launch_conv_stem_f32, &ConvSlot::w0stem_dev, &ConvSlot::scale_dev, &y3_net::stem_mode,
+    &F32_SPLIT};
 constexpr y3::ConvFamily BF16_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
     "y3_net_set_tile_bf16: bad argument",
     "y3_net_set_tile_bf16: tile id %d is retired (20: the pipelined tile of round 2; 33..36: tap-row reuse and the four-wave tile of round 4; y3_tile_built)",
     "y3_net_set_tile_bf16: tile does not fit this conv", 32, resident_rule_bf16,
-    &ConvSlot::wbf_dev, 2, choose_tile_bf16, y3::launch_conv_bf16, refine_bf16, y3::launch_conv_stem_bf16, &ConvSlot::w0raw_dev, &BF16_SPLIT};
-// fp16 plans: the bf16 family's tile table, forced-tile field, chooser and refine rule; fp16 weights and launcher; no fused stem, no split form
+    &ConvSlot::wbf_dev, 2, choose_tile_bf16, y3::launch_conv_bf16, refine_bf16, y3::launch_conv_stem_bf16, &ConvSlot::w0raw_dev, &ConvSlot::scale_dev,
+    &y3_net::stem_mode, &BF16_SPLIT};
+// fp16 plans: the bf16 family's tile table, forced-tile field, chooser and refine rule; fp16 weights and launchers; the fused stem and the
+// split form behind switches of their own (y3_net_set_stem_fusion_f16, y3_net_set_low_latency_f16 / _split_k_f16), off by default
 constexpr y3::ConvFamily F16_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
     BF16_FAMILY.bad, BF16_FAMILY.retired, BF16_FAMILY.misfit, 32, resident_rule_bf16,
-    &ConvSlot::wf16_dev, 2, choose_tile_bf16, y3::launch_conv_f16, refine_bf16, nullptr, nullptr, nullptr};
+    &ConvSlot::wf16_dev, 2, choose_tile_bf16, y3::launch_conv_f16, refine_bf16, y3::launch_conv_stem_f16, &ConvSlot::w0norm_dev, &ConvSlot::scale0norm_dev,
+    &y3_net::stem_mode_f16, &F16_SPLIT};
 constexpr y3::ConvFamily X3_FAMILY = {
     y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x3_tile_built, &ConvSlot::tile_x3, &ConvSlot::cout_pad64,
     "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: tile does not fit this conv", -1, nullptr,
-    &ConvSlot::wx3_dev, 6, choose_tile_x3, y3::launch_conv_f32x3, nullptr, nullptr, nullptr, nullptr};
+    &ConvSlot::wx3_dev, 6, choose_tile_x3, y3::launch_conv_f32x3, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 constexpr y3::ConvFamily X2_FAMILY = {
     y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x2_tile_built, &ConvSlot::tile_x2, &ConvSlot::cout_pad64,
     "y3_net_set_tile_x2: bad argument", "y3_net_set_tile_x2: tile does not fit this conv", "y3_net_set_tile_x2: tile does not fit this conv", -1, nullptr,
-    &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr, nullptr};
+    &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 // "forced tile, else the family's chooser": the tile part of the launch decision
 int family_tile(const y3::ConvFamily &f, const ConvSlot &c, long long M, long long M_plan, bool arena_out)
@@ -496,7 +532,7 @@ static y3_status set_forced_tile(const y3::ConvFamily &f, y3_net *net, int slot,
     return Y3_OK;
 }
 
-// ---- split-K (low-latency fp32 and bf16 plans) --------------------------------------------------------------------------------------
+// ---- split-K (low-latency fp32, bf16 and fp16 plans) --------------------------------------------------------------------------------
 // Can conv `slot` ever run split in the mode of `f` (which has a split form)?  From the graph and the forced tile alone (no plan needed):
 // not the first layer, not a detection head (y3_net_detect runs the heads through conv_head.hip / decodes them in the launch, and the
 // composed route must stay bit-identical to it), only on the tiles the split form is built for, and with a Cout the mode's finish launch
@@ -576,7 +612,7 @@ static y3_status resolve_splits_of_setter(y3_net *net)
     return y3::resolve_splits(net);
 }
 
-// The one body of y3_net_set_low_latency / _bf16.  was_set: the flag that records the call (fp32: the Y3_LOW_LATENCY override then stays out)
+// The one body of y3_net_set_low_latency / _bf16 / _f16.  was_set: the flag that records the call (fp32: the Y3_LOW_LATENCY override then stays out)
 static y3_status set_low_latency(const y3::ConvFamily &f, y3_net *net, int on, bool y3_net::*was_set = nullptr)
 {
     if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "%s: argument must be 0 or 1", f.split->set_switch);
@@ -585,7 +621,7 @@ static y3_status set_low_latency(const y3::ConvFamily &f, y3_net *net, int on, b
     return resolve_splits_of_setter(net);
 }
 
-// The one body of y3_net_set_split_k / _bf16: the request of the mode of `f`; a forced S only where the conv can take it
+// The one body of y3_net_set_split_k / _bf16 / _f16: the request of the mode of `f`; a forced S only where the conv can take it
 static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int S)
 {
     const y3::SplitForm &sf = *f.split;
@@ -609,7 +645,7 @@ static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int
     return resolve_splits_of_setter(net);
 }
 
-// y3_net_get_split_k / _bf16: the split in force when the net is planned in the mode of `f`, 1 otherwise
+// y3_net_get_split_k / _bf16 / _f16: the split in force when the net is planned in the mode of `f`, 1 otherwise
 static int split_in_force(const y3::ConvFamily &f, const y3_net *net, int slot)
 {
     if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height || &y3::family_of(net) != &f) return 1;
@@ -709,7 +745,7 @@ void y3_net_destroy(y3_net *net)
         }
     }
     for (ConvSlot &c : net->convs)
-        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev})
+        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, (void *)c.w0norm_dev, (void *)c.scale0norm_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev})
             if (p) (void)hipFree(p);
     delete net;
 }
@@ -742,6 +778,12 @@ try {
         HIP_TRY(upload(c.w_dev, std::vector<float>(w, w + (size_t)K * d.cout)));
         HIP_TRY(upload(c.w0stem_dev, pack_stem28(w, K, d.cout, scale.data())));
         HIP_TRY(upload(c.w0raw_dev, pack_stem28(w, K, d.cout, nullptr)));
+        // ... and normalised per output channel by a power of two, with the scale that undoes it (fp16)
+        std::vector<int> exps;
+        HIP_TRY(upload(c.w0norm_dev, pack_stem28_norm(w, K, d.cout, exps)));
+        std::vector<float> scale_norm(scale.begin(), scale.begin() + d.cout);
+        for (int n = 0; n < d.cout; ++n) scale_norm[n] = ldexpf(scale_norm[n], exps[n]);
+        HIP_TRY(upload(c.scale0norm_dev, scale_norm));
     } else {
         // fp32 path: the BN scale is folded into the packed weights (one VALU multiply less per output element; VALU
         // time is matrix-pipe time for the fp32 MFMA).  The bf16 copy keeps the unscaled weights + scale in the epilogue.
@@ -792,19 +834,27 @@ try {
 }
 Y3_CATCH("y3_net_set_lanes")
 
-y3_status y3_net_set_stem_fusion(y3_net *net, int on)
-try {
-    if (!net || on < 0 || on > 2) return fail(Y3_ERR_INVALID, "y3_net_set_stem_fusion: argument must be 0, 1 or 2");
-    net->stem_mode = on;
-    net->stem_mode_set = true;
-    // takes effect at once on a planned net when the graph qualifies (decided again by the next y3_net_plan)
-    if (net->height) {
-        net->stem_fused = on && y3::stem_applicable(net);
-        net->stem_conv2 = net->stem_fused && on == 1 && y3::stem_conv2_applicable(net);
-    }
+// The one body of y3_net_set_stem_fusion / _f16: the switch `mode` of the plans it acts on
+static y3_status set_stem_fusion(const char *who, y3_net *net, int y3_net::*mode, int on)
+{
+    if (!net || on < 0 || on > 2) return fail(Y3_ERR_INVALID, "%s: argument must be 0, 1 or 2", who);
+    net->*mode = on;
+    // takes effect at once on a planned net of the switch's mode when the graph qualifies (decided again by the next y3_net_plan)
+    if (net->height) y3::resolve_stem(net);
     return resolve_splits_of_setter(net);   // a conv inside the fused stem is not split
 }
+
+y3_status y3_net_set_stem_fusion(y3_net *net, int on)
+try {
+    const y3_status st = set_stem_fusion("y3_net_set_stem_fusion", net, &y3_net::stem_mode, on);
+    if (st == Y3_OK) net->stem_mode_set = true;
+    return st;
+}
 Y3_CATCH("y3_net_set_stem_fusion")
+
+y3_status y3_net_set_stem_fusion_f16(y3_net *net, int on)
+try { return set_stem_fusion("y3_net_set_stem_fusion_f16", net, &y3_net::stem_mode_f16, on); }
+Y3_CATCH("y3_net_set_stem_fusion_f16")
 
 y3_status y3_net_set_k_chunk(y3_net *net, int channels)
 try {
@@ -829,6 +879,14 @@ Y3_CATCH("y3_net_set_low_latency_bf16")
 y3_status y3_net_set_split_k_bf16(y3_net *net, int slot, int S)
 try { return set_split_k(BF16_FAMILY, net, slot, S); }
 Y3_CATCH("y3_net_set_split_k_bf16")
+
+y3_status y3_net_set_low_latency_f16(y3_net *net, int on)
+try { return set_low_latency(F16_FAMILY, net, on); }
+Y3_CATCH("y3_net_set_low_latency_f16")
+
+y3_status y3_net_set_split_k_f16(y3_net *net, int slot, int S)
+try { return set_split_k(F16_FAMILY, net, slot, S); }
+Y3_CATCH("y3_net_set_split_k_f16")
 
 y3_status y3_net_set_xcd_mode(y3_net *net, int mode)
 try {
@@ -859,6 +917,8 @@ Y3_CATCH("y3_net_keep_activations")
 int y3_net_get_split_k(const y3_net *net, int slot) { return split_in_force(F32_FAMILY, net, slot); }
 
 int y3_net_get_split_k_bf16(const y3_net *net, int slot) { return split_in_force(BF16_FAMILY, net, slot); }
+
+int y3_net_get_split_k_f16(const y3_net *net, int slot) { return split_in_force(F16_FAMILY, net, slot); }
 
 int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice)
 {

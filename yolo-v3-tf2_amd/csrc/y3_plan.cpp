@@ -171,8 +171,7 @@ try {
         static const int env = [] { const char *e = getenv("Y3_STEM_MODE"); return e ? atoi(e) : -1; }();
         if (env >= 0 && env <= 2 && !net->stem_mode_set) net->stem_mode = env;
     }
-    net->stem_fused = net->stem_mode && y3::stem_applicable(net);
-    net->stem_conv2 = net->stem_fused && net->stem_mode == 1 && y3::stem_conv2_applicable(net);
+    y3::resolve_stem(net);
     {   // Y3_LOW_LATENCY (tools/ab_libs.py: a low-latency plan in a child process that knows nothing of it) overrides the default, not the setter
         static const int env = [] { const char *e = getenv("Y3_LOW_LATENCY"); return e ? atoi(e) : -1; }();
         if ((env == 0 || env == 1) && !net->low_latency_set) net->low_latency = env == 1;

@@ -100,6 +100,7 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
                          detect_config["nms_iou_threshold"], detect_config["yolo_max_boxes"],
                          detect_config.get("input_weights_path"), weights)
     model.model.set_dtype(detect_config.get("dtype"))     # optional key: f32 | bf16 | f16; absent: f32
+    model.model.set_stem_fusion_f16(detect_config.get("f16_fused_stem"))   # optional key, acts on dtype f16 only; absent: off
     net = model.model._device_net()
     if net.image_size != S or net.max_batch < batch_size:
         net.plan(max(batch_size, net.max_batch), S)
@@ -161,7 +162,8 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     val_loss, perGrid and perSource[xy,wh,obj,class] are printed as the reference's eager loop prints them (train.py:86-91) and
     the return value becomes (results, {"sum": float64 [3,4], "images": int, "errors": int}) as Net.evaluate_stream gives it.
     The regulariser (model.losses, decay_factor) that the reference's totLoss includes is not part of it.
-    An optional `dtype: f32 | bf16 | f16` key of detect_config selects the conv arithmetic of the on_device pass (absent: f32)."""
+    An optional `dtype: f32 | bf16 | f16` key of detect_config selects the conv arithmetic of the on_device pass (absent: f32);
+    an optional `f16_fused_stem: true` runs the first convs of an f16 plan as the fused stem kernel (absent: off)."""
     if loss and not on_device:
         raise ValueError("evaluate: loss=True needs on_device=True (the loss is computed on the GPU, from the device pass)")
     anchors_table = np.asarray(get_anchors(detect_config["anchors_file"]), np.float32)

@@ -54,6 +54,9 @@ class DetectModel:
 
 
 class Inference:
+    # fp16 plans with the fused stem kernel (runtime.Net.set_stem_fusion_f16; None: off).  The optional YAML key `f16_fused_stem` of the
+    # inference config lands here (main()); __call__ keeps the reference's keys plus the two every plan has, low_latency and dtype.
+    f16_fused_stem = None
 
     @staticmethod
     def gather_valid_detections_results(bboxes_padded, class_indices_padded, scores_padded, selected_indices_padded,
@@ -99,10 +102,12 @@ class Inference:
         return (canvas_h, canvas_w), anchors_table
 
     def build(self, model_config_file, classes_name_file, anchors_file, input_weights_path, yolo_max_boxes,
-              nms_iou_threshold, nms_score_threshold, weights=None, low_latency=None, dtype=None):
+              nms_iou_threshold, nms_score_threshold, weights=None, low_latency=None, dtype=None, f16_fused_stem=None):
         """low_latency (optional YAML key; None or absent: off): plan the network for latency at one to eight images -- the
         fp32 convs that leave most of the chip idle at such a batch are split along K (runtime.Net.set_low_latency).
-        dtype (optional YAML key: f32 | bf16 | f16; None or absent: f32): the conv arithmetic (runtime.Net.set_dtype)."""
+        dtype (optional YAML key: f32 | bf16 | f16; None or absent: f32): the conv arithmetic (runtime.Net.set_dtype).
+        f16_fused_stem (optional YAML key; None or absent: what self.f16_fused_stem says, off by default): with dtype f16, the first
+        convs as the fused stem kernel (runtime.Net.set_stem_fusion_f16); without effect on any other dtype."""
         anchors_table = get_anchors(anchors_file).astype(np.float32)      # reference: inference.py:83
         class_names = [c.strip() for c in open(classes_name_file).readlines()]
         nclasses = len(class_names)
@@ -121,6 +126,7 @@ class Inference:
             model.load_weights(input_weights_path).expect_partial()
         model.set_low_latency(low_latency)
         model.set_dtype(dtype)
+        model.set_stem_fusion_f16(self.f16_fused_stem if f16_fused_stem is None else f16_fused_stem)
         print("weights loaded")
         return DetectModel(model, anchors_table, nclasses, yolo_max_boxes, nms_iou_threshold,
                            nms_score_threshold), class_names
@@ -213,7 +219,9 @@ def main(argv=None):
     args = parser.parse_args(argv)
     with open(args.config, "r") as stream:
         detect_config = yaml.safe_load(stream)
-    Inference()(**detect_config)
+    inference = Inference()
+    inference.f16_fused_stem = detect_config.pop("f16_fused_stem", None)    # optional key, absent: off
+    inference(**detect_config)
 
 
 if __name__ == "__main__":

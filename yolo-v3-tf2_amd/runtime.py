@@ -222,7 +222,7 @@ class Net:
             raise Y3Error(f"{who}: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
         return int(slot)
 
-    def _set_low_latency(self, sfx: str, on):   # sfx, here and below: "" the fp32 plans' entry points, "_bf16" the bf16 plans'
+    def _set_low_latency(self, sfx: str, on):   # sfx, here and below: "" the fp32 plans' entry points, "_bf16" the bf16 plans', "_f16" the fp16 plans'
         on = int(self._low_latency_arg(on))     # the argument checks come first: they need no device net
         check(getattr(self.lib, "y3_net_set_low_latency" + sfx)(self._h, on), "y3_net_set_low_latency" + sfx)
 
@@ -265,10 +265,38 @@ class Net:
         """K slices in force for conv `slot` in a bf16 plan after plan() (1: the ordinary launch; 1 on every other plan)."""
         return self._split_k("_bf16", slot)
 
+    def set_low_latency_f16(self, on=True):
+        """Low-latency fp16 plan for one to eight images (y3_net_set_low_latency_f16): as set_low_latency_bf16, for a plan made with
+        Y3_DTYPE_F16.  The three switches are independent; each acts on plans of its own dtype only.  None means off."""
+        self._set_low_latency("_f16", on)
+
+    def set_split_k_f16(self, slot: int, S: int):
+        """K slices of conv `slot` in an fp16 plan: -1 the heuristic (in force only with set_low_latency_f16), 1 off, 2..16 forced.
+        Refused as set_split_k_bf16 refuses, with "a plan that is not fp16" for "a plan that is not bf16"."""
+        self._set_split_k("_f16", slot, S)
+
+    def split_k_f16(self, slot: int) -> int:
+        """K slices in force for conv `slot` in an fp16 plan after plan() (1: the ordinary launch; 1 on every other plan)."""
+        return self._split_k("_f16", slot)
+
+    @staticmethod
+    def _stem_fusion_arg(on) -> int:
+        if on is None:
+            return 0
+        if isinstance(on, (bool, np.bool_, int, np.integer)) and int(on) in (0, 1, 2):
+            return int(on)
+        raise Y3Error(f"stem fusion must be None, a bool, 0, 1 or 2 (got {on!r})")
+
     def set_stem_fusion(self, on):
         """conv0 + conv1 (+ the 1x1 conv that follows them) as one kernel (default on; applies when the program starts with
         the Darknet-53 stem and the plan is fp32 or bf16 without keep_activations).  2: conv0 + conv1 only."""
         check(self.lib.y3_net_set_stem_fusion(self._h, int(on)), "y3_net_set_stem_fusion")
+
+    def set_stem_fusion_f16(self, on=True):
+        """The same switch for fp16 plans, and for them only (y3_net_set_stem_fusion_f16): off by default; True / 1, 2 as
+        set_stem_fusion; None means off.  Pixel values must be finite and at most 65504 in magnitude."""
+        on = self._stem_fusion_arg(on)          # the argument check comes first: it needs no device net
+        check(self.lib.y3_net_set_stem_fusion_f16(self._h, on), "y3_net_set_stem_fusion_f16")
 
     def set_early_chunk(self, n_convs: int, chunk_images: int):
         """Before plan(): the first n_convs convs run chunk_images images at a time (their activations then stay in the
@@ -303,7 +331,7 @@ class Net:
         dtype: _lib.Y3_DTYPE_F32 (default, fp32 MFMA), _lib.Y3_DTYPE_F32X3 (fp32-accurate on the bf16 matrix cores:
         three bf16 planes per value), _lib.Y3_DTYPE_F32X2 (two fp16 planes per value, 2^-22 representation, |x| < 65504)
         _lib.Y3_DTYPE_BF16 (bf16 activations/weights, fp32 accumulate) or _lib.Y3_DTYPE_F16 (the same with IEEE fp16: 8 x closer to
-        fp32, values beyond 65504 become inf; never the fused stem, never split-K)."""
+        fp32, values beyond 65504 become inf; the fused stem and split-K only through set_stem_fusion_f16 / set_low_latency_f16)."""
         if dtype is None:
             dtype = self.dtype
         H, W = canvas_hw(image_size)

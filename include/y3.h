@@ -43,7 +43,7 @@ enum {
 };
 
 /* activation storage / MFMA input type of the conv stack */
-enum { Y3_DTYPE_F32 = 0, Y3_DTYPE_BF16 = 1, Y3_DTYPE_F32X3 = 2, Y3_DTYPE_F32X2 = 3, Y3_DTYPE_F16 = 4 };
+enum { Y3_DTYPE_F32 = 0, Y3_DTYPE_BF16 = 1, Y3_DTYPE_F32X3 = 2, Y3_DTYPE_F32X2 = 3, Y3_DTYPE_F16 = 4, Y3_DTYPE_I8 = 5 };
 
 int y3_version(void);
 const char *y3_last_error(void);
@@ -282,6 +282,41 @@ y3_status y3_net_forward(y3_net *net, const float *images_dev, int batch, float 
 /* debugging / tests: copy tensor `tensor_id` of the last forward to dst_dev as fp32 (element count returned
  * through *n_elems; dst_dev may be NULL to query the size) */
 y3_status y3_net_read_tensor(y3_net *net, int tensor_id, int batch, float *dst_dev, size_t *n_elems, void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * int8 plans (Y3_DTYPE_I8): post-training quantisation, calibrated by the caller.
+ * Format: symmetric int8 in [-127, 127]; one fp32 scale s_t per activation tensor (set here), one fp32 scale s_w[c] per output
+ * channel of a conv's weights (the library's: y3_net_set_conv_weights quantises the raw conv weights, s_w[c] = absmax_c / 127 or 1 for an
+ * all-zero channel, q = clamp(rint(w / s_w[c])) with a true division and round to nearest even; a further copy of the weights, 62 MB for
+ * YOLOv3; BN stays in the epilogue).
+ * A conv that stores int8 computes, per output element, on exact i32 sums (v_mfma_i32_32x32x32_i8 / v_mfma_i32_16x16x64_i8):
+ *     v = (float)acc * sc[c] + sh[c]          two fp32 roundings, never contracted; sc[c] = (s_in * s_w[c]) * bn_scale[c], sh the fp32 plan's shift
+ *     v = max(v, 0.1f * v)                    when leaky
+ *     v = (float)r * s_res + v                when there is a shortcut; r the int8 shortcut value
+ *     q = clamp(rintf(v * (1.0f / s_out)), -127, 127)
+ * and a conv that writes an fp32 grid (the heads) stores v = (float)acc * (s_in * s_w[c]) + bias[c].  Every stored byte and every head
+ * logit is a fixed function of the input bytes: yolo_v3_tf2_amd/quant.py restates it in NumPy and the tests compare with no tolerance.
+ * Where int8 starts: the plan finds the first conv c* in op order such that it and every conv after it has Cin % 128 == 0 (both parts of
+ * a concat), and Cout % 16 == 0 unless it writes an fp32 output (YOLOv3: conv 9; 87 % of the FLOPs are behind it).  The convs before c*
+ * launch exactly what a Y3_DTYPE_F16 plan launches (y3_net_set_stem_fusion_f16 acts on them); every tensor written before the cut and read
+ * behind it gets an int8 copy from one elementwise launch, q = clamp(rintf((float)x * (1.0f / s_t))) (YOLOv3: conv 8's output); an input
+ * that feeds an MFMA conv directly (layer tests) is handed over as fp16 and quantised the same way.  A graph with no qualifying conv is
+ * refused (Y3_ERR_INVALID), a plan that needs an unset scale is refused with Y3_ERR_STATE naming the tensor, and the two sources of a
+ * concat conv must carry the same scale (Y3_ERR_INVALID naming the conv).
+ * Tiles: the bf16 table's ids for the tiles that have an int8 form (y3_tile_built(Y3_DTYPE_I8, id): 8, 10, 11, 12, 17, 19, 24, 26, 27,
+ * 29), chosen by the bf16 heuristic; y3_net_set_tile_bf16 forces one (a forced tile without an int8 form leaves the conv to the
+ * heuristic).  No int8 tuning table is shipped.  y3_net_forward_decode / y3_net_detect decode the heads in the launch as in a bf16 plan.
+ * Not in this version: split-K (none of the low-latency switches acts on an int8 plan), a weight-resident tile, BK = 32 tiles (so no int8
+ * for Cin = 32 / 64), and the int8 copy fused into the producing epilogue.
+ *
+ * y3_net_set_act_scales: n_tensors must be the net's tensor count; entries <= 0 mean unset.  Read by the next y3_net_plan.
+ * y3_net_get_act_scale: the scale set for a tensor, 0 when unset.  y3_net_i8_first_conv: c* of a net planned in Y3_DTYPE_I8, else -1.
+ * y3_net_read_tensor_i8: the raw bytes of an int8 tensor of the last forward (a tensor behind the cut, or the int8 copy of one that
+ * crosses it); y3_net_read_tensor on an int8 tensor returns (float)q * s. */
+y3_status y3_net_set_act_scales(y3_net *net, const float *scales, int n_tensors);
+float y3_net_get_act_scale(const y3_net *net, int tensor_id);
+int y3_net_i8_first_conv(const y3_net *net);
+y3_status y3_net_read_tensor_i8(y3_net *net, int tensor_id, int batch, int8_t *dst_dev, size_t *n_elems, void *stream);
 
 /* conv FLOPs (2*MAC) of one image at the planned size (height x width) */
 double y3_net_flops_per_image(const y3_net *net);

@@ -17,8 +17,10 @@ from . import PACKAGE_DIR
 LIB_PATH = os.environ.get("Y3_LIB_PATH") or os.path.join(PACKAGE_DIR, "lib", "liby3hip.so")
 
 Y3_OK = 0
-Y3_DTYPE_F32, Y3_DTYPE_BF16, Y3_DTYPE_F32X3, Y3_DTYPE_F32X2, Y3_DTYPE_F16 = 0, 1, 2, 3, 4
-DTYPE_TAGS = {Y3_DTYPE_F32: "f32", Y3_DTYPE_BF16: "bf16", Y3_DTYPE_F32X3: "f32x3", Y3_DTYPE_F32X2: "f32x2", Y3_DTYPE_F16: "f16"}
+Y3_DTYPE_F32, Y3_DTYPE_BF16, Y3_DTYPE_F32X3, Y3_DTYPE_F32X2, Y3_DTYPE_F16, Y3_DTYPE_I8 = 0, 1, 2, 3, 4, 5
+DTYPE_TAGS = {Y3_DTYPE_F32: "f32", Y3_DTYPE_BF16: "bf16", Y3_DTYPE_F32X3: "f32x3", Y3_DTYPE_F32X2: "f32x2", Y3_DTYPE_F16: "f16", Y3_DTYPE_I8: "i8"}
+# int8 plans: the ids of TILES_BF16 that have an int8 form (csrc/conv_i8.hip; y3_tile_built(Y3_DTYPE_I8, id)); BK is 128 channels
+TILES_I8_BUILT = (8, 10, 11, 12, 17, 19, 24, 26, 27, 29)
 TILES_X2_BUILT = (0, 1, 2, 3, 4, 8, 12, 26, 27)
 TILES_X3_BUILT = (0, 1, 2, 3, 4, 8, 9, 12, 13, 14)
 Y3_AUX_ADD, Y3_AUX_UPSAMPLE2X, Y3_AUX_CONCAT = 0, 1, 2
@@ -130,6 +132,10 @@ SYMBOLS = {
     "y3_net_plan_hw": (_i, [_vp, _i, _i, _i, _i]),
     "y3_net_forward": (_i, [_vp, _vp, _i, C.POINTER(_vp), _vp]),
     "y3_net_read_tensor": (_i, [_vp, _i, _i, _vp, C.POINTER(_sz), _vp]),
+    "y3_net_set_act_scales": (_i, [_vp, _fp, _i]),
+    "y3_net_get_act_scale": (_f, [_vp, _i]),
+    "y3_net_i8_first_conv": (_i, [_vp]),
+    "y3_net_read_tensor_i8": (_i, [_vp, _i, _i, _vp, C.POINTER(_sz), _vp]),
     "y3_net_flops_per_image": (C.c_double, [_vp]),
     "y3_net_profile_convs": (_i, [_vp, _vp, _i, _fp, _i, _vp]),
     "y3_preprocess_image": (_i, [_vp, _i, _i, _i, _i, _vp, _i, _i, _vp]),

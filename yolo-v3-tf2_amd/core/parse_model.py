@@ -44,6 +44,7 @@ class YoloModel:
         self.low_latency_f16 = False
         self.stem_fusion_f16 = 0
         self.dtype = None     # None: fp32 (set_dtype)
+        self.i8_calibration = None   # path of the activation scales an "i8" plan needs (set_i8_calibration)
 
     # lazily create the device object so that building/inspecting a model works without a GPU
     def _device_net(self):
@@ -56,6 +57,8 @@ class YoloModel:
                 self._net.set_low_latency_f16(True)
             if self.stem_fusion_f16:
                 self._net.set_stem_fusion_f16(self.stem_fusion_f16)
+            if self.i8_calibration:
+                self._net.load_calibration(self.i8_calibration)
             if self.dtype is not None:
                 self._net.set_dtype(self.dtype)
             if self._weights is not None:
@@ -86,11 +89,19 @@ class YoloModel:
 
     def set_dtype(self, dtype):
         """Conv arithmetic of the plans (runtime.Net.set_dtype): None or "f32" (default), "bf16", "f16" -- 16-bit activations and
-        weights on the matrix cores, fp32 accumulation, fp32 images in and fp32 grids out -- or a plane-split mode."""
+        weights on the matrix cores, fp32 accumulation, fp32 images in and fp32 grids out -- a plane-split mode, or "i8": calibrated
+        int8 from the first conv that qualifies on (set_i8_calibration first: the plan needs the activation scales)."""
         from ..runtime import Net
         self.dtype = Net._dtype_arg(dtype)
         if self._net is not None:
             self._net.set_dtype(self.dtype)
+
+    def set_i8_calibration(self, path):
+        """The calibration file (tools/calibrate_i8.py; runtime.Net.save_calibration) whose activation scales dtype "i8" plans with;
+        None: none.  A file made for another graph is refused when the device net reads it."""
+        self.i8_calibration = path or None
+        if self._net is not None and self.i8_calibration:
+            self._net.load_calibration(self.i8_calibration)
 
     def set_weights_dict(self, weights):
         self._weights = weights

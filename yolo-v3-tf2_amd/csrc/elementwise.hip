@@ -112,4 +112,46 @@ hipError_t launch_to_f32(int dtype, const void *src, float *dst, size_t npix, in
     return hipGetLastError();
 }
 
+// ---- int8 plans: the boundary copy of a tensor written before the cut (fp16 -> int8) and a stored int8 net output -> fp32 ----
+// q = clamp(rintf((float)x * inv_s), -127, 127): sixteen values per thread, two 16-byte loads and one 16-byte store
+__global__ __launch_bounds__(256) void quantize16_to_i8(const u32x4 *x, u32x4 *y, size_t n16, float inv_s)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) {
+        const u32x4 a = x[2 * i], b = x[2 * i + 1];
+        u32x4 out;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const unsigned w0 = k < 2 ? a[2 * k] : b[2 * k - 4], w1 = k < 2 ? a[2 * k + 1] : b[2 * k - 3];
+            const float v[4] = {f16lo(w0), f16hi(w0), f16lo(w1), f16hi(w1)};
+            unsigned w = 0;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) w |= ((unsigned)(int)fminf(fmaxf(rintf(v[j] * inv_s), -127.0f), 127.0f) & 0xffu) << (8 * j);
+            out[k] = w;
+        }
+        y[i] = out;
+    }
+}
+
+hipError_t launch_quantize16_to_i8(const void *src_f16, void *dst_i8, size_t n, float inv_s, hipStream_t s)
+{
+    if ((n & 15) || ((uintptr_t)src_f16 & 15) || ((uintptr_t)dst_i8 & 15)) return hipErrorInvalidValue;
+    const size_t n16 = n >> 4;
+    const unsigned blocks = (unsigned)((n16 + 255) / 256 < 4096 ? (n16 + 255) / 256 : 4096);
+    hipLaunchKernelGGL(quantize16_to_i8, dim3(blocks ? blocks : 1), dim3(256), 0, s, static_cast<const u32x4 *>(src_f16),
+                       static_cast<u32x4 *>(dst_i8), n16, inv_s);
+    return hipGetLastError();
+}
+
+__global__ __launch_bounds__(256) void i8_to_f32(const signed char *x, float *y, size_t n, float scale)
+{
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = (float)x[i] * scale;
+}
+
+hipError_t launch_i8_to_f32(const void *src_i8, float *dst, size_t n, float scale, hipStream_t s)
+{
+    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    hipLaunchKernelGGL(i8_to_f32, dim3(blocks ? blocks : 1), dim3(256), 0, s, static_cast<const signed char *>(src_i8), dst, n, scale);
+    return hipGetLastError();
+}
+
 }  // namespace y3

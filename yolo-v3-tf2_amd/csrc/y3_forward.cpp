@@ -37,18 +37,28 @@ struct Slice {
     const Forward &f;
     int b0, nb, lane;
     hipStream_t s;
-    const y3::ConvFamily &fam = y3::family_of(net);
 
     size_t img_elems(int t) const { return (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels; }
     // element size: head grids are always fp32; the image batch is fp32 when the Cin = 3 first-layer kernel reads it
-    // (a model whose input feeds an MFMA conv directly hands bf16 in bf16 mode, fp16 in fp16 mode); everything else follows the plan
+    // (a model whose input feeds an MFMA conv directly hands bf16 in bf16 mode, fp16 in fp16 and int8 mode); everything else follows the
+    // plan, per tensor (an int8 plan: fp16 before its cut, int8 behind it)
     size_t elem_bytes(int t) const
     {
         if (net->out_slot[t] >= 0) return 4;
-        if (t == net->input_tensor) return net->tensors[t].channels != 3 ? fam.elem_bytes : 4;
-        return fam.elem_bytes;
+        if (t == net->input_tensor && net->tensors[t].channels == 3) return 4;
+        return net->telem[t];
     }
     size_t bytes(int t) const { return (size_t)nb * img_elems(t) * elem_bytes(t); }
+    // an int8 conv's view of operand t: the int8 copy of a tensor that crosses the cut, else the tensor itself (int8 in the arena)
+    bool crosses(int t) const { return t >= 0 && net->tq8[t] != nullptr; }
+    void *ptr_q(int t) const { return static_cast<char *>(net->tq8[t]) + (size_t)b0 * img_elems(t); }
+    // the int8 copy of tensor t for this slice's images: q = clamp(rintf((float)x * (1 / s)))
+    y3_status quantize_crossing(int t) const
+    {
+        hipError_t e = y3::launch_quantize16_to_i8(ptr(t), ptr_q(t), (size_t)nb * img_elems(t), 1.0f / net->tscale[t], s);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "int8 copy of tensor %d: %s", t, hipGetErrorString(e));
+        return Y3_OK;
+    }
 
     void *ptr(int t) const
     {
@@ -73,13 +83,19 @@ struct Slice {
     {
         const ConvSlot &c = net->convs[conv];
         const y3_conv_desc &d = c.d;
+        const y3::ConvFamily &fam = y3::family_of_conv(net, conv);
+        const bool i8 = y3::conv_is_i8(net, conv);
+        auto rd = [&](int t) { return i8 && crosses(t) ? ptr_q(t) : ptr(t); };
+        auto rd_bytes = [&](int t) { return i8 && crosses(t) ? (size_t)nb * img_elems(t) : bytes(t); };
         y3::ConvArgs a{};
-        a.src0 = ptr(d.src0);
-        a.src1 = ptr(d.src1);
+        a.src0 = rd(d.src0);
+        a.src1 = rd(d.src1);
         a.wpk = c.*fam.w;
-        a.scale = c.scale_dev;
+        a.scale = i8 ? c.sc_i8_dev : c.scale_dev;   // int8: (s_in * s_w[c]) * bn_scale[c]
         a.shift = c.shift_dev;
-        a.residual = ptr(d.residual);
+        a.residual = rd(d.residual);
+        a.q_res = c.q_res;
+        a.q_inv = c.q_inv;
         a.dst = ptr(d.dst);
         a.B = nb;
         a.H = net->height / d.in_div;
@@ -97,8 +113,8 @@ struct Slice {
         a.leaky = d.leaky;
         a.M = nb * a.Ho * a.Wo;
         a.K = c.K;
-        a.src0_bytes = (unsigned)bytes(d.src0);
-        a.src1_bytes = d.src1 >= 0 ? (unsigned)bytes(d.src1) : 0;
+        a.src0_bytes = (unsigned)rd_bytes(d.src0);
+        a.src1_bytes = d.src1 >= 0 ? (unsigned)rd_bytes(d.src1) : 0;
         a.w_bytes = (unsigned)((size_t)a.CoutPad * c.K * fam.elem_bytes);
         a.dst_bytes = (unsigned)bytes(d.dst);
         a.n_cus = net->n_cus;
@@ -119,6 +135,7 @@ struct Slice {
     y3_status launch_stem(const y3::ConvArgs &a1) const
     {
         const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[1].index];
+        const y3::ConvFamily &fam = y3::family_of_conv(net, net->ops[1].index);   // an int8 plan: the fp16 plans' stem, before the cut
         y3::StemArgs sa{};
         sa.img = static_cast<const float *>(ptr(c0.d.src0));
         sa.w0 = c0.*fam.w0_stem;
@@ -158,10 +175,11 @@ struct Slice {
     {
         const int conv = net->ops[oi].index;
         const ConvSlot &c = net->convs[conv];
+        const y3::ConvFamily &fam = y3::family_of_conv(net, conv);
         hipError_t e;
         switch (ch.kind) {
             case y3::ConvKind::Stem: return launch_stem(a);
-            case y3::ConvKind::First: e = y3::launch_conv_first(a, static_cast<const float *>(c.w_dev), net->dtype, s); break;
+            case y3::ConvKind::First: e = y3::launch_conv_first(a, static_cast<const float *>(c.w_dev), y3::dtype_of_conv(net, conv), s); break;
             case y3::ConvKind::HeadDecodeF32: e = y3::launch_conv_head_decode_f32(a, s); break;
             case y3::ConvKind::SplitK:
                 if (lane >= net->split_ws_lanes) return fail(Y3_ERR_STATE, "conv %d: no split-K workspace for lane %d", conv, lane);
@@ -203,6 +221,9 @@ struct Slice {
             HIP_TRY(hipEventCreate(&ev0));
             HIP_TRY(hipEventCreate(&ev1));
         }
+        // int8 plans: an input handed over as fp16 that an int8 conv reads gets its int8 copy before the first op ...
+        if (op_begin == 0 && crosses(net->input_tensor))
+            if (y3_status st = quantize_crossing(net->input_tensor); st != Y3_OK) return st;
         for (int oi = op_begin; oi < op_end; ++oi) {
             const Op &o = net->ops[oi];
             if (o.kind != 0) {
@@ -216,23 +237,30 @@ struct Slice {
             a.xcd_gn = ch.xcd_gn;
             if (ch.kind == y3::ConvKind::InStem) {   // runs inside conv1's launch (fused stem)
                 if (f.ms_out && o.index < f.n_ms) f.ms_out[o.index] = 0.0f;
-                continue;
+            } else {
+                if (f.ms_out) HIP_TRY(hipEventRecord(ev0, s));
+                if (y3_status st = launch_conv(oi, a, ch); st != Y3_OK) return st;
+                if (f.ms_out) {
+                    HIP_TRY(hipEventRecord(ev1, s));
+                    HIP_TRY(hipEventSynchronize(ev1));
+                    float ms = 0;
+                    HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
+                    if (o.index < f.n_ms) f.ms_out[o.index] = ms;
+                }
             }
-            if (f.ms_out) HIP_TRY(hipEventRecord(ev0, s));
-            if (y3_status st = launch_conv(oi, a, ch); st != Y3_OK) return st;
-            if (f.ms_out) {
-                HIP_TRY(hipEventRecord(ev1, s));
-                HIP_TRY(hipEventSynchronize(ev1));
-                float ms = 0;
-                HIP_TRY(hipEventElapsedTime(&ms, ev0, ev1));
-                if (o.index < f.n_ms) f.ms_out[o.index] = ms;
-            }
+            // ... and a tensor written before the cut that an int8 conv reads gets its copy behind the op that wrote it
+            const int dst = net->convs[o.index].d.dst;
+            if (crosses(dst))
+                if (y3_status st = quantize_crossing(dst); st != Y3_OK) return st;
         }
         for (int k = 0; k < 3 && op_end == (int)net->ops.size(); ++k) {
             const int t = net->outputs[k];
             if (!net->staged[t]) continue;
             const size_t npix = (size_t)nb * rows(net, t) * cols(net, t);
-            hipError_t e = y3::launch_to_f32(net->dtype, ptr(t), f.grids[k] + (size_t)b0 * img_elems(t), npix, net->tensors[t].channels, s);
+            float *out = f.grids[k] + (size_t)b0 * img_elems(t);
+            hipError_t e = net->dtype != Y3_DTYPE_I8 ? y3::launch_to_f32(net->dtype, ptr(t), out, npix, net->tensors[t].channels, s)
+                           : net->telem[t] == 1      ? y3::launch_i8_to_f32(ptr(t), out, npix * net->tensors[t].channels, net->tscale[t], s)
+                                                     : y3::launch_to_f32(Y3_DTYPE_F16, ptr(t), out, npix, net->tensors[t].channels, s);
             if (e != hipSuccess) return fail(Y3_ERR_HIP, "output %d conversion: %s", k, hipGetErrorString(e));
         }
         if (f.ms_out) {
@@ -463,11 +491,30 @@ try {
     if (!dst_dev) return Y3_OK;
     if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
     Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
-    hipError_t e = y3::launch_to_f32(net->dtype, net->tdev[t], dst_dev, npix, net->tensors[t].channels, (hipStream_t)stream);
+    // an int8 plan: (float)q * s behind the cut, the fp16 value before it
+    hipError_t e = net->dtype != Y3_DTYPE_I8 ? y3::launch_to_f32(net->dtype, net->tdev[t], dst_dev, npix, net->tensors[t].channels, (hipStream_t)stream)
+                   : net->telem[t] == 1      ? y3::launch_i8_to_f32(net->tdev[t], dst_dev, n, net->tscale[t], (hipStream_t)stream)
+                                             : y3::launch_to_f32(Y3_DTYPE_F16, net->tdev[t], dst_dev, npix, net->tensors[t].channels, (hipStream_t)stream);
     if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
     return Y3_OK;
 }
 Y3_CATCH("y3_net_read_tensor")
+
+y3_status y3_net_read_tensor_i8(y3_net *net, int t, int batch, int8_t *dst_dev, size_t *n_elems, void *stream)
+try {
+    if (!net || t < 0 || t >= (int)net->tensors.size() || !net->height || batch <= 0 || batch > net->max_batch)
+        return fail(Y3_ERR_INVALID, "y3_net_read_tensor_i8: bad argument");
+    const size_t n = (size_t)batch * rows(net, t) * cols(net, t) * net->tensors[t].channels;
+    if (n_elems) *n_elems = n;
+    if (!dst_dev) return Y3_OK;
+    // the int8 copy of a tensor that crosses the cut, else an int8 tensor of the arena
+    const void *src = net->dtype != Y3_DTYPE_I8 ? nullptr : net->tq8[t] ? net->tq8[t] : (net->telem[t] == 1 && net->out_slot[t] < 0) ? net->tdev[t] : nullptr;
+    if (!src) return fail(Y3_ERR_STATE, "y3_net_read_tensor_i8: tensor %d is not held as int8 in this plan", t);
+    Y3_ENTER_DEVICE(net);
+    HIP_TRY(hipMemcpyAsync(dst_dev, src, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_read_tensor_i8")
 
 // ------------------------------------------------------------------------------------------ forward + decode
 namespace {
@@ -477,7 +524,7 @@ namespace {
 bool heads_can_decode(const y3_net *net)
 {
     static const bool off = [] { const char *e = getenv("Y3_FUSE_DECODE"); return e && e[0] == '0'; }();
-    if (off || net->nclasses <= 0 || (net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16 && net->dtype != Y3_DTYPE_F16)) return false;
+    if (off || net->nclasses <= 0 || (net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16 && net->dtype != Y3_DTYPE_F16 && net->dtype != Y3_DTYPE_I8)) return false;
     if (net->keep_all || net->early_ops > 0 || 3 * (5 + net->nclasses) > 256) return false;
     for (int k = 0; k < 3; ++k) {
         const int t = net->outputs[k];

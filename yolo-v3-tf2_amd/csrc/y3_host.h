@@ -79,6 +79,12 @@ struct ConvSlot {
     void *wf16_dev = nullptr;  // same, IEEE fp16 rounded to nearest even on the host (Y3_DTYPE_F16 plans; not for the first layer)
     float *scale_dev = nullptr;
     float *shift_dev = nullptr;
+    // int8 plans (Y3_DTYPE_I8; not for the first layer): the raw weights quantised per output channel, packed [CoutPad64][K] int8, with
+    // their scales s_w[c] and the BN scale on the host; sc_i8_dev = (s_in * s_w[c]) * bn_scale[c], formed when the plan knows s_in
+    void *wi8_dev = nullptr;
+    std::vector<float> sw_host, bn_scale_host;   // [CoutPad64]
+    float *sc_i8_dev = nullptr;                  // [CoutPad64]
+    float q_res = 0.0f, q_inv = 0.0f;            // (at plan time) scale of the int8 shortcut tensor; 1 / scale of the int8 output tensor
 };
 
 struct Op {
@@ -138,6 +144,17 @@ struct y3_net {
     std::vector<size_t> tbytes;    // bytes at max_batch
     std::vector<size_t> tblock;    // size of the arena block the tensor lives in
     std::vector<void *> blocks;    // distinct hipMalloc'ed blocks
+    // int8 plans.  act_scale: y3_net_set_act_scales, one fp32 scale per tensor, <= 0 unset (read by y3_net_plan).  i8_first_conv: c*, the
+    // first conv slot that runs in int8 (-1: not an int8 plan); the convs before it launch what an fp16 plan launches.  telem: bytes per
+    // element of every tensor in the arena (every plan: the mode's; int8 plans: 2 before the cut, 1 behind it).  tq8: the int8 copy of a
+    // tensor written before the cut (or handed in) and read behind it (tcross: such a tensor, decided before the arena is placed), image i
+    // at i * image elements; tscale: the scales the plan took.
+    std::vector<float> act_scale;
+    int i8_first_conv = -1;
+    std::vector<unsigned char> telem;
+    std::vector<char> tcross;
+    std::vector<void *> tq8;
+    std::vector<float> tscale;
 };
 
 inline int rows(const y3_net *n, int t) { return n->height / n->tensors[t].div; }
@@ -188,6 +205,10 @@ struct ConvFamily {
 };
 const ConvFamily *conv_family(int dtype);   // null: no such mode
 inline const ConvFamily &family_of(const y3_net *net) { return *conv_family(net->dtype); }   // the planned mode's (fp32 before the first plan)
+// ... of conv `slot`: an int8 plan runs the convs before its cut as an fp16 plan does
+inline bool conv_is_i8(const y3_net *net, int slot) { return net->dtype == Y3_DTYPE_I8 && net->i8_first_conv >= 0 && slot >= net->i8_first_conv; }
+inline int dtype_of_conv(const y3_net *net, int slot) { return net->dtype != Y3_DTYPE_I8 || conv_is_i8(net, slot) ? net->dtype : (int)Y3_DTYPE_F16; }
+inline const ConvFamily &family_of_conv(const y3_net *net, int slot) { return *conv_family(dtype_of_conv(net, slot)); }
 
 // What conv op `oi` launches for the rows of one call.  InStem: nothing of its own, it runs inside the Stem launch of op 1.
 enum class ConvKind { First, Stem, InStem, HeadDecodeF32, Mfma, SplitK };
@@ -208,6 +229,10 @@ bool stem_conv2_applicable(const y3_net *net);
 void resolve_stem(y3_net *net);   // stem_fused / stem_conv2 of a planned net from the planned mode's switch and the graph
 bool output_staged(const y3_net *net, int t);
 y3_status resolve_splits(y3_net *net);
+// int8 plans: the cut, the element size of every tensor and the scales the plan needs (y3_net_plan, before the arena is placed) ...
+y3_status resolve_i8(y3_net *net);
+// ... and the epilogue scales of int8 conv `slot` on the device, once its weights are loaded (y3_net_plan; y3_net_set_conv_weights on a planned net)
+y3_status upload_i8_scales(y3_net *net, int slot);
 void free_plan(y3_net *net);
 
 // y3_net_detect scratch for `batch` images: grid sizes {gh, gw}, boxes per image, byte offsets of the parts and their total

@@ -42,6 +42,9 @@ struct ConvArgs {
     unsigned long long *clk_stamps;   // [4]
     int n_cus;             // compute units of the net's device, read once by y3_net_plan: sizes the grids of the persistent kernels (conv_res_*.hip)
     int device;            // the net's device index (the launch goes there: Y3_ENTER_DEVICE); -1 = not known, launchers ask the runtime
+    // int8 convs only (conv_i8.hip; `scale` is then (s_in * s_w[c]) * bn_scale[c]): the scale of the int8 shortcut tensor, and 1 / the scale
+    // of the int8 output tensor.  Last in the struct: the kernel arguments of every other launch keep their offsets.
+    float q_res, q_inv;
 };
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel instantiation, device): the attribute belongs to the
@@ -182,6 +185,15 @@ hipError_t launch_conv_res_bf16(const ConvArgs &a, hipStream_t s);
 hipError_t launch_conv_f16(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
 hipError_t launch_conv_f16_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s);
 hipError_t launch_conv_res_f16(const ConvArgs &a, hipStream_t s);
+
+// int8 path (conv_i8.hip; Y3_DTYPE_I8): int8 operands, exact i32 accumulate, the ids of the bf16 table for the tiles that have an int8 form
+// (LDS-DMA, 128-byte rows: 8, 10, 11, 12, 17, 19 and 24, 26, 27, 29 on the 16x16x64 form); bk = 128 channels.  out_f32: a.dst is an fp32 grid.
+TileInfo conv_i8_tile_info(int tile);
+bool conv_i8_tile_built(int tile);
+hipError_t launch_conv_i8(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
+// n fp16 values (n % 16 == 0) -> int8: q = clamp(rintf((float)x * inv_s), -127, 127); and int8 -> fp32: (float)q * s  (elementwise.hip)
+hipError_t launch_quantize16_to_i8(const void *src_f16, void *dst_i8, size_t n, float inv_s, hipStream_t s);
+hipError_t launch_i8_to_f32(const void *src_i8, float *dst, size_t n, float scale, hipStream_t s);
 
 // fp32-accurate path on the bf16 matrix cores, three bf16 planes per value (conv_f32x3.hip)
 static constexpr int X3_TILE_COUNT = 34;

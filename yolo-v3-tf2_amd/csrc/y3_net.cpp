@@ -168,6 +168,22 @@ std::vector<unsigned short> pack_planes(const std::vector<float> &pk, int K, int
     return px;
 }
 
+// int8 plans: [rows][K] int8 of the raw [CoutPad][K] weights pk, symmetric per output channel: s_w[n] = absmax_n / 127 (1 for an all-zero
+// channel), q = clamp(rint(w / s_w[n]), -127, 127) with a true fp32 division and round to nearest even; rows past Cout zero, their scale 1
+std::vector<signed char> pack_i8(const std::vector<float> &pk, int K, int cout, int rows, std::vector<float> &sw)
+{
+    std::vector<signed char> q((size_t)rows * K, 0);
+    sw.assign(rows, 1.0f);
+    for (int n = 0; n < cout; ++n) {
+        float mx = 0.0f;
+        for (int k = 0; k < K; ++k) mx = std::max(mx, fabsf(pk[(size_t)n * K + k]));
+        if (mx > 0.0f && std::isfinite(mx)) sw[n] = mx / 127.0f;
+        for (int k = 0; k < K; ++k)
+            q[(size_t)n * K + k] = (signed char)std::min(127.0f, std::max(-127.0f, nearbyintf(pk[(size_t)n * K + k] / sw[n])));
+    }
+    return q;
+}
+
 // hipMalloc the device buffer on first use, then copy the host vector into it
 template <class P, class T>
 hipError_t upload(P *&dev, const std::vector<T> &host)
@@ -234,6 +250,16 @@ int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16
     if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
     if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
     return first_reaching(n32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+}
+
+// int8 plans: the bf16 chooser's tile where it has an int8 form (the LDS-DMA tiles with 128-byte rows, both MFMA shapes); where it has
+// none (a Cout that only the 32-wide register-staged tile divides) the 64-wide LDS-DMA tiles over Cout padded to 64
+int choose_tile_i8(const ConvSlot &c, long long M, long long M_plan, bool arena_out)
+{
+    const int t = choose_tile_bf16(c, M, M_plan, arena_out);
+    if (y3::conv_i8_tile_built(t) && fits(y3::conv_i8_tile_info(t), c, c.cout_pad64)) return t;
+    static constexpr int n64[] = {10, 11};
+    return first_reaching(n64, y3::conv_i8_tile_info, c, c.cout_pad64, M, 512);
 }
 
 // channels per K chunk of a 3x3 fp32 conv when the caller has not chosen (y3_net_set_k_chunk(-1)); Y3_K_CHUNK overrides (tools)
@@ -461,10 +487,21 @@ constexpr y3::ConvFamily X2_FAMILY = {
     "y3_net_set_tile_x2: bad argument", "y3_net_set_tile_x2: tile does not fit this conv", "y3_net_set_tile_x2: tile does not fit this conv", -1, nullptr,
     &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
-// "forced tile, else the family's chooser": the tile part of the launch decision
+// int8 plans (Y3_DTYPE_I8): the convs from the cut on (y3_plan.cpp, resolve_i8).  The bf16 family's tile ids and forced-tile field (a
+// forced tile without an int8 form, or one that does not fit, leaves the conv to the chooser), the bf16 refine rule, int8 weights over Cout
+// padded to 64; the fused stem is the fp16 plans' (it runs before the cut, behind y3_net_set_stem_fusion_f16); no split form.
+constexpr y3::ConvFamily I8_FAMILY = {
+    y3::BF16_TILE_COUNT, y3::conv_i8_tile_info, y3::conv_i8_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad64,
+    BF16_FAMILY.bad, BF16_FAMILY.retired, BF16_FAMILY.misfit, -1, nullptr,
+    &ConvSlot::wi8_dev, 1, choose_tile_i8, y3::launch_conv_i8, refine_bf16, y3::launch_conv_stem_f16, &ConvSlot::w0norm_dev, &ConvSlot::scale0norm_dev,
+    &y3_net::stem_mode_f16, nullptr};
+
+// "forced tile, else the family's chooser": the tile part of the launch decision.  (A forced tile was checked by its setter against the
+// family it was forced for; an int8 plan shares the bf16 field, so the check is made again here.)
 int family_tile(const y3::ConvFamily &f, const ConvSlot &c, long long M, long long M_plan, bool arena_out)
 {
-    return c.*f.tile >= 0 ? c.*f.tile : f.choose(c, M, M_plan, arena_out);
+    const int t = c.*f.tile;
+    return t >= 0 && f.built(t) && fits(f.info(t), c, c.*f.cout_pad) ? t : f.choose(c, M, M_plan, arena_out);
 }
 
 }  // namespace
@@ -477,6 +514,7 @@ const y3::ConvFamily *y3::conv_family(int dtype)
         case Y3_DTYPE_F32X3: return &X3_FAMILY;
         case Y3_DTYPE_F32X2: return &X2_FAMILY;
         case Y3_DTYPE_F16: return &F16_FAMILY;
+        case Y3_DTYPE_I8: return &I8_FAMILY;
         default: return nullptr;
     }
 }
@@ -493,7 +531,7 @@ y3::ConvChoice y3::choose_conv(const y3_net *net, int oi, const ConvArgs &a)
     else if (net->stem_fused && oi == 1) ch.kind = ConvKind::Stem;
     else if (c.first_layer) ch.kind = ConvKind::First;
     if (ch.kind != ConvKind::Mfma) return ch;
-    const ConvFamily &f = family_of(net);
+    const ConvFamily &f = family_of_conv(net, net->ops[oi].index);   // an int8 plan: fp16 before the cut, int8 from it on
     ch.tile = family_tile(f, c, a.M, (long long)net->max_batch * a.Ho * a.Wo, net->out_slot[c.d.dst] < 0);
     if (f.refine) f.refine(net, c, a, ch);
     return ch;
@@ -506,7 +544,7 @@ y3::ConvChoice y3::choose_conv_planned(const y3_net *net, int oi)
     a.Ho = net->height / c.d.out_div;
     a.Wo = net->width / c.d.out_div;
     a.M = net->max_batch * a.Ho * a.Wo;
-    a.CoutPad = c.*family_of(net).cout_pad;
+    a.CoutPad = c.*family_of_conv(net, net->ops[oi].index).cout_pad;
     return choose_conv(net, oi, a);
 }
 
@@ -745,7 +783,7 @@ void y3_net_destroy(y3_net *net)
         }
     }
     for (ConvSlot &c : net->convs)
-        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, (void *)c.w0norm_dev, (void *)c.scale0norm_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev})
+        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, (void *)c.w0norm_dev, (void *)c.scale0norm_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev, c.wi8_dev, (void *)c.sc_i8_dev})
             if (p) (void)hipFree(p);
     delete net;
 }
@@ -796,10 +834,14 @@ try {
         c.x2_ok = std::all_of(pk_scaled.begin(), pk_scaled.end(), [](float x) { return fabsf(x) < 65504.0f; });
         HIP_TRY(upload(c.wx3_dev, pack_planes<3>(pk, K, d.cout, CP64, split_bf16x3)));         // unscaled, like the bf16 copy
         HIP_TRY(upload(c.wx2_dev, pack_planes<2>(pk_scaled, K, d.cout, CP64, split_f16x2)));   // BN-scaled, like the fp32 copy
+        // the int8 copy: the raw weights quantised per output channel (BN stays in the epilogue); their scales stay on the host for the plan
+        HIP_TRY(upload(c.wi8_dev, pack_i8(pk, K, d.cout, CP64, c.sw_host)));
+        c.bn_scale_host = scale;
     }
     HIP_TRY(upload(c.scale_dev, scale));
     HIP_TRY(upload(c.shift_dev, shift));
     c.loaded = true;
+    if (y3::conv_is_i8(net, slot)) return y3::upload_i8_scales(net, slot);   // a planned int8 net: this conv's epilogue scales follow its weights
     return Y3_OK;
 }
 Y3_CATCH("y3_net_set_conv_weights")
@@ -913,6 +955,26 @@ try {
     return Y3_OK;
 }
 Y3_CATCH("y3_net_keep_activations")
+
+y3_status y3_net_set_act_scales(y3_net *net, const float *scales, int n_tensors)
+try {
+    if (!net || !scales) return fail(Y3_ERR_INVALID, "y3_net_set_act_scales: null argument");
+    if (n_tensors != (int)net->tensors.size())
+        return fail(Y3_ERR_INVALID, "y3_net_set_act_scales: %d scales for a net of %zu tensors", n_tensors, net->tensors.size());
+    for (int t = 0; t < n_tensors; ++t)
+        if (scales[t] > 0.0f && !std::isfinite(scales[t])) return fail(Y3_ERR_INVALID, "y3_net_set_act_scales: the scale of tensor %d is not finite", t);
+    net->act_scale.assign(scales, scales + n_tensors);
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_act_scales")
+
+float y3_net_get_act_scale(const y3_net *net, int tensor_id)
+{
+    if (!net || tensor_id < 0 || tensor_id >= (int)net->act_scale.size() || !(net->act_scale[tensor_id] > 0.0f)) return 0.0f;
+    return net->act_scale[tensor_id];
+}
+
+int y3_net_i8_first_conv(const y3_net *net) { return (net && net->height && net->dtype == Y3_DTYPE_I8) ? net->i8_first_conv : -1; }
 
 int y3_net_get_split_k(const y3_net *net, int slot) { return split_in_force(F32_FAMILY, net, slot); }
 

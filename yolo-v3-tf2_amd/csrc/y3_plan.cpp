@@ -17,6 +17,7 @@ void y3::free_plan(y3_net *n)
     for (void *p : n->blocks) (void)hipFree(p);
     n->blocks.clear();
     n->tdev.assign(n->tensors.size(), nullptr);
+    n->tq8.assign(n->tensors.size(), nullptr);   // the int8 copies were blocks
 }
 
 // forked streams / events of the concurrent sub-batches: created at plan time so that a forward enqueues work only
@@ -66,6 +67,75 @@ static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const
         net->tdev[t] = pool[pick].p;
         net->tblock[t] = pool[pick].bytes;
     }
+    return Y3_OK;
+}
+
+// ---- int8 plans -------------------------------------------------------------------------------------------------------------------
+// The cut c*: the first conv in op order such that it and every conv after it has Cin % 128 == 0 (both parts of a concat), and
+// Cout % 16 == 0 unless it writes an fp32 grid itself.  From c* on the convs run in int8; before it the plan is an fp16 plan.  A tensor
+// written before the cut (or handed in) and read behind it gets an int8 copy (tq8) from one elementwise launch.
+y3_status y3::resolve_i8(y3_net *net)
+{
+    const int nt = (int)net->tensors.size(), nc = (int)net->convs.size();
+    net->i8_first_conv = -1;
+    net->telem.assign(nt, (unsigned char)conv_family(net->dtype)->elem_bytes);
+    net->tq8.assign(nt, nullptr);
+    net->tcross.assign(nt, 0);
+    net->tscale.assign(nt, 0.0f);
+    if (net->dtype != Y3_DTYPE_I8) return Y3_OK;
+    int cut = nc;
+    for (int i = nc - 1; i >= 0; --i) {   // conv slots are in op order
+        const ConvSlot &c = net->convs[i];
+        const y3_conv_desc &d = c.d;
+        const bool ok = !c.first_layer && d.cin % 128 == 0 && (d.src1 < 0 || (d.c0 % 128 == 0 && (d.cin - d.c0) % 128 == 0)) &&
+                        (net->out_slot[d.dst] >= 0 || d.cout % 16 == 0);
+        if (!ok) break;
+        cut = i;
+    }
+    if (cut >= nc)
+        return fail(Y3_ERR_INVALID, "y3_net_plan: no conv of this graph qualifies for int8 (the last conv needs Cin %% 128 == 0 and, unless it writes an fp32 output, Cout %% 16 == 0)");
+    net->i8_first_conv = cut;
+    std::fill(net->telem.begin(), net->telem.end(), (unsigned char)2);   // before the cut: an fp16 plan's tensors
+    std::vector<char> behind(nt, 0);                                     // written by a conv behind the cut
+    for (int i = cut; i < nc; ++i) behind[net->convs[i].d.dst] = 1;
+    auto scale_of = [&](int t) { return t < (int)net->act_scale.size() && net->act_scale[t] > 0.0f ? net->act_scale[t] : 0.0f; };
+    auto need = [&](int t) -> y3_status {
+        if (!(scale_of(t) > 0.0f))
+            return fail(Y3_ERR_STATE, "y3_net_plan: an int8 plan needs the scale of tensor %d (y3_net_set_act_scales; Net.calibrate_i8)", t);
+        net->tscale[t] = scale_of(t);
+        return Y3_OK;
+    };
+    for (int i = cut; i < nc; ++i) {
+        ConvSlot &c = net->convs[i];
+        const y3_conv_desc &d = c.d;
+        for (int t : {d.src0, d.src1, d.residual}) {
+            if (t < 0) continue;
+            if (y3_status st = need(t); st != Y3_OK) return st;
+            if (!behind[t]) net->tcross[t] = 1;   // its int8 copy is allocated once the arena is placed
+        }
+        if (d.src1 >= 0 && scale_of(d.src0) != scale_of(d.src1))
+            return fail(Y3_ERR_INVALID, "y3_net_plan: conv %d concatenates tensors %d and %d with different int8 scales (%g, %g); they must be equal",
+                        i, d.src0, d.src1, (double)scale_of(d.src0), (double)scale_of(d.src1));
+        c.q_res = d.residual >= 0 ? scale_of(d.residual) : 0.0f;
+        c.q_inv = 0.0f;
+        if (net->out_slot[d.dst] < 0) {   // stores int8
+            if (y3_status st = need(d.dst); st != Y3_OK) return st;
+            net->telem[d.dst] = 1;
+            c.q_inv = 1.0f / scale_of(d.dst);
+        }
+    }
+    return Y3_OK;
+}
+
+y3_status y3::upload_i8_scales(y3_net *net, int slot)
+{
+    ConvSlot &c = net->convs[slot];
+    if (!c.loaded || c.sw_host.empty()) return Y3_OK;   // follows with the weights
+    const float s_in = net->tscale[c.d.src0];
+    std::vector<float> sc(c.cout_pad64);
+    for (int n = 0; n < c.cout_pad64; ++n) sc[n] = (s_in * c.sw_host[n]) * c.bn_scale_host[n];
+    if (!c.sc_i8_dev) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&c.sc_i8_dev), sc.size() * sizeof(float)));
+    HIP_TRY(hipMemcpy(c.sc_i8_dev, sc.data(), sc.size() * sizeof(float), hipMemcpyHostToDevice));
     return Y3_OK;
 }
 
@@ -160,12 +230,34 @@ try {
     }
     net->dense.assign(nt, 0);
     for (int t = 0; t < nt; ++t) net->dense[t] = (first[t] >= 0 && first[t] < net->early_ops) ? 1 : 0;
+    if (y3_status st = y3::resolve_i8(net); st != Y3_OK) {   // every plan: the element size per tensor; int8 plans: the cut and the scales
+        net->height = net->width = net->max_batch = 0;      // no plan
+        net->dtype = Y3_DTYPE_F32;
+        return st;
+    }
     for (int t = 0; t < nt; ++t) {
-        net->tbytes[t] = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels * y3::conv_family(dtype)->elem_bytes;
+        net->tbytes[t] = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels * net->telem[t];
         if (net->tbytes[t] >= 0xFFFFFFF0ull && first[t] >= 0)
             return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, net->tbytes[t]);
     }
     if (y3_status st = place_tensors(net, first, last); st != Y3_OK) return st;
+    for (int t = 0; t < nt; ++t) {   // int8 plans: the int8 copies of the tensors that cross the cut, blocks of their own
+        if (!net->tcross[t]) continue;
+        const size_t bytes = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels;
+        void *p = nullptr;
+        if (hipError_t e = hipMalloc(&p, bytes + 4096); e != hipSuccess) {
+            y3::free_plan(net);
+            return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) for the int8 copy of tensor %d failed: %s", bytes, t, hipGetErrorString(e));
+        }
+        net->blocks.push_back(p);
+        net->tq8[t] = p;
+    }
+    for (int i = 0; i < (int)net->convs.size(); ++i)
+        if (y3::conv_is_i8(net, i))
+            if (y3_status st = y3::upload_i8_scales(net, i); st != Y3_OK) {
+                y3::free_plan(net);
+                return st;
+            }
     if (y3_status st = ensure_lanes(net); st != Y3_OK) return st;
     {   // Y3_STEM_MODE (tools: same-process-tree A/B of the stem forms) overrides the default, not an explicit setter call
         static const int env = [] { const char *e = getenv("Y3_STEM_MODE"); return e ? atoi(e) : -1; }();

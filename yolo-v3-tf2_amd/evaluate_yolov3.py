@@ -99,7 +99,8 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     model = create_model(detect_config["model_config_file"], nclasses, anchors_table, min(thresholds),
                          detect_config["nms_iou_threshold"], detect_config["yolo_max_boxes"],
                          detect_config.get("input_weights_path"), weights)
-    model.model.set_dtype(detect_config.get("dtype"))     # optional key: f32 | bf16 | f16; absent: f32
+    model.model.set_i8_calibration(detect_config.get("i8_calibration"))   # optional key, needed with dtype i8: the file of tools/calibrate_i8.py
+    model.model.set_dtype(detect_config.get("dtype"))     # optional key: f32 | bf16 | f16 | i8; absent: f32
     model.model.set_stem_fusion_f16(detect_config.get("f16_fused_stem"))   # optional key, acts on dtype f16 only; absent: off
     net = model.model._device_net()
     if net.image_size != S or net.max_batch < batch_size:

@@ -102,10 +102,12 @@ class Inference:
         return (canvas_h, canvas_w), anchors_table
 
     def build(self, model_config_file, classes_name_file, anchors_file, input_weights_path, yolo_max_boxes,
-              nms_iou_threshold, nms_score_threshold, weights=None, low_latency=None, dtype=None, f16_fused_stem=None):
+              nms_iou_threshold, nms_score_threshold, weights=None, low_latency=None, dtype=None, f16_fused_stem=None,
+              i8_calibration=None):
         """low_latency (optional YAML key; None or absent: off): plan the network for latency at one to eight images -- the
         fp32 convs that leave most of the chip idle at such a batch are split along K (runtime.Net.set_low_latency).
-        dtype (optional YAML key: f32 | bf16 | f16; None or absent: f32): the conv arithmetic (runtime.Net.set_dtype).
+        dtype (optional YAML key: f32 | bf16 | f16 | i8; None or absent: f32): the conv arithmetic (runtime.Net.set_dtype).
+        i8_calibration (optional YAML key, needed with dtype i8): the file of activation scales tools/calibrate_i8.py wrote.
         f16_fused_stem (optional YAML key; None or absent: what self.f16_fused_stem says, off by default): with dtype f16, the first
         convs as the fused stem kernel (runtime.Net.set_stem_fusion_f16); without effect on any other dtype."""
         anchors_table = get_anchors(anchors_file).astype(np.float32)      # reference: inference.py:83
@@ -125,6 +127,7 @@ class Inference:
         else:
             model.load_weights(input_weights_path).expect_partial()
         model.set_low_latency(low_latency)
+        model.set_i8_calibration(i8_calibration)
         model.set_dtype(dtype)
         model.set_stem_fusion_f16(self.f16_fused_stem if f16_fused_stem is None else f16_fused_stem)
         print("weights loaded")
@@ -134,7 +137,7 @@ class Inference:
     def __call__(self, model_config_file, classes_name_file, anchors_file, input_weights_path, image_size,
                  input_data_source, images_dir, tfrecords_dir, batch_size, image_file_path, output_dir, yolo_max_boxes,
                  nms_iou_threshold, nms_score_threshold, bbox_color, font_size, display_result_images=None,
-                 save_model_path=None, weights=None, low_latency=None, dtype=None):
+                 save_model_path=None, weights=None, low_latency=None, dtype=None, i8_calibration=None):
         os.makedirs(output_dir, exist_ok=True)
         detections_text_list_outfile = f"{output_dir}/detect.txt"
         try:
@@ -143,7 +146,8 @@ class Inference:
             pass
         out = open(detections_text_list_outfile, "a")
         model, class_names = self.build(model_config_file, classes_name_file, anchors_file, input_weights_path,
-                                        yolo_max_boxes, nms_iou_threshold, nms_score_threshold, weights, low_latency, dtype)
+                                        yolo_max_boxes, nms_iou_threshold, nms_score_threshold, weights, low_latency, dtype,
+                                        i8_calibration=i8_calibration)
         self.detect_model = model    # the DetectModel of the last call (its .model is the YoloModel, ._device_net() the planned Net)
         results = []
         import torch

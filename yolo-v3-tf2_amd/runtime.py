@@ -196,7 +196,8 @@ class Net:
 
     def set_dtype(self, dtype):
         """The conv arithmetic of the plans this net makes for itself from now on (forward / detect re-plan when the batch
-        shape changes; plan() without a dtype): None or "f32", "bf16", "f16", "f32x3", "f32x2", or a _lib.Y3_DTYPE_* value.
+        shape changes; plan() without a dtype): None or "f32", "bf16", "f16", "f32x3", "f32x2", "i8" (needs the activation scales:
+        calibrate_i8 / load_calibration / set_act_scales), or a _lib.Y3_DTYPE_* value.
         A net already planned in another dtype is planned again, same batch and canvas."""
         dtype = self._dtype_arg(dtype)
         if self.max_batch and dtype != self.dtype:
@@ -352,12 +353,17 @@ class Net:
         through set_tile_bf16 (same kernels, same tile ids; no fp16 table is tuned or shipped)."""
         import json
         import os
-        tag = _lib.DTYPE_TAGS[_lib.Y3_DTYPE_BF16 if self.dtype == _lib.Y3_DTYPE_F16 else self.dtype]
+        sixteen = self.dtype in (_lib.Y3_DTYPE_F16, _lib.Y3_DTYPE_I8)
+        tag = _lib.DTYPE_TAGS[_lib.Y3_DTYPE_BF16 if sixteen else self.dtype]
         path = tuning_table_path(tag, self.max_batch, self.image_size)
         kind, fn = {_lib.Y3_DTYPE_F32: ("", self.lib.y3_net_set_tile), _lib.Y3_DTYPE_BF16: ("_bf16", self.lib.y3_net_set_tile_bf16),
                     _lib.Y3_DTYPE_F32X3: ("_x3", self.lib.y3_net_set_tile_x3),
                     _lib.Y3_DTYPE_F32X2: ("_x2", self.lib.y3_net_set_tile_x2),
-                    _lib.Y3_DTYPE_F16: ("_bf16", self.lib.y3_net_set_tile_bf16)}[self.dtype]
+                    _lib.Y3_DTYPE_F16: ("_bf16", self.lib.y3_net_set_tile_bf16),
+                    _lib.Y3_DTYPE_I8: ("_bf16", self.lib.y3_net_set_tile_bf16)}[self.dtype]
+        # an int8 plan: the convs before its cut run as an fp16 plan's and take the bf16 table like one (lanes included); the int8 convs
+        # are left to the library's heuristic (no int8 table is tuned or shipped)
+        i8_from = self.i8_first_conv() if self.dtype == _lib.Y3_DTYPE_I8 else len(self.conv_ops)
         forced = self.__dict__.get("_forced_tiles", {})
         table, lanes = {}, 1
         if os.path.exists(path) and not os.environ.get("Y3_NO_TUNING"):
@@ -369,7 +375,8 @@ class Net:
         for slot, o in enumerate(self.conv_ops):
             if o.cin == 3 or (kind, slot) in forced:
                 continue
-            check(fn(self._h, slot, int(table.get(self.conv_signature(o, self.image_size), -1))), f"y3_net_set_tile{kind}")
+            tile = int(table.get(self.conv_signature(o, self.image_size), -1)) if slot < i8_from else -1
+            check(fn(self._h, slot, tile), f"y3_net_set_tile{kind}")
 
     def grid_sizes(self, image_size=None):
         """Per head: g for an int image size, (gh, gw) for an (H, W) pair (default: what the net was planned with)."""
@@ -402,7 +409,8 @@ class Net:
             if images.dtype != torch.float16 or images.dim() != 5 or images.shape[3] != 2 or images.shape[4] != cin:
                 raise Y3Error(f"images must be float16 [B,S,S,2,{cin}] (split2_planes) in the two-plane mode")
         else:
-            want = torch.float32 if cin == 3 else {_lib.Y3_DTYPE_BF16: torch.bfloat16, _lib.Y3_DTYPE_F16: torch.float16}.get(self.dtype, torch.float32)
+            want = torch.float32 if cin == 3 else {_lib.Y3_DTYPE_BF16: torch.bfloat16, _lib.Y3_DTYPE_F16: torch.float16,
+                                                   _lib.Y3_DTYPE_I8: torch.float16}.get(self.dtype, torch.float32)
             if images.dtype != want or images.dim() != 4 or images.shape[3] != cin:
                 raise Y3Error(f"images must be {want} [B,S,S,{cin}]")
         B = self._plan_for(images)
@@ -459,6 +467,79 @@ class Net:
         check(self.lib.y3_net_read_tensor(self._h, tensor_id, batch, _dev(out), C.byref(n), _lib.stream_ptr()),
               "y3_net_read_tensor")
         return out
+
+    # -- int8 plans (include/y3.h, "int8 plans"; the scheme restated in quant.py) ----------------------------------------------------
+    def read_tensor_i8(self, tensor_id: int, batch: int) -> torch.Tensor:
+        """The raw bytes of an int8 tensor of the last forward of an int8 plan: a tensor behind the cut, or the int8 copy of one that
+        crosses it.  -> int8 [batch, h, w, C]."""
+        n = C.c_size_t()
+        check(self.lib.y3_net_read_tensor_i8(self._h, tensor_id, batch, None, C.byref(n), None), "y3_net_read_tensor_i8")
+        t = self.program.tensors[tensor_id]
+        out = torch.empty((batch, self.canvas[0] // t.div, self.canvas[1] // t.div, t.channels), dtype=torch.int8, device="cuda")
+        assert out.numel() == n.value
+        check(self.lib.y3_net_read_tensor_i8(self._h, tensor_id, batch, _dev(out), C.byref(n), _lib.stream_ptr()), "y3_net_read_tensor_i8")
+        return out
+
+    def set_act_scales(self, scales):
+        """One fp32 scale per tensor of the program (entries <= 0 or None: unset), read by the next plan() in "i8"."""
+        a = np.ascontiguousarray([0.0 if s is None else float(s) for s in scales], np.float32)
+        check(self.lib.y3_net_set_act_scales(self._h, _fptr(a), int(a.size)), "y3_net_set_act_scales")
+
+    def act_scales(self) -> List[float]:
+        """The scales in force, one per tensor; 0.0 where unset."""
+        return [float(self.lib.y3_net_get_act_scale(self._h, t)) for t in range(len(self.program.tensors))]
+
+    def i8_first_conv(self) -> int:
+        """c*: the first conv slot an int8 plan runs in int8 (-1 when the net is not planned in "i8")."""
+        return int(self.lib.y3_net_i8_first_conv(self._h))
+
+    def calibrate_i8(self, images: torch.Tensor, percentile: float = 100.0) -> List[float]:
+        """Activation scales for int8 plans from one batch of images [B,H,W,3] fp32 on the GPU: runs the fp32 plan with every
+        activation kept, takes per tensor the absmax of |x| (percentile=100) or the given percentile of |x|, divides by 127, gives the
+        two sources of every concat conv the larger of their scales, sets the scales (set_act_scales) and returns them.  Offline: the
+        reductions are torch's.  The net is left planned in fp32 with activations kept; plan it again for inference."""
+        from . import quant
+        if not 0.0 < float(percentile) <= 100.0:
+            raise Y3Error(f"calibrate_i8: percentile must be in (0, 100] (got {percentile!r})")
+        _need_cuda(images)
+        B = int(images.shape[0])
+        self.keep_activations(True)
+        self.plan(B, (int(images.shape[1]), int(images.shape[2])), _lib.Y3_DTYPE_F32)
+        grids = self.forward(images)
+        p = self.program
+        scales = [0.0] * len(p.tensors)
+        written = {o.dst for o in p.conv_ops()}
+        if p.tensors[p.input_tensor].channels != 3:   # layer tests: the input feeds an MFMA conv directly and is quantised itself
+            written.add(p.input_tensor)
+        for t in sorted(written):
+            x = images if t == p.input_tensor else grids[p.outputs.index(t)] if t in p.outputs else self.read_tensor(t, B)
+            a = x.abs().flatten().float()
+            if float(percentile) >= 100.0:
+                m = float(a.max())
+            else:   # the k-th smallest of |x| at the percentile (kthvalue: exact, no interpolation)
+                k = min(a.numel(), max(1, int(np.ceil(a.numel() * float(percentile) / 100.0))))
+                m = float(a.kthvalue(k).values)
+            scales[t] = quant.scale_from_absmax(m)
+        torch.cuda.synchronize()
+        scales = quant.equalize_concat(p, scales)
+        self.set_act_scales(scales)
+        self.keep_activations(False)
+        return scales
+
+    def save_calibration(self, path: str):
+        """The scales in force as JSON (tensor id -> scale) with the program's conv signature."""
+        from . import quant
+        quant.save_calibration(path, self.program, self.act_scales())
+
+    def load_calibration(self, path: str):
+        """Set the scales of a file save_calibration wrote; a table made for another graph is refused (Y3Error)."""
+        from . import quant
+        try:
+            scales = quant.load_calibration(path, self.program)
+        except ValueError as e:
+            raise Y3Error(str(e)) from None
+        self.set_act_scales(scales)
+        return scales
 
     def forward_decode(self, images: torch.Tensor, anchors):
         """images -> (bboxes [B,N,4], class_indices [B,N] int64, scores [B,N]): the conv program with the head convs decoding

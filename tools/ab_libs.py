@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of two builds of liby3hip.so on ONE box: alternating child processes (Y3_LIB_PATH), each timing the conv stack of
 the headline workload.  Boxes differ by +-2.5 %, processes on one box by < 0.5 %.
-   python tools/ab_libs.py yolo-v3-tf2_amd/lib/liby3hip.so yolo-v3-tf2_amd/lib/liby3hip_var.so [--dtype f32] [--rounds 3]
+   python tools/ab_libs.py yolo-v3-tf2_amd/lib/liby3hip.so yolo-v3-tf2_amd/lib/liby3hip_var.so [--dtype f32] [--rounds 3]     (--dtype: a tag of runtime.Net, "i8" included)
 A contender may also be LIB.so@TABLE.json: that build with Y3_TUNING_FILE=TABLE.json (a tile table for the SAME dtype / batch / size),
 and carry environment settings for its child process after a percent sign: LIB.so%Y3_LANE_STAGGER=1,OTHER=2 (tool knobs of the library)."""
 import argparse
@@ -25,8 +25,10 @@ if data == "zeros":   # every operand of every MFMA is zero: no toggling in the 
     for k in w:
         if not k.endswith(".var"): w[k] = w[k] * 0
 net = runtime.Net(p); net.load_weights(w)
-net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f32x2": _lib.Y3_DTYPE_F32X2, "f32x3": _lib.Y3_DTYPE_F32X3, "f16": _lib.Y3_DTYPE_F16}[dt])
 x = torch.rand((B, S, S, 3), device="cuda") if data != "zeros" else torch.zeros((B, S, S, 3), device="cuda")
+dtype = runtime.Net._dtype_arg(dt)
+if dtype == _lib.Y3_DTYPE_I8: net.calibrate_i8(x[:2].contiguous())   # the activation scales an int8 plan needs, as tools/time_i8.py takes them
+net.plan(B, S, dtype)
 g = [torch.empty((B, s, s, 3, 85), device="cuda") for s in net.grid_sizes()]
 import numpy as np
 from yolo_v3_tf2_amd.core.utils import get_anchors

@@ -1,8 +1,9 @@
 #!/usr/bin/env python3
 """SHA-256 of what the conv program produces (three head grids, the fused decode outputs, the packed detections and num_valid of
 net.detect) for a seeded batch: two builds of the library (Y3_LIB_PATH) that print the same digests are bit-identical on that plan.
-   python tools/hash_outputs.py --dtype bf16 --batch 128          (--dtype f32 | bf16 | f16 | f32x3 | f32x2; --lanes N overrides the table's;
-                                                                   --low-latency: the low-latency plan of an f32, bf16 or f16 net)"""
+   python tools/hash_outputs.py --dtype bf16 --batch 128          (--dtype f32 | bf16 | f16 | f32x3 | f32x2 | i8; --lanes N overrides the table's;
+                                                                   --low-latency: the low-latency plan of an f32, bf16 or f16 net)
+--dtype i8: the activation scales are calibrated first on two images of the seeded batch (Net.calibrate_i8, as tools/time_i8.py does)."""
 import argparse
 import hashlib
 import os
@@ -36,11 +37,13 @@ def main():
     net.load_weights(synthetic_weights(p, seed=4321))
     if a.low_latency:   # before plan(): the switch of the chosen dtype
         {_lib.Y3_DTYPE_BF16: net.set_low_latency_bf16, _lib.Y3_DTYPE_F16: net.set_low_latency_f16}.get(dtype, net.set_low_latency)(True)
+    x = torch.from_numpy(np.random.default_rng(77).random((a.batch, a.image_size, a.image_size, 3), dtype=np.float32)).cuda()
+    if dtype == _lib.Y3_DTYPE_I8:
+        net.calibrate_i8(x[:2].contiguous())
     net.plan(a.batch, a.image_size, dtype)
     if a.lanes:   # after plan(): it sets the lane count from the tuning table
         net.set_lanes(a.lanes)
     anchors = get_anchors(os.path.join(ROOT, "datasets/coco2012/anchors.txt")).astype(np.float32)
-    x = torch.from_numpy(np.random.default_rng(77).random((a.batch, a.image_size, a.image_size, 3), dtype=np.float32)).cuda()
     outs = list(net.forward(x)) + list(net.forward_decode(x, anchors)) + list(net.detect(x, anchors, 100, 0.5, 0.1))
     torch.cuda.synchronize()
     for i, t in enumerate(outs):

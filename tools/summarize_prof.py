@@ -20,12 +20,13 @@ def short(name):
         dma = ",dma" if m.group(8) == "1" else ""
         extra = "".join(",x" + v.strip() for v in m.group(9).split(",") if v.strip() and v.strip() != "0")
         return f"conv_f32_mfma<{32*tm*wr}x{32*tn*wc},w{wr*wc},s{m.group(6)}{dma}{extra}{',cat' if m.group(5) == 'true' else ''}>"
-    m = re.search(r"(?:conv_bf16_mfma<|conv16_mfma<y3::(?:Bf16|F16)Elem, )(\d+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false)(?:, (true|false), (\d+), (true|false))?", name)
+    m = re.search(r"(?:conv_bf16_mfma<|conv16_mfma<y3::(?:Bf16|F16|I8)Elem, )(\d+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false)(?:, (true|false), (\d+), (true|false))?", name)
     if m:
         tm, tn, wr, wc, bk = (int(m.group(i)) for i in range(1, 6))
-        kind = "conv_f16_mfma" if "F16Elem" in m.group(0) else "conv_bf16_mfma"   # one kernel template for both 16-bit types (csrc/conv_16bit.h)
+        # one kernel template for the three element types (csrc/conv_16bit.h); int8's k is in channels = bytes
+        kind = "conv_f16_mfma" if "F16Elem" in m.group(0) else "conv_i8_mfma" if "I8Elem" in m.group(0) else "conv_bf16_mfma"
         return (f"{kind}<{32*tm*wr}x{32*tn*wc},w{wr*wc},k{bk}{',dma' if m.group(8) == 'true' else ''}"
-                f"{',16x16x32' if m.group(10) == 'true' else ''}{',cat' if m.group(6) == 'true' else ''}"
+                f"{(',16x16x64' if 'I8Elem' in m.group(0) else ',16x16x32') if m.group(10) == 'true' else ''}{',cat' if m.group(6) == 'true' else ''}"
                 f"{',f32out' if m.group(7) == 'true' else ''}>")
     m = re.search(r"conv_f32x3_mfma<(\d+), (\d+), (\d+), (\d+), (\d+), (\d+), (true|false), (true|false), (\d+)", name)
     if m:

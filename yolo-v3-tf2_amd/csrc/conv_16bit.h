@@ -1,8 +1,15 @@
 // Implicit-GEMM convolution with 16-bit operands on the gfx950 matrix cores, fp32 accumulate: the one kernel body of the bf16 plans
 // (conv_bf16.hip, v_mfma_f32_32x32x16_bf16 / 16x16x32_bf16) and of the fp16 plans (conv_f16.hip, the _f16 forms of the same two
-// instructions), generic over the element traits E (Bf16Elem / F16Elem, y3_device.h).  Included by those two files only; each instantiates
-// the tile table below for its type.  The operand lane maps, the fragments of eight elements and the accumulator layouts are the same for
-// both types; the type shows in the MFMA, in the one rounding of the epilogue (E::pack2) and in the widening of the shortcut operand.
+// instructions), generic over the element traits E (Bf16Elem / F16Elem, y3_device.h).  Included by those two files and by conv_i8.hip
+// (next paragraph); each of the two instantiates the tile table below for its type.  The operand lane maps, the fragments of eight elements
+// and the accumulator layouts are the same for both types; the type shows in the MFMA, in the one rounding of the epilogue (E::pack2) and in
+// the widening of the shortcut operand.
+//
+// The names (file, conv16_mfma; the tools and the records under profiles/ parse them) now stand for the kernel of 16-BYTE PIECES: a third
+// element type, I8Elem (conv_i8.hip, the int8 plans), instantiates the same body.  What an operand row, a lane's fragment and an output piece
+// are is counted in bytes (E::BYTES per element: EB, EPP, KROWB below), so int8 is the 128-byte-row LDS-DMA tiles at BK = 128 channels; its
+// accumulators are i32 and enter bn_act through (float), and its output pieces hold 16 channels, quantised by E::quant.  Split-K, the
+// register-staged form and the 64-byte rows are built for the 16-bit types only (the static_asserts of the kernel).
 //
 // BASELINE config 5 ("bf16 MFMA fused conv+BN+LeakyReLU"): same fused op as conv_f32.hip
 // (reference: core/parse_model.py:27-52,72,134,155-156) with 16-bit activations/weights in HBM and LDS.
@@ -74,22 +81,26 @@ __device__ __forceinline__ u32x4 add_res_pack(float (&v)[8], const u32x4 &rr, bo
 template <class E, int TM, int TN, int WR, int WC, int BK, bool CONCAT, bool OUT_F32, bool DMA = false, int MINW = 1, bool M16 = false, bool SPLIT = false>
 __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs p)
 {
-    static_assert(!SPLIT || (DMA && BK == 64 && !M16 && !OUT_F32), "the split-K form is built for the LDS-DMA 32x32x16 tiles with BK = 64");
+    constexpr int EB = E::BYTES;     // bytes per element: 2, or 1 (int8)
+    constexpr int EPP = 16 / EB;     // elements per 16-byte piece
+    constexpr int KROWB = EB * BK;   // bytes of one row of a K tile
+    static_assert(!SPLIT || (DMA && KROWB == 128 && EB == 2 && !M16 && !OUT_F32), "the split-K form is built for the 16-bit LDS-DMA 32x32x16 tiles with BK = 64");
     Y3_STAMP(0);
     Y3_STAMP_IDS();
-    static_assert(!DMA || BK == 64 || BK == 32, "LDS-DMA variant needs 128-byte or 64-byte rows");
-    static_assert(!M16 || (DMA && BK == 64), "the 16x16x32 form is built on the 128-byte swizzled rows");
+    static_assert(!DMA || KROWB == 128 || (KROWB == 64 && EB == 2), "LDS-DMA variant needs 128-byte rows, or 64-byte rows of 16-bit elements");
+    static_assert(!M16 || (DMA && KROWB == 128), "the 16x16 form is built on the 128-byte swizzled rows");
+    static_assert(EB == 2 || (EB == 1 && DMA), "the register-staged form is built for 16-bit elements only");
     constexpr int MB = M16 ? 2 * TM : TM, NB = M16 ? 2 * TN : TN;   // accumulator blocks per wave
-    using acc_t = typename std::conditional<M16, f32x4, f32x16>::type;
-    constexpr int DROWS = 1024 / (2 * BK);   // rows one wave DMA instruction (1 KiB) fills: 8 (BK 64) or 16 (BK 32)
+    using acc_t = typename std::conditional<M16, typename E::acc16, typename E::acc32>::type;
+    constexpr int DROWS = 1024 / KROWB;   // rows one wave DMA instruction (1 KiB) fills: 8 (128-byte rows) or 16 (64-byte rows)
     constexpr int BM = 32 * TM * WR;
     constexpr int BN = 32 * TN * WC;
     constexpr int NT = 64 * WR * WC;
-    constexpr int LPR = BK / 8;      // lanes per row (16 B = 8 elements each)
+    constexpr int LPR = BK / EPP;    // lanes per row (16 B each)
     constexpr int RP = NT / LPR;     // rows per load pass
     constexpr int AP = BM / RP, BP = BN / RP;
     static_assert(BM % RP == 0 && BN % RP == 0 && AP >= 1 && BP >= 1, "tile too small for the thread count");
-    constexpr int ROWB = DMA ? 2 * BK : 2 * BK + 16;  // LDS row bytes
+    constexpr int ROWB = DMA ? KROWB : KROWB + 16;  // LDS row bytes
     constexpr int STAGE_B = (BM + BN) * ROWB;      // bytes per stage
     constexpr int CROW = BN + 4;                   // floats per row of the epilogue tile
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -110,8 +121,8 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
     const unsigned OOB0 = p.src0_bytes, OOB1 = CONCAT ? p.src1_bytes : p.src0_bytes;
 
     const int lrow = tid / LPR;
-    // first element of this lane's 16-B piece in the K tile (DMA: the logical chunk landing in physical chunk tid % LPR; BK 32 key written out: measured)
-    const int lchunk = DMA ? (BK == 64 ? swizzled_chunk<8>(lrow, tid % LPR) : (tid % LPR) ^ ((lrow >> 2) & 3)) * 8 : (tid % LPR) * 8;
+    // first element of this lane's 16-B piece in the K tile (DMA: the logical chunk landing in physical chunk tid % LPR; 64-byte-row key written out: measured)
+    const int lchunk = DMA ? (KROWB == 128 ? swizzled_chunk<8>(lrow, tid % LPR) : (tid % LPR) ^ ((lrow >> 2) & 3)) * EPP : (tid % LPR) * EPP;
     int aoff[AP];
     int aoff1[CONCAT ? AP : 1];
     int ahw[AP];
@@ -119,7 +130,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
     const TileOrigin org = tile_origin(p, m0);   // (b, ho, wo) of every row: conv_common.h
 #pragma unroll
     for (int i = 0; i < AP; ++i) {
-        if constexpr (OUT_F32 && !CONCAT) {   // the head convs: gather_row's offsets written out (through it five prologue instructions moved: measured)
+        if constexpr (OUT_F32 && !CONCAT && EB == 2) {   // the 16-bit head convs: gather_row's offsets written out (through it five prologue instructions moved: measured; int8 was built on gather_row)
             const int m = m0 + i * RP + lrow;
             int b, ho, wo;
             tile_row(p, org, org.wo0 + i * RP + lrow, b, ho, wo);
@@ -130,7 +141,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
     }
     unsigned boff[BP];
 #pragma unroll
-    for (int j = 0; j < BP; ++j) boff[j] = (unsigned)((n0 + j * RP + lrow) * p.K + lchunk) * 2u;
+    for (int j = 0; j < BP; ++j) boff[j] = (unsigned)((n0 + j * RP + lrow) * p.K + lchunk) * (unsigned)EB;
 
     // K tiles of this workgroup's walk: all of them, or slice blockIdx.y of gridDim.y (starting at tile kt0 of the walk)
     const int kt0 = SPLIT ? (int)blockIdx.y * (p.K / BK) / (int)gridDim.y : 0;
@@ -147,8 +158,8 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
         if (CONCAT) {
 #pragma unroll
             for (int i = 0; i < AP; ++i) {
-                avoff[i] = (ahw[i] < 0) ? OOB0 : (unsigned)(aoff[i] + lchunk) * 2u;
-                avoff1[i] = (ahw[i] < 0) ? OOB1 : (unsigned)(aoff1[i] + lchunk) * 2u;
+                avoff[i] = (ahw[i] < 0) ? OOB0 : (unsigned)(aoff[i] + lchunk) * (unsigned)EB;
+                avoff1[i] = (ahw[i] < 0) ? OOB1 : (unsigned)(aoff1[i] + lchunk) * (unsigned)EB;
             }
         } else {
             const int u = tap / p.ksize, v = tap - u * p.ksize;
@@ -157,7 +168,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
             for (int i = 0; i < AP; ++i) {
                 const int hi = (ahw[i] >> 16) + u, wi = (int)(short)(ahw[i] & 0xffff) + v;
                 const bool ok = (unsigned)hi < (unsigned)p.H && (unsigned)wi < (unsigned)p.W;
-                avoff[i] = ok ? (unsigned)(aoff[i] + toff) * 2u : OOB0;
+                avoff[i] = ok ? (unsigned)(aoff[i] + toff) * (unsigned)EB : OOB0;
             }
         }
     };
@@ -182,41 +193,41 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
         if (CONCAT && c0 >= p.C0) {
 #pragma unroll
             for (int i = 0; i < AP; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lds_ptr)(sa + i * RP * ROWB), 16, (int)avoff1[i], (c0 - p.C0) * 2, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs1, (lds_ptr)(sa + i * RP * ROWB), 16, (int)avoff1[i], (c0 - p.C0) * EB, 0, 0);
         } else {
 #pragma unroll
             for (int i = 0; i < AP; ++i)
-                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lds_ptr)(sa + i * RP * ROWB), 16, (int)avoff[i], c0 * 2, 0, 0);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs0, (lds_ptr)(sa + i * RP * ROWB), 16, (int)avoff[i], c0 * EB, 0, 0);
         }
 #pragma unroll
         for (int j = 0; j < BP; ++j)
-            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(sb + j * RP * ROWB), 16, (int)boff[j], kglob * 2, 0, 0);
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(rsw, (lds_ptr)(sb + j * RP * ROWB), 16, (int)boff[j], kglob * EB, 0, 0);
         advance_k();
     };
     auto fetch = [&]() {
         if (CONCAT) {
             if (c0 < p.C0) {
 #pragma unroll
-                for (int i = 0; i < AP; ++i) ra[i] = bload16(rs0, avoff[i], c0 * 2);
+                for (int i = 0; i < AP; ++i) ra[i] = bload16(rs0, avoff[i], c0 * EB);
             } else {
 #pragma unroll
-                for (int i = 0; i < AP; ++i) ra[i] = bload16(rs1, avoff1[i], (c0 - p.C0) * 2);
+                for (int i = 0; i < AP; ++i) ra[i] = bload16(rs1, avoff1[i], (c0 - p.C0) * EB);
             }
         } else {
 #pragma unroll
-            for (int i = 0; i < AP; ++i) ra[i] = bload16(rs0, avoff[i], c0 * 2);
+            for (int i = 0; i < AP; ++i) ra[i] = bload16(rs0, avoff[i], c0 * EB);
         }
 #pragma unroll
-        for (int j = 0; j < BP; ++j) rb[j] = bload16(rsw, boff[j], kglob * 2);
+        for (int j = 0; j < BP; ++j) rb[j] = bload16(rsw, boff[j], kglob * EB);
         advance_k();
     };
     auto stage = [&](int buf) {
         unsigned char *sa = smem + buf * STAGE_B;
         unsigned char *sb = sa + BM * ROWB;
 #pragma unroll
-        for (int i = 0; i < AP; ++i) *reinterpret_cast<u32x4 *>(sa + (i * RP + lrow) * ROWB + lchunk * 2) = ra[i];
+        for (int i = 0; i < AP; ++i) *reinterpret_cast<u32x4 *>(sa + (i * RP + lrow) * ROWB + lchunk * EB) = ra[i];
 #pragma unroll
-        for (int j = 0; j < BP; ++j) *reinterpret_cast<u32x4 *>(sb + (j * RP + lrow) * ROWB + lchunk * 2) = rb[j];
+        for (int j = 0; j < BP; ++j) *reinterpret_cast<u32x4 *>(sb + (j * RP + lrow) * ROWB + lchunk * EB) = rb[j];
     };
 
     acc_t acc[MB][NB];
@@ -225,7 +236,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
 #pragma unroll
         for (int j = 0; j < NB; ++j)
 #pragma unroll
-            for (int e = 0; e < (M16 ? 4 : 16); ++e) acc[i][j][e] = 0.0f;
+            for (int e = 0; e < (M16 ? 4 : 16); ++e) acc[i][j][e] = 0;
 
     Y3_STAMP(1);
     if (DMA) {
@@ -241,7 +252,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
     const int fr = M16 ? (lane & 15) : (lane & 31), fh = M16 ? (lane >> 4) : (lane >> 5);   // row in the block, k group
     const int a_frag = (wr * 32 * TM + fr) * ROWB + (DMA ? 0 : fh * 16);
     const int b_frag = BM * ROWB + (wc * 32 * TN + fr) * ROWB + (DMA ? 0 : fh * 16);
-    constexpr int KS = M16 ? BK / 32 : BK / 16;      // MFMA k steps per K tile
+    constexpr int KS = M16 ? KROWB / 64 : KROWB / 32;   // MFMA k steps per K tile: 64 / 32 bytes of k each
     constexpr int BR = M16 ? 16 : 32;                // rows per block
     int foff[KS];  // byte offset of this lane's 16-B piece of k-step s inside its row
 #pragma unroll
@@ -302,20 +313,21 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
             }
         }
     } else if constexpr (!OUT_F32) {
-        // ---- 16-bit output: per-wave epilogue, no workgroup barrier ------------------------------------------------------
+        // ---- output in the element type: per-wave epilogue, no workgroup barrier ------------------------------------------
         // Every wave transposes its own 32 x (32 TN) fp32 blocks through a private LDS scratch (the operand tiles are dead
-        // after the loop's last barrier) and stores whole 16-byte pieces of 8 channels: rows of 64 TN bytes per wave, full
-        // 128-B lines for TN >= 2.  LDS operations of one wave execute in order, so the write -> read hand-off between
-        // its lanes needs no barrier, and a wave leaves as soon as ITS stores are issued.  The shortcut operand is added
-        // in fp32 before the single rounding to the element type (the oracle's bf16 mode rounds where the pipeline stores).
+        // after the loop's last barrier) and stores whole 16-byte pieces of EPP channels (8, int8: 16): 16-bit rows of 64 TN
+        // bytes per wave, full 128-B lines for TN >= 2.  LDS operations of one wave execute in order, so the write -> read
+        // hand-off between its lanes needs no barrier, and a wave leaves as soon as ITS stores are issued.  The shortcut is added
+        // in fp32 before the single rounding to the element type (the oracle's bf16 mode rounds where the pipeline stores);
+        // int8 (conv_i8.hip has the scheme): the shortcut value times its tensor's scale, then E::quant, four bytes a word.
         // (round 3: the workgroup-wide fp32 tile + 2 barriers per pass this replaces cost 27 % of the bf16 conv stack,
         // profiles/r03_ab_bf16_epilogue_probe.txt)
         constexpr int CW = 32 * TN;              // floats per scratch row = channels per wave
-        constexpr int PPRW = CW / 8;             // 16-byte output pieces per row
+        constexpr int PPRW = CW / EPP;            // 16-byte output pieces per row
         constexpr int NPL = 32 * PPRW / 64;      // pieces per lane per 32-row block
         float *S = reinterpret_cast<float *>(smem) + wave * (32 * CW);
-        unsigned short *dstb = static_cast<unsigned short *>(p.dst);
-        const unsigned short *res = static_cast<const unsigned short *>(p.residual);
+        typename E::stored *dstb = static_cast<typename E::stored *>(p.dst);
+        const typename E::stored *res = static_cast<const typename E::stored *>(p.residual);
         const int nw = n0 + wc * CW;             // first channel of this wave
         float sc[NB], sh[NB];
 #pragma unroll
@@ -334,8 +346,10 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
                 for (int it = 0; it < NPL; ++it) {
                     const int q = lane + it * 64;
                     const int r = q / PPRW, pc = q - r * PPRW;
-                    rr[it] = (mw + r < p.M) ? *reinterpret_cast<const u32x4 *>(res + (size_t)(mw + r) * p.Cout + nw + pc * 8)
-                                            : u32x4{0u, 0u, 0u, 0u};
+                    // int8 asks Cout % 16 only, so a wave's last pieces may lie past Cout: its column guard, here and at the store, is one
+                    // condition with a constant term (a bool narrowed under if constexpr moved the 20 int8-output instantiations: measured)
+                    rr[it] = (mw + r < p.M && (EB == 2 || nw + pc * EPP < p.Cout)) ? *reinterpret_cast<const u32x4 *>(res + (size_t)(mw + r) * p.Cout + nw + pc * EPP)
+                                                                                    : u32x4{0u, 0u, 0u, 0u};
                 }
             }
             if constexpr (M16) {
@@ -345,14 +359,14 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
                     for (int j = 0; j < NB; ++j)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            S[mfma16_row(e, fh, mb) * CW + j * 16 + fr] = bn_act(acc[2 * i + mb][j][e], sc[j], sh[j], p.leaky);
+                            S[mfma16_row(e, fh, mb) * CW + j * 16 + fr] = bn_act((float)acc[2 * i + mb][j][e], sc[j], sh[j], p.leaky);
                         }
             } else {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        S[mfma32_row(e, fh) * CW + j * 32 + fr] = bn_act(acc[i][j][e], sc[j], sh[j], p.leaky);
+                        S[mfma32_row(e, fh) * CW + j * 32 + fr] = bn_act((float)acc[i][j][e], sc[j], sh[j], p.leaky);
                     }
                 }
             }
@@ -365,11 +379,27 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
             for (int it = 0; it < NPL; ++it) {
                 const int q = lane + it * 64;
                 const int r = q / PPRW, pc = q - r * PPRW;
-                const f32x4 v0 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8);
-                const f32x4 v1 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8 + 4);
-                float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
-                const u32x4 out = add_res_pack<E>(v, rr[it], res != nullptr);
-                if (mw + r < p.M) *reinterpret_cast<u32x4 *>(dstb + (size_t)(mw + r) * p.Cout + nw + pc * 8) = out;
+                u32x4 out;
+                if constexpr (EB == 2) {
+                    const f32x4 v0 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8);
+                    const f32x4 v1 = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * 8 + 4);
+                    float v[8] = {v0[0], v0[1], v0[2], v0[3], v1[0], v1[1], v1[2], v1[3]};
+                    out = add_res_pack<E>(v, rr[it], res != nullptr);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const f32x4 v = *reinterpret_cast<const f32x4 *>(S + r * CW + pc * EPP + 4 * k);
+                        unsigned w = 0;
+#pragma unroll
+                        for (int b = 0; b < 4; ++b) {
+                            float x = v[b];
+                            if (res) x = (float)E::sbyte(rr[it][k], b) * p.q_res + x;
+                            w |= ((unsigned)E::quant(x, p.q_inv) & 0xffu) << (8 * b);
+                        }
+                        out[k] = w;
+                    }
+                }
+                if (mw + r < p.M && (EB == 2 || nw + pc * EPP < p.Cout)) *reinterpret_cast<u32x4 *>(dstb + (size_t)(mw + r) * p.Cout + nw + pc * EPP) = out;
             }
             // ... and the next pass's writes below this pass's reads
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -393,12 +423,12 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
                     for (int mb = 0; mb < 2; ++mb)
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
-                            C[(wr * 32 + 16 * mb + mfma16_row(e, fh)) * CROW + nl] = bn_act(acc[2 * i + mb][j][e], sc, sh, p.leaky);
+                            C[(wr * 32 + 16 * mb + mfma16_row(e, fh)) * CROW + nl] = bn_act((float)acc[2 * i + mb][j][e], sc, sh, p.leaky);
                         }
                 } else {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
-                        C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = bn_act(acc[i][j][e], sc, sh, p.leaky);
+                        C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = bn_act((float)acc[i][j][e], sc, sh, p.leaky);
                     }
                 }
             }
@@ -441,8 +471,8 @@ static hipError_t launch_kb(const ConvArgs &a, hipStream_t s)
 {
     constexpr int BM = 32 * TM * WR, BN = 32 * TN * WC;
     const int tilesM = (a.M + BM - 1) / BM, tilesN = a.CoutPad / BN;
-    const size_t stages = 2 * (size_t)(BM + BN) * (DMA ? 2 * BK : 2 * BK + 16);
-    // epilogue: fp32 output -> one workgroup-wide 32-row block per wave row; 16-bit output -> 32 x (32 TN) floats per wave
+    const size_t stages = 2 * (size_t)(BM + BN) * (DMA ? E::BYTES * BK : E::BYTES * BK + 16);
+    // epilogue: fp32 output -> one workgroup-wide 32-row block per wave row; output in the element type -> 32 x (32 TN) floats per wave
     const size_t ctile = OUT_F32 ? (size_t)WR * 32 * (BN + 4) * sizeof(float) : (size_t)WR * WC * 32 * 32 * TN * sizeof(float);
     return launch_conv_kernel<conv16_mfma<E, TM, TN, WR, WC, BK, CONCAT, OUT_F32, DMA, MINW, M16>>(a, tilesM * tilesN, 64 * WR * WC,
                                                                                                  std::max(stages, ctile), s);
@@ -474,7 +504,8 @@ static hipError_t launch_res(const ConvArgs &a, bool out_f32, hipStream_t s)
 
 // Ids are stable (tuning files refer to them) and the same for both element types.  The table holds exactly the tiles a plan can select --
 // a packaged tuning table (tuning/bf16_*.json), the library's heuristic or the head-decode fallback (choose_tile_bf16 / refine_bf16 in
-// y3_net.cpp) names every one of them (tests/test_abi.py); the other ids are retired.
+// y3_net.cpp) names every one of them (tests/test_abi.py); the other ids are retired.  I8Elem has a table of its own under the same ids
+// (an explicit specialisation, conv_i8.hip).
 template <class E> struct Tiles16 { static const Tile16 table[BF16_TILE_COUNT]; };
 template <class E> const Tile16 Tiles16<E>::table[BF16_TILE_COUNT] = {
     tile<E, 2, 2, 2, 2, 64>(),                  //  0: 128x128

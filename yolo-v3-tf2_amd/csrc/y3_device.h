@@ -71,11 +71,16 @@ __device__ __forceinline__ unsigned pack_f16(float lo, float hi)
 }
 
 // ---- element traits of the 16-bit MFMA conv kernels (conv_16bit.h, conv_res_16bit.h): the fragment of eight elements a lane feeds
-// an MFMA, the two MFMA shapes, two floats -> one packed word (one rounding each, to nearest even), one packed word -> two floats.
+// an MFMA, the two MFMA shapes with their accumulators, the element's size in bytes and its type as stored (conv_16bit.h is generic over
+// both: I8Elem, conv_i8.hip), two floats -> one packed word (one rounding each, to nearest even), one packed word -> two floats.
 // The lane maps of the operands and of the accumulators are the same for both types.  split_hi / split_lo: the two elements a value is split
 // into for the fused stem's conv0 (conv_stem.hip): bf16 v = hi + lo; fp16 v = hi + lo * 2^-11 with hi = 0 below the normal range.
 struct Bf16Elem {
     using frag = bf16x8;
+    using acc32 = f32x16;   // accumulators of mfma32 / mfma16
+    using acc16 = f32x4;
+    using stored = unsigned short;
+    static constexpr int BYTES = 2;
     using elem = __bf16;
     static __device__ __forceinline__ unsigned short bits(float x) { return bf16_bits(x); }
     static __device__ __forceinline__ elem split_hi(float v) { return (__bf16)v; }
@@ -88,6 +93,10 @@ struct Bf16Elem {
 };
 struct F16Elem {
     using frag = f16x8;
+    using acc32 = f32x16;   // accumulators of mfma32 / mfma16
+    using acc16 = f32x4;
+    using stored = unsigned short;
+    static constexpr int BYTES = 2;
     using elem = _Float16;
     static __device__ __forceinline__ unsigned short bits(float x) { return f16_bits(x); }
     static __device__ __forceinline__ elem split_hi(float v) { return fabsf(v) < 6.103515625e-05f ? (_Float16)0.0f : (_Float16)v; }

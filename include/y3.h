@@ -140,6 +140,21 @@ y3_status y3_net_set_xcd_mode(y3_net *net, int mode);
  * major order re-fetched the operands of the 13x13 layers ~18x from beyond L2).  The same products in another summation
  * order: results differ from the tap-major ones in the last bits.  0: tap-major; -1 (default): chosen per conv. */
 y3_status y3_net_set_k_chunk(y3_net *net, int channels);
+/* Border skip of the fp32 3x3 convs.  A 3x3 conv with pad 1 multiplies zeros wherever a tap of a border pixel falls outside the image
+ * (10 % of the products at 13^2).  Where a call's images come in whole blocks of 32 (batch % 32 == 0 per lane), an fp32 plan runs its
+ * single-source 3x3 convs (not the first layer, the fused stem, the weight-resident tile 33 or a split-K conv) with GEMM rows ordered
+ * position-major, batch-minor over a table of output positions sorted by which taps read inside the image, and every workgroup leaves
+ * out the taps that are padding for all of its positions.  Only products with zero are left out: results are bit-identical for finite
+ * weights (a non-finite weight met 0 * inf = NaN at the border before and is skipped now).  mode -1 (default): the library's rule,
+ * 0: off, 1: on wherever legal.  Read by every forward; other plans and ineligible convs launch what they always did.
+ * y3_net_get_border_skip: in how many of its sub-batches (y3_net_set_lanes) a forward of `batch` images launches conv `conv_slot` of the
+ * planned net that way under the mode in force (0: the raster launch everywhere, or no plan).
+ * y3_border_order (pure, no device): the position table of one conv geometry, Ho * Wo entries ho << 20 | wo << 9 | mask9, bit u * 3 + v of
+ * mask9 = input pixel (ho * stride - pad + u, wo * stride - pad + v) lies inside H x W; stably sorted by
+ * (number of bits set in mask9, mask9): positions of one mask stay together, in raster order.  Ho, Wo <= 2047. */
+y3_status y3_net_set_border_skip(y3_net *net, int mode);
+int y3_net_get_border_skip(const y3_net *net, int conv_slot, int batch);
+void y3_border_order(int Ho, int Wo, int H, int W, int stride, int pad, uint32_t *out);
 /* Low-latency fp32 plans: split-K convs for small batches (one to eight images), off by default.
  * At one 416^2 image the convs of the 13^2 .. 52^2 grids launch 24 .. 172 workgroups on 256 compute units, each walking the whole
  * K = taps * Cin alone.  With y3_net_set_low_latency(net, 1), called before y3_net_plan, each eligible conv is cut along K into S slices

@@ -58,6 +58,53 @@ __device__ __forceinline__ void gather_row(const ConvArgs &p, const TileOrigin &
     }
 }
 
+// Batch-minor rows (ConvArgs::pos_tab set, B % 32 == 0): GEMM row m = j * B + b, j an index into the position table, so each 32-row block of
+// a tile is ONE output position of 32 consecutive images.  Everything here is wave-uniform: one scalar division for the tile, then compares.
+// The entries behind the table (blocks of rows >= M) are zero: no live tap, position (0, 0).
+struct TileBlocks { int j0, r0, n32; unsigned live; };   // block 0 of the tile: table index, 32-image group; groups per position; OR of the blocks' tap masks
+
+__device__ __forceinline__ unsigned pos_entry(const ConvArgs &p, int j)
+{
+    const int n = p.Ho * p.Wo;
+    return (unsigned)__builtin_amdgcn_readfirstlane((int)p.pos_tab[j < n ? j : n]);
+}
+
+template <int NBLK>
+__device__ __forceinline__ TileBlocks tile_blocks(const ConvArgs &p, int m0)
+{
+    TileBlocks t;
+    t.n32 = p.B >> 5;
+    const int g0 = m0 >> 5;
+    t.j0 = t.n32 == 1 ? g0 : g0 / t.n32;
+    t.r0 = g0 - t.j0 * t.n32;
+    t.live = 0;
+    int j = t.j0, r = t.r0;
+#pragma unroll
+    for (int k = 0; k < NBLK; ++k) {
+        t.live |= pos_mask(pos_entry(p, j));
+        if (++r == t.n32) {
+            r = 0;
+            ++j;
+        }
+    }
+    return t;
+}
+
+// block kb (< NBLK, wave-uniform, possibly known only at run time) of the tile: its table entry and its first image
+template <int NBLK>
+__device__ __forceinline__ void tile_block(const ConvArgs &p, const TileBlocks &t, int kb, unsigned &ent, int &img)
+{
+    int j = t.j0, r = t.r0 + kb;
+#pragma unroll
+    for (int w = 1; w < NBLK; ++w)   // r < n32 + NBLK - 1: at most NBLK - 1 positions further
+        if (r >= t.n32) {
+            r -= t.n32;
+            ++j;
+        }
+    ent = pos_entry(p, j);
+    img = r << 5;
+}
+
 // LDS-DMA operand rows of LPR 16-byte chunks (2, 4 or 8), unpadded: chunk c of row r is stored at chunk position c ^ key(r), key = (r >> shift) & (LPR - 1)
 // with the shift that lets 16 consecutive rows cover all 16 slots of a 256-byte bank row.  XOR is its own inverse: the same call gives the logical chunk
 // landing in a physical position (the SOURCE address of a direct-to-LDS load) and the physical position of a logical chunk (a fragment read).

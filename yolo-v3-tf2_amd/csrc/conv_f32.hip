@@ -22,6 +22,11 @@
 // kept where it is in force, and slices are counted along that walk -- and stores its raw accumulators (no epilogue, rows >= M
 // included: the slab is padded to whole tiles) into slab y of a workspace [S][Mpad][CoutPad].  splitk_finish_f32, a separate launch
 // on the same stream, adds the slabs in the order 0, 1, ..., S-1 and applies the epilogue above.
+//
+// Border skip (BMIN = true; ConvArgs::pos_tab set: 3x3, single source, unsplit, B % 32 == 0): GEMM rows are batch-minor, m = j * B + b with j an
+// index into the conv geometry's position table (positions sorted by which taps read inside the image), so a 32-row block is one output
+// position of 32 images and a tile holds BM / 32 positions.  The K walk visits only the taps that are live for some position of the tile, in
+// the order they had; what is left out are products with the zeros of the padding, so the result keeps its bits.
 #include <algorithm>
 #include <type_traits>
 
@@ -59,10 +64,11 @@ __device__ int y3_dbg32_sel_k = -1;
 #define Y3_STAMP32(k) do { } while (0)
 #endif
 
-template <int TM, int TN, int WR, int WC, bool CONCAT, int STAGES, int MINW = 1, int DMA = 0, bool SPLIT = false>
+template <int TM, int TN, int WR, int WC, bool CONCAT, int STAGES, int MINW = 1, int DMA = 0, bool SPLIT = false, bool BMIN = false>
 __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvArgs p)
 {
     static_assert(!SPLIT || (!DMA && STAGES == 1), "the split-K form is built for the register-staged single-stage tiles");
+    static_assert(!BMIN || (!CONCAT && !SPLIT), "batch-minor rows are built for the unsplit single-source launch");
     Y3_STAMP32(0);
 #ifdef Y3_PHASE_STAMPS
     if (threadIdx.x == 0 && blockIdx.x < 32768 && p.K == y3_dbg32_sel_k) {
@@ -94,7 +100,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     const int tilesN = p.CoutPad / BN;
     // K tiles of this workgroup's walk: all of them, or slice blockIdx.y of gridDim.y (starting at tile kt0 of the walk)
     const int kt0 = SPLIT ? (int)blockIdx.y * (p.K / BK) / (int)gridDim.y : 0;
-    const int KT = SPLIT ? ((int)blockIdx.y + 1) * (p.K / BK) / (int)gridDim.y - kt0 : p.K / BK;
+    int KT = SPLIT ? ((int)blockIdx.y + 1) * (p.K / BK) / (int)gridDim.y - kt0 : p.K / BK;   // (BMIN: the live taps' tiles, below)
     const __amdgpu_buffer_rsrc_t rs0 = buffer_rsrc(p.src0, p.src0_bytes);
     const __amdgpu_buffer_rsrc_t rs1 = buffer_rsrc(CONCAT ? p.src1 : p.src0, CONCAT ? p.src1_bytes : p.src0_bytes);
     const __amdgpu_buffer_rsrc_t rsw = buffer_rsrc(p.wpk, p.w_bytes);
@@ -133,10 +139,25 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     int aoff1[CONCAT ? AP : 1];        // CONCAT: element offset of (b, ho, wo, 0) in src1
     int ahw[AP];                       // hi0 << 16 | (wi0 & 0xffff); row >= M marked by hi0 = -32768
     const int C1 = p.Cin - p.C0;
-    const TileOrigin org = tile_origin(p, m0);   // (b, ho, wo) of every row: conv_common.h
+    // BMIN: the tile's 32-row blocks, each one output position of 32 images (conv_common.h); `live` = the taps that read inside the image
+    // for some position of the tile.  Raster rows: one unused block, every tap.
+    constexpr int NBLK = BMIN ? BM / 32 : 1;
+    TileBlocks blk{0, 0, 1, 0x1ffu};
+    unsigned eent[BMIN ? TM : 1];   // BMIN: table entry and first image of the TM accumulator blocks of this wave (epilogue)
+    int eimg[BMIN ? TM : 1];
+    if constexpr (BMIN) {
+        blk = tile_blocks<NBLK>(p, m0);
+        if (blk.live == 0) blk.live = 1;   // (no position at all: cannot happen for a tile of the grid; every load is then out of range)
+        KT = __builtin_popcount(blk.live) * (p.Cin / BK);
 #pragma unroll
-    for (int i = 0; i < AP; ++i)
-        gather_row<CONCAT, 1>(p, org, m0 + i * RP + lrow, org.wo0 + i * RP + lrow, C1, aoff[i], aoff1[CONCAT ? i : 0], ahw[i]);
+        for (int i = 0; i < TM; ++i) tile_block<NBLK>(p, blk, wr * TM + i, eent[i], eimg[i]);
+    } else {
+        const TileOrigin org = tile_origin(p, m0);   // (b, ho, wo) of every row: conv_common.h
+#pragma unroll
+        for (int i = 0; i < AP; ++i)
+            gather_row<CONCAT, 1>(p, org, m0 + i * RP + lrow, org.wo0 + i * RP + lrow, C1, aoff[i], aoff1[CONCAT ? i : 0], ahw[i]);
+    }
+    const int tap0 = BMIN ? __builtin_ctz(blk.live) : 0;   // first tap of the walk (of every channel chunk)
     unsigned boff[BP];  // byte offset of this lane's piece of weight row n, k = 0
 #pragma unroll
     for (int j = 0; j < BP; ++j) boff[j] = (unsigned)((n0 + j * RP + lrow) * p.K + lchunk) * 4u;
@@ -151,8 +172,8 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     // 9 * CK / 32 consecutive K tiles instead of being Cin / 32 tiles apart, so the tap re-reads hit in L2: with the classic
     // order a 512 -> 1024 @13 launch fetched 1.5-1.9 GB from beyond L2 for 85 MB of operands (tools/traffic_per_layer.py).
     const int CK = (!CONCAT && p.k_chunk > 0 && p.k_chunk < p.Cin) ? p.k_chunk : p.Cin;
-    int kglob = 0;  // k index of the next tile to fetch
-    int tap = 0;
+    int tap = tap0;
+    int kglob = BMIN ? tap * p.Cin : 0;  // k index of the next tile to fetch
     int c0 = 0;
     int cend = CK;            // end of the current channel chunk (classic order: Cin)
     const int taps = p.ksize * p.ksize;
@@ -187,7 +208,23 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
             for (int i = 0; i < AP; ++i) avoff[i] = ((okmask[i] >> tap) & 1u) ? abase4[i] + toff4 : OOB0;
         }
     };
-    if (!CONCAT) {
+    if constexpr (BMIN) {
+        // pass i reads rows [i * RP + lrow]: block (i * RP + lrow) / 32 of the tile, wave-uniform (RP = 32: block i; RP = 64: the wave's half),
+        // image = the block's first + lrow % 32.  okmask comes from the table (the formula below, evaluated on the host; a block of rows >= M
+        // reads a zero entry), so it and the tap test of set_tap are scalar.
+        static_assert(RP == 32 || RP == 64, "a load pass covers one or two 32-row blocks");
+#pragma unroll
+        for (int i = 0; i < AP; ++i) {
+            unsigned e;
+            int b;
+            tile_block<NBLK>(p, blk, RP == 32 ? i : 2 * i + (wave >> 2), e, b);
+            b += lrow & 31;
+            const int hi0 = pos_ho(e) * p.stride - p.pad, wi0 = pos_wo(e) * p.stride - p.pad;
+            aoff[i] = ((b * p.H + hi0) * p.W + wi0) * p.Cin;
+            okmask[i] = pos_mask(e);
+            abase4[i] = (unsigned)(aoff[i] + lchunk) * 4u;
+        }
+    } else if (!CONCAT) {
         // per row: bit t of okmask = tap t reads inside the image (rows >= M: no bit set); byte offset of the lane's piece at tap 0
 #pragma unroll
         for (int i = 0; i < AP; ++i) {
@@ -218,9 +255,14 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     auto advance_k = [&]() {
         c0 += BK;
         if (c0 == cend) {
-            ++tap;
+            if constexpr (BMIN) {   // the next live tap (none left: taps, as the full walk ends)
+                const unsigned rest = blk.live >> (tap + 1);
+                tap = rest ? tap + 1 + __builtin_ctz(rest) : taps;
+            } else {
+                ++tap;
+            }
             if (!CONCAT && tap == taps && cend != p.Cin) {   // chunked order: next channel chunk, first tap again
-                tap = 0;
+                tap = tap0;
                 cend += CK;
             }
             c0 = cend - CK;
@@ -302,7 +344,8 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
 
     // epilogue geometry
     const bool interior = (m0 + BM <= p.M) && (n0 + BN <= p.Cout);
-    const int row_bytes = p.Cout * 4;
+    // bytes between two rows of an accumulator block in dst: the next pixel; BMIN: the same pixel of the next image
+    const int row_bytes = BMIN ? p.Ho * p.Wo * p.Cout * 4 : p.Cout * 4;
 
     for (int kt = 0; kt < KT; ++kt) {
         const int cur = (STAGES == 2) ? (kt & 1) : 0;
@@ -385,13 +428,21 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int mbase = m0 + (wr * TM + i) * 32 + 4 * fh;
-                const unsigned vbase = (unsigned)(mbase * p.Cout + n) * 4u;
+                unsigned vbase;
+                if constexpr (BMIN) {   // block wr * TM + i of the tile: pixel (ho, wo) of images img + 4 fh + mfma32_row(e)
+                    const unsigned pe = eent[i];
+                    const int b = eimg[i] + 4 * fh;
+                    vbase = (unsigned)(((b * p.Ho + pos_ho(pe)) * p.Wo + pos_wo(pe)) * p.Cout + n) * 4u;
+                } else {
+                    vbase = (unsigned)(mbase * p.Cout + n) * 4u;
+                }
                 unsigned off[16];
                 if (!interior) {
 #pragma unroll
                     for (int e = 0; e < 16; ++e) {
                         const int m = mbase + mfma32_row(e);
-                        off[e] = (n_ok && m < p.M) ? (unsigned)(m * p.Cout + n) * 4u : p.dst_bytes;
+                        if constexpr (BMIN) off[e] = (n_ok && m < p.M) ? vbase + (unsigned)(mfma32_row(e) * row_bytes) : p.dst_bytes;
+                        else off[e] = (n_ok && m < p.M) ? (unsigned)(m * p.Cout + n) * 4u : p.dst_bytes;
                     }
                 }
                 float r[16];
@@ -484,6 +535,14 @@ static hipError_t launch_k(const ConvArgs &a, hipStream_t s)
         int rows = 0;                                           // largest M block
         for (int xm = 0; xm < gm; ++xm) rows = std::max(rows, (xm + 1) * tilesM / gm - xm * tilesM / gm);
         grid = 8 * rows * (tilesN / a.xcd_gn);
+    }
+    if constexpr (!CONCAT) {   // batch-minor rows with the border taps skipped: the launch decision (refine_f32) sets the table only where this holds
+        if (a.pos_tab) {
+            if (a.ksize != 3 || a.B < 32 || a.B % 32 || a.M != a.B * a.Ho * a.Wo || a.Ho > kPosMaxGrid || a.Wo > kPosMaxGrid) return hipErrorInvalidValue;
+            return launch_conv_kernel<conv_f32_mfma<TM, TN, WR, WC, false, STAGES, MINW, DMA, false, true>>(a, grid, 64 * WR * WC, lds, s);
+        }
+    } else if (a.pos_tab) {
+        return hipErrorInvalidValue;
     }
     return launch_conv_kernel<conv_f32_mfma<TM, TN, WR, WC, CONCAT, STAGES, MINW, DMA>>(a, grid, 64 * WR * WC, lds, s);
 }

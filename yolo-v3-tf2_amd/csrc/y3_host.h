@@ -85,6 +85,7 @@ struct ConvSlot {
     std::vector<float> sw_host, bn_scale_host;   // [CoutPad64]
     float *sc_i8_dev = nullptr;                  // [CoutPad64]
     float q_res = 0.0f, q_inv = 0.0f;            // (at plan time) scale of the int8 shortcut tensor; 1 / scale of the int8 output tensor
+    const uint32_t *pos_tab = nullptr;           // (at plan time, fp32 plans) the position table of this 3x3 single-source conv's geometry, else null
 };
 
 struct Op {
@@ -137,6 +138,11 @@ struct y3_net {
     size_t split_ws_lane = 0;
     int split_ws_lanes = 0;
     int k_chunk = -1;              // y3_net_set_k_chunk: fp32 3x3 convs walk K chunk-major, this many input channels per chunk; 0 tap-major; -1 per-conv default
+    // y3_net_set_border_skip: fp32 3x3 convs on batch-minor rows that skip their padding taps; -1 the rule, 0 off, 1 on wherever legal.
+    // pos_tabs: one position table per conv geometry of the plan (y3_plan.cpp), on the device, freed with the plan; ConvSlot::pos_tab points into it
+    int border_skip = -1;
+    struct PosTab { int Ho, Wo, H, W, stride; uint32_t *dev; };
+    std::vector<PosTab> pos_tabs;
     hipEvent_t fork_ev = nullptr;
     hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
     hipEvent_t join_ev[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -218,6 +224,7 @@ struct ConvChoice {
     int k_chunk;   // ConvArgs::k_chunk
     int xcd_gn;    // ConvArgs::xcd_gn
     int split_k;   // SplitK: slices
+    const uint32_t *pos_tab;   // ConvArgs::pos_tab (fp32 border skip), null: raster rows
 };
 // The one launch decision.  `a`: the slice's ConvArgs (rows of the call, byte sizes, a.dec set when the conv decodes its own tiles).
 ConvChoice choose_conv(const y3_net *net, int oi, const ConvArgs &a);
@@ -229,6 +236,8 @@ bool stem_conv2_applicable(const y3_net *net);
 void resolve_stem(y3_net *net);   // stem_fused / stem_conv2 of a planned net from the planned mode's switch and the graph
 bool output_staged(const y3_net *net, int t);
 y3_status resolve_splits(y3_net *net);
+// fp32 plans: the position table of every 3x3 single-source conv's geometry, built and uploaded once per geometry (y3_net_plan)
+y3_status resolve_border(y3_net *net);
 // int8 plans: the cut, the element size of every tensor and the scales the plan needs (y3_net_plan, before the arena is placed) ...
 y3_status resolve_i8(y3_net *net);
 // ... and the epilogue scales of int8 conv `slot` on the device, once its weights are loaded (y3_net_plan; y3_net_set_conv_weights on a planned net)

@@ -43,9 +43,24 @@ struct ConvArgs {
     int n_cus;             // compute units of the net's device, read once by y3_net_plan: sizes the grids of the persistent kernels (conv_res_*.hip)
     int device;            // the net's device index (the launch goes there: Y3_ENTER_DEVICE); -1 = not known, launchers ask the runtime
     // int8 convs only (conv_i8.hip; `scale` is then (s_in * s_w[c]) * bn_scale[c]): the scale of the int8 shortcut tensor, and 1 / the scale
-    // of the int8 output tensor.  Last in the struct: the kernel arguments of every other launch keep their offsets.
+    // of the int8 output tensor.  Behind everything the other launches read: their kernel arguments keep their offsets.
     float q_res, q_inv;
+    // fp32 MFMA kernel, 3x3 single-source convs with B % 32 == 0 (border skip): the conv geometry's position table on the
+    // device (border_order below; kPosTabPad zero entries behind the Ho * Wo positions) -> GEMM rows are batch-minor, m = j * B + b with
+    // j an index into the table, and a tile's K walk leaves out the taps that are padding for all of its positions.  Null: raster rows,
+    // every tap.  After q_res / q_inv for the same reason as they are where they are.
+    const uint32_t *pos_tab;
 };
+
+// One position of a 3x3 conv's output grid: (ho, wo) and mask9, bit t = tap t = (u, v) = (t / 3, t % 3) reads inside the image.
+constexpr int kPosMaxGrid = 2047;   // ho, wo in 11 bits each
+constexpr int kPosTabPad = 8;       // zero entries behind the table: the blocks of a tile's rows >= M (at most 256 / 32) read them
+constexpr uint32_t pos_pack(int ho, int wo, uint32_t mask9) { return ((uint32_t)ho << 20) | ((uint32_t)wo << 9) | mask9; }
+constexpr int pos_ho(uint32_t e) { return (int)(e >> 20); }
+constexpr int pos_wo(uint32_t e) { return (int)((e >> 9) & 0x7ffu); }
+constexpr uint32_t pos_mask(uint32_t e) { return e & 0x1ffu; }
+// The table of one geometry: all Ho * Wo positions, stably sorted by (live taps, mask9) (positions of one mask keep raster order).  Host only (y3_plan.cpp).
+void border_order(int Ho, int Wo, int H, int W, int stride, int pad, uint32_t *out);
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) once per (kernel instantiation, device): the attribute belongs to the
 // device's copy of the code object, so a process driving several GPUs must set it on each.

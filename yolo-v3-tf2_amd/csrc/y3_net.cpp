@@ -273,6 +273,17 @@ int default_k_chunk(const ConvSlot &c)
     return (c.d.size == 3 && c.d.cin >= 256) ? 128 : 0;
 }
 
+// the border-skip rule when the caller has not chosen (y3_net_set_border_skip(-1)): the eligible convs of at most kBorderSkipMaxPositions
+// output positions; Y3_BORDER_SKIP=0 (off) and Y3_BORDER_SKIP_MAX_POS override (tools).  No limit: at 64 x 416^2 on two lanes the step reads
+// 30.467 / 30.416 / 30.246 / 30.224 ms with the skip allowed up to 13^2 / 26^2 / 52^2 / everywhere, 30.823 ms off (profiles/border_skip_ab.txt)
+constexpr int kBorderSkipMaxPositions = 1 << 30;
+bool default_border_skip(const y3::ConvArgs &a)
+{
+    static const int env = [] { const char *e = getenv("Y3_BORDER_SKIP"); return e ? atoi(e) : -1; }();
+    static const int max_pos = [] { const char *e = getenv("Y3_BORDER_SKIP_MAX_POS"); return e ? atoi(e) : kBorderSkipMaxPositions; }();
+    return env != 0 && a.Ho * a.Wo <= max_pos;
+}
+
 // How the 8 XCDs (each with its own 4 MB L2) divide the tile matrix of one fp32 conv launch: as a (8/gn) x gn grid of
 // blocks.  An XCD then streams 1/gn of the weights and 1/gm of the activations; the L2-miss traffic of the launch is
 // about gn * (activation bytes) + gm * (weight bytes), provided an XCD's weight slice stays L2-resident (<= 2.5 MB) while
@@ -403,6 +414,11 @@ void refine_f32(const y3_net *net, const ConvSlot &c, const y3::ConvArgs &a, y3:
     // K order of the 3x3 convs (conv_f32.hip): chunk-major when the conv has more input channels than one chunk
     const int ck = net->k_chunk >= 0 ? net->k_chunk : default_k_chunk(c);
     if (c.d.size == 3 && c.d.src1 < 0 && ck > 0 && c.d.cin > ck && c.d.cin % ck == 0 && ck % 32 == 0) ch.k_chunk = ck;
+    // Border skip: batch-minor rows over the geometry's position table (c.pos_tab: fp32 plan, 3x3, single source), for the generic tiles of
+    // an unsplit launch whose images come in whole 32-row blocks; the row step of an accumulator block (one image) must fit the scalar offset
+    const bool legal = c.pos_tab && ch.kind == y3::ConvKind::Mfma && ch.tile != 33 && a.B >= 32 && a.B % 32 == 0 &&
+                       (long long)a.Ho * a.Wo * a.Cout * 4 * 32 < 0x7fffffffLL;
+    if (legal && (net->border_skip >= 0 ? net->border_skip == 1 : default_border_skip(a))) ch.pos_tab = c.pos_tab;
 }
 
 // bf16 and fp16 plans: a head conv that decodes its own tiles needs a 256-wide tile
@@ -905,6 +921,38 @@ try {
     return Y3_OK;
 }
 Y3_CATCH("y3_net_set_k_chunk")
+
+y3_status y3_net_set_border_skip(y3_net *net, int mode)
+try {
+    if (!net || mode < -1 || mode > 1) return fail(Y3_ERR_INVALID, "y3_net_set_border_skip: -1 (the rule), 0 (off) or 1 (on wherever legal)");
+    net->border_skip = mode;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_border_skip")
+
+int y3_net_get_border_skip(const y3_net *net, int slot, int batch)
+{
+    if (!net || !net->height || slot < 0 || slot >= (int)net->convs.size() || batch <= 0 || batch > net->max_batch) return 0;
+    const int oi = y3::conv_op(net, slot);
+    if (oi < 0) return 0;
+    const ConvSlot &c = net->convs[slot];
+    int lanes = net->lanes, n = 0;
+    while (lanes > 1 && batch / lanes < 1) --lanes;
+    for (int l = 0; l < lanes; ++l) {   // the sub-batches of y3_net_forward; a conv of the chunked leading segment: its first chunk
+        int nb = (int)((long long)batch * (l + 1) / lanes) - (int)((long long)batch * l / lanes);
+        if (oi < net->early_ops && nb > net->early_chunk) nb = net->early_chunk;
+        if (nb <= 0) continue;
+        y3::ConvArgs a{};
+        a.B = nb;
+        a.Ho = net->height / c.d.out_div;
+        a.Wo = net->width / c.d.out_div;
+        a.M = nb * a.Ho * a.Wo;
+        a.Cout = c.d.cout;
+        a.CoutPad = c.*y3::family_of_conv(net, slot).cout_pad;
+        n += y3::choose_conv(net, oi, a).pos_tab != nullptr;
+    }
+    return n;
+}
 
 y3_status y3_net_set_low_latency(y3_net *net, int on)
 try { return set_low_latency(F32_FAMILY, net, on, &y3_net::low_latency_set); }

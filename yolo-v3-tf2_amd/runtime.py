@@ -183,6 +183,14 @@ class Net:
         """K order of the fp32 3x3 convs: channels per chunk (multiple of 32) walked chunk-major, 0 tap-major, -1 default."""
         check(self.lib.y3_net_set_k_chunk(self._h, int(channels)), "y3_net_set_k_chunk")
 
+    def set_border_skip(self, mode: int):
+        """fp32 3x3 convs on batch-minor rows that skip their padding taps (bit-identical): -1 the library's rule, 0 off, 1 on wherever legal."""
+        check(self.lib.y3_net_set_border_skip(self._h, int(mode)), "y3_net_set_border_skip")
+
+    def border_skip(self, slot: int, batch: int) -> int:
+        """In how many of its sub-batches a forward of `batch` images launches conv `slot` of the planned net with the border skip."""
+        return int(self.lib.y3_net_get_border_skip(self._h, int(slot), int(batch)))
+
     @staticmethod
     def _dtype_arg(dtype) -> int:
         """None (absent: fp32), a _lib.Y3_DTYPE_* value or its tag ("f32", "bf16", "f16", "f32x3", "f32x2") -> the Y3_DTYPE_* value."""

@@ -138,6 +138,30 @@ def oracle_launch(O, op, weights, tensor, acc64=True, bf16_weights=False):
     return y
 
 
+# The bars the parity suites hold a conv launch's fp32 output to, in one place so that the class-count suite
+# (tests/test_class_counts_gpu.py) applies the very bars the 80-class tests apply.
+NETWORK_GRID_BAR = 1e-4      # free-running fp32 head logits against the oracle, absolute (test_network_grids_match_oracle)
+
+
+def f32_conv_bar(ref):
+    """An fp32 output of one conv launch against the oracle on the same inputs: 2e-5 of the output's magnitude (fp32 with another
+    summation order over K <= 4608).  test_conv_layers_match_oracle, the x3 / x2 layer tests, and the fp32 head outputs of the
+    bf16 / fp16 teacher-forced tests."""
+    return 2e-5 * max(1.0, float(np.abs(ref).max()))
+
+
+def bf16_tile_bar(ref):
+    """A forced bf16 tile's fp32 output against the bf16-emulating oracle, free running over one layer (test_bf16_every_tile)."""
+    return 2e-4 * max(1.0, float(np.abs(ref).max()))
+
+
+def check_f32_conv(got, ref, what):
+    """assert |got - ref|max <= f32_conv_bar(ref); -> (deviation, bar)."""
+    err, bar = float(np.abs(got - ref).max()), f32_conv_bar(ref)
+    assert err <= bar, (what, err, bar)
+    return err, bar
+
+
 # the per-tile matrix (tests/test_tile_matrix_gpu.py, tests/test_tile_matrix_host.py): one seed, three images, a square and a non-square canvas
 TILE_MATRIX_SEED = 3
 TILE_MATRIX_BATCH = 3

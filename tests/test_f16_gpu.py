@@ -14,7 +14,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from tests.f16_oracle import f16_emulation, f16_ulp_elem, free_running_floor, rel_l2, round_f16  # noqa: E402
-from tests.helpers import mini_program, oracle_launch, unfolded_program  # noqa: E402
+from tests.helpers import check_f32_conv, mini_program, oracle_launch, unfolded_program  # noqa: E402
 from yolo_v3_tf2_amd import _lib  # noqa: E402
 
 F16, BF16 = _lib.Y3_DTYPE_F16, _lib.Y3_DTYPE_BF16
@@ -119,8 +119,7 @@ def test_f16_every_layer_teacher_forced(rt, program, weights):
         with f16_emulation():       # the Cin = 3 first layer is fp32 arithmetic on fp32 weights
             y = oracle_launch(O, o, weights, dev, acc64=True, bf16_weights=(o.cin != 3))
         if o.dst in outs:                                   # head conv: fp32 straight from the accumulators
-            err, bar = float(np.abs(outs[o.dst] - y).max()), 2e-5 * max(1.0, float(np.abs(y).max()))
-            assert err <= bar, (o.conv_index, err, bar)
+            err, bar = check_f32_conv(outs[o.dst], y, o.conv_index)
             worst_head = max(worst_head, err / bar)
             continue
         w_, f_ = _stored_check(dev(o.dst), y, 1.2e-2, o.conv_index)

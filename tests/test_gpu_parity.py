@@ -14,6 +14,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 from yolo_v3_tf2_amd import _lib  # noqa: E402  (tile tables for the parametrised tile tests)
+from tests.helpers import NETWORK_GRID_BAR, bf16_tile_bar, check_f32_conv  # noqa: E402  (the bars tests/test_class_counts_gpu.py shares)
 
 
 @pytest.fixture(scope="module")
@@ -88,9 +89,7 @@ def test_conv_layers_match_oracle(rt, case):
     got = net.forward(_cuda(x))
     torch.cuda.synchronize()
     for r, g in zip(ref, got):
-        g = g.cpu().numpy().reshape(r.shape)
-        tol = 2e-5 * max(1.0, float(np.abs(r).max()))
-        assert np.abs(g - r).max() <= tol, (case, float(np.abs(g - r).max()), tol)
+        check_f32_conv(g.cpu().numpy().reshape(r.shape), r, case)
 
 
 def _real_tiles():
@@ -232,9 +231,7 @@ def test_x3_conv_layers_match_fp32_oracle(rt, case):
     got = net.forward(xin)
     torch.cuda.synchronize()
     for r, g in zip(ref, got):
-        g = g.cpu().numpy().reshape(r.shape)
-        tol = 2e-5 * max(1.0, float(np.abs(r).max()))
-        assert np.abs(g - r).max() <= tol, (case, float(np.abs(g - r).max()), tol)
+        check_f32_conv(g.cpu().numpy().reshape(r.shape), r, case)
 
 
 @pytest.mark.parametrize("tile", _lib.TILES_X3_BUILT)
@@ -311,9 +308,7 @@ def test_x2_conv_layers_match_fp32_oracle(rt, case):
     got = net.forward(xin)
     torch.cuda.synchronize()
     for r, g in zip(ref, got):
-        g = g.cpu().numpy().reshape(r.shape)
-        tol = 2e-5 * max(1.0, float(np.abs(r).max()))
-        assert np.abs(g - r).max() <= tol, (case, float(np.abs(g - r).max()), tol)
+        check_f32_conv(g.cpu().numpy().reshape(r.shape), r, case)
 
 
 def test_x2_split_is_accurate_to_2_pow_minus_22(rt):
@@ -462,7 +457,7 @@ def test_bf16_every_tile(rt, tile):
     got = net.forward(_cuda(x).to(torch.bfloat16))
     torch.cuda.synchronize()
     for r, g in zip(ref, got):
-        assert np.abs(g.cpu().numpy().reshape(r.shape) - r).max() <= 2e-4 * max(1.0, float(np.abs(r).max()))
+        assert np.abs(g.cpu().numpy().reshape(r.shape) - r).max() <= bf16_tile_bar(r)
 
 
 @pytest.mark.parametrize("cin,cout,S,B", [(32, 64, 40, 3), (64, 128, 36, 2), (64, 64, 33, 2), (32, 128, 70, 1)])
@@ -614,8 +609,7 @@ def test_bf16_every_layer_teacher_forced_within_one_ulp(rt, program, weights):
         if o.residual >= 0:
             y = O.add(dev(o.residual), y)
         if o.dst in outs:                                   # head conv: fp32 straight from the accumulators
-            got = outs[o.dst]
-            assert np.abs(got - y).max() <= 2e-5 * max(1.0, float(np.abs(y).max())), i
+            check_f32_conv(outs[o.dst], y, i)
             continue
         exp = O.round_bf16(y)
         got = net.read_tensor(o.dst, B).cpu().numpy()
@@ -699,7 +693,7 @@ def test_network_grids_match_oracle(rt, program, weights, S, B):
     got = net.forward(_cuda(x))
     torch.cuda.synchronize()
     for r, g in zip(ref, got):
-        assert np.abs(g.cpu().numpy() - r).max() <= 1e-4
+        assert np.abs(g.cpu().numpy() - r).max() <= NETWORK_GRID_BAR
 
 
 def test_forward_is_deterministic(rt, program, weights):

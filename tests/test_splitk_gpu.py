@@ -29,22 +29,7 @@ def _bar(r):
     return 2e-5 * max(1.0, float(np.abs(r).max()))
 
 
-C3 = dict(size=3)
-# name -> (in_ch, image size, B, chain, heads, slots that are split); the conv under test is three times the same head, or a chain conv
-LAYERS = {
-    # M = 169: ragged last tile; K = 576: 18 K tiles -- S = 2, 3 divide evenly, 4 -> slices of 4, 5, 4, 5 tiles, 8 -> two and three
-    "c64_13": (64, 13, 1, [], [dict(filters=64, **C3)] * 3, (0, 1, 2)),
-    # the same conv with leaky and a shortcut from the input: residual and activation of the finish kernel
-    "c64_13_res": (64, 13, 1, [dict(filters=64, size=1), dict(filters=64, size=3, shortcut=-3)], [dict(filters=64, size=1)] * 3, (1,)),
-    # Cin = 256: the default chunk-major K order (128 channels per chunk, 36 K tiles per chunk, 4 per tap) is in force
-    "c256_13": (256, 13, 1, [], [dict(filters=128, **C3)] * 3, (0, 1, 2)),
-    # stride 2 at 14 x 14: padding taps in every slice
-    "s2_14": (64, 14, 1, [], [dict(filters=128, size=3, stride=2)] * 3, (0, 1, 2)),
-    # the head shape: 255 channels (CoutPad 256), bias, linear -- the scalar form of the finish kernel; 4 K tiles
-    "head255": (128, 13, 1, [], [dict(filters=255, size=1, bn=False, act="linear")] * 3, (0, 1, 2)),
-    # three images at 14 x 14: M = 588 spans ten tiles and the image boundaries
-    "b3_14": (64, 14, 3, [], [dict(filters=128, **C3)] * 3, (0, 1, 2)),
-}
+from tests.splitk_cases import C3, LAYERS_F32 as LAYERS  # noqa: E402,F401  -- the table is shared with the host tiers
 LAYER_CASES = [
     ("c64_13", 2, 11), ("c64_13", 3, 11), ("c64_13", 4, 11), ("c64_13", 8, 11),
     ("c64_13_res", 3, 11), ("c64_13_res", 4, 11),

@@ -240,9 +240,10 @@ __global__ __launch_bounds__(64 * WR * WC) void conv_f32x3_mfma(const ConvArgs p
             const float sc = p.scale[n0 + nl], sh = p.shift[n0 + nl];
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
-                // three planes: BN scale applied here; two planes: scale already folded into the packed weights
+                // three planes: BN scale applied here; two planes: scale already folded into the packed weights, sc the power of two the
+                // channel's weights were normalised by (exact)
                 float v = NPL == 3 ? acc[0][i][j][e] * sc + sh
-                                   : (acc[0][i][j][e] + acc[NACC - 1][i][j][e] * (1.0f / 2048.0f)) + sh;
+                                   : (acc[0][i][j][e] + acc[NACC - 1][i][j][e] * (1.0f / 2048.0f)) * sc + sh;
                 if (p.leaky) v = fmaxf(v, 0.1f * v);
                 C[(wr * 32 + mfma32_row(e, fh)) * CROW + nl] = v;
             }

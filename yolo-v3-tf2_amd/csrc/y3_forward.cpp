@@ -91,7 +91,8 @@ struct Slice {
         a.src0 = rd(d.src0);
         a.src1 = rd(d.src1);
         a.wpk = c.*fam.w;
-        a.scale = i8 ? c.sc_i8_dev : c.scale_dev;   // int8: (s_in * s_w[c]) * bn_scale[c]
+        // int8: (s_in * s_w[c]) * bn_scale[c]; two-plane: the power of two its packed weights were divided by (the BN scale is folded in)
+        a.scale = i8 ? c.sc_i8_dev : fam.w == &ConvSlot::wx2_dev && !c.first_layer ? c.scale_x2_dev : c.scale_dev;   // the Cin = 3 layer runs conv_first in every mode
         a.shift = c.shift_dev;
         a.residual = rd(d.residual);
         a.q_res = c.q_res;

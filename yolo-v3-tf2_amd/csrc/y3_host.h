@@ -67,7 +67,10 @@ struct ConvSlot {
     void *wx3_dev = nullptr;   // packed [CoutPad64][3 planes][K] bf16 (hi, mid, lo of the fp32 weights)
     int tile_x2 = -1;
     bool x2_ok = true;         // false: a BN-scaled weight is outside the fp16 range, the two-plane mode cannot be planned
-    void *wx2_dev = nullptr;   // packed [CoutPad64][2 planes][K] fp16 (h, l' = (w - h) * 2^11 of the BN-scaled weights)
+    // packed [CoutPad64][2 planes][K] fp16: h, l' = (w - h) * 2^11 of the BN-scaled weights, every output channel n divided by 2^e_n first
+    // (its largest magnitude in [1, 2); e_n = 0 for an all-zero channel), and scale_x2_dev[n] = 2^e_n, which the kernel's epilogue applies
+    void *wx2_dev = nullptr;
+    float *scale_x2_dev = nullptr;   // [CoutPad64]
     void *w_dev = nullptr;     // packed [CoutPad][K] fp32 (or HWIO for the first layer)
     float *w0stem_dev = nullptr;   // first layer only: [28][Cout] = HWIO rows x BN scale, row 27 zero (fused stem kernel, fp32)
     float *w0raw_dev = nullptr;    // first layer only: the same without the scale (fused stem kernel, bf16 mode)

@@ -147,6 +147,22 @@ void split_bf16x3(float x, unsigned short v[3])
     v[2] = f32_to_bf16_rne(r1 - bf16_to_f32(v[1]));
 }
 
+// two-plane weights: every output channel's row of pk [CoutPad][K] divided by 2^e_n, e_n such that the row's largest magnitude lands in
+// [1, 2) (0 for an all-zero row) -- exact, a power of two -- and pow2[n] = 2^e_n for the kernel's epilogue.  Without it a channel whose
+// BN-scaled weights lie below 2^-13 (a small gamma over a large variance) has subnormal l' planes, 2^-36 absolute instead of 2^-22 relative.
+std::vector<float> normalise_rows(std::vector<float> pk, int K, int cout, std::vector<float> &pow2)
+{
+    for (int n = 0; n < cout; ++n) {
+        float mx = 0.0f;
+        for (int k = 0; k < K; ++k) mx = std::max(mx, fabsf(pk[(size_t)n * K + k]));
+        if (!(mx > 0.0f) || !std::isfinite(mx)) continue;
+        const int e = std::ilogb(mx);
+        pow2[n] = ldexpf(1.0f, e);
+        for (int k = 0; k < K; ++k) pk[(size_t)n * K + k] = ldexpf(pk[(size_t)n * K + k], -e);
+    }
+    return pk;
+}
+
 // two fp16 planes: w = h + l' * 2^-11 (up to 2^-22 |w|) while |w| < 65504
 void split_f16x2(float x, unsigned short v[2])
 {
@@ -799,7 +815,7 @@ void y3_net_destroy(y3_net *net)
         }
     }
     for (ConvSlot &c : net->convs)
-        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, (void *)c.w0norm_dev, (void *)c.scale0norm_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_dev, (void *)c.shift_dev, c.wi8_dev, (void *)c.sc_i8_dev})
+        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, (void *)c.w0norm_dev, (void *)c.scale0norm_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_x2_dev, (void *)c.scale_dev, (void *)c.shift_dev, c.wi8_dev, (void *)c.sc_i8_dev})
             if (p) (void)hipFree(p);
     delete net;
 }
@@ -846,10 +862,15 @@ try {
         HIP_TRY(upload(c.wbf_dev, pack_planes<1>(pk, K, d.cout, CP, [](float x, unsigned short *v) { v[0] = f32_to_bf16_rne(x); })));
         // the fp16 copy, packed like the bf16 one (unscaled, round to nearest even; |w| beyond the fp16 range becomes inf, as IEEE says)
         HIP_TRY(upload(c.wf16_dev, pack_planes<1>(pk, K, d.cout, CP, [](float x, unsigned short *v) { v[0] = f32_to_f16_rne(x); })));
-        // a scaled weight outside the fp16 range: y3_net_plan(Y3_DTYPE_F32X2) refuses the net; other modes are unaffected
+        // a scaled weight outside the fp16 range: y3_net_plan(Y3_DTYPE_F32X2) refuses the net; other modes are unaffected.  The planes below are
+        // normalised into [1, 2) per channel, so fp16 could represent such weights: the refusal is kept as the mode's stated contract (a channel
+        // whose scaled weights reach 65504 leaves the fp16 range of its activation planes for inputs of order 1), not as a representability bound of the packing
         c.x2_ok = std::all_of(pk_scaled.begin(), pk_scaled.end(), [](float x) { return fabsf(x) < 65504.0f; });
         HIP_TRY(upload(c.wx3_dev, pack_planes<3>(pk, K, d.cout, CP64, split_bf16x3)));         // unscaled, like the bf16 copy
-        HIP_TRY(upload(c.wx2_dev, pack_planes<2>(pk_scaled, K, d.cout, CP64, split_f16x2)));   // BN-scaled, like the fp32 copy
+        // BN-scaled, like the fp32 copy, and normalised per output channel by a power of two that the epilogue puts back
+        std::vector<float> pow2(CP64, 1.0f);
+        HIP_TRY(upload(c.wx2_dev, pack_planes<2>(normalise_rows(pk_scaled, K, d.cout, pow2), K, d.cout, CP64, split_f16x2)));
+        HIP_TRY(upload(c.scale_x2_dev, pow2));
         // the int8 copy: the raw weights quantised per output channel (BN stays in the epilogue); their scales stay on the host for the plan
         HIP_TRY(upload(c.wi8_dev, pack_i8(pk, K, d.cout, CP64, c.sw_host)));
         c.bn_scale_host = scale;

@@ -133,7 +133,8 @@ y3_status y3_net_set_lanes(y3_net *net, int lanes);
 /* Placement of the fp32 conv tiles on the 8 XCDs (each has a private 4 MB L2).  1 (default): per conv, the XCDs form an
  * (8/gn) x gn grid over the (pixel-tile, channel-tile) matrix, gn chosen so that an XCD's slice of the weights stays in
  * its L2 (the 256->512 / 512->1024 3x3 weights are 4.7 / 18.9 MB); 0: every XCD takes a contiguous run of tiles.
- * Results are bit-identical in both modes (same per-tile arithmetic). */
+ * Results are bit-identical in both modes (same per-tile arithmetic).  A batch-minor launch (border skip, below) splits its border
+ * tiles, whose K walks are short, and its interior tiles evenly over the XCD pixel-tile ranges of either mode (8 ranges in mode 0). */
 y3_status y3_net_set_xcd_mode(y3_net *net, int mode);
 /* K order of the fp32 3x3 convs.  channels > 0 (a multiple of 32): for every chunk of that many input channels all 9 taps,
  * then the next chunk, so that the 9 reads of a pixel (one per tap) fall close together in time and hit in L2 (the tap-
@@ -151,10 +152,16 @@ y3_status y3_net_set_k_chunk(y3_net *net, int channels);
  * planned net that way under the mode in force (0: the raster launch everywhere, or no plan).
  * y3_border_order (pure, no device): the position table of one conv geometry, Ho * Wo entries ho << 20 | wo << 9 | mask9, bit u * 3 + v of
  * mask9 = input pixel (ho * stride - pad + u, wo * stride - pad + v) lies inside H x W; stably sorted by
- * (number of bits set in mask9, mask9): positions of one mask stay together, in raster order.  Ho, Wo <= 2047. */
+ * (number of bits set in mask9, mask9): positions of one mask stay together, in raster order.  Ho, Wo <= 2047.
+ * y3_border_tile_map (pure, no device): the workgroup -> tile mapping of such a launch, from the function its kernel evaluates.  T pixel
+ * tiles, the first Tb of them border tiles, gm in {1, 2, 4, 8} XCD pixel-tile ranges of 8 / gm XCDs each, tilesN channel tiles (a multiple
+ * of 8 / gm).  Returns the launch's grid size, -1 for arguments no launch has; out, unless null, receives (pixel tile, channel tile) per
+ * workgroup, (-1, -1) for a padding workgroup that exits at once.  Workgroup b runs on XCD b % 8, range (b % 8) / (8 / gm); every range
+ * holds its share of border tiles [x Tb / gm, (x + 1) Tb / gm) and of interior tiles. */
 y3_status y3_net_set_border_skip(y3_net *net, int mode);
 int y3_net_get_border_skip(const y3_net *net, int conv_slot, int batch);
 void y3_border_order(int Ho, int Wo, int H, int W, int stride, int pad, uint32_t *out);
+int y3_border_tile_map(int T, int Tb, int gm, int tilesN, int32_t *out);
 /* Low-latency fp32 plans: split-K convs for small batches (one to eight images), off by default.
  * At one 416^2 image the convs of the 13^2 .. 52^2 grids launch 24 .. 172 workgroups on 256 compute units, each walking the whole
  * K = taps * Cin alone.  With y3_net_set_low_latency(net, 1), called before y3_net_plan, each eligible conv is cut along K into S slices

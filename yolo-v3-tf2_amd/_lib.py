@@ -116,6 +116,7 @@ SYMBOLS = {
     "y3_net_set_border_skip": (_i, [_vp, _i]),
     "y3_net_get_border_skip": (_i, [_vp, _i, _i]),
     "y3_border_order": (None, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_uint32)]),
+    "y3_border_tile_map": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int32)]),
     "y3_net_set_stem_fusion": (_i, [_vp, _i]),
     "y3_net_set_low_latency": (_i, [_vp, _i]),
     "y3_net_set_split_k": (_i, [_vp, _i, _i]),

@@ -27,6 +27,8 @@
 // index into the conv geometry's position table (positions sorted by which taps read inside the image), so a 32-row block is one output
 // position of 32 images and a tile holds BM / 32 positions.  The K walk visits only the taps that are live for some position of the tile, in
 // the order they had; what is left out are products with the zeros of the padding, so the result keeps its bits.
+// The table's sort puts the tiles with such a short walk first; ConvArgs::border_tiles >= 0 deals them, and the interior tiles, evenly over the
+// XCD M-ranges (balanced_tile, y3_kernels.h) -- which workgroup computes a tile changes, nothing of the tile.
 #include <algorithm>
 #include <type_traits>
 
@@ -112,7 +114,14 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv_f32_mfma(const ConvAr
     const int fr = lane & 31, fh = lane >> 5;
 
     int mt = logical / tilesN, nt = logical - mt * tilesN;
-    if (p.xcd_gn > 0) {
+    if (BMIN && p.border_tiles >= 0) {
+        // balanced order (y3_kernels.h; launch_k sizes the grid for it): the XCD grid of the blocked order below (8 x 1 where that order is
+        // not in force), every M-range with its share of the short border tiles and of the interior ones.  Scalar work, once.
+        const TileMN t = balanced_tile(bid, p.xcd_gn > 0 ? p.xcd_gn : 1, tilesN, p.border_tiles, (p.M + BM - 1) / BM);
+        mt = t.mt;
+        nt = t.nt;
+        if (mt < 0) return;                    // padding workgroups
+    } else if (p.xcd_gn > 0) {
         // XCD-blocked order (launch_k sizes the grid for it): the 8 XCDs form a (8/gn) x gn grid over the tile matrix;
         // XCD (xm, xn) owns M-tiles [xm*tilesM/gm, (xm+1)*tilesM/gm) x N-tiles [xn*tilesN/gn, +tilesN/gn), N fastest.
         // With gn > 1 an XCD streams only 1/gn of the weight matrix through its 4 MB L2 (the 256->512 and 512->1024
@@ -539,6 +548,8 @@ static hipError_t launch_k(const ConvArgs &a, hipStream_t s)
     if constexpr (!CONCAT) {   // batch-minor rows with the border taps skipped: the launch decision (refine_f32) sets the table only where this holds
         if (a.pos_tab) {
             if (a.ksize != 3 || a.B < 32 || a.B % 32 || a.M != a.B * a.Ho * a.Wo || a.Ho > kPosMaxGrid || a.Wo > kPosMaxGrid) return hipErrorInvalidValue;
+            if (a.border_tiles > tilesM) return hipErrorInvalidValue;
+            if (a.border_tiles >= 0) grid = balanced_grid(a.xcd_gn > 0 ? a.xcd_gn : 1, tilesN, a.border_tiles, tilesM);   // (xcd_gn was checked above)
             return launch_conv_kernel<conv_f32_mfma<TM, TN, WR, WC, false, STAGES, MINW, DMA, false, true>>(a, grid, 64 * WR * WC, lds, s);
         }
     } else if (a.pos_tab) {

@@ -78,7 +78,7 @@ struct Slice {
     }
 
     // ConvArgs of conv slot `conv` in the plan's mode; a.dec set where it decodes its output in place (fused decode; its grid is then
-    // not written).  The launch decision (y3::choose_conv) adds k_chunk, xcd_gn and pos_tab; nothing else is changed afterwards.
+    // not written).  The launch decision (y3::choose_conv) adds k_chunk, xcd_gn, pos_tab and border_tiles; nothing else is changed afterwards.
     y3::ConvArgs conv_args(int conv) const
     {
         const ConvSlot &c = net->convs[conv];
@@ -237,6 +237,7 @@ struct Slice {
             a.k_chunk = ch.k_chunk;
             a.xcd_gn = ch.xcd_gn;
             a.pos_tab = ch.pos_tab;
+            a.border_tiles = ch.border_tiles;
             if (ch.kind == y3::ConvKind::InStem) {   // runs inside conv1's launch (fused stem)
                 if (f.ms_out && o.index < f.n_ms) f.ms_out[o.index] = 0.0f;
             } else {

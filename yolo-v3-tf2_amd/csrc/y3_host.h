@@ -89,6 +89,7 @@ struct ConvSlot {
     float *sc_i8_dev = nullptr;                  // [CoutPad64]
     float q_res = 0.0f, q_inv = 0.0f;            // (at plan time) scale of the int8 shortcut tensor; 1 / scale of the int8 output tensor
     const uint32_t *pos_tab = nullptr;           // (at plan time, fp32 plans) the position table of this 3x3 single-source conv's geometry, else null
+    int pos_border = 0;                          // ... and how many of its positions, the table's first, have a tap outside the image
 };
 
 struct Op {
@@ -144,7 +145,7 @@ struct y3_net {
     // y3_net_set_border_skip: fp32 3x3 convs on batch-minor rows that skip their padding taps; -1 the rule, 0 off, 1 on wherever legal.
     // pos_tabs: one position table per conv geometry of the plan (y3_plan.cpp), on the device, freed with the plan; ConvSlot::pos_tab points into it
     int border_skip = -1;
-    struct PosTab { int Ho, Wo, H, W, stride; uint32_t *dev; };
+    struct PosTab { int Ho, Wo, H, W, stride; uint32_t *dev; int border; };   // border: positions with mask9 != 0x1ff, the table's first
     std::vector<PosTab> pos_tabs;
     hipEvent_t fork_ev = nullptr;
     hipStream_t lane_stream[4] = {nullptr, nullptr, nullptr, nullptr};
@@ -228,6 +229,7 @@ struct ConvChoice {
     int xcd_gn;    // ConvArgs::xcd_gn
     int split_k;   // SplitK: slices
     const uint32_t *pos_tab;   // ConvArgs::pos_tab (fp32 border skip), null: raster rows
+    int border_tiles;          // ConvArgs::border_tiles (with pos_tab: the balanced tile -> XCD mapping), -1: the raster launches' mapping
 };
 // The one launch decision.  `a`: the slice's ConvArgs (rows of the call, byte sizes, a.dec set when the conv decodes its own tiles).
 ConvChoice choose_conv(const y3_net *net, int oi, const ConvArgs &a);

@@ -50,7 +50,48 @@ struct ConvArgs {
     // j an index into the table, and a tile's K walk leaves out the taps that are padding for all of its positions.  Null: raster rows,
     // every tap.  After q_res / q_inv for the same reason as they are where they are.
     const uint32_t *pos_tab;
+    // ... with pos_tab: the leading M-tiles that hold a border position (the table's sort puts them first), for the balanced tile -> XCD
+    // mapping (balanced_mtile below); -1: the mapping of the raster launches.  Behind pos_tab as pos_tab is behind q_res / q_inv.
+    int border_tiles;
 };
+
+// Balanced tile -> XCD mapping of the batch-minor launches (conv_f32.hip; DESIGN.md section 4, "Border skip").  The T M-tiles of a launch are
+// the Tb border tiles, whose K walks are short, and the T - Tb interior ones; a launch ends when its slowest XCD does, so each of the gm XCD
+// M-ranges takes an equal share of both kinds: range xm owns border tiles [xm Tb / gm, (xm + 1) Tb / gm) and interior tiles
+// [Tb + xm Ti / gm, Tb + (xm + 1) Ti / gm).  balanced_range: how many tiles that is.  balanced_mtile: the M-tile of local index lm of the
+// range -- the interior tiles first, so the short ones end the range's work -- or -1 behind its end (a padding workgroup).
+// -DY3_BORDER_FIRST (tools/ab_libs.py variant): the other order.
+__host__ __device__ inline int balanced_range(int xm, int gm, int Tb, int T)
+{
+    return ((xm + 1) * Tb / gm - xm * Tb / gm) + ((xm + 1) * (T - Tb) / gm - xm * (T - Tb) / gm);
+}
+__host__ __device__ inline int balanced_mtile(int lm, int xm, int gm, int Tb, int T)
+{
+    const int blo = xm * Tb / gm, nb = (xm + 1) * Tb / gm - blo;
+    const int ilo = Tb + xm * (T - Tb) / gm, ni = Tb + (xm + 1) * (T - Tb) / gm - ilo;
+    if (lm >= nb + ni) return -1;
+#ifdef Y3_BORDER_FIRST
+    return lm < nb ? blo + lm : ilo + (lm - nb);
+#else
+    return lm < ni ? ilo + lm : blo + (lm - ni);
+#endif
+}
+// Workgroups of such a launch: the 8 XCDs form a gm x gn grid (gn = 8 / gm divides tilesN), XCD bid & 7 = (xm, xn) takes local index bid >> 3
+// of its block, N fastest; the grid is sized for the largest range.  balanced_tile: workgroup bid -> (M-tile, N-tile), mt = -1: padding.
+struct TileMN { int mt, nt; };
+__host__ __device__ inline TileMN balanced_tile(int bid, int gn, int tilesN, int Tb, int T)
+{
+    const int gm = 8 / gn, xcd = bid & 7, xm = xcd / gn, xn = xcd - xm * gn;
+    const int nb = tilesN / gn, j = bid >> 3, lm = j / nb;
+    return {balanced_mtile(lm, xm, gm, Tb, T), xn * nb + (j - lm * nb)};
+}
+inline int balanced_grid(int gn, int tilesN, int Tb, int T)
+{
+    const int gm = 8 / gn;
+    int rows = 0;
+    for (int xm = 0; xm < gm; ++xm) rows = rows > balanced_range(xm, gm, Tb, T) ? rows : balanced_range(xm, gm, Tb, T);
+    return 8 * rows * (tilesN / gn);
+}
 
 // One position of a 3x3 conv's output grid: (ho, wo) and mask9, bit t = tap t = (u, v) = (t / 3, t % 3) reads inside the image.
 constexpr int kPosMaxGrid = 2047;   // ho, wo in 11 bits each

@@ -299,6 +299,13 @@ bool default_border_skip(const y3::ConvArgs &a)
     static const int max_pos = [] { const char *e = getenv("Y3_BORDER_SKIP_MAX_POS"); return e ? atoi(e) : kBorderSkipMaxPositions; }();
     return env != 0 && a.Ho * a.Wo <= max_pos;
 }
+// ... and its launches deal their border and interior tiles evenly over the XCD M-ranges (y3_kernels.h, balanced_tile); Y3_BORDER_BALANCE=0:
+// the tile -> XCD mapping of the raster launches, under which one range gets every short tile (tools: the A/B of profiles/border_balance_ab.txt)
+bool border_balance()
+{
+    static const int env = [] { const char *e = getenv("Y3_BORDER_BALANCE"); return e ? atoi(e) : 1; }();
+    return env != 0;
+}
 
 // How the 8 XCDs (each with its own 4 MB L2) divide the tile matrix of one fp32 conv launch: as a (8/gn) x gn grid of
 // blocks.  An XCD then streams 1/gn of the weights and 1/gm of the activations; the L2-miss traffic of the launch is
@@ -434,7 +441,13 @@ void refine_f32(const y3_net *net, const ConvSlot &c, const y3::ConvArgs &a, y3:
     // an unsplit launch whose images come in whole 32-row blocks; the row step of an accumulator block (one image) must fit the scalar offset
     const bool legal = c.pos_tab && ch.kind == y3::ConvKind::Mfma && ch.tile != 33 && a.B >= 32 && a.B % 32 == 0 &&
                        (long long)a.Ho * a.Wo * a.Cout * 4 * 32 < 0x7fffffffLL;
-    if (legal && (net->border_skip >= 0 ? net->border_skip == 1 : default_border_skip(a))) ch.pos_tab = c.pos_tab;
+    if (legal && (net->border_skip >= 0 ? net->border_skip == 1 : default_border_skip(a))) {
+        ch.pos_tab = c.pos_tab;
+        // the leading tiles that hold a border position, for the balanced tile -> XCD mapping (y3_kernels.h): rows are m = j * B + b and the
+        // border positions are the table's first, so every tile that begins below row pos_border * B
+        const long long bm = y3::conv_tile_info(ch.tile).bm;
+        if (border_balance()) ch.border_tiles = (int)std::min(((long long)c.pos_border * a.B + bm - 1) / bm, (a.M + bm - 1) / bm);
+    }
 }
 
 // bf16 and fp16 plans: a head conv that decodes its own tiles needs a 256-wide tile
@@ -558,7 +571,7 @@ const y3::ConvFamily *y3::conv_family(int dtype)
 y3::ConvChoice y3::choose_conv(const y3_net *net, int oi, const ConvArgs &a)
 {
     const ConvSlot &c = net->convs[net->ops[oi].index];
-    ConvChoice ch{ConvKind::Mfma, -1, 0, 0, 1};
+    ConvChoice ch{ConvKind::Mfma, -1, 0, 0, 1, nullptr, -1};
     if ((net->stem_fused && oi == 0) || (net->stem_conv2 && oi == 2)) ch.kind = ConvKind::InStem;
     else if (net->stem_fused && oi == 1) ch.kind = ConvKind::Stem;
     else if (c.first_layer) ch.kind = ConvKind::First;

@@ -16,7 +16,10 @@ void y3::free_plan(y3_net *n)
     n->split_ws_lanes = 0;
     for (const y3_net::PosTab &t : n->pos_tabs) (void)hipFree(t.dev);
     n->pos_tabs.clear();
-    for (ConvSlot &c : n->convs) c.pos_tab = nullptr;
+    for (ConvSlot &c : n->convs) {
+        c.pos_tab = nullptr;
+        c.pos_border = 0;
+    }
     for (void *p : n->blocks) (void)hipFree(p);
     n->blocks.clear();
     n->tdev.assign(n->tensors.size(), nullptr);
@@ -60,19 +63,24 @@ y3_status y3::resolve_border(y3_net *net)
     for (ConvSlot &c : net->convs) {
         const y3_conv_desc &d = c.d;
         if (d.size != 3 || d.src1 >= 0 || c.first_layer) continue;
-        const y3_net::PosTab g{net->height / d.out_div, net->width / d.out_div, net->height / d.in_div, net->width / d.in_div, d.stride, nullptr};
+        const y3_net::PosTab g{net->height / d.out_div, net->width / d.out_div, net->height / d.in_div, net->width / d.in_div, d.stride, nullptr, 0};
         if (g.Ho > kPosMaxGrid || g.Wo > kPosMaxGrid) continue;
         for (const y3_net::PosTab &t : net->pos_tabs)
-            if (t.Ho == g.Ho && t.Wo == g.Wo && t.H == g.H && t.W == g.W && t.stride == g.stride) c.pos_tab = t.dev;
+            if (t.Ho == g.Ho && t.Wo == g.Wo && t.H == g.H && t.W == g.W && t.stride == g.stride) {
+                c.pos_tab = t.dev;
+                c.pos_border = t.border;
+            }
         if (c.pos_tab) continue;
         const size_t n = (size_t)g.Ho * g.Wo;
         std::vector<uint32_t> tab(n + kPosTabPad, 0u);   // the zero entries behind: a tile's blocks of rows >= M
         border_order(g.Ho, g.Wo, g.H, g.W, g.stride, 1, tab.data());
         net->pos_tabs.push_back(g);
         y3_net::PosTab &t = net->pos_tabs.back();   // in the list before the copy: free_plan frees it on every path
+        while ((size_t)t.border < n && pos_mask(tab[t.border]) != 0x1ffu) ++t.border;   // the interior, all nine taps live, sorts last
         HIP_TRY(hipMalloc(reinterpret_cast<void **>(&t.dev), tab.size() * sizeof(uint32_t)));
         HIP_TRY(hipMemcpy(t.dev, tab.data(), tab.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         c.pos_tab = t.dev;
+        c.pos_border = t.border;
     }
     return Y3_OK;
 }
@@ -349,6 +357,18 @@ Y3_CATCH("y3_net_plan_hw")
 void y3_border_order(int Ho, int Wo, int H, int W, int stride, int pad, uint32_t *out)
 {
     if (out && Ho > 0 && Wo > 0 && Ho <= y3::kPosMaxGrid && Wo <= y3::kPosMaxGrid) y3::border_order(Ho, Wo, H, W, stride, pad, out);
+}
+
+int y3_border_tile_map(int T, int Tb, int gm, int tilesN, int32_t *out)
+{
+    if (T < 1 || Tb < 0 || Tb > T || (gm != 1 && gm != 2 && gm != 4 && gm != 8) || tilesN < 1 || tilesN % (8 / gm)) return -1;
+    const int gn = 8 / gm, grid = y3::balanced_grid(gn, tilesN, Tb, T);
+    for (int bid = 0; out && bid < grid; ++bid) {
+        const y3::TileMN t = y3::balanced_tile(bid, gn, tilesN, Tb, T);
+        out[2 * bid] = t.mt;
+        out[2 * bid + 1] = t.mt < 0 ? -1 : t.nt;
+    }
+    return grid;
 }
 
 y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype)

@@ -211,6 +211,27 @@ int y3_net_get_split_k_bf16(const y3_net *net, int conv_slot);
 y3_status y3_net_set_low_latency_f16(y3_net *net, int on);
 y3_status y3_net_set_split_k_f16(y3_net *net, int conv_slot, int S);
 int y3_net_get_split_k_f16(const y3_net *net, int conv_slot);
+/* Low-latency int8 plans: the same for Y3_DTYPE_I8 plans (see "int8 plans" below), with a switch, a request and a decision of their own
+ * (off and -1 by default: an int8 plan on which these are never called launches what it always did).  They act on the int8 convs, those
+ * from y3_net_i8_first_conv on; the convs before the cut launch what an fp16 plan launches and stay unsplit under every switch, the
+ * fp16 one included (splitting them is not built).  Tiles 11 and 12 on v_mfma_i32_32x32x32_i8, K tiles of 128 (K / 128); the rule is
+ * y3_choose_split_k on the conv's shape, its int8 tile at the planned max_batch and the compute units, and only for convs of at
+ * least 36 K tiles (K >= 4608: measured, profiles/latency_i8_splitk_sweep.txt -- int8 launches are short, and every shorter conv loses
+ * to the second launch at some batch from 1 to 8; a forced S is taken as given).  A slice stores its
+ * raw i32 accumulators (no conversion: a partial sum beyond 2^24 has no float); the second launch adds the S values as integers and
+ * applies the unsplit int8 epilogue's own operations.  Integer sums do not depend on order, so a split int8 conv gives the unsplit conv's
+ * bits -- and those of yolo_v3_tf2_amd/quant.py -- on all data and at every S: the low-latency int8 plan's results ARE the default int8
+ * plan's.  Never split in an int8 plan: every conv before the cut (so the first layer and the stem convs), any conv whose tile at the
+ * planned rows is not 11 or 12 (the 16x16x64 tiles and the 16-wave tiles have no split form), a conv storing int8 with Cout % 16 != 0,
+ * the three detection-head convs.
+ * y3_net_set_low_latency_i8: 0 / 1, off by default.  y3_net_set_split_k_i8: -1 = the rule when the int8 switch is on (else 1), 1 = off,
+ * 2..16 forced; an ineligible conv, S > K / 128, a forced value on a planned net whose dtype is not Y3_DTYPE_I8 ("only Y3_DTYPE_I8
+ * plans take an int8 split") or on a conv before the cut of a planned int8 net ("runs in fp16 in this plan") is refused with
+ * Y3_ERR_INVALID and a message.  y3_net_get_split_k_i8: the value in force after planning; 1 before, 1 on a plan that is not int8 (the
+ * fp32, bf16 and fp16 getters answer 1 on an int8 plan, and their setters refuse one). */
+y3_status y3_net_set_low_latency_i8(y3_net *net, int on);
+y3_status y3_net_set_split_k_i8(y3_net *net, int conv_slot, int S);
+int y3_net_get_split_k_i8(const y3_net *net, int conv_slot);
 y3_status y3_net_keep_activations(y3_net *net, int keep);
 /* 1 (default): when the program starts with conv0 (3x3/1, 3 -> 32) feeding only conv1 (3x3/2, 32 -> 64) -- the Darknet-53
  * stem, reference config/models/yolov3/backbone.yaml layers 1-2 -- and the plan is fp32 or bf16 without keep_activations,
@@ -328,8 +349,9 @@ y3_status y3_net_read_tensor(y3_net *net, int tensor_id, int batch, float *dst_d
  * Tiles: the bf16 table's ids for the tiles that have an int8 form (y3_tile_built(Y3_DTYPE_I8, id): 8, 10, 11, 12, 17, 19, 24, 26, 27,
  * 29), chosen by the bf16 heuristic; y3_net_set_tile_bf16 forces one (a forced tile without an int8 form leaves the conv to the
  * heuristic).  No int8 tuning table is shipped.  y3_net_forward_decode / y3_net_detect decode the heads in the launch as in a bf16 plan.
- * Not in this version: split-K (none of the low-latency switches acts on an int8 plan), a weight-resident tile, BK = 32 tiles (so no int8
- * for Cin = 32 / 64), and the int8 copy fused into the producing epilogue.
+ * Split-K: y3_net_set_low_latency_i8 / y3_net_set_split_k_i8 above (the fp32, bf16 and fp16 switches do not act on an int8 plan).
+ * Not in this version: a weight-resident tile, BK = 32 tiles (so no int8 for Cin = 32 / 64), split forms of the 16x16x64 and 16-wave
+ * tiles, and the int8 copy fused into the producing epilogue.
  *
  * y3_net_set_act_scales: n_tensors must be the net's tensor count; entries <= 0 mean unset.  Read by the next y3_net_plan.
  * y3_net_get_act_scale: the scale set for a tensor, 0 when unset.  y3_net_i8_first_conv: c* of a net planned in Y3_DTYPE_I8, else -1.

@@ -27,16 +27,17 @@ def main():
     ap.add_argument("--batch", type=int, default=128)
     ap.add_argument("--image-size", type=int, default=416)
     ap.add_argument("--lanes", type=int, default=0, help="concurrent sub-batches (0: what plan() takes from the tuning table)")
-    ap.add_argument("--low-latency", action="store_true", help="the split-K plan of --dtype f32 / bf16 / f16 (set_low_latency / set_low_latency_bf16 / set_low_latency_f16)")
+    ap.add_argument("--low-latency", action="store_true", help="the split-K plan of --dtype f32 / bf16 / f16 / i8 (set_low_latency / set_low_latency_bf16 / set_low_latency_f16 / set_low_latency_i8)")
     a = ap.parse_args()
     dtype = runtime.Net._dtype_arg(a.dtype)
-    if a.low_latency and dtype not in (_lib.Y3_DTYPE_F32, _lib.Y3_DTYPE_BF16, _lib.Y3_DTYPE_F16):
-        ap.error("--low-latency: only f32, bf16 and f16 plans split K")
+    if a.low_latency and dtype not in (_lib.Y3_DTYPE_F32, _lib.Y3_DTYPE_BF16, _lib.Y3_DTYPE_F16, _lib.Y3_DTYPE_I8):
+        ap.error("--low-latency: only f32, bf16, f16 and i8 plans split K")
     p = load_program(os.path.join(ROOT, "config/models/yolov3/model.yaml"), 80)
     net = runtime.Net(p)
     net.load_weights(synthetic_weights(p, seed=4321))
     if a.low_latency:   # before plan(): the switch of the chosen dtype
-        {_lib.Y3_DTYPE_BF16: net.set_low_latency_bf16, _lib.Y3_DTYPE_F16: net.set_low_latency_f16}.get(dtype, net.set_low_latency)(True)
+        {_lib.Y3_DTYPE_BF16: net.set_low_latency_bf16, _lib.Y3_DTYPE_F16: net.set_low_latency_f16,
+         _lib.Y3_DTYPE_I8: net.set_low_latency_i8}.get(dtype, net.set_low_latency)(True)
     x = torch.from_numpy(np.random.default_rng(77).random((a.batch, a.image_size, a.image_size, 3), dtype=np.float32)).cuda()
     if dtype == _lib.Y3_DTYPE_I8:
         net.calibrate_i8(x[:2].contiguous())

@@ -5,7 +5,9 @@ launch -- is timed alone with y3_net_profile_convs, median of --repeats; the tab
 the S the rule picks and what the rule leaves on the table, then the sums over the conv stack: unsplit, rule, best per conv.
     python tools/sweep_split_k.py [--size 416] [--batches 1 2 4 8] [--dtype f32] [--out profiles/latency_splitk_sweep.txt]
 --dtype bf16 sweeps a bf16 plan through y3_net_set_split_k_bf16 (K tiles of 64; profiles/latency_bf16_splitk_sweep.txt).
---dtype f16 sweeps an fp16 plan through y3_net_set_split_k_f16 (K tiles of 64; profiles/latency_f16_splitk_sweep.txt)."""
+--dtype f16 sweeps an fp16 plan through y3_net_set_split_k_f16 (K tiles of 64; profiles/latency_f16_splitk_sweep.txt).
+--dtype i8 sweeps an int8 plan through y3_net_set_split_k_i8 (K tiles of 128, the convs from the cut on; the activation scales are
+calibrated here on two seeded frames of each size, as tools/time_i8.py does; profiles/latency_i8_splitk_sweep.txt)."""
 import argparse
 import os
 import sys
@@ -22,10 +24,10 @@ def main():
     ap.add_argument("--batches", type=int, nargs="+", default=[1, 2, 4, 8])
     ap.add_argument("--splits", type=int, nargs="+", default=[1, 2, 3, 4, 6, 8, 12, 16])
     ap.add_argument("--repeats", type=int, default=15)
-    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"])
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16", "i8"])
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    sfx = {"f32": "", "bf16": "_bf16", "f16": "_f16"}[a.dtype]
+    sfx = {"f32": "", "bf16": "_bf16", "f16": "_f16", "i8": "_i8"}[a.dtype]
 
     import torch
     import yolo_v3_tf2_amd  # noqa: F401
@@ -41,12 +43,20 @@ def main():
 
     program = load_program(os.path.join(ROOT, "config/models/yolov3/model.yaml"), 80)
     net = runtime.Net(program)
-    net.load_weights(synthetic_weights(program))
+    weights = synthetic_weights(program)
+    net.load_weights(weights)
     n = len(net.conv_ops)
     set_split, get_split, set_ll = getattr(net, "set_split_k" + sfx), getattr(net, "split_k" + sfx), getattr(net, "set_low_latency" + sfx)
-    dtype, bk = {"f32": (_lib.Y3_DTYPE_F32, 32), "bf16": (_lib.Y3_DTYPE_BF16, 64), "f16": (_lib.Y3_DTYPE_F16, 64)}[a.dtype]
+    dtype, bk = {"f32": (_lib.Y3_DTYPE_F32, 32), "bf16": (_lib.Y3_DTYPE_BF16, 64), "f16": (_lib.Y3_DTYPE_F16, 64),
+                 "i8": (_lib.Y3_DTYPE_I8, 128)}[a.dtype]
     say(f"# tools/sweep_split_k.py  device: {torch.cuda.get_device_name(0)}  { {'f32': 'fp32', 'f16': 'fp16'}.get(a.dtype, a.dtype)}; ms per conv launch alone (split: slices + finish), median of {a.repeats}")
     for S_img in a.size:
+        if a.dtype == "i8":
+            cal = runtime.Net(program)
+            cal.load_weights(weights)
+            net.set_act_scales(cal.calibrate_i8(torch.rand((2, S_img, S_img, 3), device="cuda", generator=torch.Generator(device="cuda").manual_seed(0))))
+            del cal
+            torch.cuda.empty_cache()
         for B in a.batches:
             x = torch.rand((B, S_img, S_img, 3), device="cuda")
             for i in range(n):

@@ -12,6 +12,8 @@ between its windows.  The split in force per conv is printed for every plan.
     python tools/time_latency.py [--sizes 416 608] [--batches 1 2 4 8] [--calls 1000] [--windows 4] [--per-conv] [--dtype f32] [--out profiles/latency.txt]
 --dtype bf16 times bf16 plans, the low-latency one through y3_net_set_low_latency_bf16 (profiles/latency_bf16.txt).
 --dtype f16 times fp16 plans, the low-latency one through y3_net_set_low_latency_f16 (profiles/latency_f16.txt).
+--dtype i8 times int8 plans, the low-latency one through y3_net_set_low_latency_i8 (profiles/latency_i8.txt); the activation scales are
+calibrated here on two seeded frames of each size, as tools/time_i8.py does.
 --f16-fused-stem (with --dtype f16) switches the fused stem on in the "on" plan as well (y3_net_set_stem_fusion_f16).
 --control makes "on" a SECOND DEFAULT-PLAN net: the same launches from two net objects, i.e. what the protocol reads when nothing differs.
 --per-conv adds, for batch 1, the per-conv table of y3_net_profile_convs (each launch timed alone; a split conv is its two launches)."""
@@ -34,12 +36,12 @@ def main():
     ap.add_argument("--windows", type=int, default=4, help="alternated windows the calls are divided into")
     ap.add_argument("--warmup", type=int, default=30)
     ap.add_argument("--per-conv", action="store_true")
-    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16"])
+    ap.add_argument("--dtype", default="f32", choices=["f32", "bf16", "f16", "i8"])
     ap.add_argument("--control", action="store_true", help="'on' is a second default-plan net (two net objects, the same launches)")
     ap.add_argument("--f16-fused-stem", action="store_true", help="fp16: the 'on' plan also fuses the stem")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    sfx = {"f32": "", "bf16": "_bf16", "f16": "_f16"}[a.dtype]
+    sfx = {"f32": "", "bf16": "_bf16", "f16": "_f16", "i8": "_i8"}[a.dtype]
 
     import torch
     import yolo_v3_tf2_amd  # noqa: F401
@@ -71,10 +73,18 @@ def main():
         "; times in ms; 'pairs' = windows in which on < off")
     per_window = max(1, a.calls // a.windows)
     for S in a.sizes:
+        if a.dtype == "i8":
+            cal = runtime.Net(program)
+            cal.load_weights(weights)
+            scales = cal.calibrate_i8(torch.rand((2, S, S, 3), device="cuda", generator=torch.Generator(device="cuda").manual_seed(0)))
+            del cal
+            torch.cuda.empty_cache()
+            for net in nets.values():
+                net.set_act_scales(scales)
         for B in a.batches:
             x = torch.rand((B, S, S, 3), device="cuda")
             for net in nets.values():
-                net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f16": _lib.Y3_DTYPE_F16}[a.dtype])
+                net.plan(B, S, {"f32": _lib.Y3_DTYPE_F32, "bf16": _lib.Y3_DTYPE_BF16, "f16": _lib.Y3_DTYPE_F16, "i8": _lib.Y3_DTYPE_I8}[a.dtype])
             splits = [getattr(nets["on"], "split_k" + sfx)(i) for i in range(len(nets["on"].conv_ops))]
             say(f"\n== {S} x {S}, batch {B}: {sum(s > 1 for s in splits)} convs split; S per conv: {splits}")
             step = {k: (lambda n=n: n.detect(x, anchors, 100, 0.5, 0.1)) for k, n in nets.items()}

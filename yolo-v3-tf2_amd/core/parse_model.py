@@ -42,6 +42,7 @@ class YoloModel:
         self._weights = None
         self.low_latency = False
         self.low_latency_f16 = False
+        self.low_latency_i8 = False
         self.stem_fusion_f16 = 0
         self.dtype = None     # None: fp32 (set_dtype)
         self.i8_calibration = None   # path of the activation scales an "i8" plan needs (set_i8_calibration)
@@ -55,6 +56,8 @@ class YoloModel:
                 self._net.set_low_latency(True)
             if self.low_latency_f16:
                 self._net.set_low_latency_f16(True)
+            if self.low_latency_i8:
+                self._net.set_low_latency_i8(True)
             if self.stem_fusion_f16:
                 self._net.set_stem_fusion_f16(self.stem_fusion_f16)
             if self.i8_calibration:
@@ -79,6 +82,13 @@ class YoloModel:
         self.low_latency_f16 = Net._low_latency_arg(on)
         if self._net is not None:
             self._net.set_low_latency_f16(self.low_latency_f16)
+
+    def set_low_latency_i8(self, on=True):
+        """Low-latency int8 plans (runtime.Net.set_low_latency_i8): the same for plans made with dtype "i8"."""
+        from ..runtime import Net
+        self.low_latency_i8 = Net._low_latency_arg(on)
+        if self._net is not None:
+            self._net.set_low_latency_i8(self.low_latency_i8)
 
     def set_stem_fusion_f16(self, on=True):
         """The fused stem kernel for fp16 plans (runtime.Net.set_stem_fusion_f16): off by default; acts on dtype "f16" only."""

@@ -8,7 +8,7 @@
 // The names (file, conv16_mfma; the tools and the records under profiles/ parse them) now stand for the kernel of 16-BYTE PIECES: a third
 // element type, I8Elem (conv_i8.hip, the int8 plans), instantiates the same body.  What an operand row, a lane's fragment and an output piece
 // are is counted in bytes (E::BYTES per element: EB, EPP, KROWB below), so int8 is the 128-byte-row LDS-DMA tiles at BK = 128 channels; its
-// accumulators are i32 and enter bn_act through (float), and its output pieces hold 16 channels, quantised by E::quant.  Split-K, the
+// accumulators are i32 and enter bn_act through (float), and its output pieces hold 16 channels, quantised by E::quant.  The
 // register-staged form and the 64-byte rows are built for the 16-bit types only (the static_asserts of the kernel).
 //
 // BASELINE config 5 ("bf16 MFMA fused conv+BN+LeakyReLU"): same fused op as conv_f32.hip
@@ -25,6 +25,9 @@
 // K tiles [y*KT/S, (y+1)*KT/S) of the same tap-major walk and stores its raw fp32 accumulators (no epilogue, rows >= M included) straight
 // from the accumulator registers into slab y of a workspace [S][Mpad][CoutPad] fp32, through the slab's own buffer resource.
 // splitk_finish16, a separate launch on the same stream, adds the slabs in the order 0, 1, ..., S-1 and applies the epilogue.
+// int8 (y3_net_set_low_latency_i8, conv_i8.hip: launch_conv_i8_split): the same slice launch at BK = 128 with the slab holding the raw
+// i32 accumulators -- no conversion, so the split is exact at every S -- and a finish kernel of its own, splitk_finish_i8, which adds
+// integers and applies the int8 epilogue.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -84,7 +87,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
     constexpr int EB = E::BYTES;     // bytes per element: 2, or 1 (int8)
     constexpr int EPP = 16 / EB;     // elements per 16-byte piece
     constexpr int KROWB = EB * BK;   // bytes of one row of a K tile
-    static_assert(!SPLIT || (DMA && KROWB == 128 && EB == 2 && !M16 && !OUT_F32), "the split-K form is built for the 16-bit LDS-DMA 32x32x16 tiles with BK = 64");
+    static_assert(!SPLIT || (DMA && KROWB == 128 && !M16 && !OUT_F32), "the split-K form is built for the LDS-DMA 32x32 tiles with 128-byte rows (BK = 64, int8: 128)");
     Y3_STAMP(0);
     Y3_STAMP_IDS();
     static_assert(!DMA || KROWB == 128 || (KROWB == 64 && EB == 2), "LDS-DMA variant needs 128-byte rows, or 64-byte rows of 16-bit elements");
@@ -296,7 +299,7 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
     if constexpr (SPLIT) {
         // raw accumulators -> slab blockIdx.y, straight from the registers: p.dst is the workspace, p.dst_bytes the bytes of ONE slab
         // [Mpad][CoutPad] (Mpad = whole tiles, so every row of the tile has its place; the range check of the slab's own buffer resource
-        // drops anything else).  A store instruction writes two rows of 32 consecutive floats: whole 128-byte lines.
+        // drops anything else).  A store instruction writes two rows of 32 consecutive floats (int8: raw i32 sums): whole 128-byte lines.
         const __amdgpu_buffer_rsrc_t rss = buffer_rsrc(static_cast<const char *>(p.dst) + (size_t)blockIdx.y * p.dst_bytes, p.dst_bytes);
         const int slab_row_bytes = p.CoutPad * 4;
 #pragma unroll
@@ -307,9 +310,12 @@ __global__ __launch_bounds__(64 * WR * WC, MINW) void conv16_mfma(const ConvArgs
                 const int mbase = m0 + (wr * TM + i) * 32 + 4 * fh;
                 const unsigned vbase = (unsigned)(mbase * p.CoutPad + n) * 4u;
 #pragma unroll
-                for (int e = 0; e < 16; ++e)
-                    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, (float)acc[i][j][e]), rss, (int)vbase,
-                                                          mfma32_row(e) * slab_row_bytes, 0);
+                for (int e = 0; e < 16; ++e) {
+                    unsigned bits;   // int8: the i32 sum itself (a partial sum beyond 2^24 has no float), else the fp32 accumulator
+                    if constexpr (EB == 1) bits = (unsigned)acc[i][j][e];
+                    else bits = __builtin_bit_cast(unsigned, (float)acc[i][j][e]);
+                    __builtin_amdgcn_raw_buffer_store_b32(bits, rss, (int)vbase, mfma32_row(e) * slab_row_bytes, 0);
+                }
             }
         }
     } else if constexpr (!OUT_F32) {
@@ -593,13 +599,15 @@ __global__ __launch_bounds__(256) void splitk_finish16(const float *__restrict__
     }
 }
 
-// The split-K form is instantiated for the two tiles a small plan lands on: 11 (64x64) and 12 (64x128), both LDS-DMA, BK 64, four waves
+// The split-K form is instantiated for the two tiles a small plan lands on: 11 (64x64) and 12 (64x128), both LDS-DMA with 128-byte rows
+// (BK 64; int8: 128), four waves
 template <class E, int TN>
 static hipError_t launch_split_t(const ConvArgs &c, int grid, int S, hipStream_t s)
 {
+    constexpr int BK = 128 / E::BYTES;
     constexpr size_t lds = 2 * (size_t)(64 + 64 * TN) * 128;   // the two operand stages; a split launch has no epilogue tile
-    if (c.src1) return launch_conv_kernel<conv16_mfma<E, 1, TN, 2, 2, 64, true, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
-    return launch_conv_kernel<conv16_mfma<E, 1, TN, 2, 2, 64, false, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+    if (c.src1) return launch_conv_kernel<conv16_mfma<E, 1, TN, 2, 2, BK, true, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
+    return launch_conv_kernel<conv16_mfma<E, 1, TN, 2, 2, BK, false, false, true, 1, false, true>>(c, grid, 256, lds, s, S);
 }
 
 inline bool conv16_split_tile(int tile) { return tile == 11 || tile == 12; }

@@ -16,7 +16,10 @@
 //   v = (float)r * q_res + v            when there is a shortcut; r the int8 shortcut value, q_res its tensor's scale
 //   q = clamp(rintf(v * q_inv), -127, 127)
 // int8 output: 16 channels per 16-byte piece, the shortcut read in the same pieces.  fp32 output (head grids): v stored as is.
-// No split-K, no weight-resident form, no BK = 32 tiles (include/y3.h).
+// Split-K (low-latency int8 plans, y3_net_set_low_latency_i8; tiles 11 and 12): the SPLIT form of the kernel body stores a slice's raw i32
+// accumulators into its slab [S][Mpad][CoutPad] of 4-byte elements, and splitk_finish_i8 below adds the slabs as integers and applies
+// the four lines above.  i32 sums do not depend on order, so a split conv gives the unsplit conv's bits on all data and at every S.
+// No weight-resident form, no BK = 32 tiles (include/y3.h).
 #include "conv_16bit.h"
 
 namespace y3 {
@@ -75,6 +78,78 @@ hipError_t launch_conv_i8(const ConvArgs &a, int tile, bool out_f32, hipStream_t
     if (!out_f32 && (a.Cout % 16 || ((uintptr_t)a.dst & 15) || ((uintptr_t)a.residual & 15))) return hipErrorInvalidValue;
     if (out_f32 && a.residual) return hipErrorInvalidValue;
     return launch_conv16<I8Elem>(a, tile, out_f32, s);
+}
+
+// Second half of a split-K int8 conv (low-latency int8 plans): per element the S slab values added as integers -- exact, so the sum is the
+// unsplit launch's accumulator whatever S is -- then the four lines of the header above through the unsplit epilogue's helpers.  int8
+// output: 16 channels per thread, one 16-byte output piece, the shortcut read in the same piece (Cout % 16 == 0).  OUT_F32 (a conv that
+// writes an fp32 net output itself, Cout = 255 in CoutPad = 256 included): one element per thread.
+template <bool OUT_F32>
+__global__ __launch_bounds__(256) void splitk_finish_i8(const int *__restrict__ ws, int S, size_t slab_elems, int cout_pad,
+                                                        const float *__restrict__ scale, const float *__restrict__ shift,
+                                                        const signed char *__restrict__ residual, void *__restrict__ dst, int M, int cout,
+                                                        int leaky, float q_res, float q_inv)
+{
+    constexpr int W = OUT_F32 ? 1 : 16;
+    const int per_row = cout / W;
+    const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (size_t)M * per_row) return;
+    const int m = (int)(idx / per_row);
+    const int n = ((int)(idx - (size_t)m * per_row)) * W;
+    const int *src = ws + (size_t)m * cout_pad + n;
+    if constexpr (OUT_F32) {
+        int acc = *src;
+        for (int s = 1; s < S; ++s) acc += src[(size_t)s * slab_elems];
+        static_cast<float *>(dst)[(size_t)m * cout + n] = bn_act((float)acc, scale[n], shift[n], leaky);
+    } else {
+        i32x4 acc[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[k] = *reinterpret_cast<const i32x4 *>(src + 4 * k);
+        for (int s = 1; s < S; ++s) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[k] += *reinterpret_cast<const i32x4 *>(src + (size_t)s * slab_elems + 4 * k);
+        }
+        const size_t o = (size_t)m * cout + n;
+        u32x4 rr{0u, 0u, 0u, 0u};
+        if (residual) rr = *reinterpret_cast<const u32x4 *>(residual + o);
+        u32x4 out;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const f32x4 sc = *reinterpret_cast<const f32x4 *>(scale + n + 4 * k), sh = *reinterpret_cast<const f32x4 *>(shift + n + 4 * k);
+            unsigned w = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                float x = bn_act((float)acc[k][b], sc[b], sh[b], leaky);
+                if (residual) x = (float)I8Elem::sbyte(rr[k], b) * q_res + x;
+                w |= ((unsigned)I8Elem::quant(x, q_inv) & 0xffu) << (8 * b);
+            }
+            out[k] = w;
+        }
+        *reinterpret_cast<u32x4 *>(static_cast<signed char *>(dst) + o) = out;
+    }
+}
+
+bool conv_i8_split_tile(int tile) { return conv16_split_tile(tile); }
+
+// The split launch of tile 11 / 12 (K tiles of 128) and its finish launch on the same stream, with the checks of launch_conv_i8
+hipError_t launch_conv_i8_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s)
+{
+    if (a.K % 128 || !conv16_split_tile(tile)) return hipErrorInvalidValue;
+    // the finish launch moves 16 channels per thread: whole 16-byte pieces of dst and of the shortcut
+    if (!out_f32 && (a.Cout % 16 || ((uintptr_t)a.dst & 15) || ((uintptr_t)a.residual & 15))) return hipErrorInvalidValue;
+    if (out_f32 && a.residual) return hipErrorInvalidValue;
+    const auto [c, slab, grid] = split_launch(a, Tiles16<I8Elem>::table[tile].info, S, ws, ws_bytes);
+    if (!slab) return hipErrorInvalidValue;
+    if (hipError_t e = tile == 12 ? launch_split_t<I8Elem, 2>(c, grid, S, s) : launch_split_t<I8Elem, 1>(c, grid, S, s); e != hipSuccess) return e;
+    const int *wsi = static_cast<const int *>(ws);
+    const signed char *res = static_cast<const signed char *>(a.residual);
+    const size_t n = (size_t)a.M * (out_f32 ? a.Cout : a.Cout / 16);
+    const dim3 fgrid((unsigned)((n + 255) / 256));
+    if (out_f32)
+        hipLaunchKernelGGL((splitk_finish_i8<true>), fgrid, dim3(256), 0, s, wsi, S, slab / 4, a.CoutPad, a.scale, a.shift, res, a.dst, a.M, a.Cout, a.leaky, a.q_res, a.q_inv);
+    else
+        hipLaunchKernelGGL((splitk_finish_i8<false>), fgrid, dim3(256), 0, s, wsi, S, slab / 4, a.CoutPad, a.scale, a.shift, res, a.dst, a.M, a.Cout, a.leaky, a.q_res, a.q_inv);
+    return hipGetLastError();
 }
 
 }  // namespace y3

@@ -60,6 +60,7 @@ struct ConvSlot {
     int split_req = -1;        // y3_net_set_split_k: -1 the heuristic (low-latency plans only), 1 off, 2..16 forced
     int split_req_bf16 = -1;   // y3_net_set_split_k_bf16: as split_req, for bf16 plans
     int split_req_f16 = -1;    // y3_net_set_split_k_f16: as split_req, for fp16 plans
+    int split_req_i8 = -1;     // y3_net_set_split_k_i8: as split_req, for the int8 convs of an int8 plan
     int split_k = 1;           // K slices in force in the current plan, decided by resolve_splits from plan-time quantities only (1: the unsplit launch)
     int tile_bf16 = -1;        // the 16-bit plans' forced tile: bf16 and fp16 plans share the tile table (y3_net_set_tile_bf16)
     int tile_x3 = -1;
@@ -138,6 +139,7 @@ struct y3_net {
     bool low_latency = false;      // y3_net_set_low_latency: every eligible fp32 conv takes y3_choose_split_k
     bool low_latency_bf16 = false; // y3_net_set_low_latency_bf16: every eligible bf16 conv takes y3_choose_split_k
     bool low_latency_f16 = false;  // y3_net_set_low_latency_f16: every eligible fp16 conv takes y3_choose_split_k
+    bool low_latency_i8 = false;   // y3_net_set_low_latency_i8: every eligible int8 conv of an int8 plan takes y3_choose_split_k
     void *split_ws = nullptr;      // split-K slabs: split_ws_lanes regions of split_ws_lane bytes, one per lane (lanes run concurrently)
     size_t split_ws_lane = 0;
     int split_ws_lanes = 0;

@@ -247,6 +247,12 @@ hipError_t launch_conv_res_f16(const ConvArgs &a, hipStream_t s);
 TileInfo conv_i8_tile_info(int tile);
 bool conv_i8_tile_built(int tile);
 hipError_t launch_conv_i8(const ConvArgs &a, int tile, bool out_f32, hipStream_t s);
+// split-K form of the same conv (conv_i8.hip): S >= 2 slices of the K walk (K tiles of 128) as S times the workgroups, raw i32
+// accumulators into ws [S][Mpad][CoutPad] of 4-byte elements (at least S * split_slab_bytes), then splitk_finish_i8 on the same stream:
+// the slabs added as integers (exact: the unsplit launch's bits at every S), the int8 epilogue, the store to a.dst (int8, or fp32 with
+// out_f32).  Tiles 11 and 12 only (conv_i8_split_tile); the checks of launch_conv_i8.
+bool conv_i8_split_tile(int tile);
+hipError_t launch_conv_i8_split(const ConvArgs &a, int tile, bool out_f32, int S, void *ws, size_t ws_bytes, hipStream_t s);
 // n fp16 values (n % 16 == 0) -> int8: q = clamp(rintf((float)x * inv_s), -127, 127); and int8 -> fp32: (float)q * s  (elementwise.hip)
 hipError_t launch_quantize16_to_i8(const void *src_f16, void *dst_i8, size_t n, float inv_s, hipStream_t s);
 hipError_t launch_i8_to_f32(const void *src_i8, float *dst, size_t n, float scale, hipStream_t s);

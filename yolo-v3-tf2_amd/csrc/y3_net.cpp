@@ -503,6 +503,29 @@ constexpr y3::SplitForm F16_SPLIT = {
     "y3_net_set_split_k_f16", "y3_net_set_low_latency_f16", BF16_SPLIT.no_form, BF16_SPLIT.tiles,
     "only Y3_DTYPE_F16 plans take an fp16 split", 8, "a split conv storing fp16 needs Cout % 8 == 0"};
 
+// K tiles of 128 from which the rule splits an int8 conv: 36 (K >= 4608), the smallest K-tile count of
+// profiles/latency_i8_splitk_sweep.txt from which every conv at or above it gains from the rule's S at every batch from 1 to 8 -- the
+// 13^2 3x3 convs 512 -> 1024 (36 K tiles: 21.8 -> 16.1 us at one 416^2 image, 30.0 -> 24.9 us at eight).  Every shorter int8 conv is a
+// launch of 7 .. 15 us that the finish launch and the slab traffic outweigh at some batch: the 26^2 3x3 of 18 K tiles is even at one image
+// (-0.3 .. +0.3 us at S = 4) and loses 1 .. 6 us from two images on, the 52^2 3x3 of 9 K tiles and the 13^2 1x1 of 8 lose 1 .. 8 us at
+// every batch.  int8 launches are about half as long as the 16-bit ones, so the finish launch weighs twice as much and the floor sits
+// higher in K than the 16-bit one (32 tiles of 64).  A forced S is taken as given.  Y3_SPLIT_MIN_K_TILES_I8: a variant build for the
+// record, as Y3_SPLIT_MIN_K_TILES_BF16 above (the sweep file was taken with 0, so that its "rule" column is y3_choose_split_k alone).
+#ifndef Y3_SPLIT_MIN_K_TILES_I8
+#define Y3_SPLIT_MIN_K_TILES_I8 36
+#endif
+constexpr int kSplitMinKTilesI8 = Y3_SPLIT_MIN_K_TILES_I8;
+
+// int8: tiles 11 and 12 (LDS-DMA, BK = 128 channels, 32x32x32 MFMA); the slabs hold raw i32 sums and the finish launch stores int8 in whole
+// 16-byte pieces of 16 channels (a conv that writes an fp32 net output itself takes any Cout).  Acts on the int8 convs of an int8 plan only:
+// the fp16 convs before the cut stay unsplit under every switch (resolve_splits).
+constexpr y3::SplitForm I8_SPLIT = {
+    y3::conv_i8_split_tile, y3::launch_conv_i8_split, 128, kSplitMinKTilesI8, &ConvSlot::split_req_i8, &y3_net::low_latency_i8,
+    "y3_net_set_split_k_i8", "y3_net_set_low_latency_i8",
+    [](int) { return "the conv's tile has no split form (tiles 11 and 12 have)"; },
+    "tiles 11 and 12 have",
+    "only Y3_DTYPE_I8 plans take an int8 split", 16, "a split conv storing int8 needs Cout % 16 == 0"};
+
 constexpr y3::ConvFamily F32_FAMILY = {
     y3::TILE_COUNT, y3::conv_tile_info, y3::conv_tile_built, &ConvSlot::tile, &ConvSlot::cout_pad,
     "y3_net_set_tile: bad argument", "y3_net_set_tile: tile id %d is retired (the timing ablations of rounds 1-2; y3_tile_built)",
@@ -534,12 +557,13 @@ constexpr y3::ConvFamily X2_FAMILY = {
 
 // int8 plans (Y3_DTYPE_I8): the convs from the cut on (y3_plan.cpp, resolve_i8).  The bf16 family's tile ids and forced-tile field (a
 // forced tile without an int8 form, or one that does not fit, leaves the conv to the chooser), the bf16 refine rule, int8 weights over Cout
-// padded to 64; the fused stem is the fp16 plans' (it runs before the cut, behind y3_net_set_stem_fusion_f16); no split form.
+// padded to 64; the fused stem is the fp16 plans' (it runs before the cut, behind y3_net_set_stem_fusion_f16); the split form behind
+// switches of its own (y3_net_set_low_latency_i8 / _split_k_i8), off by default.
 constexpr y3::ConvFamily I8_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_i8_tile_info, y3::conv_i8_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad64,
     BF16_FAMILY.bad, BF16_FAMILY.retired, BF16_FAMILY.misfit, -1, nullptr,
     &ConvSlot::wi8_dev, 1, choose_tile_i8, y3::launch_conv_i8, refine_bf16, y3::launch_conv_stem_f16, &ConvSlot::w0norm_dev, &ConvSlot::scale0norm_dev,
-    &y3_net::stem_mode_f16, nullptr};
+    &y3_net::stem_mode_f16, &I8_SPLIT};
 
 // "forced tile, else the family's chooser": the tile part of the launch decision.  (A forced tile was checked by its setter against the
 // family it was forced for; an int8 plan shares the bf16 field, so the check is made again here.)
@@ -615,7 +639,7 @@ static y3_status set_forced_tile(const y3::ConvFamily &f, y3_net *net, int slot,
     return Y3_OK;
 }
 
-// ---- split-K (low-latency fp32, bf16 and fp16 plans) --------------------------------------------------------------------------------
+// ---- split-K (low-latency fp32, bf16, fp16 and int8 plans) --------------------------------------------------------------------------------
 // Can conv `slot` ever run split in the mode of `f` (which has a split form)?  From the graph and the forced tile alone (no plan needed):
 // not the first layer, not a detection head (y3_net_detect runs the heads through conv_head.hip / decodes them in the launch, and the
 // composed route must stay bit-identical to it), only on the tiles the split form is built for, and with a Cout the mode's finish launch
@@ -643,13 +667,17 @@ static bool split_eligible(const y3::ConvFamily &f, const y3_net *net, int slot,
 y3_status y3::resolve_splits(y3_net *net)
 {
     if (!net->height) return Y3_OK;
-    const ConvFamily &f = family_of(net);
     size_t lane_bytes = 0;
     for (int oi = 0; oi < (int)net->ops.size(); ++oi) {
         if (net->ops[oi].kind != 0) continue;
         const int slot = net->ops[oi].index;
         ConvSlot &c = net->convs[slot];
         c.split_k = 1;
+        // an int8 plan is mixed: its convs before the cut launch what an fp16 plan launches and stay unsplit under every switch (their K
+        // is at most 9 tiles of 64, below the 16-bit floor); from the cut on the int8 family decides
+        if (net->dtype == Y3_DTYPE_I8 && !conv_is_i8(net, slot)) continue;
+        const ConvFamily &f = family_of_conv(net, slot);
+        const int cout_pad = c.*f.cout_pad;
         // a mode with a split form splits by its own request and switch; the rule and its inputs are the same for all
         if (!f.split || !split_eligible(f, net, slot, nullptr)) continue;
         const SplitForm &sf = *f.split;
@@ -660,8 +688,8 @@ y3_status y3::resolve_splits(y3_net *net)
         if (!sf.tile(ch.tile)) continue;                       // the tile at the planned rows has no split form (bf16: 8 instead of 11 / 12)
         const long long M = (long long)net->max_batch * (net->height / c.d.out_div) * (net->width / c.d.out_div);
         const TileInfo t = f.info(ch.tile);
-        const long long tiles = ((M + t.bm - 1) / t.bm) * (c.cout_pad / t.bn);
-        const size_t slab = split_slab_bytes(t, M, c.cout_pad);
+        const long long tiles = ((M + t.bm - 1) / t.bm) * (cout_pad / t.bn);
+        const size_t slab = split_slab_bytes(t, M, cout_pad);
         const int kt = c.K / sf.bk;
         if (req < 0 && kt < sf.min_k_tiles) continue;          // the mode's floor (kSplitMinKTilesBf16 says why); a forced S is taken as given
         int S = req > 1 ? req : y3_choose_split_k(tiles, kt, net->n_cus, (long long)slab);
@@ -695,7 +723,7 @@ static y3_status resolve_splits_of_setter(y3_net *net)
     return y3::resolve_splits(net);
 }
 
-// The one body of y3_net_set_low_latency / _bf16 / _f16.  was_set: the flag that records the call (fp32: the Y3_LOW_LATENCY override then stays out)
+// The one body of y3_net_set_low_latency / _bf16 / _f16 / _i8.  was_set: the flag that records the call (fp32: the Y3_LOW_LATENCY override then stays out)
 static y3_status set_low_latency(const y3::ConvFamily &f, y3_net *net, int on, bool y3_net::*was_set = nullptr)
 {
     if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "%s: argument must be 0 or 1", f.split->set_switch);
@@ -704,7 +732,7 @@ static y3_status set_low_latency(const y3::ConvFamily &f, y3_net *net, int on, b
     return resolve_splits_of_setter(net);
 }
 
-// The one body of y3_net_set_split_k / _bf16 / _f16: the request of the mode of `f`; a forced S only where the conv can take it
+// The one body of y3_net_set_split_k / _bf16 / _f16 / _i8: the request of the mode of `f`; a forced S only where the conv can take it
 static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int S)
 {
     const y3::SplitForm &sf = *f.split;
@@ -715,6 +743,9 @@ static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int
         const char *why = nullptr;
         if (!split_eligible(f, net, slot, &why)) return fail(Y3_ERR_INVALID, "%s: conv %d: %s", sf.set_split, slot, why);
         if (net->height && &y3::family_of(net) != &f) return fail(Y3_ERR_INVALID, "%s: conv %d: %s", sf.set_split, slot, sf.other_plan);
+        if (net->height && &y3::family_of_conv(net, slot) != &f)   // an int8 plan's convs before the cut
+            return fail(Y3_ERR_INVALID, "%s: conv %d runs in fp16 in this plan (it lies before the int8 cut, conv %d), and the fp16 convs of an int8 plan are never split",
+                        sf.set_split, slot, net->i8_first_conv);
         if (const int oi = y3::conv_op(net, slot); net->height && oi >= 0) {
             const y3::ConvChoice ch = y3::choose_conv_planned(net, oi);   // .tile: the conv's tile at the planned rows, split or not
             if (ch.kind == y3::ConvKind::Stem || ch.kind == y3::ConvKind::InStem)
@@ -728,7 +759,7 @@ static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int
     return resolve_splits_of_setter(net);
 }
 
-// y3_net_get_split_k / _bf16 / _f16: the split in force when the net is planned in the mode of `f`, 1 otherwise
+// y3_net_get_split_k / _bf16 / _f16 / _i8: the split in force when the net is planned in the mode of `f`, 1 otherwise
 static int split_in_force(const y3::ConvFamily &f, const y3_net *net, int slot)
 {
     if (!net || slot < 0 || slot >= (int)net->convs.size() || !net->height || &y3::family_of(net) != &f) return 1;
@@ -1012,6 +1043,14 @@ y3_status y3_net_set_split_k_f16(y3_net *net, int slot, int S)
 try { return set_split_k(F16_FAMILY, net, slot, S); }
 Y3_CATCH("y3_net_set_split_k_f16")
 
+y3_status y3_net_set_low_latency_i8(y3_net *net, int on)
+try { return set_low_latency(I8_FAMILY, net, on); }
+Y3_CATCH("y3_net_set_low_latency_i8")
+
+y3_status y3_net_set_split_k_i8(y3_net *net, int slot, int S)
+try { return set_split_k(I8_FAMILY, net, slot, S); }
+Y3_CATCH("y3_net_set_split_k_i8")
+
 y3_status y3_net_set_xcd_mode(y3_net *net, int mode)
 try {
     if (!net || mode < 0 || mode > 1) return fail(Y3_ERR_INVALID, "y3_net_set_xcd_mode: mode must be 0 or 1");
@@ -1063,6 +1102,8 @@ int y3_net_get_split_k(const y3_net *net, int slot) { return split_in_force(F32_
 int y3_net_get_split_k_bf16(const y3_net *net, int slot) { return split_in_force(BF16_FAMILY, net, slot); }
 
 int y3_net_get_split_k_f16(const y3_net *net, int slot) { return split_in_force(F16_FAMILY, net, slot); }
+
+int y3_net_get_split_k_i8(const y3_net *net, int slot) { return split_in_force(I8_FAMILY, net, slot); }
 
 int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_bytes_per_slice)
 {

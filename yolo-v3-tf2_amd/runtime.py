@@ -231,7 +231,7 @@ class Net:
             raise Y3Error(f"{who}: conv slot must be an int in [0, {len(self.conv_ops)}) (got {slot!r})")
         return int(slot)
 
-    def _set_low_latency(self, sfx: str, on):   # sfx, here and below: "" the fp32 plans' entry points, "_bf16" the bf16 plans', "_f16" the fp16 plans'
+    def _set_low_latency(self, sfx: str, on):   # sfx, here and below: "" the fp32 plans' entry points, "_bf16" the bf16 plans', "_f16" the fp16 plans', "_i8" the int8 plans'
         on = int(self._low_latency_arg(on))     # the argument checks come first: they need no device net
         check(getattr(self.lib, "y3_net_set_low_latency" + sfx)(self._h, on), "y3_net_set_low_latency" + sfx)
 
@@ -287,6 +287,22 @@ class Net:
     def split_k_f16(self, slot: int) -> int:
         """K slices in force for conv `slot` in an fp16 plan after plan() (1: the ordinary launch; 1 on every other plan)."""
         return self._split_k("_f16", slot)
+
+    def set_low_latency_i8(self, on=True):
+        """Low-latency int8 plan for one to eight images (y3_net_set_low_latency_i8): as set_low_latency_f16, for a plan made with
+        Y3_DTYPE_I8.  It acts on the int8 convs (from i8_first_conv() on); the fp16 convs before the cut stay unsplit.  The slices hold
+        i32 sums, so the results are the default int8 plan's bit for bit.  The four switches are independent.  None means off."""
+        self._set_low_latency("_i8", on)
+
+    def set_split_k_i8(self, slot: int, S: int):
+        """K slices of conv `slot` in an int8 plan: -1 the heuristic (in force only with set_low_latency_i8), 1 off, 2..16 forced.
+        An ineligible conv (first layer, a detection head, a tile other than 11 / 12, a conv before the cut of a planned int8 net, a
+        plan that is not int8) or S above the conv's K tiles (K / 128) raises here."""
+        self._set_split_k("_i8", slot, S)
+
+    def split_k_i8(self, slot: int) -> int:
+        """K slices in force for conv `slot` in an int8 plan after plan() (1: the ordinary launch; 1 on every other plan)."""
+        return self._split_k("_i8", slot)
 
     @staticmethod
     def _stem_fusion_arg(on) -> int:

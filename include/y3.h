@@ -557,6 +557,43 @@ y3_status y3_evaluate_detections(const void *packed_dev, const int32_t *num_vali
                                  int64_t *counters_dev, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Matching for COCO-style average precision, from the same detect pass.  NO reference counterpart (the reference stops at the
+ * counters above, whose quirk -- two predictions on one ground-truth box are both TP -- makes them incomparable with a published
+ * mAP).  The rule is this project's statement of the COCO matching: greedy in score order, a ground-truth box matched at most once
+ * per IoU threshold; no crowd flags, no area ranges, max_boxes as the per-image cap.  The tie direction is recalled from the
+ * COCO evaluation's loop, not checked against pycocotools.
+ * Inputs exactly as for y3_evaluate_detections: packed_dev [batch,max_boxes,7], num_valid_dev clamped to [0,max_boxes], padded
+ * ground truth with counts clamped to [0,max_gt].  iou_thresholds_host [n_iou] fp32 is read during the call (the thresholds
+ * travel in the kernel arguments).  Per image b:
+ *   one_class != 0  every row class and every ground-truth class is taken as 0
+ *   error image     a ground-truth class outside [0,nclasses), or the class of a row r < num_valid[b] outside [0,nclasses) (both
+ *                   after one_class): gt_totals[nclasses] += 1 and nothing else; all its record rows are written as invalid
+ *   IoU             the fp32 expression of y3_evaluate_detections, computed by the same device function
+ *   matching        per threshold t_k, independently: the rows are walked in ROW ORDER r = 0 .. num_valid-1.  y3_net_detect writes
+ *                   them in descending score; the call does NOT sort.  Row r may take ground-truth row g when the classes are
+ *                   equal, g is not yet taken at this threshold and iou(r,g) >= t_k in fp32 (a NaN never qualifies).  Among those
+ *                   it takes the largest IoU (compared as fp32 values: -0 equals +0), the HIGHER g on a tie; bit k of the row's
+ *                   mask is set and g is taken at threshold k.  The masks of different thresholds are independent: a row can
+ *                   match at 0.75 and not at 0.5, when a better-scored row took its box at 0.5 and fails at 0.75
+ *   records         records_dev uint32 [batch][max_boxes][2]: {score bits, class | mask << 16} for r < num_valid[b] of a counted
+ *                   image (the class after one_class), {0, 0xFFFFFFFF} for every other row.  EVERY row is written, the buffer may
+ *                   be uninitialised; fixed slots, no cursor: the record order is a function of the input order alone
+ *   gt_totals       gt_totals_dev int64 [nclasses + 2]: [c] += 1 per ground-truth row of class c, [nclasses] += 1 per error image,
+ *                   [nclasses + 1] += 1 per counted image.  ADDED to, never zeroed, like counters_dev
+ * Checked on the host before anything is enqueued (Y3_ERR_INVALID with a message): batch >= 1, max_boxes in [1,1024], max_gt in
+ * [1,1024], nclasses in [1,4096], n_iou in [1,16], finite thresholds, no null pointer, records / gt_totals 8-byte aligned.  The
+ * call only enqueues on `stream` -- no allocation, query or synchronise -- and can be captured into a HIP graph (the thresholds
+ * are then frozen in).  LDS: 20 max_gt + 24 max_boxes + 4 nclasses bytes, at most 60 KB.
+ * Host restatement: evaluate_detections.match_detections; the AP integral over a data set's records:
+ * evaluate_detections.average_precision.
+ * ---------------------------------------------------------------------------------------- */
+y3_status y3_match_detections(const void *packed_dev, const int32_t *num_valid_dev, int batch, int max_boxes,
+                              const float *gt_boxes_dev /*[batch,max_gt,4]*/, const int32_t *gt_classes_dev /*[batch,max_gt]*/,
+                              const int32_t *gt_count_dev /*[batch]*/, int max_gt, int nclasses, const float *iou_thresholds_host,
+                              int n_iou, int one_class, uint32_t *records_dev /*[batch][max_boxes][2]*/,
+                              int64_t *gt_totals_dev /*[nclasses + 2]*/, void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Validation loss from the raw head grids (reference: core/preprocess_dataset.py:19-92, _arrange_in_grid; core/loss_func.py:19-69,
  * get_loss_func; train.py:39-54, _calc_loss).  The reference picks a checkpoint by val_loss; these two calls give its four sums
  * (xy, wh, obj, class) per image and scale from the grids y3_net_forward writes.  No gradient is taken and nothing here trains;

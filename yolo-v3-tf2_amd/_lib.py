@@ -154,6 +154,7 @@ SYMBOLS = {
     "y3_unletterbox_detections": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp]),
     "y3_unletterbox_detections_hw": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _i, _vp]),
     "y3_evaluate_detections": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _f, _fp, _i, _i, _vp, _vp]),
+    "y3_match_detections": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _fp, _i, _i, _vp, _vp, _vp]),
     "y3_yolo_assign_targets": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_int32), _fp, _vp, _vp]),
     "y3_yolo_loss": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _i, _vp, _vp]),
     "y3_yolo_decode": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),

@@ -8,7 +8,8 @@
 // the active rows are counted into per-class LDS counters, and the non-zero ones are added to the caller's int64 counters with
 // 64-bit vector atomic adds.  Integer adds commute: the result does not depend on the order the workgroups arrive in.
 // IoU in fp32, each operation rounded on its own (the library is built with -ffp-contract=off), minimum / maximum and arg-max
-// with NumPy's NaN rules: host restatement evaluate_detections.sweep_counters, bit for bit.
+// with NumPy's NaN rules (box_iou.h, the body ap_match.hip shares): host restatement evaluate_detections.sweep_counters, bit for bit.
+#include "box_iou.h"
 #include "y3_kernels.h"
 
 namespace y3 {
@@ -18,10 +19,6 @@ namespace {
 constexpr int kEvalThreads = 256;
 constexpr int kEvalRowsPerThread = kEvalMaxBoxes / kEvalThreads;
 static_assert(kEvalRowsPerThread * kEvalThreads == kEvalMaxBoxes, "a thread owns max_boxes / 256 rows");
-
-// np.maximum / np.minimum: a NaN in either operand is the result
-__device__ __forceinline__ float np_max(float a, float b) { return (a >= b || a != a) ? a : b; }
-__device__ __forceinline__ float np_min(float a, float b) { return (a <= b || a != a) ? a : b; }
 
 }  // namespace
 
@@ -82,11 +79,7 @@ __global__ __launch_bounds__(kEvalThreads) void evaluate_kernel(const unsigned *
             float bv = 0.0f;
             for (int g = 0; g < g_n; ++g) {
                 const float4 q = *reinterpret_cast<const float4 *>(s_box + g * 4);   // every lane reads the same row: a broadcast
-                const float ow = np_max(np_min(x2, q.z) - np_max(x1, q.x), 0.0f);
-                const float oh = np_max(np_min(y2, q.w) - np_max(y1, q.y), 0.0f);
-                const float inter = ow * oh;
-                const float a2 = (q.z - q.x) * (q.w - q.y);
-                const float iou = inter / ((a1 + a2) - inter);
+                const float iou = box_iou(x1, y1, x2, y2, a1, q);
                 if (g == 0 || (bv == bv && !(iou <= bv))) {   // np.argmax: the first NaN ends the search
                     bv = iou;
                     best[k] = g;

@@ -317,6 +317,13 @@ hipError_t launch_evaluate(const void *packed, const int32_t *nv, int B, int M, 
                            const int32_t *gt_count, int G, int nc, float iou_thr, const EvalThresholds &thr, int T, int one_class,
                            int64_t *counters, hipStream_t s);
 
+// Matching for average precision (ap_match.hip; include/y3.h, y3_match_detections): the same inputs and limits, the IoU thresholds
+// of one launch by value in the kernel arguments (thr.s[0 .. K)), one wave per threshold.
+size_t ap_match_lds_bytes(int max_boxes, int max_gt, int nclasses);
+hipError_t launch_ap_match(const void *packed, const int32_t *nv, int B, int M, const float *gt_boxes, const int32_t *gt_classes,
+                           const int32_t *gt_count, int G, int nc, const EvalThresholds &thr, int K, int one_class, uint32_t *records,
+                           int64_t *totals, hipStream_t s);
+
 // Validation loss (loss.hip; include/y3.h, y3_yolo_assign_targets / y3_yolo_loss).  Grid sizes, the first decode row of each scale and the
 // anchors travel by value in the kernel arguments.  A grid side is at most kLossMaxGrid: row indices stay far inside an int and the
 // bitmap of a scale's rows inside LDS.

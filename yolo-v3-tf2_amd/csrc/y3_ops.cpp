@@ -267,6 +267,38 @@ try {
 }
 Y3_CATCH("y3_evaluate_detections")
 
+y3_status y3_match_detections(const void *packed_dev, const int32_t *num_valid_dev, int batch, int max_boxes,
+                              const float *gt_boxes_dev, const int32_t *gt_classes_dev, const int32_t *gt_count_dev, int max_gt,
+                              int nclasses, const float *iou_thresholds_host, int n_iou, int one_class, uint32_t *records_dev,
+                              int64_t *gt_totals_dev, void *stream)
+try {
+    if (!packed_dev || !num_valid_dev || !gt_boxes_dev || !gt_classes_dev || !gt_count_dev || !iou_thresholds_host || !records_dev ||
+        !gt_totals_dev)
+        return fail(Y3_ERR_INVALID, "y3_match_detections: null pointer");
+    if (batch < 1) return fail(Y3_ERR_INVALID, "y3_match_detections: batch must be at least 1 (got %d)", batch);
+    if (max_boxes < 1 || max_boxes > y3::kEvalMaxBoxes)
+        return fail(Y3_ERR_INVALID, "y3_match_detections: max_boxes must be in [1,%d] (got %d)", y3::kEvalMaxBoxes, max_boxes);
+    if (max_gt < 1 || max_gt > y3::kEvalMaxGt)
+        return fail(Y3_ERR_INVALID, "y3_match_detections: max_gt must be in [1,%d] (got %d)", y3::kEvalMaxGt, max_gt);
+    if (nclasses < 1 || nclasses > y3::kEvalMaxClasses)
+        return fail(Y3_ERR_INVALID, "y3_match_detections: nclasses must be in [1,%d] (got %d)", y3::kEvalMaxClasses, nclasses);
+    if (n_iou < 1 || n_iou > y3::kEvalMaxThresholds)
+        return fail(Y3_ERR_INVALID, "y3_match_detections: n_iou must be in [1,%d] (got %d)", y3::kEvalMaxThresholds, n_iou);
+    y3::EvalThresholds thr{};
+    for (int k = 0; k < n_iou; ++k) {
+        if (!std::isfinite(iou_thresholds_host[k]))
+            return fail(Y3_ERR_INVALID, "y3_match_detections: iou_thresholds[%d] is not finite", k);
+        thr.s[k] = iou_thresholds_host[k];
+    }
+    if (((uintptr_t)packed_dev & 3) || ((uintptr_t)gt_boxes_dev & 3) || ((uintptr_t)records_dev & 7) || ((uintptr_t)gt_totals_dev & 7))
+        return fail(Y3_ERR_INVALID, "y3_match_detections: packed / gt_boxes not 4-byte or records / gt_totals not 8-byte aligned");
+    hipError_t e = y3::launch_ap_match(packed_dev, num_valid_dev, batch, max_boxes, gt_boxes_dev, gt_classes_dev, gt_count_dev, max_gt,
+                                       nclasses, thr, n_iou, one_class != 0, records_dev, gt_totals_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_match_detections launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_match_detections")
+
 // ------------------------------------------------------------------------------------------ validation loss
 namespace {
 // The checks and the by-value geometry the two loss entries share: grid sizes, first decode row per scale, anchors.

@@ -87,8 +87,16 @@ def report_loss(loss):
     return val_loss, per_grid, per_source
 
 
+def report_ap(ap, iou_thresholds):
+    """Prints AP50 and AP75 (when those IoU thresholds are among iou_thresholds) and mAP of Net.evaluate_stream's AP dict."""
+    parts = [f'AP{int(round(100 * float(t)))}:{ap["map"][k]:.4f}' for k, t in enumerate(iou_thresholds)
+             if any(np.float32(t) == np.float32(v) for v in (0.5, 0.75))]
+    lo, hi = float(min(iou_thresholds)), float(max(iou_thresholds))
+    print(", ".join(parts + [f'mAP@[{lo:.2f}:{hi:.2f}]:{ap["mAP"]:.4f}', f'images:{ap["images"]}', f'errors:{ap["errors"]}']))
+
+
 def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_batches, weights, one_class, anchors_table, nclasses,
-                        loss=False):
+                        loss=False, ap=None):
     """One model and one pass: the un-stacked data set is batched here (images with unlike numbers of boxes may share a batch)
     by a generator that Net.evaluate_stream draws from, so records are decoded while earlier batches run and the data set is
     never held in memory; only the counters come back."""
@@ -135,7 +143,10 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     out = net.evaluate_stream(frames(), ground_truth(), anchors_table, max_boxes, detect_config["nms_iou_threshold"],
                               thresholds, nclasses, evaluate_iou_threshold=evaluate_iou_threshold,
                               one_class="both" if one_class else False, mode=0, max_batch=batch_size,
-                              max_blob_bytes=batch_size * (S * S * 12 + 16), max_gt=max_boxes, loss=loss)
+                              max_blob_bytes=batch_size * (S * S * 12 + 16), max_gt=max_boxes, loss=loss, ap=ap)
+    out, ap_result = (out[:-1], out[-1]) if ap is not None else (out, None)
+    if ap is not None:
+        out = out if loss else out[0]
     out, loss_sums = out if loss else (out, None)
     plain, one = out if one_class else (out, None)
     results = []
@@ -146,12 +157,16 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
         results.append((threshold, recall, precision, counters, counters_oneclass))
     if loss:
         report_loss(loss_sums)
-        return results, loss_sums
+    if ap is not None:
+        from .runtime import ap_iou_thresholds
+        report_ap(ap_result, ap_iou_thresholds(ap))
+    if loss or ap is not None:
+        return (results,) + ((loss_sums,) if loss else ()) + ((ap_result,) if ap is not None else ())
     return results
 
 
 def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshold=0.5, max_batches=20, weights=None,
-             one_class=True, on_device=False, loss=False):
+             one_class=True, on_device=False, loss=False, ap=None):
     """The loop of reference evaluate_yolov3.py:153-232: for every score threshold build the detect model, run the
     first `max_batches` dataset batches (`dataset.take(20)` there), count, and report (recall, precision).
     Returns [(threshold, recall, precision, counters, counters_oneclass)].
@@ -163,16 +178,24 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     val_loss, perGrid and perSource[xy,wh,obj,class] are printed as the reference's eager loop prints them (train.py:86-91) and
     the return value becomes (results, {"sum": float64 [3,4], "images": int, "errors": int}) as Net.evaluate_stream gives it.
     The regulariser (model.losses, decay_factor) that the reference's totLoss includes is not part of it.
+    ap=True or a sequence of IoU thresholds (with on_device=True): COCO-style average precision from the same pass, matched on the
+    GPU (Net.evaluate_stream, ap=; True means the ten thresholds 0.5 ... 0.95).  AP50, AP75 (when those thresholds are present) and
+    mAP are printed and the dict of evaluate_detections.average_precision is returned after the existing results: (results, ap)
+    or (results, loss, ap).  AP is no reference counterpart; it is taken over the detections at the LOWEST of
+    evaluate_nms_score_thresholds, with the class ids as they are (the plain variant, whatever one_class says).
     An optional `dtype: f32 | bf16 | f16` key of detect_config selects the conv arithmetic of the on_device pass (absent: f32);
     an optional `f16_fused_stem: true` runs the first convs of an f16 plan as the fused stem kernel (absent: off)."""
     if loss and not on_device:
         raise ValueError("evaluate: loss=True needs on_device=True (the loss is computed on the GPU, from the device pass)")
+    ap = None if ap is False else ap
+    if ap is not None and not on_device:
+        raise ValueError("evaluate: ap needs on_device=True (the detections are matched on the GPU, in the device pass)")
     anchors_table = np.asarray(get_anchors(detect_config["anchors_file"]), np.float32)
     class_names = [c.strip() for c in open(detect_config["classes_name_file"]).readlines()]
     nclasses = len(class_names)
     if on_device:
         return _evaluate_on_device(detect_config, list(evaluate_nms_score_thresholds), evaluate_iou_threshold, max_batches, weights,
-                                   one_class, anchors_table, nclasses, loss=loss)
+                                   one_class, anchors_table, nclasses, loss=loss, ap=ap)
     dataset = prepare_dataset(detect_config["tfrecords_dir"], detect_config["batch_size"], detect_config["image_size"],
                               detect_config["yolo_max_boxes"], detect_config["classes_name_file"])
     results = []
@@ -208,16 +231,23 @@ def main(argv=None):
                     help="one pass over the data set for all thresholds, counters computed on the GPU")
     ap.add_argument("--loss", action="store_true",
                     help="with --on-device: also val_loss, perGrid and perSource[xy,wh,obj,class] from the same pass")
+    ap.add_argument("--ap", action="store_true",
+                    help="with --on-device: also COCO-style AP50, AP75 and mAP from the same pass (IoU thresholds: the optional "
+                         "evaluate_ap_iou_thresholds key of the evaluate config, by default 0.5, 0.55, ..., 0.95)")
     a = ap.parse_args(argv)
     if a.loss and not a.on_device:
         ap.error("--loss needs --on-device")
+    if a.ap and not a.on_device:
+        ap.error("--ap needs --on-device")
     with open(a.evaluate_config) as s:
-        thresholds = yaml.safe_load(s)["evaluate_nms_score_thresholds"]
+        evaluate_config = yaml.safe_load(s)
+    thresholds = evaluate_config["evaluate_nms_score_thresholds"]
+    ap_thresholds = (evaluate_config.get("evaluate_ap_iou_thresholds") or True) if a.ap else None
     with open(a.config) as s:
         detect_config = yaml.safe_load(s)
-    results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss)
-    if a.loss:
-        results = results[0]      # the loss has been printed by evaluate
+    results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss, ap=ap_thresholds)
+    if a.loss or a.ap:
+        results = results[0]      # the loss and the AP have been printed by evaluate
     print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in results])
 
 

@@ -716,7 +716,7 @@ class Net:
     def evaluate_stream(self, batches, gts, anchors, max_boxes: int, iou_threshold: float, score_thresholds, nclasses: int,
                         evaluate_iou_threshold: float = 0.5, one_class=False, mode=1, depth: int = 2,
                         max_batch: Optional[int] = None, max_blob_bytes: Optional[int] = None, letterbox=False,
-                        max_gt: Optional[int] = None, loss=False):
+                        max_gt: Optional[int] = None, loss=False, ap=None):
         """Frames in host memory -> the evaluation counters of EVERY NMS score threshold, from one detect pass: NumPy int64
         [T, 5*nclasses + 2] (rows as y3_evaluate_detections / evaluate_detections.counters_from_row name them), T =
         len(score_thresholds).  one_class=True: every class id taken as 0; one_class="both": the pair (plain counters,
@@ -743,8 +743,20 @@ class Net:
         grids with the ground truth already on the device, and the sums come back with the counters in the one final copy.
         nclasses must be the program's.  Not together with letterbox=True: the reference trains on letterboxed images with
         unmapped boxes, and mapping the ground truth onto the canvas is a decision this method does not take.  Not on a
-        non-square (H, W) plan either: y3_yolo_assign_targets / y3_yolo_loss take one g per scale."""
+        non-square (H, W) plan either: y3_yolo_assign_targets / y3_yolo_loss take one g per scale.
+        ap=True (or a sequence of 1 to 16 IoU thresholds; True means 0.5, 0.55, ..., 0.95): COCO-style average precision from
+        the same pass; the return value gains a LAST element, the dict of evaluate_detections.average_precision ("ap" float64
+        [K, nclasses], "map" [K], "mAP", "images", "errors").  Per batch ONE y3_match_detections is enqueued on the same
+        stream behind y3_evaluate_detections, on the same packed rows (already in frame coordinates with letterbox=True) and
+        the same ground-truth words; its records (8 bytes per packed row) stay on the device until the stream ends and come
+        back with the counters, and the integral is taken on the host.  The rows of y3_net_detect at min(score_thresholds)
+        are what is matched: pass a low score threshold for a meaningful AP.  one_class=True matches with every class taken
+        as 0; with one_class="both" AP follows the plain variant.  AP has no reference counterpart: the matching rule (greedy
+        in score order, a ground-truth box matched at most once per IoU threshold; no crowd flags, no area ranges, max_boxes
+        as the per-image cap) is this project's statement of the COCO matching and is not checked against pycocotools.
+        ap=None enqueues nothing new and returns exactly what is described above."""
         thresholds = [float(t) for t in score_thresholds]
+        ap_thr = None if ap is None or ap is False else ap_iou_thresholds(ap)
         if loss and letterbox:
             raise Y3Error("evaluate_stream: loss=True cannot be combined with letterbox=True (the ground truth is not mapped onto the canvas)")
         if loss and self.canvas[0] != self.canvas[1]:
@@ -769,6 +781,8 @@ class Net:
         thr = np.asarray(thresholds, np.float32)
         counters = None
         n_counters = len(variants) * T * (5 * nc + 2)
+        n_loss, n_ap = (14 if loss else 0), (nc + 2 if ap_thr is not None else 0)
+        ap_records = []     # per batch, the [n, M, 2] records: on the device until the stream ends
         a = np.ascontiguousarray(np.asarray(anchors, np.float32).reshape(3, 3, 2))
         slots = {}      # ring slot -> pinned ground-truth words, their device copy, "copied" event
         for i, handle, packed_dev, nv_dev, cur, stage, grids in self._detect_batches(
@@ -783,10 +797,11 @@ class Net:
                 raise Y3Error(f"evaluate_stream: batch {i} has {n} frames, its ground truth {len(gt)} entries")
             if counters is None:
                 # one buffer of 64-bit words, read back once: the counters, then (loss) the [3,4] float64 sums, the images counted and the errors
-                result = torch.zeros(n_counters + (14 if loss else 0), dtype=torch.int64, device=stage.device)
+                # ... then (ap) the nclasses + 2 ground-truth totals of y3_match_detections
+                result = torch.zeros(n_counters + n_loss + n_ap, dtype=torch.int64, device=stage.device)
                 counters = result[:n_counters].view(len(variants), T, 5 * nc + 2)
                 if loss:
-                    loss_sum, loss_images = result[n_counters:n_counters + 12].view(torch.float64).view(3, 4), result[n_counters + 12:]
+                    loss_sum, loss_images = result[n_counters:n_counters + 12].view(torch.float64).view(3, 4), result[n_counters + 12:n_counters + 14]
                     cells_d = torch.empty((stage.max_batch, G), dtype=torch.int32, device=stage.device)
                     loss_d = torch.empty((stage.max_batch, 3, 4), dtype=torch.float64, device=stage.device)
                     gs = [g for g, _ in self._grid_hw()]
@@ -808,6 +823,11 @@ class Net:
                 check(self.lib.y3_evaluate_detections(_dev(packed_dev), _dev(nv_dev), n, M, _dev(boxes_d), _dev(classes_d),
                                                       _dev(count_d), G, nc, float(evaluate_iou_threshold), _fptr(thr), T, oc,
                                                       _dev(counters[v]), C.c_void_p(cur.cuda_stream)), "y3_evaluate_detections")
+            if ap_thr is not None:
+                ap_records.append(torch.empty((n, M, 2), dtype=torch.int32, device=stage.device))
+                check(self.lib.y3_match_detections(_dev(packed_dev), _dev(nv_dev), n, M, _dev(boxes_d), _dev(classes_d), _dev(count_d),
+                                                   G, nc, _fptr(ap_thr), len(ap_thr), variants[0], _dev(ap_records[-1]),
+                                                   _dev(result[n_counters + n_loss:]), C.c_void_p(cur.cuda_stream)), "y3_match_detections")
             if loss:
                 assign_targets(boxes_d.view(torch.float32), classes_d, count_d, a, gs, nc, cells=cells_d[:n])
                 yolo_loss(grids, a, nc, boxes_d.view(torch.float32), classes_d, cells_d[:n], loss=loss_d[:n])
@@ -817,15 +837,22 @@ class Net:
         if next(gt_iter, missing) is not missing:
             raise Y3Error("evaluate_stream: `gts` has more entries than there are batches")
         if counters is None:
-            out = np.zeros(n_counters + (14 if loss else 0), np.int64)
+            out = np.zeros(n_counters + n_loss + n_ap, np.int64)
         else:
             out = result.cpu().numpy()      # the one read-back: waits for the stream
         words, out = out, out[:n_counters].reshape(len(variants), T, 5 * nc + 2)
         counted = (out[0], out[1]) if both else out[0]
-        if not loss:
+        if not loss and ap_thr is None:
             return counted
-        return counted, {"sum": words[n_counters:n_counters + 12].view(np.float64).reshape(3, 4).copy(),
-                         "images": int(words[n_counters + 12]), "errors": int(words[n_counters + 13])}
+        ret = [counted]
+        if loss:
+            ret.append({"sum": words[n_counters:n_counters + 12].view(np.float64).reshape(3, 4).copy(),
+                        "images": int(words[n_counters + 12]), "errors": int(words[n_counters + 13])})
+        if ap_thr is not None:
+            from .evaluate_detections import average_precision
+            rec = torch.cat(ap_records).cpu().numpy() if ap_records else np.zeros((0, M, 2), np.int32)   # behind the read-back above
+            ret.append(average_precision(rec.view(np.uint32), words[n_counters + n_loss:], nc, len(ap_thr)))
+        return tuple(ret)
 
     def flops_per_image(self) -> float:
         return float(self.lib.y3_net_flops_per_image(self._h))
@@ -1112,6 +1139,55 @@ def evaluate_detections(packed: torch.Tensor, num_valid: torch.Tensor, gt_boxes:
                                              G, nc, float(iou_threshold), _fptr(thr), len(thr), int(bool(one_class)),
                                              _dev(counters), _lib.stream_ptr()), "y3_evaluate_detections")
     return counters
+
+
+def ap_iou_thresholds(ap):
+    """The `ap` argument of evaluate_stream / evaluate -> its IoU thresholds, float32 [K]: True means the ten thresholds 0.5, 0.55,
+    ..., 0.95 of mAP@[.5:.95] (evaluate_detections.AP_IOU_THRESHOLDS), a sequence means those thresholds."""
+    from .evaluate_detections import AP_IOU_THRESHOLDS
+    thr = AP_IOU_THRESHOLDS if ap is True else np.ascontiguousarray(np.asarray(ap, np.float32).reshape(-1))
+    if not 1 <= len(thr) <= 16 or not np.isfinite(thr).all():
+        raise Y3Error("ap: 1 to 16 finite IoU thresholds (or True for 0.5, 0.55, ..., 0.95)")
+    return thr
+
+
+def match_detections(packed: torch.Tensor, num_valid: torch.Tensor, gt_boxes: torch.Tensor, gt_classes: torch.Tensor,
+                     gt_count: torch.Tensor, nclasses: int, iou_thresholds, one_class=False,
+                     records: Optional[torch.Tensor] = None, gt_totals: Optional[torch.Tensor] = None):
+    """The inputs of evaluate_detections -> (records int32 [B,M,2], gt_totals int64 [nclasses + 2]) on the GPU: per image the
+    greedy matching behind COCO-style average precision, at every IoU threshold of iou_thresholds [K <= 16] (y3_match_detections;
+    host restatement: evaluate_detections.match_detections, which also names the words; evaluate_detections.average_precision
+    integrates the records of a data set).  The rows are matched in ROW order -- Net.detect writes them in descending score --
+    and nothing is sorted.  records: the tensor to write (every row of it is written; torch has no arithmetic on uint32, so the
+    words travel as int32 like the packed rows: .view(np.uint32) on the host); gt_totals=None: a zeroed tensor is made, otherwise
+    the call ADDS to the one given.  Enqueues on the current stream only."""
+    _need_cuda(packed, num_valid, gt_boxes, gt_classes, gt_count, records, gt_totals)
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != 7:
+        raise Y3Error("packed must be contiguous int32 [B,M,7]")
+    B, M = packed.shape[0], packed.shape[1]
+    if num_valid.dtype != torch.int32 or num_valid.shape != (B,):
+        raise Y3Error(f"num_valid must be int32 [{B}]")
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 4:
+        raise Y3Error(f"gt_boxes must be float32 [{B},G,4]")
+    G = gt_boxes.shape[1]
+    if gt_classes.dtype != torch.int32 or gt_classes.shape != (B, G):
+        raise Y3Error(f"gt_classes must be int32 [{B},{G}]")
+    if gt_count.dtype != torch.int32 or gt_count.shape != (B,):
+        raise Y3Error(f"gt_count must be int32 [{B}]")
+    thr = np.ascontiguousarray(np.asarray(iou_thresholds, np.float32).reshape(-1))
+    nc = int(nclasses)
+    if records is None:
+        records = torch.empty((B, M, 2), dtype=torch.int32, device=packed.device)
+    elif records.dtype != torch.int32 or records.shape != (B, M, 2):
+        raise Y3Error(f"records must be int32 [{B},{M},2]")
+    if gt_totals is None:
+        gt_totals = torch.zeros((max(nc, 0) + 2,), dtype=torch.int64, device=packed.device)
+    elif gt_totals.dtype != torch.int64 or gt_totals.shape != (nc + 2,):
+        raise Y3Error(f"gt_totals must be int64 [{nc + 2}]")
+    check(_lib.load().y3_match_detections(_dev(packed), _dev(num_valid), B, M, _dev(gt_boxes), _dev(gt_classes), _dev(gt_count),
+                                          G, nc, _fptr(thr), len(thr), int(bool(one_class)), _dev(records), _dev(gt_totals),
+                                          _lib.stream_ptr()), "y3_match_detections")
+    return records, gt_totals
 
 
 def _gt_args(who, gt_boxes, gt_classes):

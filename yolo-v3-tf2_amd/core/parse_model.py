@@ -31,6 +31,10 @@ class _LoadStatus:
         return self
 
 
+_DEFERRED_DEFAULTS = {"set_low_latency": False, "set_low_latency_f16": False, "set_low_latency_i8": False, "set_stem_fusion_f16": 0,
+                      "load_calibration": None, "set_dtype": None}
+
+
 class YoloModel:
     """Callable network: image batch [B,S,S,3] (fp32, NHWC, values in [0,1]) -> [grid13, grid26, grid52],
     each [B,g,g,3,5+nclasses] (reference: the Keras Model returned by build_model, core/parse_model.py:313)."""
@@ -40,78 +44,66 @@ class YoloModel:
         self.name = name
         self._net = None
         self._weights = None
-        self.low_latency = False
-        self.low_latency_f16 = False
-        self.low_latency_i8 = False
-        self.stem_fusion_f16 = 0
-        self.dtype = None     # None: fp32 (set_dtype)
-        self.i8_calibration = None   # path of the activation scales an "i8" plan needs (set_i8_calibration)
+        # the settings a device net is given when it is made, Net method -> argument, in the order they are applied: the low-latency
+        # switches, stem fusion, the calibration file an "i8" plan needs, the dtype (None: fp32).  An entry at its value here is skipped.
+        self._deferred = dict(_DEFERRED_DEFAULTS)
+
+    def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, i8_calibration, dtype
+        method = {"i8_calibration": "load_calibration"}.get(name, "set_" + name)
+        if method in _DEFERRED_DEFAULTS and "_deferred" in self.__dict__:
+            return self._deferred[method]
+        raise AttributeError(f"{type(self).__name__!r} object has no attribute {name!r}")
 
     # lazily create the device object so that building/inspecting a model works without a GPU
     def _device_net(self):
         if self._net is None:
             from ..runtime import Net
             self._net = Net(self.program)
-            if self.low_latency:
-                self._net.set_low_latency(True)
-            if self.low_latency_f16:
-                self._net.set_low_latency_f16(True)
-            if self.low_latency_i8:
-                self._net.set_low_latency_i8(True)
-            if self.stem_fusion_f16:
-                self._net.set_stem_fusion_f16(self.stem_fusion_f16)
-            if self.i8_calibration:
-                self._net.load_calibration(self.i8_calibration)
-            if self.dtype is not None:
-                self._net.set_dtype(self.dtype)
+            for method, arg in self._deferred.items():
+                if arg != _DEFERRED_DEFAULTS[method]:
+                    getattr(self._net, method)(arg)
             if self._weights is not None:
                 self._net.load_weights(self._weights)
         return self._net
+
+    def _defer(self, method, arg):
+        """Record a validated setting and, when the device net exists, apply it (an unset one is not: there is nothing to undo)."""
+        self._deferred[method] = arg
+        if self._net is not None and (method.startswith("set_") or arg != _DEFERRED_DEFAULTS[method]):
+            getattr(self._net, method)(arg)
 
     def set_low_latency(self, on=True):
         """Low-latency fp32 plans (runtime.Net.set_low_latency): split-K convs for batches of one to eight images.  Takes
         effect at the next plan, i.e. before the first call or when the batch shape changes."""
         from ..runtime import Net
-        self.low_latency = Net._low_latency_arg(on)
-        if self._net is not None:
-            self._net.set_low_latency(self.low_latency)
+        self._defer("set_low_latency", Net._low_latency_arg(on))
 
     def set_low_latency_f16(self, on=True):
         """Low-latency fp16 plans (runtime.Net.set_low_latency_f16): the same for plans made with dtype "f16"."""
         from ..runtime import Net
-        self.low_latency_f16 = Net._low_latency_arg(on)
-        if self._net is not None:
-            self._net.set_low_latency_f16(self.low_latency_f16)
+        self._defer("set_low_latency_f16", Net._low_latency_arg(on))
 
     def set_low_latency_i8(self, on=True):
         """Low-latency int8 plans (runtime.Net.set_low_latency_i8): the same for plans made with dtype "i8"."""
         from ..runtime import Net
-        self.low_latency_i8 = Net._low_latency_arg(on)
-        if self._net is not None:
-            self._net.set_low_latency_i8(self.low_latency_i8)
+        self._defer("set_low_latency_i8", Net._low_latency_arg(on))
 
     def set_stem_fusion_f16(self, on=True):
         """The fused stem kernel for fp16 plans (runtime.Net.set_stem_fusion_f16): off by default; acts on dtype "f16" only."""
         from ..runtime import Net
-        self.stem_fusion_f16 = Net._stem_fusion_arg(on)
-        if self._net is not None:
-            self._net.set_stem_fusion_f16(self.stem_fusion_f16)
+        self._defer("set_stem_fusion_f16", Net._stem_fusion_arg(on))
 
     def set_dtype(self, dtype):
         """Conv arithmetic of the plans (runtime.Net.set_dtype): None or "f32" (default), "bf16", "f16" -- 16-bit activations and
         weights on the matrix cores, fp32 accumulation, fp32 images in and fp32 grids out -- a plane-split mode, or "i8": calibrated
         int8 from the first conv that qualifies on (set_i8_calibration first: the plan needs the activation scales)."""
         from ..runtime import Net
-        self.dtype = Net._dtype_arg(dtype)
-        if self._net is not None:
-            self._net.set_dtype(self.dtype)
+        self._defer("set_dtype", Net._dtype_arg(dtype))
 
     def set_i8_calibration(self, path):
         """The calibration file (tools/calibrate_i8.py; runtime.Net.save_calibration) whose activation scales dtype "i8" plans with;
         None: none.  A file made for another graph is refused when the device net reads it."""
-        self.i8_calibration = path or None
-        if self._net is not None and self.i8_calibration:
-            self._net.load_calibration(self.i8_calibration)
+        self._defer("load_calibration", path or None)
 
     def set_weights_dict(self, weights):
         self._weights = weights

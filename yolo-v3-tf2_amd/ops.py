@@ -1,0 +1,328 @@
+"""The stand-alone ops behind the network: decode, class scores, NMS and the packed rows, the evaluation counters and the AP
+matching, target assignment and the validation loss, the plane-split helpers.  Torch tensors in, torch tensors out; each C entry
+point named here is called from this one place.  The private forms with an `out` argument are what the streaming loops (stream.py)
+write into their preallocated buffers with."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Dict, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._args import _anchors, _dev, _fptr, _need_cuda
+from ._lib import Y3Error, check
+
+
+def _grids_args(grids, square=True):
+    _need_cuda(*grids)
+    if len(grids) != 3:
+        raise Y3Error("expected three grids")
+    for g in grids:
+        if g.dtype != torch.float32 or g.dim() != 5 or g.shape[3] != 3 or (square and g.shape[1] != g.shape[2]):
+            raise Y3Error("each grid must be float32 [B,g,g,3,5+nc]" if square else "each grid must be float32 [B,gh,gw,3,5+nc]")
+    ptrs = (C.c_void_p * 3)(*[g.data_ptr() for g in grids])
+    if square:
+        gs = (C.c_int32 * 3)(*[g.shape[1] for g in grids])
+    else:       # grid_hw[3][2] = {gh, gw}
+        gs = (C.c_int32 * 6)(*[v for g in grids for v in (g.shape[1], g.shape[2])])
+    B = grids[0].shape[0]
+    N = sum(3 * g.shape[1] * g.shape[2] for g in grids)
+    return ptrs, gs, B, N
+
+
+def yolo_decode(grids, anchors_table, nclasses):
+    """-> (bboxes [B,N,4], confidence [B,N,1], class_probs [B,N,nc]).  Grids [B,gh,gw,3,5+nc]: each centre is normalised by
+    its own axis (include/y3.h, y3_yolo_decode_hw), which for gh == gw is the reference's arithmetic bit for bit."""
+    ptrs, gs, B, N = _grids_args(grids, square=False)
+    a = _anchors(anchors_table)
+    dev = grids[0].device
+    bboxes = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
+    conf = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
+    probs = torch.empty((B, N, nclasses), dtype=torch.float32, device=dev)
+    check(_lib.load().y3_yolo_decode_hw(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(conf), _dev(probs),
+                                     _lib.stream_ptr()), "y3_yolo_decode")
+    return bboxes, conf, probs
+
+
+def yolo_decode_scores(grids, anchors_table, nclasses):
+    """fused decode + class arg-max/score -> (bboxes [B,N,4], class_indices [B,N] i64, scores [B,N])"""
+    return _decode_scores(grids, anchors_table, nclasses)
+
+
+def _decode_scores(grids, anchors_table, nclasses, out=None):
+    ptrs, gs, B, N = _grids_args(grids, square=False)
+    a = _anchors(anchors_table)
+    dev = grids[0].device
+    bboxes, cls, scores = out or (torch.empty((B, N, 4), dtype=torch.float32, device=dev),
+                                  torch.empty((B, N), dtype=torch.int64, device=dev),
+                                  torch.empty((B, N), dtype=torch.float32, device=dev))
+    check(_lib.load().y3_yolo_decode_scores_hw(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores),
+                                            _lib.stream_ptr()), "y3_yolo_decode_scores")
+    return bboxes, cls, scores
+
+
+def class_scores(conf, probs):
+    _need_cuda(conf, probs)
+    B, N, nc = probs.shape
+    cls = torch.empty((B, N), dtype=torch.int64, device=probs.device)
+    scores = torch.empty((B, N), dtype=torch.float32, device=probs.device)
+    check(_lib.load().y3_class_scores(_dev(conf), _dev(probs), B, N, nc, _dev(cls), _dev(scores), _lib.stream_ptr()),
+          "y3_class_scores")
+    return cls, scores
+
+
+def split3_planes(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [...,C] -> bf16 [...,3,C] with hi + mid + lo == x exactly (the activation format of Y3_DTYPE_F32X3)."""
+    hi = x.to(torch.bfloat16)
+    r1 = x - hi.float()
+    mid = r1.to(torch.bfloat16)
+    lo = (r1 - mid.float()).to(torch.bfloat16)
+    return torch.stack([hi, mid, lo], dim=-2).contiguous()
+
+
+def split2_planes(x: torch.Tensor) -> torch.Tensor:
+    """fp32 [...,C] -> fp16 [...,2,C]: h = fp16(x), l' = fp16((x - h) * 2^11), x == h + l' * 2^-11 up to 2^-22 |x|
+    (the activation format of Y3_DTYPE_F32X2)."""
+    h = x.to(torch.float16)
+    lo = ((x - h.float()) * 2048.0).to(torch.float16)
+    return torch.stack([h, lo], dim=-2).contiguous()
+
+
+def pack_ground_truth(gts, max_gt: Optional[int] = None, out=None):
+    """A list of per-image (boxes [g,4], classes [g]) -> padded (boxes [B,G,4] float32, classes [B,G] int32, count [B] int32),
+    the ground-truth form of evaluate_detections.  Pure NumPy.  G = max_gt, by default the largest g of the list (at least 1);
+    an image with more rows than max_gt raises.  out: the three arrays to fill (e.g. views of pinned memory); rows behind
+    an image's count are zeroed."""
+    gts = [(np.asarray(b, np.float32).reshape(-1, 4), np.asarray(c).reshape(-1)) for b, c in gts]
+    for i, (b, c) in enumerate(gts):
+        if len(b) != len(c):
+            raise Y3Error(f"pack_ground_truth: image {i} has {len(b)} boxes and {len(c)} classes")
+    most = max((len(c) for _, c in gts), default=0)
+    G = max(most, 1) if max_gt is None else int(max_gt)
+    if G < 1 or most > G:
+        raise Y3Error(f"pack_ground_truth: max_gt = {G}, the images hold up to {most} boxes")
+    B = len(gts)
+    if out is None:
+        out = (np.empty((B, G, 4), np.float32), np.empty((B, G), np.int32), np.empty((B,), np.int32))
+    boxes, classes, count = out
+    if (boxes.shape, classes.shape, count.shape) != ((B, G, 4), (B, G), (B,)) or \
+            (boxes.dtype, classes.dtype, count.dtype) != (np.float32, np.int32, np.int32):
+        raise Y3Error(f"pack_ground_truth: out must be float32 [{B},{G},4], int32 [{B},{G}], int32 [{B}]")
+    boxes[...] = 0
+    classes[...] = 0
+    for i, (b, c) in enumerate(gts):
+        boxes[i, :len(b)] = b
+        classes[i, :len(c)] = c
+        count[i] = len(c)
+    return boxes, classes, count
+
+
+def _gt_views(words, n: int, G: int):
+    """A 1-D int32 buffer (NumPy or torch) -> its (boxes [n,G,4], classes [n,G], count [n]) parts, boxes still as words."""
+    nb, ncl = n * G * 4, n * G
+    return words[:nb].reshape(n, G, 4), words[nb:nb + ncl].reshape(n, G), words[nb + ncl:nb + ncl + n]
+
+
+def _scored_args(packed, num_valid, gt_boxes, gt_classes, gt_count):
+    """The checks evaluate_detections and match_detections share -> (B, M, G)."""
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != 7:
+        raise Y3Error("packed must be contiguous int32 [B,M,7]")
+    B, M = packed.shape[0], packed.shape[1]
+    if num_valid.dtype != torch.int32 or num_valid.shape != (B,):
+        raise Y3Error(f"num_valid must be int32 [{B}]")
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3 or gt_boxes.shape[0] != B or gt_boxes.shape[2] != 4:
+        raise Y3Error(f"gt_boxes must be float32 [{B},G,4]")
+    G = gt_boxes.shape[1]
+    if gt_classes.dtype != torch.int32 or gt_classes.shape != (B, G):
+        raise Y3Error(f"gt_classes must be int32 [{B},{G}]")
+    if gt_count.dtype != torch.int32 or gt_count.shape != (B,):
+        raise Y3Error(f"gt_count must be int32 [{B}]")
+    return B, M, G
+
+
+def evaluate_detections(packed: torch.Tensor, num_valid: torch.Tensor, gt_boxes: torch.Tensor, gt_classes: torch.Tensor,
+                        gt_count: torch.Tensor, nclasses: int, iou_threshold: float, score_thresholds, one_class=False,
+                        counters: Optional[torch.Tensor] = None):
+    """packed [B,M,7] int32 words and num_valid [B] int32 on the GPU (Net.detect at the LOWEST threshold of the sweep,
+    pack_detections, unletterbox_detections), ground truth on the GPU as pack_ground_truth lays it out (gt_boxes [B,G,4]
+    float32, gt_classes [B,G] int32, gt_count [B] int32) -> the counters of every score threshold, int64
+    [T, 5*nclasses + 2] on the GPU: preds, gts, tp, fp, fn (each [nclasses]), errors, examples per threshold
+    (y3_evaluate_detections; host restatement: evaluate_detections.sweep_counters).  counters=None: a zeroed tensor is
+    made; otherwise the call ADDS to the one given.  Enqueues on the current stream only."""
+    _need_cuda(packed, num_valid, gt_boxes, gt_classes, gt_count, counters)
+    B, M, G = _scored_args(packed, num_valid, gt_boxes, gt_classes, gt_count)
+    thr = np.ascontiguousarray(np.asarray(score_thresholds, np.float32).reshape(-1))
+    nc = int(nclasses)
+    if counters is None:
+        counters = torch.zeros((len(thr), 5 * nc + 2), dtype=torch.int64, device=packed.device)
+    elif counters.dtype != torch.int64 or counters.shape != (len(thr), 5 * nc + 2):
+        raise Y3Error(f"counters must be int64 [{len(thr)},{5 * nc + 2}]")
+    check(_lib.load().y3_evaluate_detections(_dev(packed), _dev(num_valid), B, M, _dev(gt_boxes), _dev(gt_classes), _dev(gt_count),
+                                             G, nc, float(iou_threshold), _fptr(thr), len(thr), int(bool(one_class)),
+                                             _dev(counters), _lib.stream_ptr()), "y3_evaluate_detections")
+    return counters
+
+
+def ap_iou_thresholds(ap):
+    """The `ap` argument of evaluate_stream / evaluate -> its IoU thresholds, float32 [K]: True means the ten thresholds 0.5, 0.55,
+    ..., 0.95 of mAP@[.5:.95] (evaluate_detections.AP_IOU_THRESHOLDS), a sequence means those thresholds."""
+    from .evaluate_detections import AP_IOU_THRESHOLDS
+    thr = AP_IOU_THRESHOLDS if ap is True else np.ascontiguousarray(np.asarray(ap, np.float32).reshape(-1))
+    if not 1 <= len(thr) <= 16 or not np.isfinite(thr).all():
+        raise Y3Error("ap: 1 to 16 finite IoU thresholds (or True for 0.5, 0.55, ..., 0.95)")
+    return thr
+
+
+def match_detections(packed: torch.Tensor, num_valid: torch.Tensor, gt_boxes: torch.Tensor, gt_classes: torch.Tensor,
+                     gt_count: torch.Tensor, nclasses: int, iou_thresholds, one_class=False,
+                     records: Optional[torch.Tensor] = None, gt_totals: Optional[torch.Tensor] = None):
+    """The inputs of evaluate_detections -> (records int32 [B,M,2], gt_totals int64 [nclasses + 2]) on the GPU: per image the
+    greedy matching behind COCO-style average precision, at every IoU threshold of iou_thresholds [K <= 16] (y3_match_detections;
+    host restatement: evaluate_detections.match_detections, which also names the words; evaluate_detections.average_precision
+    integrates the records of a data set).  The rows are matched in ROW order -- Net.detect writes them in descending score --
+    and nothing is sorted.  records: the tensor to write (every row of it is written; torch has no arithmetic on uint32, so the
+    words travel as int32 like the packed rows: .view(np.uint32) on the host); gt_totals=None: a zeroed tensor is made, otherwise
+    the call ADDS to the one given.  Enqueues on the current stream only."""
+    return _match(packed, num_valid, gt_boxes, gt_classes, gt_count, nclasses, iou_thresholds, one_class, records, gt_totals)
+
+
+def _match(packed, num_valid, gt_boxes, gt_classes, gt_count, nclasses, iou_thresholds, one_class, records, gt_totals, lib=None):
+    """match_detections; lib: the library handle to call through (a Net's own `lib`) instead of the module's."""
+    _need_cuda(packed, num_valid, gt_boxes, gt_classes, gt_count, records, gt_totals)
+    B, M, G = _scored_args(packed, num_valid, gt_boxes, gt_classes, gt_count)
+    thr = np.ascontiguousarray(np.asarray(iou_thresholds, np.float32).reshape(-1))
+    nc = int(nclasses)
+    if records is None:
+        records = torch.empty((B, M, 2), dtype=torch.int32, device=packed.device)
+    elif records.dtype != torch.int32 or records.shape != (B, M, 2):
+        raise Y3Error(f"records must be int32 [{B},{M},2]")
+    if gt_totals is None:
+        gt_totals = torch.zeros((max(nc, 0) + 2,), dtype=torch.int64, device=packed.device)
+    elif gt_totals.dtype != torch.int64 or gt_totals.shape != (nc + 2,):
+        raise Y3Error(f"gt_totals must be int64 [{nc + 2}]")
+    check((lib or _lib.load()).y3_match_detections(_dev(packed), _dev(num_valid), B, M, _dev(gt_boxes), _dev(gt_classes), _dev(gt_count),
+                                          G, nc, _fptr(thr), len(thr), int(bool(one_class)), _dev(records), _dev(gt_totals),
+                                          _lib.stream_ptr()), "y3_match_detections")
+    return records, gt_totals
+
+
+def _gt_args(who, gt_boxes, gt_classes):
+    if gt_boxes.dtype != torch.float32 or gt_boxes.dim() != 3 or gt_boxes.shape[2] != 4:
+        raise Y3Error(f"{who}: gt_boxes must be float32 [B,G,4]")
+    B, G = gt_boxes.shape[0], gt_boxes.shape[1]
+    if gt_classes.dtype != torch.int32 or gt_classes.shape != (B, G):
+        raise Y3Error(f"{who}: gt_classes must be int32 [{B},{G}]")
+    return B, G
+
+
+def assign_targets(gt_boxes: torch.Tensor, gt_classes: torch.Tensor, gt_count: torch.Tensor, anchors_table, grid_sizes,
+                   nclasses: int, cells: Optional[torch.Tensor] = None):
+    """Ground truth on the GPU as pack_ground_truth lays it out (gt_boxes [B,G,4] float32, gt_classes [B,G] int32, gt_count [B]
+    int32) -> cells [B,G] int32 on the GPU: per ground-truth row the index of its label's row in decode's row order (best
+    anchor by width/height IoU, the cell of its centre, the later row winning a shared cell), -1 behind the count, -2 for a row
+    that lost its cell, -3 for the rows of an error image (y3_yolo_assign_targets; reference
+    core/preprocess_dataset.py::_arrange_in_grid in sparse form; host restatement: core.preprocess_dataset.assign_targets).
+    cells: the tensor to write.  Enqueues on the current stream only."""
+    _need_cuda(gt_boxes, gt_classes, gt_count, cells)
+    B, G = _gt_args("assign_targets", gt_boxes, gt_classes)
+    if gt_count.dtype != torch.int32 or gt_count.shape != (B,):
+        raise Y3Error(f"assign_targets: gt_count must be int32 [{B}]")
+    gs = [int(g) for g in grid_sizes]
+    if len(gs) != 3:
+        raise Y3Error("assign_targets: three grid sizes")
+    a = _anchors(anchors_table)
+    if cells is None:
+        cells = torch.empty((B, G), dtype=torch.int32, device=gt_boxes.device)
+    elif cells.dtype != torch.int32 or cells.shape != (B, G):
+        raise Y3Error(f"assign_targets: cells must be int32 [{B},{G}]")
+    check(_lib.load().y3_yolo_assign_targets(_dev(gt_boxes), _dev(gt_classes), _dev(gt_count), B, G, int(nclasses),
+                                             (C.c_int32 * 3)(*gs), _fptr(a), _dev(cells), _lib.stream_ptr()),
+          "y3_yolo_assign_targets")
+    return cells
+
+
+def yolo_loss(grids, anchors_table, nclasses: int, gt_boxes: torch.Tensor, gt_classes: torch.Tensor, cells: torch.Tensor,
+              loss: Optional[torch.Tensor] = None):
+    """The raw head grids of Net.forward ([B,g,g,3,5+nc] each) + ground truth + the cells of assign_targets -> float64 [B,3,4] on
+    the GPU: per image and scale the sums xy, wh, obj, class of reference core/loss_func.py (y3_yolo_loss; host restatement:
+    core.loss_func.loss_from_cells).  An error image (cells -3) gets twelve zeros.  Each image's numbers are bit-identical
+    whatever batch it is in.  This is the validation loss: no gradient, and the regulariser the reference's training loop adds
+    (model.losses) is not part of it.  loss: the tensor to write (overwritten, not added to).  Enqueues on the current stream only."""
+    ptrs, gs, B, _ = _grids_args(grids)
+    _need_cuda(gt_boxes, gt_classes, cells, loss)
+    nc = int(nclasses)
+    if any(g.shape[4] != 5 + nc for g in grids):
+        raise Y3Error(f"yolo_loss: each grid must be float32 [B,g,g,3,{5 + nc}]")
+    if any(g.shape[0] != B for g in grids):
+        raise Y3Error("yolo_loss: the grids hold unlike batches")
+    Bg, G = _gt_args("yolo_loss", gt_boxes, gt_classes)
+    if Bg != B:
+        raise Y3Error(f"yolo_loss: {B} images in the grids, {Bg} in the ground truth")
+    if cells.dtype != torch.int32 or cells.shape != (B, G):
+        raise Y3Error(f"yolo_loss: cells must be int32 [{B},{G}]")
+    a = _anchors(anchors_table)
+    if loss is None:
+        loss = torch.empty((B, 3, 4), dtype=torch.float64, device=gt_boxes.device)
+    elif loss.dtype != torch.float64 or loss.shape != (B, 3, 4):
+        raise Y3Error(f"yolo_loss: loss must be float64 [{B},3,4]")
+    check(_lib.load().y3_yolo_loss(ptrs, gs, B, nc, _fptr(a), _dev(gt_boxes), _dev(gt_classes), _dev(cells), G, _dev(loss),
+                                   _lib.stream_ptr()), "y3_yolo_loss")
+    return loss
+
+
+_ws_cache: Dict[tuple, torch.Tensor] = {}
+
+
+def _nms_workspace_bytes(B, N):
+    return _lib.load().y3_nms_workspace_bytes(B, N)
+
+
+def nms_padded(bboxes, scores, max_output_size, iou_threshold, score_threshold):
+    """-> (selected_indices_padded [B,M] i32, num_valid [B] i32)"""
+    return _nms(bboxes, scores, max_output_size, iou_threshold, score_threshold)
+
+
+def _nms(bboxes, scores, max_output_size, iou_threshold, score_threshold, out=None, ws=None):
+    """nms_padded; out: the (sel, nv) tensors to write; ws: the caller's own workspace instead of the process-wide _ws_cache."""
+    _need_cuda(bboxes, scores)
+    if bboxes.dtype != torch.float32 or scores.dtype != torch.float32:
+        raise Y3Error("boxes and scores must be float32")
+    B, N = scores.shape
+    lib = _lib.load()
+    if ws is None:
+        need = _nms_workspace_bytes(B, N)
+        key = (bboxes.device.index, need)
+        ws = _ws_cache.get(key)
+        if ws is None:
+            _ws_cache.clear()
+            ws = _ws_cache[key] = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+    sel, nv = out or (torch.empty((B, int(max_output_size)), dtype=torch.int32, device=bboxes.device),
+                      torch.empty((B,), dtype=torch.int32, device=bboxes.device))
+    check(lib.y3_nms_padded(_dev(bboxes), _dev(scores), B, N, int(max_output_size), float(iou_threshold),
+                            float(score_threshold), _dev(sel), _dev(nv), _dev(ws), ws.numel(), _lib.stream_ptr()),
+          "y3_nms_padded")
+    return sel, nv
+
+
+def pack_detections(bboxes, cls, scores, sel, nv):
+    """-> [B,M,7] int32 words: box (4 x f32 bits), score (f32 bits), class, index; rows >= num_valid zero"""
+    return _pack(bboxes, cls, scores, sel, nv)
+
+
+def _pack(bboxes, cls, scores, sel, nv, out=None):
+    _need_cuda(bboxes, cls, scores, sel, nv)
+    B, N = scores.shape
+    M = sel.shape[1]
+    if out is None:
+        out = torch.empty((B, M, 7), dtype=torch.int32, device=bboxes.device)
+    check(_lib.load().y3_pack_detections(_dev(bboxes), _dev(cls), _dev(scores), _dev(sel), _dev(nv), B, N, M, _dev(out),
+                                         _lib.stream_ptr()), "y3_pack_detections")
+    return out
+
+
+def unpack_detections(packed: torch.Tensor):
+    """[.., M, 7] int32 words -> (boxes f32 [..,M,4], scores f32 [..,M], classes i32, indices i32)"""
+    f = packed[..., :5].contiguous().view(torch.float32)
+    return f[..., :4], f[..., 4], packed[..., 5], packed[..., 6]

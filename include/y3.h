@@ -469,6 +469,21 @@ y3_status y3_nms_padded(const float *bboxes_dev, const float *scores_dev, int ba
                         float iou_threshold, float score_threshold, int32_t *selected_idx_dev,
                         int32_t *num_valid_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
 
+/* Per-class NMS (no reference counterpart; off by default everywhere).  The rule of y3_nms_padded with one predicate changed: a
+ * candidate is suppressed by an earlier kept candidate iff their class ids are equal AND IoU >= iou_threshold (the same fp32 IoU,
+ * the arguments in the same order).  Everything else is y3_nms_padded's: scores <= score_threshold are masked out, the
+ * canonicalisation is decided by box [0,0] of the batch, the order is (score descending, index ascending) with -0 == +0, a box is
+ * selected iff any of its coordinates is > 0, and the first max_output_size selected boxes OVER ALL CLASSES TOGETHER are returned in
+ * sorted order, the rest of the row zero, num_valid = min(count, max_output_size).  With all class ids equal the outputs are those
+ * of y3_nms_padded bit for bit.  class_idx_dev: int64 [batch,n] as y3_class_scores / y3_net_forward_decode write it; the ids are
+ * compared as int32 and must lie in [0, 2^31).  iou_threshold <= 0 (the tile quirk of the agnostic rule) has no meaning here and is
+ * refused with Y3_ERR_INVALID; the other argument checks are y3_nms_padded's.  The workspace holds the class ids of spilled kept
+ * boxes as well: y3_nms_per_class_workspace_bytes = y3_nms_workspace_bytes + batch * n * 4.  Only enqueues: may be captured. */
+size_t y3_nms_per_class_workspace_bytes(int batch, int n);
+y3_status y3_nms_padded_per_class(const float *bboxes_dev, const float *scores_dev, const int64_t *class_idx_dev, int batch, int n,
+                                  int max_output_size, float iou_threshold, float score_threshold, int32_t *selected_idx_dev,
+                                  int32_t *num_valid_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+
 /* Inference.gather_valid_detections_results for a whole batch (reference: inference.py:21-28), packed for the
  * multi-GPU exchange: per image max_out rows of {box[4], score, class (int32), index (int32)} = 7 x 4 bytes
  * (rows >= num_valid zeroed), i.e. packed_dev is [B,max_out,7] of 32-bit words. */
@@ -496,6 +511,13 @@ y3_status y3_net_forward_decode(y3_net *net, const float *images_dev, int batch,
 y3_status y3_net_detect(y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
                         float iou_threshold, float score_threshold, void *packed_dev, int32_t *num_valid_dev,
                         void *stream);
+/* Which NMS rule y3_net_detect enqueues: Y3_NMS_AGNOSTIC (the default: y3_nms_padded, the reference's rule) or Y3_NMS_PER_CLASS
+ * (y3_nms_padded_per_class on the class ids of the decode; iou_threshold must then be > 0).  Read when y3_net_detect enqueues: a
+ * captured graph keeps the mode it was captured in.  y3_net_plan reserves the larger workspace, so the mode may be switched
+ * after planning.  Nothing else about y3_net_detect changes: the packed rows keep their format. */
+enum { Y3_NMS_AGNOSTIC = 0, Y3_NMS_PER_CLASS = 1 };
+y3_status y3_net_set_nms_mode(y3_net *net, int mode);
+int y3_net_get_nms_mode(const y3_net *net);
 
 /* Packed detections of letterboxed images -> coordinates of the source frames, in place (no reference counterpart: the
  * reference leaves its boxes on the padded canvas).  packed_dev [batch,max_boxes,7] and num_valid_dev [batch] as written by

@@ -24,6 +24,7 @@ TILES_I8_BUILT = (8, 10, 11, 12, 17, 19, 24, 26, 27, 29)
 TILES_X2_BUILT = (0, 1, 2, 3, 4, 8, 12, 26, 27)
 TILES_X3_BUILT = (0, 1, 2, 3, 4, 8, 9, 12, 13, 14)
 Y3_AUX_ADD, Y3_AUX_UPSAMPLE2X, Y3_AUX_CONCAT = 0, 1, 2
+Y3_NMS_AGNOSTIC, Y3_NMS_PER_CLASS = 0, 1   # y3_net_set_nms_mode
 # (BM, BN, waves, LDS stages) of every tile id of the fp32 MFMA conv kernel (mirror of kTiles in csrc/conv_f32.hip)
 # (0, 0, 0, 0): a retired id (y3_tile_built answers 0).  Round 5: only tiles a packaged tuning table or the library's heuristic selects are built.
 _Z = (0, 0, 0, 0)
@@ -164,6 +165,10 @@ SYMBOLS = {
     "y3_class_scores": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "y3_nms_workspace_bytes": (_sz, [_i, _i]),
     "y3_nms_padded": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "y3_nms_per_class_workspace_bytes": (_sz, [_i, _i]),
+    "y3_nms_padded_per_class": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
+    "y3_net_set_nms_mode": (_i, [_vp, _i]),
+    "y3_net_get_nms_mode": (_i, [_vp]),
     "y3_pack_detections": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "y3_crc32c": (C.c_uint32, [_vp, C.c_size_t]),
     "y3_net_forward_decode": (_i, [_vp, _vp, _i, _fp, _vp, _vp, _vp, _vp]),

@@ -47,6 +47,7 @@ class YoloModel:
         # the settings a device net is given when it is made, Net method -> argument, in the order they are applied: the low-latency
         # switches, stem fusion, the calibration file an "i8" plan needs, the dtype (None: fp32).  An entry at its value here is skipped.
         self._deferred = dict(_DEFERRED_DEFAULTS)
+        self.nms_per_class = False      # set_nms_per_class: a property of the device net, not one of its methods, so kept beside them
 
     def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, i8_calibration, dtype
         method = {"i8_calibration": "load_calibration"}.get(name, "set_" + name)
@@ -62,6 +63,7 @@ class YoloModel:
             for method, arg in self._deferred.items():
                 if arg != _DEFERRED_DEFAULTS[method]:
                     getattr(self._net, method)(arg)
+            self._net.nms_per_class = self.nms_per_class
             if self._weights is not None:
                 self._net.load_weights(self._weights)
         return self._net
@@ -92,6 +94,16 @@ class YoloModel:
         """The fused stem kernel for fp16 plans (runtime.Net.set_stem_fusion_f16): off by default; acts on dtype "f16" only."""
         from ..runtime import Net
         self._defer("set_stem_fusion_f16", Net._stem_fusion_arg(on))
+
+    def set_nms_per_class(self, on=True):
+        """Per-class NMS (runtime.Net.nms_per_class; no reference counterpart): a box is suppressed only by a kept box of its own
+        class.  None or False: the reference's class-agnostic rule, the default.  The device net's detect / detect_stream /
+        evaluate_stream and both routes of inference.DetectModel follow it."""
+        if on is not None and not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"set_nms_per_class: a bool or None (got {on!r})")
+        self.nms_per_class = bool(on)
+        if self._net is not None:
+            self._net.nms_per_class = self.nms_per_class
 
     def set_dtype(self, dtype):
         """Conv arithmetic of the plans (runtime.Net.set_dtype): None or "f32" (default), "bf16", "f16" -- 16-bit activations and

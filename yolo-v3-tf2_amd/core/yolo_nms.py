@@ -1,4 +1,5 @@
 """Host mirror of reference core/yolo_nms.py -- same name and signature, HIP underneath."""
+from ..ops import nms_padded_per_class as _nms_padded_per_class
 from ..runtime import class_scores as _class_scores, nms_padded as _nms_padded
 
 
@@ -8,10 +9,24 @@ def yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold):
     selected_indices_padded [B,max] i32, num_valid_detections [B] i32) -- reference: core/yolo_nms.py:16-34.
     Class-agnostic NMS with TF's `non_max_suppression_padded` semantics (IoU >= threshold suppresses,
     score > threshold passes, ties by lower index)."""
+    return _yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold, per_class=False)
+
+
+def yolo_nms_per_class(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold):
+    """yolo_nms with the per-class rule (no reference counterpart): a box is suppressed only by a kept box of its own class
+    (ops.nms_padded_per_class), yolo_max_boxes over all classes together.  Same arguments, same 5-tuple; nms_iou_threshold > 0."""
+    return _yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold, per_class=True)
+
+
+def _yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold, per_class):
     from .yolo_decode_layer import _to_device
     bboxes, confidence, class_probs = (_to_device(t) for t in outputs)
     class_indices, scores = _class_scores(confidence.contiguous(), class_probs.contiguous())
     bboxes = bboxes.reshape(bboxes.shape[0], -1, 4).contiguous()
-    selected_indices_padded, num_valid_detections = _nms_padded(bboxes, scores, yolo_max_boxes, nms_iou_threshold,
-                                                                nms_score_threshold)
+    if per_class:
+        selected_indices_padded, num_valid_detections = _nms_padded_per_class(bboxes, scores, class_indices, yolo_max_boxes,
+                                                                              nms_iou_threshold, nms_score_threshold)
+    else:
+        selected_indices_padded, num_valid_detections = _nms_padded(bboxes, scores, yolo_max_boxes, nms_iou_threshold,
+                                                                    nms_score_threshold)
     return (bboxes, class_indices, scores, selected_indices_padded, num_valid_detections)

@@ -23,6 +23,15 @@
 // are written to lists and turned into indices by all threads afterwards.  Two more (same round): the test against the kept list works on
 // (candidate, kept box) pairs spread over all threads, and the suppression rows come from balanced pairs (128 steps per thread instead of
 // 255 for thread 0).  93 -> 68 us per call at 64-128 images x 10647 boxes (profiles/r05_nms_chains.txt).
+//
+// Per-class mode (y3_nms_padded_per_class; no reference counterpart): the same five steps, and step 4 alone reads
+//   4'. suppress when the two class ids are equal AND IoU >= T (the same fp32 IoU, the arguments in the same order).
+// Masking, canonicalisation, the sort, "selected" and the first M selected boxes OVER ALL CLASSES TOGETHER stay as above.  It is the
+// PER_CLASS instantiation of the one kernel body: each chunk's candidates carry their class id beside s_cbox, the kept list beside
+// s_kbox (9 KB of LDS more, this instantiation only), spilled survivors into the workspace (B*N*4 bytes more), and the class test
+// comes first wherever iou_tf is called -- a boolean AND, so it cannot change a bit of the outcome.  Class ids are the int64 [B,N]
+// of y3_class_scores, compared as int32: they must lie in [0, 2^31) (pack_kernel assumes the same).  T <= 0 (the tile quirk of the
+// agnostic rule) has no meaning here; the host refuses it.
 #include "y3_device.h"
 #include "y3_kernels.h"
 
@@ -82,8 +91,19 @@ struct NmsArgs {
     u64 *ws;              // [B][P2] scratch keys, P2 = next pow2 >= N
     int P2;
     float *spill;         // [B][N][4] kept boxes beyond KEPT_CAP
+    // per-class mode only (behind everything the class-agnostic kernel reads)
+    const int64_t *cls;   // [B,N] class ids in [0, 2^31)
+    int32_t *spill_cls;   // [B][N] class ids of the kept boxes beyond KEPT_CAP
 };
 
+// the class ids of the chunk's candidates and of the kept list in LDS; empty, and never named, in the class-agnostic instantiation
+template <bool PER_CLASS> struct NmsClassLds {};
+template <> struct NmsClassLds<true> {
+    int kept[KEPT_CAP];
+    int cand[NMS_THREADS];
+};
+
+template <bool PER_CLASS>
 __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
 {
     __shared__ __attribute__((aligned(16))) u64 s_keys[SORT_CAP];
@@ -93,6 +113,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
     __shared__ u64 s_alive[4], s_posany[4];
     __shared__ int s_keptpos[NMS_THREADS], s_selpos[NMS_THREADS], s_ok[NMS_THREADS];
     __shared__ int s_cnt, s_nkept_chunk, s_nsel, s_nalive;
+    __shared__ NmsClassLds<PER_CLASS> s_cls;
 
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
@@ -101,6 +122,12 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
     int32_t *sel = p.sel + (size_t)b * p.M;
     u64 *gkeys = p.ws + (size_t)b * p.P2;
     float *gspill = p.spill + (size_t)b * p.N * 4;
+    [[maybe_unused]] const int64_t *cls = nullptr;
+    [[maybe_unused]] int32_t *gspill_cls = nullptr;
+    if constexpr (PER_CLASS) {
+        cls = p.cls + (size_t)b * p.N;
+        gspill_cls = p.spill_cls + (size_t)b * p.N;
+    }
 
     // canonicalisation flags from box [0,0] of the batch after masking (TF looks at that box only)
     const float m00 = (p.scores[0] > p.S) ? 1.0f : 0.0f;
@@ -147,7 +174,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
     // T <= 0 (tile quirk, see oracle/y3_oracle.c): nothing is suppressed inside the first 512 sorted positions and
     // everything behind them is wiped.  (The host rejects T <= 0 together with S < 0, where zeroed boxes could
     // sort in front of kept ones.)
-    const bool degenerate = !(p.T > 0.0f);
+    const bool degenerate = PER_CLASS ? false : !(p.T > 0.0f);   // per class: T > 0 always, the host refuses the rest
     int nc = s_cnt;
     // ---- 2. sort ------------------------------------------------------------------------------------
     int P = 1;
@@ -168,14 +195,18 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
     for (int pos = 0; pos < nc; pos += NMS_THREADS) {
         const int cnt = min(NMS_THREADS, nc - pos);
         const int nalive = s_nalive;
+        const int nsel0 = s_nsel;   // read here, where no wave writes it: wave 0 stores the chunk's new count before the barrier behind its resolve
         f32x4 mine = {0.f, 0.f, 0.f, 0.f};
+        [[maybe_unused]] int my_cls = 0;
         if (tid < cnt) {
             const int my_idx = (int)(unsigned)(keys[pos + tid] & 0xFFFFFFFFull);
             mine = *reinterpret_cast<const f32x4 *>(boxes + (size_t)my_idx * 4);
+            if constexpr (PER_CLASS) my_cls = (int)cls[my_idx];
             if (swap_y) { const float t = mine[0]; mine[0] = mine[2]; mine[2] = t; }
             if (swap_x) { const float t = mine[1]; mine[1] = mine[3]; mine[3] = t; }
         }
         *reinterpret_cast<f32x4 *>(s_cbox + tid * 4) = mine;
+        if constexpr (PER_CLASS) s_cls.cand[tid] = my_cls;
         s_ok[tid] = tid < cnt ? 1 : 0;
         unsigned *m32 = reinterpret_cast<unsigned *>(s_mask);   // the chunk's suppression rows as 8 x 32 bits per candidate
 #pragma unroll
@@ -190,8 +221,13 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
             const int c = tid & ((1 << sh) - 1), a0 = tid >> sh, astep = NMS_THREADS >> sh;
             if (c < cnt) {
                 const f32x4 cb = *reinterpret_cast<const f32x4 *>(s_cbox + c * 4);
+                [[maybe_unused]] int cc = 0;
+                if constexpr (PER_CLASS) cc = s_cls.cand[c];
                 bool hit = false;
                 for (int a = a0; a < nalive; a += astep) {
+                    if constexpr (PER_CLASS) {   // the class test first: another class's kept box is neither fetched nor measured
+                        if ((a < KEPT_CAP ? s_cls.kept[a] : gspill_cls[a - KEPT_CAP]) != cc) continue;
+                    }
                     const f32x4 kb = a < KEPT_CAP ? *reinterpret_cast<const f32x4 *>(s_kbox + a * 4)
                                                   : *reinterpret_cast<const f32x4 *>(gspill + (size_t)(a - KEPT_CAP) * 4);   // spilled survivors (rare: see the header)
                     if (iou_tf(kb, cb) >= p.T) hit = true;
@@ -218,17 +254,23 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
                     const int j = (tid + d) & (NMS_THREADS - 1);
                     const int lo = j > tid ? tid : j, hi = j > tid ? j : tid;
                     if (hi >= cnt) continue;
+                    if constexpr (PER_CLASS) {
+                        if (s_cls.cand[j] != my_cls) continue;
+                    }
                     const f32x4 other = *reinterpret_cast<const f32x4 *>(s_cbox + j * 4);
                     const f32x4 a = j > tid ? mine : other, b = j > tid ? other : mine;
                     if (iou_tf(a, b) >= p.T) atomicOr(&m32[lo * 8 + (hi >> 5)], 1u << (hi & 31));
                 }
             } else if (ok) {
-                for (int j = tid + 1; j < cnt; ++j)
+                for (int j = tid + 1; j < cnt; ++j) {
+                    if constexpr (PER_CLASS) {
+                        if (s_cls.cand[j] != my_cls) continue;
+                    }
                     if (iou_tf(mine, *reinterpret_cast<const f32x4 *>(s_cbox + j * 4)) >= p.T) m32[tid * 8 + (j >> 5)] |= 1u << (j & 31);
+                }
             }
         }
         __syncthreads();
-        const int nsel0 = s_nsel;
         if (tid < 64) {
             // wave 0, every lane redundantly (uniform control flow): walk the alive bits in order.  Lane L holds the rows of
             // candidates L, 64 + L, 128 + L, 192 + L; row t = lane (t & 63) of set (t >> 6), fetched with v_readlane.
@@ -281,6 +323,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const NmsArgs p)
             const int slot = nalive + tid;
             float *dst = slot < KEPT_CAP ? s_kbox + slot * 4 : gspill + (size_t)(slot - KEPT_CAP) * 4;
             *reinterpret_cast<f32x4 *>(dst) = *reinterpret_cast<const f32x4 *>(s_cbox + t * 4);
+            if constexpr (PER_CLASS) *(slot < KEPT_CAP ? s_cls.kept + slot : gspill_cls + (slot - KEPT_CAP)) = s_cls.cand[t];
         }
         if (tid == 0) s_nalive = nalive + nk;
         __syncthreads();
@@ -302,14 +345,23 @@ size_t nms_workspace_bytes(int B, int N)
     return (size_t)B * next_pow2(N > 1 ? N : 1) * sizeof(u64) + (size_t)B * (N > 1 ? N : 1) * 4 * sizeof(float);
 }
 
-hipError_t launch_nms(const float *boxes, const float *scores, int B, int N, int M, float T, float S, int32_t *sel,
-                      int32_t *num_valid, void *ws, hipStream_t s)
+// the same, then the class ids of the spilled kept boxes [B][N] i32
+size_t nms_per_class_workspace_bytes(int B, int N) { return nms_workspace_bytes(B, N) + (size_t)B * (N > 1 ? N : 1) * sizeof(int32_t); }
+
+// cls: null for the class-agnostic rule; the class ids [B,N] for the per-class one, ws then holding nms_per_class_workspace_bytes
+hipError_t launch_nms(const float *boxes, const float *scores, const int64_t *cls, int B, int N, int M, float T, float S,
+                      int32_t *sel, int32_t *num_valid, void *ws, hipStream_t s)
 {
     const int P2 = next_pow2(N > 1 ? N : 1);
     u64 *keys = static_cast<u64 *>(ws);
-    NmsArgs a{boxes, scores, N, M, T, S, sel, num_valid, keys, P2, reinterpret_cast<float *>(keys + (size_t)B * P2)};
+    float *spill = reinterpret_cast<float *>(keys + (size_t)B * P2);
+    int32_t *spill_cls = cls ? reinterpret_cast<int32_t *>(spill + (size_t)B * (N > 1 ? N : 1) * 4) : nullptr;
+    NmsArgs a{boxes, scores, N, M, T, S, sel, num_valid, keys, P2, spill, cls, spill_cls};
     dim3 grid(B), block(NMS_THREADS);
-    hipLaunchKernelGGL(nms_kernel, grid, block, 0, s, a);
+    if (cls)
+        hipLaunchKernelGGL(nms_kernel<true>, grid, block, 0, s, a);
+    else
+        hipLaunchKernelGGL(nms_kernel<false>, grid, block, 0, s, a);
     return hipGetLastError();
 }
 

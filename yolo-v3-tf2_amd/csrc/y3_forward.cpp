@@ -621,8 +621,12 @@ try {
     // workgroups take CUs from the other lane's last convs; profiles/r05_ab_bf16_lane_nms.txt.  Batch-wide launches behind the join again.)
     st = forward_decode(net, L, images_dev, batch, anchors_host, boxes, cls, scores, stream);
     if (st != Y3_OK) return st;
-    st = y3_nms_padded(boxes, scores, batch, n, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
-                       b + L.nms_ws, L.total - L.nms_ws, stream);
+    if (net->nms_mode == Y3_NMS_PER_CLASS)
+        st = y3_nms_padded_per_class(boxes, scores, cls, batch, n, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
+                                     b + L.nms_ws, L.total - L.nms_ws, stream);
+    else
+        st = y3_nms_padded(boxes, scores, batch, n, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
+                           b + L.nms_ws, L.total - L.nms_ws, stream);
     if (st != Y3_OK) return st;
     return y3_pack_detections(boxes, cls, scores, sel, num_valid_dev, batch, n, max_boxes, packed_dev, stream);
 }

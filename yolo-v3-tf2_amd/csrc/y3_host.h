@@ -129,6 +129,7 @@ struct y3_net {
     // y3_net_plan for max_batch images and Y3_MAX_OUTPUT_BOXES rows, so y3_net_detect itself only enqueues work
     void *det_buf = nullptr;
     size_t det_bytes = 0;
+    int nms_mode = 0;              // y3_net_set_nms_mode: Y3_NMS_AGNOSTIC / Y3_NMS_PER_CLASS, read by y3_net_detect when it enqueues
     int stem_mode = 1;             // y3_net_set_stem_fusion: 1 = conv0 + conv1 (+ the 1x1 after them) as one kernel when the graph allows it; 2 = conv0 + conv1 only
     bool stem_mode_set = false;    // y3_net_set_stem_fusion was called (the Y3_STEM_MODE tool override then stays out)
     int stem_mode_f16 = 0;         // y3_net_set_stem_fusion_f16: the same three values for Y3_DTYPE_F16 plans, which stem_mode does not act on; off by default

@@ -337,8 +337,10 @@ hipError_t launch_yolo_loss(const LossGrids &grids, const LossGeom &geo, int B, 
                             const int32_t *gt_classes, const int32_t *cells, int G, double *loss, hipStream_t s);
 
 size_t nms_workspace_bytes(int B, int N);
-hipError_t launch_nms(const float *boxes, const float *scores, int B, int N, int M, float T, float S, int32_t *sel,
-                      int32_t *num_valid, void *ws, hipStream_t s);
+size_t nms_per_class_workspace_bytes(int B, int N);   // the above + B * N * 4: the class ids of the spilled kept boxes
+// cls: null for the class-agnostic rule; the class ids [B,N] for the per-class one, ws then holding nms_per_class_workspace_bytes
+hipError_t launch_nms(const float *boxes, const float *scores, const int64_t *cls, int B, int N, int M, float T, float S,
+                      int32_t *sel, int32_t *num_valid, void *ws, hipStream_t s);
 hipError_t launch_pack(const float *boxes, const int64_t *cls, const float *scores, const int32_t *sel,
                        const int32_t *nv, int B, int N, int M, void *packed, hipStream_t s);
 

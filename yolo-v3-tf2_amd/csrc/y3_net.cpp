@@ -1059,6 +1059,17 @@ try {
 }
 Y3_CATCH("y3_net_set_xcd_mode")
 
+y3_status y3_net_set_nms_mode(y3_net *net, int mode)
+try {
+    if (!net || (mode != Y3_NMS_AGNOSTIC && mode != Y3_NMS_PER_CLASS))
+        return fail(Y3_ERR_INVALID, "y3_net_set_nms_mode: mode must be Y3_NMS_AGNOSTIC (0) or Y3_NMS_PER_CLASS (1)");
+    net->nms_mode = mode;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_nms_mode")
+
+int y3_net_get_nms_mode(const y3_net *net) { return net ? net->nms_mode : Y3_NMS_AGNOSTIC; }
+
 y3_status y3_net_set_early_chunk(y3_net *net, int n_convs, int chunk_images)
 try {
     if (!net || n_convs < 0 || chunk_images < 0) return fail(Y3_ERR_INVALID, "y3_net_set_early_chunk: bad argument");

@@ -450,26 +450,48 @@ try {
 Y3_CATCH("y3_class_scores")
 
 size_t y3_nms_workspace_bytes(int batch, int n) { return (batch > 0 && n > 0) ? y3::nms_workspace_bytes(batch, n) : 0; }
+size_t y3_nms_per_class_workspace_bytes(int batch, int n) { return (batch > 0 && n > 0) ? y3::nms_per_class_workspace_bytes(batch, n) : 0; }
+
+// y3_nms_padded (class_idx_dev null) and y3_nms_padded_per_class: the argument checks both share, then the one launch
+static y3_status nms_padded(const char *who, const float *bboxes_dev, const float *scores_dev, const int64_t *class_idx_dev, int batch,
+                            int n, int max_output_size, float iou_threshold, float score_threshold, int32_t *selected_idx_dev,
+                            int32_t *num_valid_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    if (!bboxes_dev || !scores_dev || !selected_idx_dev || !num_valid_dev || batch <= 0 || n <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument", who);
+    if (max_output_size <= 0 || max_output_size > 1024)
+        return fail(Y3_ERR_INVALID, "%s: max_output_size must be in [1,1024]", who);
+    if ((uintptr_t)bboxes_dev & 15) return fail(Y3_ERR_INVALID, "%s: bboxes not 16-byte aligned", who);
+    if (class_idx_dev && !(iou_threshold > 0.0f))
+        return fail(Y3_ERR_INVALID, "%s: iou_threshold must be > 0 (iou_threshold <= 0 is the tile quirk of the class-agnostic rule)", who);
+    if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
+        return fail(Y3_ERR_INVALID, "%s: iou_threshold <= 0 together with score_threshold < 0 is not supported", who);
+    const size_t need = class_idx_dev ? y3::nms_per_class_workspace_bytes(batch, n) : y3::nms_workspace_bytes(batch, n);
+    if (!workspace_dev || workspace_bytes < need) return fail(Y3_ERR_INVALID, "%s: workspace too small (need %zu bytes)", who, need);
+    hipError_t e = y3::launch_nms(bboxes_dev, scores_dev, class_idx_dev, batch, n, max_output_size, iou_threshold, score_threshold,
+                                  selected_idx_dev, num_valid_dev, workspace_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}
 
 y3_status y3_nms_padded(const float *bboxes_dev, const float *scores_dev, int batch, int n, int max_output_size,
                         float iou_threshold, float score_threshold, int32_t *selected_idx_dev,
                         int32_t *num_valid_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
 try {
-    if (!bboxes_dev || !scores_dev || !selected_idx_dev || !num_valid_dev || batch <= 0 || n <= 0)
-        return fail(Y3_ERR_INVALID, "y3_nms_padded: bad argument");
-    if (max_output_size <= 0 || max_output_size > 1024)
-        return fail(Y3_ERR_INVALID, "y3_nms_padded: max_output_size must be in [1,1024]");
-    if ((uintptr_t)bboxes_dev & 15) return fail(Y3_ERR_INVALID, "y3_nms_padded: bboxes not 16-byte aligned");
-    if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
-        return fail(Y3_ERR_INVALID, "y3_nms_padded: iou_threshold <= 0 together with score_threshold < 0 is not supported");
-    if (!workspace_dev || workspace_bytes < y3::nms_workspace_bytes(batch, n))
-        return fail(Y3_ERR_INVALID, "y3_nms_padded: workspace too small (need %zu bytes)", y3::nms_workspace_bytes(batch, n));
-    hipError_t e = y3::launch_nms(bboxes_dev, scores_dev, batch, n, max_output_size, iou_threshold, score_threshold,
-                                  selected_idx_dev, num_valid_dev, workspace_dev, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_nms_padded launch: %s", hipGetErrorString(e));
-    return Y3_OK;
+    return nms_padded("y3_nms_padded", bboxes_dev, scores_dev, nullptr, batch, n, max_output_size, iou_threshold, score_threshold,
+                      selected_idx_dev, num_valid_dev, workspace_dev, workspace_bytes, stream);
 }
 Y3_CATCH("y3_nms_padded")
+
+y3_status y3_nms_padded_per_class(const float *bboxes_dev, const float *scores_dev, const int64_t *class_idx_dev, int batch, int n,
+                                  int max_output_size, float iou_threshold, float score_threshold, int32_t *selected_idx_dev,
+                                  int32_t *num_valid_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
+try {
+    if (!class_idx_dev) return fail(Y3_ERR_INVALID, "y3_nms_padded_per_class: bad argument");
+    return nms_padded("y3_nms_padded_per_class", bboxes_dev, scores_dev, class_idx_dev, batch, n, max_output_size, iou_threshold,
+                      score_threshold, selected_idx_dev, num_valid_dev, workspace_dev, workspace_bytes, stream);
+}
+Y3_CATCH("y3_nms_padded_per_class")
 
 y3_status y3_pack_detections(const float *bboxes_dev, const int64_t *class_idx_dev, const float *scores_dev,
                              const int32_t *selected_idx_dev, const int32_t *num_valid_dev, int batch, int n,

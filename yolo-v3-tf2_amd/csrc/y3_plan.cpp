@@ -223,7 +223,7 @@ y3::DetectLayout y3::detect_layout(const y3_net *net, int batch)
     L.scores = L.cls + up((size_t)batch * n * 8);
     L.sel = L.scores + up((size_t)batch * n * 4);       // selected indices
     L.nms_ws = L.sel + up((size_t)batch * Y3_MAX_OUTPUT_BOXES * 4);
-    L.total = L.nms_ws + nms_workspace_bytes(batch, (int)n);
+    L.total = L.nms_ws + nms_per_class_workspace_bytes(batch, (int)n);   // the larger of the two: the NMS mode may be switched after planning
     return L;
 }
 

@@ -96,7 +96,7 @@ def report_ap(ap, iou_thresholds):
 
 
 def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_batches, weights, one_class, anchors_table, nclasses,
-                        loss=False, ap=None):
+                        loss=False, ap=None, nms_per_class=False):
     """One model and one pass: the un-stacked data set is batched here (images with unlike numbers of boxes may share a batch)
     by a generator that Net.evaluate_stream draws from, so records are decoded while earlier batches run and the data set is
     never held in memory; only the counters come back."""
@@ -110,6 +110,7 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     model.model.set_i8_calibration(detect_config.get("i8_calibration"))   # optional key, needed with dtype i8: the file of tools/calibrate_i8.py
     model.model.set_dtype(detect_config.get("dtype"))     # optional key: f32 | bf16 | f16 | i8; absent: f32
     model.model.set_stem_fusion_f16(detect_config.get("f16_fused_stem"))   # optional key, acts on dtype f16 only; absent: off
+    model.model.set_nms_per_class(nms_per_class)          # the device net's detect, and the composed route of loss=True, follow it
     net = model.model._device_net()
     if net.image_size != S or net.max_batch < batch_size:
         net.plan(max(batch_size, net.max_batch), S)
@@ -166,7 +167,7 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
 
 
 def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshold=0.5, max_batches=20, weights=None,
-             one_class=True, on_device=False, loss=False, ap=None):
+             one_class=True, on_device=False, loss=False, ap=None, nms_per_class=False):
     """The loop of reference evaluate_yolov3.py:153-232: for every score threshold build the detect model, run the
     first `max_batches` dataset batches (`dataset.take(20)` there), count, and report (recall, precision).
     Returns [(threshold, recall, precision, counters, counters_oneclass)].
@@ -184,7 +185,11 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     or (results, loss, ap).  AP is no reference counterpart; it is taken over the detections at the LOWEST of
     evaluate_nms_score_thresholds, with the class ids as they are (the plain variant, whatever one_class says).
     An optional `dtype: f32 | bf16 | f16` key of detect_config selects the conv arithmetic of the on_device pass (absent: f32);
-    an optional `f16_fused_stem: true` runs the first convs of an f16 plan as the fused stem kernel (absent: off)."""
+    an optional `f16_fused_stem: true` runs the first convs of an f16 plan as the fused stem kernel (absent: off).
+    nms_per_class=True, or an optional `nms_per_class: true` key of detect_config (absent: off), on either route: per-class NMS
+    (Net.nms_per_class; no reference counterpart) -- a box is suppressed only by a kept box of its own class, the rule published
+    YOLOv3 mAP figures are taken under.  The one-pass argument of on_device=True holds as it stands: a box is never affected by a
+    box scored below it under either rule."""
     if loss and not on_device:
         raise ValueError("evaluate: loss=True needs on_device=True (the loss is computed on the GPU, from the device pass)")
     ap = None if ap is False else ap
@@ -193,9 +198,10 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     anchors_table = np.asarray(get_anchors(detect_config["anchors_file"]), np.float32)
     class_names = [c.strip() for c in open(detect_config["classes_name_file"]).readlines()]
     nclasses = len(class_names)
+    nms_per_class = bool(nms_per_class or detect_config.get("nms_per_class"))
     if on_device:
         return _evaluate_on_device(detect_config, list(evaluate_nms_score_thresholds), evaluate_iou_threshold, max_batches, weights,
-                                   one_class, anchors_table, nclasses, loss=loss, ap=ap)
+                                   one_class, anchors_table, nclasses, loss=loss, ap=ap, nms_per_class=nms_per_class)
     dataset = prepare_dataset(detect_config["tfrecords_dir"], detect_config["batch_size"], detect_config["image_size"],
                               detect_config["yolo_max_boxes"], detect_config["classes_name_file"])
     results = []
@@ -203,6 +209,7 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
         model = create_model(detect_config["model_config_file"], nclasses, anchors_table, nms_score_threshold,
                              detect_config["nms_iou_threshold"], detect_config["yolo_max_boxes"],
                              detect_config.get("input_weights_path"), weights)
+        model.model.set_nms_per_class(nms_per_class)
         eval_detections = EvaluateDetections(nclasses, evaluate_iou_threshold)
         eval_detections_oneclass = EvaluateDetections(nclasses, evaluate_iou_threshold)
         for n, (batch_images, batch_gt_y) in enumerate(dataset):
@@ -222,7 +229,7 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     return results
 
 
-def main(argv=None):
+def _arg_parser():
     import argparse
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="config/detect_config.yaml")
@@ -234,6 +241,14 @@ def main(argv=None):
     ap.add_argument("--ap", action="store_true",
                     help="with --on-device: also COCO-style AP50, AP75 and mAP from the same pass (IoU thresholds: the optional "
                          "evaluate_ap_iou_thresholds key of the evaluate config, by default 0.5, 0.55, ..., 0.95)")
+    ap.add_argument("--nms-per-class", action="store_true",
+                    help="per-class NMS: a box is suppressed only by a kept box of its own class (also the optional nms_per_class "
+                         "key of either config; absent: the reference's class-agnostic rule)")
+    return ap
+
+
+def main(argv=None):
+    ap = _arg_parser()
     a = ap.parse_args(argv)
     if a.loss and not a.on_device:
         ap.error("--loss needs --on-device")
@@ -245,7 +260,8 @@ def main(argv=None):
     ap_thresholds = (evaluate_config.get("evaluate_ap_iou_thresholds") or True) if a.ap else None
     with open(a.config) as s:
         detect_config = yaml.safe_load(s)
-    results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss, ap=ap_thresholds)
+    results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss, ap=ap_thresholds,
+                       nms_per_class=a.nms_per_class or bool(evaluate_config.get("nms_per_class")))
     if a.loss or a.ap:
         results = results[0]      # the loss and the AP have been printed by evaluate
     print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in results])

@@ -39,14 +39,20 @@ class DetectModel:
     def __call__(self, images):
         """images: [B,S,S,3] fp32 (numpy or CUDA tensor) -> the 5-tuple as CUDA tensors."""
         grids = self.model(images)
+        per_class = bool(getattr(self.model, "nms_per_class", False))      # the model's switch (set_nms_per_class), read per call
         if self.fused:
-            from . import runtime
+            from . import ops, runtime
             bboxes, cls, scores = runtime.yolo_decode_scores(grids, self.anchors_table, self.nclasses)
-            sel, nv = runtime.nms_padded(bboxes, scores, self.yolo_max_boxes, self.nms_iou_threshold,
-                                         self.nms_score_threshold)
+            if per_class:
+                sel, nv = ops.nms_padded_per_class(bboxes, scores, cls, self.yolo_max_boxes, self.nms_iou_threshold,
+                                                   self.nms_score_threshold)
+            else:
+                sel, nv = runtime.nms_padded(bboxes, scores, self.yolo_max_boxes, self.nms_iou_threshold,
+                                             self.nms_score_threshold)
             return bboxes, cls, scores, sel, nv
         from .core.yolo_decode_layer import yolo_decode
         decoded_output = yolo_decode(grids, self.anchors_table, self.nclasses)      # reference: inference.py:111
+        self.nms_layer.per_class = per_class
         return self.nms_layer(decoded_output)                                        # reference: inference.py:114-115
 
     def predict(self, images, **_):
@@ -57,6 +63,9 @@ class Inference:
     # fp16 plans with the fused stem kernel (runtime.Net.set_stem_fusion_f16; None: off).  The optional YAML key `f16_fused_stem` of the
     # inference config lands here (main()); __call__ keeps the reference's keys plus the two every plan has, low_latency and dtype.
     f16_fused_stem = None
+    # Per-class NMS (core.parse_model.YoloModel.set_nms_per_class; None or False: the reference's class-agnostic rule).  The optional YAML
+    # key `nms_per_class` lands here the same way.
+    nms_per_class = None
 
     @staticmethod
     def gather_valid_detections_results(bboxes_padded, class_indices_padded, scores_padded, selected_indices_padded,
@@ -130,6 +139,7 @@ class Inference:
         model.set_i8_calibration(i8_calibration)
         model.set_dtype(dtype)
         model.set_stem_fusion_f16(self.f16_fused_stem if f16_fused_stem is None else f16_fused_stem)
+        model.set_nms_per_class(self.nms_per_class)
         print("weights loaded")
         return DetectModel(model, anchors_table, nclasses, yolo_max_boxes, nms_iou_threshold,
                            nms_score_threshold), class_names
@@ -225,6 +235,7 @@ def main(argv=None):
         detect_config = yaml.safe_load(stream)
     inference = Inference()
     inference.f16_fused_stem = detect_config.pop("f16_fused_stem", None)    # optional key, absent: off
+    inference.nms_per_class = detect_config.pop("nms_per_class", None)      # optional key, absent: off
     inference(**detect_config)
 
 

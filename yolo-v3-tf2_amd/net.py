@@ -128,6 +128,19 @@ class Net:
         """In how many of its sub-batches a forward of `batch` images launches conv `slot` of the planned net with the border skip."""
         return int(self.lib.y3_net_get_border_skip(self._h, int(slot), int(batch)))
 
+    @property
+    def nms_per_class(self) -> bool:
+        """Which NMS rule detect, detect_stream and evaluate_stream run (y3_net_set_nms_mode): False (the default), the reference's
+        class-agnostic rule; True, a box is suppressed only by a kept box of its own class (ops.nms_padded_per_class; needs
+        iou_threshold > 0).  Read whenever a detect is enqueued: a captured graph keeps the rule it was captured with."""
+        return self.lib.y3_net_get_nms_mode(self._h) == _lib.Y3_NMS_PER_CLASS
+
+    @nms_per_class.setter
+    def nms_per_class(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"nms_per_class: a bool (got {on!r})")
+        check(self.lib.y3_net_set_nms_mode(self._h, _lib.Y3_NMS_PER_CLASS if on else _lib.Y3_NMS_AGNOSTIC), "y3_net_set_nms_mode")
+
     @staticmethod
     def _dtype_arg(dtype) -> int:
         """None (absent: fp32), a _lib.Y3_DTYPE_* value or its tag ("f32", "bf16", "f16", "f32x3", "f32x2") -> the Y3_DTYPE_* value."""

@@ -272,11 +272,14 @@ def yolo_loss(grids, anchors_table, nclasses: int, gt_boxes: torch.Tensor, gt_cl
     return loss
 
 
-_ws_cache: Dict[tuple, torch.Tensor] = {}
+# the last NMS workspace per rule (per class or not): ((device, bytes), tensor).  One per rule, so that a call under the other rule
+# does not free the workspace a captured graph of this one replays on
+_ws_cache: Dict[bool, tuple] = {}
 
 
-def _nms_workspace_bytes(B, N):
-    return _lib.load().y3_nms_workspace_bytes(B, N)
+def _nms_workspace_bytes(B, N, per_class=False):
+    lib = _lib.load()
+    return lib.y3_nms_per_class_workspace_bytes(B, N) if per_class else lib.y3_nms_workspace_bytes(B, N)
 
 
 def nms_padded(bboxes, scores, max_output_size, iou_threshold, score_threshold):
@@ -284,25 +287,41 @@ def nms_padded(bboxes, scores, max_output_size, iou_threshold, score_threshold):
     return _nms(bboxes, scores, max_output_size, iou_threshold, score_threshold)
 
 
-def _nms(bboxes, scores, max_output_size, iou_threshold, score_threshold, out=None, ws=None):
-    """nms_padded; out: the (sel, nv) tensors to write; ws: the caller's own workspace instead of the process-wide _ws_cache."""
-    _need_cuda(bboxes, scores)
+def nms_padded_per_class(bboxes, scores, classes, max_output_size, iou_threshold, score_threshold):
+    """nms_padded with one predicate changed (y3_nms_padded_per_class): a box is suppressed by an earlier kept box iff their class
+    ids are equal and IoU >= iou_threshold; the first max_output_size selected boxes over all classes together are returned.
+    classes: int64 [B,N] as class_scores / yolo_decode_scores give them, ids in [0, 2^31).  iou_threshold must be > 0.
+    -> (selected_indices_padded [B,M] i32, num_valid [B] i32).  Host restatement: nms_per_class.nms_padded_per_class_ref."""
+    return _nms(bboxes, scores, max_output_size, iou_threshold, score_threshold, classes=classes)
+
+
+def _nms(bboxes, scores, max_output_size, iou_threshold, score_threshold, out=None, ws=None, classes=None):
+    """nms_padded, with `classes` nms_padded_per_class; out: the (sel, nv) tensors to write; ws: the caller's own workspace instead
+    of the process-wide _ws_cache."""
+    _need_cuda(bboxes, scores, classes)
     if bboxes.dtype != torch.float32 or scores.dtype != torch.float32:
         raise Y3Error("boxes and scores must be float32")
     B, N = scores.shape
+    if classes is not None and (classes.dtype != torch.int64 or classes.shape != (B, N) or not classes.is_contiguous()):
+        raise Y3Error(f"nms_padded_per_class: classes must be contiguous int64 [{B},{N}]")
     lib = _lib.load()
     if ws is None:
-        need = _nms_workspace_bytes(B, N)
+        need = _nms_workspace_bytes(B, N, classes is not None)
         key = (bboxes.device.index, need)
-        ws = _ws_cache.get(key)
-        if ws is None:
-            _ws_cache.clear()
-            ws = _ws_cache[key] = torch.empty(need, dtype=torch.uint8, device=bboxes.device)
+        held = _ws_cache.get(classes is not None)
+        if held is None or held[0] != key:
+            held = _ws_cache[classes is not None] = (key, torch.empty(need, dtype=torch.uint8, device=bboxes.device))
+        ws = held[1]
     sel, nv = out or (torch.empty((B, int(max_output_size)), dtype=torch.int32, device=bboxes.device),
                       torch.empty((B,), dtype=torch.int32, device=bboxes.device))
-    check(lib.y3_nms_padded(_dev(bboxes), _dev(scores), B, N, int(max_output_size), float(iou_threshold),
-                            float(score_threshold), _dev(sel), _dev(nv), _dev(ws), ws.numel(), _lib.stream_ptr()),
-          "y3_nms_padded")
+    if classes is None:
+        check(lib.y3_nms_padded(_dev(bboxes), _dev(scores), B, N, int(max_output_size), float(iou_threshold),
+                                float(score_threshold), _dev(sel), _dev(nv), _dev(ws), ws.numel(), _lib.stream_ptr()),
+              "y3_nms_padded")
+    else:
+        check(lib.y3_nms_padded_per_class(_dev(bboxes), _dev(scores), _dev(classes), B, N, int(max_output_size), float(iou_threshold),
+                                          float(score_threshold), _dev(sel), _dev(nv), _dev(ws), ws.numel(), _lib.stream_ptr()),
+              "y3_nms_padded_per_class")
     return sel, nv
 
 

@@ -52,7 +52,8 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
     The device buffers are slot i % depth of a ring: the consumer's reads are ordered before their reuse by the stream.
     keep_grids: the consumer wants the raw head grids as well (`grids`: three [n,g,g,3,5+nc] views, otherwise None), so
     each batch takes the composed route include/y3.h documents as bit-identical to y3_net_detect: y3_net_forward into
-    grid buffers made once here, y3_yolo_decode_scores, y3_nms_padded, y3_pack_detections.  One set of buffers, the NMS
+    grid buffers made once here, y3_yolo_decode_scores, y3_nms_padded (y3_nms_padded_per_class when net.nms_per_class is set,
+    as y3_net_detect itself chooses), y3_pack_detections.  One set of buffers, the NMS
     workspace among them, serves every batch: all of it runs on the one stream."""
     if max_batch is None or max_blob_bytes is None:
         if not isinstance(batches, (list, tuple)):
@@ -86,7 +87,7 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
         cls = torch.empty((max_batch, N), dtype=torch.int64, device=dev)
         scores = torch.empty((max_batch, N), dtype=torch.float32, device=dev)
         sel = torch.empty((max_batch, M), dtype=torch.int32, device=dev)
-        ws = torch.empty(ops._nms_workspace_bytes(max_batch, N), dtype=torch.uint8, device=dev)
+        ws = torch.empty(ops._nms_workspace_bytes(max_batch, N, per_class=True), dtype=torch.uint8, device=dev)   # serves either rule
     it = iter(batches)
     first = next(it, None)
     handle = stage.submit(first, mode, letterbox) if first is not None else None
@@ -103,7 +104,8 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
             grids = [t[:n] for t in grid_bufs]
             check(net.lib.y3_net_forward(net._h, _dev(handle.batch), n, grid_ptrs, sp), "y3_net_forward")
             decoded = ops._decode_scores(grids, a, nc, out=(bboxes[:n], cls[:n], scores[:n]))
-            picked = ops._nms(decoded[0], decoded[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws)
+            picked = ops._nms(decoded[0], decoded[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws,
+                              classes=decoded[1] if net.nms_per_class else None)     # the rule y3_net_detect would take
             ops._pack(*decoded, *picked, out=packed_dev[:n])
         else:
             check(net.lib.y3_net_detect(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),

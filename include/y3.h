@@ -539,6 +539,67 @@ y3_status y3_unletterbox_detections_hw(void *packed_dev, const int32_t *num_vali
                                        int max_boxes, int canvas_h, int canvas_w, void *stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Sliced inference (no reference counterpart; nothing here runs unless it is called): a large frame is cut into overlapping
+ * windows, every window goes through the network as an image of its own, and the windows' detections are mapped back to the frame
+ * and merged by a second NMS.  Host restatements: tiles.tile_grid, tiles.merge_tile_detections_ref.
+ * ---------------------------------------------------------------------------------------- */
+/* The windows of a height x width frame, on the host, integers only: out[T][4] = {y0, x0, ch, cw}, rows x cols windows in
+ * row-major order and, with overview != 0, the whole frame {0, 0, height, width} LAST.  Per axis, with extent e, count k and
+ * ov = overlap_px:
+ *   len = ceil_div(e + (k - 1) * ov, k)          origin of window i = floor(i * (e - len) / (k - 1)), 0 when k == 1
+ * so that every window lies inside the frame, the windows cover it, the first starts at 0, the last ends at e and neighbours
+ * overlap by at least ov.  Returns T = rows * cols + (overview ? 1 : 0), or -1 (with y3_last_error) for what it refuses: a null
+ * `out`, height or width < 1, rows or cols outside [1,8], ov < 0, ov > min(height, width), T > 64. */
+int y3_tile_grid(int height, int width, int rows, int cols, int overlap_px, int overview, int32_t *out);
+
+/* y3_preprocess_batch_hw for windows of images: tile i is the window [y0, y0 + ch) x [x0, x0 + cw) of the
+ * height x width x channels image that starts `offset` bytes into pixels_dev, and is treated AS AN IMAGE OF ITS OWN: the bilinear
+ * taps clamp at the window's edges, and with Y3_IMAGE_LETTERBOX the geometry is that of a ch x cw image.  `mode` as in
+ * y3_image_desc.  Tile i is written to batch_dev[first_slot + i], and every value is bit-identical to y3_preprocess_batch_hw on a
+ * contiguous copy of the window: the same per-pixel body reads the frame with the frame's row pitch.  Several tiles may name the
+ * same image, which is therefore uploaded once.  The descriptors travel in the kernel arguments, 72 tiles per launch.  Checked on
+ * the host before anything is enqueued (Y3_ERR_INVALID names the tile): everything y3_preprocess_batch checks, ch and cw >= 1,
+ * the window inside the image, the letterbox of ch x cw fitting the canvas.  Only enqueues on `stream`; can be captured. */
+typedef struct y3_tile_desc { uint64_t offset; int32_t height, width, channels, mode; int32_t y0, x0, ch, cw; } y3_tile_desc;
+y3_status y3_preprocess_tiles_hw(const void *pixels_dev, size_t pixels_bytes, const y3_tile_desc *descs_host, int n_tiles,
+                                 float *batch_dev, int first_slot, int canvas_h, int canvas_w, void *stream);
+/* y3_letterbox_geometry_hw for tiles, on the host: geoms_out_host[n_tiles][4] = {sh, sw, top, left} from (ch, cw) and mode of
+ * each descriptor -- the geometry of a ch x cw image; without the flag {canvas_h, canvas_w, 0, 0}. */
+y3_status y3_tile_letterbox_geometry_hw(const y3_tile_desc *descs_host, int n_tiles, int canvas_h, int canvas_w, int32_t *geoms_out_host);
+
+/* The tiles' packed rows -> one packed result per frame.  packed_dev [frames*tiles,max_boxes,7] and num_valid_dev [frames*tiles]
+ * are what y3_net_detect leaves on the tile batch (tile t of frame f is image f * tiles + t): boxes normalised to the canvas and
+ * NOT un-letterboxed.  tiles_host [frames*tiles][4] = {y0, x0, ch, cw} (y3_tile_grid), geoms_host [frames*tiles][4] =
+ * {sh, sw, top, left} (y3_tile_letterbox_geometry_hw), frame_hw_host [frames][2] = {h, w}; all three are read during the call
+ * (they travel in the kernel arguments, 64 tile images per launch).
+ * merge_tiles_kernel writes three candidate arrays per frame into the workspace, candidate n = t * max_boxes + r: boxes
+ * [frames,tiles*max_boxes,4], scores [frames,tiles*max_boxes], class ids int64 [frames,tiles*max_boxes].  For a row
+ * r < num_valid (clamped to [0,max_boxes]), per axis in fp32, every operation rounded on its own:
+ *   u  = (x * (float)canvas_w - (float)left) / (float)sw        u = x where sw == canvas_w and left == 0
+ *   x' = ((float)x0 + u * (float)cw) / (float)w                 x' = u where x0 == 0 and cw == w
+ * and y likewise with sh, top, canvas_h, y0, ch, h.  u is the expression of y3_unletterbox_detections_hw, but the identity is
+ * decided PER AXIS here (there the whole geometry decides: an axis that fills the canvas of a letterboxed image is computed as
+ * x * W / W, which need not be x).  Score and class are copied; nothing is clipped.  A row r >= num_valid becomes box 0, score 0,
+ * class 0, which the padded NMS never selects; every word of the three arrays is written.
+ * Then, on the same stream and on those arrays, the existing y3_nms_padded(frames, tiles*max_boxes, max_boxes, iou_threshold,
+ * score_threshold) -- y3_nms_padded_per_class with nms_mode == Y3_NMS_PER_CLASS -- and y3_pack_detections: the merged rows are
+ * that rule applied to the union of the tiles' survivors, every quirk of it included (the canonicalisation decided by candidate 0
+ * of frame 0, iou_threshold <= 0).  packed_out_dev [frames,max_boxes,7], num_valid_out_dev [frames]; the index word of a merged
+ * row is t * max_boxes + r.
+ * The workspace (16-byte aligned) holds, each part starting on a multiple of 16 bytes and in this order, the candidate boxes, class ids
+ * and scores, the selected indices [frames,max_boxes] and the NMS workspace of (frames, tiles*max_boxes):
+ * y3_merge_tiles_workspace_bytes, which serves either mode and is 0 for arguments the call refuses.  Checked on the host before
+ * anything is enqueued (Y3_ERR_INVALID names the offender): frames >= 1, tiles in [1,64], max_boxes in [1,1024], frames * tiles *
+ * max_boxes < 2^31, the windows inside their frames, the geometries inside the canvas, nms_mode, the threshold checks of the NMS
+ * call, the workspace size, the alignment (packed 4 bytes, workspace 16).  Only enqueues on `stream`; can be captured. */
+size_t y3_merge_tiles_workspace_bytes(int frames, int tiles, int max_boxes);
+y3_status y3_merge_tile_detections(const void *packed_dev, const int32_t *num_valid_dev, const int32_t *tiles_host,
+                                   const int32_t *geoms_host, const int32_t *frame_hw_host, int frames, int tiles, int max_boxes,
+                                   int canvas_h, int canvas_w, int nms_mode, float iou_threshold, float score_threshold,
+                                   void *packed_out_dev, int32_t *num_valid_out_dev, void *workspace_dev, size_t workspace_bytes,
+                                   void *stream);
+
+/* ------------------------------------------------------------------------------------------
  * Evaluation counters for every NMS score threshold of a sweep, from ONE detect pass (reference:
  * evaluate_detections.py:37-48,82-135, EvaluateDetections.iou_alg / evaluate; evaluate_yolov3.py:153-232, the loop over
  * evaluate_nms_score_thresholds that the reference runs as one whole pass over the data set per threshold).

@@ -25,6 +25,7 @@ TILES_X2_BUILT = (0, 1, 2, 3, 4, 8, 12, 26, 27)
 TILES_X3_BUILT = (0, 1, 2, 3, 4, 8, 9, 12, 13, 14)
 Y3_AUX_ADD, Y3_AUX_UPSAMPLE2X, Y3_AUX_CONCAT = 0, 1, 2
 Y3_NMS_AGNOSTIC, Y3_NMS_PER_CLASS = 0, 1   # y3_net_set_nms_mode
+MAX_TILES = 64   # y3_tile_grid, y3_merge_tile_detections: tiles per frame
 # (BM, BN, waves, LDS stages) of every tile id of the fp32 MFMA conv kernel (mirror of kTiles in csrc/conv_f32.hip)
 # (0, 0, 0, 0): a retired id (y3_tile_built answers 0).  Round 5: only tiles a packaged tuning table or the library's heuristic selects are built.
 _Z = (0, 0, 0, 0)
@@ -92,6 +93,11 @@ class ImageDesc(C.Structure):
                 ("mode", C.c_int32)]
 
 
+class TileDesc(C.Structure):
+    """y3_tile_desc: one window of an image of a y3_preprocess_tiles_hw pixel blob."""
+    _fields_ = [("offset", C.c_uint64)] + [(n, C.c_int32) for n in ("height", "width", "channels", "mode", "y0", "x0", "ch", "cw")]
+
+
 _vp, _i, _f, _sz = C.c_void_p, C.c_int, C.c_float, C.c_size_t
 _fp = C.POINTER(C.c_float)
 
@@ -154,6 +160,12 @@ SYMBOLS = {
     "y3_letterbox_geometry_hw": (_i, [C.POINTER(ImageDesc), _i, _i, _i, C.POINTER(C.c_int32)]),
     "y3_unletterbox_detections": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _vp]),
     "y3_unletterbox_detections_hw": (_i, [_vp, _vp, C.POINTER(C.c_int32), _i, _i, _i, _i, _vp]),
+    "y3_tile_grid": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(C.c_int32)]),
+    "y3_preprocess_tiles_hw": (_i, [_vp, _sz, C.POINTER(TileDesc), _i, _vp, _i, _i, _i, _vp]),
+    "y3_tile_letterbox_geometry_hw": (_i, [C.POINTER(TileDesc), _i, _i, _i, C.POINTER(C.c_int32)]),
+    "y3_merge_tiles_workspace_bytes": (_sz, [_i, _i, _i]),
+    "y3_merge_tile_detections": (_i, [_vp, _vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32), _i, _i, _i, _i, _i, _i,
+                                      _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "y3_evaluate_detections": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _f, _fp, _i, _i, _vp, _vp]),
     "y3_match_detections": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i, _i, _fp, _i, _i, _vp, _vp, _vp]),
     "y3_yolo_assign_targets": (_i, [_vp, _vp, _vp, _i, _i, _i, C.POINTER(C.c_int32), _fp, _vp, _vp]),

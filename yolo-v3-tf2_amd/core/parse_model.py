@@ -48,6 +48,7 @@ class YoloModel:
         # switches, stem fusion, the calibration file an "i8" plan needs, the dtype (None: fp32).  An entry at its value here is skipped.
         self._deferred = dict(_DEFERRED_DEFAULTS)
         self.nms_per_class = False      # set_nms_per_class: a property of the device net, not one of its methods, so kept beside them
+        self.tiles = None               # set_tiles: (rows, cols, overlap_px, overview), the device net's property of that name
 
     def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, i8_calibration, dtype
         method = {"i8_calibration": "load_calibration"}.get(name, "set_" + name)
@@ -64,6 +65,7 @@ class YoloModel:
                 if arg != _DEFERRED_DEFAULTS[method]:
                     getattr(self._net, method)(arg)
             self._net.nms_per_class = self.nms_per_class
+            self._net.tiles = self.tiles
             if self._weights is not None:
                 self._net.load_weights(self._weights)
         return self._net
@@ -104,6 +106,21 @@ class YoloModel:
         self.nms_per_class = bool(on)
         if self._net is not None:
             self._net.nms_per_class = self.nms_per_class
+
+    def set_tiles(self, rows=None, cols=None, overlap_px=0, overview=False):
+        """Sliced inference (runtime.Net.detect_stream / evaluate_stream, tiles=; no reference counterpart): every frame is cut into
+        rows x cols windows overlapping by at least overlap_px pixels, plus the whole frame with overview, each window runs through the
+        network at full resolution and the windows' detections are merged on the device.  set_tiles(None), the default: off.  The device
+        net's detect_stream / evaluate_stream follow it (runtime.Net.tiles), and through them inference.Inference and evaluate_yolov3."""
+        if rows is None:
+            tiles = None
+        else:
+            from ..tiles import tile_grid
+            tiles = (int(rows), int(cols), int(overlap_px), bool(overview))
+            tile_grid(max(tiles[2], 1), max(tiles[2], 1), *tiles)      # the grid's own checks on the smallest frame that takes the overlap (ValueError)
+        self.tiles = tiles
+        if self._net is not None:
+            self._net.tiles = tiles
 
     def set_dtype(self, dtype):
         """Conv arithmetic of the plans (runtime.Net.set_dtype): None or "f32" (default), "bf16", "f16" -- 16-bit activations and

@@ -9,8 +9,9 @@
 // Arithmetic restated from TF's ResizeBilinear CPU kernel: in = (out + 0.5) * (in_size / out_size) - 0.5,
 // lower = max(floor(in), 0), upper = min(ceil(in), in_size - 1), lerp = in - floor(in); interpolate along x first
 // (top, bottom) then along y; fp32, no contraction.  HBM-bound and tiny.  resize_kernel: one image per launch, one thread per
-// output pixel; preprocess_batch_kernel: up to 64 unlike images per launch, four pixels per thread.
-// Both also serve the aspect-preserving form of reference core/utils.py:17-28 (resize_image: tf.image.resize(
+// output pixel; preprocess_batch_kernel: up to 64 unlike images per launch, four pixels per thread; preprocess_tiles_kernel: the same for
+// up to 72 windows of such images, each window an image of its own (sliced inference; include/y3.h, y3_preprocess_tiles_hw).
+// All of them also serve the aspect-preserving form of reference core/utils.py:17-28 (resize_image: tf.image.resize(
 // preserve_aspect_ratio=True) + pad_to_bounding_box), flag Y3_IMAGE_LETTERBOX: resize to sh x sw, centred on a zero canvas.
 #include <type_traits>
 
@@ -34,9 +35,11 @@ __device__ __forceinline__ float px<RawU8>(const RawU8 *p) { return (float)p->v;
 // LB (Y3_IMAGE_LETTERBOX): the resize is to g.sh x g.sw and sits at (g.top, g.left) of the canvas; a pixel outside that
 // block is 0.0f -- it is written like any other, a reused slot keeps nothing of its last image.  Inside, the same operations in
 // the same order with (sh, sw) in the place of (Hc, Wc).  LB = false compiles to what it was before the flag existed.
+// row_pitch: elements of T from one source row to the next -- W * pix_stride for an image of its own, the frame's pitch for a window
+// of a frame (preprocess_tiles_kernel), whose taps clamp at the window's edges like any image's.
 template <typename T, bool LB>
-__device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, int Hc, int Wc, LetterboxGeom g, int i,
-                                             float *out)
+__device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, size_t row_pitch, int Hc, int Wc,
+                                             LetterboxGeom g, int i, float *out)
 {
     int oy = i / Wc, ox = i - oy * Wc;
     if (LB) {
@@ -54,7 +57,7 @@ __device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, i
     const int y0 = max((int)fly, 0), y1 = min((int)ceilf(fy), H - 1);
     const int x0 = max((int)flx, 0), x1 = min((int)ceilf(fx), W - 1);
     const float ly = fy - fly, lx = fx - flx;
-    const T *r0 = src + (size_t)y0 * W * pix_stride, *r1 = src + (size_t)y1 * W * pix_stride;
+    const T *r0 = src + (size_t)y0 * row_pitch, *r1 = src + (size_t)y1 * row_pitch;
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float tl = px<T>(r0 + x0 * pix_stride + c), tr = px<T>(r0 + x1 * pix_stride + c);
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, 
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= Hc * Wc) return;
     float v[3];
-    resize_pixel<T, LB>(src, H, W, pix_stride, Hc, Wc, g, i, v);
+    resize_pixel<T, LB>(src, H, W, pix_stride, (size_t)W * pix_stride, Hc, Wc, g, i, v);
 #pragma unroll
     for (int c = 0; c < 3; ++c) dst[(size_t)i * 3 + c] = v[c];
 }
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, 
 // pixel and three scalar stores per thread.  Each of the four pixels decides on its own whether it is padding: a thread may
 // straddle the edge of the letterboxed block.
 template <typename T, bool VEC, bool LB>
-__device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src, int H, int W, int pix_stride,
+__device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src, int H, int W, int pix_stride, size_t row_pitch,
                                                       float *__restrict__ dst, int Hc, int Wc, LetterboxGeom g)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
@@ -94,7 +97,7 @@ __device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src,
         if (q * 4 >= Hc * Wc) return;
         float v[12];
 #pragma unroll
-        for (int p = 0; p < 4; ++p) resize_pixel<T, LB>(src, H, W, pix_stride, Hc, Wc, g, q * 4 + p, v + 3 * p);
+        for (int p = 0; p < 4; ++p) resize_pixel<T, LB>(src, H, W, pix_stride, row_pitch, Hc, Wc, g, q * 4 + p, v + 3 * p);
         float4 *o = reinterpret_cast<float4 *>(dst + (size_t)q * 12);
         o[0] = make_float4(v[0], v[1], v[2], v[3]);
         o[1] = make_float4(v[4], v[5], v[6], v[7]);
@@ -102,22 +105,24 @@ __device__ __forceinline__ void preprocess_batch_body(const T *__restrict__ src,
     } else {
         if (q >= Hc * Wc) return;
         float v[3];
-        resize_pixel<T, LB>(src, H, W, pix_stride, Hc, Wc, g, q, v);
+        resize_pixel<T, LB>(src, H, W, pix_stride, row_pitch, Hc, Wc, g, q, v);
 #pragma unroll
         for (int c = 0; c < 3; ++c) dst[(size_t)q * 3 + c] = v[c];
     }
 }
 
+// src: the first pixel of the H x W image (or window); pix_stride channels per pixel, pitch_px pixels from one row to the next
 template <bool VEC, bool LB>
-__device__ __forceinline__ void preprocess_batch_modes(const unsigned char *__restrict__ src, const y3_image_desc &d, int mode,
-                                                       float *__restrict__ dst, int Hc, int Wc, LetterboxGeom g)
+__device__ __forceinline__ void preprocess_batch_modes(const unsigned char *__restrict__ src, int H, int W, int pix_stride, int pitch_px,
+                                                       int mode, float *__restrict__ dst, int Hc, int Wc, LetterboxGeom g)
 {
+    const size_t row_pitch = (size_t)pitch_px * pix_stride;
     if (mode == 2)
-        preprocess_batch_body<RawU8, VEC, LB>(reinterpret_cast<const RawU8 *>(src), d.height, d.width, d.channels, dst, Hc, Wc, g);
+        preprocess_batch_body<RawU8, VEC, LB>(reinterpret_cast<const RawU8 *>(src), H, W, pix_stride, row_pitch, dst, Hc, Wc, g);
     else if (mode == 1)
-        preprocess_batch_body<unsigned char, VEC, LB>(src, d.height, d.width, d.channels, dst, Hc, Wc, g);
+        preprocess_batch_body<unsigned char, VEC, LB>(src, H, W, pix_stride, row_pitch, dst, Hc, Wc, g);
     else
-        preprocess_batch_body<float, VEC, LB>(reinterpret_cast<const float *>(src), d.height, d.width, d.channels, dst, Hc, Wc, g);
+        preprocess_batch_body<float, VEC, LB>(reinterpret_cast<const float *>(src), H, W, pix_stride, row_pitch, dst, Hc, Wc, g);
 }
 
 template <bool VEC>
@@ -129,9 +134,27 @@ __global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned ch
     float *dst = batch + (size_t)blockIdx.y * Hc * Wc * 3;
     const int mode = d.mode & ~Y3_IMAGE_LETTERBOX;
     if (d.mode & Y3_IMAGE_LETTERBOX)                      // one branch per workgroup each, outside the pixel body
-        preprocess_batch_modes<VEC, true>(src, d, mode, dst, Hc, Wc, table.g[blockIdx.y]);
+        preprocess_batch_modes<VEC, true>(src, d.height, d.width, d.channels, d.width, mode, dst, Hc, Wc, table.g[blockIdx.y]);
     else
-        preprocess_batch_modes<VEC, false>(src, d, mode, dst, Hc, Wc, LetterboxGeom{});
+        preprocess_batch_modes<VEC, false>(src, d.height, d.width, d.channels, d.width, mode, dst, Hc, Wc, LetterboxGeom{});
+}
+
+// Windows of frames as images of their own (include/y3.h, y3_preprocess_tiles_hw): the kernel above with the source pointer moved to the
+// window's first pixel, the window's extent as the image's and the frame's width as the row pitch -- the pixel body is the same code, so a tile
+// has the bits preprocess_batch_kernel gives for a contiguous copy of the window.  Same launch shape: four pixels, three 16-byte stores.
+template <bool VEC>
+__global__ __launch_bounds__(256) void preprocess_tiles_kernel(const unsigned char *__restrict__ pixels, TileTable table,
+                                                               float *__restrict__ batch, int Hc, int Wc)
+{
+    const y3_tile_desc d = table.d[blockIdx.y];
+    const int mode = d.mode & ~Y3_IMAGE_LETTERBOX;
+    const size_t elem = mode == 0 ? sizeof(float) : 1;
+    const unsigned char *src = pixels + d.offset + ((size_t)d.y0 * d.width + d.x0) * d.channels * elem;
+    float *dst = batch + (size_t)blockIdx.y * Hc * Wc * 3;
+    if (d.mode & Y3_IMAGE_LETTERBOX)
+        preprocess_batch_modes<VEC, true>(src, d.ch, d.cw, d.channels, d.width, mode, dst, Hc, Wc, table.g[blockIdx.y]);
+    else
+        preprocess_batch_modes<VEC, false>(src, d.ch, d.cw, d.channels, d.width, mode, dst, Hc, Wc, LetterboxGeom{});
 }
 
 template <typename T>
@@ -177,6 +200,26 @@ hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *desc
         hipLaunchKernelGGL(preprocess_batch_kernel<true>, grid, block, 0, s, p, table, dst, Hc, Wc);
     else
         hipLaunchKernelGGL(preprocess_batch_kernel<false>, grid, block, 0, s, p, table, dst, Hc, Wc);
+    return hipGetLastError();
+}
+
+// descs / geoms: n (1..kTileTableTiles) validated tile descriptors and their geometries; dst: slot of the first tile
+hipError_t launch_preprocess_tiles(const void *pixels, const y3_tile_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
+                                   int Wc, hipStream_t s)
+{
+    TileTable table{};
+    for (int i = 0; i < n; ++i) {
+        table.d[i] = descs[i];
+        table.g[i] = geoms[i];
+    }
+    const bool vec = ((size_t)Hc * Wc) % 4 == 0 && ((uintptr_t)dst & 15) == 0;
+    const int per_block = vec ? 1024 : 256;
+    dim3 grid((unsigned)(((size_t)Hc * Wc + per_block - 1) / per_block), (unsigned)n), block(256);
+    const unsigned char *p = static_cast<const unsigned char *>(pixels);
+    if (vec)
+        hipLaunchKernelGGL(preprocess_tiles_kernel<true>, grid, block, 0, s, p, table, dst, Hc, Wc);
+    else
+        hipLaunchKernelGGL(preprocess_tiles_kernel<false>, grid, block, 0, s, p, table, dst, Hc, Wc);
     return hipGetLastError();
 }
 

@@ -303,6 +303,26 @@ static_assert(sizeof(y3_image_desc) == 24 && sizeof(PreprocessTable) + 64 <= 409
 hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
                                    int Wc, hipStream_t s);
 
+// The tile descriptors and geometries of one preprocess_tiles_kernel launch, by value like PreprocessTable: 56 bytes per tile, as many
+// as the 4 KB of kernel arguments hold beside the two pointers and the canvas.
+constexpr int kTileTableTiles = 72;
+struct TileTable { y3_tile_desc d[kTileTableTiles]; LetterboxGeom g[kTileTableTiles]; };
+static_assert(sizeof(y3_tile_desc) == 40 && sizeof(TileTable) + 64 <= 4096 && sizeof(TileTable) + 64 + 56 > 4096,
+              "tile table must fill the kernel arguments");
+hipError_t launch_preprocess_tiles(const void *pixels, const y3_tile_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
+                                   int Wc, hipStream_t s);
+
+// Sliced inference, the merge (tiles.hip; include/y3.h, y3_merge_tile_detections).  One entry per tile image: its window of the frame, its
+// letterbox geometry on the canvas and the frame's extent; 64 entries per merge_tiles_kernel launch, by value in the kernel arguments.
+constexpr int kMergeTableTiles = 64, kMergeMaxTiles = 64;
+struct MergeTile { int32_t y0, x0, ch, cw; LetterboxGeom g; int32_t h, w; };
+struct MergeTable { MergeTile t[kMergeTableTiles]; };
+static_assert(sizeof(MergeTile) == 40 && sizeof(MergeTable) + 64 <= 4096, "merge table must fit the kernel arguments");
+// packed / nv: the first tile image of the launch; boxes / scores / cls: its first candidate (image i of the launch owns candidates
+// [i * M, (i + 1) * M)); n: 1..kMergeTableTiles entries
+hipError_t launch_merge_tiles(const void *packed, const int32_t *nv, const MergeTile *entries, int n, int M, int Hc, int Wc, float *boxes,
+                              float *scores, int64_t *cls, hipStream_t s);
+
 // The geometries of one unletterbox_kernel launch, by value in the kernel arguments like PreprocessTable.
 constexpr int kUnletterboxTableImages = 64;
 struct UnletterboxTable { LetterboxGeom g[kUnletterboxTableImages]; };

@@ -240,6 +240,210 @@ try {
 }
 Y3_CATCH("y3_unletterbox_detections")
 
+// ------------------------------------------------------------------------------------------ sliced inference
+int y3_tile_grid(int height, int width, int rows, int cols, int overlap_px, int overview, int32_t *out)
+{
+    const char *who = "y3_tile_grid";
+    if (!out) return fail(Y3_ERR_INVALID, "%s: null pointer", who);
+    if (height < 1 || width < 1) return fail(Y3_ERR_INVALID, "%s: height and width must be at least 1 (got %d x %d)", who, height, width);
+    if (rows < 1 || rows > 8 || cols < 1 || cols > 8) return fail(Y3_ERR_INVALID, "%s: rows and cols must be in [1,8] (got %d x %d)", who, rows, cols);
+    if (overlap_px < 0 || overlap_px > std::min(height, width))
+        return fail(Y3_ERR_INVALID, "%s: overlap_px must be in [0, min(height, width)] (got %d for %d x %d)", who, overlap_px, height, width);
+    const int T = rows * cols + (overview ? 1 : 0);
+    if (T > y3::kMergeMaxTiles) return fail(Y3_ERR_INVALID, "%s: %d tiles, at most %d", who, T, y3::kMergeMaxTiles);
+    // one axis: the window length, then the origin of window i (64-bit products: e * k stays far below 2^63)
+    auto length = [&](int e, int k) { return (int)(((long long)e + (long long)(k - 1) * overlap_px + k - 1) / k); };
+    auto origin = [](int e, int len, int k, int i) { return k == 1 ? 0 : (int)((long long)i * (e - len) / (k - 1)); };
+    const int lh = length(height, rows), lw = length(width, cols);
+    for (int i = 0; i < rows; ++i)
+        for (int j = 0; j < cols; ++j) {
+            int32_t *o = out + ((size_t)i * cols + j) * 4;
+            o[0] = origin(height, lh, rows, i);
+            o[1] = origin(width, lw, cols, j);
+            o[2] = lh;
+            o[3] = lw;
+        }
+    if (overview) {
+        int32_t *o = out + (size_t)rows * cols * 4;
+        o[0] = 0, o[1] = 0, o[2] = height, o[3] = width;
+    }
+    return T;
+}
+
+// what y3_preprocess_tiles_hw and y3_tile_letterbox_geometry_hw check of a tile's window: it is an image of ch x cw inside height x width
+static y3_status tile_window_ok(const char *who, int i, const y3_tile_desc &d)
+{
+    if (!image_mode_ok(d.mode))
+        return fail(Y3_ERR_INVALID, "%s: tile %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
+    if (d.height < 1 || d.width < 1)
+        return fail(Y3_ERR_INVALID, "%s: tile %d: height and width must be at least 1 (got %d x %d)", who, i, d.height, d.width);
+    if (d.ch < 1 || d.cw < 1) return fail(Y3_ERR_INVALID, "%s: tile %d: ch and cw must be at least 1 (got %d x %d)", who, i, d.ch, d.cw);
+    if (d.y0 < 0 || d.x0 < 0 || d.y0 > d.height - d.ch || d.x0 > d.width - d.cw)
+        return fail(Y3_ERR_INVALID, "%s: tile %d: window %d x %d at (%d, %d) does not lie inside the %d x %d image", who, i, d.ch, d.cw,
+                    d.y0, d.x0, d.height, d.width);
+    return Y3_OK;
+}
+
+y3_status y3_preprocess_tiles_hw(const void *pixels_dev, size_t pixels_bytes, const y3_tile_desc *descs_host, int n_tiles,
+                                 float *batch_dev, int first_slot, int canvas_h, int canvas_w, void *stream)
+try {
+    const char *who = "y3_preprocess_tiles_hw";
+    const int Hc = canvas_h, Wc = canvas_w;
+    if (!pixels_dev || !descs_host || !batch_dev || n_tiles < 1 || first_slot < 0 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_tiles < 1, first_slot < 0 or canvas <= 0)", who);
+    // every check before the first launch, as in y3_preprocess_batch
+    for (int i = 0; i < n_tiles; ++i) {
+        const y3_tile_desc &d = descs_host[i];
+        if (d.channels < 3 || d.channels > 4)
+            return fail(Y3_ERR_INVALID, "%s: tile %d: channels must be 3 or 4 (got %d)", who, i, d.channels);
+        if (y3_status st = tile_window_ok(who, i, d); st != Y3_OK) return st;
+        const bool f32 = (d.mode & ~Y3_IMAGE_LETTERBOX) == 0;
+        if (f32 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
+            return fail(Y3_ERR_INVALID, "%s: tile %d: float32 pixels must be 4-byte aligned (offset %llu)", who, i,
+                        (unsigned long long)d.offset);
+        const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (f32 ? 4 : 1));
+        if ((unsigned __int128)d.offset + bytes > (unsigned __int128)pixels_bytes)
+            return fail(Y3_ERR_INVALID, "%s: tile %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", who, i,
+                        d.height, d.width, d.channels, (unsigned long long)d.offset, pixels_bytes);
+        const y3::LetterboxGeom g = image_geom(d.mode, d.ch, d.cw, Hc, Wc);
+        if (!y3::letterbox_geom_fits(g, Hc, Wc))
+            return fail(Y3_ERR_INVALID, "%s: tile %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, i,
+                        d.ch, d.cw, g.sh, g.sw, g.top, g.left, Hc, Wc);
+    }
+    const size_t per_image = (size_t)Hc * Wc * 3;
+    for (int i0 = 0; i0 < n_tiles; i0 += y3::kTileTableTiles) {
+        const int n = std::min(y3::kTileTableTiles, n_tiles - i0);
+        y3::LetterboxGeom geoms[y3::kTileTableTiles];     // on the stack: the call allocates nothing
+        for (int i = 0; i < n; ++i) geoms[i] = image_geom(descs_host[i0 + i].mode, descs_host[i0 + i].ch, descs_host[i0 + i].cw, Hc, Wc);
+        hipError_t e = y3::launch_preprocess_tiles(pixels_dev, descs_host + i0, geoms, n, batch_dev + ((size_t)first_slot + i0) * per_image,
+                                                   Hc, Wc, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    }
+    return Y3_OK;
+}
+Y3_CATCH("y3_preprocess_tiles_hw")
+
+y3_status y3_tile_letterbox_geometry_hw(const y3_tile_desc *descs_host, int n_tiles, int canvas_h, int canvas_w, int32_t *geoms_out_host)
+try {
+    const char *who = "y3_tile_letterbox_geometry_hw";
+    if (!descs_host || !geoms_out_host || n_tiles < 1 || canvas_h <= 0 || canvas_w <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_tiles < 1 or canvas <= 0)", who);
+    for (int i = 0; i < n_tiles; ++i)
+        if (y3_status st = tile_window_ok(who, i, descs_host[i]); st != Y3_OK) return st;
+    for (int i = 0; i < n_tiles; ++i) {
+        const y3::LetterboxGeom g = image_geom(descs_host[i].mode, descs_host[i].ch, descs_host[i].cw, canvas_h, canvas_w);
+        memcpy(geoms_out_host + (size_t)i * 4, &g, sizeof(g));
+    }
+    return Y3_OK;
+}
+Y3_CATCH("y3_tile_letterbox_geometry_hw")
+
+namespace {
+// The layout of y3_merge_tile_detections' workspace, every part 16-byte aligned: candidate boxes [F,N,4] f32, class ids [F,N] i64, scores
+// [F,N] f32, selected indices [F,M] i32, then the NMS workspace of (F, N) -- the per-class one, which serves either rule.  N = tiles * max_boxes.
+struct MergeLayout { size_t boxes, cls, scores, sel, nms, nms_bytes, total; };
+bool merge_sizes_ok(int frames, int tiles, int max_boxes)
+{
+    return frames >= 1 && tiles >= 1 && tiles <= y3::kMergeMaxTiles && max_boxes >= 1 && max_boxes <= Y3_MAX_OUTPUT_BOXES &&
+           (unsigned long long)frames * tiles * max_boxes <= 0x7fffffffull;
+}
+MergeLayout merge_layout(int frames, int tiles, int max_boxes)
+{
+    const size_t F = frames, N = (size_t)tiles * max_boxes, M = max_boxes;
+    auto up = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    MergeLayout l{};
+    l.boxes = 0;
+    l.cls = up(l.boxes + F * N * 4 * sizeof(float));
+    l.scores = up(l.cls + F * N * sizeof(int64_t));
+    l.sel = up(l.scores + F * N * sizeof(float));
+    l.nms = up(l.sel + F * M * sizeof(int32_t));
+    l.nms_bytes = y3::nms_per_class_workspace_bytes(frames, (int)N);
+    l.total = l.nms + l.nms_bytes;
+    return l;
+}
+}  // namespace
+
+size_t y3_merge_tiles_workspace_bytes(int frames, int tiles, int max_boxes)
+{
+    return merge_sizes_ok(frames, tiles, max_boxes) ? merge_layout(frames, tiles, max_boxes).total : 0;
+}
+
+y3_status y3_merge_tile_detections(const void *packed_dev, const int32_t *num_valid_dev, const int32_t *tiles_host,
+                                   const int32_t *geoms_host, const int32_t *frame_hw_host, int frames, int tiles, int max_boxes,
+                                   int canvas_h, int canvas_w, int nms_mode, float iou_threshold, float score_threshold,
+                                   void *packed_out_dev, int32_t *num_valid_out_dev, void *workspace_dev, size_t workspace_bytes,
+                                   void *stream)
+try {
+    const char *who = "y3_merge_tile_detections";
+    const int Hc = canvas_h, Wc = canvas_w;
+    if (!packed_dev || !num_valid_dev || !tiles_host || !geoms_host || !frame_hw_host || !packed_out_dev || !num_valid_out_dev)
+        return fail(Y3_ERR_INVALID, "%s: null pointer", who);
+    if (frames < 1) return fail(Y3_ERR_INVALID, "%s: frames must be at least 1 (got %d)", who, frames);
+    if (tiles < 1 || tiles > y3::kMergeMaxTiles) return fail(Y3_ERR_INVALID, "%s: tiles must be in [1,%d] (got %d)", who, y3::kMergeMaxTiles, tiles);
+    if (max_boxes < 1 || max_boxes > Y3_MAX_OUTPUT_BOXES)
+        return fail(Y3_ERR_INVALID, "%s: max_boxes must be in [1,%d] (got %d)", who, Y3_MAX_OUTPUT_BOXES, max_boxes);
+    if (!merge_sizes_ok(frames, tiles, max_boxes))
+        return fail(Y3_ERR_INVALID, "%s: frames * tiles * max_boxes must stay below 2^31 (got %d x %d x %d)", who, frames, tiles, max_boxes);
+    if (Hc <= 0 || Wc <= 0) return fail(Y3_ERR_INVALID, "%s: canvas must be at least 1 x 1 (got %d x %d)", who, Hc, Wc);
+    if (nms_mode != Y3_NMS_AGNOSTIC && nms_mode != Y3_NMS_PER_CLASS)
+        return fail(Y3_ERR_INVALID, "%s: nms_mode must be Y3_NMS_AGNOSTIC or Y3_NMS_PER_CLASS (got %d)", who, nms_mode);
+    // the threshold checks of the NMS call that follows, made here: nothing may be enqueued by a refused call
+    if (nms_mode == Y3_NMS_PER_CLASS && !(iou_threshold > 0.0f))
+        return fail(Y3_ERR_INVALID, "%s: iou_threshold must be > 0 with Y3_NMS_PER_CLASS", who);
+    if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
+        return fail(Y3_ERR_INVALID, "%s: iou_threshold <= 0 together with score_threshold < 0 is not supported", who);
+    for (int f = 0; f < frames; ++f) {
+        const int h = frame_hw_host[f * 2], w = frame_hw_host[f * 2 + 1];
+        if (h < 1 || w < 1) return fail(Y3_ERR_INVALID, "%s: frame %d: height and width must be at least 1 (got %d x %d)", who, f, h, w);
+        for (int t = 0; t < tiles; ++t) {
+            const int32_t *win = tiles_host + ((size_t)f * tiles + t) * 4;
+            if (win[2] < 1 || win[3] < 1 || win[0] < 0 || win[1] < 0 || win[0] > h - win[2] || win[1] > w - win[3])
+                return fail(Y3_ERR_INVALID, "%s: frame %d, tile %d: window %d x %d at (%d, %d) does not lie inside the %d x %d frame", who, f, t,
+                            win[2], win[3], win[0], win[1], h, w);
+            y3::LetterboxGeom g;
+            memcpy(&g, geoms_host + ((size_t)f * tiles + t) * 4, sizeof(g));
+            if (!y3::letterbox_geom_fits(g, Hc, Wc))
+                return fail(Y3_ERR_INVALID, "%s: frame %d, tile %d: geometry %d x %d at (%d, %d) does not lie inside %d x %d", who, f, t,
+                            g.sh, g.sw, g.top, g.left, Hc, Wc);
+        }
+    }
+    const MergeLayout l = merge_layout(frames, tiles, max_boxes);
+    if (!workspace_dev || workspace_bytes < l.total) return fail(Y3_ERR_INVALID, "%s: workspace too small (need %zu bytes)", who, l.total);
+    if (((uintptr_t)packed_dev & 3) || ((uintptr_t)packed_out_dev & 3) || ((uintptr_t)workspace_dev & 15))
+        return fail(Y3_ERR_INVALID, "%s: packed / packed_out not 4-byte or workspace not 16-byte aligned", who);
+    char *ws = static_cast<char *>(workspace_dev);
+    float *boxes = reinterpret_cast<float *>(ws + l.boxes), *scores = reinterpret_cast<float *>(ws + l.scores);
+    int64_t *cls = reinterpret_cast<int64_t *>(ws + l.cls);
+    int32_t *sel = reinterpret_cast<int32_t *>(ws + l.sel);
+    const int images = frames * tiles, N = tiles * max_boxes;
+    const unsigned *packed = static_cast<const unsigned *>(packed_dev);
+    for (int i0 = 0; i0 < images; i0 += y3::kMergeTableTiles) {
+        const int n = std::min(y3::kMergeTableTiles, images - i0);
+        y3::MergeTile entries[y3::kMergeTableTiles];
+        for (int i = 0; i < n; ++i) {
+            const int gi = i0 + i;
+            const int32_t *win = tiles_host + (size_t)gi * 4, *hw = frame_hw_host + (size_t)(gi / tiles) * 2;
+            y3::MergeTile &e = entries[i];
+            e.y0 = win[0], e.x0 = win[1], e.ch = win[2], e.cw = win[3];
+            memcpy(&e.g, geoms_host + (size_t)gi * 4, sizeof(e.g));
+            e.h = hw[0], e.w = hw[1];
+        }
+        const size_t c0 = (size_t)i0 * max_boxes;      // first candidate of the launch
+        hipError_t e = y3::launch_merge_tiles(packed + c0 * 7, num_valid_dev + i0, entries, n, max_boxes, Hc, Wc, boxes + c0 * 4, scores + c0,
+                                              cls + c0, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    }
+    // the existing NMS and pack, through their own entry points: their checks were made above, so neither can refuse what follows a launch
+    y3_status st = nms_mode == Y3_NMS_PER_CLASS
+        ? y3_nms_padded_per_class(boxes, scores, cls, frames, N, max_boxes, iou_threshold, score_threshold, sel, num_valid_out_dev,
+                                  ws + l.nms, l.nms_bytes, stream)
+        : y3_nms_padded(boxes, scores, frames, N, max_boxes, iou_threshold, score_threshold, sel, num_valid_out_dev, ws + l.nms,
+                        l.nms_bytes, stream);
+    if (st != Y3_OK) return st;
+    return y3_pack_detections(boxes, cls, scores, sel, num_valid_out_dev, frames, N, max_boxes, packed_out_dev, stream);
+}
+Y3_CATCH("y3_merge_tile_detections")
+
 y3_status y3_evaluate_detections(const void *packed_dev, const int32_t *num_valid_dev, int batch, int max_boxes,
                                  const float *gt_boxes_dev, const int32_t *gt_classes_dev, const int32_t *gt_count_dev, int max_gt,
                                  int nclasses, float iou_threshold, const float *score_thresholds_host, int n_thresholds,

@@ -96,7 +96,7 @@ def report_ap(ap, iou_thresholds):
 
 
 def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_batches, weights, one_class, anchors_table, nclasses,
-                        loss=False, ap=None, nms_per_class=False):
+                        loss=False, ap=None, nms_per_class=False, tiles=None):
     """One model and one pass: the un-stacked data set is batched here (images with unlike numbers of boxes may share a batch)
     by a generator that Net.evaluate_stream draws from, so records are decoded while earlier batches run and the data set is
     never held in memory; only the counters come back."""
@@ -111,6 +111,7 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     model.model.set_dtype(detect_config.get("dtype"))     # optional key: f32 | bf16 | f16 | i8; absent: f32
     model.model.set_stem_fusion_f16(detect_config.get("f16_fused_stem"))   # optional key, acts on dtype f16 only; absent: off
     model.model.set_nms_per_class(nms_per_class)          # the device net's detect, and the composed route of loss=True, follow it
+    model.model.set_tiles(*(tiles or (None,)))            # sliced inference: the device net's streams follow it
     net = model.model._device_net()
     if net.image_size != S or net.max_batch < batch_size:
         net.plan(max(batch_size, net.max_batch), S)
@@ -167,7 +168,7 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
 
 
 def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshold=0.5, max_batches=20, weights=None,
-             one_class=True, on_device=False, loss=False, ap=None, nms_per_class=False):
+             one_class=True, on_device=False, loss=False, ap=None, nms_per_class=False, tiles=None):
     """The loop of reference evaluate_yolov3.py:153-232: for every score threshold build the detect model, run the
     first `max_batches` dataset batches (`dataset.take(20)` there), count, and report (recall, precision).
     Returns [(threshold, recall, precision, counters, counters_oneclass)].
@@ -189,7 +190,18 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     nms_per_class=True, or an optional `nms_per_class: true` key of detect_config (absent: off), on either route: per-class NMS
     (Net.nms_per_class; no reference counterpart) -- a box is suppressed only by a kept box of its own class, the rule published
     YOLOv3 mAP figures are taken under.  The one-pass argument of on_device=True holds as it stands: a box is never affected by a
-    box scored below it under either rule."""
+    box scored below it under either rule.
+    tiles=(rows, cols, overlap_px, overview) (with on_device=True), or the optional keys `tiles: [rows, cols]`, `tile_overlap`,
+    `tile_overview` of detect_config: sliced inference (Net.evaluate_stream, tiles=) -- every record, resized to image_size on the host as
+    before, is cut into windows on the device, each window is detected at image_size and the windows' detections are merged by a second
+    NMS; the counters and the AP are taken on the merged rows.  One pass still serves every threshold ("Sliced inference").
+    Not together with loss=True."""
+    from .inference import Inference
+    tiles = tiles or Inference.tiles_from_config(detect_config)
+    if tiles is not None and not on_device:
+        raise ValueError("evaluate: tiles need on_device=True (the windows are cut and merged on the GPU, in the device pass)")
+    if tiles is not None and loss:
+        raise ValueError("evaluate: loss=True cannot be combined with tiles")
     if loss and not on_device:
         raise ValueError("evaluate: loss=True needs on_device=True (the loss is computed on the GPU, from the device pass)")
     ap = None if ap is False else ap
@@ -201,7 +213,7 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     nms_per_class = bool(nms_per_class or detect_config.get("nms_per_class"))
     if on_device:
         return _evaluate_on_device(detect_config, list(evaluate_nms_score_thresholds), evaluate_iou_threshold, max_batches, weights,
-                                   one_class, anchors_table, nclasses, loss=loss, ap=ap, nms_per_class=nms_per_class)
+                                   one_class, anchors_table, nclasses, loss=loss, ap=ap, nms_per_class=nms_per_class, tiles=tiles)
     dataset = prepare_dataset(detect_config["tfrecords_dir"], detect_config["batch_size"], detect_config["image_size"],
                               detect_config["yolo_max_boxes"], detect_config["classes_name_file"])
     results = []
@@ -244,6 +256,11 @@ def _arg_parser():
     ap.add_argument("--nms-per-class", action="store_true",
                     help="per-class NMS: a box is suppressed only by a kept box of its own class (also the optional nms_per_class "
                          "key of either config; absent: the reference's class-agnostic rule)")
+    ap.add_argument("--tiles", type=int, nargs=2, metavar=("R", "C"),
+                    help="with --on-device: sliced inference, every frame cut into R x C overlapping windows that are detected at full "
+                         "resolution and merged on the GPU (also the optional tiles / tile_overlap / tile_overview keys of the detect config)")
+    ap.add_argument("--tile-overlap", type=int, default=0, metavar="P", help="with --tiles: neighbouring windows overlap by at least P pixels")
+    ap.add_argument("--tile-overview", action="store_true", help="with --tiles: the whole frame as one more tile")
     return ap
 
 
@@ -254,6 +271,12 @@ def main(argv=None):
         ap.error("--loss needs --on-device")
     if a.ap and not a.on_device:
         ap.error("--ap needs --on-device")
+    if a.tiles and not a.on_device:
+        ap.error("--tiles needs --on-device")
+    if (a.tile_overlap or a.tile_overview) and not a.tiles:
+        ap.error("--tile-overlap / --tile-overview need --tiles")
+    if a.tiles and a.loss:
+        ap.error("--tiles cannot be combined with --loss")
     with open(a.evaluate_config) as s:
         evaluate_config = yaml.safe_load(s)
     thresholds = evaluate_config["evaluate_nms_score_thresholds"]
@@ -261,7 +284,8 @@ def main(argv=None):
     with open(a.config) as s:
         detect_config = yaml.safe_load(s)
     results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss, ap=ap_thresholds,
-                       nms_per_class=a.nms_per_class or bool(evaluate_config.get("nms_per_class")))
+                       nms_per_class=a.nms_per_class or bool(evaluate_config.get("nms_per_class")),
+                       tiles=(a.tiles[0], a.tiles[1], a.tile_overlap, a.tile_overview) if a.tiles else None)
     if a.loss or a.ap:
         results = results[0]      # the loss and the AP have been printed by evaluate
     print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in results])

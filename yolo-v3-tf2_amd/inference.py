@@ -66,6 +66,35 @@ class Inference:
     # Per-class NMS (core.parse_model.YoloModel.set_nms_per_class; None or False: the reference's class-agnostic rule).  The optional YAML
     # key `nms_per_class` lands here the same way.
     nms_per_class = None
+    # Sliced inference (core.parse_model.YoloModel.set_tiles; None: off): (rows, cols, overlap_px, overview).  The optional YAML keys
+    # `tiles: [rows, cols]`, `tile_overlap: <pixels>` and `tile_overview: true|false` land here the same way (tiles_from_config).
+    tiles = None
+
+    @staticmethod
+    def tiles_from_config(config, pop=False):
+        """The optional keys tiles / tile_overlap / tile_overview of a config dict -> (rows, cols, overlap_px, overview), or None when
+        `tiles` is absent.  pop: take the three keys out of the dict."""
+        get = config.pop if pop else config.get
+        grid, overlap, overview = get("tiles", None), get("tile_overlap", None), get("tile_overview", None)
+        if grid is None:
+            if overlap is not None or overview is not None:
+                raise ValueError("tile_overlap / tile_overview need `tiles: [rows, cols]`")
+            return None
+        if len(grid) != 2:
+            raise ValueError(f"tiles must be [rows, cols] (got {grid!r})")
+        return int(grid[0]), int(grid[1]), int(overlap or 0), bool(overview)
+
+    def _detect_tiled(self, model, frames, mode):
+        """Sliced inference of one batch of host frames (uint8 [H,W,3|4]) through the device net's detect_stream -> per frame
+        (bboxes [n,4], classes [n], scores [n]), the boxes normalised to the frame."""
+        net = model.model._device_net()
+        (packed, nv), = net.detect_stream([frames], model.anchors_table, model.yolo_max_boxes, model.nms_iou_threshold,
+                                          model.nms_score_threshold, mode=mode)      # the net's `tiles` property is the model's
+        out = []
+        for rows, n in zip(packed, nv):
+            rows = rows[:int(n)]
+            out.append((rows[:, :4].copy().view(np.float32), rows[:, 5].astype(np.int64), rows[:, 4].copy().view(np.float32)))
+        return out
 
     @staticmethod
     def gather_valid_detections_results(bboxes_padded, class_indices_padded, scores_padded, selected_indices_padded,
@@ -140,6 +169,7 @@ class Inference:
         model.set_dtype(dtype)
         model.set_stem_fusion_f16(self.f16_fused_stem if f16_fused_stem is None else f16_fused_stem)
         model.set_nms_per_class(self.nms_per_class)
+        model.set_tiles(*(self.tiles or (None,)))
         print("weights loaded")
         return DetectModel(model, anchors_table, nclasses, yolo_max_boxes, nms_iou_threshold,
                            nms_score_threshold), class_names
@@ -163,6 +193,11 @@ class Inference:
         import torch
         from . import runtime
         (canvas_h, canvas_w), model.anchors_table = self.canvas_and_anchors(image_size, model.anchors_table)
+        tiled = model.model.tiles is not None
+        if tiled:       # sliced inference: the frames go to the device whole, the windows are cut, detected and merged there
+            net = model.model._device_net()
+            if net.canvas != (canvas_h, canvas_w):
+                net.plan(max(net.max_batch, 1), (canvas_h, canvas_w) if canvas_h != canvas_w else canvas_h)
         if input_data_source == "tfrecords":
             # reference: inference.py:119-144.  Records are parsed on the host (core/load_tfrecords.py); the
             # resize(0..255 values) / 255 of parse_tfrecord_fn runs on the GPU straight into the batch tensor.  The
@@ -173,6 +208,15 @@ class Inference:
 
             def run_batch(images_u8):
                 nonlocal image_index
+                if tiled:       # boxes in frame coordinates: drawn on the frame itself
+                    for img, (bboxes, classes, scores) in zip(images_u8, self._detect_tiled(model, images_u8, 2)):
+                        classes_names = [class_names[idx] for idx in classes]
+                        annotated, detections = self.annotate(img[..., :3].astype(np.float32) / 255.0, bboxes, classes_names, scores, font_size)
+                        self._dump_detections_text(detections, out)
+                        annotated.save(f"{output_dir}/detect_{image_index}.jpg")
+                        results.append((bboxes, classes, scores, classes_names))
+                        image_index += 1
+                    return
                 batch_dev = torch.empty((len(images_u8), canvas_h, canvas_w, 3), dtype=torch.float32,
                                         device="cuda")
                 # one copy and one launch for the batch (mode 2: resize the 0..255 values, then / 255)
@@ -206,6 +250,14 @@ class Inference:
             # decode on the host, then uint8 -> [0,1] -> bilinear resize on the GPU straight into the batch tensor
             # (reference: inference.py:157-158 decode_image + tf.image.resize)
             orig_image = load_image_u8(file)
+            if tiled:
+                (bboxes, classes, scores), = self._detect_tiled(model, [orig_image], 1)
+                classes_names = [class_names[idx] for idx in classes]
+                annotated, detections = self.annotate(orig_image.astype(np.float32) / 255.0, bboxes, classes_names, scores, font_size)
+                self._dump_detections_text(detections, out)
+                annotated.save(f"{output_dir}/detect_{image_index}.jpg")
+                results.append((bboxes, classes, scores, classes_names))
+                continue
             batch_dev = torch.empty((1, canvas_h, canvas_w, 3), dtype=torch.float32, device="cuda")
             runtime.preprocess_image(torch.from_numpy(orig_image).cuda(), batch_dev, 0)
             b_boxes, b_cls, b_scores, b_sel, b_nv = (t.cpu().numpy() for t in model(batch_dev))
@@ -236,6 +288,7 @@ def main(argv=None):
     inference = Inference()
     inference.f16_fused_stem = detect_config.pop("f16_fused_stem", None)    # optional key, absent: off
     inference.nms_per_class = detect_config.pop("nms_per_class", None)      # optional key, absent: off
+    inference.tiles = Inference.tiles_from_config(detect_config, pop=True)  # optional keys tiles / tile_overlap / tile_overview, absent: off
     inference(**detect_config)
 
 

@@ -211,13 +211,106 @@ def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Ten
     return batch
 
 
+# y3_tile_desc (include/y3.h): a window (y0, x0, ch, cw) of an image of a pixel blob; what tile_descs returns and preprocess_tiles takes
+TILE_DESC_DTYPE = np.dtype([("offset", "<u8"), ("height", "<i4"), ("width", "<i4"), ("channels", "<i4"), ("mode", "<i4"),
+                            ("y0", "<i4"), ("x0", "<i4"), ("ch", "<i4"), ("cw", "<i4")])
+
+
+def tile_grid(height, width, rows, cols, overlap_px=0, overview=False) -> np.ndarray:
+    """y3_tile_grid: the windows of a height x width frame, int32 [T,4] = (y0, x0, ch, cw), row-major, the overview tile (the
+    whole frame) last; Y3Error for what the library refuses.  One host call, no GPU.  NumPy restatement: tiles.tile_grid."""
+    out = np.empty((_lib.MAX_TILES + 1, 4), np.int32)
+    T = _lib.load().y3_tile_grid(int(height), int(width), int(rows), int(cols), int(overlap_px), int(bool(overview)),
+                                 out.ctypes.data_as(C.POINTER(C.c_int32)))
+    if T < 0:       # the status; the count otherwise
+        check(T, "y3_tile_grid")
+    return out[:T].copy()
+
+
+def tile_descs(images, descs, rows, cols, overlap_px=0, overview=False):
+    """The descriptor array of pack_images -> (tile descriptors [n*T] (TILE_DESC_DTYPE), windows int32 [n*T,4]): the grid of
+    y3_tile_grid over every image, tile t of image i at index i * T + t.  A tile names its image's pixels in the blob, which
+    therefore holds -- and uploads -- every frame once.  images: the list the descriptors were packed from (only its length is
+    checked), or None."""
+    d, _ = _descs_arg(descs)
+    if images is not None and len(images) != len(d):
+        raise Y3Error(f"tile_descs: {len(images)} images, {len(d)} descriptors")
+    T = int(rows) * int(cols) + (1 if overview else 0)
+    out = np.zeros(len(d) * T, TILE_DESC_DTYPE)
+    windows = np.empty((len(d) * T, 4), np.int32)
+    grids = {}      # one library call per distinct frame shape
+    for i, im in enumerate(d):
+        hw = (int(im["height"]), int(im["width"]))
+        if hw not in grids:
+            grids[hw] = tile_grid(*hw, rows, cols, overlap_px, overview)
+        windows[i * T:(i + 1) * T] = grids[hw]
+        for name in ("offset", "height", "width", "channels", "mode"):
+            out[name][i * T:(i + 1) * T] = im[name]
+    for k, name in enumerate(("y0", "x0", "ch", "cw")):
+        out[name] = windows[:, k]
+    return out, windows
+
+
+def _tile_descs_arg(descs):
+    if not isinstance(descs, np.ndarray) or descs.dtype != TILE_DESC_DTYPE or descs.ndim != 1:
+        raise Y3Error("descs must be the tile descriptor array of tile_descs")
+    d = np.ascontiguousarray(descs)
+    return d, d.ctypes.data_as(C.POINTER(_lib.TileDesc))
+
+
+def tile_letterbox_geometries(descs: np.ndarray, image_size) -> np.ndarray:
+    """letterbox_geometries for tile descriptors: int32 [n,4] (sh, sw, top, left) of each window taken as a ch x cw image
+    (y3_tile_letterbox_geometry_hw); the rows merge_tile_detections takes."""
+    d, d_ptr = _tile_descs_arg(descs)
+    geoms = np.empty((len(d), 4), np.int32)
+    Hc, Wc = canvas_hw(image_size)
+    check(_lib.load().y3_tile_letterbox_geometry_hw(d_ptr, len(d), Hc, Wc, geoms.ctypes.data_as(C.POINTER(C.c_int32))),
+          "y3_tile_letterbox_geometry")
+    return geoms
+
+
+def preprocess_tiles(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Tensor, first_slot: int = 0):
+    """preprocess_batch for windows: the pixel blob of pack_images on the GPU and the tile descriptors of tile_descs ->
+    batch[first_slot + i] for tile i, one launch per 72 tiles (y3_preprocess_tiles_hw); every slot has the bits preprocess_batch
+    gives for a contiguous copy of the window."""
+    _need_cuda(blob_dev, batch)
+    if blob_dev.dtype != torch.uint8 or blob_dev.dim() != 1:
+        raise Y3Error("blob_dev must be a 1-D uint8 tensor")
+    d, d_ptr = _tile_descs_arg(descs)
+    if batch.dtype != torch.float32 or batch.dim() != 4 or batch.shape[3] != 3:
+        raise Y3Error("batch must be float32 [B,Hc,Wc,3]")
+    if not (0 <= first_slot and first_slot + len(descs) <= batch.shape[0]):
+        raise Y3Error(f"slots {first_slot}..{first_slot + len(descs) - 1} are outside the batch of {batch.shape[0]}")
+    check(_lib.load().y3_preprocess_tiles_hw(_dev(blob_dev), blob_dev.numel(), d_ptr, len(d), _dev(batch), int(first_slot),
+                                             batch.shape[1], batch.shape[2], _lib.stream_ptr()), "y3_preprocess_tiles")
+    return batch
+
+
 class StagedBatch:
     """What InputStage.submit returns: `batch` ([n,S,S,3] fp32 on the GPU) holds the images once a stream has waited on
     the event `ready`; hand it back with InputStage.release when the consumer's work on it is enqueued.  `geometry`
-    (int32 [n,4] on the host: sh, sw, top, left) says where each frame lies in its slot."""
+    (int32 [n,4] on the host: sh, sw, top, left) says where each frame lies in its slot.  `frames`: how many frames were handed in, n."""
 
     def __init__(self, slot, batch, ready, geometry):
         self.slot, self.batch, self.ready, self.geometry = slot, batch, ready, geometry
+
+    @property
+    def frames(self) -> int:
+        return self.batch.shape[0]
+
+
+class StagedTiles(StagedBatch):
+    """What TiledInputStage.submit returns: the batch holds frames * T tile images, tile t of frame f in slot f * T + t; `geometry` is
+    per tile, `windows` (int32 [frames*T,4]: y0, x0, ch, cw) and `frame_hw` (int32 [frames,2]) are the other two tables
+    merge_tile_detections takes, and `frames` counts the frames."""
+
+    def __init__(self, slot, batch, ready, geometry, windows, frame_hw):
+        super().__init__(slot, batch, ready, geometry)
+        self.windows, self.frame_hw = windows, frame_hw
+
+    @property
+    def frames(self) -> int:
+        return len(self.frame_hw)
 
 
 class _StageSlot:
@@ -239,6 +332,8 @@ class InputStage:
     Every wait is on an event: the host waits for `ready` of the slot's previous use before it overwrites the pinned
     blob, the copy stream waits for `released` before it overwrites the device buffers.  Nothing synchronises the device."""
 
+    tiles_per_image = 1     # images a frame becomes in the device batch; TiledInputStage sets its T before the slots are made
+
     def __init__(self, image_size, max_batch: int, max_blob_bytes: int, depth: int = 2):
         _lib.require_gpu()      # image_size: an int S or an (H, W) canvas
         if min(canvas_hw(image_size)) < 1 or max_batch < 1 or max_blob_bytes < 1 or depth < 1:
@@ -247,13 +342,19 @@ class InputStage:
         self.max_batch, self.depth = int(max_batch), int(depth)
         self.device = torch.device("cuda", torch.cuda.current_device())
         self.stream = torch.cuda.Stream(self.device)
-        self.slots = [_StageSlot(self.image_size, self.max_batch, int(max_blob_bytes), self.device) for _ in range(self.depth)]
+        self.slots = [_StageSlot(self.image_size, self.max_batch * self.tiles_per_image, int(max_blob_bytes), self.device)
+                      for _ in range(self.depth)]
         for s in self.slots:     # used on the copy stream for as long as the stage lives
             s.blob_dev.record_stream(self.stream)
             s.batch.record_stream(self.stream)
         self._next = 0
 
     def submit(self, images, mode, letterbox=False) -> StagedBatch:
+        return self._submit(images, mode, letterbox, None)
+
+    def _submit(self, images, mode, letterbox, tiles):
+        """submit; tiles: None, or TiledInputStage's (rows, cols, overlap_px, overview) -- the frames are packed and uploaded in the
+        same way, and the resize reads them window by window."""
         images = list(images)
         if not 1 <= len(images) <= self.max_batch:
             raise Y3Error(f"InputStage.submit: {len(images)} images, the stage holds 1..{self.max_batch}")
@@ -263,17 +364,28 @@ class InputStage:
         if slot.state == "released":
             slot.ready.synchronize()     # the slot's earlier copy has left the pinned blob
         blob, descs = pack_images(images, mode, out=slot.pinned_np, letterbox=letterbox)
-        geometry = letterbox_geometries(descs, self.image_size)     # one host call per batch
+        windows = frame_hw = None
+        if tiles is None:
+            geometry = letterbox_geometries(descs, self.image_size)     # one host call per batch
+        else:       # the frames are packed and uploaded once, exactly as above; only the resize reads them window by window
+            tdescs, windows = tile_descs(images, descs, *tiles)
+            geometry = tile_letterbox_geometries(tdescs, self.image_size)
+            frame_hw = np.stack([descs["height"], descs["width"]], axis=1).astype(np.int32)
         n = blob.size
         with torch.cuda.stream(self.stream):
             if slot.state == "released":
                 self.stream.wait_event(slot.released)
             slot.blob_dev[:n].copy_(slot.pinned[:n], non_blocking=True)
-            preprocess_batch(slot.blob_dev, descs, slot.batch, 0)
+            if tiles is None:
+                preprocess_batch(slot.blob_dev, descs, slot.batch, 0)
+            else:
+                preprocess_tiles(slot.blob_dev, tdescs, slot.batch, 0)
             slot.ready.record(self.stream)
         slot.state = "held"
         self._next = (self._next + 1) % self.depth
-        return StagedBatch(slot, slot.batch[:len(images)], slot.ready, geometry)
+        if tiles is None:
+            return StagedBatch(slot, slot.batch[:len(images)], slot.ready, geometry)
+        return StagedTiles(slot, slot.batch[:len(geometry)], slot.ready, geometry, windows, frame_hw)
 
     def release(self, handle: StagedBatch):
         """Call on the consumer's stream after its last use of handle.batch has been enqueued."""
@@ -281,3 +393,31 @@ class InputStage:
             raise Y3Error("InputStage.release: not a batch in flight")
         handle.slot.released.record(torch.cuda.current_stream())
         handle.slot.state = "released"
+
+
+def tiles_arg(who, tiles):
+    """(rows, cols, overlap_px, overview) as the streams and TiledInputStage take it -> the tuple in its types, and T, the tile images per
+    frame; Y3Error for what no frame could be cut by (y3_tile_grid refuses the rest per frame: an overlap larger than the frame)."""
+    try:
+        rows, cols, overlap_px, overview = tiles
+        t = (int(rows), int(cols), int(overlap_px), bool(overview))
+    except (TypeError, ValueError):
+        raise Y3Error(f"{who}: tiles must be (rows, cols, overlap_px, overview) (got {tiles!r})") from None
+    T = t[0] * t[1] + (1 if t[3] else 0)
+    if not (1 <= t[0] <= 8 and 1 <= t[1] <= 8 and t[2] >= 0 and T <= _lib.MAX_TILES):
+        raise Y3Error(f"{who}: tiles: rows and cols in [1,8], overlap_px >= 0, at most {_lib.MAX_TILES} tiles per frame (got {t!r})")
+    return t, T
+
+
+class TiledInputStage(InputStage):
+    """InputStage for sliced inference: tiles = (rows, cols, overlap_px, overview), T = rows * cols + overview tile images per frame.
+    The device batches hold max_batch * T images; submit packs and uploads the frames ONCE, exactly as InputStage does, and
+    y3_preprocess_tiles_hw cuts every frame's windows (y3_tile_grid) out of that one upload, each window stretched -- or with
+    letterbox=True letterboxed -- onto the canvas as an image of its own.  The handle is a StagedTiles."""
+
+    def __init__(self, image_size, max_batch: int, max_blob_bytes: int, tiles, depth: int = 2):
+        self.tiles, self.tiles_per_image = tiles_arg("TiledInputStage", tiles)
+        super().__init__(image_size, max_batch, max_blob_bytes, depth)
+
+    def submit(self, images, mode, letterbox=False) -> StagedTiles:
+        return self._submit(images, mode, letterbox, self.tiles)

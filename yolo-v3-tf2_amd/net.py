@@ -75,6 +75,7 @@ class Net:
         check(self.lib.y3_net_create(tens, len(p.tensors), k_arr, len(kinds), c_arr, len(convs), a_arr, len(auxs),
                                      p.input_tensor, outs, p.nclasses, C.byref(self._h)), "y3_net_create")
         self.image_size = 0
+        self._tiles, self._merge_iou_threshold = None, None      # the properties tiles / merge_iou_threshold
         self.canvas = (0, 0)     # the planned (H, W); image_size is the int S for a plan made with an int
         self.max_batch = 0
         self.dtype = _lib.Y3_DTYPE_F32
@@ -140,6 +141,30 @@ class Net:
         if not isinstance(on, (bool, np.bool_)):
             raise TypeError(f"nms_per_class: a bool (got {on!r})")
         check(self.lib.y3_net_set_nms_mode(self._h, _lib.Y3_NMS_PER_CLASS if on else _lib.Y3_NMS_AGNOSTIC), "y3_net_set_nms_mode")
+
+    @property
+    def tiles(self):
+        """Sliced inference in detect_stream / evaluate_stream: None (off, the default) or (rows, cols, overlap_px, overview) -- every frame
+        is cut into rows x cols windows overlapping by at least overlap_px pixels (y3_tile_grid), plus the whole frame with overview; each
+        window runs through the network as an image of its own and y3_merge_tile_detections merges the windows' detections per frame.
+        Read when a stream starts.  No reference counterpart."""
+        return self._tiles
+
+    @tiles.setter
+    def tiles(self, tiles):
+        from .input_stage import tiles_arg
+        self._tiles = None if tiles is None else tiles_arg("Net.tiles", tiles)[0]
+
+    @property
+    def merge_iou_threshold(self):
+        """The IoU threshold of the merge NMS of sliced inference; None (the default): the stream's iou_threshold."""
+        return self._merge_iou_threshold
+
+    @merge_iou_threshold.setter
+    def merge_iou_threshold(self, t):
+        if t is not None and not isinstance(t, (int, float, np.floating)):
+            raise TypeError(f"merge_iou_threshold: a number or None (got {t!r})")
+        self._merge_iou_threshold = None if t is None else float(t)
 
     @staticmethod
     def _dtype_arg(dtype) -> int:
@@ -550,9 +575,18 @@ class Net:
         y3_unletterbox_detections runs behind y3_net_detect on the same stream, before the read-back.
         The net keeps its planned image size -- an (H, W) plan letterboxes (or stretches) onto that canvas, and the yielded
         boxes are in source-frame coordinates all the same; the anchors are then the caller's rect_anchors -- and is re-planned at most once, for max_batch images; the stage's blobs hold
-        max_blob_bytes.  Both default to the largest list of `batches`, which must then be a list or tuple."""
+        max_blob_bytes.  Both default to the largest list of `batches`, which must then be a list or tuple.
+        With the property `tiles` set to (rows, cols, overlap_px, overview): sliced inference for frames much larger than the canvas
+        (a property like nms_per_class, so that the signature stays what it is; `merge_iou_threshold` beside it).  Every frame, uploaded
+        once, is cut on the device into rows x cols overlapping windows (y3_tile_grid) plus, with overview, the whole frame; each
+        window is stretched -- or with letterbox=True letterboxed -- onto the canvas as an image of its own
+        (y3_preprocess_tiles_hw); y3_net_detect runs on the max_batch * T tile images the net is planned for; and
+        y3_merge_tile_detections, in the place of y3_unletterbox_detections, maps the tiles' rows to the frame and runs the padded
+        NMS over their union at merge_iou_threshold (default: iou_threshold), in the net's NMS mode.  The yielded rows are per
+        FRAME, normalised to the frame, with the shapes described above; the index word of a row is t * max_boxes + r, its tile
+        and its row there.  tiles = None, the default, enqueues exactly what it did before the property existed."""
         return stream.detect_stream(self, batches, anchors, max_boxes, iou_threshold, score_threshold, mode, depth, max_batch,
-                                    max_blob_bytes, letterbox)
+                                    max_blob_bytes, letterbox, self.tiles, self.merge_iou_threshold)
 
     def evaluate_stream(self, batches, gts, anchors, max_boxes: int, iou_threshold: float, score_thresholds, nclasses: int,
                         evaluate_iou_threshold: float = 0.5, one_class=False, mode=1, depth: int = 2,
@@ -595,10 +629,15 @@ class Net:
         as 0; with one_class="both" AP follows the plain variant.  AP has no reference counterpart: the matching rule (greedy
         in score order, a ground-truth box matched at most once per IoU threshold; no crowd flags, no area ranges, max_boxes
         as the per-image cap) is this project's statement of the COCO matching and is not checked against pycocotools.
-        ap=None enqueues nothing new and returns exactly what is described above."""
+        ap=None enqueues nothing new and returns exactly what is described above.
+        With the properties `tiles` / `merge_iou_threshold` set: sliced inference as in detect_stream, in the same loop: the counters and the AP are taken on
+        the merged per-frame rows, against ground truth in frame coordinates.  The one detect pass still serves every score
+        threshold: both stages are greedy rules in which no box is affected by a lower-scored one, and the per-tile cap keeps a
+        prefix, so the merged rows at a higher threshold are the rows with score > threshold of the merged rows at the lowest
+        ("Sliced inference").  Not together with loss=True."""
         return stream.evaluate_stream(self, batches, gts, anchors, max_boxes, iou_threshold, score_thresholds, nclasses,
                                       evaluate_iou_threshold, one_class, mode, depth, max_batch, max_blob_bytes, letterbox,
-                                      max_gt, loss, ap)
+                                      max_gt, loss, ap, self.tiles, self.merge_iou_threshold)
 
     def flops_per_image(self) -> float:
         return float(self.lib.y3_net_flops_per_image(self._h))

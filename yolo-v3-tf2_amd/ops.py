@@ -341,6 +341,56 @@ def _pack(bboxes, cls, scores, sel, nv, out=None):
     return out
 
 
+def merge_tiles_workspace_bytes(frames: int, tiles: int, max_boxes: int) -> int:
+    """y3_merge_tiles_workspace_bytes: the workspace merge_tile_detections needs (either NMS rule); 0 for sizes it refuses."""
+    return int(_lib.load().y3_merge_tiles_workspace_bytes(int(frames), int(tiles), int(max_boxes)))
+
+
+def merge_tile_detections(packed: torch.Tensor, num_valid: torch.Tensor, windows, geoms, frame_hw, image_size,
+                          iou_threshold: float, score_threshold: float, per_class: bool = False, out=None,
+                          ws: Optional[torch.Tensor] = None, lib=None):
+    """Sliced inference, the merge (y3_merge_tile_detections; host restatement: tiles.merge_tile_detections_ref).  packed
+    [F*T,M,7] int32 words and num_valid [F*T] int32 on the GPU as Net.detect leaves them on the tile batch (tile t of frame f is
+    image f * T + t; the boxes normalised to the canvas, NOT un-letterboxed); on the host windows int32 [F*T,4] = (y0, x0, ch,
+    cw) (tile_descs), geoms int32 [F*T,4] (tile_letterbox_geometries) and frame_hw int32 [F,2] -> (packed [F,M,7], num_valid
+    [F]) per FRAME, in frame coordinates: the tiles' rows mapped to the frame (merge_tiles_kernel), then the existing padded NMS
+    over their union (per class with per_class=True) at iou_threshold / score_threshold with max_output_size M, then the
+    existing pack.  The index word of a merged row is t * M + r.  image_size: the canvas, an int S or an (H, W) pair.
+    out: the (packed, num_valid) tensors to write; ws: a uint8 workspace of merge_tiles_workspace_bytes(F, T, M) (one is made
+    otherwise); lib: the library handle to call through.  Enqueues on the current stream only."""
+    _need_cuda(packed, num_valid, ws)
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != 7:
+        raise Y3Error("packed must be contiguous int32 [F*T,M,7]")
+    fh = np.ascontiguousarray(frame_hw, dtype=np.int32)
+    if fh.ndim != 2 or fh.shape[1] != 2 or len(fh) < 1 or packed.shape[0] % len(fh):
+        raise Y3Error(f"frame_hw must be int32 [F,2] with F dividing the {packed.shape[0]} tile images")
+    F, M = len(fh), packed.shape[1]
+    T = packed.shape[0] // F
+    if num_valid.dtype != torch.int32 or num_valid.shape != (F * T,):
+        raise Y3Error(f"num_valid must be int32 [{F * T}]")
+    w, g = np.ascontiguousarray(windows, dtype=np.int32), np.ascontiguousarray(geoms, dtype=np.int32)
+    if w.shape != (F * T, 4) or g.shape != (F * T, 4):
+        raise Y3Error(f"windows and geoms must be int32 [{F * T},4]")
+    lib = lib or _lib.load()
+    if ws is None:
+        ws = torch.empty(max(lib.y3_merge_tiles_workspace_bytes(F, T, M), 16), dtype=torch.uint8, device=packed.device)
+    elif ws.dtype != torch.uint8 or ws.dim() != 1:
+        raise Y3Error("ws must be a 1-D uint8 tensor")
+    merged, nv = out or (torch.empty((F, M, 7), dtype=torch.int32, device=packed.device),
+                         torch.empty((F,), dtype=torch.int32, device=packed.device))
+    _need_cuda(merged, nv)
+    if merged.dtype != torch.int32 or merged.shape != (F, M, 7) or nv.dtype != torch.int32 or nv.shape != (F,):
+        raise Y3Error(f"out must be int32 [{F},{M},7] and int32 [{F}]")
+    from .input_stage import canvas_hw
+    Hc, Wc = canvas_hw(image_size)
+    i32 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int32))
+    check(lib.y3_merge_tile_detections(_dev(packed), _dev(num_valid), i32(w), i32(g), i32(fh), F, T, M, Hc, Wc,
+                                       _lib.Y3_NMS_PER_CLASS if per_class else _lib.Y3_NMS_AGNOSTIC, float(iou_threshold),
+                                       float(score_threshold), _dev(merged), _dev(nv), _dev(ws), ws.numel(), _lib.stream_ptr()),
+          "y3_merge_tile_detections")
+    return merged, nv
+
+
 def unpack_detections(packed: torch.Tensor):
     """[.., M, 7] int32 words -> (boxes f32 [..,M,4], scores f32 [..,M], classes i32, indices i32)"""
     f = packed[..., :5].contiguous().view(torch.float32)

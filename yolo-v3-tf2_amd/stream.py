@@ -13,10 +13,11 @@ import torch
 from . import ops
 from ._args import _anchors, _dev, _fptr
 from ._lib import Y3Error, check
-from .input_stage import InputStage, packed_nbytes, unletterbox_detections
+from .input_stage import InputStage, TiledInputStage, packed_nbytes, tiles_arg, unletterbox_detections
 
 
-def detect_stream(net, batches, anchors, max_boxes, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes, letterbox):
+def detect_stream(net, batches, anchors, max_boxes, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes, letterbox,
+                  tiles=None, merge_iou_threshold=None):
     M = int(max_boxes)
     outs = {}       # ring slot -> pinned rows, pinned counts, event: made on the slot's first use
     pending = []
@@ -28,8 +29,9 @@ def detect_stream(net, batches, anchors, max_boxes, iou_threshold, score_thresho
         return packed_host[:n].numpy().copy(), nv_host[:n].numpy().copy()
 
     for i, handle, packed_dev, nv_dev, cur, stage, _ in _detect_batches(
-            net, "detect_stream", batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes, letterbox):
-        k, n = i % stage.depth, handle.batch.shape[0]
+            net, "detect_stream", batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes, letterbox,
+            tiles=tiles, merge_iou_threshold=merge_iou_threshold):
+        k, n = i % stage.depth, handle.frames
         if k not in outs:
             outs[k] = (torch.empty((stage.max_batch, M, 7), dtype=torch.int32, pin_memory=True),
                        torch.empty((stage.max_batch,), dtype=torch.int32, pin_memory=True), torch.cuda.Event())
@@ -45,7 +47,7 @@ def detect_stream(net, batches, anchors, max_boxes, iou_threshold, score_thresho
 
 
 def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes,
-                    letterbox, keep_grids=False):
+                    letterbox, keep_grids=False, tiles=None, merge_iou_threshold=None):
     """The loop detect_stream and evaluate_stream share: a generator that stages batch i+1 on the InputStage's copy stream,
     enqueues y3_net_detect (and, with letterbox, y3_unletterbox_detections) of batch i on the current stream, and yields
     (i, handle, packed_dev, nv_dev, stream, stage, grids) for the consumer to enqueue its own work on `stream` behind them.
@@ -54,7 +56,20 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
     each batch takes the composed route include/y3.h documents as bit-identical to y3_net_detect: y3_net_forward into
     grid buffers made once here, y3_yolo_decode_scores, y3_nms_padded (y3_nms_padded_per_class when net.nms_per_class is set,
     as y3_net_detect itself chooses), y3_pack_detections.  One set of buffers, the NMS
-    workspace among them, serves every batch: all of it runs on the one stream."""
+    workspace among them, serves every batch: all of it runs on the one stream.
+    tiles = (rows, cols, overlap_px, overview): sliced inference.  The stage cuts every frame into T windows from the one upload, the
+    net is planned for max_batch * T tile images, y3_net_detect runs on the tile batch in the net's NMS mode into a ring of its own, and
+    y3_merge_tile_detections (the same mode, merge_iou_threshold, by default iou_threshold) takes the place of
+    y3_unletterbox_detections: what is yielded is per FRAME and in frame coordinates, with the shapes of the untiled route.
+    tiles=None enqueues exactly what it did before the argument existed."""
+    T = 1
+    if tiles is not None:
+        if keep_grids:
+            raise Y3Error(f"{who}: loss=True cannot be combined with tiles (the ground truth is not mapped onto the windows)")
+        tiles, T = tiles_arg(who, tiles)
+        merge_iou = float(iou_threshold if merge_iou_threshold is None else merge_iou_threshold)
+    elif merge_iou_threshold is not None:
+        raise Y3Error(f"{who}: merge_iou_threshold needs tiles")
     if max_batch is None or max_blob_bytes is None:
         if not isinstance(batches, (list, tuple)):
             raise Y3Error(f"{who}: pass max_batch and max_blob_bytes when `batches` is not a list or tuple")
@@ -69,13 +84,18 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
         raise Y3Error(f"{who}: depth must be at least 2 (batch i+1 is staged while batch i is detected)")
     if max_batch < 1:
         return
-    stage = InputStage(S, max_batch, max(int(max_blob_bytes), 16), depth)
-    if max_batch > net.max_batch:
-        net.plan(max_batch, S)
+    stage = (InputStage(S, max_batch, max(int(max_blob_bytes), 16), depth) if tiles is None else
+             TiledInputStage(S, max_batch, max(int(max_blob_bytes), 16), tiles, depth))
+    if max_batch * T > net.max_batch:
+        net.plan(max_batch * T, S)
     a = _anchors(anchors, reshape=True)
     dev = stage.device
     ring = [(torch.empty((max_batch, M, 7), dtype=torch.int32, device=dev),
              torch.empty((max_batch,), dtype=torch.int32, device=dev)) for _ in range(stage.depth)]
+    if tiles is not None:       # the tiles' rows, and the workspace of the merge: one of each, all of it runs on the one stream
+        tile_packed = torch.empty((max_batch * T, M, 7), dtype=torch.int32, device=dev)
+        tile_nv = torch.empty((max_batch * T,), dtype=torch.int32, device=dev)
+        merge_ws = torch.empty(max(ops.merge_tiles_workspace_bytes(max_batch, T, M), 16), dtype=torch.uint8, device=dev)
     if keep_grids:
         nc, gs = net.program.nclasses, net._grid_hw()
         if nc <= 0:
@@ -107,11 +127,19 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
             picked = ops._nms(decoded[0], decoded[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws,
                               classes=decoded[1] if net.nms_per_class else None)     # the rule y3_net_detect would take
             ops._pack(*decoded, *picked, out=packed_dev[:n])
+        elif tiles is not None:
+            check(net.lib.y3_net_detect(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
+                                        float(score_threshold), _dev(tile_packed), _dev(tile_nv), sp), "y3_net_detect")
         else:
             check(net.lib.y3_net_detect(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
                                         float(score_threshold), _dev(packed_dev), _dev(nv_dev), sp), "y3_net_detect")
         stage.release(handle)
-        if letterbox:
+        if tiles is not None:
+            f = handle.frames
+            ops.merge_tile_detections(tile_packed[:n], tile_nv[:n], handle.windows, handle.geometry, handle.frame_hw, net.canvas,
+                                      merge_iou, score_threshold, per_class=net.nms_per_class, out=(packed_dev[:f], nv_dev[:f]),
+                                      ws=merge_ws, lib=net.lib)
+        elif letterbox:
             unletterbox_detections(packed_dev[:n], nv_dev[:n], handle.geometry, net.canvas)
         yield i, handle, packed_dev, nv_dev, cur, stage, grids
         handle, i = following, i + 1
@@ -210,11 +238,13 @@ class _Loss:
 
 
 def evaluate_stream(net, batches, gts, anchors, max_boxes, iou_threshold, score_thresholds, nclasses, evaluate_iou_threshold,
-                    one_class, mode, depth, max_batch, max_blob_bytes, letterbox, max_gt, loss, ap):
+                    one_class, mode, depth, max_batch, max_blob_bytes, letterbox, max_gt, loss, ap, tiles=None, merge_iou_threshold=None):
     thresholds = [float(t) for t in score_thresholds]
     ap_thr = None if ap is None or ap is False else ops.ap_iou_thresholds(ap)
     if loss and letterbox:
         raise Y3Error("evaluate_stream: loss=True cannot be combined with letterbox=True (the ground truth is not mapped onto the canvas)")
+    if loss and tiles is not None:
+        raise Y3Error("evaluate_stream: loss=True cannot be combined with tiles (the ground truth is not mapped onto the windows)")
     if loss and net.canvas[0] != net.canvas[1]:
         raise ValueError(f"evaluate_stream: loss=True needs a square plan (the net is planned for {net.canvas[0]} x {net.canvas[1]}; "
                          "the loss kernels take one grid size per scale)")
@@ -245,8 +275,8 @@ def evaluate_stream(net, batches, gts, anchors, max_boxes, iou_threshold, score_
     gt_ring, result = _GroundTruthRing(G), None
     for i, handle, packed_dev, nv_dev, cur, stage, grids in _detect_batches(
             net, "evaluate_stream", batches, anchors, M, iou_threshold, min(thresholds), mode, depth, max_batch, max_blob_bytes, letterbox,
-            keep_grids=bool(loss)):
-        n = handle.batch.shape[0]
+            keep_grids=bool(loss), tiles=tiles, merge_iou_threshold=merge_iou_threshold):
+        n = handle.frames
         gt = next(gt_iter, missing)
         if gt is missing:
             raise Y3Error(f"evaluate_stream: `gts` ends before batch {i}")

@@ -396,7 +396,7 @@ y3_status y3_preprocess_image(const void *image_dev, int is_uint8, int height, i
 y3_status y3_preprocess_image_hw(const void *image_dev, int is_uint8, int height, int width, int channels,
                                  float *batch_dev, int slot, int canvas_h, int canvas_w, void *stream);
 
-/* The same stage for a batch of unlike images in one launch per 64 images (no reference counterpart: the reference resizes
+/* The same stage for a batch of unlike images in one launch per 72 images (no reference counterpart: the reference resizes
  * image by image).  All images lie in ONE device blob `pixels_dev` of `pixels_bytes` bytes; image i starts `offset` bytes into
  * it, is [height,width,channels] (channels 3 or 4, alpha dropped) and has `mode` with the meaning of is_uint8 above: 0 float32
  * (offset and pixels_dev 4-byte aligned), 1 uint8 * 1/255 before the resize, 2 uint8 divided by 255 after it, each optionally
@@ -556,8 +556,9 @@ int y3_tile_grid(int height, int width, int rows, int cols, int overlap_px, int 
  * height x width x channels image that starts `offset` bytes into pixels_dev, and is treated AS AN IMAGE OF ITS OWN: the bilinear
  * taps clamp at the window's edges, and with Y3_IMAGE_LETTERBOX the geometry is that of a ch x cw image.  `mode` as in
  * y3_image_desc.  Tile i is written to batch_dev[first_slot + i], and every value is bit-identical to y3_preprocess_batch_hw on a
- * contiguous copy of the window: the same per-pixel body reads the frame with the frame's row pitch.  Several tiles may name the
- * same image, which is therefore uploaded once.  The descriptors travel in the kernel arguments, 72 tiles per launch.  Checked on
+ * contiguous copy of the window: the same kernel reads the frame with the frame's row pitch (an image is the whole-frame window of
+ * itself).  Several tiles may name the same image, which is therefore uploaded once.  The descriptors travel in the kernel
+ * arguments, 72 tiles per launch.  Checked on
  * the host before anything is enqueued (Y3_ERR_INVALID names the tile): everything y3_preprocess_batch checks, ch and cw >= 1,
  * the window inside the image, the letterbox of ch x cw fitting the canvas.  Only enqueues on `stream`; can be captured. */
 typedef struct y3_tile_desc { uint64_t offset; int32_t height, width, channels, mode; int32_t y0, x0, ch, cw; } y3_tile_desc;

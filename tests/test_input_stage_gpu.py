@@ -89,11 +89,14 @@ def test_unaligned_batch_base_takes_the_scalar_path(rt):
 
 
 def test_more_images_than_one_launch_holds(rt):
-    """150 images: three launches inside one call == the same images issued as chunks of at most 64 == per image."""
+    """150 images: launches of 72, 72 and 6 inside one call == the same images issued as chunks of 50 == per image.  A 1x1x3 image and
+    a four-channel image sit on either side of both launch boundaries."""
     S = 64
     rng = np.random.default_rng(150)
     images = [rng.integers(0, 256, (int(rng.integers(1, 40)), int(rng.integers(1, 40)), int(rng.integers(3, 5))), dtype=np.uint8)
               for _ in range(150)]
+    for i, shape in ((71, (1, 1, 3)), (72, (23, 39, 4)), (143, (39, 17, 4)), (144, (1, 1, 3))):
+        images[i] = rng.integers(0, 256, shape, dtype=np.uint8)
     modes = [int(m) for m in rng.integers(1, 3, len(images))]
     blob, descs = rt.pack_images(images, modes)
     blob_dev = _cuda(blob)

@@ -1,4 +1,4 @@
-"""Sliced inference on the device: preprocess_tiles_kernel against preprocess_batch on contiguous crops, merge_tiles_kernel + the
+"""Sliced inference on the device: preprocess_tiles on windows against preprocess_batch on contiguous crops, merge_tiles_kernel + the
 existing NMS and pack against tiles.merge_tile_detections_ref (which tests/test_tiles_host.py ties to a brute-force loop), and
 Net.detect_stream / evaluate_stream with Net.tiles set against the same calls composed by hand.  Destinations, outputs and workspaces are
 poisoned before every call; every comparison is exact, every word."""
@@ -83,7 +83,7 @@ def test_tiles_on_a_canvas_that_takes_the_scalar_stores(rt):
 
 
 def test_more_tiles_than_one_launch_holds(rt):
-    """150 windows of one frame: launches of 72, 72 and 6 tiles (preprocess_batch takes its 150 crops 64 at a time)."""
+    """150 windows of one frame: launches of 72, 72 and 6 tiles (preprocess_batch takes its 150 crops in the same three launches)."""
     rng = np.random.default_rng(7)
     f = K.frame((97, 131, 3), 2, 5)
     wins = []

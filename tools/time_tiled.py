@@ -7,7 +7,7 @@ overlapping by 64 pixels + the whole-frame overview (7 tile images per frame), f
                  times), Net.detect_stream(letterbox=True) on the 56 crops, then the boxes mapped to the frame and merged in NumPy
                  (tiles.merge_tile_detections_ref on identity geometries: detect_stream has already un-letterboxed the rows)
   tiled      (c) Net.detect_stream(letterbox=True) with net.tiles = (2, 3, 64, True): frames uploaded once, windows cut by
-                 preprocess_tiles_kernel, merge_tiles_kernel + the existing NMS and pack on the device
+                 preprocess_batch_kernel, merge_tiles_kernel + the existing NMS and pack on the device
   resident   Net.detect on 56 tile images already on the device, as frames/s (images/s / 7): what 7 x the images cost, the bound of (c)
 
 IMAGE DECODE IS EXCLUDED.  Every route is warmed up; a timed window ends in a synchronise and lasts about --window seconds; the routes
@@ -203,16 +203,17 @@ def summarize(a):
         raise SystemExit(f"no kernel trace under {a.summarize}")
     rows = sorted((int(r["Start_Timestamp"]), int(r["End_Timestamp"]) - int(r["Start_Timestamp"]), r["Kernel_Name"])
                   for r in csv.DictReader(open(files[0])))
-    first_tiled = next(s for s, _, n in rows if "preprocess_tiles_kernel" in n)
+    # one kernel name serves both phases: only the untiled phase launches unletterbox_kernel, and the tiled phase begins at the first
+    # preprocess_batch_kernel launch after the last of those
+    last_untiled = max(s for s, _, n in rows if "unletterbox_kernel" in n)
+    first_tiled = next(s for s, _, n in rows if "preprocess_batch_kernel" in n and s > last_untiled)
     groups = {k: [] for k in ("preprocess_batch_kernel (8 frames -> 8 images)", "nms_kernel, untiled (8 x 10647 boxes)",
-                              "preprocess_tiles_kernel (8 frames -> 56 images)", "nms_kernel, per tile (56 x 10647 boxes)", "merge_tiles_kernel (56 x 100 rows)",
+                              "preprocess_batch_kernel (8 frames -> 56 images)", "nms_kernel, per tile (56 x 10647 boxes)", "merge_tiles_kernel (56 x 100 rows)",
                               "nms_kernel, merge (8 x 700 candidates)", "pack_kernel, merge", "unletterbox_kernel, untiled")}
     after_merge = 0
     for s, d, n in rows:
         if "preprocess_batch_kernel" in n:
-            groups["preprocess_batch_kernel (8 frames -> 8 images)"].append(d)
-        elif "preprocess_tiles_kernel" in n:
-            groups["preprocess_tiles_kernel (8 frames -> 56 images)"].append(d)
+            groups[f"preprocess_batch_kernel (8 frames -> {56 if s >= first_tiled else 8} images)"].append(d)
         elif "merge_tiles_kernel" in n:
             groups["merge_tiles_kernel (56 x 100 rows)"].append(d)
             after_merge = 2

@@ -9,9 +9,9 @@
 // Arithmetic restated from TF's ResizeBilinear CPU kernel: in = (out + 0.5) * (in_size / out_size) - 0.5,
 // lower = max(floor(in), 0), upper = min(ceil(in), in_size - 1), lerp = in - floor(in); interpolate along x first
 // (top, bottom) then along y; fp32, no contraction.  HBM-bound and tiny.  resize_kernel: one image per launch, one thread per
-// output pixel; preprocess_batch_kernel: up to 64 unlike images per launch, four pixels per thread; preprocess_tiles_kernel: the same for
-// up to 72 windows of such images, each window an image of its own (sliced inference; include/y3.h, y3_preprocess_tiles_hw).
-// All of them also serve the aspect-preserving form of reference core/utils.py:17-28 (resize_image: tf.image.resize(
+// output pixel; preprocess_batch_kernel: up to 72 unlike views per launch, four pixels per thread -- a view is a whole image or a window of
+// one, each window an image of its own (sliced inference; include/y3.h, y3_preprocess_tiles_hw).
+// Both also serve the aspect-preserving form of reference core/utils.py:17-28 (resize_image: tf.image.resize(
 // preserve_aspect_ratio=True) + pad_to_bounding_box), flag Y3_IMAGE_LETTERBOX: resize to sh x sw, centred on a zero canvas.
 #include <type_traits>
 
@@ -36,7 +36,7 @@ __device__ __forceinline__ float px<RawU8>(const RawU8 *p) { return (float)p->v;
 // block is 0.0f -- it is written like any other, a reused slot keeps nothing of its last image.  Inside, the same operations in
 // the same order with (sh, sw) in the place of (Hc, Wc).  LB = false compiles to what it was before the flag existed.
 // row_pitch: elements of T from one source row to the next -- W * pix_stride for an image of its own, the frame's pitch for a window
-// of a frame (preprocess_tiles_kernel), whose taps clamp at the window's edges like any image's.
+// of a frame (ResizeView), whose taps clamp at the window's edges like any image's.
 template <typename T, bool LB>
 __device__ __forceinline__ void resize_pixel(const T *__restrict__ src, int H, int W, int pix_stride, size_t row_pitch, int Hc, int Wc,
                                              LetterboxGeom g, int i, float *out)
@@ -81,9 +81,10 @@ __global__ __launch_bounds__(256) void resize_kernel(const T *__restrict__ src, 
     for (int c = 0; c < 3; ++c) dst[(size_t)i * 3 + c] = v[c];
 }
 
-// A batch of unlike images in one launch: blockIdx.y is the image within the launch, blockIdx.x tiles its Hc*Wc output pixels.
-// The descriptors and geometries travel by value in the kernel arguments (PreprocessTable, 2.5 KB of the 4 KB limit): nothing
-// extra is copied, they have no lifetime to manage, and the launch can be captured into a graph.
+// A batch of unlike views in one launch: blockIdx.y is the view within the launch, blockIdx.x tiles its Hc*Wc output pixels.
+// The views travel by value in the kernel arguments (ResizeTable, 3.4 KB of the 4 KB limit): nothing extra is copied, they have
+// no lifetime to manage, and the launch can be captured into a graph.  A tile has the bits a contiguous copy of its window gets: the
+// same pixel body, reading the frame with the frame's row pitch from the window's first pixel.
 // VEC: every thread produces four consecutive pixels (12 floats) and writes them as three 16-byte stores; needs
 // Hc*Wc % 4 == 0 and a 16-byte aligned destination, which holds for every network size (sides multiples of 32).  Otherwise one
 // pixel and three scalar stores per thread.  Each of the four pixels decides on its own whether it is padding: a thread may
@@ -126,35 +127,17 @@ __device__ __forceinline__ void preprocess_batch_modes(const unsigned char *__re
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char *__restrict__ pixels, PreprocessTable table,
+__global__ __launch_bounds__(256) void preprocess_batch_kernel(const unsigned char *__restrict__ pixels, ResizeTable table,
                                                                float *__restrict__ batch, int Hc, int Wc)
 {
-    const y3_image_desc d = table.d[blockIdx.y];          // uniform per workgroup: scalar loads from the kernel arguments
-    const unsigned char *src = pixels + d.offset;
+    const ResizeView v = table.v[blockIdx.y];             // uniform per workgroup: scalar loads from the kernel arguments
+    const unsigned char *src = pixels + v.first;
     float *dst = batch + (size_t)blockIdx.y * Hc * Wc * 3;
-    const int mode = d.mode & ~Y3_IMAGE_LETTERBOX;
-    if (d.mode & Y3_IMAGE_LETTERBOX)                      // one branch per workgroup each, outside the pixel body
-        preprocess_batch_modes<VEC, true>(src, d.height, d.width, d.channels, d.width, mode, dst, Hc, Wc, table.g[blockIdx.y]);
+    const int mode = v.mode & ~Y3_IMAGE_LETTERBOX;
+    if (v.mode & Y3_IMAGE_LETTERBOX)                      // one branch per workgroup each, outside the pixel body
+        preprocess_batch_modes<VEC, true>(src, v.rows, v.cols, v.channels, v.pitch_px, mode, dst, Hc, Wc, v.g);
     else
-        preprocess_batch_modes<VEC, false>(src, d.height, d.width, d.channels, d.width, mode, dst, Hc, Wc, LetterboxGeom{});
-}
-
-// Windows of frames as images of their own (include/y3.h, y3_preprocess_tiles_hw): the kernel above with the source pointer moved to the
-// window's first pixel, the window's extent as the image's and the frame's width as the row pitch -- the pixel body is the same code, so a tile
-// has the bits preprocess_batch_kernel gives for a contiguous copy of the window.  Same launch shape: four pixels, three 16-byte stores.
-template <bool VEC>
-__global__ __launch_bounds__(256) void preprocess_tiles_kernel(const unsigned char *__restrict__ pixels, TileTable table,
-                                                               float *__restrict__ batch, int Hc, int Wc)
-{
-    const y3_tile_desc d = table.d[blockIdx.y];
-    const int mode = d.mode & ~Y3_IMAGE_LETTERBOX;
-    const size_t elem = mode == 0 ? sizeof(float) : 1;
-    const unsigned char *src = pixels + d.offset + ((size_t)d.y0 * d.width + d.x0) * d.channels * elem;
-    float *dst = batch + (size_t)blockIdx.y * Hc * Wc * 3;
-    if (d.mode & Y3_IMAGE_LETTERBOX)
-        preprocess_batch_modes<VEC, true>(src, d.ch, d.cw, d.channels, d.width, mode, dst, Hc, Wc, table.g[blockIdx.y]);
-    else
-        preprocess_batch_modes<VEC, false>(src, d.ch, d.cw, d.channels, d.width, mode, dst, Hc, Wc, LetterboxGeom{});
+        preprocess_batch_modes<VEC, false>(src, v.rows, v.cols, v.channels, v.pitch_px, mode, dst, Hc, Wc, LetterboxGeom{});
 }
 
 template <typename T>
@@ -182,16 +165,9 @@ hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride
     return hipGetLastError();
 }
 
-// descs / geoms: n (1..kPreprocessTableImages) validated descriptors and their geometries; dst: slot of the first image.
 // Vector stores when the geometry allows.
-hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
-                                   int Wc, hipStream_t s)
+hipError_t launch_preprocess_batch(const void *pixels, const ResizeTable &table, int n, float *dst, int Hc, int Wc, hipStream_t s)
 {
-    PreprocessTable table{};
-    for (int i = 0; i < n; ++i) {
-        table.d[i] = descs[i];
-        table.g[i] = geoms[i];
-    }
     const bool vec = ((size_t)Hc * Wc) % 4 == 0 && ((uintptr_t)dst & 15) == 0;
     const int per_block = vec ? 1024 : 256;
     dim3 grid((unsigned)(((size_t)Hc * Wc + per_block - 1) / per_block), (unsigned)n), block(256);
@@ -200,26 +176,6 @@ hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *desc
         hipLaunchKernelGGL(preprocess_batch_kernel<true>, grid, block, 0, s, p, table, dst, Hc, Wc);
     else
         hipLaunchKernelGGL(preprocess_batch_kernel<false>, grid, block, 0, s, p, table, dst, Hc, Wc);
-    return hipGetLastError();
-}
-
-// descs / geoms: n (1..kTileTableTiles) validated tile descriptors and their geometries; dst: slot of the first tile
-hipError_t launch_preprocess_tiles(const void *pixels, const y3_tile_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
-                                   int Wc, hipStream_t s)
-{
-    TileTable table{};
-    for (int i = 0; i < n; ++i) {
-        table.d[i] = descs[i];
-        table.g[i] = geoms[i];
-    }
-    const bool vec = ((size_t)Hc * Wc) % 4 == 0 && ((uintptr_t)dst & 15) == 0;
-    const int per_block = vec ? 1024 : 256;
-    dim3 grid((unsigned)(((size_t)Hc * Wc + per_block - 1) / per_block), (unsigned)n), block(256);
-    const unsigned char *p = static_cast<const unsigned char *>(pixels);
-    if (vec)
-        hipLaunchKernelGGL(preprocess_tiles_kernel<true>, grid, block, 0, s, p, table, dst, Hc, Wc);
-    else
-        hipLaunchKernelGGL(preprocess_tiles_kernel<false>, grid, block, 0, s, p, table, dst, Hc, Wc);
     return hipGetLastError();
 }
 

@@ -296,21 +296,16 @@ inline bool letterbox_geom_fits(const LetterboxGeom &g, int Hc, int Wc)
 // mode: 0, 1, 2 (y3_preprocess_image's is_uint8), optionally | Y3_IMAGE_LETTERBOX with the geometry g
 hipError_t launch_resize(const void *src, int mode, int H, int W, int pix_stride, float *dst, int Hc, int Wc, const LetterboxGeom &g,
                          hipStream_t s);
-// The image descriptors and geometries of one preprocess_batch_kernel launch, passed by value in the kernel arguments (the limit is 4 KB).
-constexpr int kPreprocessTableImages = 64;
-struct PreprocessTable { y3_image_desc d[kPreprocessTableImages]; LetterboxGeom g[kPreprocessTableImages]; };
-static_assert(sizeof(y3_image_desc) == 24 && sizeof(PreprocessTable) + 64 <= 4096, "descriptor table must fit the kernel arguments");
-hipError_t launch_preprocess_batch(const void *pixels, const y3_image_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
-                                   int Wc, hipStream_t s);
-
-// The tile descriptors and geometries of one preprocess_tiles_kernel launch, by value like PreprocessTable: 56 bytes per tile, as many
-// as the 4 KB of kernel arguments hold beside the two pointers and the canvas.
-constexpr int kTileTableTiles = 72;
-struct TileTable { y3_tile_desc d[kTileTableTiles]; LetterboxGeom g[kTileTableTiles]; };
-static_assert(sizeof(y3_tile_desc) == 40 && sizeof(TileTable) + 64 <= 4096 && sizeof(TileTable) + 64 + 56 > 4096,
-              "tile table must fill the kernel arguments");
-hipError_t launch_preprocess_tiles(const void *pixels, const y3_tile_desc *descs, const LetterboxGeom *geoms, int n, float *dst, int Hc,
-                                   int Wc, hipStream_t s);
+// What preprocess_batch_kernel resizes into one slot: a strided view of the pixel blob and where it lands on the canvas.  The kernel knows
+// nothing of images or tiles: an image is the whole-frame view of itself (pitch_px == cols), a tile a window of its frame (pitch_px == the
+// frame's width).  first: byte offset of the view's first pixel in the blob, computed on the host.  mode: y3_image_desc.mode.
+struct ResizeView { uint64_t first; int32_t rows, cols, pitch_px, channels, mode; LetterboxGeom g; };
+// The views of one launch, passed by value in the kernel arguments (the limit is 4 KB).
+constexpr int kResizeTableViews = 72;
+struct ResizeTable { ResizeView v[kResizeTableViews]; };
+static_assert(sizeof(ResizeView) == 48 && sizeof(ResizeTable) + 64 <= 4096, "view table must fit the kernel arguments");
+// table.v[0 .. n): validated views, n in 1..kResizeTableViews; dst: slot of the first one
+hipError_t launch_preprocess_batch(const void *pixels, const ResizeTable &table, int n, float *dst, int Hc, int Wc, hipStream_t s);
 
 // Sliced inference, the merge (tiles.hip; include/y3.h, y3_merge_tile_detections).  One entry per tile image: its window of the frame, its
 // letterbox geometry on the canvas and the frame's extent; 64 entries per merge_tiles_kernel launch, by value in the kernel arguments.
@@ -323,7 +318,7 @@ static_assert(sizeof(MergeTile) == 40 && sizeof(MergeTable) + 64 <= 4096, "merge
 hipError_t launch_merge_tiles(const void *packed, const int32_t *nv, const MergeTile *entries, int n, int M, int Hc, int Wc, float *boxes,
                               float *scores, int64_t *cls, hipStream_t s);
 
-// The geometries of one unletterbox_kernel launch, by value in the kernel arguments like PreprocessTable.
+// The geometries of one unletterbox_kernel launch, by value in the kernel arguments like ResizeTable.
 constexpr int kUnletterboxTableImages = 64;
 struct UnletterboxTable { LetterboxGeom g[kUnletterboxTableImages]; };
 hipError_t launch_unletterbox(void *packed, const int32_t *nv, const LetterboxGeom *geoms, int n, int M, int Hc, int Wc, hipStream_t s);

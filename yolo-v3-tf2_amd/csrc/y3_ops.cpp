@@ -30,6 +30,91 @@ y3::LetterboxGeom image_geom(int mode, int h, int w, int Hc, int Wc)
 {
     return (mode & Y3_IMAGE_LETTERBOX) ? y3::letterbox_geom(h, w, Hc, Wc) : y3::LetterboxGeom{Hc, Wc, 0, 0};
 }
+// the window ch x cw at (y0, x0) lies inside h x w
+bool window_in_frame(int y0, int x0, int ch, int cw, int h, int w)
+{
+    return ch >= 1 && cw >= 1 && y0 >= 0 && x0 >= 0 && y0 <= h - ch && x0 <= w - cw;
+}
+
+// A descriptor in window form is a y3_tile_desc, and an image is the whole-frame window of itself.
+y3_tile_desc as_window(const y3_image_desc &d) { return {d.offset, d.height, d.width, d.channels, d.mode, 0, 0, d.height, d.width}; }
+const y3_tile_desc &as_window(const y3_tile_desc &d) { return d; }
+
+struct Blob { const void *dev; size_t bytes; };
+
+// The one check of a descriptor, and the view preprocess_batch_kernel reads for it: `noun` i ("image" / "tile") in the messages.
+// blob null: what the geometry calls check -- mode, extent and window; channels and offset are not read and `view` gets the geometry only.
+y3_status resize_view(const char *who, const char *noun, int i, const y3_tile_desc &d, const Blob *blob, int Hc, int Wc, y3::ResizeView *view)
+{
+    if (blob && (d.channels < 3 || d.channels > 4))
+        return fail(Y3_ERR_INVALID, "%s: %s %d: channels must be 3 or 4 (got %d)", who, noun, i, d.channels);
+    if (!image_mode_ok(d.mode))
+        return fail(Y3_ERR_INVALID, "%s: %s %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, noun, i, d.mode);
+    if (d.height < 1 || d.width < 1)
+        return fail(Y3_ERR_INVALID, "%s: %s %d: height and width must be at least 1 (got %d x %d)", who, noun, i, d.height, d.width);
+    if (d.ch < 1 || d.cw < 1) return fail(Y3_ERR_INVALID, "%s: %s %d: ch and cw must be at least 1 (got %d x %d)", who, noun, i, d.ch, d.cw);
+    if (!window_in_frame(d.y0, d.x0, d.ch, d.cw, d.height, d.width))
+        return fail(Y3_ERR_INVALID, "%s: %s %d: window %d x %d at (%d, %d) does not lie inside the %d x %d image", who, noun, i, d.ch, d.cw,
+                    d.y0, d.x0, d.height, d.width);
+    view->g = image_geom(d.mode, d.ch, d.cw, Hc, Wc);
+    if (!blob) return Y3_OK;
+    const bool f32 = (d.mode & ~Y3_IMAGE_LETTERBOX) == 0;
+    if (f32 && ((d.offset & 3) || ((uintptr_t)blob->dev & 3)))
+        return fail(Y3_ERR_INVALID, "%s: %s %d: float32 pixels must be 4-byte aligned (offset %llu)", who, noun, i,
+                    (unsigned long long)d.offset);
+    // height, width < 2^31 and channels * elemsize <= 16: the product stays below 2^66, so take it in 128 bits
+    const unsigned pixel_bytes = (unsigned)(d.channels * (f32 ? 4 : 1));
+    const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * pixel_bytes;
+    if ((unsigned __int128)d.offset + bytes > (unsigned __int128)blob->bytes)
+        return fail(Y3_ERR_INVALID, "%s: %s %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", who, noun, i,
+                    d.height, d.width, d.channels, (unsigned long long)d.offset, blob->bytes);
+    if (!y3::letterbox_geom_fits(view->g, Hc, Wc))
+        return fail(Y3_ERR_INVALID, "%s: %s %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, noun, i,
+                    d.ch, d.cw, view->g.sh, view->g.sw, view->g.top, view->g.left, Hc, Wc);
+    view->first = d.offset + ((uint64_t)d.y0 * d.width + d.x0) * pixel_bytes;     // inside the blob: 64 bits hold it
+    view->rows = d.ch, view->cols = d.cw, view->pitch_px = d.width, view->channels = d.channels, view->mode = d.mode;
+    return Y3_OK;
+}
+
+// y3_preprocess_batch[_hw] (Desc = y3_image_desc) and y3_preprocess_tiles_hw (y3_tile_desc)
+template <typename Desc>
+y3_status preprocess_views(const char *who, const char *noun, const void *pixels_dev, size_t pixels_bytes, const Desc *descs_host, int n,
+                           float *batch_dev, int first_slot, int Hc, int Wc, void *stream)
+{
+    if (!pixels_dev || !descs_host || !batch_dev || n < 1 || first_slot < 0 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_%ss < 1, first_slot < 0 or canvas <= 0)", who, noun);
+    const Blob blob{pixels_dev, pixels_bytes};
+    y3::ResizeTable table{};     // on the stack: the call allocates nothing
+    // every check before the first launch: a bad descriptor late in the list must not leave the batch half written
+    for (int i = 0; i < n; ++i)
+        if (y3_status st = resize_view(who, noun, i, as_window(descs_host[i]), &blob, Hc, Wc, &table.v[0]); st != Y3_OK) return st;
+    const size_t per_image = (size_t)Hc * Wc * 3;
+    for (int i0 = 0; i0 < n; i0 += y3::kResizeTableViews) {
+        const int m = std::min(y3::kResizeTableViews, n - i0);
+        for (int i = 0; i < m; ++i) resize_view(who, noun, i0 + i, as_window(descs_host[i0 + i]), &blob, Hc, Wc, &table.v[i]);
+        hipError_t e = y3::launch_preprocess_batch(pixels_dev, table, m, batch_dev + ((size_t)first_slot + i0) * per_image, Hc, Wc,
+                                                   (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    }
+    return Y3_OK;
+}
+
+// y3_letterbox_geometry[_hw] and y3_tile_letterbox_geometry_hw: nothing is written unless every descriptor passes
+template <typename Desc>
+y3_status view_geometries(const char *who, const char *noun, const Desc *descs_host, int n, int Hc, int Wc, int32_t *geoms_out_host)
+{
+    if (!descs_host || !geoms_out_host || n < 1 || Hc <= 0 || Wc <= 0)
+        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_%ss < 1 or canvas <= 0)", who, noun);
+    static_assert(sizeof(y3::LetterboxGeom) == 4 * sizeof(int32_t), "a geometry is four int32");
+    y3::ResizeView v;
+    for (int i = 0; i < n; ++i)
+        if (y3_status st = resize_view(who, noun, i, as_window(descs_host[i]), nullptr, Hc, Wc, &v); st != Y3_OK) return st;
+    for (int i = 0; i < n; ++i) {
+        resize_view(who, noun, i, as_window(descs_host[i]), nullptr, Hc, Wc, &v);
+        memcpy(geoms_out_host + (size_t)i * 4, &v.g, sizeof(v.g));
+    }
+    return Y3_OK;
+}
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ decode
@@ -112,90 +197,29 @@ try {
 }
 Y3_CATCH("y3_preprocess_image")
 
-static y3_status preprocess_batch_hw(const char *who, const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host,
-                                     int n_images, float *batch_dev, int first_slot, int Hc, int Wc, void *stream)
-{
-    if (!pixels_dev || !descs_host || !batch_dev || n_images < 1 || first_slot < 0 || Hc <= 0 || Wc <= 0)
-        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_images < 1, first_slot < 0 or image_size <= 0)", who);
-    // every check before the first launch: a bad image late in the list must not leave the batch half written
-    for (int i = 0; i < n_images; ++i) {
-        const y3_image_desc &d = descs_host[i];
-        if (d.channels < 3 || d.channels > 4)
-            return fail(Y3_ERR_INVALID, "%s: image %d: channels must be 3 or 4 (got %d)", who, i, d.channels);
-        if (!image_mode_ok(d.mode))
-            return fail(Y3_ERR_INVALID, "%s: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
-        if (d.height < 1 || d.width < 1)
-            return fail(Y3_ERR_INVALID, "%s: image %d: height and width must be at least 1 (got %d x %d)", who, i,
-                        d.height, d.width);
-        const bool f32 = (d.mode & ~Y3_IMAGE_LETTERBOX) == 0;
-        if (f32 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
-            return fail(Y3_ERR_INVALID, "%s: image %d: float32 pixels must be 4-byte aligned (offset %llu)", who, i,
-                        (unsigned long long)d.offset);
-        // height, width < 2^31 and channels * elemsize <= 16: the product stays below 2^66, so take it in 128 bits
-        const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (f32 ? 4 : 1));
-        if ((unsigned __int128)d.offset + bytes > (unsigned __int128)pixels_bytes)
-            return fail(Y3_ERR_INVALID, "%s: image %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", who, i,
-                        d.height, d.width, d.channels, (unsigned long long)d.offset, pixels_bytes);
-        const y3::LetterboxGeom g = image_geom(d.mode, d.height, d.width, Hc, Wc);
-        if (!y3::letterbox_geom_fits(g, Hc, Wc))
-            return fail(Y3_ERR_INVALID, "%s: image %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, i,
-                        d.height, d.width, g.sh, g.sw, g.top, g.left, Hc, Wc);
-    }
-    const size_t per_image = (size_t)Hc * Wc * 3;
-    for (int i0 = 0; i0 < n_images; i0 += y3::kPreprocessTableImages) {
-        const int n = std::min(y3::kPreprocessTableImages, n_images - i0);
-        y3::LetterboxGeom geoms[y3::kPreprocessTableImages];     // on the stack: the call allocates nothing
-        for (int i = 0; i < n; ++i) geoms[i] = image_geom(descs_host[i0 + i].mode, descs_host[i0 + i].height, descs_host[i0 + i].width, Hc, Wc);
-        hipError_t e = y3::launch_preprocess_batch(pixels_dev, descs_host + i0, geoms, n, batch_dev + ((size_t)first_slot + i0) * per_image,
-                                                   Hc, Wc, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
-    }
-    return Y3_OK;
-}
-
 y3_status y3_preprocess_batch_hw(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
                                  float *batch_dev, int first_slot, int canvas_h, int canvas_w, void *stream)
 try {
-    return preprocess_batch_hw("y3_preprocess_batch_hw", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, canvas_h, canvas_w, stream);
+    return preprocess_views("y3_preprocess_batch_hw", "image", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, canvas_h, canvas_w, stream);
 }
 Y3_CATCH("y3_preprocess_batch_hw")
 
 y3_status y3_preprocess_batch(const void *pixels_dev, size_t pixels_bytes, const y3_image_desc *descs_host, int n_images,
                               float *batch_dev, int first_slot, int image_size, void *stream)
 try {
-    return preprocess_batch_hw("y3_preprocess_batch", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, image_size, image_size, stream);
+    return preprocess_views("y3_preprocess_batch", "image", pixels_dev, pixels_bytes, descs_host, n_images, batch_dev, first_slot, image_size, image_size, stream);
 }
 Y3_CATCH("y3_preprocess_batch")
 
-static y3_status letterbox_geometry_hw(const char *who, const y3_image_desc *descs_host, int n_images, int Hc, int Wc, int32_t *geoms_out_host)
-{
-    if (!descs_host || !geoms_out_host || n_images < 1 || Hc <= 0 || Wc <= 0)
-        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_images < 1 or image_size <= 0)", who);
-    for (int i = 0; i < n_images; ++i) {
-        const y3_image_desc &d = descs_host[i];
-        if (!image_mode_ok(d.mode))
-            return fail(Y3_ERR_INVALID, "%s: image %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
-        if (d.height < 1 || d.width < 1)
-            return fail(Y3_ERR_INVALID, "%s: image %d: height and width must be at least 1 (got %d x %d)", who, i,
-                        d.height, d.width);
-    }
-    static_assert(sizeof(y3::LetterboxGeom) == 4 * sizeof(int32_t), "a geometry is four int32");
-    for (int i = 0; i < n_images; ++i) {
-        const y3::LetterboxGeom g = image_geom(descs_host[i].mode, descs_host[i].height, descs_host[i].width, Hc, Wc);
-        memcpy(geoms_out_host + (size_t)i * 4, &g, sizeof(g));
-    }
-    return Y3_OK;
-}
-
 y3_status y3_letterbox_geometry_hw(const y3_image_desc *descs_host, int n_images, int canvas_h, int canvas_w, int32_t *geoms_out_host)
 try {
-    return letterbox_geometry_hw("y3_letterbox_geometry_hw", descs_host, n_images, canvas_h, canvas_w, geoms_out_host);
+    return view_geometries("y3_letterbox_geometry_hw", "image", descs_host, n_images, canvas_h, canvas_w, geoms_out_host);
 }
 Y3_CATCH("y3_letterbox_geometry_hw")
 
 y3_status y3_letterbox_geometry(const y3_image_desc *descs_host, int n_images, int image_size, int32_t *geoms_out_host)
 try {
-    return letterbox_geometry_hw("y3_letterbox_geometry", descs_host, n_images, image_size, image_size, geoms_out_host);
+    return view_geometries("y3_letterbox_geometry", "image", descs_host, n_images, image_size, image_size, geoms_out_host);
 }
 Y3_CATCH("y3_letterbox_geometry")
 
@@ -270,71 +294,16 @@ int y3_tile_grid(int height, int width, int rows, int cols, int overlap_px, int 
     return T;
 }
 
-// what y3_preprocess_tiles_hw and y3_tile_letterbox_geometry_hw check of a tile's window: it is an image of ch x cw inside height x width
-static y3_status tile_window_ok(const char *who, int i, const y3_tile_desc &d)
-{
-    if (!image_mode_ok(d.mode))
-        return fail(Y3_ERR_INVALID, "%s: tile %d: mode must be 0, 1 or 2, optionally | Y3_IMAGE_LETTERBOX (got %d)", who, i, d.mode);
-    if (d.height < 1 || d.width < 1)
-        return fail(Y3_ERR_INVALID, "%s: tile %d: height and width must be at least 1 (got %d x %d)", who, i, d.height, d.width);
-    if (d.ch < 1 || d.cw < 1) return fail(Y3_ERR_INVALID, "%s: tile %d: ch and cw must be at least 1 (got %d x %d)", who, i, d.ch, d.cw);
-    if (d.y0 < 0 || d.x0 < 0 || d.y0 > d.height - d.ch || d.x0 > d.width - d.cw)
-        return fail(Y3_ERR_INVALID, "%s: tile %d: window %d x %d at (%d, %d) does not lie inside the %d x %d image", who, i, d.ch, d.cw,
-                    d.y0, d.x0, d.height, d.width);
-    return Y3_OK;
-}
-
 y3_status y3_preprocess_tiles_hw(const void *pixels_dev, size_t pixels_bytes, const y3_tile_desc *descs_host, int n_tiles,
                                  float *batch_dev, int first_slot, int canvas_h, int canvas_w, void *stream)
 try {
-    const char *who = "y3_preprocess_tiles_hw";
-    const int Hc = canvas_h, Wc = canvas_w;
-    if (!pixels_dev || !descs_host || !batch_dev || n_tiles < 1 || first_slot < 0 || Hc <= 0 || Wc <= 0)
-        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_tiles < 1, first_slot < 0 or canvas <= 0)", who);
-    // every check before the first launch, as in y3_preprocess_batch
-    for (int i = 0; i < n_tiles; ++i) {
-        const y3_tile_desc &d = descs_host[i];
-        if (d.channels < 3 || d.channels > 4)
-            return fail(Y3_ERR_INVALID, "%s: tile %d: channels must be 3 or 4 (got %d)", who, i, d.channels);
-        if (y3_status st = tile_window_ok(who, i, d); st != Y3_OK) return st;
-        const bool f32 = (d.mode & ~Y3_IMAGE_LETTERBOX) == 0;
-        if (f32 && ((d.offset & 3) || ((uintptr_t)pixels_dev & 3)))
-            return fail(Y3_ERR_INVALID, "%s: tile %d: float32 pixels must be 4-byte aligned (offset %llu)", who, i,
-                        (unsigned long long)d.offset);
-        const unsigned __int128 bytes = (unsigned __int128)d.height * (unsigned __int128)d.width * (unsigned)(d.channels * (f32 ? 4 : 1));
-        if ((unsigned __int128)d.offset + bytes > (unsigned __int128)pixels_bytes)
-            return fail(Y3_ERR_INVALID, "%s: tile %d: %d x %d x %d at offset %llu runs past the %zu-byte pixel blob", who, i,
-                        d.height, d.width, d.channels, (unsigned long long)d.offset, pixels_bytes);
-        const y3::LetterboxGeom g = image_geom(d.mode, d.ch, d.cw, Hc, Wc);
-        if (!y3::letterbox_geom_fits(g, Hc, Wc))
-            return fail(Y3_ERR_INVALID, "%s: tile %d: letterbox of %d x %d (%d x %d at %d, %d) does not fit %d x %d", who, i,
-                        d.ch, d.cw, g.sh, g.sw, g.top, g.left, Hc, Wc);
-    }
-    const size_t per_image = (size_t)Hc * Wc * 3;
-    for (int i0 = 0; i0 < n_tiles; i0 += y3::kTileTableTiles) {
-        const int n = std::min(y3::kTileTableTiles, n_tiles - i0);
-        y3::LetterboxGeom geoms[y3::kTileTableTiles];     // on the stack: the call allocates nothing
-        for (int i = 0; i < n; ++i) geoms[i] = image_geom(descs_host[i0 + i].mode, descs_host[i0 + i].ch, descs_host[i0 + i].cw, Hc, Wc);
-        hipError_t e = y3::launch_preprocess_tiles(pixels_dev, descs_host + i0, geoms, n, batch_dev + ((size_t)first_slot + i0) * per_image,
-                                                   Hc, Wc, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
-    }
-    return Y3_OK;
+    return preprocess_views("y3_preprocess_tiles_hw", "tile", pixels_dev, pixels_bytes, descs_host, n_tiles, batch_dev, first_slot, canvas_h, canvas_w, stream);
 }
 Y3_CATCH("y3_preprocess_tiles_hw")
 
 y3_status y3_tile_letterbox_geometry_hw(const y3_tile_desc *descs_host, int n_tiles, int canvas_h, int canvas_w, int32_t *geoms_out_host)
 try {
-    const char *who = "y3_tile_letterbox_geometry_hw";
-    if (!descs_host || !geoms_out_host || n_tiles < 1 || canvas_h <= 0 || canvas_w <= 0)
-        return fail(Y3_ERR_INVALID, "%s: bad argument (null pointer, n_tiles < 1 or canvas <= 0)", who);
-    for (int i = 0; i < n_tiles; ++i)
-        if (y3_status st = tile_window_ok(who, i, descs_host[i]); st != Y3_OK) return st;
-    for (int i = 0; i < n_tiles; ++i) {
-        const y3::LetterboxGeom g = image_geom(descs_host[i].mode, descs_host[i].ch, descs_host[i].cw, canvas_h, canvas_w);
-        memcpy(geoms_out_host + (size_t)i * 4, &g, sizeof(g));
-    }
-    return Y3_OK;
+    return view_geometries("y3_tile_letterbox_geometry_hw", "tile", descs_host, n_tiles, canvas_h, canvas_w, geoms_out_host);
 }
 Y3_CATCH("y3_tile_letterbox_geometry_hw")
 
@@ -397,7 +366,7 @@ try {
         if (h < 1 || w < 1) return fail(Y3_ERR_INVALID, "%s: frame %d: height and width must be at least 1 (got %d x %d)", who, f, h, w);
         for (int t = 0; t < tiles; ++t) {
             const int32_t *win = tiles_host + ((size_t)f * tiles + t) * 4;
-            if (win[2] < 1 || win[3] < 1 || win[0] < 0 || win[1] < 0 || win[0] > h - win[2] || win[1] > w - win[3])
+            if (!window_in_frame(win[0], win[1], win[2], win[3], h, w))
                 return fail(Y3_ERR_INVALID, "%s: frame %d, tile %d: window %d x %d at (%d, %d) does not lie inside the %d x %d frame", who, f, t,
                             win[2], win[3], win[0], win[1], h, w);
             y3::LetterboxGeom g;

@@ -156,23 +156,45 @@ def pack_images(images, mode, out: Optional[np.ndarray] = None, letterbox=False)
     return out[:total], descs
 
 
-def _descs_arg(descs):
-    if not isinstance(descs, np.ndarray) or descs.dtype != IMAGE_DESC_DTYPE or descs.ndim != 1:
-        raise Y3Error("descs must be the descriptor array of pack_images")
+# The two kinds of descriptor array: (dtype, ctypes struct, what the array is called in messages)
+_IMAGES = (IMAGE_DESC_DTYPE, _lib.ImageDesc, "the descriptor array of pack_images")
+
+
+def _descs_ptr(descs, kind):
+    dtype, ctype, what = kind
+    if not isinstance(descs, np.ndarray) or descs.dtype != dtype or descs.ndim != 1:
+        raise Y3Error(f"descs must be {what}")
     d = np.ascontiguousarray(descs)
-    return d, d.ctypes.data_as(C.POINTER(_lib.ImageDesc))
+    return d, d.ctypes.data_as(C.POINTER(ctype))
+
+
+def _geometries(descs, image_size, kind, entry, name):
+    d, d_ptr = _descs_ptr(descs, kind)
+    geoms = np.empty((len(d), 4), np.int32)
+    Hc, Wc = canvas_hw(image_size)
+    check(getattr(_lib.load(), entry)(d_ptr, len(d), Hc, Wc, geoms.ctypes.data_as(C.POINTER(C.c_int32))), name)
+    return geoms
+
+
+def _preprocess(blob_dev, descs, batch, first_slot, kind, entry, name):
+    _need_cuda(blob_dev, batch)
+    if blob_dev.dtype != torch.uint8 or blob_dev.dim() != 1:
+        raise Y3Error("blob_dev must be a 1-D uint8 tensor")
+    d, d_ptr = _descs_ptr(descs, kind)
+    if batch.dtype != torch.float32 or batch.dim() != 4 or batch.shape[3] != 3:
+        raise Y3Error("batch must be float32 [B,Hc,Wc,3]")
+    if not (0 <= first_slot and first_slot + len(descs) <= batch.shape[0]):
+        raise Y3Error(f"slots {first_slot}..{first_slot + len(descs) - 1} are outside the batch of {batch.shape[0]}")
+    check(getattr(_lib.load(), entry)(_dev(blob_dev), blob_dev.numel(), d_ptr, len(d), _dev(batch), int(first_slot),
+                                      batch.shape[1], batch.shape[2], _lib.stream_ptr()), name)
+    return batch
 
 
 def letterbox_geometries(descs: np.ndarray, image_size) -> np.ndarray:
     """The descriptor array of pack_images -> int32 [n,4] (sh, sw, top, left): where each image lies on the
     canvas (image_size: an int S or an (H, W) pair), the whole canvas (H, W, 0, 0) for an image without the letterbox flag.  One host call for the whole batch
     (y3_letterbox_geometry; no GPU needed); the rows unletterbox_detections takes."""
-    d, d_ptr = _descs_arg(descs)
-    geoms = np.empty((len(d), 4), np.int32)
-    Hc, Wc = canvas_hw(image_size)
-    check(_lib.load().y3_letterbox_geometry_hw(d_ptr, len(d), Hc, Wc, geoms.ctypes.data_as(C.POINTER(C.c_int32))),
-          "y3_letterbox_geometry")
-    return geoms
+    return _geometries(descs, image_size, _IMAGES, "y3_letterbox_geometry_hw", "y3_letterbox_geometry")
 
 
 def unletterbox_detections(packed: torch.Tensor, num_valid: torch.Tensor, geoms, image_size):
@@ -196,19 +218,9 @@ def unletterbox_detections(packed: torch.Tensor, num_valid: torch.Tensor, geoms,
 
 
 def preprocess_batch(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Tensor, first_slot: int = 0):
-    """The pixel blob of pack_images on the GPU (1-D uint8) -> batch[first_slot + i] for image i, one launch per 64
+    """The pixel blob of pack_images on the GPU (1-D uint8) -> batch[first_slot + i] for image i, one launch per 72
     images (y3_preprocess_batch); every slot has the bits preprocess_image gives for the same image."""
-    _need_cuda(blob_dev, batch)
-    if blob_dev.dtype != torch.uint8 or blob_dev.dim() != 1:
-        raise Y3Error("blob_dev must be a 1-D uint8 tensor")
-    d, d_ptr = _descs_arg(descs)
-    if batch.dtype != torch.float32 or batch.dim() != 4 or batch.shape[3] != 3:
-        raise Y3Error("batch must be float32 [B,Hc,Wc,3]")
-    if not (0 <= first_slot and first_slot + len(descs) <= batch.shape[0]):
-        raise Y3Error(f"slots {first_slot}..{first_slot + len(descs) - 1} are outside the batch of {batch.shape[0]}")
-    check(_lib.load().y3_preprocess_batch_hw(_dev(blob_dev), blob_dev.numel(), d_ptr, len(d), _dev(batch), int(first_slot),
-                                             batch.shape[1], batch.shape[2], _lib.stream_ptr()), "y3_preprocess_batch")
-    return batch
+    return _preprocess(blob_dev, descs, batch, first_slot, _IMAGES, "y3_preprocess_batch_hw", "y3_preprocess_batch")
 
 
 # y3_tile_desc (include/y3.h): a window (y0, x0, ch, cw) of an image of a pixel blob; what tile_descs returns and preprocess_tiles takes
@@ -232,7 +244,7 @@ def tile_descs(images, descs, rows, cols, overlap_px=0, overview=False):
     y3_tile_grid over every image, tile t of image i at index i * T + t.  A tile names its image's pixels in the blob, which
     therefore holds -- and uploads -- every frame once.  images: the list the descriptors were packed from (only its length is
     checked), or None."""
-    d, _ = _descs_arg(descs)
+    d, _ = _descs_ptr(descs, _IMAGES)
     if images is not None and len(images) != len(d):
         raise Y3Error(f"tile_descs: {len(images)} images, {len(d)} descriptors")
     T = int(rows) * int(cols) + (1 if overview else 0)
@@ -251,39 +263,20 @@ def tile_descs(images, descs, rows, cols, overlap_px=0, overview=False):
     return out, windows
 
 
-def _tile_descs_arg(descs):
-    if not isinstance(descs, np.ndarray) or descs.dtype != TILE_DESC_DTYPE or descs.ndim != 1:
-        raise Y3Error("descs must be the tile descriptor array of tile_descs")
-    d = np.ascontiguousarray(descs)
-    return d, d.ctypes.data_as(C.POINTER(_lib.TileDesc))
+_TILES = (TILE_DESC_DTYPE, _lib.TileDesc, "the tile descriptor array of tile_descs")
 
 
 def tile_letterbox_geometries(descs: np.ndarray, image_size) -> np.ndarray:
     """letterbox_geometries for tile descriptors: int32 [n,4] (sh, sw, top, left) of each window taken as a ch x cw image
     (y3_tile_letterbox_geometry_hw); the rows merge_tile_detections takes."""
-    d, d_ptr = _tile_descs_arg(descs)
-    geoms = np.empty((len(d), 4), np.int32)
-    Hc, Wc = canvas_hw(image_size)
-    check(_lib.load().y3_tile_letterbox_geometry_hw(d_ptr, len(d), Hc, Wc, geoms.ctypes.data_as(C.POINTER(C.c_int32))),
-          "y3_tile_letterbox_geometry")
-    return geoms
+    return _geometries(descs, image_size, _TILES, "y3_tile_letterbox_geometry_hw", "y3_tile_letterbox_geometry")
 
 
 def preprocess_tiles(blob_dev: torch.Tensor, descs: np.ndarray, batch: torch.Tensor, first_slot: int = 0):
     """preprocess_batch for windows: the pixel blob of pack_images on the GPU and the tile descriptors of tile_descs ->
-    batch[first_slot + i] for tile i, one launch per 72 tiles (y3_preprocess_tiles_hw); every slot has the bits preprocess_batch
-    gives for a contiguous copy of the window."""
-    _need_cuda(blob_dev, batch)
-    if blob_dev.dtype != torch.uint8 or blob_dev.dim() != 1:
-        raise Y3Error("blob_dev must be a 1-D uint8 tensor")
-    d, d_ptr = _tile_descs_arg(descs)
-    if batch.dtype != torch.float32 or batch.dim() != 4 or batch.shape[3] != 3:
-        raise Y3Error("batch must be float32 [B,Hc,Wc,3]")
-    if not (0 <= first_slot and first_slot + len(descs) <= batch.shape[0]):
-        raise Y3Error(f"slots {first_slot}..{first_slot + len(descs) - 1} are outside the batch of {batch.shape[0]}")
-    check(_lib.load().y3_preprocess_tiles_hw(_dev(blob_dev), blob_dev.numel(), d_ptr, len(d), _dev(batch), int(first_slot),
-                                             batch.shape[1], batch.shape[2], _lib.stream_ptr()), "y3_preprocess_tiles")
-    return batch
+    batch[first_slot + i] for tile i, one launch per 72 tiles (y3_preprocess_tiles_hw, the same kernel reading the frame with its own
+    row pitch); every slot has the bits preprocess_batch gives for a contiguous copy of the window."""
+    return _preprocess(blob_dev, descs, batch, first_slot, _TILES, "y3_preprocess_tiles_hw", "y3_preprocess_tiles")
 
 
 class StagedBatch:
@@ -349,12 +342,13 @@ class InputStage:
             s.batch.record_stream(self.stream)
         self._next = 0
 
-    def submit(self, images, mode, letterbox=False) -> StagedBatch:
-        return self._submit(images, mode, letterbox, None)
+    def _resize(self, slot, images, descs):
+        """The packed frames of a slot -> (launch, handle): `launch` enqueues their resize into slot.batch on the current stream, and
+        `handle` is what submit returns, its geometry computed here with one host call per batch."""
+        handle = StagedBatch(slot, slot.batch[:len(images)], slot.ready, letterbox_geometries(descs, self.image_size))
+        return (lambda: preprocess_batch(slot.blob_dev, descs, slot.batch, 0)), handle
 
-    def _submit(self, images, mode, letterbox, tiles):
-        """submit; tiles: None, or TiledInputStage's (rows, cols, overlap_px, overview) -- the frames are packed and uploaded in the
-        same way, and the resize reads them window by window."""
+    def submit(self, images, mode, letterbox=False) -> StagedBatch:
         images = list(images)
         if not 1 <= len(images) <= self.max_batch:
             raise Y3Error(f"InputStage.submit: {len(images)} images, the stage holds 1..{self.max_batch}")
@@ -364,28 +358,17 @@ class InputStage:
         if slot.state == "released":
             slot.ready.synchronize()     # the slot's earlier copy has left the pinned blob
         blob, descs = pack_images(images, mode, out=slot.pinned_np, letterbox=letterbox)
-        windows = frame_hw = None
-        if tiles is None:
-            geometry = letterbox_geometries(descs, self.image_size)     # one host call per batch
-        else:       # the frames are packed and uploaded once, exactly as above; only the resize reads them window by window
-            tdescs, windows = tile_descs(images, descs, *tiles)
-            geometry = tile_letterbox_geometries(tdescs, self.image_size)
-            frame_hw = np.stack([descs["height"], descs["width"]], axis=1).astype(np.int32)
+        launch, handle = self._resize(slot, images, descs)
         n = blob.size
         with torch.cuda.stream(self.stream):
             if slot.state == "released":
                 self.stream.wait_event(slot.released)
             slot.blob_dev[:n].copy_(slot.pinned[:n], non_blocking=True)
-            if tiles is None:
-                preprocess_batch(slot.blob_dev, descs, slot.batch, 0)
-            else:
-                preprocess_tiles(slot.blob_dev, tdescs, slot.batch, 0)
+            launch()
             slot.ready.record(self.stream)
         slot.state = "held"
         self._next = (self._next + 1) % self.depth
-        if tiles is None:
-            return StagedBatch(slot, slot.batch[:len(images)], slot.ready, geometry)
-        return StagedTiles(slot, slot.batch[:len(geometry)], slot.ready, geometry, windows, frame_hw)
+        return handle
 
     def release(self, handle: StagedBatch):
         """Call on the consumer's stream after its last use of handle.batch has been enqueued."""
@@ -419,5 +402,9 @@ class TiledInputStage(InputStage):
         self.tiles, self.tiles_per_image = tiles_arg("TiledInputStage", tiles)
         super().__init__(image_size, max_batch, max_blob_bytes, depth)
 
-    def submit(self, images, mode, letterbox=False) -> StagedTiles:
-        return self._submit(images, mode, letterbox, self.tiles)
+    def _resize(self, slot, images, descs):
+        tdescs, windows = tile_descs(images, descs, *self.tiles)
+        geometry = tile_letterbox_geometries(tdescs, self.image_size)
+        frame_hw = np.stack([descs["height"], descs["width"]], axis=1).astype(np.int32)
+        handle = StagedTiles(slot, slot.batch[:len(geometry)], slot.ready, geometry, windows, frame_hw)
+        return (lambda: preprocess_tiles(slot.blob_dev, tdescs, slot.batch, 0)), handle

@@ -127,12 +127,10 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
             picked = ops._nms(decoded[0], decoded[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws,
                               classes=decoded[1] if net.nms_per_class else None)     # the rule y3_net_detect would take
             ops._pack(*decoded, *picked, out=packed_dev[:n])
-        elif tiles is not None:
+        else:       # the tiles' rows go to the merge, an untiled batch's straight into the ring
+            out, out_nv = (tile_packed, tile_nv) if tiles is not None else (packed_dev, nv_dev)
             check(net.lib.y3_net_detect(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
-                                        float(score_threshold), _dev(tile_packed), _dev(tile_nv), sp), "y3_net_detect")
-        else:
-            check(net.lib.y3_net_detect(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
-                                        float(score_threshold), _dev(packed_dev), _dev(nv_dev), sp), "y3_net_detect")
+                                        float(score_threshold), _dev(out), _dev(out_nv), sp), "y3_net_detect")
         stage.release(handle)
         if tiles is not None:
             f = handle.frames

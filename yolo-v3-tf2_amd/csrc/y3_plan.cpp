@@ -302,8 +302,15 @@ try {
     }
     for (int t = 0; t < nt; ++t) {
         net->tbytes[t] = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels * net->telem[t];
-        if (net->tbytes[t] >= 0xFFFFFFF0ull && first[t] >= 0)
-            return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, net->tbytes[t]);
+        // what the launches address (Slice::elem_bytes): a caller-owned fp32 grid and the fp32 image batch of the Cin = 3 layer have 4-byte
+        // elements whatever the plan's format
+        const bool f32 = net->out_slot[t] >= 0 || (t == net->input_tensor && net->tensors[t].channels == 3);
+        const size_t addressed = f32 ? net->tbytes[t] / net->telem[t] * 4 : net->tbytes[t];
+        if (addressed >= 0xFFFFFFF0ull && first[t] >= 0) {
+            net->height = net->width = net->max_batch = 0;      // no plan
+            net->dtype = Y3_DTYPE_F32;
+            return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, addressed);
+        }
     }
     if (y3_status st = place_tensors(net, first, last); st != Y3_OK) return st;
     for (int t = 0; t < nt; ++t) {   // int8 plans: the int8 copies of the tensors that cross the cut, blocks of their own

@@ -519,6 +519,56 @@ enum { Y3_NMS_AGNOSTIC = 0, Y3_NMS_PER_CLASS = 1 };
 y3_status y3_net_set_nms_mode(y3_net *net, int mode);
 int y3_net_get_nms_mode(const y3_net *net);
 
+/* ------------------------------------------------------------------------------------------
+ * Multi-label detections (no reference counterpart; Darknet's detector and the published YOLOv3 protocol): every pair (box n,
+ * class c) with conf[n] * prob[n,c] > score_threshold is a candidate of its own, and the NMS decides between candidates.
+ * bboxes / conf / prob are those of y3_yolo_decode_hw bit for bit (the same per-box body), the score is one fp32 multiply -- the
+ * expression of y3_yolo_decode_scores, so the score of a box's arg-max class is its single-label score bit for bit.  The test is
+ * strict (the complement of the NMS's "scores <= S are masked out"); a NaN score is no candidate; with score_threshold < 0 every
+ * pair with a non-NaN score is one.  The candidates of image b are numbered k = 0, 1, ... in the order (n ascending, c ascending);
+ * that order is part of the rule (the NMS breaks score ties by index) and comes from counts and prefix sums, never from the
+ * arrival order of workgroups or atomics.  totals_dev [batch] int32: the number of candidates of each image, uncapped; the first
+ * min(total, capacity) are stored: cand_boxes_dev [batch,capacity,4] f32 (16-byte aligned) = bboxes[n], cand_cls_dev
+ * [batch,capacity] int64 = c, cand_scores_dev [batch,capacity] f32, cand_src_dev [batch,capacity] int32 = n.  Rows
+ * k >= min(total, capacity) are box (0,0,0,0), score 0, class 0, source 0 (the filler of y3_merge_tile_detections: the padded NMS never
+ * selects such a row).  Every word of the five arrays is written on every call; total[b] > capacity says image b was truncated.
+ * workspace_dev: y3_decode_candidates_workspace_bytes bytes (one int32 per box; 0: bad arguments), 4-byte aligned.
+ * Checked before the first launch -- a refused call enqueues nothing: null pointers; batch, capacity, nclasses >= 1; grids and
+ * cand_boxes 16-byte aligned; batch * capacity and N * nclasses below 2^31; the workspace; 64 * (5 + nclasses) * 4 bytes of LDS
+ * within 160 KB.  Three launches (count, per-image prefix, write); only enqueues: may be captured.
+ * Downstream is what exists: y3_nms_padded_per_class / y3_nms_padded over [batch,capacity], then y3_pack_detections, then
+ * y3_candidate_sources, which rewrites the index word (word 6) of every valid packed row from k to cand_src[b,k] -- a multi-label
+ * row reads {box of n, score[n,c], c, n} and two rows of one image may share n.
+ * ---------------------------------------------------------------------------------------- */
+size_t y3_decode_candidates_workspace_bytes(const int32_t grid_hw[3][2], int batch, int nclasses);
+y3_status y3_yolo_decode_candidates_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
+                                       const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
+                                       int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,
+                                       void *workspace_dev, size_t workspace_bytes, void *stream);
+/* The same rule for callers that hold the decoded tensors, as y3_class_scores is to y3_yolo_decode_scores: bboxes_dev [batch,n,4]
+ * (16-byte aligned), conf_dev [batch,n], probs_dev [batch,n,nclasses] as y3_yolo_decode writes them -> the same five arrays, bit for
+ * bit those of y3_yolo_decode_candidates_hw on the grids they were decoded from.  workspace_dev: batch * n * 4 bytes.  The same
+ * checks before the first launch; only enqueues. */
+y3_status y3_class_candidates(const float *bboxes_dev, const float *conf_dev, const float *probs_dev, int batch, int n, int nclasses,
+                              float score_threshold, int capacity, float *cand_boxes_dev, int64_t *cand_cls_dev, float *cand_scores_dev,
+                              int32_t *cand_src_dev, int32_t *totals_dev, void *workspace_dev, size_t workspace_bytes, void *stream);
+/* packed_dev [batch,max_boxes,7], num_valid_dev [batch] as y3_pack_detections wrote them over [batch,capacity] candidates; an index
+ * word outside [0, capacity) is left alone.  Only enqueues. */
+y3_status y3_candidate_sources(void *packed_dev, const int32_t *num_valid_dev, const int32_t *cand_src_dev, int batch, int capacity,
+                               int max_boxes, void *stream);
+/* y3_net_detect in multi-label mode (off by default; with it off every call enqueues exactly what it enqueued before): y3_net_forward
+ * into the net-owned grid scratch, y3_yolo_decode_candidates_hw, the NMS of the net's mode over [batch,K], y3_pack_detections,
+ * y3_candidate_sources.  capacity 0: K = N of the plan; otherwise 1 <= capacity <= N, so that the candidates and the NMS live in the
+ * scratch y3_net_plan reserves for N boxes (a capacity above the planned N is refused with Y3_ERR_INVALID when y3_net_detect
+ * enqueues).  y3_net_plan always reserves the sources, totals and counts besides, so the switch may be flipped after planning; it is
+ * read when y3_net_detect enqueues, and a captured graph keeps what it was captured with.  Every plan dtype writes fp32 grids, so
+ * every one works.  y3_net_read_multi_label_totals enqueues a copy of the totals of the first `batch` images of the last
+ * multi-label detect enqueued on this plan (Y3_ERR_STATE: none was) into dst_dev [batch] int32, batch <= max_batch; images that detect did not have read 0. */
+y3_status y3_net_set_multi_label(y3_net *net, int on, int capacity);
+int y3_net_get_multi_label(const y3_net *net);
+int y3_net_get_multi_label_capacity(const y3_net *net);
+y3_status y3_net_read_multi_label_totals(y3_net *net, int batch, int32_t *dst_dev, void *stream);
+
 /* Packed detections of letterboxed images -> coordinates of the source frames, in place (no reference counterpart: the
  * reference leaves its boxes on the padded canvas).  packed_dev [batch,max_boxes,7] and num_valid_dev [batch] as written by
  * y3_net_detect / y3_pack_detections; geoms_host [batch][4] = {sh, sw, top, left} as y3_letterbox_geometry gives them, read

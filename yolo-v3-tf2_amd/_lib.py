@@ -181,6 +181,14 @@ SYMBOLS = {
     "y3_nms_padded_per_class": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
     "y3_net_set_nms_mode": (_i, [_vp, _i]),
     "y3_net_get_nms_mode": (_i, [_vp]),
+    "y3_decode_candidates_workspace_bytes": (_sz, [C.POINTER(C.c_int32), _i, _i]),   # grid_hw[3][2] as six int32
+    "y3_yolo_decode_candidates_hw": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "y3_class_candidates": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "y3_candidate_sources": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
+    "y3_net_set_multi_label": (_i, [_vp, _i, _i]),
+    "y3_net_get_multi_label": (_i, [_vp]),
+    "y3_net_get_multi_label_capacity": (_i, [_vp]),
+    "y3_net_read_multi_label_totals": (_i, [_vp, _i, _vp, _vp]),
     "y3_pack_detections": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "y3_crc32c": (C.c_uint32, [_vp, C.c_size_t]),
     "y3_net_forward_decode": (_i, [_vp, _vp, _i, _fp, _vp, _vp, _vp, _vp]),
@@ -223,6 +231,7 @@ def load():
 def _missing(name):
     def stub(*_):
         raise Y3Error(f"{LIB_PATH} (Y3_LIB_PATH) is an older build that does not export {name}")
+    stub.missing = True      # a switch that is off by default reads as off on such a build (Net.multi_label)
     return stub
 
 

@@ -48,6 +48,7 @@ class YoloModel:
         # switches, stem fusion, the calibration file an "i8" plan needs, the dtype (None: fp32).  An entry at its value here is skipped.
         self._deferred = dict(_DEFERRED_DEFAULTS)
         self.nms_per_class = False      # set_nms_per_class: a property of the device net, not one of its methods, so kept beside them
+        self.multi_label, self.multi_label_capacity = False, 0      # set_multi_label: the device net's properties of those names
         self.tiles = None               # set_tiles: (rows, cols, overlap_px, overview), the device net's property of that name
 
     def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, i8_calibration, dtype
@@ -65,6 +66,7 @@ class YoloModel:
                 if arg != _DEFERRED_DEFAULTS[method]:
                     getattr(self._net, method)(arg)
             self._net.nms_per_class = self.nms_per_class
+            self._net.multi_label_capacity, self._net.multi_label = self.multi_label_capacity, self.multi_label
             self._net.tiles = self.tiles
             if self._weights is not None:
                 self._net.load_weights(self._weights)
@@ -106,6 +108,19 @@ class YoloModel:
         self.nms_per_class = bool(on)
         if self._net is not None:
             self._net.nms_per_class = self.nms_per_class
+
+    def set_multi_label(self, on=True, capacity=0):
+        """Multi-label detections (runtime.Net.multi_label / multi_label_capacity; no reference counterpart): every pair (box, class)
+        with conf * prob above the score threshold is a detection of its own, and the NMS of the model's rule decides between them.
+        None or False: one label per box, the default.  capacity: candidate slots per image, 0 = every box of the plan.  The device
+        net's detect / detect_stream / evaluate_stream and both routes of inference.DetectModel follow it."""
+        if on is not None and not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"set_multi_label: a bool or None (got {on!r})")
+        if isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)) or capacity < 0:
+            raise TypeError(f"set_multi_label: capacity must be an int >= 0 (got {capacity!r})")
+        self.multi_label, self.multi_label_capacity = bool(on), int(capacity)
+        if self._net is not None:
+            self._net.multi_label_capacity, self._net.multi_label = self.multi_label_capacity, self.multi_label
 
     def set_tiles(self, rows=None, cols=None, overlap_px=0, overview=False):
         """Sliced inference (runtime.Net.detect_stream / evaluate_stream, tiles=; no reference counterpart): every frame is cut into

@@ -18,6 +18,24 @@ def yolo_nms_per_class(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_thr
     return _yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold, per_class=True)
 
 
+def yolo_nms_multi_label(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold, capacity=0, per_class=True):
+    """Multi-label detections (multilabel.py; no reference counterpart): every pair (box, class) with confidence * class_prob >
+    nms_score_threshold is a candidate of its own (ops.class_candidates; capacity slots per image, 0 = N), and the NMS -- per class by
+    default, the rule the published protocol pairs with it; per_class=False: the class-agnostic rule -- decides between them.  Returns
+    the reference-shaped 5-tuple OVER CANDIDATES: (cand_bboxes [B,K,4], cand_classes [B,K] i64, cand_scores [B,K],
+    selected_indices_padded, num_valid_detections), so that gather_valid_detections_results works unchanged."""
+    from ..ops import _nms, class_candidates
+    from .yolo_decode_layer import _to_device
+    bboxes, confidence, class_probs = (_to_device(t) for t in outputs)
+    bboxes = bboxes.reshape(bboxes.shape[0], -1, 4).contiguous()
+    K = int(capacity) or bboxes.shape[1]
+    cand_bboxes, cand_classes, cand_scores, _, _ = class_candidates(bboxes, confidence.contiguous(), class_probs.contiguous(),
+                                                                     nms_score_threshold, K)
+    selected_indices_padded, num_valid_detections = _nms(cand_bboxes, cand_scores, yolo_max_boxes, nms_iou_threshold, nms_score_threshold,
+                                                         classes=cand_classes if per_class else None)
+    return (cand_bboxes, cand_classes, cand_scores, selected_indices_padded, num_valid_detections)
+
+
 def _yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold, per_class):
     from .yolo_decode_layer import _to_device
     bboxes, confidence, class_probs = (_to_device(t) for t in outputs)

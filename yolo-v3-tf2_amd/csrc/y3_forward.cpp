@@ -616,6 +616,34 @@ try {
     float *boxes = reinterpret_cast<float *>(b + L.boxes), *scores = reinterpret_cast<float *>(b + L.scores);
     int64_t *cls = reinterpret_cast<int64_t *>(b + L.cls);
     int32_t *sel = reinterpret_cast<int32_t *>(b + L.sel);
+    if (net->multi_label) {
+        // Multi-label (include/y3.h, y3_net_set_multi_label): the composed forward into the grid scratch, the candidates over it, then the
+        // NMS, the pack and the source rewrite over [batch, K] candidates -- K <= n, so everything lives where the n boxes would.
+        const int K = net->multi_label_capacity ? net->multi_label_capacity : n;
+        if (K > n) return fail(Y3_ERR_INVALID, "y3_net_detect: multi-label capacity %d exceeds the %d boxes of the plan", K, n);
+        if (net->nms_mode == Y3_NMS_PER_CLASS && !(iou_threshold > 0.0f))   // the NMS's own checks, before the first launch
+            return fail(Y3_ERR_INVALID, "y3_net_detect: iou_threshold must be > 0 with Y3_NMS_PER_CLASS");
+        if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
+            return fail(Y3_ERR_INVALID, "y3_net_detect: iou_threshold <= 0 together with score_threshold < 0 is not supported");
+        float *grids[3] = {reinterpret_cast<float *>(b + L.grid[0]), reinterpret_cast<float *>(b + L.grid[1]), reinterpret_cast<float *>(b + L.grid[2])};
+        int32_t *src = reinterpret_cast<int32_t *>(b + L.cand_src), *totals = reinterpret_cast<int32_t *>(b + L.totals);
+        Forward f{images_dev, grids, batch, (hipStream_t)stream, net->lanes};
+        if (st = run(net, f); st != Y3_OK) return st;
+        net->multi_label_batch = batch;
+        st = y3::decode_candidates_hw("y3_net_detect", grids, L.gs, batch, net->nclasses, anchors_host, score_threshold, K, boxes, cls, scores, src,
+                                      totals, b + L.cand_ws, L.cand_ws_bytes, stream);
+        if (st != Y3_OK) return st;
+        if (net->nms_mode == Y3_NMS_PER_CLASS)
+            st = y3_nms_padded_per_class(boxes, scores, cls, batch, K, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
+                                         b + L.nms_ws, L.nms_bytes, stream);
+        else
+            st = y3_nms_padded(boxes, scores, batch, K, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev, b + L.nms_ws,
+                               L.nms_bytes, stream);
+        if (st != Y3_OK) return st;
+        st = y3_pack_detections(boxes, cls, scores, sel, num_valid_dev, batch, K, max_boxes, packed_dev, stream);
+        if (st != Y3_OK) return st;
+        return y3_candidate_sources(packed_dev, num_valid_dev, src, batch, K, max_boxes, stream);
+    }
     // conv program with the head convs decoding their own tiles (grids neither written nor read back) where the graph allows it.
     // (Round 5 ran NMS + pack per lane, on each lane's stream behind its last conv: bit-identical and 0.2 % slower under graph replay -- the NMS
     // workgroups take CUs from the other lane's last convs; profiles/r05_ab_bf16_lane_nms.txt.  Batch-wide launches behind the join again.)

@@ -130,6 +130,9 @@ struct y3_net {
     void *det_buf = nullptr;
     size_t det_bytes = 0;
     int nms_mode = 0;              // y3_net_set_nms_mode: Y3_NMS_AGNOSTIC / Y3_NMS_PER_CLASS, read by y3_net_detect when it enqueues
+    int multi_label = 0;           // y3_net_set_multi_label: y3_net_detect enqueues the candidates route; read when it enqueues
+    int multi_label_capacity = 0;  // ... with this many candidate slots per image, 0: N of the plan
+    int multi_label_batch = 0;     // images of the last multi-label detect enqueued on this plan (where its totals lie: detect_layout of that batch)
     int stem_mode = 1;             // y3_net_set_stem_fusion: 1 = conv0 + conv1 (+ the 1x1 after them) as one kernel when the graph allows it; 2 = conv0 + conv1 only
     bool stem_mode_set = false;    // y3_net_set_stem_fusion was called (the Y3_STEM_MODE tool override then stays out)
     int stem_mode_f16 = 0;         // y3_net_set_stem_fusion_f16: the same three values for Y3_DTYPE_F16 plans, which stem_mode does not act on; off by default
@@ -257,11 +260,20 @@ struct DetectLayout {
     int32_t gs[3][2];
     size_t n_boxes;
     size_t grid[3], boxes, cls, scores, sel, nms_ws, total;
+    // behind the NMS workspace (nms_bytes of it), the multi-label route's own parts: candidate sources [batch,N] i32, totals [batch] i32,
+    // and the per-box counts of y3_yolo_decode_candidates_hw (cand_ws_bytes).  Its candidates lie in boxes / cls / scores (capacity <= N).
+    size_t nms_bytes, cand_src, totals, cand_ws, cand_ws_bytes;
 };
 DetectLayout detect_layout(const y3_net *net, int batch);
 
 // y3_yolo_decode_scores_hw under the caller's name `who`
 y3_status decode_scores_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
                            const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream);
+
+// y3_yolo_decode_candidates_hw under the caller's name `who`
+y3_status decode_candidates_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+                               const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev, int64_t *cand_cls_dev,
+                               float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev, void *workspace_dev, size_t workspace_bytes,
+                               void *stream);
 
 }  // namespace y3

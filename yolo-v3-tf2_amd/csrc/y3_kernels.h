@@ -281,6 +281,16 @@ hipError_t launch_decode(const DecodeArgs &a, float *bboxes, float *conf, float 
                          float *scores, hipStream_t s);
 hipError_t launch_class_scores(const float *conf, const float *probs, size_t n, int nc, int64_t *cls,
                                float *scores, hipStream_t s);
+// Multi-label candidates (candidates.hip; include/y3.h, y3_yolo_decode_candidates_hw): count, per-image prefix, write.  counts: [B,N] i32 scratch.
+size_t candidates_lds_bytes(int nc);
+hipError_t launch_candidates(const DecodeArgs &a, float S, int K, float *cand_boxes, int64_t *cand_cls, float *cand_scores,
+                             int32_t *cand_src, int32_t *totals, int32_t *counts, hipStream_t s);
+// ... from decoded tensors: bboxes [B,N,4], conf [B,N], probs [B,N,nc]
+hipError_t launch_class_candidates(const float *bboxes, const float *conf, const float *probs, int B, int N, int nc, float S, int K,
+                                   float *cand_boxes, int64_t *cand_cls, float *cand_scores, int32_t *cand_src, int32_t *totals,
+                                   int32_t *counts, hipStream_t s);
+// word 6 of every valid packed row: candidate k -> cand_src[b, k]
+hipError_t launch_candidate_sources(void *packed, const int32_t *nv, const int32_t *cand_src, int B, int K, int M, hipStream_t s);
 
 // Letterbox geometry (include/y3.h, Y3_IMAGE_LETTERBOX): the aspect-preserving resize is to sh x sw, placed at (top, left) of
 // the Hc x Wc canvas (square entry points: Hc = Wc = S).  Layout of the int32[4] rows of y3_letterbox_geometry / y3_unletterbox_detections.

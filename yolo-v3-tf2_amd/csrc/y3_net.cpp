@@ -1070,6 +1070,37 @@ Y3_CATCH("y3_net_set_nms_mode")
 
 int y3_net_get_nms_mode(const y3_net *net) { return net ? net->nms_mode : Y3_NMS_AGNOSTIC; }
 
+y3_status y3_net_set_multi_label(y3_net *net, int on, int capacity)
+try {
+    if (!net || capacity < 0)
+        return fail(Y3_ERR_INVALID, "y3_net_set_multi_label: null net or capacity < 0 (0: N of the plan; otherwise 1 <= capacity <= N, checked when y3_net_detect enqueues)");
+    net->multi_label = on != 0;
+    net->multi_label_capacity = capacity;
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_multi_label")
+
+int y3_net_get_multi_label(const y3_net *net) { return net ? net->multi_label : 0; }
+int y3_net_get_multi_label_capacity(const y3_net *net) { return net ? net->multi_label_capacity : 0; }
+
+y3_status y3_net_read_multi_label_totals(y3_net *net, int batch, int32_t *dst_dev, void *stream)
+try {
+    if (!net || !dst_dev || batch < 1) return fail(Y3_ERR_INVALID, "y3_net_read_multi_label_totals: bad argument");
+    if (!net->height || net->nclasses <= 0 || net->multi_label_batch < 1)
+        return fail(Y3_ERR_STATE, "y3_net_read_multi_label_totals: no multi-label y3_net_detect was enqueued on this plan");
+    if (batch > net->max_batch) return fail(Y3_ERR_INVALID, "y3_net_read_multi_label_totals: batch %d > planned %d", batch, net->max_batch);
+    const y3::DetectLayout L = y3::detect_layout(net, net->multi_label_batch);
+    if (!net->det_buf || net->det_bytes < L.total)
+        return fail(Y3_ERR_STATE, "y3_net_read_multi_label_totals: detect scratch not planned (y3_net_plan allocates it)");
+    Y3_ENTER_DEVICE(net);
+    const int have = batch < net->multi_label_batch ? batch : net->multi_label_batch;   // images that detect did not have read 0
+    HIP_TRY(hipMemcpyAsync(dst_dev, static_cast<char *>(net->det_buf) + L.totals, (size_t)have * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                           (hipStream_t)stream));
+    if (batch > have) HIP_TRY(hipMemsetAsync(dst_dev + have, 0, (size_t)(batch - have) * sizeof(int32_t), (hipStream_t)stream));
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_read_multi_label_totals")
+
 y3_status y3_net_set_early_chunk(y3_net *net, int n_convs, int chunk_images)
 try {
     if (!net || n_convs < 0 || chunk_images < 0) return fail(Y3_ERR_INVALID, "y3_net_set_early_chunk: bad argument");

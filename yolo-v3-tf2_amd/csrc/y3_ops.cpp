@@ -119,11 +119,11 @@ y3_status view_geometries(const char *who, const char *noun, const Desc *descs_h
 
 // ------------------------------------------------------------------------------------------ decode
 // gs: grid_hw[3][2] = {gh, gw} per scale (the square entry points hand {g, g})
-static y3_status decode_common(const float *const grids[3], const int32_t (*gs)[2], int batch, int nc,
-                               const float *anchors, float *bboxes, float *conf, float *probs, int64_t *cls,
-                               float *scores, void *stream, const char *who)
+// The checks every decode entry shares, and the by-value arguments of its launch: grid sizes, first box of each scale, anchors
+static y3_status decode_args(const float *const grids[3], const int32_t (*gs)[2], int batch, int nc, const float *anchors, const char *who,
+                             y3::DecodeArgs *out)
 {
-    if (!grids || !gs || !anchors || !bboxes || batch <= 0 || nc <= 0) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
+    if (!grids || !gs || !anchors || batch <= 0 || nc <= 0) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
     y3::DecodeArgs a{};
     int off = 0;
     for (int s = 0; s < 3; ++s) {
@@ -139,11 +139,63 @@ static y3_status decode_common(const float *const grids[3], const int32_t (*gs)[
             a.anchors[s][k][1] = anchors[(s * 3 + k) * 2 + 1];
         }
     }
-    if ((uintptr_t)bboxes & 15) return fail(Y3_ERR_INVALID, "%s: bboxes not 16-byte aligned", who);
     a.B = batch;
     a.N = off;
     a.nc = nc;
+    *out = a;
+    return Y3_OK;
+}
+
+static y3_status decode_common(const float *const grids[3], const int32_t (*gs)[2], int batch, int nc,
+                               const float *anchors, float *bboxes, float *conf, float *probs, int64_t *cls,
+                               float *scores, void *stream, const char *who)
+{
+    if (!bboxes) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
+    y3::DecodeArgs a{};
+    if (y3_status st = decode_args(grids, gs, batch, nc, anchors, who, &a); st != Y3_OK) return st;
+    if ((uintptr_t)bboxes & 15) return fail(Y3_ERR_INVALID, "%s: bboxes not 16-byte aligned", who);
     hipError_t e = y3::launch_decode(a, bboxes, conf, probs, cls, scores, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}
+
+// boxes per image of the three grids, 0 when a side is < 1 or the count leaves an int
+static long long grid_boxes(const int32_t (*gs)[2])
+{
+    long long n = 0;
+    for (int s = 0; s < 3; ++s) {
+        if (gs[s][0] <= 0 || gs[s][1] <= 0) return 0;
+        n += 3ll * gs[s][0] * gs[s][1];
+    }
+    return n <= 0x7fffffffll ? n : 0;
+}
+
+y3_status y3::decode_candidates_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+                                   const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
+                                   int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,
+                                   void *workspace_dev, size_t workspace_bytes, void *stream)
+{
+    if (!grids_dev || !grid_hw || !anchors_host || !cand_boxes_dev || !cand_cls_dev || !cand_scores_dev || !cand_src_dev || !totals_dev)
+        return fail(Y3_ERR_INVALID, "%s: null pointer", who);
+    if (batch < 1 || capacity < 1 || nclasses < 1)
+        return fail(Y3_ERR_INVALID, "%s: batch, capacity and nclasses must be at least 1 (got %d, %d, %d)", who, batch, capacity, nclasses);
+    const long long N = grid_boxes(grid_hw);
+    if (N <= 0) return fail(Y3_ERR_INVALID, "%s: grid sides must be at least 1 and the boxes per image below 2^31", who);
+    if ((long long)batch * capacity > 0x7fffffffll || N * nclasses > 0x7fffffffll || (long long)batch * N > 0x7fffffffll)
+        return fail(Y3_ERR_INVALID, "%s: batch * capacity, N * nclasses and batch * N must stay below 2^31 (got %d x %d, %lld x %d)", who, batch,
+                    capacity, N, nclasses);
+    if (y3::candidates_lds_bytes(nclasses) > 160 * 1024)
+        return fail(Y3_ERR_INVALID, "%s: %d classes need %zu bytes of LDS, at most %d", who, nclasses, y3::candidates_lds_bytes(nclasses), 160 * 1024);
+    y3::DecodeArgs a{};
+    if (y3_status st = decode_args(grids_dev, grid_hw, batch, nclasses, anchors_host, who, &a); st != Y3_OK) return st;
+    if ((uintptr_t)cand_boxes_dev & 15) return fail(Y3_ERR_INVALID, "%s: cand_boxes not 16-byte aligned", who);
+    if (((uintptr_t)cand_cls_dev & 7) || ((uintptr_t)cand_scores_dev & 3) || ((uintptr_t)cand_src_dev & 3) || ((uintptr_t)totals_dev & 3))
+        return fail(Y3_ERR_INVALID, "%s: cand_cls not 8-byte or cand_scores / cand_src / totals not 4-byte aligned", who);
+    const size_t need = (size_t)batch * (size_t)N * sizeof(int32_t);
+    if (!workspace_dev || workspace_bytes < need || ((uintptr_t)workspace_dev & 3))
+        return fail(Y3_ERR_INVALID, "%s: workspace too small or not 4-byte aligned (need %zu bytes)", who, need);
+    hipError_t e = y3::launch_candidates(a, score_threshold, capacity, cand_boxes_dev, cand_cls_dev, cand_scores_dev, cand_src_dev, totals_dev,
+                                         static_cast<int32_t *>(workspace_dev), (hipStream_t)stream);
     if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
     return Y3_OK;
 }
@@ -609,6 +661,64 @@ try {
     return y3::decode_scores_hw("y3_yolo_decode_scores", grids_dev, hw, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
 }
 Y3_CATCH("y3_yolo_decode_scores")
+
+size_t y3_decode_candidates_workspace_bytes(const int32_t grid_hw[3][2], int batch, int nclasses)
+{
+    if (!grid_hw || batch < 1 || nclasses < 1) return 0;
+    const long long N = grid_boxes(grid_hw);
+    if (N <= 0 || (long long)batch * N > 0x7fffffffll) return 0;
+    return (size_t)batch * (size_t)N * sizeof(int32_t);
+}
+
+y3_status y3_yolo_decode_candidates_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
+                                       const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
+                                       int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,
+                                       void *workspace_dev, size_t workspace_bytes, void *stream)
+try {
+    return y3::decode_candidates_hw("y3_yolo_decode_candidates_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, score_threshold, capacity,
+                                    cand_boxes_dev, cand_cls_dev, cand_scores_dev, cand_src_dev, totals_dev, workspace_dev, workspace_bytes, stream);
+}
+Y3_CATCH("y3_yolo_decode_candidates_hw")
+
+y3_status y3_class_candidates(const float *bboxes_dev, const float *conf_dev, const float *probs_dev, int batch, int n, int nclasses,
+                              float score_threshold, int capacity, float *cand_boxes_dev, int64_t *cand_cls_dev, float *cand_scores_dev,
+                              int32_t *cand_src_dev, int32_t *totals_dev, void *workspace_dev, size_t workspace_bytes, void *stream)
+try {
+    const char *who = "y3_class_candidates";
+    if (!bboxes_dev || !conf_dev || !probs_dev || !cand_boxes_dev || !cand_cls_dev || !cand_scores_dev || !cand_src_dev || !totals_dev)
+        return fail(Y3_ERR_INVALID, "%s: null pointer", who);
+    if (batch < 1 || n < 1 || capacity < 1 || nclasses < 1)
+        return fail(Y3_ERR_INVALID, "%s: batch, n, capacity and nclasses must be at least 1 (got %d, %d, %d, %d)", who, batch, n, capacity, nclasses);
+    if ((long long)batch * capacity > 0x7fffffffll || (long long)n * nclasses > 0x7fffffffll || (long long)batch * n > 0x7fffffffll)
+        return fail(Y3_ERR_INVALID, "%s: batch * capacity, n * nclasses and batch * n must stay below 2^31", who);
+    if (((uintptr_t)bboxes_dev & 15) || ((uintptr_t)cand_boxes_dev & 15)) return fail(Y3_ERR_INVALID, "%s: bboxes / cand_boxes not 16-byte aligned", who);
+    if (((uintptr_t)cand_cls_dev & 7) || ((uintptr_t)conf_dev & 3) || ((uintptr_t)probs_dev & 3) || ((uintptr_t)cand_scores_dev & 3) ||
+        ((uintptr_t)cand_src_dev & 3) || ((uintptr_t)totals_dev & 3))
+        return fail(Y3_ERR_INVALID, "%s: cand_cls not 8-byte or a float / int32 pointer not 4-byte aligned", who);
+    const size_t need = (size_t)batch * (size_t)n * sizeof(int32_t);
+    if (!workspace_dev || workspace_bytes < need || ((uintptr_t)workspace_dev & 3))
+        return fail(Y3_ERR_INVALID, "%s: workspace too small or not 4-byte aligned (need %zu bytes)", who, need);
+    hipError_t e = y3::launch_class_candidates(bboxes_dev, conf_dev, probs_dev, batch, n, nclasses, score_threshold, capacity, cand_boxes_dev,
+                                               cand_cls_dev, cand_scores_dev, cand_src_dev, totals_dev, static_cast<int32_t *>(workspace_dev),
+                                               (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_class_candidates")
+
+y3_status y3_candidate_sources(void *packed_dev, const int32_t *num_valid_dev, const int32_t *cand_src_dev, int batch, int capacity,
+                               int max_boxes, void *stream)
+try {
+    if (!packed_dev || !num_valid_dev || !cand_src_dev) return fail(Y3_ERR_INVALID, "y3_candidate_sources: null pointer");
+    if (batch < 1 || capacity < 1 || max_boxes < 1 || (long long)batch * capacity > 0x7fffffffll || (long long)batch * max_boxes > 0x7fffffffll)
+        return fail(Y3_ERR_INVALID, "y3_candidate_sources: batch, capacity and max_boxes must be at least 1, batch * capacity and batch * max_boxes below 2^31");
+    if (((uintptr_t)packed_dev & 3) || ((uintptr_t)num_valid_dev & 3) || ((uintptr_t)cand_src_dev & 3))
+        return fail(Y3_ERR_INVALID, "y3_candidate_sources: a device pointer is not 4-byte aligned");
+    hipError_t e = y3::launch_candidate_sources(packed_dev, num_valid_dev, cand_src_dev, batch, capacity, max_boxes, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_candidate_sources launch: %s", hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_candidate_sources")
 
 y3_status y3_class_scores(const float *conf_dev, const float *probs_dev, int batch, int n, int nclasses,
                           int64_t *class_idx_dev, float *scores_dev, void *stream)

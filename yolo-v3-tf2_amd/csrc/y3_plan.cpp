@@ -223,7 +223,13 @@ y3::DetectLayout y3::detect_layout(const y3_net *net, int batch)
     L.scores = L.cls + up((size_t)batch * n * 8);
     L.sel = L.scores + up((size_t)batch * n * 4);       // selected indices
     L.nms_ws = L.sel + up((size_t)batch * Y3_MAX_OUTPUT_BOXES * 4);
-    L.total = L.nms_ws + nms_per_class_workspace_bytes(batch, (int)n);   // the larger of the two: the NMS mode may be switched after planning
+    L.nms_bytes = nms_per_class_workspace_bytes(batch, (int)n);   // the larger of the two: the NMS mode may be switched after planning
+    // always reserved: the multi-label switch may be flipped after planning as well
+    L.cand_src = L.nms_ws + up(L.nms_bytes);
+    L.totals = L.cand_src + up((size_t)batch * n * 4);
+    L.cand_ws = L.totals + up((size_t)batch * 4);
+    L.cand_ws_bytes = (size_t)batch * n * 4;
+    L.total = L.cand_ws + L.cand_ws_bytes;
     return L;
 }
 
@@ -348,6 +354,7 @@ try {
             return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) for the detect scratch failed: %s", bytes, hipGetErrorString(e));
         }
         net->det_bytes = bytes;
+        net->multi_label_batch = 0;   // no multi-label detect has written totals into this scratch
     }
     if (y3_status st = y3::resolve_splits(net); st != Y3_OK) {
         y3::free_plan(net);

@@ -96,7 +96,7 @@ def report_ap(ap, iou_thresholds):
 
 
 def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_batches, weights, one_class, anchors_table, nclasses,
-                        loss=False, ap=None, nms_per_class=False, tiles=None):
+                        loss=False, ap=None, nms_per_class=False, tiles=None, multi_label=False, multi_label_capacity=0):
     """One model and one pass: the un-stacked data set is batched here (images with unlike numbers of boxes may share a batch)
     by a generator that Net.evaluate_stream draws from, so records are decoded while earlier batches run and the data set is
     never held in memory; only the counters come back."""
@@ -111,6 +111,7 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     model.model.set_dtype(detect_config.get("dtype"))     # optional key: f32 | bf16 | f16 | i8; absent: f32
     model.model.set_stem_fusion_f16(detect_config.get("f16_fused_stem"))   # optional key, acts on dtype f16 only; absent: off
     model.model.set_nms_per_class(nms_per_class)          # the device net's detect, and the composed route of loss=True, follow it
+    model.model.set_multi_label(multi_label, multi_label_capacity)   # multi-label detections: the device net's streams follow it
     model.model.set_tiles(*(tiles or (None,)))            # sliced inference: the device net's streams follow it
     net = model.model._device_net()
     if net.image_size != S or net.max_batch < batch_size:
@@ -168,7 +169,8 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
 
 
 def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshold=0.5, max_batches=20, weights=None,
-             one_class=True, on_device=False, loss=False, ap=None, nms_per_class=False, tiles=None):
+             one_class=True, on_device=False, loss=False, ap=None, nms_per_class=False, tiles=None, multi_label=False,
+             multi_label_capacity=0):
     """The loop of reference evaluate_yolov3.py:153-232: for every score threshold build the detect model, run the
     first `max_batches` dataset batches (`dataset.take(20)` there), count, and report (recall, precision).
     Returns [(threshold, recall, precision, counters, counters_oneclass)].
@@ -195,8 +197,19 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     `tile_overview` of detect_config: sliced inference (Net.evaluate_stream, tiles=) -- every record, resized to image_size on the host as
     before, is cut into windows on the device, each window is detected at image_size and the windows' detections are merged by a second
     NMS; the counters and the AP are taken on the merged rows.  One pass still serves every threshold ("Sliced inference").
-    Not together with loss=True."""
+    Not together with loss=True.
+    multi_label=True (with on_device=True), or the optional key `multi_label: true` of detect_config; multi_label_capacity / the key of
+    that name: the candidate slots per image, 0 = every box.  Multi-label detections (Net.multi_label; no reference counterpart): every
+    pair (box, class) with conf * prob above the score threshold is a detection of its own, as Darknet's detector and the published
+    YOLOv3 protocol have it.  One pass still serves every threshold unless an image has more candidates than the capacity at the lowest
+    threshold; Net.evaluate_stream raises then.  The host route refuses the key: its per-threshold loop has no multi-label form."""
     from .inference import Inference
+    multi_label = bool(multi_label or detect_config.get("multi_label"))
+    multi_label_capacity = int(multi_label_capacity or detect_config.get("multi_label_capacity") or 0)
+    if multi_label and not on_device:
+        raise ValueError("evaluate: multi_label needs on_device=True (the candidates are formed on the GPU, in the device pass)")
+    if multi_label_capacity and not multi_label:
+        raise ValueError("evaluate: multi_label_capacity needs multi_label")
     tiles = tiles or Inference.tiles_from_config(detect_config)
     if tiles is not None and not on_device:
         raise ValueError("evaluate: tiles need on_device=True (the windows are cut and merged on the GPU, in the device pass)")
@@ -213,7 +226,8 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     nms_per_class = bool(nms_per_class or detect_config.get("nms_per_class"))
     if on_device:
         return _evaluate_on_device(detect_config, list(evaluate_nms_score_thresholds), evaluate_iou_threshold, max_batches, weights,
-                                   one_class, anchors_table, nclasses, loss=loss, ap=ap, nms_per_class=nms_per_class, tiles=tiles)
+                                   one_class, anchors_table, nclasses, loss=loss, ap=ap, nms_per_class=nms_per_class, tiles=tiles,
+                                   multi_label=multi_label, multi_label_capacity=multi_label_capacity)
     dataset = prepare_dataset(detect_config["tfrecords_dir"], detect_config["batch_size"], detect_config["image_size"],
                               detect_config["yolo_max_boxes"], detect_config["classes_name_file"])
     results = []
@@ -256,6 +270,11 @@ def _arg_parser():
     ap.add_argument("--nms-per-class", action="store_true",
                     help="per-class NMS: a box is suppressed only by a kept box of its own class (also the optional nms_per_class "
                          "key of either config; absent: the reference's class-agnostic rule)")
+    ap.add_argument("--multi-label", action="store_true",
+                    help="with --on-device: every (box, class) pair above the score threshold is a detection of its own (also the optional "
+                         "multi_label key of either config; absent: one label per box)")
+    ap.add_argument("--multi-label-capacity", type=int, default=0, metavar="K",
+                    help="with --multi-label: candidate slots per image (also the optional multi_label_capacity key); 0: every box")
     ap.add_argument("--tiles", type=int, nargs=2, metavar=("R", "C"),
                     help="with --on-device: sliced inference, every frame cut into R x C overlapping windows that are detected at full "
                          "resolution and merged on the GPU (also the optional tiles / tile_overlap / tile_overview keys of the detect config)")
@@ -273,6 +292,10 @@ def main(argv=None):
         ap.error("--ap needs --on-device")
     if a.tiles and not a.on_device:
         ap.error("--tiles needs --on-device")
+    if a.multi_label and not a.on_device:
+        ap.error("--multi-label needs --on-device")
+    if a.multi_label_capacity and not a.multi_label:
+        ap.error("--multi-label-capacity needs --multi-label")
     if (a.tile_overlap or a.tile_overview) and not a.tiles:
         ap.error("--tile-overlap / --tile-overview need --tiles")
     if a.tiles and a.loss:
@@ -285,7 +308,9 @@ def main(argv=None):
         detect_config = yaml.safe_load(s)
     results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss, ap=ap_thresholds,
                        nms_per_class=a.nms_per_class or bool(evaluate_config.get("nms_per_class")),
-                       tiles=(a.tiles[0], a.tiles[1], a.tile_overlap, a.tile_overview) if a.tiles else None)
+                       tiles=(a.tiles[0], a.tiles[1], a.tile_overlap, a.tile_overview) if a.tiles else None,
+                       multi_label=a.multi_label or bool(evaluate_config.get("multi_label")),
+                       multi_label_capacity=a.multi_label_capacity or int(evaluate_config.get("multi_label_capacity") or 0))
     if a.loss or a.ap:
         results = results[0]      # the loss and the AP have been printed by evaluate
     print([(t, float(r.mean()), float(p.mean())) for t, r, p, _, _ in results])

@@ -40,6 +40,9 @@ class DetectModel:
         """images: [B,S,S,3] fp32 (numpy or CUDA tensor) -> the 5-tuple as CUDA tensors."""
         grids = self.model(images)
         per_class = bool(getattr(self.model, "nms_per_class", False))      # the model's switch (set_nms_per_class), read per call
+        multi = bool(getattr(self.model, "multi_label", False))            # the model's switch (set_multi_label), read per call
+        if multi and self.fused:
+            return self._multi_label(grids, per_class)
         if self.fused:
             from . import ops, runtime
             bboxes, cls, scores = runtime.yolo_decode_scores(grids, self.anchors_table, self.nclasses)
@@ -53,7 +56,20 @@ class DetectModel:
         from .core.yolo_decode_layer import yolo_decode
         decoded_output = yolo_decode(grids, self.anchors_table, self.nclasses)      # reference: inference.py:111
         self.nms_layer.per_class = per_class
+        self.nms_layer.multi_label, self.nms_layer.multi_label_capacity = multi, int(getattr(self.model, "multi_label_capacity", 0))
         return self.nms_layer(decoded_output)                                        # reference: inference.py:114-115
+
+    def _multi_label(self, grids, per_class):
+        """The 5-tuple OVER CANDIDATES (multilabel.py): every pair (box, class) above the score threshold is a candidate of its own ->
+        (cand_bboxes [B,K,4], cand_classes [B,K] i64, cand_scores [B,K], selected_indices_padded, num_valid_detections), so that
+        Inference.gather_valid_detections_results works unchanged.  K: the model's multi_label_capacity, 0 = every box."""
+        from . import ops
+        N = sum(3 * g.shape[1] * g.shape[2] for g in grids)
+        K = int(getattr(self.model, "multi_label_capacity", 0)) or N
+        boxes, cls, scores, _, _ = ops.decode_candidates(grids, self.anchors_table, self.nclasses, self.nms_score_threshold, K)
+        sel, nv = ops._nms(boxes, scores, self.yolo_max_boxes, self.nms_iou_threshold, self.nms_score_threshold,
+                           classes=cls if per_class else None)
+        return boxes, cls, scores, sel, nv
 
     def predict(self, images, **_):
         return tuple(t.cpu().numpy() for t in self(images))
@@ -66,6 +82,10 @@ class Inference:
     # Per-class NMS (core.parse_model.YoloModel.set_nms_per_class; None or False: the reference's class-agnostic rule).  The optional YAML
     # key `nms_per_class` lands here the same way.
     nms_per_class = None
+    # Multi-label detections (core.parse_model.YoloModel.set_multi_label; None or False: one label per box).  The optional YAML keys
+    # `multi_label: true` and `multi_label_capacity: <int>` land here the same way.
+    multi_label = None
+    multi_label_capacity = 0
     # Sliced inference (core.parse_model.YoloModel.set_tiles; None: off): (rows, cols, overlap_px, overview).  The optional YAML keys
     # `tiles: [rows, cols]`, `tile_overlap: <pixels>` and `tile_overview: true|false` land here the same way (tiles_from_config).
     tiles = None
@@ -169,6 +189,7 @@ class Inference:
         model.set_dtype(dtype)
         model.set_stem_fusion_f16(self.f16_fused_stem if f16_fused_stem is None else f16_fused_stem)
         model.set_nms_per_class(self.nms_per_class)
+        model.set_multi_label(self.multi_label, int(self.multi_label_capacity or 0))
         model.set_tiles(*(self.tiles or (None,)))
         print("weights loaded")
         return DetectModel(model, anchors_table, nclasses, yolo_max_boxes, nms_iou_threshold,
@@ -288,6 +309,8 @@ def main(argv=None):
     inference = Inference()
     inference.f16_fused_stem = detect_config.pop("f16_fused_stem", None)    # optional key, absent: off
     inference.nms_per_class = detect_config.pop("nms_per_class", None)      # optional key, absent: off
+    inference.multi_label = detect_config.pop("multi_label", None)          # optional keys, absent: off, every box of the plan
+    inference.multi_label_capacity = detect_config.pop("multi_label_capacity", 0)
     inference.tiles = Inference.tiles_from_config(detect_config, pop=True)  # optional keys tiles / tile_overlap / tile_overview, absent: off
     inference(**detect_config)
 

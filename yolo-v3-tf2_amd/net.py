@@ -143,6 +143,44 @@ class Net:
         check(self.lib.y3_net_set_nms_mode(self._h, _lib.Y3_NMS_PER_CLASS if on else _lib.Y3_NMS_AGNOSTIC), "y3_net_set_nms_mode")
 
     @property
+    def multi_label(self) -> bool:
+        """Multi-label detections in detect, detect_stream and evaluate_stream (y3_net_set_multi_label; no reference counterpart): False
+        (the default), every box carries its arg-max class; True, every pair (box, class) with conf * prob above the score threshold is
+        a detection of its own and the NMS of the net's mode decides between them (multilabel.py restates the rule; `multi_label_capacity`
+        and `multi_label_totals` beside it).  A row then reads {box of n, conf[n] * prob[n,c], c, n} and two rows of an image may share n.
+        Read whenever a detect is enqueued: a captured graph keeps what it was captured with."""
+        get = self.lib.y3_net_get_multi_label
+        return False if getattr(get, "missing", False) else bool(get(self._h))      # an older build under Y3_LIB_PATH has no such route: off
+
+    @multi_label.setter
+    def multi_label(self, on):
+        if not isinstance(on, (bool, np.bool_)):
+            raise TypeError(f"multi_label: a bool (got {on!r})")
+        check(self.lib.y3_net_set_multi_label(self._h, int(on), self.multi_label_capacity), "y3_net_set_multi_label")
+
+    @property
+    def multi_label_capacity(self) -> int:
+        """Candidate slots per image of the multi-label route: 0 (the default), N of the plan; otherwise 1 <= capacity <= N, checked
+        when a detect is enqueued.  An image with more candidates keeps the first `capacity` in (box, class) order; multi_label_totals
+        tells."""
+        return int(self.lib.y3_net_get_multi_label_capacity(self._h))
+
+    @multi_label_capacity.setter
+    def multi_label_capacity(self, capacity):
+        if isinstance(capacity, (bool, np.bool_)) or not isinstance(capacity, (int, np.integer)):
+            raise TypeError(f"multi_label_capacity: an int (got {capacity!r})")
+        check(self.lib.y3_net_set_multi_label(self._h, int(self.multi_label), int(capacity)), "y3_net_set_multi_label")
+
+    @property
+    def multi_label_totals(self) -> torch.Tensor:
+        """[max_batch] int32 on the GPU: the candidates of every image of the last multi-label detect enqueued on this plan, uncapped
+        (0 for images it did not have); total > capacity says the image was truncated.  Enqueues a copy on the current stream."""
+        totals = torch.empty((max(self.max_batch, 1),), dtype=torch.int32, device="cuda")
+        check(self.lib.y3_net_read_multi_label_totals(self._h, totals.shape[0], _dev(totals), _lib.stream_ptr()),
+              "y3_net_read_multi_label_totals")
+        return totals
+
+    @property
     def tiles(self):
         """Sliced inference in detect_stream / evaluate_stream: None (off, the default) or (rows, cols, overlap_px, overview) -- every frame
         is cut into rows x cols windows overlapping by at least overlap_px pixels (y3_tile_grid), plus the whole frame with overview; each

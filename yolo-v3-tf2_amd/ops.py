@@ -63,6 +63,82 @@ def _decode_scores(grids, anchors_table, nclasses, out=None):
     return bboxes, cls, scores
 
 
+def decode_candidates_workspace_bytes(grid_hw, batch: int, nclasses: int) -> int:
+    """y3_decode_candidates_workspace_bytes: grid_hw = three (gh, gw) pairs; 0 for sizes decode_candidates refuses."""
+    gs = (C.c_int32 * 6)(*[int(v) for hw in grid_hw for v in hw])
+    return int(_lib.load().y3_decode_candidates_workspace_bytes(gs, int(batch), int(nclasses)))
+
+
+def decode_candidates(grids, anchors_table, nclasses, score_threshold, capacity, out=None, ws=None):
+    """Multi-label candidates (y3_yolo_decode_candidates_hw; host restatement: multilabel.candidates_ref over yolo_decode's arrays):
+    every pair (box n, class c) with conf[n] * prob[n,c] > score_threshold, numbered per image in the order (n, c) ascending, the
+    first `capacity` of them stored -> (cand_boxes [B,K,4] f32, cand_cls [B,K] i64, cand_scores [B,K] f32, cand_src [B,K] i32 = n,
+    totals [B] i32, uncapped).  Rows behind min(total, K) are zero.  Grids [B,gh,gw,3,5+nc], square or rectangular.  out: the five
+    tensors to write; ws: a uint8 workspace of decode_candidates_workspace_bytes (one is made otherwise).  Enqueues on the current
+    stream only."""
+    ptrs, gs, B, N = _grids_args(grids, square=False)
+    a = _anchors(anchors_table)
+    dev = grids[0].device
+    K = int(capacity)
+    if K < 1:
+        raise Y3Error(f"decode_candidates: capacity must be at least 1 (got {K})")
+    if out is None:
+        out = (torch.empty((B, K, 4), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.int64, device=dev),
+               torch.empty((B, K), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.int32, device=dev),
+               torch.empty((B,), dtype=torch.int32, device=dev))
+    boxes, cls, scores, src, totals = out
+    _need_cuda(boxes, cls, scores, src, totals, ws)
+    want = ((B, K, 4), torch.float32), ((B, K), torch.int64), ((B, K), torch.float32), ((B, K), torch.int32), ((B,), torch.int32)
+    if any(tuple(t.shape) != s or t.dtype != d or not t.is_contiguous() for t, (s, d) in zip(out, want)):
+        raise Y3Error(f"decode_candidates: out must be contiguous f32 [{B},{K},4], i64 [{B},{K}], f32 [{B},{K}], i32 [{B},{K}], i32 [{B}]")
+    lib = _lib.load()
+    if ws is None:
+        ws = torch.empty(max(lib.y3_decode_candidates_workspace_bytes(gs, B, int(nclasses)), 16), dtype=torch.uint8, device=dev)
+    elif ws.dtype != torch.uint8 or ws.dim() != 1:
+        raise Y3Error("ws must be a 1-D uint8 tensor")
+    check(lib.y3_yolo_decode_candidates_hw(ptrs, gs, B, int(nclasses), _fptr(a), float(score_threshold), K, _dev(boxes), _dev(cls),
+                                           _dev(scores), _dev(src), _dev(totals), _dev(ws), ws.numel(), _lib.stream_ptr()),
+          "y3_yolo_decode_candidates_hw")
+    return boxes, cls, scores, src, totals
+
+
+def class_candidates(bboxes, conf, probs, score_threshold, capacity):
+    """decode_candidates for callers that hold the decoded tensors (y3_class_candidates), as class_scores is to yolo_decode_scores:
+    bboxes [B,N,4], conf [B,N,1] or [B,N], probs [B,N,nc] as yolo_decode gives them -> the same five tensors, bit for bit those of
+    decode_candidates on the grids they were decoded from."""
+    _need_cuda(bboxes, conf, probs)
+    if bboxes.dtype != torch.float32 or conf.dtype != torch.float32 or probs.dtype != torch.float32 or probs.dim() != 3:
+        raise Y3Error("class_candidates: float32 bboxes [B,N,4], conf [B,N,1], probs [B,N,nc]")
+    B, N, nc = probs.shape
+    if bboxes.numel() != B * N * 4 or conf.numel() != B * N:
+        raise Y3Error(f"class_candidates: bboxes must hold [{B},{N},4] and conf [{B},{N}] values")
+    K, dev = int(capacity), probs.device
+    if K < 1:
+        raise Y3Error(f"class_candidates: capacity must be at least 1 (got {K})")
+    out = (torch.empty((B, K, 4), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.int64, device=dev),
+           torch.empty((B, K), dtype=torch.float32, device=dev), torch.empty((B, K), dtype=torch.int32, device=dev),
+           torch.empty((B,), dtype=torch.int32, device=dev))
+    ws = torch.empty(max(B * N * 4, 16), dtype=torch.uint8, device=dev)
+    check(_lib.load().y3_class_candidates(_dev(bboxes), _dev(conf), _dev(probs), B, N, nc, float(score_threshold), K, *[_dev(t) for t in out],
+                                          _dev(ws), ws.numel(), _lib.stream_ptr()), "y3_class_candidates")
+    return out
+
+
+def candidate_sources(packed: torch.Tensor, num_valid: torch.Tensor, cand_src: torch.Tensor):
+    """The index word (word 6) of every valid packed row, in place: candidate k -> cand_src[b,k], the box it came from
+    (y3_candidate_sources).  packed [B,M,7] int32 as pack_detections wrote it over the [B,K] candidates.  -> packed."""
+    _need_cuda(packed, num_valid, cand_src)
+    if packed.dtype != torch.int32 or packed.dim() != 3 or packed.shape[2] != 7 or not packed.is_contiguous():
+        raise Y3Error("packed must be contiguous int32 [B,M,7]")
+    B, M = packed.shape[0], packed.shape[1]
+    if num_valid.dtype != torch.int32 or num_valid.shape != (B,) or cand_src.dtype != torch.int32 or cand_src.dim() != 2 or \
+            cand_src.shape[0] != B or not cand_src.is_contiguous():
+        raise Y3Error(f"num_valid must be int32 [{B}] and cand_src contiguous int32 [{B},K]")
+    check(_lib.load().y3_candidate_sources(_dev(packed), _dev(num_valid), _dev(cand_src), B, cand_src.shape[1], M, _lib.stream_ptr()),
+          "y3_candidate_sources")
+    return packed
+
+
 def class_scores(conf, probs):
     _need_cuda(conf, probs)
     B, N, nc = probs.shape

@@ -21,6 +21,7 @@ def detect_stream(net, batches, anchors, max_boxes, iou_threshold, score_thresho
     M = int(max_boxes)
     outs = {}       # ring slot -> pinned rows, pinned counts, event: made on the slot's first use
     pending = []
+    truncated = _Truncated()
 
     def result(entry):
         k, n = entry
@@ -30,7 +31,7 @@ def detect_stream(net, batches, anchors, max_boxes, iou_threshold, score_thresho
 
     for i, handle, packed_dev, nv_dev, cur, stage, _ in _detect_batches(
             net, "detect_stream", batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes, letterbox,
-            tiles=tiles, merge_iou_threshold=merge_iou_threshold):
+            tiles=tiles, merge_iou_threshold=merge_iou_threshold, truncated=truncated):
         k, n = i % stage.depth, handle.frames
         if k not in outs:
             outs[k] = (torch.empty((stage.max_batch, M, 7), dtype=torch.int32, pin_memory=True),
@@ -44,10 +45,32 @@ def detect_stream(net, batches, anchors, max_boxes, iou_threshold, score_thresho
             yield result(pending.pop(0))
     while pending:
         yield result(pending.pop(0))
+    if truncated.images():      # behind the last result: everything of the stream has run
+        import warnings
+        warnings.warn(f"detect_stream: {truncated.images()} image(s) had more multi-label candidates than the capacity "
+                      f"{truncated.capacity} and were truncated (Net.multi_label_capacity; with tiles: tile images)", RuntimeWarning, stacklevel=2)
+
+
+class _Truncated:
+    """Multi-label streams: how many images had more candidates than the capacity.  One int64 on the device, added to behind every
+    detect on the stream's own stream and read back once, when the stream is over."""
+
+    def __init__(self):
+        self.count, self.capacity, self._host = None, 0, None
+
+    def enqueue(self, totals, capacity):
+        if self.count is None:
+            self.count, self.capacity = torch.zeros((), dtype=torch.int64, device=totals.device), int(capacity)
+        self.count += (totals > int(capacity)).sum()
+
+    def images(self):
+        if self._host is None:
+            self._host = 0 if self.count is None else int(self.count.item())
+        return self._host
 
 
 def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshold, mode, depth, max_batch, max_blob_bytes,
-                    letterbox, keep_grids=False, tiles=None, merge_iou_threshold=None):
+                    letterbox, keep_grids=False, tiles=None, merge_iou_threshold=None, truncated=None):
     """The loop detect_stream and evaluate_stream share: a generator that stages batch i+1 on the InputStage's copy stream,
     enqueues y3_net_detect (and, with letterbox, y3_unletterbox_detections) of batch i on the current stream, and yields
     (i, handle, packed_dev, nv_dev, stream, stage, grids) for the consumer to enqueue its own work on `stream` behind them.
@@ -61,7 +84,11 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
     net is planned for max_batch * T tile images, y3_net_detect runs on the tile batch in the net's NMS mode into a ring of its own, and
     y3_merge_tile_detections (the same mode, merge_iou_threshold, by default iou_threshold) takes the place of
     y3_unletterbox_detections: what is yielded is per FRAME and in frame coordinates, with the shapes of the untiled route.
-    tiles=None enqueues exactly what it did before the argument existed."""
+    tiles=None enqueues exactly what it did before the argument existed.
+    net.multi_label (read here, when the stream starts): y3_net_detect runs its multi-label route by itself -- with tiles on every tile image,
+    the merge consuming the packed rows unchanged -- and the composed route of keep_grids takes y3_yolo_decode_candidates_hw, the NMS over the
+    candidates and y3_candidate_sources in the place of y3_yolo_decode_scores and the NMS over the boxes.  Behind every detect the totals are
+    compared with the capacity on the device and counted into `truncated` (a _Truncated): no copy to the host, no synchronisation."""
     T = 1
     if tiles is not None:
         if keep_grids:
@@ -108,6 +135,17 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
         scores = torch.empty((max_batch, N), dtype=torch.float32, device=dev)
         sel = torch.empty((max_batch, M), dtype=torch.int32, device=dev)
         ws = torch.empty(ops._nms_workspace_bytes(max_batch, N, per_class=True), dtype=torch.uint8, device=dev)   # serves either rule
+    multi = bool(net.multi_label)
+    if multi:
+        n_boxes = sum(3 * gh * gw for gh, gw in net._grid_hw())
+        K = net.multi_label_capacity or n_boxes
+        if K > n_boxes:
+            raise Y3Error(f"{who}: multi_label_capacity {K} exceeds the {n_boxes} boxes of the plan")
+        totals_dev = torch.empty((max_batch * T,), dtype=torch.int32, device=dev)
+        if keep_grids:      # K <= N: the candidates live in the first K rows' worth of the buffers above
+            cand = (bboxes.view(-1)[:max_batch * K * 4].view(max_batch, K, 4), cls.view(-1)[:max_batch * K].view(max_batch, K),
+                    scores.view(-1)[:max_batch * K].view(max_batch, K), torch.empty((max_batch, K), dtype=torch.int32, device=dev))
+            cand_ws = torch.empty(max(ops.decode_candidates_workspace_bytes(gs, max_batch, nc), 16), dtype=torch.uint8, device=dev)
     it = iter(batches)
     first = next(it, None)
     handle = stage.submit(first, mode, letterbox) if first is not None else None
@@ -123,6 +161,14 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
         if keep_grids:      # the first n images of every buffer are a contiguous prefix
             grids = [t[:n] for t in grid_bufs]
             check(net.lib.y3_net_forward(net._h, _dev(handle.batch), n, grid_ptrs, sp), "y3_net_forward")
+        if keep_grids and multi:
+            c = [t[:n] for t in cand]      # [n,K,..]: contiguous prefixes
+            ops.decode_candidates(grids, a, nc, score_threshold, K, out=(*c, totals_dev[:n]), ws=cand_ws)
+            picked = ops._nms(c[0], c[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws,
+                              classes=c[1] if net.nms_per_class else None)
+            ops._pack(c[0], c[1], c[2], *picked, out=packed_dev[:n])
+            ops.candidate_sources(packed_dev[:n], nv_dev[:n], c[3])
+        elif keep_grids:
             decoded = ops._decode_scores(grids, a, nc, out=(bboxes[:n], cls[:n], scores[:n]))
             picked = ops._nms(decoded[0], decoded[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws,
                               classes=decoded[1] if net.nms_per_class else None)     # the rule y3_net_detect would take
@@ -131,6 +177,10 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
             out, out_nv = (tile_packed, tile_nv) if tiles is not None else (packed_dev, nv_dev)
             check(net.lib.y3_net_detect(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
                                         float(score_threshold), _dev(out), _dev(out_nv), sp), "y3_net_detect")
+            if multi:
+                check(net.lib.y3_net_read_multi_label_totals(net._h, n, _dev(totals_dev), sp), "y3_net_read_multi_label_totals")
+        if multi and truncated is not None:
+            truncated.enqueue(totals_dev[:n], K)
         stage.release(handle)
         if tiles is not None:
             f = handle.frames
@@ -270,10 +320,10 @@ def evaluate_stream(net, batches, gts, anchors, max_boxes, iou_threshold, score_
     part, total = {}, 0       # the layout of the one result buffer: each consumer's words, back to back
     for c in consumers:
         part[c], total = slice(total, total + c.words), total + c.words
-    gt_ring, result = _GroundTruthRing(G), None
+    gt_ring, result, truncated = _GroundTruthRing(G), None, _Truncated()
     for i, handle, packed_dev, nv_dev, cur, stage, grids in _detect_batches(
             net, "evaluate_stream", batches, anchors, M, iou_threshold, min(thresholds), mode, depth, max_batch, max_blob_bytes, letterbox,
-            keep_grids=bool(loss), tiles=tiles, merge_iou_threshold=merge_iou_threshold):
+            keep_grids=bool(loss), tiles=tiles, merge_iou_threshold=merge_iou_threshold, truncated=truncated):
         n = handle.frames
         gt = next(gt_iter, missing)
         if gt is missing:
@@ -292,5 +342,8 @@ def evaluate_stream(net, batches, gts, anchors, max_boxes, iou_threshold, score_
     if next(gt_iter, missing) is not missing:
         raise Y3Error("evaluate_stream: `gts` has more entries than there are batches")
     words = np.zeros(total, np.int64) if result is None else result.cpu().numpy()      # the one read-back: waits for the stream
+    if truncated.images():      # the one-pass argument (every threshold from the detect at the lowest) does not hold for a truncated image
+        raise Y3Error(f"evaluate_stream: {truncated.images()} image(s) had more multi-label candidates than the capacity {truncated.capacity} "
+                      "at the lowest score threshold; raise Net.multi_label_capacity (0: every box of the plan) or the lowest threshold")
     ret = [c.result(words[part[c]]) for c in (counted, summed, matched) if c is not None]      # the order of the return value
     return ret[0] if len(ret) == 1 else tuple(ret)

@@ -511,6 +511,15 @@ y3_status y3_net_forward_decode(y3_net *net, const float *images_dev, int batch,
 y3_status y3_net_detect(y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
                         float iou_threshold, float score_threshold, void *packed_dev, int32_t *num_valid_dev,
                         void *stream);
+/* y3_net_detect for callers that want the raw head grids as well (the validation loss reads them): grids_out_dev as y3_net_forward's
+ * grids_dev, three caller-owned fp32 buffers, 16-byte aligned, written exactly as y3_net_forward writes them.  The decode is then the
+ * stand-alone one over those grids (y3_yolo_decode_scores_hw; y3_yolo_decode_candidates_hw in multi-label mode) -- the composed route, to
+ * which y3_net_detect is bit-identical, so packed_dev and num_valid_dev are y3_net_detect's bit for bit.  y3_net_detect is this call
+ * without the grids: the same checks, the same scratch, the same NMS mode and multi-label switch, and every check comes before the first
+ * launch -- a refused call of either enqueues nothing. */
+y3_status y3_net_detect_grids(y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
+                              float iou_threshold, float score_threshold, float *const grids_out_dev[3], void *packed_dev,
+                              int32_t *num_valid_dev, void *stream);
 /* Which NMS rule y3_net_detect enqueues: Y3_NMS_AGNOSTIC (the default: y3_nms_padded, the reference's rule) or Y3_NMS_PER_CLASS
  * (y3_nms_padded_per_class on the class ids of the decode; iou_threshold must then be > 0).  Read when y3_net_detect enqueues: a
  * captured graph keeps the mode it was captured in.  y3_net_plan reserves the larger workspace, so the mode may be switched

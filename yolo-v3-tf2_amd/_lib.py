@@ -193,6 +193,7 @@ SYMBOLS = {
     "y3_crc32c": (C.c_uint32, [_vp, C.c_size_t]),
     "y3_net_forward_decode": (_i, [_vp, _vp, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_net_detect": (_i, [_vp, _vp, _i, _fp, _i, C.c_float, C.c_float, _vp, _vp, _vp]),
+    "y3_net_detect_grids": (_i, [_vp, _vp, _i, _fp, _i, C.c_float, C.c_float, C.POINTER(_vp), _vp, _vp, _vp]),
     "y3_comm_get_unique_id": (_i, [_vp]),
     "y3_comm_init_rank": (_i, [_vp, _i, _i, C.POINTER(_vp)]),
     "y3_comm_destroy": (None, [_vp]),

@@ -1,6 +1,6 @@
 """Host mirror of reference core/yolo_nms.py -- same name and signature, HIP underneath."""
-from ..ops import nms_padded_per_class as _nms_padded_per_class
-from ..runtime import class_scores as _class_scores, nms_padded as _nms_padded
+from ..ops import _nms
+from ..runtime import class_scores as _class_scores
 
 
 def yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold):
@@ -24,7 +24,7 @@ def yolo_nms_multi_label(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_t
     default, the rule the published protocol pairs with it; per_class=False: the class-agnostic rule -- decides between them.  Returns
     the reference-shaped 5-tuple OVER CANDIDATES: (cand_bboxes [B,K,4], cand_classes [B,K] i64, cand_scores [B,K],
     selected_indices_padded, num_valid_detections), so that gather_valid_detections_results works unchanged."""
-    from ..ops import _nms, class_candidates
+    from ..ops import class_candidates
     from .yolo_decode_layer import _to_device
     bboxes, confidence, class_probs = (_to_device(t) for t in outputs)
     bboxes = bboxes.reshape(bboxes.shape[0], -1, 4).contiguous()
@@ -41,10 +41,6 @@ def _yolo_nms(outputs, yolo_max_boxes, nms_iou_threshold, nms_score_threshold, p
     bboxes, confidence, class_probs = (_to_device(t) for t in outputs)
     class_indices, scores = _class_scores(confidence.contiguous(), class_probs.contiguous())
     bboxes = bboxes.reshape(bboxes.shape[0], -1, 4).contiguous()
-    if per_class:
-        selected_indices_padded, num_valid_detections = _nms_padded_per_class(bboxes, scores, class_indices, yolo_max_boxes,
-                                                                              nms_iou_threshold, nms_score_threshold)
-    else:
-        selected_indices_padded, num_valid_detections = _nms_padded(bboxes, scores, yolo_max_boxes, nms_iou_threshold,
-                                                                    nms_score_threshold)
+    selected_indices_padded, num_valid_detections = _nms(bboxes, scores, yolo_max_boxes, nms_iou_threshold, nms_score_threshold,
+                                                         classes=class_indices if per_class else None)
     return (bboxes, class_indices, scores, selected_indices_padded, num_valid_detections)

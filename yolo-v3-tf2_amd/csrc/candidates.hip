@@ -9,75 +9,48 @@
 //      per step, and places the survivors by ballot / popcount: slot = prefix of the box + rank of the pair inside the box.  Consecutive
 //      lanes hold consecutive pairs, so where survivors are dense consecutive lanes store consecutive rows.
 // Arithmetic: score = conf * prob, one fp32 multiply of the two values decode_kernel<WRITE_PROBS> stores (-ffp-contract=off).
-#include "y3_device.h"
-#include "y3_kernels.h"
-#include "decode_box.h"
+#include "decode_tile.h"
 
 namespace y3 {
 
-static constexpr int CAND_BOXES = 64;    // boxes per workgroup, four lanes per box: the decode's shape
-static constexpr int CAND_THREADS = CAND_BOXES * 4;
-static constexpr int CAND_WAVE_BOXES = CAND_BOXES / 4;   // boxes whose pairs one wave walks
+static constexpr int CAND_WAVE_BOXES = DEC_BOXES / 4;   // boxes whose pairs one wave walks
 
 struct CandLaunch {
-    DecodeArgs a;
-    int blk_start[4];  // first workgroup of each scale (prefix sums), [3] = total
+    DecodeLaunch d;
     float S;
     int K;
 };
 
 // WRITE = false: counts[b * N + n] = candidates of box n.  WRITE = true: counts holds the exclusive prefixes of cand_scan_kernel.
 template <bool WRITE>
-__global__ __launch_bounds__(CAND_THREADS) void candidates_kernel(const CandLaunch L, int32_t *__restrict__ counts,
-                                                                  float *__restrict__ cand_boxes, int64_t *__restrict__ cand_cls,
-                                                                  float *__restrict__ cand_scores, int32_t *__restrict__ cand_src)
+__global__ __launch_bounds__(DEC_THREADS) void candidates_kernel(const CandLaunch L, int32_t *__restrict__ counts,
+                                                                 float *__restrict__ cand_boxes, int64_t *__restrict__ cand_cls,
+                                                                 float *__restrict__ cand_scores, int32_t *__restrict__ cand_src)
 {
     extern __shared__ __attribute__((aligned(16))) float lds[];
-    __shared__ int s_cnt[CAND_BOXES];     // candidates of box j
-    __shared__ int s_first[CAND_BOXES];   // candidates of the workgroup's boxes before j
-    __shared__ int s_base[CAND_BOXES];    // candidates of the image's boxes before j (the scan's prefix)
-    __shared__ int s_img[CAND_BOXES];     // image of box j
-    __shared__ int s_n[CAND_BOXES];       // its row in the image
-    const int nc = L.a.nc, F = 5 + nc;
-    int s = 0;
-    if ((int)blockIdx.x >= L.blk_start[1]) s = 1;
-    if ((int)blockIdx.x >= L.blk_start[2]) s = 2;
-    const int gh = L.a.gh[s], gw = L.a.gw[s];
-    const int per_img = gh * gw * 3;
-    const long long total = (long long)L.a.B * per_img;            // boxes of this scale over the batch
-    const long long box0 = (long long)((int)blockIdx.x - L.blk_start[s]) * CAND_BOXES;
-    const int nbox = (int)((total - box0) < CAND_BOXES ? (total - box0) : CAND_BOXES);
-    const float *src = L.a.grid[s] + box0 * F;
-    const int nfl = nbox * F;
-    const int tid = threadIdx.x;
-    // coalesced copy (16 B per lane; box0 * F * 4 is a multiple of 16 because CAND_BOXES * 4 is)
-    const int nvec = nfl >> 2;
-    for (int i = tid; i < nvec; i += CAND_THREADS) reinterpret_cast<f32x4 *>(lds)[i] = reinterpret_cast<const f32x4 *>(src)[i];
-    for (int i = (nvec << 2) + tid; i < nfl; i += CAND_THREADS) lds[i] = src[i];
-    __syncthreads();
-
-    const int j = tid >> 2, q = tid & 3, lane = tid & 63;
-    const bool live = j < nbox;
-    const int jj = live ? j : 0;
-    const long long gi = box0 + jj;
-    const int b = (int)(gi / per_img);
-    const int r = (int)(gi - (long long)b * per_img);
-    const int a = r % 3;
-    const int cell = r / 3;
-    const int row = cell / gw, col = cell - row * gw;
-    float *t = lds + jj * F;
+    __shared__ int s_cnt[DEC_BOXES];      // candidates of box j
+    __shared__ int s_first[DEC_BOXES];    // candidates of the workgroup's boxes before j
+    __shared__ int s_base[DEC_BOXES];     // candidates of the image's boxes before j (the scan's prefix)
+    __shared__ int s_img[DEC_BOXES];      // image of box j
+    __shared__ int s_n[DEC_BOXES];        // its row in the image
+    const DecodeArgs &A = L.d.a;
+    const int nc = A.nc, F = 5 + nc;
+    const DecodeTile T = decode_tile_load(L.d, lds);
+    const int tid = threadIdx.x, j = T.j, q = T.q, lane = tid & 63, nbox = T.nbox;
+    const bool live = T.live;
+    float *t = T.t;
     f32x4 bb;
     float c, best;
     int besti;
     // the lane's class probabilities replace their logits in LDS; bb / c are valid in lane q == 0
-    decode_box_lanes<true, false>(t, q, lane, nc, gh, gw, row, col, q >= 2 ? L.a.anchors[s][a][q - 2] : 0.0f, live, bb, c, best, besti);
+    decode_box_lanes<true, false>(t, q, lane, nc, T.gh, T.gw, T.row, T.col, q >= 2 ? A.anchors[T.s][T.a][q - 2] : 0.0f, live, bb, c, best, besti);
     const float cf = __shfl(c, lane & ~3);
     int mine = 0;
     if (live)
         for (int k = q; k < nc; k += 4) mine += (cf * t[5 + k] > L.S) ? 1 : 0;    // NaN: not a candidate
     mine += __shfl_xor(mine, 1);
     mine += __shfl_xor(mine, 2);
-    const long long out_row = (long long)b * L.a.N + L.a.off[s] + r;
+    const long long out_row = T.out_row;
     if (!WRITE) {
         if (q == 0 && live) counts[out_row] = mine;
         return;
@@ -89,11 +62,11 @@ __global__ __launch_bounds__(CAND_THREADS) void candidates_kernel(const CandLaun
             s_base[j] = counts[out_row];
         }
         s_cnt[j] = mine;                 // 0 for a box behind the end
-        s_img[j] = b;
-        s_n[j] = L.a.off[s] + r;
+        s_img[j] = T.b;
+        s_n[j] = A.off[T.s] + T.r;
     }
     __syncthreads();
-    if (tid < CAND_BOXES) {              // wave 0: exclusive prefix over the 64 boxes
+    if (tid < DEC_BOXES) {               // wave 0: exclusive prefix over the 64 boxes
         const int v = s_cnt[tid];
         int incl = v;
 #pragma unroll
@@ -191,32 +164,24 @@ __global__ __launch_bounds__(256) void cand_scan_kernel(int32_t *__restrict__ co
     }
 }
 
-size_t candidates_lds_bytes(int nc) { return (size_t)CAND_BOXES * (5 + nc) * sizeof(float); }
-
 hipError_t launch_candidates(const DecodeArgs &a, float S, int K, float *cand_boxes, int64_t *cand_cls, float *cand_scores,
                              int32_t *cand_src, int32_t *totals, int32_t *counts, hipStream_t s)
 {
     CandLaunch L;
-    L.a = a;
+    L.d.a = a;
     L.S = S;
     L.K = K;
-    int acc = 0;
-    for (int i = 0; i < 3; ++i) {
-        L.blk_start[i] = acc;
-        const long long total = (long long)a.B * a.gh[i] * a.gw[i] * 3;
-        acc += (int)((total + CAND_BOXES - 1) / CAND_BOXES);
-    }
-    L.blk_start[3] = acc;
-    const size_t lds = candidates_lds_bytes(a.nc);
+    const int blocks = decode_blocks(L.d);
+    const size_t lds = decode_lds_bytes(a.nc);
     if (lds > 160 * 1024) return hipErrorInvalidValue;
     static LdsAttrOnce attr_count, attr_write;
     if (hipError_t e = set_max_lds_once(attr_count, reinterpret_cast<const void *>(candidates_kernel<false>), (int)lds); e != hipSuccess) return e;
     if (hipError_t e = set_max_lds_once(attr_write, reinterpret_cast<const void *>(candidates_kernel<true>), (int)lds); e != hipSuccess) return e;
-    hipLaunchKernelGGL(candidates_kernel<false>, dim3(acc), dim3(CAND_THREADS), lds, s, L, counts, cand_boxes, cand_cls, cand_scores, cand_src);
+    hipLaunchKernelGGL(candidates_kernel<false>, dim3(blocks), dim3(DEC_THREADS), lds, s, L, counts, cand_boxes, cand_cls, cand_scores, cand_src);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     hipLaunchKernelGGL(cand_scan_kernel, dim3(a.B), dim3(256), 0, s, counts, a.N, K, totals, cand_boxes, cand_cls, cand_scores, cand_src);
     if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    hipLaunchKernelGGL(candidates_kernel<true>, dim3(acc), dim3(CAND_THREADS), lds, s, L, counts, cand_boxes, cand_cls, cand_scores, cand_src);
+    hipLaunchKernelGGL(candidates_kernel<true>, dim3(blocks), dim3(DEC_THREADS), lds, s, L, counts, cand_boxes, cand_cls, cand_scores, cand_src);
     return hipGetLastError();
 }
 

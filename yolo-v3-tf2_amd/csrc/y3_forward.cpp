@@ -550,14 +550,17 @@ bool heads_can_decode(const y3_net *net)
     }
     return true;
 }
-// y3_net_forward_decode on the net's device, with the scratch layout L of this batch
+// The forward of `batch` images into decoded boxes / classes / scores, on the net's device, with the scratch layout L of this batch.
+// grids_out: where the caller wants the raw head grids (null: nobody does, they go to the scratch if they are written at all).  The heads
+// decode inside their own launch only when no grids are wanted and the graph allows it; otherwise the stand-alone decode over the grids.
 y3_status forward_decode(const y3_net *net, const y3::DetectLayout &L, const float *images_dev, int batch, const float *anchors_host,
-                         float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream)
+                         float *const *grids_out, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream)
 {
     char *b = static_cast<char *>(net->det_buf);
-    float *grids[3] = {reinterpret_cast<float *>(b + L.grid[0]), reinterpret_cast<float *>(b + L.grid[1]), reinterpret_cast<float *>(b + L.grid[2])};
+    float *scratch[3] = {reinterpret_cast<float *>(b + L.grid[0]), reinterpret_cast<float *>(b + L.grid[1]), reinterpret_cast<float *>(b + L.grid[2])};
+    float *const *grids = grids_out ? grids_out : scratch;
     Forward f{images_dev, grids, batch, (hipStream_t)stream, net->lanes};
-    if (!heads_can_decode(net)) {   // composed route: grids into the scratch, then the stand-alone decode
+    if (grids_out || !heads_can_decode(net)) {   // composed route
         if (y3_status st = run(net, f); st != Y3_OK) return st;
         return y3::decode_scores_hw("y3_yolo_decode_scores", grids, L.gs, batch, net->nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
     }
@@ -594,70 +597,68 @@ try {
     const y3::DetectLayout L = y3::detect_layout(net, batch);
     if (!net->det_buf || net->det_bytes < L.total)
         return fail(Y3_ERR_STATE, "y3_net_forward_decode: detect scratch not planned (y3_net_plan allocates it)");
-    return forward_decode(net, L, images_dev, batch, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+    return forward_decode(net, L, images_dev, batch, anchors_host, nullptr, bboxes_dev, class_idx_dev, scores_dev, stream);
 }
 Y3_CATCH("y3_net_forward_decode")
 
 // ------------------------------------------------------------------------------------------ whole pipeline
+// y3_net_detect (grids_out null: the raw grids are nobody's) and y3_net_detect_grids under the caller's name `who`: every check, then the
+// forward with its decode -- the candidates over the grids when the net is multi-label -- then the one tail (y3::select_and_pack).
+static y3_status detect(const char *who, y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
+                        float iou_threshold, float score_threshold, float *const *grids_out, void *packed_dev, int32_t *num_valid_dev, void *stream)
+{
+    y3_status st = check_forward_args(net, images_dev && anchors_host && packed_dev && num_valid_dev, batch, true, who);
+    if (st != Y3_OK) return st;
+    if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES) return fail(Y3_ERR_INVALID, "%s: max_boxes must be in [1,%d]", who, Y3_MAX_OUTPUT_BOXES);
+    Y3_ENTER_DEVICE(net);   // the decode / NMS / pack launches below go to the net's device; the caller's current device is restored on return
+    const y3::DetectLayout L = y3::detect_layout(net, batch);
+    if (!net->det_buf || net->det_bytes < L.total) return fail(Y3_ERR_STATE, "%s: detect scratch not planned (y3_net_plan allocates it)", who);
+    const int n = (int)L.n_boxes;
+    // Multi-label (include/y3.h, y3_net_set_multi_label): the NMS, the pack and the source rewrite run over [batch, K] candidates -- K <= n, so
+    // everything lives where the n boxes would
+    const int K = net->multi_label && net->multi_label_capacity ? net->multi_label_capacity : n;
+    if (K > n) return fail(Y3_ERR_INVALID, "%s: multi-label capacity %d exceeds the %d boxes of the plan", who, K, n);
+    if (st = y3::select_check(who, net->nms_mode, iou_threshold, score_threshold); st != Y3_OK) return st;   // before the first launch
+    char *b = static_cast<char *>(net->det_buf);
+    float *boxes = reinterpret_cast<float *>(b + L.boxes), *scores = reinterpret_cast<float *>(b + L.scores);
+    int64_t *cls = reinterpret_cast<int64_t *>(b + L.cls);
+    int32_t *sel = reinterpret_cast<int32_t *>(b + L.sel), *src = nullptr;
+    if (net->multi_label) {   // the composed forward, then the candidates over its grids
+        float *scratch[3] = {reinterpret_cast<float *>(b + L.grid[0]), reinterpret_cast<float *>(b + L.grid[1]), reinterpret_cast<float *>(b + L.grid[2])};
+        float *const *grids = grids_out ? grids_out : scratch;
+        src = reinterpret_cast<int32_t *>(b + L.cand_src);
+        if (st = run(net, {images_dev, grids, batch, (hipStream_t)stream, net->lanes}); st != Y3_OK) return st;
+        net->multi_label_batch = batch;
+        st = y3::decode_candidates_hw(who, grids, L.gs, batch, net->nclasses, anchors_host, score_threshold, K, boxes, cls, scores, src,
+                                      reinterpret_cast<int32_t *>(b + L.totals), b + L.cand_ws, L.cand_ws_bytes, stream);
+    } else {
+        // conv program with the head convs decoding their own tiles (grids neither written nor read back) where the graph allows it.
+        // (Round 5 ran NMS + pack per lane, on each lane's stream behind its last conv: bit-identical and 0.2 % slower under graph replay -- the NMS
+        // workgroups take CUs from the other lane's last convs; profiles/r05_ab_bf16_lane_nms.txt.  Batch-wide launches behind the join again.)
+        st = forward_decode(net, L, images_dev, batch, anchors_host, grids_out, boxes, cls, scores, stream);
+    }
+    if (st != Y3_OK) return st;
+    return y3::select_and_pack(who, boxes, scores, cls, src, batch, K, max_boxes, net->nms_mode, iou_threshold, score_threshold, sel, num_valid_dev,
+                               b + L.nms_ws, L.nms_bytes, packed_dev, stream);
+}
+
 y3_status y3_net_detect(y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
                         float iou_threshold, float score_threshold, void *packed_dev, int32_t *num_valid_dev,
                         void *stream)
 try {
-    y3_status st = check_forward_args(net, images_dev && anchors_host && packed_dev && num_valid_dev, batch, true, "y3_net_detect");
-    if (st != Y3_OK) return st;
-    if (max_boxes <= 0 || max_boxes > Y3_MAX_OUTPUT_BOXES)
-        return fail(Y3_ERR_INVALID, "y3_net_detect: max_boxes must be in [1,%d]", Y3_MAX_OUTPUT_BOXES);
-    Y3_ENTER_DEVICE(net);   // the decode / NMS / pack launches below go to the net's device; the caller's current device is restored on return
-    const y3::DetectLayout L = y3::detect_layout(net, batch);
-    if (!net->det_buf || net->det_bytes < L.total)
-        return fail(Y3_ERR_STATE, "y3_net_detect: detect scratch not planned (y3_net_plan allocates it)");
-    const int n = (int)L.n_boxes;
-    char *b = static_cast<char *>(net->det_buf);
-    float *boxes = reinterpret_cast<float *>(b + L.boxes), *scores = reinterpret_cast<float *>(b + L.scores);
-    int64_t *cls = reinterpret_cast<int64_t *>(b + L.cls);
-    int32_t *sel = reinterpret_cast<int32_t *>(b + L.sel);
-    if (net->multi_label) {
-        // Multi-label (include/y3.h, y3_net_set_multi_label): the composed forward into the grid scratch, the candidates over it, then the
-        // NMS, the pack and the source rewrite over [batch, K] candidates -- K <= n, so everything lives where the n boxes would.
-        const int K = net->multi_label_capacity ? net->multi_label_capacity : n;
-        if (K > n) return fail(Y3_ERR_INVALID, "y3_net_detect: multi-label capacity %d exceeds the %d boxes of the plan", K, n);
-        if (net->nms_mode == Y3_NMS_PER_CLASS && !(iou_threshold > 0.0f))   // the NMS's own checks, before the first launch
-            return fail(Y3_ERR_INVALID, "y3_net_detect: iou_threshold must be > 0 with Y3_NMS_PER_CLASS");
-        if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
-            return fail(Y3_ERR_INVALID, "y3_net_detect: iou_threshold <= 0 together with score_threshold < 0 is not supported");
-        float *grids[3] = {reinterpret_cast<float *>(b + L.grid[0]), reinterpret_cast<float *>(b + L.grid[1]), reinterpret_cast<float *>(b + L.grid[2])};
-        int32_t *src = reinterpret_cast<int32_t *>(b + L.cand_src), *totals = reinterpret_cast<int32_t *>(b + L.totals);
-        Forward f{images_dev, grids, batch, (hipStream_t)stream, net->lanes};
-        if (st = run(net, f); st != Y3_OK) return st;
-        net->multi_label_batch = batch;
-        st = y3::decode_candidates_hw("y3_net_detect", grids, L.gs, batch, net->nclasses, anchors_host, score_threshold, K, boxes, cls, scores, src,
-                                      totals, b + L.cand_ws, L.cand_ws_bytes, stream);
-        if (st != Y3_OK) return st;
-        if (net->nms_mode == Y3_NMS_PER_CLASS)
-            st = y3_nms_padded_per_class(boxes, scores, cls, batch, K, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
-                                         b + L.nms_ws, L.nms_bytes, stream);
-        else
-            st = y3_nms_padded(boxes, scores, batch, K, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev, b + L.nms_ws,
-                               L.nms_bytes, stream);
-        if (st != Y3_OK) return st;
-        st = y3_pack_detections(boxes, cls, scores, sel, num_valid_dev, batch, K, max_boxes, packed_dev, stream);
-        if (st != Y3_OK) return st;
-        return y3_candidate_sources(packed_dev, num_valid_dev, src, batch, K, max_boxes, stream);
-    }
-    // conv program with the head convs decoding their own tiles (grids neither written nor read back) where the graph allows it.
-    // (Round 5 ran NMS + pack per lane, on each lane's stream behind its last conv: bit-identical and 0.2 % slower under graph replay -- the NMS
-    // workgroups take CUs from the other lane's last convs; profiles/r05_ab_bf16_lane_nms.txt.  Batch-wide launches behind the join again.)
-    st = forward_decode(net, L, images_dev, batch, anchors_host, boxes, cls, scores, stream);
-    if (st != Y3_OK) return st;
-    if (net->nms_mode == Y3_NMS_PER_CLASS)
-        st = y3_nms_padded_per_class(boxes, scores, cls, batch, n, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
-                                     b + L.nms_ws, L.total - L.nms_ws, stream);
-    else
-        st = y3_nms_padded(boxes, scores, batch, n, max_boxes, iou_threshold, score_threshold, sel, num_valid_dev,
-                           b + L.nms_ws, L.total - L.nms_ws, stream);
-    if (st != Y3_OK) return st;
-    return y3_pack_detections(boxes, cls, scores, sel, num_valid_dev, batch, n, max_boxes, packed_dev, stream);
+    return detect("y3_net_detect", net, images_dev, batch, anchors_host, max_boxes, iou_threshold, score_threshold, nullptr, packed_dev,
+                  num_valid_dev, stream);
 }
 Y3_CATCH("y3_net_detect")
+
+y3_status y3_net_detect_grids(y3_net *net, const float *images_dev, int batch, const float *anchors_host, int max_boxes,
+                              float iou_threshold, float score_threshold, float *const grids_out_dev[3], void *packed_dev,
+                              int32_t *num_valid_dev, void *stream)
+try {
+    if (!grids_out_dev) return fail(Y3_ERR_INVALID, "y3_net_detect_grids: bad argument");
+    return detect("y3_net_detect_grids", net, images_dev, batch, anchors_host, max_boxes, iou_threshold, score_threshold, grids_out_dev,
+                  packed_dev, num_valid_dev, stream);
+}
+Y3_CATCH("y3_net_detect_grids")
 
 }  // extern "C"

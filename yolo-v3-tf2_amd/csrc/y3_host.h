@@ -276,4 +276,13 @@ y3_status decode_candidates_hw(const char *who, const float *const grids_dev[3],
                                float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev, void *workspace_dev, size_t workspace_bytes,
                                void *stream);
 
+// The detection tail, once: what follows the decode (or the candidates) in y3_net_detect[_grids] and the merge kernels in
+// y3_merge_tile_detections.  select_check: the threshold rules of the NMS of `nms_mode` (Y3_NMS_*) under the caller's name -- run it before the
+// call's first launch, so that a refused call enqueues nothing.  select_and_pack: the padded NMS of nms_mode over [batch, n] rows, the pack
+// into `packed`, and with cand_src (multi-label; null: single label) the rewrite of the packed index words to the candidates' boxes.
+y3_status select_check(const char *who, int nms_mode, float iou_threshold, float score_threshold);
+y3_status select_and_pack(const char *who, const float *boxes, const float *scores, const int64_t *cls, const int32_t *cand_src, int batch, int n,
+                          int max_boxes, int nms_mode, float iou_threshold, float score_threshold, int32_t *sel, int32_t *num_valid, void *ws,
+                          size_t ws_bytes, void *packed, void *stream);
+
 }  // namespace y3

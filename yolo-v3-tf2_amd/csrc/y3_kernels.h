@@ -277,12 +277,12 @@ struct DecodeArgs {
     float anchors[3][3][2];
     int B, N, nc;
 };
+size_t decode_lds_bytes(int nc);   // dynamic LDS of a decode-shaped workgroup (decode_tile.h): decode_kernel and candidates_kernel
 hipError_t launch_decode(const DecodeArgs &a, float *bboxes, float *conf, float *probs, int64_t *cls,
                          float *scores, hipStream_t s);
 hipError_t launch_class_scores(const float *conf, const float *probs, size_t n, int nc, int64_t *cls,
                                float *scores, hipStream_t s);
 // Multi-label candidates (candidates.hip; include/y3.h, y3_yolo_decode_candidates_hw): count, per-image prefix, write.  counts: [B,N] i32 scratch.
-size_t candidates_lds_bytes(int nc);
 hipError_t launch_candidates(const DecodeArgs &a, float S, int K, float *cand_boxes, int64_t *cand_cls, float *cand_scores,
                              int32_t *cand_src, int32_t *totals, int32_t *counts, hipStream_t s);
 // ... from decoded tensors: bboxes [B,N,4], conf [B,N], probs [B,N,nc]

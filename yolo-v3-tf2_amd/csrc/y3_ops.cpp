@@ -184,8 +184,8 @@ y3_status y3::decode_candidates_hw(const char *who, const float *const grids_dev
     if ((long long)batch * capacity > 0x7fffffffll || N * nclasses > 0x7fffffffll || (long long)batch * N > 0x7fffffffll)
         return fail(Y3_ERR_INVALID, "%s: batch * capacity, N * nclasses and batch * N must stay below 2^31 (got %d x %d, %lld x %d)", who, batch,
                     capacity, N, nclasses);
-    if (y3::candidates_lds_bytes(nclasses) > 160 * 1024)
-        return fail(Y3_ERR_INVALID, "%s: %d classes need %zu bytes of LDS, at most %d", who, nclasses, y3::candidates_lds_bytes(nclasses), 160 * 1024);
+    if (y3::decode_lds_bytes(nclasses) > 160 * 1024)
+        return fail(Y3_ERR_INVALID, "%s: %d classes need %zu bytes of LDS, at most %d", who, nclasses, y3::decode_lds_bytes(nclasses), 160 * 1024);
     y3::DecodeArgs a{};
     if (y3_status st = decode_args(grids_dev, grid_hw, batch, nclasses, anchors_host, who, &a); st != Y3_OK) return st;
     if ((uintptr_t)cand_boxes_dev & 15) return fail(Y3_ERR_INVALID, "%s: cand_boxes not 16-byte aligned", who);
@@ -408,11 +408,7 @@ try {
     if (Hc <= 0 || Wc <= 0) return fail(Y3_ERR_INVALID, "%s: canvas must be at least 1 x 1 (got %d x %d)", who, Hc, Wc);
     if (nms_mode != Y3_NMS_AGNOSTIC && nms_mode != Y3_NMS_PER_CLASS)
         return fail(Y3_ERR_INVALID, "%s: nms_mode must be Y3_NMS_AGNOSTIC or Y3_NMS_PER_CLASS (got %d)", who, nms_mode);
-    // the threshold checks of the NMS call that follows, made here: nothing may be enqueued by a refused call
-    if (nms_mode == Y3_NMS_PER_CLASS && !(iou_threshold > 0.0f))
-        return fail(Y3_ERR_INVALID, "%s: iou_threshold must be > 0 with Y3_NMS_PER_CLASS", who);
-    if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
-        return fail(Y3_ERR_INVALID, "%s: iou_threshold <= 0 together with score_threshold < 0 is not supported", who);
+    if (y3_status st = y3::select_check(who, nms_mode, iou_threshold, score_threshold); st != Y3_OK) return st;   // nothing may be enqueued by a refused call
     for (int f = 0; f < frames; ++f) {
         const int h = frame_hw_host[f * 2], w = frame_hw_host[f * 2 + 1];
         if (h < 1 || w < 1) return fail(Y3_ERR_INVALID, "%s: frame %d: height and width must be at least 1 (got %d x %d)", who, f, h, w);
@@ -454,14 +450,8 @@ try {
                                               cls + c0, (hipStream_t)stream);
         if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
     }
-    // the existing NMS and pack, through their own entry points: their checks were made above, so neither can refuse what follows a launch
-    y3_status st = nms_mode == Y3_NMS_PER_CLASS
-        ? y3_nms_padded_per_class(boxes, scores, cls, frames, N, max_boxes, iou_threshold, score_threshold, sel, num_valid_out_dev,
-                                  ws + l.nms, l.nms_bytes, stream)
-        : y3_nms_padded(boxes, scores, frames, N, max_boxes, iou_threshold, score_threshold, sel, num_valid_out_dev, ws + l.nms,
-                        l.nms_bytes, stream);
-    if (st != Y3_OK) return st;
-    return y3_pack_detections(boxes, cls, scores, sel, num_valid_out_dev, frames, N, max_boxes, packed_out_dev, stream);
+    return y3::select_and_pack(who, boxes, scores, cls, nullptr, frames, N, max_boxes, nms_mode, iou_threshold, score_threshold, sel,
+                               num_valid_out_dev, ws + l.nms, l.nms_bytes, packed_out_dev, stream);
 }
 Y3_CATCH("y3_merge_tile_detections")
 
@@ -791,3 +781,26 @@ try {
 Y3_CATCH("y3_pack_detections")
 
 }  // extern "C"
+
+// ------------------------------------------------------------------------------------------ the detection tail (y3_host.h)
+y3_status y3::select_check(const char *who, int nms_mode, float iou_threshold, float score_threshold)
+{
+    if (nms_mode == Y3_NMS_PER_CLASS && !(iou_threshold > 0.0f))
+        return fail(Y3_ERR_INVALID, "%s: iou_threshold must be > 0 with Y3_NMS_PER_CLASS", who);
+    if (!(iou_threshold > 0.0f) && score_threshold < 0.0f)
+        return fail(Y3_ERR_INVALID, "%s: iou_threshold <= 0 together with score_threshold < 0 is not supported", who);
+    return Y3_OK;
+}
+
+y3_status y3::select_and_pack(const char *who, const float *boxes, const float *scores, const int64_t *cls, const int32_t *cand_src, int batch,
+                              int n, int max_boxes, int nms_mode, float iou_threshold, float score_threshold, int32_t *sel, int32_t *num_valid,
+                              void *ws, size_t ws_bytes, void *packed, void *stream)
+{
+    y3_status st = nms_padded(who, boxes, scores, nms_mode == Y3_NMS_PER_CLASS ? cls : nullptr, batch, n, max_boxes, iou_threshold, score_threshold,
+                              sel, num_valid, ws, ws_bytes, stream);
+    if (st != Y3_OK) return st;
+    hipError_t e = y3::launch_pack(boxes, cls, scores, sel, num_valid, batch, n, max_boxes, packed, (hipStream_t)stream);
+    if (e == hipSuccess && cand_src) e = y3::launch_candidate_sources(packed, num_valid, cand_src, batch, n, max_boxes, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s: pack launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}

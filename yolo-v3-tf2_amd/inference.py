@@ -46,12 +46,8 @@ class DetectModel:
         if self.fused:
             from . import ops, runtime
             bboxes, cls, scores = runtime.yolo_decode_scores(grids, self.anchors_table, self.nclasses)
-            if per_class:
-                sel, nv = ops.nms_padded_per_class(bboxes, scores, cls, self.yolo_max_boxes, self.nms_iou_threshold,
-                                                   self.nms_score_threshold)
-            else:
-                sel, nv = runtime.nms_padded(bboxes, scores, self.yolo_max_boxes, self.nms_iou_threshold,
-                                             self.nms_score_threshold)
+            sel, nv = ops._nms(bboxes, scores, self.yolo_max_boxes, self.nms_iou_threshold, self.nms_score_threshold,
+                               classes=cls if per_class else None)
             return bboxes, cls, scores, sel, nv
         from .core.yolo_decode_layer import yolo_decode
         decoded_output = yolo_decode(grids, self.anchors_table, self.nclasses)      # reference: inference.py:111

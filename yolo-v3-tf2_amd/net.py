@@ -650,8 +650,8 @@ class Net:
         "images" images that were counted; "errors" images were not (a class outside [0,nclasses), a box centred outside the
         image, a non-finite coordinate: they add nothing to "sum").  core.loss_func.summarize_loss turns it into val_loss,
         perGrid and perSource as reference train.py:45-52 forms them.  It is the validation loss only: no gradient is taken and
-        the regulariser the reference's training loop adds (model.losses) is not part of it.  Each batch then takes the composed
-        route y3_net_forward -> y3_yolo_decode_scores -> y3_nms_padded -> y3_pack_detections (bit-identical detections; the raw
+        the regulariser the reference's training loop adds (model.losses) is not part of it.  Each batch then takes y3_net_detect_grids, the composed
+        route y3_net_forward -> y3_yolo_decode_scores -> y3_nms_padded -> y3_pack_detections as one call (bit-identical detections; the raw
         grids are written and read back, which y3_net_detect avoids), y3_yolo_assign_targets and y3_yolo_loss run on the same
         grids with the ground truth already on the device, and the sums come back with the counters in the one final copy.
         nclasses must be the program's.  Not together with letterbox=True: the reference trains on letterboxed images with

@@ -406,12 +406,11 @@ def pack_detections(bboxes, cls, scores, sel, nv):
     return _pack(bboxes, cls, scores, sel, nv)
 
 
-def _pack(bboxes, cls, scores, sel, nv, out=None):
+def _pack(bboxes, cls, scores, sel, nv):
     _need_cuda(bboxes, cls, scores, sel, nv)
     B, N = scores.shape
     M = sel.shape[1]
-    if out is None:
-        out = torch.empty((B, M, 7), dtype=torch.int32, device=bboxes.device)
+    out = torch.empty((B, M, 7), dtype=torch.int32, device=bboxes.device)
     check(_lib.load().y3_pack_detections(_dev(bboxes), _dev(cls), _dev(scores), _dev(sel), _dev(nv), B, N, M, _dev(out),
                                          _lib.stream_ptr()), "y3_pack_detections")
     return out

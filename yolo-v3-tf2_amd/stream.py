@@ -76,19 +76,16 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
     (i, handle, packed_dev, nv_dev, stream, stage, grids) for the consumer to enqueue its own work on `stream` behind them.
     The device buffers are slot i % depth of a ring: the consumer's reads are ordered before their reuse by the stream.
     keep_grids: the consumer wants the raw head grids as well (`grids`: three [n,g,g,3,5+nc] views, otherwise None), so
-    each batch takes the composed route include/y3.h documents as bit-identical to y3_net_detect: y3_net_forward into
-    grid buffers made once here, y3_yolo_decode_scores, y3_nms_padded (y3_nms_padded_per_class when net.nms_per_class is set,
-    as y3_net_detect itself chooses), y3_pack_detections.  One set of buffers, the NMS
-    workspace among them, serves every batch: all of it runs on the one stream.
+    each batch is one y3_net_detect_grids -- y3_net_detect that writes the grids, bit-identical detections -- into grid
+    buffers made once here.
     tiles = (rows, cols, overlap_px, overview): sliced inference.  The stage cuts every frame into T windows from the one upload, the
     net is planned for max_batch * T tile images, y3_net_detect runs on the tile batch in the net's NMS mode into a ring of its own, and
     y3_merge_tile_detections (the same mode, merge_iou_threshold, by default iou_threshold) takes the place of
     y3_unletterbox_detections: what is yielded is per FRAME and in frame coordinates, with the shapes of the untiled route.
     tiles=None enqueues exactly what it did before the argument existed.
-    net.multi_label (read here, when the stream starts): y3_net_detect runs its multi-label route by itself -- with tiles on every tile image,
-    the merge consuming the packed rows unchanged -- and the composed route of keep_grids takes y3_yolo_decode_candidates_hw, the NMS over the
-    candidates and y3_candidate_sources in the place of y3_yolo_decode_scores and the NMS over the boxes.  Behind every detect the totals are
-    compared with the capacity on the device and counted into `truncated` (a _Truncated): no copy to the host, no synchronisation."""
+    net.multi_label (read here, when the stream starts): y3_net_detect[_grids] runs its multi-label route by itself -- with tiles on every
+    tile image, the merge consuming the packed rows unchanged.  Behind every detect the totals are compared with the capacity on the
+    device and counted into `truncated` (a _Truncated): no copy to the host, no synchronisation."""
     T = 1
     if tiles is not None:
         if keep_grids:
@@ -127,25 +124,12 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
         nc, gs = net.program.nclasses, net._grid_hw()
         if nc <= 0:
             raise Y3Error(f"{who}: the program has no detection heads")
-        N = sum(3 * gh * gw for gh, gw in gs)
         grid_bufs = [torch.empty((max_batch, gh, gw, 3, 5 + nc), dtype=torch.float32, device=dev) for gh, gw in gs]
         grid_ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in grid_bufs])
-        bboxes = torch.empty((max_batch, N, 4), dtype=torch.float32, device=dev)
-        cls = torch.empty((max_batch, N), dtype=torch.int64, device=dev)
-        scores = torch.empty((max_batch, N), dtype=torch.float32, device=dev)
-        sel = torch.empty((max_batch, M), dtype=torch.int32, device=dev)
-        ws = torch.empty(ops._nms_workspace_bytes(max_batch, N, per_class=True), dtype=torch.uint8, device=dev)   # serves either rule
     multi = bool(net.multi_label)
-    if multi:
-        n_boxes = sum(3 * gh * gw for gh, gw in net._grid_hw())
-        K = net.multi_label_capacity or n_boxes
-        if K > n_boxes:
-            raise Y3Error(f"{who}: multi_label_capacity {K} exceeds the {n_boxes} boxes of the plan")
+    if multi:       # a capacity above the boxes of the plan: the detect refuses it
+        K = net.multi_label_capacity or sum(3 * gh * gw for gh, gw in net._grid_hw())
         totals_dev = torch.empty((max_batch * T,), dtype=torch.int32, device=dev)
-        if keep_grids:      # K <= N: the candidates live in the first K rows' worth of the buffers above
-            cand = (bboxes.view(-1)[:max_batch * K * 4].view(max_batch, K, 4), cls.view(-1)[:max_batch * K].view(max_batch, K),
-                    scores.view(-1)[:max_batch * K].view(max_batch, K), torch.empty((max_batch, K), dtype=torch.int32, device=dev))
-            cand_ws = torch.empty(max(ops.decode_candidates_workspace_bytes(gs, max_batch, nc), 16), dtype=torch.uint8, device=dev)
     it = iter(batches)
     first = next(it, None)
     handle = stage.submit(first, mode, letterbox) if first is not None else None
@@ -158,29 +142,19 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
         n = handle.batch.shape[0]
         packed_dev, nv_dev = ring[i % stage.depth]
         sp, grids = C.c_void_p(cur.cuda_stream), None
+        # the tiles' rows go to the merge, an untiled batch's straight into the ring
+        out, out_nv = (tile_packed, tile_nv) if tiles is not None else (packed_dev, nv_dev)
         if keep_grids:      # the first n images of every buffer are a contiguous prefix
             grids = [t[:n] for t in grid_bufs]
-            check(net.lib.y3_net_forward(net._h, _dev(handle.batch), n, grid_ptrs, sp), "y3_net_forward")
-        if keep_grids and multi:
-            c = [t[:n] for t in cand]      # [n,K,..]: contiguous prefixes
-            ops.decode_candidates(grids, a, nc, score_threshold, K, out=(*c, totals_dev[:n]), ws=cand_ws)
-            picked = ops._nms(c[0], c[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws,
-                              classes=c[1] if net.nms_per_class else None)
-            ops._pack(c[0], c[1], c[2], *picked, out=packed_dev[:n])
-            ops.candidate_sources(packed_dev[:n], nv_dev[:n], c[3])
-        elif keep_grids:
-            decoded = ops._decode_scores(grids, a, nc, out=(bboxes[:n], cls[:n], scores[:n]))
-            picked = ops._nms(decoded[0], decoded[2], M, iou_threshold, score_threshold, out=(sel[:n], nv_dev[:n]), ws=ws,
-                              classes=decoded[1] if net.nms_per_class else None)     # the rule y3_net_detect would take
-            ops._pack(*decoded, *picked, out=packed_dev[:n])
-        else:       # the tiles' rows go to the merge, an untiled batch's straight into the ring
-            out, out_nv = (tile_packed, tile_nv) if tiles is not None else (packed_dev, nv_dev)
+            check(net.lib.y3_net_detect_grids(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold), float(score_threshold),
+                                              grid_ptrs, _dev(out), _dev(out_nv), sp), "y3_net_detect_grids")
+        else:
             check(net.lib.y3_net_detect(net._h, _dev(handle.batch), n, _fptr(a), M, float(iou_threshold),
                                         float(score_threshold), _dev(out), _dev(out_nv), sp), "y3_net_detect")
-            if multi:
-                check(net.lib.y3_net_read_multi_label_totals(net._h, n, _dev(totals_dev), sp), "y3_net_read_multi_label_totals")
-        if multi and truncated is not None:
-            truncated.enqueue(totals_dev[:n], K)
+        if multi:
+            check(net.lib.y3_net_read_multi_label_totals(net._h, n, _dev(totals_dev), sp), "y3_net_read_multi_label_totals")
+            if truncated is not None:
+                truncated.enqueue(totals_dev[:n], K)
         stage.release(handle)
         if tiles is not None:
             f = handle.frames

@@ -100,7 +100,15 @@ typedef struct {
 
 /* op_kinds[i] == 0: take the next y3_conv_desc; == 1: take the next y3_aux_desc (execution order).
  * tensors[0..n_tensors) describes every tensor id; `input_tensor` is the image, `outputs[3]` the head
- * outputs in model order (coarsest grid first), each with 3*(5+nclasses) channels. */
+ * outputs in model order (coarsest grid first), each with 3*(5+nclasses) channels.
+ * Conv widths.  Accepted here: Cin a multiple of 32 (3 for the first layer), any Cout; a two-source conv (1x1 only) with c0 and
+ * cin - c0 multiples of 32.  What a mode then runs is decided by its tile tables, and y3_net_plan refuses a mode in which some conv
+ * has no tile (Y3_ERR_INVALID, naming the conv, its Cin / c0 / Cout and the mode) before it allocates anything:
+ *   Y3_DTYPE_F32, _F32X3, _F32X2: every accepted conv (K tiles of 32 channels; Cout padded to 32, the plane-split modes to 64).
+ *   Y3_DTYPE_BF16, _F16: K tiles of 64 channels where Cin and the concat boundary c0 are multiples of 64, any Cout; else the K tiles
+ *     of 32 channels, which exist 64 wide only: Cout rounded up to 32 must then be a multiple of 64 (Cin = 96 -> Cout = 192 runs,
+ *     96 -> 96 and 32 -> 32 are refused; so is [96, 96] -> 96).
+ *   Y3_DTYPE_I8: the convs before the cut as _F16; from the cut on Cin and c0 are multiples of 128 by the cut's own rule, any Cout. */
 y3_status y3_net_create(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
                         const y3_conv_desc *convs, int n_convs, const y3_aux_desc *aux, int n_aux,
                         int input_tensor, const int32_t outputs[3], int nclasses, y3_net **out);
@@ -126,6 +134,13 @@ y3_status y3_net_set_tile(y3_net *net, int conv_slot, int tile);
 y3_status y3_net_set_tile_bf16(y3_net *net, int conv_slot, int tile);
 y3_status y3_net_set_tile_x3(y3_net *net, int conv_slot, int tile);
 y3_status y3_net_set_tile_x2(y3_net *net, int conv_slot, int tile);   /* same tile table as _x3; a subset is built */
+/* y3_choose_tile (pure, no device): the tile id the heuristic of plan mode `dtype` (Y3_DTYPE_*; Y3_DTYPE_I8: the int8 family) gives a
+ * conv of this shape -- no forced tile, no tuning table -- through the functions the launch decision itself calls.  c0: channels of
+ * the first source of a two-source 1x1 conv, -1 for one source.  M: GEMM rows (images x output positions) of the call, M_plan: of the
+ * planned batch.  arena_out: 1 when the launch stores the mode's own format, 0 when it writes an fp32 net output itself.  Returns -1
+ * when no built tile of the mode fits the conv (y3_net_plan refuses such a net in that mode), -2 for a shape y3_net_create refuses
+ * or an unknown dtype. */
+int y3_choose_tile(int dtype, int size, int stride, int cin, int c0, int cout, long long M, long long M_plan, int arena_out);
 /* Run a forward as `lanes` (1..4) equal sub-batches: the first on the caller's stream itself, the others on forked
  * internal streams joined back into it: the tail of one sub-batch's conv kernel overlaps the next kernel of another.
  * Results are unchanged (images are independent).  Falls back to fewer lanes when the batch is not divisible. */

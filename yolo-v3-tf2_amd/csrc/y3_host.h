@@ -241,6 +241,9 @@ struct ConvChoice {
 ConvChoice choose_conv(const y3_net *net, int oi, const ConvArgs &a);
 ConvChoice choose_conv_planned(const y3_net *net, int oi);   // ... for max_batch images, as a plain forward launches it
 int conv_op(const y3_net *net, int slot);                    // the op that runs conv `slot`, -1: none
+// The first conv slot for which the planned mode (an int8 plan: fp16 before the cut, int8 from it on) has no tile that fits -- neither
+// a forced one nor the chooser's -- or -1 when every conv has one.  y3_net_plan_hw, once the mode, the cut and out_slot are known.
+int conv_without_tile(const y3_net *net);
 
 bool stem_applicable(const y3_net *net);
 bool stem_conv2_applicable(const y3_net *net);

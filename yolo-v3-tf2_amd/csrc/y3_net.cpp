@@ -213,16 +213,19 @@ hipError_t upload(P *&dev, const std::vector<T> &host)
 // Does the tile divide the conv (y3::tile_fits)?  cout_pad: the padded Cout of the mode's weights (ConvSlot::cout_pad / cout_pad64)
 bool fits(const y3::TileInfo &t, const ConvSlot &c, int cout_pad) { return y3::tile_fits(t, c.d.cin, c.d.src1 >= 0 ? c.d.c0 : -1, cout_pad); }
 
-// The first candidate tile that fits the conv and gives at least `want` workgroups for M rows over `cout_pad` channels; the last
-// candidate when none does.
+// The first candidate tile that fits the conv and gives at least `want` workgroups for M rows over `cout_pad` channels; when none
+// reaches that count, the last candidate that fits (the lists run from the largest tile to the smallest); -1 when none fits at all.
 template <size_t N>
 int first_reaching(const int (&cand)[N], y3::TileInfo (*info)(int), const ConvSlot &c, int cout_pad, long long M, long long want)
 {
+    int last_fit = -1;
     for (int t : cand) {
         const y3::TileInfo s = info(t);
-        if (fits(s, c, cout_pad) && ((M + s.bm - 1) / s.bm) * (cout_pad / s.bn) >= want) return t;
+        if (!fits(s, c, cout_pad)) continue;
+        if (((M + s.bm - 1) / s.bm) * (cout_pad / s.bn) >= want) return t;
+        last_fit = t;
     }
-    return cand[N - 1];
+    return last_fit;
 }
 
 int choose_tile_x2(const ConvSlot &c, long long M, long long, bool)
@@ -259,13 +262,19 @@ int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16
     // early 3x3 / stride-1 convs with Cin = 32 / 64 (K = 288 / 576): weights resident in LDS, input patch by LDS-DMA (tile id 32,
     // conv_res_bf16.hip) -- from the conv's shape alone, so batch- and lane-independent
     if (bf16_out && c.d.size == 3 && c.d.stride == 1 && c.d.src1 < 0 && (c.d.cin == 32 || c.d.cin == 64) && c.d.cout % 64 == 0) return 32;
-    static constexpr int bk32[] = {5, 6},    // BK = 32 (Cin = 32 layers, Cout = 64)
+    static constexpr int bk32[] = {5, 6},    // BK = 32, both 64 wide (the Cin = 32 layers; any Cin or concat boundary that 64 does not divide)
                          n128[] = {8, 12, 11},   // LDS-DMA variants: 128x128, 64x128, 64x64
                          n64[] = {10, 11}, n32[] = {4};
-    if (c.d.cin % 64) return first_reaching(bk32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
-    if (c.cout_pad % 128 == 0) return first_reaching(n128, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
-    if (c.cout_pad % 64 == 0) return first_reaching(n64, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
-    return first_reaching(n32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    // Cin % 64 == 0: the BK = 64 list of the widest N tile that divides Cout; its tiles fit unless the boundary c0 of a two-source conv is odd
+    int t = -1;
+    if (c.d.cin % 64 == 0)
+        t = c.cout_pad % 128 == 0  ? first_reaching(n128, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512)
+            : c.cout_pad % 64 == 0 ? first_reaching(n64, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512)
+                                   : first_reaching(n32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    // Cin, or the boundary c0 of a two-source conv, is an odd multiple of 32: the BK = 32 tiles, which exist 64 wide only -- so a conv
+    // whose padded Cout is an odd multiple of 32 as well has no 16-bit tile: -1, and y3_net_plan refuses the mode (conv_without_tile)
+    if (t < 0) t = first_reaching(bk32, y3::conv_bf16_tile_info, c, c.cout_pad, M, 512);
+    return t;
 }
 
 // int8 plans: the bf16 chooser's tile where it has an int8 form (the LDS-DMA tiles with 128-byte rows, both MFMA shapes); where it has
@@ -273,9 +282,9 @@ int choose_tile_bf16(const ConvSlot &c, long long M, long long M_plan, bool bf16
 int choose_tile_i8(const ConvSlot &c, long long M, long long M_plan, bool arena_out)
 {
     const int t = choose_tile_bf16(c, M, M_plan, arena_out);
-    if (y3::conv_i8_tile_built(t) && fits(y3::conv_i8_tile_info(t), c, c.cout_pad64)) return t;
+    if (t >= 0 && y3::conv_i8_tile_built(t) && fits(y3::conv_i8_tile_info(t), c, c.cout_pad64)) return t;
     static constexpr int n64[] = {10, 11};
-    return first_reaching(n64, y3::conv_i8_tile_info, c, c.cout_pad64, M, 512);
+    return first_reaching(n64, y3::conv_i8_tile_info, c, c.cout_pad64, M, 512);   // -1: Cin or c0 no multiple of 128 (never behind the cut)
 }
 
 // channels per K chunk of a 3x3 fp32 conv when the caller has not chosen (y3_net_set_k_chunk(-1)); Y3_K_CHUNK overrides (tools)
@@ -602,7 +611,9 @@ y3::ConvChoice y3::choose_conv(const y3_net *net, int oi, const ConvArgs &a)
     if (ch.kind != ConvKind::Mfma) return ch;
     const ConvFamily &f = family_of_conv(net, net->ops[oi].index);   // an int8 plan: fp16 before the cut, int8 from it on
     ch.tile = family_tile(f, c, a.M, (long long)net->max_batch * a.Ho * a.Wo, net->out_slot[c.d.dst] < 0);
-    if (f.refine) f.refine(net, c, a, ch);
+    // tile -1: the mode has no tile for this conv.  y3_net_plan refuses such a net (conv_without_tile), so no planned net gets here; the
+    // launchers answer a tile id out of range with hipErrorInvalidValue, and no refine rule is asked about a tile that does not exist
+    if (ch.tile >= 0 && f.refine) f.refine(net, c, a, ch);
     return ch;
 }
 
@@ -615,6 +626,18 @@ y3::ConvChoice y3::choose_conv_planned(const y3_net *net, int oi)
     a.M = net->max_batch * a.Ho * a.Wo;
     a.CoutPad = c.*family_of_conv(net, net->ops[oi].index).cout_pad;
     return choose_conv(net, oi, a);
+}
+
+int y3::conv_without_tile(const y3_net *net)
+{
+    for (int slot = 0; slot < (int)net->convs.size(); ++slot) {
+        const ConvSlot &c = net->convs[slot];
+        if (c.first_layer) continue;   // the direct Cin = 3 kernel (or the fused stem) in every mode
+        const long long M = (long long)net->max_batch * (net->height / c.d.out_div) * (net->width / c.d.out_div);
+        // whether a tile fits depends on the conv's widths alone, never on the rows: the planned batch answers for every call
+        if (family_tile(family_of_conv(net, slot), c, M, M, net->out_slot[c.d.dst] < 0) < 0) return slot;
+    }
+    return -1;
 }
 
 int y3::conv_op(const y3_net *net, int slot)
@@ -644,6 +667,7 @@ static y3_status set_forced_tile(const y3::ConvFamily &f, y3_net *net, int slot,
 // not the first layer, not a detection head (y3_net_detect runs the heads through conv_head.hip / decodes them in the launch, and the
 // composed route must stay bit-identical to it), only on the tiles the split form is built for, and with a Cout the mode's finish launch
 // can store.  why: the refusal's text.
+static const char *const kNoTile = "no tile of this mode divides the conv's widths";   // compared by address in set_split_k
 static bool split_eligible(const y3::ConvFamily &f, const y3_net *net, int slot, const char **why)
 {
     const y3::SplitForm &sf = *f.split;
@@ -654,6 +678,7 @@ static bool split_eligible(const y3::ConvFamily &f, const y3_net *net, int slot,
     const int tile = c.first_layer ? -1 : family_tile(f, c, 1, 1, arena_out);
     if (c.first_layer) w = "the first layer (Cin = 3) is never split";
     else if (net->nclasses > 0 && is_output(net, c.d.dst)) w = "a detection-head conv is never split (y3_net_detect decodes it in its own launch)";
+    else if (tile < 0) w = kNoTile;
     else if (!sf.tile(tile)) w = sf.no_form(tile);
     else if (c.d.cout % sf.cout_mult && arena_out) w = sf.bad_cout;
     if (why) *why = w;
@@ -741,7 +766,10 @@ static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int
     ConvSlot &c = net->convs[slot];
     if (S > 1) {
         const char *why = nullptr;
-        if (!split_eligible(f, net, slot, &why)) return fail(Y3_ERR_INVALID, "%s: conv %d: %s", sf.set_split, slot, why);
+        // (a conv that runs in another family in this plan -- another mode's plan, an int8 plan's convs before the cut, whose Cin the int8
+        // tiles need not divide -- and has no tile in f for that reason is told so by the two checks below)
+        if (!split_eligible(f, net, slot, &why) && !(why == kNoTile && net->height && &y3::family_of_conv(net, slot) != &f))
+            return fail(Y3_ERR_INVALID, "%s: conv %d: %s", sf.set_split, slot, why);
         if (net->height && &y3::family_of(net) != &f) return fail(Y3_ERR_INVALID, "%s: conv %d: %s", sf.set_split, slot, sf.other_plan);
         if (net->height && &y3::family_of_conv(net, slot) != &f)   // an int8 plan's convs before the cut
             return fail(Y3_ERR_INVALID, "%s: conv %d runs in fp16 in this plan (it lies before the int8 cut, conv %d), and the fp16 convs of an int8 plan are never split",
@@ -783,6 +811,27 @@ int y3_tile_built(int dtype, int tile)
 {
     const y3::ConvFamily *f = y3::conv_family(dtype);
     return (f && f->built(tile)) ? 1 : 0;
+}
+
+int y3_choose_tile(int dtype, int size, int stride, int cin, int c0, int cout, long long M, long long M_plan, int arena_out)
+{
+    const y3::ConvFamily *f = y3::conv_family(dtype);
+    // the shapes y3_net_create accepts for a conv that launches a tile (not the Cin = 3 first layer)
+    if (!f || !(size == 1 || size == 3) || !(stride == 1 || (stride == 2 && size == 3)) || cin <= 0 || cin % 32 || cout <= 0 || M <= 0 || M_plan <= 0)
+        return -2;
+    if (c0 >= 0 && (size != 1 || c0 == 0 || c0 >= cin || c0 % 32)) return -2;
+    ConvSlot c;   // as y3_net_create fills it; no forced tile, so family_tile asks the mode's chooser
+    c.d.size = size;
+    c.d.stride = stride;
+    c.d.cin = cin;
+    c.d.cout = cout;
+    c.d.c0 = c0 >= 0 ? c0 : cin;
+    c.d.src1 = c0 >= 0 ? 1 : -1;
+    c.d.residual = -1;
+    c.cout_pad = (cout + 31) / 32 * 32;
+    c.cout_pad64 = (cout + 63) / 64 * 64;
+    c.K = size * size * cin;
+    return family_tile(*f, c, M, M_plan, arena_out != 0);
 }
 
 y3_status y3_net_create(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,

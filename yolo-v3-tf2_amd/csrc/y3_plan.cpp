@@ -1,6 +1,7 @@
 // Planning a net for a batch, a canvas and a mode (y3_net_plan): tensor liveness and the activation arena, the lane streams, the
 // scratch of y3_net_detect, and what the planned net costs in FLOPs.
 #include <algorithm>
+#include <cstdio>
 #include <cstdlib>
 
 #include "y3_host.h"
@@ -305,6 +306,21 @@ try {
         net->height = net->width = net->max_batch = 0;      // no plan
         net->dtype = Y3_DTYPE_F32;
         return st;
+    }
+    // A conv no tile of its mode divides (the 16-bit tables have no 32-wide tile of K step 32: y3_net_create in include/y3.h): the mode
+    // cannot run the net.  Refused here, by name and before anything is allocated, not by the first forward's launch
+    if (const int slot = y3::conv_without_tile(net); slot >= 0) {
+        static const char *const names[] = {"fp32", "bf16", "f32x3", "f32x2", "fp16", "int8"};
+        const y3_conv_desc &d = net->convs[slot].d;
+        const int mode = y3::dtype_of_conv(net, slot), cut = net->i8_first_conv;
+        char where[96] = "";
+        if (dtype == Y3_DTYPE_I8 && mode != Y3_DTYPE_I8) snprintf(where, sizeof(where), " (it lies before the int8 cut, conv %d, and runs in fp16)", cut);
+        net->height = net->width = net->max_batch = 0;      // no plan
+        net->dtype = Y3_DTYPE_F32;
+        return fail(Y3_ERR_INVALID, "y3_net_plan: conv %d (Cin %d, c0 %d, Cout %d) has no %s tile%s: no built tile of that mode divides these "
+                                    "widths (with Cin or c0 an odd multiple of 32 the 16-bit modes need Cout padded to a multiple of 64); "
+                                    "Y3_DTYPE_F32, Y3_DTYPE_F32X3 and Y3_DTYPE_F32X2 run it",
+                    slot, d.cin, d.src1 >= 0 ? d.c0 : -1, d.cout, names[mode], where);
     }
     for (int t = 0; t < nt; ++t) {
         net->tbytes[t] = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels * net->telem[t];

@@ -84,8 +84,11 @@ typedef struct {
     int32_t out_div;       /* output spatial size = image_size / out_div */
 } y3_conv_desc;
 
-/* auxiliary ops that the lowering could not fold into a conv (not used by YOLOv3 itself) */
-enum { Y3_AUX_ADD = 0, Y3_AUX_UPSAMPLE2X = 1, Y3_AUX_CONCAT = 2 };
+/* auxiliary ops that the lowering could not fold into a conv (not used by YOLOv3 itself), and the two max-pools of YOLOv3-tiny, which are
+ * never folded: MaxPooling2D(2, strides 2 | 1, 'same') of src0 into dst (y3_maxpool2x2 below states the rule), src1 = -1.  Add, up-sample
+ * and concat run in Y3_DTYPE_F32 plans only; the pools run in Y3_DTYPE_F32, _BF16 and _F16 plans on the plan's stored elements, and
+ * y3_net_plan refuses a net that holds one in Y3_DTYPE_F32X3, _F32X2 and _I8 (plane-split tensors and calibrated pools are not built). */
+enum { Y3_AUX_ADD = 0, Y3_AUX_UPSAMPLE2X = 1, Y3_AUX_CONCAT = 2, Y3_AUX_MAXPOOL2X2_S2 = 3, Y3_AUX_MAXPOOL2X2_S1 = 4 };
 typedef struct {
     int32_t kind;
     int32_t src0;
@@ -112,6 +115,17 @@ typedef struct {
 y3_status y3_net_create(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
                         const y3_conv_desc *convs, int n_convs, const y3_aux_desc *aux, int n_aux,
                         int input_tensor, const int32_t outputs[3], int nclasses, y3_net **out);
+/* The same for a net of n_outputs heads, 2 (YOLOv3-tiny: 1/32 and 1/16) or 3: outputs[n_outputs].  y3_net_create IS this call with 3.
+ * y3_net_heads reports the count (0 for a null net).  Every net-level call that takes or fills per-head arrays -- y3_net_forward,
+ * y3_net_forward_decode, y3_net_detect, y3_net_detect_grids, y3_net_profile_convs, the measure_sclk calls -- reads the first
+ * y3_net_heads entries of its pointer arrays and never the rest; anchors_host is [heads][3][2]; N per image is 3 * sum over the heads
+ * of gh * gw (2535 at 416 x 416 with two heads).  NMS, pack, the evaluation counters, AP matching, the tile merge and un-letterbox
+ * work on boxes and packed rows and know nothing of heads.  y3_yolo_assign_targets / y3_yolo_loss stay three-scale.
+ * A pool op (Y3_AUX_MAXPOOL2X2_*) needs a source of a channel count that is a multiple of 32 in every mode that runs it. */
+y3_status y3_net_create_heads(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
+                              const y3_conv_desc *convs, int n_convs, const y3_aux_desc *aux, int n_aux,
+                              int input_tensor, const int32_t *outputs, int n_outputs, int nclasses, y3_net **out);
+int y3_net_heads(const y3_net *net);
 void y3_net_destroy(y3_net *net);
 
 /* Weights of conv `conv_slot` (index into the `convs` array given at creation), host pointers.
@@ -467,6 +481,30 @@ y3_status y3_yolo_decode_scores_hw(const float *const grids_dev[3], const int32_
                                    int nclasses, const float *anchors_host, float *bboxes_dev,
                                    int64_t *class_idx_dev, float *scores_dev, void *stream);
 
+/* The decodes for n_scales grids, 1 <= n_scales <= 3 (two for YOLOv3-tiny): grids_dev[n_scales], grid_hw[n_scales][2], anchors_host
+ * [n_scales][3][2], N = 3 * sum over those scales of gh_s * gw_s; nothing behind entry n_scales - 1 of an array is read.  These are the
+ * one body: y3_yolo_decode_hw / y3_yolo_decode_scores_hw ARE these calls with 3, the square forms those with {g, g}. */
+y3_status y3_yolo_decode_hw_n(const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
+                              const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream);
+y3_status y3_yolo_decode_scores_hw_n(const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
+                                     const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev,
+                                     void *stream);
+
+/* ------------------------------------------------------------------------------------------
+ * MaxPooling2D(pool_size = 2, strides = stride, padding = 'same'), stride 1 or 2 (reference: core/parse_model.py:78-99), the pools of
+ * YOLOv3-tiny.  src_dev [batch,H,W,C] -> dst_dev [batch,H/stride,W/stride,C], NHWC, elements of `dtype`: Y3_DTYPE_F32 (fp32),
+ * Y3_DTYPE_BF16 or Y3_DTYPE_F16 (2 bytes); C * element size must be a multiple of 16 bytes, both pointers 16-byte aligned.
+ *   stride 2 (H and W even): out[y, x] = max over in[2y .. 2y + 1, 2x .. 2x + 1]
+ *   stride 1: 'same' pads one row below and one column to the right and padding never wins, so
+ *             out[y, x] = max over in[y .. min(y + 1, H - 1), x .. min(x + 1, W - 1)]
+ * Elements are compared as values and the winning element's bits are stored.  What a window holding a NaN gives, and the sign of a
+ * result that is zero when the window holds both -0 and +0, are unspecified.  TensorFlow's own kernel is not pinned by this project's
+ * tests; yolo_v3_tf2_amd/maxpool.py restates the rule in NumPy.  Only enqueues on `stream`: no allocation, query or synchronisation, so
+ * it can be captured into a HIP graph.  A net runs the same kernel for its Y3_AUX_MAXPOOL2X2_* ops, per lane slice.
+ * ---------------------------------------------------------------------------------------- */
+y3_status y3_maxpool2x2(const void *src_dev, void *dst_dev, int batch, int height, int width, int channels, int stride, int dtype,
+                        void *stream);
+
 /* ------------------------------------------------------------------------------------------
  * yolo_nms / YoloNmsLayer.call   (reference: core/yolo_nms.py:16-34, core/yolo_nms_layer.py:26-29)
  * ---------------------------------------------------------------------------------------- */
@@ -565,6 +603,12 @@ int y3_net_get_nms_mode(const y3_net *net);
  * row reads {box of n, score[n,c], c, n} and two rows of one image may share n.
  * ---------------------------------------------------------------------------------------- */
 size_t y3_decode_candidates_workspace_bytes(const int32_t grid_hw[3][2], int batch, int nclasses);
+/* ... for n_scales grids (1..3), as y3_yolo_decode_hw_n: the three-scale names above and below ARE these calls with 3. */
+size_t y3_decode_candidates_workspace_bytes_n(const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses);
+y3_status y3_yolo_decode_candidates_hw_n(const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
+                                         const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
+                                         int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,
+                                         void *workspace_dev, size_t workspace_bytes, void *stream);
 y3_status y3_yolo_decode_candidates_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
                                        const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
                                        int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,

@@ -23,14 +23,17 @@ def _need_cuda(*ts):
             raise Y3Error("expected contiguous CUDA(HIP) tensors; the y3 kernels have no CPU fallback")
 
 
-def _anchors(anchors_table, reshape=False):
-    """-> float32 [3,3,2], contiguous.  reshape: any 18 values are taken (the Net methods); otherwise the shape is checked."""
+def _anchors(anchors_table, reshape=False, scales=3):
+    """-> float32 [scales,3,2], contiguous (scales: the grids / the net's heads, three or two).  reshape: any scales * 6 values are taken
+    (the Net methods); otherwise the shape is checked."""
     a = np.ascontiguousarray(anchors_table.detach().cpu().numpy() if isinstance(anchors_table, torch.Tensor)
                              else anchors_table, np.float32)
     if reshape:
-        a = np.ascontiguousarray(a.reshape(3, 3, 2))
-    if a.shape != (3, 3, 2):
-        raise Y3Error("anchors_table must be [3,3,2]")
+        if a.size != scales * 6:
+            raise Y3Error(f"anchors_table must hold {scales} x 3 (w, h) pairs (got {a.size} values)")
+        a = np.ascontiguousarray(a.reshape(scales, 3, 2))
+    if a.shape != (scales, 3, 2):
+        raise Y3Error(f"anchors_table must be [{scales},3,2]")
     return a
 
 

@@ -23,7 +23,7 @@ DTYPE_TAGS = {Y3_DTYPE_F32: "f32", Y3_DTYPE_BF16: "bf16", Y3_DTYPE_F32X3: "f32x3
 TILES_I8_BUILT = (8, 10, 11, 12, 17, 19, 24, 26, 27, 29)
 TILES_X2_BUILT = (0, 1, 2, 3, 4, 8, 12, 26, 27)
 TILES_X3_BUILT = (0, 1, 2, 3, 4, 8, 9, 12, 13, 14)
-Y3_AUX_ADD, Y3_AUX_UPSAMPLE2X, Y3_AUX_CONCAT = 0, 1, 2
+Y3_AUX_ADD, Y3_AUX_UPSAMPLE2X, Y3_AUX_CONCAT, Y3_AUX_MAXPOOL2X2_S2, Y3_AUX_MAXPOOL2X2_S1 = 0, 1, 2, 3, 4
 Y3_NMS_AGNOSTIC, Y3_NMS_PER_CLASS = 0, 1   # y3_net_set_nms_mode
 MAX_TILES = 64   # y3_tile_grid, y3_merge_tile_detections: tiles per frame
 # (BM, BN, waves, LDS stages) of every tile id of the fp32 MFMA conv kernel (mirror of kTiles in csrc/conv_f32.hip)
@@ -109,6 +109,9 @@ SYMBOLS = {
     "y3_tile_built": (_i, [_i, _i]),
     "y3_net_create": (_i, [C.POINTER(TensorDesc), _i, C.POINTER(C.c_int32), _i, C.POINTER(ConvDesc), _i,
                            C.POINTER(AuxDesc), _i, _i, C.POINTER(C.c_int32), _i, C.POINTER(_vp)]),
+    "y3_net_create_heads": (_i, [C.POINTER(TensorDesc), _i, C.POINTER(C.c_int32), _i, C.POINTER(ConvDesc), _i,
+                                 C.POINTER(AuxDesc), _i, _i, C.POINTER(C.c_int32), _i, _i, C.POINTER(_vp)]),
+    "y3_net_heads": (_i, [_vp]),
     "y3_net_destroy": (None, [_vp]),
     "y3_net_set_conv_weights": (_i, [_vp, _i, _fp, _fp, _fp, _fp, _fp, _fp, _f]),
     "y3_net_set_tile": (_i, [_vp, _i, _i]),
@@ -175,6 +178,9 @@ SYMBOLS = {
     "y3_yolo_decode_scores": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
     "y3_yolo_decode_hw": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),   # grid_hw[3][2] as six int32
     "y3_yolo_decode_scores_hw": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _vp, _vp, _vp, _vp]),
+    "y3_yolo_decode_hw_n": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _i, _fp, _vp, _vp, _vp, _vp]),   # grid_hw[n][2] as 2 n int32
+    "y3_yolo_decode_scores_hw_n": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _i, _fp, _vp, _vp, _vp, _vp]),
+    "y3_maxpool2x2": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "y3_class_scores": (_i, [_vp, _vp, _i, _i, _i, _vp, _vp, _vp]),
     "y3_nms_workspace_bytes": (_sz, [_i, _i]),
     "y3_nms_padded": (_i, [_vp, _vp, _i, _i, _i, _f, _f, _vp, _vp, _vp, _sz, _vp]),
@@ -184,6 +190,8 @@ SYMBOLS = {
     "y3_net_get_nms_mode": (_i, [_vp]),
     "y3_decode_candidates_workspace_bytes": (_sz, [C.POINTER(C.c_int32), _i, _i]),   # grid_hw[3][2] as six int32
     "y3_yolo_decode_candidates_hw": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _fp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "y3_decode_candidates_workspace_bytes_n": (_sz, [C.POINTER(C.c_int32), _i, _i, _i]),
+    "y3_yolo_decode_candidates_hw_n": (_i, [C.POINTER(_vp), C.POINTER(C.c_int32), _i, _i, _i, _fp, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "y3_class_candidates": (_i, [_vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "y3_candidate_sources": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "y3_net_set_multi_label": (_i, [_vp, _i, _i]),

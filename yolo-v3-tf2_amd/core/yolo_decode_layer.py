@@ -4,7 +4,7 @@ from ..runtime import yolo_decode as _decode
 
 def yolo_decode(model_output_grids, anchors_table, nclasses):
     """model_output_grids: 3 x [B,g,g,3,5+nclasses] CUDA tensors; anchors_table [3,3,2] (normalised w,h,
-    row s for grid s).  Returns (all_grids_bboxes [B,N,4], all_grids_confidence [B,N,1],
+    row s for grid s) -- or two grids and [2,3,2] for a two-head model (YOLOv3-tiny).  Returns (all_grids_bboxes [B,N,4], all_grids_confidence [B,N,1],
     all_grids_class_probs [B,N,nclasses]) -- reference: core/yolo_decode_layer.py:15-36."""
     return _decode([_to_device(g) for g in model_output_grids], anchors_table, nclasses)
 
@@ -21,7 +21,7 @@ def yolo_decode_hw_host(model_output_grids, anchors_table, nclasses):
     f32 = np.float32
     one, two = f32(1.0), f32(2.0)
     sigmoid = lambda t: (one / (one + np.exp(-t, dtype=f32))).astype(f32)
-    anchors = np.asarray(anchors_table, f32).reshape(3, 3, 2)
+    anchors = np.asarray(anchors_table, f32).reshape(-1, 3, 2)      # a row per grid: three, or two for YOLOv3-tiny
     boxes, confs, probs = [], [], []
     for s, grid in enumerate(model_output_grids):
         g = np.asarray(grid, f32)

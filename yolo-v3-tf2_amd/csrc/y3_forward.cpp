@@ -9,11 +9,11 @@
 // runs the conv program; the net itself is read-only while a forward is enqueued.
 struct Forward {
     const float *images;
-    float *const *grids;                     // [3] caller's fp32 head grids
+    float *const *grids;                     // [heads] caller's fp32 head grids
     int batch;
     hipStream_t stream;
     int lanes;                               // concurrent sub-batches this call may use (the net's y3_net_set_lanes, or 1)
-    const y3::DecodeHead *heads = nullptr;   // [3] in output order: the head convs decode their own tiles into these buffers
+    const y3::DecodeHead *heads = nullptr;   // [heads] in output order: the head convs decode their own tiles into these buffers
                                              // (per scale: first box index, grid size, anchors) instead of writing grids
     unsigned long long *clk = nullptr;       // y3_net_measure_sclk*: device buffer the stamped launch(es) write
     int clk_conv = -1;                       // ... which conv (-2: every conv, 8 words each at clk + 8 conv)
@@ -196,8 +196,16 @@ struct Slice {
 
     y3_status run_aux(int index) const
     {
-        if (net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
         const y3_aux_desc &x = net->aux[index];
+        if (x.kind == Y3_AUX_MAXPOOL2X2_S2 || x.kind == Y3_AUX_MAXPOOL2X2_S1) {   // on the plan's stored elements: fp32, bf16 or fp16 (y3_net_plan)
+            const int stride = x.kind == Y3_AUX_MAXPOOL2X2_S2 ? 2 : 1;
+            if (!ptr(x.src0) || !ptr(x.dst) || elem_bytes(x.src0) != elem_bytes(x.dst)) return fail(Y3_ERR_STATE, "aux op %d: tensor not planned", index);
+            const int dt = elem_bytes(x.src0) == 4 ? (int)Y3_DTYPE_F32 : net->dtype;
+            hipError_t e = y3::launch_maxpool2x2(ptr(x.src0), ptr(x.dst), nb, rows(net, x.src0), cols(net, x.src0), net->tensors[x.src0].channels, stride, dt, s);
+            if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d (max-pool) launch: %s", index, hipGetErrorString(e));
+            return Y3_OK;
+        }
+        if (net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
         auto p = [&](int t) { return static_cast<float *>(ptr(t)); };
         const int sh = rows(net, x.dst), sw = cols(net, x.dst);
         const int C = net->tensors[x.dst].channels;
@@ -256,7 +264,7 @@ struct Slice {
             if (crosses(dst))
                 if (y3_status st = quantize_crossing(dst); st != Y3_OK) return st;
         }
-        for (int k = 0; k < 3 && op_end == (int)net->ops.size(); ++k) {
+        for (int k = 0; k < net->n_heads && op_end == (int)net->ops.size(); ++k) {
             const int t = net->outputs[k];
             if (!net->staged[t]) continue;
             const size_t npix = (size_t)nb * rows(net, t) * cols(net, t);
@@ -282,7 +290,7 @@ static y3_status run(const y3_net *net, const Forward &f)
     if (net->dtype == Y3_DTYPE_F32X2)
         for (size_t i = 0; i < net->convs.size(); ++i)
             if (!net->convs[i].x2_ok) return fail(Y3_ERR_INVALID, "y3_net_forward: conv %zu has a weight outside the fp16 range of the two-plane mode", i);
-    for (int i = 0; i < 3; ++i)
+    for (int i = 0; i < net->n_heads; ++i)
         if (!f.grids[i] || ((uintptr_t)f.grids[i] & 15)) return fail(Y3_ERR_INVALID, "y3_net_forward: grid %d null or not 16-byte aligned", i);
     if ((uintptr_t)f.images & 3) return fail(Y3_ERR_INVALID, "y3_net_forward: images not 4-byte aligned");
     Y3_ENTER_DEVICE(net);   // launches go to the net's device whatever the caller's current one is; restored on return
@@ -364,7 +372,7 @@ try {
     if (!net->height || batch <= 0) return fail(Y3_ERR_STATE, "y3_net_profile_convs: call y3_net_plan first (and batch > 0)");
     Y3_ENTER_DEVICE(net);
     float *g[3] = {nullptr, nullptr, nullptr};
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < net->n_heads; ++i) {
         const int t = net->outputs[i];
         hipError_t e = hipMalloc(&g[i], (size_t)batch * rows(net, t) * cols(net, t) * net->tensors[net->outputs[i]].channels * sizeof(float));
         if (e != hipSuccess) {
@@ -377,7 +385,7 @@ try {
     f.n_ms = n;
     y3_status st = run(net, f);
     (void)hipStreamSynchronize((hipStream_t)stream);
-    for (int i = 0; i < 3; ++i) (void)hipFree(g[i]);
+    for (int i = 0; i < net->n_heads; ++i) (void)hipFree(g[i]);
     return st;
 }
 Y3_CATCH("y3_net_profile_convs")
@@ -521,7 +529,7 @@ Y3_CATCH("y3_net_read_tensor_i8")
 
 // ------------------------------------------------------------------------------------------ forward + decode
 namespace {
-// Can the three heads decode in place?  Each output must come from a 1x1 / stride-1 single-source conv without shortcut whose
+// Can the heads decode in place?  Each output must come from a 1x1 / stride-1 single-source conv without shortcut whose
 // 3 * (5 + nc) channels fit one 256-wide tile, written straight to the caller-visible grid (not staged), in an fp32, bf16
 // or fp16 plan.  Y3_FUSE_DECODE=0 (tools: A/B against the composed route) switches the fusion off.
 bool heads_can_decode(const y3_net *net)
@@ -529,7 +537,7 @@ bool heads_can_decode(const y3_net *net)
     static const bool off = [] { const char *e = getenv("Y3_FUSE_DECODE"); return e && e[0] == '0'; }();
     if (off || net->nclasses <= 0 || (net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16 && net->dtype != Y3_DTYPE_F16 && net->dtype != Y3_DTYPE_I8)) return false;
     if (net->keep_all || net->early_ops > 0 || 3 * (5 + net->nclasses) > 256) return false;
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < net->n_heads; ++k) {
         const int t = net->outputs[k];
         if (net->staged[t]) return false;
         int producers = 0;
@@ -562,11 +570,11 @@ y3_status forward_decode(const y3_net *net, const y3::DetectLayout &L, const flo
     Forward f{images_dev, grids, batch, (hipStream_t)stream, net->lanes};
     if (grids_out || !heads_can_decode(net)) {   // composed route
         if (y3_status st = run(net, f); st != Y3_OK) return st;
-        return y3::decode_scores_hw("y3_yolo_decode_scores", grids, L.gs, batch, net->nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+        return y3::decode_scores_hw("y3_yolo_decode_scores", grids, L.gs, net->n_heads, batch, net->nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
     }
     y3::DecodeHead heads[3];
     int first = 0;
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < net->n_heads; ++k) {
         heads[k].boxes = bboxes_dev;
         heads[k].cls = class_idx_dev;
         heads[k].scores = scores_dev;
@@ -629,7 +637,7 @@ static y3_status detect(const char *who, y3_net *net, const float *images_dev, i
         src = reinterpret_cast<int32_t *>(b + L.cand_src);
         if (st = run(net, {images_dev, grids, batch, (hipStream_t)stream, net->lanes}); st != Y3_OK) return st;
         net->multi_label_batch = batch;
-        st = y3::decode_candidates_hw(who, grids, L.gs, batch, net->nclasses, anchors_host, score_threshold, K, boxes, cls, scores, src,
+        st = y3::decode_candidates_hw(who, grids, L.gs, net->n_heads, batch, net->nclasses, anchors_host, score_threshold, K, boxes, cls, scores, src,
                                       reinterpret_cast<int32_t *>(b + L.totals), b + L.cand_ws, L.cand_ws_bytes, stream);
     } else {
         // conv program with the head convs decoding their own tiles (grids neither written nor read back) where the graph allows it.

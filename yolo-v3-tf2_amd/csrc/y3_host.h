@@ -110,6 +110,8 @@ struct y3_net {
     std::vector<y3_aux_desc> aux;
     int input_tensor = 0;
     int outputs[3] = {0, 0, 0};
+    int n_heads = 3;               // how many of them the net has (y3_net_create_heads): 3, or 2 for YOLOv3-tiny
+    bool has_pool = false;         // an aux op is a max-pool: fp32, bf16 and fp16 plans only (y3_net_plan)
     int nclasses = 0;
     // plan
     int max_batch = 0, height = 0, width = 0, dtype = Y3_DTYPE_F32;   // the planned canvas: height x width (0: no plan)
@@ -175,7 +177,12 @@ struct y3_net {
 
 inline int rows(const y3_net *n, int t) { return n->height / n->tensors[t].div; }
 inline int cols(const y3_net *n, int t) { return n->width / n->tensors[t].div; }
-inline bool is_output(const y3_net *net, int t) { return t == net->outputs[0] || t == net->outputs[1] || t == net->outputs[2]; }
+inline bool is_output(const y3_net *net, int t)
+{
+    for (int k = 0; k < net->n_heads; ++k)
+        if (t == net->outputs[k]) return true;
+    return false;
+}
 
 namespace y3 {
 
@@ -258,7 +265,7 @@ y3_status resolve_i8(y3_net *net);
 y3_status upload_i8_scales(y3_net *net, int slot);
 void free_plan(y3_net *net);
 
-// y3_net_detect scratch for `batch` images: grid sizes {gh, gw}, boxes per image, byte offsets of the parts and their total
+// y3_net_detect scratch for `batch` images: grid sizes {gh, gw} of the net's heads, boxes per image, byte offsets of the parts and their total
 struct DetectLayout {
     int32_t gs[3][2];
     size_t n_boxes;
@@ -269,12 +276,12 @@ struct DetectLayout {
 };
 DetectLayout detect_layout(const y3_net *net, int batch);
 
-// y3_yolo_decode_scores_hw under the caller's name `who`
-y3_status decode_scores_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+// y3_yolo_decode_scores_hw_n under the caller's name `who`
+y3_status decode_scores_hw(const char *who, const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
                            const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream);
 
-// y3_yolo_decode_candidates_hw under the caller's name `who`
-y3_status decode_candidates_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+// y3_yolo_decode_candidates_hw_n under the caller's name `who`
+y3_status decode_candidates_hw(const char *who, const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
                                const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev, int64_t *cand_cls_dev,
                                float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev, void *workspace_dev, size_t workspace_bytes,
                                void *stream);

@@ -834,12 +834,13 @@ int y3_choose_tile(int dtype, int size, int stride, int cin, int c0, int cout, l
     return family_tile(*f, c, M, M_plan, arena_out != 0);
 }
 
-y3_status y3_net_create(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
-                        const y3_conv_desc *convs, int n_convs, const y3_aux_desc *aux, int n_aux, int input_tensor,
-                        const int32_t outputs[3], int nclasses, y3_net **out)
+y3_status y3_net_create_heads(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
+                              const y3_conv_desc *convs, int n_convs, const y3_aux_desc *aux, int n_aux, int input_tensor,
+                              const int32_t *outputs, int n_outputs, int nclasses, y3_net **out)
 try {
     if (!tensors || !op_kinds || !convs || !outputs || !out || n_tensors <= 0 || n_ops <= 0 || n_convs < 0 || n_aux < 0)
         return fail(Y3_ERR_INVALID, "y3_net_create: null, empty or negative-count argument");
+    if (n_outputs != 2 && n_outputs != 3) return fail(Y3_ERR_INVALID, "y3_net_create_heads: a net has 2 or 3 outputs (got %d)", n_outputs);
     if (y3::test_fail_alloc()) throw std::bad_alloc();   // tests only: the allocation below failing
     std::unique_ptr<y3_net> net(new y3_net());           // released to the caller on success only: no path leaks it, thrown ones included
     if (hipGetDevice(&net->device) != hipSuccess) return fail(Y3_ERR_NODEVICE, "y3_net_create: no HIP device");
@@ -879,7 +880,17 @@ try {
     }
     if (bad_t(input_tensor)) { return fail(Y3_ERR_INVALID, "y3_net_create: bad input tensor"); }
     net->input_tensor = input_tensor;
-    for (int i = 0; i < 3; ++i) {
+    for (const y3_aux_desc &x : net->aux) {
+        if (x.kind != Y3_AUX_MAXPOOL2X2_S2 && x.kind != Y3_AUX_MAXPOOL2X2_S1) continue;
+        const int up = x.kind == Y3_AUX_MAXPOOL2X2_S2 ? 2 : 1;
+        if (bad_t(x.src0) || bad_t(x.dst) || tensors[x.src0].channels % 32 || tensors[x.dst].channels != tensors[x.src0].channels ||
+            tensors[x.dst].div != tensors[x.src0].div * up)
+            return fail(Y3_ERR_INVALID, "y3_net_create: max-pool op (kind %d) needs a source of Cin %% 32 == 0 channels and a destination of "
+                                        "the same width at %s", x.kind, up == 2 ? "twice the source's div" : "the source's div");
+        net->has_pool = true;
+    }
+    net->n_heads = n_outputs;
+    for (int i = 0; i < n_outputs; ++i) {
         // nclasses == 0: raw feature outputs (layer tests); otherwise the yolo head layout is enforced
         if (bad_t(outputs[i]) || (nclasses > 0 && tensors[outputs[i]].channels != 3 * (5 + nclasses))) {
             return fail(Y3_ERR_INVALID, "y3_net_create: output %d must have 3*(5+nclasses) channels", i);
@@ -894,7 +905,17 @@ try {
     *out = net.release();
     return Y3_OK;
 }
+Y3_CATCH("y3_net_create_heads")
+
+y3_status y3_net_create(const y3_tensor_desc *tensors, int n_tensors, const int32_t *op_kinds, int n_ops,
+                        const y3_conv_desc *convs, int n_convs, const y3_aux_desc *aux, int n_aux, int input_tensor,
+                        const int32_t outputs[3], int nclasses, y3_net **out)
+try {
+    return y3_net_create_heads(tensors, n_tensors, op_kinds, n_ops, convs, n_convs, aux, n_aux, input_tensor, outputs, 3, nclasses, out);
+}
 Y3_CATCH("y3_net_create")
+
+int y3_net_heads(const y3_net *net) { return net ? net->n_heads : 0; }
 
 void y3_net_destroy(y3_net *net)
 {

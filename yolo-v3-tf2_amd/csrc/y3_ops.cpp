@@ -118,15 +118,16 @@ y3_status view_geometries(const char *who, const char *noun, const Desc *descs_h
 }  // namespace
 
 // ------------------------------------------------------------------------------------------ decode
-// gs: grid_hw[3][2] = {gh, gw} per scale (the square entry points hand {g, g})
+// gs: grid_hw[ns][2] = {gh, gw} per scale (the square entry points hand {g, g}); ns: scales, 1..3 (the three-scale entry points hand 3)
 // The checks every decode entry shares, and the by-value arguments of its launch: grid sizes, first box of each scale, anchors
-static y3_status decode_args(const float *const grids[3], const int32_t (*gs)[2], int batch, int nc, const float *anchors, const char *who,
+static y3_status decode_args(const float *const *grids, const int32_t (*gs)[2], int ns, int batch, int nc, const float *anchors, const char *who,
                              y3::DecodeArgs *out)
 {
     if (!grids || !gs || !anchors || batch <= 0 || nc <= 0) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
-    y3::DecodeArgs a{};
+    if (ns < 1 || ns > 3) return fail(Y3_ERR_INVALID, "%s: 1 to 3 scales (got %d)", who, ns);
+    y3::DecodeArgs a{};   // a scale behind ns stays empty: no boxes, no workgroup
     int off = 0;
-    for (int s = 0; s < 3; ++s) {
+    for (int s = 0; s < ns; ++s) {
         if (!grids[s] || gs[s][0] <= 0 || gs[s][1] <= 0 || ((uintptr_t)grids[s] & 15))
             return fail(Y3_ERR_INVALID, "%s: grid %d null, empty or not 16-byte aligned", who, s);
         a.grid[s] = grids[s];
@@ -146,31 +147,32 @@ static y3_status decode_args(const float *const grids[3], const int32_t (*gs)[2]
     return Y3_OK;
 }
 
-static y3_status decode_common(const float *const grids[3], const int32_t (*gs)[2], int batch, int nc,
+static y3_status decode_common(const float *const *grids, const int32_t (*gs)[2], int ns, int batch, int nc,
                                const float *anchors, float *bboxes, float *conf, float *probs, int64_t *cls,
                                float *scores, void *stream, const char *who)
 {
     if (!bboxes) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
     y3::DecodeArgs a{};
-    if (y3_status st = decode_args(grids, gs, batch, nc, anchors, who, &a); st != Y3_OK) return st;
+    if (y3_status st = decode_args(grids, gs, ns, batch, nc, anchors, who, &a); st != Y3_OK) return st;
     if ((uintptr_t)bboxes & 15) return fail(Y3_ERR_INVALID, "%s: bboxes not 16-byte aligned", who);
     hipError_t e = y3::launch_decode(a, bboxes, conf, probs, cls, scores, (hipStream_t)stream);
     if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
     return Y3_OK;
 }
 
-// boxes per image of the three grids, 0 when a side is < 1 or the count leaves an int
-static long long grid_boxes(const int32_t (*gs)[2])
+// boxes per image of the ns grids, 0 when ns is not 1..3, a side is < 1 or the count leaves an int
+static long long grid_boxes(const int32_t (*gs)[2], int ns)
 {
     long long n = 0;
-    for (int s = 0; s < 3; ++s) {
+    if (ns < 1 || ns > 3) return 0;
+    for (int s = 0; s < ns; ++s) {
         if (gs[s][0] <= 0 || gs[s][1] <= 0) return 0;
         n += 3ll * gs[s][0] * gs[s][1];
     }
     return n <= 0x7fffffffll ? n : 0;
 }
 
-y3_status y3::decode_candidates_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+y3_status y3::decode_candidates_hw(const char *who, const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
                                    const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
                                    int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,
                                    void *workspace_dev, size_t workspace_bytes, void *stream)
@@ -179,7 +181,8 @@ y3_status y3::decode_candidates_hw(const char *who, const float *const grids_dev
         return fail(Y3_ERR_INVALID, "%s: null pointer", who);
     if (batch < 1 || capacity < 1 || nclasses < 1)
         return fail(Y3_ERR_INVALID, "%s: batch, capacity and nclasses must be at least 1 (got %d, %d, %d)", who, batch, capacity, nclasses);
-    const long long N = grid_boxes(grid_hw);
+    if (n_scales < 1 || n_scales > 3) return fail(Y3_ERR_INVALID, "%s: 1 to 3 scales (got %d)", who, n_scales);
+    const long long N = grid_boxes(grid_hw, n_scales);
     if (N <= 0) return fail(Y3_ERR_INVALID, "%s: grid sides must be at least 1 and the boxes per image below 2^31", who);
     if ((long long)batch * capacity > 0x7fffffffll || N * nclasses > 0x7fffffffll || (long long)batch * N > 0x7fffffffll)
         return fail(Y3_ERR_INVALID, "%s: batch * capacity, N * nclasses and batch * N must stay below 2^31 (got %d x %d, %lld x %d)", who, batch,
@@ -187,7 +190,7 @@ y3_status y3::decode_candidates_hw(const char *who, const float *const grids_dev
     if (y3::decode_lds_bytes(nclasses) > 160 * 1024)
         return fail(Y3_ERR_INVALID, "%s: %d classes need %zu bytes of LDS, at most %d", who, nclasses, y3::decode_lds_bytes(nclasses), 160 * 1024);
     y3::DecodeArgs a{};
-    if (y3_status st = decode_args(grids_dev, grid_hw, batch, nclasses, anchors_host, who, &a); st != Y3_OK) return st;
+    if (y3_status st = decode_args(grids_dev, grid_hw, n_scales, batch, nclasses, anchors_host, who, &a); st != Y3_OK) return st;
     if ((uintptr_t)cand_boxes_dev & 15) return fail(Y3_ERR_INVALID, "%s: cand_boxes not 16-byte aligned", who);
     if (((uintptr_t)cand_cls_dev & 7) || ((uintptr_t)cand_scores_dev & 3) || ((uintptr_t)cand_src_dev & 3) || ((uintptr_t)totals_dev & 3))
         return fail(Y3_ERR_INVALID, "%s: cand_cls not 8-byte or cand_scores / cand_src / totals not 4-byte aligned", who);
@@ -201,18 +204,18 @@ y3_status y3::decode_candidates_hw(const char *who, const float *const grids_dev
 }
 
 // The square entry points are the _hw ones with {g, g}; `who` names the entry point the caller used in the messages.
-static y3_status yolo_decode_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
+static y3_status yolo_decode_hw(const char *who, const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
                                 const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
 {
     if (!conf_dev || !probs_dev) return fail(Y3_ERR_INVALID, "%s: null output", who);
-    return decode_common(grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, nullptr, nullptr, stream, who);
+    return decode_common(grids_dev, grid_hw, n_scales, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, nullptr, nullptr, stream, who);
 }
 
-y3_status y3::decode_scores_hw(const char *who, const float *const grids_dev[3], const int32_t (*grid_hw)[2], int batch, int nclasses,
-                                       const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream)
+y3_status y3::decode_scores_hw(const char *who, const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
+                               const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev, void *stream)
 {
     if (!class_idx_dev || !scores_dev) return fail(Y3_ERR_INVALID, "%s: null output", who);
-    return decode_common(grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, nullptr, nullptr, class_idx_dev, scores_dev, stream, who);
+    return decode_common(grids_dev, grid_hw, n_scales, batch, nclasses, anchors_host, bboxes_dev, nullptr, nullptr, class_idx_dev, scores_dev, stream, who);
 }
 
 extern "C" {
@@ -619,15 +622,50 @@ uint32_t y3_crc32c(const void *data_host, size_t nbytes)
 y3_status y3_yolo_decode_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
                             const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
 try {
-    return yolo_decode_hw("y3_yolo_decode_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
+    return yolo_decode_hw("y3_yolo_decode_hw", grids_dev, grid_hw, 3, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
 }
 Y3_CATCH("y3_yolo_decode_hw")
+
+y3_status y3_yolo_decode_hw_n(const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
+                              const float *anchors_host, float *bboxes_dev, float *conf_dev, float *probs_dev, void *stream)
+try {
+    return yolo_decode_hw("y3_yolo_decode_hw_n", grids_dev, grid_hw, n_scales, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode_hw_n")
+
+y3_status y3_yolo_decode_scores_hw_n(const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
+                                     const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev, float *scores_dev,
+                                     void *stream)
+try {
+    return y3::decode_scores_hw("y3_yolo_decode_scores_hw_n", grids_dev, grid_hw, n_scales, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+}
+Y3_CATCH("y3_yolo_decode_scores_hw_n")
+
+y3_status y3_maxpool2x2(const void *src_dev, void *dst_dev, int batch, int height, int width, int channels, int stride, int dtype,
+                        void *stream)
+try {
+    const char *who = "y3_maxpool2x2";
+    if (!src_dev || !dst_dev || batch < 1 || height < 1 || width < 1 || channels < 1) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
+    if (dtype != Y3_DTYPE_F32 && dtype != Y3_DTYPE_BF16 && dtype != Y3_DTYPE_F16)
+        return fail(Y3_ERR_INVALID, "%s: dtype must be Y3_DTYPE_F32, Y3_DTYPE_BF16 or Y3_DTYPE_F16 (got %d)", who, dtype);
+    if (stride != 1 && stride != 2) return fail(Y3_ERR_INVALID, "%s: stride must be 1 or 2 (got %d)", who, stride);
+    if (stride == 2 && ((height | width) & 1)) return fail(Y3_ERR_INVALID, "%s: a stride-2 pool needs even extents (got %d x %d)", who, height, width);
+    const int eb = dtype == Y3_DTYPE_F32 ? 4 : 2;
+    if (((long long)channels * eb) % 16) return fail(Y3_ERR_INVALID, "%s: %d channels of %d bytes are no multiple of 16 bytes", who, channels, eb);
+    if (((uintptr_t)src_dev & 15) || ((uintptr_t)dst_dev & 15)) return fail(Y3_ERR_INVALID, "%s: src / dst not 16-byte aligned", who);
+    if ((long long)batch * (height / stride) > 0x7fffffffll || (long long)(width / stride) * channels * eb / 16 > 0x00ffffffll)
+        return fail(Y3_ERR_INVALID, "%s: batch * output rows must stay below 2^31 and an output row below 2^28 bytes", who);
+    hipError_t e = y3::launch_maxpool2x2(src_dev, dst_dev, batch, height, width, channels, stride, dtype, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(Y3_ERR_HIP, "%s launch: %s", who, hipGetErrorString(e));
+    return Y3_OK;
+}
+Y3_CATCH("y3_maxpool2x2")
 
 y3_status y3_yolo_decode_scores_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
                                    const float *anchors_host, float *bboxes_dev, int64_t *class_idx_dev,
                                    float *scores_dev, void *stream)
 try {
-    return y3::decode_scores_hw("y3_yolo_decode_scores_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+    return y3::decode_scores_hw("y3_yolo_decode_scores_hw", grids_dev, grid_hw, 3, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
 }
 Y3_CATCH("y3_yolo_decode_scores_hw")
 
@@ -637,7 +675,7 @@ try {
     if (!conf_dev || !probs_dev) return fail(Y3_ERR_INVALID, "y3_yolo_decode: null output");
     if (!grid_sizes) return fail(Y3_ERR_INVALID, "y3_yolo_decode: bad argument");
     const int32_t hw[3][2] = {{grid_sizes[0], grid_sizes[0]}, {grid_sizes[1], grid_sizes[1]}, {grid_sizes[2], grid_sizes[2]}};
-    return yolo_decode_hw("y3_yolo_decode", grids_dev, hw, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
+    return yolo_decode_hw("y3_yolo_decode", grids_dev, hw, 3, batch, nclasses, anchors_host, bboxes_dev, conf_dev, probs_dev, stream);
 }
 Y3_CATCH("y3_yolo_decode")
 
@@ -648,24 +686,40 @@ try {
     if (!class_idx_dev || !scores_dev) return fail(Y3_ERR_INVALID, "y3_yolo_decode_scores: null output");
     if (!grid_sizes) return fail(Y3_ERR_INVALID, "y3_yolo_decode_scores: bad argument");
     const int32_t hw[3][2] = {{grid_sizes[0], grid_sizes[0]}, {grid_sizes[1], grid_sizes[1]}, {grid_sizes[2], grid_sizes[2]}};
-    return y3::decode_scores_hw("y3_yolo_decode_scores", grids_dev, hw, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
+    return y3::decode_scores_hw("y3_yolo_decode_scores", grids_dev, hw, 3, batch, nclasses, anchors_host, bboxes_dev, class_idx_dev, scores_dev, stream);
 }
 Y3_CATCH("y3_yolo_decode_scores")
 
-size_t y3_decode_candidates_workspace_bytes(const int32_t grid_hw[3][2], int batch, int nclasses)
+size_t y3_decode_candidates_workspace_bytes_n(const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses)
 {
     if (!grid_hw || batch < 1 || nclasses < 1) return 0;
-    const long long N = grid_boxes(grid_hw);
+    const long long N = grid_boxes(grid_hw, n_scales);
     if (N <= 0 || (long long)batch * N > 0x7fffffffll) return 0;
     return (size_t)batch * (size_t)N * sizeof(int32_t);
 }
+
+size_t y3_decode_candidates_workspace_bytes(const int32_t grid_hw[3][2], int batch, int nclasses)
+{
+    return y3_decode_candidates_workspace_bytes_n(grid_hw, 3, batch, nclasses);
+}
+
+y3_status y3_yolo_decode_candidates_hw_n(const float *const *grids_dev, const int32_t (*grid_hw)[2], int n_scales, int batch, int nclasses,
+                                         const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
+                                         int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,
+                                         void *workspace_dev, size_t workspace_bytes, void *stream)
+try {
+    return y3::decode_candidates_hw("y3_yolo_decode_candidates_hw_n", grids_dev, grid_hw, n_scales, batch, nclasses, anchors_host, score_threshold,
+                                    capacity, cand_boxes_dev, cand_cls_dev, cand_scores_dev, cand_src_dev, totals_dev, workspace_dev,
+                                    workspace_bytes, stream);
+}
+Y3_CATCH("y3_yolo_decode_candidates_hw_n")
 
 y3_status y3_yolo_decode_candidates_hw(const float *const grids_dev[3], const int32_t grid_hw[3][2], int batch, int nclasses,
                                        const float *anchors_host, float score_threshold, int capacity, float *cand_boxes_dev,
                                        int64_t *cand_cls_dev, float *cand_scores_dev, int32_t *cand_src_dev, int32_t *totals_dev,
                                        void *workspace_dev, size_t workspace_bytes, void *stream)
 try {
-    return y3::decode_candidates_hw("y3_yolo_decode_candidates_hw", grids_dev, grid_hw, batch, nclasses, anchors_host, score_threshold, capacity,
+    return y3::decode_candidates_hw("y3_yolo_decode_candidates_hw", grids_dev, grid_hw, 3, batch, nclasses, anchors_host, score_threshold, capacity,
                                     cand_boxes_dev, cand_cls_dev, cand_scores_dev, cand_src_dev, totals_dev, workspace_dev, workspace_bytes, stream);
 }
 Y3_CATCH("y3_yolo_decode_candidates_hw")

@@ -211,7 +211,7 @@ y3::DetectLayout y3::detect_layout(const y3_net *net, int batch)
     auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
     DetectLayout L{};
     size_t n = 0, at = 0;
-    for (int i = 0; i < 3; ++i) {
+    for (int i = 0; i < net->n_heads; ++i) {
         L.gs[i][0] = rows(net, net->outputs[i]);
         L.gs[i][1] = cols(net, net->outputs[i]);
         L.grid[i] = at;
@@ -240,6 +240,10 @@ y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int 
 try {
     if (!net || max_batch <= 0 || height <= 0 || width <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
     if (!y3::conv_family(dtype)) return fail(Y3_ERR_INVALID, "y3_net_plan: unknown dtype %d", dtype);
+    if (net->has_pool && (dtype == Y3_DTYPE_F32X3 || dtype == Y3_DTYPE_F32X2 || dtype == Y3_DTYPE_I8))
+        return fail(Y3_ERR_INVALID, "y3_net_plan: the net holds a max-pool op (Y3_AUX_MAXPOOL2X2_*), which %s; "
+                                    "Y3_DTYPE_F32, Y3_DTYPE_BF16 and Y3_DTYPE_F16 run it",
+                    dtype == Y3_DTYPE_I8 ? "has no calibrated int8 form" : "does not read plane-split tensors");
     for (const y3_tensor_desc &t : net->tensors)
         if (t.div <= 0 || height % t.div || width % t.div) {
             if (height == width) return fail(Y3_ERR_INVALID, "y3_net_plan: image_size %d not divisible by %d", height, t.div);   // the square call's text, as ever
@@ -283,7 +287,7 @@ try {
     // (output_staged), so a launch that stores an fp32 grid itself (out_slot >= 0) is never a first layer and never has a residual.
     net->staged.assign(nt, 0);
     net->out_slot.assign(nt, -1);
-    for (int k = 2; k >= 0; --k) {   // a tensor named twice takes the first grid
+    for (int k = net->n_heads - 1; k >= 0; --k) {   // a tensor named twice takes the first grid
         const int t = net->outputs[k];
         net->staged[t] = dtype != Y3_DTYPE_F32 && y3::output_staged(net, t);
         net->out_slot[t] = net->staged[t] ? -1 : (signed char)k;

@@ -4,11 +4,12 @@ Reads the model YAML schema of the reference's graph builder
 (reference: core/parse_model.py:216-314 `create_sub_model_inputs`,
 `create_sub_model_layers`, `build_model`) and produces
 
-  * a node list with the reference's layer semantics (conv / shortcut / route /
-    upsample / yolo, reference: core/parse_model.py:13-56,59-75,102-160,209-213);
+  * a node list with the reference's layer semantics (conv / maxpool / shortcut / route /
+    upsample / yolo, reference: core/parse_model.py:13-56,59-75,78-99,102-160,209-213);
   * a *lowered* program for the HIP runtime in which BatchNorm, LeakyReLU, the
     shortcut add and the nearest-upsample + channel-concat feeding a 1x1 conv
-    are folded into the conv launches.
+    are folded into the conv launches.  A max-pool is never folded: it
+    is an op of its own between two conv launches.
 
 No arithmetic happens here; this is host logic only and runs without a GPU.
 """
@@ -65,10 +66,10 @@ class Tensor:
 
 @dataclass
 class Node:
-    kind: str                       # conv | add | upsample | concat | yolo
+    kind: str                       # conv | maxpool | add | upsample | concat | yolo
     inputs: List[int]
     output: int
-    # conv attributes
+    # conv attributes (maxpool: size 2, stride 1 or 2)
     size: int = 0
     stride: int = 1
     filters: int = 0
@@ -80,7 +81,8 @@ class Node:
 
 @dataclass
 class ConvOp:
-    """One launch of the fused conv kernel."""
+    """One launch of the fused conv kernel.  cin / c0 / cout are the widths the launch sees: the stored widths of its tensors
+    (Program.stored), which exceed the node's real widths where the lowering pads channels."""
     conv_index: int
     size: int
     stride: int
@@ -100,7 +102,7 @@ class ConvOp:
 
 @dataclass
 class AuxOp:
-    kind: str                       # add | upsample | concat
+    kind: str                       # add | upsample | concat | maxpool_s2 | maxpool_s1
     inputs: List[int]
     dst: int
 
@@ -111,9 +113,13 @@ class Program:
     nodes: List[Node]
     ops: list                       # ConvOp | AuxOp in execution order
     input_tensor: int
-    outputs: List[int]              # head outputs in model order (13, 26, 52 grid)
+    outputs: List[int]              # head outputs in model order, coarsest grid first: three (YOLOv3) or two (YOLOv3-tiny)
     nclasses: int
     conv_nodes: List[Node] = field(default_factory=list)
+    # per tensor id: the channel count the device stores (_lower).  tensors[t].channels everywhere except behind a conv whose
+    # output width is no multiple of 32 and feeds another conv, directly or through pools: that tensor and the pooled ones are
+    # stored padded to the next multiple of 32, the pad channels exact zeros (weights.pad_weights).
+    stored: List[int] = field(default_factory=list)
     model_config_file: Optional[str] = None   # the model.yaml this program was read from (load_program)
 
     def conv_ops(self) -> List[ConvOp]:
@@ -173,6 +179,27 @@ class _Builder:
                                bn="batch_normalize" in conf, leaky=(act == "leaky"),
                                conv_index=self.nconv, sub_model=sub))
         self.nconv += 1
+        return out
+
+    # reference: core/parse_model.py:78-99 (MaxPooling2D(size, stride, 'same'))
+    def maxpool(self, x, conf, sub):
+        who = f"{sub}.maxpool (layer {len(self.nodes)})"
+        try:
+            size, stride = [int(v) for v in conf["size_xy"]], [int(v) for v in conf["stride_xy"]]
+        except (KeyError, TypeError, ValueError):
+            raise ValueError(f"{who}: needs size_xy and stride_xy, two ints each") from None
+        if len(size) != 2 or len(stride) != 2 or size[0] != size[1] or stride[0] != stride[1]:
+            raise ValueError(f"{who}: size_xy {size} / stride_xy {stride}: only equal x and y are supported")
+        if size[0] != 2 or stride[0] not in (1, 2):
+            raise ValueError(f"{who}: size {size[0]} stride {stride[0]}: only the 2x2 pools of stride 1 and 2 are supported")
+        if conf.get("padding", "valid") != "same":
+            raise ValueError(f"{who}: padding {conf.get('padding', 'valid')!r}: only 'same' is supported")
+        t = self.tensors[x]
+        if stride[0] == 2 and t.div >= 32:
+            raise ValueError(f"{who}: a stride-2 pool on a 1/{t.div} tensor: its extent is odd for image sizes that are "
+                             f"multiples of 32 only")
+        out = self.new_tensor(t.channels, t.div * stride[0], f"{sub}.maxpool")
+        self.nodes.append(Node("maxpool", [x], out, size=2, stride=stride[0], sub_model=sub))
         return out
 
     # reference: core/parse_model.py:143-160
@@ -246,8 +273,9 @@ class _Builder:
                 x = self.route(conf, inputs, layers, sub)
             elif kind == "upsample":
                 x = self.upsample(x, conf, sub)
+            elif kind == "maxpool":
+                x = self.maxpool(x, conf, sub)
             else:
-                # 'maxpool' (tiny model only) is outside the hot path: SURVEY.md section 2
                 raise ValueError("{} not recognized as layer_conf type".format(kind))
             layers.append(x)
         return layers
@@ -339,6 +367,33 @@ def _lower(p: Program):
             t = alias[t]
         return t
 
+    # Channel padding: a conv output of a width that is no multiple of 32 is stored padded when everything that reads it, directly
+    # or through pools only, is a conv (the device's convs take Cin % 32 == 0); the pools carry the padded width.
+    stored = [t.channels for t in p.tensors]
+    for n in p.nodes:
+        if n.kind != "conv" or n.filters % 32 == 0:
+            continue
+        chain, todo, convs = [n.output], [n.output], 0
+        while todo:
+            t = todo.pop()
+            if t in external:
+                convs = -1
+                break
+            for c in consumers.get(t, []):
+                if c.kind == "maxpool":
+                    chain.append(c.output)
+                    todo.append(c.output)
+                elif c.kind == "conv" and convs >= 0:
+                    convs += 1
+                else:
+                    convs = -1
+            if convs < 0:
+                break
+        if convs > 0:
+            for t in chain:
+                stored[t] = (n.filters + 31) // 32 * 32
+    p.stored = stored
+
     ops = []
     for n in p.nodes:
         if n.kind == "yolo":
@@ -347,8 +402,8 @@ def _lower(p: Program):
         if n.kind == "conv":
             src = n.inputs[0]
             tin = p.tensors[src]
-            op = ConvOp(n.conv_index, n.size, n.stride, tin.channels, n.filters, n.bn, n.leaky,
-                        src0=real(src), src0_upsample=False, c0=tin.channels, src1=-1, residual=-1,
+            op = ConvOp(n.conv_index, n.size, n.stride, stored[src], stored[n.output], n.bn, n.leaky,
+                        src0=real(src), src0_upsample=False, c0=stored[src], src1=-1, residual=-1,
                         dst=n.output, in_div=tin.div, out_div=p.tensors[n.output].div)
             pn = producer.get(src)
             # K6: [upsample(a), b] concat -> 1x1 conv; read both sources in the conv's A-gather
@@ -379,6 +434,8 @@ def _lower(p: Program):
             if n.output in folded:
                 continue
             ops.append(AuxOp(n.kind, [real(i) for i in n.inputs], n.output))
+        elif n.kind == "maxpool":               # never folded
+            ops.append(AuxOp(f"maxpool_s{n.stride}", [real(n.inputs[0])], n.output))
     # drop aux producers that were folded away before being visited (upsample/concat precede the conv)
     ops = [o for o in ops if not (isinstance(o, AuxOp) and o.dst in folded)]
     p.ops = ops

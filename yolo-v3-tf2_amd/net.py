@@ -14,9 +14,10 @@ from ._args import _anchors, _dev, _fptr, _images_arg, _need_cuda
 from ._lib import AuxDesc, ConvDesc, TensorDesc, Y3Error, check
 from .graph import AuxOp, ConvOp, Program
 from .input_stage import canvas_hw
-from .weights import BN_EPS
+from .weights import BN_EPS, pad_weights
 
-_AUX_KIND = {"add": _lib.Y3_AUX_ADD, "upsample": _lib.Y3_AUX_UPSAMPLE2X, "concat": _lib.Y3_AUX_CONCAT}
+_AUX_KIND = {"add": _lib.Y3_AUX_ADD, "upsample": _lib.Y3_AUX_UPSAMPLE2X, "concat": _lib.Y3_AUX_CONCAT,
+             "maxpool_s2": _lib.Y3_AUX_MAXPOOL2X2_S2, "maxpool_s1": _lib.Y3_AUX_MAXPOOL2X2_S1}
 # plan dtype -> the suffix of its tile setter (y3_net_set_tile*): fp16 and int8 plans run the 16-bit conv family's tiles
 _TILE_KIND = {_lib.Y3_DTYPE_F32: "", _lib.Y3_DTYPE_BF16: "_bf16", _lib.Y3_DTYPE_F32X3: "_x3", _lib.Y3_DTYPE_F32X2: "_x2",
               _lib.Y3_DTYPE_F16: "_bf16", _lib.Y3_DTYPE_I8: "_bf16"}
@@ -53,7 +54,10 @@ class Net:
         self.program = program
         self.lib = _lib.load()
         p = program
-        tens = (TensorDesc * len(p.tensors))(*[TensorDesc(t.channels, t.div) for t in p.tensors])
+        # the device holds the stored widths (graph.Program.stored: padded where a narrow conv output feeds a conv); read_tensor,
+        # flops_per_image and the weight dictionary stay at the real ones
+        self._stored = list(p.stored) if p.stored else [t.channels for t in p.tensors]
+        tens = (TensorDesc * len(p.tensors))(*[TensorDesc(c, t.div) for c, t in zip(self._stored, p.tensors)])
         kinds, convs, auxs = [], [], []
         self.conv_ops: List[ConvOp] = []
         for o in p.ops:
@@ -65,15 +69,21 @@ class Net:
             elif isinstance(o, AuxOp):
                 kinds.append(1)
                 auxs.append(AuxDesc(_AUX_KIND[o.kind], o.inputs[0], o.inputs[1] if len(o.inputs) > 1 else -1, o.dst))
-        if len(p.outputs) != 3:
-            raise Y3Error("the HIP path expects exactly three detection heads")
+        if len(p.outputs) not in (2, 3):
+            raise Y3Error(f"the HIP path runs nets of two or three detection heads (this program has {len(p.outputs)})")
+        self.heads = len(p.outputs)
         self._h = C.c_void_p()
         k_arr = (C.c_int32 * len(kinds))(*kinds)
         c_arr = (ConvDesc * max(1, len(convs)))(*convs)
         a_arr = (AuxDesc * max(1, len(auxs)))(*auxs)
-        outs = (C.c_int32 * 3)(*p.outputs)
-        check(self.lib.y3_net_create(tens, len(p.tensors), k_arr, len(kinds), c_arr, len(convs), a_arr, len(auxs),
-                                     p.input_tensor, outs, p.nclasses, C.byref(self._h)), "y3_net_create")
+        outs = (C.c_int32 * self.heads)(*p.outputs)
+        if self.heads == 3 and getattr(self.lib.y3_net_create_heads, "missing", False):      # an older build under Y3_LIB_PATH: three heads only
+            st = self.lib.y3_net_create(tens, len(p.tensors), k_arr, len(kinds), c_arr, len(convs), a_arr, len(auxs), p.input_tensor, outs,
+                                        p.nclasses, C.byref(self._h))
+        else:
+            st = self.lib.y3_net_create_heads(tens, len(p.tensors), k_arr, len(kinds), c_arr, len(convs), a_arr, len(auxs), p.input_tensor,
+                                              outs, self.heads, p.nclasses, C.byref(self._h))
+        check(st, "y3_net_create")
         self.image_size = 0
         self._tiles, self._merge_iou_threshold = None, None      # the properties tiles / merge_iou_threshold
         self.canvas = (0, 0)     # the planned (H, W); image_size is the int S for a plan made with an int
@@ -89,6 +99,16 @@ class Net:
 
     # -- weights ----------------------------------------------------------------------------------
     def load_weights(self, weights: Dict[str, np.ndarray], eps: float = BN_EPS):
+        """weights: the dictionary at the real widths of the program's nodes; where the lowering pads channels the upload is padded
+        (weights.pad_weights: zero rows and filters, BN statistics that make the pad channels exact zeros)."""
+        p = self.program
+        real = {n.conv_index: (n.size, n.size, p.tensors[n.inputs[0]].channels, n.filters) for n in p.conv_nodes}
+        for o in self.conv_ops:
+            shape = np.shape(weights[f"conv{o.conv_index}.w"])
+            if tuple(shape) != real[o.conv_index]:
+                raise Y3Error(f"conv{o.conv_index}.w has shape {tuple(shape)}, expected {real[o.conv_index]}")
+        if self._stored != [t.channels for t in p.tensors]:
+            weights = pad_weights(p, weights)
         for slot, o in enumerate(self.conv_ops):
             i = o.conv_index
             w = np.ascontiguousarray(weights[f"conv{i}.w"], np.float32)
@@ -433,7 +453,7 @@ class Net:
         return B
 
     def forward(self, images: torch.Tensor, out: Optional[Sequence[torch.Tensor]] = None) -> List[torch.Tensor]:
-        """images [B,H,W,3] fp32 on the GPU -> [grid13, grid26, grid52], each [B,gh,gw,3,5+nc]."""
+        """images [B,H,W,3] fp32 on the GPU -> the head grids, coarsest first (three, or two for a two-head net), each [B,gh,gw,3,5+nc]."""
         _need_cuda(images)
         cin = self.program.tensors[self.program.input_tensor].channels
         # bf16 / fp16 plan + an input that feeds an MFMA conv directly (layer tests): the input is bf16 / fp16 as well
@@ -459,18 +479,23 @@ class Net:
                 out = [torch.empty((B, gh, gw, self.program.tensors[o].channels), dtype=torch.float32,
                                    device=images.device) for (gh, gw), o in zip(gs, self.program.outputs)]
         _need_cuda(*out)
-        ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in out])
+        ptrs = self._grid_ptrs(out)
         check(self.lib.y3_net_forward(self._h, _dev(images), B, ptrs, _lib.stream_ptr()), "y3_net_forward")
         return list(out)
 
     __call__ = forward
+
+    def _grid_ptrs(self, out):
+        if len(out) != self.heads:
+            raise Y3Error(f"expected {self.heads} head grids (got {len(out)})")
+        return (C.c_void_p * self.heads)(*[t.data_ptr() for t in out])
 
     def measure_sclk(self, images: torch.Tensor, out: Sequence[torch.Tensor], forwards: int = 30, conv: int = -1) -> float:
         """Shader clock (MHz) the chip holds under this network's load: `forwards` forwards back to back, in the last one
         a conv launch stamps s_memtime / s_memrealtime (y3_net_measure_sclk: the conv with the most FLOPs; conv >= 0:
         that conv slot, y3_net_measure_sclk_conv).  Raises when no launch of the plan / not that launch carries stamps."""
         _need_cuda(images, *out)
-        ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in out])
+        ptrs = self._grid_ptrs(out)
         mhz = C.c_float()
         if conv >= 0:
             check(self.lib.y3_net_measure_sclk_conv(self._h, _dev(images), images.shape[0], ptrs, int(forwards), int(conv),
@@ -484,7 +509,7 @@ class Net:
         """Per conv slot: (MHz, start_us, end_us) of the stamped workgroup of its launch in the last of `forwards`
         back-to-back forwards (y3_net_measure_sclk_all); MHz 0 where a conv leaves no stamps.  numpy arrays."""
         _need_cuda(images, *out)
-        ptrs = (C.c_void_p * 3)(*[t.data_ptr() for t in out])
+        ptrs = self._grid_ptrs(out)
         n = len(self.conv_ops)
         mhz = (C.c_float * n)()
         t0 = (C.c_double * n)()
@@ -493,15 +518,15 @@ class Net:
                                                _lib.stream_ptr()), "y3_net_measure_sclk_all")
         return np.array(mhz[:], dtype=np.float64), np.array(t0[:]), np.array(t1[:])
 
-    def _read_tensor(self, sfx: str, dtype, tensor_id: int, batch: int) -> torch.Tensor:
+    def _read_tensor(self, sfx: str, dtype, tensor_id: int, batch: int, stored=False) -> torch.Tensor:
         fn, what = getattr(self.lib, "y3_net_read_tensor" + sfx), "y3_net_read_tensor" + sfx
         n = C.c_size_t()
         check(fn(self._h, tensor_id, batch, None, C.byref(n), None), what)
         t = self.program.tensors[tensor_id]
-        out = torch.empty((batch, self.canvas[0] // t.div, self.canvas[1] // t.div, t.channels), dtype=dtype, device="cuda")
+        out = torch.empty((batch, self.canvas[0] // t.div, self.canvas[1] // t.div, self._stored[tensor_id]), dtype=dtype, device="cuda")
         assert out.numel() == n.value
         check(fn(self._h, tensor_id, batch, _dev(out), C.byref(n), _lib.stream_ptr()), what)
-        return out
+        return out if stored or self._stored[tensor_id] == t.channels else out[..., :t.channels].contiguous()      # the real channels
 
     def read_tensor(self, tensor_id: int, batch: int) -> torch.Tensor:
         return self._read_tensor("", torch.float32, tensor_id, batch)
@@ -579,7 +604,7 @@ class Net:
         forward() + yolo_decode_scores()."""
         _images_arg(images)
         B = self._plan_for(images)
-        a = _anchors(anchors, reshape=True)
+        a = _anchors(anchors, reshape=True, scales=self.heads)
         n = sum(3 * gh * gw for gh, gw in self._grid_hw())
         bboxes = torch.empty((B, n, 4), dtype=torch.float32, device=images.device)
         cls = torch.empty((B, n), dtype=torch.int64, device=images.device)
@@ -593,7 +618,7 @@ class Net:
         `unpack_detections` splits the rows."""
         _images_arg(images)
         B = self._plan_for(images)
-        a = _anchors(anchors, reshape=True)
+        a = _anchors(anchors, reshape=True, scales=self.heads)
         packed = torch.empty((B, int(max_boxes), 7), dtype=torch.int32, device=images.device)
         nv = torch.empty((B,), dtype=torch.int32, device=images.device)
         check(self.lib.y3_net_detect(self._h, _dev(images), B, _fptr(a), int(max_boxes), float(iou_threshold),
@@ -678,6 +703,10 @@ class Net:
                                       max_gt, loss, ap, self.tiles, self.merge_iou_threshold)
 
     def flops_per_image(self) -> float:
+        """2 * MAC of the convs at the planned canvas, at the real channel counts (the device's own count, y3_net_flops_per_image,
+        where nothing is padded)."""
+        if self._stored != [t.channels for t in self.program.tensors]:
+            return float(self.program.flops_per_image(self.canvas)) if self.canvas[0] else 0.0
         return float(self.lib.y3_net_flops_per_image(self._h))
 
     def profile_convs(self, images: torch.Tensor) -> np.ndarray:

@@ -16,32 +16,35 @@ from ._lib import Y3Error, check
 
 
 def _grids_args(grids, square=True):
+    """square: the three-scale entry points' (ptrs, grid_sizes[3]); otherwise (ptrs, grid_hw[n][2]) of the n = 2 or 3 grids handed in,
+    for the _n entry points."""
     _need_cuda(*grids)
-    if len(grids) != 3:
-        raise Y3Error("expected three grids")
+    if len(grids) != 3 and (square or len(grids) != 2):
+        raise Y3Error("expected three grids" if square else "expected two or three grids")
     for g in grids:
         if g.dtype != torch.float32 or g.dim() != 5 or g.shape[3] != 3 or (square and g.shape[1] != g.shape[2]):
             raise Y3Error("each grid must be float32 [B,g,g,3,5+nc]" if square else "each grid must be float32 [B,gh,gw,3,5+nc]")
-    ptrs = (C.c_void_p * 3)(*[g.data_ptr() for g in grids])
+    ptrs = (C.c_void_p * len(grids))(*[g.data_ptr() for g in grids])
     if square:
         gs = (C.c_int32 * 3)(*[g.shape[1] for g in grids])
-    else:       # grid_hw[3][2] = {gh, gw}
-        gs = (C.c_int32 * 6)(*[v for g in grids for v in (g.shape[1], g.shape[2])])
+    else:       # grid_hw[n][2] = {gh, gw}
+        gs = (C.c_int32 * (2 * len(grids)))(*[v for g in grids for v in (g.shape[1], g.shape[2])])
     B = grids[0].shape[0]
     N = sum(3 * g.shape[1] * g.shape[2] for g in grids)
     return ptrs, gs, B, N
 
 
 def yolo_decode(grids, anchors_table, nclasses):
-    """-> (bboxes [B,N,4], confidence [B,N,1], class_probs [B,N,nc]).  Grids [B,gh,gw,3,5+nc]: each centre is normalised by
-    its own axis (include/y3.h, y3_yolo_decode_hw), which for gh == gw is the reference's arithmetic bit for bit."""
+    """-> (bboxes [B,N,4], confidence [B,N,1], class_probs [B,N,nc]).  Three grids [B,gh,gw,3,5+nc], or two (YOLOv3-tiny) with an
+    anchors_table [2,3,2]: each centre is normalised by its own axis (include/y3.h, y3_yolo_decode_hw), which for gh == gw is the
+    reference's arithmetic bit for bit."""
     ptrs, gs, B, N = _grids_args(grids, square=False)
-    a = _anchors(anchors_table)
+    a = _anchors(anchors_table, scales=len(grids))
     dev = grids[0].device
     bboxes = torch.empty((B, N, 4), dtype=torch.float32, device=dev)
     conf = torch.empty((B, N, 1), dtype=torch.float32, device=dev)
     probs = torch.empty((B, N, nclasses), dtype=torch.float32, device=dev)
-    check(_lib.load().y3_yolo_decode_hw(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(conf), _dev(probs),
+    check(_lib.load().y3_yolo_decode_hw_n(ptrs, gs, len(grids), B, nclasses, _fptr(a), _dev(bboxes), _dev(conf), _dev(probs),
                                      _lib.stream_ptr()), "y3_yolo_decode")
     return bboxes, conf, probs
 
@@ -53,20 +56,43 @@ def yolo_decode_scores(grids, anchors_table, nclasses):
 
 def _decode_scores(grids, anchors_table, nclasses, out=None):
     ptrs, gs, B, N = _grids_args(grids, square=False)
-    a = _anchors(anchors_table)
+    a = _anchors(anchors_table, scales=len(grids))
     dev = grids[0].device
     bboxes, cls, scores = out or (torch.empty((B, N, 4), dtype=torch.float32, device=dev),
                                   torch.empty((B, N), dtype=torch.int64, device=dev),
                                   torch.empty((B, N), dtype=torch.float32, device=dev))
-    check(_lib.load().y3_yolo_decode_scores_hw(ptrs, gs, B, nclasses, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores),
+    check(_lib.load().y3_yolo_decode_scores_hw_n(ptrs, gs, len(grids), B, nclasses, _fptr(a), _dev(bboxes), _dev(cls), _dev(scores),
                                             _lib.stream_ptr()), "y3_yolo_decode_scores")
     return bboxes, cls, scores
 
 
+def maxpool2x2(x: torch.Tensor, stride: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """MaxPooling2D(2, strides=stride, 'same') of x [B,H,W,C] (float32, bfloat16 or float16, on the GPU) -> [B,H/stride,W/stride,C]
+    (y3_maxpool2x2; maxpool.maxpool2x2_ref restates the rule).  stride 1 or 2, stride 2 on even H and W; C * element size a multiple
+    of 16 bytes.  Enqueues on the current stream only."""
+    _need_cuda(x, out)
+    dt = {torch.float32: _lib.Y3_DTYPE_F32, torch.bfloat16: _lib.Y3_DTYPE_BF16, torch.float16: _lib.Y3_DTYPE_F16}.get(x.dtype)
+    if dt is None or x.dim() != 4:
+        raise Y3Error("maxpool2x2: x must be float32, bfloat16 or float16 [B,H,W,C]")
+    if stride not in (1, 2):
+        raise Y3Error(f"maxpool2x2: stride must be 1 or 2 (got {stride!r})")
+    B, H, W, Cc = (int(v) for v in x.shape)
+    if stride == 2 and (H % 2 or W % 2):
+        raise Y3Error(f"maxpool2x2: a stride-2 pool needs even extents (got {H} x {W})")
+    shape = (B, H // stride, W // stride, Cc)
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != shape or out.dtype != x.dtype:
+        raise Y3Error(f"maxpool2x2: out must be {x.dtype} {list(shape)}")
+    check(_lib.load().y3_maxpool2x2(_dev(x), _dev(out), B, H, W, Cc, int(stride), dt, _lib.stream_ptr()), "y3_maxpool2x2")
+    return out
+
+
 def decode_candidates_workspace_bytes(grid_hw, batch: int, nclasses: int) -> int:
-    """y3_decode_candidates_workspace_bytes: grid_hw = three (gh, gw) pairs; 0 for sizes decode_candidates refuses."""
-    gs = (C.c_int32 * 6)(*[int(v) for hw in grid_hw for v in hw])
-    return int(_lib.load().y3_decode_candidates_workspace_bytes(gs, int(batch), int(nclasses)))
+    """y3_decode_candidates_workspace_bytes_n: grid_hw = two or three (gh, gw) pairs; 0 for sizes decode_candidates refuses."""
+    grid_hw = [tuple(hw) for hw in grid_hw]
+    gs = (C.c_int32 * (2 * len(grid_hw)))(*[int(v) for hw in grid_hw for v in hw])
+    return int(_lib.load().y3_decode_candidates_workspace_bytes_n(gs, len(grid_hw), int(batch), int(nclasses)))
 
 
 def decode_candidates(grids, anchors_table, nclasses, score_threshold, capacity, out=None, ws=None):
@@ -77,7 +103,7 @@ def decode_candidates(grids, anchors_table, nclasses, score_threshold, capacity,
     tensors to write; ws: a uint8 workspace of decode_candidates_workspace_bytes (one is made otherwise).  Enqueues on the current
     stream only."""
     ptrs, gs, B, N = _grids_args(grids, square=False)
-    a = _anchors(anchors_table)
+    a = _anchors(anchors_table, scales=len(grids))
     dev = grids[0].device
     K = int(capacity)
     if K < 1:
@@ -93,10 +119,10 @@ def decode_candidates(grids, anchors_table, nclasses, score_threshold, capacity,
         raise Y3Error(f"decode_candidates: out must be contiguous f32 [{B},{K},4], i64 [{B},{K}], f32 [{B},{K}], i32 [{B},{K}], i32 [{B}]")
     lib = _lib.load()
     if ws is None:
-        ws = torch.empty(max(lib.y3_decode_candidates_workspace_bytes(gs, B, int(nclasses)), 16), dtype=torch.uint8, device=dev)
+        ws = torch.empty(max(lib.y3_decode_candidates_workspace_bytes_n(gs, len(grids), B, int(nclasses)), 16), dtype=torch.uint8, device=dev)
     elif ws.dtype != torch.uint8 or ws.dim() != 1:
         raise Y3Error("ws must be a 1-D uint8 tensor")
-    check(lib.y3_yolo_decode_candidates_hw(ptrs, gs, B, int(nclasses), _fptr(a), float(score_threshold), K, _dev(boxes), _dev(cls),
+    check(lib.y3_yolo_decode_candidates_hw_n(ptrs, gs, len(grids), B, int(nclasses), _fptr(a), float(score_threshold), K, _dev(boxes), _dev(cls),
                                            _dev(scores), _dev(src), _dev(totals), _dev(ws), ws.numel(), _lib.stream_ptr()),
           "y3_yolo_decode_candidates_hw")
     return boxes, cls, scores, src, totals

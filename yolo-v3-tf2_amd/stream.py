@@ -112,7 +112,7 @@ def _detect_batches(net, who, batches, anchors, M, iou_threshold, score_threshol
              TiledInputStage(S, max_batch, max(int(max_blob_bytes), 16), tiles, depth))
     if max_batch * T > net.max_batch:
         net.plan(max_batch * T, S)
-    a = _anchors(anchors, reshape=True)
+    a = _anchors(anchors, reshape=True, scales=net.heads)
     dev = stage.device
     ring = [(torch.empty((max_batch, M, 7), dtype=torch.int32, device=dev),
              torch.empty((max_batch,), dtype=torch.int32, device=dev)) for _ in range(stage.depth)]
@@ -263,6 +263,9 @@ def evaluate_stream(net, batches, gts, anchors, max_boxes, iou_threshold, score_
                     one_class, mode, depth, max_batch, max_blob_bytes, letterbox, max_gt, loss, ap, tiles=None, merge_iou_threshold=None):
     thresholds = [float(t) for t in score_thresholds]
     ap_thr = None if ap is None or ap is False else ops.ap_iou_thresholds(ap)
+    if loss and net.heads != 3:
+        raise Y3Error(f"evaluate_stream: loss=True needs a three-head net (this one has {net.heads}; "
+                      "y3_yolo_assign_targets / y3_yolo_loss are three-scale)")
     if loss and letterbox:
         raise Y3Error("evaluate_stream: loss=True cannot be combined with letterbox=True (the ground truth is not mapped onto the canvas)")
     if loss and tiles is not None:
@@ -286,7 +289,7 @@ def evaluate_stream(net, batches, gts, anchors, max_boxes, iou_threshold, score_
     gt_iter, missing = iter(gts), object()
     nc, M = int(nclasses), int(max_boxes)
     variants = (0, 1) if both else (int(bool(one_class)),)
-    a = _anchors(anchors, reshape=True)
+    a = _anchors(anchors, reshape=True) if loss else None      # the loss's own copy (three scales); the detect takes the net's head count
     counted = _Counters(nc, thresholds, evaluate_iou_threshold, variants, both)
     matched = _AveragePrecision(net, nc, M, ap_thr, variants[0]) if ap_thr is not None else None
     summed = _Loss(net, a, nc) if loss else None

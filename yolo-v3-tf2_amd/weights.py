@@ -51,6 +51,29 @@ def synthetic_weights(program, seed: int = 4321) -> Dict[str, np.ndarray]:
     return out
 
 
+def pad_weights(program, weights: Dict[str, np.ndarray]) -> Dict[str, np.ndarray]:
+    """The weights as the device holds them where the lowering pads channels (Program.stored): HWIO kernels with zero rows for the
+    pad channels of their input and zero filters for the pad channels of their output, the BN statistics of a pad channel gamma 0,
+    beta 0, mean 0, var 1 (scale 0, shift 0: the channel comes out as exact zeros), a bias 0.  Every product added is 0 * 0, so a
+    real channel is the unpadded computation as a number.  Entries of convs that are not padded are returned as they are."""
+    stored = program.stored or [t.channels for t in program.tensors]
+    fill = {"gamma": 0.0, "beta": 0.0, "mean": 0.0, "var": 1.0, "bias": 0.0}
+    out = dict(weights)
+    for n in program.conv_nodes:
+        i, cin, cout = n.conv_index, program.tensors[n.inputs[0]].channels, n.filters
+        pin, pout = stored[n.inputs[0]], stored[n.output]
+        if (pin, pout) == (cin, cout):
+            continue
+        w = np.zeros((n.size, n.size, pin, pout), np.float32)
+        w[:, :, :cin, :cout] = weights[f"conv{i}.w"]
+        out[f"conv{i}.w"] = w
+        for k in (("gamma", "beta", "mean", "var") if n.bn else ("bias",)):
+            v = np.full((pout,), fill[k], np.float32)
+            v[:cout] = weights[f"conv{i}.{k}"]
+            out[f"conv{i}.{k}"] = v
+    return out
+
+
 def save_weights(path: str, weights: Dict[str, np.ndarray]):
     from safetensors.numpy import save_file
     save_file({k: np.ascontiguousarray(v) for k, v in weights.items()}, path)

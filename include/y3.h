@@ -286,6 +286,23 @@ y3_status y3_net_set_stem_fusion(y3_net *net, int on);
  * (bounded by tests/test_f16_stem_gpu.py).  Precondition: pixel values finite and of magnitude at most 65504 -- a larger one makes hi
  * infinite and the result NaN, where the unfused fp16 plan only overflows at its outputs. */
 y3_status y3_net_set_stem_fusion_f16(y3_net *net, int on);
+/* The fused stem of YOLOv3-tiny (csrc/conv_tiny_stem.hip), a switch of its own: 0 (default) one launch per op; 1: when the program starts
+ * with conv0 (the 3x3/1 first layer, 3 -> 16 stored as 32) -> Y3_AUX_MAXPOOL2X2_S2 -> conv1 (3x3/1, 16 stored as 32 -> 32, single source,
+ * no shortcut) -> Y3_AUX_MAXPOOL2X2_S2, each of the first three outputs has exactly one reader, none of the four is a net output and there
+ * are no early chunks, a Y3_DTYPE_F32, Y3_DTYPE_BF16 or Y3_DTYPE_F16 plan runs the four as ONE launch at the real widths 16 and K = 144:
+ * conv0's tensor, pool 0's and conv1's never reach memory, and the 32 -> 32 conv, for which the 16-bit modes have no tile, never asks for
+ * one -- so such a net plans in the 16-bit modes, which refuse it with the switch off.  Where the rule does not hold the switch is ignored.
+ * Read by y3_net_plan: set it before planning.  y3_net_set_stem_fusion / _f16 do not act on it, and it does not act on them; anything but
+ * 0 or 1 is Y3_ERR_INVALID.  Arithmetic: conv0 in fp32 from fp32 weights in every mode, in the stand-alone first-layer launch's order
+ * (acc * scale + shift, leaky, one rounding to the plan's format); conv1 on v_mfma_f32_32x32x2_f32 (fp32 plans) or v_mfma_f32_32x32x16_bf16
+ * / _f16 from 16-bit weights and the 16-bit pooled patch, fp32 accumulation, one rounding before pool 1; both pools compare values and keep
+ * the winner's bits (y3_maxpool2x2's order).  conv0's stored channels 16..31 must be the lowering's zero pad channels (scale 0, shift 0):
+ * a forward on other weights is refused with Y3_ERR_INVALID.  y3_net_keep_activations does not switch the fusion off: the three tensors
+ * inside the launch are not stored, and y3_net_read_tensor on one of them is refused with Y3_ERR_STATE and a message naming this switch.
+ * The convs inside are never split (a forced split-K on one is refused by name).
+ * y3_net_get_tiny_stem_fused: 1 when the planned net runs the fused launch, 0 otherwise, also before a plan. */
+y3_status y3_net_set_tiny_stem_fusion(y3_net *net, int on);
+int y3_net_get_tiny_stem_fused(const y3_net *net);
 /* Measurement aid (bench.py): the shader clock the chip holds under this network's load.  Runs `forwards` forwards back to
  * back (grids_dev as for y3_net_forward); in the last one, thread 0 of the middle workgroup of the conv with the most FLOPs (fp32
  * plans: an MFMA conv launch; bf16 plans, and fp16 plans with y3_net_set_stem_fusion_f16: the fused stem kernel) reads s_memtime and s_memrealtime at its entry and after

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """YOLOv3-tiny on the device: what one detect costs, and what the max-pool kernel reaches.
 
-fp32 (the only mode that plans the tiny model), config/models/yolov3_tiny/model.yaml with synthetic weights, Net.detect on
+fp32 (--dtype bf16 / f16 with --fused-stem: the fused tiny stem, with which the tiny model plans in the 16-bit modes), config/models/yolov3_tiny/model.yaml with synthetic weights, Net.detect on
 device-resident frames, by the protocol of tools/time_latency.py:
   eager  -- every call between a pair of device events on the stream;
   graph  -- the call captured with torch.cuda.graph, every replay timed with the host clock around a synchronise;
@@ -37,6 +37,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--pool-calls", type=int, default=200)
     ap.add_argument("--profile-steps", type=int, default=0, help="enqueue this many detects and exit (for rocprofv3)")
+    ap.add_argument("--dtype", choices=("f32", "bf16", "f16"), default="f32", help="the plans' conv arithmetic; bf16 and f16 need --fused-stem")
+    ap.add_argument("--fused-stem", action="store_true", help="the fused tiny stem kernel (Net.set_tiny_stem_fusion) in the measured plan; "
+                                                               "sections 1 and 2 then alternate it with the fp32 plan without the switch")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -58,11 +61,17 @@ def main():
     anchors = get_anchors(os.path.join(ROOT, "datasets/coco2012/anchors_tiny.txt")).astype(np.float32)
     B, S = a.batch, a.size
 
-    def make(batch, low_latency=False):
+    dtype = runtime.Net._dtype_arg(a.dtype)
+    if a.dtype != "f32" and not a.fused_stem:
+        ap.error("--dtype bf16 / f16 needs --fused-stem: the tiny model plans in a 16-bit mode only with the fused stem")
+
+    def make(batch, low_latency=False, fused=None, dt=None):
+        """fused / dt None: what the command line says; the baseline of an A/B is make(batch, fused=False, dt=0), the fp32 plan without the switch"""
         net = runtime.Net(program)
         net.load_weights(weights)
         net.set_low_latency(low_latency)
-        net.plan(batch, S)
+        net.set_tiny_stem_fusion(a.fused_stem if fused is None else fused)
+        net.plan(batch, S, dtype if dt is None else dt)
         return net
 
     if a.profile_steps:
@@ -73,7 +82,7 @@ def main():
         torch.cuda.synchronize()
         return
 
-    say(f"# tools/time_tiny.py  device: {torch.cuda.get_device_name(0)}  fp32  YOLOv3-tiny, {len(program.conv_ops())} convs, "
+    say(f"# tools/time_tiny.py  device: {torch.cuda.get_device_name(0)}  {a.dtype}{' fused stem' if a.fused_stem else ''}  YOLOv3-tiny, {len(program.conv_ops())} convs, "
         f"{sum(isinstance(o, AuxOp) for o in program.ops)} aux ops, N = {sum(3 * g * g for g in program.grid_sizes(S))} boxes at {S}")
     say(f"# GFLOP / image at {S}: {program.flops_per_image(S) / 1e9:.3f} (real channel counts)")
 
@@ -148,18 +157,29 @@ def main():
     net = make(B)
     x = torch.rand((B, S, S, 3), device="cuda")
     say(f"\n== detect, {B} x {S} x {S}, lanes {getattr(net, 'lanes', 1)}")
-    r = timed({"default": lambda: net.detect(x, anchors, 100, 0.5, 0.1)}, a.calls, "throughput")
+    steps = {"default": lambda: net.detect(x, anchors, 100, 0.5, 0.1)}
+    if a.fused_stem:      # A/B in one process: the fp32 plan without the switch in alternated windows
+        base = make(B, fused=False, dt=0)
+        say(f"   'default' = {a.dtype} with the fused tiny stem (tiny_stem_fused = {net.tiny_stem_fused}); 'f32_unfused' = the fp32 plan without the switch")
+        steps["f32_unfused"] = lambda: base.detect(x, anchors, 100, 0.5, 0.1)
+    r = timed(steps, a.calls, "throughput")
     for form in ("eager", "graph"):
-        med = float(np.median(np.concatenate(r[form]["default"])))
-        say(f"throughput {form}: {B / med * 1e3:.0f} images/s ({med:.4f} ms per step of {B})")
+        for k in steps:
+            med = float(np.median(np.concatenate(r[form][k])))
+            say(f"throughput {form} {k}: {B / med * 1e3:.0f} images/s ({med:.4f} ms per step of {B})")
+    if a.fused_stem:
+        del base
     pools = [(o, program.tensors[o.inputs[0]]) for o in program.ops if isinstance(o, AuxOp) and o.kind.startswith("maxpool")]
     del net
     torch.cuda.empty_cache()
 
     # ---- 2. latency at one image
-    nets = {"default": make(1), "low_latency": make(1, True)}
+    nets = {"default": make(1), "low_latency": make(1, True)} if not a.fused_stem else {"default": make(1), "f32_unfused": make(1, fused=False, dt=0)}
     x1 = torch.rand((1, S, S, 3), device="cuda")
-    say(f"\n== detect, 1 x {S} x {S}; K slices per conv of the low-latency plan: {[nets['low_latency'].split_k(i) for i in range(len(program.conv_ops()))]}")
+    if "low_latency" in nets:
+        say(f"\n== detect, 1 x {S} x {S}; K slices per conv of the low-latency plan: {[nets['low_latency'].split_k(i) for i in range(len(program.conv_ops()))]}")
+    else:
+        say(f"\n== detect, 1 x {S} x {S}; {a.dtype} with the fused tiny stem against the fp32 plan without the switch")
     timed({k: (lambda n=n: n.detect(x1, anchors, 100, 0.5, 0.1)) for k, n in nets.items()}, max(a.calls, 400), "latency")
     del nets
     torch.cuda.empty_cache()

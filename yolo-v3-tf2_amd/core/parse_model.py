@@ -32,6 +32,7 @@ class _LoadStatus:
 
 
 _DEFERRED_DEFAULTS = {"set_low_latency": False, "set_low_latency_f16": False, "set_low_latency_i8": False, "set_stem_fusion_f16": 0,
+                      "set_tiny_stem_fusion": 0,
                       "load_calibration": None, "set_dtype": None}
 
 
@@ -51,7 +52,7 @@ class YoloModel:
         self.multi_label, self.multi_label_capacity = False, 0      # set_multi_label: the device net's properties of those names
         self.tiles = None               # set_tiles: (rows, cols, overlap_px, overview), the device net's property of that name
 
-    def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, i8_calibration, dtype
+    def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, tiny_stem_fusion, i8_calibration, dtype
         method = {"i8_calibration": "load_calibration"}.get(name, "set_" + name)
         if method in _DEFERRED_DEFAULTS and "_deferred" in self.__dict__:
             return self._deferred[method]
@@ -98,6 +99,12 @@ class YoloModel:
         """The fused stem kernel for fp16 plans (runtime.Net.set_stem_fusion_f16): off by default; acts on dtype "f16" only."""
         from ..runtime import Net
         self._defer("set_stem_fusion_f16", Net._stem_fusion_arg(on))
+
+    def set_tiny_stem_fusion(self, on=True):
+        """The fused stem kernel of YOLOv3-tiny (runtime.Net.set_tiny_stem_fusion): off by default; with it the tiny model also plans in
+        dtype "bf16" and "f16".  Ignored by a program that does not start with tiny's stem.  Takes effect at the next plan."""
+        from ..runtime import Net
+        self._defer("set_tiny_stem_fusion", Net._tiny_stem_arg(on))
 
     def set_nms_per_class(self, on=True):
         """Per-class NMS (runtime.Net.nms_per_class; no reference counterpart): a box is suppressed only by a kept box of its own

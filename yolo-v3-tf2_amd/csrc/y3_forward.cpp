@@ -171,6 +171,34 @@ struct Slice {
         return Y3_OK;
     }
 
+    // the fused tiny stem launch (op 2): conv0 (op 0), the pools of ops 1 and 3 and conv1 run inside it; it stores pool 1's tensor
+    y3_status launch_tiny_stem() const
+    {
+        const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[2].index];
+        const y3::ConvFamily &fam = y3::family_of_conv(net, net->ops[2].index);
+        const int out = net->aux[net->ops[3].index].dst;
+        y3::TinyStemArgs ta{};
+        ta.img = static_cast<const float *>(ptr(c0.d.src0));
+        ta.w0 = c0.w0tiny_dev;
+        ta.scale0 = c0.scale_dev;
+        ta.shift0 = c0.shift_dev;
+        ta.w1 = c1.*fam.w1_tiny;
+        ta.scale1 = c1.scale_dev;
+        ta.shift1 = c1.shift_dev;
+        ta.dst = ptr(out);
+        ta.B = nb;
+        ta.H = net->height;
+        ta.W = net->width;
+        ta.leaky0 = c0.d.leaky;
+        ta.leaky1 = c1.d.leaky;
+        ta.device = net->device;
+        ta.n_cus = net->n_cus;
+        if (!ta.img || !ta.dst || !ta.w0 || !ta.w1) return fail(Y3_ERR_STATE, "conv %d (fused tiny stem): tensor not planned or weights not loaded", net->ops[2].index);
+        hipError_t e = fam.launch_tiny_stem(ta, s);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "conv %d (fused tiny stem) launch: %s", net->ops[2].index, hipGetErrorString(e));
+        return Y3_OK;
+    }
+
     // launch conv op oi as y3::choose_conv decided
     y3_status launch_conv(int oi, const y3::ConvArgs &a, const y3::ConvChoice &ch) const
     {
@@ -180,6 +208,7 @@ struct Slice {
         hipError_t e;
         switch (ch.kind) {
             case y3::ConvKind::Stem: return launch_stem(a);
+            case y3::ConvKind::TinyStem: return launch_tiny_stem();
             case y3::ConvKind::First: e = y3::launch_conv_first(a, static_cast<const float *>(c.w_dev), y3::dtype_of_conv(net, conv), s); break;
             case y3::ConvKind::HeadDecodeF32: e = y3::launch_conv_head_decode_f32(a, s); break;
             case y3::ConvKind::SplitK:
@@ -205,17 +234,27 @@ struct Slice {
             if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d (max-pool) launch: %s", index, hipGetErrorString(e));
             return Y3_OK;
         }
-        if (net->dtype != Y3_DTYPE_F32) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
+        // The up-sample and the concat only move elements: a bf16 or fp16 plan runs them on its 16-bit tensors as on fp32 tensors of half the
+        // channels (two elements per 4-byte word; YOLOv3-tiny's up-sample and its concat in front of a 3x3 conv).  The add is arithmetic and
+        // stays fp32 only, as every stand-alone op does in the plane-split and int8 plans.
+        const bool moves = x.kind == Y3_AUX_UPSAMPLE2X || x.kind == Y3_AUX_CONCAT;
+        const bool sixteen = (net->dtype == Y3_DTYPE_BF16 || net->dtype == Y3_DTYPE_F16) && moves && elem_bytes(x.dst) == 2 && elem_bytes(x.src0) == 2 &&
+                             (x.src1 < 0 || elem_bytes(x.src1) == 2);
+        if (net->dtype != Y3_DTYPE_F32 && !sixteen) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
         auto p = [&](int t) { return static_cast<float *>(ptr(t)); };
         const int sh = rows(net, x.dst), sw = cols(net, x.dst);
+        const int per = sixteen ? 2 : 1;   // elements per 4-byte word
         const int C = net->tensors[x.dst].channels;
+        if (moves && (!p(x.src0) || !p(x.dst) || (x.kind == Y3_AUX_CONCAT && !p(x.src1)))) return fail(Y3_ERR_STATE, "aux op %d: tensor not planned", index);
+        if (sixteen && (C % 8 || net->tensors[x.src0].channels % 8))
+            return fail(Y3_ERR_INVALID, "aux op %d: a stand-alone up-sample / concat of a 16-bit plan needs channel counts that are multiples of 8", index);
         hipError_t e = hipSuccess;
         if (x.kind == Y3_AUX_ADD)
             e = y3::launch_add(p(x.src0), p(x.src1), p(x.dst), (size_t)nb * sh * sw * C, s);
         else if (x.kind == Y3_AUX_UPSAMPLE2X)
-            e = y3::launch_upsample2x(p(x.src0), nb, sh / 2, sw / 2, C, p(x.dst), s);
+            e = y3::launch_upsample2x(p(x.src0), nb, sh / 2, sw / 2, C / per, p(x.dst), s);
         else if (x.kind == Y3_AUX_CONCAT)
-            e = y3::launch_concat(p(x.src0), net->tensors[x.src0].channels, p(x.src1), net->tensors[x.src1].channels, (size_t)nb * sh * sw, p(x.dst), s);
+            e = y3::launch_concat(p(x.src0), net->tensors[x.src0].channels / per, p(x.src1), net->tensors[x.src1].channels / per, (size_t)nb * sh * sw, p(x.dst), s);
         else
             return fail(Y3_ERR_INVALID, "unknown aux op kind %d", x.kind);
         if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d launch: %s", index, hipGetErrorString(e));
@@ -236,17 +275,20 @@ struct Slice {
         for (int oi = op_begin; oi < op_end; ++oi) {
             const Op &o = net->ops[oi];
             if (o.kind != 0) {
+                if (net->tiny_stem_fused && (oi == 1 || oi == 3)) continue;   // the pools inside the fused tiny stem launch
                 if (y3_status st = run_aux(o.index); st != Y3_OK) return st;
                 continue;
             }
             y3::ConvArgs a = conv_args(o.index);
-            if (!a.src0 || (!a.dst && !a.dec.boxes)) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", o.index);
             const y3::ConvChoice ch = y3::choose_conv(net, oi, a);
+            // (the convs of the fused tiny stem read and write tensors that are not stored: launch_tiny_stem checks its own)
+            const bool tiny = ch.kind == y3::ConvKind::TinyStem || ch.kind == y3::ConvKind::InTinyStem;
+            if (!tiny && (!a.src0 || (!a.dst && !a.dec.boxes))) return fail(Y3_ERR_STATE, "conv %d: tensor not planned", o.index);
             a.k_chunk = ch.k_chunk;
             a.xcd_gn = ch.xcd_gn;
             a.pos_tab = ch.pos_tab;
             a.border_tiles = ch.border_tiles;
-            if (ch.kind == y3::ConvKind::InStem) {   // runs inside conv1's launch (fused stem)
+            if (ch.kind == y3::ConvKind::InStem || ch.kind == y3::ConvKind::InTinyStem) {   // runs inside conv1's launch (fused stem, fused tiny stem)
                 if (f.ms_out && o.index < f.n_ms) f.ms_out[o.index] = 0.0f;
             } else {
                 if (f.ms_out) HIP_TRY(hipEventRecord(ev0, s));
@@ -290,6 +332,9 @@ static y3_status run(const y3_net *net, const Forward &f)
     if (net->dtype == Y3_DTYPE_F32X2)
         for (size_t i = 0; i < net->convs.size(); ++i)
             if (!net->convs[i].x2_ok) return fail(Y3_ERR_INVALID, "y3_net_forward: conv %zu has a weight outside the fp16 range of the two-plane mode", i);
+    if (net->tiny_stem_fused && !net->convs[net->ops[0].index].tiny_pad_zero)
+        return fail(Y3_ERR_INVALID, "y3_net_forward: the fused tiny stem (y3_net_set_tiny_stem_fusion) computes 16 channels of conv %d; its stored channels 16..31 "
+                                    "must be zero pad channels (BN scale 0 and shift 0), and these weights give them values", net->ops[0].index);
     for (int i = 0; i < net->n_heads; ++i)
         if (!f.grids[i] || ((uintptr_t)f.grids[i] & 15)) return fail(Y3_ERR_INVALID, "y3_net_forward: grid %d null or not 16-byte aligned", i);
     if ((uintptr_t)f.images & 3) return fail(Y3_ERR_INVALID, "y3_net_forward: images not 4-byte aligned");
@@ -500,6 +545,9 @@ try {
     const size_t n = npix * net->tensors[t].channels;
     if (n_elems) *n_elems = n;
     if (!dst_dev) return Y3_OK;
+    if (net->tiny_stem_fused && net->tiny_inner[t])
+        return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d lies inside the fused tiny stem launch and is never stored (y3_net_set_tiny_stem_fusion(net, 0) and "
+                                  "a new plan keep it)", t);
     if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
     Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
     // an int8 plan: (float)q * s behind the cut, the fp16 value before it

@@ -79,6 +79,13 @@ struct ConvSlot {
     // [1, 2); e_n = 0 for an all-zero channel), and the conv0 scale of that kernel alone, scale * 2^e_n (scale_dev stays conv_first's)
     float *w0norm_dev = nullptr;
     float *scale0norm_dev = nullptr;
+    // fused tiny stem (conv_tiny_stem.hip), the kernel's own copies at the real widths.  First layer: w0tiny_dev [27][16], the HWIO rows of
+    // output channels 0..15, unscaled (scale_dev / shift_dev carry their scale and shift in their first 16 entries), and tiny_pad_zero: output
+    // channels 16..31 have scale 0 and shift 0, that is, they are the lowering's zero pad channels.  A 3x3 conv 32 -> 32: w1tiny_*_dev
+    // [144][32], row tap * 16 + c from input channels c < 16, unscaled, in fp32, bf16 and fp16
+    float *w0tiny_dev = nullptr;
+    bool tiny_pad_zero = false;
+    void *w1tiny_dev = nullptr, *w1tiny_bf_dev = nullptr, *w1tiny_f16_dev = nullptr;
     void *wbf_dev = nullptr;   // same, bf16 (not for the first layer)
     void *wf16_dev = nullptr;  // same, IEEE fp16 rounded to nearest even on the host (Y3_DTYPE_F16 plans; not for the first layer)
     float *scale_dev = nullptr;
@@ -140,6 +147,9 @@ struct y3_net {
     int stem_mode_f16 = 0;         // y3_net_set_stem_fusion_f16: the same three values for Y3_DTYPE_F16 plans, which stem_mode does not act on; off by default
     bool stem_fused = false;       // (at plan time) the first two convs run as the fused stem kernel
     bool stem_conv2 = false;       // ... and the 1x1 conv that follows them (64 -> 32) runs inside it as well (fp32 and bf16 plans)
+    int tiny_stem_mode = 0;        // y3_net_set_tiny_stem_fusion: 1 = conv0 + pool 0 + conv1 + pool 1 of YOLOv3-tiny as one kernel when the graph allows it (fp32, bf16, fp16 plans); read by y3_net_plan
+    bool tiny_stem_fused = false;  // (at plan time) ops 0..3 run as the fused tiny stem kernel, launched by op 2
+    std::vector<char> tiny_inner;  // ... and the tensors inside it (conv0's, pool 0's, conv1's): no launch stores them, they get no arena block
     int xcd_mode = 1;              // y3_net_set_xcd_mode: 0 contiguous tile runs per XCD, 1 XCD-blocked order chosen per conv
     bool low_latency_set = false;  // y3_net_set_low_latency was called (the Y3_LOW_LATENCY tool override then stays out)
     bool low_latency = false;      // y3_net_set_low_latency: every eligible fp32 conv takes y3_choose_split_k
@@ -225,6 +235,9 @@ struct ConvFamily {
     float *ConvSlot::*scale0_stem;                 // conv0's scale for that kernel (fp16: its weights are normalised per channel)
     int y3_net::*stem_mode;                        // the switch: 0 off, 1 conv0 + conv1 + the 1x1 after them, 2 conv0 + conv1
     const SplitForm *split;                        // null: the mode never splits K
+    // fused tiny stem kernel (null: the mode has none) and conv1's [144][32] weights it reads
+    hipError_t (*launch_tiny_stem)(const TinyStemArgs &, hipStream_t);
+    void *ConvSlot::*w1_tiny;
 };
 const ConvFamily *conv_family(int dtype);   // null: no such mode
 inline const ConvFamily &family_of(const y3_net *net) { return *conv_family(net->dtype); }   // the planned mode's (fp32 before the first plan)
@@ -233,8 +246,9 @@ inline bool conv_is_i8(const y3_net *net, int slot) { return net->dtype == Y3_DT
 inline int dtype_of_conv(const y3_net *net, int slot) { return net->dtype != Y3_DTYPE_I8 || conv_is_i8(net, slot) ? net->dtype : (int)Y3_DTYPE_F16; }
 inline const ConvFamily &family_of_conv(const y3_net *net, int slot) { return *conv_family(dtype_of_conv(net, slot)); }
 
-// What conv op `oi` launches for the rows of one call.  InStem: nothing of its own, it runs inside the Stem launch of op 1.
-enum class ConvKind { First, Stem, InStem, HeadDecodeF32, Mfma, SplitK };
+// What conv op `oi` launches for the rows of one call.  InStem: nothing of its own, it runs inside the Stem launch of op 1.  TinyStem: op 2 of
+// a net whose ops 0..3 run as the fused tiny stem; InTinyStem: op 0 of it (the two pools between are skipped by the forward).
+enum class ConvKind { First, Stem, InStem, HeadDecodeF32, Mfma, SplitK, TinyStem, InTinyStem };
 struct ConvChoice {
     ConvKind kind;
     int tile;      // Mfma, SplitK: tile id of the family's table
@@ -255,6 +269,8 @@ int conv_without_tile(const y3_net *net);
 bool stem_applicable(const y3_net *net);
 bool stem_conv2_applicable(const y3_net *net);
 void resolve_stem(y3_net *net);   // stem_fused / stem_conv2 of a planned net from the planned mode's switch and the graph
+bool tiny_stem_applicable(const y3_net *net);
+void resolve_tiny_stem(y3_net *net);   // tiny_stem_fused / tiny_inner from y3_net_set_tiny_stem_fusion, the planned mode and the graph (y3_net_plan, before conv_without_tile)
 bool output_staged(const y3_net *net, int t);
 y3_status resolve_splits(y3_net *net);
 // fp32 plans: the position table of every 3x3 single-source conv's geometry, built and uploaded once per geometry (y3_net_plan)

@@ -222,6 +222,27 @@ hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s);
 hipError_t launch_conv_stem_bf16(const StemArgs &a, hipStream_t s);   // conv0 on bf16 MFMA from split (hi + lo) operands (~2^-16 per product), bf16 patch, conv1 on bf16 MFMA
 hipError_t launch_conv_stem_f16(const StemArgs &a, hipStream_t s);    // the same kernel on f16 MFMA: conv0 from (hi + lo' 2^-11) operands (~2^-22 per product), fp16 patch
 
+// fused stem of YOLOv3-tiny (conv_tiny_stem.hip): conv0 (3x3/1, 3->16) + max-pool 2x2/2 + conv1 (3x3/1, 16->32) + max-pool 2x2/2, both convs
+// BN + optional leaky, one launch at the real widths; only pool 1's tensor reaches memory
+struct TinyStemArgs {
+    const float *img;      // [B,H,W,3] fp32
+    const float *w0;       // conv0 weights [27][16] fp32, row k = (u*3 + v)*3 + c, unscaled
+    const float *scale0;   // [16]  y = acc*scale + shift, as the stand-alone first-layer launch
+    const float *shift0;   // [16]
+    const void *w1;        // conv1 weights [144][32], row k = tap*16 + c, unscaled: fp32 / bf16 / fp16
+    const float *scale1;   // [32]
+    const float *shift1;   // [32]
+    void *dst;             // [B,H/4,W/4,32] fp32 / bf16 / fp16
+    int B, H, W;           // image height and width, each % 32 == 0
+    int leaky0, leaky1;
+    int tiles_y, tiles_x, n_tiles;   // filled by the launcher
+    int device;            // as ConvArgs::device
+    int n_cus;             // as ConvArgs::n_cus (persistent workgroups)
+};
+hipError_t launch_conv_tiny_stem_f32(const TinyStemArgs &a, hipStream_t s);
+hipError_t launch_conv_tiny_stem_bf16(const TinyStemArgs &a, hipStream_t s);
+hipError_t launch_conv_tiny_stem_f16(const TinyStemArgs &a, hipStream_t s);
+
 // bf16 path (conv_bf16.hip; the kernel body, shared with the fp16 path: conv_16bit.h)
 static constexpr int BF16_TILE_COUNT = 37;   // 32: the weight-resident 3x3 kernel (conv_res_bf16.hip); 20, 33..36: retired ids
 TileInfo conv_bf16_tile_info(int tile);

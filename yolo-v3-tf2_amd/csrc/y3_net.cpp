@@ -400,6 +400,51 @@ void y3::resolve_stem(y3_net *net)
     net->stem_conv2 = net->stem_fused && mode == 1 && stem_conv2_applicable(net);
 }
 
+// The fused stem of YOLOv3-tiny (csrc/conv_tiny_stem.hip).  Ops 0..3 are conv0 (the 3x3/1 first layer, 3 -> 16 stored as 32) reading the input,
+// Y3_AUX_MAXPOOL2X2_S2 on it, a 3x3/1 conv 16 (stored 32) -> 32 with a single source and no shortcut, and Y3_AUX_MAXPOOL2X2_S2 on that; each of
+// the first three outputs has exactly one reader, none of the four is a net output, there are no early chunks, and the plan's mode has the
+// kernel (fp32, bf16, fp16).  The stored widths are all the graph tells: that conv0's channels 16..31 are zero pad channels is a property of its
+// weights (ConvSlot::tiny_pad_zero), which the forward asks for.  keep_activations does not matter: the tensors inside are simply not stored.
+bool y3::tiny_stem_applicable(const y3_net *net)
+{
+    if (!family_of(net).launch_tiny_stem || net->height % 32 || net->width % 32 || net->early_ops > 0) return false;
+    if (net->ops.size() < 5 || net->ops[0].kind != 0 || net->ops[1].kind == 0 || net->ops[2].kind != 0 || net->ops[3].kind == 0) return false;
+    const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[2].index];
+    const y3_conv_desc &a = c0.d, &b = c1.d;
+    const y3_aux_desc &p0 = net->aux[net->ops[1].index], &p1 = net->aux[net->ops[3].index];
+    if (!c0.first_layer || a.size != 3 || a.stride != 1 || a.cout != 32 || a.residual >= 0 || a.src1 >= 0 || a.src0 != net->input_tensor) return false;
+    if (p0.kind != Y3_AUX_MAXPOOL2X2_S2 || p0.src0 != a.dst) return false;
+    if (b.size != 3 || b.stride != 1 || b.cin != 32 || b.cout != 32 || b.residual >= 0 || b.src1 >= 0 || b.src0 != p0.dst) return false;
+    if (p1.kind != Y3_AUX_MAXPOOL2X2_S2 || p1.src0 != b.dst) return false;
+    if (a.in_div != 1 || net->tensors[p1.dst].div != 4 || net->tensors[p1.dst].channels != 32) return false;
+    const int inner[3] = {a.dst, p0.dst, b.dst};
+    for (int t : {a.dst, p0.dst, b.dst, p1.dst})
+        if (is_output(net, t) || t == net->input_tensor) return false;
+    for (int t : inner) {   // exactly one reader, and nobody else writes it
+        int readers = 0, writers = 0;
+        for (const ConvSlot &c : net->convs) {
+            readers += (c.d.src0 == t) + (c.d.src1 == t) + (c.d.residual == t);
+            writers += c.d.dst == t;
+        }
+        for (const y3_aux_desc &x : net->aux) {
+            readers += (x.src0 == t) + (x.src1 == t);
+            writers += x.dst == t;
+        }
+        if (readers != 1 || writers != 1) return false;
+    }
+    return true;
+}
+
+void y3::resolve_tiny_stem(y3_net *net)
+{
+    net->tiny_stem_fused = net->tiny_stem_mode == 1 && tiny_stem_applicable(net);
+    net->tiny_inner.assign(net->tensors.size(), 0);
+    if (!net->tiny_stem_fused) return;
+    net->tiny_inner[net->convs[net->ops[0].index].d.dst] = 1;
+    net->tiny_inner[net->aux[net->ops[1].index].dst] = 1;
+    net->tiny_inner[net->convs[net->ops[2].index].d.dst] = 1;
+}
+
 // Is net output t staged in a non-fp32 plan -- produced in the arena in the mode's own format and converted into the caller's fp32
 // grid at the end of the forward -- because a conv reads it again inside the net, or a conv with no fp32-output form of its launch
 // (shortcut, first layer) writes it?  Needs no plan: y3_net_plan marks `staged` by it, and y3_net_set_tile_bf16 refuses the
@@ -540,29 +585,29 @@ constexpr y3::ConvFamily F32_FAMILY = {
     "y3_net_set_tile: bad argument", "y3_net_set_tile: tile id %d is retired (the timing ablations of rounds 1-2; y3_tile_built)",
     "y3_net_set_tile: tile does not divide Cout", 33, resident_rule_f32,
     &ConvSlot::w_dev, 4, choose_tile, launch_f32, refine_f32, y3::launch_conv_stem_f32, &ConvSlot::w0stem_dev, &ConvSlot::scale_dev, &y3_net::stem_mode,
-    &F32_SPLIT};
+    &F32_SPLIT, y3::launch_conv_tiny_stem_f32, &ConvSlot::w1tiny_dev};
 constexpr y3::ConvFamily BF16_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
     "y3_net_set_tile_bf16: bad argument",
     "y3_net_set_tile_bf16: tile id %d is retired (20: the pipelined tile of round 2; 33..36: tap-row reuse and the four-wave tile of round 4; y3_tile_built)",
     "y3_net_set_tile_bf16: tile does not fit this conv", 32, resident_rule_bf16,
     &ConvSlot::wbf_dev, 2, choose_tile_bf16, y3::launch_conv_bf16, refine_bf16, y3::launch_conv_stem_bf16, &ConvSlot::w0raw_dev, &ConvSlot::scale_dev,
-    &y3_net::stem_mode, &BF16_SPLIT};
+    &y3_net::stem_mode, &BF16_SPLIT, y3::launch_conv_tiny_stem_bf16, &ConvSlot::w1tiny_bf_dev};
 // fp16 plans: the bf16 family's tile table, forced-tile field, chooser and refine rule; fp16 weights and launchers; the fused stem and the
 // split form behind switches of their own (y3_net_set_stem_fusion_f16, y3_net_set_low_latency_f16 / _split_k_f16), off by default
 constexpr y3::ConvFamily F16_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_bf16_tile_info, y3::conv_bf16_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad,
     BF16_FAMILY.bad, BF16_FAMILY.retired, BF16_FAMILY.misfit, 32, resident_rule_bf16,
     &ConvSlot::wf16_dev, 2, choose_tile_bf16, y3::launch_conv_f16, refine_bf16, y3::launch_conv_stem_f16, &ConvSlot::w0norm_dev, &ConvSlot::scale0norm_dev,
-    &y3_net::stem_mode_f16, &F16_SPLIT};
+    &y3_net::stem_mode_f16, &F16_SPLIT, y3::launch_conv_tiny_stem_f16, &ConvSlot::w1tiny_f16_dev};
 constexpr y3::ConvFamily X3_FAMILY = {
     y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x3_tile_built, &ConvSlot::tile_x3, &ConvSlot::cout_pad64,
     "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: bad argument", "y3_net_set_tile_x3: tile does not fit this conv", -1, nullptr,
-    &ConvSlot::wx3_dev, 6, choose_tile_x3, y3::launch_conv_f32x3, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    &ConvSlot::wx3_dev, 6, choose_tile_x3, y3::launch_conv_f32x3, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 constexpr y3::ConvFamily X2_FAMILY = {
     y3::X3_TILE_COUNT, y3::conv_x3_tile_info, y3::conv_x2_tile_built, &ConvSlot::tile_x2, &ConvSlot::cout_pad64,
     "y3_net_set_tile_x2: bad argument", "y3_net_set_tile_x2: tile does not fit this conv", "y3_net_set_tile_x2: tile does not fit this conv", -1, nullptr,
-    &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    &ConvSlot::wx2_dev, 4, choose_tile_x2, y3::launch_conv_f32x2, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
 
 // int8 plans (Y3_DTYPE_I8): the convs from the cut on (y3_plan.cpp, resolve_i8).  The bf16 family's tile ids and forced-tile field (a
 // forced tile without an int8 form, or one that does not fit, leaves the conv to the chooser), the bf16 refine rule, int8 weights over Cout
@@ -572,7 +617,7 @@ constexpr y3::ConvFamily I8_FAMILY = {
     y3::BF16_TILE_COUNT, y3::conv_i8_tile_info, y3::conv_i8_tile_built, &ConvSlot::tile_bf16, &ConvSlot::cout_pad64,
     BF16_FAMILY.bad, BF16_FAMILY.retired, BF16_FAMILY.misfit, -1, nullptr,
     &ConvSlot::wi8_dev, 1, choose_tile_i8, y3::launch_conv_i8, refine_bf16, y3::launch_conv_stem_f16, &ConvSlot::w0norm_dev, &ConvSlot::scale0norm_dev,
-    &y3_net::stem_mode_f16, &I8_SPLIT};
+    &y3_net::stem_mode_f16, &I8_SPLIT, nullptr, nullptr};
 
 // "forced tile, else the family's chooser": the tile part of the launch decision.  (A forced tile was checked by its setter against the
 // family it was forced for; an int8 plan shares the bf16 field, so the check is made again here.)
@@ -605,7 +650,9 @@ y3::ConvChoice y3::choose_conv(const y3_net *net, int oi, const ConvArgs &a)
 {
     const ConvSlot &c = net->convs[net->ops[oi].index];
     ConvChoice ch{ConvKind::Mfma, -1, 0, 0, 1, nullptr, -1};
-    if ((net->stem_fused && oi == 0) || (net->stem_conv2 && oi == 2)) ch.kind = ConvKind::InStem;
+    if (net->tiny_stem_fused && oi == 0) ch.kind = ConvKind::InTinyStem;
+    else if (net->tiny_stem_fused && oi == 2) ch.kind = ConvKind::TinyStem;
+    else if ((net->stem_fused && oi == 0) || (net->stem_conv2 && oi == 2)) ch.kind = ConvKind::InStem;
     else if (net->stem_fused && oi == 1) ch.kind = ConvKind::Stem;
     else if (c.first_layer) ch.kind = ConvKind::First;
     if (ch.kind != ConvKind::Mfma) return ch;
@@ -633,6 +680,7 @@ int y3::conv_without_tile(const y3_net *net)
     for (int slot = 0; slot < (int)net->convs.size(); ++slot) {
         const ConvSlot &c = net->convs[slot];
         if (c.first_layer) continue;   // the direct Cin = 3 kernel (or the fused stem) in every mode
+        if (net->tiny_stem_fused && slot == net->ops[2].index) continue;   // runs inside the fused tiny stem launch: it never asks a tile table
         const long long M = (long long)net->max_batch * (net->height / c.d.out_div) * (net->width / c.d.out_div);
         // whether a tile fits depends on the conv's widths alone, never on the rows: the planned batch answers for every call
         if (family_tile(family_of_conv(net, slot), c, M, M, net->out_slot[c.d.dst] < 0) < 0) return slot;
@@ -766,6 +814,9 @@ static y3_status set_split_k(const y3::ConvFamily &f, y3_net *net, int slot, int
     ConvSlot &c = net->convs[slot];
     if (S > 1) {
         const char *why = nullptr;
+        // a conv of the fused tiny stem first: its 32 -> 32 conv has no 16-bit tile, and the refusal should name the stem, not the tile table
+        if (const int oi = y3::conv_op(net, slot); net->height && net->tiny_stem_fused && (oi == 0 || oi == 2))
+            return fail(Y3_ERR_INVALID, "%s: conv %d runs inside the fused tiny stem kernel (y3_net_set_tiny_stem_fusion), which is never split", sf.set_split, slot);
         // (a conv that runs in another family in this plan -- another mode's plan, an int8 plan's convs before the cut, whose Cin the int8
         // tiles need not divide -- and has no tile in f for that reason is told so by the two checks below)
         if (!split_eligible(f, net, slot, &why) && !(why == kNoTile && net->height && &y3::family_of_conv(net, slot) != &f))
@@ -929,7 +980,7 @@ void y3_net_destroy(y3_net *net)
         }
     }
     for (ConvSlot &c : net->convs)
-        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, (void *)c.w0norm_dev, (void *)c.scale0norm_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_x2_dev, (void *)c.scale_dev, (void *)c.shift_dev, c.wi8_dev, (void *)c.sc_i8_dev})
+        for (void *p : {c.w_dev, (void *)c.w0stem_dev, (void *)c.w0raw_dev, (void *)c.w0norm_dev, (void *)c.scale0norm_dev, c.wbf_dev, c.wf16_dev, c.wx3_dev, c.wx2_dev, (void *)c.scale_x2_dev, (void *)c.scale_dev, (void *)c.shift_dev, c.wi8_dev, (void *)c.sc_i8_dev, (void *)c.w0tiny_dev, c.w1tiny_dev, c.w1tiny_bf_dev, c.w1tiny_f16_dev})
             if (p) (void)hipFree(p);
     delete net;
 }
@@ -968,6 +1019,14 @@ try {
         std::vector<float> scale_norm(scale.begin(), scale.begin() + d.cout);
         for (int n = 0; n < d.cout; ++n) scale_norm[n] = ldexpf(scale_norm[n], exps[n]);
         HIP_TRY(upload(c.scale0norm_dev, scale_norm));
+        // the fused tiny stem's copy at the real width 16: the HWIO rows of output channels 0..15 (unscaled; scale_dev / shift_dev begin with
+        // their scale and shift), and whether channels 16..31 are the lowering's zero pad channels
+        std::vector<float> w16((size_t)K * 16);
+        for (int k = 0; k < K; ++k)
+            for (int n = 0; n < 16; ++n) w16[(size_t)k * 16 + n] = w[(size_t)k * d.cout + n];
+        HIP_TRY(upload(c.w0tiny_dev, w16));
+        c.tiny_pad_zero = true;
+        for (int n = 16; n < d.cout; ++n) c.tiny_pad_zero = c.tiny_pad_zero && scale[n] == 0.0f && shift[n] == 0.0f;
     } else {
         // fp32 path: the BN scale is folded into the packed weights (one VALU multiply less per output element; VALU
         // time is matrix-pipe time for the fp32 MFMA).  The bf16 copy keeps the unscaled weights + scale in the epilogue.
@@ -988,6 +1047,21 @@ try {
         // the int8 copy: the raw weights quantised per output channel (BN stays in the epilogue); their scales stay on the host for the plan
         HIP_TRY(upload(c.wi8_dev, pack_i8(pk, K, d.cout, CP64, c.sw_host)));
         c.bn_scale_host = scale;
+        if (d.size == 3 && d.stride == 1 && d.cin == 32 && d.cout == 32 && d.src1 < 0) {
+            // the fused tiny stem's copies at the real input width 16: [144][32], row tap * 16 + c from input channels c < 16, unscaled
+            std::vector<float> t32((size_t)144 * 32);
+            for (int tap = 0; tap < 9; ++tap)
+                for (int ch = 0; ch < 16; ++ch)
+                    for (int n = 0; n < 32; ++n) t32[((size_t)tap * 16 + ch) * 32 + n] = w[((size_t)tap * 32 + ch) * 32 + n];
+            std::vector<unsigned short> tb(t32.size()), th(t32.size());
+            for (size_t i = 0; i < t32.size(); ++i) {
+                tb[i] = f32_to_bf16_rne(t32[i]);
+                th[i] = f32_to_f16_rne(t32[i]);
+            }
+            HIP_TRY(upload(c.w1tiny_dev, t32));
+            HIP_TRY(upload(c.w1tiny_bf_dev, tb));
+            HIP_TRY(upload(c.w1tiny_f16_dev, th));
+        }
     }
     HIP_TRY(upload(c.scale_dev, scale));
     HIP_TRY(upload(c.shift_dev, shift));
@@ -1048,6 +1122,16 @@ Y3_CATCH("y3_net_set_stem_fusion")
 y3_status y3_net_set_stem_fusion_f16(y3_net *net, int on)
 try { return set_stem_fusion("y3_net_set_stem_fusion_f16", net, &y3_net::stem_mode_f16, on); }
 Y3_CATCH("y3_net_set_stem_fusion_f16")
+
+y3_status y3_net_set_tiny_stem_fusion(y3_net *net, int on)
+try {
+    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "y3_net_set_tiny_stem_fusion: argument must be 0 or 1");
+    net->tiny_stem_mode = on;   // read by the next y3_net_plan: the arena is placed by it
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_tiny_stem_fusion")
+
+int y3_net_get_tiny_stem_fused(const y3_net *net) { return net && net->height && net->tiny_stem_fused ? 1 : 0; }
 
 y3_status y3_net_set_k_chunk(y3_net *net, int channels)
 try {

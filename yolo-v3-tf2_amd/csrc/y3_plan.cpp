@@ -108,7 +108,7 @@ static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const
     std::vector<int> order;
     for (int t = 0; t < nt; ++t) {
         const bool external = t == net->input_tensor || net->out_slot[t] >= 0;
-        if (first[t] >= 0 && !external) order.push_back(t);
+        if (first[t] >= 0 && !external && !net->tiny_inner[t]) order.push_back(t);   // a tensor inside the fused tiny stem is never stored
     }
     std::sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
     for (int t : order) {
@@ -309,8 +309,10 @@ try {
     if (y3_status st = y3::resolve_i8(net); st != Y3_OK) {   // every plan: the element size per tensor; int8 plans: the cut and the scales
         net->height = net->width = net->max_batch = 0;      // no plan
         net->dtype = Y3_DTYPE_F32;
+        net->tiny_stem_fused = false;
         return st;
     }
+    y3::resolve_tiny_stem(net);   // before the tile check: the 32 -> 32 conv inside the fused tiny stem asks no tile table
     // A conv no tile of its mode divides (the 16-bit tables have no 32-wide tile of K step 32: y3_net_create in include/y3.h): the mode
     // cannot run the net.  Refused here, by name and before anything is allocated, not by the first forward's launch
     if (const int slot = y3::conv_without_tile(net); slot >= 0) {
@@ -321,6 +323,7 @@ try {
         if (dtype == Y3_DTYPE_I8 && mode != Y3_DTYPE_I8) snprintf(where, sizeof(where), " (it lies before the int8 cut, conv %d, and runs in fp16)", cut);
         net->height = net->width = net->max_batch = 0;      // no plan
         net->dtype = Y3_DTYPE_F32;
+        net->tiny_stem_fused = false;
         return fail(Y3_ERR_INVALID, "y3_net_plan: conv %d (Cin %d, c0 %d, Cout %d) has no %s tile%s: no built tile of that mode divides these "
                                     "widths (with Cin or c0 an odd multiple of 32 the 16-bit modes need Cout padded to a multiple of 64); "
                                     "Y3_DTYPE_F32, Y3_DTYPE_F32X3 and Y3_DTYPE_F32X2 run it",
@@ -332,9 +335,10 @@ try {
         // elements whatever the plan's format
         const bool f32 = net->out_slot[t] >= 0 || (t == net->input_tensor && net->tensors[t].channels == 3);
         const size_t addressed = f32 ? net->tbytes[t] / net->telem[t] * 4 : net->tbytes[t];
-        if (addressed >= 0xFFFFFFF0ull && first[t] >= 0) {
+        if (addressed >= 0xFFFFFFF0ull && first[t] >= 0 && !net->tiny_inner[t]) {
             net->height = net->width = net->max_batch = 0;      // no plan
             net->dtype = Y3_DTYPE_F32;
+            net->tiny_stem_fused = false;
             return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, addressed);
         }
     }

@@ -440,3 +440,30 @@ def _lower(p: Program):
     ops = [o for o in ops if not (isinstance(o, AuxOp) and o.dst in folded)]
     p.ops = ops
     p.outputs = [real(o) for o in p.outputs]
+
+
+def tiny_stem_applicable(p: Program) -> bool:
+    """Does the lowered program start with the stem of YOLOv3-tiny, which Net.set_tiny_stem_fusion runs as one kernel (include/y3.h,
+    y3_net_set_tiny_stem_fusion)?  Op 0 the first-layer conv 3x3 / 1, 3 -> 16 (stored 32) on the input, op 1 a max-pool 2x2 / 2 on it, op 2
+    a 3x3 / 1 conv 16 (stored 32) -> 32 with one source and no shortcut, op 3 a max-pool 2x2 / 2 on it; each of the first three outputs
+    has exactly one reader and none of the four is a net output.  The device decides the same from the stored widths and conv0's weights."""
+    ops = p.ops
+    if len(ops) < 5 or not (isinstance(ops[0], ConvOp) and isinstance(ops[1], AuxOp) and isinstance(ops[2], ConvOp) and isinstance(ops[3], AuxOp)):
+        return False
+    c0, p0, c1, p1 = ops[:4]
+    stored = p.stored or [t.channels for t in p.tensors]
+    if not (c0.size == 3 and c0.stride == 1 and c0.cin == 3 and c0.src0 == p.input_tensor and c0.src1 < 0 and c0.residual < 0
+            and p.tensors[c0.dst].channels == 16 and stored[c0.dst] == 32):
+        return False
+    if not (p0.kind == "maxpool_s2" and p0.inputs == [c0.dst] and p1.kind == "maxpool_s2" and p1.inputs == [c1.dst]):
+        return False
+    if not (c1.size == 3 and c1.stride == 1 and c1.src0 == p0.dst and c1.src1 < 0 and c1.residual < 0 and not c1.src0_upsample
+            and p.tensors[p0.dst].channels == 16 and c1.cin == 32 and c1.cout == 32 and p.tensors[c1.dst].channels == 32):
+        return False
+    if any(t in p.outputs for t in (c0.dst, p0.dst, c1.dst, p1.dst)):
+        return False
+    for t in (c0.dst, p0.dst, c1.dst):
+        readers = sum((o.src0 == t) + (o.src1 == t) + (o.residual == t) if isinstance(o, ConvOp) else o.inputs.count(t) for o in ops)
+        if readers != 1:
+            return False
+    return True

@@ -45,7 +45,33 @@ def tuning_table_path(tag: str, batch: int, image_size) -> str:
     return path
 
 
-class Net:
+class _TinyStemSwitch:
+    """The fused stem of YOLOv3-tiny (include/y3.h, y3_net_set_tiny_stem_fusion; csrc/conv_tiny_stem.hip): the part of Net's interface that
+    came with it, kept in a base of its own."""
+
+    @staticmethod
+    def _tiny_stem_arg(on) -> int:
+        if on is None:
+            return 0
+        if isinstance(on, (bool, np.bool_, int, np.integer)) and int(on) in (0, 1):
+            return int(on)
+        raise Y3Error(f"tiny stem fusion must be None, a bool, 0 or 1 (got {on!r})")
+
+    def set_tiny_stem_fusion(self, on=True):
+        """conv0 + pool 0 + conv1 + pool 1 of YOLOv3-tiny as one kernel: off by default; None means off.  Before plan().  Acts on fp32, bf16
+        and fp16 plans of a program that starts with that stem and is ignored on any other; with it tiny plans in bf16 and fp16, which
+        refuse it otherwise.  keep_activations() does not switch it off: the three tensors inside the launch are not stored, and
+        read_tensor on one of them raises.  set_stem_fusion / set_stem_fusion_f16 do not act on it, nor it on them."""
+        on = self._tiny_stem_arg(on)            # the argument check comes first: it needs no device net
+        check(self.lib.y3_net_set_tiny_stem_fusion(self._h, on), "y3_net_set_tiny_stem_fusion")
+
+    @property
+    def tiny_stem_fused(self) -> int:
+        """1 when the planned net runs the fused tiny stem launch (y3_net_get_tiny_stem_fused), 0 otherwise, also before plan()."""
+        return int(self.lib.y3_net_get_tiny_stem_fused(self._h))
+
+
+class Net(_TinyStemSwitch):
     """Device-side network = the fused conv program (reference counterpart: the Keras Model returned by
     ParseModel.build_model, core/parse_model.py:279-314)."""
 

@@ -261,6 +261,16 @@ int y3_net_get_split_k_f16(const y3_net *net, int conv_slot);
 y3_status y3_net_set_low_latency_i8(y3_net *net, int on);
 y3_status y3_net_set_split_k_i8(y3_net *net, int conv_slot, int S);
 int y3_net_get_split_k_i8(const y3_net *net, int conv_slot);
+/* The persistent kernels: a fixed grid of workgroups, each walking its tiles with tile += grid (the fused stems) or, per output-channel
+ * slice, spatial tile += grid / slices (the weight-resident 3x3 convs).  Y3_PERSISTENT_*: which one.  TINY_STEM -- the fused YOLOv3-tiny
+ * stem in every format, tiles of 4 x 8 pool-1 pixels, min(n_tiles, 4 * n_cus); STEM_F32 / STEM_16 -- the fused YOLOv3 stem, tiles of
+ * 8 x 16 conv1 pixels, min(n_tiles, n_cus) in fp32 and min(n_tiles, 2 * n_cus) in bf16 / fp16; RES_F32 (tile id 33, tiles of 8 x 16
+ * pixels) / RES_16 (16-bit tile id 32, tiles of 4 x 32 pixels) -- min(n_tiles, max(1, n_cus / slices)) * slices with slices = Cout / 64.
+ * A workgroup's walk is n_tiles / (grid / slices) tiles long, one more for the first n_tiles % (grid / slices) of a slice. */
+enum { Y3_PERSISTENT_TINY_STEM = 0, Y3_PERSISTENT_STEM_F32 = 1, Y3_PERSISTENT_STEM_16 = 2, Y3_PERSISTENT_RES_F32 = 3, Y3_PERSISTENT_RES_16 = 4 };
+/* Workgroups the persistent kernel `kind` launches for n_tiles spatial tiles, `slices` output-channel slices (weight-resident convs;
+ * 1 otherwise) on a device of n_cus compute units; <= 0: bad arguments.  Pure, no device. */
+int y3_persistent_grid(int kind, long long n_tiles, int slices, int n_cus);
 y3_status y3_net_keep_activations(y3_net *net, int keep);
 /* 1 (default): when the program starts with conv0 (3x3/1, 3 -> 32) feeding only conv1 (3x3/2, 32 -> 64) -- the Darknet-53
  * stem, reference config/models/yolov3/backbone.yaml layers 1-2 -- and the plan is fp32 or bf16 without keep_activations,

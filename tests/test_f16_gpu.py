@@ -49,7 +49,8 @@ def _stored_check(got, ref, cap, what):
 @pytest.mark.parametrize("cin,cout,S,B", [(32, 64, 40, 3), (64, 128, 36, 2), (64, 64, 33, 2), (32, 128, 70, 1)])
 def test_f16_weight_resident_3x3_matches_oracle_and_generic_tiles(rt, cin, cout, S, B):
     """Tile id 32 in an fp16 plan (csrc/conv_res_f16.hip), the shapes of test_bf16_weight_resident_3x3_matches_oracle_and_generic_tiles:
-    with and without a shortcut, BN + leaky and linear + bias, ragged last tile columns and rows, several images.  Every 3x3 launch
+    with and without a shortcut, BN + leaky and linear + bias, ragged last tile columns and rows, several images (one tile per
+    persistent workgroup at these shapes; walks of three tiles: tests/test_persistent_walk_gpu.py).  Every 3x3 launch
     against the fp16 oracle on its own device inputs, and the whole net bit for bit against the generic tile of the same MFMA shape."""
     from oracle import oracle as O
     from yolo_v3_tf2_amd.weights import synthetic_weights

@@ -465,8 +465,9 @@ def test_bf16_weight_resident_3x3_matches_oracle_and_generic_tiles(rt, cin, cout
     """bf16 tile id 32 (csrc/conv_res_bf16.hip): 3x3 / stride-1 convs with 32 / 64 input channels run with their weights resident in
     LDS and the input patch of a 4 x 32-pixel tile fetched by LDS-DMA (zero padding = the buffer bounds check).  With and without
     a shortcut, BN + leaky and linear + bias, image widths that are not multiples of the 32-pixel tile (40, 36, 33, 70 -> ragged
-    last column of tiles), heights not multiples of 4 (33, 70 -> ragged last row), several images (persistent workgroups walk
-    tiles of different images): every output against the bf16-emulating oracle under the per-layer bf16 bar, and against the
+    last column of tiles), heights not multiples of 4 (33, 70 -> ragged last row), several images (these shapes give at most 60 tiles
+    to 256 workgroups, 36 to 128 per slice: ONE tile per workgroup; walks of three tiles across images are
+    tests/test_persistent_walk_gpu.py): every output against the bf16-emulating oracle under the per-layer bf16 bar, and against the
     generic LDS-DMA tile of the same MFMA shape (same k order: tap * Cin + c in groups of 16) bit for bit."""
     from tests.helpers import mini_program
     from yolo_v3_tf2_amd.weights import synthetic_weights

@@ -25,6 +25,8 @@ TILES_X2_BUILT = (0, 1, 2, 3, 4, 8, 12, 26, 27)
 TILES_X3_BUILT = (0, 1, 2, 3, 4, 8, 9, 12, 13, 14)
 Y3_AUX_ADD, Y3_AUX_UPSAMPLE2X, Y3_AUX_CONCAT, Y3_AUX_MAXPOOL2X2_S2, Y3_AUX_MAXPOOL2X2_S1 = 0, 1, 2, 3, 4
 Y3_NMS_AGNOSTIC, Y3_NMS_PER_CLASS = 0, 1   # y3_net_set_nms_mode
+# y3_persistent_grid: the persistent kernels (fused tiny stem, fused stem fp32 / 16-bit, weight-resident conv fp32 / 16-bit)
+Y3_PERSISTENT_TINY_STEM, Y3_PERSISTENT_STEM_F32, Y3_PERSISTENT_STEM_16, Y3_PERSISTENT_RES_F32, Y3_PERSISTENT_RES_16 = 0, 1, 2, 3, 4
 MAX_TILES = 64   # y3_tile_grid, y3_merge_tile_detections: tiles per frame
 # (BM, BN, waves, LDS stages) of every tile id of the fp32 MFMA conv kernel (mirror of kTiles in csrc/conv_f32.hip)
 # (0, 0, 0, 0): a retired id (y3_tile_built answers 0).  Round 5: only tiles a packaged tuning table or the library's heuristic selects are built.
@@ -133,6 +135,7 @@ SYMBOLS = {
     "y3_net_set_split_k": (_i, [_vp, _i, _i]),
     "y3_net_get_split_k": (_i, [_vp, _i]),
     "y3_choose_split_k": (_i, [C.c_longlong, _i, _i, C.c_longlong]),
+    "y3_persistent_grid": (_i, [_i, C.c_longlong, _i, _i]),
     "y3_net_set_low_latency_bf16": (_i, [_vp, _i]),
     "y3_net_set_split_k_bf16": (_i, [_vp, _i, _i]),
     "y3_net_get_split_k_bf16": (_i, [_vp, _i]),

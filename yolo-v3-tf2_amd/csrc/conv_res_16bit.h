@@ -242,10 +242,7 @@ static hipError_t launch(const ConvArgs &a, hipStream_t s)
     const int tiles_x = (a.Wo + RTW - 1) / RTW, tiles_y = (a.Ho + RTH - 1) / RTH;
     const int n_spatial = a.B * tiles_y * tiles_x, slices = a.Cout / RSLICE;
     const int cus = a.n_cus > 0 ? a.n_cus : 256;                // read once at plan time (y3_net_plan): no runtime query on the enqueue path
-    int per_slice = cus / slices;                               // one persistent workgroup per CU (the resident weights + two patches fill its LDS)
-    if (per_slice < 1) per_slice = 1;
-    if (per_slice > n_spatial) per_slice = n_spatial;
-    const int grid = per_slice * slices;
+    const int grid = persistent_res_per_slice(n_spatial, slices, cus) * slices;   // one persistent workgroup per CU (the resident weights + two patches fill its LDS)
     if (a.Cin == 32) {
         static LdsAttrOnce attr;
         if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv3x3_res16<E, 32>), ResGeom<32>::LDS_BYTES, a.device); e != hipSuccess) return e;

@@ -347,7 +347,7 @@ hipError_t launch_conv_stem_f32(const StemArgs &a, hipStream_t s)
     static LdsAttrOnce attr;
     if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv_stem_f32), LDS_BYTES, a.device); e != hipSuccess) return e;
     const int cus = a.n_cus > 0 ? a.n_cus : 256;                // read once at plan time (y3_net_plan)
-    const int grid = p.n_tiles < cus ? p.n_tiles : cus;         // one persistent workgroup per CU
+    const int grid = persistent_stem_grid(p.n_tiles, kStemWgPerCuF32, cus);   // one persistent workgroup per CU
     hipLaunchKernelGGL(conv_stem_f32, dim3(grid), dim3(NT), LDS_BYTES, s, p);
     return hipGetLastError();
 }
@@ -709,7 +709,7 @@ static hipError_t launch_conv_stem16(const StemArgs &a, hipStream_t s)
     static LdsAttrOnce attr;   // per instantiation
     if (hipError_t e = set_max_lds_once(attr, reinterpret_cast<const void *>(conv_stem16<E>), LDS_BYTES_B, a.device); e != hipSuccess) return e;
     const int cus = a.n_cus > 0 ? a.n_cus : 256;                // read once at plan time (y3_net_plan)
-    const int grid = p.n_tiles < 2 * cus ? p.n_tiles : 2 * cus;   // two persistent workgroups per CU
+    const int grid = persistent_stem_grid(p.n_tiles, kStemWgPerCu16, cus);   // two persistent workgroups per CU
     hipLaunchKernelGGL(conv_stem16<E>, dim3(grid), dim3(NT), LDS_BYTES_B, s, p);
     return hipGetLastError();
 }

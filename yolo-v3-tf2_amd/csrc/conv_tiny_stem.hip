@@ -57,7 +57,7 @@ constexpr int IMG_F = IH * IW * 3;                // 2508 floats
 constexpr int NT = 256;
 constexpr int ROUNDS = (NPOS + 63) / 64;          // 3: pooled positions per lane in phase 1
 constexpr int IMG_PER_THREAD = (IMG_F + NT - 1) / NT;   // 10
-constexpr int WG_PER_CU = 4;                      // persistent workgroups per CU the grid is sized for
+constexpr int WG_PER_CU = kTinyStemWgPerCu;       // persistent workgroups per CU the grid is sized for (4; y3_kernels.h)
 struct F32 {};                                    // element tag of the fp32 form (the 16-bit forms: Bf16Elem, F16Elem)
 template <class E> constexpr int elem_bytes() { return std::is_same_v<E, F32> ? 4 : 2; }
 constexpr int W0_F = 27 * C0;                     // conv0's weights: 432 floats
@@ -322,7 +322,7 @@ static hipError_t launch_conv_tiny_stem(KERNEL kernel, const TinyStemArgs &a, hi
     if (n > 0x7fffffffll) return hipErrorInvalidValue;
     p.n_tiles = (int)n;
     const int cus = a.n_cus > 0 ? a.n_cus : 256;                // read once at plan time (y3_net_plan)
-    const int grid = p.n_tiles < WG_PER_CU * cus ? p.n_tiles : WG_PER_CU * cus;
+    const int grid = persistent_stem_grid(p.n_tiles, WG_PER_CU, cus);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), lds_bytes<E>(), s, p);
     return hipGetLastError();
 }

@@ -118,6 +118,26 @@ inline hipError_t set_max_lds_once(LdsAttrOnce &st, const void *fn, int bytes, i
     return e;
 }
 
+// Grids of the persistent kernels (a fixed number of workgroups walks the tiles, tile += gridDim.x): the one definition their launchers
+// call and y3_persistent_grid (include/y3.h, Y3_PERSISTENT_*) answers from.  cus > 0.
+// A fused stem: wg_per_cu workgroups per CU, never more than there are tiles.
+constexpr int kTinyStemWgPerCu = 4;   // conv_tiny_stem.hip, all three formats
+constexpr int kStemWgPerCuF32 = 1;    // conv_stem.hip, conv_stem_f32
+constexpr int kStemWgPerCu16 = 2;     // conv_stem.hip, conv_stem16<bf16 / f16>
+inline int persistent_stem_grid(long long n_tiles, int wg_per_cu, int cus)
+{
+    return n_tiles < (long long)wg_per_cu * cus ? (int)n_tiles : wg_per_cu * cus;
+}
+// A weight-resident conv (conv_res_f32.hip, conv_res_16bit.h): one workgroup per CU, the CUs shared out evenly among the output-channel
+// slices; workgroup w keeps slice w % slices and walks the spatial tiles w / slices, + grid / slices, ...  -> workgroups per slice.
+inline int persistent_res_per_slice(long long n_spatial, int slices, int cus)
+{
+    int per_slice = cus / slices;
+    if (per_slice < 1) per_slice = 1;
+    if (per_slice > n_spatial) per_slice = (int)n_spatial;
+    return per_slice;
+}
+
 // The tail every MFMA conv launcher shares: the dynamic-LDS attribute once per (instantiation, device), the launch, its status.
 template <auto KERNEL>
 static hipError_t launch_conv_kernel(const ConvArgs &a, int grid, int threads, size_t lds, hipStream_t s, int grid_y = 1)

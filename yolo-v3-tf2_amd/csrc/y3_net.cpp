@@ -1319,4 +1319,19 @@ int y3_choose_split_k(long long tiles, int k_tiles, int n_cus, long long slab_by
     return S < 2 ? 1 : (int)S;
 }
 
+int y3_persistent_grid(int kind, long long n_tiles, int slices, int n_cus)
+{
+    // the launchers' own formulas (y3_kernels.h); what they refuse or never see is refused here: no tiles, more than an int of them,
+    // slices on a kernel that has none
+    if (n_tiles <= 0 || n_tiles > 0x7fffffffll || slices <= 0 || n_cus <= 0) return 0;
+    switch (kind) {
+        case Y3_PERSISTENT_TINY_STEM: return slices == 1 ? y3::persistent_stem_grid(n_tiles, y3::kTinyStemWgPerCu, n_cus) : 0;
+        case Y3_PERSISTENT_STEM_F32: return slices == 1 ? y3::persistent_stem_grid(n_tiles, y3::kStemWgPerCuF32, n_cus) : 0;
+        case Y3_PERSISTENT_STEM_16: return slices == 1 ? y3::persistent_stem_grid(n_tiles, y3::kStemWgPerCu16, n_cus) : 0;
+        case Y3_PERSISTENT_RES_F32:
+        case Y3_PERSISTENT_RES_16: return y3::persistent_res_per_slice(n_tiles, slices, n_cus) * slices;
+        default: return 0;
+    }
+}
+
 }  // extern "C"

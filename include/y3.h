@@ -271,6 +271,17 @@ enum { Y3_PERSISTENT_TINY_STEM = 0, Y3_PERSISTENT_STEM_F32 = 1, Y3_PERSISTENT_ST
 /* Workgroups the persistent kernel `kind` launches for n_tiles spatial tiles, `slices` output-channel slices (weight-resident convs;
  * 1 otherwise) on a device of n_cus compute units; <= 0: bad arguments.  Pure, no device. */
 int y3_persistent_grid(int kind, long long n_tiles, int slices, int n_cus);
+/* Lane regions.  A forward of `batch` images on `lanes` concurrent sub-batches (y3_net_set_lanes; a forward uses min(lanes, batch))
+ * gives lane l the images [start[l], start[l+1]), start[l] = batch * l / lanes, and every arena block of block_bytes bytes is cut into one
+ * region per lane.  y3_lane_offset is the byte offset of lane `lane`'s region from the block start -- the function every launch's
+ * addresses come from:
+ *     off[0] = 0,   off[l] = roundup256(off[l-1] + ceil(block_bytes * (start[l] - start[l-1]) / batch))
+ * Every offset is a multiple of 256; a region holds its lane's share of the block, ceil(block_bytes * nb / batch) >= nb * image bytes of
+ * any tensor that fits the block at `batch` images, before the next one starts, so two lanes never share a byte; the last region ends
+ * fewer than 256 * lanes bytes past the block, inside the 4096 bytes of slack every block is allocated with.  Where
+ * block_bytes * start[l] / batch is a multiple of 256 for every lane the regions are contiguous: off[l] is that value.
+ * -1: block_bytes < 0, batch < 1, lanes outside 1..4 or above batch, lane outside [0, lanes).  Pure, no device. */
+long long y3_lane_offset(long long block_bytes, int batch, int lanes, int lane);
 y3_status y3_net_keep_activations(y3_net *net, int keep);
 /* 1 (default): when the program starts with conv0 (3x3/1, 3 -> 32) feeding only conv1 (3x3/2, 32 -> 64) -- the Darknet-53
  * stem, reference config/models/yolov3/backbone.yaml layers 1-2 -- and the plan is fp32 or bf16 without keep_activations,
@@ -378,8 +389,14 @@ y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int 
  * Replaces model(inputs) (reference: inference.py:109). */
 y3_status y3_net_forward(y3_net *net, const float *images_dev, int batch, float *const grids_dev[3], void *stream);
 
-/* debugging / tests: copy tensor `tensor_id` of the last forward to dst_dev as fp32 (element count returned
- * through *n_elems; dst_dev may be NULL to query the size) */
+/* debugging / tests: copy images [0, batch) of tensor `tensor_id` of the last forward to dst_dev as fp32 (element count returned
+ * through *n_elems; dst_dev may be NULL to query the size).  batch outside 1..max_batch is refused with Y3_ERR_INVALID, the size
+ * query included.  The net remembers the (batch, lanes) of the last forward enqueued on the plan: after a forward on one lane any
+ * batch up to max_batch reads image i at i * image bytes (images beyond that forward's batch hold what earlier forwards left); after
+ * a forward on several lanes the images lie in the lanes' regions (y3_lane_offset): where those follow one another without a gap the
+ * read is the one-lane read; otherwise the images are gathered from the regions, lane by lane, and a batch other than that forward's is
+ * refused with Y3_ERR_STATE -- its images are not where a contiguous read would look.
+ * y3_net_read_tensor_i8 below follows the same rules for an int8 tensor of the arena. */
 y3_status y3_net_read_tensor(y3_net *net, int tensor_id, int batch, float *dst_dev, size_t *n_elems, void *stream);
 
 /* ------------------------------------------------------------------------------------------

@@ -36,9 +36,16 @@ def test_high_tensors_and_checked_images(case):
         b0, nb = hc.lane_ranges(case)[-1]
         assert b0 > 0 and all(v == (b0, nb) for v in high.values())
         assert all(hc.tensor_bytes(case, t, hc.lane_ranges(case)[0][1]) <= hc.HIGH for t in high), "the last lane ALONE is high"
-        # a lane's region of an arena block starts at its first image rounded up to 256 bytes: no gap, so read_tensor sees the batch in order
+        # a lane's region of an arena block starts where the lane before it ends, rounded up to 256 bytes (y3_lane_offset): with every
+        # lane's bytes a multiple of 256 there is no gap, each region starts at its first image, and read_tensor sees the batch in order
+        from yolo_v3_tf2_amd import _lib
         p, _ = case.program()
-        assert all(b0 * hc.image_bytes(case, t) % 256 == 0 for t in hc.plan_tensors(case) if t != p.input_tensor and t not in p.outputs)
+        arena = [t for t in hc.plan_tensors(case) if t != p.input_tensor and t not in p.outputs]
+        assert all(b0 * hc.image_bytes(case, t) % 256 == 0 for t in arena)
+        for t in arena:
+            per = hc.image_bytes(case, t)
+            offs = [_lib.load().y3_lane_offset(case.batch * per, case.batch, case.lanes, l) for l in range(case.lanes)]
+            assert offs == [s * per for s, _ in hc.lane_ranges(case)], (case.name, t, offs)
     if case.border_skip:
         assert all(nb % 32 == 0 and nb >= 32 for _, nb in hc.lane_ranges(case))
     if case.near_guard:

@@ -136,6 +136,7 @@ SYMBOLS = {
     "y3_net_get_split_k": (_i, [_vp, _i]),
     "y3_choose_split_k": (_i, [C.c_longlong, _i, _i, C.c_longlong]),
     "y3_persistent_grid": (_i, [_i, C.c_longlong, _i, _i]),
+    "y3_lane_offset": (C.c_longlong, [C.c_longlong, _i, _i, _i]),
     "y3_net_set_low_latency_bf16": (_i, [_vp, _i]),
     "y3_net_set_split_k_bf16": (_i, [_vp, _i, _i]),
     "y3_net_get_split_k_bf16": (_i, [_vp, _i]),

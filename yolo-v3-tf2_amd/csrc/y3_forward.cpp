@@ -31,12 +31,16 @@ static y3_status check_forward_args(const y3_net *net, bool args_ok, int batch, 
     return Y3_OK;
 }
 
-// The part of a forward one run() step enqueues: images [b0, b0 + nb) of the batch, as lane `lane`, on stream s
+// first image of lane l when `batch` images run on `lanes` lanes: the one split run(), y3_lane_offset and the tensor read-back share
+static inline int lane_start(int batch, int lanes, int l) { return (int)((long long)batch * l / lanes); }
+
+// The part of a forward one run() step enqueues: images [b0, b0 + nb) of the batch, as lane `lane` of `lanes`, on stream s
 struct Slice {
     const y3_net *net;
     const Forward &f;
     int b0, nb, lane;
     hipStream_t s;
+    int lanes;                               // the lanes this forward runs on (run(): min(f.lanes, batch))
 
     size_t img_elems(int t) const { return (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels; }
     // element size: head grids are always fp32; the image batch is fp32 when the Cin = 3 first-layer kernel reads it
@@ -72,9 +76,8 @@ struct Slice {
         char *blk = static_cast<char *>(net->tdev[t]);
         if (!blk) return nullptr;
         if (net->dense[t]) return blk + (size_t)b0 * img_elems(t) * elem_bytes(t);
-        // lane regions start at the lane's first image (scaled to the block size), 256-B aligned; blocks carry 4 KiB of slack
-        const size_t off = ((size_t)((double)net->tblock[t] * b0 / f.batch) + 255) & ~(size_t)255;
-        return blk + (lane ? off : 0);
+        // lane regions: y3_lane_offset (include/y3.h), 256-B aligned and disjoint; blocks carry 4 KiB of slack
+        return blk + (lane ? (size_t)y3_lane_offset((long long)net->tblock[t], f.batch, lanes, lane) : 0);
     }
 
     // ConvArgs of conv slot `conv` in the plan's mode; a.dec set where it decodes its output in place (fused decode; its grid is then
@@ -345,6 +348,9 @@ static y3_status run(const y3_net *net, const Forward &f)
     // conv kernel drains (its last workgroups leave CUs under-occupied), the other sub-batch's kernel fills them.
     int lanes = f.lanes;
     while (lanes > 1 && batch / lanes < 1) --lanes;
+    // where this forward leaves its images in the arena: y3_net_read_tensor gathers them from there
+    net->last_batch = batch;
+    net->last_lanes = lanes;
     // leading segment in chunks small enough for their activations to stay in the 256 MB Infinity Cache between the
     // conv that writes them and the one that reads them, then the rest of the op list on the whole (sub-)batch
     const int k_early = f.ms_out ? 0 : net->early_ops;
@@ -352,18 +358,18 @@ static y3_status run(const y3_net *net, const Forward &f)
         if (k_early > 0) {
             for (int c0 = 0; c0 < nb; c0 += net->early_chunk) {
                 const int cn = nb - c0 < net->early_chunk ? nb - c0 : net->early_chunk;
-                y3_status r = Slice{net, f, b0 + c0, cn, lane, st}.run(0, k_early);
+                y3_status r = Slice{net, f, b0 + c0, cn, lane, st, lanes}.run(0, k_early);
                 if (r != Y3_OK) return r;
             }
         }
-        return Slice{net, f, b0, nb, lane, st}.run(k_early, (int)net->ops.size());
+        return Slice{net, f, b0, nb, lane, st, lanes}.run(k_early, (int)net->ops.size());
     };
     if (lanes == 1) return run_lane(0, batch, s, 0);
     if (!net->fork_ev) return fail(Y3_ERR_STATE, "y3_net_forward: no lane streams (y3_net_plan creates them)");
     HIP_TRY(hipEventRecord(net->fork_ev, s));
     // equal sub-batches (measured with tools/lanes_sweep.py: weighted 2:3 / 3:4:5 splits were 2-3 % slower)
     int start[Y3_MAX_LANES + 1];
-    for (int l = 0; l <= lanes; ++l) start[l] = (int)((long long)batch * l / lanes);
+    for (int l = 0; l <= lanes; ++l) start[l] = lane_start(batch, lanes, l);
     // lane 0 runs on the caller's stream itself: its first kernel needs no cross-queue signal to start, and the join waits for the other lanes only
     // (fp32 eager step 31.324 -> 31.218 ms, +0.3 %, every round of three; bf16 graph replay unchanged: profiles/r05_ab_lane0_on_caller_stream.txt)
     hipStream_t ls[Y3_MAX_LANES];
@@ -389,7 +395,7 @@ static y3_status run(const y3_net *net, const Forward &f)
             for (int l = 0; l < lanes; ++l) {
                 const int nb = start[l + 1] - start[l];
                 if (nb <= 0) continue;
-                y3_status st = Slice{net, f, start[l], nb, l, ls[l]}.run(oi, oi + 1);
+                y3_status st = Slice{net, f, start[l], nb, l, ls[l], lanes}.run(oi, oi + 1);
                 if (st != Y3_OK) return st;
             }
     }
@@ -537,24 +543,67 @@ try {
 }
 Y3_CATCH("y3_net_measure_sclk_all")
 
+// In how many lane regions arena tensor t of the last forward lies for a read of `batch` images (1: image i at i * image bytes).  After a
+// forward on several lanes only that forward's batch can be gathered; a tensor of the chunked segment is dense whatever the lanes.
+static y3_status read_lanes(const y3_net *net, int t, int batch, const char *who, int *lanes)
+{
+    *lanes = 1;
+    if (net->dense[t] || net->last_lanes <= 1) return Y3_OK;
+    // regions that follow one another without a gap (the shipped networks at a full batch): image i at i * image bytes, as after one lane
+    const size_t img_bytes = (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels * net->telem[t];
+    bool contiguous = true;
+    for (int l = 1; l < net->last_lanes; ++l)
+        contiguous = contiguous && (size_t)y3_lane_offset((long long)net->tblock[t], net->last_batch, net->last_lanes, l) ==
+                                       (size_t)lane_start(net->last_batch, net->last_lanes, l) * img_bytes;
+    if (contiguous) return Y3_OK;
+    if (batch != net->last_batch)
+        return fail(Y3_ERR_STATE, "%s: the last forward wrote %d images on %d lanes; its tensors can be read back at that batch only (asked: %d)", who,
+                    net->last_batch, net->last_lanes, batch);
+    *lanes = net->last_lanes;
+    return Y3_OK;
+}
+
+long long y3_lane_offset(long long block_bytes, int batch, int lanes, int lane)
+{
+    if (block_bytes < 0 || batch < 1 || lanes < 1 || lanes > Y3_MAX_LANES || lanes > batch || lane < 0 || lane >= lanes) return -1;
+    unsigned long long off = 0;
+    for (int l = 1; l <= lane; ++l) {
+        const unsigned long long nb = (unsigned long long)(lane_start(batch, lanes, l) - lane_start(batch, lanes, l - 1));
+        const unsigned long long share = ((unsigned long long)block_bytes * nb + (unsigned long long)batch - 1) / (unsigned long long)batch;   // ceil
+        off = (off + share + 255) & ~255ull;
+    }
+    return (long long)off;
+}
+
 y3_status y3_net_read_tensor(y3_net *net, int t, int batch, float *dst_dev, size_t *n_elems, void *stream)
 try {
     if (!net || t < 0 || t >= (int)net->tensors.size() || !net->height)
         return fail(Y3_ERR_INVALID, "y3_net_read_tensor: bad argument");
-    const size_t npix = (size_t)batch * rows(net, t) * cols(net, t);
-    const size_t n = npix * net->tensors[t].channels;
+    if (batch < 1 || batch > net->max_batch) return fail(Y3_ERR_INVALID, "y3_net_read_tensor: batch %d outside 1..%d of the plan", batch, net->max_batch);
+    const size_t ipix = (size_t)rows(net, t) * cols(net, t);
+    const size_t n = (size_t)batch * ipix * net->tensors[t].channels;
     if (n_elems) *n_elems = n;
     if (!dst_dev) return Y3_OK;
     if (net->tiny_stem_fused && net->tiny_inner[t])
         return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d lies inside the fused tiny stem launch and is never stored (y3_net_set_tiny_stem_fusion(net, 0) and "
                                   "a new plan keep it)", t);
     if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
+    int lanes = 1;
+    if (y3_status st = read_lanes(net, t, batch, "y3_net_read_tensor", &lanes); st != Y3_OK) return st;
     Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
-    // an int8 plan: (float)q * s behind the cut, the fp16 value before it
-    hipError_t e = net->dtype != Y3_DTYPE_I8 ? y3::launch_to_f32(net->dtype, net->tdev[t], dst_dev, npix, net->tensors[t].channels, (hipStream_t)stream)
-                   : net->telem[t] == 1      ? y3::launch_i8_to_f32(net->tdev[t], dst_dev, n, net->tscale[t], (hipStream_t)stream)
-                                             : y3::launch_to_f32(Y3_DTYPE_F16, net->tdev[t], dst_dev, npix, net->tensors[t].channels, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
+    const int C = net->tensors[t].channels;
+    for (int l = 0; l < lanes; ++l) {   // one lane: the whole batch from the block start
+        const int b0 = lane_start(batch, lanes, l), nb = lane_start(batch, lanes, l + 1) - b0;
+        if (nb <= 0) continue;
+        const char *src = static_cast<const char *>(net->tdev[t]) + (l ? (size_t)y3_lane_offset((long long)net->tblock[t], batch, lanes, l) : 0);
+        float *dst = dst_dev + (size_t)b0 * ipix * C;
+        const size_t npix = (size_t)nb * ipix;
+        // an int8 plan: (float)q * s behind the cut, the fp16 value before it
+        hipError_t e = net->dtype != Y3_DTYPE_I8 ? y3::launch_to_f32(net->dtype, src, dst, npix, C, (hipStream_t)stream)
+                       : net->telem[t] == 1      ? y3::launch_i8_to_f32(src, dst, npix * C, net->tscale[t], (hipStream_t)stream)
+                                                 : y3::launch_to_f32(Y3_DTYPE_F16, src, dst, npix, C, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(Y3_ERR_HIP, "y3_net_read_tensor: %s", hipGetErrorString(e));
+    }
     return Y3_OK;
 }
 Y3_CATCH("y3_net_read_tensor")
@@ -563,14 +612,23 @@ y3_status y3_net_read_tensor_i8(y3_net *net, int t, int batch, int8_t *dst_dev, 
 try {
     if (!net || t < 0 || t >= (int)net->tensors.size() || !net->height || batch <= 0 || batch > net->max_batch)
         return fail(Y3_ERR_INVALID, "y3_net_read_tensor_i8: bad argument");
-    const size_t n = (size_t)batch * rows(net, t) * cols(net, t) * net->tensors[t].channels;
+    const size_t img = (size_t)rows(net, t) * cols(net, t) * net->tensors[t].channels;
+    const size_t n = (size_t)batch * img;
     if (n_elems) *n_elems = n;
     if (!dst_dev) return Y3_OK;
-    // the int8 copy of a tensor that crosses the cut, else an int8 tensor of the arena
+    // the int8 copy of a tensor that crosses the cut (image i at i * image bytes whatever the lanes), else an int8 tensor of the arena
     const void *src = net->dtype != Y3_DTYPE_I8 ? nullptr : net->tq8[t] ? net->tq8[t] : (net->telem[t] == 1 && net->out_slot[t] < 0) ? net->tdev[t] : nullptr;
     if (!src) return fail(Y3_ERR_STATE, "y3_net_read_tensor_i8: tensor %d is not held as int8 in this plan", t);
+    int lanes = 1;
+    if (!net->tq8[t])
+        if (y3_status st = read_lanes(net, t, batch, "y3_net_read_tensor_i8", &lanes); st != Y3_OK) return st;
     Y3_ENTER_DEVICE(net);
-    HIP_TRY(hipMemcpyAsync(dst_dev, src, n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    for (int l = 0; l < lanes; ++l) {
+        const int b0 = lane_start(batch, lanes, l), nb = lane_start(batch, lanes, l + 1) - b0;
+        if (nb <= 0) continue;
+        const char *from = static_cast<const char *>(src) + (l ? (size_t)y3_lane_offset((long long)net->tblock[t], batch, lanes, l) : 0);
+        HIP_TRY(hipMemcpyAsync(dst_dev + (size_t)b0 * img, from, (size_t)nb * img, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    }
     return Y3_OK;
 }
 Y3_CATCH("y3_net_read_tensor_i8")

@@ -172,6 +172,9 @@ struct y3_net {
     std::vector<size_t> tbytes;    // bytes at max_batch
     std::vector<size_t> tblock;    // size of the arena block the tensor lives in
     std::vector<void *> blocks;    // distinct hipMalloc'ed blocks
+    // (batch, lanes) of the last forward enqueued on this plan, 0 before the first: where its images lie in the arena (y3_lane_offset), for
+    // y3_net_read_tensor.  The one thing a forward notes in the net it otherwise only reads.
+    mutable int last_batch = 0, last_lanes = 0;
     // int8 plans.  act_scale: y3_net_set_act_scales, one fp32 scale per tensor, <= 0 unset (read by y3_net_plan).  i8_first_conv: c*, the
     // first conv slot that runs in int8 (-1: not an int8 plan); the convs before it launch what an fp16 plan launches.  telem: bytes per
     // element of every tensor in the arena (every plan: the mode's; int8 plans: 2 before the cut, 1 behind it).  tq8: the int8 copy of a

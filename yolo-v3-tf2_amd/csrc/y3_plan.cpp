@@ -343,6 +343,7 @@ try {
         }
     }
     if (y3_status st = place_tensors(net, first, last); st != Y3_OK) return st;
+    net->last_batch = net->last_lanes = 0;   // no forward has written into this arena
     for (int t = 0; t < nt; ++t) {   // int8 plans: the int8 copies of the tensors that cross the cut, blocks of their own
         if (!net->tcross[t]) continue;
         const size_t bytes = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels;

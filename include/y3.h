@@ -136,12 +136,25 @@ y3_status y3_net_set_conv_weights(y3_net *net, int conv_slot, const float *w, co
                                   const float *beta, const float *mean, const float *var, const float *bias,
                                   float eps);
 
-/* Tuning/testing knobs (no reference counterpart).
+/* Setters on a planned net.  A y3_net lives long and is planned again and again (another batch, canvas or mode); every y3_net_set_* and
+ * y3_net_keep_activations may be called before the first plan, between plans and on a planned net, and states below which of two things
+ * it does on a planned net:
+ *   ACTS AT ONCE -- the very next forward / detect runs as a fresh net would that was configured that way before its one plan:
+ *     y3_net_set_lanes, y3_net_set_tile / _bf16 / _x3 / _x2, y3_net_set_low_latency* and y3_net_set_split_k*, y3_net_set_stem_fusion /
+ *     _f16, y3_net_set_k_chunk, y3_net_set_border_skip, y3_net_set_xcd_mode, y3_net_set_nms_mode, y3_net_set_multi_label.
+ *   WAITS FOR THE NEXT PLAN -- the planned net keeps running, bit for bit, what it ran before the call; y3_net_plan reads the value:
+ *     y3_net_set_tiny_stem_fusion, y3_net_set_early_chunk, y3_net_keep_activations, y3_net_set_act_scales (they decide the arena).
+ *     The plan keeps its own copy of what it read; no decision of a planned net reads the live value.
+ * Every setting survives y3_net_plan: a plan changes none of them.  y3_net_set_conv_weights on a planned net acts at once, in every
+ * format, the int8 epilogue scales of the plan in force included.  (tests/test_lifecycle_gpu.py holds a long-lived net to this.)
+ * Tuning/testing knobs (no reference counterpart).
  * y3_net_set_tile: force the block tile of one conv (index into the kernel's tile table; -1 = heuristic).
  * A tile that cannot serve the conv (shape, or a bf16-only tile on a conv that writes an fp32 net output) is refused here with
  * Y3_ERR_INVALID and a message, not by the forward.
+ * On a planned net the forced tile acts at once (the split decision of the plan is made again with it); it survives y3_net_plan.
  * y3_net_keep_activations(1) before y3_net_plan: no buffer reuse, so y3_net_read_tensor can read any
- * intermediate after a forward.
+ * intermediate after a forward.  On a planned net it waits for the next plan: the arena, the fused stem (which needs buffer reuse) and
+ * the route y3_net_detect takes stay those of the plan in force.
  * y3_net_set_tile_bf16 acts on both 16-bit plans: Y3_DTYPE_BF16 and Y3_DTYPE_F16 plans share the tile ids, the heuristic and this
  * per-conv forced tile (no fp16 table is tuned or shipped). */
 y3_status y3_net_set_tile(y3_net *net, int conv_slot, int tile);
@@ -157,18 +170,21 @@ y3_status y3_net_set_tile_x2(y3_net *net, int conv_slot, int tile);   /* same ti
 int y3_choose_tile(int dtype, int size, int stride, int cin, int c0, int cout, long long M, long long M_plan, int arena_out);
 /* Run a forward as `lanes` (1..4) equal sub-batches: the first on the caller's stream itself, the others on forked
  * internal streams joined back into it: the tail of one sub-batch's conv kernel overlaps the next kernel of another.
- * Results are unchanged (images are independent).  Falls back to fewer lanes when the batch is not divisible. */
+ * Results are unchanged (images are independent).  Falls back to fewer lanes when the batch is not divisible.
+ * Acts at once on a planned net (the split-K workspace grows to one region per lane). */
 y3_status y3_net_set_lanes(y3_net *net, int lanes);
 /* Placement of the fp32 conv tiles on the 8 XCDs (each has a private 4 MB L2).  1 (default): per conv, the XCDs form an
  * (8/gn) x gn grid over the (pixel-tile, channel-tile) matrix, gn chosen so that an XCD's slice of the weights stays in
  * its L2 (the 256->512 / 512->1024 3x3 weights are 4.7 / 18.9 MB); 0: every XCD takes a contiguous run of tiles.
  * Results are bit-identical in both modes (same per-tile arithmetic).  A batch-minor launch (border skip, below) splits its border
- * tiles, whose K walks are short, and its interior tiles evenly over the XCD pixel-tile ranges of either mode (8 ranges in mode 0). */
+ * tiles, whose K walks are short, and its interior tiles evenly over the XCD pixel-tile ranges of either mode (8 ranges in mode 0).
+ * Read by every forward: acts at once on a planned net. */
 y3_status y3_net_set_xcd_mode(y3_net *net, int mode);
 /* K order of the fp32 3x3 convs.  channels > 0 (a multiple of 32): for every chunk of that many input channels all 9 taps,
  * then the next chunk, so that the 9 reads of a pixel (one per tap) fall close together in time and hit in L2 (the tap-
  * major order re-fetched the operands of the 13x13 layers ~18x from beyond L2).  The same products in another summation
- * order: results differ from the tap-major ones in the last bits.  0: tap-major; -1 (default): chosen per conv. */
+ * order: results differ from the tap-major ones in the last bits.  0: tap-major; -1 (default): chosen per conv.
+ * Read by every forward: acts at once on a planned net. */
 y3_status y3_net_set_k_chunk(y3_net *net, int channels);
 /* Border skip of the fp32 3x3 convs.  A 3x3 conv with pad 1 multiplies zeros wherever a tap of a border pixel falls outside the image
  * (10 % of the products at 13^2).  Where a call's images come in whole blocks of 32 (batch % 32 == 0 per lane), an fp32 plan runs its
@@ -176,7 +192,7 @@ y3_status y3_net_set_k_chunk(y3_net *net, int channels);
  * position-major, batch-minor over a table of output positions sorted by which taps read inside the image, and every workgroup leaves
  * out the taps that are padding for all of its positions.  Only products with zero are left out: results are bit-identical for finite
  * weights (a non-finite weight met 0 * inf = NaN at the border before and is skipped now).  mode -1 (default): the library's rule,
- * 0: off, 1: on wherever legal.  Read by every forward; other plans and ineligible convs launch what they always did.
+ * 0: off, 1: on wherever legal.  Read by every forward (acts at once on a planned net); other plans and ineligible convs launch what they always did.
  * y3_net_get_border_skip: in how many of its sub-batches (y3_net_set_lanes) a forward of `batch` images launches conv `conv_slot` of the
  * planned net that way under the mode in force (0: the raster launch everywhere, or no plan).
  * y3_border_order (pure, no device): the position table of one conv geometry, Ho * Wo entries ho << 20 | wo << 9 | mask9, bit u * 3 + v of
@@ -208,7 +224,10 @@ int y3_border_tile_map(int T, int Tb, int gm, int tilesN, int32_t *out);
  * low latency is on.  An ineligible conv or S > the conv's K tiles (K / 32) is refused here with Y3_ERR_INVALID and a message, not
  * by the forward.  y3_net_get_split_k: the value in force after planning (1 before).
  * y3_choose_split_k (pure, no device): 1 when tiles >= 2 * n_cus; else the smallest S with tiles * S >= 2 * n_cus, capped at
- * k_tiles / 4, at 16 and at 16 MiB of slabs (S * slab_bytes_per_slice); tiles = workgroups of the unsplit launch. */
+ * k_tiles / 4, at 16 and at 16 MiB of slabs (S * slab_bytes_per_slice); tiles = workgroups of the unsplit launch.
+ * On a planned net the switch and the request act at once, here and in the _bf16 / _f16 / _i8 calls below: the decision of the plan in
+ * force is made again from the same plan-time quantities and the workspace grows if it must.  Switches and requests of every mode
+ * survive y3_net_plan, also a plan in another mode, where they rest. */
 y3_status y3_net_set_low_latency(y3_net *net, int on);
 y3_status y3_net_set_split_k(y3_net *net, int conv_slot, int S);
 int y3_net_get_split_k(const y3_net *net, int conv_slot);
@@ -293,7 +312,9 @@ y3_status y3_net_keep_activations(y3_net *net, int keep);
  * kernels).  bf16 plans: the fused kernel forms conv0's products on the bf16 matrix cores from operands split x = hi + lo
  * (hi*hi + hi*lo + lo*hi, fp32 accumulation: ~2^-16 relative error per product, NOT fp32 arithmetic) and rounds the result to
  * bf16 where the pipeline stores it; against the one-launch-per-conv form a fraction of a percent of conv0's bf16 values round
- * the other way (bounded by tests/test_gpu_parity.py::test_fused_stem_bf16_matches_oracle_and_the_two_launch_form). */
+ * the other way (bounded by tests/test_gpu_parity.py::test_fused_stem_bf16_matches_oracle_and_the_two_launch_form).
+ * Acts at once on a planned net of a mode it acts on (the split decision is made again: a conv inside the fused stem is not split);
+ * "without keep_activations" is what the plan in force was made with. */
 y3_status y3_net_set_stem_fusion(y3_net *net, int on);
 /* The same switch for Y3_DTYPE_F16 plans, and for them only: 0 (default: one launch per conv, as an fp16 plan always ran), 1, 2 with the
  * meanings above; it does not act on a plan of any other mode, as y3_net_set_stem_fusion does not act on an fp16 plan.  The graph decides
@@ -305,7 +326,7 @@ y3_status y3_net_set_stem_fusion(y3_net *net, int on);
  * the accuracy does not depend on the weights' magnitude and no operand that matters is subnormal (nothing relies on what the matrix
  * pipe does with one).  Against the one-launch-per-conv fp16 plan a fraction of a percent of conv0's fp16 values round the other way
  * (bounded by tests/test_f16_stem_gpu.py).  Precondition: pixel values finite and of magnitude at most 65504 -- a larger one makes hi
- * infinite and the result NaN, where the unfused fp16 plan only overflows at its outputs. */
+ * infinite and the result NaN, where the unfused fp16 plan only overflows at its outputs.  Acts at once on a planned fp16 or int8 net. */
 y3_status y3_net_set_stem_fusion_f16(y3_net *net, int on);
 /* The fused stem of YOLOv3-tiny (csrc/conv_tiny_stem.hip), a switch of its own: 0 (default) one launch per op; 1: when the program starts
  * with conv0 (the 3x3/1 first layer, 3 -> 16 stored as 32) -> Y3_AUX_MAXPOOL2X2_S2 -> conv1 (3x3/1, 16 stored as 32 -> 32, single source,
@@ -313,7 +334,8 @@ y3_status y3_net_set_stem_fusion_f16(y3_net *net, int on);
  * are no early chunks, a Y3_DTYPE_F32, Y3_DTYPE_BF16 or Y3_DTYPE_F16 plan runs the four as ONE launch at the real widths 16 and K = 144:
  * conv0's tensor, pool 0's and conv1's never reach memory, and the 32 -> 32 conv, for which the 16-bit modes have no tile, never asks for
  * one -- so such a net plans in the 16-bit modes, which refuse it with the switch off.  Where the rule does not hold the switch is ignored.
- * Read by y3_net_plan: set it before planning.  y3_net_set_stem_fusion / _f16 do not act on it, and it does not act on them; anything but
+ * Read by y3_net_plan: set it before planning; on a planned net it waits for the next plan (the arena of the plan in force has, or has
+ * not, the three tensors).  y3_net_set_stem_fusion / _f16 do not act on it, and it does not act on them; anything but
  * 0 or 1 is Y3_ERR_INVALID.  Arithmetic: conv0 in fp32 from fp32 weights in every mode, in the stand-alone first-layer launch's order
  * (acc * scale + shift, leaky, one rounding to the plan's format); conv1 on v_mfma_f32_32x32x2_f32 (fp32 plans) or v_mfma_f32_32x32x16_bf16
  * / _f16 from 16-bit weights and the 16-bit pooled patch, fp32 accumulation, one rounding before pool 1; both pools compare values and keep
@@ -346,8 +368,12 @@ y3_status y3_net_measure_sclk_all(y3_net *net, const float *images_dev, int batc
 /* Before y3_net_plan: run the first n_convs convs chunk_images images at a time, then the rest of the network on the
  * whole batch.  The first layers' activations are the largest tensors of the network (1.4 GB for 64 images at 416x416);
  * in chunks they are still in the Infinity Cache when the next conv reads them.  Results are unchanged (images are
- * independent).  0, 0 switches it off. */
+ * independent).  0, 0 switches it off.  On a planned net it waits for the next plan: the plan keeps the segment and the chunk size it
+ * was made with (the chunked tensors have blocks of their own), and a forward steps through a chunked segment by that size, at least 1. */
 y3_status y3_net_set_early_chunk(y3_net *net, int n_convs, int chunk_images);
+/* How many leading ops the plan in force runs in chunks (0: none, or no plan) and, through *chunk_images unless null, of how many
+ * images: what the plan was made with, whatever the setter was called with since. */
+int y3_net_get_early_chunk(const y3_net *net, int *chunk_images);
 
 /* Allocate the activation arena for batches up to `max_batch` of image_size x image_size inputs
  * and select the conv arithmetic type (Y3_DTYPE_*).  May be called again to re-plan.
@@ -382,8 +408,29 @@ y3_status y3_net_plan(y3_net *net, int max_batch, int image_size, int dtype);
  * images_dev is [B,height,width,3], head grid s is [B, height/div_s, width/div_s, 3*(5+nc)], N = 3 * sum gh_s * gw_s.  The
  * decode inside y3_net_forward_decode / y3_net_detect is y3_yolo_decode_scores_hw below (per-axis normalisation); anchors are
  * normalised (w, h): the caller divides w by the canvas width and h by the canvas height.  The fused stem (y3_net_set_stem_fusion)
- * and the fused head decode serve rectangular plans like square ones.  No tile was tuned for a rectangular plan. */
+ * and the fused head decode serve rectangular plans like square ones.  No tile was tuned for a rectangular plan.
+ *
+ * A refused or failed call on a planned net leaves one of two states, never a third:
+ *   (a) the old plan intact -- nothing was touched, the next forward has the bits of the one before;
+ *   (b) no plan -- the old one is freed, y3_net_get_plan answers 0 and every call that needs a plan says "call y3_net_plan first".
+ *     refusal                                                                      status          leaves
+ *     bad argument, unknown dtype                                                  Y3_ERR_INVALID  (a)
+ *     a max-pool net in Y3_DTYPE_F32X3 / _F32X2 / _I8                              Y3_ERR_INVALID  (a)
+ *     a side not divisible by a tensor's div                                       Y3_ERR_INVALID  (a)
+ *     Y3_DTYPE_F32X2 with a BN-scaled weight outside the fp16 range                Y3_ERR_INVALID  (a)
+ *     Y3_DTYPE_I8 with no qualifying conv, or unequal scales at a concat           Y3_ERR_INVALID  (b)
+ *     Y3_DTYPE_I8 without a scale it needs                                         Y3_ERR_STATE    (b)
+ *     a conv without a tile in the mode                                            Y3_ERR_INVALID  (b)
+ *     a tensor of 4 GiB or more (refused before anything is allocated)             Y3_ERR_INVALID  (b)
+ *     out of memory (arena, int8 copies, detect scratch, split-K workspace)        Y3_ERR_OOM      (b)
+ *     any other failure once the old plan is freed (a HIP error, an exception)     its own         (b)
+ * y3_net_get_plan: 1 and the planned max_batch, height, width and dtype (null pointers are skipped) of a planned net; 0 and 0, 0, 0,
+ * Y3_DTYPE_F32 without a plan.  A caller that mirrors the plan (Net.max_batch / canvas) asks it after a failed call.
+ * A plan is a set of device addresses.  A hipGraph captured from a forward holds the addresses of the plan it was captured on: after
+ * another y3_net_plan (or a refusal of kind (b)) those are freed, nothing in the graph or in the library can detect that, and
+ * replaying it is undefined.  Capture again after every plan. */
 y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int dtype);
+int y3_net_get_plan(const y3_net *net, int *max_batch, int *height, int *width, int *dtype);
 
 /* images_dev [B,S,S,3] fp32 -> grids_dev[3], each [B,g,g,3*(5+nc)] fp32 (== [B,g,g,3,5+nc]).
  * Replaces model(inputs) (reference: inference.py:109). */
@@ -395,7 +442,9 @@ y3_status y3_net_forward(y3_net *net, const float *images_dev, int batch, float 
  * batch up to max_batch reads image i at i * image bytes (images beyond that forward's batch hold what earlier forwards left); after
  * a forward on several lanes the images lie in the lanes' regions (y3_lane_offset): where those follow one another without a gap the
  * read is the one-lane read; otherwise the images are gathered from the regions, lane by lane, and a batch other than that forward's is
- * refused with Y3_ERR_STATE -- its images are not where a contiguous read would look.
+ * refused with Y3_ERR_STATE -- its images are not where a contiguous read would look.  Right after y3_net_plan, before any forward on
+ * the new plan, a read (not the size query) is refused with Y3_ERR_STATE as well: the new arena holds nothing of the net's, and the
+ * previous plan's tensors are gone with it.
  * y3_net_read_tensor_i8 below follows the same rules for an int8 tensor of the arena. */
 y3_status y3_net_read_tensor(y3_net *net, int tensor_id, int batch, float *dst_dev, size_t *n_elems, void *stream);
 
@@ -426,7 +475,8 @@ y3_status y3_net_read_tensor(y3_net *net, int tensor_id, int batch, float *dst_d
  * Not in this version: a weight-resident tile, BK = 32 tiles (so no int8 for Cin = 32 / 64), split forms of the 16x16x64 and 16-wave
  * tiles, and the int8 copy fused into the producing epilogue.
  *
- * y3_net_set_act_scales: n_tensors must be the net's tensor count; entries <= 0 mean unset.  Read by the next y3_net_plan.
+ * y3_net_set_act_scales: n_tensors must be the net's tensor count; entries <= 0 mean unset.  Read by the next y3_net_plan: on a planned
+ * int8 net it waits for it (the plan in force keeps the scales it took, also for weights loaded later).
  * y3_net_get_act_scale: the scale set for a tensor, 0 when unset.  y3_net_i8_first_conv: c* of a net planned in Y3_DTYPE_I8, else -1.
  * y3_net_read_tensor_i8: the raw bytes of an int8 tensor of the last forward (a tensor behind the cut, or the int8 copy of one that
  * crosses it); y3_net_read_tensor on an int8 tensor returns (float)q * s. */

@@ -207,8 +207,15 @@ def test_plan_refuses_a_tensor_at_the_guard(rt):
         net.plan(case.batch + 1, case.canvas)
     assert net.flops_per_image() == 0.0
     x = torch.zeros((1, *case.canvas, 64), device="cuda")
-    with pytest.raises(rt.Y3Error, match="call y3_net_plan first"):
+    # the library has no plan and says so; Net knows it as well (include/y3.h, the table at y3_net_plan_hw: outcome (b)) ...
+    import ctypes
+    grids = (ctypes.c_void_p * 3)()
+    assert net.lib.y3_net_forward(net._h, x.data_ptr(), 1, grids, None) == -4 and b"call y3_net_plan first" in net.lib.y3_last_error()
+    assert net.lib.y3_net_get_plan(net._h, None, None, None, None) == 0 and (net.max_batch, net.canvas) == (0, (0, 0))
+    # ... so its forward plans by itself and gets as far as the weights this net never had
+    with pytest.raises(rt.Y3Error, match="has no weights"):
         net.forward(x)
+    assert (net.max_batch, net.canvas) == (1, tuple(case.canvas))
     net.plan(2, case.canvas)                               # the net itself is unharmed
     assert net.flops_per_image() > 0
 

@@ -55,7 +55,7 @@ def main():
         net.set_early_chunk(n_convs, chunk)
         net.plan(a.batch, a.image_size, dt)
         measure(f"early {n_convs} convs x {chunk} img")
-    net.set_early_chunk(0, 0)
+    net.set_early_chunk(0, 0)      # waits for the next plan (include/y3.h): every run below plans first
     for t in [int(v) for v in a.force.split(",") if v]:
         net.plan(a.batch, a.image_size, dt)     # resets to the table
         for slot, o in enumerate(net.conv_ops):

@@ -154,6 +154,8 @@ SYMBOLS = {
     "y3_net_measure_sclk_all": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _fp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),
     "y3_net_plan": (_i, [_vp, _i, _i, _i]),
     "y3_net_plan_hw": (_i, [_vp, _i, _i, _i, _i]),
+    "y3_net_get_plan": (_i, [_vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), C.POINTER(_i)]),
+    "y3_net_get_early_chunk": (_i, [_vp, C.POINTER(_i)]),
     "y3_net_forward": (_i, [_vp, _vp, _i, C.POINTER(_vp), _vp]),
     "y3_net_read_tensor": (_i, [_vp, _i, _i, _vp, C.POINTER(_sz), _vp]),
     "y3_net_set_act_scales": (_i, [_vp, _fp, _i]),

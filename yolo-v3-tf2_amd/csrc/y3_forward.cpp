@@ -356,8 +356,9 @@ static y3_status run(const y3_net *net, const Forward &f)
     const int k_early = f.ms_out ? 0 : net->early_ops;
     auto run_lane = [&](int b0, int nb, hipStream_t st, int lane) -> y3_status {
         if (k_early > 0) {
-            for (int c0 = 0; c0 < nb; c0 += net->early_chunk) {
-                const int cn = nb - c0 < net->early_chunk ? nb - c0 : net->early_chunk;
+            const int step = net->early_step;   // the plan's copy, >= 1 with early_ops > 0 (y3_net_plan_hw): y3_net_set_early_chunk on a planned net waits for the next plan
+            for (int c0 = 0; c0 < nb; c0 += step) {
+                const int cn = nb - c0 < step ? nb - c0 : step;
                 y3_status r = Slice{net, f, b0 + c0, cn, lane, st, lanes}.run(0, k_early);
                 if (r != Y3_OK) return r;
             }
@@ -588,6 +589,7 @@ try {
         return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d lies inside the fused tiny stem launch and is never stored (y3_net_set_tiny_stem_fusion(net, 0) and "
                                   "a new plan keep it)", t);
     if (!net->tdev[t]) return fail(Y3_ERR_STATE, "y3_net_read_tensor: tensor %d is not held in the arena", t);
+    if (net->last_batch < 1) return fail(Y3_ERR_STATE, "y3_net_read_tensor: no forward was enqueued on this plan; its arena holds nothing to read");
     int lanes = 1;
     if (y3_status st = read_lanes(net, t, batch, "y3_net_read_tensor", &lanes); st != Y3_OK) return st;
     Y3_ENTER_DEVICE(net);   // the conversion kernels / the copy below read the net's arena: enqueue them on its device
@@ -619,6 +621,7 @@ try {
     // the int8 copy of a tensor that crosses the cut (image i at i * image bytes whatever the lanes), else an int8 tensor of the arena
     const void *src = net->dtype != Y3_DTYPE_I8 ? nullptr : net->tq8[t] ? net->tq8[t] : (net->telem[t] == 1 && net->out_slot[t] < 0) ? net->tdev[t] : nullptr;
     if (!src) return fail(Y3_ERR_STATE, "y3_net_read_tensor_i8: tensor %d is not held as int8 in this plan", t);
+    if (net->last_batch < 1) return fail(Y3_ERR_STATE, "y3_net_read_tensor_i8: no forward was enqueued on this plan; its arena holds nothing to read");
     int lanes = 1;
     if (!net->tq8[t])
         if (y3_status st = read_lanes(net, t, batch, "y3_net_read_tensor_i8", &lanes); st != Y3_OK) return st;
@@ -642,7 +645,7 @@ bool heads_can_decode(const y3_net *net)
 {
     static const bool off = [] { const char *e = getenv("Y3_FUSE_DECODE"); return e && e[0] == '0'; }();
     if (off || net->nclasses <= 0 || (net->dtype != Y3_DTYPE_F32 && net->dtype != Y3_DTYPE_BF16 && net->dtype != Y3_DTYPE_F16 && net->dtype != Y3_DTYPE_I8)) return false;
-    if (net->keep_all || net->early_ops > 0 || 3 * (5 + net->nclasses) > 256) return false;
+    if (net->kept || net->early_ops > 0 || 3 * (5 + net->nclasses) > 256) return false;
     for (int k = 0; k < net->n_heads; ++k) {
         const int t = net->outputs[k];
         if (net->staged[t]) return false;

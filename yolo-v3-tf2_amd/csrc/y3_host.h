@@ -122,11 +122,13 @@ struct y3_net {
     int nclasses = 0;
     // plan
     int max_batch = 0, height = 0, width = 0, dtype = Y3_DTYPE_F32;   // the planned canvas: height x width (0: no plan)
-    int keep_all = 0;              // 1: no buffer reuse, every intermediate stays readable after a forward
+    int keep_all = 0;              // y3_net_keep_activations: 1: no buffer reuse, every intermediate stays readable after a forward; read by y3_net_plan
+    int kept = 0;                  // (at plan time) keep_all as the plan found it: what the arena is, and what every decision of the planned net follows
     int lanes = 1;                 // sub-batches run concurrently on forked streams (y3_net_set_lanes)
     int early_convs = 0;           // y3_net_set_early_chunk: the first early_convs convs run early_chunk images at a time
     int early_chunk = 0;
     int early_ops = 0;             // (at plan time) number of leading ops that form the chunked segment
+    int early_step = 0;            // (at plan time) images per chunk of that segment: early_chunk as the plan found it, >= 1 whenever early_ops > 0
     std::vector<char> dense;       // tensor written by the chunked segment: own block, image i at i * image_bytes
     // (non-fp32 modes) output tensors that another op reads, or that a residual / first-layer conv writes: produced in
     // the arena in the mode's own format and converted into the caller's fp32 buffer at the end of the forward
@@ -283,6 +285,8 @@ y3_status resolve_i8(y3_net *net);
 // ... and the epilogue scales of int8 conv `slot` on the device, once its weights are loaded (y3_net_plan; y3_net_set_conv_weights on a planned net)
 y3_status upload_i8_scales(y3_net *net, int slot);
 void free_plan(y3_net *net);
+// free_plan and "no plan" in every field an entry point asks: a plan refused or failed after the old one was freed leaves this
+void drop_plan(y3_net *net);
 
 // y3_net_detect scratch for `batch` images: grid sizes {gh, gw} of the net's heads, boxes per image, byte offsets of the parts and their total
 struct DetectLayout {

@@ -360,7 +360,7 @@ int choose_tile(const ConvSlot &c, long long M, long long, bool)
 // else reads conv0's output, and the plan's mode has a fused stem with every intermediate reusable: the pair runs as csrc/conv_stem.hip.
 bool y3::stem_applicable(const y3_net *net)
 {
-    if (!family_of(net).launch_stem || net->keep_all || net->height % 32 || net->width % 32 || net->early_ops > 0)
+    if (!family_of(net).launch_stem || net->kept || net->height % 32 || net->width % 32 || net->early_ops > 0)
         return false;
     if (net->ops.size() < 2 || net->ops[0].kind != 0 || net->ops[1].kind != 0) return false;
     const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[1].index];
@@ -1159,7 +1159,7 @@ int y3_net_get_border_skip(const y3_net *net, int slot, int batch)
     while (lanes > 1 && batch / lanes < 1) --lanes;
     for (int l = 0; l < lanes; ++l) {   // the sub-batches of y3_net_forward; a conv of the chunked leading segment: its first chunk
         int nb = (int)((long long)batch * (l + 1) / lanes) - (int)((long long)batch * l / lanes);
-        if (oi < net->early_ops && nb > net->early_chunk) nb = net->early_chunk;
+        if (oi < net->early_ops && nb > net->early_step) nb = net->early_step;
         if (nb <= 0) continue;
         y3::ConvArgs a{};
         a.B = nb;

@@ -27,6 +27,20 @@ void y3::free_plan(y3_net *n)
     n->tq8.assign(n->tensors.size(), nullptr);   // the int8 copies were blocks
 }
 
+void y3::drop_plan(y3_net *n)
+{
+    free_plan(n);
+    n->height = n->width = n->max_batch = 0;
+    n->dtype = Y3_DTYPE_F32;
+    n->early_ops = n->early_step = 0;
+    n->kept = 0;
+    n->stem_fused = n->stem_conv2 = n->tiny_stem_fused = false;
+    n->i8_first_conv = -1;
+    n->last_batch = n->last_lanes = 0;
+    n->multi_label_batch = 0;
+    for (ConvSlot &c : n->convs) c.split_k = 1;
+}
+
 // ---- border skip (fp32 3x3 convs) ---------------------------------------------------------------------------
 // mask9 of output position (ho, wo): bit u * 3 + v = tap (u, v) reads input pixel (ho * stride - pad + u, wo * stride - pad + v) inside
 // the H x W image -- the formula of the kernel's okmask (conv_f32.hip).  The positions go out stably sorted by mask class: by the number
@@ -112,7 +126,7 @@ static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const
     }
     std::sort(order.begin(), order.end(), [&](int a, int b) { return first[a] < first[b]; });
     for (int t : order) {
-        const int until = (net->keep_all || net->dense[t]) ? (int)net->ops.size() + 1 : last[t];
+        const int until = (net->kept || net->dense[t]) ? (int)net->ops.size() + 1 : last[t];
         int pick = -1;
         for (int k = 0; k < (int)pool.size() && !net->dense[t]; ++k)
             if (pool[k].free_at < first[t] && pool[k].bytes >= net->tbytes[t] &&
@@ -122,7 +136,7 @@ static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const
             void *p = nullptr;
             hipError_t e = hipMalloc(&p, net->tbytes[t] + 4096);
             if (e != hipSuccess) {
-                y3::free_plan(net);
+                y3::drop_plan(net);
                 return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) failed: %s", net->tbytes[t], hipGetErrorString(e));
             }
             net->blocks.push_back(p);
@@ -236,8 +250,9 @@ y3::DetectLayout y3::detect_layout(const y3_net *net, int batch)
 
 extern "C" {
 
-y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int dtype)
-try {
+// y3_net_plan_hw's body.  freed: set once the old plan is gone -- from there on every failure, a thrown one included, ends in drop_plan
+static y3_status plan_hw(y3_net *net, int max_batch, int height, int width, int dtype, bool &freed)
+{
     if (!net || max_batch <= 0 || height <= 0 || width <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
     if (!y3::conv_family(dtype)) return fail(Y3_ERR_INVALID, "y3_net_plan: unknown dtype %d", dtype);
     if (net->has_pool && (dtype == Y3_DTYPE_F32X3 || dtype == Y3_DTYPE_F32X2 || dtype == Y3_DTYPE_I8))
@@ -261,6 +276,7 @@ try {
         net->n_cus = cus > 0 ? cus : 256;
     }
     y3::free_plan(net);
+    freed = true;
     net->max_batch = max_batch;
     net->height = height;
     net->width = width;
@@ -295,8 +311,12 @@ try {
     }
     // chunked leading segment: every op before the (early_convs)-th conv; tensors it writes get blocks of their own,
     // laid out densely by image, because they are rewritten chunk after chunk while earlier chunks' results are still live
+    // The plan keeps its own copies (kept, early_step) of the two setters it reads: y3_net_keep_activations and y3_net_set_early_chunk on a
+    // planned net wait for the next plan, and nothing the planned net decides or enqueues reads their live fields
+    net->kept = net->keep_all;
     net->early_ops = 0;
-    if (net->early_convs > 0 && net->early_chunk > 0) {
+    net->early_step = net->early_chunk;
+    if (net->early_convs > 0 && net->early_step > 0) {
         int seen = 0;
         for (int i = 0; i < (int)net->ops.size(); ++i) {
             if (net->ops[i].kind == 0 && seen++ == net->early_convs) break;
@@ -304,12 +324,11 @@ try {
         }
         if (net->early_ops >= (int)net->ops.size()) net->early_ops = 0;
     }
+    if (net->early_ops == 0) net->early_step = 0;   // early_ops > 0 only under the condition above: the forward's chunk loop steps by >= 1
     net->dense.assign(nt, 0);
     for (int t = 0; t < nt; ++t) net->dense[t] = (first[t] >= 0 && first[t] < net->early_ops) ? 1 : 0;
     if (y3_status st = y3::resolve_i8(net); st != Y3_OK) {   // every plan: the element size per tensor; int8 plans: the cut and the scales
-        net->height = net->width = net->max_batch = 0;      // no plan
-        net->dtype = Y3_DTYPE_F32;
-        net->tiny_stem_fused = false;
+        y3::drop_plan(net);
         return st;
     }
     y3::resolve_tiny_stem(net);   // before the tile check: the 32 -> 32 conv inside the fused tiny stem asks no tile table
@@ -321,9 +340,7 @@ try {
         const int mode = y3::dtype_of_conv(net, slot), cut = net->i8_first_conv;
         char where[96] = "";
         if (dtype == Y3_DTYPE_I8 && mode != Y3_DTYPE_I8) snprintf(where, sizeof(where), " (it lies before the int8 cut, conv %d, and runs in fp16)", cut);
-        net->height = net->width = net->max_batch = 0;      // no plan
-        net->dtype = Y3_DTYPE_F32;
-        net->tiny_stem_fused = false;
+        y3::drop_plan(net);
         return fail(Y3_ERR_INVALID, "y3_net_plan: conv %d (Cin %d, c0 %d, Cout %d) has no %s tile%s: no built tile of that mode divides these "
                                     "widths (with Cin or c0 an odd multiple of 32 the 16-bit modes need Cout padded to a multiple of 64); "
                                     "Y3_DTYPE_F32, Y3_DTYPE_F32X3 and Y3_DTYPE_F32X2 run it",
@@ -336,9 +353,7 @@ try {
         const bool f32 = net->out_slot[t] >= 0 || (t == net->input_tensor && net->tensors[t].channels == 3);
         const size_t addressed = f32 ? net->tbytes[t] / net->telem[t] * 4 : net->tbytes[t];
         if (addressed >= 0xFFFFFFF0ull && first[t] >= 0 && !net->tiny_inner[t]) {
-            net->height = net->width = net->max_batch = 0;      // no plan
-            net->dtype = Y3_DTYPE_F32;
-            net->tiny_stem_fused = false;
+            y3::drop_plan(net);
             return fail(Y3_ERR_INVALID, "y3_net_plan: tensor %d is %zu bytes; 32-bit buffer offsets need < 4 GiB, lower max_batch", t, addressed);
         }
     }
@@ -349,7 +364,7 @@ try {
         const size_t bytes = (size_t)max_batch * rows(net, t) * cols(net, t) * net->tensors[t].channels;
         void *p = nullptr;
         if (hipError_t e = hipMalloc(&p, bytes + 4096); e != hipSuccess) {
-            y3::free_plan(net);
+            y3::drop_plan(net);
             return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) for the int8 copy of tensor %d failed: %s", bytes, t, hipGetErrorString(e));
         }
         net->blocks.push_back(p);
@@ -358,7 +373,7 @@ try {
     for (int i = 0; i < (int)net->convs.size(); ++i)
         if (y3::conv_is_i8(net, i))
             if (y3_status st = y3::upload_i8_scales(net, i); st != Y3_OK) {
-                y3::free_plan(net);
+                y3::drop_plan(net);
                 return st;
             }
     if (y3_status st = ensure_lanes(net); st != Y3_OK) return st;
@@ -375,21 +390,35 @@ try {
         const size_t bytes = y3::detect_layout(net, max_batch).total;
         hipError_t e = hipMalloc(&net->det_buf, bytes);
         if (e != hipSuccess) {
-            y3::free_plan(net);
+            y3::drop_plan(net);
             return fail(Y3_ERR_OOM, "y3_net_plan: hipMalloc(%zu) for the detect scratch failed: %s", bytes, hipGetErrorString(e));
         }
         net->det_bytes = bytes;
         net->multi_label_batch = 0;   // no multi-label detect has written totals into this scratch
     }
     if (y3_status st = y3::resolve_splits(net); st != Y3_OK) {
-        y3::free_plan(net);
+        y3::drop_plan(net);
         return st;
     }
     if (y3_status st = y3::resolve_border(net); st != Y3_OK) {
-        y3::free_plan(net);
+        y3::drop_plan(net);
         return st;
     }
     return Y3_OK;
+}
+
+y3_status y3_net_plan_hw(y3_net *net, int max_batch, int height, int width, int dtype)
+try {
+    bool freed = false;
+    y3_status st;
+    try {
+        st = plan_hw(net, max_batch, height, width, dtype, freed);
+    } catch (...) {
+        st = y3::on_exception("y3_net_plan_hw");
+    }
+    // (a) or (b), never a third state (include/y3.h): a failure behind free_plan -- a refusal, a HIP error, an exception -- leaves no plan
+    if (st != Y3_OK && freed) y3::drop_plan(net);
+    return st;
 }
 Y3_CATCH("y3_net_plan_hw")
 
@@ -415,6 +444,23 @@ try {
     return y3_net_plan_hw(net, max_batch, image_size, image_size, dtype);
 }
 Y3_CATCH("y3_net_plan")
+
+int y3_net_get_plan(const y3_net *net, int *max_batch, int *height, int *width, int *dtype)
+{
+    const bool planned = net && net->height > 0;
+    if (max_batch) *max_batch = planned ? net->max_batch : 0;
+    if (height) *height = planned ? net->height : 0;
+    if (width) *width = planned ? net->width : 0;
+    if (dtype) *dtype = planned ? net->dtype : (int)Y3_DTYPE_F32;
+    return planned ? 1 : 0;
+}
+
+int y3_net_get_early_chunk(const y3_net *net, int *chunk_images)
+{
+    const bool planned = net && net->height > 0;
+    if (chunk_images) *chunk_images = planned ? net->early_step : 0;
+    return planned ? net->early_ops : 0;
+}
 
 double y3_net_flops_per_image(const y3_net *net)
 {

@@ -58,7 +58,8 @@ class _TinyStemSwitch:
         raise Y3Error(f"tiny stem fusion must be None, a bool, 0 or 1 (got {on!r})")
 
     def set_tiny_stem_fusion(self, on=True):
-        """conv0 + pool 0 + conv1 + pool 1 of YOLOv3-tiny as one kernel: off by default; None means off.  Before plan().  Acts on fp32, bf16
+        """conv0 + pool 0 + conv1 + pool 1 of YOLOv3-tiny as one kernel: off by default; None means off.  Before plan(): on a planned net it
+        waits for the next plan.  Acts on fp32, bf16
         and fp16 plans of a program that starts with that stem and is ignored on any other; with it tiny plans in bf16 and fp16, which
         refuse it otherwise.  keep_activations() does not switch it off: the three tensors inside the launch are not stored, and
         read_tensor on one of them raises.  set_stem_fusion / set_stem_fusion_f16 do not act on it, nor it on them."""
@@ -153,22 +154,29 @@ class Net(_TinyStemSwitch):
 
     # -- planning / execution ---------------------------------------------------------------------
     def keep_activations(self, keep=True):
+        """No buffer reuse in the plans made from now on, so that read_tensor reads any stored tensor after a forward.  On a planned net
+        it waits for the next plan() (include/y3.h, "Setters on a planned net")."""
         check(self.lib.y3_net_keep_activations(self._h, int(keep)), "y3_net_keep_activations")
 
     def set_lanes(self, lanes: int):
+        """Concurrent sub-batches of a forward, 1..4; acts at once on a planned net.  plan() sets it from the plan's tuning table (1
+        without one): call it after plan()."""
         check(self.lib.y3_net_set_lanes(self._h, int(lanes)), "y3_net_set_lanes")
         self.lanes = int(lanes)
 
     def set_xcd_mode(self, mode: int):
-        """fp32 conv tile placement on the 8 XCDs: 1 = XCD-blocked order chosen per conv (default), 0 = contiguous runs."""
+        """fp32 conv tile placement on the 8 XCDs: 1 = XCD-blocked order chosen per conv (default), 0 = contiguous runs.  Read by every
+        forward: acts at once on a planned net and survives plan()."""
         check(self.lib.y3_net_set_xcd_mode(self._h, int(mode)), "y3_net_set_xcd_mode")
 
     def set_k_chunk(self, channels: int):
-        """K order of the fp32 3x3 convs: channels per chunk (multiple of 32) walked chunk-major, 0 tap-major, -1 default."""
+        """K order of the fp32 3x3 convs: channels per chunk (multiple of 32) walked chunk-major, 0 tap-major, -1 default.  Read by every forward:
+        acts at once on a planned net and survives plan()."""
         check(self.lib.y3_net_set_k_chunk(self._h, int(channels)), "y3_net_set_k_chunk")
 
     def set_border_skip(self, mode: int):
-        """fp32 3x3 convs on batch-minor rows that skip their padding taps (bit-identical): -1 the library's rule, 0 off, 1 on wherever legal."""
+        """fp32 3x3 convs on batch-minor rows that skip their padding taps (bit-identical): -1 the library's rule, 0 off, 1 on wherever legal.
+        Read by every forward: acts at once on a planned net and survives plan()."""
         check(self.lib.y3_net_set_border_skip(self._h, int(mode)), "y3_net_set_border_skip")
 
     def border_skip(self, slot: int, batch: int) -> int:
@@ -265,7 +273,8 @@ class Net(_TinyStemSwitch):
         """The conv arithmetic of the plans this net makes for itself from now on (forward / detect re-plan when the batch
         shape changes; plan() without a dtype): None or "f32", "bf16", "f16", "f32x3", "f32x2", "i8" (needs the activation scales:
         calibrate_i8 / load_calibration / set_act_scales), or a _lib.Y3_DTYPE_* value.
-        A net already planned in another dtype is planned again, same batch and canvas."""
+        A net already planned in another dtype is planned again, same batch and canvas.  When that plan is refused the call raises and
+        the dtype stays what it was: the old plan is intact, or gone (max_batch 0) and the next forward plans in the old dtype (plan())."""
         dtype = self._dtype_arg(dtype)
         if self.max_batch and dtype != self.dtype:
             self.plan(self.max_batch, self.image_size, dtype)
@@ -305,7 +314,9 @@ class Net(_TinyStemSwitch):
     def set_low_latency(self, on=True):
         """Low-latency fp32 plan for one to eight images (y3_net_set_low_latency), before plan(): each eligible conv is cut
         along K into the number of slices y3_choose_split_k gives for the planned batch, summed in a fixed order by a second
-        launch.  Off by default; results differ from the default plan's in the last bits.  None means off."""
+        launch.  Off by default; results differ from the default plan's in the last bits.  None means off.  This switch and the _bf16 / _f16 /
+        _i8 ones, like the set_split_k* requests, act at once on a planned net of their mode and survive plan(), also a plan in another
+        mode, where they rest."""
         self._set_low_latency("", on)
 
     def set_split_k(self, slot: int, S: int):
@@ -373,22 +384,25 @@ class Net(_TinyStemSwitch):
 
     def set_stem_fusion(self, on):
         """conv0 + conv1 (+ the 1x1 conv that follows them) as one kernel (default on; applies when the program starts with
-        the Darknet-53 stem and the plan is fp32 or bf16 without keep_activations).  2: conv0 + conv1 only."""
+        the Darknet-53 stem and the plan is fp32 or bf16 without keep_activations).  2: conv0 + conv1 only.  Acts at once on a planned
+        fp32 or bf16 net; survives plan()."""
         check(self.lib.y3_net_set_stem_fusion(self._h, int(on)), "y3_net_set_stem_fusion")
 
     def set_stem_fusion_f16(self, on=True):
         """The same switch for fp16 plans, and for them only (y3_net_set_stem_fusion_f16): off by default; True / 1, 2 as
-        set_stem_fusion; None means off.  Pixel values must be finite and at most 65504 in magnitude."""
+        set_stem_fusion; None means off.  Pixel values must be finite and at most 65504 in magnitude.  Acts at once on a planned fp16 or
+        int8 net; survives plan()."""
         on = self._stem_fusion_arg(on)          # the argument check comes first: it needs no device net
         check(self.lib.y3_net_set_stem_fusion_f16(self._h, on), "y3_net_set_stem_fusion_f16")
 
     def set_early_chunk(self, n_convs: int, chunk_images: int):
         """Before plan(): the first n_convs convs run chunk_images images at a time (their activations then stay in the
-        Infinity Cache between producer and consumer); 0, 0 switches it off."""
+        Infinity Cache between producer and consumer); 0, 0 switches it off.  On a planned net it waits for the next plan(): the plan in
+        force keeps the segment and the chunk size it was made with."""
         check(self.lib.y3_net_set_early_chunk(self._h, int(n_convs), int(chunk_images)), "y3_net_set_early_chunk")
 
-    # A tile forced through these setters survives plan(): the tuning table only fills the convs left on automatic
-    # (tile -1 hands the conv back to the table / the library's heuristic).
+    # A tile forced through these setters acts at once on a planned net and survives plan(): the tuning table only fills the convs left
+    # on automatic (tile -1 hands the conv back to the library's heuristic at once, and to the table at the next plan()).
     def _set_tile(self, kind: str, slot: int, tile: int):     # kind: a suffix of _TILE_KIND
         check(getattr(self.lib, "y3_net_set_tile" + kind)(self._h, slot, tile), f"y3_net_set_tile{kind}")
 
@@ -418,15 +432,33 @@ class Net(_TinyStemSwitch):
         dtype: _lib.Y3_DTYPE_F32 (default, fp32 MFMA), _lib.Y3_DTYPE_F32X3 (fp32-accurate on the bf16 matrix cores:
         three bf16 planes per value), _lib.Y3_DTYPE_F32X2 (two fp16 planes per value, 2^-22 representation, |x| < 65504)
         _lib.Y3_DTYPE_BF16 (bf16 activations/weights, fp32 accumulate) or _lib.Y3_DTYPE_F16 (the same with IEEE fp16: 8 x closer to
-        fp32, values beyond 65504 become inf; the fused stem and split-K only through set_stem_fusion_f16 / set_low_latency_f16)."""
+        fp32, values beyond 65504 become inf; the fused stem and split-K only through set_stem_fusion_f16 / set_low_latency_f16).
+        A refused plan raises and leaves either the old plan intact, with these fields unchanged, or no plan at all: max_batch 0 and
+        canvas (0, 0), and the next forward / detect plans by itself (include/y3.h names which refusal leaves which).  Every set_*
+        survives a plan; lanes alone are set again by each plan, from its tuning table."""
         if dtype is None:
             dtype = self.dtype
         H, W = canvas_hw(image_size)
-        check(self.lib.y3_net_plan_hw(self._h, max_batch, H, W, dtype), "y3_net_plan")
+        try:
+            check(self.lib.y3_net_plan_hw(self._h, max_batch, H, W, dtype), "y3_net_plan")
+        except Y3Error:
+            self._forget_plan_if_gone()
+            raise
         self.max_batch, self.dtype, self.canvas = max_batch, dtype, (H, W)
         # the form grid_sizes() answers in -- g for an int plan, (gh, gw) for a pair plan -- is that of the last plan() a caller made
         self.image_size = int(image_size) if isinstance(image_size, (int, np.integer)) else (H, W)
         self._apply_tuning()
+
+    def _forget_plan_if_gone(self):
+        """After a refused plan(): the library either kept the old plan, and so do max_batch / canvas / image_size / dtype, or freed it
+        (include/y3.h, the table at y3_net_plan_hw; y3_net_get_plan tells) -- then max_batch = 0 and canvas = (0, 0) as before the first
+        plan, image_size keeps only its form (0 or (0, 0): _plan_for's rule), dtype stays what it was before the call, and the next
+        forward / detect plans by itself in that dtype."""
+        get = self.lib.y3_net_get_plan
+        if getattr(get, "missing", False) or get(self._h, None, None, None, None):
+            return
+        self.max_batch, self.canvas = 0, (0, 0)
+        self.image_size = (0, 0) if isinstance(self.image_size, tuple) else 0
 
     @staticmethod
     def conv_signature(o: ConvOp, image_size) -> str:
@@ -462,7 +494,7 @@ class Net(_TinyStemSwitch):
 
     def grid_sizes(self, image_size=None):
         """Per head: g for an int image size, (gh, gw) for an (H, W) pair (default: what the net was planned with)."""
-        return self.program.grid_sizes(image_size or self.image_size)
+        return self.program.grid_sizes(image_size or (self.image_size if self.max_batch else 0))
 
     def _grid_hw(self):
         return [(self.canvas[0] // self.program.tensors[o].div, self.canvas[1] // self.program.tensors[o].div)
@@ -564,7 +596,8 @@ class Net(_TinyStemSwitch):
         return self._read_tensor("_i8", torch.int8, tensor_id, batch)
 
     def set_act_scales(self, scales):
-        """One fp32 scale per tensor of the program (entries <= 0 or None: unset), read by the next plan() in "i8"."""
+        """One fp32 scale per tensor of the program (entries <= 0 or None: unset), read by the next plan() in "i8": a planned int8 net
+        keeps the scales its plan took."""
         a = np.ascontiguousarray([0.0 if s is None else float(s) for s in scales], np.float32)
         check(self.lib.y3_net_set_act_scales(self._h, _fptr(a), int(a.size)), "y3_net_set_act_scales")
 

@@ -143,7 +143,8 @@ y3_status y3_net_set_conv_weights(y3_net *net, int conv_slot, const float *w, co
  *     y3_net_set_lanes, y3_net_set_tile / _bf16 / _x3 / _x2, y3_net_set_low_latency* and y3_net_set_split_k*, y3_net_set_stem_fusion /
  *     _f16, y3_net_set_k_chunk, y3_net_set_border_skip, y3_net_set_xcd_mode, y3_net_set_nms_mode, y3_net_set_multi_label.
  *   WAITS FOR THE NEXT PLAN -- the planned net keeps running, bit for bit, what it ran before the call; y3_net_plan reads the value:
- *     y3_net_set_tiny_stem_fusion, y3_net_set_early_chunk, y3_net_keep_activations, y3_net_set_act_scales (they decide the arena).
+ *     y3_net_set_tiny_stem_fusion, y3_net_set_pools_i8, y3_net_set_early_chunk, y3_net_keep_activations, y3_net_set_act_scales (they
+ *     decide the arena).
  *     The plan keeps its own copy of what it read; no decision of a planned net reads the live value.
  * Every setting survives y3_net_plan: a plan changes none of them.  y3_net_set_conv_weights on a planned net acts at once, in every
  * format, the int8 epilogue scales of the plan in force included.  (tests/test_lifecycle_gpu.py holds a long-lived net to this.)
@@ -479,7 +480,25 @@ y3_status y3_net_read_tensor(y3_net *net, int tensor_id, int batch, float *dst_d
  * int8 net it waits for it (the plan in force keeps the scales it took, also for weights loaded later).
  * y3_net_get_act_scale: the scale set for a tensor, 0 when unset.  y3_net_i8_first_conv: c* of a net planned in Y3_DTYPE_I8, else -1.
  * y3_net_read_tensor_i8: the raw bytes of an int8 tensor of the last forward (a tensor behind the cut, or the int8 copy of one that
- * crosses it); y3_net_read_tensor on an int8 tensor returns (float)q * s. */
+ * crosses it); y3_net_read_tensor on an int8 tensor returns (float)q * s.
+ *
+ * Stand-alone ops in int8 (YOLOv3-tiny), a switch of its own: y3_net_set_pools_i8(net, 1), off by default and read by the next
+ * y3_net_plan (a planned net keeps its plan).  Off: an int8 plan refuses a net that holds a max-pool, and runs no stand-alone op behind
+ * its cut.  On, in a Y3_DTYPE_I8 plan (it does nothing in any other): the cut is found as before, from the convs alone; a tensor is
+ * behind the cut when a conv at or after the cut or an int8 aux op writes it; walking the aux ops in op order, a max-pool (either
+ * stride), an up-sample or a concat whose every source is behind the cut runs in int8 -- the pool through y3_maxpool2x2's kernel on signed
+ * bytes, the other two as moves of bytes -- and its destination is an int8 tensor; an aux op none of whose sources is behind the cut runs as
+ * in an fp16 plan.  Such an op only selects or moves stored bytes, so its destination and all its sources must carry ONE scale: unequal
+ * scales are refused with Y3_ERR_INVALID naming the op, the tensors and the values, a missing one with Y3_ERR_STATE naming the tensor
+ * (the quantiser is monotone, so a pool of quantised values is the quantised pool, byte for byte).  Refused by name with Y3_ERR_INVALID,
+ * and with the plan in force left as it is: a concat with one source behind the cut and one before it, a stand-alone add with a source
+ * behind the cut, an aux op behind the cut that reads a net output, an int8 aux op with a channel count that is no multiple of 16.  A
+ * tensor written before the cut by a conv or an aux op and read by an int8 conv gets its int8 copy as before (tiny: pool 3's output, tensor
+ * 8).  The part before the cut is an fp16 plan bit for bit: YOLOv3-tiny needs y3_net_set_tiny_stem_fusion as well (its 32 -> 32 conv has
+ * no fp16 tile), and the fused tiny stem then runs in its fp16 form.  y3_net_pools_i8: 1 when the plan in force runs at least one aux op in
+ * int8, else 0 (no plan, a null net). */
+y3_status y3_net_set_pools_i8(y3_net *net, int on);
+int y3_net_pools_i8(const y3_net *net);
 y3_status y3_net_set_act_scales(y3_net *net, const float *scales, int n_tensors);
 float y3_net_get_act_scale(const y3_net *net, int tensor_id);
 int y3_net_i8_first_conv(const y3_net *net);
@@ -587,7 +606,8 @@ y3_status y3_yolo_decode_scores_hw_n(const float *const *grids_dev, const int32_
 /* ------------------------------------------------------------------------------------------
  * MaxPooling2D(pool_size = 2, strides = stride, padding = 'same'), stride 1 or 2 (reference: core/parse_model.py:78-99), the pools of
  * YOLOv3-tiny.  src_dev [batch,H,W,C] -> dst_dev [batch,H/stride,W/stride,C], NHWC, elements of `dtype`: Y3_DTYPE_F32 (fp32),
- * Y3_DTYPE_BF16 or Y3_DTYPE_F16 (2 bytes); C * element size must be a multiple of 16 bytes, both pointers 16-byte aligned.
+ * Y3_DTYPE_BF16 or Y3_DTYPE_F16 (2 bytes), or Y3_DTYPE_I8 (signed bytes, all 256 values legal, each byte compared on its own);
+ * C * element size must be a multiple of 16 bytes, both pointers 16-byte aligned.
  *   stride 2 (H and W even): out[y, x] = max over in[2y .. 2y + 1, 2x .. 2x + 1]
  *   stride 1: 'same' pads one row below and one column to the right and padding never wins, so
  *             out[y, x] = max over in[y .. min(y + 1, H - 1), x .. min(x + 1, W - 1)]

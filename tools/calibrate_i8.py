@@ -2,7 +2,8 @@
 """Write the activation scales an int8 plan needs (dtype: i8 + i8_calibration: FILE in the inference / evaluation YAML) from a directory
 of images: every image is resized to the network size as inference does, the fp32 plan runs with its activations kept, and per tensor
 the largest |x| over all batches (or the given percentile of |x|, the largest over the batches) divided by 127 is the scale; the two
-sources of a concat conv take the larger of theirs (runtime.Net.calibrate_i8, quant.py).  Needs a GPU.
+sources of a concat conv take the larger of theirs, and in a pooled net (YOLOv3-tiny, Net.set_pools_i8) every tensor an aux op writes is
+measured too and every class of quant.scale_classes takes its largest scale (runtime.Net.calibrate_i8, quant.py).  Needs a GPU.
 
     python tools/calibrate_i8.py --images DIR --weights FILE.safetensors --out cal.json [--size 416] [--batch 8] [--percentile 100]
                                  [--model config/models/yolov3/model.yaml] [--classes 80]        (--weights synthetic: seeded random ones)"""
@@ -46,6 +47,7 @@ def main():
         raise SystemExit(f"no .png / .jpg images in {a.images}")
     net = runtime.Net(program)
     net.load_weights(w)
+    net.set_pools_i8(True)      # a pooled net (YOLOv3-tiny): also the scales of the tensors its aux ops write; a net without aux ops: no difference
     worst = [0.0] * len(program.tensors)
     for i in range(0, len(files), a.batch):
         chunk = files[i:i + a.batch]

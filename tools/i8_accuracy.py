@@ -9,6 +9,11 @@
 
     python tools/i8_accuracy.py                      # synthetic network, 2 x 96^2, input seed 1234: the figures of DESIGN.md section 7, "int8 plans"
     python tools/i8_accuracy.py --image datasets/coco2012/images/girl.png --size 416
+    python tools/i8_accuracy.py --model tiny         # YOLOv3-tiny (Net.set_pools_i8): the figures of DESIGN.md, "YOLOv3-tiny in int8"
+
+--model tiny: the fp32 side is a node walker over the tiny program from the oracle's layers and the package's NumPy max-pool (the oracle's
+own forward has no pool), the fp16 side the same walker with fp16 weights and every conv output rounded to fp16; calibration also takes
+the tensors the int8 aux ops write, and every class of quant.scale_classes its largest scale.
 """
 import argparse
 import os
@@ -47,6 +52,57 @@ def calibrate_cpu(program, kept, percentile):
     return quant.equalize_concat(program, scales)
 
 
+def walk(program, weights, x, f16=False):
+    """{tensor id: fp32 NHWC} of every node of a program with max-pools, at the real widths.  f16: what an fp16 plan stores -- the
+    weights of every conv but the Cin = 3 one and every conv output rounded to fp16 (pools, up-sample and concat select or move)."""
+    from yolo_v3_tf2_amd.maxpool import maxpool2x2_ref
+    vals = {program.input_tensor: np.ascontiguousarray(x, np.float32)}
+    for n in program.nodes:
+        a = vals[n.inputs[0]]
+        if n.kind == "conv":
+            w = {k: v for k, v in weights.items() if k.startswith(f"conv{n.conv_index}.")}
+            if f16 and a.shape[-1] != 3:
+                w[f"conv{n.conv_index}.w"] = round_f16(w[f"conv{n.conv_index}.w"])
+            y = O.conv_block(a, w, n.conv_index, n.size, n.stride, n.bn, n.leaky)
+            y = round_f16(y) if f16 else y
+        elif n.kind == "maxpool":
+            y = maxpool2x2_ref(a, n.stride)
+        elif n.kind == "add":
+            y = O.add(a, vals[n.inputs[1]])
+            y = round_f16(y) if f16 else y
+        elif n.kind == "upsample":
+            y = O.upsample2x(a)
+        elif n.kind == "concat":
+            y = O.concat(a, vals[n.inputs[1]])
+        elif n.kind == "yolo":
+            y = a.reshape(a.shape[0], a.shape[1], a.shape[2], 3, a.shape[3] // 3)
+        else:
+            raise ValueError(n.kind)
+        vals[n.output] = y
+    return vals
+
+
+def measure_pooled(program, weights, x, percentiles=(100.0, 99.99)):
+    """measure() for a program with max-pools (YOLOv3-tiny, Net.set_pools_i8): -> {"f32": fp32 head grids, percentile: (int8 grids,
+    [rel L2 per head])}."""
+    cut = quant.first_i8_conv(program)
+    convs = program.conv_ops()
+    aux, _ = quant.i8_aux_ops(program, cut)
+    crossing = quant.crossing_tensors(program, cut)
+    need = {o.dst for o in convs[cut:] if not quant.writes_f32(program, o)} | {o.dst for o in aux} | set(crossing)
+    v32 = walk(program, weights, x)
+    v16 = walk(program, weights, x, f16=True)
+    g32 = [v32[t].reshape(v32[t].shape[0], v32[t].shape[1], v32[t].shape[2], 3, -1) for t in program.outputs]
+    out = {"f32": g32}
+    for pc in percentiles:
+        scales = calibrate_cpu(program, {t: v32[t] for t in need}, pc)
+        boundary = {t: quant.quantize(v16[t], scales[t]) for t in crossing}
+        t8 = quant.forward_i8(program, weights, scales, boundary, cut)
+        grids = [t8[t].reshape(g.shape) for t, g in zip(program.outputs, g32)]
+        out[pc] = (grids, [rel_l2(a, b) for a, b in zip(grids, g32)])
+    return out
+
+
 def measure(program, weights, x, percentiles=(100.0, 99.99)):
     """-> {"f32": fp32 oracle grids, percentile: (int8 grids, [rel L2 per head])}."""
     convs = program.conv_ops()
@@ -82,19 +138,21 @@ def main():
     ap.add_argument("--image", default=None)
     ap.add_argument("--size", type=int, default=96)
     ap.add_argument("--seed", type=int, default=4321, help="synthetic weights")
+    ap.add_argument("--model", choices=("yolov3", "tiny"), default="yolov3")
     args = ap.parse_args()
     from yolo_v3_tf2_amd.core.utils import get_anchors
     from yolo_v3_tf2_amd.graph import load_program
     from yolo_v3_tf2_amd.weights import synthetic_weights
-    program = load_program(os.path.join(ROOT, "config/models/yolov3/model.yaml"), 80)
+    tiny = args.model == "tiny"
+    program = load_program(os.path.join(ROOT, "config/models/yolov3_tiny/model.yaml" if tiny else "config/models/yolov3/model.yaml"), 80)
     weights = synthetic_weights(program, seed=args.seed)
     if args.image:
         img = O.resize_bilinear(O.decode_image_rgb01(args.image), args.size, args.size)
         x = img[None]
     else:
         x = np.random.default_rng(1234).random((2, args.size, args.size, 3), dtype=np.float32)
-    r = measure(program, weights, x)
-    anchors = get_anchors(os.path.join(ROOT, "datasets/coco2012/anchors.txt")).astype("float32")
+    r = (measure_pooled if tiny else measure)(program, weights, x)
+    anchors = get_anchors(os.path.join(ROOT, "datasets/coco2012/anchors_tiny.txt" if tiny else "datasets/coco2012/anchors.txt")).astype("float32")
     s32, c32 = scores_of(r["f32"], anchors, 80)
     cand = s32 > 0.1
     for pc in (100.0, 99.99):

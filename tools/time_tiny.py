@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """YOLOv3-tiny on the device: what one detect costs, and what the max-pool kernel reaches.
 
-fp32 (--dtype bf16 / f16 with --fused-stem: the fused tiny stem, with which the tiny model plans in the 16-bit modes), config/models/yolov3_tiny/model.yaml with synthetic weights, Net.detect on
+fp32 (--dtype bf16 / f16 with --fused-stem: the fused tiny stem, with which the tiny model plans in the 16-bit modes; --dtype i8 with
+--fused-stem: the int8 plan with Net.set_pools_i8, calibrated on the spot from two random frames, alternated with the fp16 and bf16 plans under
+the same stem switch, and at one image also with set_low_latency_i8; section 3 is left out), config/models/yolov3_tiny/model.yaml with synthetic weights, Net.detect on
 device-resident frames, by the protocol of tools/time_latency.py:
   eager  -- every call between a pair of device events on the stream;
   graph  -- the call captured with torch.cuda.graph, every replay timed with the host clock around a synchronise;
@@ -37,7 +39,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--pool-calls", type=int, default=200)
     ap.add_argument("--profile-steps", type=int, default=0, help="enqueue this many detects and exit (for rocprofv3)")
-    ap.add_argument("--dtype", choices=("f32", "bf16", "f16"), default="f32", help="the plans' conv arithmetic; bf16 and f16 need --fused-stem")
+    ap.add_argument("--dtype", choices=("f32", "bf16", "f16", "i8"), default="f32", help="the plans' conv arithmetic; bf16, f16 and i8 need --fused-stem")
     ap.add_argument("--fused-stem", action="store_true", help="the fused tiny stem kernel (Net.set_tiny_stem_fusion) in the measured plan; "
                                                                "sections 1 and 2 then alternate it with the fp32 plan without the switch")
     ap.add_argument("--out", default=None)
@@ -63,7 +65,9 @@ def main():
 
     dtype = runtime.Net._dtype_arg(a.dtype)
     if a.dtype != "f32" and not a.fused_stem:
-        ap.error("--dtype bf16 / f16 needs --fused-stem: the tiny model plans in a 16-bit mode only with the fused stem")
+        ap.error("--dtype bf16 / f16 / i8 needs --fused-stem: the tiny model plans in a 16-bit mode, and before an int8 cut, only with the fused stem")
+    i8 = a.dtype == "i8"
+    scales = []
 
     def make(batch, low_latency=False, fused=None, dt=None):
         """fused / dt None: what the command line says; the baseline of an A/B is make(batch, fused=False, dt=0), the fp32 plan without the switch"""
@@ -71,7 +75,14 @@ def main():
         net.load_weights(weights)
         net.set_low_latency(low_latency)
         net.set_tiny_stem_fusion(a.fused_stem if fused is None else fused)
-        net.plan(batch, S, dtype if dt is None else dt)
+        dt = dtype if dt is None else dt
+        if dt == runtime.Net._dtype_arg("i8"):
+            net.set_low_latency_i8(low_latency)
+            net.set_pools_i8(True)
+            if not scales:      # absmax calibration from two random frames, once; every int8 net of this run takes the same scales
+                scales.extend(net.calibrate_i8(torch.rand((2, S, S, 3), device="cuda", generator=torch.Generator("cuda").manual_seed(1))))
+            net.set_act_scales(scales)
+        net.plan(batch, S, dt)
         return net
 
     if a.profile_steps:
@@ -158,7 +169,13 @@ def main():
     x = torch.rand((B, S, S, 3), device="cuda")
     say(f"\n== detect, {B} x {S} x {S}, lanes {getattr(net, 'lanes', 1)}")
     steps = {"default": lambda: net.detect(x, anchors, 100, 0.5, 0.1)}
-    if a.fused_stem:      # A/B in one process: the fp32 plan without the switch in alternated windows
+    if i8:                # A/B in one process: the fp16 and bf16 plans under the same stem switch in alternated windows
+        others = {k: make(B, dt=runtime.Net._dtype_arg(k)) for k in ("f16", "bf16")}
+        say(f"   'default' = i8 with set_pools_i8 and the fused tiny stem (pools_i8 = {net.pools_i8}, cut = conv {net.i8_first_conv()}, tiny_stem_fused = "
+            f"{net.tiny_stem_fused}); 'f16', 'bf16' = those plans with the fused tiny stem")
+        for k, n in others.items():
+            steps[k] = lambda n=n: n.detect(x, anchors, 100, 0.5, 0.1)
+    elif a.fused_stem:    # A/B in one process: the fp32 plan without the switch in alternated windows
         base = make(B, fused=False, dt=0)
         say(f"   'default' = {a.dtype} with the fused tiny stem (tiny_stem_fused = {net.tiny_stem_fused}); 'f32_unfused' = the fp32 plan without the switch")
         steps["f32_unfused"] = lambda: base.detect(x, anchors, 100, 0.5, 0.1)
@@ -167,22 +184,35 @@ def main():
         for k in steps:
             med = float(np.median(np.concatenate(r[form][k])))
             say(f"throughput {form} {k}: {B / med * 1e3:.0f} images/s ({med:.4f} ms per step of {B})")
-    if a.fused_stem:
+    if i8:
+        del others
+    elif a.fused_stem:
         del base
     pools = [(o, program.tensors[o.inputs[0]]) for o in program.ops if isinstance(o, AuxOp) and o.kind.startswith("maxpool")]
     del net
     torch.cuda.empty_cache()
 
     # ---- 2. latency at one image
-    nets = {"default": make(1), "low_latency": make(1, True)} if not a.fused_stem else {"default": make(1), "f32_unfused": make(1, fused=False, dt=0)}
+    if i8:
+        nets = {"default": make(1), "low_latency": make(1, True), "f16": make(1, dt=runtime.Net._dtype_arg("f16")), "bf16": make(1, dt=runtime.Net._dtype_arg("bf16"))}
+    else:
+        nets = {"default": make(1), "low_latency": make(1, True)} if not a.fused_stem else {"default": make(1), "f32_unfused": make(1, fused=False, dt=0)}
     x1 = torch.rand((1, S, S, 3), device="cuda")
-    if "low_latency" in nets:
+    if i8:
+        say(f"\n== detect, 1 x {S} x {S}; i8 default, i8 with set_low_latency_i8 (K slices per conv: "
+            f"{[nets['low_latency'].split_k_i8(i) for i in range(len(program.conv_ops()))]}), f16 and bf16, all with the fused tiny stem")
+    elif "low_latency" in nets:
         say(f"\n== detect, 1 x {S} x {S}; K slices per conv of the low-latency plan: {[nets['low_latency'].split_k(i) for i in range(len(program.conv_ops()))]}")
     else:
         say(f"\n== detect, 1 x {S} x {S}; {a.dtype} with the fused tiny stem against the fp32 plan without the switch")
     timed({k: (lambda n=n: n.detect(x1, anchors, 100, 0.5, 0.1)) for k, n in nets.items()}, max(a.calls, 400), "latency")
     del nets
     torch.cuda.empty_cache()
+    if a.dtype not in ("f32", "bf16", "f16"):      # section 3 times the fp32 pool kernel on the six pools' shapes: an int8 plan launches two of them on bytes
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+        return
 
     # ---- 3. the pool kernel alone, beside a device-to-device copy of the same byte count
     say(f"\n== ops.maxpool2x2 on the six pools' own shapes, batch {B}, fp32 (stored widths); copy = torch copy_ of (read + written) / 2 bytes, "

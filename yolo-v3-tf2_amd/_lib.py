@@ -149,6 +149,8 @@ SYMBOLS = {
     "y3_net_set_stem_fusion_f16": (_i, [_vp, _i]),
     "y3_net_set_tiny_stem_fusion": (_i, [_vp, _i]),
     "y3_net_get_tiny_stem_fused": (_i, [_vp]),
+    "y3_net_set_pools_i8": (_i, [_vp, _i]),
+    "y3_net_pools_i8": (_i, [_vp]),
     "y3_net_measure_sclk": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _fp, _vp]),
     "y3_net_measure_sclk_conv": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _i, _fp, _vp]),
     "y3_net_measure_sclk_all": (_i, [_vp, _vp, _i, C.POINTER(_vp), _i, _fp, C.POINTER(C.c_double), C.POINTER(C.c_double), _vp]),

@@ -32,7 +32,7 @@ class _LoadStatus:
 
 
 _DEFERRED_DEFAULTS = {"set_low_latency": False, "set_low_latency_f16": False, "set_low_latency_i8": False, "set_stem_fusion_f16": 0,
-                      "set_tiny_stem_fusion": 0,
+                      "set_tiny_stem_fusion": 0, "set_pools_i8": 0,
                       "load_calibration": None, "set_dtype": None}
 
 
@@ -52,7 +52,7 @@ class YoloModel:
         self.multi_label, self.multi_label_capacity = False, 0      # set_multi_label: the device net's properties of those names
         self.tiles = None               # set_tiles: (rows, cols, overlap_px, overview), the device net's property of that name
 
-    def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, tiny_stem_fusion, i8_calibration, dtype
+    def __getattr__(self, name):     # the settings read as attributes: low_latency, ..., stem_fusion_f16, tiny_stem_fusion, pools_i8, i8_calibration, dtype
         method = {"i8_calibration": "load_calibration"}.get(name, "set_" + name)
         if method in _DEFERRED_DEFAULTS and "_deferred" in self.__dict__:
             return self._deferred[method]
@@ -105,6 +105,12 @@ class YoloModel:
         dtype "bf16" and "f16".  Ignored by a program that does not start with tiny's stem.  Takes effect at the next plan."""
         from ..runtime import Net
         self._defer("set_tiny_stem_fusion", Net._tiny_stem_arg(on))
+
+    def set_pools_i8(self, on=True):
+        """Stand-alone ops of dtype "i8" plans on int8 tensors (runtime.Net.set_pools_i8): off by default; with it, and with
+        set_tiny_stem_fusion, the tiny model plans in dtype "i8".  Does nothing in any other dtype.  Takes effect at the next plan."""
+        from ..runtime import Net
+        self._defer("set_pools_i8", Net._pools_i8_arg(on))
 
     def set_nms_per_class(self, on=True):
         """Per-class NMS (runtime.Net.nms_per_class; no reference counterpart): a box is suppressed only by a kept box of its own

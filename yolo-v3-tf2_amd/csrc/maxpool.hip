@@ -3,19 +3,30 @@
 // run along the channels and then along the output row, so a wave's stores are one contiguous run and its loads two (the two input rows).
 // out[y, x] = max(in[y0 .. min(y0 + 1, H - 1), x0 .. min(x0 + 1, W - 1)]), (y0, x0) = (y, x) * stride: the clamps are the whole border
 // rule ('same' padding never wins a max), there is no running maximum with a start value.  Elements are compared as values and the
-// winner's bits are stored; a NaN in a window and the sign of a zero result are unspecified.
+// winner's bits are stored; a NaN in a window and the sign of a zero result are unspecified.  An int8 plan's pools behind its cut run the
+// same body on 16 signed bytes per vector (Y3_DTYPE_I8): every byte value is legal, -128 included.
 #include "../../include/y3.h"
 #include "y3_device.h"
 #include "y3_kernels.h"
 
 namespace y3 {
 
-// the larger of two elements of format FMT held in 32-bit words: one fp32, or two bf16 / fp16 (each half on its own)
+typedef short s16x2 __attribute__((ext_vector_type(2)));
+
+// the larger of two elements of format FMT held in 32-bit words: one fp32, two bf16 / fp16 (each half on its own), or four signed bytes
+// (each on its own: a byte in the high half of a 16-bit lane, the low half zero, orders as the byte does -- v_pk_max_i16 on the odd bytes,
+// and on the even bytes moved up by eight bits)
 template <int FMT>
 __device__ __forceinline__ unsigned max_word(unsigned a, unsigned b)
 {
     if constexpr (FMT == Y3_DTYPE_F32) {
         return __uint_as_float(b) > __uint_as_float(a) ? b : a;
+    } else if constexpr (FMT == Y3_DTYPE_I8) {
+        constexpr unsigned odd = 0xff00ff00u;
+        auto pk_max = [](unsigned u, unsigned v) {
+            return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(s16x2, u), __builtin_bit_cast(s16x2, v)));
+        };
+        return pk_max(a & odd, b & odd) | (pk_max((a << 8) & odd, (b << 8) & odd) >> 8);
     } else {
         float alo, ahi, blo, bhi;
         if constexpr (FMT == Y3_DTYPE_BF16) {
@@ -80,11 +91,11 @@ static hipError_t launch_fmt(const void *src, void *dst, int B, int H, int W, in
     return hipGetLastError();
 }
 
-// dtype: Y3_DTYPE_F32, _BF16 or _F16 (the element format); C * element size a multiple of 16 bytes, both pointers 16-byte aligned;
+// dtype: Y3_DTYPE_F32, _BF16, _F16 or _I8 (the element format); C * element size a multiple of 16 bytes, both pointers 16-byte aligned;
 // stride 2 on even H and W.  Only enqueues.
 hipError_t launch_maxpool2x2(const void *src, void *dst, int B, int H, int W, int C, int stride, int dtype, hipStream_t s)
 {
-    const int eb = dtype == Y3_DTYPE_F32 ? 4 : 2;
+    const int eb = dtype == Y3_DTYPE_F32 ? 4 : dtype == Y3_DTYPE_I8 ? 1 : 2;
     if (B < 1 || H < 1 || W < 1 || C < 1 || (stride != 1 && stride != 2) || (stride == 2 && ((H | W) & 1)) || ((long long)C * eb) % 16 ||
         ((uintptr_t)src & 15) || ((uintptr_t)dst & 15))
         return hipErrorInvalidValue;
@@ -93,6 +104,7 @@ hipError_t launch_maxpool2x2(const void *src, void *dst, int B, int H, int W, in
         case Y3_DTYPE_F32: return launch_fmt<Y3_DTYPE_F32>(src, dst, B, H, W, V, stride, s);
         case Y3_DTYPE_BF16: return launch_fmt<Y3_DTYPE_BF16>(src, dst, B, H, W, V, stride, s);
         case Y3_DTYPE_F16: return launch_fmt<Y3_DTYPE_F16>(src, dst, B, H, W, V, stride, s);
+        case Y3_DTYPE_I8: return launch_fmt<Y3_DTYPE_I8>(src, dst, B, H, W, V, stride, s);
         default: return hipErrorInvalidValue;
     }
 }

@@ -229,28 +229,35 @@ struct Slice {
     y3_status run_aux(int index) const
     {
         const y3_aux_desc &x = net->aux[index];
-        if (x.kind == Y3_AUX_MAXPOOL2X2_S2 || x.kind == Y3_AUX_MAXPOOL2X2_S1) {   // on the plan's stored elements: fp32, bf16 or fp16 (y3_net_plan)
+        // an int8 plan runs an aux op on int8 tensors behind its cut (y3_net_set_pools_i8; resolve_i8 decided) and as an fp16 plan before it
+        const int eb = (int)elem_bytes(x.dst);
+        if (x.kind == Y3_AUX_MAXPOOL2X2_S2 || x.kind == Y3_AUX_MAXPOOL2X2_S1) {   // on the plan's stored elements: fp32, bf16, fp16 or int8 (y3_net_plan)
             const int stride = x.kind == Y3_AUX_MAXPOOL2X2_S2 ? 2 : 1;
             if (!ptr(x.src0) || !ptr(x.dst) || elem_bytes(x.src0) != elem_bytes(x.dst)) return fail(Y3_ERR_STATE, "aux op %d: tensor not planned", index);
-            const int dt = elem_bytes(x.src0) == 4 ? (int)Y3_DTYPE_F32 : net->dtype;
+            const int dt = eb == 4 ? (int)Y3_DTYPE_F32 : eb == 1 ? (int)Y3_DTYPE_I8 : net->dtype == Y3_DTYPE_I8 ? (int)Y3_DTYPE_F16 : net->dtype;
             hipError_t e = y3::launch_maxpool2x2(ptr(x.src0), ptr(x.dst), nb, rows(net, x.src0), cols(net, x.src0), net->tensors[x.src0].channels, stride, dt, s);
             if (e != hipSuccess) return fail(Y3_ERR_HIP, "aux op %d (max-pool) launch: %s", index, hipGetErrorString(e));
             return Y3_OK;
         }
         // The up-sample and the concat only move elements: a bf16 or fp16 plan runs them on its 16-bit tensors as on fp32 tensors of half the
-        // channels (two elements per 4-byte word; YOLOv3-tiny's up-sample and its concat in front of a 3x3 conv).  The add is arithmetic and
-        // stays fp32 only, as every stand-alone op does in the plane-split and int8 plans.
+        // channels (two elements per 4-byte word; YOLOv3-tiny's up-sample and its concat in front of a 3x3 conv), an int8 plan with
+        // y3_net_set_pools_i8 on its int8 tensors as on fp32 tensors of a quarter of the channels, and on its fp16 tensors before the cut as an
+        // fp16 plan.  The add is arithmetic and stays fp32 only, as every stand-alone op does in the plane-split plans and in an int8 plan
+        // without that switch.
         const bool moves = x.kind == Y3_AUX_UPSAMPLE2X || x.kind == Y3_AUX_CONCAT;
-        const bool sixteen = (net->dtype == Y3_DTYPE_BF16 || net->dtype == Y3_DTYPE_F16) && moves && elem_bytes(x.dst) == 2 && elem_bytes(x.src0) == 2 &&
-                             (x.src1 < 0 || elem_bytes(x.src1) == 2);
-        if (net->dtype != Y3_DTYPE_F32 && !sixteen) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
+        const bool narrow_plan = net->dtype == Y3_DTYPE_BF16 || net->dtype == Y3_DTYPE_F16 || (net->dtype == Y3_DTYPE_I8 && net->pools_i8_plan);
+        const bool narrow = narrow_plan && moves && (eb == 2 || eb == 1) && eb == (net->aux_i8[index] ? 1 : 2) && (int)elem_bytes(x.src0) == eb &&
+                            (x.src1 < 0 || (int)elem_bytes(x.src1) == eb);
+        if (net->dtype != Y3_DTYPE_F32 && !narrow) return fail(Y3_ERR_INVALID, "stand-alone add/upsample/concat ops are fp32 only");
         auto p = [&](int t) { return static_cast<float *>(ptr(t)); };
         const int sh = rows(net, x.dst), sw = cols(net, x.dst);
-        const int per = sixteen ? 2 : 1;   // elements per 4-byte word
+        const int per = narrow ? 4 / eb : 1;   // elements per 4-byte word
         const int C = net->tensors[x.dst].channels;
         if (moves && (!p(x.src0) || !p(x.dst) || (x.kind == Y3_AUX_CONCAT && !p(x.src1)))) return fail(Y3_ERR_STATE, "aux op %d: tensor not planned", index);
-        if (sixteen && (C % 8 || net->tensors[x.src0].channels % 8))
+        if (narrow && eb == 2 && (C % 8 || net->tensors[x.src0].channels % 8))
             return fail(Y3_ERR_INVALID, "aux op %d: a stand-alone up-sample / concat of a 16-bit plan needs channel counts that are multiples of 8", index);
+        if (narrow && eb == 1 && (C % 16 || net->tensors[x.src0].channels % 16))   // y3_net_plan refused it: never reached
+            return fail(Y3_ERR_INVALID, "aux op %d: a stand-alone up-sample / concat on int8 tensors needs channel counts that are multiples of 16", index);
         hipError_t e = hipSuccess;
         if (x.kind == Y3_AUX_ADD)
             e = y3::launch_add(p(x.src0), p(x.src1), p(x.dst), (size_t)nb * sh * sw * C, s);
@@ -278,8 +285,11 @@ struct Slice {
         for (int oi = op_begin; oi < op_end; ++oi) {
             const Op &o = net->ops[oi];
             if (o.kind != 0) {
-                if (net->tiny_stem_fused && (oi == 1 || oi == 3)) continue;   // the pools inside the fused tiny stem launch
-                if (y3_status st = run_aux(o.index); st != Y3_OK) return st;
+                if (!(net->tiny_stem_fused && (oi == 1 || oi == 3)))   // (the pools inside the fused tiny stem launch run with op 2)
+                    if (y3_status st = run_aux(o.index); st != Y3_OK) return st;
+                // an int8 plan: a tensor an aux op writes before the cut that an int8 conv reads gets its copy behind that op (tiny: pool 3's)
+                if (const int dst = net->aux[o.index].dst; crosses(dst))
+                    if (y3_status st = quantize_crossing(dst); st != Y3_OK) return st;
                 continue;
             }
             y3::ConvArgs a = conv_args(o.index);

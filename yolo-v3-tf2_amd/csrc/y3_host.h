@@ -118,7 +118,7 @@ struct y3_net {
     int input_tensor = 0;
     int outputs[3] = {0, 0, 0};
     int n_heads = 3;               // how many of them the net has (y3_net_create_heads): 3, or 2 for YOLOv3-tiny
-    bool has_pool = false;         // an aux op is a max-pool: fp32, bf16 and fp16 plans only (y3_net_plan)
+    bool has_pool = false;         // an aux op is a max-pool: fp32, bf16 and fp16 plans, and int8 plans with y3_net_set_pools_i8 (y3_net_plan)
     int nclasses = 0;
     // plan
     int max_batch = 0, height = 0, width = 0, dtype = Y3_DTYPE_F32;   // the planned canvas: height x width (0: no plan)
@@ -182,7 +182,12 @@ struct y3_net {
     // element of every tensor in the arena (every plan: the mode's; int8 plans: 2 before the cut, 1 behind it).  tq8: the int8 copy of a
     // tensor written before the cut (or handed in) and read behind it (tcross: such a tensor, decided before the arena is placed), image i
     // at i * image elements; tscale: the scales the plan took.
+    // pools_i8_mode: y3_net_set_pools_i8, read by y3_net_plan; aux_i8: (at plan time) per aux op, 1 when the plan runs it on int8 tensors
+    // behind the cut (a max-pool, an up-sample or a concat whose every source is behind the cut), else the op runs as in an fp16 plan.
     std::vector<float> act_scale;
+    int pools_i8_mode = 0;
+    bool pools_i8_plan = false;    // (at plan time) pools_i8_mode as the int8 plan in force found it
+    std::vector<char> aux_i8;
     int i8_first_conv = -1;
     std::vector<unsigned char> telem;
     std::vector<char> tcross;
@@ -282,6 +287,11 @@ y3_status resolve_splits(y3_net *net);
 y3_status resolve_border(y3_net *net);
 // int8 plans: the cut, the element size of every tensor and the scales the plan needs (y3_net_plan, before the arena is placed) ...
 y3_status resolve_i8(y3_net *net);
+// ... the cut itself, from the graph alone (the conv count: no conv qualifies) ...
+int i8_cut(const y3_net *net);
+// ... and, with y3_net_set_pools_i8, which aux ops run in int8 behind that cut (aux_i8, null: only the check) or why the graph is refused;
+// from the graph alone, so y3_net_plan asks before it frees the plan in force
+y3_status resolve_i8_aux(const y3_net *net, int cut, std::vector<char> *aux_i8, std::vector<char> *behind);
 // ... and the epilogue scales of int8 conv `slot` on the device, once its weights are loaded (y3_net_plan; y3_net_set_conv_weights on a planned net)
 y3_status upload_i8_scales(y3_net *net, int slot);
 void free_plan(y3_net *net);

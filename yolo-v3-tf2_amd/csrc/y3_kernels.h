@@ -310,7 +310,7 @@ bool conv_x2_tile_built(int tile);     // 26, 27: two planes only
 hipError_t launch_add(const float *a, const float *b, float *y, size_t n, hipStream_t s);
 hipError_t launch_upsample2x(const float *x, int B, int H, int W, int C, float *y, hipStream_t s);
 hipError_t launch_concat(const float *a, int Ca, const float *b, int Cb, size_t npix, float *y, hipStream_t s);
-// MaxPooling2D(2, stride 1 | 2, 'same') on [B,H,W,C] elements of dtype Y3_DTYPE_F32 / _BF16 / _F16 (maxpool.hip)
+// MaxPooling2D(2, stride 1 | 2, 'same') on [B,H,W,C] elements of dtype Y3_DTYPE_F32 / _BF16 / _F16 / _I8 (maxpool.hip)
 hipError_t launch_maxpool2x2(const void *src, void *dst, int B, int H, int W, int C, int stride, int dtype, hipStream_t s);
 
 struct DecodeArgs {   // of one to three scales: an absent scale has gh = gw = 0, no boxes and no workgroup

@@ -403,12 +403,14 @@ void y3::resolve_stem(y3_net *net)
 // The fused stem of YOLOv3-tiny (csrc/conv_tiny_stem.hip).  Ops 0..3 are conv0 (the 3x3/1 first layer, 3 -> 16 stored as 32) reading the input,
 // Y3_AUX_MAXPOOL2X2_S2 on it, a 3x3/1 conv 16 (stored 32) -> 32 with a single source and no shortcut, and Y3_AUX_MAXPOOL2X2_S2 on that; each of
 // the first three outputs has exactly one reader, none of the four is a net output, there are no early chunks, and the plan's mode has the
-// kernel (fp32, bf16, fp16).  The stored widths are all the graph tells: that conv0's channels 16..31 are zero pad channels is a property of its
+// kernel (fp32, bf16, fp16; an int8 plan whose cut lies behind op 3 runs this part as an fp16 plan and takes the fp16 kernel).  The stored widths are all the graph tells: that conv0's channels 16..31 are zero pad channels is a property of its
 // weights (ConvSlot::tiny_pad_zero), which the forward asks for.  keep_activations does not matter: the tensors inside are simply not stored.
 bool y3::tiny_stem_applicable(const y3_net *net)
 {
-    if (!family_of(net).launch_tiny_stem || net->height % 32 || net->width % 32 || net->early_ops > 0) return false;
+    if (net->height % 32 || net->width % 32 || net->early_ops > 0) return false;
     if (net->ops.size() < 5 || net->ops[0].kind != 0 || net->ops[1].kind == 0 || net->ops[2].kind != 0 || net->ops[3].kind == 0) return false;
+    // the mode of conv1: the plan's, or fp16 before the cut of an int8 plan (resolve_i8 has run); conv1 itself behind the cut has no kernel
+    if (!family_of_conv(net, net->ops[2].index).launch_tiny_stem) return false;
     const ConvSlot &c0 = net->convs[net->ops[0].index], &c1 = net->convs[net->ops[2].index];
     const y3_conv_desc &a = c0.d, &b = c1.d;
     const y3_aux_desc &p0 = net->aux[net->ops[1].index], &p1 = net->aux[net->ops[3].index];
@@ -1132,6 +1134,22 @@ try {
 Y3_CATCH("y3_net_set_tiny_stem_fusion")
 
 int y3_net_get_tiny_stem_fused(const y3_net *net) { return net && net->height && net->tiny_stem_fused ? 1 : 0; }
+
+y3_status y3_net_set_pools_i8(y3_net *net, int on)
+try {
+    if (!net || on < 0 || on > 1) return fail(Y3_ERR_INVALID, "y3_net_set_pools_i8: argument must be 0 or 1");
+    net->pools_i8_mode = on;   // read by the next y3_net_plan: the element size of the arena's tensors follows it
+    return Y3_OK;
+}
+Y3_CATCH("y3_net_set_pools_i8")
+
+int y3_net_pools_i8(const y3_net *net)
+{
+    if (!net || !net->height || net->dtype != Y3_DTYPE_I8) return 0;
+    for (char on : net->aux_i8)
+        if (on) return 1;
+    return 0;
+}
 
 y3_status y3_net_set_k_chunk(y3_net *net, int channels)
 try {

@@ -646,11 +646,11 @@ y3_status y3_maxpool2x2(const void *src_dev, void *dst_dev, int batch, int heigh
 try {
     const char *who = "y3_maxpool2x2";
     if (!src_dev || !dst_dev || batch < 1 || height < 1 || width < 1 || channels < 1) return fail(Y3_ERR_INVALID, "%s: bad argument", who);
-    if (dtype != Y3_DTYPE_F32 && dtype != Y3_DTYPE_BF16 && dtype != Y3_DTYPE_F16)
-        return fail(Y3_ERR_INVALID, "%s: dtype must be Y3_DTYPE_F32, Y3_DTYPE_BF16 or Y3_DTYPE_F16 (got %d)", who, dtype);
+    if (dtype != Y3_DTYPE_F32 && dtype != Y3_DTYPE_BF16 && dtype != Y3_DTYPE_F16 && dtype != Y3_DTYPE_I8)
+        return fail(Y3_ERR_INVALID, "%s: dtype must be Y3_DTYPE_F32, Y3_DTYPE_BF16, Y3_DTYPE_F16 or Y3_DTYPE_I8 (got %d)", who, dtype);
     if (stride != 1 && stride != 2) return fail(Y3_ERR_INVALID, "%s: stride must be 1 or 2 (got %d)", who, stride);
     if (stride == 2 && ((height | width) & 1)) return fail(Y3_ERR_INVALID, "%s: a stride-2 pool needs even extents (got %d x %d)", who, height, width);
-    const int eb = dtype == Y3_DTYPE_F32 ? 4 : 2;
+    const int eb = dtype == Y3_DTYPE_F32 ? 4 : dtype == Y3_DTYPE_I8 ? 1 : 2;
     if (((long long)channels * eb) % 16) return fail(Y3_ERR_INVALID, "%s: %d channels of %d bytes are no multiple of 16 bytes", who, channels, eb);
     if (((uintptr_t)src_dev & 15) || ((uintptr_t)dst_dev & 15)) return fail(Y3_ERR_INVALID, "%s: src / dst not 16-byte aligned", who);
     if ((long long)batch * (height / stride) > 0x7fffffffll || (long long)(width / stride) * channels * eb / 16 > 0x00ffffffll)

@@ -36,6 +36,8 @@ void y3::drop_plan(y3_net *n)
     n->kept = 0;
     n->stem_fused = n->stem_conv2 = n->tiny_stem_fused = false;
     n->i8_first_conv = -1;
+    n->aux_i8.assign(n->aux.size(), 0);
+    n->pools_i8_plan = false;
     n->last_batch = n->last_lanes = 0;
     n->multi_label_batch = 0;
     for (ConvSlot &c : n->convs) c.split_k = 1;
@@ -154,6 +156,67 @@ static y3_status place_tensors(y3_net *net, const std::vector<int> &first, const
 // The cut c*: the first conv in op order such that it and every conv after it has Cin % 128 == 0 (both parts of a concat), and
 // Cout % 16 == 0 unless it writes an fp32 grid itself.  From c* on the convs run in int8; before it the plan is an fp16 plan.  A tensor
 // written before the cut (or handed in) and read behind it gets an int8 copy (tq8) from one elementwise launch.
+// A conv "writes an fp32 grid itself" when its destination is a net output that a non-fp32 plan does not stage (output_staged): the one
+// predicate plan_hw forms out_slot from, so the cut found before the old plan is freed is the cut the plan takes.  -> the conv count when
+// no conv qualifies.
+int y3::i8_cut(const y3_net *net)
+{
+    const int nc = (int)net->convs.size();
+    int cut = nc;
+    for (int i = nc - 1; i >= 0; --i) {   // conv slots are in op order
+        const ConvSlot &c = net->convs[i];
+        const y3_conv_desc &d = c.d;
+        const bool grid = is_output(net, d.dst) && !output_staged(net, d.dst);
+        const bool ok = !c.first_layer && d.cin % 128 == 0 && (d.src1 < 0 || (d.c0 % 128 == 0 && (d.cin - d.c0) % 128 == 0)) &&
+                        (grid || d.cout % 16 == 0);
+        if (!ok) break;
+        cut = i;
+    }
+    return cut;
+}
+
+// Stand-alone ops of an int8 plan under y3_net_set_pools_i8 (include/y3.h, "Stand-alone ops in int8").  A tensor is behind the cut when a
+// conv from the cut on or an int8 aux op writes it; walking the aux ops in op order, a pool, an up-sample or a concat runs in int8 when
+// every source it has is behind the cut, and as in an fp16 plan when none is.  Reads the graph alone (no plan, no scales).
+y3_status y3::resolve_i8_aux(const y3_net *net, int cut, std::vector<char> *aux_i8, std::vector<char> *behind_out)
+{
+    static const char *const names[] = {"add", "up-sample", "concat", "max-pool, stride 2", "max-pool, stride 1"};
+    const int nt = (int)net->tensors.size(), nc = (int)net->convs.size();
+    if (aux_i8) aux_i8->assign(net->aux.size(), 0);
+    std::vector<char> behind(nt, 0);
+    for (int i = cut; i < nc; ++i) behind[net->convs[i].d.dst] = 1;
+    for (const Op &o : net->ops) {
+        if (o.kind == 0 || cut >= nc || !net->pools_i8_mode) continue;
+        const y3_aux_desc &x = net->aux[o.index];
+        const char *name = x.kind >= 0 && x.kind <= 4 ? names[x.kind] : "unknown";
+        const int n_src = x.src1 >= 0 ? 2 : 1, n_behind = behind[x.src0] + (x.src1 >= 0 ? behind[x.src1] : 0);
+        if (n_behind == 0) continue;   // before the cut: the fp16 plan's op
+        if (x.kind == Y3_AUX_ADD)
+            return fail(Y3_ERR_INVALID, "y3_net_plan: aux op %d (%s) reads tensor %d behind the int8 cut, conv %d; a stand-alone add has no int8 form "
+                                        "(a shortcut folded into its conv has)", o.index, name, behind[x.src0] ? x.src0 : x.src1, cut);
+        if (n_behind < n_src)
+            return fail(Y3_ERR_INVALID, "y3_net_plan: aux op %d (%s) joins tensor %d behind the int8 cut, conv %d, with tensor %d before it; both sources "
+                                        "of an int8 concat must lie behind the cut", o.index, name, behind[x.src0] ? x.src0 : x.src1, cut,
+                        behind[x.src0] ? x.src1 : x.src0);
+        for (int t : {x.src0, x.src1})
+            if (t >= 0 && is_output(net, t))
+                return fail(Y3_ERR_INVALID, "y3_net_plan: aux op %d (%s) reads tensor %d, a net output behind the int8 cut (an fp32 grid, or an int8 "
+                                            "tensor converted at the end of the forward); an int8 aux op reads arena tensors only", o.index, name, t);
+        if (is_output(net, x.dst))
+            return fail(Y3_ERR_INVALID, "y3_net_plan: aux op %d (%s) writes tensor %d, a net output; an int8 aux op writes arena tensors only", o.index, name, x.dst);
+        // (no graph y3_net_create accepts gets here today: an int8 tensor is written by a conv with Cout % 16 == 0 -- the cut rule -- or moved
+        // from such tensors; the guard is what the 16-byte moves rely on should the cut rule ever widen)
+        for (int t : {x.src0, x.src1, x.dst})
+            if (t >= 0 && net->tensors[t].channels % 16)
+                return fail(Y3_ERR_INVALID, "y3_net_plan: aux op %d (%s) behind the int8 cut moves 16-byte pieces of 16 int8 channels; tensor %d has %d "
+                                            "channels, no multiple of 16", o.index, name, t, net->tensors[t].channels);
+        if (aux_i8) (*aux_i8)[o.index] = 1;
+        behind[x.dst] = 1;
+    }
+    if (behind_out) *behind_out = behind;
+    return Y3_OK;
+}
+
 y3_status y3::resolve_i8(y3_net *net)
 {
     const int nt = (int)net->tensors.size(), nc = (int)net->convs.size();
@@ -162,22 +225,16 @@ y3_status y3::resolve_i8(y3_net *net)
     net->tq8.assign(nt, nullptr);
     net->tcross.assign(nt, 0);
     net->tscale.assign(nt, 0.0f);
+    net->aux_i8.assign(net->aux.size(), 0);
+    net->pools_i8_plan = net->dtype == Y3_DTYPE_I8 && net->pools_i8_mode;   // the plan's copy: the setter on a planned net waits for the next plan
     if (net->dtype != Y3_DTYPE_I8) return Y3_OK;
-    int cut = nc;
-    for (int i = nc - 1; i >= 0; --i) {   // conv slots are in op order
-        const ConvSlot &c = net->convs[i];
-        const y3_conv_desc &d = c.d;
-        const bool ok = !c.first_layer && d.cin % 128 == 0 && (d.src1 < 0 || (d.c0 % 128 == 0 && (d.cin - d.c0) % 128 == 0)) &&
-                        (net->out_slot[d.dst] >= 0 || d.cout % 16 == 0);
-        if (!ok) break;
-        cut = i;
-    }
+    const int cut = i8_cut(net);
     if (cut >= nc)
         return fail(Y3_ERR_INVALID, "y3_net_plan: no conv of this graph qualifies for int8 (the last conv needs Cin %% 128 == 0 and, unless it writes an fp32 output, Cout %% 16 == 0)");
     net->i8_first_conv = cut;
     std::fill(net->telem.begin(), net->telem.end(), (unsigned char)2);   // before the cut: an fp16 plan's tensors
-    std::vector<char> behind(nt, 0);                                     // written by a conv behind the cut
-    for (int i = cut; i < nc; ++i) behind[net->convs[i].d.dst] = 1;
+    std::vector<char> behind;                                            // written by a conv behind the cut, or by an int8 aux op
+    if (y3_status st = resolve_i8_aux(net, cut, &net->aux_i8, &behind); st != Y3_OK) return st;
     auto scale_of = [&](int t) { return t < (int)net->act_scale.size() && net->act_scale[t] > 0.0f ? net->act_scale[t] : 0.0f; };
     auto need = [&](int t) -> y3_status {
         if (!(scale_of(t) > 0.0f))
@@ -203,6 +260,20 @@ y3_status y3::resolve_i8(y3_net *net)
             net->telem[d.dst] = 1;
             c.q_inv = 1.0f / scale_of(d.dst);
         }
+    }
+    // an int8 aux op selects or moves stored bytes: its destination and every source carry one scale
+    for (size_t k = 0; k < net->aux.size(); ++k) {
+        if (!net->aux_i8[k]) continue;
+        const y3_aux_desc &x = net->aux[k];
+        if (y3_status st = need(x.dst); st != Y3_OK) return st;
+        for (int t : {x.src0, x.src1}) {
+            if (t < 0) continue;
+            if (y3_status st = need(t); st != Y3_OK) return st;
+            if (scale_of(t) != scale_of(x.dst))
+                return fail(Y3_ERR_INVALID, "y3_net_plan: aux op %zu moves int8 bytes between tensors %d and %d with different int8 scales (%g, %g); they must be equal",
+                            k, t, x.dst, (double)scale_of(t), (double)scale_of(x.dst));
+        }
+        net->telem[x.dst] = 1;
     }
     return Y3_OK;
 }
@@ -255,7 +326,7 @@ static y3_status plan_hw(y3_net *net, int max_batch, int height, int width, int 
 {
     if (!net || max_batch <= 0 || height <= 0 || width <= 0) return fail(Y3_ERR_INVALID, "y3_net_plan: bad argument");
     if (!y3::conv_family(dtype)) return fail(Y3_ERR_INVALID, "y3_net_plan: unknown dtype %d", dtype);
-    if (net->has_pool && (dtype == Y3_DTYPE_F32X3 || dtype == Y3_DTYPE_F32X2 || dtype == Y3_DTYPE_I8))
+    if (net->has_pool && (dtype == Y3_DTYPE_F32X3 || dtype == Y3_DTYPE_F32X2 || (dtype == Y3_DTYPE_I8 && !net->pools_i8_mode)))
         return fail(Y3_ERR_INVALID, "y3_net_plan: the net holds a max-pool op (Y3_AUX_MAXPOOL2X2_*), which %s; "
                                     "Y3_DTYPE_F32, Y3_DTYPE_BF16 and Y3_DTYPE_F16 run it",
                     dtype == Y3_DTYPE_I8 ? "has no calibrated int8 form" : "does not read plane-split tensors");
@@ -269,6 +340,8 @@ static y3_status plan_hw(y3_net *net, int max_batch, int height, int width, int 
             if (net->convs[i].loaded && !net->convs[i].x2_ok)
                 return fail(Y3_ERR_INVALID, "y3_net_plan: conv %zu has a BN-scaled weight outside the fp16 range (|w| >= 65504); "
                                             "the two-plane mode cannot represent it, use Y3_DTYPE_F32 or Y3_DTYPE_F32X3", i);
+    if (dtype == Y3_DTYPE_I8 && net->pools_i8_mode)   // what the graph itself rules out: refused with the plan in force left as it is
+        if (y3_status st = y3::resolve_i8_aux(net, y3::i8_cut(net), nullptr, nullptr); st != Y3_OK) return st;
     Y3_ENTER_DEVICE(net);
     if (net->n_cus <= 0) {   // once per net: the launch path itself makes no device query
         int cus = 0;

@@ -111,6 +111,7 @@ def _evaluate_on_device(detect_config, thresholds, evaluate_iou_threshold, max_b
     model.model.set_dtype(detect_config.get("dtype"))     # optional key: f32 | bf16 | f16 | i8; absent: f32
     model.model.set_stem_fusion_f16(detect_config.get("f16_fused_stem"))   # optional key, acts on dtype f16 only; absent: off
     model.model.set_tiny_stem_fusion(detect_config.get("tiny_fused_stem"))   # optional key, the fused stem of YOLOv3-tiny (f32, bf16, f16); absent: off
+    model.model.set_pools_i8(detect_config.get("i8_pools"))   # optional key, the pools, up-sample and concat of an i8 plan on int8 tensors (YOLOv3-tiny); absent: off
     model.model.set_nms_per_class(nms_per_class)          # the device net's detect, and the composed route of loss=True, follow it
     model.model.set_multi_label(multi_label, multi_label_capacity)   # multi-label detections: the device net's streams follow it
     model.model.set_tiles(*(tiles or (None,)))            # sliced inference: the device net's streams follow it
@@ -191,7 +192,7 @@ def evaluate(detect_config, evaluate_nms_score_thresholds, evaluate_iou_threshol
     An optional `dtype: f32 | bf16 | f16` key of detect_config selects the conv arithmetic of the on_device pass (absent: f32);
     an optional `f16_fused_stem: true` runs the first convs of an f16 plan as the fused stem kernel (absent: off);
     an optional `tiny_fused_stem: true` runs the stem of the YOLOv3-tiny model as its fused kernel (absent: off), with which that model
-    also takes `dtype: bf16` and `dtype: f16`.
+    also takes `dtype: bf16` and `dtype: f16`; an optional `i8_pools: true` on top of it lets that model take `dtype: i8` (absent: off).
     nms_per_class=True, or an optional `nms_per_class: true` key of detect_config (absent: off), on either route: per-class NMS
     (Net.nms_per_class; no reference counterpart) -- a box is suppressed only by a kept box of its own class, the rule published
     YOLOv3 mAP figures are taken under.  The one-pass argument of on_device=True holds as it stands: a box is never affected by a
@@ -273,6 +274,10 @@ def _arg_parser():
     ap.add_argument("--tiny-fused-stem", action="store_true",
                     help="with --on-device: the stem of the YOLOv3-tiny model as one fused kernel, with which that model also runs in "
                          "dtype bf16 and f16 (also the optional tiny_fused_stem key of the detect config; absent: off)")
+    ap.add_argument("--i8-pools", action="store_true",
+                    help="with --on-device: a dtype i8 plan runs the pools, the up-sample and the concat behind its cut on int8 tensors, with "
+                         "which (and --tiny-fused-stem) the YOLOv3-tiny model runs in dtype i8 (also the optional i8_pools key of the detect "
+                         "config; absent: off)")
     ap.add_argument("--nms-per-class", action="store_true",
                     help="per-class NMS: a box is suppressed only by a kept box of its own class (also the optional nms_per_class "
                          "key of either config; absent: the reference's class-agnostic rule)")
@@ -300,6 +305,8 @@ def main(argv=None):
         ap.error("--tiles needs --on-device")
     if a.tiny_fused_stem and not a.on_device:
         ap.error("--tiny-fused-stem needs --on-device")
+    if a.i8_pools and not a.on_device:
+        ap.error("--i8-pools needs --on-device")
     if a.multi_label and not a.on_device:
         ap.error("--multi-label needs --on-device")
     if a.multi_label_capacity and not a.multi_label:
@@ -316,6 +323,8 @@ def main(argv=None):
         detect_config = yaml.safe_load(s)
     if a.tiny_fused_stem:
         detect_config["tiny_fused_stem"] = True
+    if a.i8_pools:
+        detect_config["i8_pools"] = True
     results = evaluate(detect_config, thresholds, on_device=a.on_device, loss=a.loss, ap=ap_thresholds,
                        nms_per_class=a.nms_per_class or bool(evaluate_config.get("nms_per_class")),
                        tiles=(a.tiles[0], a.tiles[1], a.tile_overlap, a.tile_overview) if a.tiles else None,

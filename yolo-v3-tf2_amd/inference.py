@@ -78,6 +78,9 @@ class Inference:
     # The fused stem kernel of YOLOv3-tiny (runtime.Net.set_tiny_stem_fusion; None: off), with which the tiny model also runs in dtype bf16
     # and f16.  The optional YAML key `tiny_fused_stem` lands here the same way.
     tiny_fused_stem = None
+    # Stand-alone ops of dtype i8 plans on int8 tensors (runtime.Net.set_pools_i8; None: off), with which -- and with tiny_fused_stem -- the
+    # tiny model runs in dtype i8.  The optional YAML key `i8_pools` lands here the same way.
+    i8_pools = None
     # Per-class NMS (core.parse_model.YoloModel.set_nms_per_class; None or False: the reference's class-agnostic rule).  The optional YAML
     # key `nms_per_class` lands here the same way.
     nms_per_class = None
@@ -188,6 +191,7 @@ class Inference:
         model.set_dtype(dtype)
         model.set_stem_fusion_f16(self.f16_fused_stem if f16_fused_stem is None else f16_fused_stem)
         model.set_tiny_stem_fusion(self.tiny_fused_stem)
+        model.set_pools_i8(self.i8_pools)
         model.set_nms_per_class(self.nms_per_class)
         model.set_multi_label(self.multi_label, int(self.multi_label_capacity or 0))
         model.set_tiles(*(self.tiles or (None,)))
@@ -309,6 +313,7 @@ def main(argv=None):
     inference = Inference()
     inference.f16_fused_stem = detect_config.pop("f16_fused_stem", None)    # optional key, absent: off
     inference.tiny_fused_stem = detect_config.pop("tiny_fused_stem", None)  # optional key, absent: off
+    inference.i8_pools = detect_config.pop("i8_pools", None)                # optional key, absent: off
     inference.nms_per_class = detect_config.pop("nms_per_class", None)      # optional key, absent: off
     inference.multi_label = detect_config.pop("multi_label", None)          # optional keys, absent: off, every box of the plan
     inference.multi_label_capacity = detect_config.pop("multi_label_capacity", 0)

@@ -72,7 +72,34 @@ class _TinyStemSwitch:
         return int(self.lib.y3_net_get_tiny_stem_fused(self._h))
 
 
-class Net(_TinyStemSwitch):
+class _PoolsI8Switch:
+    """Stand-alone ops of an int8 plan (include/y3.h, y3_net_set_pools_i8: the max-pools, the up-sample and the concat of YOLOv3-tiny on
+    int8 tensors behind the cut): the part of Net's interface that came with it, kept in a base of its own."""
+
+    @staticmethod
+    def _pools_i8_arg(on) -> int:
+        if on is None:
+            return 0
+        if isinstance(on, (bool, np.bool_, int, np.integer)) and int(on) in (0, 1):
+            return int(on)
+        raise Y3Error(f"pools_i8 must be None, a bool, 0 or 1 (got {on!r})")
+
+    def set_pools_i8(self, on=True):
+        """An "i8" plan runs the max-pools, up-samples and concats behind its cut on int8 tensors instead of refusing a net that holds a
+        pool: off by default; None means off.  Before plan(): on a planned net it waits for the next plan.  Does nothing in any other
+        dtype.  YOLOv3-tiny needs set_tiny_stem_fusion as well (the part before the cut is an fp16 plan), and scales for the tensors the
+        aux ops write (calibrate_i8 with this switch on measures them)."""
+        on = self._pools_i8_arg(on)             # the argument check comes first: it needs no device net
+        check(self.lib.y3_net_set_pools_i8(self._h, on), "y3_net_set_pools_i8")
+        self.__dict__["_pools_i8_on"] = on
+
+    @property
+    def pools_i8(self) -> int:
+        """1 when the plan in force runs at least one aux op in int8 (y3_net_pools_i8), 0 otherwise, also before plan()."""
+        return int(self.lib.y3_net_pools_i8(self._h))
+
+
+class Net(_TinyStemSwitch, _PoolsI8Switch):
     """Device-side network = the fused conv program (reference counterpart: the Keras Model returned by
     ParseModel.build_model, core/parse_model.py:279-314)."""
 
@@ -612,7 +639,8 @@ class Net(_TinyStemSwitch):
     def calibrate_i8(self, images: torch.Tensor, percentile: float = 100.0) -> List[float]:
         """Activation scales for int8 plans from one batch of images [B,H,W,3] fp32 on the GPU: runs the fp32 plan with every
         activation kept, takes per tensor the absmax of |x| (percentile=100) or the given percentile of |x|, divides by 127, gives the
-        two sources of every concat conv the larger of their scales, sets the scales (set_act_scales) and returns them.  Offline: the
+        two sources of every concat conv the larger of their scales (with set_pools_i8: also measures the tensors the aux ops write, and
+        gives every class of quant.scale_classes its largest scale), sets the scales (set_act_scales) and returns them.  Offline: the
         reductions are torch's.  The net is left planned in fp32 with activations kept; plan it again for inference."""
         from . import quant
         if not 0.0 < float(percentile) <= 100.0:
@@ -625,6 +653,10 @@ class Net(_TinyStemSwitch):
         p = self.program
         scales = [0.0] * len(p.tensors)
         written = {o.dst for o in p.conv_ops()}
+        if self.__dict__.get("_pools_i8_on"):   # set_pools_i8: the tensors the aux ops write carry scales of their own
+            written |= {o.dst for o in p.ops if isinstance(o, AuxOp)}
+            if self.tiny_stem_fused:            # ... but those the fused tiny stem keeps on chip: they lie before any cut
+                written -= {p.ops[0].dst, p.ops[1].dst, p.ops[2].dst}
         if p.tensors[p.input_tensor].channels != 3:   # layer tests: the input feeds an MFMA conv directly and is quantised itself
             written.add(p.input_tensor)
         for t in sorted(written):
@@ -637,7 +669,7 @@ class Net(_TinyStemSwitch):
                 m = float(a.kthvalue(k).values)
             scales[t] = quant.scale_from_absmax(m)
         torch.cuda.synchronize()
-        scales = quant.equalize_concat(p, scales)
+        scales = quant.equalize_concat(p, scales, classes=bool(self.__dict__.get("_pools_i8_on")))
         self.set_act_scales(scales)
         self.keep_activations(False)
         return scales

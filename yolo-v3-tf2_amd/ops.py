@@ -67,13 +67,14 @@ def _decode_scores(grids, anchors_table, nclasses, out=None):
 
 
 def maxpool2x2(x: torch.Tensor, stride: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    """MaxPooling2D(2, strides=stride, 'same') of x [B,H,W,C] (float32, bfloat16 or float16, on the GPU) -> [B,H/stride,W/stride,C]
+    """MaxPooling2D(2, strides=stride, 'same') of x [B,H,W,C] (float32, bfloat16, float16 or int8, on the GPU) -> [B,H/stride,W/stride,C]
     (y3_maxpool2x2; maxpool.maxpool2x2_ref restates the rule).  stride 1 or 2, stride 2 on even H and W; C * element size a multiple
-    of 16 bytes.  Enqueues on the current stream only."""
+    of 16 bytes (int8: C % 16 == 0; every byte value is legal).  Enqueues on the current stream only."""
     _need_cuda(x, out)
-    dt = {torch.float32: _lib.Y3_DTYPE_F32, torch.bfloat16: _lib.Y3_DTYPE_BF16, torch.float16: _lib.Y3_DTYPE_F16}.get(x.dtype)
+    dt = {torch.float32: _lib.Y3_DTYPE_F32, torch.bfloat16: _lib.Y3_DTYPE_BF16, torch.float16: _lib.Y3_DTYPE_F16,
+          torch.int8: _lib.Y3_DTYPE_I8}.get(x.dtype)
     if dt is None or x.dim() != 4:
-        raise Y3Error("maxpool2x2: x must be float32, bfloat16 or float16 [B,H,W,C]")
+        raise Y3Error("maxpool2x2: x must be float32, bfloat16, float16 or int8 [B,H,W,C]")
     if stride not in (1, 2):
         raise Y3Error(f"maxpool2x2: stride must be 1 or 2 (got {stride!r})")
     B, H, W, Cc = (int(v) for v in x.shape)

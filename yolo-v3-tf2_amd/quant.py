@@ -8,6 +8,8 @@ integer conv goes through torch.nn.functional.conv2d in float64 (|sum| <= 127 * 
     weights   s_w[c] = absmax_c / 127 (1 for an all-zero channel), q = clamp(rint(w / s_w[c]))       raw weights, BN in the epilogue
     epilogue  v = (float)acc * sc[c] + sh[c];  v = max(v, 0.1f v) when leaky;  v = (float)r * s_res + v with a shortcut;
               q = clamp(rintf(v * (1.0f / s_out)));   sc[c] = (s_in * s_w[c]) * bn_scale[c];  an fp32 output stores v
+    aux ops   (Net.set_pools_i8) a max-pool, an up-sample or a concat whose every source lies behind the cut selects or moves stored bytes:
+              destination and sources carry one scale (scale_classes), the pool compares the bytes as signed values
 """
 from __future__ import annotations
 
@@ -15,7 +17,8 @@ from typing import Callable, Dict, Optional
 
 import numpy as np
 
-from .graph import ConvOp, Program
+from .graph import AuxOp, ConvOp, Program
+from .maxpool import maxpool2x2_ref
 from .weights import BN_EPS
 
 F32 = np.float32
@@ -106,15 +109,65 @@ def conv_i8(o: ConvOp, weights: Dict[str, np.ndarray], tensor_q: Callable[[int],
     return np.clip(np.rint(v * inv), -127.0, 127.0).astype(np.int8)
 
 
+def i8_aux_ops(p: Program, cut: int):
+    """Which aux ops an int8 plan with Net.set_pools_i8 runs on int8 tensors (y3_net_plan's rule): a tensor is behind the cut when a conv
+    from slot `cut` on or an int8 aux op writes it; walking the aux ops in op order, a max-pool, an up-sample or a concat runs in int8 when
+    every source it has is behind the cut, and as in an fp16 plan when none is.  -> (the AuxOp objects that run in int8, in op order; the
+    set of tensor ids behind the cut).  ValueError for what the plan refuses: a concat with one source on each side, an add behind the cut."""
+    behind = {o.dst for o in p.conv_ops()[cut:]}
+    chosen = []
+    for o in p.ops:
+        if not isinstance(o, AuxOp):
+            continue
+        n = sum(t in behind for t in o.inputs)
+        if n == 0:
+            continue
+        if o.kind == "add":
+            raise ValueError(f"a stand-alone add ({o.inputs} -> {o.dst}) behind the int8 cut has no int8 form")
+        if n < len(o.inputs):
+            raise ValueError(f"{o.kind} ({o.inputs} -> {o.dst}) has one source behind the int8 cut and one before it")
+        chosen.append(o)
+        behind.add(o.dst)
+    return chosen, behind
+
+
+def crossing_tensors(p: Program, cut: int):
+    """The tensors not behind the cut that an int8 conv reads (sorted): each gets an int8 copy, quantize(x, scale)."""
+    convs = p.conv_ops()
+    _, behind = i8_aux_ops(p, cut)
+    return sorted({t for o in convs[cut:] for t in (o.src0, o.src1, o.residual) if t >= 0 and t not in behind})
+
+
+def aux_i8(o: AuxOp, tensor_q: Callable[[int], np.ndarray], scales) -> np.ndarray:
+    """One int8 aux launch from its own int8 inputs: the max-pool on signed bytes, the up-sample and the concat as moves of bytes."""
+    for t in o.inputs:
+        assert F32(scales[t]) == F32(scales[o.dst]), "an int8 aux op's destination and sources carry one scale"
+    x = tensor_q(o.inputs[0])
+    assert x.dtype == np.int8
+    if o.kind in ("maxpool_s2", "maxpool_s1"):
+        return maxpool2x2_ref(x, 2 if o.kind == "maxpool_s2" else 1)
+    if o.kind == "upsample":
+        return x.repeat(2, axis=1).repeat(2, axis=2)
+    if o.kind == "concat":
+        return np.concatenate([x, tensor_q(o.inputs[1])], axis=3)
+    raise ValueError(o.kind)
+
+
 def forward_i8(p: Program, weights: Dict[str, np.ndarray], scales, boundary: Dict[int, np.ndarray], first_conv: Optional[int] = None,
                eps: float = BN_EPS):
     """The network behind the cut, free-running from the int8 boundary tensors {tensor id: int8 NHWC} (the copies of what crosses the
-    cut).  -> {tensor id: int8 NHWC, or fp32 NHWC for a tensor a launch writes as an fp32 output} of every conv from c* on."""
+    cut): p.ops walked from the cut conv on, the convs and the int8 aux ops (i8_aux_ops).  -> {tensor id: int8 NHWC, or fp32 NHWC for a
+    tensor a launch writes as an fp32 output} of every conv from c* on and every int8 aux op."""
     cut = first_i8_conv(p) if first_conv is None else first_conv
     assert cut >= 0, "no conv of this program qualifies for int8"
     t: Dict[int, np.ndarray] = dict(boundary)
-    for o in p.conv_ops()[cut:]:
-        t[o.dst] = conv_i8(o, weights, t.__getitem__, scales, writes_f32(p, o), eps)
+    in_i8 = {id(o) for o in i8_aux_ops(p, cut)[0]}
+    start = p.ops.index(p.conv_ops()[cut])
+    for o in p.ops[start:]:
+        if isinstance(o, ConvOp):
+            t[o.dst] = conv_i8(o, weights, t.__getitem__, scales, writes_f32(p, o), eps)
+        elif id(o) in in_i8:
+            t[o.dst] = aux_i8(o, t.__getitem__, scales)
     return t
 
 
@@ -125,9 +178,53 @@ def scale_from_absmax(a: float) -> float:
     return float(a / F32(127.0)) if a > 0 and np.isfinite(a) else 1.0
 
 
-def equalize_concat(p: Program, scales):
-    """The two sources of every concat conv take the larger of their scales (repeated until nothing changes: a tensor may feed two)."""
+def scale_classes(p: Program, cut: Optional[int] = None):
+    """The sets of tensors that must carry one scale in an int8 plan with Net.set_pools_i8: the destination and every source of an int8
+    aux op (i8_aux_ops), and the two sources of every concat conv, merged where they share a tensor.  -> a list of sorted lists, classes
+    of one tensor left out, ordered by their first member."""
+    cut = first_i8_conv(p) if cut is None else cut
+    parent = list(range(len(p.tensors)))
+
+    def find(a):
+        while parent[a] != a:
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        return a
+
+    def tie(a, b):
+        a, b = find(a), find(b)
+        if a != b:
+            parent[max(a, b)] = min(a, b)
+
+    for o in p.conv_ops():
+        if o.src1 >= 0:
+            tie(o.src0, o.src1)
+    if cut >= 0:
+        for o in i8_aux_ops(p, cut)[0]:
+            for t in o.inputs:
+                tie(t, o.dst)
+    groups: Dict[int, list] = {}
+    for t in range(len(p.tensors)):
+        groups.setdefault(find(t), []).append(t)
+    return [g for _, g in sorted(groups.items()) if len(g) > 1]
+
+
+def equalize_concat(p: Program, scales, classes: Optional[bool] = None):
+    """The two sources of every concat conv take the larger of their scales (repeated until nothing changes: a tensor may feed two).
+    classes (None: whenever the program has int8 aux ops behind its cut, a pooled net; Net.calibrate_i8 passes its set_pools_i8 switch):
+    every class of scale_classes takes the largest scale of its members instead, unset members (<= 0 or None) included once any member
+    has one."""
     s = list(scales)
+    cut = first_i8_conv(p)
+    if classes is None:
+        classes = cut >= 0 and bool(i8_aux_ops(p, cut)[0])
+    if classes and cut >= 0:
+        for g in scale_classes(p, cut):
+            m = max((s[t] or 0.0) for t in g)
+            if m > 0:
+                for t in g:
+                    s[t] = m
+        return s
     changed = True
     while changed:
         changed = False
